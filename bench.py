@@ -11,7 +11,9 @@ by contiguous index blocks, one process per GPU, no data-path collective (weak s
 group (RCCL) is used for the barriers around the timed region, the max-over-ranks of the elapsed time
 and a final all-gather of per-shard solution checksums.
 
-Prints ONE JSON line on rank 0 (contract in the task statement) with `roofline` and `cpu_baseline`.
+Prints ONE JSON line on rank 0 (contract in the task statement) with `roofline`.  A plain run does only what that line's headline
+figure needs: setup, warm-up, the timed steps (and the --dump-outputs files).  --full adds `cpu_baseline`, the side measurements
+(`factor_kept`, `config1_large`, `config4_lsi`) and, at N > 1, the scatter / gather of problem blocks.
 """
 import argparse
 import datetime
@@ -40,7 +42,12 @@ def main():
     ap.add_argument("--batch", type=int, default=PER_GPU_BATCH, help="problems per GPU")
     ap.add_argument("--keep-factor", action="store_true", help="also write the factor to HBM (40,360 B/problem variant)")
     ap.add_argument("--resident-batches", type=int, default=4, help="distinct batches resident in HBM that the steps rotate through")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure and check what the headline figure does not need: the CPU baseline, the side measurements (factor kept, "
+                         "configs[1], configs[4]) and, at N > 1, the scatter / gather of problem blocks; a plain run does setup, warm-up and the timed steps only")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="after the timed steps, write what the timed path returned in its last step to DIR/<name>.npy (float64, "
+                                                          "at most 64 MB in all: a fixed, seeded sample of the problems beyond that)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
     ap.add_argument("--overlapped", action="store_true", help="N=1: also time two half batches on two streams (extra field, never `value`); off by default so that\n                    the default command launches the bench kernel only as the timed step does (profiles/ hold rocprofv3 summaries of it)")
     ap.add_argument("--dist-backend", default="nccl", choices=["nccl", "gloo"],
                     help="nccl (= RCCL, the real thing); gloo only to rehearse the multi-rank control flow on a box with fewer GPUs than ranks")
@@ -49,7 +56,7 @@ def main():
                     help="lse (default): the headline metric, BASELINE configs[2]/[3]; lsi: configs[4], a lock-step batch of 1024 LexLSI instances "
                          "warm-started to ~30 factorizations each, instance blocks sharded over the ranks (strong scaling)")
     ap.add_argument("--lsi-batch", type=int, default=1024, help="--workload lsi: instances in the whole job")
-    ap.add_argument("--no-extras", action="store_true", help="N=1: skip the config1_large / config4_lsi / factor_kept side measurements (profiling runs)")
+    ap.add_argument("--no-extras", action="store_true", help="with --full, N=1: skip the config1_large / config4_lsi / factor_kept side measurements (profiling runs)")
     ap.add_argument("--dry-run", action="store_true", help="control flow only (launcher, process group, barriers, max-over-ranks, rank-0 line): no GPU, no kernels; "
                                                             "what the non-GPU test of the self-launcher runs with --dist-backend gloo")
     args = ap.parse_args()
@@ -133,6 +140,11 @@ def main():
         barrier()
         elapsed = time.perf_counter() - t0
     kernel_ms = ev0.elapsed_time(ev1) / args.steps  # HIP events on the launch stream: average launch duration
+    if args.dump_outputs:  # the last timed step's results (resident batch (steps - 1) % nres), before the guard below may re-run batch 0
+        out = {"x": solver.get_x(), "ranks": solver.getRanks()[0], "column_permutations": solver.get_column_permutations()}
+        if args.keep_factor:
+            out.update(factor=solver.get_lexqr(), hh_scalars=solver.get_hh_scalars())
+        dump_outputs(args.dump_outputs, out, rank, world)
     if (args.steps - 1) % nres != 0:  # leave the solutions of batch 0 behind for the guard and the scatter/gather check below
         with torch.cuda.stream(stream):
             step(0)
@@ -191,7 +203,7 @@ def main():
     #      itself, the solutions are gathered on rank 0.  Reported separately; never part of `value`.  A failure here is
     #      reported, it does not take the benchmark down.
     scatter_gather = None
-    if world > 1 and not os.environ.get("LEXLS_BENCH_SKIP_SCATTER"):
+    if world > 1 and args.full and not os.environ.get("LEXLS_BENCH_SKIP_SCATTER"):
         try:
             from lexls_amd import sharding
             cdev = torch.device("cuda", device_index) if args.dist_backend == "nccl" else torch.device("cpu")
@@ -265,7 +277,7 @@ def main():
                               "flops_per_problem": flops_per, "flops_executed_per_problem": executed,
                               "frac_on_flops_executed": executed * batch / (kernel_ms * 1e-3) / 1e12 / FP64_VECTOR_PEAK_TFLOPS},
         }
-        if world == 1 and not args.no_extras and not args.keep_factor:
+        if world == 1 and args.full and not args.no_extras and not args.keep_factor:
             line["factor_kept"] = side_factor_kept(solver, stream, ptrs, nres, batch, torch)
             line["config1_large"] = side_config1_large(device_index, not args.no_cpu_baseline)
             line["config4_lsi"] = side_config4_lsi(device_index, not args.no_cpu_baseline)
@@ -275,7 +287,7 @@ def main():
             line["scatter_gather_ok"] = bool("error" not in scatter_gather and scatter_gather.get("blocks_verified"))
         if world == 1 and overlapped is not None:
             line["overlapped"] = overlapped
-        if world == 1 and not args.no_cpu_baseline:
+        if world == 1 and args.full and not args.no_cpu_baseline:
             line["cpu_baseline"] = cpu_baseline(lod_host, args.cpu_seconds)
         print(json.dumps(line), flush=True)
 
@@ -311,6 +323,8 @@ def bench_lsi(args, world, rank, device_index, coll_device, torch, dist):
         r = srv.run(pert, active_guess=guess, x0=cold["x"])
     barrier()
     elapsed = time.perf_counter() - t0
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, {"x": r["x"], "v": r["v"], "active": r["active"]}, rank, world)
     f = np.array([i["factorizations"] for i in r["info"]], np.float64)
     solved = sum(i["status"] == 0 for i in r["info"])
     t = torch.tensor([elapsed, f.sum(), float(solved), float(f.max())], dtype=torch.float64, device=coll_device)
@@ -331,7 +345,7 @@ def bench_lsi(args, world, rank, device_index, coll_device, torch, dist):
         rate = fsum * args.steps / elapsed
         extra["roofline"] = {"bound": "fp64", "achieved": rate * flops / 1e12, "peak": FP64_VECTOR_PEAK_TFLOPS, "unit": "TFLOP/s", "frac": rate * flops / 1e12 / FP64_VECTOR_PEAK_TFLOPS,
                              "traffic": None, "note": "flops of a full 60 x 41 problem per factorization (upper bound); the path is a latency chain per instance (DESIGN.md 3.5)"}
-        if world == 1 and not args.no_cpu_baseline:
+        if world == 1 and args.full and not args.no_cpu_baseline:
             from oracle import oracle_ctypes as oc
             share = host_cpu_share()
             cores = max(1, int(round(share["effective_cores"])))
@@ -574,6 +588,27 @@ def side_config4_lsi(device_index, with_cpu, total=1024):
         return out
     except Exception as exc:  # noqa: BLE001
         return {"error": f"{type(exc).__name__}: {exc}"}
+
+
+DUMP_BYTES = 64_000_000  # --dump-outputs: all ranks' files together
+
+
+def dump_outputs(out_dir, arrays, rank, world):
+    """--dump-outputs: one float64 .npy per result array (leading axis = problem of this rank's batch; at N > 1 every rank writes its shard,
+    suffixed _rank<r>).  Beyond this rank's share of DUMP_BYTES, the same seeded sample of problems is taken from every array and its
+    indices are written as problem_index."""
+    arrays = {k: np.asarray(a, np.float64) for k, a in arrays.items()}
+    batch = len(next(iter(arrays.values())))
+    row_bytes = sum(a[0].nbytes for a in arrays.values())
+    keep = (DUMP_BYTES // world - 4096) // (row_bytes + 8)  # (4096: the .npy headers)
+    if keep < batch:
+        idx = np.sort(np.random.default_rng(SEED0).choice(batch, keep, replace=False))
+        arrays = {k: a[idx] for k, a in arrays.items()}
+        arrays["problem_index"] = idx.astype(np.float64)
+    os.makedirs(out_dir, exist_ok=True)
+    suffix = f"_rank{rank}" if world > 1 else ""
+    for k, a in arrays.items():
+        np.save(os.path.join(out_dir, f"{k}{suffix}.npy"), a)
 
 
 def _committed_traffic(keep_factor):

@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""Distils the rocprofv3 CSVs of profiles/collect_r03.sh (under gpurun_out/) into the committed summaries:
+"""Distils the rocprofv3 CSVs of profiles/collect_r03.sh (under profile_out/, or $PROFILE_OUT) into the committed summaries:
 profiles/<tag>_kernel_stats.csv, <tag>_summary.md, <tag>_bench.json and the `x_only` entry of pmc_summary.json (read by bench.py).
 
 HBM traffic (MI355X_MICROARCH.md, section HBM): FETCH_SIZE and WRITE_SIZE come from separate passes, in KB.  gfx950 tallies a
@@ -30,7 +30,7 @@ def counters(path, ksub):
 
 def main():
     tag, ksub = sys.argv[1], sys.argv[2]
-    g = os.path.join(ROOT, "gpurun_out")
+    g = os.environ.get("PROFILE_OUT", os.path.join(ROOT, "profile_out"))
     stats_src = os.path.join(g, f"prof_stats_{tag}", "stats_kernel_stats.csv")
     shutil.copy(stats_src, os.path.join(ROOT, "profiles", f"{tag}_kernel_stats.csv"))
     st = rows(stats_src)

@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""Distils the rocprofv3 CSVs of profiles/collect_r04.sh (under gpurun_out/) into the committed summaries of round 4:
+"""Distils the rocprofv3 CSVs of profiles/collect_r04.sh (under profile_out/, or $PROFILE_OUT) into the committed summaries of round 4:
 profiles/r04_kernel_stats.csv (bench.py's default command: lqr_qtol), r04m_kernel_stats.csv (the same command on the matrix-core kernel lqr_mfma,
 LEXLS_KERNEL_POLICY=7), r04_large / r04_lsi kernel stats, r04_summary.md, r04_bench*.json and the `x_only` / `x_only_mfma` entries of
 pmc_summary.json (bench.py reads `x_only` for roofline.traffic).
@@ -14,7 +14,7 @@ import re
 import shutil
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-G = os.path.join(ROOT, "gpurun_out")
+G = os.environ.get("PROFILE_OUT", os.path.join(ROOT, "profile_out"))
 
 
 def rows(path):
