@@ -47,7 +47,9 @@ enum lexls_array
     LEXLS_ARRAY_TOTAL_RANK, /* uint32   batch                   TotalRank                             */
     LEXLS_ARRAY_V,          /* double   batch x cap             residuals (get_v)                     */
     LEXLS_ARRAY_LAMBDA,     /* double   batch x (nVar+cap)      [lambda_fixed; lambda] of the last sensitivity call */
-    LEXLS_ARRAY_INPUT       /* double   batch x cap x (nVar+1)  library-owned input buffer            */
+    LEXLS_ARRAY_INPUT,      /* double   batch x cap x (nVar+1)  library-owned input buffer            */
+    LEXLS_ARRAY_GUARD_ESTIMATE, /* double batch                 accuracy guard: estimate of the last solve (lexls_lse_set_accuracy_guard) */
+    LEXLS_ARRAY_GUARD_STATUS    /* uint8  batch                 accuracy guard: status of the last solve                                  */
 };
 
 /* replaces LexLS::Exception::what() (typedefs.h:300-314): no exception crosses the ABI — every entry point returns a status code and
@@ -220,8 +222,28 @@ const char *lexls_lse_last_kernel(lexls_lse_t h);
  *       shape only).  Automatic dispatch (0) takes lqr_qtol first — the faster one on MI355X (41 us against 57 us per 4096 IK problems) — and
  *       lqr_mfma for the shapes lqr_qtol's slices do not hold.
  *   Policy 0 is therefore NOT bit-exact for those x-only solves; a caller that needs (B) everywhere sets policy 5 (per handle) or runs under
- *   LEXLS_QTOL=0 (whole process; read at every factorization, so it may be changed between solves). */
+ *   LEXLS_QTOL=0 (whole process; read at every factorization, so it may be changed between solves) — or switches the accuracy guard on below.
+ *   ACCURACY GUARD (lexls_lse_set_accuracy_guard, off by default).  With the guard on, a solve that would run on lqr_qtol (policies 0 and 6) runs on
+ *   its estimating instantiation, which also writes per problem an estimate of how far it can vouch for its (T) answer: the maximum over the
+ *   pivots of |pivot column in its level's raw rows| / |R_jj| (cancellation in the factorization).  A solve that would run on another (T) kernel
+ *   (lqr_mfma: policy 0 for shapes lqr_qtol does not hold, policies 7 / 8 / 9; the step-per-pivot large path) takes the bit-exact kernel for the
+ *   shape instead.  CONTRACT of mode 2: every problem is either solved under (B), or under (T) with an estimate below the threshold — a flagged
+ *   problem is re-solved in the same stream by the bit-exact four-per-wavefront kernel (the one policy 4 takes), so its x, ranks, first columns
+ *   and permutation are bit-identical to the oracle.  Mode 1 only reports.  The default threshold (64) separates, with about five times room
+ *   either way, well-conditioned IK problems (estimates up to 13) from every problem whose x moves by more than 1e-11 under one-ulp changes of its
+ *   data on the calibration sets (estimates from 421 on: scripts/calibrate_guard.py); it flags every badly scaled problem too. */
 int lexls_lse_set_kernel_policy(lexls_lse_t h, int policy);
+
+/* mode 0: off (default, today's behaviour). 1: report only. 2: report + re-solve flagged problems under (B).
+ * threshold <= 0: the calibrated default.  Takes effect at the next factorization; the guard never syncs the stream nor copies to the host
+ * inside a solve (deferred sync keeps working). */
+int lexls_lse_set_accuracy_guard(lexls_lse_t h, int mode, double threshold);
+/* per problem: estimate (double) and status (uint8): 0 solved under (B) by the kernel chosen,
+ * 1 (T) and estimate below the threshold, 2 (T) flagged and not re-solved (mode 1),
+ * 3 flagged and re-solved under (B) (mode 2).  *h_flagged = number of problems with status 2 or 3. Any pointer may be NULL.
+ * Describes the last factorization; all zeros when it ran with the guard off.  Waits for the handle's stream (also under deferred sync).
+ * Status 0 problems report estimate 0. */
+int lexls_lse_get_accuracy(lexls_lse_t h, double *h_estimate, uint8_t *h_status, uint32_t *h_flagged);
 
 /* ---- prefix reuse ------------------------------------------------------------------------------
  * The reference refactorizes the whole hierarchy in every LexLSI iteration although one row of one level changed (README.md:14 "No update

@@ -25,11 +25,12 @@ SYMBOLS = [
     "lexls_lse_get_x", "lexls_lse_get_factor", "lexls_lse_get_hh_scalars", "lexls_lse_get_permutation", "lexls_lse_get_ranks",
     "lexls_lse_get_v", "lexls_lse_get_mu", "lexls_lse_get_lambda", "lexls_lse_get_sensitivity", "lexls_lse_get_ctr_type",
     "lexls_lse_device_ptr", "lexls_lse_last_kernel", "lexls_lse_set_kernel_policy",
+    "lexls_lse_set_accuracy_guard", "lexls_lse_get_accuracy",
     "lexls_lse_set_prefix_reuse", "lexls_lse_prefix_reuse_ready", "lexls_lse_set_resume_levels",
     "lexls_lsi_solve", "lexls_lsi_solve_dat", "lexls_lsi_batch_solve",
 ]
 
-ARRAY = dict(x=0, factor=1, hh=2, perm=3, rank=4, first_col=5, total_rank=6, v=7, lam=8, input=9)
+ARRAY = dict(x=0, factor=1, hh=2, perm=3, rank=4, first_col=5, total_rank=6, v=7, lam=8, input=9, guard_estimate=10, guard_status=11)
 
 _lib = None
 
@@ -49,6 +50,10 @@ def lib() -> C.CDLL:
         _lib.lexls_last_error.restype = C.c_char_p
         _lib.lexls_lse_last_kernel.restype = C.c_char_p
         _lib.lexls_lse_last_kernel.argtypes = [C.c_void_p]
+        _lib.lexls_lse_set_accuracy_guard.restype = C.c_int
+        _lib.lexls_lse_set_accuracy_guard.argtypes = [C.c_void_p, C.c_int, C.c_double]
+        _lib.lexls_lse_get_accuracy.restype = C.c_int
+        _lib.lexls_lse_get_accuracy.argtypes = [C.c_void_p, C.POINTER(C.c_double), C.POINTER(C.c_uint8), C.POINTER(C.c_uint32)]
     return _lib
 
 

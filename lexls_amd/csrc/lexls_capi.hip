@@ -78,6 +78,13 @@ struct lexls_lse_s
     double reg_variable;
     double *d_reg_factor, *d_reg_scratch, *d_reg_mu;
     bool sens_scan; // lexls_lse_set_sensitivity_scan
+    // accuracy guard (lexls_lse_set_accuracy_guard): mode 0 off, 1 report, 2 report + re-solve; arrays allocated when first switched on
+    int guard_mode           = 0;
+    double guard_threshold   = 0.0;
+    double *d_guard_est      = nullptr; // batch
+    uint8_t *d_guard_status  = nullptr; // batch
+    uint32_t *d_guard_ind    = nullptr; // 1 + batch: [count, flagged problems]
+    bool guard_last          = false;   // the last factorization ran with the guard on (the arrays describe it)
     char *d_round_in, *d_round_out; // the per-round arrays live in two slabs (lexls_lse_round_layout): one copy each way per round
     lexls_round_layout lay;
 
@@ -264,7 +271,8 @@ extern "C"
         if (!h) return LEXLS_OK;
         (void)hipSetDevice(h->device);
         void *ptrs[] = {h->d_in_owned, h->d_fac, h->d_hh, h->d_v, h->d_lambda, h->d_scratch, h->d_perm, h->d_rank, h->d_fcol, h->d_round_in, h->d_round_out,
-                        h->d_large_state, h->d_large_ws, h->d_norms, h->d_cdata, h->d_reg_factor, h->d_reg_scratch, h->d_reg_mu, h->d_resume_level, h->d_resume_state};
+                        h->d_large_state, h->d_large_ws, h->d_norms, h->d_cdata, h->d_reg_factor, h->d_reg_scratch, h->d_reg_mu, h->d_resume_level, h->d_resume_state,
+                        h->d_guard_est, h->d_guard_status, h->d_guard_ind};
         for (void *p : ptrs)
             if (p) (void)hipFree(p);
         if (h->h_dims_pinned) (void)hipHostFree(h->h_dims_pinned);
@@ -759,6 +767,11 @@ extern "C"
         return (e && std::atoi(e) == 0) ? 0 : 1;
     }
 
+    /// Default threshold of the accuracy guard's estimate (max over pivots of |raw pivot column| / |R_jj|), calibrated by
+    /// scripts/calibrate_guard.py ("Accuracy guard"): the largest estimate of 4096 well-conditioned IK problems is 13.1, the
+    /// smallest of a problem whose x moves by more than 1e-11 under one-ulp changes of its data 421 — about five times either way
+    static constexpr double kGuardDefaultThreshold = 64.0;
+
     /// opportunistic_solve: the caller only asked for the factor; kernels that produce x on the way at no extra launch do (the wave kernels
     /// always, the generic kernel on request), so that a later lexls_lse_solve of the same factor has nothing left to do
     static int run_lqr(lexls_lse_t h, bool write_factor, bool do_solve, bool opportunistic_solve = false)
@@ -770,23 +783,29 @@ extern "C"
         const char *variant = "";
         const LseArgs a     = h->args();
         const bool shape_kernels = h->force_generic != 1;
+        // accuracy guard: lqr_qtol runs as its estimating instantiation; every other tolerance-contract kernel gives way to the bit-exact one
+        const bool guard = h->guard_mode != 0;
+        int tolerance    = tolerance_mode(h);
+        if (guard && tolerance != 0) tolerance = (tolerance == 1 || tolerance == 6) ? 6 : 0;
+        const GuardArrays guard_arrays{h->d_guard_est, h->d_guard_status, h->d_guard_ind};
+        const GuardArrays *gp = guard ? &guard_arrays : nullptr;
         // (the regularization family lives in the register-resident wave kernel's REG instantiations and in the generic kernel)
         if (shape_kernels && wave_kernel_supports(a, h->max_rows, h->max_level_dim, h->has_fixed))
         {
             const int ll = h->fused_gather ? -1 : (h->force_generic == 2 ? -1 : (h->force_generic == 3 ? 1 : (h->force_generic == 4 ? 2 : 0)));
             // the tolerance-contract kernel (lqr_qtol_impl.h): automatic dispatch and policy 6; LEXLS_QTOL=0 keeps every solve bit-exact
-            HIP_TRY(launch_lqr_wave(a, h->max_level_dim, write_factor, h->has_fixed, ll, h->stream, &variant, tolerance_mode(h))); // always solves as well
+            HIP_TRY(launch_lqr_wave(a, h->max_level_dim, write_factor, h->has_fixed, ll, h->stream, &variant, tolerance, gp)); // always solves as well
         }
         else if (shape_kernels && h->force_generic != 2 && h->max_rows > 64 && h->max_level_dim <= 16 && a.nObj <= 16 &&
                  deep_kernel_supports(a, h->max_level_dim, write_factor, h->has_fixed))
         {
             // deep hierarchies (more than 64 rows in all): the left-looking kernels, whose LDS holds pivot rows only (x-only solves of the IK
             // shape: the tolerance-contract kernel under the same rules as above — it reads a level's rows when the level starts, too)
-            HIP_TRY(launch_lqr_wave(a, h->max_level_dim, write_factor, h->has_fixed, 2, h->stream, &variant, tolerance_mode(h)));
+            HIP_TRY(launch_lqr_wave(a, h->max_level_dim, write_factor, h->has_fixed, 2, h->stream, &variant, tolerance, gp));
         }
         else if (shape_kernels && h->reg_type == 0 && !generic_fits_lds(a, h->max_rows) && large_kernel_supports(a, h->max_level_dim, h->has_fixed))
         {
-            if (h->force_generic == 5) // the bit-exact multi-launch path (ordered chains: parity tests, reference for the fast path)
+            if (h->force_generic == 5 || guard) // the bit-exact multi-launch path (ordered chains: parity tests, reference for the fast path)
             {
                 if (!h->d_large_state) HIP_TRY(hipMalloc(&h->d_large_state, large_state_bytes(h->batch)));
                 if (!h->d_norms) HIP_TRY(hipMalloc((void **)&h->d_norms, 8 * (size_t)h->batch * h->nVar));
@@ -808,7 +827,7 @@ extern "C"
                 HIP_TRY(launch_lqr_large_fast(a, h->level_max.data(), h->max_rows, h->d_large_ws, h->stream));
                 variant = "lqr_large<step-per-pivot,mfma>";
             }
-            if (do_solve) HIP_TRY(launch_solve_generic(a, h->stream, h->force_generic != 5)); // (the step-per-pivot path's contract allows reciprocals)
+            if (do_solve) HIP_TRY(launch_solve_generic(a, h->stream, h->force_generic != 5 && !guard)); // (the step-per-pivot path's contract allows reciprocals)
             solved       = do_solve;
             write_factor = true;
         }
@@ -816,6 +835,20 @@ extern "C"
         {
             solved = do_solve || opportunistic_solve;
             HIP_TRY(launch_lqr_generic(a, h->max_rows, write_factor, solved, h->stream, &variant));
+        }
+        h->guard_last = guard;
+        if (guard)
+        {
+            if (std::strstr(variant, ",guard>")) // flags -> status (and the list), then the bit-exact re-solve of the flagged problems: all in the stream
+            {
+                HIP_TRY(launch_guard_compact(h->d_guard_est, h->d_guard_status, h->d_guard_ind, h->batch, h->guard_threshold, h->guard_mode, h->stream));
+                if (h->guard_mode == 2) HIP_TRY(launch_quad_resolve(a, h->max_level_dim, h->d_guard_ind, h->stream));
+            }
+            else // a bit-exact kernel solved: status 0, no estimate
+            {
+                HIP_TRY(hipMemsetAsync(h->d_guard_est, 0, 8 * (size_t)h->batch, h->stream));
+                HIP_TRY(hipMemsetAsync(h->d_guard_status, 0, (size_t)h->batch, h->stream));
+            }
         }
         // prefix reuse: the levels handed over are consumed; the state is there for the next factorization iff this one was the register-resident
         // wave kernel keeping its factor (every other kernel ignores both pointers and factorizes everything)
@@ -996,6 +1029,11 @@ extern "C"
         case LEXLS_ARRAY_TOTAL_RANK: *d_ptr = h->d_totalrank; break;
         case LEXLS_ARRAY_V: *d_ptr = h->d_v; break;
         case LEXLS_ARRAY_LAMBDA: *d_ptr = h->d_lambda; break;
+        case LEXLS_ARRAY_GUARD_ESTIMATE:
+        case LEXLS_ARRAY_GUARD_STATUS:
+            if (!h->d_guard_est) return fail(LEXLS_ERR_INVALID, "lexls_lse_device_ptr: the accuracy guard has not been switched on (lexls_lse_set_accuracy_guard)");
+            *d_ptr = which == LEXLS_ARRAY_GUARD_ESTIMATE ? (void *)h->d_guard_est : (void *)h->d_guard_status;
+            break;
         case LEXLS_ARRAY_INPUT:
             if (!h->d_in_owned)
             {
@@ -1012,6 +1050,57 @@ extern "C"
     }
 
     const char *lexls_lse_last_kernel(lexls_lse_t h) { return h ? h->last_kernel : ""; }
+
+    int lexls_lse_set_accuracy_guard(lexls_lse_t h, int mode, double threshold)
+    {
+        CHECK_HANDLE(h);
+        if (mode < 0 || mode > 2) return fail(LEXLS_ERR_INVALID, "lexls_lse_set_accuracy_guard: mode must be 0, 1 or 2");
+        if (mode != 0 && !h->d_guard_est)
+        {
+            HIP_TRY(hipSetDevice(h->device));
+            HIP_TRY(hipMalloc((void **)&h->d_guard_est, 8 * (size_t)h->batch));
+            HIP_TRY(hipMalloc((void **)&h->d_guard_status, (size_t)h->batch));
+            HIP_TRY(hipMalloc((void **)&h->d_guard_ind, 4 * (1 + (size_t)h->batch)));
+            HIP_TRY(hipMemsetAsync(h->d_guard_est, 0, 8 * (size_t)h->batch, h->stream));
+            HIP_TRY(hipMemsetAsync(h->d_guard_status, 0, (size_t)h->batch, h->stream));
+            HIP_TRY(hipMemsetAsync(h->d_guard_ind, 0, 4 * (1 + (size_t)h->batch), h->stream));
+            if (!h->deferred_sync) HIP_TRY(hipStreamSynchronize(h->stream));
+        }
+        h->guard_mode      = mode;
+        h->guard_threshold = threshold > 0.0 ? threshold : kGuardDefaultThreshold; // (NaN: the default as well)
+        return LEXLS_OK;
+    }
+
+    int lexls_lse_get_accuracy(lexls_lse_t h, double *h_estimate, uint8_t *h_status, uint32_t *h_flagged)
+    {
+        CHECK_HANDLE(h);
+        const size_t B = h->batch;
+        if (!h->d_guard_est || !h->guard_last) // the last solve ran without the guard: nothing to report
+        {
+            if (h_estimate) std::memset(h_estimate, 0, 8 * B);
+            if (h_status) std::memset(h_status, 0, B);
+            if (h_flagged) *h_flagged = 0;
+            return LEXLS_OK;
+        }
+        HIP_TRY(hipSetDevice(h->device));
+        std::vector<uint8_t> own;
+        uint8_t *st = h_status;
+        if (!st && h_flagged)
+        {
+            own.resize(B);
+            st = own.data();
+        }
+        if (h_estimate) HIP_TRY(hipMemcpyAsync(h_estimate, h->d_guard_est, 8 * B, hipMemcpyDeviceToHost, h->stream));
+        if (st) HIP_TRY(hipMemcpyAsync(st, h->d_guard_status, B, hipMemcpyDeviceToHost, h->stream));
+        HIP_TRY(hipStreamSynchronize(h->stream)); // (also under deferred sync: the count is made on the host)
+        if (h_flagged)
+        {
+            uint32_t c = 0;
+            for (size_t b = 0; b < B; b++) c += st[b] >= 2 ? 1u : 0u;
+            *h_flagged = c;
+        }
+        return LEXLS_OK;
+    }
 
     int lexls_lse_set_prefix_reuse(lexls_lse_t h, int enable)
     {

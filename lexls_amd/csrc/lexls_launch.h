@@ -30,8 +30,23 @@ namespace lexls
     /// tolerance: x-only solves of the shapes lqr_mfma_impl.h / lqr_qtol_impl.h serve may take those kernels (pivots / ranks exact, x within 1e-10
     /// instead of bit-identical to the oracle).  0 = bit-exact kernels only; 1 = automatic (lqr_mfma where it serves, else lqr_qtol); 6 = lqr_qtol
     /// only; 7 / 8 = lqr_mfma with two / one problem per wavefront, else lqr_qtol
+    /// guard (NULL: off): the accuracy guard's device arrays (lexls_lse_set_accuracy_guard).  With a guard, lqr_qtol runs as its estimating
+    /// instantiation (est: batch doubles; ind[0], the compaction counter, is cleared) and *variant names it with ",guard"
+    struct GuardArrays
+    {
+        double *est;   // batch: the estimate
+        uint8_t *status; // batch
+        uint32_t *ind; // 1 + batch: [count, problems flagged for the re-solve]
+    };
     hipError_t launch_lqr_wave(const LseArgs &a, uint32_t max_level_dim, bool write_factor, bool has_fixed, int left_looking, hipStream_t s,
-                               const char **variant, int tolerance = 0);
+                               const char **variant, int tolerance = 0, const GuardArrays *guard = nullptr);
+    /// the guard's re-solve (mode 2): the bit-exact x-only four-per-wavefront instantiation policy 4 takes for these arguments, in its indirect
+    /// form over ind = [count, list]; hipErrorNotSupported where policy 4 would take no four-per-wavefront kernel
+    hipError_t launch_quad_resolve(const LseArgs &a, uint32_t max_level_dim, const uint32_t *ind, hipStream_t s);
+
+    // lexls_guard.hip — the accuracy guard's compaction: status[b] from est[b] against the threshold (1 below it; 2 flagged, mode 1; 3 flagged,
+    // mode 2) and, in mode 2, ind = [count, flagged problems] (ind[0] cleared by the estimating kernel in front of it in the stream)
+    hipError_t launch_guard_compact(const double *est, uint8_t *status, uint32_t *ind, uint32_t batch, double threshold, int mode, hipStream_t s);
 
     /// The resident active-set iterations of a lock-step LexLSI batch as one persistent launch (lsi_fused_impl.h): l-QR (the register-resident wave
     /// kernel's body, rows gathered by reference) -> removal sweep -> iteration, per instance until it stops or `count` iterations are done.

@@ -1,0 +1,695 @@
+// Body of lqr_qtol_kernel / lqr_qtol_est_kernel (lqr_qtol_impl.h), included inside both: template parameters NS, MD, SIG, NV; arguments a,
+// img_doubles, group_bytes, stagger; EST (constexpr bool), est_out, count_reset.
+            static_assert(NS >= 1 && NS <= 4 && MD <= 16 && (MD % 4) == 0, "shape limits of the row layout / two row parts of even size");
+            constexpr int NH  = 2;        // row parts of the staging transposition
+            constexpr int RP  = MD / NH;  // rows per part
+            constexpr int HP  = RP / 2;   // 16-byte pieces per column and part
+            constexpr int kHandoffStride = 8 * MD + 16; // bytes between the lanes' hand-off slots: 16-byte aligned, b128 stores of 8 lanes on 32 banks
+            constexpr int NIH = NS * HP;  // load instructions per part (16 NS columns x HP pieces / 16 lanes)
+#ifndef LEXLS_QTOL_PF_STEPS
+#define LEXLS_QTOL_PF_STEPS 9
+#endif
+            constexpr int PF_STEPS = LEXLS_QTOL_PF_STEPS < MD ? LEXLS_QTOL_PF_STEPS : MD; // pivot steps over which a level's requests are spread
+            extern __shared__ double smem[];
+            // LDS is addressed by 32-bit byte addresses turned into address-space-3 pointers directly (base of the dynamic block folded into the
+            // slice offset once): an access through a generic pointer costs an extra add of the block's base (zero) per access
+            typedef __attribute__((address_space(3))) char lds_char;
+            const int lds0 = (int)(unsigned)(size_t)(lds_char *)smem;
+            const int lane = threadIdx.x & 63;
+            // QT_WPB wavefronts per workgroup (independent of each other; one per SIMD): a quarter of the workgroups to dispatch
+            const uint32_t wq = QT_WPB > 1 ? blockIdx.x * QT_WPB + (uint32_t)__builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6)) : blockIdx.x; // this wavefront's quad of problems (in scalar registers)
+            if (wq * 4u >= a.batch) return; // (a wavefront beyond the batch: nothing of it is waited for)
+            if constexpr (EST)
+            {
+                if (wq == 0 && lane == 0) *count_reset = 0u;
+            }
+            const int g    = lane >> 4; // row = problem inside the wave
+            const int gl   = lane & 15;
+            const int n    = NV ? NV : (int)a.nVar;
+            const int cap  = (int)a.cap;
+            const int nObj = (int)a.nObj;
+            const uint32_t b  = wq * 4u + (uint32_t)g;
+            const uint32_t bb = b < a.batch ? b : a.batch - 1u; // rows beyond the batch idle on a valid address
+            const bool live   = b < a.batch && !(a.skip && a.skip[bb]);
+            const uint32_t pstride = (uint32_t)cap * (uint32_t)(n + 1);
+            const double *inw      = a.in + (size_t)wq * 4u * pstride; // wave-uniform base; lane offsets stay 32-bit
+            const uint32_t poff    = (bb - wq * 4u) * pstride;
+
+            // ---- the first level's rows are requested before anything else (every wave of the chip asks for its first level at once: the HBM serves
+            //      this burst at its full rate, and nothing can be computed before it lands).  Its position layout is the identity, so lane = column
+            //      loads the block directly, no staging; for such a burst this pattern is also the fastest of those measured
+            //      (scripts/ubench/loadpat.hip: 7.7-8.4 k cycles per level against 9.5 k for the 48-byte pieces) ----
+            double blk[NS][MD]; // the level block, position layout
+#pragma unroll
+            for (int s = 0; s < NS; s++)
+            {
+                const int P       = 16 * s + gl - SIG;
+                const int c       = (P >= 0 && P <= n) ? P : 0;
+                const qt_d2 *src2 = reinterpret_cast<const qt_d2 *>(inw + (poff + (uint32_t)(c * cap)));
+#pragma unroll
+                for (int r = 0; r < MD / 2; r++)
+                {
+                    const qt_d2 v     = src2[r];
+                    blk[s][2 * r]     = v.x;
+                    blk[s][2 * r + 1] = v.y;
+                }
+            }
+
+            // ---- LDS carve-up of this row's slice (byte offsets; launch_qtol_t computes group_bytes) ----
+            const int o_img   = lds0 + (int)((QT_WPB > 1 ? (threadIdx.x >> 6) * 4u : 0u) + (uint32_t)g) * (int)group_bytes;
+            const int o_xs    = o_img + 8 * (int)img_doubles; // 16*NS : x by position (zero until the back-substitution: also the "U" of a position that is no pivot yet)
+            const int o_ex    = o_xs + 8 * 16 * NS;           // MD    : dump slots (one dword per lane) of byte stores that do not apply
+            const int o_phys  = o_ex + 8 * MD;                // 64 B  : physical column at each position
+            const int o_perm  = o_phys + 64;                  // 64 B  : column_permutations
+            const int o_meta  = o_perm + 64;                  // kQuadMaxObj x {first column, rank, image offset, image width}
+            const int o_emap  = o_meta + 16 * kQuadMaxObj;    // 16 NS x 8 B: byte k of entry j = column index of PHYSICAL column j in the image of level k
+            const int o_stage = o_emap + 8 * 16 * NS;         // max((n + 1) RP, 16 MD) doubles: staging block of the level loads; 16 hand-off slots of the pivot steps
+            auto D   = [&](int off) -> __attribute__((address_space(3))) double & { return *(__attribute__((address_space(3))) double *)(size_t)(unsigned)off; };
+            auto D2  = [&](int off) -> __attribute__((address_space(3))) qt_d2 & { return *(__attribute__((address_space(3))) qt_d2 *)(size_t)(unsigned)off; };
+            auto B8  = [&](int off) -> __attribute__((address_space(3))) uint8_t & { return *(__attribute__((address_space(3))) uint8_t *)(size_t)(unsigned)off; };
+            auto U32 = [&](int off) -> __attribute__((address_space(3))) uint32_t & { return *(__attribute__((address_space(3))) uint32_t *)(size_t)(unsigned)off; };
+            auto U64 = [&](int off) -> __attribute__((address_space(3))) unsigned long long & { return *(__attribute__((address_space(3))) unsigned long long *)(size_t)(unsigned)off; };
+            typedef unsigned qt_u4 __attribute__((ext_vector_type(4)));
+            auto U4 = [&](int off) -> __attribute__((address_space(3))) qt_u4 & { return *(__attribute__((address_space(3))) qt_u4 *)(size_t)(unsigned)off; };
+
+#pragma unroll
+            for (int s = 0; s < 4; s++) B8(o_phys + 16 * s + gl) = (uint8_t)(16 * s + gl);
+#pragma unroll
+            for (int s = 0; s < NS; s++)
+            {
+                D(o_emap + 8 * (16 * s + gl)) = 0.0;
+                D(o_xs + 8 * (16 * s + gl))   = 0.0;
+            }
+            quad_lds_fence();
+
+            // The four waves of a CU (one per SIMD) start a little apart: every wave of the chip is in the same phase of the same level otherwise,
+            // and each level's rows are asked for by all 1024 waves at once — a burst the HBM serves at its full rate while every SIMD waits
+            if (stagger)
+            {
+                const unsigned simd = __builtin_amdgcn_s_getreg((4 << 0) | (4 << 6) | ((2 - 1) << 11)); // HW_REG_HW_ID, bits [5:4] = SIMD
+                for (unsigned i = 0; i < simd * stagger; i++) __builtin_amdgcn_s_sleep(8);
+            }
+
+            // ---- level loads: pieces of 16 bytes, HP consecutive pieces = RP rows of one column, columns in consecutive lanes ----
+            const int CH = (n + 1) * HP; // pieces per problem, level and row part
+            static_assert(NH * NIH <= 18, "eighteen piece registers");
+            // piece t = (row part t / NIH, instruction t % NIH) of the level whose first row is Frow -> its fixed registers
+            // byte offsets of this lane's pieces inside a level, computed once (the division by HP is not repeated per request)
+            uint32_t pieceoff[NH * NIH];
+            for_each_index<0, NH * NIH>([&](auto tt) __attribute__((always_inline)) {
+                constexpr int t = decltype(tt)::value, h = t / NIH, i = t % NIH;
+                int ch        = 16 * i + gl;
+                ch            = ch < CH ? ch : CH - 1; // lanes past the end repeat the last piece (same bytes to the same LDS address)
+                const int col = ch / HP, m = ch - col * HP;
+                pieceoff[t]   = 8u * (poff + (uint32_t)(col * cap + h * RP + 2 * m)); // bytes
+            });
+            auto prefetch_piece = [&](auto tt, int Frow) __attribute__((always_inline)) {
+                constexpr int t = decltype(tt)::value, i = t % NIH;
+                if (16 * i < CH) // wave-uniform
+                    qt_pf_load<t>(inw + Frow, pieceoff[t]);
+            };
+
+            int rp[NS];         // slot s, lane l: LDS byte address of the (triangular) image row of pivot position c = 16 s + l - SIG
+            int rq[NS];         // slot s, lane l: v_perm selector that picks the byte of pivot position c's LEVEL out of a column's index word
+            unsigned long long em[NS]; // the index word of the column held in slot s
+            int pos[NS];        // current position of the column held in slot s
+            int pc[NS];         // its physical column
+#pragma unroll
+            for (int s = 0; s < NS; s++)
+            {
+                rp[s]  = o_xs; // (a position that is not a pivot yet "reads" zeros of the x block: see the elimination)
+                rq[s]  = 0x0c0c0c00;
+                em[s]  = 0ull;
+                pos[s] = 0;
+                pc[s]  = 0;
+            }
+
+            int ColIndex   = 0; // per row (uniform inside a row), like everything below
+            int TotalRank  = 0;
+            int imgoff     = 0; // doubles
+            bool exh       = false;
+            bool have_next = false; // the pieces of the level about to start are already in flight / in registers (wave-uniform)
+            double est2    = 0.0;   // (EST) this lane's largest |raw column|^2 / (4 R_jj^2) over the pivots it held
+            double rsq[NS];         // (EST) squared norm of the column in slot s over the level's rows as loaded (set at every level start)
+            STAMP_DECL
+            STAMP(0)
+#ifdef LEXLS_QTOL_CHAIN
+            unsigned long long cacc[7] = {0, 0, 0, 0, 0, 0, 0};
+#endif
+#ifdef LEXLS_WAVE_STAMPS
+            unsigned long long lst_t0 = clock64();
+#endif
+
+            for (int k = 0; k < nObj; k++)
+            {
+                const bool work = live && !exh; // x only: once the columns are exhausted nothing below matters
+                const int Fc    = ColIndex;
+                int rank        = 0;
+                if (__ballot(work) == 0ull)
+                {
+                    if (gl == 0)
+                    {
+                        U32(o_meta + 16 * k)      = (uint32_t)Fc;
+                        U32(o_meta + 16 * k + 4)  = 0u;
+                        U32(o_meta + 16 * k + 8)  = (uint32_t)imgoff;
+                        U32(o_meta + 16 * k + 12) = (uint32_t)(n + 1 - Fc);
+                    }
+                    continue;
+                }
+                const int F = k * MD;
+                if (k > 0 && !have_next) // a level whose predecessor could have exhausted the columns: all pieces at once
+                    for_each_index<0, NH * NIH>([&](auto tt) __attribute__((always_inline)) { prefetch_piece(tt, F); });
+
+                // =====================================================================================
+                // position layout of the level; staged pieces -> block
+                // =====================================================================================
+#pragma unroll
+                for (int s = 0; s < NS; s++)
+                {
+                    const int P  = 16 * s + gl - SIG;
+                    const int ph = (int)B8(o_phys + (P >= 0 && P < n ? P : 0)); // (unconditional reads: the three slots' look-ups go out together)
+                    pc[s]        = (P >= 0 && P < n) ? ph : (P == n ? n : 0);
+                    pos[s]       = (P >= 0 && P <= n) ? P : 0x3fffff;
+                }
+#pragma unroll
+                for (int s = 0; s < NS; s++) em[s] = U64(o_emap + 8 * pc[s]);
+                if (k > 0)
+                for_each_index<0, NH>([&](auto hh) __attribute__((always_inline)) {
+                    constexpr int h = decltype(hh)::value;
+                    // the pieces come out of their fixed registers (requested during the level in front, or just now)
+                    if constexpr (h == 0) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+                    for_each_index<0, NIH>([&](auto ii) __attribute__((always_inline)) {
+                        constexpr int i = decltype(ii)::value;
+                        if (16 * i < CH)
+                        {
+                            int ch = 16 * i + gl;
+                            ch     = ch < CH ? ch : CH - 1;
+                            qt_pf_store_lds<h * NIH + i>(o_stage + 16 * ch);
+                        }
+                    });
+                    quad_lds_fence();
+#pragma unroll
+                    for (int s = 0; s < NS; s++)
+                    {
+#pragma unroll
+                        for (int m = 0; m < HP; m++)
+                        {
+                            const qt_d2 v            = D2(o_stage + 16 * (pc[s] * HP + m));
+                            blk[s][h * RP + 2 * m]     = v.x;
+                            blk[s][h * RP + 2 * m + 1] = v.y;
+                        }
+                    }
+                    quad_lds_fence();
+                });
+                STAMP(1)
+                LSTAMP(0)
+                if constexpr (EST)
+                {
+#pragma unroll
+                    for (int s = 0; s < NS; s++)
+                    {
+                        double t = 0.0;
+#pragma unroll
+                        for (int r = 0; r < MD; r++) t = dfma(blk[s][r], blk[s][r], t);
+                        rsq[s] = t;
+                    }
+                }
+                // the next level's rows: requested while this level is factorised (two pieces per pivot step, below), unless this level can
+                // exhaust the columns
+                const bool prefetch = (k + 1 < nObj) && (rows_min(work ? Fc : 0x3fffffff) + MD < n);
+                have_next           = prefetch;
+
+                // =====================================================================================
+                // Gauss elimination of these rows by every finished pivot c' (lexlse.h:431-471, left-looking, normalised pivot rows)
+                // =====================================================================================
+                const int Fcmax = rows_max(work ? Fc : 0);
+                {
+                    // U'[c'][P] of this lane's columns is fetched one pivot ahead of its use (the read depends on a row-broadcast address)
+                    auto fetch_u = [&](auto cc, double (&u)[NS]) __attribute__((always_inline)) {
+                        constexpr int C  = decltype(cc)::value;
+                        constexpr int sc = (C + SIG) / 16, lc = (C + SIG) % 16;
+                        const int rowp   = gbci<lc>(rp[sc]);
+                        const int selq   = gbci<lc>(rq[sc]);
+#pragma unroll
+                        for (int s = sc; s < NS; s++)
+                        {
+                            const unsigned e = __builtin_amdgcn_perm((unsigned)(em[s] >> 32), (unsigned)em[s], (unsigned)selq);
+                            u[s]             = D(rowp + (int)(e << 3));
+                        }
+                    };
+                    double ua[NS], ub[NS]; // even / odd steps (no copies between the steps)
+#pragma unroll
+                    for (int s = 0; s < NS; s++) ua[s] = ub[s] = 0.0;
+                    if (Fcmax > 0) fetch_u(std::integral_constant<int, 0>{}, ua);
+                    qt_for_each_while<0, 16 * NS - SIG>(
+                        [&](auto cc) __attribute__((always_inline)) { return decltype(cc)::value < Fcmax; }, // wave-uniform
+                        [&](auto cc) __attribute__((always_inline)) {
+                            constexpr int C  = decltype(cc)::value;
+                            constexpr int sc = (C + SIG) / 16, lc = (C + SIG) % 16;
+                            double(&ucur)[NS]  = (C & 1) ? ub : ua;
+                            double(&unext)[NS] = (C & 1) ? ua : ub;
+                            // a row of the wavefront whose own pivots end before Fcmax meets the zeros of the x block as "U'": every fma adds a zero product
+                            double lr[MD];
+                            for_each_index<0, MD>([&](auto rr) {
+                                constexpr int r = decltype(rr)::value;
+                                lr[r]           = gbc<lc>(blk[sc][r]);
+                            });
+#pragma unroll
+                            for (int r = 0; r < MD; r++) blk[sc][r] = dfma(-lr[r], ucur[sc], blk[sc][r]);
+                            // (the next step's U' behind the first slot's work: its address chain does not stall the step's start)
+                            if constexpr (C + 1 < 16 * NS - SIG)
+                            {
+                                if (C + 1 < Fcmax) fetch_u(std::integral_constant<int, C + 1>{}, unext);
+                            }
+#pragma unroll
+                            for (int s = sc + 1; s < NS; s++)
+                            {
+#pragma unroll
+                                for (int r = 0; r < MD; r++) blk[s][r] = dfma(-lr[r], ucur[s], blk[s][r]);
+                            }
+                        });
+                }
+                STAMP(7)
+                LSTAMP(1)
+
+                // =====================================================================================
+                // Householder QR with column pivoting of the level (lexlse.h:182-268), slots S0 .. NS-1.
+                // Straight-line per pivot, ONE basic block: a row that has stopped keeps executing on data nobody reads again, its bookkeeping
+                // frozen by selects.  Order inside a step = the dependency chain, with everything that is not on it placed in its shadows:
+                //   read the pivot column (LDS, slot of the winning lane)  ->  tail / fresh norm  ->  1/sqrt  ->  row j of the block,
+                //   down-dated norms  ->  DECISION for pivot j+1 (local best, two butterflies)  ->  next read.
+                // Beside the chain: the raw dot products (beside the 1/sqrt), the reciprocal of c0 - beta and the rank-one update of the rows
+                // below (beside the butterflies), then every lane stores the column of its local best slot in its own LDS slot — the store
+                // does not wait for the decision, only the next step's read address does.
+                // =====================================================================================
+                auto factor_level = [&](auto s0c) __attribute__((always_inline)) {
+                    constexpr int S0 = decltype(s0c)::value;
+                    constexpr int SL = NS - S0; // live slots
+                    double nrm[NS];
+#pragma unroll
+                    for (int s = S0; s < NS; s++)
+                    {
+                        double t = 0.0;
+#pragma unroll
+                        for (int r = 0; r < MD; r++) t = dfma(blk[s][r], blk[s][r], t); // lexlse.h:193-196
+                        nrm[s] = sel(pos[s] >= ColIndex && pos[s] < n, t, qt_with_hi(t, kQtSentinelHi));
+                    }
+                    bool go = work;
+#ifdef LEXLS_QTOL_CHAIN
+                    unsigned long long ct[7] = {0, 0, 0, 0, 0, 0, 0}, cp1 = 0;
+                    bool cvalid = false;
+#endif
+                    // Pivot decision: first maximum (by position) of the down-dated norms (lexlse.h:205-206) as ONE f64 max butterfly: the low twelve
+                    // bits of a candidate's norm are replaced by 4095 - (position << 6 | slot << 4 | lane) for the comparison, so that equal
+                    // norms order by position and the winner's identity comes out of the maximum itself.  (Norms that agree in their upper
+                    // 52 - 12 mantissa bits also order by position: a 2^-40 window in which the reference's own choice depends on its summation
+                    // order.  The norms themselves stay untouched.)
+                    int cur_lbs = S0, nxt_lbs = S0;     // slot of the lane's local best candidate: for this pivot / the next one
+                    bool cur_ispl = false, nxt_ispl = false; // this lane holds the pivot column
+                    unsigned cur_w = 0, nxt_w = 0;      // the winner's 12-bit key (position << 6 | slot << 4 | lane)
+                    double pbest = 0.0;                 // the lane's local best, packed
+                    auto decide_local = [&]() __attribute__((always_inline)) {
+#pragma unroll
+                        for (int s = S0; s < NS; s++)
+                        {
+                            const int kinv  = (0xFFF - ((s << 4) | gl)) - (pos[s] << 6);
+                            const double pv = __hiloint2double(__double2hiint(nrm[s]), (__double2loint(nrm[s]) & ~0xFFF) | kinv);
+                            pbest           = s == S0 ? pv : vmax(pbest, pv);
+                        }
+                        nxt_lbs = ((0xFFF - (__double2loint(pbest) & 0xFFF)) >> 4) & 3;
+                    };
+                    auto decide_finish = [&](double m) __attribute__((always_inline)) {
+                        const int mlo = __double2loint(m);
+                        nxt_w         = (unsigned)(0xFFF - (mlo & 0xFFF));
+                        nxt_ispl      = ((__double2loint(pbest) ^ mlo) & 0xFFF) == 0;
+                    };
+                    // prologue: decision for pivot 0, every lane's best column to its hand-off slot
+                    {
+                        decide_local();
+                        decide_finish(row_max16(pbest));
+                        double colv[MD];
+#pragma unroll
+                        for (int r = 0; r < MD; r++) colv[r] = blk[S0][r];
+#pragma unroll
+                        for (int s = S0 + 1; s < NS; s++)
+                        {
+                            const bool pick = nxt_lbs == s;
+#pragma unroll
+                            for (int r = 0; r < MD; r++) colv[r] = sel(pick, blk[s][r], colv[r]);
+                        }
+#pragma unroll
+                        for (int r = 0; r < MD; r += 2) D2(o_stage + gl * kHandoffStride + 8 * r) = qt_d2{colv[r], colv[r + 1]};
+                        cur_lbs = nxt_lbs, cur_ispl = nxt_ispl, cur_w = nxt_w;
+                    }
+                    // the winner's column is read AHEAD: as soon as a step knows the next pivot's lane, the read is issued — the rest of the step (rank-one
+                    // update of the other columns) runs while it is on its way
+                    double coln[MD];
+                    auto fetch_column = [&](auto jjc, unsigned w) __attribute__((always_inline)) {
+                        constexpr int ce0 = decltype(jjc)::value & ~1;
+                        quad_lds_fence();
+                        const int src = o_stage + (int)(w & 15u) * kHandoffStride;
+#pragma unroll
+                        for (int r = ce0; r < MD; r += 2)
+                        {
+                            const qt_d2 v   = D2(src + 8 * r);
+                            coln[r]         = v.x;
+                            coln[r + 1]     = v.y;
+                        }
+                    };
+                    fetch_column(std::integral_constant<int, 0>{}, cur_w);
+
+                    int pf_issued = 0; // pieces of the next level requested so far (wave-uniform)
+                    qt_for_each_while<0, MD>(
+                        [&](auto jc) __attribute__((always_inline)) { return (decltype(jc)::value % 4 != 0) || __ballot(go) != 0ull; }, // tested every fourth step: no row of the wavefront has work left -> ONE branch leaves the level
+                        [&](auto cnt) __attribute__((always_inline)) {
+                        constexpr int j   = decltype(cnt)::value;
+                        constexpr int ce  = j & ~1;       // first (even) row of this step's hand-off
+                        constexpr int cen = (j + 1) & ~1; // ... of the next step's
+                        // the next level's pieces: PF_PER per pivot step from the first step on (what an early end leaves over is requested behind the loop)
+                        {
+                            constexpr int TOT = NH * NIH, PF_PER = (TOT + PF_STEPS - 1) / PF_STEPS;
+                            constexpr int lo = (j * PF_PER < TOT ? j * PF_PER : TOT), hi = ((j + 1) * PF_PER < TOT ? (j + 1) * PF_PER : TOT);
+                            if (prefetch) for_each_index<lo, hi>([&](auto tt) __attribute__((always_inline)) { prefetch_piece(tt, F + MD); });
+                            pf_issued = hi;
+                        }
+                        const bool act = go;
+                        CSTAMP(0, (int)cur_w)
+                        double col[MD];
+#pragma unroll
+                        for (int r = ce; r < MD; r++) col[r] = coln[r];
+                        FSTAMP(2)
+                        CSTAMP(1, __double2loint(col[MD - 1]))
+                        CSTAMP_COLLECT
+                        const double c0 = col[j];
+                        // tail norm in three partial sums, fresh norm = c0^2 + tail (lexlse.h:210-211, :241)
+                        double t0 = 0.0, t1 = 0.0, t2 = 0.0;
+#pragma unroll
+                        for (int r = j + 1; r < MD; r++)
+                        {
+                            if ((r - j) % 3 == 1) t0 = dfma(col[r], col[r], t0);
+                            if ((r - j) % 3 == 2) t1 = dfma(col[r], col[r], t1);
+                            if ((r - j) % 3 == 0) t2 = dfma(col[r], col[r], t2);
+                        }
+                        const double tailSq = (t0 + t1) + t2;
+                        const double fresh  = dfma(c0, c0, tailSq);
+                        CSTAMP(2, __double2loint(fresh))
+                        const bool cont     = act && !(fresh < a.tol); // rank test on the squared norm (lexlse.h:214); no branch: a stopped row runs on
+                        go                  = cont;
+                        // 1 / sqrt(fresh): v_rsq_f64 and two coupled iterations (g -> sqrt, h -> 1 / (2 sqrt))
+                        double g, h;
+                        {
+                            const double y = __builtin_amdgcn_rsq(fresh);
+                            g              = fresh * y;
+                            h              = 0.5 * y;
+                            double r       = dfma(-h, g, 0.5);
+                            g              = dfma(g, r, g);
+                            h              = dfma(h, r, h);
+#ifndef LEXLS_QTOL_ONE_NEWTON
+                            r              = dfma(-h, g, 0.5);
+                            g              = dfma(g, r, g);
+                            h              = dfma(h, r, h);
+#endif
+                        }
+                        const bool neg    = c0 >= 0.0;       // beta = -sign(c0) sqrt(fresh)
+                        const double beta = neg ? -g : g;
+                        const double ibet = (neg ? -2.0 : 2.0) * h; // 1 / beta
+                        CSTAMP(3, __double2loint(ibet))
+                        const double rden = qt_rcp1(c0 - beta);     // (for the rows below; not on the chain to the next decision)
+                        // raw dot products col . a of every live column (beside the chain above)
+                        double dw[NS];
+#pragma unroll
+                        for (int s = S0; s < NS; s++)
+                        {
+                            double d0 = 0.0, d1 = 0.0;
+#pragma unroll
+                            for (int r = j + 1; r < MD; r++)
+                            {
+                                if ((r - j) & 1)
+                                    d0 = dfma(col[r], blk[s][r], d0);
+                                else
+                                    d1 = dfma(col[r], blk[s][r], d1);
+                            }
+                            dw[s] = dfma(c0, blk[s][j], d0 + d1);
+                        }
+                        FSTAMP(3)
+                        // row j of the block: R_js = (col . a_s) / beta (final after this reflector); norm down-date (lexlse.h:262-266); the pivot
+                        // column leaves the candidates; the row is kept normalised by 1 / R_jj.  gs: a_s[r] += gs col[r] for the rows below,
+                        // gs = (R_js - a_s[j]) / (c0 - beta)   (= a_s - tau v v.a_s, lexlse.h:243-246)
+                        double gs[NS];
+#pragma unroll
+                        for (int s = S0; s < NS; s++)
+                        {
+                            const double t = dw[s] * ibet;
+                            gs[s]          = (t - blk[s][j]) * rden;
+                            nrm[s]         = dfma(-t, t, nrm[s]);
+                            nrm[s]         = sel(cont && cur_ispl && cur_lbs == s, qt_with_hi(nrm[s], kQtSentinelHi), nrm[s]);
+                            blk[s][j]      = t * ibet;
+                        }
+                        CSTAMP(4, __double2hiint(nrm[NS - 1]))
+                        // column "swap": update the position map (lexlse.h:222-232)
+                        const int ppos = (int)(cur_w >> 6);
+#pragma unroll
+                        for (int s = S0; s < NS; s++)
+                        {
+                            const bool front = cont && pos[s] == ColIndex;
+                            pos[s]           = sel(front, ppos, pos[s]);
+                            pos[s]           = sel(cont && cur_ispl && cur_lbs == s, ColIndex, pos[s]);
+                        }
+                        B8(sel(cont && cur_ispl, o_perm + ColIndex, o_ex + 4 * gl)) = (uint8_t)ppos; // (o_ex: dump slots, one bank per lane — same-address stores of many lanes serialise)
+                        if constexpr (EST)
+                        {
+                            // the pivot's lane: its raw squared norm times h^2 = 1 / (4 fresh)
+                            double r2 = rsq[S0];
+#pragma unroll
+                            for (int s = S0 + 1; s < NS; s++) r2 = sel(cur_lbs == s, rsq[s], r2);
+                            est2 = sel(cont && cur_ispl, vmax(est2, r2 * (h * h)), est2);
+                        }
+                        ColIndex += cont ? 1 : 0;
+                        rank += cont ? 1 : 0;
+                        const bool full = cont && ColIndex == n;
+                        exh             = exh || full;
+                        go              = go && !full;
+                        FSTAMP(4)
+                        if constexpr (j + 1 < MD && SL == 1)
+                        {
+                            // one live slot: the lane's best column IS the slot — update it (in the stalls of the butterfly), store it
+                            decide_local();
+                            double m = pbest;
+                            auto upd_rows = [&](auto qq) __attribute__((always_inline)) {
+                                constexpr int q = decltype(qq)::value;
+#pragma unroll
+                                for (int r = j + 1; r < MD; r++)
+                                    if ((r - j - 1) % 4 == q) blk[S0][r] = dfma(gs[S0], col[r], blk[S0][r]);
+                            };
+                            m = dpp_max<0xB1>(m);
+                            upd_rows(std::integral_constant<int, 0>{});
+                            m = dpp_max<0x4E>(m);
+                            upd_rows(std::integral_constant<int, 1>{});
+                            m = dpp_max<0x141>(m);
+                            upd_rows(std::integral_constant<int, 2>{});
+                            m = dpp_max<0x140>(m);
+                            upd_rows(std::integral_constant<int, 3>{});
+#pragma unroll
+                            for (int r = cen; r < MD; r += 2) D2(o_stage + gl * kHandoffStride + 8 * r) = qt_d2{blk[S0][r], blk[S0][r + 1]};
+                            decide_finish(m);
+                            fetch_column(std::integral_constant<int, j + 1>{}, nxt_w);
+                        }
+                        else if constexpr (j + 1 < MD)
+                        {
+                            // The decision for the next pivot: local part, then the four butterfly stages.  In the stalls of the stages: the lane's
+                            // best column (for the next hand-off) is picked out of the slots BEFORE the rank-one update, updated on its own and
+                            // stored — the store does not wait for the decision, only the next step's read address does
+                            decide_local();
+                            double colv[MD];
+                            double gsb = gs[S0];
+                            double m   = pbest;
+                            auto pick_rows = [&](auto qq) __attribute__((always_inline)) {
+                                constexpr int q = decltype(qq)::value;
+#pragma unroll
+                                for (int r = cen; r < MD; r++)
+                                    if ((r - cen) % 4 == q)
+                                    {
+                                        colv[r] = blk[S0][r];
+#pragma unroll
+                                        for (int s = S0 + 1; s < NS; s++) colv[r] = sel(nxt_lbs == s, blk[s][r], colv[r]);
+                                    }
+                            };
+                            m = dpp_max<0xB1>(m);
+                            pick_rows(std::integral_constant<int, 0>{});
+                            m = dpp_max<0x4E>(m);
+                            pick_rows(std::integral_constant<int, 1>{});
+                            m = dpp_max<0x141>(m);
+                            pick_rows(std::integral_constant<int, 2>{});
+                            m = dpp_max<0x140>(m);
+                            pick_rows(std::integral_constant<int, 3>{});
+#pragma unroll
+                            for (int s = S0 + 1; s < NS; s++) gsb = sel(nxt_lbs == s, gs[s], gsb);
+#pragma unroll
+                            for (int r = (cen > j + 1 ? cen : j + 1); r < MD; r++) colv[r] = dfma(gsb, col[r], colv[r]);
+#pragma unroll
+                            for (int r = cen; r < MD; r += 2) D2(o_stage + gl * kHandoffStride + 8 * r) = qt_d2{colv[r], colv[r + 1]};
+                            decide_finish(m);
+                            fetch_column(std::integral_constant<int, j + 1>{}, nxt_w);
+                        }
+                        CSTAMP(5, (int)nxt_w)
+                        // rows below of every live column
+                        if constexpr (!(j + 1 < MD && SL == 1))
+                        {
+#pragma unroll
+                            for (int s = S0; s < NS; s++)
+                            {
+#pragma unroll
+                                for (int r = j + 1; r < MD; r++) blk[s][r] = dfma(gs[s], col[r], blk[s][r]);
+                            }
+                        }
+                        cur_lbs = nxt_lbs, cur_ispl = nxt_ispl, cur_w = nxt_w;
+                        CSTAMP(6, __double2loint(blk[NS - 1][MD - 1]))
+                        FSTAMP(5)
+                    });
+                    if (prefetch)
+                        for_each_index<0, NH * NIH>([&](auto tt) __attribute__((always_inline)) {
+                            if (decltype(tt)::value >= pf_issued) prefetch_piece(tt, F + MD);
+                        });
+                    (void)SL;
+                };
+                {
+                    const int s0 = (rows_min(work ? Fc : 0x3fffffff) + SIG) >> 4;
+                    if (NS > 3 && s0 >= 3)
+                        factor_level(std::integral_constant<int, (NS > 3 ? 3 : 0)>{});
+                    else if (NS > 2 && s0 >= 2)
+                        factor_level(std::integral_constant<int, (NS > 2 ? 2 : 0)>{});
+                    else if (NS > 1 && s0 >= 1)
+                        factor_level(std::integral_constant<int, (NS > 1 ? 1 : 0)>{});
+                    else
+                        factor_level(std::integral_constant<int, 0>{});
+                }
+                STAMP(5)
+                LSTAMP(2)
+
+                // =====================================================================================
+                // level end: triangular image [R_k T_k | rhs_k] / diag in end-of-level position order, maps
+                // =====================================================================================
+                const int wk   = n + 1 - Fc;
+                const int dump = o_stage + 8 * gl; // stores that do not apply go to a dump slot of the lane's own (the staging block is idle here): no divergent regions, no bank conflicts
+                int roff[MD];          // byte offset of image row p (triangular packing), the same for every slot
+#pragma unroll
+                for (int p = 0; p < MD; p++) roff[p] = 8 * (p * wk - p * (p + 1) / 2);
+#pragma unroll
+                for (int s = 0; s < NS; s++)
+                {
+                    const int P0  = 16 * s + gl - SIG;
+                    const bool mv = work && P0 <= n && P0 >= Fc; // columns that were live in this level (the RHS included)
+                    const int e   = pos[s] - Fc;                 // index of this column in the level's image: end-of-level position order
+                    const int lim = mv ? (e < rank - 1 ? e : rank - 1) : -1; // rows 0 .. lim of the column go to the image (p < rank, p <= e)
+                    const int base = o_img + 8 * (imgoff + e);
+                    if (mv)
+                    {
+#pragma unroll
+                        for (int p = 0; p < MD; p++) D(sel(p <= lim, base + roff[p], dump)) = blk[s][p];
+                        B8(o_emap + 8 * pc[s] + k) = (uint8_t)e;
+                        if (P0 < n) B8(o_phys + pos[s]) = (uint8_t)pc[s];
+                    }
+                    // pivot position P0 of this level: its image row and the selector of this level's index byte
+                    const bool piv = work && P0 >= Fc && P0 < Fc + rank;
+                    const int p    = P0 - Fc;
+                    rp[s]          = sel(piv, o_img + 8 * (imgoff + p * wk - p * (p + 1) / 2), rp[s]);
+                    rq[s]          = sel(piv, 0x0c0c0c00 | k, rq[s]);
+                }
+                STAMP(6)
+                LSTAMP(3)
+                if (gl == 0)
+                {
+                    U32(o_meta + 16 * k)      = (uint32_t)Fc;
+                    U32(o_meta + 16 * k + 4)  = (uint32_t)rank;
+                    U32(o_meta + 16 * k + 8)  = (uint32_t)imgoff;
+                    U32(o_meta + 16 * k + 12) = (uint32_t)wk;
+                }
+                quad_lds_fence();
+                imgoff += wk * rank - rank * (rank - 1) / 2;
+                TotalRank += rank;
+            }
+
+            // ---- solve(): block back-substitution on the normalised images (lexlse.h:1015-1045); lane p <-> row p of a level.  Straight-line
+            // per level: what does not apply reads a zero (position 16 NS - 1 of the x block is never written) or goes to the dump slot ----
+            const int o_zero = o_xs + 8 * (16 * NS - 1);
+            for (int k = nObj; k--;)
+            {
+                const qt_u4 mt = U4(o_meta + 16 * k); // {first column, rank, image offset, image width}
+                const int rank = live ? (int)mt.y : 0;
+                const int rmax = rows_max(rank);
+                if (rmax == 0) continue;
+                const int Fc = (int)mt.x, ok = (int)mt.z, wk = (int)mt.w;
+                const int c0   = Fc + rank;
+                const int acc  = rank > 0 ? TotalRank - c0 : 0;
+                const int amax = rows_max(acc);
+                const int p    = gl < rank ? gl : 0;
+                const int row  = o_img + 8 * (ok + p * wk - p * (p + 1) / 2);
+                double col[MD];
+#pragma unroll
+                for (int j = 1; j < MD; j++) col[j] = D(sel(j < rank && gl < j, row + 8 * j, o_zero));
+                double sv = D(sel(gl < rank, row + 8 * (n - Fc), o_zero));
+                // rhs'_k - T'_k x_later (lexlse.h:1029-1033): the column at final position c sits at its level-k index inside the image;
+                // sixteen solved positions per trip — lane j looks up index and x of position c0 + base + j, the row-broadcast hands them out
+                for (int base = 0; base < amax; base += 16)
+                {
+                    const bool have = base + gl < acc;
+                    const int c     = have ? c0 + base + gl : 16 * NS - 1;
+                    const int ph    = (int)B8(o_phys + c);
+                    const int offv  = have ? (int)B8(o_emap + 8 * ph + k) : 0;
+                    const double xv = D(o_xs + 8 * c); // (zero where the position does not apply)
+                    double uj[16]; // all sixteen reads in flight before the first is used (issued a few at a time, each group pays the LDS latency)
+                    for_each_index<0, 16>([&](auto jj) {
+                        constexpr int j = decltype(jj)::value;
+                        uj[j]           = D(row + 8 * gbci<j>(offv));
+                    });
+                    __builtin_amdgcn_sched_barrier(0);
+                    double s0 = 0.0, s1 = 0.0; // two chains
+                    for_each_index<0, 16>([&](auto jj) {
+                        constexpr int j = decltype(jj)::value;
+                        if (j & 1)
+                            s1 = dfma(-uj[j], gbc<j>(xv), s1);
+                        else
+                            s0 = dfma(-uj[j], gbc<j>(xv), s0);
+                    });
+                    sv += s0 + s1;
+                }
+                sv = sel(gl < rank, sv, 0.0);
+                for_each_index<1, MD>([&](auto jj) {
+                    constexpr int j = MD - decltype(jj)::value; // MD-1 .. 1
+                    sv = dfma(-col[j], gbc<j>(sv), sv); // unit diagonal; col[j] is zero at and below the diagonal and beyond the rank
+                });
+                D(sel(gl < rank, o_xs + 8 * (Fc + gl), o_stage + 8 * gl)) = sv;
+                quad_lds_fence();
+            }
+            STAMP(9)
+            // ---- results ----
+            if (live)
+            {
+#pragma unroll
+                for (int s = 0; s < NS; s++)
+                {
+                    const int P = 16 * s + gl; // every position once, whatever the layout offset
+                    if (P < n)
+                    {
+                        a.x[(size_t)b * n + B8(o_phys + P)] = D(o_xs + 8 * P); // x = P x: the variable at position P (lexlse.h:1044)
+                        a.perm[(size_t)b * n + P]           = (P < TotalRank) ? (uint32_t)B8(o_perm + P) : (uint32_t)P;
+                    }
+                }
+                if (gl < nObj)
+                {
+                    a.fcol[(size_t)b * nObj + gl] = U32(o_meta + 16 * gl);
+                    a.rank[(size_t)b * nObj + gl] = U32(o_meta + 16 * gl + 4);
+                }
+                if (gl == 0) a.totalrank[b] = (uint32_t)TotalRank;
+            }
+            if constexpr (EST)
+            {
+                const double e2 = row_max16(est2);
+                if (gl == 0 && b < a.batch) est_out[b] = (live && e2 > 0.0) ? 2.0 * qt_sqrt(e2) : 0.0; // (no pivot at all: nothing to vouch for)
+            }
+            STAMP(10)
+            STAMP_WRITE
+#ifdef LEXLS_QTOL_CHAIN
+            if (lane == 0)
+                for (int i_ = 0; i_ < 7; i_++) a.lambda[(size_t)b * (n + cap) + 30 + i_] = (double)cacc[i_];
+#endif

@@ -1,0 +1,3 @@
+// x only, indirect: the accuracy guard's bit-exact re-solve of the problems lqr_qtol flagged (same arithmetic as lqr_quad_1x12_x)
+#include "lqr_quad_impl.h"
+LEXLS_QUAD_INSTANCE_IND(launch_quad_1x12_xi, 1,12,0)

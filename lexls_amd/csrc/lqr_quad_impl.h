@@ -44,8 +44,12 @@ namespace lexls
         /// the first positions by the reference's chained swap rule (an edit of the position -> physical-column map before the first level
         /// is loaded), every level block moves their contribution to its right-hand side when it is loaded (ordered chain over the fixed
         /// positions, row-broadcast operands), and from then on a fixed position behaves like a pivot with a zero reciprocal diagonal.
-        template <int NS, int MD, bool WF, int SIG, bool FIX = false>
-        __global__ __launch_bounds__(64) void lqr_quad_kernel(LseArgs a, uint32_t img_doubles, uint32_t group_bytes)
+        /// IND: the indirect form of the accuracy guard's re-solve (lexls_lse_set_accuracy_guard, mode 2).  ind = [count, list...] in device
+        /// memory: row i of the grid solves problem list[i] while i < count and idles otherwise (a wavefront wholly beyond count exits at
+        /// once), so that a launch sized for the whole batch serves a count known only on the device.  Nothing else changes: the same
+        /// arithmetic as the direct form, results written to the problem's own slots.
+        template <int NS, int MD, bool WF, int SIG, bool FIX = false, bool IND = false>
+        __global__ __launch_bounds__(64) void lqr_quad_kernel(LseArgs a, uint32_t img_doubles, uint32_t group_bytes, const uint32_t *ind)
         {
             static_assert(NS >= 1 && NS <= 4 && MD <= 16 && (MD % 2) == 0, "shape limits of the row layout");
             extern __shared__ double smem[];
@@ -56,7 +60,13 @@ namespace lexls
             const int n    = (int)a.nVar;
             const int cap  = (int)a.cap;
             const int nObj = (int)a.nObj;
-            const uint32_t b  = blockIdx.x * 4u + (uint32_t)g;
+            uint32_t b = blockIdx.x * 4u + (uint32_t)g;
+            if constexpr (IND)
+            {
+                const uint32_t count = ind[0];
+                if (blockIdx.x * 4u >= count) return;
+                b = b < count ? ind[1 + b] : a.batch;
+            }
             const uint32_t bb = b < a.batch ? b : a.batch - 1u; // rows beyond the batch idle on a valid address
             const bool live   = b < a.batch && !(a.skip && a.skip[bb]);
             const size_t pstride = (size_t)cap * (n + 1);
@@ -851,8 +861,8 @@ namespace lexls
             return (8 * ((size_t)quad_image_doubles(n, nObj, md) + 16 * NS + 18) + 64 + 64 + 16 * kQuadMaxObj + 512 + 4 * kQuadMaxObj + 15) & ~(size_t)15;
         }
 
-        template <int NS, int MD, bool WF, int SIG, bool FIX = false>
-        hipError_t launch_quad_t(const LseArgs &a, hipStream_t s)
+        template <int NS, int MD, bool WF, int SIG, bool FIX = false, bool IND = false>
+        hipError_t launch_quad_t(const LseArgs &a, hipStream_t s, const uint32_t *ind = nullptr)
         {
             const uint32_t img = quad_image_doubles(a.nVar, a.nObj, MD);
             const size_t gbytes = quad_group_bytes<NS>(a.nVar, a.nObj, MD);
@@ -860,11 +870,11 @@ namespace lexls
             if (lds > kMaxLdsBytes || a.nObj > (uint32_t)kQuadMaxObj || a.nVar + 1 + SIG > 16u * NS || a.nVar > 63u) return hipErrorInvalidValue;
             if (lds > 64 * 1024)
             {
-                hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(lqr_quad_kernel<NS, MD, WF, SIG, FIX>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+                hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(lqr_quad_kernel<NS, MD, WF, SIG, FIX, IND>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
                 if (e != hipSuccess) return e;
             }
             const uint32_t blocks = (a.batch + 3u) / 4u;
-            hipLaunchKernelGGL((lqr_quad_kernel<NS, MD, WF, SIG, FIX>), dim3(blocks), dim3(64), lds, s, a, img, (uint32_t)gbytes);
+            hipLaunchKernelGGL((lqr_quad_kernel<NS, MD, WF, SIG, FIX, IND>), dim3(blocks), dim3(64), lds, s, a, img, (uint32_t)gbytes, ind);
             return hipGetLastError();
         }
     } // namespace
@@ -875,3 +885,6 @@ namespace lexls
     namespace lexls { hipError_t NAME(const LseArgs &a, hipStream_t s) { return launch_quad_t<NS, MD, WF, SIG>(a, s); } }
 #define LEXLS_QUAD_INSTANCE_FIX(NAME, NS, MD, WF, SIG) \
     namespace lexls { hipError_t NAME(const LseArgs &a, hipStream_t s) { return launch_quad_t<NS, MD, WF, SIG, true>(a, s); } }
+// x only, indirect (IND): ind = [count, problem list] in device memory
+#define LEXLS_QUAD_INSTANCE_IND(NAME, NS, MD, SIG) \
+    namespace lexls { hipError_t NAME(const LseArgs &a, hipStream_t s, const uint32_t *ind) { return launch_quad_t<NS, MD, false, SIG, false, true>(a, s, ind); } }

@@ -44,6 +44,15 @@ namespace lexls
     hipError_t launch_quad_3x12s7_fF(const LseArgs &a, hipStream_t s);
     size_t quad_lds_bytes(uint32_t slots, uint32_t md, uint32_t nVar, uint32_t nObj);
     hipError_t launch_qtol_3x12s7(const LseArgs &a, hipStream_t s);
+    hipError_t launch_qtol_3x12s7e(const LseArgs &a, hipStream_t s, double *est, uint32_t *count);
+    hipError_t launch_qtol_3x12e(const LseArgs &a, hipStream_t s, double *est, uint32_t *count);
+    hipError_t launch_qtol_2x12e(const LseArgs &a, hipStream_t s, double *est, uint32_t *count);
+    hipError_t launch_qtol_3x8e(const LseArgs &a, hipStream_t s, double *est, uint32_t *count);
+    hipError_t launch_qtol_2x8e(const LseArgs &a, hipStream_t s, double *est, uint32_t *count);
+    hipError_t launch_quad_1x12_xi(const LseArgs &a, hipStream_t s, const uint32_t *ind);
+    hipError_t launch_quad_2x12_xi(const LseArgs &a, hipStream_t s, const uint32_t *ind);
+    hipError_t launch_quad_3x12_xi(const LseArgs &a, hipStream_t s, const uint32_t *ind);
+    hipError_t launch_quad_3x12s7_xi(const LseArgs &a, hipStream_t s, const uint32_t *ind);
     size_t launch_qtol_3x12s7_lds(uint32_t nVar, uint32_t nObj);
     hipError_t launch_qtol_3x12(const LseArgs &a, hipStream_t s);
     size_t launch_qtol_3x12_lds(uint32_t nVar, uint32_t nObj);
@@ -169,8 +178,20 @@ namespace lexls
         return !has_fixed && max_level_dim <= 12 && a.nVar + 1 <= 41 && a.nObj <= 8;
     }
 
+    hipError_t launch_quad_resolve(const LseArgs &a, uint32_t max_level_dim, const uint32_t *ind, hipStream_t s)
+    {
+        switch (quad_choice(a, max_level_dim, false, 2, false))
+        {
+        case 5: return launch_quad_1x12_xi(a, s, ind);
+        case 4: return launch_quad_2x12_xi(a, s, ind);
+        case 2: return launch_quad_3x12s7_xi(a, s, ind);
+        case 1: return launch_quad_3x12_xi(a, s, ind);
+        default: return hipErrorNotSupported;
+        }
+    }
+
     hipError_t launch_lqr_wave(const LseArgs &a, uint32_t max_level_dim, bool write_factor, bool has_fixed, int left_looking, hipStream_t s,
-                               const char **variant, int tolerance)
+                               const char **variant, int tolerance, const GuardArrays *guard)
     {
         const uint32_t nc = a.nVar + 1;
         // tolerance: 0 bit-exact kernels only; 1 automatic (lqr_qtol where it serves — the faster of the two on MI355X: 41 us against 57 us per
@@ -190,7 +211,17 @@ namespace lexls
             case 3: *variant = "lqr_mfma<64,12>"; return launch_mfma_64x12(a, s);
             default: break;
             }
-        if (tolerance != 0)
+        if (tolerance != 0 && guard)
+            switch (qtol_choice(a, write_factor, has_fixed))
+            {
+            case 1: *variant = "lqr_qtol<3,12,shift 7,guard>"; return launch_qtol_3x12s7e(a, s, guard->est, guard->ind);
+            case 2: *variant = "lqr_qtol<3,12,guard>"; return launch_qtol_3x12e(a, s, guard->est, guard->ind);
+            case 3: *variant = "lqr_qtol<2,12,guard>"; return launch_qtol_2x12e(a, s, guard->est, guard->ind);
+            case 4: *variant = "lqr_qtol<3,8,guard>"; return launch_qtol_3x8e(a, s, guard->est, guard->ind);
+            case 5: *variant = "lqr_qtol<2,8,guard>"; return launch_qtol_2x8e(a, s, guard->est, guard->ind);
+            default: break;
+            }
+        else if (tolerance != 0)
             switch (qtol_choice(a, write_factor, has_fixed))
             {
             case 1: *variant = "lqr_qtol<3,12,shift 7>"; return launch_qtol_3x12s7(a, s);

@@ -264,3 +264,17 @@ class BatchedLexLSE:
 
     def last_kernel(self) -> str:
         return capi.lib().lexls_lse_last_kernel(self._h).decode()
+
+    def set_accuracy_guard(self, mode: int, threshold: float = 0.0):
+        """lexls_lse_set_accuracy_guard: 0 off (default), 1 report, 2 report and re-solve the flagged problems on the bit-exact kernel
+        (include/lexls_hip.h, policy comment); threshold <= 0: the calibrated default"""
+        capi.check(capi.lib().lexls_lse_set_accuracy_guard(self._h, int(mode), float(threshold)))
+
+    def get_accuracy(self):
+        """(estimate (batch,) float64, status (batch,) uint8, flagged int) of the last factorization: status 0 solved under (B), 1 (T) below
+        the threshold, 2 flagged (mode 1), 3 flagged and re-solved under (B) (mode 2); flagged = number of problems with status 2 or 3"""
+        est = np.zeros(self.batch)
+        st = np.zeros(self.batch, np.uint8)
+        nf = C.c_uint32(0)
+        capi.check(capi.lib().lexls_lse_get_accuracy(self._h, _ptr(est, C.c_double), _ptr(st, C.c_uint8), C.byref(nf)))
+        return est, st, int(nf.value)

@@ -68,6 +68,35 @@ def lse_batch_fast(seed0: int, batch: int, nvar: int, dims) -> np.ndarray:
     return vals.reshape(batch, nvar + 1, m).copy()
 
 
+def near_dependent_batch(seed: int, batch: int, nvar: int, dims, delta: float) -> np.ndarray:
+    """lse_batch_fast with one column of every problem replaced by a random combination of two others plus `delta` N(0,1) noise
+    (nvar >= 3): full rank above any rank tolerance, but the smaller `delta`, the more cancellation in the factorization."""
+    lod = lse_batch_fast(seed, batch, nvar, dims)
+    m = lod.shape[2]
+    pick = (uniform(seed, 3 * batch, 1).reshape(batch, 3) * np.array([nvar, nvar - 1, nvar - 2])).astype(np.int64)
+    coef = normal(seed, 2 * batch, 2).reshape(batch, 2)
+    noise = normal(seed, batch * m, 3).reshape(batch, m)
+    for b in range(batch):
+        cols = list(range(nvar))
+        k = cols.pop(int(pick[b, 0]))
+        i = cols.pop(int(pick[b, 1]))
+        j = cols[int(pick[b, 2])]
+        lod[b, k, :] = coef[b, 0] * lod[b, i, :] + coef[b, 1] * lod[b, j, :] + delta * noise[b]
+    return lod
+
+
+def badly_scaled_batch(seed: int, batch: int, nvar: int, dims) -> np.ndarray:
+    """lse_batch_fast with the columns of every problem scaled by 10^U(-3, 3) and its rows (right-hand side included) by 10^U(-2, 2),
+    each problem its own scales."""
+    lod = lse_batch_fast(seed, batch, nvar, dims)
+    m = lod.shape[2]
+    col = 10.0 ** (6.0 * uniform(seed, batch * nvar, 1).reshape(batch, nvar) - 3.0)
+    row = 10.0 ** (4.0 * uniform(seed, batch * m, 2).reshape(batch, m) - 2.0)
+    lod[:, :nvar, :] *= col[:, :, None]
+    lod *= row[:, None, :]
+    return lod
+
+
 def rank_deficient_problem(seed: int, nvar: int, dims, ranks) -> np.ndarray:
     """Problem whose level k has exactly `ranks[k]` new directions beyond the levels above it.
 
