@@ -49,7 +49,8 @@ enum lexls_array
     LEXLS_ARRAY_LAMBDA,     /* double   batch x (nVar+cap)      [lambda_fixed; lambda] of the last sensitivity call */
     LEXLS_ARRAY_INPUT,      /* double   batch x cap x (nVar+1)  library-owned input buffer            */
     LEXLS_ARRAY_GUARD_ESTIMATE, /* double batch                 accuracy guard: estimate of the last solve (lexls_lse_set_accuracy_guard) */
-    LEXLS_ARRAY_GUARD_STATUS    /* uint8  batch                 accuracy guard: status of the last solve                                  */
+    LEXLS_ARRAY_GUARD_STATUS,   /* uint8  batch                 accuracy guard: status of the last solve                                  */
+    LEXLS_ARRAY_MULTIPLIERS     /* double batch x nObj x (nVar+cap) every objective's multipliers (lexls_lse_multipliers)                 */
 };
 
 /* replaces LexLS::Exception::what() (typedefs.h:300-314): no exception crosses the ABI — every entry point returns a status code and
@@ -163,6 +164,19 @@ int lexls_lse_sensitivity(lexls_lse_t h, const int32_t *h_obj_index, int32_t obj
 int lexls_lse_set_sensitivity_scan(lexls_lse_t h, int on);
 /* same, with the per-problem objective indices already on the device (the obj_index array of lexls_lse_upload_round) */
 int lexls_lse_sensitivity_resident(lexls_lse_t h, double tol_wrong_sign_lambda, double tol_correct_sign_lambda);
+
+/* Every objective's multipliers at once: column k of problem b is what lexls_lse_get_lambda returns after ObjectiveSensitivity(k) — the
+ * [lambda_fixed; lambda] workspace head(nMeaningful), nMeaningful = nfixed + dims[0] + ... + dims[k], zero from row nMeaningful on (lexlse.h:611-762,
+ * :636-639; the matrix LexLSI::getLambda assembles, lexlsi.h:573-590).  Bit-identical to nObj calls of lexls_lse_sensitivity(k); takes no decisions
+ * and leaves the types, the sensitivity outputs and LEXLS_ARRAY_LAMBDA as they are.  Needs a factorization whose factor was kept.  One launch where
+ * the removal sweep serves the shape (levels of up to 16 rows, at most 8 objectives, nVar <= 64), else nObj launches.
+ * lexls_lse_get_multipliers returns the matrices of the last lexls_lse_multipliers call as long as they belong to the current factor: after a later
+ * factorization, or any call that invalidates the factor (a new problem, dimensions, fixed variables, regularization), it fails with
+ * LEXLS_ERR_INVALID until lexls_lse_multipliers runs again (LEXLS_ARRAY_MULTIPLIERS keeps the last contents).
+ * Layout of h_L (lexls_lse_get_multipliers, LEXLS_ARRAY_MULTIPLIERS): batch x nObj x (nVar + cap) doubles — problem-major, then objective k,
+ * then the nVar + cap rows of its column (rows [0, nfixed) the fixed variables in fixVariable order, then the constraint rows of the levels). */
+int lexls_lse_multipliers(lexls_lse_t h);
+int lexls_lse_get_multipliers(lexls_lse_t h, double *h_L);
 
 /* ---- results (synchronise the stream, then D2H) ------------------------------------------------- */
 int lexls_lse_get_x(lexls_lse_t h, double *h_x);                    /* get_x()      lexlse.h:1587 */
@@ -297,6 +311,12 @@ int lexls_lsi_batch_solve_ex(int device, uint32_t batch, uint32_t nVar, uint32_t
                              const double *h_data, const uint32_t *h_var_index, const uint8_t *h_active_guess, const double *h_x0,
                              const double *h_reg_factors, const double *h_params, uint32_t nparams, double *h_x, int32_t *h_info6,
                              uint8_t *h_active, double *h_v, int32_t *h_rounds2);
+/* lexls_lsi_batch_solve_ex plus the multipliers of every instance: h_lambda (batch x sum(dims) x nObj, layout of lexls_lsi_batch_get_lambda) or
+ * NULL (= lexls_lsi_batch_solve_ex) */
+int lexls_lsi_batch_solve_ex2(int device, uint32_t batch, uint32_t nVar, uint32_t nObj, const uint32_t *h_dims, const int32_t *h_types,
+                              const double *h_data, const uint32_t *h_var_index, const uint8_t *h_active_guess, const double *h_x0,
+                              const double *h_reg_factors, const double *h_params, uint32_t nparams, double *h_x, int32_t *h_info6,
+                              uint8_t *h_active, double *h_v, int32_t *h_rounds2, double *h_lambda);
 /* The same batch as an object that outlives one solve — the way the reference uses LexLSI (constructed and sized once, lexlsi.h:56-112, then
  * fed successive problems): lexls_lsi_batch_create makes the device buffers, pinned blocks, streams and the host worker pool for `batch`
  * problems of the structure (nVar, dims, types); every lexls_lsi_batch_run solves `batch` new problems of that structure (arguments as
@@ -316,6 +336,22 @@ int lexls_lsi_batch_run(lexls_lsi_batch_t b, const double *h_data, const uint32_
  * next to the equality solve when the batch is created with LEXLS_LSI_DEVICE_STEP=1 in the environment; off by default. */
 int lexls_lsi_batch_stats(lexls_lsi_batch_t b, int32_t *h_stats4);
 int lexls_lsi_batch_destroy(lexls_lsi_batch_t b);
+/* LexLSI::getLambda (lexlsi.h:552-605) of every instance of the LAST lexls_lsi_batch_run on this batch: h_lambda receives batch x total x nObj
+ * doubles — per instance the `lambda` of lexls_lsi_debug (total x nObj, column-major, objectives stacked, user's constraint order), instances back
+ * to back.  Row of an active constraint = its multipliers in the equality problem of the instance's final working set (placed through
+ * getActiveCtrIndex, :592-604); inactive constraints 0; column 0 zero when objective 0 holds simple bounds (nObjOffset), the active simple bounds'
+ * rows carrying the fixed-variable multipliers.  Computed on request only, on the device in the batch's streams: the final equality problems are
+ * formed from the working sets the run kept (rows gathered from the resident constraint data), factorized with the factor kept on a bit-exact
+ * kernel — the same factor for instances that ended PROBLEM_SOLVED and for those the reference re-forms and refactorizes first (:568-571) —,
+ * every objective's multipliers taken at once (lexls_lse_multipliers), scattered into user order, copied back.  Bit-identical to
+ * lexls_lsi_solve_debug's `lambda` on each instance, every run path included (persistent launch, lock-step stages, LEXLS_LSI_RESIDENT=0, warm
+ * starts, v0, factorization limits, deactivate_first_wrong_sign), factorized with the run's tol_linear_dependence.
+ * Cost to runs that never ask: none, except with deactivate_first_wrong_sign — that path solves its instances one by one on the host driver and
+ * copies the batch's constraint data to the device once per run (what get_lambda gathers from later).
+ * Errors: LEXLS_ERR_INVALID before any run (or after a failed one); LEXLS_ERR_UNSUPPORTED after a run with cycling_handling_enabled (the bounds it
+ * relaxed live on the host only), after a regularized run (regularization_type != 0), or when the batch's constraint data is not resident
+ * (LEXLS_LSI_HOST_STAGING, data beyond 2^31 doubles per instance) or holds more than 65535 constraints per instance.  A later run replaces the multipliers of the previous one. */
+int lexls_lsi_batch_get_lambda(lexls_lsi_batch_t b, double *h_lambda);
 /* lexls_lsi_solve plus what the MEX front end also passes (interfaces/matlab-octave/lexlsi.cpp:527-625): h_v0 = initial residuals,
  * sum(dims) doubles (set_v0 per objective) or NULL; h_reg_factors = one regularization factor per objective or NULL; h_params with
  * nparams == 9 (as lexls_lsi_solve) or 12: + regularization_type, variable_regularization_factor, max_number_of_CG_iterations. */

@@ -28,9 +28,11 @@ SYMBOLS = [
     "lexls_lse_set_accuracy_guard", "lexls_lse_get_accuracy",
     "lexls_lse_set_prefix_reuse", "lexls_lse_prefix_reuse_ready", "lexls_lse_set_resume_levels",
     "lexls_lsi_solve", "lexls_lsi_solve_dat", "lexls_lsi_batch_solve",
+    "lexls_lse_multipliers", "lexls_lse_get_multipliers", "lexls_lsi_batch_get_lambda", "lexls_lsi_batch_solve_ex2",
 ]
 
-ARRAY = dict(x=0, factor=1, hh=2, perm=3, rank=4, first_col=5, total_rank=6, v=7, lam=8, input=9, guard_estimate=10, guard_status=11)
+ARRAY = dict(x=0, factor=1, hh=2, perm=3, rank=4, first_col=5, total_rank=6, v=7, lam=8, input=9, guard_estimate=10, guard_status=11,
+             multipliers=12)
 
 _lib = None
 

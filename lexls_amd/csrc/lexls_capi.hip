@@ -78,6 +78,12 @@ struct lexls_lse_s
     double reg_variable;
     double *d_reg_factor, *d_reg_scratch, *d_reg_mu;
     bool sens_scan; // lexls_lse_set_sensitivity_scan
+    // lexls_lse_multipliers: every objective's multipliers (batch x nObj x (nVar + cap)) and the scratch of its per-objective fallback
+    double *d_mult        = nullptr;
+    void *d_mult_scratch  = nullptr;
+    bool mult_valid       = false;
+    uint64_t mult_epoch   = 0;      // factor_epoch the multipliers belong to
+    bool mult_swept       = false;
     // accuracy guard (lexls_lse_set_accuracy_guard): mode 0 off, 1 report, 2 report + re-solve; arrays allocated when first switched on
     int guard_mode           = 0;
     double guard_threshold   = 0.0;
@@ -272,7 +278,7 @@ extern "C"
         (void)hipSetDevice(h->device);
         void *ptrs[] = {h->d_in_owned, h->d_fac, h->d_hh, h->d_v, h->d_lambda, h->d_scratch, h->d_perm, h->d_rank, h->d_fcol, h->d_round_in, h->d_round_out,
                         h->d_large_state, h->d_large_ws, h->d_norms, h->d_cdata, h->d_reg_factor, h->d_reg_scratch, h->d_reg_mu, h->d_resume_level, h->d_resume_state,
-                        h->d_guard_est, h->d_guard_status, h->d_guard_ind};
+                        h->d_guard_est, h->d_guard_status, h->d_guard_ind, h->d_mult, h->d_mult_scratch};
         for (void *p : ptrs)
             if (p) (void)hipFree(p);
         if (h->h_dims_pinned) (void)hipHostFree(h->h_dims_pinned);
@@ -956,6 +962,29 @@ extern "C"
         return LEXLS_OK;
     }
 
+    int lexls_lse_multipliers(lexls_lse_t h)
+    {
+        if (int rc = need_factor(h, "lexls_lse_multipliers")) return rc;
+        HIP_TRY(hipSetDevice(h->device));
+        const LseArgs a = h->args();
+        if (!h->d_mult) HIP_TRY(hipMalloc((void **)&h->d_mult, 8 * (size_t)h->batch * h->nObj * (h->nVar + h->cap)));
+        if (!multipliers_sweep_serves(a, h->max_level_dim) && !h->d_mult_scratch) HIP_TRY(hipMalloc(&h->d_mult_scratch, multipliers_scratch_bytes(a)));
+        HIP_TRY(launch_multipliers(a, h->d_mult, h->max_level_dim, h->stream, h->d_mult_scratch, &h->mult_swept));
+        h->mult_valid = true;
+        h->mult_epoch = h->factor_epoch;
+        return LEXLS_OK;
+    }
+
+    /* internal (the lock-step LexLSI driver): the handle's kernel policy (lexls_lse_set_kernel_policy), to put it back after a change */
+    int lexls_internal_kernel_policy(lexls_lse_t h) { return h ? h->force_generic : 0; }
+
+    /* internal (the lock-step LexLSI driver): the device buffer lexls_lse_multipliers filled last, and whether the sweep served it */
+    const double *lexls_internal_multipliers(lexls_lse_t h, int *swept)
+    {
+        if (swept) *swept = (h && h->mult_swept) ? 1 : 0;
+        return (h && h->mult_valid) ? h->d_mult : nullptr;
+    }
+
     static int download(lexls_lse_t h, void *dst, const void *src, size_t bytes)
     {
         CHECK_HANDLE(h);
@@ -1003,6 +1032,14 @@ extern "C"
     {
         return h ? download(h, h_lambda, h->d_lambda, 8 * (size_t)h->batch * (h->nVar + h->cap)) : fail(LEXLS_ERR_INVALID, "null handle");
     }
+    int lexls_lse_get_multipliers(lexls_lse_t h, double *h_L)
+    {
+        CHECK_HANDLE(h);
+        if (!h->mult_valid) return fail(LEXLS_ERR_INVALID, "lexls_lse_get_multipliers: call lexls_lse_multipliers first");
+        if (!h->factor_valid || h->mult_epoch != h->factor_epoch)
+            return fail(LEXLS_ERR_INVALID, "lexls_lse_get_multipliers: the problem or its factorization changed since lexls_lse_multipliers (call it again)");
+        return download(h, h_L, h->d_mult, 8 * (size_t)h->batch * h->nObj * (h->nVar + h->cap));
+    }
     int lexls_lse_get_sensitivity(lexls_lse_t h, int32_t *h_found_ctr_obj, double *h_max_abs)
     {
         CHECK_HANDLE(h);
@@ -1033,6 +1070,14 @@ extern "C"
         case LEXLS_ARRAY_GUARD_STATUS:
             if (!h->d_guard_est) return fail(LEXLS_ERR_INVALID, "lexls_lse_device_ptr: the accuracy guard has not been switched on (lexls_lse_set_accuracy_guard)");
             *d_ptr = which == LEXLS_ARRAY_GUARD_ESTIMATE ? (void *)h->d_guard_est : (void *)h->d_guard_status;
+            break;
+        case LEXLS_ARRAY_MULTIPLIERS:
+            if (!h->d_mult)
+            {
+                HIP_TRY(hipSetDevice(h->device));
+                HIP_TRY(hipMalloc((void **)&h->d_mult, 8 * (size_t)h->batch * h->nObj * (h->nVar + h->cap)));
+            }
+            *d_ptr = h->d_mult;
             break;
         case LEXLS_ARRAY_INPUT:
             if (!h->d_in_owned)

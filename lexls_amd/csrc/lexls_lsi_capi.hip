@@ -25,6 +25,9 @@ extern "C" int lexls_internal_round_resident(lexls_lse_t h, int has_fixed);     
 extern "C" int32_t *lexls_internal_resume_levels(lexls_lse_t h);                                     // lexls_capi.hip
 extern "C" void lexls_internal_arm_resume(lexls_lse_t h);                                            // lexls_capi.hip
 extern "C" int lexls_internal_resident_fused(lexls_lse_t h, int has_fixed, int count, double tolW, double tolC, const void *resident_args, size_t resident_args_bytes); // lexls_capi.hip
+extern "C" const double *lexls_internal_multipliers(lexls_lse_t h, int *swept);                        // lexls_capi.hip
+extern "C" void lexls_internal_set_error(const char *msg);                                             // lexls_capi.hip
+extern "C" int lexls_internal_kernel_policy(lexls_lse_t h);                                           // lexls_capi.hip
 #include "lqr_wave_common.h" // wave_max
 
 namespace
@@ -901,6 +904,31 @@ namespace
     };
 } // namespace
 
+namespace
+{
+    /// getLambda's last loop (lexlsi.h:592-604) for a whole group: the rows of the multiplier matrices (lexls_lse_multipliers: B x nObjL x ldo,
+    /// row r = r-th active constraint in working-set order, simple bounds first) go to the user's order — instance b's output is total x nObj,
+    /// column-major, column off + k = LexLSE objective k, column 0 zero when objective 0 holds simple bounds, inactive rows zero.
+    /// One workgroup per instance, lane = active constraint; map = [nact (B) | pos (B x total): user row of active constraint r].
+    __global__ __launch_bounds__(64) void lsi_lambda_scatter_kernel(const double *__restrict__ mult, const uint32_t *__restrict__ map, uint32_t B, uint32_t total,
+                                                                    uint32_t nObj, uint32_t nObjL, uint32_t off, uint32_t ldo, double *__restrict__ out)
+    {
+        const uint32_t b = blockIdx.x;
+        double *o        = out + (size_t)b * total * nObj;
+        for (uint32_t i = threadIdx.x; i < total * nObj; i += blockDim.x) o[i] = 0.0;
+        __syncthreads();
+        const uint32_t na   = min(map[b], min(total, ldo));
+        const uint32_t *pos = map + B + (size_t)b * total;
+        const double *m     = mult + (size_t)b * nObjL * ldo;
+        for (uint32_t r = threadIdx.x; r < na; r += blockDim.x)
+        {
+            const uint32_t u = pos[r];
+            if (u >= total) continue;
+            for (uint32_t k = 0; k < nObjL; k++) o[u + (size_t)(off + k) * total] = m[(size_t)k * ldo + r];
+        }
+    }
+} // namespace
+
 /// A lock-step batch that outlives one solve (the reference constructs a LexLSI once and feeds it successive problems, lexlsi.h:56-112):
 /// device buffers, pinned blocks, streams and the worker pool are made once; every run() re-reads the problem data.
 struct lexls_lsi_batch_s
@@ -918,6 +946,31 @@ struct lexls_lsi_batch_s
     bool resident_ok = false;
     double t_create = 0.0;
     int32_t last_stats[4] = {0, 0, 0, 0}; // of the last run: factorize+solve stages, sensitivity stages, stages with the step on the device, groups
+    // ---- getLambda of the last run (lexls_lsi_batch_get_lambda, lexlsi.h:552-605) ----
+    // What the run leaves behind for it: every instance's final working set in working-set order and its active simple bounds (variable and
+    // bound value, the fixed variables of formLexLSE, objective.h:255-272); the general rows are gathered from the constraint data that stays
+    // resident in the group handles.  lam_rc: -1 no run yet (or the last one failed), LEXLS_OK, or the code get_lambda returns (lam_msg).
+    int lam_rc = -1;
+    std::string lam_msg;
+    double lam_tol = 1e-12;           // tol_linear_dependence of that run (the factorizations of getLambda use it, as the reference's do)
+    std::vector<uint32_t> data_off;   // per objective: offset of its block in one instance's constraint data
+    std::vector<uint16_t> ws_na;      // batch x nObj: active constraints per objective
+    std::vector<uint16_t> ws_idx;     // batch x total: per objective (from its first row on) the active constraints in working-set order
+    std::vector<uint8_t> ws_type;     // batch x total: their activation types
+    std::vector<uint32_t> ws_fixvar;  // batch x dims[0] (simple bounds only): variables of the active simple bounds, working-set order
+    std::vector<double> ws_fixval;    // batch x dims[0]: the bound each one is fixed at
+    struct LambdaBufs                 // per group, made at the first get_lambda
+    {
+        Pinned<uint32_t> map;         // [nact (B) | pos (B x total)]
+        uint32_t *d_map = NULL;
+        double *d_out   = NULL;       // B x total x nObj
+        ~LambdaBufs()
+        {
+            if (d_map) (void)hipFree(d_map);
+            if (d_out) (void)hipFree(d_out);
+        }
+    };
+    std::vector<std::unique_ptr<LambdaBufs>> lam_bufs;
 
     lexls_lsi_batch_s(int device_, uint32_t batch_, uint32_t nVar_, uint32_t nObj_, const uint32_t *h_dims, const int32_t *h_types)
     : device(device_), batch(batch_), nVar(nVar_), nObj(nObj_)
@@ -929,8 +982,17 @@ struct lexls_lsi_batch_s
         if (nObj - off == 0) throw Exception("Problems consisting of one level of simple bounds are not supported."); // lexlsi.cpp:417
         for (uint32_t k = 0; k < nObj; k++)
         {
+            data_off.push_back(static_cast<uint32_t>(per_data));
             per_data += (size_t)h_dims[k] * (h_types[k] == 1 ? 2 : nVar + 2);
             total += h_dims[k];
+        }
+        ws_na.assign((size_t)batch * nObj, 0);
+        ws_idx.assign((size_t)batch * total, 0);
+        ws_type.assign((size_t)batch * total, 0);
+        if (off)
+        {
+            ws_fixvar.assign((size_t)batch * h_dims[0], 0);
+            ws_fixval.assign((size_t)batch * h_dims[0], 0.0);
         }
         const double t_begin = BatchCtx::now();
         // The instances can be split into groups that take turns: while one group's stage runs on the GPU (its own stream), the host
@@ -1014,10 +1076,180 @@ struct lexls_lsi_batch_s
         t_create = BatchCtx::now() - t_begin;
     }
 
+    /// instance b's final working set from its host objects (workingset.h order)
+    template <class LSI>
+    void keep_working_set(uint32_t b, const LSI &inst, const double *data, const uint32_t *var_index)
+    {
+        const std::vector<internal::Objective> &obj = inst.getObjectives();
+        uint32_t first = 0;
+        for (uint32_t k = 0; k < nObj; k++)
+        {
+            const uint32_t na = static_cast<uint32_t>(obj[k].getActiveCtrCount());
+            ws_na[(size_t)b * nObj + k] = static_cast<uint16_t>(na);
+            for (uint32_t a = 0; a < na; a++)
+            {
+                ws_idx[(size_t)b * total + first + a]  = static_cast<uint16_t>(obj[k].getActiveCtrIndex(a));
+                ws_type[(size_t)b * total + first + a] = static_cast<uint8_t>(obj[k].getActiveCtrType(a));
+            }
+            first += dims[k];
+        }
+        keep_fixed(b, data, var_index);
+    }
+    /// the same from the resident slabs a run downloaded (lists in working-set order, types by constraint)
+    void keep_working_set_resident(uint32_t b, BatchCtx &ctx, uint32_t k, const double *data, const uint32_t *var_index)
+    {
+        const char *base   = ctx.rws_host.data();
+        const uint8_t *cs  = reinterpret_cast<const uint8_t *>(base) + (size_t)k * total;
+        const uint16_t *act = reinterpret_cast<const uint16_t *>(base + ctx.r_act) + (size_t)k * total;
+        const uint16_t *na  = reinterpret_cast<const uint16_t *>(base + ctx.r_na) + (size_t)k * STEP_MAX_OBJ;
+        uint32_t first = 0;
+        for (uint32_t o = 0; o < nObj; o++)
+        {
+            ws_na[(size_t)b * nObj + o] = na[o];
+            for (uint32_t a = 0; a < na[o]; a++)
+            {
+                ws_idx[(size_t)b * total + first + a]  = act[first + a];
+                ws_type[(size_t)b * total + first + a] = cs[first + act[first + a]];
+            }
+            first += dims[o];
+        }
+        keep_fixed(b, data, var_index);
+    }
+    /// fixVariable(var, bound) of formLexLSE for the active simple bounds (objective.h:257-271): lb, or ub for CTR_ACTIVE_UB / CTR_ACTIVE_EQ
+    void keep_fixed(uint32_t b, const double *data, const uint32_t *var_index)
+    {
+        if (!off) return;
+        const uint32_t d0 = dims[0], na = ws_na[(size_t)b * nObj];
+        for (uint32_t a = 0; a < na && a < d0; a++)
+        {
+            const uint32_t c = ws_idx[(size_t)b * total + a];
+            ws_fixvar[(size_t)b * d0 + a] = var_index ? var_index[c] : 0u;
+            ws_fixval[(size_t)b * d0 + a] = ws_type[(size_t)b * total + a] == CTR_ACTIVE_LB ? data[c] : data[d0 + c];
+        }
+    }
+
+    /// LexLSI::getLambda (lexlsi.h:552-605) for every instance of the last run, on the device in each group's stream: the final equality
+    /// problems are formed (rows gathered by reference, fixed variables posted), factorized with the factor kept on a bit-exact kernel, all
+    /// objectives' multipliers taken in one sweep (lexls_lse_multipliers), scattered into the user's order, one copy back per group
+    int get_lambda(double *h_lambda)
+    {
+        if (lam_rc < 0) throw Exception("lexls_lsi_batch_get_lambda: no completed lexls_lsi_batch_run on this batch");
+        if (lam_rc != LEXLS_OK)
+        {
+            lexls_internal_set_error(lam_msg.c_str());
+            return lam_rc;
+        }
+        if (!h_lambda) throw Exception("lexls_lsi_batch_get_lambda: null output");
+        const uint32_t nObjL = nObj - off, d0 = off ? dims[0] : 0u;
+        if (lam_bufs.empty())
+        {
+            lam_bufs.resize(nGroups);
+            for (uint32_t g = 0; g < nGroups; g++)
+            {
+                lam_bufs[g].reset(new LambdaBufs());
+                LambdaBufs &lb    = *lam_bufs[g];
+                const size_t Bg   = grp[g]->B;
+                lb.map.assign(Bg + Bg * total, 0u);
+                if (hipSetDevice(device) != hipSuccess || hipMalloc((void **)&lb.d_map, 4 * (Bg + Bg * total)) != hipSuccess ||
+                    hipMalloc((void **)&lb.d_out, 8 * Bg * total * nObj) != hipSuccess)
+                    throw Exception("hipMalloc failed (lexls_lsi_batch_get_lambda)");
+            }
+        }
+        // LEXLS_LSI_TIMING: the stages one by one (a synchronisation behind each) and their times on stderr
+        const bool timing = std::getenv("LEXLS_LSI_TIMING") != nullptr;
+        double ts[4] = {0, 0, 0, 0}, tp = BatchCtx::now();
+        auto stage = [&](int i, BatchCtx &c) {
+            if (!timing) return;
+            hip_check(lexls_lse_synchronize(c.h));
+            const double t = BatchCtx::now();
+            ts[i] += t - tp;
+            tp = t;
+        };
+        for (uint32_t g = 0; g < nGroups; g++)
+        {
+            BatchCtx &ctx  = *grp[g];
+            LambdaBufs &lb = *lam_bufs[g];
+            // the in block of the final equality problems (lexls_lse_round_layout), as formLexLSE posts them (objective.h:255-294)
+            pool->run(ctx.B, [&](uint32_t k) {
+                const uint32_t b  = lo[g] + k;
+                const uint16_t *na = ws_na.data() + (size_t)b * nObj;
+                const uint16_t *ix = ws_idx.data() + (size_t)b * total;
+                const uint8_t *ty  = ws_type.data() + (size_t)b * total;
+                uint32_t *pos      = lb.map.data() + ctx.B + (size_t)k * total;
+                uint32_t r = 0, row = 0, first = 0;
+                const uint32_t nf = off ? std::min<uint32_t>(na[0], nVar) : 0u; // (formLexLSE fixes each variable once: at most nVar, lexlse.h:1453)
+                ctx.nfixed[k]     = nf;
+                for (uint32_t a = 0; a < nf; a++)
+                {
+                    ctx.fixed_idx[(size_t)k * nVar + a]  = ws_fixvar[(size_t)b * d0 + a];
+                    ctx.fixed_val[(size_t)k * nVar + a]  = ws_fixval[(size_t)b * d0 + a];
+                    ctx.fixed_type[(size_t)k * nVar + a] = ty[a];
+                    pos[r++]                             = ix[a];
+                }
+                std::fill(ctx.row_ld.begin() + (size_t)k * ctx.cap, ctx.row_ld.begin() + (size_t)(k + 1) * ctx.cap, 0u);
+                if (off) first = dims[0];
+                for (uint32_t o = off; o < nObj; o++)
+                {
+                    ctx.dims[(size_t)k * nObjL + (o - off)] = na[o];
+                    for (uint32_t a = 0; a < na[o]; a++)
+                    {
+                        const uint8_t t                      = ty[first + a];
+                        ctx.row_src[(size_t)k * ctx.cap + row] = data_off[o] + ix[first + a];
+                        ctx.row_ld[(size_t)k * ctx.cap + row]  = dims[o] | (t == CTR_ACTIVE_LB ? 0u : 0x80000000u);
+                        ctx.ctr_type[(size_t)k * ctx.cap + row] = t;
+                        row++;
+                        pos[r++] = first + ix[first + a];
+                    }
+                    first += dims[o];
+                }
+                lb.map[k]     = r;
+                ctx.skip[k]   = 0;
+                ctx.objidx[k] = -1;
+            });
+            stage(0, ctx);
+            // the equality solver's parameters of this run, whichever path it took (the one-by-one path of deactivate_first_wrong_sign never set
+            // them on these handles; an earlier run of the batch object may have left a regularization there): lam_rc == LEXLS_OK means unregularized
+            hip_check(lexls_lse_set_tolerance(ctx.h, lam_tol));
+            hip_check(lexls_lse_set_regularization(ctx.h, 0, NULL, 0, 0.0));
+            const int policy = lexls_internal_kernel_policy(ctx.h);
+            hip_check(lexls_lse_set_kernel_policy(ctx.h, 5)); // bit-exact kernels whatever the shape (the factor of the reference's getLambda)
+            int rc = lexls_internal_upload_round_trusted(ctx.h, ctx.in_block.data(), 1);
+            if (rc == LEXLS_OK) rc = lexls_lse_factorize(ctx.h);
+            hip_check(lexls_lse_set_kernel_policy(ctx.h, policy));
+            hip_check(rc);
+            stage(1, ctx);
+            hip_check(lexls_lse_multipliers(ctx.h));
+            stage(2, ctx);
+            const double *d_mult = lexls_internal_multipliers(ctx.h, NULL);
+            if (!d_mult) throw Exception("lexls_lsi_batch_get_lambda: no multipliers");
+            if (hipMemcpyAsync(lb.d_map, lb.map.data(), 4 * ((size_t)ctx.B + (size_t)ctx.B * total), hipMemcpyHostToDevice, ctx.stream) != hipSuccess)
+                throw Exception("hipMemcpyAsync failed (lexls_lsi_batch_get_lambda)");
+            hipLaunchKernelGGL(lsi_lambda_scatter_kernel, dim3(ctx.B), dim3(64), 0, ctx.stream, d_mult, lb.d_map, ctx.B, (uint32_t)total, nObj, nObjL, off,
+                               nVar + ctx.cap, lb.d_out);
+            if (hipGetLastError() != hipSuccess) throw Exception("lsi_lambda_scatter_kernel launch failed");
+            if (hipMemcpyAsync(h_lambda + (size_t)lo[g] * total * nObj, lb.d_out, 8 * (size_t)ctx.B * total * nObj, hipMemcpyDeviceToHost, ctx.stream) != hipSuccess)
+                throw Exception("hipMemcpyAsync failed (lexls_lsi_batch_get_lambda)");
+            stage(3, ctx);
+        }
+        for (uint32_t g = 0; g < nGroups; g++)
+            if (hipStreamSynchronize(grp[g]->stream) != hipSuccess) throw Exception("lexls_lsi_batch_get_lambda: stream synchronisation failed");
+        if (timing)
+            std::fprintf(stderr, "lexls_lsi_batch_get_lambda: %.4f ms = form the problems (host) %.4f + upload, gather, factorize %.4f + multipliers %.4f + scatter, copy back %.4f (%u groups)\n",
+                         1e3 * (ts[0] + ts[1] + ts[2] + ts[3]), 1e3 * ts[0], 1e3 * ts[1], 1e3 * ts[2], 1e3 * ts[3], nGroups);
+        return LEXLS_OK;
+    }
+
     void run(const double *h_data, const uint32_t *h_var_index, const uint8_t *h_active_guess, const double *h_x0, const double *h_v0,
              const double *h_reg_factors, const ParametersLexLSI &par, double *h_x, int32_t *h_info6, uint8_t *h_active, double *h_v, int32_t *h_rounds2)
     {
         if (!h_data || !h_x) throw Exception("lexls_lsi_batch_run: null data / x");
+        lam_rc  = -1;
+        lam_tol = par.tol_linear_dependence;
+        // getLambda of this run needs the rows gathered from resident constraint data, unrelaxed bounds and unregularized factorizations
+        const int lam_after = (par.cycling_handling_enabled || par.regularization_type != REGULARIZATION_NONE || !gather || total > 65535) ? LEXLS_ERR_UNSUPPORTED : LEXLS_OK;
+        const char *lam_why = par.cycling_handling_enabled ? "lexls_lsi_batch_get_lambda: not available after a run with cycling handling enabled (it relaxes bounds on the host)"
+                              : par.regularization_type != REGULARIZATION_NONE ? "lexls_lsi_batch_get_lambda: not available after a regularized run"
+                                                                                : "lexls_lsi_batch_get_lambda: not available when the constraint data is not resident on the device (or beyond 65535 constraints)";
         if (par.deactivate_first_wrong_sign)
         {
             // The lock-step stages ask the device for ONE removal candidate per instance; this option (lexlsi.h:1089-1103) wants every
@@ -1039,11 +1271,19 @@ struct lexls_lsi_batch_s
                 runner::collect(lsi, p, h_x + (size_t)b * nVar, &info, h_active ? h_active + (size_t)b * total : NULL, h_v ? h_v + (size_t)b * total : NULL);
                 if (h_info6) std::memcpy(h_info6 + (size_t)b * 6, &info, sizeof(info));
                 fs += info.factorizations;
+                keep_working_set(b, lsi, p.data, p.var_index);
             }
             last_stats[0] = fs;
             last_stats[1] = last_stats[2] = 0;
             last_stats[3] = 1;
             if (h_rounds2) h_rounds2[0] = fs, h_rounds2[1] = 0;
+            // (these instances never used the group handles: the constraint data getLambda gathers from goes there now — one copy of the batch's
+            // data per run, asked for or not: the caller's array is gone when get_lambda comes, and this path solves its instances one by one,
+            // milliseconds each, against ~1 ms per 16 MB for the copy)
+            if (lam_after == LEXLS_OK && (!off || h_var_index))
+                for (uint32_t g = 0; g < nGroups; g++) hip_check(lexls_lse_set_constraint_data(grp[g]->h, h_data + (size_t)lo[g] * per_data, per_data));
+            lam_rc  = (off && !h_var_index) ? LEXLS_ERR_INVALID : lam_after;
+            lam_msg = lam_rc == LEXLS_ERR_INVALID ? "lexls_lsi_batch_get_lambda: the run had no variable indices" : lam_why;
             return;
         }
         const uint32_t *h_dims = dims.data();
@@ -1293,6 +1533,7 @@ struct lexls_lsi_batch_s
                     if (h_v) std::copy(st + nVar, st + nVar + total, h_v + (size_t)b * total);
                     if (h_active) std::copy(ctx.r_ctr_state(k), ctx.r_ctr_state(k) + total, h_active + (size_t)b * total);
                     if (h_info6) std::memcpy(h_info6 + (size_t)b * 6, ctx.r_info_of(k), 6 * sizeof(int32_t));
+                    keep_working_set_resident(b, ctx, k, prob[b].data, prob[b].var_index);
                     return;
                 }
             }
@@ -1300,6 +1541,7 @@ struct lexls_lsi_batch_s
             runner::collect(*lsi[b], prob[b], h_x + (size_t)b * nVar, &info, h_active ? h_active + (size_t)b * total : NULL,
                             h_v ? h_v + (size_t)b * total : NULL);
             if (h_info6) std::memcpy(h_info6 + (size_t)b * 6, &info, sizeof(info));
+            keep_working_set(b, *lsi[b], prob[b].data, prob[b].var_index);
             if (run_step)
             {
                 BatchCtx &ctx    = *grp[group_of[b]];
@@ -1347,6 +1589,8 @@ struct lexls_lsi_batch_s
             h_rounds2[1] = rounds_sens;
         }
         last_stats[0] = rounds_fs, last_stats[1] = rounds_sens, last_stats[2] = rounds_step, last_stats[3] = (int32_t)nGroups;
+        lam_rc  = lam_after;
+        lam_msg = lam_why;
         bool any_left = false;
         for (uint32_t b = 0; b < batch && !any_left; b++) any_left = lsi[b] != nullptr;
         if (any_left) pool.run(batch, [&](uint32_t b) { lsi[b].reset(); }); // a thousand LexLSI objects (dozens of vectors each): freed in parallel, not serially on return
@@ -1413,6 +1657,33 @@ extern "C"
             lexls_internal_set_error(e.what());
             return LEXLS_ERR_INVALID;
         }
+    }
+
+    int lexls_lsi_batch_get_lambda(lexls_lsi_batch_t b, double *h_lambda)
+    {
+        try
+        {
+            if (!b) throw Exception("lexls_lsi_batch_get_lambda: null handle");
+            return b->get_lambda(h_lambda);
+        }
+        catch (const std::exception &e)
+        {
+            lexls_internal_set_error(e.what());
+            return LEXLS_ERR_INVALID;
+        }
+    }
+
+    int lexls_lsi_batch_solve_ex2(int device, uint32_t batch, uint32_t nVar, uint32_t nObj, const uint32_t *h_dims, const int32_t *h_types,
+                                  const double *h_data, const uint32_t *h_var_index, const uint8_t *h_active_guess, const double *h_x0,
+                                  const double *h_reg_factors, const double *h_params, uint32_t nparams, double *h_x, int32_t *h_info6,
+                                  uint8_t *h_active, double *h_v, int32_t *h_rounds2, double *h_lambda)
+    {
+        lexls_lsi_batch_t b = NULL;
+        int rc              = lexls_lsi_batch_create(&b, device, batch, nVar, nObj, h_dims, h_types);
+        if (rc == LEXLS_OK) rc = lexls_lsi_batch_run(b, h_data, h_var_index, h_active_guess, h_x0, NULL, h_reg_factors, h_params, nparams, h_x, h_info6, h_active, h_v, h_rounds2);
+        if (rc == LEXLS_OK && h_lambda) rc = lexls_lsi_batch_get_lambda(b, h_lambda);
+        lexls_lsi_batch_destroy(b);
+        return rc;
     }
 
     int lexls_lsi_batch_solve_ex(int device, uint32_t batch, uint32_t nVar, uint32_t nObj, const uint32_t *h_dims, const int32_t *h_types,

@@ -74,8 +74,12 @@ namespace lexls
 
         constexpr int SWEEP_MD = 16, SWEEP_T = 2; // rows per level; objective registers per DPP row (4 rows x 2 = 8 objectives)
 
-        template <int MD> // rows per level the unrolled reflector loops cover (12 for the IK shapes: a quarter fewer wave-uniform tests than 16)
-        __device__ __forceinline__ void sensitivity_sweep_body(const LseArgs &a, const int32_t *obj_index, int32_t obj_all, double tolW, double tolC, int scan_up, const uint32_t b)
+        // EMIT (multipliers_sweep_kernel, lexls_lse_multipliers): the sweep of every objective and nothing else — column L of emit[b] (nObj columns of
+        // nVar + cap, [lambda_fixed; lambda]) receives what the results block below writes for the objective the search stopped at, for every L;
+        // no decisions, no marks, no types written.  EMIT = false is the removal search as it always was.
+        template <int MD, bool EMIT = false> // MD: rows per level the unrolled reflector loops cover (12 for the IK shapes: a quarter fewer wave-uniform tests than 16)
+        __device__ __forceinline__ void sensitivity_sweep_body(const LseArgs &a, const int32_t *obj_index, int32_t obj_all, double tolW, double tolC, int scan_up, const uint32_t b,
+                                                               double *emit = nullptr)
         {
             static_assert(MD <= SWEEP_MD, "row layout: one level row per lane of a 16-lane DPP row");
 #ifdef LEXLS_SWEEP_STAMPS
@@ -284,6 +288,22 @@ namespace lexls
             }
             __syncthreads();
 
+            if constexpr (EMIT)
+            {
+                // getWorkspace().head(nMeaningful) after ObjectiveSensitivity(L), zero beyond (lexlse.h:636-639; lexlsi.h:573-590)
+                const uint32_t ldo = n + cap;
+                uint32_t nLam      = 0;
+                for (int L = oi; L <= last; L++)
+                {
+                    nLam += dims[L];
+                    double *out      = emit + ((size_t)b * nObj + (uint32_t)L) * ldo;
+                    const double *lm = LamAll + (size_t)(L - oi) * cap;
+                    const double *fx = FixAll + (size_t)(L - oi) * n;
+                    for (uint32_t i = lane; i < ldo; i += 64) out[i] = i < nf ? fx[i] : (i < nf + nLam ? lm[i - nf] : 0.0);
+                }
+                return;
+            }
+
             SSTAMP(3)
             // ---- decisions, objective by objective (findDescentDirection, lexlse.h:935-987): sequential semantics — the most negative
             //      sign-adjusted multiplier wins, the first one among equals; marks are in place before the next group is looked at ----
@@ -415,6 +435,13 @@ namespace lexls
         __global__ __launch_bounds__(64) void sensitivity_sweep_kernel(LseArgs a, const int32_t *obj_index, int32_t obj_all, double tolW, double tolC, int scan_up)
         {
             sensitivity_sweep_body<MD>(a, obj_index, obj_all, tolW, tolC, scan_up, blockIdx.x);
+        }
+
+        /// every objective's multipliers of every problem (lexls_lse_multipliers): out = batch x nObj x (nVar + cap)
+        template <int MD>
+        __global__ __launch_bounds__(64) void multipliers_sweep_kernel(LseArgs a, double *out)
+        {
+            sensitivity_sweep_body<MD, true>(a, nullptr, 0, 0.0, 0.0, 1, blockIdx.x, out);
         }
 
         /// dynamic LDS of one sweep: staged factor, Householder scalars, multipliers / right-hand sides / fixed-variable multipliers of 8 objectives, types

@@ -1910,6 +1910,53 @@ namespace lexls
         return hipGetLastError();
     }
 
+    /// every objective's multipliers in one launch (multipliers_sweep_kernel) where the sweep serves the shape — as for the removal search, but
+    /// whatever the batch size: there is no per-objective launch to weigh it against
+    bool multipliers_sweep_serves(const LseArgs &a, uint32_t sweep_level_dim_hint)
+    {
+        return a.reg_type != 7 && sweep_level_dim_hint > 0 && sweep_level_dim_hint <= (uint32_t)SWEEP_MD && a.nObj <= 8 && a.nVar <= 64 &&
+               sweep_lds_bytes(a) <= 64 * 1024 && !std::getenv("LEXLS_SENS_NO_SWEEP");
+    }
+
+    size_t multipliers_scratch_bytes(const LseArgs &a)
+    {
+        const size_t B = a.batch;
+        return 8 * B * ((size_t)a.nVar + a.cap) + 8 * B + 4 * 3 * B + B * ((size_t)a.cap + a.nVar);
+    }
+
+    hipError_t launch_multipliers(const LseArgs &a, double *d_out, uint32_t sweep_level_dim_hint, hipStream_t s, void *d_scratch, bool *swept)
+    {
+        const size_t ldo = (size_t)a.nVar + a.cap;
+        if (multipliers_sweep_serves(a, sweep_level_dim_hint))
+        {
+            if (swept) *swept = true;
+            if (sweep_level_dim_hint <= 12)
+                hipLaunchKernelGGL(multipliers_sweep_kernel<12>, dim3(a.batch), dim3(64), sweep_lds_bytes(a), s, a, d_out);
+            else
+                hipLaunchKernelGGL(multipliers_sweep_kernel<SWEEP_MD>, dim3(a.batch), dim3(64), sweep_lds_bytes(a), s, a, d_out);
+            return hipGetLastError();
+        }
+        if (swept) *swept = false;
+        // one sensitivity_kernel launch per objective, each copied into its column; the launches write the multipliers, decisions and marks into
+        // scratch (the types are copied there first: the handle's own arrays stay as they are, as they do under the sweep)
+        if (!d_scratch) return hipErrorInvalidValue;
+        LseArgs t      = a;
+        const size_t B = a.batch;
+        t.lambda       = static_cast<double *>(d_scratch);
+        t.maxabs       = t.lambda + B * ldo;
+        t.sens         = reinterpret_cast<int32_t *>(t.maxabs + B);
+        t.ctr_type     = reinterpret_cast<uint8_t *>(t.sens + 3 * B);
+        t.fixed_type   = t.ctr_type + B * a.cap;
+        hipError_t e   = hipMemcpyAsync(t.ctr_type, a.ctr_type, B * a.cap, hipMemcpyDeviceToDevice, s);
+        if (e == hipSuccess) e = hipMemcpyAsync(t.fixed_type, a.fixed_type, B * a.nVar, hipMemcpyDeviceToDevice, s);
+        for (uint32_t k = 0; k < a.nObj && e == hipSuccess; k++)
+        {
+            e = launch_sensitivity(t, nullptr, (int32_t)k, 1e-8, 1e-12, s, false, 0);
+            if (e == hipSuccess) e = hipMemcpy2DAsync(d_out + k * ldo, 8 * ldo * a.nObj, t.lambda, 8 * ldo, 8 * ldo, B, hipMemcpyDeviceToDevice, s);
+        }
+        return e;
+    }
+
     hipError_t launch_leastnorm(const LseArgs &a, hipStream_t s)
     {
         const size_t lds = 8 * (2 * (size_t)a.nVar + 4);

@@ -234,6 +234,14 @@ class BatchedLexLSE:
         capi.check(capi.lib().lexls_lse_get_lambda(self._h, _ptr(lam, C.c_double)))
         return lam
 
+    def multipliers(self):
+        """every objective's multipliers on the current factor (lexls_lse_multipliers + lexls_lse_get_multipliers): (batch, nObj, nVar+cap),
+        row k of problem b = getWorkspace() after ObjectiveSensitivity(k) — zero from nfixed + dims[0] + ... + dims[k] on"""
+        capi.check(capi.lib().lexls_lse_multipliers(self._h))
+        L = np.zeros((self.batch, self.nObj, self.nVar + self.cap))
+        capi.check(capi.lib().lexls_lse_get_multipliers(self._h, _ptr(L, C.c_double)))
+        return L
+
     def getCtrType(self):
         t = np.zeros((self.batch, self.cap), np.uint8)
         capi.check(capi.lib().lexls_lse_get_ctr_type(self._h, _ptr(t, C.c_uint8)))

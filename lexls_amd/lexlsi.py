@@ -286,14 +286,32 @@ class LsiBatch:
         return dict(x=x, info=InfoRows(info), active=active, v=v,
                     rounds=dict(factorize_solve=int(rounds[0]), sensitivity=int(rounds[1])), dims=self.dims)
 
+    def lambda_array(self) -> np.ndarray:
+        """getLambda of every instance of the last run (lexls_lsi_batch_get_lambda): (batch, nObj, total) — instance b's total x nObj
+        column-major matrix, row = constraint in the user's order (objectives stacked), column = objective"""
+        lam = np.zeros((self.batch, len(self.dims), self.total))
+        capi.check(capi.lib().lexls_lsi_batch_get_lambda(self._h, _p(lam, C.c_double)))
+        return lam
 
-def lsi_batch_solve(nvar: int, problems, active_guess=None, x0=None, device: int = 0, regularization_factors=None, **params):
+    def lambdas(self):
+        """per instance the list of per-objective (dim_k x nObj) multiplier matrices that frontend.lexlsi(..., debug=True) returns as
+        d["lambda"] (LexLSI::getLambda, lexlsi.h:552-605), for the last run"""
+        lam = self.lambda_array()
+        cuts = np.cumsum(self.dims)[:-1]
+        return [np.split(np.ascontiguousarray(m.T), cuts) for m in lam]
+
+
+def lsi_batch_solve(nvar: int, problems, active_guess=None, x0=None, device: int = 0, regularization_factors=None, with_lambda: bool = False, **params):
     """Lock-step batch of LexLSI problems of one structure (BASELINE configs[4]).  `problems`: list of objective lists
     (same dims / types) or a PackedBatch; `active_guess`: per problem list of per-objective flag arrays, a (batch, total) uint8
-    array, or None; `x0`: (batch, nvar) or None.  One-shot form of LsiBatch (create + run + destroy)."""
+    array, or None; `x0`: (batch, nvar) or None.  One-shot form of LsiBatch (create + run + destroy).  with_lambda: the result also
+    has "lambda", per instance the matrices of LsiBatch.lambdas()."""
     pk = problems if isinstance(problems, PackedBatch) else pack_batch(nvar, problems)
     b = LsiBatch(nvar, pk.dims, pk.types, pk.batch, device=device)
     try:
-        return b.run(pk, active_guess=active_guess, x0=x0, regularization_factors=regularization_factors, **params)
+        r = b.run(pk, active_guess=active_guess, x0=x0, regularization_factors=regularization_factors, **params)
+        if with_lambda:
+            r["lambda"] = b.lambdas()
+        return r
     finally:
         b.close()
