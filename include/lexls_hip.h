@@ -306,7 +306,9 @@ int lexls_lsi_batch_solve(int device, uint32_t batch, uint32_t nVar, uint32_t nO
                           const double *h_params9, double *h_x, int32_t *h_info6, uint8_t *h_active, double *h_v, int32_t *h_rounds2);
 /* lexls_lsi_batch_solve with the regularization inputs of lexls_lsi_solve_ex: h_reg_factors = one factor per objective, shared by the batch,
  * or NULL; h_params with nparams == 9 or 12 (+ regularization_type, variable_regularization_factor, max_number_of_CG_iterations).
- * Regularized batches run their factorizations on the generic kernel. */
+ * Regularized batches (every regularization_type but the experimental 7) run their active-set iterations resident on the device like plain ones,
+ * on the REG instantiations of the register-resident l-QR where the shape has one ("How a run executes" below); type 7 and the other shapes
+ * keep the host-driven lock-step stages, their factorizations on the generic kernel. */
 int lexls_lsi_batch_solve_ex(int device, uint32_t batch, uint32_t nVar, uint32_t nObj, const uint32_t *h_dims, const int32_t *h_types,
                              const double *h_data, const uint32_t *h_var_index, const uint8_t *h_active_guess, const double *h_x0,
                              const double *h_reg_factors, const double *h_params, uint32_t nparams, double *h_x, int32_t *h_info6,
@@ -331,6 +333,14 @@ int lexls_lsi_batch_run(lexls_lsi_batch_t b, const double *h_data, const uint32_
  * nVar + 1 <= 41 with levels of up to 12 rows, nVar + 1 <= 64 with levels of up to 16 — except 42..48 columns), everything behind the first resident
  * stage is ONE launch: per instance l-QR -> step -> removal search behind an unblocked step -> working-set change, until the instance stops
  * (LEXLS_LSI_NO_FUSED=1, read per run: three launches per lock-step stage instead; same results bit for bit).
+ * A regularized run (regularization_type 1..6, 8, 9) takes the same route: its regularization — type, variable factor, CG iteration bound and one
+ * factor per LexLSE level (objective k + 1's for level k when objective 0 holds simple bounds, which become fixed variables and are not
+ * regularized) — is put on the device once per run, in every group's stream, and the l-QR of an iteration is the regularized instantiation of the
+ * register-resident kernel, inside the persistent launch or as the stage's l-QR launch.  Such an iteration refactorizes every level (the
+ * null-space basis the damping reads accumulates over the levels: no prefix reuse).  Where the regularization routines' LDS does not fit the
+ * persistent launch's 64 KB the stages are taken, where it does not fit a workgroup at all the host path.  Host path as before, whatever the
+ * type: regularization_type 7, cycling handling, deactivate_first_wrong_sign, shapes without a register-resident kernel.
+ * lexls_lsi_batch_stats:
  * of the last lexls_lsi_batch_run: {factorize+solve stages, sensitivity stages, stages whose iteration step ran on the device, groups}.
  * The step of an iteration (A*dx, ratio test, update of x / v / A*x: lexlsi.h:987-1029, :1234-1240) runs on the device
  * next to the equality solve when the batch is created with LEXLS_LSI_DEVICE_STEP=1 in the environment; off by default. */
@@ -383,6 +393,12 @@ int lexls_lsi_solve_debug(int device, uint32_t nVar, uint32_t nObj, const uint32
  * `#Solution` block when present (may be NULL).  one_based: simple-bound indices in the file are 1-based. */
 int lexls_lsi_solve_dat(int device, const char *path, int one_based, int use_active_guess, int use_x_guess, double *h_x, int32_t *h_info6,
                         double *h_solution);
+/* The kernel that served the resident active-set iterations of the LAST lexls_lsi_batch_run on this batch (a string the library owns):
+ * "lsi_fused<lqr_wave<41,12,exact>>", "lsi_fused<lqr_wave<41,12,regularized>>", ... for the persistent launch; the l-QR kernel of the last
+ * lock-step stage ("lqr_wave<41,12,regularized>", "lqr_quad<3,12,factor,fixed>", ...) where the stages ran (LEXLS_LSI_NO_FUSED=1, or no
+ * persistent instantiation); "host" when no instance's iterations were resident (LEXLS_LSI_RESIDENT=0, regularization_type 7, cycling handling,
+ * deactivate_first_wrong_sign, every instance done in phase 1); "" before the first run. */
+const char *lexls_lsi_batch_last_kernel(lexls_lsi_batch_t b);
 
 #ifdef __cplusplus
 }

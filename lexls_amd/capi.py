@@ -29,6 +29,7 @@ SYMBOLS = [
     "lexls_lse_set_prefix_reuse", "lexls_lse_prefix_reuse_ready", "lexls_lse_set_resume_levels",
     "lexls_lsi_solve", "lexls_lsi_solve_dat", "lexls_lsi_batch_solve",
     "lexls_lse_multipliers", "lexls_lse_get_multipliers", "lexls_lsi_batch_get_lambda", "lexls_lsi_batch_solve_ex2",
+    "lexls_lsi_batch_last_kernel",
 ]
 
 ARRAY = dict(x=0, factor=1, hh=2, perm=3, rank=4, first_col=5, total_rank=6, v=7, lam=8, input=9, guard_estimate=10, guard_status=11,
@@ -52,6 +53,8 @@ def lib() -> C.CDLL:
         _lib.lexls_last_error.restype = C.c_char_p
         _lib.lexls_lse_last_kernel.restype = C.c_char_p
         _lib.lexls_lse_last_kernel.argtypes = [C.c_void_p]
+        _lib.lexls_lsi_batch_last_kernel.restype = C.c_char_p
+        _lib.lexls_lsi_batch_last_kernel.argtypes = [C.c_void_p]
         _lib.lexls_lse_set_accuracy_guard.restype = C.c_int
         _lib.lexls_lse_set_accuracy_guard.argtypes = [C.c_void_p, C.c_int, C.c_double]
         _lib.lexls_lse_get_accuracy.restype = C.c_int

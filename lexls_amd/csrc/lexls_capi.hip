@@ -77,6 +77,7 @@ struct lexls_lse_s
     uint32_t reg_cg_iters;
     double reg_variable;
     double *d_reg_factor, *d_reg_scratch, *d_reg_mu;
+    std::vector<double> reg_stage; // host copy behind the enqueued upload of the regularization factors (set_regularization)
     bool sens_scan; // lexls_lse_set_sensitivity_scan
     // lexls_lse_multipliers: every objective's multipliers (batch x nObj x (nVar + cap)) and the scratch of its per-objective fallback
     double *d_mult        = nullptr;
@@ -316,25 +317,21 @@ extern "C"
         return e;
     }
 
-    int lexls_lse_set_regularization(lexls_lse_t h, int type, const double *h_factors, int per_problem, double variable_factor)
+    /// lexls_lse_set_regularization / lexls_internal_set_regularization_block: the factors are staged in the handle (reg_stage) and enqueued in
+    /// its stream; wait: the stream is synchronised before returning
+    static int set_regularization(lexls_lse_t h, int type, const double *h_factors, int per_problem, double variable_factor, bool wait)
     {
-        CHECK_HANDLE(h);
         if ((uint32_t)type != h->reg_type) HIP_TRY(materialize_fused_gather(h));
-        switch (type)
-        {
-        case 0: case 1: case 2: case 3: case 4: case 5: case 6: case 7: case 8: case 9: break;
-        default: return fail(LEXLS_ERR_INVALID, "set_regularization: unknown regularization type");
-        }
         HIP_TRY(hipSetDevice(h->device));
         h->factor_valid = false;
         h->reg_type     = (uint32_t)type;
         h->reg_variable = variable_factor;
         if (type == 0) return LEXLS_OK;
         const size_t B = h->batch, nObj = h->nObj;
-        std::vector<double> f(B * nObj, 0.0);
+        h->reg_stage.assign(B * nObj, 0.0);
         if (h_factors)
             for (size_t b = 0; b < B; b++)
-                for (size_t k = 0; k < nObj; k++) f[b * nObj + k] = per_problem ? h_factors[b * nObj + k] : h_factors[k];
+                for (size_t k = 0; k < nObj; k++) h->reg_stage[b * nObj + k] = per_problem ? h_factors[b * nObj + k] : h_factors[k];
         if (!h->d_reg_factor) HIP_TRY(hipMalloc((void **)&h->d_reg_factor, 8 * B * nObj));
         if (!h->d_reg_scratch)
         {
@@ -348,9 +345,47 @@ extern "C"
             HIP_TRY(hipMalloc((void **)&h->d_reg_mu, bytes));
             HIP_TRY(hipMemsetAsync(h->d_reg_mu, 0, bytes, h->stream));
         }
-        HIP_TRY(hipMemcpyAsync(h->d_reg_factor, f.data(), 8 * B * nObj, hipMemcpyHostToDevice, h->stream));
-        HIP_TRY(hipStreamSynchronize(h->stream)); // f is a temporary
+        HIP_TRY(hipMemcpyAsync(h->d_reg_factor, h->reg_stage.data(), 8 * B * nObj, hipMemcpyHostToDevice, h->stream));
+        if (wait) HIP_TRY(hipStreamSynchronize(h->stream));
         return LEXLS_OK;
+    }
+
+    int lexls_lse_set_regularization(lexls_lse_t h, int type, const double *h_factors, int per_problem, double variable_factor)
+    {
+        CHECK_HANDLE(h);
+        if (type < 0 || type > 9) return fail(LEXLS_ERR_INVALID, "set_regularization: unknown regularization type");
+        return set_regularization(h, type, h_factors, per_problem, variable_factor, true);
+    }
+
+    /* internal (the lock-step LexLSI driver): the regularization of ONE run as a block that stays on the device for its length — the type, the
+     * variable factor and the CG iteration bound (they travel in every launch's argument block) and one factor per LexLSE level, the same for
+     * every problem of the batch, in the array the kernels read (batch x nObj).  What lexls_lse_set_regularization + lexls_lse_set_cg_iterations
+     * set, but only ENQUEUED in the handle's stream: nothing is waited for (the staging copy lives in the handle; the caller synchronises the
+     * stream before the next call, as every run of the driver does when it downloads its results).  Also drops what prefix reuse kept: a
+     * regularized factorization reads nothing back and leaves nothing to read back. */
+    int lexls_internal_set_regularization_block(lexls_lse_t h, int type, const double *h_level_factors, double variable_factor, uint32_t cg_iterations)
+    {
+        CHECK_HANDLE(h);
+        if (type < 1 || type > 9) return fail(LEXLS_ERR_INVALID, "set_regularization_block: regularization type outside 1 .. 9");
+        h->resume_valid = false;
+        h->resume_armed = false;
+        h->reg_cg_iters = cg_iterations;
+        return set_regularization(h, type, h_level_factors, 0, variable_factor, false);
+    }
+
+    /* internal (the lock-step LexLSI driver): can the resident iterations of this handle's batch run under regularization `type`?  Every type
+     * the REG instantiations of the register-resident wave kernel serve (all but the experimental type 7) on the shapes that kernel takes, as
+     * long as the l-QR image plus the regularization routines' vectors fit a workgroup's LDS (their work matrix and the null-space basis are
+     * optional there).  Decided from the capacities given at creation: nothing is launched, nothing changes. */
+    int lexls_internal_resident_reg_serves(lexls_lse_t h, int type)
+    {
+        if (!h || type < 1 || type > 9 || h->force_generic == 1) return 0;
+        uint32_t max_level = 0;
+        for (uint32_t v : h->maxdim) max_level = v > max_level ? v : max_level;
+        LseArgs a  = h->args();
+        a.reg_type = (uint32_t)type;
+        if (!wave_kernel_supports(a, h->cap ? h->cap : 1, max_level, true)) return 0;
+        return wave_reg_kernel_fits(a, max_level) ? 1 : 0;
     }
 
     int lexls_lse_set_cg_iterations(lexls_lse_t h, uint32_t max_iterations)
@@ -605,7 +640,8 @@ extern "C"
         // behind a gather launch is ahead of it at every batch size (1024 instances, n = 47, 5 x 12, cold: 21.3 -> 17.1 ms)
         const bool wide_slot = h->nVar + 1 > 41 && h->nVar + 1 <= 48 && h->max_level_dim <= 12;
         const int ll = h->force_generic == 3 ? 1 : (h->force_generic == 4 ? 2 : (wide_slot && h->force_generic == 0 ? 0 : -1));
-        if (h->force_generic != 1 && h->reg_type == 0 && wave_kernel_supports(h->args(), h->max_rows, h->max_level_dim, h->has_fixed) &&
+        // (a regularized round: the REG instantiation of that kernel, the same load; type 7 has none, wave_kernel_supports)
+        if (h->force_generic != 1 && wave_kernel_supports(h->args(), h->max_rows, h->max_level_dim, h->has_fixed) &&
             wave_dispatch_is_register_resident(h->args(), h->max_level_dim, h->has_fixed, ll))
             h->fused_gather = true;
         else
@@ -622,12 +658,13 @@ extern "C"
     {
         CHECK_HANDLE(h);
         if (!h->d_cdata || !h->d_in_owned) return fail(LEXLS_ERR_INVALID, "resident_fused: needs resident constraint data and one uploaded round");
-        if (h->force_generic != 0 || h->reg_type != 0 || std::getenv("LEXLS_LSI_NO_FUSED")) return 1;
+        if (h->force_generic != 0 || std::getenv("LEXLS_LSI_NO_FUSED")) return 1;
+        const bool reg = h->reg_type != 0; // the launch with the regularized l-QR: no prefix reuse (lqr_small_impl.h), so no resume levels either way
         HIP_TRY(hipSetDevice(h->device));
         // what lexls_internal_round_resident would set — on a copy of the fields first: nothing changes when the launch is not taken
         uint32_t max_level = 0;
         for (uint32_t v : h->maxdim) max_level = v > max_level ? v : max_level;
-        if (h->nVar + 1 > 41 && h->nVar + 1 <= 48 && max_level <= 12) return 1; // (42..48 columns: the four-per-wavefront kernel behind a gather launch, as lexls_internal_round_resident decides)
+        if (!reg && h->nVar + 1 > 41 && h->nVar + 1 <= 48 && max_level <= 12) return 1; // (42..48 columns: the four-per-wavefront kernel behind a gather launch, as lexls_internal_round_resident decides)
         {
             lexls_lse_s probe    = *h; // (plain fields and pointers; the vectors are copied, the probe owns nothing it frees)
             probe.max_rows       = h->cap ? h->cap : 1;
@@ -638,7 +675,7 @@ extern "C"
             probe.has_skip       = true;
             probe.fused_gather   = true;
             probe.d_in           = h->d_in_owned;
-            probe.resume_armed   = h->resume_enabled;
+            probe.resume_armed   = h->resume_enabled && !reg;
             const LseArgs pa     = probe.args();
             const char *variant  = "";
             if (!wave_kernel_supports(pa, probe.max_rows, max_level, probe.has_fixed)) return 1;
@@ -657,7 +694,7 @@ extern "C"
         h->fused_gather  = true;
         h->d_in          = h->d_in_owned;
         h->resume_armed  = false;
-        h->resume_valid  = h->resume_enabled && h->d_resume_state != nullptr;
+        h->resume_valid  = h->resume_enabled && h->d_resume_state != nullptr && !reg;
         h->factor_valid  = true;
         h->factor_epoch++;
         h->x_epoch       = h->factor_epoch;
@@ -1179,7 +1216,8 @@ extern "C"
     }
     /* internal (the lock-step LexLSI driver): the device array its resident iterations write the levels into, and the promise that it holds
      * them for the next factorization */
-    int32_t *lexls_internal_resume_levels(lexls_lse_t h) { return (h && h->resume_enabled) ? h->d_resume_level : nullptr; }
+    /* (NULL under regularization: its factorizations read no levels back, so the resident iterations post none) */
+    int32_t *lexls_internal_resume_levels(lexls_lse_t h) { return (h && h->resume_enabled && h->reg_type == 0) ? h->d_resume_level : nullptr; }
     void lexls_internal_arm_resume(lexls_lse_t h)
     {
         if (h && h->resume_enabled) h->resume_armed = true;

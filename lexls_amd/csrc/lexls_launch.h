@@ -32,6 +32,8 @@ namespace lexls
     bool wave_kernel_supports(const LseArgs &a, uint32_t max_rows, uint32_t max_level_dim, bool has_fixed);
     bool deep_kernel_supports(const LseArgs &a, uint32_t max_level_dim, bool write_factor, bool has_fixed);
     bool wave_dispatch_is_register_resident(const LseArgs &a, uint32_t max_level_dim, bool has_fixed, int left_looking);
+    bool wave_reg_kernel_fits(const LseArgs &a, uint32_t max_level_dim);
+    size_t wave_reg_lds_share();
     /// tolerance: x-only solves of the shapes lqr_mfma_impl.h / lqr_qtol_impl.h serve may take those kernels (pivots / ranks exact, x within 1e-10
     /// instead of bit-identical to the oracle).  0 = bit-exact kernels only; 1 = automatic (lqr_mfma where it serves, else lqr_qtol); 6 = lqr_qtol
     /// only; 7 / 8 = lqr_mfma with two / one problem per wavefront, else lqr_qtol
@@ -57,7 +59,8 @@ namespace lexls
     /// kernel's body, rows gathered by reference) -> removal sweep -> iteration, per instance until it stops or `count` iterations are done.
     /// resident_args: the driver's ResidentArgs (lexls_lsi_device.h).  hipErrorNotSupported: the shape has no persistent instantiation (the caller
     /// enqueues the three kernels per stage instead); the conditions are those under which launch_lqr_wave(a, ..., factor kept, left_looking < 0)
-    /// takes the same register-resident instantiation and launch_sensitivity the sweep
+    /// takes the same register-resident instantiation and launch_sensitivity the sweep.  a.reg_type != 0: the launch whose l-QR phase is the
+    /// regularized body (every type but 7); a.reg_factor / a.reg_scratch are on the device already; it neither reads nor leaves prefix-reuse state
     hipError_t launch_lsi_fused(const LseArgs &a, uint32_t max_level_dim, bool has_fixed, const int32_t *d_obj_index, double tolW, double tolC, bool scan_up,
                                 const void *resident_args, size_t resident_args_bytes, int count, hipStream_t s, const char **variant);
 

@@ -24,6 +24,8 @@ extern "C" char *lexls_internal_round_in(lexls_lse_t h);                        
 extern "C" int lexls_internal_round_resident(lexls_lse_t h, int has_fixed);                          // lexls_capi.hip
 extern "C" int32_t *lexls_internal_resume_levels(lexls_lse_t h);                                     // lexls_capi.hip
 extern "C" void lexls_internal_arm_resume(lexls_lse_t h);                                            // lexls_capi.hip
+extern "C" int lexls_internal_set_regularization_block(lexls_lse_t h, int type, const double *h_level_factors, double variable_factor, uint32_t cg_iterations); // lexls_capi.hip
+extern "C" int lexls_internal_resident_reg_serves(lexls_lse_t h, int type);                          // lexls_capi.hip
 extern "C" int lexls_internal_resident_fused(lexls_lse_t h, int has_fixed, int count, double tolW, double tolC, const void *resident_args, size_t resident_args_bytes); // lexls_capi.hip
 extern "C" const double *lexls_internal_multipliers(lexls_lse_t h, int *swept);                        // lexls_capi.hip
 extern "C" void lexls_internal_set_error(const char *msg);                                             // lexls_capi.hip
@@ -177,6 +179,7 @@ namespace
         std::vector<int32_t> iterations_at_handover;
         int rounds_fs_at_handover = 0, rounds_sens_at_handover = 0;
         bool fused_all = false, fused_refused = false; // the rest of the resident iterations is one persistent launch / the shape has none
+        const char *resident_kernel = "";              // the kernel that served the resident iterations of this run (download_resident)
         int rounds_fs = 0, rounds_sens = 0, rounds_step = 0;
         double t_enqueue = 0, t_wait = 0; // seconds, reported when LEXLS_LSI_TIMING is set
         static double now() { return std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count(); }
@@ -359,6 +362,7 @@ namespace
                 throw Exception("hipMemcpyAsync failed (resident hand-over)");
             rounds_resident = 0;
             fused_all       = false;
+            fused_refused   = false; // (decided per run: the next one may be of another kind — plain / regularized — or under another LEXLS_LSI_NO_FUSED)
             rounds_fs_at_handover   = rounds_fs;
             rounds_sens_at_handover = rounds_sens;
             iterations_at_handover.assign(B, 0);
@@ -418,6 +422,7 @@ namespace
                 hipMemcpyAsync(rstate_host.data(), d_rstate, 8 * (size_t)B * rshape.SD, hipMemcpyDeviceToHost, stream) != hipSuccess ||
                 hipStreamSynchronize(stream) != hipSuccess)
                 throw Exception("download of the resident state failed");
+            resident_kernel = lexls_lse_last_kernel(h); // the persistent launch, or the l-QR kernel of the last stage
             if (fused_all && std::getenv("LEXLS_FUSED_STAMPS_DUMP")) // (a -DLEXLS_FUSED_STAMPS build leaves its phase clocks in the multiplier buffer)
             {
                 std::vector<double> lam((size_t)B * (n + cap));
@@ -952,6 +957,7 @@ struct lexls_lsi_batch_s
     // resident in the group handles.  lam_rc: -1 no run yet (or the last one failed), LEXLS_OK, or the code get_lambda returns (lam_msg).
     int lam_rc = -1;
     std::string lam_msg;
+    const char *last_kernel = ""; // lexls_lsi_batch_last_kernel: what served the resident iterations of the last run ("host": nothing did)
     double lam_tol = 1e-12;           // tol_linear_dependence of that run (the factorizations of getLambda use it, as the reference's do)
     std::vector<uint32_t> data_off;   // per objective: offset of its block in one instance's constraint data
     std::vector<uint16_t> ws_na;      // batch x nObj: active constraints per objective
@@ -1245,6 +1251,7 @@ struct lexls_lsi_batch_s
         if (!h_data || !h_x) throw Exception("lexls_lsi_batch_run: null data / x");
         lam_rc  = -1;
         lam_tol = par.tol_linear_dependence;
+        last_kernel = "host";
         // getLambda of this run needs the rows gathered from resident constraint data, unrelaxed bounds and unregularized factorizations
         const int lam_after = (par.cycling_handling_enabled || par.regularization_type != REGULARIZATION_NONE || !gather || total > 65535) ? LEXLS_ERR_UNSUPPORTED : LEXLS_OK;
         const char *lam_why = par.cycling_handling_enabled ? "lexls_lsi_batch_get_lambda: not available after a run with cycling handling enabled (it relaxes bounds on the host)"
@@ -1318,6 +1325,28 @@ struct lexls_lsi_batch_s
                 }
             }
         }
+        // whole iterations on the device: plain runs and the regularized ones the register-resident kernel's REG instantiations serve (every
+        // type but the experimental 7).  Cycling handling edits the host's bounds: host path, as every other case
+        const int reg_type      = static_cast<int>(par.regularization_type);
+        const bool run_resident = run_gather && resident_ok && grp[0]->resident && (reg_type == 0 || lexls_internal_resident_reg_serves(grp[0]->h, reg_type)) &&
+                                  par.max_number_of_factorizations < 0x7fffffff;
+        // a regularized resident run: its regularization goes to the device ONCE, as a block in every group's stream — LexLSE level k takes the
+        // factor of objective k + off (a simple-bounds objective 0 becomes fixed variables and has none: lexlsi.h formLexLSE), whatever the level
+        // holds in the working set of the moment.  The host copy the instances post into (SlotLSE::setRegularizationFactor) starts from the
+        // same values, so phase 1 finds nothing to upload again.  (Here, before the constraint data's upload starts on another thread: this call may touch the handles.)
+        if (run_resident && reg_type != 0)
+        {
+            std::vector<double> level_factor(nObj - off, 0.0);
+            if (h_reg_factors)
+                for (uint32_t k = 0; k + off < nObj; k++) level_factor[k] = h_reg_factors[k + off];
+            for (uint32_t g = 0; g < nGroups; g++)
+            {
+                BatchCtx &ctx = *grp[g];
+                hip_check(lexls_internal_set_regularization_block(ctx.h, reg_type, level_factor.data(), ctx.reg_variable, ctx.reg_cg_iters));
+                for (uint32_t b = 0; b < ctx.B; b++) std::copy(level_factor.begin(), level_factor.end(), ctx.reg_factor.begin() + (size_t)b * ctx.nObjL);
+                ctx.reg_dirty.store(false);
+            }
+        }
         // the constraint data goes to the device (16 MB for 1024 IK instances: ~0.4 ms) while the worker pool builds the instances' host
         // objects and runs their phase 1: nothing of that touches the handles; joined before the first stage
         int upload_rc = LEXLS_OK;
@@ -1339,10 +1368,6 @@ struct lexls_lsi_batch_s
                 if (t.joinable()) t.join();
             }
         } joiner{uploader};
-        // whole iterations on the device: plain runs only (cycling handling edits the host's bounds; a regularized equality problem has
-        // per-run factors the host posts)
-        const bool run_resident = run_gather && resident_ok && grp[0]->resident && par.regularization_type == REGULARIZATION_NONE &&
-                                  par.max_number_of_factorizations < 0x7fffffff;
         if (run_resident)
             for (uint32_t g = 0; g < nGroups; g++)
             {
@@ -1508,7 +1533,11 @@ struct lexls_lsi_batch_s
                     }
             }
             for (uint32_t g = 0; g < nGroups; g++)
-                if (grp[g]->n_resident) grp[g]->download_resident();
+                if (grp[g]->n_resident)
+                {
+                    grp[g]->download_resident();
+                    last_kernel = grp[g]->resident_kernel; // (every group takes the same path: same shape, same regularization)
+                }
         }
         if (run_step) // x and v of the instances whose state lives on the device
             for (uint32_t g = 0; g < nGroups; g++)
@@ -1634,6 +1663,8 @@ extern "C"
         std::memcpy(h_stats4, b->last_stats, sizeof(b->last_stats));
         return LEXLS_OK;
     }
+
+    const char *lexls_lsi_batch_last_kernel(lexls_lsi_batch_t b) { return b ? b->last_kernel : ""; }
 
     int lexls_lsi_batch_destroy(lexls_lsi_batch_t b)
     {

@@ -2,6 +2,7 @@
 // translation unit lqr_small_<shape>.hip so that they compile in parallel.
 #include "lexls_kernels.h"
 #include "lexls_launch.h"
+#include "lqr_small_impl.h" // (the launchers' LDS formulas; nothing is instantiated here)
 
 namespace lexls
 {
@@ -13,6 +14,9 @@ namespace lexls
     LEXLS_DECLARE_LSI_FUSED(launch_lsi_fused_41x12e)
     LEXLS_DECLARE_LSI_FUSED(launch_lsi_fused_41x12)
     LEXLS_DECLARE_LSI_FUSED(launch_lsi_fused_64x16)
+    LEXLS_DECLARE_LSI_FUSED(launch_lsi_fused_41x12e_R)
+    LEXLS_DECLARE_LSI_FUSED(launch_lsi_fused_41x12_R)
+    LEXLS_DECLARE_LSI_FUSED(launch_lsi_fused_64x16_R)
 #undef LEXLS_DECLARE_LSI_FUSED
     hipError_t launch_wave_41x12_x(const LseArgs &a, hipStream_t s);
     hipError_t launch_wave_41x12_f(const LseArgs &a, hipStream_t s);
@@ -107,6 +111,26 @@ namespace lexls
         (void)has_fixed; // fixed variables are handled in-kernel
         if (a.reg_type == 7) return false; // the experimental type's by-products need the level lists: generic kernel (lexls_regularize.h)
         return a.nVar + 1 <= 64 && max_rows <= 64 && max_level_dim <= 16 && a.nObj <= 16;
+    }
+
+    /// LDS one wavefront of a REG launch may fill with the regularization routines' optional pieces (work matrix, null-space basis): a CU's LDS
+    /// over LEXLS_REG_LDS_WAVES (1 .. 8, default 8) wavefronts.  Read at the first call and kept for the life of the process.
+    size_t wave_reg_lds_share()
+    {
+        static const size_t share = [] {
+            const char *e = std::getenv("LEXLS_REG_LDS_WAVES");
+            const long w  = e ? std::atol(e) : 8;
+            return kMaxLdsBytes / (size_t)(w < 1 ? 1 : (w > 8 ? 8 : w));
+        }();
+        return share;
+    }
+
+    /// true when the REG instantiation launch_lqr_wave takes for a regularized batch of these capacities gets its LDS (the launcher's own test)
+    bool wave_reg_kernel_fits(const LseArgs &a, uint32_t max_level_dim)
+    {
+        uint32_t reg_cfg = 0;
+        if (max_level_dim <= 12 && a.nVar + 1 <= 41) return wave_reg_lds_bytes<12>(a, wave_lds_bytes<41, 12>(a, wave_img_doubles<12>(a)), reg_cfg) <= kMaxLdsBytes;
+        return wave_reg_lds_bytes<16>(a, wave_lds_bytes<64, 16>(a, wave_img_doubles<16>(a)), reg_cfg) <= kMaxLdsBytes;
     }
 
     /// waves of the register-resident kernel the device holds at once (2 per SIMD): up to that many problems run in ONE round of it
@@ -310,8 +334,24 @@ namespace lexls
                                 const void *resident_args, size_t resident_args_bytes, int count, hipStream_t s, const char **variant)
     {
         const uint32_t nc = a.nVar + 1;
-        if (a.reg_type != 0 || !a.g_cdata || !wave_dispatch_is_register_resident(a, max_level_dim, has_fixed, -1) || !sensitivity_sweep_serves(a, max_level_dim))
+        if (!a.g_cdata || !wave_dispatch_is_register_resident(a, max_level_dim, has_fixed, -1) || !sensitivity_sweep_serves(a, max_level_dim))
             return hipErrorNotSupported;
+        if (a.reg_type != 0) // the regularization family: the launch whose l-QR phase is the REG body (every type the REG wave kernel serves)
+        {
+            if (!wave_kernel_supports(a, a.cap, max_level_dim, has_fixed)) return hipErrorNotSupported;
+            if (max_level_dim <= 12 && nc == 41)
+            {
+                *variant = "lsi_fused<lqr_wave<41,12,exact,regularized>>";
+                return launch_lsi_fused_41x12e_R(a, max_level_dim, d_obj_index, tolW, tolC, scan_up, resident_args, resident_args_bytes, count, s);
+            }
+            if (max_level_dim <= 12 && nc <= 41)
+            {
+                *variant = "lsi_fused<lqr_wave<41,12,regularized>>";
+                return launch_lsi_fused_41x12_R(a, max_level_dim, d_obj_index, tolW, tolC, scan_up, resident_args, resident_args_bytes, count, s);
+            }
+            *variant = "lsi_fused<lqr_wave<64,16,regularized>>";
+            return launch_lsi_fused_64x16_R(a, max_level_dim, d_obj_index, tolW, tolC, scan_up, resident_args, resident_args_bytes, count, s);
+        }
         // (the register-resident instantiation launch_lqr_wave takes for these arguments)
         if (max_level_dim <= 12 && nc == 41)
         {

@@ -7,6 +7,7 @@
 // prologues / epilogues per stage (4.3 us each: the duration of a launch whose instances all skip), the lock step itself (an instance no
 // longer waits for the slowest one of its stage) and the host's chunked enqueue-and-poll.  One wavefront per instance; the phases hand
 // their results over through HBM exactly as the separate kernels do, with a device-scope fence between them.
+// A regularized run (every type but 7) takes lsi_fused_reg_kernel: the same loop with the REG body as its l-QR phase (no prefix reuse there).
 #pragma once
 #include "lqr_small_impl.h"
 #include "lexls_sweep_impl.h"
@@ -40,6 +41,22 @@ namespace lexls
             return *(const FusedArgs *)(FusedArgsPtr)(((unsigned long long)hi << 32) | lo);
         }
 
+        /// the regularized launch: the same block (at offset 0, where the common phases read it) and where the l-QR's regularization routines
+        /// find their LDS (lqr_wave_body's reg_cfg).  The regularization itself — type, variable factor, CG iterations, the factors per level —
+        /// is in the LseArgs, put on the device once per run (lexls_internal_set_regularization_block)
+        struct FusedArgsReg
+        {
+            FusedArgs f;
+            uint32_t reg_cfg;
+        };
+        typedef const FusedArgsReg __attribute__((address_space(4))) *FusedArgsRegPtr;
+        __device__ __forceinline__ const FusedArgsReg &fused_args_reg(unsigned long long kernarg)
+        {
+            const unsigned lo = (unsigned)__builtin_amdgcn_readfirstlane((int)(unsigned)kernarg);
+            const unsigned hi = (unsigned)__builtin_amdgcn_readfirstlane((int)(unsigned)(kernarg >> 32));
+            return *(const FusedArgsReg *)(FusedArgsRegPtr)(((unsigned long long)hi << 32) | lo);
+        }
+
         // the three phases as functions of their own (not inlined): each keeps the register allocation it has as a kernel — inlined into one
         // body they cost 330 spilled scalar registers (two argument structs live across everything) and ran slower than the three launches
         template <int NC, int MD, bool EXACT>
@@ -47,6 +64,14 @@ namespace lexls
         {
             const FusedArgs &fa = fused_args(kernarg);
             lqr_wave_body<NC, MD, EXACT, true, false>(fa.a, fa.img_doubles, 0u, b);
+        }
+        /// the l-QR of a regularized run: the REG body refactorizes every level (its null-space basis accumulates over the levels: no prefix
+        /// reuse, lqr_small_impl.h) — the launch carries neither resume levels nor resume state for it
+        template <int NC, int MD, bool EXACT>
+        __device__ __noinline__ void fused_phase_lqr_reg(unsigned long long kernarg, uint32_t b)
+        {
+            const FusedArgsReg &fr = fused_args_reg(kernarg);
+            lqr_wave_body<NC, MD, EXACT, true, true>(fr.f.a, fr.f.img_doubles, fr.reg_cfg, b);
         }
         template <int SMD>
         __device__ __noinline__ void fused_phase_sweep(unsigned long long kernarg, uint32_t b)
@@ -72,8 +97,9 @@ namespace lexls
 #endif
         }
 
-        template <int NC, int MD, bool EXACT, int SMD>
-        __global__ __launch_bounds__(64, 1) void lsi_fused_kernel(FusedArgs fa)
+        /// the iterations of instance blockIdx.x; REG: the l-QR phase is the regularized body, everything else is the same code
+        template <int NC, int MD, bool EXACT, int SMD, bool REG>
+        __device__ __forceinline__ void lsi_fused_loop(const FusedArgs &fa)
         {
             const uint32_t b                = blockIdx.x;
             const unsigned long long kernarg = (unsigned long long)__builtin_amdgcn_kernarg_segment_ptr(); // (FusedArgs is the only parameter: offset 0)
@@ -88,7 +114,10 @@ namespace lexls
             for (int it = 0; it < fa.count; it++)
             {
                 if (!fa.ra.alive[b]) break; // (wave-uniform; lsi_iterate_body clears it when the instance stops, at the latest after max_factorizations)
-                fused_phase_lqr<NC, MD, EXACT>(kernarg, b);
+                if constexpr (REG)
+                    fused_phase_lqr_reg<NC, MD, EXACT>(kernarg, b);
+                else
+                    fused_phase_lqr<NC, MD, EXACT>(kernarg, b);
                 fused_phase_fence();
                 FUSED_STAMP(0)
                 const StepVerdict verdict = fused_phase_step(kernarg, b);
@@ -122,11 +151,23 @@ namespace lexls
 #undef FUSED_STAMP
         }
 
-        template <int NC, int MD, bool EXACT>
+        template <int NC, int MD, bool EXACT, int SMD>
+        __global__ __launch_bounds__(64, 1) void lsi_fused_kernel(FusedArgs fa)
+        {
+            lsi_fused_loop<NC, MD, EXACT, SMD, false>(fa);
+        }
+        template <int NC, int MD, bool EXACT, int SMD>
+        __global__ __launch_bounds__(64, 1) void lsi_fused_reg_kernel(FusedArgsReg fr)
+        {
+            lsi_fused_loop<NC, MD, EXACT, SMD, true>(fr.f);
+        }
+
+        template <int NC, int MD, bool EXACT, bool REG = false>
         hipError_t launch_lsi_fused_t(const LseArgs &a, uint32_t sweep_level_dim, const int32_t *d_obj_index, double tolW, double tolC, bool scan_up, const void *resident_args,
                                       size_t resident_args_bytes, int count, hipStream_t s)
         {
-            FusedArgs fa;
+            FusedArgsReg fr;
+            FusedArgs &fa = fr.f;
             if (resident_args_bytes != sizeof(fa.ra)) return hipErrorInvalidValue;
             std::memcpy(&fa.ra, resident_args, sizeof(fa.ra));
             fa.a           = a;
@@ -136,16 +177,35 @@ namespace lexls
             fa.img_doubles = wave_img_doubles<MD>(a);
             fa.scan_up     = scan_up ? 1 : 0;
             fa.count       = count;
+            fr.reg_cfg     = 0;
             size_t lds      = wave_lds_bytes<NC, MD>(a, fa.img_doubles);
+            if constexpr (REG) // the regularization routines' LDS behind the l-QR image, by the rule of the stage path's launcher
+            {
+                if (!a.reg_scratch || !a.reg_factor) return hipErrorInvalidValue;
+                fa.a.resume_level = nullptr;
+                fa.a.resume_state = nullptr;
+                fa.ra.resume      = nullptr;
+                lds               = wave_reg_lds_bytes<MD>(a, lds, fr.reg_cfg);
+            }
             const size_t l2 = sweep_lds_bytes(a);
             const size_t l3 = resident_lds_per_wave(fa.ra.sh.SD, fa.ra.sh.total);
             lds             = lds > l2 ? lds : l2;
             lds             = lds > l3 ? lds : l3;
             if (lds > 64 * 1024) return hipErrorNotSupported; // (the caller falls back to the three launches per stage)
-            if (sweep_level_dim <= 12)
-                hipLaunchKernelGGL((lsi_fused_kernel<NC, MD, EXACT, 12>), dim3(a.batch), dim3(64), lds, s, fa);
+            if constexpr (REG)
+            {
+                if (sweep_level_dim <= 12)
+                    hipLaunchKernelGGL((lsi_fused_reg_kernel<NC, MD, EXACT, 12>), dim3(a.batch), dim3(64), lds, s, fr);
+                else
+                    hipLaunchKernelGGL((lsi_fused_reg_kernel<NC, MD, EXACT, SWEEP_MD>), dim3(a.batch), dim3(64), lds, s, fr);
+            }
             else
-                hipLaunchKernelGGL((lsi_fused_kernel<NC, MD, EXACT, SWEEP_MD>), dim3(a.batch), dim3(64), lds, s, fa);
+            {
+                if (sweep_level_dim <= 12)
+                    hipLaunchKernelGGL((lsi_fused_kernel<NC, MD, EXACT, 12>), dim3(a.batch), dim3(64), lds, s, fa);
+                else
+                    hipLaunchKernelGGL((lsi_fused_kernel<NC, MD, EXACT, SWEEP_MD>), dim3(a.batch), dim3(64), lds, s, fa);
+            }
             return hipGetLastError();
         }
     } // namespace
@@ -158,5 +218,15 @@ namespace lexls
                         size_t resident_args_bytes, int count, hipStream_t s)                                                                                     \
         {                                                                                                                                                         \
             return launch_lsi_fused_t<NC, MD, EXACT>(a, sweep_level_dim, d_obj_index, tolW, tolC, scan_up, resident_args, resident_args_bytes, count, s);          \
+        }                                                                                                                                                         \
+    }
+/// the same launch with the regularized l-QR (lqr_wave_body<..., REG>): instantiation files of their own (lsi_fused_*_R.hip)
+#define LEXLS_LSI_FUSED_INSTANCE_REG(NAME, NC, MD, EXACT)                                                                                                         \
+    namespace lexls                                                                                                                                               \
+    {                                                                                                                                                             \
+        hipError_t NAME(const LseArgs &a, uint32_t sweep_level_dim, const int32_t *d_obj_index, double tolW, double tolC, bool scan_up, const void *resident_args,  \
+                        size_t resident_args_bytes, int count, hipStream_t s)                                                                                     \
+        {                                                                                                                                                         \
+            return launch_lsi_fused_t<NC, MD, EXACT, true>(a, sweep_level_dim, d_obj_index, tolW, tolC, scan_up, resident_args, resident_args_bytes, count, s);    \
         }                                                                                                                                                         \
     }

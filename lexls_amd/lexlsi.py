@@ -259,6 +259,12 @@ class LsiBatch:
         capi.check(capi.lib().lexls_lsi_batch_stats(self._h, _p(st, C.c_int32)))
         return dict(factorize_solve=int(st[0]), sensitivity=int(st[1]), device_step=int(st[2]), groups=int(st[3]))
 
+    def last_kernel(self) -> str:
+        """the kernel that served the resident active-set iterations of the last run (lexls_lsi_batch_last_kernel): the persistent launch
+        ("lsi_fused<...>", with "regularized" for a regularized run), the l-QR kernel of the lock-step stages, or "host" when the run was not
+        resident"""
+        return capi.lib().lexls_lsi_batch_last_kernel(self._h).decode()
+
     def run(self, problems, active_guess=None, x0=None, regularization_factors=None, v0=None, **params):
         """`problems`: list of objective lists or a PackedBatch of this batch's structure; other arguments as lsi_batch_solve"""
         pk = problems if isinstance(problems, PackedBatch) else pack_batch(self.nvar, problems)
