@@ -2,6 +2,7 @@
 // dispatch.  There is deliberately NO CPU fallback: without a usable HIP device every entry point
 // that needs one fails with LEXLS_ERR_NO_DEVICE / LEXLS_ERR_HIP.
 #include "../../include/lexls_hip.h"
+#include "lexls_internal.h"
 #include "lexls_kernels.h"
 #include "lexls_launch.h"
 #include "lexls_regularize.h"
@@ -145,7 +146,6 @@ struct lexls_lse_s
 extern "C"
 {
     const char *lexls_last_error(void) { return g_err.c_str(); }
-    /* internal: lets the other translation units of the library report through lexls_last_error() */
     void lexls_internal_set_error(const char *msg) { g_err = msg ? msg : ""; }
     int lexls_version(void) { return 100; }
 
@@ -607,14 +607,9 @@ extern "C"
         return LEXLS_OK;
     }
 
-    /* internal: the resident constraint data (lexls_lse_set_constraint_data), read by the lock-step driver's step kernel */
     const double *lexls_internal_cdata(lexls_lse_t h) { return h ? h->d_cdata : nullptr; }
 
-    /* internal: the device copy of the in slab (lexls_lse_round_layout) — the lock-step driver's resident iterations write the next
-     * equality problem's dimensions, fixed variables, types and row references there themselves */
     char *lexls_internal_round_in(lexls_lse_t h) { return h ? h->d_round_in : nullptr; }
-    /* internal: the in slab was written ON THE DEVICE (same stream): gather the rows it names.  The host does not know this round's
-     * dimensions, so kernel choice and LDS budgets follow the capacities given at creation (every kernel takes smaller problems). */
     int lexls_internal_round_resident(lexls_lse_t h, int has_fixed)
     {
         CHECK_HANDLE(h);
@@ -704,8 +699,6 @@ extern "C"
 
     static int upload_round(lexls_lse_t h, const void *h_in, int gather, bool trusted);
     int lexls_lse_upload_round(lexls_lse_t h, const void *h_in, int gather) { return upload_round(h, h_in, gather, false); }
-    /* internal (not in include/lexls_hip.h): the lock-step LexLSI driver of this library fills the block itself — variable indices and
-     * row references come from its own working sets — and skips the per-element argument checks */
     int lexls_internal_upload_round_trusted(lexls_lse_t h, const void *h_in, int gather) { return upload_round(h, h_in, gather, true); }
 
     static int upload_round(lexls_lse_t h, const void *h_in, int gather, bool trusted)
@@ -1012,10 +1005,8 @@ extern "C"
         return LEXLS_OK;
     }
 
-    /* internal (the lock-step LexLSI driver): the handle's kernel policy (lexls_lse_set_kernel_policy), to put it back after a change */
     int lexls_internal_kernel_policy(lexls_lse_t h) { return h ? h->force_generic : 0; }
 
-    /* internal (the lock-step LexLSI driver): the device buffer lexls_lse_multipliers filled last, and whether the sweep served it */
     const double *lexls_internal_multipliers(lexls_lse_t h, int *swept)
     {
         if (swept) *swept = (h && h->mult_swept) ? 1 : 0;
@@ -1214,9 +1205,6 @@ extern "C"
         h->resume_armed = true;
         return LEXLS_OK;
     }
-    /* internal (the lock-step LexLSI driver): the device array its resident iterations write the levels into, and the promise that it holds
-     * them for the next factorization */
-    /* (NULL under regularization: its factorizations read no levels back, so the resident iterations post none) */
     int32_t *lexls_internal_resume_levels(lexls_lse_t h) { return (h && h->resume_enabled && h->reg_type == 0) ? h->d_resume_level : nullptr; }
     void lexls_internal_arm_resume(lexls_lse_t h)
     {

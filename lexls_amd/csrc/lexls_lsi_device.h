@@ -1,4 +1,4 @@
-// Device side of the lock-step LexLSI driver (lexls_lsi_capi.hip): the step of an iteration and the resident working-set iteration, one wavefront per
+// Device side of the lock-step LexLSI driver (lsi_batch_ctx.h, compiled in lexls_lsi_capi.hip): the step of an iteration and the resident working-set iteration, one wavefront per
 // instance.  A header because two translation units run it: the driver launches lsi_step_kernel / lsi_iterate_kernel as kernels of their own,
 // lsi_fused_*.hip runs the iteration's body inside the persistent kernel (l-QR -> removal sweep -> iteration, until the instance stops).
 #pragma once
@@ -248,6 +248,8 @@ namespace
     /// u16 [act | inact | inact_pos] and u8 [ctr_state]
     __host__ __device__ inline size_t resident_lds_per_wave(uint32_t SD, uint32_t total) { return (8 * (size_t)SD + 7 * (size_t)total + 2 * STEP_MAX_OBJ + 15) & ~size_t(15); }
 
+    /// per instance: entries of ResidentArgs::na and words of ResidentArgs::info (the host lays the slab out with the same: lsi_batch_ctx.h)
+    constexpr uint32_t RESIDENT_NA_STRIDE = STEP_MAX_OBJ, RESIDENT_INFO_STRIDE = 8;
     /// LDS of one instance's wavefront and its slices of the resident arrays
     struct ResidentView
     {
@@ -283,8 +285,8 @@ namespace
         v.g_act  = a.act + (size_t)b * total;
         v.g_ina  = a.inact + (size_t)b * total;
         v.g_ipos = a.inact_pos + (size_t)b * total;
-        v.g_na   = a.na + (size_t)b * STEP_MAX_OBJ;
-        v.info   = a.info + (size_t)b * 8;
+        v.g_na   = a.na + (size_t)b * RESIDENT_NA_STRIDE;
+        v.info   = a.info + (size_t)b * RESIDENT_INFO_STRIDE;
         return v;
     }
     __device__ __forceinline__ void resident_load_lists(const ResidentArgs &a, const ResidentView &v, const uint32_t lane)

@@ -1,0 +1,737 @@
+// The lock-step LexLSI batch object: B host driver instances (include/lexls/lexlsi.h) over the equality-solver handles of a few groups (lsi_batch_ctx.h).
+#pragma once
+#include <lexls/lsi_runner.h>
+#include <memory>
+#include <thread>
+#include "lsi_slot.h"
+#include "lsi_worker_pool.h"
+
+namespace
+{
+    /// One problem through the single-problem driver (every equality problem on the device, the removal search of an iteration in one
+    /// device call); `lsi` is left solved for what the caller reads next.
+    runner::LsiInfo solve_one(internal::LexLSI &lsi, int device, const runner::LsiProblem &p, const ParametersLexLSI &par, double *h_x, int32_t *h_info6, uint8_t *h_active, double *h_v)
+    {
+        lsi.getLexLSE().setDevice(device);
+        lsi.getLexLSE().setSensitivityScan(true);
+        lsi.setSensitivityScansAllLevels(true);
+        runner::setup(lsi, p, par);
+        lsi.solve();
+        runner::LsiInfo info;
+        runner::collect(lsi, p, h_x, &info, h_active, h_v);
+        if (h_info6) std::memcpy(h_info6, &info, sizeof(info));
+        return info;
+    }
+
+    /// getLambda's last loop (lexlsi.h:592-604) for a whole group: the rows of the multiplier matrices (lexls_lse_multipliers: B x nObjL x ldo,
+    /// row r = r-th active constraint in working-set order, simple bounds first) go to the user's order — instance b's output is total x nObj,
+    /// column-major, column off + k = LexLSE objective k, column 0 zero when objective 0 holds simple bounds, inactive rows zero.
+    /// One workgroup per instance, lane = active constraint; map = [nact (B) | pos (B x total): user row of active constraint r].
+    __global__ __launch_bounds__(64) void lsi_lambda_scatter_kernel(const double *__restrict__ mult, const uint32_t *__restrict__ map, uint32_t B, uint32_t total,
+                                                                    uint32_t nObj, uint32_t nObjL, uint32_t off, uint32_t ldo, double *__restrict__ out)
+    {
+        const uint32_t b = blockIdx.x;
+        double *o        = out + (size_t)b * total * nObj;
+        for (uint32_t i = threadIdx.x; i < total * nObj; i += blockDim.x) o[i] = 0.0;
+        __syncthreads();
+        const uint32_t na   = min(map[b], min(total, ldo));
+        const uint32_t *pos = map + B + (size_t)b * total;
+        const double *m     = mult + (size_t)b * nObjL * ldo;
+        for (uint32_t r = threadIdx.x; r < na; r += blockDim.x)
+        {
+            const uint32_t u = pos[r];
+            if (u >= total) continue;
+            for (uint32_t k = 0; k < nObjL; k++) o[u + (size_t)(off + k) * total] = m[(size_t)k * ldo + r];
+        }
+    }
+} // namespace
+
+/// A lock-step batch that outlives one solve (the reference constructs a LexLSI once and feeds it successive problems, lexlsi.h:56-112):
+/// device buffers, pinned blocks, streams and the worker pool are made once; every run() re-reads the problem data.
+struct lexls_lsi_batch_s
+{
+    int device;
+    uint32_t batch, nVar, nObj, off;
+    std::vector<uint32_t> dims;
+    std::vector<int32_t> types;
+    size_t per_data = 0, total = 0;
+    bool gather = false;
+    uint32_t nGroups = 1;
+    std::vector<std::unique_ptr<BatchCtx>> grp;
+    std::vector<uint32_t> lo, group_of;
+    std::unique_ptr<WorkerPool> pool;
+    bool resident_ok = false;
+    double t_create = 0.0;
+    int32_t last_stats[4] = {0, 0, 0, 0}; // of the last run: factorize+solve stages, sensitivity stages, stages with the step on the device, groups
+    // ---- getLambda of the last run (lexls_lsi_batch_get_lambda, lexlsi.h:552-605) ----
+    // What the run leaves behind for it: every instance's final working set in working-set order and its active simple bounds (variable and
+    // bound value, the fixed variables of formLexLSE, objective.h:255-272); the general rows are gathered from the constraint data that stays
+    // resident in the group handles.  lam_rc: -1 no run yet (or the last one failed), LEXLS_OK, or the code get_lambda returns (lam_msg).
+    int lam_rc = -1;
+    std::string lam_msg;
+    const char *last_kernel = ""; // lexls_lsi_batch_last_kernel: what served the resident iterations of the last run ("host": nothing did)
+    double lam_tol = 1e-12;           // tol_linear_dependence of that run (the factorizations of getLambda use it, as the reference's do)
+    std::vector<uint32_t> data_off;   // per objective: offset of its block in one instance's constraint data
+    std::vector<uint32_t> first;      // per objective: its first row among an instance's `total` constraints
+    std::vector<uint16_t> ws_na;      // batch x nObj: active constraints per objective
+    std::vector<uint16_t> ws_idx;     // batch x total: per objective (from its first row on) the active constraints in working-set order
+    std::vector<uint8_t> ws_type;     // batch x total: their activation types
+    std::vector<uint32_t> ws_fixvar;  // batch x dims[0] (simple bounds only): variables of the active simple bounds, working-set order
+    std::vector<double> ws_fixval;    // batch x dims[0]: the bound each one is fixed at
+    struct LambdaBufs                 // per group, made at the first get_lambda
+    {
+        Pinned<uint32_t> map;         // [nact (B) | pos (B x total)]
+        uint32_t *d_map = NULL;
+        double *d_out   = NULL;       // B x total x nObj
+        ~LambdaBufs()
+        {
+            if (d_map) (void)hipFree(d_map);
+            if (d_out) (void)hipFree(d_out);
+        }
+    };
+    std::vector<std::unique_ptr<LambdaBufs>> lam_bufs;
+
+    /// what a group's next stage must serve (Run::wants): somebody alive, a factorize+solve, a sensitivity, a device-side step, a solve whose x the host needs
+    enum : uint32_t { WANT_ALIVE = 1u, WANT_FS = 2u, WANT_SENS = 4u, WANT_STEP = 8u, WANT_X = 16u };
+
+    /// What the phases of ONE run() share.  It lives on run()'s stack: between two runs the batch object keeps the statistics of the last
+    /// one and the working sets get_lambda needs, nothing else.
+    struct Run
+    {
+        const double *h_data, *h_x0, *h_v0, *h_reg_factors;
+        const uint32_t *h_var_index;
+        const uint8_t *h_active_guess;
+        const ParametersLexLSI &par;
+        double *h_x, *h_v;
+        int32_t *h_info6, *h_rounds2;
+        uint8_t *h_active;
+        const RunSwitches sw;
+        bool gather = false, resident = false, step = false; // of this run: rows gathered on the device, resident iterations, device-side step
+        std::vector<SlotStep> hooks; // (before the instances that point to them)
+        std::vector<std::unique_ptr<SlotLSI>> lsi;
+        std::vector<runner::LsiProblem> prob;
+        std::vector<std::atomic<uint32_t>> wants; // per group: WANT_* of the next stage
+        double t_begin = 0.0, t_ctx = 0.0, t_setup = 0.0, t_host = 0.0;
+    };
+
+    lexls_lsi_batch_s(int device_, uint32_t batch_, uint32_t nVar_, uint32_t nObj_, const uint32_t *h_dims, const int32_t *h_types)
+    : device(device_), batch(batch_), nVar(nVar_), nObj(nObj_)
+    {
+        if (batch == 0 || nObj == 0) throw Exception("lexls_lsi_batch_solve: empty batch");
+        dims.assign(h_dims, h_dims + nObj);
+        types.assign(h_types, h_types + nObj);
+        off = (h_types[0] == 1) ? 1 : 0;
+        if (nObj - off == 0) throw Exception("Problems consisting of one level of simple bounds are not supported."); // lexlsi.cpp:417
+        for (uint32_t k = 0; k < nObj; k++)
+        {
+            data_off.push_back(static_cast<uint32_t>(per_data));
+            first.push_back(static_cast<uint32_t>(total));
+            per_data += objective_elems(h_dims[k], h_types[k], nVar);
+            total += h_dims[k];
+        }
+        ws_na.assign((size_t)batch * nObj, 0);
+        ws_idx.assign((size_t)batch * total, 0);
+        ws_type.assign((size_t)batch * total, 0);
+        if (off)
+        {
+            ws_fixvar.assign((size_t)batch * h_dims[0], 0);
+            ws_fixval.assign((size_t)batch * h_dims[0], 0.0);
+        }
+        const double t_begin = BatchCtx::now();
+        const CreateSwitches sw;
+        // The instances can be split into groups that take turns: while one group's stage runs on the GPU (its own stream), the host
+        // advances the active-set logic of the other one.  Every stage carries fixed costs (one copy each way, launches, one
+        // synchronisation) that a split multiplies, so it pays for large batches only.  Measured on MI355X, cold
+        // solve of n = 40, 5 x 12, seconds with 1 / 2 / 3 groups: 512 instances 0.034 / 0.030 / 0.040; 1024: 0.039 / 0.034 / 0.045
+        // (256 instances, an earlier state of the driver: 0.044 / 0.047).  LEXLS_LSI_GROUPS overrides the number.
+        // (With resident iterations — the default, see below — there is no host work per stage left to overlap: one group.)
+        nGroups = ((!sw.resident || sw.device_step) && batch >= 512) ? 2u : 1u;
+        if (sw.groups) nGroups = std::max(1, std::atoi(sw.groups));
+        nGroups = std::min(nGroups, batch);
+        gather = per_data < 0x7fffffffull && !sw.host_staging; // (LEXLS_LSI_HOST_STAGING, a diagnostic switch: assemble on the host, stage over PCIe)
+        grp.resize(nGroups);
+        lo.assign(nGroups + 1, 0);
+        for (uint32_t g = 0; g < nGroups; g++) lo[g + 1] = lo[g] + batch / nGroups + (g < batch % nGroups ? 1u : 0u);
+        for (uint32_t g = 0; g < nGroups; g++)
+        {
+            grp[g].reset(new BatchCtx());
+            BatchCtx &ctx = *grp[g];
+            ctx.create(device, lo[g + 1] - lo[g], nVar, nObj - off, h_dims + off, gather, sw.prefix_reuse);
+            hip_check(lexls_lse_set_deferred_sync(ctx.h, 1)); // every per-round array of BatchCtx is pinned and only touched between stages
+            hip_check(lexls_lse_set_sensitivity_scan(ctx.h, 1)); // the removal search of an iteration in ONE sensitivity stage (all its levels)
+            // The removal search runs speculatively behind every factorization (a third fewer stages: one synchronisation per active-set
+            // iteration instead of two).  With round 1's 83-us level-by-level search it lost (1024 instances cold 0.040 s vs 0.036 s); since the
+            // search is one 36-us sweep (sensitivity_sweep_kernel) it wins: warm-started ~30 iterations 0.027-0.028 s vs 0.029-0.034 s.
+            // LEXLS_LSI_SPECULATIVE_SENS=0 restores the two-stage form.
+            ctx.spec_sens = sw.spec_sens;
+        }
+        // the step of an iteration can run on the device when the constraint data is resident
+        StepShape sh;
+        std::memset(&sh, 0, sizeof(sh));
+        sh.n = nVar, sh.nObj = nObj, sh.total = (uint32_t)total, sh.SD = nVar + 2 * (uint32_t)total, sh.per_data = per_data, sh.dim0 = off ? h_dims[0] : 0;
+        const uint64_t elems = nObj <= STEP_MAX_OBJ ? fill_shape(sh, h_dims, h_types, nVar) : 0;
+        // Off by default: measured on MI355X (scripts/lsi_ab.sh; 1024 / 4096 instances of n = 40, 5 x 12) it is a wash — cold 0.052 s
+        // vs 0.049 s at 1024, 0.117 s vs 0.120 s at 4096: the host's share of a stage is parallel and small, the extra copy + kernel +
+        // copy of a stage is not free.  LEXLS_LSI_DEVICE_STEP=1 turns it on.
+        bool step_ok = sw.device_step && gather && nObj <= STEP_MAX_OBJ && 8 * (size_t)sh.SD * 4 <= 48 * 1024;
+        for (uint32_t k = 0; k < nObj && step_ok; k++) step_ok = h_dims[k] <= 65535;
+        if (step_ok)
+            for (uint32_t g = 0; g < nGroups; g++) grp[g]->create_step(sh);
+        // Resident iterations (lsi_iterate_kernel), the default where the structure allows it: after phase 1 the instances leave the host —
+        // a stage is row gather + l-QR + removal sweep + step / working-set change / next problem, all enqueued, and the host only polls
+        // how many instances have stopped.  LEXLS_LSI_RESIDENT=0 keeps the active-set logic on the host (one synchronisation per stage).
+        resident_ok = sw.resident && !step_ok && gather && nObj <= STEP_MAX_OBJ && 4 * resident_lds_per_wave(sh.SD, (uint32_t)total) <= 48 * 1024 && total <= 65535 && elems <= 0xffffffffull;
+        for (uint32_t k = 1; k < nObj && resident_ok; k++) resident_ok = h_types[k] != 1; // (the driver itself only takes a simple-bounds objective first, lexlsi.h:402-405)
+        if (resident_ok)
+            for (uint32_t g = 0; g < nGroups; g++) grp[g]->create_resident(sh, off);
+        group_of.resize(batch);
+        for (uint32_t g = 0; g < nGroups; g++)
+            for (uint32_t b = lo[g]; b < lo[g + 1]; b++) group_of[b] = g;
+        pool.reset(new WorkerPool(WorkerPool::default_workers(batch), sw.pool_spin_seconds));
+        t_create = BatchCtx::now() - t_begin;
+    }
+
+    /// instance b's final working set from its host objects (workingset.h order)
+    template <class LSI>
+    void keep_working_set(uint32_t b, const LSI &inst, const double *data, const uint32_t *var_index)
+    {
+        uint16_t *ix = &ws_idx[(size_t)b * total];
+        uint8_t *ty  = &ws_type[(size_t)b * total];
+        for (uint32_t k = 0; k < nObj; k++) ws_na[(size_t)b * nObj + k] = static_cast<uint16_t>(inst.getObjectives()[k].getActiveCtrCount());
+        walk_working_set(inst.getObjectives(), nObj, [&](uint32_t k, Index a, Index c, ConstraintActivationType t) { ix[first[k] + a] = static_cast<uint16_t>(c), ty[first[k] + a] = static_cast<uint8_t>(t); }, [](uint32_t, Index, Index) {});
+        keep_fixed(b, data, var_index);
+    }
+    /// the same from the resident slabs a run downloaded (lists in working-set order, types by constraint)
+    void keep_working_set_resident(uint32_t b, BatchCtx &ctx, uint32_t k, const double *data, const uint32_t *var_index)
+    {
+        char *base          = ctx.rws_host.data();
+        const uint8_t *cs   = ctx.rl.ctr_state(base, k);
+        const uint16_t *act = ctx.rl.act(base, k), *na = ctx.rl.na(base, k);
+        for (uint32_t o = 0; o < nObj; o++)
+        {
+            ws_na[(size_t)b * nObj + o] = na[o];
+            for (uint32_t a = 0; a < na[o]; a++)
+            {
+                ws_idx[(size_t)b * total + first[o] + a]  = act[first[o] + a];
+                ws_type[(size_t)b * total + first[o] + a] = cs[first[o] + act[first[o] + a]];
+            }
+        }
+        keep_fixed(b, data, var_index);
+    }
+    /// fixVariable(var, bound) of formLexLSE for the active simple bounds (objective.h:257-271): lb, or ub for CTR_ACTIVE_UB / CTR_ACTIVE_EQ
+    void keep_fixed(uint32_t b, const double *data, const uint32_t *var_index)
+    {
+        if (!off) return;
+        const uint32_t d0 = dims[0], na = ws_na[(size_t)b * nObj];
+        for (uint32_t a = 0; a < na && a < d0; a++)
+        {
+            const uint32_t c = ws_idx[(size_t)b * total + a];
+            ws_fixvar[(size_t)b * d0 + a] = var_index ? var_index[c] : 0u;
+            ws_fixval[(size_t)b * d0 + a] = ws_type[(size_t)b * total + a] == CTR_ACTIVE_LB ? data[c] : data[d0 + c];
+        }
+    }
+
+    /// instance k of group g: the in block of its final equality problem (lexls_lse_round_layout), as formLexLSE posts it (objective.h:255-294),
+    /// and the user row of every active constraint
+    void form_final_problem(uint32_t g, uint32_t k, LambdaBufs &lb)
+    {
+        BatchCtx &ctx        = *grp[g];
+        const uint32_t nObjL = nObj - off, d0 = off ? dims[0] : 0u;
+        const uint32_t b  = lo[g] + k;
+        const uint16_t *na = ws_na.data() + (size_t)b * nObj;
+        const uint16_t *ix = ws_idx.data() + (size_t)b * total;
+        const uint8_t *ty  = ws_type.data() + (size_t)b * total;
+        uint32_t *pos      = lb.map.data() + ctx.B + (size_t)k * total;
+        uint32_t r = 0, row = 0;
+        const uint32_t nf = off ? std::min<uint32_t>(na[0], nVar) : 0u; // (formLexLSE fixes each variable once: at most nVar, lexlse.h:1453)
+        ctx.nfixed[k]     = nf;
+        for (uint32_t a = 0; a < nf; a++)
+        {
+            ctx.fixed_idx[(size_t)k * nVar + a]  = ws_fixvar[(size_t)b * d0 + a];
+            ctx.fixed_val[(size_t)k * nVar + a]  = ws_fixval[(size_t)b * d0 + a];
+            ctx.fixed_type[(size_t)k * nVar + a] = ty[a];
+            pos[r++]                             = ix[a];
+        }
+        std::fill(ctx.row_ld.begin() + (size_t)k * ctx.cap, ctx.row_ld.begin() + (size_t)(k + 1) * ctx.cap, 0u);
+        for (uint32_t o = off; o < nObj; o++)
+        {
+            ctx.dims[(size_t)k * nObjL + (o - off)] = na[o];
+            for (uint32_t a = 0; a < na[o]; a++)
+            {
+                const uint8_t t                      = ty[first[o] + a];
+                ctx.row_src[(size_t)k * ctx.cap + row] = data_off[o] + ix[first[o] + a];
+                ctx.row_ld[(size_t)k * ctx.cap + row]  = dims[o] | (t == CTR_ACTIVE_LB ? 0u : 0x80000000u);
+                ctx.ctr_type[(size_t)k * ctx.cap + row] = t;
+                row++;
+                pos[r++] = first[o] + ix[first[o] + a];
+            }
+        }
+        lb.map[k]     = r;
+        ctx.skip[k]   = 0;
+        ctx.objidx[k] = -1;
+    }
+
+    /// LexLSI::getLambda (lexlsi.h:552-605) for every instance of the last run, on the device in each group's stream: the final equality
+    /// problems are formed (rows gathered by reference, fixed variables posted), factorized with the factor kept on a bit-exact kernel, all
+    /// objectives' multipliers taken in one sweep (lexls_lse_multipliers), scattered into the user's order, one copy back per group
+    int get_lambda(double *h_lambda)
+    {
+        if (lam_rc < 0) throw Exception("lexls_lsi_batch_get_lambda: no completed lexls_lsi_batch_run on this batch");
+        if (lam_rc != LEXLS_OK)
+        {
+            lexls_internal_set_error(lam_msg.c_str());
+            return lam_rc;
+        }
+        if (!h_lambda) throw Exception("lexls_lsi_batch_get_lambda: null output");
+        const uint32_t nObjL = nObj - off;
+        if (lam_bufs.empty())
+        {
+            lam_bufs.resize(nGroups);
+            for (uint32_t g = 0; g < nGroups; g++)
+            {
+                lam_bufs[g].reset(new LambdaBufs());
+                LambdaBufs &lb    = *lam_bufs[g];
+                const size_t Bg   = grp[g]->B;
+                lb.map.assign(Bg + Bg * total, 0u);
+                if (hipSetDevice(device) != hipSuccess || hipMalloc((void **)&lb.d_map, 4 * (Bg + Bg * total)) != hipSuccess ||
+                    hipMalloc((void **)&lb.d_out, 8 * Bg * total * nObj) != hipSuccess)
+                    throw Exception("hipMalloc failed (lexls_lsi_batch_get_lambda)");
+            }
+        }
+        // LEXLS_LSI_TIMING: the stages one by one (a synchronisation behind each) and their times on stderr
+        const bool timing = RunSwitches().timing;
+        double ts[4] = {0, 0, 0, 0}, tp = BatchCtx::now();
+        auto stage = [&](int i, BatchCtx &c) {
+            if (!timing) return;
+            hip_check(lexls_lse_synchronize(c.h));
+            const double t = BatchCtx::now();
+            ts[i] += t - tp;
+            tp = t;
+        };
+        for (uint32_t g = 0; g < nGroups; g++)
+        {
+            BatchCtx &ctx  = *grp[g];
+            LambdaBufs &lb = *lam_bufs[g];
+            pool->run(ctx.B, [&](uint32_t k) { form_final_problem(g, k, lb); });
+            stage(0, ctx);
+            // the equality solver's parameters of this run, whichever path it took (the one-by-one path of deactivate_first_wrong_sign never set
+            // them on these handles; an earlier run of the batch object may have left a regularization there): lam_rc == LEXLS_OK means unregularized
+            hip_check(lexls_lse_set_tolerance(ctx.h, lam_tol));
+            hip_check(lexls_lse_set_regularization(ctx.h, 0, NULL, 0, 0.0));
+            const int policy = lexls_internal_kernel_policy(ctx.h);
+            hip_check(lexls_lse_set_kernel_policy(ctx.h, 5)); // bit-exact kernels whatever the shape (the factor of the reference's getLambda)
+            int rc = lexls_internal_upload_round_trusted(ctx.h, ctx.in_block.data(), 1);
+            if (rc == LEXLS_OK) rc = lexls_lse_factorize(ctx.h);
+            hip_check(lexls_lse_set_kernel_policy(ctx.h, policy));
+            hip_check(rc);
+            stage(1, ctx);
+            hip_check(lexls_lse_multipliers(ctx.h));
+            stage(2, ctx);
+            const double *d_mult = lexls_internal_multipliers(ctx.h, NULL);
+            if (!d_mult) throw Exception("lexls_lsi_batch_get_lambda: no multipliers");
+            if (hipMemcpyAsync(lb.d_map, lb.map.data(), 4 * ((size_t)ctx.B + (size_t)ctx.B * total), hipMemcpyHostToDevice, ctx.stream) != hipSuccess)
+                throw Exception("hipMemcpyAsync failed (lexls_lsi_batch_get_lambda)");
+            hipLaunchKernelGGL(lsi_lambda_scatter_kernel, dim3(ctx.B), dim3(64), 0, ctx.stream, d_mult, lb.d_map, ctx.B, (uint32_t)total, nObj, nObjL, off,
+                               nVar + ctx.cap, lb.d_out);
+            if (hipGetLastError() != hipSuccess) throw Exception("lsi_lambda_scatter_kernel launch failed");
+            if (hipMemcpyAsync(h_lambda + (size_t)lo[g] * total * nObj, lb.d_out, 8 * (size_t)ctx.B * total * nObj, hipMemcpyDeviceToHost, ctx.stream) != hipSuccess)
+                throw Exception("hipMemcpyAsync failed (lexls_lsi_batch_get_lambda)");
+            stage(3, ctx);
+        }
+        for (uint32_t g = 0; g < nGroups; g++)
+            if (hipStreamSynchronize(grp[g]->stream) != hipSuccess) throw Exception("lexls_lsi_batch_get_lambda: stream synchronisation failed");
+        if (timing)
+            std::fprintf(stderr, "lexls_lsi_batch_get_lambda: %.4f ms = form the problems (host) %.4f + upload, gather, factorize %.4f + multipliers %.4f + scatter, copy back %.4f (%u groups)\n",
+                         1e3 * (ts[0] + ts[1] + ts[2] + ts[3]), 1e3 * ts[0], 1e3 * ts[1], 1e3 * ts[2], 1e3 * ts[3], nGroups);
+        return LEXLS_OK;
+    }
+
+
+    runner::LsiProblem problem(const Run &r, uint32_t b) const
+    {
+        return {nVar, nObj, dims.data(), types.data(), r.h_data + (size_t)b * per_data, r.h_var_index ? r.h_var_index + (size_t)b * dims[0] : NULL,
+                r.h_active_guess ? r.h_active_guess + (size_t)b * total : NULL, r.h_x0 ? r.h_x0 + (size_t)b * nVar : NULL, r.h_v0 ? r.h_v0 + (size_t)b * total : NULL, r.h_reg_factors};
+    }
+    BatchCtx &group_of_instance(uint32_t b, uint32_t &k)
+    {
+        k = b - lo[group_of[b]];
+        return *grp[group_of[b]];
+    }
+
+    void run(const double *h_data, const uint32_t *h_var_index, const uint8_t *h_active_guess, const double *h_x0, const double *h_v0,
+             const double *h_reg_factors, const ParametersLexLSI &par, double *h_x, int32_t *h_info6, uint8_t *h_active, double *h_v, int32_t *h_rounds2)
+    {
+        if (!h_data || !h_x) throw Exception("lexls_lsi_batch_run: null data / x");
+        lam_rc  = -1;
+        lam_tol = par.tol_linear_dependence;
+        last_kernel = "host";
+        // getLambda of this run needs the rows gathered from resident constraint data, unrelaxed bounds and unregularized factorizations
+        const int lam_after = (par.cycling_handling_enabled || par.regularization_type != REGULARIZATION_NONE || !gather || total > 65535) ? LEXLS_ERR_UNSUPPORTED : LEXLS_OK;
+        const char *lam_why = par.cycling_handling_enabled ? "lexls_lsi_batch_get_lambda: not available after a run with cycling handling enabled (it relaxes bounds on the host)"
+                              : par.regularization_type != REGULARIZATION_NONE ? "lexls_lsi_batch_get_lambda: not available after a regularized run"
+                                                                                : "lexls_lsi_batch_get_lambda: not available when the constraint data is not resident on the device (or beyond 65535 constraints)";
+        Run r{h_data, h_x0, h_v0, h_reg_factors, h_var_index, h_active_guess, par, h_x, h_v, h_info6, h_rounds2, h_active};
+        if (par.deactivate_first_wrong_sign)
+        {
+            run_one_by_one(r, lam_after == LEXLS_OK);
+            lam_rc  = (off && !h_var_index) ? LEXLS_ERR_INVALID : lam_after;
+            lam_msg = lam_rc == LEXLS_ERR_INVALID ? "lexls_lsi_batch_get_lambda: the run had no variable indices" : lam_why;
+            return;
+        }
+        r.t_begin = BatchCtx::now();
+        pool->prewake(); // (the workers went to sleep between two solves; they are needed in ~0.1 ms)
+        prepare_groups(r);
+        upload_regularization_block(r); // (before the constraint data's upload starts on another thread: this call may touch the handles)
+        build_instances(r);
+        host_rounds(r);
+        if (r.resident) resident_rounds(r);
+        collect(r);
+        report(r);
+        lam_rc  = lam_after;
+        lam_msg = lam_why;
+        bool any_left = false;
+        for (uint32_t b = 0; b < batch && !any_left; b++) any_left = r.lsi[b] != nullptr;
+        if (any_left) pool->run(batch, [&](uint32_t b) { r.lsi[b].reset(); }); // a thousand LexLSI objects (dozens of vectors each): freed in parallel, not serially on return
+    }
+
+    /// The lock-step stages ask the device for ONE removal candidate per instance; deactivate_first_wrong_sign (lexlsi.h:1089-1103) wants every
+    /// wrong-sign multiplier of the first level that has one, read back per iteration.  Such a batch runs its instances one after the other
+    /// through the single-problem driver — same results as lexls_lsi_solve_ex on each, every equality problem on the GPU.
+    void run_one_by_one(Run &r, bool lambda_possible)
+    {
+        int32_t fs = 0;
+        for (uint32_t b = 0; b < batch; b++)
+        {
+            const runner::LsiProblem p = problem(r, b);
+            internal::LexLSI lsi;
+            fs += solve_one(lsi, device, p, r.par, r.h_x + (size_t)b * nVar, r.h_info6 ? r.h_info6 + (size_t)b * 6 : NULL, r.h_active ? r.h_active + (size_t)b * total : NULL,
+                            r.h_v ? r.h_v + (size_t)b * total : NULL).factorizations;
+            keep_working_set(b, lsi, p.data, p.var_index);
+        }
+        last_stats[0] = fs, last_stats[1] = last_stats[2] = 0, last_stats[3] = 1;
+        if (r.h_rounds2) r.h_rounds2[0] = fs, r.h_rounds2[1] = 0;
+        // (these instances never used the group handles: the constraint data getLambda gathers from goes there now — one copy of the batch's
+        // data per run, asked for or not: the caller's array is gone when get_lambda comes, and this path solves its instances one by one,
+        // milliseconds each, against ~1 ms per 16 MB for the copy)
+        if (lambda_possible && (!off || r.h_var_index))
+            for (uint32_t g = 0; g < nGroups; g++) hip_check(lexls_lse_set_constraint_data(grp[g]->h, r.h_data + (size_t)lo[g] * per_data, per_data));
+    }
+
+    /// the variable indices of a simple-bounds objective 0 (dim0 per instance) of group g, for the step kernels
+    void upload_variable_indices(const Run &r, uint32_t g, uint32_t *d_var, uint32_t dim0)
+    {
+        if (!dim0) return;
+        BatchCtx &ctx = *grp[g];
+        if (!r.h_var_index) throw Exception("lexls_lsi_batch_run: a simple-bounds objective needs variable indices");
+        if (hipMemcpyAsync(d_var, r.h_var_index + (size_t)lo[g] * dim0, 4 * (size_t)ctx.B * dim0, hipMemcpyHostToDevice, ctx.stream) != hipSuccess || hipStreamSynchronize(ctx.stream) != hipSuccess)
+            throw Exception("upload of the variable indices failed");
+    }
+
+    /// every group back to what a fresh one holds, with this run's parameters; decides what kind of run it is
+    void prepare_groups(Run &r)
+    {
+        // Cycling handling relaxes bounds in the host copy of the constraint data (cycling.h:32-65, objective.h:774-790): such a run
+        // assembles its problems on the host from that copy instead of gathering rows of the resident (unrelaxed) device copy
+        r.gather = gather && !r.par.cycling_handling_enabled;
+        for (uint32_t g = 0; g < nGroups; g++)
+        {
+            BatchCtx &ctx = *grp[g];
+            ctx.gather    = r.gather;
+            if (!r.gather) ctx.need_staging();
+            ctx.reset();
+            hip_check(lexls_lse_set_tolerance(ctx.h, r.par.tol_linear_dependence));
+            ctx.reg_type = static_cast<int>(r.par.regularization_type), ctx.reg_variable = r.par.variable_regularization_factor, ctx.reg_cg_iters = r.par.max_number_of_CG_iterations;
+            ctx.reg_dirty.store(ctx.reg_type != 0);
+            if (ctx.reg_type == 0) hip_check(lexls_lse_set_regularization(ctx.h, 0, NULL, 0, 0.0));
+            if (r.gather && ctx.device_step)
+            {
+                ctx.shape.tol_feasibility = r.par.tol_feasibility;
+                upload_variable_indices(r, g, ctx.d_var, ctx.shape.dim0);
+            }
+        }
+        // whole iterations on the device: plain runs and the regularized ones the register-resident kernel's REG instantiations serve (every
+        // type but the experimental 7).  Cycling handling edits the host's bounds: host path, as every other case
+        const int reg_type = static_cast<int>(r.par.regularization_type);
+        r.resident = r.gather && resident_ok && grp[0]->resident && (reg_type == 0 || lexls_internal_resident_reg_serves(grp[0]->h, reg_type)) && r.par.max_number_of_factorizations < 0x7fffffff;
+        r.step     = r.gather && grp[0]->device_step;
+    }
+
+    /// A regularized resident run: its regularization goes to the device ONCE, as a block in every group's stream — LexLSE level k takes the
+    /// factor of objective k + off (a simple-bounds objective 0 becomes fixed variables and has none: lexlsi.h formLexLSE), whatever the level
+    /// holds in the working set of the moment.  The host copy the instances post into (SlotLSE::setRegularizationFactor) starts from the
+    /// same values, so phase 1 finds nothing to upload again.
+    void upload_regularization_block(Run &r)
+    {
+        const int reg_type = static_cast<int>(r.par.regularization_type);
+        if (!r.resident || reg_type == 0) return;
+        std::vector<double> level_factor(nObj - off, 0.0);
+        if (r.h_reg_factors)
+            for (uint32_t k = 0; k + off < nObj; k++) level_factor[k] = r.h_reg_factors[k + off];
+        for (uint32_t g = 0; g < nGroups; g++)
+        {
+            BatchCtx &ctx = *grp[g];
+            hip_check(lexls_internal_set_regularization_block(ctx.h, reg_type, level_factor.data(), ctx.reg_variable, ctx.reg_cg_iters));
+            for (uint32_t b = 0; b < ctx.B; b++) std::copy(level_factor.begin(), level_factor.end(), ctx.reg_factor.begin() + (size_t)b * ctx.nObjL);
+            ctx.reg_dirty.store(false);
+        }
+    }
+
+    /// The constraint data goes to the device (16 MB for 1024 IK instances: ~0.4 ms) while the worker pool builds the instances' host
+    /// objects and runs their phase 1: nothing of that touches the handles; joined before the first stage.
+    void build_instances(Run &r)
+    {
+        int upload_rc = LEXLS_OK;
+        std::string upload_err;
+        std::thread uploader;
+        if (r.gather)
+            uploader = std::thread([&]() {
+                for (uint32_t g = 0; g < nGroups && upload_rc == LEXLS_OK; g++)
+                {
+                    upload_rc = lexls_lse_set_constraint_data(grp[g]->h, r.h_data + (size_t)lo[g] * per_data, per_data);
+                    if (upload_rc != LEXLS_OK) upload_err = lexls_last_error();
+                }
+            });
+        struct Joiner // (the setup below may throw)
+        {
+            std::thread &t;
+            ~Joiner()
+            {
+                if (t.joinable()) t.join();
+            }
+        } joiner{uploader};
+        if (r.resident)
+            for (uint32_t g = 0; g < nGroups; g++)
+            {
+                grp[g]->rshape.tol_feasibility = r.par.tol_feasibility;
+                upload_variable_indices(r, g, grp[g]->d_rvar, grp[g]->rshape.dim0);
+            }
+        r.hooks = std::vector<SlotStep>(r.step ? batch : 0);
+        r.t_ctx = BatchCtx::now() - r.t_begin;
+        r.lsi   = std::vector<std::unique_ptr<SlotLSI>>(batch);
+        r.prob.resize(batch);
+        pool->run(batch, [&](uint32_t b) {
+            uint32_t k;
+            BatchCtx &ctx = group_of_instance(b, k);
+            r.lsi[b].reset(new SlotLSI());
+            r.lsi[b]->getLexLSE().bind(&ctx, k);
+            r.prob[b] = problem(r, b);
+            runner::setup(*r.lsi[b], r.prob[b], r.par);
+            r.lsi[b]->setSensitivityScansAllLevels(true);
+            if (r.step)
+            {
+                r.hooks[b].c = &ctx;
+                r.hooks[b].b = k;
+                r.lsi[b]->setStepHook(&r.hooks[b]);
+            }
+            r.lsi[b]->begin();
+        });
+        if (uploader.joinable()) uploader.join();
+        if (upload_rc != LEXLS_OK) throw Exception(std::string("liblexls_hip: ") + upload_err);
+        r.t_setup = BatchCtx::now() - r.t_begin;
+    }
+
+    /// The job of instance k of group g between two stages: take over the results of the stage that just finished (if it was served), advance
+    /// its active-set logic, and post what it needs next into the group's round block and into r.wants[g].
+    void advance_instance(Run &r, uint32_t g, uint32_t k)
+    {
+        BatchCtx &ctx = *grp[g];
+        SlotLSI &inst = *r.lsi[lo[g] + k];
+        if (r.resident && ctx.is_resident[k]) return; // waits for the others to leave phase 1
+        const bool served_fs = ctx.stage_fs && !ctx.skip[k], served_sens = ctx.stage_sens && ctx.skip[k] && ctx.objidx[k] >= 0;
+        const bool has_spec  = served_fs && ctx.stage_sens && ctx.objidx[k] == 0; // its removal search ran right behind its l-QR
+        if (r.step) ctx.mode()[k] = 0; // (the hook raises it again when the instance posts an iteration's equality problem)
+        if (served_fs) ctx.take_solution(k);
+        if (served_fs || served_sens) inst.advance();
+        if (has_spec && !inst.finished() && inst.need() == SlotLSI::NEED_SENSITIVITY && inst.needLevel() == 0) inst.advance(); // step not blocked: use it
+        const bool alive = !inst.finished();
+        if (r.resident && alive && inst.atIterationSolve())
+        {
+            // phase 1 is over and the equality problem of a regular iteration is staged: from here on the instance iterates on the
+            // device (its staged problem is served by the first resident stage)
+            ctx.hand_over(k, inst);
+            ctx.skip[k]   = 1;
+            ctx.objidx[k] = -1;
+            return;
+        }
+        const bool fs    = alive && inst.need() == SlotLSI::NEED_FACTORIZE_SOLVE;
+        const bool se    = alive && inst.need() == SlotLSI::NEED_SENSITIVITY;
+        const bool spec  = fs && ctx.spec_sens;
+        ctx.skip[k]      = fs ? 0 : 1;
+        ctx.objidx[k]    = se ? static_cast<int32_t>(inst.needLevel()) : (spec ? 0 : -1);
+        const bool dstep = r.step && fs && ctx.mode()[k] != 0;
+        const uint32_t w = (alive ? WANT_ALIVE : 0u) | (fs ? WANT_FS : 0u) | ((se || spec) ? WANT_SENS : 0u) | (dstep ? WANT_STEP : 0u) | ((fs && !dstep) ? WANT_X : 0u);
+        if (w & ~r.wants[g].load(std::memory_order_relaxed)) r.wants[g].fetch_or(w, std::memory_order_relaxed);
+    }
+    void turn(Run &r, uint32_t g)
+    {
+        r.wants[g].store(0);
+        const double t0 = BatchCtx::now();
+        pool->run(lo[g + 1] - lo[g], [&](uint32_t k) { advance_instance(r, g, k); });
+        r.t_host += BatchCtx::now() - t0;
+    }
+    /// one stage of group g for what its instances asked for; false when no instance of the group is alive any more
+    bool enqueue(Run &r, uint32_t g)
+    {
+        BatchCtx &ctx    = *grp[g];
+        const uint32_t w = r.wants[g].load();
+        ctx.stage_fs = ctx.stage_sens = false;
+        if (!(w & WANT_ALIVE)) return false;
+        if (!(w & (WANT_FS | WANT_SENS))) throw Exception("lexls_lsi_batch_solve: an instance is alive but requests nothing");
+        ctx.enqueue_stage((w & WANT_FS) != 0, (w & WANT_SENS) != 0, (w & WANT_STEP) != 0, (w & WANT_X) != 0, r.par.tol_wrong_sign_lambda, r.par.tol_correct_sign_lambda);
+        return true;
+    }
+
+    /// The stages the host's active-set logic drives.  One stage of group g serves every pending factorize+solve of the group in one call and
+    /// every pending ObjectiveSensitivity in one call (different instances), both only enqueued.  Between two stages every instance of the
+    /// group runs ONE job on the worker pool (advance_instance).
+    void host_rounds(Run &r)
+    {
+        r.wants = std::vector<std::atomic<uint32_t>>(nGroups);
+        std::vector<char> alive(nGroups, 0);
+        bool any = false;
+        for (uint32_t g = 0; g < nGroups; g++)
+        {
+            turn(r, g); // nothing served yet: only posts the first requests
+            any = (alive[g] = enqueue(r, g)) || any;
+        }
+        while (any)
+        {
+            any = false;
+            for (uint32_t g = 0; g < nGroups; g++)
+                if (alive[g])
+                {
+                    grp[g]->finish_stage(); // the other groups' stages keep the GPU busy meanwhile
+                    turn(r, g);
+                    alive[g] = enqueue(r, g);
+                    any      = any || alive[g];
+                }
+        }
+    }
+
+    /// the iterations of the handed-over instances, on the device until every one has stopped; their slabs come back at the end
+    void resident_rounds(Run &r)
+    {
+        std::vector<char> going(nGroups, 0);
+        bool more = false;
+        for (uint32_t g = 0; g < nGroups; g++)
+        {
+            BatchCtx &ctx  = *grp[g];
+            ctx.n_resident = 0;
+            for (uint32_t k = 0; k < ctx.B; k++)
+            {
+                const bool res = ctx.is_resident[k] != 0;
+                ctx.skip[k]    = res ? 0 : 1;
+                ctx.objidx[k]  = res ? 0 : -1;
+                ctx.n_resident += res ? 1u : 0u;
+            }
+            if (ctx.n_resident)
+            {
+                ctx.begin_resident();
+                going[g] = 1;
+                more     = true;
+            }
+        }
+        // stages are enqueued in chunks; after each chunk ONE word comes back (instances that have stopped).  Stages past an
+        // instance's end skip it in every kernel; a chunk that turns out not to be needed costs a few launches of early-exit kernels
+        const int chunk = 8;
+        bool freed = false;
+        while (more)
+        {
+            more = false;
+            for (uint32_t g = 0; g < nGroups; g++)
+                if (going[g]) grp[g]->enqueue_resident(chunk, r.par.tol_wrong_sign_lambda, r.par.tol_correct_sign_lambda, static_cast<int32_t>(r.par.max_number_of_factorizations));
+            if (!freed) // the handed-over instances' host objects (a thousand LexLSI instances, dozens of vectors each) are not needed any
+            {           // more: they are freed now, while the GPU works on the first chunk, instead of on the caller's time at the end
+                freed = true;
+                pool->run(batch, [&](uint32_t b) {
+                    uint32_t k;
+                    if (group_of_instance(b, k).is_resident[k]) r.lsi[b].reset();
+                });
+            }
+            for (uint32_t g = 0; g < nGroups; g++)
+                if (going[g])
+                {
+                    if (grp[g]->resident_done()) going[g] = 0;
+                    more = more || going[g];
+                }
+        }
+        for (uint32_t g = 0; g < nGroups; g++)
+            if (grp[g]->n_resident)
+            {
+                grp[g]->download_resident(r.sw.stamps_dump);
+                last_kernel = grp[g]->resident_kernel; // (every group takes the same path: same shape, same regularization)
+            }
+    }
+
+    /// instance b's results into the caller's arrays, and its final working set for get_lambda
+    void collect_instance(Run &r, uint32_t b)
+    {
+        uint32_t k;
+        BatchCtx &ctx = group_of_instance(b, k);
+        double *x = r.h_x + (size_t)b * nVar, *v = r.h_v ? r.h_v + (size_t)b * total : NULL;
+        if (r.resident && ctx.is_resident[k]) // x, v, working set and counters as the device left them (its host object is gone already)
+        {
+            unpack_state(ctx.rstate_host.data() + (size_t)k * ctx.rshape.SD, nVar, total, x, v);
+            if (r.h_active) std::copy(ctx.rl.ctr_state(ctx.rws_host.data(), k), ctx.rl.ctr_state(ctx.rws_host.data(), k) + total, r.h_active + (size_t)b * total);
+            if (r.h_info6) std::memcpy(r.h_info6 + (size_t)b * 6, ctx.rl.info(ctx.rws_host.data(), k), 6 * sizeof(int32_t));
+            keep_working_set_resident(b, ctx, k, r.prob[b].data, r.prob[b].var_index);
+            return;
+        }
+        runner::LsiInfo info;
+        runner::collect(*r.lsi[b], r.prob[b], x, &info, r.h_active ? r.h_active + (size_t)b * total : NULL, v);
+        if (r.h_info6) std::memcpy(r.h_info6 + (size_t)b * 6, &info, sizeof(info));
+        keep_working_set(b, *r.lsi[b], r.prob[b].data, r.prob[b].var_index);
+        if (r.step && ctx.on_device[k]) unpack_state(ctx.state_host.data() + (size_t)k * ctx.shape.SD, nVar, total, x, v);
+    }
+    void collect(Run &r)
+    {
+        if (r.step) // x and v of the instances whose state lives on the device
+            for (uint32_t g = 0; g < nGroups; g++)
+            {
+                BatchCtx &ctx = *grp[g];
+                if (hipMemcpyAsync(ctx.state_host.data(), ctx.d_state, 8 * (size_t)ctx.B * ctx.shape.SD, hipMemcpyDeviceToHost, ctx.stream) != hipSuccess ||
+                    hipStreamSynchronize(ctx.stream) != hipSuccess)
+                    throw Exception("download of the final state failed");
+            }
+        bool every_instance_resident = r.resident; // (then the job below is four small copies per instance)
+        for (uint32_t g = 0; g < nGroups && every_instance_resident; g++)
+            for (uint32_t k = 0; k < grp[g]->B && every_instance_resident; k++) every_instance_resident = grp[g]->is_resident[k] != 0;
+        pool->run(batch, [&](uint32_t b) { collect_instance(r, b); }, every_instance_resident);
+    }
+
+    /// statistics of the run (lexls_lsi_batch_stats, h_rounds2) and, under LEXLS_LSI_TIMING, where its time went
+    void report(Run &r)
+    {
+        int rounds_fs = 0, rounds_sens = 0, rounds_step = 0;
+        double t_enq = 0.0, t_wait = 0.0;
+        for (uint32_t g = 0; g < nGroups; g++)
+        {
+            rounds_fs += grp[g]->rounds_fs;
+            rounds_sens += grp[g]->rounds_sens;
+            rounds_step += grp[g]->rounds_step + grp[g]->rounds_resident;
+            t_enq += grp[g]->t_enqueue;
+            t_wait += grp[g]->t_wait;
+        }
+        if (r.sw.timing && r.resident) // prefix reuse: what the lock-step stages could and what a per-instance loop would save
+        {
+            long sumK = 0, cnt = 0, worstK = 0, worstN = -1;
+            for (uint32_t g = 0; g < nGroups; g++)
+                for (uint32_t k = 0; k < grp[g]->B; k++)
+                    if (grp[g]->is_resident[k])
+                    {
+                        const int32_t *inf = grp[g]->rl.info(grp[g]->rws_host.data(), k);
+                        sumK += inf[6], cnt += inf[7];
+                        if (inf[7] > worstN) worstN = inf[7], worstK = inf[6];
+                    }
+            std::fprintf(stderr, "lexls_lsi_batch_solve: prefix reuse: %ld resident factorizations behind a working-set change, %.2f levels read back on average; the instance with the most (%ld): %.2f\n",
+                         cnt, cnt ? (double)sumK / cnt : 0.0, worstN, worstN > 0 ? (double)worstK / worstN : 0.0);
+        }
+        if (r.sw.timing)
+            std::fprintf(stderr, "lexls_lsi_batch_solve: setup = %.4f s reset / constraint upload + %.4f s LexLSI objects (batch created in %.4f s)\n", r.t_ctx, r.t_setup - r.t_ctx, t_create),
+            std::fprintf(stderr, "lexls_lsi_batch_solve: total %.4f s = setup %.4f + enqueue %.4f + wait for the GPU %.4f + host logic %.4f + rest %.4f (%u groups, %d+%d stages, %d with the step on the device)\n",
+                         BatchCtx::now() - r.t_begin, r.t_setup, t_enq, t_wait, r.t_host, BatchCtx::now() - r.t_begin - r.t_setup - t_enq - t_wait - r.t_host, nGroups,
+                         rounds_fs, rounds_sens, rounds_step);
+        if (r.h_rounds2) r.h_rounds2[0] = rounds_fs, r.h_rounds2[1] = rounds_sens;
+        last_stats[0] = rounds_fs, last_stats[1] = rounds_sens, last_stats[2] = rounds_step, last_stats[3] = (int32_t)nGroups;
+    }
+};

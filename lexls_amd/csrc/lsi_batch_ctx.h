@@ -1,0 +1,597 @@
+// One group of a lock-step LexLSI batch: its equality-solver handle, streams, the pinned per-round blocks, the slabs of the device-side step
+// and of the resident iterations, and the enqueueing of stages.  Included once, by lexls_lsi_capi.hip (it launches lsi_step_kernel / lsi_iterate_kernel).
+#pragma once
+#include <atomic>
+#include <chrono>
+#include <cstdio>
+#include <cstdlib>
+#include "lexls_internal.h"
+#include "lexls_lsi_device.h" // StepShape / StepArgs / lsi_step_kernel, ResidentArgs / lsi_iterate_kernel (shared with the persistent iteration kernel)
+
+namespace
+{
+    void hip_check(int rc)
+    {
+        if (rc != LEXLS_OK) throw Exception(std::string("liblexls_hip: ") + lexls_last_error());
+    }
+
+    /// The environment switches of the driver, read in two places only: these at the creation of a batch object ...
+    struct CreateSwitches
+    {
+        static const char *env(const char *name, const char *unset)
+        {
+            const char *e = std::getenv(name);
+            return e ? e : unset;
+        }
+        const bool resident = std::atoi(env("LEXLS_LSI_RESIDENT", "1")) != 0, device_step = std::atoi(env("LEXLS_LSI_DEVICE_STEP", "0")) != 0, spec_sens = std::atoi(env("LEXLS_LSI_SPECULATIVE_SENS", "1")) != 0,
+                   prefix_reuse = std::atoi(env("LEXLS_LSI_PREFIX_REUSE", "1")) != 0, host_staging = std::getenv("LEXLS_LSI_HOST_STAGING") != nullptr;
+        const char *const groups = std::getenv("LEXLS_LSI_GROUPS");                                   // NULL: not given
+        const double pool_spin_seconds = 1e-6 * std::atof(env("LEXLS_POOL_SPIN_US", "300")); // diagnostic: 0 = the pool's workers sleep at once
+    };
+    /// ... and these once per lexls_lsi_batch_run / lexls_lsi_batch_get_lambda
+    struct RunSwitches
+    {
+        const bool timing = std::getenv("LEXLS_LSI_TIMING") != nullptr;
+        const bool stamps_dump = std::getenv("LEXLS_FUSED_STAMPS_DUMP") != nullptr; // (a -DLEXLS_FUSED_STAMPS build leaves its phase clocks in the multiplier buffer)
+    };
+
+    /// typed window into a pinned block (the per-round arrays of a batch sit in blocks laid out like the handle's device slabs)
+    template <class T>
+    struct View
+    {
+        T *p     = NULL;
+        size_t n = 0;
+        void bind(void *base, uint64_t offset, size_t n_, T v)
+        {
+            p = reinterpret_cast<T *>(static_cast<char *>(base) + offset);
+            n = n_;
+            std::fill(p, p + n, v);
+        }
+        T *data() { return p; }
+        T &operator[](size_t i) { return p[i]; }
+        T *begin() { return p; }
+        T *end() { return p + n; }
+    };
+
+    /// host array in pinned memory (hipHostMalloc): the per-round copies of a lock-step batch are enqueued, not waited for
+    /// (lexls_lse_set_deferred_sync), so their sources / destinations must be DMA-able and stable until the round's synchronize
+    template <class T>
+    struct Pinned
+    {
+        T *p     = NULL;
+        size_t n = 0;
+        Pinned() {}
+        Pinned(const Pinned &)            = delete;
+        Pinned &operator=(const Pinned &) = delete;
+        ~Pinned()
+        {
+            if (p) (void)hipHostFree(p);
+        }
+        void assign(size_t n_, T v)
+        {
+            if (p) (void)hipHostFree(p);
+            p = NULL;
+            if (hipHostMalloc((void **)&p, (n_ ? n_ : 1) * sizeof(T), hipHostMallocDefault) != hipSuccess) throw Exception("hipHostMalloc failed (lock-step LSI batch)");
+            n = n_;
+            std::fill(p, p + n, v);
+        }
+        T *data() { return p; }
+        T &operator[](size_t i) { return p[i]; }
+        T *begin() { return p; }
+        T *end() { return p + n; }
+    };
+
+    /// elements of one objective's block in an instance's constraint data: [A | lb | ub], or [lb | ub] for simple bounds
+    inline uint64_t objective_elems(uint32_t dim, int32_t type, uint32_t nVar) { return (uint64_t)dim * (type == 1 ? 2 : nVar + 2); }
+    /// the per-objective part of a shape (nObj <= STEP_MAX_OBJ); returns the elements of one instance's constraint data
+    inline uint64_t fill_shape(StepShape &sh, const uint32_t *dims, const int32_t *types, uint32_t nVar)
+    {
+        uint64_t o = 0;
+        uint32_t f = 0;
+        for (uint32_t k = 0; k < sh.nObj; k++)
+        {
+            sh.dim[k] = dims[k], sh.simple[k] = types[k] == 1, sh.first[k] = f, sh.off[k] = o;
+            o += objective_elems(dims[k], types[k], nVar);
+            f += dims[k];
+        }
+        return o;
+    }
+
+    /// Working-set slab of the device-side step, as lsi_step_kernel reads it (StepArgs): [mode B | ctr_state B x total | inact_pos (u16) B x total],
+    /// every part 16-aligned.  base: the host mirror or the device slab.
+    struct StepSlab
+    {
+        size_t total = 0, o_state = 0, o_pos = 0, bytes = 0;
+        explicit StepSlab(size_t B = 0, size_t total_ = 0) : total(total_)
+        {
+            o_state = (B + 15) & ~size_t(15);
+            o_pos   = (o_state + B * total + 15) & ~size_t(15);
+            bytes   = o_pos + 2 * B * total;
+        }
+        uint8_t *mode(uint8_t *base) const { return base; }
+        uint8_t *ctr_state(uint8_t *base, size_t b = 0) const { return base + o_state + b * total; }
+        uint16_t *inact_pos(uint8_t *base, size_t b = 0) const { return reinterpret_cast<uint16_t *>(base + o_pos) + b * total; }
+    };
+    /// Slab of the resident iterations, as lsi_iterate_kernel reads it (ResidentArgs): ctr_state | alive | act | inact | inact_pos | na | info |
+    /// finished, every part 256-aligned.  base: the host mirror or the device slab; b: the instance.
+    struct ResidentSlab
+    {
+        size_t total = 0, o_alive = 0, o_act = 0, o_inact = 0, o_ipos = 0, o_na = 0, o_info = 0, o_fin = 0, bytes = 0;
+        explicit ResidentSlab(size_t B = 0, size_t total_ = 0) : total(total_)
+        {
+            auto up  = [](size_t v) { return (v + 255) & ~size_t(255); };
+            size_t o = up(B * total); // ctr_state at 0
+            o_alive = o, o = up(o + B);
+            o_act = o, o = up(o + 2 * B * total);
+            o_inact = o, o = up(o + 2 * B * total);
+            o_ipos = o, o = up(o + 2 * B * total);
+            o_na = o, o = up(o + 2 * B * RESIDENT_NA_STRIDE);
+            o_info = o, o = up(o + 4 * B * RESIDENT_INFO_STRIDE);
+            o_fin = o, o = up(o + 16);
+            bytes = o;
+        }
+        uint8_t *ctr_state(char *base, size_t b = 0) const { return reinterpret_cast<uint8_t *>(base) + b * total; }
+        uint8_t *alive(char *base) const { return reinterpret_cast<uint8_t *>(base + o_alive); }
+        uint16_t *act(char *base, size_t b = 0) const { return reinterpret_cast<uint16_t *>(base + o_act) + b * total; }
+        uint16_t *inact(char *base, size_t b = 0) const { return reinterpret_cast<uint16_t *>(base + o_inact) + b * total; }
+        uint16_t *inact_pos(char *base, size_t b = 0) const { return reinterpret_cast<uint16_t *>(base + o_ipos) + b * total; }
+        uint16_t *na(char *base, size_t b = 0) const { return reinterpret_cast<uint16_t *>(base + o_na) + b * RESIDENT_NA_STRIDE; }
+        int32_t *info(char *base, size_t b = 0) const { return reinterpret_cast<int32_t *>(base + o_info) + b * RESIDENT_INFO_STRIDE; }
+        uint32_t *finished(char *base) const { return reinterpret_cast<uint32_t *>(base + o_fin); }
+    };
+
+    /// an instance's [x | v | A x] into its row of a state array (sh.SD doubles) ...
+    inline void pack_state(double *st, const StepShape &sh, const dVectorType &x, const std::vector<internal::Objective> &obj)
+    {
+        for (uint32_t j = 0; j < sh.n; j++) st[j] = x(j);
+        for (uint32_t k = 0; k < sh.nObj; k++)
+        {
+            const dVectorType &v = obj[k].get_v(), &ax = obj[k].get_Ax();
+            for (uint32_t i = 0; i < sh.dim[k]; i++)
+            {
+                st[sh.n + sh.first[k] + i]            = v(i);
+                st[sh.n + sh.total + sh.first[k] + i] = ax(i);
+            }
+        }
+    }
+    /// ... and x / v (NULL: not wanted) back out of one
+    inline void unpack_state(const double *st, size_t n, size_t total, double *x, double *v)
+    {
+        std::copy(st, st + n, x);
+        if (v) std::copy(st + n, st + n + total, v);
+    }
+
+    /// The one walk over an instance's working set (workingset.h order): active(k, a, ctr, type) for the a-th active constraint of objective k,
+    /// inactive(k, i, ctr) for its i-th inactive one
+    template <class A, class I>
+    inline void walk_working_set(const std::vector<internal::Objective> &obj, uint32_t nObj, A &&active, I &&inactive)
+    {
+        for (uint32_t k = 0; k < nObj; k++)
+        {
+            for (Index a = 0; a < obj[k].getActiveCtrCount(); a++) active(k, a, obj[k].getActiveCtrIndex(a), obj[k].getActiveCtrType(a));
+            for (Index i = 0; i < obj[k].getInactiveCtrCount(); i++) inactive(k, i, obj[k].getInactiveCtrIndex(i));
+        }
+    }
+
+    struct BatchCtx
+    {
+        lexls_lse_t h = NULL;
+        hipStream_t stream = NULL; // every group of a lock-step batch has its own stream: group A's kernels run while group B's host logic does
+        hipStream_t stream_sens = NULL; // the sensitivity kernel of a stage serves other instances than its l-QR kernel: they run side by side
+        hipEvent_t ev_uploaded = NULL, ev_sens_done = NULL;
+        bool stage_fs = false, stage_sens = false; // what the stage in flight serves
+        uint32_t B = 0, n = 0, nObjL = 0, cap = 0;
+        size_t pstride = 0;
+        std::vector<uint32_t> maxdim, totalrank;
+        std::vector<double> x;
+        lexls_round_layout lay;
+        Pinned<char> in_block, out_block; // pinned mirrors of the handle's round slabs: ONE copy each per stage
+        View<uint32_t> dims, nfixed, fixed_idx, row_src, row_ld, tr_dl; // row_src/row_ld: B x cap, where each LOD row comes from (device gather)
+        View<double> fixed_val, maxabs, x_dl;
+        double *lod = NULL; // B x cap x (n+1), PINNED: host-staging fallback, uploaded every active-set round
+        View<uint8_t> fixed_type, ctr_type, skip;
+        View<int32_t> sens, objidx;
+        std::vector<double> reg_factor;        // B x nObjL regularization factors (host copy; uploaded when they change)
+        int reg_type = 0;                      // LexLS::RegularizationType shared by the batch
+        double reg_variable = 0.0;
+        uint32_t reg_cg_iters = 10;
+        std::atomic<bool> reg_dirty{false};
+        bool gather = false;                   // constraint data resident on the device: only row references travel per round
+        // ---- step of an iteration on the device (lsi_step_kernel) ----
+        bool device_step = false;
+        StepShape shape;
+        double *d_state = NULL, *d_state_in = NULL, *d_res = NULL;
+        uint32_t *d_var = NULL;
+        uint8_t *d_wset = NULL;
+        Pinned<double> state_host, res_host;       // B x SD (hand-over staging, final download), B x 4
+        StepSlab wl;                               // layout of d_wset / wset_host
+        Pinned<uint8_t> wset_host;
+        std::vector<uint8_t> on_device;            // per instance: x / v / A x live on the device
+        std::atomic<bool> handover{false};         // some instance put its state into state_host for the next stage
+        bool spec_sens  = false; // every factorization is followed by its removal search in the same stage (results used if the step is not blocked)
+        // ---- resident iterations (lsi_iterate_kernel): x / v / A x, the working sets and the counters of an instance live on the device ----
+        bool resident = false; // buffers exist (the structure allows it)
+        StepShape rshape;
+        uint32_t r_off = 0;
+        double *d_rstate = NULL;
+        uint32_t *d_rvar = NULL;
+        ResidentSlab rl; // layout of d_rws / rws_host
+        char *d_rws = NULL;
+        Pinned<char> rws_host;
+        Pinned<double> rstate_host;
+        Pinned<uint32_t> fin_host;
+        std::vector<uint8_t> is_resident; // per instance: handed over to the device
+        uint32_t n_resident  = 0;
+        int rounds_resident  = 0;
+        std::vector<int32_t> iterations_at_handover;
+        int rounds_fs_at_handover = 0, rounds_sens_at_handover = 0;
+        bool fused_all = false, fused_refused = false; // the rest of the resident iterations is one persistent launch / the shape has none
+        const char *resident_kernel = "";              // the kernel that served the resident iterations of this run (download_resident)
+        int rounds_fs = 0, rounds_sens = 0, rounds_step = 0;
+        double t_enqueue = 0, t_wait = 0; // seconds, reported when LEXLS_LSI_TIMING is set
+        static double now() { return std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count(); }
+
+        void create(int device, uint32_t B_, uint32_t n_, uint32_t nObjL_, const uint32_t *maxdim_, bool gather_, bool prefix_reuse)
+        {
+            gather = gather_, B = B_, n = n_, nObjL = nObjL_;
+            maxdim.assign(maxdim_, maxdim_ + nObjL);
+            cap = 0;
+            for (uint32_t k = 0; k < nObjL; k++) cap += maxdim[k];
+            pstride = (size_t)cap * (n + 1);
+            hip_check(lexls_lse_create(&h, device, B, n, nObjL, maxdim.data()));
+            if (prefix_reuse) hip_check(lexls_lse_set_prefix_reuse(h, 1)); // in the resident iterations; off: everything is factorized in every iteration
+            if (hipStreamCreateWithFlags(&stream, hipStreamNonBlocking) != hipSuccess || hipStreamCreateWithFlags(&stream_sens, hipStreamNonBlocking) != hipSuccess ||
+                hipEventCreateWithFlags(&ev_uploaded, hipEventDisableTiming) != hipSuccess || hipEventCreateWithFlags(&ev_sens_done, hipEventDisableTiming) != hipSuccess)
+                throw Exception("hipStreamCreate / hipEventCreate failed (lock-step LSI batch)");
+            hip_check(lexls_lse_set_stream(h, stream));
+            hip_check(lexls_lse_round_layout(h, &lay));
+            in_block.assign(lay.in_bytes, 0);
+            out_block.assign(lay.out_bytes, 0);
+            if (!gather) need_staging();
+            reset();
+        }
+
+        /// host staging of whole problems (pinned, B x cap x (n+1)): only for runs without the device-side gather
+        void need_staging()
+        {
+            if (lod) return;
+            if (hipHostMalloc((void **)&lod, 8 * (size_t)B * pstride, hipHostMallocDefault) != hipSuccess) throw Exception("hipHostMalloc failed for the LSI staging buffer");
+            std::memset(lod, 0, 8 * (size_t)B * pstride);
+        }
+
+        /// buffers of the device-side step for a batch of this structure (once per batch object)
+        void create_step(const StepShape &sh)
+        {
+            shape = sh;
+            wl    = StepSlab(B, sh.total);
+            if (hipMalloc((void **)&d_state, 8 * (size_t)B * sh.SD) != hipSuccess || hipMalloc((void **)&d_state_in, 8 * (size_t)B * sh.SD) != hipSuccess ||
+                hipMalloc((void **)&d_res, 8 * (size_t)B * 4) != hipSuccess || hipMalloc((void **)&d_var, 4 * (size_t)B * (sh.dim0 ? sh.dim0 : 1)) != hipSuccess ||
+                hipMalloc((void **)&d_wset, wl.bytes) != hipSuccess)
+                throw Exception("hipMalloc failed (device-side LSI step)");
+            state_host.assign((size_t)B * sh.SD, 0.0);
+            res_host.assign((size_t)B * 4, 0.0);
+            wset_host.assign(wl.bytes, 0);
+            on_device.assign(B, 0);
+            device_step = true;
+        }
+        /// buffers of the resident iterations for a batch of this structure (once per batch object)
+        void create_resident(const StepShape &sh, uint32_t off)
+        {
+            rshape = sh;
+            r_off  = off;
+            rl     = ResidentSlab(B, sh.total);
+            if (hipMalloc((void **)&d_rstate, 8 * (size_t)B * sh.SD) != hipSuccess || hipMalloc((void **)&d_rws, rl.bytes) != hipSuccess ||
+                hipMalloc((void **)&d_rvar, 4 * (size_t)B * (sh.dim0 ? sh.dim0 : 1)) != hipSuccess)
+                throw Exception("hipMalloc failed (resident LSI iterations)");
+            rws_host.assign(rl.bytes, 0);
+            rstate_host.assign((size_t)B * sh.SD, 0.0);
+            fin_host.assign(4, 0u);
+            is_resident.assign(B, 0);
+            resident = true;
+        }
+
+        /// instance b (its equality problem of a regular iteration is formed and staged in the in block) leaves the host: state, working
+        /// sets in list order (workingset.h) and counters go into the hand-over slabs
+        template <class LSI>
+        void hand_over(uint32_t b, const LSI &inst)
+        {
+            char *base = rws_host.data();
+            pack_state(rstate_host.data() + (size_t)b * rshape.SD, rshape, inst.get_x(), inst.getObjectives());
+            uint8_t *cs = rl.ctr_state(base, b);
+            uint16_t *act = rl.act(base, b), *ina = rl.inact(base, b), *ip = rl.inact_pos(base, b), *na = rl.na(base, b);
+            std::memset(cs, 0, rshape.total);
+            for (uint32_t k = 0; k < rshape.nObj; k++) na[k] = static_cast<uint16_t>(inst.getObjectives()[k].getActiveCtrCount());
+            walk_working_set(inst.getObjectives(), rshape.nObj, [&](uint32_t k, Index a, Index c, ConstraintActivationType t) { act[rshape.first[k] + a] = static_cast<uint16_t>(c), cs[rshape.first[k] + c] = static_cast<uint8_t>(t); },
+                             [&](uint32_t k, Index i, Index c) { ina[rshape.first[k] + i] = static_cast<uint16_t>(c), ip[rshape.first[k] + c] = static_cast<uint16_t>(i); });
+            int32_t *info = rl.info(base, b);
+            info[0]       = static_cast<int32_t>(inst.getStatus());
+            info[1]       = static_cast<int32_t>(inst.getIterationsCount());
+            info[2]       = static_cast<int32_t>(inst.getActivationsCount());
+            info[3]       = static_cast<int32_t>(inst.getDeactivationsCount());
+            info[4]       = static_cast<int32_t>(inst.getFactorizationsCount());
+            info[5]       = static_cast<int32_t>(totalrank[b]);
+            info[6] = info[7] = 0; // prefix reuse: levels read back, summed over the resident factorizations; their number
+            rl.alive(base)[b] = 1;
+            is_resident[b]    = 1; // (its staged equality problem is served by the first resident stage, followed by its removal sweep)
+        }
+
+        ResidentArgs resident_args(int32_t max_factorizations)
+        {
+            ResidentArgs ra;
+            std::memset(&ra, 0, sizeof(ra));
+            void *d_out = NULL;
+            hip_check(lexls_lse_device_ptr(h, LEXLS_ARRAY_X, &d_out)); // x is the head of the out slab (lexls_lse_round_layout)
+            char *out = static_cast<char *>(d_out), *in = lexls_internal_round_in(h);
+            ra.sh     = rshape;
+            ra.B = B, ra.cap = cap, ra.nObjL = nObjL, ra.off = r_off;
+            ra.max_factorizations = max_factorizations;
+            ra.cdata     = lexls_internal_cdata(h);
+            ra.var       = d_rvar;
+            ra.x_lse     = reinterpret_cast<const double *>(out + lay.x);
+            ra.totalrank = reinterpret_cast<const uint32_t *>(out + lay.total_rank);
+            ra.sens      = reinterpret_cast<const int32_t *>(out + lay.found);
+            ra.state     = d_rstate;
+            ra.ctr_state = rl.ctr_state(d_rws), ra.alive = rl.alive(d_rws), ra.act = rl.act(d_rws), ra.inact = rl.inact(d_rws), ra.inact_pos = rl.inact_pos(d_rws);
+            ra.na = rl.na(d_rws), ra.info = rl.info(d_rws), ra.finished = rl.finished(d_rws);
+            ra.dims      = reinterpret_cast<uint32_t *>(in + lay.dims);
+            ra.nfixed    = reinterpret_cast<uint32_t *>(in + lay.nfixed);
+            ra.fixed_idx = reinterpret_cast<uint32_t *>(in + lay.fixed_idx);
+            ra.fixed_val = reinterpret_cast<double *>(in + lay.fixed_val);
+            ra.skip      = reinterpret_cast<uint8_t *>(in + lay.skip);
+            ra.objidx    = reinterpret_cast<int32_t *>(in + lay.obj_index);
+            ra.row_src   = reinterpret_cast<uint32_t *>(in + lay.row_src);
+            ra.row_ld    = reinterpret_cast<uint32_t *>(in + lay.row_ld);
+            ra.fixed_type = reinterpret_cast<uint8_t *>(in + lay.fixed_type);
+            ra.ctr_type   = reinterpret_cast<uint8_t *>(in + lay.ctr_type);
+            ra.resume     = lexls_internal_resume_levels(h);
+            return ra;
+        }
+
+        /// the handed-over instances start: slabs up, then `count` whole iterations are enqueued (nothing is waited for)
+        void begin_resident()
+        {
+            *rl.finished(rws_host.data()) = 0u;
+            if (hipMemcpyAsync(d_rws, rws_host.data(), rl.bytes, hipMemcpyHostToDevice, stream) != hipSuccess ||
+                hipMemcpyAsync(d_rstate, rstate_host.data(), 8 * (size_t)B * rshape.SD, hipMemcpyHostToDevice, stream) != hipSuccess)
+                throw Exception("hipMemcpyAsync failed (resident hand-over)");
+            rounds_resident = 0;
+            fused_all       = false;
+            fused_refused   = false; // (decided per run: the next one may be of another kind — plain / regularized — or under another LEXLS_LSI_NO_FUSED)
+            rounds_fs_at_handover   = rounds_fs;
+            rounds_sens_at_handover = rounds_sens;
+            iterations_at_handover.assign(B, 0);
+            for (uint32_t b = 0; b < B; b++) iterations_at_handover[b] = rl.info(rws_host.data(), b)[1];
+        }
+        void enqueue_resident(int count, double tolW, double tolC, int32_t max_factorizations)
+        {
+            const double t0        = now();
+            const ResidentArgs ra  = resident_args(max_factorizations);
+            for (int i = 0; i < count && !fused_all; i++)
+            {
+                if (rounds_resident == 0)
+                    hip_check(lexls_internal_upload_round_trusted(h, in_block.data(), 1)); // the problems the host formed last
+                else
+                {
+                    // every iteration that is left, of every instance, in ONE persistent launch (lsi_fused_impl.h) where the shape has one: an
+                    // instance runs l-QR -> removal sweep -> iteration until it stops, at most max_factorizations times
+                    if (!fused_refused)
+                    {
+                        const int rc = lexls_internal_resident_fused(h, rshape.dim0 ? 1 : 0, max_factorizations > 0 ? max_factorizations : 1, tolW, tolC, &ra, sizeof(ra));
+                        if (rc == LEXLS_OK)
+                        {
+                            fused_all = true;
+                            rounds_resident++, rounds_fs++, rounds_sens++;
+                            break;
+                        }
+                        if (rc != 1) hip_check(rc);
+                        fused_refused = true;
+                    }
+                    hip_check(lexls_internal_round_resident(h, rshape.dim0 ? 1 : 0)); // the problems lsi_iterate_kernel formed
+                    lexls_internal_arm_resume(h);                                     // ... and the levels it found unchanged
+                }
+                hip_check(lexls_lse_factorize_solve(h, 1));
+                hip_check(lexls_lse_sensitivity_resident(h, tolW, tolC)); // speculative: used when the step is not blocked
+                hipLaunchKernelGGL(lsi_iterate_kernel, dim3((B + 3) / 4), dim3(256), 4 * resident_lds_per_wave(rshape.SD, rshape.total), stream, ra);
+                if (hipGetLastError() != hipSuccess) throw Exception("lsi_iterate_kernel launch failed");
+                rounds_resident++, rounds_fs++, rounds_sens++;
+            }
+            if (hipMemcpyAsync(fin_host.data(), rl.finished(d_rws), 4, hipMemcpyDeviceToHost, stream) != hipSuccess) throw Exception("hipMemcpyAsync failed (finished count)");
+            t_enqueue += now() - t0;
+        }
+        /// waits for what is enqueued; true when every handed-over instance has stopped
+        bool resident_done()
+        {
+            finish_stage();
+            return fin_host[0] >= n_resident;
+        }
+        /// the phase clocks a -DLEXLS_FUSED_STAMPS build of the persistent launch leaves in the multiplier buffer
+        void dump_stamps()
+        {
+            std::vector<double> lam((size_t)B * (n + cap));
+            hip_check(lexls_lse_get_lambda(h, lam.data()));
+            hip_check(lexls_lse_synchronize(h));
+            double sum[6] = {0, 0, 0, 0, 0, 0}, most[6] = {0, 0, 0, 0, 0, 0};
+            for (uint32_t b = 0; b < B; b++)
+            {
+                const double *o = lam.data() + (size_t)b * (n + cap);
+                for (int i = 0; i < 6; i++) sum[i] += o[i];
+                if (o[4] > most[4])
+                    for (int i = 0; i < 6; i++) most[i] = o[i];
+            }
+            std::fprintf(stderr, "persistent launch, cycles per iteration [l-QR | step | removal search (per iteration) | finish], iterations, searches: all instances %.0f | %.0f | %.0f | %.0f, %.0f, %.0f; the longest-running one %.0f | %.0f | %.0f | %.0f, %.0f, %.0f\n",
+                         sum[0] / sum[4], sum[1] / sum[4], sum[2] / sum[4], sum[3] / sum[4], sum[4], sum[5], most[0] / most[4], most[1] / most[4], most[2] / most[4], most[3] / most[4], most[4], most[5]);
+        }
+        void download_resident(bool stamps_dump)
+        {
+            if (hipMemcpyAsync(rws_host.data(), d_rws, rl.bytes, hipMemcpyDeviceToHost, stream) != hipSuccess ||
+                hipMemcpyAsync(rstate_host.data(), d_rstate, 8 * (size_t)B * rshape.SD, hipMemcpyDeviceToHost, stream) != hipSuccess ||
+                hipStreamSynchronize(stream) != hipSuccess)
+                throw Exception("download of the resident state failed");
+            resident_kernel = lexls_lse_last_kernel(h); // the persistent launch, or the l-QR kernel of the last stage
+            if (fused_all && stamps_dump) dump_stamps();
+            if (fused_all) // the persistent launch: the stages it ran = the iterations of the instance that ran longest (statistics only)
+            {
+                int32_t most = 0;
+                for (uint32_t b = 0; b < B; b++)
+                    if (is_resident[b])
+                    {
+                        const int32_t d = rl.info(rws_host.data(), b)[1] - iterations_at_handover[b];
+                        most            = d > most ? d : most;
+                    }
+                rounds_resident = most;
+                rounds_fs       = rounds_fs_at_handover + most;
+                rounds_sens     = rounds_sens_at_handover + most;
+            }
+        }
+        uint8_t *mode() { return wl.mode(wset_host.data()); }
+
+        /// per-solve state: what a freshly created context holds (a context serves many lexls_lsi_batch_run calls)
+        void reset()
+        {
+            dims.bind(in_block.data(), lay.dims, (size_t)B * nObjL, 0);
+            nfixed.bind(in_block.data(), lay.nfixed, B, 0);
+            fixed_idx.bind(in_block.data(), lay.fixed_idx, (size_t)B * n, 0);
+            fixed_val.bind(in_block.data(), lay.fixed_val, (size_t)B * n, 0.0);
+            skip.bind(in_block.data(), lay.skip, B, 0);
+            objidx.bind(in_block.data(), lay.obj_index, B, -1);
+            row_src.bind(in_block.data(), lay.row_src, (size_t)B * cap, 0);
+            row_ld.bind(in_block.data(), lay.row_ld, (size_t)B * cap, 0);
+            fixed_type.bind(in_block.data(), lay.fixed_type, (size_t)B * n, static_cast<uint8_t>(CTR_ACTIVE_UB));
+            ctr_type.bind(in_block.data(), lay.ctr_type, (size_t)B * cap, static_cast<uint8_t>(CTR_INACTIVE));
+            x_dl.bind(out_block.data(), lay.x, (size_t)B * n, 0.0);
+            tr_dl.bind(out_block.data(), lay.total_rank, B, 0);
+            sens.bind(out_block.data(), lay.found, (size_t)B * 3, 0);
+            maxabs.bind(out_block.data(), lay.max_abs, B, 0.0);
+            if (lod) std::memset(lod, 0, 8 * (size_t)B * pstride);
+            x.assign((size_t)B * n, 0.0);
+            totalrank.assign(B, 0);
+            reg_factor.assign((size_t)B * nObjL, 0.0);
+            rounds_fs = rounds_sens = rounds_step = 0;
+            t_enqueue = t_wait = 0.0;
+            if (device_step)
+            {
+                std::fill(wset_host.begin(), wset_host.end(), 0);
+                std::fill(on_device.begin(), on_device.end(), 0);
+                handover.store(false);
+            }
+            stage_fs = stage_sens = false;
+            if (resident)
+            {
+                std::fill(rws_host.begin(), rws_host.end(), 0);
+                std::fill(is_resident.begin(), is_resident.end(), 0);
+                n_resident      = 0;
+                rounds_resident = 0;
+            }
+        }
+        ~BatchCtx()
+        {
+            if (h) lexls_lse_destroy(h);
+            void *dev[] = {d_state, d_state_in, d_res, d_var, d_wset, d_rstate, d_rvar, d_rws};
+            for (void *q : dev)
+                if (q) (void)hipFree(q);
+            if (stream) (void)hipStreamDestroy(stream);
+            if (stream_sens) (void)hipStreamDestroy(stream_sens);
+            if (ev_uploaded) (void)hipEventDestroy(ev_uploaded);
+            if (ev_sens_done) (void)hipEventDestroy(ev_sens_done);
+            if (lod) (void)hipHostFree(lod);
+        }
+
+        /// working sets up, (state hand-over,) lsi_step_kernel, verdicts back: enqueued behind the equality solve of the stage
+        void enqueue_step()
+        {
+            if (hipMemcpyAsync(d_wset, wset_host.data(), wl.bytes, hipMemcpyHostToDevice, stream) != hipSuccess) throw Exception("hipMemcpyAsync failed (working sets)");
+            if (handover.exchange(false) &&
+                hipMemcpyAsync(d_state_in, state_host.data(), 8 * (size_t)B * shape.SD, hipMemcpyHostToDevice, stream) != hipSuccess)
+                throw Exception("hipMemcpyAsync failed (state hand-over)");
+            void *d_x = NULL;
+            hip_check(lexls_lse_device_ptr(h, LEXLS_ARRAY_X, &d_x));
+            StepArgs sa;
+            sa.sh        = shape;
+            sa.B         = B;
+            sa.cdata     = lexls_internal_cdata(h);
+            sa.var       = d_var;
+            sa.x_lse     = static_cast<const double *>(d_x);
+            sa.state     = d_state;
+            sa.state_in  = d_state_in;
+            sa.mode = wl.mode(d_wset), sa.ctr_state = wl.ctr_state(d_wset), sa.inact_pos = wl.inact_pos(d_wset);
+            sa.res       = d_res;
+            hipLaunchKernelGGL(lsi_step_kernel, dim3((B + 3) / 4), dim3(256), 8 * (size_t)shape.SD * 4, stream, sa);
+            if (hipGetLastError() != hipSuccess ||
+                hipMemcpyAsync(res_host.data(), d_res, 8 * (size_t)B * 4, hipMemcpyDeviceToHost, stream) != hipSuccess)
+                throw Exception("lsi_step_kernel launch / result copy failed");
+        }
+
+        /// Enqueue ONE stage on this group's stream: a batched factorize+solve for the instances with skip == 0 (if serve_fs) and a batched
+        /// ObjectiveSensitivity for the instances with objidx >= 0 (if serve_sens) — disjoint sets of instances.  Nothing is waited for.
+        void enqueue_stage(bool serve_fs, bool serve_sens, bool use_step, bool x_needed, double tolW, double tolC)
+        {
+            const double t0 = now();
+            stage_fs   = serve_fs;
+            stage_sens = serve_sens;
+            if (serve_fs)
+            {
+                if (reg_type != 0 && reg_dirty.exchange(false)) // the factors are the same every round: uploaded once (this call synchronises)
+                {
+                    hip_check(lexls_lse_set_cg_iterations(h, reg_cg_iters));
+                    hip_check(lexls_lse_set_regularization(h, reg_type, reg_factor.data(), 1, reg_variable));
+                }
+                // dims, fixed variables, types, skip flags, sensitivity levels and row references: one copy (+ the gather kernel)
+                hip_check(lexls_internal_upload_round_trusted(h, in_block.data(), gather ? 1 : 0));
+                if (serve_sens && hipEventRecord(ev_uploaded, stream) != hipSuccess) throw Exception("hipEventRecord failed");
+                if (!gather) hip_check(lexls_lse_set_problem_host(h, lod));
+                hip_check(lexls_lse_factorize_solve(h, 1));
+                rounds_fs++;
+                if (use_step) rounds_step++;
+                if (use_step) enqueue_step(); // the step of the iteration, right behind its equality solve (same stream)
+            }
+            if (serve_sens)
+            {
+                if (serve_fs && !spec_sens)
+                {
+                    // disjoint instances (a problem is either re-factorised or asked for multipliers): the two kernels are both
+                    // latency-bound at these batch sizes and share the chip — second stream, joined again before the download
+                    if (hipStreamWaitEvent(stream_sens, ev_uploaded, 0) != hipSuccess) throw Exception("hipStreamWaitEvent failed");
+                    hip_check(lexls_lse_set_stream(h, stream_sens));
+                    hip_check(lexls_lse_sensitivity_resident(h, tolW, tolC));
+                    hip_check(lexls_lse_set_stream(h, stream));
+                    if (hipEventRecord(ev_sens_done, stream_sens) != hipSuccess || hipStreamWaitEvent(stream, ev_sens_done, 0) != hipSuccess)
+                        throw Exception("hipEventRecord / hipStreamWaitEvent failed");
+                }
+                else if (serve_fs)
+                    hip_check(lexls_lse_sensitivity_resident(h, tolW, tolC)); // behind the l-QR kernel: it reads the factors just made
+                else
+                    hip_check(lexls_lse_sensitivity(h, objidx.data(), 0, tolW, tolC));
+                rounds_sens++;
+            }
+            // x / total rank / sensitivity verdicts in one copy.  (The CORRECT_SIGN_OF_LAMBDA marks ObjectiveSensitivity leaves on the
+            // device, lexlse.h:866-987, only matter between the levels of ONE removal search — which is one launch here,
+            // lexls_lse_set_sensitivity_scan — so they never have to come back: the next equality problem sets every row's type anew.)
+            if (x_needed || !serve_fs)
+                hip_check(lexls_lse_download_round(h, out_block.data(), NULL));
+            else
+            {
+                // every equality solve of this stage feeds a device-side step: x stays on the device, only the tail of the out slab
+                // (total ranks, sensitivity verdicts) comes back
+                void *d_out = NULL;
+                hip_check(lexls_lse_device_ptr(h, LEXLS_ARRAY_X, &d_out)); // x is the head of the out slab (lexls_lse_round_layout)
+                if (hipMemcpyAsync(out_block.data() + lay.total_rank, static_cast<char *>(d_out) + lay.total_rank, lay.out_bytes - lay.total_rank, hipMemcpyDeviceToHost,
+                                   stream) != hipSuccess)
+                    throw Exception("hipMemcpyAsync failed (results without x)");
+            }
+            t_enqueue += now() - t0;
+        }
+
+        /// wait for the stage in flight (the ONE synchronisation of a stage); its results are taken over per instance, on the worker pool
+        void finish_stage()
+        {
+            const double t0 = now();
+            hip_check(lexls_lse_synchronize(h));
+            t_wait += now() - t0;
+        }
+        void take_solution(uint32_t b)
+        {
+            std::copy(x_dl.begin() + (size_t)b * n, x_dl.begin() + (size_t)(b + 1) * n, x.begin() + (size_t)b * n);
+            totalrank[b] = tr_dl[b];
+        }
+    };
+} // namespace
