@@ -207,7 +207,8 @@ const char *lexls_lse_last_kernel(lexls_lse_t h);
  *                  its DATA move by one ulp, is solved to a small multiple of that sensitivity instead (scripts/soak_qtol.py: 21 k
  *                  random batches, 92 such problems beyond 1e-10, at most 20 x their one-ulp sensitivity — 47 x once levels of eight rows
  *                  joined the soak, 91 x on lqr_mfma's soak; the soaks' bound is 100 x, a random one-ulp perturbation being a LOWER
- *                  estimate of what rounding does to such a problem —; pivots and ranks exact in all).
+ *                  estimate of what rounding does to such a problem —; pivots and ranks exact in all.  Policy 10 opens hierarchies of
+ *                  SHORT levels, where badly scaled data have exceeded that multiple: see policy 10 below).
  *                  PIVOT RULE under (T).  The reference takes the first maximum of the down-dated column norms (lexlse.h:205-206).  lqr_mfma compares
  *                  the norms by VALUE (whole doubles; equal values: the smallest position) — the reference's rule on this kernel's own norms.
  *                  lqr_qtol compares them in ONE max butterfly on a packed key whose low 12 mantissa bits carry the position: two candidates whose
@@ -235,9 +236,22 @@ const char *lexls_lse_last_kernel(lexls_lse_t h);
  *       else as 6;  8 = the same kernel with one problem per wavefront (four wavefronts per SIMD);  9 = with four problems per wavefront (the IK
  *       shape only).  Automatic dispatch (0) takes lqr_qtol first — the faster one on MI355X (41 us against 57 us per 4096 IK problems) — and
  *       lqr_mfma for the shapes lqr_qtol's slices do not hold.
+ *   10 = as 6, and additionally lqr_qtol's RAGGED instantiations (T) for x-only solves whose levels have AT MOST 12 rows each — per-problem
+ *       dimensions (lexls_lse_set_obj_dim(..., per_problem = 1)), any mix, empty levels included — under lqr_qtol's other conditions (no fixed
+ *       variables, no regularization, factor not kept, <= 8 levels, n <= 40 in practice).  A batch whose levels all have 12 (or all 8) rows takes
+ *       the same kernel as under 6; what the ragged form does not serve goes where 6 sends it.  Opt-in: policy 0 keeps such batches on (B).
+ *       Contract (T), same 2^-40 position window of the pivot rule: a level of d rows is factorized as that level with zero rows appended,
+ *       which changes neither pivots nor x (tests/test_ragged_padding_oracle.py); x is bit-identical to lqr_qtol's on the zero-padded problem.
+ *       MEASURED on hierarchies of short levels (scripts/soak_qtol_ragged.py, 13 k random batches, pivots and ranks exact in all): on data whose
+ *       rows are scaled over four and columns over six decades, 2 problems (levels of 2 / 7 / 3 / 2 and of <= 12 rows, n = 14 and 11) came out at
+ *       1.12e-10 and 1.23e-10 — just beyond 1e-10 although their one-ulp sensitivity is 1.1e-13 and 3.0e-14 (990 x and 4,147 x: beyond the
+ *       100 x the soaks allow; the uniform kernels' largest is 47 x).  It is lqr_qtol's arithmetic on such levels, not the ragged loads (same
+ *       bits as the uniform kernel on the padded problems).  A caller with badly scaled data and short levels should not rely on 1e-10 under
+ *       policy 10; well-scaled data keep it (every case of tests/test_gpu_qtol_ragged.py).  With the accuracy guard on, a ragged batch takes the bit-exact
+ *       kernel of its shape (status 0): there is no estimating ragged instantiation.
  *   Policy 0 is therefore NOT bit-exact for those x-only solves; a caller that needs (B) everywhere sets policy 5 (per handle) or runs under
  *   LEXLS_QTOL=0 (whole process; read at every factorization, so it may be changed between solves) — or switches the accuracy guard on below.
- *   ACCURACY GUARD (lexls_lse_set_accuracy_guard, off by default).  With the guard on, a solve that would run on lqr_qtol (policies 0 and 6) runs on
+ *   ACCURACY GUARD (lexls_lse_set_accuracy_guard, off by default).  With the guard on, a solve that would run on lqr_qtol (policies 0 and 6; uniform batches under 10) runs on
  *   its estimating instantiation, which also writes per problem an estimate of how far it can vouch for its (T) answer: the maximum over the
  *   pivots of |pivot column in its level's raw rows| / |R_jj| (cancellation in the factorization).  A solve that would run on another (T) kernel
  *   (lqr_mfma: policy 0 for shapes lqr_qtol does not hold, policies 7 / 8 / 9; the step-per-pivot large path) takes the bit-exact kernel for the

@@ -791,13 +791,13 @@ extern "C"
         return LEXLS_OK;
     }
 
-    /// Which tolerance-contract kernels a factorization of this handle may take (launch_lqr_wave's `tolerance`): policies 6 / 7 / 8 name one;
+    /// Which tolerance-contract kernels a factorization of this handle may take (launch_lqr_wave's `tolerance`): policies 6 .. 10 name them;
     /// automatic dispatch (policy 0) takes them wherever they serve unless the process runs under LEXLS_QTOL=0 (read at every call, so that a
     /// caller may change it between solves); every other policy stays on the bit-exact kernels
     static int tolerance_mode(lexls_lse_t h)
     {
         if (h->fused_gather) return 0;
-        if (h->force_generic >= 6 && h->force_generic <= 9) return h->force_generic;
+        if (h->force_generic >= 6 && h->force_generic <= 10) return h->force_generic;
         if (h->force_generic != 0) return 0;
         const char *e = std::getenv("LEXLS_QTOL");
         return (e && std::atoi(e) == 0) ? 0 : 1;
@@ -819,10 +819,11 @@ extern "C"
         const char *variant = "";
         const LseArgs a     = h->args();
         const bool shape_kernels = h->force_generic != 1;
-        // accuracy guard: lqr_qtol runs as its estimating instantiation; every other tolerance-contract kernel gives way to the bit-exact one
+        // accuracy guard: lqr_qtol runs as its estimating instantiation; every other tolerance-contract kernel (the ragged lqr_qtol of policy 10
+        // included) gives way to the bit-exact one
         const bool guard = h->guard_mode != 0;
         int tolerance    = tolerance_mode(h);
-        if (guard && tolerance != 0) tolerance = (tolerance == 1 || tolerance == 6) ? 6 : 0;
+        if (guard && tolerance != 0) tolerance = (tolerance == 1 || tolerance == 6 || tolerance == 10) ? 6 : 0;
         const GuardArrays guard_arrays{h->d_guard_est, h->d_guard_status, h->d_guard_ind};
         const GuardArrays *gp = guard ? &guard_arrays : nullptr;
         // (the regularization family lives in the register-resident wave kernel's REG instantiations and in the generic kernel)

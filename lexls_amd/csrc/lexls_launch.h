@@ -28,15 +28,17 @@ namespace lexls
     hipError_t launch_gather_rows(const LseArgs &a, const double *d_cdata, uint64_t per_problem, const uint32_t *d_row_src, const uint32_t *d_row_ld,
                                   double *d_dst, hipStream_t s);
 
-    // lqr_small.hip — one wavefront per problem, problem in VGPRs (n+1 <= 64, rows <= 64, level dims <= 16)
+    // lqr_small.hip — dispatch of the shape kernels (n+1 <= 64, level dims <= 16): one wavefront per problem with the problem in VGPRs, the
+    // left-looking forms (one or four problems per wavefront, any number of rows), the tolerance-contract kernels
     bool wave_kernel_supports(const LseArgs &a, uint32_t max_rows, uint32_t max_level_dim, bool has_fixed);
     bool deep_kernel_supports(const LseArgs &a, uint32_t max_level_dim, bool write_factor, bool has_fixed);
     bool wave_dispatch_is_register_resident(const LseArgs &a, uint32_t max_level_dim, bool has_fixed, int left_looking);
     bool wave_reg_kernel_fits(const LseArgs &a, uint32_t max_level_dim);
     size_t wave_reg_lds_share();
     /// tolerance: x-only solves of the shapes lqr_mfma_impl.h / lqr_qtol_impl.h serve may take those kernels (pivots / ranks exact, x within 1e-10
-    /// instead of bit-identical to the oracle).  0 = bit-exact kernels only; 1 = automatic (lqr_mfma where it serves, else lqr_qtol); 6 = lqr_qtol
-    /// only; 7 / 8 = lqr_mfma with two / one problem per wavefront, else lqr_qtol
+    /// instead of bit-identical to the oracle).  0 = bit-exact kernels only; 1 = automatic (lqr_qtol where it serves, else lqr_mfma); 6 = lqr_qtol
+    /// only; 7 / 8 / 9 = lqr_mfma with two / one / four problems per wavefront, else lqr_qtol; 10 = as 6, and lqr_qtol's ragged instantiations
+    /// (levels of at most 12 rows, per-problem dimensions) where the uniform ones do not serve
     /// guard (NULL: off): the accuracy guard's device arrays (lexls_lse_set_accuracy_guard).  With a guard, lqr_qtol runs as its estimating
     /// instantiation (est: batch doubles; ind[0], the compaction counter, is cleared) and *variant names it with ",guard"
     struct GuardArrays

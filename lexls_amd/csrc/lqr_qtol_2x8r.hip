@@ -1,0 +1,3 @@
+// n + 1 <= 32 columns, levels of up to 8 rows (per-problem dimensions), x only, tolerance contract: the ragged form
+#include "lqr_qtol_impl.h"
+LEXLS_QTOL_INSTANCE_RAG(launch_qtol_2x8r, 2, 8, 0, 0)

@@ -1,5 +1,5 @@
-// Body of lqr_qtol_kernel / lqr_qtol_est_kernel (lqr_qtol_impl.h), included inside both: template parameters NS, MD, SIG, NV; arguments a,
-// img_doubles, group_bytes, stagger; EST (constexpr bool), est_out, count_reset.
+// Body of lqr_qtol_kernel / lqr_qtol_est_kernel / lqr_qtol_rag_kernel (lqr_qtol_impl.h), included inside each: template parameters NS, MD, SIG, NV;
+// arguments a, img_doubles, group_bytes, stagger; EST (constexpr bool), est_out, count_reset; RAG (constexpr bool): levels of up to MD rows.
             static_assert(NS >= 1 && NS <= 4 && MD <= 16 && (MD % 4) == 0, "shape limits of the row layout / two row parts of even size");
             constexpr int NH  = 2;        // row parts of the staging transposition
             constexpr int RP  = MD / NH;  // rows per part
@@ -34,6 +34,26 @@
             const uint32_t pstride = (uint32_t)cap * (uint32_t)(n + 1);
             const double *inw      = a.in + (size_t)wq * 4u * pstride; // wave-uniform base; lane offsets stay 32-bit
             const uint32_t poff    = (bb - wq * 4u) * pstride;
+            // (RAG) level k of this problem has (dpack >> 4 k) & 15 <= MD rows, packed: its first row is the sum of the levels in front (Frow).
+            // Rows d .. MD-1 of a level block are zeros, whatever lies behind the level in memory: see lqr_qtol_impl.h
+            uint32_t dpack = 0;
+            int Frow       = 0;
+            if constexpr (RAG)
+            {
+                static_assert(!EST && MD <= 15 && kQuadMaxObj <= 8, "four bits per level in one word; no estimating ragged form");
+                const uint32_t dk = gl < nObj ? a.dims[(size_t)bb * (uint32_t)nObj + (uint32_t)gl] : 0u;
+                const int dv      = (int)(dk < (uint32_t)MD ? dk : (uint32_t)MD);
+                for_each_index<0, kQuadMaxObj>([&](auto kk) __attribute__((always_inline)) {
+                    constexpr int k_ = decltype(kk)::value;
+                    dpack |= (uint32_t)gbci<k_>(dv) << (4 * k_);
+                });
+            }
+            // (RAG) the pair of rows R, R + 1 of a column is read at row min(R, cap - 2): no load leaves the column, so none leaves the input array.
+            // R == cap - 1 (the column's last row, first of its pair) then arrives in the second half; rows from cap on belong to no level
+            auto rag_rows = [&](qt_d2 v, int R, int r, int d, double &lo, double &hi) __attribute__((always_inline)) {
+                lo = sel(r < d, sel(R == cap - 1, v.y, v.x), 0.0);
+                hi = sel(r + 1 < d, v.y, 0.0);
+            };
 
             // ---- the first level's rows are requested before anything else (every wave of the chip asks for its first level at once: the HBM serves
             //      this burst at its full rate, and nothing can be computed before it lands).  Its position layout is the identity, so lane = column
@@ -45,13 +65,28 @@
             {
                 const int P       = 16 * s + gl - SIG;
                 const int c       = (P >= 0 && P <= n) ? P : 0;
-                const qt_d2 *src2 = reinterpret_cast<const qt_d2 *>(inw + (poff + (uint32_t)(c * cap)));
-#pragma unroll
-                for (int r = 0; r < MD / 2; r++)
+                if constexpr (RAG)
                 {
-                    const qt_d2 v     = src2[r];
-                    blk[s][2 * r]     = v.x;
-                    blk[s][2 * r + 1] = v.y;
+                    const double *colp = inw + (poff + (uint32_t)(c * cap));
+                    const int d0       = (int)(dpack & 15u);
+#pragma unroll
+                    for (int r = 0; r < MD / 2; r++)
+                    {
+                        const int Rc  = 2 * r < cap - 2 ? 2 * r : cap - 2;
+                        const qt_d2 v = *reinterpret_cast<const qt_d2u *>(colp + Rc); // (8-byte aligned when cap is odd)
+                        rag_rows(v, 2 * r, 2 * r, d0, blk[s][2 * r], blk[s][2 * r + 1]);
+                    }
+                }
+                else
+                {
+                    const qt_d2 *src2 = reinterpret_cast<const qt_d2 *>(inw + (poff + (uint32_t)(c * cap)));
+#pragma unroll
+                    for (int r = 0; r < MD / 2; r++)
+                    {
+                        const qt_d2 v     = src2[r];
+                        blk[s][2 * r]     = v.x;
+                        blk[s][2 * r + 1] = v.y;
+                    }
                 }
             }
 
@@ -101,12 +136,26 @@
                 int ch        = 16 * i + gl;
                 ch            = ch < CH ? ch : CH - 1; // lanes past the end repeat the last piece (same bytes to the same LDS address)
                 const int col = ch / HP, m = ch - col * HP;
-                pieceoff[t]   = 8u * (poff + (uint32_t)(col * cap + h * RP + 2 * m)); // bytes
+                if constexpr (RAG)
+                    pieceoff[t] = ((uint32_t)(col * cap) << 2) | (uint32_t)m; // column offset in doubles and the pair inside the part: the row is per problem
+                else
+                    pieceoff[t] = 8u * (poff + (uint32_t)(col * cap + h * RP + 2 * m)); // bytes
             });
-            auto prefetch_piece = [&](auto tt, int Frow) __attribute__((always_inline)) {
+            static_assert(HP <= 4, "two bits for the pair index of a ragged piece");
+            auto prefetch_piece = [&](auto tt, int Flev) __attribute__((always_inline)) { // Flev: first row of the level asked for
                 constexpr int t = decltype(tt)::value, i = t % NIH;
                 if (16 * i < CH) // wave-uniform
-                    qt_pf_load<t>(inw + Frow, pieceoff[t]);
+                {
+                    if constexpr (RAG)
+                    {
+                        // the level's first row differs between the four problems of the wavefront: it goes into the lane's offset (clamped: rag_rows)
+                        constexpr int h = t / NIH;
+                        const int R     = Flev + h * RP + 2 * (int)(pieceoff[t] & 3u);
+                        qt_pf_load<t>(inw, 8u * (poff + (pieceoff[t] >> 2) + (uint32_t)(R < cap - 2 ? R : cap - 2)));
+                    }
+                    else
+                        qt_pf_load<t>(inw + Flev, pieceoff[t]);
+                }
             };
 
             int rp[NS];         // slot s, lane l: LDS byte address of the (triangular) image row of pivot position c = 16 s + l - SIG
@@ -143,6 +192,9 @@
             for (int k = 0; k < nObj; k++)
             {
                 const bool work = live && !exh; // x only: once the columns are exhausted nothing below matters
+                const int F     = RAG ? Frow : k * MD;                       // first row of the level
+                const int dlev  = RAG ? (int)((dpack >> (4 * k)) & 15u) : MD; // its rows (RAG: per problem)
+                if constexpr (RAG) Frow += dlev;
                 const int Fc    = ColIndex;
                 int rank        = 0;
                 if (__ballot(work) == 0ull)
@@ -156,7 +208,6 @@
                     }
                     continue;
                 }
-                const int F = k * MD;
                 if (k > 0 && !have_next) // a level whose predecessor could have exhausted the columns: all pieces at once
                     for_each_index<0, NH * NIH>([&](auto tt) __attribute__((always_inline)) { prefetch_piece(tt, F); });
 
@@ -195,8 +246,13 @@
                         for (int m = 0; m < HP; m++)
                         {
                             const qt_d2 v            = D2(o_stage + 16 * (pc[s] * HP + m));
-                            blk[s][h * RP + 2 * m]     = v.x;
-                            blk[s][h * RP + 2 * m + 1] = v.y;
+                            if constexpr (RAG)
+                                rag_rows(v, F + h * RP + 2 * m, h * RP + 2 * m, dlev, blk[s][h * RP + 2 * m], blk[s][h * RP + 2 * m + 1]);
+                            else
+                            {
+                                blk[s][h * RP + 2 * m]     = v.x;
+                                blk[s][h * RP + 2 * m + 1] = v.y;
+                            }
                         }
                     }
                     quad_lds_fence();
@@ -369,7 +425,7 @@
                         {
                             constexpr int TOT = NH * NIH, PF_PER = (TOT + PF_STEPS - 1) / PF_STEPS;
                             constexpr int lo = (j * PF_PER < TOT ? j * PF_PER : TOT), hi = ((j + 1) * PF_PER < TOT ? (j + 1) * PF_PER : TOT);
-                            if (prefetch) for_each_index<lo, hi>([&](auto tt) __attribute__((always_inline)) { prefetch_piece(tt, F + MD); });
+                            if (prefetch) for_each_index<lo, hi>([&](auto tt) __attribute__((always_inline)) { prefetch_piece(tt, F + dlev); });
                             pf_issued = hi;
                         }
                         const bool act = go;
@@ -393,7 +449,9 @@
                         const double tailSq = (t0 + t1) + t2;
                         const double fresh  = dfma(c0, c0, tailSq);
                         CSTAMP(2, __double2loint(fresh))
-                        const bool cont     = act && !(fresh < a.tol); // rank test on the squared norm (lexlse.h:214); no branch: a stopped row runs on
+                        // rank test on the squared norm (lexlse.h:214); no branch: a stopped row runs on.  (RAG) a level ends with its own rows, whatever
+                        // the tolerance: behind them the column is exactly zero
+                        const bool cont     = RAG ? (act && !(fresh < a.tol) && j < dlev) : (act && !(fresh < a.tol));
                         go                  = cont;
                         // 1 / sqrt(fresh): v_rsq_f64 and two coupled iterations (g -> sqrt, h -> 1 / (2 sqrt))
                         double g, h;
@@ -548,7 +606,7 @@
                     });
                     if (prefetch)
                         for_each_index<0, NH * NIH>([&](auto tt) __attribute__((always_inline)) {
-                            if (decltype(tt)::value >= pf_issued) prefetch_piece(tt, F + MD);
+                            if (decltype(tt)::value >= pf_issued) prefetch_piece(tt, F + dlev);
                         });
                     (void)SL;
                 };

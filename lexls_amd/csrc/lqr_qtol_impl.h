@@ -128,6 +128,7 @@ namespace lexls
         }
 
         typedef double qt_d2 __attribute__((ext_vector_type(2))); // 16 bytes as a native vector (the level pieces stay in registers)
+        typedef qt_d2 qt_d2u __attribute__((aligned(8)));         // ... read at the alignment of a double (ragged levels)
 
 
         // ---- the level-ahead pieces live in FIXED accumulation registers a[184:255], managed by inline assembly -----------------------
@@ -173,6 +174,27 @@ namespace lexls
         __global__ __launch_bounds__(64 * QT_WPB) void lqr_qtol_kernel(LseArgs a, uint32_t img_doubles, uint32_t group_bytes, uint32_t stagger)
         {
             constexpr bool EST           = false;
+            constexpr bool RAG           = false;
+            double *const est_out        = nullptr;
+            uint32_t *const count_reset  = nullptr;
+#include "lqr_qtol_body.inc"
+        }
+
+        /// RAG: the ragged instantiation (lexls_lse_set_kernel_policy(h, 10)): level k of problem b has a.dims[b][k] <= MD rows, packed (its first
+        /// row is the sum of the dimensions in front of it, as everywhere in the library).  The level block is the level with MD - d zero rows
+        /// appended: a zero row adds nothing to a norm, a tail sum or a dot product and stays zero under the Gauss step and the rank-one update,
+        /// so pivots, ranks and x are those of the level itself (tests/test_ragged_padding_oracle.py pins this on the oracle).  What differs
+        /// from the uniform body: the level's first row is per problem (per-lane offsets of the level loads instead of a scalar base), rows
+        /// d .. MD-1 are replaced by zeros after the load (select, not multiply: the memory behind a level holds the next level, slack, the next
+        /// column), the loads are clamped to the column, and a level stops after d pivots whatever the tolerance.  The 16-byte loads sit at
+        /// 8-byte alignment when a level starts at an odd row (or cap is odd): global memory accesses need no more than dword alignment in the
+        /// unaligned access mode the HSA runtime runs kernels in (the compiler itself emits global_load_dwordx4 for an 8-byte aligned qt_d2u);
+        /// the LDS side keeps its 16 bytes.
+        template <int NS, int MD, int SIG, int NV>
+        __global__ __launch_bounds__(64 * QT_WPB) void lqr_qtol_rag_kernel(LseArgs a, uint32_t img_doubles, uint32_t group_bytes, uint32_t stagger)
+        {
+            constexpr bool EST           = false;
+            constexpr bool RAG           = true;
             double *const est_out        = nullptr;
             uint32_t *const count_reset  = nullptr;
 #include "lqr_qtol_body.inc"
@@ -185,6 +207,7 @@ namespace lexls
                                                                           uint32_t *count_reset)
         {
             constexpr bool EST = true;
+            constexpr bool RAG = false;
 #include "lqr_qtol_body.inc"
         }
 
@@ -212,11 +235,14 @@ namespace lexls
             return ((raw + 127) / 256) * 256 + 128;
         }
 
-        template <int NS, int MD, int SIG, int NV, bool EST = false>
+        template <int NS, int MD, int SIG, int NV, bool EST = false, bool RAG = false>
         hipError_t launch_qtol_t(const LseArgs &a, hipStream_t s, double *est_out = nullptr, uint32_t *count_reset = nullptr)
         {
+            static_assert(!(EST && RAG), "no estimating ragged form");
             const void *kfn;
-            if constexpr (EST)
+            if constexpr (RAG)
+                kfn = reinterpret_cast<const void *>(lqr_qtol_rag_kernel<NS, MD, SIG, NV>);
+            else if constexpr (EST)
                 kfn = reinterpret_cast<const void *>(lqr_qtol_est_kernel<NS, MD, SIG, NV>);
             else
                 kfn = reinterpret_cast<const void *>(lqr_qtol_kernel<NS, MD, SIG, NV>);
@@ -224,7 +250,8 @@ namespace lexls
             const size_t gbytes = qtol_group_bytes<NS, MD>(a.nVar, a.nObj);
             const size_t lds    = 4 * QT_WPB * gbytes;
             if (lds > kMaxLdsBytes || a.nObj > (uint32_t)kQuadMaxObj || a.nVar + 1 + SIG > 16u * NS || a.nVar > 63u || (NV && a.nVar != (uint32_t)NV)) return hipErrorInvalidValue;
-            if (a.uniform_dim != (uint32_t)MD || (a.cap & 1u) || (reinterpret_cast<uintptr_t>(a.in) & 15u) || a.nfixed || a.reg_type != 0) return hipErrorInvalidValue;
+            if ((reinterpret_cast<uintptr_t>(a.in) & (RAG ? 7u : 15u)) || a.nfixed || a.reg_type != 0) return hipErrorInvalidValue; // (RAG: its 16-byte loads are 8-byte aligned anyway)
+            if (RAG ? (a.cap < 2u || !a.dims) : (a.uniform_dim != (uint32_t)MD || (a.cap & 1u))) return hipErrorInvalidValue; // (RAG: the caller vouches for dims <= MD; the kernel clamps)
             if (lds > 64 * 1024)
             {
                 static size_t granted[64] = {0}; // per device: the attribute is set once, not per launch
@@ -239,7 +266,9 @@ namespace lexls
             }
             const uint32_t blocks = (a.batch + 4u * QT_WPB - 1u) / (4u * QT_WPB);
             static const uint32_t stagger = std::getenv("LEXLS_QTOL_STAGGER") ? (uint32_t)std::atoi(std::getenv("LEXLS_QTOL_STAGGER")) : 0u; // x 512 cycles per SIMD index
-            if constexpr (EST)
+            if constexpr (RAG)
+                hipLaunchKernelGGL((lqr_qtol_rag_kernel<NS, MD, SIG, NV>), dim3(blocks), dim3(64 * QT_WPB), lds, s, a, img, (uint32_t)gbytes, stagger);
+            else if constexpr (EST)
                 hipLaunchKernelGGL((lqr_qtol_est_kernel<NS, MD, SIG, NV>), dim3(blocks), dim3(64 * QT_WPB), lds, s, a, img, (uint32_t)gbytes, stagger, est_out, count_reset);
             else
                 hipLaunchKernelGGL((lqr_qtol_kernel<NS, MD, SIG, NV>), dim3(blocks), dim3(64 * QT_WPB), lds, s, a, img, (uint32_t)gbytes, stagger);
@@ -254,3 +283,6 @@ namespace lexls
 // the accuracy guard's instantiation: est_out (batch doubles) receives the estimate, *count_reset is cleared
 #define LEXLS_QTOL_INSTANCE_EST(NAME, NS, MD, SIG, NV) \
     namespace lexls { hipError_t NAME(const LseArgs &a, hipStream_t s, double *est_out, uint32_t *count_reset) { return launch_qtol_t<NS, MD, SIG, NV, true>(a, s, est_out, count_reset); } }
+// the ragged instantiation (levels of up to MD rows, per-problem dimensions); its LDS is that of the uniform instantiation of the shape
+#define LEXLS_QTOL_INSTANCE_RAG(NAME, NS, MD, SIG, NV) \
+    namespace lexls { hipError_t NAME(const LseArgs &a, hipStream_t s) { return launch_qtol_t<NS, MD, SIG, NV, false, true>(a, s); } }

@@ -66,6 +66,11 @@ namespace lexls
     size_t launch_qtol_3x8_lds(uint32_t nVar, uint32_t nObj);
     hipError_t launch_qtol_2x8(const LseArgs &a, hipStream_t s);
     size_t launch_qtol_2x8_lds(uint32_t nVar, uint32_t nObj);
+    hipError_t launch_qtol_3x12s7r(const LseArgs &a, hipStream_t s);
+    hipError_t launch_qtol_3x12r(const LseArgs &a, hipStream_t s);
+    hipError_t launch_qtol_2x12r(const LseArgs &a, hipStream_t s);
+    hipError_t launch_qtol_3x8r(const LseArgs &a, hipStream_t s);
+    hipError_t launch_qtol_2x8r(const LseArgs &a, hipStream_t s);
     hipError_t launch_mfma_32x12n40(const LseArgs &a, hipStream_t s);
     size_t launch_mfma_32x12n40_lds(uint32_t nVar, uint32_t nObj);
     hipError_t launch_mfma_32x12(const LseArgs &a, hipStream_t s);
@@ -95,6 +100,25 @@ namespace lexls
     {
         if (write_factor || has_fixed || a.reg_type != 0 || (a.uniform_dim != 12 && a.uniform_dim != 8) || a.nObj > 8 || (a.cap & 1u) != 0 || (reinterpret_cast<uintptr_t>(a.in) & 15u) != 0 || a.g_cdata) return 0;
         if (a.uniform_dim == 8) // levels of eight rows (round 4): 4: 33 .. 48 columns, 5: up to 32
+        {
+            if (a.nVar + 1 <= 32) return (a.nVar >= 2 && launch_qtol_2x8_lds(a.nVar, a.nObj) <= kMaxLdsBytes) ? 5 : 0;
+            if (a.nVar + 1 <= 48) return launch_qtol_3x8_lds(a.nVar, a.nObj) <= kMaxLdsBytes ? 4 : 0;
+            return 0;
+        }
+        if (a.nVar == 40) return launch_qtol_3x12s7_lds(a.nVar, a.nObj) <= kMaxLdsBytes ? 1 : 0;
+        if (a.nVar + 1 <= 32) return (a.nVar >= 2 && launch_qtol_2x12_lds(a.nVar, a.nObj) <= kMaxLdsBytes) ? 3 : 0;
+        if (a.nVar + 1 <= 48) return launch_qtol_3x12_lds(a.nVar, a.nObj) <= kMaxLdsBytes ? 2 : 0;
+        return 0;
+    }
+
+    /// which RAGGED instantiation of lqr_qtol (kernel policy 10) serves these arguments (0: none): x-only solves whose levels have at most 12 rows
+    /// each — per-problem dimensions, any mix, zeros included — under qtol_choice's other conditions (cap may be odd and the input needs the
+    /// alignment of a double only: so do the ragged loads).  Numbered like qtol_choice: the eight-row pair (4, 5) where no level has more than 8 rows, else the
+    /// twelve-row trio (1: n = 40, 2: 33 .. 48 columns, 3: up to 32).  Uniform batches of 12 or 8 rows are qtol_choice's
+    static int qtol_ragged_choice(const LseArgs &a, uint32_t max_level_dim, bool write_factor, bool has_fixed)
+    {
+        if (write_factor || has_fixed || a.reg_type != 0 || max_level_dim > 12 || a.nObj > 8 || a.cap < 2 || !a.dims || (reinterpret_cast<uintptr_t>(a.in) & 7u) != 0 || a.g_cdata) return 0;
+        if (max_level_dim <= 8)
         {
             if (a.nVar + 1 <= 32) return (a.nVar >= 2 && launch_qtol_2x8_lds(a.nVar, a.nObj) <= kMaxLdsBytes) ? 5 : 0;
             if (a.nVar + 1 <= 48) return launch_qtol_3x8_lds(a.nVar, a.nObj) <= kMaxLdsBytes ? 4 : 0;
@@ -220,7 +244,7 @@ namespace lexls
         const uint32_t nc = a.nVar + 1;
         // tolerance: 0 bit-exact kernels only; 1 automatic (lqr_qtol where it serves — the faster of the two on MI355X: 41 us against 57 us per
         // 4096 IK problems — else the matrix-core kernel); 6 lqr_qtol only; 7 / 8 / 9 lqr_mfma with two / one / four problems per wavefront
-        // (9: the IK shape only), else lqr_qtol
+        // (9: the IK shape only), else lqr_qtol; 10 as 6, and lqr_qtol's ragged instantiations for levels of at most 12 rows
         auto try_mfma = [&](bool one_per_wave) -> int { return mfma_choice(a, write_factor, has_fixed, one_per_wave); };
         if (tolerance == 9 && try_mfma(false) == 1)
         {
@@ -253,6 +277,16 @@ namespace lexls
             case 3: *variant = "lqr_qtol<2,12>"; return launch_qtol_2x12(a, s);
             case 4: *variant = "lqr_qtol<3,8>"; return launch_qtol_3x8(a, s);
             case 5: *variant = "lqr_qtol<2,8>"; return launch_qtol_2x8(a, s);
+            default: break;
+            }
+        if (tolerance == 10) // levels of up to 12 rows, per-problem dimensions (uniform 12 / 8 went to the shipped instantiations above; with the accuracy guard on the caller asks for 6)
+            switch (qtol_ragged_choice(a, max_level_dim, write_factor, has_fixed))
+            {
+            case 1: *variant = "lqr_qtol<3,12,shift 7,ragged>"; return launch_qtol_3x12s7r(a, s);
+            case 2: *variant = "lqr_qtol<3,12,ragged>"; return launch_qtol_3x12r(a, s);
+            case 3: *variant = "lqr_qtol<2,12,ragged>"; return launch_qtol_2x12r(a, s);
+            case 4: *variant = "lqr_qtol<3,8,ragged>"; return launch_qtol_3x8r(a, s);
+            case 5: *variant = "lqr_qtol<2,8,ragged>"; return launch_qtol_2x8r(a, s);
             default: break;
             }
         if (tolerance == 1) // shapes lqr_qtol's four slices per wavefront do not hold

@@ -267,7 +267,10 @@ class BatchedLexLSE:
 
     def set_kernel_policy(self, policy: int):
         """diagnostics (lexls_lse_set_kernel_policy): 0 automatic dispatch, 1 generic kernel only, 2 never the left-looking wave kernel,
-        3 the left-looking wave kernel whenever the shape allows it"""
+        3 the left-looking wave kernel whenever the shape allows it, 4 the bit-exact four-problems-per-wavefront kernel, 5 bit-exact everywhere,
+        6 the tolerance-contract kernel lqr_qtol wherever it serves (levels of exactly 12 or exactly 8 rows), 7 / 8 / 9 lqr_mfma,
+        10 as 6 plus lqr_qtol's ragged instantiations: x-only solves whose levels have at most 12 rows each, per-problem dimensions (setObjDim
+        with a (batch, nObj) array), empty levels included; same tolerance contract (include/lexls_hip.h)"""
         capi.check(capi.lib().lexls_lse_set_kernel_policy(self._h, C.c_int(int(policy))))
 
     def last_kernel(self) -> str:
