@@ -443,6 +443,9 @@ namespace LexLS
             /// working sets resident can run whole iterations by itself (lock-step device batches)
             bool atIterationSolve() const { return pc == PC_IT_SOLVED && pending == NEED_FACTORIZE_SOLVE; }
             const std::vector<Objective> &getObjectives() const { return objectives; }
+            /// the active constraints in the order they entered the working set (the list findFirstCtrWrongSign walks, lexlsi.h:1034-1046): a
+            /// backend that takes the iterations over (lock-step device batches) carries the order on as one activation stamp per constraint
+            const std::vector<ConstraintInfo> &getActivationOrder() const { return WS; }
             Index needLevel() const { return sens_level; }
             bool finished() const { return pc == PC_DONE; }
 
@@ -505,8 +508,8 @@ namespace LexLS
                     bool found;
                     if (parameters.deactivate_first_wrong_sign)
                     {
-                        // lexlsi.h:1063-1105: collects every wrong-sign multiplier level by level on the spot (not batchable: the lock-step
-                        // driver rejects this option); the objective index comes back absolute
+                        // lexlsi.h:1063-1105: collects every wrong-sign multiplier level by level (an equality solver of a lock-step batch hands
+                        // out the set its stage collected); the objective index comes back absolute
                         Index o_abs = 0;
                         found       = findActiveCtr2Remove_first(o_abs, CtrIndex2Remove, lambda_wrong_sign);
                         ObjIndex2Remove = static_cast<int>(o_abs) - static_cast<int>(nObjOffset);

@@ -52,6 +52,12 @@ enum lexls_array
     LEXLS_ARRAY_GUARD_STATUS,   /* uint8  batch                 accuracy guard: status of the last solve                                  */
     LEXLS_ARRAY_MULTIPLIERS     /* double batch x nObj x (nVar+cap) every objective's multipliers (lexls_lse_multipliers)                 */
 };
+/* The ids behind LEXLS_ARRAY_MULTIPLIERS continue the numbering of enum lexls_array (the list above is pinned as it stands by
+ * tests/test_lsi_lambda_api.py); lexls_lse_device_ptr takes them like the others. */
+enum lexls_array_more
+{
+    LEXLS_ARRAY_WRONG_SIGN = LEXLS_ARRAY_MULTIPLIERS + 1 /* uint8 batch x (nVar+cap) the wrong-sign set of the last lexls_lse_sensitivity_collect call */
+};
 
 /* replaces LexLS::Exception::what() (typedefs.h:300-314): no exception crosses the ABI — every entry point returns a status code and
  * leaves the message of the last failure here */
@@ -164,6 +170,20 @@ int lexls_lse_sensitivity(lexls_lse_t h, const int32_t *h_obj_index, int32_t obj
 int lexls_lse_set_sensitivity_scan(lexls_lse_t h, int on);
 /* same, with the per-problem objective indices already on the device (the obj_index array of lexls_lse_upload_round) */
 int lexls_lse_sensitivity_resident(lexls_lse_t h, double tol_wrong_sign_lambda, double tol_correct_sign_lambda);
+/* replaces void ObjectiveSensitivity(ObjIndex, tolWrong, tolCorrect, ctr_wrong_sign) (lexlse.h:511-602 around the scan of :866-910), the
+ * overload LexLSI's deactivate_first_wrong_sign rule calls (lexlsi.h:1063-1105): the same multipliers (LEXLS_ARRAY_LAMBDA) and the same
+ * CORRECT_SIGN_OF_LAMBDA marks in the constraint and fixed-variable types, but instead of the most negative wrong-sign multiplier EVERY one is
+ * reported: LEXLS_ARRAY_WRONG_SIGN / lexls_lse_get_wrong_sign, batch x (nVar + cap) bytes per call — bytes [0, nVar) the fixed variables in
+ * fixVariable order, bytes [nVar, nVar + cap) the constraint rows in LOD order; 1 where the reference pushes a ConstraintInfo, 0 elsewhere.
+ * Scan order: the objective's own level, the levels above it downwards, the fixed variables.  The reference's quirk for the fixed variables is
+ * kept (lexlse.h:599-600): min(dims[0], nfixed) entries are scanned, entry k reads the CONSTRAINT multiplier Lambda[k] against fixed type k, and
+ * sets byte k.  Arguments as lexls_lse_sensitivity; with lexls_lse_set_sensitivity_scan on it goes on to the next objective until one reports a
+ * non-empty set or the last is done (the loop of lexlsi.h:1072-1083; marks of the objectives passed stay in place).
+ * lexls_lse_get_sensitivity then gives {set non-empty, number of entries, objective the search stopped at} and max_abs = 0 (the reference sets
+ * lambda_wrong_sign = 0 on this path); {0, -1, -2} for a problem whose objective index is negative.  _resident: objective indices from the
+ * round slab, as lexls_lse_sensitivity_resident. */
+int lexls_lse_sensitivity_collect(lexls_lse_t h, const int32_t *h_obj_index, int32_t obj_index_all, double tol_wrong_sign_lambda, double tol_correct_sign_lambda);
+int lexls_lse_sensitivity_collect_resident(lexls_lse_t h, double tol_wrong_sign_lambda, double tol_correct_sign_lambda);
 
 /* Every objective's multipliers at once: column k of problem b is what lexls_lse_get_lambda returns after ObjectiveSensitivity(k) — the
  * [lambda_fixed; lambda] workspace head(nMeaningful), nMeaningful = nfixed + dims[0] + ... + dims[k], zero from row nMeaningful on (lexlse.h:611-762,
@@ -192,6 +212,7 @@ int lexls_lse_get_mu(lexls_lse_t h, double *h_x_mu, double *h_x_mu_rhs, double *
 int lexls_lse_get_lambda(lexls_lse_t h, double *h_lambda);          /* getWorkspace() after ObjectiveSensitivity, lexlse.h:1621 */
 /* h_found_ctr_obj: batch x 3 int32 {found, CtrIndex2Remove, ObjIndex2Remove}; h_max_abs: batch */
 int lexls_lse_get_sensitivity(lexls_lse_t h, int32_t *h_found_ctr_obj, double *h_max_abs);
+int lexls_lse_get_wrong_sign(lexls_lse_t h, uint8_t *h_mask);    /* batch x (nVar + cap): the set of the last lexls_lse_sensitivity_collect call */
 int lexls_lse_get_ctr_type(lexls_lse_t h, uint8_t *h_types);
 int lexls_lse_get_fixed_type(lexls_lse_t h, uint8_t *h_types);   /* batch x nVar: activation types of the fixed variables incl. the CORRECT_SIGN_OF_LAMBDA marks (lexlse.h:866-987) */
 /* raw device pointer of one of the handle's arrays (enum lexls_array), for zero-copy consumers */
@@ -353,7 +374,12 @@ int lexls_lsi_batch_run(lexls_lsi_batch_t b, const double *h_data, const uint32_
  * register-resident kernel, inside the persistent launch or as the stage's l-QR launch.  Such an iteration refactorizes every level (the
  * null-space basis the damping reads accumulates over the levels: no prefix reuse).  Where the regularization routines' LDS does not fit the
  * persistent launch's 64 KB the stages are taken, where it does not fit a workgroup at all the host path.  Host path as before, whatever the
- * type: regularization_type 7, cycling handling, deactivate_first_wrong_sign, shapes without a register-resident kernel.
+ * type: regularization_type 7, cycling handling, shapes without a register-resident kernel.
+ * deactivate_first_wrong_sign (lexlsi.h:1063-1105) is a removal RULE, not another path: a run that would be resident without it is resident with
+ * it — the removal search collects the wrong-sign set (lexls_lse_sensitivity_collect) and the iteration removes its member that entered the
+ * working set first (an activation stamp per constraint carries the order of the reference's WS list).  Where such a run would not be resident
+ * (LEXLS_LSI_RESIDENT=0, cycling handling, type 7, no register-resident kernel, data not resident) its instances go through the single-problem
+ * driver one after the other.
  * lexls_lsi_batch_stats:
  * of the last lexls_lsi_batch_run: {factorize+solve stages, sensitivity stages, stages whose iteration step ran on the device, groups}.
  * The step of an iteration (A*dx, ratio test, update of x / v / A*x: lexlsi.h:987-1029, :1234-1240) runs on the device
@@ -370,8 +396,9 @@ int lexls_lsi_batch_destroy(lexls_lsi_batch_t b);
  * every objective's multipliers taken at once (lexls_lse_multipliers), scattered into user order, copied back.  Bit-identical to
  * lexls_lsi_solve_debug's `lambda` on each instance, every run path included (persistent launch, lock-step stages, LEXLS_LSI_RESIDENT=0, warm
  * starts, v0, factorization limits, deactivate_first_wrong_sign), factorized with the run's tol_linear_dependence.
- * Cost to runs that never ask: none, except with deactivate_first_wrong_sign — that path solves its instances one by one on the host driver and
- * copies the batch's constraint data to the device once per run (what get_lambda gathers from later).
+ * Cost to runs that never ask: none, except for a deactivate_first_wrong_sign run that is NOT resident — its instances go one by one through the
+ * single-problem driver, which never uses the batch's handles, so the constraint data is copied to the device once per run (what get_lambda
+ * gathers from later); a resident run with that rule has the data there already, like any other.
  * Errors: LEXLS_ERR_INVALID before any run (or after a failed one); LEXLS_ERR_UNSUPPORTED after a run with cycling_handling_enabled (the bounds it
  * relaxed live on the host only), after a regularized run (regularization_type != 0), or when the batch's constraint data is not resident
  * (LEXLS_LSI_HOST_STAGING, data beyond 2^31 doubles per instance) or holds more than 65535 constraints per instance.  A later run replaces the multipliers of the previous one. */
@@ -411,7 +438,7 @@ int lexls_lsi_solve_dat(int device, const char *path, int one_based, int use_act
  * "lsi_fused<lqr_wave<41,12,exact>>", "lsi_fused<lqr_wave<41,12,regularized>>", ... for the persistent launch; the l-QR kernel of the last
  * lock-step stage ("lqr_wave<41,12,regularized>", "lqr_quad<3,12,factor,fixed>", ...) where the stages ran (LEXLS_LSI_NO_FUSED=1, or no
  * persistent instantiation); "host" when no instance's iterations were resident (LEXLS_LSI_RESIDENT=0, regularization_type 7, cycling handling,
- * deactivate_first_wrong_sign, every instance done in phase 1); "" before the first run. */
+ * every instance done in phase 1); "" before the first run.  deactivate_first_wrong_sign does not change the name. */
 const char *lexls_lsi_batch_last_kernel(lexls_lsi_batch_t b);
 
 #ifdef __cplusplus

@@ -29,11 +29,12 @@ SYMBOLS = [
     "lexls_lse_set_prefix_reuse", "lexls_lse_prefix_reuse_ready", "lexls_lse_set_resume_levels",
     "lexls_lsi_solve", "lexls_lsi_solve_dat", "lexls_lsi_batch_solve",
     "lexls_lse_multipliers", "lexls_lse_get_multipliers", "lexls_lsi_batch_get_lambda", "lexls_lsi_batch_solve_ex2",
+    "lexls_lse_sensitivity_collect", "lexls_lse_sensitivity_collect_resident", "lexls_lse_get_wrong_sign",
     "lexls_lsi_batch_last_kernel",
 ]
 
 ARRAY = dict(x=0, factor=1, hh=2, perm=3, rank=4, first_col=5, total_rank=6, v=7, lam=8, input=9, guard_estimate=10, guard_status=11,
-             multipliers=12)
+             multipliers=12, wrong_sign=13)
 
 _lib = None
 
@@ -59,6 +60,12 @@ def lib() -> C.CDLL:
         _lib.lexls_lse_set_accuracy_guard.argtypes = [C.c_void_p, C.c_int, C.c_double]
         _lib.lexls_lse_get_accuracy.restype = C.c_int
         _lib.lexls_lse_get_accuracy.argtypes = [C.c_void_p, C.POINTER(C.c_double), C.POINTER(C.c_uint8), C.POINTER(C.c_uint32)]
+        _lib.lexls_lse_sensitivity_collect.restype = C.c_int
+        _lib.lexls_lse_sensitivity_collect.argtypes = [C.c_void_p, C.POINTER(C.c_int32), C.c_int32, C.c_double, C.c_double]
+        _lib.lexls_lse_sensitivity_collect_resident.restype = C.c_int
+        _lib.lexls_lse_sensitivity_collect_resident.argtypes = [C.c_void_p, C.c_double, C.c_double]
+        _lib.lexls_lse_get_wrong_sign.restype = C.c_int
+        _lib.lexls_lse_get_wrong_sign.argtypes = [C.c_void_p, C.POINTER(C.c_uint8)]
     return _lib
 
 

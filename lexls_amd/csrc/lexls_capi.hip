@@ -80,6 +80,7 @@ struct lexls_lse_s
     double *d_reg_factor, *d_reg_scratch, *d_reg_mu;
     std::vector<double> reg_stage; // host copy behind the enqueued upload of the regularization factors (set_regularization)
     bool sens_scan; // lexls_lse_set_sensitivity_scan
+    uint8_t *d_wrong_sign = nullptr; // batch x (nVar + cap): the set of lexls_lse_sensitivity_collect (allocated at its first call / LEXLS_ARRAY_WRONG_SIGN)
     // lexls_lse_multipliers: every objective's multipliers (batch x nObj x (nVar + cap)) and the scratch of its per-objective fallback
     double *d_mult        = nullptr;
     void *d_mult_scratch  = nullptr;
@@ -138,6 +139,7 @@ struct lexls_lse_s
         a.g_row_ld     = d_row_ld;
         a.resume_state = resume_enabled ? d_resume_state : nullptr;
         a.resume_level = (resume_enabled && resume_armed && resume_valid) ? d_resume_level : nullptr;
+        a.wrong_sign   = d_wrong_sign;
         return a;
     }
     size_t problem_elems() const { return (size_t)cap * (nVar + 1); }
@@ -279,7 +281,7 @@ extern "C"
         (void)hipSetDevice(h->device);
         void *ptrs[] = {h->d_in_owned, h->d_fac, h->d_hh, h->d_v, h->d_lambda, h->d_scratch, h->d_perm, h->d_rank, h->d_fcol, h->d_round_in, h->d_round_out,
                         h->d_large_state, h->d_large_ws, h->d_norms, h->d_cdata, h->d_reg_factor, h->d_reg_scratch, h->d_reg_mu, h->d_resume_level, h->d_resume_state,
-                        h->d_guard_est, h->d_guard_status, h->d_guard_ind, h->d_mult, h->d_mult_scratch};
+                        h->d_guard_est, h->d_guard_status, h->d_guard_ind, h->d_mult, h->d_mult_scratch, h->d_wrong_sign};
         for (void *p : ptrs)
             if (p) (void)hipFree(p);
         if (h->h_dims_pinned) (void)hipHostFree(h->h_dims_pinned);
@@ -993,6 +995,43 @@ extern "C"
         return LEXLS_OK;
     }
 
+    static int need_wrong_sign(lexls_lse_t h)
+    {
+        if (h->d_wrong_sign) return LEXLS_OK;
+        const size_t bytes = (size_t)h->batch * (h->nVar + h->cap);
+        HIP_TRY(hipSetDevice(h->device));
+        HIP_TRY(hipMalloc((void **)&h->d_wrong_sign, bytes));
+        HIP_TRY(hipMemsetAsync(h->d_wrong_sign, 0, bytes, h->stream));
+        return LEXLS_OK;
+    }
+
+    int lexls_lse_sensitivity_collect(lexls_lse_t h, const int32_t *h_obj_index, int32_t obj_index_all, double tolW, double tolC)
+    {
+        if (int rc = need_factor(h, "lexls_lse_sensitivity_collect")) return rc;
+        if (int rc = need_wrong_sign(h)) return rc;
+        const int32_t *d_obj = nullptr;
+        if (h_obj_index)
+        {
+            HIP_TRY(hipMemcpyAsync(h->d_objidx, h_obj_index, 4 * (size_t)h->batch, hipMemcpyHostToDevice, h->stream));
+            if (!h->deferred_sync) HIP_TRY(hipStreamSynchronize(h->stream));
+            d_obj = h->d_objidx;
+        }
+        else if (obj_index_all < 0 || (uint32_t)obj_index_all >= h->nObj)
+        {
+            return fail(LEXLS_ERR_INVALID, "ObjIndex >= nObj");
+        }
+        HIP_TRY(launch_sensitivity(h->args(), d_obj, obj_index_all, tolW, tolC, h->stream, h->sens_scan, h->max_level_dim, true));
+        return LEXLS_OK;
+    }
+
+    int lexls_lse_sensitivity_collect_resident(lexls_lse_t h, double tolW, double tolC)
+    {
+        if (int rc = need_factor(h, "lexls_lse_sensitivity_collect_resident")) return rc;
+        if (int rc = need_wrong_sign(h)) return rc;
+        HIP_TRY(launch_sensitivity(h->args(), h->d_objidx, 0, tolW, tolC, h->stream, h->sens_scan, h->max_level_dim, true));
+        return LEXLS_OK;
+    }
+
     int lexls_lse_multipliers(lexls_lse_t h)
     {
         if (int rc = need_factor(h, "lexls_lse_multipliers")) return rc;
@@ -1077,6 +1116,12 @@ extern "C"
         if (!rc && h_max_abs) rc = download(h, h_max_abs, h->d_maxabs, 8 * (size_t)h->batch);
         return rc;
     }
+    int lexls_lse_get_wrong_sign(lexls_lse_t h, uint8_t *h_mask)
+    {
+        CHECK_HANDLE(h);
+        if (!h->d_wrong_sign) return fail(LEXLS_ERR_INVALID, "lexls_lse_get_wrong_sign: call lexls_lse_sensitivity_collect first");
+        return download(h, h_mask, h->d_wrong_sign, (size_t)h->batch * (h->nVar + h->cap));
+    }
     int lexls_lse_get_fixed_type(lexls_lse_t h, uint8_t *h_types) { return h ? download(h, h_types, h->d_fixed_type, (size_t)h->batch * h->nVar) : fail(LEXLS_ERR_INVALID, "null handle"); }
     int lexls_lse_get_ctr_type(lexls_lse_t h, uint8_t *h_types) { return h ? download(h, h_types, h->d_ctr_type, (size_t)h->batch * h->cap) : fail(LEXLS_ERR_INVALID, "null handle"); }
 
@@ -1107,6 +1152,10 @@ extern "C"
                 HIP_TRY(hipMalloc((void **)&h->d_mult, 8 * (size_t)h->batch * h->nObj * (h->nVar + h->cap)));
             }
             *d_ptr = h->d_mult;
+            break;
+        case LEXLS_ARRAY_WRONG_SIGN:
+            if (int rc = need_wrong_sign(h)) return rc;
+            *d_ptr = h->d_wrong_sign;
             break;
         case LEXLS_ARRAY_INPUT:
             if (!h->d_in_owned)

@@ -62,6 +62,10 @@ namespace lexls
         // on is redone.  Same instructions on the same operands for everything that is recomputed: results identical bit for bit.
         const int32_t *resume_level;
         uint8_t *resume_state;
+        // The wrong-sign SET of the collecting removal search (lexls_lse_sensitivity_collect; lexlse.h:511-602): batch x (nVar + cap) bytes, the
+        // fixed variables first, then the constraint rows in LOD order; 1 where the reference pushes a ConstraintInfo.  NULL until a collecting
+        // call (or LEXLS_ARRAY_WRONG_SIGN) allocates it; the deciding search never touches it.
+        uint8_t *wrong_sign;
     };
     /// per problem: the position of every physical column after each level (nObj x 64 bytes) and after the last one (64 bytes)
     __host__ __device__ inline size_t resume_state_bytes(uint32_t nObj) { return 64 * ((size_t)nObj + 1); }

@@ -15,7 +15,8 @@ namespace lexls
     hipError_t launch_solve_generic(const LseArgs &a, hipStream_t s, bool reciprocal_diagonal = false);
     hipError_t launch_residual(const LseArgs &a, hipStream_t s);
     hipError_t launch_sensitivity(const LseArgs &a, const int32_t *d_obj_index, int32_t obj_all, double tolW, double tolC, hipStream_t s, bool scan_up = false,
-                                  uint32_t sweep_level_dim_hint = 0); // hint = largest level dimension of the batch (enables the single-sweep kernel)
+                                  uint32_t sweep_level_dim_hint = 0, // hint = largest level dimension of the batch (enables the single-sweep kernel)
+                                  bool collect = false);             // the wrong-sign SET into a.wrong_sign instead of one candidate (lexls_lse_sensitivity_collect)
     bool sensitivity_sweep_serves(const LseArgs &a, uint32_t sweep_level_dim_hint); // launch_sensitivity takes the one-wavefront-per-problem sweep for these arguments
     /// lexls_lse_multipliers: d_out = batch x nObj x (nVar + cap), column k = the [lambda_fixed; lambda] of ObjectiveSensitivity(k).  One launch of the
     /// sweep's emitting form where multipliers_sweep_serves, else nObj sensitivity_kernel launches (d_scratch: multipliers_scratch_bytes)

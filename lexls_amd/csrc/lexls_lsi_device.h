@@ -242,6 +242,14 @@ namespace
         uint32_t *row_src, *row_ld;
         uint8_t *fixed_type, *ctr_type;
         int32_t *resume; // B: the LexLSE level this iteration's working-set change sits in = the levels the next factorization may read back (NULL: off)
+        // deactivate_first_wrong_sign (lexlsi.h:1063-1105): the removal search leaves the SET of wrong-sign multipliers (lexls_lse_sensitivity_collect) and
+        // the constraint of it that entered the working set first leaves.  The reference keeps one list WS of all active constraints (push_back on
+        // activation, ordered erase on removal): an erase preserves the order of the rest, so a stamp per constraint, taken from a counter at its
+        // activation, carries the whole order — "first in WS among the candidates" = "smallest stamp among the candidates", no list to shift.
+        uint32_t first_wrong_sign;  // 0: the search names one constraint (a.sens), nothing below is touched
+        const uint8_t *wrong_sign;  // B x (n + cap): the set — fixed variables first, then the rows of the equality problem (LEXLS_ARRAY_WRONG_SIGN)
+        uint32_t *stamp;            // B x total: activation stamp per constraint (meaningful for the active ones)
+        uint32_t *next_stamp;       // B: the next stamp to hand out
     };
 
     /// LDS of one instance's wavefront: [dx n | A dx total | dv total] doubles, u16 na[STEP_MAX_OBJ], then the working-set lists
@@ -343,14 +351,44 @@ namespace
         const int blk_obj       = verdict.blk_obj;
         const uint32_t blk_ctr  = verdict.blk_ctr, blk_type = verdict.blk_type;
         const bool blocked      = blk_obj >= 0;
-        const int32_t found_i = blocked ? 0 : a.sens[(size_t)b * 3], rm_pos = blocked ? -1 : a.sens[(size_t)b * 3 + 1], rm_lvl = blocked ? -2 : a.sens[(size_t)b * 3 + 2];
+        const int32_t found_i = blocked ? 0 : a.sens[(size_t)b * 3];
+        int32_t rm_pos = blocked ? -1 : a.sens[(size_t)b * 3 + 1], rm_lvl = blocked ? -2 : a.sens[(size_t)b * 3 + 2];
+        if (a.first_wrong_sign && found_i != 0) // (wave-uniform)
+        {
+            // findFirstCtrWrongSign (lexlsi.h:1034-1046) over the set: row i of LexLSE level k is the i-th active constraint of objective k + off, fixed
+            // entry i the i-th active simple bound (lexlsi.h:1087-1096); the smallest stamp wins (stamps are unique: no ties)
+            const uint8_t *ws      = a.wrong_sign + (size_t)b * (n + a.cap);
+            const uint32_t *stamp  = a.stamp + (size_t)b * total;
+            double best            = INFINITY; // (a stamp is below 2^32: exact)
+            int32_t best_pos = -1, best_lvl = -2;
+            uint32_t row0 = 0;
+            for (uint32_t k = 0; k < sh.nObj; k++)
+            {
+                const uint32_t f = sh.first[k], nak = na[k];
+                const bool fixed = sh.simple[k] != 0;
+                for (uint32_t i = lane; i < nak; i += 64)
+                {
+                    if (fixed ? (i < n && ws[i]) : ws[n + row0 + i] != 0)
+                    {
+                        const double st = (double)stamp[f + act[f + i]];
+                        if (st < best) best = st, best_pos = (int32_t)i, best_lvl = (int32_t)k - (int32_t)a.off;
+                    }
+                }
+                if (!fixed) row0 += nak;
+            }
+            const double wmin = -lexls::wave_max(-best);
+            const unsigned long long who = __ballot(best == wmin);
+            const int win = (int)__builtin_ctzll(who ? who : 1ull);
+            rm_pos = __builtin_amdgcn_readlane(best_pos, win);
+            rm_lvl = __builtin_amdgcn_readlane(best_lvl, win);
+        }
         const int32_t nfact   = info[4] + 1; // lexlsi.h:1172
         const int32_t niter = info[1], nact = info[2], ndeact = info[3];
         const uint32_t trank = a.totalrank[b];
         (void)n;
 
         // ---- one working-set change (lexlsi.h:1181-1232) and the counters; lane 0 on the LDS copy ----
-        const bool removed = !blocked && found_i != 0;
+        const bool removed = !blocked && found_i != 0 && rm_pos >= 0; // (rm_pos < 0: a collected set nobody maps to — not reached with a consistent set)
         const bool done    = (!blocked && !removed) || nfact >= a.max_factorizations; // lexlsi.h:236-240
         if (lane == 0)
         {
@@ -363,6 +401,7 @@ namespace
                 cs[f + blk_ctr]    = (uint8_t)blk_type;
                 act[f + nak]       = (uint16_t)blk_ctr;
                 na[blk_obj]        = (uint16_t)(nak + 1);
+                if (a.first_wrong_sign) a.stamp[(size_t)b * total + f + blk_ctr] = a.next_stamp[b]++; // WS.push_back (lexlsi.h:148-173)
             }
             else if (removed) // OPERATION_REMOVE: workingset.h:99-108
             {

@@ -77,7 +77,9 @@ namespace lexls
         // EMIT (multipliers_sweep_kernel, lexls_lse_multipliers): the sweep of every objective and nothing else — column L of emit[b] (nObj columns of
         // nVar + cap, [lambda_fixed; lambda]) receives what the results block below writes for the objective the search stopped at, for every L;
         // no decisions, no marks, no types written.  EMIT = false is the removal search as it always was.
-        template <int MD, bool EMIT = false> // MD: rows per level the unrolled reflector loops cover (12 for the IK shapes: a quarter fewer wave-uniform tests than 16)
+        // COLLECT (lexls_lse_sensitivity_collect; lexlse.h:511-602 around :866-910, deactivate_first_wrong_sign): the same chains, and in place of the
+        // arg-min of the decisions block the SET of wrong-sign multipliers of the first objective that has one, as bytes in a.wrong_sign.
+        template <int MD, bool EMIT = false, bool COLLECT = false> // MD: rows per level the unrolled reflector loops cover (12 for the IK shapes: a quarter fewer wave-uniform tests than 16)
         __device__ __forceinline__ void sensitivity_sweep_body(const LseArgs &a, const int32_t *obj_index, int32_t obj_all, double tolW, double tolC, int scan_up, const uint32_t b,
                                                                double *emit = nullptr)
         {
@@ -310,6 +312,48 @@ namespace lexls
             double best   = 0.0;
             uint32_t bctr = 0;
             int bobj = -2, found = 0, Lout = oi;
+            if constexpr (COLLECT)
+            {
+                // The scan of lexlse.h:891-908 over the levels L .. 0 of objective L and then over the fixed variables: disjoint entries, so ONE pass over
+                // the rows serves all of them (their order only matters to an arg-min).  The fixed variables keep the reference's quirk (lexlse.h:599-600):
+                // min(dims[0], nVarFixed) entries, the CONSTRAINT multipliers Lambda[k] against fixed_var_type[k].  An objective with an empty set
+                // leaves only its marks; the next one sees them.
+                uint8_t *ws       = a.wrong_sign + (size_t)b * (n + cap);
+                const uint32_t nq = dims[0] < nf ? dims[0] : nf;
+                auto wrong_sign   = [&](uint8_t *ty, double al) __attribute__((always_inline)) {
+                    const uint8_t t = *ty;
+                    if (t == CTR_ACTIVE_LB) al = -al;
+                    const bool look = t != CTR_ACTIVE_EQ && t != CORRECT_SIGN_OF_LAMBDA;
+                    if (look && al > tolC) *ty = CORRECT_SIGN_OF_LAMBDA;
+                    return look && !(al > tolC) && al < -tolW;
+                };
+                for (int L = oi; L <= last; L++)
+                {
+                    Lout             = L;
+                    const double *lm = LamAll + (size_t)(L - oi) * cap;
+                    uint32_t nLam    = 0;
+                    for (int k = 0; k <= L; k++) nLam += dims[k];
+                    uint32_t cnt = 0;
+                    for (uint32_t i0 = 0; i0 < cap; i0 += 64) // (wave-uniform trips)
+                    {
+                        const uint32_t i = i0 + lane;
+                        const bool cand  = i < nLam ? wrong_sign(types + i, lm[i]) : false;
+                        if (i < cap) ws[n + i] = cand ? 1 : 0;
+                        cnt += (uint32_t)__popcll(__ballot(cand));
+                    }
+                    const bool candf = lane < nq ? wrong_sign(types + cap + lane, lm[lane]) : false; // (nVar <= 64 on this kernel)
+                    if (lane < n) ws[lane] = candf ? 1 : 0;
+                    cnt += (uint32_t)__popcll(__ballot(candf));
+                    __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
+                    asm volatile("" ::: "memory");
+                    bctr  = cnt;
+                    bobj  = L;
+                    found = cnt != 0;
+                    if (found) break;
+                }
+            }
+            else
+            {
             auto scan_group = [&](uint8_t *ty, const double *lm, uint32_t count, int tag) __attribute__((always_inline)) {
                 for (uint32_t g0 = 0; g0 < count; g0 += 16)
                 {
@@ -395,6 +439,7 @@ namespace lexls
                 if (nf > 0) scan_group(types + cap, FixAll + (size_t)(L - oi) * n, nf, -1);
                 if (found) break;
             }
+            }
 
             SSTAMP(4)
             // ---- results of the objective the search stopped at (getWorkspace: [lambda_fixed; lambda], lexlse.h:636-639) ----
@@ -416,8 +461,8 @@ namespace lexls
                 if (lane == 0)
                 {
                     sens[0]     = found;
-                    sens[1]     = found ? (int32_t)bctr : -1;
-                    sens[2]     = found ? bobj : -2;
+                    sens[1]     = (found || COLLECT) ? (int32_t)bctr : -1; // (COLLECT: {set non-empty, entries, objective the search stopped at})
+                    sens[2]     = (found || COLLECT) ? bobj : -2;
                     a.maxabs[b] = best;
                 }
             }
@@ -431,10 +476,10 @@ namespace lexls
 #endif
         }
 
-        template <int MD>
+        template <int MD, bool COLLECT = false>
         __global__ __launch_bounds__(64) void sensitivity_sweep_kernel(LseArgs a, const int32_t *obj_index, int32_t obj_all, double tolW, double tolC, int scan_up)
         {
-            sensitivity_sweep_body<MD>(a, obj_index, obj_all, tolW, tolC, scan_up, blockIdx.x);
+            sensitivity_sweep_body<MD, false, COLLECT>(a, obj_index, obj_all, tolW, tolC, scan_up, blockIdx.x);
         }
 
         /// every objective's multipliers of every problem (lexls_lse_multipliers): out = batch x nObj x (nVar + cap)

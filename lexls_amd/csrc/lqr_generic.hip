@@ -1123,8 +1123,33 @@ namespace lexls
             }
         }
 
+        /// the collecting form (lexlse.h:866-910, deactivate_first_wrong_sign): same marks, and every wrong-sign multiplier of the group is noted in
+        /// `mask` instead of the most negative one being kept; st->ctr counts them
+        __device__ void collect_wrong_sign(uint8_t *types, const double *lambda, uint32_t count, double tolW, double tolC, uint8_t *mask, SensState *st)
+        {
+            for (uint32_t k = 0; k < count; k++)
+            {
+                const uint8_t t = types[k];
+                if (t == CTR_ACTIVE_EQ || t == CORRECT_SIGN_OF_LAMBDA) continue;
+                double al = lambda[k];
+                if (t == CTR_ACTIVE_LB) al = -al;
+                if (al > tolC)
+                {
+                    types[k] = CORRECT_SIGN_OF_LAMBDA;
+                }
+                else if (al < -tolW)
+                {
+                    mask[k] = 1;
+                    st->ctr++;
+                    st->found = 1;
+                }
+            }
+        }
+
+        /// collect != 0 (lexls_lse_sensitivity_collect): the wrong-sign SET of lexlse.h:511-602 goes to a.wrong_sign, sens = {set non-empty, entries,
+        /// objective the search stopped at}, maxabs = 0
         template <int NT, bool STAGE>
-        __global__ __launch_bounds__(NT) void sensitivity_kernel(LseArgs a, const int32_t *obj_index, int32_t obj_all, double tolW, double tolC, int scan_up)
+        __global__ __launch_bounds__(NT) void sensitivity_kernel(LseArgs a, const int32_t *obj_index, int32_t obj_all, double tolW, double tolC, int scan_up, int collect)
         {
             extern __shared__ double smem[];
             const uint32_t b = blockIdx.x, tid = threadIdx.x;
@@ -1187,11 +1212,14 @@ namespace lexls
                 nLambda += dims[k];
             }
             for (uint32_t i = tid; i < n + cap + n; i += NT) smem[i] = 0.0;
+            uint8_t *ws = collect ? a.wrong_sign + (size_t)b * (n + cap) : nullptr;
+            if (collect) // (an objective is only looked at while the set is empty: cleared here, entries set by thread 0 behind the barrier)
+                for (uint32_t i = tid; i < n + cap; i += NT) ws[i] = 0;
             if (tid == 0)
             {
                 st->maxabs = 0.0;
                 st->ctr    = 0;
-                st->obj    = -2;
+                st->obj    = collect ? (int)ObjIndex : -2;
                 st->found  = 0;
             }
             __syncthreads();
@@ -1256,7 +1284,13 @@ namespace lexls
             else
                 apply_q_block<NT>(W, ld, hh, F, Fc, dim, rank, Lambda + F, bcast, tid);
             }
-            if (tid == 0) find_descent(ctr_type + F, Lambda + F, dim, tolW, tolC, (int)ObjIndex, st);
+            if (tid == 0)
+            {
+                if (collect)
+                    collect_wrong_sign(ctr_type + F, Lambda + F, dim, tolW, tolC, ws + n + F, st);
+                else
+                    find_descent(ctr_type + F, Lambda + F, dim, tolW, tolC, (int)ObjIndex, st);
+            }
 
             if (ObjIndex > 0)
             {
@@ -1281,7 +1315,13 @@ namespace lexls
                     {
                         rhs[c] -= chain_dot<8>(W + F + c * ld, Lambda + F, dim, 0.0);
                     }
-                    if (tid == 0) find_descent(ctr_type + F, Lambda + F, dim, tolW, tolC, (int)k, st);
+                    if (tid == 0)
+                    {
+                        if (collect)
+                            collect_wrong_sign(ctr_type + F, Lambda + F, dim, tolW, tolC, ws + n + F, st);
+                        else
+                            find_descent(ctr_type + F, Lambda + F, dim, tolW, tolC, (int)k, st);
+                    }
                     __syncthreads();
                 }
             }
@@ -1296,7 +1336,14 @@ namespace lexls
                     LambdaFixed[c] = -s;
                 }
                 __syncthreads();
-                if (tid == 0) find_descent(fix_type, LambdaFixed, nf, tolW, tolC, -1, st);
+                if (tid == 0)
+                {
+                    // (collect: the reference's quirk, lexlse.h:599-600 — min(dims[0], nVarFixed) entries, the constraint multipliers Lambda[k])
+                    if (collect)
+                        collect_wrong_sign(fix_type, Lambda, dims[0] < nf ? dims[0] : nf, tolW, tolC, ws, st);
+                    else
+                        find_descent(fix_type, LambdaFixed, nf, tolW, tolC, -1, st);
+                }
             }
             __syncthreads();
 
@@ -1313,8 +1360,8 @@ namespace lexls
             if (tid == 0)
             {
                 sens[0]     = st->found;
-                sens[1]     = st->found ? (int32_t)st->ctr : -1;
-                sens[2]     = st->found ? st->obj : -2;
+                sens[1]     = (st->found || collect) ? (int32_t)st->ctr : -1;
+                sens[2]     = (st->found || collect) ? st->obj : -2;
                 a.maxabs[b] = st->maxabs;
             }
             const int found = st->found; // (LDS, written before the last barrier)
@@ -1875,8 +1922,10 @@ namespace lexls
                a.batch <= 4u * (uint32_t)cus_of_current_device() && !std::getenv("LEXLS_SENS_NO_SWEEP");
     }
 
-    hipError_t launch_sensitivity(const LseArgs &a, const int32_t *d_obj_index, int32_t obj_all, double tolW, double tolC, hipStream_t s, bool scan_up, uint32_t sweep_level_dim_hint)
+    hipError_t launch_sensitivity(const LseArgs &a, const int32_t *d_obj_index, int32_t obj_all, double tolW, double tolC, hipStream_t s, bool scan_up, uint32_t sweep_level_dim_hint,
+                                  bool collect)
     {
+        if (collect && !a.wrong_sign) return hipErrorInvalidValue;
         const size_t lds = 8 * (2 * (size_t)a.nVar + a.cap + 2) + sizeof(SensState) + 16;
         if (lds > kMaxLdsBytes) return hipErrorInvalidValue;
         // Factor staged into LDS when latency is what counts: few problems per CU (a lock-step LSI stage) — with thousands of problems
@@ -1886,7 +1935,11 @@ namespace lexls
         const size_t lds_sweep  = sweep_lds_bytes(a);
         if (sensitivity_sweep_serves(a, sweep_level_dim_hint))
         {
-            if (sweep_level_dim_hint <= 12)
+            if (collect && sweep_level_dim_hint <= 12)
+                hipLaunchKernelGGL((sensitivity_sweep_kernel<12, true>), dim3(a.batch), dim3(64), lds_sweep, s, a, d_obj_index, obj_all, tolW, tolC, scan_up ? 1 : 0);
+            else if (collect)
+                hipLaunchKernelGGL((sensitivity_sweep_kernel<SWEEP_MD, true>), dim3(a.batch), dim3(64), lds_sweep, s, a, d_obj_index, obj_all, tolW, tolC, scan_up ? 1 : 0);
+            else if (sweep_level_dim_hint <= 12)
                 hipLaunchKernelGGL(sensitivity_sweep_kernel<12>, dim3(a.batch), dim3(64), lds_sweep, s, a, d_obj_index, obj_all, tolW, tolC, scan_up ? 1 : 0);
             else
                 hipLaunchKernelGGL(sensitivity_sweep_kernel<SWEEP_MD>, dim3(a.batch), dim3(64), lds_sweep, s, a, d_obj_index, obj_all, tolW, tolC, scan_up ? 1 : 0);
@@ -1901,12 +1954,12 @@ namespace lexls
                 hipError_t e = set_lds(sensitivity_kernel<64, true>, lds_staged);
                 if (e != hipSuccess) return e;
             }
-            hipLaunchKernelGGL((sensitivity_kernel<64, true>), dim3(a.batch), dim3(64), lds_staged, s, a, d_obj_index, obj_all, tolW, tolC, scan_up ? 1 : 0);
+            hipLaunchKernelGGL((sensitivity_kernel<64, true>), dim3(a.batch), dim3(64), lds_staged, s, a, d_obj_index, obj_all, tolW, tolC, scan_up ? 1 : 0, collect ? 1 : 0);
             return hipGetLastError();
         }
         hipError_t e = set_lds(sensitivity_kernel<64, false>, lds);
         if (e != hipSuccess) return e;
-        hipLaunchKernelGGL((sensitivity_kernel<64, false>), dim3(a.batch), dim3(64), lds, s, a, d_obj_index, obj_all, tolW, tolC, scan_up ? 1 : 0);
+        hipLaunchKernelGGL((sensitivity_kernel<64, false>), dim3(a.batch), dim3(64), lds, s, a, d_obj_index, obj_all, tolW, tolC, scan_up ? 1 : 0, collect ? 1 : 0);
         return hipGetLastError();
     }
 

@@ -314,7 +314,7 @@ struct lexls_lsi_batch_s
             LambdaBufs &lb = *lam_bufs[g];
             pool->run(ctx.B, [&](uint32_t k) { form_final_problem(g, k, lb); });
             stage(0, ctx);
-            // the equality solver's parameters of this run, whichever path it took (the one-by-one path of deactivate_first_wrong_sign never set
+            // the equality solver's parameters of this run, whichever path it took (the one-by-one path of a non-resident deactivate_first_wrong_sign run never set
             // them on these handles; an earlier run of the batch object may have left a regularization there): lam_rc == LEXLS_OK means unregularized
             hip_check(lexls_lse_set_tolerance(ctx.h, lam_tol));
             hip_check(lexls_lse_set_regularization(ctx.h, 0, NULL, 0, 0.0));
@@ -371,7 +371,9 @@ struct lexls_lsi_batch_s
                               : par.regularization_type != REGULARIZATION_NONE ? "lexls_lsi_batch_get_lambda: not available after a regularized run"
                                                                                 : "lexls_lsi_batch_get_lambda: not available when the constraint data is not resident on the device (or beyond 65535 constraints)";
         Run r{h_data, h_x0, h_v0, h_reg_factors, h_var_index, h_active_guess, par, h_x, h_v, h_info6, h_rounds2, h_active};
-        if (par.deactivate_first_wrong_sign)
+        // deactivate_first_wrong_sign is a removal rule the resident iterations know (collecting removal search + activation stamps, lexls_lsi_device.h);
+        // the host-driven lock-step stages of a whole run do not: where the run would not be resident its instances go one by one
+        if (par.deactivate_first_wrong_sign && !would_be_resident(par))
         {
             run_one_by_one(r, lam_after == LEXLS_OK);
             lam_rc  = (off && !h_var_index) ? LEXLS_ERR_INVALID : lam_after;
@@ -394,9 +396,9 @@ struct lexls_lsi_batch_s
         if (any_left) pool->run(batch, [&](uint32_t b) { r.lsi[b].reset(); }); // a thousand LexLSI objects (dozens of vectors each): freed in parallel, not serially on return
     }
 
-    /// The lock-step stages ask the device for ONE removal candidate per instance; deactivate_first_wrong_sign (lexlsi.h:1089-1103) wants every
-    /// wrong-sign multiplier of the first level that has one, read back per iteration.  Such a batch runs its instances one after the other
-    /// through the single-problem driver — same results as lexls_lsi_solve_ex on each, every equality problem on the GPU.
+    /// A deactivate_first_wrong_sign run (lexlsi.h:1089-1103) that cannot be resident (LEXLS_LSI_RESIDENT=0, cycling handling, regularization type 7,
+    /// no register-resident kernel, data not gathered): its instances go one after the other through the single-problem driver — same results as
+    /// lexls_lsi_solve_ex on each, every equality problem on the GPU, the wrong-sign multipliers read back per iteration.
     void run_one_by_one(Run &r, bool lambda_possible)
     {
         int32_t fs = 0;
@@ -427,6 +429,15 @@ struct lexls_lsi_batch_s
             throw Exception("upload of the variable indices failed");
     }
 
+    /// whole iterations on the device: plain runs and the regularized ones the register-resident kernel's REG instantiations serve (every
+    /// type but the experimental 7).  Cycling handling edits the host's bounds: host path, as every other case
+    bool would_be_resident(const ParametersLexLSI &par) const
+    {
+        const int reg_type = static_cast<int>(par.regularization_type);
+        return gather && !par.cycling_handling_enabled && resident_ok && grp[0]->resident && (reg_type == 0 || lexls_internal_resident_reg_serves(grp[0]->h, reg_type)) &&
+               par.max_number_of_factorizations < 0x7fffffff;
+    }
+
     /// every group back to what a fresh one holds, with this run's parameters; decides what kind of run it is
     void prepare_groups(Run &r)
     {
@@ -439,6 +450,7 @@ struct lexls_lsi_batch_s
             ctx.gather    = r.gather;
             if (!r.gather) ctx.need_staging();
             ctx.reset();
+            ctx.set_first_wrong_sign(r.par.deactivate_first_wrong_sign);
             hip_check(lexls_lse_set_tolerance(ctx.h, r.par.tol_linear_dependence));
             ctx.reg_type = static_cast<int>(r.par.regularization_type), ctx.reg_variable = r.par.variable_regularization_factor, ctx.reg_cg_iters = r.par.max_number_of_CG_iterations;
             ctx.reg_dirty.store(ctx.reg_type != 0);
@@ -449,10 +461,7 @@ struct lexls_lsi_batch_s
                 upload_variable_indices(r, g, ctx.d_var, ctx.shape.dim0);
             }
         }
-        // whole iterations on the device: plain runs and the regularized ones the register-resident kernel's REG instantiations serve (every
-        // type but the experimental 7).  Cycling handling edits the host's bounds: host path, as every other case
-        const int reg_type = static_cast<int>(r.par.regularization_type);
-        r.resident = r.gather && resident_ok && grp[0]->resident && (reg_type == 0 || lexls_internal_resident_reg_serves(grp[0]->h, reg_type)) && r.par.max_number_of_factorizations < 0x7fffffff;
+        r.resident = would_be_resident(r.par);
         r.step     = r.gather && grp[0]->device_step;
     }
 

@@ -113,10 +113,11 @@ namespace
         uint16_t *inact_pos(uint8_t *base, size_t b = 0) const { return reinterpret_cast<uint16_t *>(base + o_pos) + b * total; }
     };
     /// Slab of the resident iterations, as lsi_iterate_kernel reads it (ResidentArgs): ctr_state | alive | act | inact | inact_pos | na | info |
-    /// finished, every part 256-aligned.  base: the host mirror or the device slab; b: the instance.
+    /// finished | stamp | next_stamp, every part 256-aligned.  base: the host mirror or the device slab; b: the instance.  The activation stamps
+    /// (deactivate_first_wrong_sign) come last: only a run with that rule uploads them (bytes), every other copy stops in front of them (bytes_core).
     struct ResidentSlab
     {
-        size_t total = 0, o_alive = 0, o_act = 0, o_inact = 0, o_ipos = 0, o_na = 0, o_info = 0, o_fin = 0, bytes = 0;
+        size_t total = 0, o_alive = 0, o_act = 0, o_inact = 0, o_ipos = 0, o_na = 0, o_info = 0, o_fin = 0, o_stamp = 0, o_next = 0, bytes_core = 0, bytes = 0;
         explicit ResidentSlab(size_t B = 0, size_t total_ = 0) : total(total_)
         {
             auto up  = [](size_t v) { return (v + 255) & ~size_t(255); };
@@ -128,6 +129,9 @@ namespace
             o_na = o, o = up(o + 2 * B * RESIDENT_NA_STRIDE);
             o_info = o, o = up(o + 4 * B * RESIDENT_INFO_STRIDE);
             o_fin = o, o = up(o + 16);
+            bytes_core = o;
+            o_stamp = o, o = up(o + 4 * B * total);
+            o_next = o, o = up(o + 4 * B);
             bytes = o;
         }
         uint8_t *ctr_state(char *base, size_t b = 0) const { return reinterpret_cast<uint8_t *>(base) + b * total; }
@@ -138,6 +142,8 @@ namespace
         uint16_t *na(char *base, size_t b = 0) const { return reinterpret_cast<uint16_t *>(base + o_na) + b * RESIDENT_NA_STRIDE; }
         int32_t *info(char *base, size_t b = 0) const { return reinterpret_cast<int32_t *>(base + o_info) + b * RESIDENT_INFO_STRIDE; }
         uint32_t *finished(char *base) const { return reinterpret_cast<uint32_t *>(base + o_fin); }
+        uint32_t *stamp(char *base, size_t b = 0) const { return reinterpret_cast<uint32_t *>(base + o_stamp) + b * total; }
+        uint32_t *next_stamp(char *base) const { return reinterpret_cast<uint32_t *>(base + o_next); }
     };
 
     /// an instance's [x | v | A x] into its row of a state array (sh.SD doubles) ...
@@ -225,6 +231,9 @@ namespace
         int rounds_resident  = 0;
         std::vector<int32_t> iterations_at_handover;
         int rounds_fs_at_handover = 0, rounds_sens_at_handover = 0;
+        bool first_wrong_sign = false;     // this run removes by deactivate_first_wrong_sign: collecting removal searches, activation stamps
+        uint8_t *d_wrong_sign = NULL;      // the handle's LEXLS_ARRAY_WRONG_SIGN
+        Pinned<uint8_t> wrong_sign_host;   // B x (n + cap): the set of the last host-driven sensitivity stage (made at the first run with the rule)
         bool fused_all = false, fused_refused = false; // the rest of the resident iterations is one persistent launch / the shape has none
         const char *resident_kernel = "";              // the kernel that served the resident iterations of this run (download_resident)
         int rounds_fs = 0, rounds_sens = 0, rounds_step = 0;
@@ -311,6 +320,13 @@ namespace
             info[4]       = static_cast<int32_t>(inst.getFactorizationsCount());
             info[5]       = static_cast<int32_t>(totalrank[b]);
             info[6] = info[7] = 0; // prefix reuse: levels read back, summed over the resident factorizations; their number
+            if (first_wrong_sign) // position in the reference's WS list = stamp (lexlsi.h: activate / deactivate keep that list ordered by activation)
+            {
+                uint32_t *stamp = rl.stamp(base, b);
+                const std::vector<ConstraintInfo> &order = inst.getActivationOrder();
+                for (size_t p = 0; p < order.size(); p++) stamp[rshape.first[order[p].get_obj_index()] + order[p].get_ctr_index()] = static_cast<uint32_t>(p);
+                rl.next_stamp(base)[b] = static_cast<uint32_t>(order.size());
+            }
             rl.alive(base)[b] = 1;
             is_resident[b]    = 1; // (its staged equality problem is served by the first resident stage, followed by its removal sweep)
         }
@@ -344,14 +360,27 @@ namespace
             ra.fixed_type = reinterpret_cast<uint8_t *>(in + lay.fixed_type);
             ra.ctr_type   = reinterpret_cast<uint8_t *>(in + lay.ctr_type);
             ra.resume     = lexls_internal_resume_levels(h);
+            ra.first_wrong_sign = first_wrong_sign ? 1u : 0u;
+            ra.wrong_sign = d_wrong_sign, ra.stamp = rl.stamp(d_rws), ra.next_stamp = rl.next_stamp(d_rws);
             return ra;
+        }
+
+        /// the removal rule of the run that starts (deactivate_first_wrong_sign); the set's buffers are made at the first run that needs them
+        void set_first_wrong_sign(bool on)
+        {
+            first_wrong_sign = on;
+            if (!on || d_wrong_sign) return;
+            void *p = NULL;
+            hip_check(lexls_lse_device_ptr(h, LEXLS_ARRAY_WRONG_SIGN, &p));
+            d_wrong_sign = static_cast<uint8_t *>(p);
+            wrong_sign_host.assign((size_t)B * (n + cap), 0);
         }
 
         /// the handed-over instances start: slabs up, then `count` whole iterations are enqueued (nothing is waited for)
         void begin_resident()
         {
             *rl.finished(rws_host.data()) = 0u;
-            if (hipMemcpyAsync(d_rws, rws_host.data(), rl.bytes, hipMemcpyHostToDevice, stream) != hipSuccess ||
+            if (hipMemcpyAsync(d_rws, rws_host.data(), first_wrong_sign ? rl.bytes : rl.bytes_core, hipMemcpyHostToDevice, stream) != hipSuccess ||
                 hipMemcpyAsync(d_rstate, rstate_host.data(), 8 * (size_t)B * rshape.SD, hipMemcpyHostToDevice, stream) != hipSuccess)
                 throw Exception("hipMemcpyAsync failed (resident hand-over)");
             rounds_resident = 0;
@@ -390,7 +419,7 @@ namespace
                     lexls_internal_arm_resume(h);                                     // ... and the levels it found unchanged
                 }
                 hip_check(lexls_lse_factorize_solve(h, 1));
-                hip_check(lexls_lse_sensitivity_resident(h, tolW, tolC)); // speculative: used when the step is not blocked
+                hip_check(first_wrong_sign ? lexls_lse_sensitivity_collect_resident(h, tolW, tolC) : lexls_lse_sensitivity_resident(h, tolW, tolC)); // speculative: used when the step is not blocked
                 hipLaunchKernelGGL(lsi_iterate_kernel, dim3((B + 3) / 4), dim3(256), 4 * resident_lds_per_wave(rshape.SD, rshape.total), stream, ra);
                 if (hipGetLastError() != hipSuccess) throw Exception("lsi_iterate_kernel launch failed");
                 rounds_resident++, rounds_fs++, rounds_sens++;
@@ -423,7 +452,7 @@ namespace
         }
         void download_resident(bool stamps_dump)
         {
-            if (hipMemcpyAsync(rws_host.data(), d_rws, rl.bytes, hipMemcpyDeviceToHost, stream) != hipSuccess ||
+            if (hipMemcpyAsync(rws_host.data(), d_rws, rl.bytes_core, hipMemcpyDeviceToHost, stream) != hipSuccess ||
                 hipMemcpyAsync(rstate_host.data(), d_rstate, 8 * (size_t)B * rshape.SD, hipMemcpyDeviceToHost, stream) != hipSuccess ||
                 hipStreamSynchronize(stream) != hipSuccess)
                 throw Exception("download of the resident state failed");
@@ -477,7 +506,7 @@ namespace
             stage_fs = stage_sens = false;
             if (resident)
             {
-                std::fill(rws_host.begin(), rws_host.end(), 0);
+                std::fill(rws_host.begin(), rws_host.begin() + rl.bytes_core, 0); // (the stamps behind: hand_over writes every one a run reads)
                 std::fill(is_resident.begin(), is_resident.end(), 0);
                 n_resident      = 0;
                 rounds_resident = 0;
@@ -552,15 +581,18 @@ namespace
                     // latency-bound at these batch sizes and share the chip — second stream, joined again before the download
                     if (hipStreamWaitEvent(stream_sens, ev_uploaded, 0) != hipSuccess) throw Exception("hipStreamWaitEvent failed");
                     hip_check(lexls_lse_set_stream(h, stream_sens));
-                    hip_check(lexls_lse_sensitivity_resident(h, tolW, tolC));
+                    hip_check(first_wrong_sign ? lexls_lse_sensitivity_collect_resident(h, tolW, tolC) : lexls_lse_sensitivity_resident(h, tolW, tolC));
                     hip_check(lexls_lse_set_stream(h, stream));
                     if (hipEventRecord(ev_sens_done, stream_sens) != hipSuccess || hipStreamWaitEvent(stream, ev_sens_done, 0) != hipSuccess)
                         throw Exception("hipEventRecord / hipStreamWaitEvent failed");
                 }
                 else if (serve_fs)
-                    hip_check(lexls_lse_sensitivity_resident(h, tolW, tolC)); // behind the l-QR kernel: it reads the factors just made
+                    hip_check(first_wrong_sign ? lexls_lse_sensitivity_collect_resident(h, tolW, tolC) : lexls_lse_sensitivity_resident(h, tolW, tolC)); // behind the l-QR kernel: it reads the factors just made
                 else
-                    hip_check(lexls_lse_sensitivity(h, objidx.data(), 0, tolW, tolC));
+                    hip_check(first_wrong_sign ? lexls_lse_sensitivity_collect(h, objidx.data(), 0, tolW, tolC) : lexls_lse_sensitivity(h, objidx.data(), 0, tolW, tolC));
+                // the set itself, for the instances whose removal search the host still runs (phase 1: SlotLSE::ObjectiveSensitivity)
+                if (first_wrong_sign && hipMemcpyAsync(wrong_sign_host.data(), d_wrong_sign, (size_t)B * (n + cap), hipMemcpyDeviceToHost, stream) != hipSuccess)
+                    throw Exception("hipMemcpyAsync failed (wrong-sign set)");
                 rounds_sens++;
             }
             // x / total rank / sensitivity verdicts in one copy.  (The CORRECT_SIGN_OF_LAMBDA marks ObjectiveSensitivity leaves on the

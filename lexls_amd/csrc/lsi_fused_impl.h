@@ -30,6 +30,7 @@ namespace lexls
             double tolW, tolC;
             uint32_t img_doubles;
             int scan_up, count;
+            int collect; // deactivate_first_wrong_sign: the removal search collects the wrong-sign set (ResidentArgs::first_wrong_sign picks from it)
         };
         /// the kernel hands the phases the address of its argument segment (as an integer: function arguments travel in vector registers); a phase
         /// makes it a wave-uniform pointer into the constant address space again, so that its reads of the arguments are scalar loads
@@ -73,11 +74,11 @@ namespace lexls
             const FusedArgsReg &fr = fused_args_reg(kernarg);
             lqr_wave_body<NC, MD, EXACT, true, true>(fr.f.a, fr.f.img_doubles, fr.reg_cfg, b);
         }
-        template <int SMD>
+        template <int SMD, bool COLLECT = false>
         __device__ __noinline__ void fused_phase_sweep(unsigned long long kernarg, uint32_t b)
         {
             const FusedArgs &fa = fused_args(kernarg);
-            sensitivity_sweep_body<SMD>(fa.a, fa.obj_index, 0, fa.tolW, fa.tolC, fa.scan_up, b);
+            sensitivity_sweep_body<SMD, false, COLLECT>(fa.a, fa.obj_index, 0, fa.tolW, fa.tolC, fa.scan_up, b);
         }
         __device__ __noinline__ StepVerdict fused_phase_step(unsigned long long kernarg, uint32_t b) { return lsi_iterate_step(fused_args(kernarg).ra, b, 0u); }
         __device__ __noinline__ void fused_phase_finish(unsigned long long kernarg, uint32_t b, StepVerdict verdict)
@@ -125,7 +126,10 @@ namespace lexls
                 FUSED_STAMP(1)
                 if (verdict.blk_obj < 0) // the removal search only behind a step that nothing blocked (lexlsi.h:1181-1232; the per-stage launches run it
                 {                        // speculatively for every instance and ignore it for the blocked ones)
-                    fused_phase_sweep<SMD>(kernarg, b);
+                    if (fa.collect) // (wave-uniform; the plain search is the function it always was)
+                        fused_phase_sweep<SMD, true>(kernarg, b);
+                    else
+                        fused_phase_sweep<SMD>(kernarg, b);
                     fused_phase_fence();
 #ifdef LEXLS_FUSED_STAMPS
                     fn_sw++;
@@ -177,6 +181,8 @@ namespace lexls
             fa.img_doubles = wave_img_doubles<MD>(a);
             fa.scan_up     = scan_up ? 1 : 0;
             fa.count       = count;
+            fa.collect     = fa.ra.first_wrong_sign ? 1 : 0;
+            if (fa.collect && (!a.wrong_sign || fa.ra.wrong_sign != a.wrong_sign || !fa.ra.stamp)) return hipErrorInvalidValue;
             fr.reg_cfg     = 0;
             size_t lds      = wave_lds_bytes<NC, MD>(a, fa.img_doubles);
             if constexpr (REG) // the regularization routines' LDS behind the l-QR image, by the rule of the stage path's launcher

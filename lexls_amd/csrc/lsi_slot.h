@@ -89,7 +89,21 @@ namespace
             }
             return s3[0] != 0;
         }
-        void ObjectiveSensitivity(Index, RealScalar, RealScalar, std::vector<ConstraintInfo> &) { throw Exception("not available in lock-step batches"); }
+        /// the collecting overload (lexlse.h:511-602): the set the stage's lexls_lse_sensitivity_collect left, in the reference's push order (levels
+        /// from the objective the search stopped at downwards, then the fixed variables).  The stage went through the objectives by itself
+        /// (lexls_lse_set_sensitivity_scan): a call for a later objective finds the same — empty — set.
+        void ObjectiveSensitivity(Index, RealScalar, RealScalar, std::vector<ConstraintInfo> &ctr_wrong_sign)
+        {
+            if (!c->first_wrong_sign) throw Exception("SlotLSE: the stage did not collect the wrong-sign set");
+            const int32_t *s3 = &c->sens[(size_t)b * 3];
+            if (!s3[0]) return;
+            const uint8_t *ws = c->wrong_sign_host.data() + (size_t)b * (c->n + c->cap);
+            for (Index k = static_cast<Index>(s3[2]) + 1; k--;)
+                for (Index i = 0; i < getDim(k); i++)
+                    if (ws[c->n + first_row[k] + i]) ctr_wrong_sign.push_back(ConstraintInfo(static_cast<int>(k), static_cast<int>(i)));
+            for (Index i = 0; i < nVarFixed; i++)
+                if (ws[i]) ctr_wrong_sign.push_back(ConstraintInfo(-1, static_cast<int>(i)));
+        }
         const dVectorType &get_x() const { return x; }
         Index getTotalRank() const { return c->totalrank[b]; }
         Index getDim(Index k) const { return c->dims[(size_t)b * c->nObjL + k]; }

@@ -185,6 +185,31 @@ class BatchedLexLSE:
         capi.check(capi.lib().lexls_lse_get_sensitivity(self._h, _ptr(sens, C.c_int32), _ptr(maxabs, C.c_double)))
         return sens[:, 0].astype(bool), sens[:, 1], sens[:, 2], maxabs
 
+    def sensitivity_collect(self, ObjIndex, tol_wrong_sign_lambda=1e-8, tol_correct_sign_lambda=1e-12):
+        """The collecting overload ObjectiveSensitivity(ObjIndex, tolW, tolC, ctr_wrong_sign) (lexlse.h:511-602, deactivate_first_wrong_sign):
+        every wrong-sign multiplier instead of the most negative one.  ObjIndex: int (all problems), per-problem int32 array (negative =
+        skip) or None (the indices upload_round left on the device).  Returns (non_empty, entries, obj): per problem whether the set is
+        non-empty, its size and the objective the search stopped at; the set itself: wrong_sign()."""
+        lib = capi.lib()
+        if ObjIndex is None:
+            capi.check(lib.lexls_lse_sensitivity_collect_resident(self._h, C.c_double(tol_wrong_sign_lambda), C.c_double(tol_correct_sign_lambda)))
+        elif np.isscalar(ObjIndex):
+            capi.check(lib.lexls_lse_sensitivity_collect(self._h, None, C.c_int32(int(ObjIndex)), C.c_double(tol_wrong_sign_lambda), C.c_double(tol_correct_sign_lambda)))
+        else:
+            oi = np.ascontiguousarray(ObjIndex, np.int32)
+            assert oi.shape == (self.batch,)
+            capi.check(lib.lexls_lse_sensitivity_collect(self._h, _ptr(oi, C.c_int32), C.c_int32(0), C.c_double(tol_wrong_sign_lambda), C.c_double(tol_correct_sign_lambda)))
+        sens = np.zeros((self.batch, 3), np.int32)
+        capi.check(lib.lexls_lse_get_sensitivity(self._h, _ptr(sens, C.c_int32), None))
+        return sens[:, 0].astype(bool), sens[:, 1], sens[:, 2]
+
+    def wrong_sign(self):
+        """the set of the last sensitivity_collect call, (batch, nVar + cap) uint8: columns [0, nVar) the fixed variables in fixVariable order,
+        then the constraint rows in LOD order; 1 where the reference pushes a ConstraintInfo"""
+        m = np.zeros((self.batch, self.nVar + self.cap), np.uint8)
+        capi.check(capi.lib().lexls_lse_get_wrong_sign(self._h, _ptr(m, C.c_uint8)))
+        return m
+
     # ---- results --------------------------------------------------------------------------------
     def get_x(self):
         x = np.zeros((self.batch, self.nVar))
@@ -245,6 +270,12 @@ class BatchedLexLSE:
     def getCtrType(self):
         t = np.zeros((self.batch, self.cap), np.uint8)
         capi.check(capi.lib().lexls_lse_get_ctr_type(self._h, _ptr(t, C.c_uint8)))
+        return t
+
+    def getFixedType(self):
+        """activation types of the fixed variables incl. the CORRECT_SIGN_OF_LAMBDA marks, (batch, nVar)"""
+        t = np.zeros((self.batch, self.nVar), np.uint8)
+        capi.check(capi.lib().lexls_lse_get_fixed_type(self._h, _ptr(t, C.c_uint8)))
         return t
 
     def device_ptr(self, name: str) -> int:
