@@ -66,13 +66,23 @@ namespace LexLS
             void set_relax_step(RealScalar s) { step = s; }
             Index get_counter() const { return relaxations_done; }
 
-        private:
+            /// the last working-set change the handler was told of (valid: there was one)
             struct Event
             {
                 bool valid;
                 OperationType operation;
                 ConstraintIdentifier what;
             };
+            /// The handler's whole memory, for a backend that takes the iterations over from the host driver or hands them back (lock-step
+            /// device batches): the last event and the relaxations done.  The parameters (set_max_counter, set_relax_step) are not part of it.
+            const Event &get_last_event() const { return last; }
+            void set_state(const Event &last_event, Index relaxations_done_)
+            {
+                last             = last_event;
+                relaxations_done = relaxations_done_;
+            }
+
+        private:
             void forget()
             {
                 last.valid     = false;

@@ -273,6 +273,9 @@ namespace LexLS
             const dVectorType &get_residual_mu() { return lexlse.get_residual_mu(); }
 
             Index getCyclingCounter() const { return cycling_handler.get_counter(); }
+            /// the cycling handler itself: a backend that takes the iterations over at atIterationSolve() continues from its state
+            CyclingHandler &getCyclingHandler() { return cycling_handler; }
+            const CyclingHandler &getCyclingHandler() const { return cycling_handler; }
             Index getFactorizationsCount() const { return nFactorizations; }
             Index getActivationsCount() const { return nActivations; }
             Index getDeactivationsCount() const { return nDeactivations; }

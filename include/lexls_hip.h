@@ -374,11 +374,19 @@ int lexls_lsi_batch_run(lexls_lsi_batch_t b, const double *h_data, const uint32_
  * register-resident kernel, inside the persistent launch or as the stage's l-QR launch.  Such an iteration refactorizes every level (the
  * null-space basis the damping reads accumulates over the levels: no prefix reuse).  Where the regularization routines' LDS does not fit the
  * persistent launch's 64 KB the stages are taken, where it does not fit a workgroup at all the host path.  Host path as before, whatever the
- * type: regularization_type 7, cycling handling, shapes without a register-resident kernel.
+ * type: regularization_type 7, cycling handling of a regularized run, shapes without a register-resident kernel.
+ * cycling_handling_enabled (cycling.h:32-65) is part of the resident iteration of an unregularized run (regularization_type 0): the handler of
+ * every instance — its last working-set change, the relaxations it has done — travels with the instance when it leaves the host; an ADD of the
+ * (objective, constraint, type) that was just REMOVEd moves that bound by cycling_relax_step in the instance's resident constraint data, where the
+ * next equality problems, the step and v read it; after cycling_max_counter relaxations the instance ends PROBLEM_SOLVED_CYCLING_HANDLING (tested
+ * before the factorization limit, as lexlsi.h does).  Persistent launch and stages alike.  The caller's h_data is never written, and every run
+ * uploads it anew: nothing of a run's relaxations reaches the next one.  A REGULARIZED run with cycling handling keeps the host path (its
+ * instances relax their host copies of the bounds and the equality problems are assembled from those), as do LEXLS_LSI_RESIDENT=0, shapes
+ * without a register-resident kernel and data that is not resident (LEXLS_LSI_HOST_STAGING).
  * deactivate_first_wrong_sign (lexlsi.h:1063-1105) is a removal RULE, not another path: a run that would be resident without it is resident with
  * it — the removal search collects the wrong-sign set (lexls_lse_sensitivity_collect) and the iteration removes its member that entered the
  * working set first (an activation stamp per constraint carries the order of the reference's WS list).  Where such a run would not be resident
- * (LEXLS_LSI_RESIDENT=0, cycling handling, type 7, no register-resident kernel, data not resident) its instances go through the single-problem
+ * (LEXLS_LSI_RESIDENT=0, cycling handling of a regularized run, type 7, no register-resident kernel, data not resident) its instances go through the single-problem
  * driver one after the other.
  * lexls_lsi_batch_stats:
  * of the last lexls_lsi_batch_run: {factorize+solve stages, sensitivity stages, stages whose iteration step ran on the device, groups}.
@@ -399,10 +407,16 @@ int lexls_lsi_batch_destroy(lexls_lsi_batch_t b);
  * Cost to runs that never ask: none, except for a deactivate_first_wrong_sign run that is NOT resident — its instances go one by one through the
  * single-problem driver, which never uses the batch's handles, so the constraint data is copied to the device once per run (what get_lambda
  * gathers from later); a resident run with that rule has the data there already, like any other.
- * Errors: LEXLS_ERR_INVALID before any run (or after a failed one); LEXLS_ERR_UNSUPPORTED after a run with cycling_handling_enabled (the bounds it
- * relaxed live on the host only), after a regularized run (regularization_type != 0), or when the batch's constraint data is not resident
+ * Errors: LEXLS_ERR_INVALID before any run (or after a failed one); LEXLS_ERR_UNSUPPORTED after ANY run with cycling_handling_enabled (it may have
+ * relaxed bounds — in the instances' host copies on the host path, in the resident constraint data of a resident run — and the final equality
+ * problems are not re-formed from relaxed data after the run), after a regularized run (regularization_type != 0), or when the batch's constraint data is not resident
  * (LEXLS_LSI_HOST_STAGING, data beyond 2^31 doubles per instance) or holds more than 65535 constraints per instance.  A later run replaces the multipliers of the previous one. */
 int lexls_lsi_batch_get_lambda(lexls_lsi_batch_t b, double *h_lambda);
+/* LexLSI::getCyclingCounter() (lexlsi.h, CyclingHandler::get_counter, cycling.h) of every instance of the LAST lexls_lsi_batch_run on this batch:
+ * h_counts receives `batch` values, the bounds each instance's cycling handler relaxed (the working-set log's cycling_detected entries, counted).
+ * Whatever path served the run: host path, lock-step stages, persistent launch, one by one through the single-problem driver.  All zeros after a
+ * run without cycling handling.  Errors: LEXLS_ERR_INVALID before the first run or after a failed one. */
+int lexls_lsi_batch_get_cycling_counters(lexls_lsi_batch_t b, uint32_t *h_counts);
 /* lexls_lsi_solve plus what the MEX front end also passes (interfaces/matlab-octave/lexlsi.cpp:527-625): h_v0 = initial residuals,
  * sum(dims) doubles (set_v0 per objective) or NULL; h_reg_factors = one regularization factor per objective or NULL; h_params with
  * nparams == 9 (as lexls_lsi_solve) or 12: + regularization_type, variable_regularization_factor, max_number_of_CG_iterations. */
@@ -437,8 +451,9 @@ int lexls_lsi_solve_dat(int device, const char *path, int one_based, int use_act
 /* The kernel that served the resident active-set iterations of the LAST lexls_lsi_batch_run on this batch (a string the library owns):
  * "lsi_fused<lqr_wave<41,12,exact>>", "lsi_fused<lqr_wave<41,12,regularized>>", ... for the persistent launch; the l-QR kernel of the last
  * lock-step stage ("lqr_wave<41,12,regularized>", "lqr_quad<3,12,factor,fixed>", ...) where the stages ran (LEXLS_LSI_NO_FUSED=1, or no
- * persistent instantiation); "host" when no instance's iterations were resident (LEXLS_LSI_RESIDENT=0, regularization_type 7, cycling handling,
- * every instance done in phase 1); "" before the first run.  deactivate_first_wrong_sign does not change the name. */
+ * persistent instantiation); "host" when no instance's iterations were resident (LEXLS_LSI_RESIDENT=0, regularization_type 7, cycling handling of a
+ * regularized run, every instance done in phase 1); "" before the first run.  Neither deactivate_first_wrong_sign nor cycling handling of an
+ * unregularized run changes the name. */
 const char *lexls_lsi_batch_last_kernel(lexls_lsi_batch_t b);
 
 #ifdef __cplusplus

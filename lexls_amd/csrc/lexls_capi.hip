@@ -610,6 +610,7 @@ extern "C"
     }
 
     const double *lexls_internal_cdata(lexls_lse_t h) { return h ? h->d_cdata : nullptr; }
+    double *lexls_internal_cdata_writable(lexls_lse_t h) { return h ? h->d_cdata : nullptr; }
 
     char *lexls_internal_round_in(lexls_lse_t h) { return h ? h->d_round_in : nullptr; }
     int lexls_internal_round_resident(lexls_lse_t h, int has_fixed)

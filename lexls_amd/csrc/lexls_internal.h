@@ -11,6 +11,8 @@ extern "C"
     int lexls_internal_upload_round_trusted(lexls_lse_t h, const void *h_in, int gather);
     /// the resident constraint data (lexls_lse_set_constraint_data), read by the driver's step kernels
     const double *lexls_internal_cdata(lexls_lse_t h);
+    /// the same for the resident iterations of a run with cycling handling, which relax bounds in it (every run uploads the data anew)
+    double *lexls_internal_cdata_writable(lexls_lse_t h);
     /// the device copy of the in slab (lexls_lse_round_layout): the resident iterations write the next equality problem there themselves
     char *lexls_internal_round_in(lexls_lse_t h);
     /// the in slab was written ON THE DEVICE (same stream): gather the rows it names; kernel choice follows the capacities given at creation

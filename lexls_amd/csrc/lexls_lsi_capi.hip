@@ -104,6 +104,14 @@ extern "C"
         });
     }
 
+    int lexls_lsi_batch_get_cycling_counters(lexls_lsi_batch_t b, uint32_t *h_counts)
+    {
+        return guarded([&]() {
+            if (!b) throw Exception("lexls_lsi_batch_get_cycling_counters: null handle");
+            return b->get_cycling_counters(h_counts);
+        });
+    }
+
     int lexls_lsi_batch_solve_ex2(int device, uint32_t batch, uint32_t nVar, uint32_t nObj, const uint32_t *h_dims, const int32_t *h_types,
                                   const double *h_data, const uint32_t *h_var_index, const uint8_t *h_active_guess, const double *h_x0,
                                   const double *h_reg_factors, const double *h_params, uint32_t nparams, double *h_x, int32_t *h_info6,

@@ -222,7 +222,7 @@ namespace
         StepShape sh;
         uint32_t B, cap, nObjL, off; // off = 1: objective 0 is the simple-bounds objective (its active bounds are the fixed variables)
         int32_t max_factorizations;
-        const double *cdata;
+        double *cdata;             // B x per_data; written by a run with cycling handling only (a relaxed bound), read-only for every other
         const uint32_t *var;
         const double *x_lse;       // B x n
         const uint32_t *totalrank; // B
@@ -250,6 +250,13 @@ namespace
         const uint8_t *wrong_sign;  // B x (n + cap): the set — fixed variables first, then the rows of the equality problem (LEXLS_ARRAY_WRONG_SIGN)
         uint32_t *stamp;            // B x total: activation stamp per constraint (meaningful for the active ones)
         uint32_t *next_stamp;       // B: the next stamp to hand out
+        // cycling handling (cycling.h:32-65, lexlsi.h:642-662): the handler of every instance — its last working-set change and the relaxations it has
+        // done — lives in `cyc`; an ADD of the triple that was just REMOVEd relaxes that bound in the instance's constraint data (cdata), where
+        // every later reader finds it: the row gather of the next equality problems, fixed_val, the step's bound reads, hence the final v
+        uint32_t cycling;            // 0: nothing below is touched
+        uint32_t cycling_max_counter;
+        double cycling_relax_step;
+        uint32_t *cyc;               // B x RESIDENT_CYC_STRIDE: valid, operation, objective, constraint, type, relaxations done, -, -
     };
 
     /// LDS of one instance's wavefront: [dx n | A dx total | dv total] doubles, u16 na[STEP_MAX_OBJ], then the working-set lists
@@ -258,6 +265,9 @@ namespace
 
     /// per instance: entries of ResidentArgs::na and words of ResidentArgs::info (the host lays the slab out with the same: lsi_batch_ctx.h)
     constexpr uint32_t RESIDENT_NA_STRIDE = STEP_MAX_OBJ, RESIDENT_INFO_STRIDE = 8;
+    /// words of ResidentArgs::cyc per instance and what they hold
+    constexpr uint32_t RESIDENT_CYC_STRIDE = 8;
+    enum : uint32_t { CYC_VALID = 0, CYC_OPERATION, CYC_OBJ, CYC_CTR, CYC_TYPE, CYC_COUNT };
     /// LDS of one instance's wavefront and its slices of the resident arrays
     struct ResidentView
     {
@@ -265,7 +275,7 @@ namespace
         uint16_t *na, *act, *ina, *ipos;
         uint8_t *cs;
         double *st;
-        const double *data;
+        double *data;
         const uint32_t *var;
         uint8_t *g_cs;
         uint16_t *g_act, *g_ina, *g_ipos, *g_na;
@@ -345,7 +355,7 @@ namespace
         if (RELOAD) resident_load_lists(a, v, lane);
         uint16_t *na = v.na, *act = v.act, *ina = v.ina, *ipos = v.ipos;
         uint8_t *cs  = v.cs;
-        const double *data  = v.data;
+        double *data        = v.data;
         const uint32_t *var = v.var;
         int32_t *info       = v.info;
         const int blk_obj       = verdict.blk_obj;
@@ -389,7 +399,30 @@ namespace
 
         // ---- one working-set change (lexlsi.h:1181-1232) and the counters; lane 0 on the LDS copy ----
         const bool removed = !blocked && found_i != 0 && rm_pos >= 0; // (rm_pos < 0: a collected set nobody maps to — not reached with a consistent set)
-        const bool done    = (!blocked && !removed) || nfact >= a.max_factorizations; // lexlsi.h:236-240
+        // cycling handling (lexlsi.h:642-647, CyclingHandler::update): what this change is called — for a removal the constraint's index in its
+        // objective and the type it had BEFORE it left — and whether it closes a REMOVE -> ADD circle.  Every lane works it out (the lists are
+        // still as the step left them); lane 0 acts on it below
+        uint32_t *cyc = nullptr;
+        uint32_t ev_op = 0, ev_obj = 0, ev_ctr = 0, ev_type = 0;
+        bool cyc_relax = false, cyc_stop = false;
+        if (a.cycling && (blocked || removed)) // (wave-uniform)
+        {
+            cyc = a.cyc + (size_t)b * RESIDENT_CYC_STRIDE;
+            if (blocked)
+                ev_op = (uint32_t)internal::OPERATION_ADD, ev_obj = (uint32_t)blk_obj, ev_ctr = blk_ctr, ev_type = blk_type;
+            else
+            {
+                ev_op  = (uint32_t)internal::OPERATION_REMOVE;
+                ev_obj = (uint32_t)(rm_lvl + (int32_t)a.off);
+                ev_ctr = act[sh.first[ev_obj] + (uint32_t)rm_pos];
+                ev_type = cs[sh.first[ev_obj] + ev_ctr];
+            }
+            const bool circle = cyc[CYC_VALID] != 0 && blocked && cyc[CYC_OPERATION] == (uint32_t)internal::OPERATION_REMOVE && cyc[CYC_OBJ] == ev_obj &&
+                                cyc[CYC_CTR] == ev_ctr && cyc[CYC_TYPE] == ev_type;
+            cyc_stop  = circle && cyc[CYC_COUNT] >= a.cycling_max_counter; // PROBLEM_SOLVED_CYCLING_HANDLING: tested before the factorization limit (lexlsi.h:650-658)
+            cyc_relax = circle && !cyc_stop;
+        }
+        const bool done = (!blocked && !removed) || cyc_stop || nfact >= a.max_factorizations; // lexlsi.h:236-240
         if (lane == 0)
         {
             if (blocked) // OPERATION_ADD: workingset.h:79-92
@@ -414,6 +447,17 @@ namespace
                 ipos[f + c]  = (uint16_t)nik;
                 na[k]        = (uint16_t)(nak - 1);
             }
+            if (cyc && !cyc_stop) // (a circle beyond the allowed relaxations ends the instance and is not recorded)
+            {
+                if (cyc_relax) // Objective::relax_bounds (objective.h:774-790) on the resident data: [A lb ub] with ld = dim, or [lb ub]
+                {
+                    const uint32_t dim = sh.dim[ev_obj], ub = ev_type == CTR_ACTIVE_LB ? 0u : 1u;
+                    double *w          = data + sh.off[ev_obj] + ev_ctr + (size_t)(sh.simple[ev_obj] ? ub : n + ub) * dim;
+                    *w                 = ub ? *w + a.cycling_relax_step : *w - a.cycling_relax_step;
+                    cyc[CYC_COUNT] += 1u;
+                }
+                cyc[CYC_VALID] = 1u, cyc[CYC_OPERATION] = ev_op, cyc[CYC_OBJ] = ev_obj, cyc[CYC_CTR] = ev_ctr, cyc[CYC_TYPE] = ev_type;
+            }
             // prefix reuse: the change touches ONE objective; the equality problem's levels above it keep their rows (an activation appends to
             // its level, a removal erases in order: workingset.h:79-108), so the next factorization reads them back.  A change in the
             // simple-bounds objective changes the fixed variables: everything again.
@@ -423,7 +467,8 @@ namespace
                 a.resume[b]     = K;
                 if (!done) info[6] += K, info[7] += 1;
             }
-            info[0] = (!blocked && !removed) ? (int32_t)PROBLEM_SOLVED : (done ? (int32_t)MAX_NUMBER_OF_FACTORIZATIONS_EXCEEDED : info[0]);
+            info[0] = cyc_stop ? (int32_t)PROBLEM_SOLVED_CYCLING_HANDLING
+                               : ((!blocked && !removed) ? (int32_t)PROBLEM_SOLVED : (done ? (int32_t)MAX_NUMBER_OF_FACTORIZATIONS_EXCEEDED : info[0]));
             info[1] = niter + 1;
             info[2] = nact + (blocked ? 1 : 0);
             info[3] = ndeact + (removed ? 1 : 0);
@@ -439,6 +484,9 @@ namespace
         }
         __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
         asm volatile("" ::: "memory");
+        // a relaxed bound is one vector store of lane 0; the lanes below (fixed_val) read it with per-lane vector loads, as every reader of the
+        // constraint data does: the store has to be complete before them
+        if (cyc_relax) __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
         for (uint32_t g = lane; g < total; g += 64) // (a change touches a handful of entries; the lists are short: all of them go back)
         {
             v.g_act[g]  = act[g];

@@ -90,6 +90,7 @@ struct lexls_lsi_batch_s
         }
     };
     std::vector<std::unique_ptr<LambdaBufs>> lam_bufs;
+    std::vector<uint32_t> cycling_count; // batch: LexLSI::getCyclingCounter() of every instance of the last run (lexls_lsi_batch_get_cycling_counters)
 
     /// what a group's next stage must serve (Run::wants): somebody alive, a factorize+solve, a sensitivity, a device-side step, a solve whose x the host needs
     enum : uint32_t { WANT_ALIVE = 1u, WANT_FS = 2u, WANT_SENS = 4u, WANT_STEP = 8u, WANT_X = 16u };
@@ -132,6 +133,7 @@ struct lexls_lsi_batch_s
         ws_na.assign((size_t)batch * nObj, 0);
         ws_idx.assign((size_t)batch * total, 0);
         ws_type.assign((size_t)batch * total, 0);
+        cycling_count.assign(batch, 0u);
         if (off)
         {
             ws_fixvar.assign((size_t)batch * h_dims[0], 0);
@@ -347,6 +349,15 @@ struct lexls_lsi_batch_s
     }
 
 
+    /// LexLSI::getCyclingCounter() of every instance of the last run, whichever path served it
+    int get_cycling_counters(uint32_t *h_counts) const
+    {
+        if (lam_rc < 0) throw Exception("lexls_lsi_batch_get_cycling_counters: no completed lexls_lsi_batch_run on this batch");
+        if (!h_counts) throw Exception("lexls_lsi_batch_get_cycling_counters: null output");
+        std::copy(cycling_count.begin(), cycling_count.end(), h_counts);
+        return LEXLS_OK;
+    }
+
     runner::LsiProblem problem(const Run &r, uint32_t b) const
     {
         return {nVar, nObj, dims.data(), types.data(), r.h_data + (size_t)b * per_data, r.h_var_index ? r.h_var_index + (size_t)b * dims[0] : NULL,
@@ -365,9 +376,10 @@ struct lexls_lsi_batch_s
         lam_rc  = -1;
         lam_tol = par.tol_linear_dependence;
         last_kernel = "host";
+        std::fill(cycling_count.begin(), cycling_count.end(), 0u);
         // getLambda of this run needs the rows gathered from resident constraint data, unrelaxed bounds and unregularized factorizations
         const int lam_after = (par.cycling_handling_enabled || par.regularization_type != REGULARIZATION_NONE || !gather || total > 65535) ? LEXLS_ERR_UNSUPPORTED : LEXLS_OK;
-        const char *lam_why = par.cycling_handling_enabled ? "lexls_lsi_batch_get_lambda: not available after a run with cycling handling enabled (it relaxes bounds on the host)"
+        const char *lam_why = par.cycling_handling_enabled ? "lexls_lsi_batch_get_lambda: not available after a run with cycling handling enabled (it may have relaxed bounds: in the instances' host copies, or in the resident constraint data of a resident run)"
                               : par.regularization_type != REGULARIZATION_NONE ? "lexls_lsi_batch_get_lambda: not available after a regularized run"
                                                                                 : "lexls_lsi_batch_get_lambda: not available when the constraint data is not resident on the device (or beyond 65535 constraints)";
         Run r{h_data, h_x0, h_v0, h_reg_factors, h_var_index, h_active_guess, par, h_x, h_v, h_info6, h_rounds2, h_active};
@@ -396,7 +408,7 @@ struct lexls_lsi_batch_s
         if (any_left) pool->run(batch, [&](uint32_t b) { r.lsi[b].reset(); }); // a thousand LexLSI objects (dozens of vectors each): freed in parallel, not serially on return
     }
 
-    /// A deactivate_first_wrong_sign run (lexlsi.h:1089-1103) that cannot be resident (LEXLS_LSI_RESIDENT=0, cycling handling, regularization type 7,
+    /// A deactivate_first_wrong_sign run (lexlsi.h:1089-1103) that cannot be resident (LEXLS_LSI_RESIDENT=0, cycling handling of a regularized run, regularization type 7,
     /// no register-resident kernel, data not gathered): its instances go one after the other through the single-problem driver — same results as
     /// lexls_lsi_solve_ex on each, every equality problem on the GPU, the wrong-sign multipliers read back per iteration.
     void run_one_by_one(Run &r, bool lambda_possible)
@@ -409,6 +421,7 @@ struct lexls_lsi_batch_s
             fs += solve_one(lsi, device, p, r.par, r.h_x + (size_t)b * nVar, r.h_info6 ? r.h_info6 + (size_t)b * 6 : NULL, r.h_active ? r.h_active + (size_t)b * total : NULL,
                             r.h_v ? r.h_v + (size_t)b * total : NULL).factorizations;
             keep_working_set(b, lsi, p.data, p.var_index);
+            cycling_count[b] = static_cast<uint32_t>(lsi.getCyclingCounter());
         }
         last_stats[0] = fs, last_stats[1] = last_stats[2] = 0, last_stats[3] = 1;
         if (r.h_rounds2) r.h_rounds2[0] = fs, r.h_rounds2[1] = 0;
@@ -430,20 +443,25 @@ struct lexls_lsi_batch_s
     }
 
     /// whole iterations on the device: plain runs and the regularized ones the register-resident kernel's REG instantiations serve (every
-    /// type but the experimental 7).  Cycling handling edits the host's bounds: host path, as every other case
+    /// type but the experimental 7).  Cycling handling is part of the resident iteration of an unregularized run (the handler's state travels with the
+    /// instance, a relaxed bound is written into the resident constraint data: lexls_lsi_device.h); a regularized run with cycling handling keeps
+    /// the host path, as every other case
     bool would_be_resident(const ParametersLexLSI &par) const
     {
         const int reg_type = static_cast<int>(par.regularization_type);
-        return gather && !par.cycling_handling_enabled && resident_ok && grp[0]->resident && (reg_type == 0 || lexls_internal_resident_reg_serves(grp[0]->h, reg_type)) &&
+        return gather && (!par.cycling_handling_enabled || reg_type == 0) && resident_ok && grp[0]->resident && (reg_type == 0 || lexls_internal_resident_reg_serves(grp[0]->h, reg_type)) &&
                par.max_number_of_factorizations < 0x7fffffff;
     }
 
     /// every group back to what a fresh one holds, with this run's parameters; decides what kind of run it is
     void prepare_groups(Run &r)
     {
-        // Cycling handling relaxes bounds in the host copy of the constraint data (cycling.h:32-65, objective.h:774-790): such a run
-        // assembles its problems on the host from that copy instead of gathering rows of the resident (unrelaxed) device copy
-        r.gather = gather && !r.par.cycling_handling_enabled;
+        // Cycling handling on the host relaxes bounds in the instances' host copies of the constraint data (cycling.h:32-65, objective.h:774-790):
+        // such a run assembles its problems on the host from those copies instead of gathering rows of the resident (unrelaxed) device copy.
+        // A resident run relaxes the device copy itself; what the host does of it before the hand-over (at most one working-set change per
+        // instance) relaxes nothing, so its stages gather from the device copy like any other run's
+        r.resident = would_be_resident(r.par);
+        r.gather   = gather && (!r.par.cycling_handling_enabled || r.resident);
         for (uint32_t g = 0; g < nGroups; g++)
         {
             BatchCtx &ctx = *grp[g];
@@ -451,6 +469,7 @@ struct lexls_lsi_batch_s
             if (!r.gather) ctx.need_staging();
             ctx.reset();
             ctx.set_first_wrong_sign(r.par.deactivate_first_wrong_sign);
+            ctx.set_cycling(r.par.cycling_handling_enabled && r.resident, r.par.cycling_relax_step, static_cast<uint32_t>(r.par.cycling_max_counter));
             hip_check(lexls_lse_set_tolerance(ctx.h, r.par.tol_linear_dependence));
             ctx.reg_type = static_cast<int>(r.par.regularization_type), ctx.reg_variable = r.par.variable_regularization_factor, ctx.reg_cg_iters = r.par.max_number_of_CG_iterations;
             ctx.reg_dirty.store(ctx.reg_type != 0);
@@ -461,7 +480,6 @@ struct lexls_lsi_batch_s
                 upload_variable_indices(r, g, ctx.d_var, ctx.shape.dim0);
             }
         }
-        r.resident = would_be_resident(r.par);
         r.step     = r.gather && grp[0]->device_step;
     }
 
@@ -683,6 +701,7 @@ struct lexls_lsi_batch_s
             unpack_state(ctx.rstate_host.data() + (size_t)k * ctx.rshape.SD, nVar, total, x, v);
             if (r.h_active) std::copy(ctx.rl.ctr_state(ctx.rws_host.data(), k), ctx.rl.ctr_state(ctx.rws_host.data(), k) + total, r.h_active + (size_t)b * total);
             if (r.h_info6) std::memcpy(r.h_info6 + (size_t)b * 6, ctx.rl.info(ctx.rws_host.data(), k), 6 * sizeof(int32_t));
+            if (ctx.cycling) cycling_count[b] = ctx.rl.cyc(ctx.rws_host.data(), k)[CYC_COUNT];
             keep_working_set_resident(b, ctx, k, r.prob[b].data, r.prob[b].var_index);
             return;
         }
@@ -690,6 +709,7 @@ struct lexls_lsi_batch_s
         runner::collect(*r.lsi[b], r.prob[b], x, &info, r.h_active ? r.h_active + (size_t)b * total : NULL, v);
         if (r.h_info6) std::memcpy(r.h_info6 + (size_t)b * 6, &info, sizeof(info));
         keep_working_set(b, *r.lsi[b], r.prob[b].data, r.prob[b].var_index);
+        cycling_count[b] = static_cast<uint32_t>(r.lsi[b]->getCyclingCounter());
         if (r.step && ctx.on_device[k]) unpack_state(ctx.state_host.data() + (size_t)k * ctx.shape.SD, nVar, total, x, v);
     }
     void collect(Run &r)

@@ -113,11 +113,14 @@ namespace
         uint16_t *inact_pos(uint8_t *base, size_t b = 0) const { return reinterpret_cast<uint16_t *>(base + o_pos) + b * total; }
     };
     /// Slab of the resident iterations, as lsi_iterate_kernel reads it (ResidentArgs): ctr_state | alive | act | inact | inact_pos | na | info |
-    /// finished | stamp | next_stamp, every part 256-aligned.  base: the host mirror or the device slab; b: the instance.  The activation stamps
-    /// (deactivate_first_wrong_sign) come last: only a run with that rule uploads them (bytes), every other copy stops in front of them (bytes_core).
+    /// finished | stamp | next_stamp | cyc, every part 256-aligned.  base: the host mirror or the device slab; b: the instance.  The activation stamps
+    /// (deactivate_first_wrong_sign) follow the core: only a run with that rule uploads them (bytes_stamps), every other copy stops in front of them
+    /// (bytes_core).  The cycling handlers' state (RESIDENT_CYC_STRIDE words per instance, laid out like info) comes last and travels, as a copy
+    /// of its own each way, only in runs with cycling handling (o_cyc, bytes_cyc).
     struct ResidentSlab
     {
-        size_t total = 0, o_alive = 0, o_act = 0, o_inact = 0, o_ipos = 0, o_na = 0, o_info = 0, o_fin = 0, o_stamp = 0, o_next = 0, bytes_core = 0, bytes = 0;
+        size_t total = 0, o_alive = 0, o_act = 0, o_inact = 0, o_ipos = 0, o_na = 0, o_info = 0, o_fin = 0, o_stamp = 0, o_next = 0, o_cyc = 0, bytes_core = 0, bytes_stamps = 0,
+               bytes_cyc = 0, bytes = 0;
         explicit ResidentSlab(size_t B = 0, size_t total_ = 0) : total(total_)
         {
             auto up  = [](size_t v) { return (v + 255) & ~size_t(255); };
@@ -132,6 +135,9 @@ namespace
             bytes_core = o;
             o_stamp = o, o = up(o + 4 * B * total);
             o_next = o, o = up(o + 4 * B);
+            bytes_stamps = o;
+            o_cyc = o, o = up(o + 4 * B * RESIDENT_CYC_STRIDE);
+            bytes_cyc = 4 * B * RESIDENT_CYC_STRIDE;
             bytes = o;
         }
         uint8_t *ctr_state(char *base, size_t b = 0) const { return reinterpret_cast<uint8_t *>(base) + b * total; }
@@ -144,6 +150,7 @@ namespace
         uint32_t *finished(char *base) const { return reinterpret_cast<uint32_t *>(base + o_fin); }
         uint32_t *stamp(char *base, size_t b = 0) const { return reinterpret_cast<uint32_t *>(base + o_stamp) + b * total; }
         uint32_t *next_stamp(char *base) const { return reinterpret_cast<uint32_t *>(base + o_next); }
+        uint32_t *cyc(char *base, size_t b = 0) const { return reinterpret_cast<uint32_t *>(base + o_cyc) + b * RESIDENT_CYC_STRIDE; }
     };
 
     /// an instance's [x | v | A x] into its row of a state array (sh.SD doubles) ...
@@ -234,6 +241,9 @@ namespace
         bool first_wrong_sign = false;     // this run removes by deactivate_first_wrong_sign: collecting removal searches, activation stamps
         uint8_t *d_wrong_sign = NULL;      // the handle's LEXLS_ARRAY_WRONG_SIGN
         Pinned<uint8_t> wrong_sign_host;   // B x (n + cap): the set of the last host-driven sensitivity stage (made at the first run with the rule)
+        bool cycling = false;              // this run handles cycling on the device: handler state in the slab, relaxed bounds in the resident constraint data
+        double cycling_relax_step = 0.0;
+        uint32_t cycling_max_counter = 0;
         bool fused_all = false, fused_refused = false; // the rest of the resident iterations is one persistent launch / the shape has none
         const char *resident_kernel = "";              // the kernel that served the resident iterations of this run (download_resident)
         int rounds_fs = 0, rounds_sens = 0, rounds_step = 0;
@@ -327,6 +337,19 @@ namespace
                 for (size_t p = 0; p < order.size(); p++) stamp[rshape.first[order[p].get_obj_index()] + order[p].get_ctr_index()] = static_cast<uint32_t>(p);
                 rl.next_stamp(base)[b] = static_cast<uint32_t>(order.size());
             }
+            if (cycling) // iteration 0 ran on the host and may have told the handler of an ADD or a REMOVE: the device continues from there.  (No bound is
+            {            // relaxed yet — a circle takes two changes, the host made at most one — so the uploaded constraint data is the handler's data.)
+                const internal::CyclingHandler &ch = inst.getCyclingHandler();
+                uint32_t *c                        = rl.cyc(base, b);
+                std::fill(c, c + RESIDENT_CYC_STRIDE, 0u);
+                c[CYC_VALID]     = ch.get_last_event().valid ? 1u : 0u;
+                c[CYC_OPERATION] = static_cast<uint32_t>(ch.get_last_event().operation);
+                c[CYC_OBJ]       = static_cast<uint32_t>(ch.get_last_event().what.obj_index);
+                c[CYC_CTR]       = static_cast<uint32_t>(ch.get_last_event().what.ctr_index);
+                c[CYC_TYPE]      = static_cast<uint32_t>(ch.get_last_event().what.ctr_type);
+                c[CYC_COUNT]     = static_cast<uint32_t>(ch.get_counter());
+                if (ch.get_counter() != 0) throw Exception("lexls_lsi_batch_run: a bound was relaxed before the instance became resident");
+            }
             rl.alive(base)[b] = 1;
             is_resident[b]    = 1; // (its staged equality problem is served by the first resident stage, followed by its removal sweep)
         }
@@ -341,7 +364,7 @@ namespace
             ra.sh     = rshape;
             ra.B = B, ra.cap = cap, ra.nObjL = nObjL, ra.off = r_off;
             ra.max_factorizations = max_factorizations;
-            ra.cdata     = lexls_internal_cdata(h);
+            ra.cdata     = lexls_internal_cdata_writable(h);
             ra.var       = d_rvar;
             ra.x_lse     = reinterpret_cast<const double *>(out + lay.x);
             ra.totalrank = reinterpret_cast<const uint32_t *>(out + lay.total_rank);
@@ -362,6 +385,7 @@ namespace
             ra.resume     = lexls_internal_resume_levels(h);
             ra.first_wrong_sign = first_wrong_sign ? 1u : 0u;
             ra.wrong_sign = d_wrong_sign, ra.stamp = rl.stamp(d_rws), ra.next_stamp = rl.next_stamp(d_rws);
+            ra.cycling = cycling ? 1u : 0u, ra.cycling_max_counter = cycling_max_counter, ra.cycling_relax_step = cycling_relax_step, ra.cyc = rl.cyc(d_rws);
             return ra;
         }
 
@@ -376,11 +400,15 @@ namespace
             wrong_sign_host.assign((size_t)B * (n + cap), 0);
         }
 
+        /// cycling handling of the run that starts (on: the resident iterations do it; a run that handles cycling on the host passes off)
+        void set_cycling(bool on, double relax_step, uint32_t max_counter) { cycling = on, cycling_relax_step = relax_step, cycling_max_counter = max_counter; }
+
         /// the handed-over instances start: slabs up, then `count` whole iterations are enqueued (nothing is waited for)
         void begin_resident()
         {
             *rl.finished(rws_host.data()) = 0u;
-            if (hipMemcpyAsync(d_rws, rws_host.data(), first_wrong_sign ? rl.bytes : rl.bytes_core, hipMemcpyHostToDevice, stream) != hipSuccess ||
+            if (hipMemcpyAsync(d_rws, rws_host.data(), first_wrong_sign ? rl.bytes_stamps : rl.bytes_core, hipMemcpyHostToDevice, stream) != hipSuccess ||
+                (cycling && hipMemcpyAsync(d_rws + rl.o_cyc, rws_host.data() + rl.o_cyc, rl.bytes_cyc, hipMemcpyHostToDevice, stream) != hipSuccess) ||
                 hipMemcpyAsync(d_rstate, rstate_host.data(), 8 * (size_t)B * rshape.SD, hipMemcpyHostToDevice, stream) != hipSuccess)
                 throw Exception("hipMemcpyAsync failed (resident hand-over)");
             rounds_resident = 0;
@@ -453,6 +481,7 @@ namespace
         void download_resident(bool stamps_dump)
         {
             if (hipMemcpyAsync(rws_host.data(), d_rws, rl.bytes_core, hipMemcpyDeviceToHost, stream) != hipSuccess ||
+                (cycling && hipMemcpyAsync(rws_host.data() + rl.o_cyc, d_rws + rl.o_cyc, rl.bytes_cyc, hipMemcpyDeviceToHost, stream) != hipSuccess) || // the relaxations done
                 hipMemcpyAsync(rstate_host.data(), d_rstate, 8 * (size_t)B * rshape.SD, hipMemcpyDeviceToHost, stream) != hipSuccess ||
                 hipStreamSynchronize(stream) != hipSuccess)
                 throw Exception("download of the resident state failed");

@@ -262,7 +262,7 @@ class LsiBatch:
     def last_kernel(self) -> str:
         """the kernel that served the resident active-set iterations of the last run (lexls_lsi_batch_last_kernel): the persistent launch
         ("lsi_fused<...>", with "regularized" for a regularized run), the l-QR kernel of the lock-step stages, or "host" when the run was not
-        resident"""
+        resident (LEXLS_LSI_RESIDENT=0, regularization type 7, cycling handling of a regularized run, ...)"""
         return capi.lib().lexls_lsi_batch_last_kernel(self._h).decode()
 
     def run(self, problems, active_guess=None, x0=None, regularization_factors=None, v0=None, **params):
@@ -291,6 +291,13 @@ class LsiBatch:
             _p(rounds, C.c_int32)))
         return dict(x=x, info=InfoRows(info), active=active, v=v,
                     rounds=dict(factorize_solve=int(rounds[0]), sensitivity=int(rounds[1])), dims=self.dims)
+
+    def cycling_counters(self) -> np.ndarray:
+        """LexLSI::getCyclingCounter() of every instance of the last run (lexls_lsi_batch_get_cycling_counters): (batch,) uint32, the bounds each
+        instance's cycling handler relaxed; zeros after a run without cycling_handling_enabled"""
+        counts = np.zeros(self.batch, np.uint32)
+        capi.check(capi.lib().lexls_lsi_batch_get_cycling_counters(self._h, _p(counts, C.c_uint32)))
+        return counts
 
     def lambda_array(self) -> np.ndarray:
         """getLambda of every instance of the last run (lexls_lsi_batch_get_lambda): (batch, nObj, total) — instance b's total x nObj
