@@ -363,6 +363,22 @@ int lexls_lsi_batch_create(lexls_lsi_batch_t *out, int device, uint32_t batch, u
 int lexls_lsi_batch_run(lexls_lsi_batch_t b, const double *h_data, const uint32_t *h_var_index, const uint8_t *h_active_guess, const double *h_x0,
                         const double *h_v0 /* batch x sum(dims) initial residuals (set_v0, lexlsi.cpp:571-588) or NULL */, const double *h_reg_factors, const double *h_params, uint32_t nparams, double *h_x, int32_t *h_info6, uint8_t *h_active,
                         double *h_v, int32_t *h_rounds2);
+/* lexls_lsi_batch_run for a caller whose problems are in device memory already (a simulator, a torch pipeline): the same arrays and layouts, in
+ * memory of the batch's device — d_data (batch x per-instance data), d_var_index (batch x dims[0]; required with a simple-bounds objective 0, else
+ * NULL), d_active_guess / d_x0 (may be NULL) in, d_x (required) and d_info6 / d_active / d_v (may be NULL) out.  It stands for these members of
+ * lexls_lsi_batch_run: h_data, h_var_index, h_active_guess, h_x0, h_x, h_info6, h_active, h_v; h_v0 and h_rounds2 have no counterpart (initial
+ * residuals are not offered here; lexls_lsi_batch_stats has the stage counts).  Parameters and regularization factors stay host arrays.
+ * The caller has finished writing the inputs before the call; the call returns when the outputs are complete (host-synchronous).  No constraint
+ * data, state or result passes through host memory: the data is copied device-to-device into every group's resident copy (the caller's arrays
+ * are never written, runs with cycling handling included), phase 1 is device work (below), a scatter kernel writes the results from the resident
+ * slabs.  What does come back to the host: a fault word, the count of stopped instances, and after the run the working-set lists and counters
+ * that lexls_lsi_batch_get_lambda / _get_cycling_counters / _stats / _last_kernel answer from, as after the equivalent lexls_lsi_batch_run.
+ * Serves every run that is resident (next paragraph).  Everything else returns LEXLS_ERR_UNSUPPORTED before any device work and leaves the outputs
+ * alone — LEXLS_LSI_RESIDENT=0, LEXLS_LSI_HOST_STAGING, regularization_type 7, cycling handling of a regularized run, shapes without a
+ * register-resident kernel: there is no detour over the host.  An instance with lb > ub, variable indices that repeat or are not below nVar, or a
+ * guess flag above 3 ends the call with LEXLS_ERR_INVALID before anything is solved; lexls_last_error() names the first such instance and the reason. */
+int lexls_lsi_batch_run_device(lexls_lsi_batch_t b, const double *d_data, const uint32_t *d_var_index, const uint8_t *d_active_guess,
+                               const double *d_x0, const double *h_reg_factors, const double *h_params, uint32_t nparams, double *d_x, int32_t *d_info6, uint8_t *d_active, double *d_v);
 /* How a run executes: phase 1 of every instance on the host; from then on the instance's active-set iterations are resident on the
  * device (LEXLS_LSI_RESIDENT=0: host logic, lock-step stages).  Where the batch's shape has a persistent instantiation (the register-resident l-QR shapes:
  * nVar + 1 <= 41 with levels of up to 12 rows, nVar + 1 <= 64 with levels of up to 16 — except 42..48 columns), everything behind the first resident
@@ -388,6 +404,13 @@ int lexls_lsi_batch_run(lexls_lsi_batch_t b, const double *h_data, const uint32_
  * working set first (an activation stamp per constraint carries the order of the reference's WS list).  Where such a run would not be resident
  * (LEXLS_LSI_RESIDENT=0, cycling handling of a regularized run, type 7, no register-resident kernel, data not resident) its instances go through the single-problem
  * driver one after the other.
+ * Phase 1 as device work: lexls_lsi_batch_run_device always, lexls_lsi_batch_run when LEXLS_LSI_DEVICE_PHASE1=1 is in the environment (read per
+ * run; off by default) and the run is resident and has no h_v0 — otherwise the switch changes nothing.  No host LexLSI objects are built: one
+ * kernel does the input checks and equality activations of LexLSI::setData, api_activate over the guess (the working-set lists and activation
+ * stamps in the reference's order), A x0 and v0, and writes the first equality problem into the equality solver's in slab; the stage of every
+ * resident iteration follows (l-QR + speculative removal search), then iteration 0 as the resident iteration itself (without x0: on x = the
+ * solution of the first problem, with dx = 0).  Same results bit for bit, the same kernels named by lexls_lsi_batch_last_kernel, phase 1's stage
+ * counted by lexls_lsi_batch_stats like any other.  The host path's printf warnings are not reproduced; the input faults above are errors.
  * lexls_lsi_batch_stats:
  * of the last lexls_lsi_batch_run: {factorize+solve stages, sensitivity stages, stages whose iteration step ran on the device, groups}.
  * The step of an iteration (A*dx, ratio test, update of x / v / A*x: lexlsi.h:987-1029, :1234-1240) runs on the device

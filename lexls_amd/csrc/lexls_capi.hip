@@ -572,6 +572,33 @@ extern "C"
         return LEXLS_OK;
     }
 
+    int lexls_internal_set_constraint_data_device(lexls_lse_t h, const double *d_data, uint64_t per_problem)
+    {
+        CHECK_HANDLE(h);
+        if (!d_data || per_problem == 0) return fail(LEXLS_ERR_INVALID, "set_constraint_data_device: null / empty");
+        HIP_TRY(hipSetDevice(h->device));
+        const size_t bytes = 8 * (size_t)h->batch * per_problem;
+        if (h->d_cdata && h->cdata_per_problem != per_problem)
+        {
+            HIP_TRY(hipFree(h->d_cdata));
+            h->d_cdata = nullptr;
+        }
+        if (!h->d_cdata) HIP_TRY(hipMalloc((void **)&h->d_cdata, bytes));
+        h->cdata_per_problem = per_problem;
+        HIP_TRY(hipMemcpyAsync(h->d_cdata, d_data, bytes, hipMemcpyDeviceToDevice, h->stream));
+        return LEXLS_OK;
+    }
+
+    int lexls_internal_ensure_gather_buffer(lexls_lse_t h)
+    {
+        CHECK_HANDLE(h);
+        if (h->d_in_owned) return LEXLS_OK;
+        HIP_TRY(hipSetDevice(h->device));
+        HIP_TRY(hipMalloc((void **)&h->d_in_owned, 8 * (size_t)h->batch * h->problem_elems()));
+        HIP_TRY(hipMemsetAsync(h->d_in_owned, 0, 8 * (size_t)h->batch * h->problem_elems(), h->stream));
+        return LEXLS_OK;
+    }
+
     int lexls_lse_gather_problem(lexls_lse_t h, const uint32_t *h_row_src, const uint32_t *h_row_ld)
     {
         CHECK_HANDLE(h);

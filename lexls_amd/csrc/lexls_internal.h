@@ -11,6 +11,10 @@ extern "C"
     int lexls_internal_upload_round_trusted(lexls_lse_t h, const void *h_in, int gather);
     /// the resident constraint data (lexls_lse_set_constraint_data), read by the driver's step kernels
     const double *lexls_internal_cdata(lexls_lse_t h);
+    /// lexls_lse_set_constraint_data from memory of the handle's device: a device-to-device copy, only ENQUEUED in the handle's stream
+    int lexls_internal_set_constraint_data_device(lexls_lse_t h, const double *d_data, uint64_t per_problem);
+    /// the buffer gathered rows go to exists (a handle that never uploaded a round has none; lexls_internal_round_resident needs it)
+    int lexls_internal_ensure_gather_buffer(lexls_lse_t h);
     /// the same for the resident iterations of a run with cycling handling, which relax bounds in it (every run uploads the data anew)
     double *lexls_internal_cdata_writable(lexls_lse_t h);
     /// the device copy of the in slab (lexls_lse_round_layout): the resident iterations write the next equality problem there themselves

@@ -96,6 +96,26 @@ extern "C"
         });
     }
 
+    int lexls_lsi_batch_run_device(lexls_lsi_batch_t b, const double *d_data, const uint32_t *d_var_index, const uint8_t *d_active_guess, const double *d_x0,
+                                   const double *h_reg_factors, const double *h_params, uint32_t nparams, double *d_x, int32_t *d_info6, uint8_t *d_active, double *d_v)
+    {
+        return guarded([&]() {
+            if (!b) throw Exception("lexls_lsi_batch_run_device: null handle");
+            if (h_params && nparams != 9 && nparams != 12) throw Exception("lexls_lsi_batch_run_device: 9 or 12 parameters expected");
+            if (!d_data || !d_x) throw Exception("lexls_lsi_batch_run_device: null data / x");
+            if (b->off && !d_var_index) throw Exception("lexls_lsi_batch_run_device: a simple-bounds objective needs variable indices");
+            const ParametersLexLSI par = unpack(h_params, nparams);
+            if (!b->would_be_resident(par)) // no detour over the host: nothing is launched, the outputs stay as they are
+            {
+                lexls_internal_set_error("lexls_lsi_batch_run_device: only runs that are resident on the device are served (not: LEXLS_LSI_RESIDENT=0, LEXLS_LSI_HOST_STAGING, "
+                                         "regularization type 7, cycling handling of a regularized run, shapes without a register-resident kernel)");
+                return static_cast<int>(LEXLS_ERR_UNSUPPORTED);
+            }
+            b->run_device({d_data, d_var_index, d_active_guess, d_x0, d_x, d_info6, d_active, d_v}, h_reg_factors, par);
+            return static_cast<int>(LEXLS_OK);
+        });
+    }
+
     int lexls_lsi_batch_get_lambda(lexls_lsi_batch_t b, double *h_lambda)
     {
         return guarded([&]() {

@@ -5,6 +5,7 @@
 #include <lexls/lexls.h>
 #include <hip/hip_runtime.h>
 #include "lqr_wave_common.h" // wave_max
+#include "lsi_phase1_setup.h" // StepShape, lsi_form_equality_problem (also compiled for the host)
 
 namespace
 {
@@ -13,16 +14,6 @@ namespace
     // =============================================================================================
     // The step of one active-set iteration on the device (lexlsi.h:987-1029 + :1234-1240, objective.h:260-338, :521-589)
     // =============================================================================================
-    constexpr uint32_t STEP_MAX_OBJ = 16;
-    struct StepShape
-    {
-        uint32_t n, nObj, total, SD; // SD = n + 2 total: per instance [x | v | A x]
-        uint32_t dim[STEP_MAX_OBJ], simple[STEP_MAX_OBJ], first[STEP_MAX_OBJ];
-        uint64_t off[STEP_MAX_OBJ]; // first element of the objective's [A | lb | ub] (or [lb | ub]) block inside a problem's data
-        uint64_t per_data;
-        uint32_t dim0;
-        double tol_feasibility;
-    };
     /// working-set block of a stage: per instance `mode` (0: no step, 1: state on the device, 2: state arrives in the staging copy),
     /// per constraint its activation type (0 = inactive) and, for the inactive ones, the position in the objective's inactive list
     struct StepArgs
@@ -498,38 +489,8 @@ namespace
         if (done) return;
 
         // ---- the next equality problem (lexlsi.h:968-982, objective.h:434-494), lane = active constraint ----
-        uint32_t counter = 0;
-        for (uint32_t k = 0; k < sh.nObj; k++)
-        {
-            const uint32_t f = sh.first[k], dim = sh.dim[k], nak = na[k];
-            const double *blk = data + sh.off[k];
-            if (sh.simple[k])
-            {
-                if (lane == 0) a.nfixed[b] = nak;
-                for (uint32_t i = lane; i < nak; i += 64)
-                {
-                    const uint32_t c = act[f + i], t = cs[f + c];
-                    const size_t o   = (size_t)b * n + i;
-                    a.fixed_idx[o]   = var[c];
-                    a.fixed_val[o]   = (t == CTR_ACTIVE_LB) ? blk[c] : blk[c + dim];
-                    a.fixed_type[o]  = (uint8_t)t;
-                }
-            }
-            else
-            {
-                if (lane == 0) a.dims[(size_t)b * a.nObjL + k - a.off] = nak;
-                for (uint32_t i = lane; i < nak; i += 64)
-                {
-                    const uint32_t c = act[f + i], t = cs[f + c];
-                    const size_t o   = (size_t)b * a.cap + counter + i;
-                    a.row_src[o]     = (uint32_t)(sh.off[k] + c);
-                    a.row_ld[o]      = dim | (t == CTR_ACTIVE_LB ? 0u : 0x80000000u);
-                    a.ctr_type[o]    = (uint8_t)t;
-                }
-                counter += nak;
-            }
-        }
-        for (uint32_t r = counter + lane; r < a.cap; r += 64) a.row_ld[(size_t)b * a.cap + r] = 0u;
+        const EqualityProblemSlab slab = {a.dims, a.nfixed, a.fixed_idx, a.fixed_val, a.row_src, a.row_ld, a.fixed_type, a.ctr_type};
+        lsi_form_equality_problem(sh, a.off, a.nObjL, a.cap, b, data, var, na, act, cs, slab, lane, 64u);
     }
 
     /// one instance's wavefront: b = the instance, wib = the wavefront's slice of the dynamic LDS

@@ -218,7 +218,14 @@ struct lexls_lsi_batch_s
                 ws_type[(size_t)b * total + first[o] + a] = cs[first[o] + act[first[o] + a]];
             }
         }
-        keep_fixed(b, data, var_index);
+        if (data)
+            keep_fixed(b, data, var_index);
+        else if (off && ctx.fix_var_host.n) // (a lexls_lsi_batch_run_device run: the scatter kernel read them from the resident data)
+            for (uint32_t a = 0; a < na[0] && a < dims[0]; a++)
+            {
+                ws_fixvar[(size_t)b * dims[0] + a] = ctx.fix_var_host[(size_t)k * dims[0] + a];
+                ws_fixval[(size_t)b * dims[0] + a] = ctx.fix_val_host[(size_t)k * dims[0] + a];
+            }
     }
     /// fixVariable(var, bound) of formLexLSE for the active simple bounds (objective.h:257-271): lb, or ub for CTR_ACTIVE_UB / CTR_ACTIVE_EQ
     void keep_fixed(uint32_t b, const double *data, const uint32_t *var_index)
@@ -388,6 +395,13 @@ struct lexls_lsi_batch_s
         if (par.deactivate_first_wrong_sign && !would_be_resident(par))
         {
             run_one_by_one(r, lam_after == LEXLS_OK);
+            lam_rc  = (off && !h_var_index) ? LEXLS_ERR_INVALID : lam_after;
+            lam_msg = lam_rc == LEXLS_ERR_INVALID ? "lexls_lsi_batch_get_lambda: the run had no variable indices" : lam_why;
+            return;
+        }
+        if (r.sw.device_phase1 && !h_v0 && would_be_resident(par)) // LEXLS_LSI_DEVICE_PHASE1=1: no host objects, phase 1 is device work
+        {
+            run_phase1_on_device(r, NULL);
             lam_rc  = (off && !h_var_index) ? LEXLS_ERR_INVALID : lam_after;
             lam_msg = lam_rc == LEXLS_ERR_INVALID ? "lexls_lsi_batch_get_lambda: the run had no variable indices" : lam_why;
             return;
@@ -658,10 +672,22 @@ struct lexls_lsi_batch_s
                 more     = true;
             }
         }
+        resident_chunks(r, going, more);
+        for (uint32_t g = 0; g < nGroups; g++)
+            if (grp[g]->n_resident)
+            {
+                grp[g]->download_resident(r.sw.stamps_dump);
+                last_kernel = grp[g]->resident_kernel; // (every group takes the same path: same shape, same regularization)
+            }
+    }
+
+    /// stages of the groups in `going` until every one of their instances has stopped
+    void resident_chunks(Run &r, std::vector<char> &going, bool more)
+    {
         // stages are enqueued in chunks; after each chunk ONE word comes back (instances that have stopped).  Stages past an
         // instance's end skip it in every kernel; a chunk that turns out not to be needed costs a few launches of early-exit kernels
         const int chunk = 8;
-        bool freed = false;
+        bool freed = r.lsi.empty(); // (phase 1 on the device: there are no host objects)
         while (more)
         {
             more = false;
@@ -682,12 +708,113 @@ struct lexls_lsi_batch_s
                     more = more || going[g];
                 }
         }
+    }
+
+    /// the arrays of lexls_lsi_batch_run_device: memory of the batch's device
+    struct DeviceArrays
+    {
+        const double *data;
+        const uint32_t *var_index;
+        const uint8_t *active_guess;
+        const double *x0;
+        double *x;
+        int32_t *info6;
+        uint8_t *active;
+        double *v;
+    };
+
+    /// A resident run (would_be_resident) without host LexLSI objects: the constraint data goes into every group's resident copy, the setup kernel
+    /// writes the slabs and the first equality problem where they live, iteration 0 follows the first stage on the device (lsi_phase1_device.h),
+    /// and the run goes on as the resident run it is.  dev == NULL: the arrays of r are host memory (lexls_lsi_batch_run under
+    /// LEXLS_LSI_DEVICE_PHASE1=1) — uploaded, results taken from the downloaded slabs; otherwise everything stays on the device
+    void run_phase1_on_device(Run &r, const DeviceArrays *dev)
+    {
+        r.t_begin = BatchCtx::now();
+        prepare_groups(r);
+        if (!r.resident) throw Exception("lexls_lsi_batch_run: phase 1 on the device needs a resident run");
+        upload_regularization_block(r);
+        const double *data     = dev ? dev->data : r.h_data;
+        const uint32_t *var    = dev ? dev->var_index : r.h_var_index;
+        const uint8_t *guess   = dev ? dev->active_guess : r.h_active_guess;
+        const double *x0       = dev ? dev->x0 : r.h_x0;
+        const uint32_t dim0    = off ? dims[0] : 0u;
+        const int32_t max_fact = static_cast<int32_t>(r.par.max_number_of_factorizations);
+        if (dim0 && !var) throw Exception("lexls_lsi_batch_run: a simple-bounds objective needs variable indices");
         for (uint32_t g = 0; g < nGroups; g++)
-            if (grp[g]->n_resident)
+        {
+            BatchCtx &ctx              = *grp[g];
+            ctx.rshape.tol_feasibility = r.par.tol_feasibility;
+            hip_check(dev ? lexls_internal_set_constraint_data_device(ctx.h, data + (size_t)lo[g] * per_data, per_data) : lexls_lse_set_constraint_data(ctx.h, data + (size_t)lo[g] * per_data, per_data));
+            if (dim0 && hipMemcpyAsync(ctx.d_rvar, var + (size_t)lo[g] * dim0, 4 * (size_t)ctx.B * dim0, dev ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, ctx.stream) != hipSuccess)
+                throw Exception("copy of the variable indices failed");
+            const uint8_t *gg = guess ? guess + (size_t)lo[g] * total : NULL;
+            const double *xg  = x0 ? x0 + (size_t)lo[g] * nVar : NULL;
+            ctx.enqueue_phase1_setup(dev ? xg : ctx.stage_x0(xg), dev ? gg : ctx.stage_guess(gg), lo[g], max_fact);
+        }
+        r.t_ctx = BatchCtx::now() - r.t_begin;
+        uint32_t fault = 0xffffffffu;
+        for (uint32_t g = 0; g < nGroups; g++)
+        {
+            grp[g]->finish_stage();
+            fault = std::min(fault, grp[g]->p1_fault_host[0]);
+        }
+        if (fault != 0xffffffffu) // nothing else is launched for this run
+            throw Exception("lexls_lsi_batch_run: instance " + std::to_string(fault >> 3) + ": " + p1_fault_text(fault & 7u));
+        for (uint32_t g = 0; g < nGroups; g++) grp[g]->enqueue_phase1_stage(x0 != NULL, r.par.tol_wrong_sign_lambda, r.par.tol_correct_sign_lambda, max_fact);
+        r.t_setup = BatchCtx::now() - r.t_begin;
+        std::vector<char> going(nGroups, 0), went(nGroups, 0);
+        bool more = false;
+        for (uint32_t g = 0; g < nGroups; g++)
+        {
+            went[g] = going[g] = grp[g]->resident_done() ? 0 : 1; // (an instance that stopped in iteration 0 never reaches a resident stage)
+            more               = more || going[g];
+        }
+        resident_chunks(r, going, more);
+        const bool keep_fixed_bounds = lam_rc_after(r.par) == LEXLS_OK;
+        for (uint32_t g = 0; g < nGroups; g++)
+        {
+            BatchCtx &ctx = *grp[g];
+            if (dev)
+                ctx.scatter_results(dev->x + (size_t)lo[g] * nVar, dev->info6 ? dev->info6 + (size_t)lo[g] * 6 : NULL, dev->active ? dev->active + (size_t)lo[g] * total : NULL,
+                                    dev->v ? dev->v + (size_t)lo[g] * total : NULL, keep_fixed_bounds);
+            ctx.download_resident(r.sw.stamps_dump, dev == NULL);
+            if (went[g]) last_kernel = ctx.resident_kernel;
+        }
+        if (dev) // the working sets for get_lambda, the relaxations done; x / v / info / active are in the caller's arrays already
+            for (uint32_t b = 0; b < batch; b++)
             {
-                grp[g]->download_resident(r.sw.stamps_dump);
-                last_kernel = grp[g]->resident_kernel; // (every group takes the same path: same shape, same regularization)
+                uint32_t k;
+                BatchCtx &ctx = group_of_instance(b, k);
+                if (ctx.cycling) cycling_count[b] = ctx.rl.cyc(ctx.rws_host.data(), k)[CYC_COUNT];
+                keep_working_set_resident(b, ctx, k, NULL, NULL);
             }
+        else
+        {
+            r.prob.resize(batch);
+            for (uint32_t b = 0; b < batch; b++) r.prob[b] = problem(r, b);
+            collect(r);
+        }
+        report(r);
+    }
+
+    /// what lexls_lsi_batch_get_lambda answers after a run with these parameters (LEXLS_OK: it is served)
+    int lam_rc_after(const ParametersLexLSI &par) const
+    {
+        return (par.cycling_handling_enabled || par.regularization_type != REGULARIZATION_NONE || !gather || total > 65535) ? LEXLS_ERR_UNSUPPORTED : LEXLS_OK;
+    }
+
+    /// lexls_lsi_batch_run_device: the caller has checked would_be_resident(par)
+    void run_device(const DeviceArrays &dev, const double *h_reg_factors, const ParametersLexLSI &par)
+    {
+        lam_rc      = -1;
+        lam_tol     = par.tol_linear_dependence;
+        last_kernel = "host";
+        std::fill(cycling_count.begin(), cycling_count.end(), 0u);
+        Run r{NULL, NULL, NULL, h_reg_factors, NULL, NULL, par, NULL, NULL, NULL, NULL, NULL};
+        run_phase1_on_device(r, &dev);
+        lam_rc  = lam_rc_after(par);
+        lam_msg = par.cycling_handling_enabled ? "lexls_lsi_batch_get_lambda: not available after a run with cycling handling enabled (it may have relaxed bounds in the resident constraint data)"
+                                               : "lexls_lsi_batch_get_lambda: not available after a regularized run";
     }
 
     /// instance b's results into the caller's arrays, and its final working set for get_lambda

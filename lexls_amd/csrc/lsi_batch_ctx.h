@@ -7,6 +7,7 @@
 #include <cstdlib>
 #include "lexls_internal.h"
 #include "lexls_lsi_device.h" // StepShape / StepArgs / lsi_step_kernel, ResidentArgs / lsi_iterate_kernel (shared with the persistent iteration kernel)
+#include "lsi_phase1_device.h" // lsi_phase1_setup_kernel / lsi_phase1_finish_kernel / lsi_result_scatter_kernel
 
 namespace
 {
@@ -33,6 +34,7 @@ namespace
     {
         const bool timing = std::getenv("LEXLS_LSI_TIMING") != nullptr;
         const bool stamps_dump = std::getenv("LEXLS_FUSED_STAMPS_DUMP") != nullptr; // (a -DLEXLS_FUSED_STAMPS build leaves its phase clocks in the multiplier buffer)
+        const bool device_phase1 = std::atoi(CreateSwitches::env("LEXLS_LSI_DEVICE_PHASE1", "0")) != 0; // phase 1 of a resident run as device work (lsi_phase1_device.h)
     };
 
     /// typed window into a pinned block (the per-round arrays of a batch sit in blocks laid out like the handle's device slabs)
@@ -244,6 +246,16 @@ namespace
         bool cycling = false;              // this run handles cycling on the device: handler state in the slab, relaxed bounds in the resident constraint data
         double cycling_relax_step = 0.0;
         uint32_t cycling_max_counter = 0;
+        // ---- phase 1 on the device (lsi_phase1_device.h): no host objects, the slabs are written where they live ----
+        bool phase1_on_device = false;     // this run: the first resident stage finds its problem in the device's in slab
+        uint32_t *d_p1_fault = NULL;       // the setup kernel's error word
+        Pinned<uint32_t> p1_fault_host;
+        uint8_t *d_p1_guess = NULL;        // B x total / B x n: staging of a host caller's guess and x0 (made at the first run that needs them)
+        double *d_p1_x0 = NULL;
+        uint32_t *d_fix_var = NULL;        // B x dim0 each: the active simple bounds of a run whose data never was on the host (lexls_lsi_batch_get_lambda)
+        double *d_fix_val = NULL;
+        Pinned<uint32_t> fix_var_host;
+        Pinned<double> fix_val_host;
         bool fused_all = false, fused_refused = false; // the rest of the resident iterations is one persistent launch / the shape has none
         const char *resident_kernel = "";              // the kernel that served the resident iterations of this run (download_resident)
         int rounds_fs = 0, rounds_sens = 0, rounds_step = 0;
@@ -425,7 +437,7 @@ namespace
             const ResidentArgs ra  = resident_args(max_factorizations);
             for (int i = 0; i < count && !fused_all; i++)
             {
-                if (rounds_resident == 0)
+                if (rounds_resident == 0 && !phase1_on_device)
                     hip_check(lexls_internal_upload_round_trusted(h, in_block.data(), 1)); // the problems the host formed last
                 else
                 {
@@ -478,11 +490,12 @@ namespace
             std::fprintf(stderr, "persistent launch, cycles per iteration [l-QR | step | removal search (per iteration) | finish], iterations, searches: all instances %.0f | %.0f | %.0f | %.0f, %.0f, %.0f; the longest-running one %.0f | %.0f | %.0f | %.0f, %.0f, %.0f\n",
                          sum[0] / sum[4], sum[1] / sum[4], sum[2] / sum[4], sum[3] / sum[4], sum[4], sum[5], most[0] / most[4], most[1] / most[4], most[2] / most[4], most[3] / most[4], most[4], most[5]);
         }
-        void download_resident(bool stamps_dump)
+        /// with_state = false: x and v went from the device slab to device arrays of the caller (scatter_results)
+        void download_resident(bool stamps_dump, bool with_state = true)
         {
             if (hipMemcpyAsync(rws_host.data(), d_rws, rl.bytes_core, hipMemcpyDeviceToHost, stream) != hipSuccess ||
                 (cycling && hipMemcpyAsync(rws_host.data() + rl.o_cyc, d_rws + rl.o_cyc, rl.bytes_cyc, hipMemcpyDeviceToHost, stream) != hipSuccess) || // the relaxations done
-                hipMemcpyAsync(rstate_host.data(), d_rstate, 8 * (size_t)B * rshape.SD, hipMemcpyDeviceToHost, stream) != hipSuccess ||
+                (with_state && hipMemcpyAsync(rstate_host.data(), d_rstate, 8 * (size_t)B * rshape.SD, hipMemcpyDeviceToHost, stream) != hipSuccess) ||
                 hipStreamSynchronize(stream) != hipSuccess)
                 throw Exception("download of the resident state failed");
             resident_kernel = lexls_lse_last_kernel(h); // the persistent launch, or the l-QR kernel of the last stage
@@ -502,6 +515,92 @@ namespace
             }
         }
         uint8_t *mode() { return wl.mode(wset_host.data()); }
+
+        /// Phase 1 as device work, first half: checks, working sets, stamps, counters, the state of a given x0 and the first equality problem, written
+        /// by lsi_phase1_setup_kernel into the resident slabs and the in slab (what runner::setup + LexLSI::begin() + hand_over put there).
+        /// d_x0 / d_guess: device arrays of this group's instances or NULL; first: the group's first instance in the batch.  The constraint data
+        /// and the variable indices are in the handle / d_rvar already (same stream).  The fault word comes back with the next synchronisation
+        void enqueue_phase1_setup(const double *d_x0, const uint8_t *d_guess, uint32_t first, int32_t max_factorizations)
+        {
+            const double t0 = now();
+            if (!d_p1_fault)
+            {
+                if (hipMalloc((void **)&d_p1_fault, 16) != hipSuccess) throw Exception("hipMalloc failed (phase 1 on the device)");
+                p1_fault_host.assign(4, 0xffffffffu);
+            }
+            hip_check(lexls_internal_ensure_gather_buffer(h));
+            phase1_on_device = true;
+            Phase1Args pa;
+            pa.ra = resident_args(max_factorizations);
+            pa.x0 = d_x0, pa.guess = d_guess, pa.fault = d_p1_fault, pa.first = first;
+            if (hipMemsetAsync(d_p1_fault, 0xff, 16, stream) != hipSuccess) throw Exception("hipMemsetAsync failed (phase 1 on the device)");
+            hipLaunchKernelGGL(lsi_phase1_setup_kernel, dim3((B + 3) / 4), dim3(256), 4 * resident_lds_per_wave(rshape.SD, rshape.total), stream, pa);
+            if (hipGetLastError() != hipSuccess || hipMemcpyAsync(p1_fault_host.data(), d_p1_fault, 4, hipMemcpyDeviceToHost, stream) != hipSuccess)
+                throw Exception("lsi_phase1_setup_kernel launch failed");
+            t_enqueue += now() - t0;
+        }
+        /// second half: the stage of every resident iteration on the first problem — row gather + l-QR, the speculative removal search — and
+        /// lsi_phase1_finish_kernel (iteration 0).  Every instance is resident from here on; the count of stopped instances comes back
+        void enqueue_phase1_stage(bool has_x0, double tolW, double tolC, int32_t max_factorizations)
+        {
+            const double t0       = now();
+            const ResidentArgs ra = resident_args(max_factorizations);
+            hip_check(lexls_internal_round_resident(h, rshape.dim0 ? 1 : 0)); // (no resume levels: nothing has been factorized yet)
+            hip_check(lexls_lse_factorize_solve(h, 1));
+            hip_check(first_wrong_sign ? lexls_lse_sensitivity_collect_resident(h, tolW, tolC) : lexls_lse_sensitivity_resident(h, tolW, tolC));
+            hipLaunchKernelGGL(lsi_phase1_finish_kernel, dim3((B + 3) / 4), dim3(256), 4 * resident_lds_per_wave(rshape.SD, rshape.total), stream, ra, has_x0 ? 1u : 0u);
+            if (hipGetLastError() != hipSuccess) throw Exception("lsi_phase1_finish_kernel launch failed");
+            rounds_fs++, rounds_sens++;
+            if (hipMemcpyAsync(fin_host.data(), rl.finished(d_rws), 4, hipMemcpyDeviceToHost, stream) != hipSuccess) throw Exception("hipMemcpyAsync failed (finished count)");
+            std::fill(is_resident.begin(), is_resident.end(), 1);
+            n_resident      = B;
+            rounds_resident = 0;
+            fused_all = fused_refused = false;
+            rounds_fs_at_handover   = rounds_fs;
+            rounds_sens_at_handover = rounds_sens;
+            iterations_at_handover.assign(B, 1); // iteration 0 belongs to phase 1
+            t_enqueue += now() - t0;
+        }
+        /// x / info / active / v of this group's instances from the slabs into device arrays of the caller (d_info6 / d_active / d_v may be NULL);
+        /// with_fixed: the active simple bounds for lexls_lsi_batch_get_lambda as well (fix_var_host / fix_val_host, behind the next synchronisation)
+        void scatter_results(double *d_x, int32_t *d_info6, uint8_t *d_active, double *d_v, bool with_fixed)
+        {
+            with_fixed = with_fixed && rshape.dim0 != 0;
+            if (with_fixed && !d_fix_var)
+            {
+                if (hipMalloc((void **)&d_fix_var, 4 * (size_t)B * rshape.dim0) != hipSuccess || hipMalloc((void **)&d_fix_val, 8 * (size_t)B * rshape.dim0) != hipSuccess)
+                    throw Exception("hipMalloc failed (phase 1 on the device)");
+                fix_var_host.assign((size_t)B * rshape.dim0, 0u);
+                fix_val_host.assign((size_t)B * rshape.dim0, 0.0);
+            }
+            ScatterArgs sa;
+            std::memset(&sa, 0, sizeof(sa));
+            sa.sh = rshape, sa.B = B;
+            sa.state = d_rstate, sa.cdata = lexls_internal_cdata(h), sa.var = d_rvar;
+            sa.ctr_state = rl.ctr_state(d_rws), sa.act = rl.act(d_rws), sa.na = rl.na(d_rws), sa.info = rl.info(d_rws);
+            sa.x = d_x, sa.v = d_v, sa.info6 = d_info6, sa.active = d_active;
+            sa.fix_var = with_fixed ? d_fix_var : NULL, sa.fix_val = with_fixed ? d_fix_val : NULL;
+            hipLaunchKernelGGL(lsi_result_scatter_kernel, dim3((B + 3) / 4), dim3(256), 0, stream, sa);
+            if (hipGetLastError() != hipSuccess) throw Exception("lsi_result_scatter_kernel launch failed");
+            if (with_fixed && (hipMemcpyAsync(fix_var_host.data(), d_fix_var, 4 * (size_t)B * rshape.dim0, hipMemcpyDeviceToHost, stream) != hipSuccess ||
+                               hipMemcpyAsync(fix_val_host.data(), d_fix_val, 8 * (size_t)B * rshape.dim0, hipMemcpyDeviceToHost, stream) != hipSuccess))
+                throw Exception("hipMemcpyAsync failed (active simple bounds)");
+        }
+        /// a host caller's guess / x0 for the setup kernel: staged in device buffers of the group (NULL in, NULL out)
+        const uint8_t *stage_guess(const uint8_t *h_guess)
+        {
+            if (!h_guess) return NULL;
+            if (!d_p1_guess && hipMalloc((void **)&d_p1_guess, (size_t)B * rshape.total) != hipSuccess) throw Exception("hipMalloc failed (phase 1 on the device)");
+            if (hipMemcpyAsync(d_p1_guess, h_guess, (size_t)B * rshape.total, hipMemcpyHostToDevice, stream) != hipSuccess) throw Exception("upload of the active-set guess failed");
+            return d_p1_guess;
+        }
+        const double *stage_x0(const double *h_x0)
+        {
+            if (!h_x0) return NULL;
+            if (!d_p1_x0 && hipMalloc((void **)&d_p1_x0, 8 * (size_t)B * n) != hipSuccess) throw Exception("hipMalloc failed (phase 1 on the device)");
+            if (hipMemcpyAsync(d_p1_x0, h_x0, 8 * (size_t)B * n, hipMemcpyHostToDevice, stream) != hipSuccess) throw Exception("upload of x0 failed");
+            return d_p1_x0;
+        }
 
         /// per-solve state: what a freshly created context holds (a context serves many lexls_lsi_batch_run calls)
         void reset()
@@ -533,6 +632,7 @@ namespace
                 handover.store(false);
             }
             stage_fs = stage_sens = false;
+            phase1_on_device = false;
             if (resident)
             {
                 std::fill(rws_host.begin(), rws_host.begin() + rl.bytes_core, 0); // (the stamps behind: hand_over writes every one a run reads)
@@ -544,7 +644,7 @@ namespace
         ~BatchCtx()
         {
             if (h) lexls_lse_destroy(h);
-            void *dev[] = {d_state, d_state_in, d_res, d_var, d_wset, d_rstate, d_rvar, d_rws};
+            void *dev[] = {d_state, d_state_in, d_res, d_var, d_wset, d_rstate, d_rvar, d_rws, d_p1_fault, d_p1_guess, d_p1_x0, d_fix_var, d_fix_val};
             for (void *q : dev)
                 if (q) (void)hipFree(q);
             if (stream) (void)hipStreamDestroy(stream);

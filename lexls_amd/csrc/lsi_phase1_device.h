@@ -1,0 +1,210 @@
+// Phase 1 of a lock-step LexLSI batch as device work (lsi_batch.h: run_phase1_device): what the host worker pool otherwise does over host LexLSI
+// objects in front of the first resident stage.  With the default modify_* parameters and set_min_init_ctr_violation = true (the C ABI has no
+// slot for others) it is
+//     lsi_phase1_setup_kernel   checks, working set, stamps, counters, [x | v | A x] from x0, the first equality problem
+//     l-QR + removal search     the stage every resident iteration runs (lexls_lse_factorize_solve, lexls_lse_sensitivity_*_resident)
+//     lsi_phase1_finish_kernel  without x0: x = x_lse, A x, v; then iteration 0 = lsi_iterate_body, the resident iteration itself
+// One wavefront per instance, four per workgroup, the LDS of lsi_iterate_kernel.  Included once, by lsi_batch_ctx.h.
+#pragma once
+#include "lexls_lsi_device.h"
+
+namespace
+{
+    struct Phase1Args
+    {
+        ResidentArgs ra;
+        const double *x0;     // B x n, or NULL: the instances start from the solution of their first equality problem
+        const uint8_t *guess; // B x total, or NULL
+        uint32_t *fault;      // one word for the run: min over the faulty instances of (index in the batch) * 8 + P1_* code
+        uint32_t first;       // index in the batch of this group's instance 0
+    };
+
+    /// Objective::initialize_Ax + initialize_v0 (objective.h:162-196, set_min_init_ctr_violation) for the x in x_s (LDS, n doubles), lane =
+    /// constraint: st = [x | v | A x].  A x is apply_A's ordered chain per row (objective.h:435-455).  cs: the activation types (LDS)
+    __device__ __forceinline__ void lsi_phase1_state(const StepShape &sh, const double *data, const uint32_t *var_b, const double *x_s, const uint8_t *cs, double *st)
+    {
+        const uint32_t lane = threadIdx.x & 63u;
+        const uint32_t n = sh.n, total = sh.total;
+        for (uint32_t j = lane; j < n; j += 64) st[j] = x_s[j];
+        for (uint32_t g = lane; g < total; g += 64)
+        {
+            uint32_t k = 0;
+            while (k + 1 < sh.nObj && g >= sh.first[k + 1]) k++;
+            const uint32_t dim = sh.dim[k], c = g - sh.first[k];
+            const double *blk  = data + sh.off[k];
+            double ax, lb, ub;
+            if (sh.simple[k])
+            {
+                ax = x_s[var_b[c]];
+                lb = blk[c];
+                ub = blk[c + dim];
+            }
+            else
+            {
+                ax = 0.0;
+                for (uint32_t j = 0; j < n; j++) ax = lexls::dfma(blk[c + (size_t)j * dim], x_s[j], ax);
+                lb = blk[c + (size_t)n * dim];
+                ub = blk[c + (size_t)(n + 1) * dim];
+            }
+            const uint32_t t = cs[g];
+            double v;
+            if (t == CTR_ACTIVE_LB)
+                v = ax - lb;
+            else if (t == CTR_ACTIVE_UB)
+                v = ax - ub;
+            else if (t != CTR_INACTIVE) // CTR_ACTIVE_EQ keeps the first loop's value (objective.h:164)
+                v = ax - 0.5 * (lb + ub);
+            else if (ax <= lb)
+                v = ax - lb;
+            else if (ax >= ub)
+                v = ax - ub;
+            else
+                v = 0.0;
+            st[n + g]         = v;
+            st[n + total + g] = ax;
+        }
+    }
+
+    __global__ __launch_bounds__(256) void lsi_phase1_setup_kernel(Phase1Args p)
+    {
+        const ResidentArgs &a = p.ra;
+        const uint32_t lane = threadIdx.x & 63u, wib = threadIdx.x >> 6;
+        const uint32_t b    = blockIdx.x * 4 + wib;
+        if (b >= a.B) return;
+        const StepShape &sh  = a.sh;
+        const uint32_t n = sh.n, total = sh.total;
+        const ResidentView v = resident_view(a, b, wib);
+        uint8_t *cls         = reinterpret_cast<uint8_t *>(v.dv_s);  // total bytes of the step's LDS, free here
+        uint32_t *stamp_s    = reinterpret_cast<uint32_t *>(v.adx_s); // total words
+        const uint8_t *guess = p.guess ? p.guess + (size_t)b * total : nullptr;
+
+        // ---- the checks, lane = constraint ----
+        uint32_t fault = 0xffffffffu;
+        for (uint32_t g = lane; g < total; g += 64)
+        {
+            uint32_t k = 0;
+            while (k + 1 < sh.nObj && g >= sh.first[k + 1]) k++;
+            const uint8_t rc = p1_row_class(sh, v.data, k, g - sh.first[k]);
+            cls[g]           = rc;
+            if (rc == P1_ROW_FAULT) fault = min(fault, (uint32_t)P1_LB_ABOVE_UB);
+            if (guess && p1_guess_fault(guess[g]) != P1_OK) fault = min(fault, (uint32_t)P1_GUESS_TYPE);
+        }
+        for (uint32_t c = lane; c < sh.dim0; c += 64)
+        {
+            const uint32_t f = p1_var_fault(sh, v.var, c);
+            if (f != P1_OK) fault = min(fault, f);
+        }
+        const uint32_t worst = (uint32_t)(-lexls::wave_maxi(-(int)min(fault, 0xffffu))); // (wave-uniform)
+        if (worst != 0xffffu) // nothing more for a faulty instance: its variable indices may point anywhere
+        {
+            if (lane == 0) atomicMin(p.fault, (p.first + b) * 8u + worst);
+            return;
+        }
+        __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
+        asm volatile("" ::: "memory");
+
+        // ---- the working set: one lane, in the reference's order ----
+        if (lane == 0)
+        {
+            uint32_t next = 0;
+            p1_build_working_set(sh, cls, guess, v.cs, v.act, v.ina, v.ipos, v.na, stamp_s, &next);
+            a.next_stamp[b] = next;
+            a.alive[b]      = 1;
+            a.skip[b]       = 0;
+            a.objidx[b]     = 0; // the removal search runs behind the factorization (speculative)
+            if (b == 0) *a.finished = 0u;
+        }
+        __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
+        asm volatile("" ::: "memory");
+        for (uint32_t g = lane; g < total; g += 64)
+        {
+            v.g_act[g]  = v.act[g];
+            v.g_ina[g]  = v.ina[g];
+            v.g_ipos[g] = v.ipos[g];
+            v.g_cs[g]   = v.cs[g];
+            if (v.cs[g]) a.stamp[(size_t)b * total + g] = stamp_s[g];
+        }
+        if (lane < STEP_MAX_OBJ) v.g_na[lane] = v.na[lane];
+        if (lane < RESIDENT_INFO_STRIDE) v.info[lane] = lane == 0 ? (int32_t)TERMINATION_STATUS_UNKNOWN : 0; // counters zero, nothing factorized yet
+        if (lane < RESIDENT_CYC_STRIDE) a.cyc[(size_t)b * RESIDENT_CYC_STRIDE + lane] = 0u;                  // the cycling handler has seen no event
+
+        // ---- [x | v | A x] of a given x0 (without one: after the first solve, lsi_phase1_finish_kernel) ----
+        if (p.x0)
+        {
+            for (uint32_t j = lane; j < n; j += 64) v.dx_s[j] = p.x0[(size_t)b * n + j];
+            __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
+            asm volatile("" ::: "memory");
+            lsi_phase1_state(sh, v.data, v.var, v.dx_s, v.cs, v.st);
+        }
+
+        // ---- the first equality problem ----
+        const EqualityProblemSlab slab = {a.dims, a.nfixed, a.fixed_idx, a.fixed_val, a.row_src, a.row_ld, a.fixed_type, a.ctr_type};
+        lsi_form_equality_problem(sh, a.off, a.nObjL, a.cap, b, v.data, v.var, v.na, v.act, v.cs, slab, lane, 64u);
+    }
+
+    /// behind the first factorization and its removal search: iteration 0.  has_x0 == 0: phase 1 takes x = x_lse first (lexlsi.h:350-357), the step
+    /// that follows is then dx = 0.  The rest is the resident iteration: nFactorizations = 1, the blocking test or the removal, iteration_finish
+    /// with its termination tests, the next equality problem
+    __global__ __launch_bounds__(256) void lsi_phase1_finish_kernel(ResidentArgs a, uint32_t has_x0)
+    {
+        const uint32_t lane = threadIdx.x & 63u, wib = threadIdx.x >> 6;
+        const uint32_t b    = blockIdx.x * 4 + wib;
+        if (b >= a.B) return;
+        if (!a.alive[b]) return;
+        if (!has_x0)
+        {
+            const ResidentView v = resident_view(a, b, wib);
+            for (uint32_t j = lane; j < a.sh.n; j += 64) v.dx_s[j] = a.x_lse[(size_t)b * a.sh.n + j];
+            for (uint32_t g = lane; g < a.sh.total; g += 64) v.cs[g] = v.g_cs[g];
+            __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
+            asm volatile("" ::: "memory");
+            lsi_phase1_state(a.sh, v.data, v.var, v.dx_s, v.cs, v.st);
+            __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "workgroup"); // the step reads the state back from memory
+            asm volatile("" ::: "memory");
+        }
+        lsi_iterate_body(a, b, wib);
+    }
+
+    /// where the results of a run go when the caller's arrays are device memory (lexls_lsi_batch_run_device); fix_var / fix_val: what
+    /// lexls_lsi_batch_get_lambda needs of the active simple bounds (variable and bound, working-set order), NULL when it is not offered
+    struct ScatterArgs
+    {
+        StepShape sh;
+        uint32_t B;
+        const double *state, *cdata;
+        const uint32_t *var;
+        const uint8_t *ctr_state;
+        const uint16_t *act, *na;
+        const int32_t *info;
+        double *x, *v;
+        int32_t *info6;
+        uint8_t *active;
+        uint32_t *fix_var;
+        double *fix_val;
+    };
+    __global__ __launch_bounds__(256) void lsi_result_scatter_kernel(ScatterArgs s)
+    {
+        const uint32_t lane = threadIdx.x & 63u;
+        const uint32_t b    = blockIdx.x * 4 + (threadIdx.x >> 6);
+        if (b >= s.B) return;
+        const uint32_t n = s.sh.n, total = s.sh.total;
+        const double *st = s.state + (size_t)b * s.sh.SD;
+        for (uint32_t j = lane; j < n; j += 64) s.x[(size_t)b * n + j] = st[j];
+        if (s.v)
+            for (uint32_t g = lane; g < total; g += 64) s.v[(size_t)b * total + g] = st[n + g];
+        if (s.active)
+            for (uint32_t g = lane; g < total; g += 64) s.active[(size_t)b * total + g] = s.ctr_state[(size_t)b * total + g];
+        if (s.info6 && lane < 6) s.info6[(size_t)b * 6 + lane] = s.info[(size_t)b * RESIDENT_INFO_STRIDE + lane];
+        if (s.fix_var && s.sh.dim0)
+        {
+            const uint32_t d0 = s.sh.dim0, na0 = s.na[(size_t)b * RESIDENT_NA_STRIDE];
+            const double *blk = s.cdata + (size_t)b * s.sh.per_data + s.sh.off[0];
+            for (uint32_t i = lane; i < na0 && i < d0; i += 64)
+            {
+                const uint32_t c = s.act[(size_t)b * total + i], t = s.ctr_state[(size_t)b * total + c];
+                s.fix_var[(size_t)b * d0 + i] = s.var[(size_t)b * d0 + c];
+                s.fix_val[(size_t)b * d0 + i] = t == CTR_ACTIVE_LB ? blk[c] : blk[c + d0];
+            }
+        }
+    }
+} // namespace

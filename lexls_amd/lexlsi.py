@@ -234,7 +234,7 @@ class LsiBatch:
     host worker pool are made once for `batch` problems of one structure; every run() solves new data of that structure."""
 
     def __init__(self, nvar: int, dims, types, batch: int, device: int = 0):
-        self.nvar, self.batch = int(nvar), int(batch)
+        self.nvar, self.batch, self.device = int(nvar), int(batch), int(device)
         self.dims = np.ascontiguousarray(dims, np.uint32)
         self.types = np.ascontiguousarray(types, np.int32)
         self.total = int(self.dims.sum())
@@ -291,6 +291,56 @@ class LsiBatch:
             _p(rounds, C.c_int32)))
         return dict(x=x, info=InfoRows(info), active=active, v=v,
                     rounds=dict(factorize_solve=int(rounds[0]), sensitivity=int(rounds[1])), dims=self.dims)
+
+    def _device_array(self, name, t, dtype, shape, optional=True):
+        """the device address of a caller's tensor (anything with data_ptr(), i.e. torch tensors) after checking what the library takes for granted"""
+        if t is None:
+            if optional:
+                return None
+            raise ValueError(f"run_device: {name} is required")
+        if not hasattr(t, "data_ptr"):
+            raise TypeError(f"run_device: {name} must be a device tensor (something with data_ptr()), not {type(t).__name__}")
+        import torch
+        if t.dtype != dtype:
+            raise TypeError(f"run_device: {name} must be {dtype}, not {t.dtype}")
+        if t.device.type != "cuda" or (t.device.index or 0) != self.device:
+            raise ValueError(f"run_device: {name} is on {t.device}, the batch is on device {self.device}")
+        if not t.is_contiguous():
+            raise ValueError(f"run_device: {name} must be contiguous")
+        if t.numel() != int(np.prod(shape)):
+            raise ValueError(f"run_device: {name} has {t.numel()} elements, {tuple(shape)} expected")
+        return C.c_void_p(t.data_ptr())
+
+    def run_device(self, data, var_index=None, active_guess=None, x0=None, regularization_factors=None, **params):
+        """lexls_lsi_batch_run_device: a run whose problems are on the batch's device already and whose results stay there.  `data`: float64
+        (batch, per-instance data) in the flat layout of PackedBatch.data; `var_index`: int32 (batch, dims[0]), required when objective 0 holds
+        simple bounds; `active_guess`: uint8 (batch, total) or None; `x0`: float64 (batch, nvar) or None — torch tensors (anything with
+        data_ptr()), contiguous.  Returns {"x", "info", "active", "v"} as torch tensors on that device (info: (batch, 6) int32, columns
+        INFO_KEYS).  Only runs that are resident on the device are served; everything else raises (LEXLS_ERR_UNSUPPORTED), nothing is computed
+        on the host instead.  stats(), last_kernel(), lambdas() and cycling_counters() work afterwards as after run()."""
+        import torch
+        batch, total, nvar = self.batch, self.total, self.nvar
+        per_data = int(sum(int(d) * (2 if t == 1 else nvar + 2) for d, t in zip(self.dims, self.types)))
+        simple = int(self.types[0]) == 1
+        d_data = self._device_array("data", data, torch.float64, (batch, per_data), optional=False)
+        d_var = self._device_array("var_index", var_index, torch.int32, (batch, int(self.dims[0])), optional=not simple) if simple else None
+        d_guess = self._device_array("active_guess", active_guess, torch.uint8, (batch, total))
+        d_x0 = self._device_array("x0", x0, torch.float64, (batch, nvar))
+        if regularization_factors is not None or any(k in REG_PARAM_KEYS for k in params):
+            par = pack_params_ex(**params)
+        else:
+            par = pack_params(**params)
+        rfa = None if regularization_factors is None else np.ascontiguousarray(regularization_factors, np.float64)
+        dev = torch.device("cuda", self.device)
+        x = torch.zeros((batch, nvar), dtype=torch.float64, device=dev)
+        info = torch.zeros((batch, 6), dtype=torch.int32, device=dev)
+        active = torch.zeros((batch, total), dtype=torch.uint8, device=dev)
+        v = torch.zeros((batch, total), dtype=torch.float64, device=dev)
+        torch.cuda.synchronize(dev)  # the inputs (and the zeroed outputs) are complete before the library's own streams read and write them
+        capi.check(capi.lib().lexls_lsi_batch_run_device(
+            self._h, d_data, d_var, d_guess, d_x0, _p(rfa, C.c_double), _p(par, C.c_double), C.c_uint32(len(par)),
+            C.c_void_p(x.data_ptr()), C.c_void_p(info.data_ptr()), C.c_void_p(active.data_ptr()), C.c_void_p(v.data_ptr())))
+        return dict(x=x, info=info, active=active, v=v)
 
     def cycling_counters(self) -> np.ndarray:
         """LexLSI::getCyclingCounter() of every instance of the last run (lexls_lsi_batch_get_cycling_counters): (batch,) uint32, the bounds each
