@@ -367,7 +367,7 @@ int lexls_lsi_batch_run(lexls_lsi_batch_t b, const double *h_data, const uint32_
  * memory of the batch's device — d_data (batch x per-instance data), d_var_index (batch x dims[0]; required with a simple-bounds objective 0, else
  * NULL), d_active_guess / d_x0 (may be NULL) in, d_x (required) and d_info6 / d_active / d_v (may be NULL) out.  It stands for these members of
  * lexls_lsi_batch_run: h_data, h_var_index, h_active_guess, h_x0, h_x, h_info6, h_active, h_v; h_v0 and h_rounds2 have no counterpart (initial
- * residuals are not offered here; lexls_lsi_batch_stats has the stage counts).  Parameters and regularization factors stay host arrays.
+ * residuals are taken by lexls_lsi_batch_run_device_ex below; lexls_lsi_batch_stats has the stage counts).  Parameters and regularization factors stay host arrays.
  * The caller has finished writing the inputs before the call; the call returns when the outputs are complete (host-synchronous).  No constraint
  * data, state or result passes through host memory: the data is copied device-to-device into every group's resident copy (the caller's arrays
  * are never written, runs with cycling handling included), phase 1 is device work (below), a scatter kernel writes the results from the resident
@@ -379,6 +379,28 @@ int lexls_lsi_batch_run(lexls_lsi_batch_t b, const double *h_data, const uint32_
  * guess flag above 3 ends the call with LEXLS_ERR_INVALID before anything is solved; lexls_last_error() names the first such instance and the reason. */
 int lexls_lsi_batch_run_device(lexls_lsi_batch_t b, const double *d_data, const uint32_t *d_var_index, const uint8_t *d_active_guess,
                                const double *d_x0, const double *h_reg_factors, const double *h_params, uint32_t nparams, double *d_x, int32_t *d_info6, uint8_t *d_active, double *d_v);
+/* lexls_lsi_batch_run_device with the rest of a warm start and of the results in device memory, for a closed loop on the device: solve, perturb
+ * the data there, solve again from active / x / v of the previous answer.  lexls_lsi_batch_run_device itself is unchanged; with d_v0, d_lambda and
+ * d_cycling_counts all NULL this call IS that one (the old entry point calls this one with the three NULL).  The three may be given in any combination.
+ * d_v0: batch x sum(dims) initial residuals, the layout of h_v0 of lexls_lsi_batch_run — the reference's set_v0 per objective (lexlsi.cpp:571-588).
+ *   Together with d_x0 every objective's v is the given vector as it stands: A x0 is still formed, the guess is activated as given, and neither
+ *   formInitialWorkingSet nor initialize_v0 is run (Objective::phase1, objective.h:226-236) — a branch of the phase-1 setup kernel that reads the
+ *   caller's array where it lies; nothing of v0 passes through host memory and the array is never written.  d_v0 without d_x0 is disregarded, as
+ *   the reference does (lexlsi.h:695-701): the run is the one without v0.  The reference's warning is not printed (warnings are not reproduced on
+ *   this path), and its "partially specified" case cannot arise: one array covers all objectives.
+ * d_lambda: batch x sum(dims) x nObj doubles, the layout of lexls_lsi_batch_get_lambda — the multipliers of THIS run, written by the scatter kernel
+ *   that puts them into the user's order straight into the caller's device array (no host copy).  Same conditions as lexls_lsi_batch_get_lambda:
+ *   for a run after which that call would answer LEXLS_ERR_UNSUPPORTED — cycling handling enabled, regularization_type != 0, more than 65535
+ *   constraints per instance — this call returns LEXLS_ERR_UNSUPPORTED when d_lambda is non-NULL, before any device work, every output left alone
+ *   (the rule of lexls_lsi_batch_run_device: no detour).  A later lexls_lsi_batch_get_lambda on the batch still answers, with the same bits.
+ * d_cycling_counts: `batch` uint32, what lexls_lsi_batch_get_cycling_counters returns, written by the result scatter kernel; zeros after a run
+ *   without cycling handling.
+ * Otherwise as lexls_lsi_batch_run_device: host-synchronous, LEXLS_ERR_UNSUPPORTED for every run that is not resident, LEXLS_ERR_INVALID for input
+ * faults.  lexls_lsi_batch_run keeps its behaviour: LEXLS_LSI_DEVICE_PHASE1=1 still changes nothing when h_v0 is given. */
+int lexls_lsi_batch_run_device_ex(lexls_lsi_batch_t b, const double *d_data, const uint32_t *d_var_index, const uint8_t *d_active_guess,
+                                  const double *d_x0, const double *d_v0, const double *h_reg_factors, const double *h_params, uint32_t nparams,
+                                  double *d_x, int32_t *d_info6, uint8_t *d_active, double *d_v,
+                                  double *d_lambda, uint32_t *d_cycling_counts);
 /* How a run executes: phase 1 of every instance on the host; from then on the instance's active-set iterations are resident on the
  * device (LEXLS_LSI_RESIDENT=0: host logic, lock-step stages).  Where the batch's shape has a persistent instantiation (the register-resident l-QR shapes:
  * nVar + 1 <= 41 with levels of up to 12 rows, nVar + 1 <= 64 with levels of up to 16 — except 42..48 columns), everything behind the first resident

@@ -30,7 +30,7 @@ SYMBOLS = [
     "lexls_lsi_solve", "lexls_lsi_solve_dat", "lexls_lsi_batch_solve",
     "lexls_lse_multipliers", "lexls_lse_get_multipliers", "lexls_lsi_batch_get_lambda", "lexls_lsi_batch_solve_ex2",
     "lexls_lse_sensitivity_collect", "lexls_lse_sensitivity_collect_resident", "lexls_lse_get_wrong_sign",
-    "lexls_lsi_batch_get_cycling_counters", "lexls_lsi_batch_run_device",
+    "lexls_lsi_batch_get_cycling_counters", "lexls_lsi_batch_run_device", "lexls_lsi_batch_run_device_ex",
     "lexls_lsi_batch_last_kernel",
 ]
 
@@ -72,6 +72,9 @@ def lib() -> C.CDLL:
         _lib.lexls_lsi_batch_run_device.restype = C.c_int
         _lib.lexls_lsi_batch_run_device.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_double), C.POINTER(C.c_double),
                                                     C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]  # the d_* arrays: device addresses
+        _lib.lexls_lsi_batch_run_device_ex.restype = C.c_int
+        _lib.lexls_lsi_batch_run_device_ex.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_double), C.POINTER(C.c_double),
+                                                       C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]  # + d_v0; d_lambda, d_cycling_counts
     return _lib
 
 

@@ -99,6 +99,13 @@ extern "C"
     int lexls_lsi_batch_run_device(lexls_lsi_batch_t b, const double *d_data, const uint32_t *d_var_index, const uint8_t *d_active_guess, const double *d_x0,
                                    const double *h_reg_factors, const double *h_params, uint32_t nparams, double *d_x, int32_t *d_info6, uint8_t *d_active, double *d_v)
     {
+        return lexls_lsi_batch_run_device_ex(b, d_data, d_var_index, d_active_guess, d_x0, NULL, h_reg_factors, h_params, nparams, d_x, d_info6, d_active, d_v, NULL, NULL);
+    }
+
+    int lexls_lsi_batch_run_device_ex(lexls_lsi_batch_t b, const double *d_data, const uint32_t *d_var_index, const uint8_t *d_active_guess, const double *d_x0,
+                                      const double *d_v0, const double *h_reg_factors, const double *h_params, uint32_t nparams, double *d_x, int32_t *d_info6,
+                                      uint8_t *d_active, double *d_v, double *d_lambda, uint32_t *d_cycling_counts)
+    {
         return guarded([&]() {
             if (!b) throw Exception("lexls_lsi_batch_run_device: null handle");
             if (h_params && nparams != 9 && nparams != 12) throw Exception("lexls_lsi_batch_run_device: 9 or 12 parameters expected");
@@ -111,8 +118,17 @@ extern "C"
                                          "regularization type 7, cycling handling of a regularized run, shapes without a register-resident kernel)");
                 return static_cast<int>(LEXLS_ERR_UNSUPPORTED);
             }
-            b->run_device({d_data, d_var_index, d_active_guess, d_x0, d_x, d_info6, d_active, d_v}, h_reg_factors, par);
-            return static_cast<int>(LEXLS_OK);
+            if (d_lambda && b->lam_rc_after(par) != LEXLS_OK) // what lexls_lsi_batch_get_lambda would answer after this run: refused now, before any device work
+            {
+                lexls_internal_set_error("lexls_lsi_batch_run_device_ex: d_lambda is not served for a run with cycling handling enabled, a regularized run or more than 65535 "
+                                         "constraints (lexls_lsi_batch_get_lambda is not available after such a run)");
+                return static_cast<int>(LEXLS_ERR_UNSUPPORTED);
+            }
+            lexls_lsi_batch_s::DeviceArrays dev{d_data, d_var_index, d_active_guess, d_x0, d_x, d_info6, d_active, d_v};
+            dev.v0 = d_x0 ? d_v0 : NULL; // v0 without x0 is disregarded (lexlsi.h:695-701)
+            dev.cycling_counts = d_cycling_counts;
+            b->run_device(dev, h_reg_factors, par);
+            return d_lambda ? b->get_lambda(NULL, d_lambda) : static_cast<int>(LEXLS_OK);
         });
     }
 

@@ -282,8 +282,9 @@ struct lexls_lsi_batch_s
 
     /// LexLSI::getLambda (lexlsi.h:552-605) for every instance of the last run, on the device in each group's stream: the final equality
     /// problems are formed (rows gathered by reference, fixed variables posted), factorized with the factor kept on a bit-exact kernel, all
-    /// objectives' multipliers taken in one sweep (lexls_lse_multipliers), scattered into the user's order, one copy back per group
-    int get_lambda(double *h_lambda)
+    /// objectives' multipliers taken in one sweep (lexls_lse_multipliers), scattered into the user's order, one copy back per group.
+    /// d_lambda (lexls_lsi_batch_run_device_ex): memory of the batch's device instead — the scatter kernel writes there, nothing is copied back
+    int get_lambda(double *h_lambda, double *d_lambda = NULL)
     {
         if (lam_rc < 0) throw Exception("lexls_lsi_batch_get_lambda: no completed lexls_lsi_batch_run on this batch");
         if (lam_rc != LEXLS_OK)
@@ -291,7 +292,7 @@ struct lexls_lsi_batch_s
             lexls_internal_set_error(lam_msg.c_str());
             return lam_rc;
         }
-        if (!h_lambda) throw Exception("lexls_lsi_batch_get_lambda: null output");
+        if (!h_lambda && !d_lambda) throw Exception("lexls_lsi_batch_get_lambda: null output");
         const uint32_t nObjL = nObj - off;
         if (lam_bufs.empty())
         {
@@ -341,9 +342,9 @@ struct lexls_lsi_batch_s
             if (hipMemcpyAsync(lb.d_map, lb.map.data(), 4 * ((size_t)ctx.B + (size_t)ctx.B * total), hipMemcpyHostToDevice, ctx.stream) != hipSuccess)
                 throw Exception("hipMemcpyAsync failed (lexls_lsi_batch_get_lambda)");
             hipLaunchKernelGGL(lsi_lambda_scatter_kernel, dim3(ctx.B), dim3(64), 0, ctx.stream, d_mult, lb.d_map, ctx.B, (uint32_t)total, nObj, nObjL, off,
-                               nVar + ctx.cap, lb.d_out);
+                               nVar + ctx.cap, d_lambda ? d_lambda + (size_t)lo[g] * total * nObj : lb.d_out);
             if (hipGetLastError() != hipSuccess) throw Exception("lsi_lambda_scatter_kernel launch failed");
-            if (hipMemcpyAsync(h_lambda + (size_t)lo[g] * total * nObj, lb.d_out, 8 * (size_t)ctx.B * total * nObj, hipMemcpyDeviceToHost, ctx.stream) != hipSuccess)
+            if (!d_lambda && hipMemcpyAsync(h_lambda + (size_t)lo[g] * total * nObj, lb.d_out, 8 * (size_t)ctx.B * total * nObj, hipMemcpyDeviceToHost, ctx.stream) != hipSuccess)
                 throw Exception("hipMemcpyAsync failed (lexls_lsi_batch_get_lambda)");
             stage(3, ctx);
         }
@@ -721,6 +722,8 @@ struct lexls_lsi_batch_s
         int32_t *info6;
         uint8_t *active;
         double *v;
+        const double *v0 = NULL;        // lexls_lsi_batch_run_device_ex: initial residuals (used with x0 only)
+        uint32_t *cycling_counts = NULL; // ... and where the scatter kernel leaves the cycling handlers' relaxation counts
     };
 
     /// A resident run (would_be_resident) without host LexLSI objects: the constraint data goes into every group's resident copy, the setup kernel
@@ -737,6 +740,7 @@ struct lexls_lsi_batch_s
         const uint32_t *var    = dev ? dev->var_index : r.h_var_index;
         const uint8_t *guess   = dev ? dev->active_guess : r.h_active_guess;
         const double *x0       = dev ? dev->x0 : r.h_x0;
+        const double *v0       = dev ? dev->v0 : NULL; // (only lexls_lsi_batch_run_device_ex gives one, and only together with x0)
         const uint32_t dim0    = off ? dims[0] : 0u;
         const int32_t max_fact = static_cast<int32_t>(r.par.max_number_of_factorizations);
         if (dim0 && !var) throw Exception("lexls_lsi_batch_run: a simple-bounds objective needs variable indices");
@@ -749,7 +753,7 @@ struct lexls_lsi_batch_s
                 throw Exception("copy of the variable indices failed");
             const uint8_t *gg = guess ? guess + (size_t)lo[g] * total : NULL;
             const double *xg  = x0 ? x0 + (size_t)lo[g] * nVar : NULL;
-            ctx.enqueue_phase1_setup(dev ? xg : ctx.stage_x0(xg), dev ? gg : ctx.stage_guess(gg), lo[g], max_fact);
+            ctx.enqueue_phase1_setup(dev ? xg : ctx.stage_x0(xg), dev ? gg : ctx.stage_guess(gg), lo[g], max_fact, v0 ? v0 + (size_t)lo[g] * total : NULL);
         }
         r.t_ctx = BatchCtx::now() - r.t_begin;
         uint32_t fault = 0xffffffffu;
@@ -776,7 +780,7 @@ struct lexls_lsi_batch_s
             BatchCtx &ctx = *grp[g];
             if (dev)
                 ctx.scatter_results(dev->x + (size_t)lo[g] * nVar, dev->info6 ? dev->info6 + (size_t)lo[g] * 6 : NULL, dev->active ? dev->active + (size_t)lo[g] * total : NULL,
-                                    dev->v ? dev->v + (size_t)lo[g] * total : NULL, keep_fixed_bounds);
+                                    dev->v ? dev->v + (size_t)lo[g] * total : NULL, keep_fixed_bounds, dev->cycling_counts ? dev->cycling_counts + lo[g] : NULL);
             ctx.download_resident(r.sw.stamps_dump, dev == NULL);
             if (went[g]) last_kernel = ctx.resident_kernel;
         }
@@ -803,7 +807,7 @@ struct lexls_lsi_batch_s
         return (par.cycling_handling_enabled || par.regularization_type != REGULARIZATION_NONE || !gather || total > 65535) ? LEXLS_ERR_UNSUPPORTED : LEXLS_OK;
     }
 
-    /// lexls_lsi_batch_run_device: the caller has checked would_be_resident(par)
+    /// lexls_lsi_batch_run_device(_ex): the caller has checked would_be_resident(par)
     void run_device(const DeviceArrays &dev, const double *h_reg_factors, const ParametersLexLSI &par)
     {
         lam_rc      = -1;

@@ -518,9 +518,10 @@ namespace
 
         /// Phase 1 as device work, first half: checks, working sets, stamps, counters, the state of a given x0 and the first equality problem, written
         /// by lsi_phase1_setup_kernel into the resident slabs and the in slab (what runner::setup + LexLSI::begin() + hand_over put there).
-        /// d_x0 / d_guess: device arrays of this group's instances or NULL; first: the group's first instance in the batch.  The constraint data
+        /// d_x0 / d_guess / d_v0: device arrays of this group's instances or NULL (d_v0, the caller's initial residuals, is read where it lies and
+        /// only together with d_x0); first: the group's first instance in the batch.  The constraint data
         /// and the variable indices are in the handle / d_rvar already (same stream).  The fault word comes back with the next synchronisation
-        void enqueue_phase1_setup(const double *d_x0, const uint8_t *d_guess, uint32_t first, int32_t max_factorizations)
+        void enqueue_phase1_setup(const double *d_x0, const uint8_t *d_guess, uint32_t first, int32_t max_factorizations, const double *d_v0 = NULL)
         {
             const double t0 = now();
             if (!d_p1_fault)
@@ -532,7 +533,7 @@ namespace
             phase1_on_device = true;
             Phase1Args pa;
             pa.ra = resident_args(max_factorizations);
-            pa.x0 = d_x0, pa.guess = d_guess, pa.fault = d_p1_fault, pa.first = first;
+            pa.x0 = d_x0, pa.guess = d_guess, pa.v0 = d_v0, pa.fault = d_p1_fault, pa.first = first;
             if (hipMemsetAsync(d_p1_fault, 0xff, 16, stream) != hipSuccess) throw Exception("hipMemsetAsync failed (phase 1 on the device)");
             hipLaunchKernelGGL(lsi_phase1_setup_kernel, dim3((B + 3) / 4), dim3(256), 4 * resident_lds_per_wave(rshape.SD, rshape.total), stream, pa);
             if (hipGetLastError() != hipSuccess || hipMemcpyAsync(p1_fault_host.data(), d_p1_fault, 4, hipMemcpyDeviceToHost, stream) != hipSuccess)
@@ -562,8 +563,9 @@ namespace
             t_enqueue += now() - t0;
         }
         /// x / info / active / v of this group's instances from the slabs into device arrays of the caller (d_info6 / d_active / d_v may be NULL);
-        /// with_fixed: the active simple bounds for lexls_lsi_batch_get_lambda as well (fix_var_host / fix_val_host, behind the next synchronisation)
-        void scatter_results(double *d_x, int32_t *d_info6, uint8_t *d_active, double *d_v, bool with_fixed)
+        /// with_fixed: the active simple bounds for lexls_lsi_batch_get_lambda as well (fix_var_host / fix_val_host, behind the next synchronisation);
+        /// d_cyc_count (B words or NULL): the relaxations of every instance's cycling handler, zeros for a run without cycling handling
+        void scatter_results(double *d_x, int32_t *d_info6, uint8_t *d_active, double *d_v, bool with_fixed, uint32_t *d_cyc_count = NULL)
         {
             with_fixed = with_fixed && rshape.dim0 != 0;
             if (with_fixed && !d_fix_var)
@@ -580,6 +582,7 @@ namespace
             sa.ctr_state = rl.ctr_state(d_rws), sa.act = rl.act(d_rws), sa.na = rl.na(d_rws), sa.info = rl.info(d_rws);
             sa.x = d_x, sa.v = d_v, sa.info6 = d_info6, sa.active = d_active;
             sa.fix_var = with_fixed ? d_fix_var : NULL, sa.fix_val = with_fixed ? d_fix_val : NULL;
+            sa.cyc = cycling ? rl.cyc(d_rws) : NULL, sa.cyc_count = d_cyc_count;
             hipLaunchKernelGGL(lsi_result_scatter_kernel, dim3((B + 3) / 4), dim3(256), 0, stream, sa);
             if (hipGetLastError() != hipSuccess) throw Exception("lsi_result_scatter_kernel launch failed");
             if (with_fixed && (hipMemcpyAsync(fix_var_host.data(), d_fix_var, 4 * (size_t)B * rshape.dim0, hipMemcpyDeviceToHost, stream) != hipSuccess ||

@@ -15,13 +15,16 @@ namespace
         ResidentArgs ra;
         const double *x0;     // B x n, or NULL: the instances start from the solution of their first equality problem
         const uint8_t *guess; // B x total, or NULL
+        const double *v0;     // B x total, or NULL: with x0 the instances' v is this array as it stands (set_v0, objective.h:226-236); read only with x0
         uint32_t *fault;      // one word for the run: min over the faulty instances of (index in the batch) * 8 + P1_* code
         uint32_t first;       // index in the batch of this group's instance 0
     };
 
     /// Objective::initialize_Ax + initialize_v0 (objective.h:162-196, set_min_init_ctr_violation) for the x in x_s (LDS, n doubles), lane =
-    /// constraint: st = [x | v | A x].  A x is apply_A's ordered chain per row (objective.h:435-455).  cs: the activation types (LDS)
-    __device__ __forceinline__ void lsi_phase1_state(const StepShape &sh, const double *data, const uint32_t *var_b, const double *x_s, const uint8_t *cs, double *st)
+    /// constraint: st = [x | v | A x].  A x is apply_A's ordered chain per row (objective.h:435-455).  cs: the activation types (LDS).
+    /// v0 (the instance's total doubles, or NULL): Objective::phase1 with v0_is_specified — A x is formed, initialize_v0 is not run, v is v0
+    __device__ __forceinline__ void lsi_phase1_state(const StepShape &sh, const double *data, const uint32_t *var_b, const double *x_s, const uint8_t *cs, double *st,
+                                                     const double *v0 = nullptr)
     {
         const uint32_t lane = threadIdx.x & 63u;
         const uint32_t n = sh.n, total = sh.total;
@@ -48,7 +51,9 @@ namespace
             }
             const uint32_t t = cs[g];
             double v;
-            if (t == CTR_ACTIVE_LB)
+            if (v0)
+                v = v0[g];
+            else if (t == CTR_ACTIVE_LB)
                 v = ax - lb;
             else if (t == CTR_ACTIVE_UB)
                 v = ax - ub;
@@ -134,7 +139,7 @@ namespace
             for (uint32_t j = lane; j < n; j += 64) v.dx_s[j] = p.x0[(size_t)b * n + j];
             __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
             asm volatile("" ::: "memory");
-            lsi_phase1_state(sh, v.data, v.var, v.dx_s, v.cs, v.st);
+            lsi_phase1_state(sh, v.data, v.var, v.dx_s, v.cs, v.st, p.v0 ? p.v0 + (size_t)b * total : nullptr);
         }
 
         // ---- the first equality problem ----
@@ -166,7 +171,9 @@ namespace
     }
 
     /// where the results of a run go when the caller's arrays are device memory (lexls_lsi_batch_run_device); fix_var / fix_val: what
-    /// lexls_lsi_batch_get_lambda needs of the active simple bounds (variable and bound, working-set order), NULL when it is not offered
+    /// lexls_lsi_batch_get_lambda needs of the active simple bounds (variable and bound, working-set order), NULL when it is not offered;
+    /// cyc_count (B words, or NULL): the relaxations every instance's cycling handler did, from cyc (the handlers' slab; NULL: a run without
+    /// cycling handling, zeros)
     struct ScatterArgs
     {
         StepShape sh;
@@ -181,6 +188,8 @@ namespace
         uint8_t *active;
         uint32_t *fix_var;
         double *fix_val;
+        const uint32_t *cyc;
+        uint32_t *cyc_count;
     };
     __global__ __launch_bounds__(256) void lsi_result_scatter_kernel(ScatterArgs s)
     {
@@ -195,6 +204,7 @@ namespace
         if (s.active)
             for (uint32_t g = lane; g < total; g += 64) s.active[(size_t)b * total + g] = s.ctr_state[(size_t)b * total + g];
         if (s.info6 && lane < 6) s.info6[(size_t)b * 6 + lane] = s.info[(size_t)b * RESIDENT_INFO_STRIDE + lane];
+        if (s.cyc_count && lane == 0) s.cyc_count[b] = s.cyc ? s.cyc[(size_t)b * RESIDENT_CYC_STRIDE + CYC_COUNT] : 0u;
         if (s.fix_var && s.sh.dim0)
         {
             const uint32_t d0 = s.sh.dim0, na0 = s.na[(size_t)b * RESIDENT_NA_STRIDE];

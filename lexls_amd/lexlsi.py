@@ -311,13 +311,20 @@ class LsiBatch:
             raise ValueError(f"run_device: {name} has {t.numel()} elements, {tuple(shape)} expected")
         return C.c_void_p(t.data_ptr())
 
-    def run_device(self, data, var_index=None, active_guess=None, x0=None, regularization_factors=None, **params):
+    def run_device(self, data, var_index=None, active_guess=None, x0=None, regularization_factors=None, v0=None, with_lambda=False,
+                   with_cycling_counters=False, **params):
         """lexls_lsi_batch_run_device: a run whose problems are on the batch's device already and whose results stay there.  `data`: float64
         (batch, per-instance data) in the flat layout of PackedBatch.data; `var_index`: int32 (batch, dims[0]), required when objective 0 holds
         simple bounds; `active_guess`: uint8 (batch, total) or None; `x0`: float64 (batch, nvar) or None — torch tensors (anything with
         data_ptr()), contiguous.  Returns {"x", "info", "active", "v"} as torch tensors on that device (info: (batch, 6) int32, columns
         INFO_KEYS).  Only runs that are resident on the device are served; everything else raises (LEXLS_ERR_UNSUPPORTED), nothing is computed
-        on the host instead.  stats(), last_kernel(), lambdas() and cycling_counters() work afterwards as after run()."""
+        on the host instead.  stats(), last_kernel(), lambdas() and cycling_counters() work afterwards as after run().
+
+        The rest of a warm start and of the results on the device (lexls_lsi_batch_run_device_ex; without these keywords the call above is made):
+        `v0`: float64 (batch, total) initial residuals, taken as they stand together with x0 and disregarded without it (the reference's set_v0);
+        `with_lambda`: the result also has "lambda", (batch, nObj, total) float64, the layout of lambda_array() — raises (LEXLS_ERR_UNSUPPORTED,
+        nothing computed) for a run with cycling handling or regularization; `with_cycling_counters`: the result also has "cycling_counters",
+        (batch,) int32 holding the uint32 bits of cycling_counters()."""
         import torch
         batch, total, nvar = self.batch, self.total, self.nvar
         per_data = int(sum(int(d) * (2 if t == 1 else nvar + 2) for d, t in zip(self.dims, self.types)))
@@ -326,6 +333,7 @@ class LsiBatch:
         d_var = self._device_array("var_index", var_index, torch.int32, (batch, int(self.dims[0])), optional=not simple) if simple else None
         d_guess = self._device_array("active_guess", active_guess, torch.uint8, (batch, total))
         d_x0 = self._device_array("x0", x0, torch.float64, (batch, nvar))
+        d_v0 = self._device_array("v0", v0, torch.float64, (batch, total))
         if regularization_factors is not None or any(k in REG_PARAM_KEYS for k in params):
             par = pack_params_ex(**params)
         else:
@@ -336,11 +344,22 @@ class LsiBatch:
         info = torch.zeros((batch, 6), dtype=torch.int32, device=dev)
         active = torch.zeros((batch, total), dtype=torch.uint8, device=dev)
         v = torch.zeros((batch, total), dtype=torch.float64, device=dev)
+        r = dict(x=x, info=info, active=active, v=v)
+        if with_lambda:
+            r["lambda"] = torch.zeros((batch, len(self.dims), total), dtype=torch.float64, device=dev)
+        if with_cycling_counters:
+            r["cycling_counters"] = torch.zeros((batch,), dtype=torch.int32, device=dev)
         torch.cuda.synchronize(dev)  # the inputs (and the zeroed outputs) are complete before the library's own streams read and write them
-        capi.check(capi.lib().lexls_lsi_batch_run_device(
-            self._h, d_data, d_var, d_guess, d_x0, _p(rfa, C.c_double), _p(par, C.c_double), C.c_uint32(len(par)),
-            C.c_void_p(x.data_ptr()), C.c_void_p(info.data_ptr()), C.c_void_p(active.data_ptr()), C.c_void_p(v.data_ptr())))
-        return dict(x=x, info=info, active=active, v=v)
+        out = [C.c_void_p(x.data_ptr()), C.c_void_p(info.data_ptr()), C.c_void_p(active.data_ptr()), C.c_void_p(v.data_ptr())]
+        if v0 is None and not with_lambda and not with_cycling_counters:
+            capi.check(capi.lib().lexls_lsi_batch_run_device(
+                self._h, d_data, d_var, d_guess, d_x0, _p(rfa, C.c_double), _p(par, C.c_double), C.c_uint32(len(par)), *out))
+        else:
+            capi.check(capi.lib().lexls_lsi_batch_run_device_ex(
+                self._h, d_data, d_var, d_guess, d_x0, d_v0, _p(rfa, C.c_double), _p(par, C.c_double), C.c_uint32(len(par)), *out,
+                C.c_void_p(r["lambda"].data_ptr()) if with_lambda else None,
+                C.c_void_p(r["cycling_counters"].data_ptr()) if with_cycling_counters else None))
+        return r
 
     def cycling_counters(self) -> np.ndarray:
         """LexLSI::getCyclingCounter() of every instance of the last run (lexls_lsi_batch_get_cycling_counters): (batch,) uint32, the bounds each
