@@ -177,7 +177,10 @@ int lexls_lse_sensitivity_resident(lexls_lse_t h, double tol_wrong_sign_lambda, 
  * fixVariable order, bytes [nVar, nVar + cap) the constraint rows in LOD order; 1 where the reference pushes a ConstraintInfo, 0 elsewhere.
  * Scan order: the objective's own level, the levels above it downwards, the fixed variables.  The reference's quirk for the fixed variables is
  * kept (lexlse.h:599-600): min(dims[0], nfixed) entries are scanned, entry k reads the CONSTRAINT multiplier Lambda[k] against fixed type k, and
- * sets byte k.  Arguments as lexls_lse_sensitivity; with lexls_lse_set_sensitivity_scan on it goes on to the next objective until one reports a
+ * sets byte k.  CONSEQUENCE, known and kept for fidelity to the reference: the true multipliers of the fixed variables are never examined by
+ * this rule, so a LexLSI run with deactivate_first_wrong_sign on a hierarchy with simple bounds can end with PROBLEM_SOLVED at a point that is
+ * not lexicographically optimal — a simple bound keeps a multiplier of the wrong sign (smallest case found: n = 3, dims (2, 2, 3),
+ * tests/test_lexopt_certificate.py; the default rule, lexls_lse_sensitivity, is not affected).  Arguments as lexls_lse_sensitivity; with lexls_lse_set_sensitivity_scan on it goes on to the next objective until one reports a
  * non-empty set or the last is done (the loop of lexlsi.h:1072-1083; marks of the objectives passed stay in place).
  * lexls_lse_get_sensitivity then gives {set non-empty, number of entries, objective the search stopped at} and max_abs = 0 (the reference sets
  * lambda_wrong_sign = 0 on this path); {0, -1, -2} for a problem whose objective index is negative.  _resident: objective indices from the
