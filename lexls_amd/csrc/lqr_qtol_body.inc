@@ -191,6 +191,7 @@
 
             for (int k = 0; k < nObj; k++)
             {
+                QT_MARK("level-top")
                 const bool work = live && !exh; // x only: once the columns are exhausted nothing below matters
                 const int F     = RAG ? Frow : k * MD;                       // first row of the level
                 const int dlev  = RAG ? (int)((dpack >> (4 * k)) & 15u) : MD; // its rows (RAG: per problem)
@@ -214,6 +215,7 @@
                 // =====================================================================================
                 // position layout of the level; staged pieces -> block
                 // =====================================================================================
+                QT_MARK("level-start")
 #pragma unroll
                 for (int s = 0; s < NS; s++)
                 {
@@ -227,6 +229,7 @@
                 if (k > 0)
                 for_each_index<0, NH>([&](auto hh) __attribute__((always_inline)) {
                     constexpr int h = decltype(hh)::value;
+                    QT_MARK1("level-stage", h)
                     // the pieces come out of their fixed registers (requested during the level in front, or just now)
                     if constexpr (h == 0) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
                     for_each_index<0, NIH>([&](auto ii) __attribute__((always_inline)) {
@@ -259,6 +262,7 @@
                 });
                 STAMP(1)
                 LSTAMP(0)
+                QT_MARK("level-post")
                 if constexpr (EST)
                 {
 #pragma unroll
@@ -304,29 +308,49 @@
                             constexpr int sc = (C + SIG) / 16, lc = (C + SIG) % 16;
                             double(&ucur)[NS]  = (C & 1) ? ub : ua;
                             double(&unext)[NS] = (C & 1) ? ua : ub;
+                            QT_MARK1("elim", C)
                             // a row of the wavefront whose own pivots end before Fcmax meets the zeros of the x block as "U'": every fma adds a zero product
-                            double lr[MD];
-                            for_each_index<0, MD>([&](auto rr) {
-                                constexpr int r = decltype(rr)::value;
-                                lr[r]           = gbc<lc>(blk[sc][r]);
-                            });
-#pragma unroll
-                            for (int r = 0; r < MD; r++) blk[sc][r] = dfma(-lr[r], ucur[sc], blk[sc][r]);
-                            // (the next step's U' behind the first slot's work: its address chain does not stall the step's start)
-                            if constexpr (C + 1 < 16 * NS - SIG)
+                            if constexpr (NS - sc <= 2)
                             {
-                                if (C + 1 < Fcmax) fetch_u(std::integral_constant<int, C + 1>{}, unext);
+                                // one or two slots left: the broadcast of l rides in the fma (qt_gauss_dpp: MD instructions per slot, no moves).  The
+                                // slot behind first — it reads the l of the pivot's slot, whose own update (last) turns lane lc into zero
+                                if constexpr (sc + 1 < NS) qt_gauss_dpp<lc>(blk[sc + 1], blk[sc], ucur[sc + 1]);
+                                if constexpr (C + 1 < 16 * NS - SIG)
+                                {
+                                    if (C + 1 < Fcmax) fetch_u(std::integral_constant<int, C + 1>{}, unext);
+                                }
+                                qt_gauss_dpp_self<lc>(blk[sc], ucur[sc]);
                             }
-#pragma unroll
-                            for (int s = sc + 1; s < NS; s++)
+                            else
                             {
+                                double lr[MD];
+                                for_each_index<0, MD>([&](auto rr) {
+                                    constexpr int r = decltype(rr)::value;
+                                    lr[r]           = gbc<lc>(blk[sc][r]);
+                                });
 #pragma unroll
-                                for (int r = 0; r < MD; r++) blk[s][r] = dfma(-lr[r], ucur[s], blk[s][r]);
+                                for (int r = 0; r < MD; r++) blk[sc][r] = dfma(-lr[r], ucur[sc], blk[sc][r]);
+                                // (the next step's U' behind the first slot's work: its address chain does not stall the step's start)
+                                if constexpr (C + 1 < 16 * NS - SIG)
+                                {
+                                    if (C + 1 < Fcmax) fetch_u(std::integral_constant<int, C + 1>{}, unext);
+                                }
+#pragma unroll
+                                for (int s = sc + 1; s < NS; s++)
+                                {
+#pragma unroll
+                                    for (int r = 0; r < MD; r++) blk[s][r] = dfma(-lr[r], ucur[s], blk[s][r]);
+                                }
                             }
                         });
+                    // (what follows may read the block through DPP: the wait states behind the last block's writes, which the compiler does not count.
+                    //  Here, once per level, and not at the end of qt_gauss_dpp_self, where it would be paid in every step: between the steps the
+                    //  next block's own leading s_nop serves.  A level without a folded step pays two idle cycles)
+                    asm volatile("s_nop 1");
                 }
                 STAMP(7)
                 LSTAMP(1)
+                QT_MARK("hh-select")
 
                 // =====================================================================================
                 // Householder QR with column pivoting of the level (lexlse.h:182-268), slots S0 .. NS-1.
@@ -341,6 +365,7 @@
                 auto factor_level = [&](auto s0c) __attribute__((always_inline)) {
                     constexpr int S0 = decltype(s0c)::value;
                     constexpr int SL = NS - S0; // live slots
+                    QT_MARK1("hh-pro", S0)
                     double nrm[NS];
 #pragma unroll
                     for (int s = S0; s < NS; s++)
@@ -421,6 +446,7 @@
                         constexpr int j   = decltype(cnt)::value;
                         constexpr int ce  = j & ~1;       // first (even) row of this step's hand-off
                         constexpr int cen = (j + 1) & ~1; // ... of the next step's
+                        QT_MARK2("hh-step", S0, j)
                         // the next level's pieces: PF_PER per pivot step from the first step on (what an early end leaves over is requested behind the loop)
                         {
                             constexpr int TOT = NH * NIH, PF_PER = (TOT + PF_STEPS - 1) / PF_STEPS;
@@ -604,6 +630,7 @@
                         CSTAMP(6, __double2loint(blk[NS - 1][MD - 1]))
                         FSTAMP(5)
                     });
+                    QT_MARK1("hh-end", S0)
                     if (prefetch)
                         for_each_index<0, NH * NIH>([&](auto tt) __attribute__((always_inline)) {
                             if (decltype(tt)::value >= pf_issued) prefetch_piece(tt, F + dlev);
@@ -627,6 +654,7 @@
                 // =====================================================================================
                 // level end: triangular image [R_k T_k | rhs_k] / diag in end-of-level position order, maps
                 // =====================================================================================
+                QT_MARK("level-end")
                 const int wk   = n + 1 - Fc;
                 const int dump = o_stage + 8 * gl; // stores that do not apply go to a dump slot of the lane's own (the staging block is idle here): no divergent regions, no bank conflicts
                 int roff[MD];          // byte offset of image row p (triangular packing), the same for every slot
@@ -642,11 +670,13 @@
                     const int base = o_img + 8 * (imgoff + e);
                     if (mv)
                     {
+                        QT_MARK1("level-end-store", s)
 #pragma unroll
                         for (int p = 0; p < MD; p++) D(sel(p <= lim, base + roff[p], dump)) = blk[s][p];
                         B8(o_emap + 8 * pc[s] + k) = (uint8_t)e;
                         if (P0 < n) B8(o_phys + pos[s]) = (uint8_t)pc[s];
                     }
+                    QT_MARK1("level-end-maps", s)
                     // pivot position P0 of this level: its image row and the selector of this level's index byte
                     const bool piv = work && P0 >= Fc && P0 < Fc + rank;
                     const int p    = P0 - Fc;
@@ -669,9 +699,11 @@
 
             // ---- solve(): block back-substitution on the normalised images (lexlse.h:1015-1045); lane p <-> row p of a level.  Straight-line
             // per level: what does not apply reads a zero (position 16 NS - 1 of the x block is never written) or goes to the dump slot ----
+            QT_MARK("solve-top")
             const int o_zero = o_xs + 8 * (16 * NS - 1);
             for (int k = nObj; k--;)
             {
+                QT_MARK("solve-level")
                 const qt_u4 mt = U4(o_meta + 16 * k); // {first column, rank, image offset, image width}
                 const int rank = live ? (int)mt.y : 0;
                 const int rmax = rows_max(rank);
@@ -690,6 +722,7 @@
                 // sixteen solved positions per trip — lane j looks up index and x of position c0 + base + j, the row-broadcast hands them out
                 for (int base = 0; base < amax; base += 16)
                 {
+                    QT_MARK("solve-trip")
                     const bool have = base + gl < acc;
                     const int c     = have ? c0 + base + gl : 16 * NS - 1;
                     const int ph    = (int)B8(o_phys + c);
@@ -711,6 +744,7 @@
                     });
                     sv += s0 + s1;
                 }
+                QT_MARK("solve-tail")
                 sv = sel(gl < rank, sv, 0.0);
                 for_each_index<1, MD>([&](auto jj) {
                     constexpr int j = MD - decltype(jj)::value; // MD-1 .. 1
@@ -721,6 +755,7 @@
             }
             STAMP(9)
             // ---- results ----
+            QT_MARK("output")
             if (live)
             {
 #pragma unroll

@@ -113,6 +113,17 @@ namespace lexls
 #else
 #define LSTAMP(ph)
 #endif
+// Region marks (-DLEXLS_QTOL_MARKS, assembly only): a comment line "; qtol-region <name> [i [j]]" at the head of every phase and of every unrolled
+// step, by which scripts/qtol_insn_table.py splits the kernel's assembly and weighs each part with its trip count.  The product build has none.
+#ifdef LEXLS_QTOL_MARKS
+#define QT_MARK(name) asm volatile("; qtol-region " name);
+#define QT_MARK1(name, i) asm volatile("; qtol-region " name " %0" ::"i"(i));
+#define QT_MARK2(name, i, j) asm volatile("; qtol-region " name " %0 %1" ::"n"(i), "n"(j));
+#else
+#define QT_MARK(name)
+#define QT_MARK1(name, i)
+#define QT_MARK2(name, i, j)
+#endif
         /// f(integral_constant<int, I>) for I = B, B+1, ... while pred(I) holds: the first failing test leaves the whole remainder behind one branch
         template <int B, int E, class P, class F>
         __device__ __forceinline__ void qt_for_each_while(P &&pred, F &&f)
@@ -158,6 +169,52 @@ namespace lexls
             QT_PF_LIST(QT_PF_STORE)
 #undef QT_PF_STORE
         }
+
+        // ---- Gauss step with the row broadcast folded into the fma: d[r] = fma(bcast_L(s[r]), -u, d[r]), r = 0 .. MD-1, as v_fmac_f64_dpp
+        // row_newbcast:L — one instruction per row instead of v_mov_b64_dpp + v_fma_f64 (scripts/ubench/fmac_dpp.hip: 5.7 against 4.4 + 4.4
+        // cycles).  fma(l, -u, a) rounds as fma(-l, u, a).  A DPP read wants two wait states behind a VALU write of its source; the compiler
+        // does not look inside inline assembly, so each block opens with s_nop 1 (what the compiler put in front may have written a source,
+        // e.g. a reload from an accumulation register) and no row of a block reads what the row in front of it wrote.
+        // Precondition: FULL EXEC.  gbc<> (update_dpp with bound_ctrl and old = 0) hands a zero to a row whose source lane is disabled; these
+        // instructions carry no bound_ctrl, so a disabled source lane would suppress the write instead.  lqr_qtol's body is straight-line with
+        // selects (rows beyond the batch run on a valid problem), every lane is enabled wherever the helpers are called.
+#define QT_FD(i) "v_fmac_f64_dpp %[d" #i "], %[s" #i "], -%[u] row_newbcast:%[l] row_mask:0xf bank_mask:0xf\n\t"
+#define QT_FS(i) "v_fmac_f64_dpp %[d" #i "], %[d" #i "], -%[u] row_newbcast:%[l] row_mask:0xf bank_mask:0xf\n\t"
+#define QT_FO(i) [d##i] "+v"(d[i])
+#define QT_FI(i) [s##i] "v"(s[i])
+        /// another slot's rows: d (slot behind the pivot's) -= bcast_L(s) u, s = the rows of the pivot's slot
+        template <int L, int MD>
+        __device__ __forceinline__ void qt_gauss_dpp(double (&d)[MD], const double (&s)[MD], double u)
+        {
+            static_assert(MD == 8 || MD == 12, "operand lists below");
+            if constexpr (MD == 8)
+                asm volatile("s_nop 1\n\t" QT_FD(0) QT_FD(1) QT_FD(2) QT_FD(3) QT_FD(4) QT_FD(5) QT_FD(6) QT_FD(7)
+                             : QT_FO(0), QT_FO(1), QT_FO(2), QT_FO(3), QT_FO(4), QT_FO(5), QT_FO(6), QT_FO(7)
+                             : QT_FI(0), QT_FI(1), QT_FI(2), QT_FI(3), QT_FI(4), QT_FI(5), QT_FI(6), QT_FI(7), [u] "v"(u), [l] "n"(L));
+            else
+                asm volatile("s_nop 1\n\t" QT_FD(0) QT_FD(1) QT_FD(2) QT_FD(3) QT_FD(4) QT_FD(5) QT_FD(6) QT_FD(7) QT_FD(8) QT_FD(9) QT_FD(10) QT_FD(11)
+                             : QT_FO(0), QT_FO(1), QT_FO(2), QT_FO(3), QT_FO(4), QT_FO(5), QT_FO(6), QT_FO(7), QT_FO(8), QT_FO(9), QT_FO(10), QT_FO(11)
+                             : QT_FI(0), QT_FI(1), QT_FI(2), QT_FI(3), QT_FI(4), QT_FI(5), QT_FI(6), QT_FI(7), QT_FI(8), QT_FI(9), QT_FI(10), QT_FI(11),
+                               [u] "v"(u), [l] "n"(L));
+        }
+        /// the pivot's own slot, LAST in its step (lane L of it becomes zero: U'[c'][c'] is 1): every row reads lane L of itself
+        template <int L, int MD>
+        __device__ __forceinline__ void qt_gauss_dpp_self(double (&d)[MD], double u)
+        {
+            static_assert(MD == 8 || MD == 12, "operand lists below");
+            if constexpr (MD == 8)
+                asm volatile("s_nop 1\n\t" QT_FS(0) QT_FS(1) QT_FS(2) QT_FS(3) QT_FS(4) QT_FS(5) QT_FS(6) QT_FS(7)
+                             : QT_FO(0), QT_FO(1), QT_FO(2), QT_FO(3), QT_FO(4), QT_FO(5), QT_FO(6), QT_FO(7)
+                             : [u] "v"(u), [l] "n"(L));
+            else
+                asm volatile("s_nop 1\n\t" QT_FS(0) QT_FS(1) QT_FS(2) QT_FS(3) QT_FS(4) QT_FS(5) QT_FS(6) QT_FS(7) QT_FS(8) QT_FS(9) QT_FS(10) QT_FS(11)
+                             : QT_FO(0), QT_FO(1), QT_FO(2), QT_FO(3), QT_FO(4), QT_FO(5), QT_FO(6), QT_FO(7), QT_FO(8), QT_FO(9), QT_FO(10), QT_FO(11)
+                             : [u] "v"(u), [l] "n"(L));
+        }
+#undef QT_FD
+#undef QT_FS
+#undef QT_FO
+#undef QT_FI
 
         constexpr int kQtSentinelHi = (int)0xFFE00000; // -2^1023 * 1.x: below every down-dated norm, finite whatever the low word
 
