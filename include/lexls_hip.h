@@ -84,7 +84,11 @@ int lexls_lse_set_deferred_sync(lexls_lse_t h, int on);
 
 /* ---- problem definition ----------------------------------------------------------------------- */
 
-/* replaces setParameters (lexlse.h:1467); only REGULARIZATION_NONE has a device path (typedefs.h:122) */
+/* replaces setParameters (lexlse.h:1467); only REGULARIZATION_NONE has a device path (typedefs.h:122).
+ * A CHANGE of the tolerance invalidates what the handle keeps from earlier factorizations: lexls_lse_solve and everything else that needs a
+ * kept factor return LEXLS_ERR_INVALID until the next factorization (never the old x), and the prefix-reuse state is dropped — resume levels
+ * set before the call are forgotten, lexls_lse_prefix_reuse_ready is 0 and lexls_lse_set_resume_levels an error until a factorization has
+ * left a new state (the levels it would read back carry the ranks of the old tolerance).  Setting the same value again changes nothing. */
 int lexls_lse_set_tolerance(lexls_lse_t h, double tol_linear_dependence);
 /* replaces setObjDim (lexlse.h:1426): h_dims is nObj values (per_problem = 0, same for the whole
  * batch) or batch x nObj values (ragged batch, per_problem = 1); each dims[k] <= maxObjDim[k] */
@@ -310,7 +314,8 @@ int lexls_lse_get_accuracy(lexls_lse_t h, double *h_estimate, uint8_t *h_status,
  * search, no reflectors: the dependent chains that make up most of the kernel's time); their elimination of the rows from level levels[b] on is
  * redone with the same instructions on the same operands.  Factor, permutation, ranks, Householder scalars and x are IDENTICAL, bit for bit, to
  * a full factorization (tests/test_gpu_prefix_reuse.py).  levels[b] = 0: factorize everything.  The levels are consumed by that factorization.
- * The caller vouches for "unchanged": the kernel does not compare rows.  Regularization, x-only solves and the other kernels ignore the request
+ * The caller vouches for "unchanged": the kernel does not compare rows.  (A change of the rank tolerance is seen by the handle itself:
+ * lexls_lse_set_tolerance drops the state and the levels set.)  Regularization, x-only solves and the other kernels ignore the request
  * (full factorization) and leave nothing to resume from. */
 int lexls_lse_set_prefix_reuse(lexls_lse_t h, int enable);
 int lexls_lse_prefix_reuse_ready(lexls_lse_t h);

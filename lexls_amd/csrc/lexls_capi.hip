@@ -413,7 +413,14 @@ extern "C"
     int lexls_lse_set_tolerance(lexls_lse_t h, double tol)
     {
         CHECK_HANDLE(h);
-        if (tol != h->tol) h->factor_valid = false; // a factor / solution computed with the old tolerance must not be served any more
+        if (tol != h->tol)
+        {
+            h->factor_valid = false; // a factor / solution computed with the old tolerance must not be served any more
+            // ... nor read back by prefix reuse: the levels of the previous factorization carry the ranks of the old tolerance (the kernel
+            // replays them, it does not repeat the rank test).  Resume levels armed before this call are dropped with the state
+            h->resume_valid = false;
+            h->resume_armed = false;
+        }
         h->tol = tol;
         return LEXLS_OK;
     }

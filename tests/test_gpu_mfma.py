@@ -54,11 +54,17 @@ def test_full_size_batch_4096(hip, oracle, policy):
     assert (ref["rank"] == [12, 12, 12, 4, 0]).all()
 
 
-@pytest.mark.parametrize("n,nobj", [(2, 1), (7, 2), (12, 1), (24, 3), (31, 4), (32, 3), (36, 5), (39, 5), (40, 2), (40, 5)])
+@pytest.mark.parametrize("n,nobj", [(2, 1), (7, 2), (12, 1), (24, 3), (31, 4), (32, 3), (36, 5), (39, 5), (40, 2), (40, 5), (41, 3), (44, 2), (47, 1), (41, 4), (44, 4), (47, 4)])
 def test_other_numbers_of_variables(hip, oracle, n, nobj):
-    """levels of 12 rows with other n: the instantiations that read n from the arguments (one and two live slots per lane)"""
+    """levels of 12 rows with other n: the instantiations that read n from the arguments (one and two live slots per lane; n = 41 .. 47: the
+    third column tile and the larger piece count of the LDS-DMA loads, as deep as two workgroups' LDS slices per CU allow — 3 / 2 / 1 levels at
+    n = 41 / 44 / 47; four levels are beyond that (lqr_mfma_impl.h, mfma_group_bytes: 16 x 10336 / 11488 / 12688 bytes against 160 KB) and
+    go where policy 6 sends them, the bit-exact four-per-wavefront kernel)"""
     dims = [12] * nobj
+    beyond_lds = n > 40 and nobj == 4
     for policy, expect in ((7, "lqr_mfma<32,12,n40>" if n == 40 else "lqr_mfma<32,12>"), (8, "lqr_mfma<64,12>")):
+        if beyond_lds:
+            expect = "lqr_quad<3,12>"
         for batch in (1, 6, 67):
             check(hip, oracle, P.lse_batch(9000 + 10 * n + batch, batch, n, dims), dims, policy, expect, n)
         ranks = [max(1, min(12, n - 12 * k) - 3) if k % 2 == 0 else 12 for k in range(nobj)]
