@@ -18,6 +18,7 @@
 #ifndef LEXLS_HIP_H
 #define LEXLS_HIP_H
 
+#include <stddef.h>
 #include <stdint.h>
 
 #ifdef __cplusplus
@@ -227,6 +228,12 @@ int lexls_lse_device_ptr(lexls_lse_t h, int which, void **d_ptr);
 
 /* name of the kernel variant the last factorize/factorize_solve call dispatched to (diagnostics) */
 const char *lexls_lse_last_kernel(lexls_lse_t h);
+/* name of the kernel variant that served the last post-factorization call (solve, residual, sensitivity / sensitivity_collect, multipliers,
+ * solve_least_norm*), NUL-terminated into buf[0 .. len) and cut to len - 1 characters: "solve_generic<256>", "residual<64>",
+ * "sensitivity_sweep<12>", "sensitivity<64,staged>", "sensitivity<64,hbm>", "multipliers_sweep<16>", "multipliers<per-objective>",
+ * "leastnorm_2<64>", ...; "" after a factorization until one of them launches (a lexls_lse_solve the factorization kernel had answered
+ * already launches nothing).  Written on the host by the launchers: diagnostics, no kernel and no launch depends on it */
+int lexls_lse_last_consumer_kernel(lexls_lse_t h, char *buf, size_t len);
 /* Kernel policy — which CONTRACT a solve is held to, and which kernel family serves it.
  *   Contracts: (B) bit-identical to the arithmetic contract of oracle/lexlse_oracle.h (pivots, ranks, Householder scalars, factor, x, multipliers);
  *              (T) BASELINE north_star's: column permutation, ranks and first columns exact, x (and factor MAGNITUDES) within 1e-10

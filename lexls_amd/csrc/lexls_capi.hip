@@ -52,6 +52,7 @@ struct lexls_lse_s
     bool dims_set, has_fixed, factor_valid, factor_in_hbm;
     uint64_t x_epoch, factor_epoch; // x_epoch == factor_epoch: d_x holds the basic solution of the current factor (lexls_lse_solve has nothing to do)
     const char *last_kernel;
+    const char *last_consumer = ""; // lexls_lse_last_consumer_kernel: the variant the last post-factorization launcher took
 
     double *d_in_owned;
     bool deferred_sync;       // lexls_lse_set_deferred_sync: copies are enqueued, not waited for
@@ -853,7 +854,7 @@ extern "C"
         CHECK_HANDLE(h);
         if (!h->d_in) return fail(LEXLS_ERR_INVALID, "no problem data: call lexls_lse_set_problem_host/device first");
         HIP_TRY(hipSetDevice(h->device));
-        const char *variant = "";
+        const char *variant = "", *consumer = "";
         const LseArgs a     = h->args();
         const bool shape_kernels = h->force_generic != 1;
         // accuracy guard: lqr_qtol runs as its estimating instantiation; every other tolerance-contract kernel (the ragged lqr_qtol of policy 10
@@ -901,7 +902,7 @@ extern "C"
                 HIP_TRY(launch_lqr_large_fast(a, h->level_max.data(), h->max_rows, h->d_large_ws, h->stream));
                 variant = "lqr_large<step-per-pivot,mfma>";
             }
-            if (do_solve) HIP_TRY(launch_solve_generic(a, h->stream, h->force_generic != 5 && !guard)); // (the step-per-pivot path's contract allows reciprocals)
+            if (do_solve) HIP_TRY(launch_solve_generic(a, h->stream, h->force_generic != 5 && !guard, &consumer)); // (the step-per-pivot path's contract allows reciprocals)
             solved       = do_solve;
             write_factor = true;
         }
@@ -929,6 +930,7 @@ extern "C"
         h->resume_armed = false;
         h->resume_valid = a.resume_state != nullptr && write_factor && h->reg_type == 0 && std::strncmp(variant, "lqr_wave<", 9) == 0;
         h->last_kernel   = variant;
+        h->last_consumer = consumer; // (what ran on the previous factor says nothing about this one)
         h->factor_valid  = true;
         h->factor_epoch++;
         if (solved) h->x_epoch = h->factor_epoch;
@@ -951,7 +953,7 @@ extern "C"
         if (int rc = need_factor(h, "lexls_lse_solve")) return rc;
         if (h->x_epoch == h->factor_epoch) return LEXLS_OK; // the factorization kernel left the basic solution in place
         HIP_TRY(hipSetDevice(h->device));
-        HIP_TRY(launch_solve_generic(h->args(), h->stream, std::strstr(h->last_kernel, "step-per-pivot") != nullptr)); // (same x as that path's factorize_solve)
+        HIP_TRY(launch_solve_generic(h->args(), h->stream, std::strstr(h->last_kernel, "step-per-pivot") != nullptr, &h->last_consumer)); // (same x as that path's factorize_solve)
         h->x_epoch = h->factor_epoch;
         return LEXLS_OK;
     }
@@ -961,7 +963,7 @@ extern "C"
         if (int rc = need_factor(h, "lexls_lse_solve_least_norm")) return rc;
         HIP_TRY(hipSetDevice(h->device));
         if (!h->d_scratch) HIP_TRY(hipMalloc((void **)&h->d_scratch, 8 * (size_t)h->batch * 2 * h->nVar * h->nVar));
-        HIP_TRY(launch_leastnorm(h->args(), h->stream));
+        HIP_TRY(launch_leastnorm(h->args(), h->stream, &h->last_consumer));
         h->x_epoch = 0; // d_x now holds a least-norm solution
         return LEXLS_OK;
     }
@@ -971,7 +973,7 @@ extern "C"
         if (int rc = need_factor(h, "lexls_lse_solve_least_norm_2")) return rc;
         HIP_TRY(hipSetDevice(h->device));
         if (!h->d_scratch) HIP_TRY(hipMalloc((void **)&h->d_scratch, 8 * (size_t)h->batch * 2 * h->nVar * h->nVar));
-        HIP_TRY(launch_leastnorm2(h->args(), h->stream));
+        HIP_TRY(launch_leastnorm2(h->args(), h->stream, &h->last_consumer));
         h->x_epoch = 0; // d_x now holds a least-norm solution
         return LEXLS_OK;
     }
@@ -983,7 +985,7 @@ extern "C"
             return fail(LEXLS_ERR_INVALID, "lexls_lse_solve_least_norm_3: needs a factorization with a regularization type that accumulates the null-space basis (lexlse.h:1217-1221)");
         HIP_TRY(hipSetDevice(h->device));
         if (!h->d_scratch) HIP_TRY(hipMalloc((void **)&h->d_scratch, 8 * (size_t)h->batch * 2 * h->nVar * h->nVar));
-        HIP_TRY(launch_leastnorm3(h->args(), h->stream));
+        HIP_TRY(launch_leastnorm3(h->args(), h->stream, &h->last_consumer));
         h->x_epoch = 0; // d_x now holds a least-norm solution
         return LEXLS_OK;
     }
@@ -992,7 +994,7 @@ extern "C"
     {
         if (int rc = need_factor(h, "lexls_lse_residual")) return rc;
         HIP_TRY(hipSetDevice(h->device));
-        HIP_TRY(launch_residual(h->args(), h->stream));
+        HIP_TRY(launch_residual(h->args(), h->stream, &h->last_consumer));
         return LEXLS_OK;
     }
 
@@ -1011,7 +1013,7 @@ extern "C"
         {
             return fail(LEXLS_ERR_INVALID, "ObjIndex >= nObj");
         }
-        HIP_TRY(launch_sensitivity(h->args(), d_obj, obj_index_all, tolW, tolC, h->stream, h->sens_scan, h->max_level_dim));
+        HIP_TRY(launch_sensitivity(h->args(), d_obj, obj_index_all, tolW, tolC, h->stream, h->sens_scan, h->max_level_dim, false, &h->last_consumer));
         return LEXLS_OK;
     }
 
@@ -1026,7 +1028,7 @@ extern "C"
     {
         if (int rc = need_factor(h, "lexls_lse_sensitivity_resident")) return rc;
         HIP_TRY(hipSetDevice(h->device));
-        HIP_TRY(launch_sensitivity(h->args(), h->d_objidx, 0, tolW, tolC, h->stream, h->sens_scan, h->max_level_dim));
+        HIP_TRY(launch_sensitivity(h->args(), h->d_objidx, 0, tolW, tolC, h->stream, h->sens_scan, h->max_level_dim, false, &h->last_consumer));
         return LEXLS_OK;
     }
 
@@ -1055,7 +1057,7 @@ extern "C"
         {
             return fail(LEXLS_ERR_INVALID, "ObjIndex >= nObj");
         }
-        HIP_TRY(launch_sensitivity(h->args(), d_obj, obj_index_all, tolW, tolC, h->stream, h->sens_scan, h->max_level_dim, true));
+        HIP_TRY(launch_sensitivity(h->args(), d_obj, obj_index_all, tolW, tolC, h->stream, h->sens_scan, h->max_level_dim, true, &h->last_consumer));
         return LEXLS_OK;
     }
 
@@ -1063,7 +1065,7 @@ extern "C"
     {
         if (int rc = need_factor(h, "lexls_lse_sensitivity_collect_resident")) return rc;
         if (int rc = need_wrong_sign(h)) return rc;
-        HIP_TRY(launch_sensitivity(h->args(), h->d_objidx, 0, tolW, tolC, h->stream, h->sens_scan, h->max_level_dim, true));
+        HIP_TRY(launch_sensitivity(h->args(), h->d_objidx, 0, tolW, tolC, h->stream, h->sens_scan, h->max_level_dim, true, &h->last_consumer));
         return LEXLS_OK;
     }
 
@@ -1074,7 +1076,7 @@ extern "C"
         const LseArgs a = h->args();
         if (!h->d_mult) HIP_TRY(hipMalloc((void **)&h->d_mult, 8 * (size_t)h->batch * h->nObj * (h->nVar + h->cap)));
         if (!multipliers_sweep_serves(a, h->max_level_dim) && !h->d_mult_scratch) HIP_TRY(hipMalloc(&h->d_mult_scratch, multipliers_scratch_bytes(a)));
-        HIP_TRY(launch_multipliers(a, h->d_mult, h->max_level_dim, h->stream, h->d_mult_scratch, &h->mult_swept));
+        HIP_TRY(launch_multipliers(a, h->d_mult, h->max_level_dim, h->stream, h->d_mult_scratch, &h->mult_swept, &h->last_consumer));
         h->mult_valid = true;
         h->mult_epoch = h->factor_epoch;
         return LEXLS_OK;
@@ -1208,6 +1210,14 @@ extern "C"
     }
 
     const char *lexls_lse_last_kernel(lexls_lse_t h) { return h ? h->last_kernel : ""; }
+
+    int lexls_lse_last_consumer_kernel(lexls_lse_t h, char *buf, size_t len)
+    {
+        CHECK_HANDLE(h);
+        if (!buf || len == 0) return fail(LEXLS_ERR_INVALID, "lexls_lse_last_consumer_kernel: no buffer");
+        std::snprintf(buf, len, "%s", h->last_consumer);
+        return LEXLS_OK;
+    }
 
     int lexls_lse_set_accuracy_guard(lexls_lse_t h, int mode, double threshold)
     {

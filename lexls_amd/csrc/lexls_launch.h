@@ -12,20 +12,22 @@ namespace lexls
 
     // lqr_generic.hip — any shape, one workgroup per problem
     hipError_t launch_lqr_generic(LseArgs a, uint32_t max_rows, bool write_factor, bool do_solve, hipStream_t s, const char **variant);
-    hipError_t launch_solve_generic(const LseArgs &a, hipStream_t s, bool reciprocal_diagonal = false);
-    hipError_t launch_residual(const LseArgs &a, hipStream_t s);
+    // (variant, where given: the name of the kernel variant launched — lexls_lse_last_consumer_kernel; host bookkeeping only)
+    hipError_t launch_solve_generic(const LseArgs &a, hipStream_t s, bool reciprocal_diagonal = false, const char **variant = nullptr);
+    hipError_t launch_residual(const LseArgs &a, hipStream_t s, const char **variant = nullptr);
     hipError_t launch_sensitivity(const LseArgs &a, const int32_t *d_obj_index, int32_t obj_all, double tolW, double tolC, hipStream_t s, bool scan_up = false,
                                   uint32_t sweep_level_dim_hint = 0, // hint = largest level dimension of the batch (enables the single-sweep kernel)
-                                  bool collect = false);             // the wrong-sign SET into a.wrong_sign instead of one candidate (lexls_lse_sensitivity_collect)
+                                  bool collect = false,              // the wrong-sign SET into a.wrong_sign instead of one candidate (lexls_lse_sensitivity_collect)
+                                  const char **variant = nullptr);
     bool sensitivity_sweep_serves(const LseArgs &a, uint32_t sweep_level_dim_hint); // launch_sensitivity takes the one-wavefront-per-problem sweep for these arguments
     /// lexls_lse_multipliers: d_out = batch x nObj x (nVar + cap), column k = the [lambda_fixed; lambda] of ObjectiveSensitivity(k).  One launch of the
     /// sweep's emitting form where multipliers_sweep_serves, else nObj sensitivity_kernel launches (d_scratch: multipliers_scratch_bytes)
     bool multipliers_sweep_serves(const LseArgs &a, uint32_t sweep_level_dim_hint);
     size_t multipliers_scratch_bytes(const LseArgs &a);
-    hipError_t launch_multipliers(const LseArgs &a, double *d_out, uint32_t sweep_level_dim_hint, hipStream_t s, void *d_scratch, bool *swept);
-    hipError_t launch_leastnorm(const LseArgs &a, hipStream_t s);
-    hipError_t launch_leastnorm2(const LseArgs &a, hipStream_t s);
-    hipError_t launch_leastnorm3(const LseArgs &a, hipStream_t s);
+    hipError_t launch_multipliers(const LseArgs &a, double *d_out, uint32_t sweep_level_dim_hint, hipStream_t s, void *d_scratch, bool *swept, const char **variant = nullptr);
+    hipError_t launch_leastnorm(const LseArgs &a, hipStream_t s, const char **variant = nullptr);
+    hipError_t launch_leastnorm2(const LseArgs &a, hipStream_t s, const char **variant = nullptr);
+    hipError_t launch_leastnorm3(const LseArgs &a, hipStream_t s, const char **variant = nullptr);
     hipError_t launch_gather_rows(const LseArgs &a, const double *d_cdata, uint64_t per_problem, const uint32_t *d_row_src, const uint32_t *d_row_ld,
                                   double *d_dst, hipStream_t s);
 

@@ -1835,7 +1835,7 @@ namespace lexls
         return launch_lqr_t<1024, false>(a, true, do_solve, s);
     }
 
-    hipError_t launch_solve_generic(const LseArgs &a, hipStream_t s, bool reciprocal_diagonal)
+    hipError_t launch_solve_generic(const LseArgs &a, hipStream_t s, bool reciprocal_diagonal, const char **variant)
     {
         const size_t lds = 16 * (size_t)a.nVar + 16 + (a.nVar + 1 <= 64 ? 0 : 8 * 64 * 65); // x by position + the diagonal of the level being solved (+ the 64 x 64 block of the blocked form)
         if (a.nVar + 1 <= 64)
@@ -1843,6 +1843,7 @@ namespace lexls
             hipError_t e = set_lds(solve_generic_kernel<64>, lds);
             if (e != hipSuccess) return e;
             hipLaunchKernelGGL((solve_generic_kernel<64>), dim3(a.batch), dim3(64), lds, s, a);
+            if (variant) *variant = "solve_generic<64>";
         }
         else
         {
@@ -1852,6 +1853,7 @@ namespace lexls
                 hipLaunchKernelGGL((solve_generic_kernel<256, true>), dim3(a.batch), dim3(256), lds, s, a);
             else
                 hipLaunchKernelGGL((solve_generic_kernel<256>), dim3(a.batch), dim3(256), lds, s, a);
+            if (variant) *variant = reciprocal_diagonal ? "solve_generic<256,reciprocal>" : "solve_generic<256>";
         }
         return hipGetLastError();
     }
@@ -1889,13 +1891,14 @@ namespace lexls
         return hipGetLastError();
     }
 
-    hipError_t launch_residual(const LseArgs &a, hipStream_t s)
+    hipError_t launch_residual(const LseArgs &a, hipStream_t s, const char **variant)
     {
         const size_t lds = 8 * ((size_t)a.cap + 2);
         if (lds > kMaxLdsBytes) return hipErrorInvalidValue;
         hipError_t e = set_lds(residual_kernel<64>, lds);
         if (e != hipSuccess) return e;
         hipLaunchKernelGGL((residual_kernel<64>), dim3(a.batch), dim3(64), lds, s, a);
+        if (variant) *variant = "residual<64>";
         return hipGetLastError();
     }
 
@@ -1923,7 +1926,7 @@ namespace lexls
     }
 
     hipError_t launch_sensitivity(const LseArgs &a, const int32_t *d_obj_index, int32_t obj_all, double tolW, double tolC, hipStream_t s, bool scan_up, uint32_t sweep_level_dim_hint,
-                                  bool collect)
+                                  bool collect, const char **variant)
     {
         if (collect && !a.wrong_sign) return hipErrorInvalidValue;
         const size_t lds = 8 * (2 * (size_t)a.nVar + a.cap + 2) + sizeof(SensState) + 16;
@@ -1935,6 +1938,8 @@ namespace lexls
         const size_t lds_sweep  = sweep_lds_bytes(a);
         if (sensitivity_sweep_serves(a, sweep_level_dim_hint))
         {
+            static_assert(SWEEP_MD == 16, "the names below spell the sweep's level capacity out");
+            if (variant) *variant = sweep_level_dim_hint <= 12 ? (collect ? "sensitivity_sweep<12,collect>" : "sensitivity_sweep<12>") : (collect ? "sensitivity_sweep<16,collect>" : "sensitivity_sweep<16>");
             if (collect && sweep_level_dim_hint <= 12)
                 hipLaunchKernelGGL((sensitivity_sweep_kernel<12, true>), dim3(a.batch), dim3(64), lds_sweep, s, a, d_obj_index, obj_all, tolW, tolC, scan_up ? 1 : 0);
             else if (collect)
@@ -1955,11 +1960,13 @@ namespace lexls
                 if (e != hipSuccess) return e;
             }
             hipLaunchKernelGGL((sensitivity_kernel<64, true>), dim3(a.batch), dim3(64), lds_staged, s, a, d_obj_index, obj_all, tolW, tolC, scan_up ? 1 : 0, collect ? 1 : 0);
+            if (variant) *variant = "sensitivity<64,staged>";
             return hipGetLastError();
         }
         hipError_t e = set_lds(sensitivity_kernel<64, false>, lds);
         if (e != hipSuccess) return e;
         hipLaunchKernelGGL((sensitivity_kernel<64, false>), dim3(a.batch), dim3(64), lds, s, a, d_obj_index, obj_all, tolW, tolC, scan_up ? 1 : 0, collect ? 1 : 0);
+        if (variant) *variant = "sensitivity<64,hbm>";
         return hipGetLastError();
     }
 
@@ -1977,12 +1984,13 @@ namespace lexls
         return 8 * B * ((size_t)a.nVar + a.cap) + 8 * B + 4 * 3 * B + B * ((size_t)a.cap + a.nVar);
     }
 
-    hipError_t launch_multipliers(const LseArgs &a, double *d_out, uint32_t sweep_level_dim_hint, hipStream_t s, void *d_scratch, bool *swept)
+    hipError_t launch_multipliers(const LseArgs &a, double *d_out, uint32_t sweep_level_dim_hint, hipStream_t s, void *d_scratch, bool *swept, const char **variant)
     {
         const size_t ldo = (size_t)a.nVar + a.cap;
         if (multipliers_sweep_serves(a, sweep_level_dim_hint))
         {
             if (swept) *swept = true;
+            if (variant) *variant = sweep_level_dim_hint <= 12 ? "multipliers_sweep<12>" : "multipliers_sweep<16>";
             if (sweep_level_dim_hint <= 12)
                 hipLaunchKernelGGL(multipliers_sweep_kernel<12>, dim3(a.batch), dim3(64), sweep_lds_bytes(a), s, a, d_out);
             else
@@ -1990,6 +1998,7 @@ namespace lexls
             return hipGetLastError();
         }
         if (swept) *swept = false;
+        if (variant) *variant = "multipliers<per-objective>";
         // one sensitivity_kernel launch per objective, each copied into its column; the launches write the multipliers, decisions and marks into
         // scratch (the types are copied there first: the handle's own arrays stay as they are, as they do under the sweep)
         if (!d_scratch) return hipErrorInvalidValue;
@@ -2010,33 +2019,36 @@ namespace lexls
         return e;
     }
 
-    hipError_t launch_leastnorm(const LseArgs &a, hipStream_t s)
+    hipError_t launch_leastnorm(const LseArgs &a, hipStream_t s, const char **variant)
     {
         const size_t lds = 8 * (2 * (size_t)a.nVar + 4);
         if (lds > kMaxLdsBytes) return hipErrorInvalidValue;
         hipError_t e = set_lds(leastnorm_kernel<64>, lds);
         if (e != hipSuccess) return e;
         hipLaunchKernelGGL((leastnorm_kernel<64>), dim3(a.batch), dim3(64), lds, s, a);
+        if (variant) *variant = "leastnorm_1<64>";
         return hipGetLastError();
     }
 
-    hipError_t launch_leastnorm2(const LseArgs &a, hipStream_t s)
+    hipError_t launch_leastnorm2(const LseArgs &a, hipStream_t s, const char **variant)
     {
         const size_t lds = 8 * (2 * (size_t)a.nVar + 4);
         if (lds > kMaxLdsBytes) return hipErrorInvalidValue;
         hipError_t e = set_lds(leastnorm2_kernel<64>, lds);
         if (e != hipSuccess) return e;
         hipLaunchKernelGGL((leastnorm2_kernel<64>), dim3(a.batch), dim3(64), lds, s, a);
+        if (variant) *variant = "leastnorm_2<64>";
         return hipGetLastError();
     }
 
-    hipError_t launch_leastnorm3(const LseArgs &a, hipStream_t s)
+    hipError_t launch_leastnorm3(const LseArgs &a, hipStream_t s, const char **variant)
     {
         const size_t lds = 8 * (3 * (size_t)a.nVar + 4);
         if (lds > kMaxLdsBytes) return hipErrorInvalidValue;
         hipError_t e = set_lds(leastnorm3_kernel<64>, lds);
         if (e != hipSuccess) return e;
         hipLaunchKernelGGL((leastnorm3_kernel<64>), dim3(a.batch), dim3(64), lds, s, a);
+        if (variant) *variant = "leastnorm_3<64>";
         return hipGetLastError();
     }
 } // namespace lexls

@@ -307,6 +307,14 @@ class BatchedLexLSE:
     def last_kernel(self) -> str:
         return capi.lib().lexls_lse_last_kernel(self._h).decode()
 
+    def last_consumer_kernel(self) -> str:
+        """the kernel variant that served the last post-factorization call — solve, get_v, ObjectiveSensitivity / sensitivity_collect,
+        multipliers, solveLeastNorm_* — (lexls_lse_last_consumer_kernel): "solve_generic<256>", "sensitivity_sweep<12>",
+        "sensitivity<64,staged>", "multipliers<per-objective>", "leastnorm_2<64>", ...; "" when none has launched on the current factor"""
+        buf = C.create_string_buffer(64)
+        capi.check(capi.lib().lexls_lse_last_consumer_kernel(self._h, buf, C.c_size_t(len(buf))))
+        return buf.value.decode()
+
     def set_accuracy_guard(self, mode: int, threshold: float = 0.0):
         """lexls_lse_set_accuracy_guard: 0 off (default), 1 report, 2 report and re-solve the flagged problems on the bit-exact kernel
         (include/lexls_hip.h, policy comment); threshold <= 0: the calibrated default"""

@@ -15,6 +15,7 @@ import ctypes as C
 import numpy as np
 import pytest
 
+import postfactor_cases
 from lexls_amd import capi, problems as P
 
 pytestmark = pytest.mark.gpu
@@ -41,42 +42,10 @@ def inputs(nfixed_of):
 
 
 def reference_collect(oracle, lod, types, nfixed, idx, val, typ, start, scan):
-    """the collecting overload on the oracle's multipliers, problem by problem"""
-    mask = np.zeros((BATCH, N + CAP), np.uint8)
-    ctr, fix = types.copy(), typ.copy()
-    lam = np.zeros((BATCH, N + CAP))
-    verdict = np.zeros((BATCH, 3), np.int32)
-    first = np.concatenate([[0], np.cumsum(DIMS)])
-    fixed = bool(nfixed.any())
-    for b in range(BATCH):
-        nf = int(nfixed[b])
-        for L in range(start, len(DIMS)):
-            kw = dict(nfixed=nfixed[b:b + 1], fixed_idx=idx[b:b + 1], fixed_val=val[b:b + 1], fixed_type=typ[b:b + 1]) if fixed else {}
-            ref = oracle.lse_run(lod[b:b + 1], DIMS, N, ctr_type=types[b:b + 1], sens_obj=L, **kw)
-            lam[b] = ref["lam"][0]
-            Lambda = lam[b, nf:]  # getWorkspace() = [lambda_fixed; lambda]
-
-            def scan_group(tarr, toff, moff, count):
-                for k in range(count):
-                    t = tarr[b, toff + k]
-                    if t == EQ or t == CORRECT:
-                        continue
-                    a = Lambda[toff + k]
-                    if t == LB:
-                        a = -a
-                    if a > TOLC:
-                        tarr[b, toff + k] = CORRECT
-                    elif a < -TOLW:
-                        mask[b, moff + k] = 1
-
-            for k in range(L, -1, -1):
-                scan_group(ctr, int(first[k]), N + int(first[k]), DIMS[k])
-            if nf > 0:
-                scan_group(fix, 0, 0, min(DIMS[0], nf))
-            verdict[b] = (int(mask[b].any()), int(mask[b].sum()), L)
-            if mask[b].any() or not scan:
-                break
-    return mask, ctr, fix, lam, verdict
+    """the collecting overload on the oracle's multipliers, problem by problem (tests/postfactor_cases.py: the same scan for any shape)"""
+    fixed = dict(nfixed=nfixed, fixed_idx=idx, fixed_val=val, fixed_type=typ) if nfixed.any() else {}
+    mask, ctr, fix, lam, verdict = postfactor_cases.reference_collect(N, DIMS, lod, DIMS, types, fixed, start, scan)
+    return mask, ctr, fix if fixed else typ.copy(), lam, verdict
 
 
 CASES = {
