@@ -42,7 +42,7 @@ struct lexls_lse_s
     int device;
     hipStream_t stream;
     uint32_t batch, nVar, nObj, cap, max_rows, max_level_dim, min_level_dim;
-    int force_generic;
+    KernelPolicy policy; // lexls_lse_set_kernel_policy
     std::vector<uint32_t> maxdim, level_max;
     void *d_large_state;
     void *d_large_ws; // work space of the fast large path
@@ -52,6 +52,7 @@ struct lexls_lse_s
     bool dims_set, has_fixed, factor_valid, factor_in_hbm;
     uint64_t x_epoch, factor_epoch; // x_epoch == factor_epoch: d_x holds the basic solution of the current factor (lexls_lse_solve has nothing to do)
     const char *last_kernel;
+    bool solve_reciprocal = false; // the plan of the last factorization: a later lexls_lse_solve may use the reciprocal diagonal
     const char *last_consumer = ""; // lexls_lse_last_consumer_kernel: the variant the last post-factorization launcher took
 
     double *d_in_owned;
@@ -187,8 +188,8 @@ extern "C"
         h->max_rows    = h->cap;
         h->max_level_dim = 0;
         h->min_level_dim = 0;
-        h->force_generic = 0;
-        if (const char *e = std::getenv("LEXLS_KERNEL_POLICY")) h->force_generic = std::atoi(e); // diagnostic default of lexls_lse_set_kernel_policy
+        h->policy = KernelPolicy::automatic;
+        if (const char *e = std::getenv("LEXLS_KERNEL_POLICY")) h->policy = static_cast<KernelPolicy>(std::atoi(e)); // diagnostic default of lexls_lse_set_kernel_policy
         h->tol         = 1e-12; // typedefs.h:120
         h->dims_set    = false;
         h->has_fixed   = false;
@@ -306,6 +307,53 @@ extern "C"
         return LEXLS_OK;
     }
 
+    /// What plan_lqr (lexls_dispatch.h) reads, from the handle as it stands; the environment and device facts are looked up here
+    /// (LEXLS_QTOL at every call, so that a caller may change it between solves)
+    static DispatchQuery query_of(const lexls_lse_s *h, bool write_factor, bool do_solve, bool opportunistic_solve = false)
+    {
+        DispatchQuery q;
+        q.batch = h->batch, q.nVar = h->nVar, q.nObj = h->nObj, q.cap = h->cap;
+        q.uniform_dim   = (h->dims_set && h->min_level_dim == h->max_level_dim) ? h->max_level_dim : 0u;
+        q.max_rows = h->max_rows, q.max_level_dim = h->max_level_dim;
+        q.has_fixed = h->has_fixed, q.reg_type = h->reg_type, q.has_dims = h->d_dims != nullptr;
+        const uintptr_t in    = reinterpret_cast<uintptr_t>(h->d_in);
+        q.align               = (in & 15u) == 0 ? 16u : ((in & 7u) == 0 ? 8u : 0u);
+        q.gather_by_reference = h->fused_gather;
+        q.write_factor = write_factor, q.do_solve = do_solve, q.opportunistic_solve = opportunistic_solve;
+        q.policy = h->policy, q.guard = h->guard_mode != 0;
+        const char *e   = std::getenv("LEXLS_QTOL");
+        q.qtol_off      = e && std::atoi(e) == 0;
+        q.wave_capacity = resident_wave_capacity();
+        q.reg_lds_share = wave_reg_lds_share();
+        return q;
+    }
+
+    /// ... of a resident LexLSI round, factor kept: the capacities given at creation stand for the dimensions (this round's are known to the
+    /// device only).  Shape, policy and LDS share only — no device is asked (callers that plan a launch add wave_capacity); the handle is not touched
+    static DispatchQuery resident_query_of(const lexls_lse_s *h, bool has_fixed, uint32_t reg_type)
+    {
+        DispatchQuery q;
+        q.batch = h->batch, q.nVar = h->nVar, q.nObj = h->nObj, q.cap = h->cap;
+        q.max_rows = h->cap ? h->cap : 1;
+        for (uint32_t v : h->maxdim) q.max_level_dim = v > q.max_level_dim ? v : q.max_level_dim;
+        q.has_fixed = has_fixed, q.reg_type = reg_type, q.policy = h->policy, q.reg_lds_share = wave_reg_lds_share();
+        return q;
+    }
+
+    /// the fields lexls_internal_round_resident and lexls_internal_resident_fused both set for such a round
+    static void enter_resident_round(lexls_lse_t h, const DispatchQuery &q, bool gather_by_reference)
+    {
+        h->level_max.assign(h->maxdim.begin(), h->maxdim.end());
+        h->max_rows      = q.max_rows;
+        h->max_level_dim = q.max_level_dim;
+        h->min_level_dim = 0; // this round's dimensions are known to the device only
+        h->dims_set      = true;
+        h->has_fixed     = q.has_fixed;
+        h->has_skip      = true;
+        h->fused_gather  = gather_by_reference;
+        h->d_in          = h->d_in_owned;
+    }
+
     /// A round whose rows are read by reference inside the register-resident wave kernel (fused_gather) leaves `in` unassembled.  Anything that
     /// can send the next factorization to ANOTHER kernel (kernel policy, regularization type) assembles the rows first.
     static hipError_t materialize_fused_gather(lexls_lse_t h)
@@ -382,13 +430,9 @@ extern "C"
      * optional there).  Decided from the capacities given at creation: nothing is launched, nothing changes. */
     int lexls_internal_resident_reg_serves(lexls_lse_t h, int type)
     {
-        if (!h || type < 1 || type > 9 || h->force_generic == 1) return 0;
-        uint32_t max_level = 0;
-        for (uint32_t v : h->maxdim) max_level = v > max_level ? v : max_level;
-        LseArgs a  = h->args();
-        a.reg_type = (uint32_t)type;
-        if (!wave_kernel_supports(a, h->cap ? h->cap : 1, max_level, true)) return 0;
-        return wave_reg_kernel_fits(a, max_level) ? 1 : 0;
+        if (!h || type < 1 || type > 9 || h->policy == KernelPolicy::generic_only) return 0;
+        const DispatchQuery q = resident_query_of(h, true, (uint32_t)type);
+        return (dispatch::wave_family_supports(q) && wave_reg_kernel_fits(q)) ? 1 : 0;
     }
 
     int lexls_lse_set_cg_iterations(lexls_lse_t h, uint32_t max_iterations)
@@ -562,10 +606,11 @@ extern "C"
         return LEXLS_OK;
     }
 
-    int lexls_lse_set_constraint_data(lexls_lse_t h, const double *h_data, uint64_t per_problem)
+    /// the batch's resident constraint data from host memory (waited for) or device memory (enqueued)
+    static int set_constraint_data(lexls_lse_t h, const char *who, const double *data, uint64_t per_problem, hipMemcpyKind kind)
     {
         CHECK_HANDLE(h);
-        if (!h_data || per_problem == 0) return fail(LEXLS_ERR_INVALID, "set_constraint_data: null / empty");
+        if (!data || per_problem == 0) return fail(LEXLS_ERR_INVALID, std::string(who) + ": null / empty");
         HIP_TRY(hipSetDevice(h->device));
         const size_t bytes = 8 * (size_t)h->batch * per_problem;
         if (h->d_cdata && h->cdata_per_problem != per_problem)
@@ -575,27 +620,12 @@ extern "C"
         }
         if (!h->d_cdata) HIP_TRY(hipMalloc((void **)&h->d_cdata, bytes));
         h->cdata_per_problem = per_problem;
-        HIP_TRY(hipMemcpyAsync(h->d_cdata, h_data, bytes, hipMemcpyHostToDevice, h->stream));
-        HIP_TRY(hipStreamSynchronize(h->stream));
+        HIP_TRY(hipMemcpyAsync(h->d_cdata, data, bytes, kind, h->stream));
+        if (kind == hipMemcpyHostToDevice) HIP_TRY(hipStreamSynchronize(h->stream));
         return LEXLS_OK;
     }
-
-    int lexls_internal_set_constraint_data_device(lexls_lse_t h, const double *d_data, uint64_t per_problem)
-    {
-        CHECK_HANDLE(h);
-        if (!d_data || per_problem == 0) return fail(LEXLS_ERR_INVALID, "set_constraint_data_device: null / empty");
-        HIP_TRY(hipSetDevice(h->device));
-        const size_t bytes = 8 * (size_t)h->batch * per_problem;
-        if (h->d_cdata && h->cdata_per_problem != per_problem)
-        {
-            HIP_TRY(hipFree(h->d_cdata));
-            h->d_cdata = nullptr;
-        }
-        if (!h->d_cdata) HIP_TRY(hipMalloc((void **)&h->d_cdata, bytes));
-        h->cdata_per_problem = per_problem;
-        HIP_TRY(hipMemcpyAsync(h->d_cdata, d_data, bytes, hipMemcpyDeviceToDevice, h->stream));
-        return LEXLS_OK;
-    }
+    int lexls_lse_set_constraint_data(lexls_lse_t h, const double *h_data, uint64_t per_problem) { return set_constraint_data(h, "set_constraint_data", h_data, per_problem, hipMemcpyHostToDevice); }
+    int lexls_internal_set_constraint_data_device(lexls_lse_t h, const double *d_data, uint64_t per_problem) { return set_constraint_data(h, "set_constraint_data_device", d_data, per_problem, hipMemcpyDeviceToDevice); }
 
     int lexls_internal_ensure_gather_buffer(lexls_lse_t h)
     {
@@ -620,12 +650,8 @@ extern "C"
             if (ld && (uint64_t)h_row_src[i] + (uint64_t)(h->nVar + 1) * ld >= h->cdata_per_problem)
                 return fail(LEXLS_ERR_INVALID, "gather_problem: row reference outside the constraint data");
         }
+        if (int rc = lexls_internal_ensure_gather_buffer(h)) return rc;
         HIP_TRY(hipSetDevice(h->device));
-        if (!h->d_in_owned)
-        {
-            HIP_TRY(hipMalloc((void **)&h->d_in_owned, 8 * B * h->problem_elems()));
-            HIP_TRY(hipMemsetAsync(h->d_in_owned, 0, 8 * B * h->problem_elems(), h->stream));
-        }
         HIP_TRY(hipMemcpyAsync(h->d_row_src, h_row_src, 4 * B * cap, hipMemcpyHostToDevice, h->stream));
         HIP_TRY(hipMemcpyAsync(h->d_row_ld, h_row_ld, 4 * B * cap, hipMemcpyHostToDevice, h->stream));
         HIP_TRY(launch_gather_rows(h->args(), h->d_cdata, h->cdata_per_problem, h->d_row_src, h->d_row_ld, h->d_in_owned, h->stream));
@@ -653,32 +679,13 @@ extern "C"
         CHECK_HANDLE(h);
         if (!h->d_cdata || !h->d_in_owned) return fail(LEXLS_ERR_INVALID, "round_resident: needs resident constraint data and one uploaded round");
         HIP_TRY(hipSetDevice(h->device));
-        uint32_t max_level = 0;
-        h->level_max.assign(h->maxdim.begin(), h->maxdim.end());
-        for (uint32_t v : h->maxdim) max_level = v > max_level ? v : max_level;
-        h->max_rows      = h->cap ? h->cap : 1;
-        h->max_level_dim = max_level;
-        h->min_level_dim = 0; // this round's dimensions are known to the device only
-        h->dims_set      = true;
-        h->has_fixed     = has_fixed != 0;
-        h->has_skip      = true;
-        h->factor_valid  = false;
-        h->fused_gather  = false;
-        h->d_in          = h->d_in_owned;
-        // the register-resident wave kernel reads the rows by reference itself (one launch and one pass over the problems less)
-        // (a forced left-looking / four-per-wavefront policy is honoured; otherwise the register-resident kernel at every batch size: on the
-        // ragged problems of a lock-step LSI stage, with the gather fused, it beats the four-per-wavefront kernel + gather launch also beyond
-        // one round — 4096 instances, warm-started ~30 iterations: 37.1 ms vs 39.1 ms)
-        // 42..48 columns are the exception: their register-resident form is the 64-column instantiation, and the four-per-wavefront kernel
-        // behind a gather launch is ahead of it at every batch size (1024 instances, n = 47, 5 x 12, cold: 21.3 -> 17.1 ms)
-        const bool wide_slot = h->nVar + 1 > 41 && h->nVar + 1 <= 48 && h->max_level_dim <= 12;
-        const int ll = h->force_generic == 3 ? 1 : (h->force_generic == 4 ? 2 : (wide_slot && h->force_generic == 0 ? 0 : -1));
-        // (a regularized round: the REG instantiation of that kernel, the same load; type 7 has none, wave_kernel_supports)
-        if (h->force_generic != 1 && wave_kernel_supports(h->args(), h->max_rows, h->max_level_dim, h->has_fixed) &&
-            wave_dispatch_is_register_resident(h->args(), h->max_level_dim, h->has_fixed, ll))
-            h->fused_gather = true;
-        else
-            HIP_TRY(launch_gather_rows(h->args(), h->d_cdata, h->cdata_per_problem, h->d_row_src, h->d_row_ld, h->d_in_owned, h->stream));
+        // the register-resident wave kernel reads the rows by reference itself where the plan says so (plan_round_gathers_by_reference)
+        DispatchQuery q = resident_query_of(h, has_fixed != 0, h->reg_type);
+        q.wave_capacity   = resident_wave_capacity();
+        const bool by_ref = plan_round_gathers_by_reference(q);
+        enter_resident_round(h, q, by_ref);
+        h->factor_valid = false;
+        if (!by_ref) HIP_TRY(launch_gather_rows(h->args(), h->d_cdata, h->cdata_per_problem, h->d_row_src, h->d_row_ld, h->d_in_owned, h->stream));
         return LEXLS_OK;
     }
 
@@ -691,41 +698,32 @@ extern "C"
     {
         CHECK_HANDLE(h);
         if (!h->d_cdata || !h->d_in_owned) return fail(LEXLS_ERR_INVALID, "resident_fused: needs resident constraint data and one uploaded round");
-        if (h->force_generic != 0 || std::getenv("LEXLS_LSI_NO_FUSED")) return 1;
+        if (std::getenv("LEXLS_LSI_NO_FUSED")) return 1;
         const bool reg = h->reg_type != 0; // the launch with the regularized l-QR: no prefix reuse (lqr_small_impl.h), so no resume levels either way
         HIP_TRY(hipSetDevice(h->device));
-        // what lexls_internal_round_resident would set — on a copy of the fields first: nothing changes when the launch is not taken
-        uint32_t max_level = 0;
-        for (uint32_t v : h->maxdim) max_level = v > max_level ? v : max_level;
-        if (!reg && h->nVar + 1 > 41 && h->nVar + 1 <= 48 && max_level <= 12) return 1; // (42..48 columns: the four-per-wavefront kernel behind a gather launch, as lexls_internal_round_resident decides)
-        {
-            lexls_lse_s probe    = *h; // (plain fields and pointers; the vectors are copied, the probe owns nothing it frees)
-            probe.max_rows       = h->cap ? h->cap : 1;
-            probe.max_level_dim  = max_level;
-            probe.min_level_dim  = 0;
-            probe.dims_set       = true;
-            probe.has_fixed      = has_fixed != 0;
-            probe.has_skip       = true;
-            probe.fused_gather   = true;
-            probe.d_in           = h->d_in_owned;
-            probe.resume_armed   = h->resume_enabled && !reg;
-            const LseArgs pa     = probe.args();
-            const char *variant  = "";
-            if (!wave_kernel_supports(pa, probe.max_rows, max_level, probe.has_fixed)) return 1;
-            const hipError_t e = launch_lsi_fused(pa, max_level, probe.has_fixed, h->d_objidx, tolW, tolC, h->sens_scan, resident_args, resident_args_bytes, count, h->stream, &variant);
-            if (e == hipErrorNotSupported) return 1;
-            HIP_TRY(e);
-            h->last_kernel = variant;
-        }
-        h->level_max.assign(h->maxdim.begin(), h->maxdim.end());
-        h->max_rows      = h->cap ? h->cap : 1;
-        h->max_level_dim = max_level;
-        h->min_level_dim = 0;
-        h->dims_set      = true;
-        h->has_fixed     = has_fixed != 0;
-        h->has_skip      = true;
-        h->fused_gather  = true;
-        h->d_in          = h->d_in_owned;
+        DispatchQuery q = resident_query_of(h, has_fixed != 0, h->reg_type);
+        q.wave_capacity = resident_wave_capacity();
+        // the arguments lexls_internal_round_resident + lexls_internal_arm_resume would leave — on a copy: nothing changes when the launch is not taken
+        LseArgs pa      = h->args();
+        pa.ldp          = odd_ld(q.max_rows);
+        pa.in           = h->d_in_owned;
+        pa.uniform_dim  = 0;
+        pa.nfixed       = q.has_fixed ? h->d_nfixed : nullptr;
+        pa.skip         = h->d_skip;
+        pa.g_cdata      = h->d_cdata;
+        pa.resume_level = (h->resume_enabled && !reg && h->resume_valid) ? h->d_resume_level : nullptr;
+        q.sweep_serves  = sensitivity_sweep_serves(pa, q.max_level_dim);
+        const KernelId id = plan_lsi_fused(q);
+        if (id == KernelId::none) return 1;
+        const FusedCall call{q.max_level_dim, h->d_objidx, tolW, tolC, h->sens_scan, resident_args, resident_args_bytes, count};
+        LaunchExtras x;
+        x.fused            = &call;
+        const hipError_t e = launch_kernel(id, pa, h->stream, x);
+        if (e == hipErrorNotSupported) return 1;
+        HIP_TRY(e);
+        h->last_kernel      = kernel_name(id);
+        h->solve_reciprocal = false;
+        enter_resident_round(h, q, true);
         h->resume_armed  = false;
         h->resume_valid  = h->resume_enabled && h->d_resume_state != nullptr && !reg;
         h->factor_valid  = true;
@@ -796,11 +794,7 @@ extern "C"
         h->factor_valid  = false;
         if (gather)
         {
-            if (!h->d_in_owned)
-            {
-                HIP_TRY(hipMalloc((void **)&h->d_in_owned, 8 * (size_t)h->batch * h->problem_elems()));
-                HIP_TRY(hipMemsetAsync(h->d_in_owned, 0, 8 * (size_t)h->batch * h->problem_elems(), h->stream));
-            }
+            if (int rc = lexls_internal_ensure_gather_buffer(h)) return rc;
             HIP_TRY(launch_gather_rows(h->args(), h->d_cdata, h->cdata_per_problem, h->d_row_src, h->d_row_ld, h->d_in_owned, h->stream));
             h->d_in = h->d_in_owned;
         }
@@ -829,18 +823,6 @@ extern "C"
         return LEXLS_OK;
     }
 
-    /// Which tolerance-contract kernels a factorization of this handle may take (launch_lqr_wave's `tolerance`): policies 6 .. 10 name them;
-    /// automatic dispatch (policy 0) takes them wherever they serve unless the process runs under LEXLS_QTOL=0 (read at every call, so that a
-    /// caller may change it between solves); every other policy stays on the bit-exact kernels
-    static int tolerance_mode(lexls_lse_t h)
-    {
-        if (h->fused_gather) return 0;
-        if (h->force_generic >= 6 && h->force_generic <= 10) return h->force_generic;
-        if (h->force_generic != 0) return 0;
-        const char *e = std::getenv("LEXLS_QTOL");
-        return (e && std::atoi(e) == 0) ? 0 : 1;
-    }
-
     /// Default threshold of the accuracy guard's estimate (max over pivots of |raw pivot column| / |R_jj|), calibrated by
     /// scripts/calibrate_guard.py ("Accuracy guard"): the largest estimate of 4096 well-conditioned IK problems is 13.1, the
     /// smallest of a problem whose x moves by more than 1e-11 under one-ulp changes of its data 421 — about five times either way
@@ -850,74 +832,47 @@ extern "C"
     /// always, the generic kernel on request), so that a later lexls_lse_solve of the same factor has nothing left to do
     static int run_lqr(lexls_lse_t h, bool write_factor, bool do_solve, bool opportunistic_solve = false)
     {
-        bool solved = true;
         CHECK_HANDLE(h);
         if (!h->d_in) return fail(LEXLS_ERR_INVALID, "no problem data: call lexls_lse_set_problem_host/device first");
         HIP_TRY(hipSetDevice(h->device));
-        const char *variant = "", *consumer = "";
-        const LseArgs a     = h->args();
-        const bool shape_kernels = h->force_generic != 1;
-        // accuracy guard: lqr_qtol runs as its estimating instantiation; every other tolerance-contract kernel (the ragged lqr_qtol of policy 10
-        // included) gives way to the bit-exact one
-        const bool guard = h->guard_mode != 0;
-        int tolerance    = tolerance_mode(h);
-        if (guard && tolerance != 0) tolerance = (tolerance == 1 || tolerance == 6 || tolerance == 10) ? 6 : 0;
-        const GuardArrays guard_arrays{h->d_guard_est, h->d_guard_status, h->d_guard_ind};
-        const GuardArrays *gp = guard ? &guard_arrays : nullptr;
-        // (the regularization family lives in the register-resident wave kernel's REG instantiations and in the generic kernel)
-        if (shape_kernels && wave_kernel_supports(a, h->max_rows, h->max_level_dim, h->has_fixed))
+        const LseArgs a       = h->args();
+        const DispatchQuery q = query_of(h, write_factor, do_solve, opportunistic_solve);
+        const KernelPlan plan = plan_lqr(q);
+        const char *consumer  = "";
+        LaunchExtras x;
+        x.est = h->d_guard_est, x.ind = h->d_guard_ind;
+        if (plan.id == KernelId::large_multi)
         {
-            const int ll = h->fused_gather ? -1 : (h->force_generic == 2 ? -1 : (h->force_generic == 3 ? 1 : (h->force_generic == 4 ? 2 : 0)));
-            // the tolerance-contract kernel (lqr_qtol_impl.h): automatic dispatch and policy 6; LEXLS_QTOL=0 keeps every solve bit-exact
-            HIP_TRY(launch_lqr_wave(a, h->max_level_dim, write_factor, h->has_fixed, ll, h->stream, &variant, tolerance, gp)); // always solves as well
+            if (!h->d_large_state) HIP_TRY(hipMalloc(&h->d_large_state, large_state_bytes(h->batch)));
+            if (!h->d_norms) HIP_TRY(hipMalloc((void **)&h->d_norms, 8 * (size_t)h->batch * h->nVar));
+            HIP_TRY(launch_lqr_large(a, h->level_max.data(), h->max_rows, h->d_large_state, h->d_norms, h->stream));
         }
-        else if (shape_kernels && h->force_generic != 2 && h->max_rows > 64 && h->max_level_dim <= 16 && a.nObj <= 16 &&
-                 deep_kernel_supports(a, h->max_level_dim, write_factor, h->has_fixed))
+        else if (plan.id == KernelId::large_fast)
         {
-            // deep hierarchies (more than 64 rows in all): the left-looking kernels, whose LDS holds pivot rows only (x-only solves of the IK
-            // shape: the tolerance-contract kernel under the same rules as above — it reads a level's rows when the level starts, too)
-            HIP_TRY(launch_lqr_wave(a, h->max_level_dim, write_factor, h->has_fixed, 2, h->stream, &variant, tolerance, gp));
-        }
-        else if (shape_kernels && h->reg_type == 0 && !generic_fits_lds(a, h->max_rows) && large_kernel_supports(a, h->max_level_dim, h->has_fixed))
-        {
-            if (h->force_generic == 5 || guard) // the bit-exact multi-launch path (ordered chains: parity tests, reference for the fast path)
+            uint32_t md = 0;
+            for (uint32_t v : h->level_max) md = v > md ? v : md;
+            const size_t need = large_fast_workspace_bytes(h->batch, h->nVar, h->cap, md);
+            if (need > h->large_ws_bytes)
             {
-                if (!h->d_large_state) HIP_TRY(hipMalloc(&h->d_large_state, large_state_bytes(h->batch)));
-                if (!h->d_norms) HIP_TRY(hipMalloc((void **)&h->d_norms, 8 * (size_t)h->batch * h->nVar));
-                HIP_TRY(launch_lqr_large(a, h->level_max.data(), h->max_rows, h->d_large_state, h->d_norms, h->stream));
-                variant = "lqr_large<multi-launch>";
+                if (h->d_large_ws) HIP_TRY(hipFree(h->d_large_ws));
+                h->d_large_ws = nullptr;
+                HIP_TRY(hipMalloc(&h->d_large_ws, need));
+                h->large_ws_bytes = need;
             }
-            else
-            {
-                uint32_t md = 0;
-                for (uint32_t v : h->level_max) md = v > md ? v : md;
-                const size_t need = large_fast_workspace_bytes(h->batch, h->nVar, h->cap, md);
-                if (need > h->large_ws_bytes)
-                {
-                    if (h->d_large_ws) HIP_TRY(hipFree(h->d_large_ws));
-                    h->d_large_ws = nullptr;
-                    HIP_TRY(hipMalloc(&h->d_large_ws, need));
-                    h->large_ws_bytes = need;
-                }
-                HIP_TRY(launch_lqr_large_fast(a, h->level_max.data(), h->max_rows, h->d_large_ws, h->stream));
-                variant = "lqr_large<step-per-pivot,mfma>";
-            }
-            if (do_solve) HIP_TRY(launch_solve_generic(a, h->stream, h->force_generic != 5 && !guard, &consumer)); // (the step-per-pivot path's contract allows reciprocals)
-            solved       = do_solve;
-            write_factor = true;
+            HIP_TRY(launch_lqr_large_fast(a, h->level_max.data(), h->max_rows, h->d_large_ws, h->stream));
         }
+        else if (plan.id == KernelId::none || plan.id >= KernelId::generic_64_lds)
+            HIP_TRY(launch_lqr_generic(a, h->max_rows, plan.id, write_factor, plan.solves_x, h->stream));
         else
+            HIP_TRY(launch_kernel(plan.id, a, h->stream, x));
+        if (plan.needs_solve_launch) HIP_TRY(launch_solve_generic(a, h->stream, plan.reciprocal_solve, &consumer));
+        h->guard_last = q.guard;
+        if (q.guard)
         {
-            solved = do_solve || opportunistic_solve;
-            HIP_TRY(launch_lqr_generic(a, h->max_rows, write_factor, solved, h->stream, &variant));
-        }
-        h->guard_last = guard;
-        if (guard)
-        {
-            if (std::strstr(variant, ",guard>")) // flags -> status (and the list), then the bit-exact re-solve of the flagged problems: all in the stream
+            if (plan.estimating) // flags -> status (and the list), then the bit-exact re-solve of the flagged problems: all in the stream
             {
                 HIP_TRY(launch_guard_compact(h->d_guard_est, h->d_guard_status, h->d_guard_ind, h->batch, h->guard_threshold, h->guard_mode, h->stream));
-                if (h->guard_mode == 2) HIP_TRY(launch_quad_resolve(a, h->max_level_dim, h->d_guard_ind, h->stream));
+                if (h->guard_mode == 2) HIP_TRY(launch_kernel(plan_guard_resolve(q), a, h->stream, x));
             }
             else // a bit-exact kernel solved: status 0, no estimate
             {
@@ -927,14 +882,15 @@ extern "C"
         }
         // prefix reuse: the levels handed over are consumed; the state is there for the next factorization iff this one was the register-resident
         // wave kernel keeping its factor (every other kernel ignores both pointers and factorizes everything)
-        h->resume_armed = false;
-        h->resume_valid = a.resume_state != nullptr && write_factor && h->reg_type == 0 && std::strncmp(variant, "lqr_wave<", 9) == 0;
-        h->last_kernel   = variant;
-        h->last_consumer = consumer; // (what ran on the previous factor says nothing about this one)
-        h->factor_valid  = true;
+        h->resume_armed     = false;
+        h->resume_valid     = a.resume_state != nullptr && write_factor && h->reg_type == 0 && plan.register_resident;
+        h->last_kernel      = plan.name;
+        h->solve_reciprocal = plan.reciprocal_solve;
+        h->last_consumer    = consumer; // (what ran on the previous factor says nothing about this one)
+        h->factor_valid     = true;
         h->factor_epoch++;
-        if (solved) h->x_epoch = h->factor_epoch;
-        h->factor_in_hbm = write_factor || std::strstr(variant, "hbm") != nullptr;
+        if (plan.solves_x) h->x_epoch = h->factor_epoch;
+        h->factor_in_hbm = plan.factor_in_hbm;
         return LEXLS_OK;
     }
 
@@ -953,41 +909,28 @@ extern "C"
         if (int rc = need_factor(h, "lexls_lse_solve")) return rc;
         if (h->x_epoch == h->factor_epoch) return LEXLS_OK; // the factorization kernel left the basic solution in place
         HIP_TRY(hipSetDevice(h->device));
-        HIP_TRY(launch_solve_generic(h->args(), h->stream, std::strstr(h->last_kernel, "step-per-pivot") != nullptr, &h->last_consumer)); // (same x as that path's factorize_solve)
+        HIP_TRY(launch_solve_generic(h->args(), h->stream, h->solve_reciprocal, &h->last_consumer)); // (same x as that path's factorize_solve)
         h->x_epoch = h->factor_epoch;
         return LEXLS_OK;
     }
 
-    int lexls_lse_solve_least_norm(lexls_lse_t h)
+    /// the three least-norm solves: same preparation, one launcher each; d_x then holds a least-norm solution
+    static int solve_least_norm(lexls_lse_t h, const char *who, hipError_t (*launch)(const LseArgs &, hipStream_t, const char **))
     {
-        if (int rc = need_factor(h, "lexls_lse_solve_least_norm")) return rc;
+        if (int rc = need_factor(h, who)) return rc;
         HIP_TRY(hipSetDevice(h->device));
         if (!h->d_scratch) HIP_TRY(hipMalloc((void **)&h->d_scratch, 8 * (size_t)h->batch * 2 * h->nVar * h->nVar));
-        HIP_TRY(launch_leastnorm(h->args(), h->stream, &h->last_consumer));
-        h->x_epoch = 0; // d_x now holds a least-norm solution
+        HIP_TRY(launch(h->args(), h->stream, &h->last_consumer));
+        h->x_epoch = 0;
         return LEXLS_OK;
     }
-
-    int lexls_lse_solve_least_norm_2(lexls_lse_t h)
-    {
-        if (int rc = need_factor(h, "lexls_lse_solve_least_norm_2")) return rc;
-        HIP_TRY(hipSetDevice(h->device));
-        if (!h->d_scratch) HIP_TRY(hipMalloc((void **)&h->d_scratch, 8 * (size_t)h->batch * 2 * h->nVar * h->nVar));
-        HIP_TRY(launch_leastnorm2(h->args(), h->stream, &h->last_consumer));
-        h->x_epoch = 0; // d_x now holds a least-norm solution
-        return LEXLS_OK;
-    }
-
+    int lexls_lse_solve_least_norm(lexls_lse_t h) { return solve_least_norm(h, "lexls_lse_solve_least_norm", launch_leastnorm); }
+    int lexls_lse_solve_least_norm_2(lexls_lse_t h) { return solve_least_norm(h, "lexls_lse_solve_least_norm_2", launch_leastnorm2); }
     int lexls_lse_solve_least_norm_3(lexls_lse_t h)
     {
-        if (int rc = need_factor(h, "lexls_lse_solve_least_norm_3")) return rc;
-        if (h->reg_type != 1 && h->reg_type != 2 && h->reg_type != 8 && h->reg_type != 3 && h->reg_type != 7)
+        if (h && h->factor_valid && h->factor_in_hbm && h->reg_type != 1 && h->reg_type != 2 && h->reg_type != 8 && h->reg_type != 3 && h->reg_type != 7)
             return fail(LEXLS_ERR_INVALID, "lexls_lse_solve_least_norm_3: needs a factorization with a regularization type that accumulates the null-space basis (lexlse.h:1217-1221)");
-        HIP_TRY(hipSetDevice(h->device));
-        if (!h->d_scratch) HIP_TRY(hipMalloc((void **)&h->d_scratch, 8 * (size_t)h->batch * 2 * h->nVar * h->nVar));
-        HIP_TRY(launch_leastnorm3(h->args(), h->stream, &h->last_consumer));
-        h->x_epoch = 0; // d_x now holds a least-norm solution
-        return LEXLS_OK;
+        return solve_least_norm(h, "lexls_lse_solve_least_norm_3", launch_leastnorm3);
     }
 
     int lexls_lse_residual(lexls_lse_t h)
@@ -995,40 +938,6 @@ extern "C"
         if (int rc = need_factor(h, "lexls_lse_residual")) return rc;
         HIP_TRY(hipSetDevice(h->device));
         HIP_TRY(launch_residual(h->args(), h->stream, &h->last_consumer));
-        return LEXLS_OK;
-    }
-
-    int lexls_lse_sensitivity(lexls_lse_t h, const int32_t *h_obj_index, int32_t obj_index_all, double tolW, double tolC)
-    {
-        if (int rc = need_factor(h, "lexls_lse_sensitivity")) return rc;
-        HIP_TRY(hipSetDevice(h->device));
-        const int32_t *d_obj = nullptr;
-        if (h_obj_index)
-        {
-            HIP_TRY(hipMemcpyAsync(h->d_objidx, h_obj_index, 4 * (size_t)h->batch, hipMemcpyHostToDevice, h->stream));
-            if (!h->deferred_sync) HIP_TRY(hipStreamSynchronize(h->stream));
-            d_obj = h->d_objidx;
-        }
-        else if (obj_index_all < 0 || (uint32_t)obj_index_all >= h->nObj)
-        {
-            return fail(LEXLS_ERR_INVALID, "ObjIndex >= nObj");
-        }
-        HIP_TRY(launch_sensitivity(h->args(), d_obj, obj_index_all, tolW, tolC, h->stream, h->sens_scan, h->max_level_dim, false, &h->last_consumer));
-        return LEXLS_OK;
-    }
-
-    int lexls_lse_set_sensitivity_scan(lexls_lse_t h, int on)
-    {
-        CHECK_HANDLE(h);
-        h->sens_scan = on != 0;
-        return LEXLS_OK;
-    }
-
-    int lexls_lse_sensitivity_resident(lexls_lse_t h, double tolW, double tolC)
-    {
-        if (int rc = need_factor(h, "lexls_lse_sensitivity_resident")) return rc;
-        HIP_TRY(hipSetDevice(h->device));
-        HIP_TRY(launch_sensitivity(h->args(), h->d_objidx, 0, tolW, tolC, h->stream, h->sens_scan, h->max_level_dim, false, &h->last_consumer));
         return LEXLS_OK;
     }
 
@@ -1042,30 +951,35 @@ extern "C"
         return LEXLS_OK;
     }
 
-    int lexls_lse_sensitivity_collect(lexls_lse_t h, const int32_t *h_obj_index, int32_t obj_index_all, double tolW, double tolC)
+    /// the removal search / the wrong-sign set (collect); the objective of each problem from the host (h_obj_index), one for all
+    /// (obj_index_all), or the indices already on the device (resident)
+    static int sensitivity(lexls_lse_t h, const char *who, const int32_t *h_obj_index, int32_t obj_index_all, bool resident, double tolW, double tolC, bool collect)
     {
-        if (int rc = need_factor(h, "lexls_lse_sensitivity_collect")) return rc;
-        if (int rc = need_wrong_sign(h)) return rc;
-        const int32_t *d_obj = nullptr;
-        if (h_obj_index)
+        if (int rc = need_factor(h, who)) return rc;
+        if (collect)
+            if (int rc = need_wrong_sign(h)) return rc;
+        HIP_TRY(hipSetDevice(h->device));
+        const int32_t *d_obj = resident ? h->d_objidx : nullptr;
+        if (!resident && h_obj_index)
         {
             HIP_TRY(hipMemcpyAsync(h->d_objidx, h_obj_index, 4 * (size_t)h->batch, hipMemcpyHostToDevice, h->stream));
             if (!h->deferred_sync) HIP_TRY(hipStreamSynchronize(h->stream));
             d_obj = h->d_objidx;
         }
-        else if (obj_index_all < 0 || (uint32_t)obj_index_all >= h->nObj)
-        {
+        else if (!resident && (obj_index_all < 0 || (uint32_t)obj_index_all >= h->nObj))
             return fail(LEXLS_ERR_INVALID, "ObjIndex >= nObj");
-        }
-        HIP_TRY(launch_sensitivity(h->args(), d_obj, obj_index_all, tolW, tolC, h->stream, h->sens_scan, h->max_level_dim, true, &h->last_consumer));
+        HIP_TRY(launch_sensitivity(h->args(), d_obj, obj_index_all, tolW, tolC, h->stream, h->sens_scan, h->max_level_dim, collect, &h->last_consumer));
         return LEXLS_OK;
     }
+    int lexls_lse_sensitivity(lexls_lse_t h, const int32_t *h_obj_index, int32_t obj_index_all, double tolW, double tolC) { return sensitivity(h, "lexls_lse_sensitivity", h_obj_index, obj_index_all, false, tolW, tolC, false); }
+    int lexls_lse_sensitivity_resident(lexls_lse_t h, double tolW, double tolC) { return sensitivity(h, "lexls_lse_sensitivity_resident", nullptr, 0, true, tolW, tolC, false); }
+    int lexls_lse_sensitivity_collect(lexls_lse_t h, const int32_t *h_obj_index, int32_t obj_index_all, double tolW, double tolC) { return sensitivity(h, "lexls_lse_sensitivity_collect", h_obj_index, obj_index_all, false, tolW, tolC, true); }
+    int lexls_lse_sensitivity_collect_resident(lexls_lse_t h, double tolW, double tolC) { return sensitivity(h, "lexls_lse_sensitivity_collect_resident", nullptr, 0, true, tolW, tolC, true); }
 
-    int lexls_lse_sensitivity_collect_resident(lexls_lse_t h, double tolW, double tolC)
+    int lexls_lse_set_sensitivity_scan(lexls_lse_t h, int on)
     {
-        if (int rc = need_factor(h, "lexls_lse_sensitivity_collect_resident")) return rc;
-        if (int rc = need_wrong_sign(h)) return rc;
-        HIP_TRY(launch_sensitivity(h->args(), h->d_objidx, 0, tolW, tolC, h->stream, h->sens_scan, h->max_level_dim, true, &h->last_consumer));
+        CHECK_HANDLE(h);
+        h->sens_scan = on != 0;
         return LEXLS_OK;
     }
 
@@ -1082,7 +996,7 @@ extern "C"
         return LEXLS_OK;
     }
 
-    int lexls_internal_kernel_policy(lexls_lse_t h) { return h ? h->force_generic : 0; }
+    int lexls_internal_kernel_policy(lexls_lse_t h) { return h ? (int)h->policy : 0; }
 
     const double *lexls_internal_multipliers(lexls_lse_t h, int *swept)
     {
@@ -1306,11 +1220,11 @@ extern "C"
         if (h && h->resume_enabled) h->resume_armed = true;
     }
 
-    int lexls_lse_set_kernel_policy(lexls_lse_t h, int force_generic)
+    int lexls_lse_set_kernel_policy(lexls_lse_t h, int policy)
     {
         CHECK_HANDLE(h);
-        if (force_generic != h->force_generic) HIP_TRY(materialize_fused_gather(h)); // another kernel may read `in`: the rows named by the round must be there
-        h->force_generic = force_generic;
+        if (policy != (int)h->policy) HIP_TRY(materialize_fused_gather(h)); // another kernel may read `in`: the rows named by the round must be there
+        h->policy = static_cast<KernelPolicy>(policy);
         return LEXLS_OK;
     }
 }

@@ -1,0 +1,209 @@
+// Dynamic-LDS byte formulas of the LexLSE kernels: ONE function per formula, read by each kernel's launcher (its carve-up must match) and by
+// the dispatch plan (lexls_dispatch.h: "does the shape fit").  Plain host arithmetic, no device code: compiles with any C++17 compiler.
+#pragma once
+#include <cstddef>
+#include <cstdint>
+
+#ifndef QT_WPB
+#define QT_WPB 4 // wavefronts per workgroup of lqr_qtol (1 or 4)
+#endif
+#ifndef LEXLS_LARGE_TC
+#define LEXLS_LARGE_TC 8 // trailing columns per apply-workgroup of the large path
+#endif
+
+namespace lexls
+{
+    /// maximum dynamic LDS one workgroup may ask for on gfx950 (160 KiB per CU)
+    constexpr size_t kMaxLdsBytes = 160 * 1024;
+
+    /// odd leading dimension >= rows for the LDS image (conflict-free column-per-lane access)
+    inline uint32_t odd_ld(uint32_t rows) { return rows | 1u; }
+
+    constexpr int kQuadMaxObj = 8; // levels: one byte per level in a column's 64-bit image-index word
+    constexpr int kMfMaxObj   = 8;
+    constexpr int SWEEP_MD    = 16; // rows per level of the sensitivity sweep
+    constexpr size_t kGenericSharedBytes = 40; // sizeof(Shared) of lqr_generic.hip (asserted there)
+
+    // ---- lqr_quad (lqr_quad_impl.h) ----
+    /// exact worst case of sum_k (n+1-Fc_k) * rank_k over rank distributions with rank_k <= md
+    inline uint32_t quad_image_doubles(uint32_t n, uint32_t nObj, uint32_t md)
+    {
+        uint32_t fc = 0, total = 0;
+        for (uint32_t k = 0; k < nObj && fc < n; k++)
+        {
+            const uint32_t r = md < n - fc ? md : n - fc;
+            total += (n + 1 - fc) * r;
+            fc += r;
+        }
+        return (total + 1) & ~1u;
+    }
+
+    template <int NS>
+    inline size_t quad_group_bytes(uint32_t n, uint32_t nObj, uint32_t md)
+    {
+        return (8 * ((size_t)quad_image_doubles(n, nObj, md) + 16 * NS + 18) + 64 + 64 + 16 * kQuadMaxObj + 512 + 4 * kQuadMaxObj + 15) & ~(size_t)15;
+    }
+
+    /// dynamic LDS one wavefront (four problems) of the four-per-wavefront kernel asks for; 0 = the shape is not served
+    inline size_t quad_lds_bytes(uint32_t slots, uint32_t md, uint32_t nVar, uint32_t nObj)
+    {
+        if (nObj > (uint32_t)kQuadMaxObj || nVar + 1 > 16u * slots || nVar > 63u) return 0;
+        const size_t g = slots == 3 ? quad_group_bytes<3>(nVar, nObj, md) : quad_group_bytes<4>(nVar, nObj, md);
+        return 4 * g;
+    }
+
+    // ---- lqr_qtol (lqr_qtol_impl.h) ----
+    /// exact worst case of the triangular images: sum_k ((n+1-Fc_k) rank_k - rank_k (rank_k - 1) / 2) over rank distributions with rank_k <= md
+    inline uint32_t qtol_image_doubles(uint32_t n, uint32_t nObj, uint32_t md)
+    {
+        uint32_t fc = 0, total = 0;
+        for (uint32_t k = 0; k < nObj && fc < n; k++)
+        {
+            const uint32_t r = md < n - fc ? md : n - fc;
+            total += (n + 1 - fc) * r - r * (r - 1) / 2;
+            fc += r;
+        }
+        return (total + 1) & ~1u;
+    }
+
+    template <int NS, int MD>
+    inline size_t qtol_group_bytes(uint32_t n, uint32_t nObj)
+    {
+        // staging block: the level pieces (half the rows at a time) or the sixteen hand-off slots of the pivot steps, whichever is larger
+        const size_t stage = 8 * (size_t)(n + 1) * (MD / 2) > 16u * (8 * MD + 16) ? 8 * (size_t)(n + 1) * (MD / 2) : 16u * (8 * MD + 16);
+        const size_t raw   = 8 * ((size_t)qtol_image_doubles(n, nObj, MD) + 16 * NS + MD) + 64 + 64 + 16 * kQuadMaxObj + 8 * 16 * NS + stage;
+        // rounded up to an ODD multiple of 128 bytes: the four problems of a wavefront read the same relative addresses of their slices at
+        // the same time; slices half a bank row apart do not collide
+        return ((raw + 127) / 256) * 256 + 128;
+    }
+
+    /// dynamic LDS of one lqr_qtol workgroup (the ragged and estimating instantiations of a shape take what the uniform one takes)
+    template <int NS, int MD>
+    inline size_t qtol_lds_bytes(uint32_t n, uint32_t nObj) { return 4 * QT_WPB * qtol_group_bytes<NS, MD>(n, nObj); }
+
+    // ---- lqr_mfma (lqr_mfma_impl.h) ----
+    /// exact worst case of the reduced rows and their inverse maps: max over rank distributions (rank_k <= md, sum <= n) of
+    /// sum_k rank_k S_k + ceil(S_k / 8), S_k = n + 1 - Fc_k - rank_k (n <= 64)
+    inline uint32_t mfma_nd_doubles(uint32_t n, uint32_t nObj, uint32_t md)
+    {
+        // best[fc]: the most doubles the levels from the current one on can need when the current one starts at column fc
+        uint32_t best[65], next[65];
+        for (uint32_t fc = 0; fc <= n; fc++) next[fc] = 0;
+        for (uint32_t k = nObj; k--;)
+        {
+            for (uint32_t fc = 0; fc <= n; fc++)
+            {
+                uint32_t m = 0;
+                for (uint32_t r = 0; r <= md && fc + r <= n; r++)
+                {
+                    const uint32_t S = n + 1 - fc - r;
+                    const uint32_t v = r * S + (r ? (S + 7) / 8 : 0) + next[fc + r]; // the rows and their inverse map
+                    m                = v > m ? v : m;
+                }
+                best[fc] = m;
+            }
+            for (uint32_t fc = 0; fc <= n; fc++) next[fc] = best[fc];
+        }
+        return (next[0] + 1) & ~1u;
+    }
+
+    template <int MD>
+    inline size_t mfma_group_bytes(uint32_t n, uint32_t nObj)
+    {
+        const size_t pfb = 8u * MD * (size_t)(n + 1) > 128u * MD ? 8u * MD * (size_t)(n + 1) : 128u * MD;
+        const size_t raw = 8 * (size_t)mfma_nd_doubles(n, nObj, MD) + pfb + 8 * MD + 16 + 16 + 48 + 8 * (size_t)nObj + 8 * (size_t)(n + 1);
+        // (no padding against bank conflicts between the problems of a wavefront: the LDS serves a wave's 8- and 16-byte accesses in lane groups
+        // that never mix the two halves of the wavefront, MI355X_MICROARCH.md LDS table)
+        return (raw + 15) & ~(size_t)15;
+    }
+
+    /// dynamic LDS of one lqr_mfma workgroup with LP lanes per problem
+    template <int LP, int MD>
+    inline size_t mfma_lds_bytes(uint32_t n, uint32_t nObj) { return 4 * (64 / LP) * mfma_group_bytes<MD>(n, nObj); }
+
+    // ---- lqr_wave (lqr_small_impl.h) and the persistent LexLSI launch (lsi_fused_impl.h) ----
+    /// doubles of the compact level images: worst case of sum_k (n+1-Fc_k) * even(rank_k) over rank distributions with rank_k <= MD
+    template <int MD>
+    inline uint32_t wave_img_doubles(uint32_t n, uint32_t nObj)
+    {
+        return (n * n) / 2 + n + (n * MD) / 2 + nObj * (n + 1) + 64 + MD * MD; // (+ zeros behind the last image: a padded level reads MD columns of it)
+    }
+    template <int NC, int MD>
+    inline size_t wave_lds_bytes(uint32_t nObj, uint32_t img)
+    {
+        return 8 * ((size_t)NC * MD + 128 + img + 64) + 4 * (64 + 4 * (size_t)nObj) + 64 + 64 * (size_t)nObj + 128 + 16;
+    }
+
+    /// REG: what lqr_wave_body's regularization routines take of the LDS behind the plain carve-up of `lds` bytes (the sum is returned) and
+    /// where the host found room for the optional pieces (reg_cfg, as the body reads it).  One rule for every launch that runs the body —
+    /// lqr_wave_kernel and the persistent LexLSI launch (lsi_fused_impl.h):
+    /// the routines' vectors always; then their work matrix (order bounded by the type: the damped triangle alone for R / R_NO_Z /
+    /// RT_NO_Z, under n/2 + the largest level for TIKHONOV — tikhonov_2 is taken while Fc + rank <= n/2, tikhonov_1 has order n - Fc —,
+    /// n for TIKHONOV_2) and the null-space basis, each while LEXLS_REG_LDS_WAVES wavefronts (default 8: the occupancy is worth more than either, measured) still share a CU's LDS
+    /// (share: wave_reg_lds_share(), lqr_small.hip — read from the environment ONCE per process, so that the driver's gate and every
+    /// launcher place the same pieces)
+    template <int MD>
+    inline size_t wave_reg_lds_bytes(uint32_t n, uint32_t reg_type, size_t share, size_t lds, uint32_t &reg_cfg)
+    {
+        const bool cg = reg_type == 2 || reg_type == 6;
+        lds           = ((lds + 15) & ~(size_t)15) + 16 + 8 * (2 * (size_t)n + 8 + (cg ? 10 * (size_t)n : 0));
+        uint32_t order = 0;
+        switch (reg_type)
+        {
+        case 3: case 4: case 5: order = MD; break;
+        case 1: order = n / 2 + MD + 1 < n ? n / 2 + MD + 1 : n; break;
+        case 8: order = n; break;
+        default: break;
+        }
+        if (order > 255) order = 0;
+        reg_cfg = 0;
+        if (order && lds + 8 * (size_t)order * order <= share)
+        {
+            reg_cfg |= order;
+            lds += 8 * (size_t)order * order;
+        }
+        const bool basis = reg_type == 1 || reg_type == 2 || reg_type == 3 || reg_type == 8;
+        if (basis && lds + 8 * (size_t)(n | 1u) * (n + 1) <= share)
+        {
+            reg_cfg |= 0x100u;
+            lds += 8 * (size_t)(n | 1u) * (n + 1);
+        }
+        return lds;
+    }
+
+    // ---- the sensitivity sweep (lexls_sweep_impl.h) ----
+    /// dynamic LDS of one sweep: staged factor, Householder scalars, multipliers / right-hand sides / fixed-variable multipliers of 8 objectives, types
+    inline size_t sweep_lds_bytes(uint32_t nVar, uint32_t cap)
+    {
+        return 8 * ((size_t)(cap | 1u) * (nVar + 1) + cap + 8 * ((size_t)cap + 2 * nVar)) + (((size_t)cap + nVar + 15) & ~(size_t)15);
+    }
+    /// the shapes the one-wavefront-per-problem sweep serves (level_dim: the largest level of the batch; 0 = unknown)
+    inline bool sweep_shape_serves(uint32_t nVar, uint32_t nObj, uint32_t cap, uint32_t reg_type, uint32_t level_dim)
+    {
+        return reg_type != 7 && level_dim > 0 && level_dim <= (uint32_t)SWEEP_MD && nObj <= 8 && nVar <= 64 && sweep_lds_bytes(nVar, cap) <= 64 * 1024;
+    }
+
+    // ---- lqr_generic (lqr_generic.hip) ----
+    /// NT threads; ldsmat: the problem staged in LDS with leading dimension ldp (else it stays in HBM)
+    inline size_t generic_lds_bytes(uint32_t ldp, uint32_t nVar, uint32_t nObj, int NT, bool ldsmat)
+    {
+        size_t b = 8 * ((ldsmat ? (size_t)ldp * (nVar + 1) : 0) + 2 * (size_t)nVar + NT);
+        b += kGenericSharedBytes + 4 * ((size_t)NT + nVar + 3 * (size_t)nObj) + 16;
+        return b;
+    }
+
+    // ---- lqr_large (lqr_large.hip) ----
+    /// dynamic LDS of the three kernels that stage in LDS, for the largest level dimension of the batch
+    struct LargeLds
+    {
+        size_t piv, app, trsm;
+    };
+    inline LargeLds large_lds_bytes(uint32_t n, uint32_t maxdim)
+    {
+        LargeLds l;
+        l.piv  = 8 * ((size_t)((maxdim + 1) & ~1u) + 1024 + 16) + 4 * 1024;
+        l.app  = 8 * ((size_t)LEXLS_LARGE_TC * (maxdim | 1u) + maxdim + LEXLS_LARGE_TC + 2);
+        l.trsm = 8 * (size_t)((n < maxdim) ? n : maxdim) * 65;
+        return l;
+    }
+} // namespace lexls

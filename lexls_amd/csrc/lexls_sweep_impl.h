@@ -72,7 +72,7 @@ namespace lexls
             return v;
         }
 
-        constexpr int SWEEP_MD = 16, SWEEP_T = 2; // rows per level; objective registers per DPP row (4 rows x 2 = 8 objectives)
+        constexpr int SWEEP_T = 2; // (SWEEP_MD, lexls_lds.h: rows per level;) objective registers per DPP row (4 rows x 2 = 8 objectives)
 
         // EMIT (multipliers_sweep_kernel, lexls_lse_multipliers): the sweep of every objective and nothing else — column L of emit[b] (nObj columns of
         // nVar + cap, [lambda_fixed; lambda]) receives what the results block below writes for the objective the search stopped at, for every L;
@@ -487,12 +487,6 @@ namespace lexls
         __global__ __launch_bounds__(64) void multipliers_sweep_kernel(LseArgs a, double *out)
         {
             sensitivity_sweep_body<MD, true>(a, nullptr, 0, 0.0, 0.0, 1, blockIdx.x, out);
-        }
-
-        /// dynamic LDS of one sweep: staged factor, Householder scalars, multipliers / right-hand sides / fixed-variable multipliers of 8 objectives, types
-        inline size_t sweep_lds_bytes(const LseArgs &a)
-        {
-            return 8 * ((size_t)(a.cap | 1u) * (a.nVar + 1) + a.cap + 8 * ((size_t)a.cap + 2 * a.nVar)) + (((size_t)a.cap + a.nVar + 15) & ~(size_t)15);
         }
     } // namespace
 } // namespace lexls

@@ -1785,17 +1785,12 @@ namespace lexls
             return hipFuncSetAttribute(reinterpret_cast<const void *>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes);
         }
 
-        size_t lqr_lds_bytes(const LseArgs &a, int NT, bool ldsmat)
-        {
-            size_t b = 8 * ((ldsmat ? (size_t)a.ldp * (a.nVar + 1) : 0) + 2 * (size_t)a.nVar + NT);
-            b += sizeof(Shared) + 4 * ((size_t)NT + a.nVar + 3 * (size_t)a.nObj) + 16;
-            return b;
-        }
+        static_assert(sizeof(Shared) == kGenericSharedBytes, "generic_lds_bytes (lexls_lds.h) counts the Shared block");
 
         template <int NT, bool LDSMAT>
         hipError_t launch_lqr_t(const LseArgs &a, bool write_factor, bool do_solve, hipStream_t s)
         {
-            const size_t lds = lqr_lds_bytes(a, NT, LDSMAT);
+            const size_t lds = generic_lds_bytes(a.ldp, a.nVar, a.nObj, NT, LDSMAT);
             hipError_t e     = set_lds(lqr_generic_kernel<NT, LDSMAT>, lds);
             if (e != hipSuccess) return e;
             hipLaunchKernelGGL((lqr_generic_kernel<NT, LDSMAT>), dim3(a.batch), dim3(NT), lds, s, a, write_factor ? 1 : 0, do_solve ? 1 : 0);
@@ -1803,36 +1798,17 @@ namespace lexls
         }
     } // namespace
 
-    bool generic_fits_lds(const LseArgs &a0, uint32_t max_rows)
+    hipError_t launch_lqr_generic(LseArgs a, uint32_t max_rows, KernelId id, bool write_factor, bool do_solve, hipStream_t s)
     {
-        LseArgs a = a0;
-        a.ldp     = odd_ld(max_rows);
-        return lqr_lds_bytes(a, 1024, true) <= kMaxLdsBytes;
-    }
-
-    hipError_t launch_lqr_generic(LseArgs a, uint32_t max_rows, bool write_factor, bool do_solve, hipStream_t s, const char **variant)
-    {
-        a.ldp             = odd_ld(max_rows);
-        const uint32_t w  = (a.nVar + 1 > max_rows) ? a.nVar + 1 : max_rows;
-        const bool fits64 = lqr_lds_bytes(a, 64, true) <= kMaxLdsBytes;
-        if (w <= 64 && fits64)
+        a.ldp = odd_ld(max_rows);
+        switch (id)
         {
-            *variant = "lqr_generic<64,lds>";
-            return launch_lqr_t<64, true>(a, write_factor, do_solve, s);
+        case KernelId::generic_64_lds: return launch_lqr_t<64, true>(a, write_factor, do_solve, s);
+        case KernelId::generic_256_lds: return launch_lqr_t<256, true>(a, write_factor, do_solve, s);
+        case KernelId::generic_1024_lds: return launch_lqr_t<1024, true>(a, write_factor, do_solve, s);
+        case KernelId::generic_1024_hbm: return launch_lqr_t<1024, false>(a, true, do_solve, s);
+        default: return hipErrorInvalidValue; // (none: nVar too large for the norm table)
         }
-        if (w <= 512 && lqr_lds_bytes(a, 256, true) <= kMaxLdsBytes)
-        {
-            *variant = "lqr_generic<256,lds>";
-            return launch_lqr_t<256, true>(a, write_factor, do_solve, s);
-        }
-        if (lqr_lds_bytes(a, 1024, true) <= kMaxLdsBytes)
-        {
-            *variant = "lqr_generic<1024,lds>";
-            return launch_lqr_t<1024, true>(a, write_factor, do_solve, s);
-        }
-        if (lqr_lds_bytes(a, 1024, false) > kMaxLdsBytes) return hipErrorInvalidValue; // nVar too large for the norm table
-        *variant = "lqr_generic<1024,hbm>";
-        return launch_lqr_t<1024, false>(a, true, do_solve, s);
     }
 
     hipError_t launch_solve_generic(const LseArgs &a, hipStream_t s, bool reciprocal_diagonal, const char **variant)
@@ -1921,7 +1897,7 @@ namespace lexls
     /// the factor staged in LDS — what a lock-step LSI stage asks for.  max_level_dim comes from the caller (0 = unknown: not taken)
     bool sensitivity_sweep_serves(const LseArgs &a, uint32_t sweep_level_dim_hint)
     {
-        return a.reg_type != 7 && sweep_level_dim_hint > 0 && sweep_level_dim_hint <= (uint32_t)SWEEP_MD && a.nObj <= 8 && a.nVar <= 64 && sweep_lds_bytes(a) <= 64 * 1024 &&
+        return sweep_shape_serves(a.nVar, a.nObj, a.cap, a.reg_type, sweep_level_dim_hint) &&
                a.batch <= 4u * (uint32_t)cus_of_current_device() && !std::getenv("LEXLS_SENS_NO_SWEEP");
     }
 
@@ -1935,7 +1911,7 @@ namespace lexls
         // the 20 KB per workgroup would cost the wavefronts in flight that hide the chains instead (4096 problems: 0.090 -> 0.126 ms)
         const size_t lds_staged = lds + 8 * ((size_t)(a.cap | 1u) * (a.nVar + 1) + a.cap) + (((size_t)a.cap + a.nVar + 15) & ~(size_t)15);
         const int cus           = cus_of_current_device();
-        const size_t lds_sweep  = sweep_lds_bytes(a);
+        const size_t lds_sweep  = sweep_lds_bytes(a.nVar, a.cap);
         if (sensitivity_sweep_serves(a, sweep_level_dim_hint))
         {
             static_assert(SWEEP_MD == 16, "the names below spell the sweep's level capacity out");
@@ -1974,8 +1950,7 @@ namespace lexls
     /// whatever the batch size: there is no per-objective launch to weigh it against
     bool multipliers_sweep_serves(const LseArgs &a, uint32_t sweep_level_dim_hint)
     {
-        return a.reg_type != 7 && sweep_level_dim_hint > 0 && sweep_level_dim_hint <= (uint32_t)SWEEP_MD && a.nObj <= 8 && a.nVar <= 64 &&
-               sweep_lds_bytes(a) <= 64 * 1024 && !std::getenv("LEXLS_SENS_NO_SWEEP");
+        return sweep_shape_serves(a.nVar, a.nObj, a.cap, a.reg_type, sweep_level_dim_hint) && !std::getenv("LEXLS_SENS_NO_SWEEP");
     }
 
     size_t multipliers_scratch_bytes(const LseArgs &a)
@@ -1992,9 +1967,9 @@ namespace lexls
             if (swept) *swept = true;
             if (variant) *variant = sweep_level_dim_hint <= 12 ? "multipliers_sweep<12>" : "multipliers_sweep<16>";
             if (sweep_level_dim_hint <= 12)
-                hipLaunchKernelGGL(multipliers_sweep_kernel<12>, dim3(a.batch), dim3(64), sweep_lds_bytes(a), s, a, d_out);
+                hipLaunchKernelGGL(multipliers_sweep_kernel<12>, dim3(a.batch), dim3(64), sweep_lds_bytes(a.nVar, a.cap), s, a, d_out);
             else
-                hipLaunchKernelGGL(multipliers_sweep_kernel<SWEEP_MD>, dim3(a.batch), dim3(64), sweep_lds_bytes(a), s, a, d_out);
+                hipLaunchKernelGGL(multipliers_sweep_kernel<SWEEP_MD>, dim3(a.batch), dim3(64), sweep_lds_bytes(a.nVar, a.cap), s, a, d_out);
             return hipGetLastError();
         }
         if (swept) *swept = false;

@@ -31,10 +31,7 @@ namespace lexls
 
     namespace
     {
-#ifndef LEXLS_LARGE_TC
-#define LEXLS_LARGE_TC 8
-#endif
-        constexpr int TC = LEXLS_LARGE_TC; // trailing columns per apply-workgroup
+        constexpr int TC = LEXLS_LARGE_TC; // trailing columns per apply-workgroup (lexls_lds.h)
         constexpr int TJ = 8;  // trailing columns per lane in the Gauss update
 
         __device__ __forceinline__ bool skipped(const LseArgs &a, uint32_t b) { return a.skip && a.skip[b]; }
@@ -1704,30 +1701,6 @@ namespace lexls
             }
         }
     } // namespace
-
-    namespace
-    {
-        /// dynamic LDS of the three kernels that stage in LDS, for the largest level dimension of the batch (ONE formula for the
-        /// dispatcher's question "does it fit" and for the launch)
-        struct LargeLds
-        {
-            size_t piv, app, trsm;
-        };
-        inline LargeLds large_lds_bytes(uint32_t n, uint32_t maxdim)
-        {
-            LargeLds l;
-            l.piv  = 8 * ((size_t)((maxdim + 1) & ~1u) + 1024 + 16) + 4 * 1024;
-            l.app  = 8 * ((size_t)TC * (maxdim | 1u) + maxdim + TC + 2);
-            l.trsm = 8 * (size_t)((n < maxdim) ? n : maxdim) * 65;
-            return l;
-        }
-    } // namespace
-
-    bool large_kernel_supports(const LseArgs &a, uint32_t max_level_dim, bool has_fixed)
-    {
-        const LargeLds l = large_lds_bytes(a.nVar, max_level_dim);
-        return !has_fixed && l.trsm <= kMaxLdsBytes && l.piv <= kMaxLdsBytes && l.app <= kMaxLdsBytes && max_level_dim < 65536 && a.nObj < 65536;
-    }
 
     size_t large_state_bytes(uint32_t batch) { return sizeof(LargeState) * (size_t)batch; }
 

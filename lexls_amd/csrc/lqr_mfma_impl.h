@@ -146,7 +146,6 @@ namespace lexls
         }
 
         constexpr double kMfSentinel = -1.0e300; // below every down-dated norm; stays there under further down-dates
-        constexpr int kMfMaxObj      = 8;
 
         // per-level phase stamps of the diagnostic build (-DLEXLS_WAVE_STAMPS): lambda[11 + 4 k + {0 Gauss step, 1 level start, 2 Householder, 3 level end}]
 #ifdef LEXLS_WAVE_STAMPS
@@ -901,48 +900,13 @@ namespace lexls
             }
         }
 
-        /// exact worst case of the reduced rows and their inverse maps: max over rank distributions (rank_k <= md, sum <= n) of
-        /// sum_k rank_k S_k + ceil(S_k / 8), S_k = n + 1 - Fc_k - rank_k
-        inline uint32_t mfma_nd_doubles(uint32_t n, uint32_t nObj, uint32_t md)
-        {
-            // best[fc]: the most doubles the levels from the current one on can need when the current one starts at column fc
-            uint32_t best[65], next[65];
-            for (uint32_t fc = 0; fc <= n; fc++) next[fc] = 0;
-            for (uint32_t k = nObj; k--;)
-            {
-                for (uint32_t fc = 0; fc <= n; fc++)
-                {
-                    uint32_t m = 0;
-                    for (uint32_t r = 0; r <= md && fc + r <= n; r++)
-                    {
-                        const uint32_t S = n + 1 - fc - r;
-                        const uint32_t v = r * S + (r ? (S + 7) / 8 : 0) + next[fc + r]; // the rows and their inverse map
-                        m                = v > m ? v : m;
-                    }
-                    best[fc] = m;
-                }
-                for (uint32_t fc = 0; fc <= n; fc++) next[fc] = best[fc];
-            }
-            return (next[0] + 1) & ~1u;
-        }
-
-        template <int MD>
-        inline size_t mfma_group_bytes(uint32_t n, uint32_t nObj)
-        {
-            const size_t pfb = 8u * MD * (size_t)(n + 1) > 128u * MD ? 8u * MD * (size_t)(n + 1) : 128u * MD;
-            const size_t raw = 8 * (size_t)mfma_nd_doubles(n, nObj, MD) + pfb + 8 * MD + 16 + 16 + 48 + 8 * (size_t)nObj + 8 * (size_t)(n + 1);
-            // (no padding against bank conflicts between the problems of a wavefront: the LDS serves a wave's 8- and 16-byte accesses in lane groups
-            // that never mix the two halves of the wavefront, MI355X_MICROARCH.md LDS table)
-            return (raw + 15) & ~(size_t)15;
-        }
-
         template <int LP, int MD, int NV>
         hipError_t launch_mfma_t(const LseArgs &a, hipStream_t s)
         {
             constexpr uint32_t G = 64 / LP;
             const uint32_t nd    = mfma_nd_doubles(a.nVar, a.nObj, MD);
             const size_t gbytes  = mfma_group_bytes<MD>(a.nVar, a.nObj);
-            const size_t lds     = 4 * G * gbytes;
+            const size_t lds     = mfma_lds_bytes<LP, MD>(a.nVar, a.nObj);
             // (two / four wavefronts per SIMD are the point of the mapping: the workgroups of a CU must fit its LDS together)
             if (lds * (LP == 64 ? 4 : (LP == 32 ? 2 : 1)) > kMaxLdsBytes || a.nObj > (uint32_t)kMfMaxObj || a.nVar + 1 > 48u || a.nVar < 1u || (NV && a.nVar != (uint32_t)NV)) return hipErrorInvalidValue;
             if (a.uniform_dim != (uint32_t)MD || (a.cap & 1u) || (reinterpret_cast<uintptr_t>(a.in) & 15u) || a.nfixed || a.reg_type != 0) return hipErrorInvalidValue;
@@ -968,5 +932,4 @@ namespace lexls
 } // namespace lexls
 
 #define LEXLS_MFMA_INSTANCE(NAME, LP, MD, NV) \
-    namespace lexls { hipError_t NAME(const LseArgs &a, hipStream_t s) { return launch_mfma_t<LP, MD, NV>(a, s); } \
-                      size_t NAME##_lds(uint32_t nVar, uint32_t nObj) { return 4 * (64 / LP) * mfma_group_bytes<MD>(nVar, nObj); } }
+    namespace lexls { hipError_t NAME(const LseArgs &a, hipStream_t s) { return launch_mfma_t<LP, MD, NV>(a, s); } }

@@ -28,9 +28,6 @@
 
 #include <cstdlib>
 
-#ifndef QT_WPB
-#define QT_WPB 4 // wavefronts per workgroup of lqr_qtol (1 or 4)
-#endif
 
 namespace lexls
 {
@@ -268,30 +265,6 @@ namespace lexls
 #include "lqr_qtol_body.inc"
         }
 
-        /// exact worst case of the triangular images: sum_k ((n+1-Fc_k) rank_k - rank_k (rank_k - 1) / 2) over rank distributions with rank_k <= md
-        inline uint32_t qtol_image_doubles(uint32_t n, uint32_t nObj, uint32_t md)
-        {
-            uint32_t fc = 0, total = 0;
-            for (uint32_t k = 0; k < nObj && fc < n; k++)
-            {
-                const uint32_t r = md < n - fc ? md : n - fc;
-                total += (n + 1 - fc) * r - r * (r - 1) / 2;
-                fc += r;
-            }
-            return (total + 1) & ~1u;
-        }
-
-        template <int NS, int MD>
-        inline size_t qtol_group_bytes(uint32_t n, uint32_t nObj)
-        {
-            // staging block: the level pieces (half the rows at a time) or the sixteen hand-off slots of the pivot steps, whichever is larger
-            const size_t stage = 8 * (size_t)(n + 1) * (MD / 2) > 16u * (8 * MD + 16) ? 8 * (size_t)(n + 1) * (MD / 2) : 16u * (8 * MD + 16);
-            const size_t raw   = 8 * ((size_t)qtol_image_doubles(n, nObj, MD) + 16 * NS + MD) + 64 + 64 + 16 * kQuadMaxObj + 8 * 16 * NS + stage;
-            // rounded up to an ODD multiple of 128 bytes: the four problems of a wavefront read the same relative addresses of their slices at
-            // the same time; slices half a bank row apart do not collide
-            return ((raw + 127) / 256) * 256 + 128;
-        }
-
         template <int NS, int MD, int SIG, int NV, bool EST = false, bool RAG = false>
         hipError_t launch_qtol_t(const LseArgs &a, hipStream_t s, double *est_out = nullptr, uint32_t *count_reset = nullptr)
         {
@@ -305,7 +278,7 @@ namespace lexls
                 kfn = reinterpret_cast<const void *>(lqr_qtol_kernel<NS, MD, SIG, NV>);
             const uint32_t img  = qtol_image_doubles(a.nVar, a.nObj, MD);
             const size_t gbytes = qtol_group_bytes<NS, MD>(a.nVar, a.nObj);
-            const size_t lds    = 4 * QT_WPB * gbytes;
+            const size_t lds    = qtol_lds_bytes<NS, MD>(a.nVar, a.nObj);
             if (lds > kMaxLdsBytes || a.nObj > (uint32_t)kQuadMaxObj || a.nVar + 1 + SIG > 16u * NS || a.nVar > 63u || (NV && a.nVar != (uint32_t)NV)) return hipErrorInvalidValue;
             if ((reinterpret_cast<uintptr_t>(a.in) & (RAG ? 7u : 15u)) || a.nfixed || a.reg_type != 0) return hipErrorInvalidValue; // (RAG: its 16-byte loads are 8-byte aligned anyway)
             if (RAG ? (a.cap < 2u || !a.dims) : (a.uniform_dim != (uint32_t)MD || (a.cap & 1u))) return hipErrorInvalidValue; // (RAG: the caller vouches for dims <= MD; the kernel clamps)
@@ -335,8 +308,7 @@ namespace lexls
 } // namespace lexls
 
 #define LEXLS_QTOL_INSTANCE(NAME, NS, MD, SIG, NV) \
-    namespace lexls { hipError_t NAME(const LseArgs &a, hipStream_t s) { return launch_qtol_t<NS, MD, SIG, NV>(a, s); } \
-                      size_t NAME##_lds(uint32_t nVar, uint32_t nObj) { return 4 * QT_WPB * qtol_group_bytes<NS, MD>(nVar, nObj); } }
+    namespace lexls { hipError_t NAME(const LseArgs &a, hipStream_t s) { return launch_qtol_t<NS, MD, SIG, NV>(a, s); } }
 // the accuracy guard's instantiation: est_out (batch doubles) receives the estimate, *count_reset is cleared
 #define LEXLS_QTOL_INSTANCE_EST(NAME, NS, MD, SIG, NV) \
     namespace lexls { hipError_t NAME(const LseArgs &a, hipStream_t s, double *est_out, uint32_t *count_reset) { return launch_qtol_t<NS, MD, SIG, NV, true>(a, s, est_out, count_reset); } }

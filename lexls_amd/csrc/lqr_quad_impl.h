@@ -35,7 +35,6 @@ namespace lexls
             asm volatile("" ::: "memory");
         }
 
-        constexpr int kQuadMaxObj = 8; // levels: one byte per level in a column's 64-bit image-index word
 
         /// SIG: position P sits in slot (P + SIG) / 16, lane (P + SIG) % 16.  With SIG = 16 NS - (n + 1) the right-hand side is the last lane of
         /// the last slot, so the live columns of a level fill the UPPER slots completely and the lower ones drop out of the Householder
@@ -842,25 +841,6 @@ namespace lexls
 
     namespace
     {
-        /// exact worst case of sum_k (n+1-Fc_k) * rank_k over rank distributions with rank_k <= md
-        inline uint32_t quad_image_doubles(uint32_t n, uint32_t nObj, uint32_t md)
-        {
-            uint32_t fc = 0, total = 0;
-            for (uint32_t k = 0; k < nObj && fc < n; k++)
-            {
-                const uint32_t r = md < n - fc ? md : n - fc;
-                total += (n + 1 - fc) * r;
-                fc += r;
-            }
-            return (total + 1) & ~1u;
-        }
-
-        template <int NS>
-        inline size_t quad_group_bytes(uint32_t n, uint32_t nObj, uint32_t md)
-        {
-            return (8 * ((size_t)quad_image_doubles(n, nObj, md) + 16 * NS + 18) + 64 + 64 + 16 * kQuadMaxObj + 512 + 4 * kQuadMaxObj + 15) & ~(size_t)15;
-        }
-
         template <int NS, int MD, bool WF, int SIG, bool FIX = false, bool IND = false>
         hipError_t launch_quad_t(const LseArgs &a, hipStream_t s, const uint32_t *ind = nullptr)
         {

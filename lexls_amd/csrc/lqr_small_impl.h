@@ -992,65 +992,13 @@ namespace lexls
 
     namespace
     {
-        /// doubles of the compact level images: worst case of sum_k (n+1-Fc_k) * even(rank_k) over rank distributions with rank_k <= MD
-        template <int MD>
-        inline uint32_t wave_img_doubles(const LseArgs &a)
-        {
-            const uint32_t n = a.nVar;
-            return (n * n) / 2 + n + (n * MD) / 2 + a.nObj * (n + 1) + 64 + MD * MD; // (+ zeros behind the last image: a padded level reads MD columns of it)
-        }
-        template <int NC, int MD>
-        inline size_t wave_lds_bytes(const LseArgs &a, uint32_t img)
-        {
-            return 8 * ((size_t)NC * MD + 128 + img + 64) + 4 * (64 + 4 * (size_t)a.nObj) + 64 + 64 * (size_t)a.nObj + 128 + 16;
-        }
-
-        /// REG: what lqr_wave_body's regularization routines take of the LDS behind the plain carve-up of `lds` bytes (the sum is returned) and
-        /// where the host found room for the optional pieces (reg_cfg, as the body reads it).  One rule for every launch that runs the body —
-        /// lqr_wave_kernel and the persistent LexLSI launch (lsi_fused_impl.h):
-        /// the routines' vectors always; then their work matrix (order bounded by the type: the damped triangle alone for R / R_NO_Z /
-        /// RT_NO_Z, under n/2 + the largest level for TIKHONOV — tikhonov_2 is taken while Fc + rank <= n/2, tikhonov_1 has order n - Fc —,
-        /// n for TIKHONOV_2) and the null-space basis, each while LEXLS_REG_LDS_WAVES wavefronts (default 8: the occupancy is worth more than either, measured) still share a CU's LDS
-        /// (the share itself: wave_reg_lds_share(), lqr_small.hip — read from the environment ONCE per process, so that the driver's gate and every
-        /// launcher place the same pieces)
-        template <int MD>
-        inline size_t wave_reg_lds_bytes(const LseArgs &a, size_t lds, uint32_t &reg_cfg)
-        {
-            const uint32_t n   = a.nVar;
-            const size_t share = wave_reg_lds_share();
-            const bool cg = a.reg_type == 2 || a.reg_type == 6;
-            lds           = ((lds + 15) & ~(size_t)15) + 16 + 8 * (2 * (size_t)n + 8 + (cg ? 10 * (size_t)n : 0));
-            uint32_t order = 0;
-            switch (a.reg_type)
-            {
-            case 3: case 4: case 5: order = MD; break;
-            case 1: order = n / 2 + MD + 1 < n ? n / 2 + MD + 1 : n; break;
-            case 8: order = n; break;
-            default: break;
-            }
-            if (order > 255) order = 0;
-            reg_cfg = 0;
-            if (order && lds + 8 * (size_t)order * order <= share)
-            {
-                reg_cfg |= order;
-                lds += 8 * (size_t)order * order;
-            }
-            const bool basis = a.reg_type == 1 || a.reg_type == 2 || a.reg_type == 3 || a.reg_type == 8;
-            if (basis && lds + 8 * (size_t)(n | 1u) * (n + 1) <= share)
-            {
-                reg_cfg |= 0x100u;
-                lds += 8 * (size_t)(n | 1u) * (n + 1);
-            }
-            return lds;
-        }
-
         template <int NC, int MD, bool EXACT, bool WF, bool REG = false>
         hipError_t launch_wave_t2(const LseArgs &a, hipStream_t s)
         {
-            const uint32_t img = wave_img_doubles<MD>(a);
-            size_t lds         = wave_lds_bytes<NC, MD>(a, img);
+            const uint32_t img = wave_img_doubles<MD>(a.nVar, a.nObj);
+            size_t lds         = wave_lds_bytes<NC, MD>(a.nObj, img);
             uint32_t reg_cfg   = 0;
-            if constexpr (REG) lds = wave_reg_lds_bytes<MD>(a, lds, reg_cfg);
+            if constexpr (REG) lds = wave_reg_lds_bytes<MD>(a.nVar, a.reg_type, wave_reg_lds_share(), lds, reg_cfg);
             if (lds > kMaxLdsBytes) return hipErrorInvalidValue;
             if (lds > 64 * 1024)
             {
