@@ -234,6 +234,12 @@ const char *lexls_lse_last_kernel(lexls_lse_t h);
  * "leastnorm_2<64>", ...; "" after a factorization until one of them launches (a lexls_lse_solve the factorization kernel had answered
  * already launches nothing).  Written on the host by the launchers: diagnostics, no kernel and no launch depends on it */
 int lexls_lse_last_consumer_kernel(lexls_lse_t h, char *buf, size_t len);
+/* lqr_large<step-per-pivot,mfma> runs the pivots of a level of a SINGLE problem inside one launch (lqr_large.hip, fast_level_persist); a launch
+ * whose bounded hand-offs ran out raises its abort flag, commits nothing, and the host redoes the level with a launch per pivot.  Of the last
+ * factorization: *in_launch = levels the one-launch form committed, *redone = levels it gave up (both 0 on every other kernel, for a batch, under
+ * LEXLS_LARGE_PERSIST=0 and where no form of the launch fits the device; LEXLS_LARGE_PERSIST=2 gives up on every level it is tried on).  Read on the host from
+ * the flag the launcher reads anyway: diagnostics, no kernel and no launch depends on it */
+int lexls_lse_last_large_levels(lexls_lse_t h, uint32_t *in_launch, uint32_t *redone);
 /* Kernel policy — which CONTRACT a solve is held to, and which kernel family serves it.
  *   Contracts: (B) bit-identical to the arithmetic contract of oracle/lexlse_oracle.h (pivots, ranks, Householder scalars, factor, x, multipliers);
  *              (T) BASELINE north_star's: column permutation, ranks and first columns exact, x (and factor MAGNITUDES) within 1e-10

@@ -54,6 +54,7 @@ struct lexls_lse_s
     const char *last_kernel;
     bool solve_reciprocal = false; // the plan of the last factorization: a later lexls_lse_solve may use the reciprocal diagonal
     const char *last_consumer = ""; // lexls_lse_last_consumer_kernel: the variant the last post-factorization launcher took
+    uint32_t large_levels[2] = {0, 0}; // lexls_lse_last_large_levels: levels of the last factorization the one-launch form committed / gave up
 
     double *d_in_owned;
     bool deferred_sync;       // lexls_lse_set_deferred_sync: copies are enqueued, not waited for
@@ -841,6 +842,7 @@ extern "C"
         const char *consumer  = "";
         LaunchExtras x;
         x.est = h->d_guard_est, x.ind = h->d_guard_ind;
+        h->large_levels[0] = h->large_levels[1] = 0u;
         if (plan.id == KernelId::large_multi)
         {
             if (!h->d_large_state) HIP_TRY(hipMalloc(&h->d_large_state, large_state_bytes(h->batch)));
@@ -859,7 +861,7 @@ extern "C"
                 HIP_TRY(hipMalloc(&h->d_large_ws, need));
                 h->large_ws_bytes = need;
             }
-            HIP_TRY(launch_lqr_large_fast(a, h->level_max.data(), h->max_rows, h->d_large_ws, h->stream));
+            HIP_TRY(launch_lqr_large_fast(a, h->level_max.data(), h->max_rows, h->d_large_ws, h->stream, h->large_levels));
         }
         else if (plan.id == KernelId::none || plan.id >= KernelId::generic_64_lds)
             HIP_TRY(launch_lqr_generic(a, h->max_rows, plan.id, write_factor, plan.solves_x, h->stream));
@@ -1130,6 +1132,15 @@ extern "C"
         CHECK_HANDLE(h);
         if (!buf || len == 0) return fail(LEXLS_ERR_INVALID, "lexls_lse_last_consumer_kernel: no buffer");
         std::snprintf(buf, len, "%s", h->last_consumer);
+        return LEXLS_OK;
+    }
+
+    int lexls_lse_last_large_levels(lexls_lse_t h, uint32_t *in_launch, uint32_t *redone)
+    {
+        CHECK_HANDLE(h);
+        if (!in_launch || !redone) return fail(LEXLS_ERR_INVALID, "lexls_lse_last_large_levels: no output");
+        *in_launch = h->large_levels[0];
+        *redone    = h->large_levels[1];
         return LEXLS_OK;
     }
 

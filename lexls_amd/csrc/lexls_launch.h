@@ -57,5 +57,7 @@ namespace lexls
     size_t large_state_bytes(uint32_t batch);
     hipError_t launch_lqr_large(const LseArgs &a, const uint32_t *h_level_max, uint32_t h_rows_max, void *d_state, double *d_norms, hipStream_t s);
     size_t large_fast_workspace_bytes(uint32_t batch, uint32_t n, uint32_t cap, uint32_t maxdim);
-    hipError_t launch_lqr_large_fast(const LseArgs &a, const uint32_t *h_level_max, uint32_t h_rows_max, void *d_workspace, hipStream_t s);
+    /// levels (where given): {levels the one-launch form committed, levels it gave up and the host redid pivot by pivot} — lexls_lse_last_large_levels;
+    /// host bookkeeping only
+    hipError_t launch_lqr_large_fast(const LseArgs &a, const uint32_t *h_level_max, uint32_t h_rows_max, void *d_workspace, hipStream_t s, uint32_t *levels = nullptr);
 } // namespace lexls

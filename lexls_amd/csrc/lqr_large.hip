@@ -1882,8 +1882,9 @@ namespace lexls
     }
 
     /// the fast large path (see the comment above fast_level_begin); gemm_only_mfma: the bit-exact multi-launch path with its trailing update on the matrix cores
-    hipError_t launch_lqr_large_fast(const LseArgs &a, const uint32_t *h_level_max, uint32_t h_rows_max, void *d_ws, hipStream_t s)
+    hipError_t launch_lqr_large_fast(const LseArgs &a, const uint32_t *h_level_max, uint32_t h_rows_max, void *d_ws, hipStream_t s, uint32_t *levels)
     {
+        if (levels) levels[0] = levels[1] = 0u;
         const uint32_t B = a.batch, n = a.nVar, cap = a.cap;
         uint32_t maxdim  = 0;
         for (uint32_t k = 0; k < a.nObj; k++) maxdim = h_level_max[k] > maxdim ? h_level_max[k] : maxdim;
@@ -1965,6 +1966,7 @@ namespace lexls
                     run_steps = true;
                 else
                     pp ^= 1u;
+                if (levels) levels[hc.abort ? 1 : 0]++;
             }
             else if (!all_exhausted)
                 run_steps = true;

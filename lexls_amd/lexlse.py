@@ -315,6 +315,14 @@ class BatchedLexLSE:
         capi.check(capi.lib().lexls_lse_last_consumer_kernel(self._h, buf, C.c_size_t(len(buf))))
         return buf.value.decode()
 
+    def last_large_levels(self):
+        """(in_launch, redone) of the last factorization (lexls_lse_last_large_levels): levels whose pivots lqr_large<step-per-pivot,mfma> ran
+        inside ONE launch, and levels that launch gave up and the host redid with a launch per pivot; (0, 0) on every other kernel, for a
+        batch, under LEXLS_LARGE_PERSIST=0 and where no form of the launch fits the device"""
+        a, r = C.c_uint32(0), C.c_uint32(0)
+        capi.check(capi.lib().lexls_lse_last_large_levels(self._h, C.byref(a), C.byref(r)))
+        return int(a.value), int(r.value)
+
     def set_accuracy_guard(self, mode: int, threshold: float = 0.0):
         """lexls_lse_set_accuracy_guard: 0 off (default), 1 report, 2 report and re-solve the flagged problems on the bit-exact kernel
         (include/lexls_hip.h, policy comment); threshold <= 0: the calibrated default"""

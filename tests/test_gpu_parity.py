@@ -393,13 +393,22 @@ def test_large_path_one_launch_per_level(hip, oracle, monkeypatch, mode):
     (LEXLS_LARGE_PERSIST=2 raises the abort flag before the launch), and on a rank-deficient problem whose levels stop early"""
     monkeypatch.setenv("LEXLS_LARGE_PERSIST", mode)
     n, dims = 150, [90, 90, 90]
+
+    def counters_tell_the_form(s, ref):
+        """lexls_lse_last_large_levels: last_kernel() is the same whether the launch committed a level or gave up and the host redid it"""
+        reached = sum(1 for k in range(len(dims)) if int(ref["rank"][0, :k].sum()) < n)  # levels that start with columns left
+        assert s.last_large_levels() == {"1": (reached, 0), "0": (0, 0), "2": (0, reached)}[mode]
+
     lod = P.rank_deficient_problem(811, n, dims, [60, 50, 30])[None]
     s, ref = run_both(hip, oracle, lod, dims, n)
     assert ref["rank"][0].tolist() == [60, 50, 30]
     check_large(s, ref, dims, n, 0)
+    counters_tell_the_form(s, ref)
     lod = P.lse_batch(5, 1, n, dims)  # full rank: the columns run out inside level 1
     s, ref = run_both(hip, oracle, lod, dims, n)
     check_large(s, ref, dims, n, 0)
+    assert ref["rank"][0].tolist() == [90, 60, 0]
+    counters_tell_the_form(s, ref)
 
 
 @LARGE_PATHS
