@@ -422,6 +422,37 @@ int lexls_lsi_batch_run_device_ex(lexls_lsi_batch_t b, const double *d_data, con
                                   const double *d_x0, const double *d_v0, const double *h_reg_factors, const double *h_params, uint32_t nparams,
                                   double *d_x, int32_t *d_info6, uint8_t *d_active, double *d_v,
                                   double *d_lambda, uint32_t *d_cycling_counts);
+/* Regularization factors of its own for every instance of the batch, in place of the one shared vector h_reg_factors of the runs: `factors` holds
+ * batch x nObj doubles, instance-major — the layout of h_reg_factors repeated per instance; for objective k, instance b takes
+ * factors[b * nObj + k] where the shared vector would have given h_reg_factors[k] (the entry of a simple-bounds objective 0 is ignored, as it is
+ * there).  This is what N separate LexLSI objects with N factor sets compute (setRegularizationFactor per objective, lexlsi.cpp:527-625).
+ * in_device_memory == 0: the array is copied at the call and may be freed.  in_device_memory == 1: the POINTER is kept — memory of the batch's
+ * device, alive until the setting is cleared or the batch destroyed — and read in the groups' streams at the start of every run, so a closed
+ * loop may rewrite the array in place between two runs (the caller's writes are complete before the run is called, as for every d_* input).
+ * factors == NULL clears the setting: the batch behaves as if this call had never been made.
+ * While the setting holds it serves every run of the object — lexls_lsi_batch_run, lexls_lsi_batch_run_device, lexls_lsi_batch_run_device_ex —
+ * and such a run passes h_reg_factors == NULL (no rule says which of two sources would win).  A run with regularization_type 0 ignores the
+ * setting as it ignores h_reg_factors.  The one-shot calls lexls_lsi_batch_solve* make their own batch object: shared factors only.
+ * What it does on each path of "How a run executes" below:
+ *   resident runs (persistent launch and lock-step stages alike): every group's regularization block is filled per instance — row lo + i of
+ *     the array is row i of the group whose first instance is lo, LexLSE level k takes the entry of objective k + 1 when objective 0 holds simple
+ *     bounds, else of objective k.  Host factors go through the block's staging copy, once per run; device factors are moved by one small
+ *     kernel (lsi_instance_factors_kernel, one thread per instance and level) in the group's stream before the run's first stage, and are
+ *     never copied to the host.  The kernels are those of a shared-factor run of the same type (lexls_lsi_batch_last_kernel names the same):
+ *     the regularized instantiations have always indexed the factors by problem;
+ *   phase 1 on the host (lexls_lsi_batch_run by default), host factors: the host LexLSI object of instance b gets row b.  With DEVICE factors
+ *     lexls_lsi_batch_run makes phase 1 device work, as if LEXLS_LSI_DEVICE_PHASE1=1 were set for that run — no host object may read the array —
+ *     and, as that path takes no h_v0, a run that gives h_v0 returns LEXLS_ERR_UNSUPPORTED;
+ *   host path (regularization_type 7, cycling handling of a regularized run, LEXLS_LSI_RESIDENT=0, shapes without a resident kernel) and the
+ *     one-by-one path of deactivate_first_wrong_sign: instance b is built with row b — host factors only.
+ * lexls_lsi_batch_get_lambda after a regularized run stays LEXLS_ERR_UNSUPPORTED.
+ * Errors of this call: LEXLS_ERR_INVALID for a null handle; LEXLS_ERR_UNSUPPORTED for in_device_memory == 1 on a batch whose regularized runs
+ * cannot be resident at all (no register-resident kernel for its shape) — the rule of lexls_lsi_batch_run_device: no detour over the host.
+ * Errors of a run while the setting holds, each before any work and with every output left alone: LEXLS_ERR_INVALID when h_reg_factors is not
+ * NULL; LEXLS_ERR_UNSUPPORTED when device factors are set and the regularized run would not be resident (regularization_type 7, cycling handling,
+ * LEXLS_LSI_RESIDENT=0 — with host factors the same run proceeds on the host path); LEXLS_ERR_UNSUPPORTED when device factors are set and
+ * lexls_lsi_batch_run is given h_v0. */
+int lexls_lsi_batch_set_instance_regularization(lexls_lsi_batch_t b, const double *factors, int in_device_memory);
 /* How a run executes: phase 1 of every instance on the host; from then on the instance's active-set iterations are resident on the
  * device (LEXLS_LSI_RESIDENT=0: host logic, lock-step stages).  Where the batch's shape has a persistent instantiation (the register-resident l-QR shapes:
  * nVar + 1 <= 41 with levels of up to 12 rows, nVar + 1 <= 64 with levels of up to 16 — except 42..48 columns), everything behind the first resident

@@ -31,6 +31,7 @@ SYMBOLS = [
     "lexls_lse_multipliers", "lexls_lse_get_multipliers", "lexls_lsi_batch_get_lambda", "lexls_lsi_batch_solve_ex2",
     "lexls_lse_sensitivity_collect", "lexls_lse_sensitivity_collect_resident", "lexls_lse_get_wrong_sign",
     "lexls_lsi_batch_get_cycling_counters", "lexls_lsi_batch_run_device", "lexls_lsi_batch_run_device_ex",
+    "lexls_lsi_batch_set_instance_regularization",
     "lexls_lsi_batch_last_kernel",
 ]
 
@@ -79,6 +80,8 @@ def lib() -> C.CDLL:
         _lib.lexls_lsi_batch_run_device_ex.restype = C.c_int
         _lib.lexls_lsi_batch_run_device_ex.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_double), C.POINTER(C.c_double),
                                                        C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]  # + d_v0; d_lambda, d_cycling_counts
+        _lib.lexls_lsi_batch_set_instance_regularization.restype = C.c_int
+        _lib.lexls_lsi_batch_set_instance_regularization.argtypes = [C.c_void_p, C.c_void_p, C.c_int]  # factors: host or device address
     return _lib
 
 

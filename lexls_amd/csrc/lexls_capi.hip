@@ -369,9 +369,9 @@ extern "C"
         return e;
     }
 
-    /// lexls_lse_set_regularization / lexls_internal_set_regularization_block: the factors are staged in the handle (reg_stage) and enqueued in
-    /// its stream; wait: the stream is synchronised before returning
-    static int set_regularization(lexls_lse_t h, int type, const double *h_factors, int per_problem, double variable_factor, bool wait)
+    /// what every way of setting a regularization shares: type and variable factor into the handle, the kept factor dropped, the device arrays
+    /// the regularized kernels read made (type != 0) — nothing is written into d_reg_factor
+    static int prepare_regularization(lexls_lse_t h, int type, double variable_factor)
     {
         if ((uint32_t)type != h->reg_type) HIP_TRY(materialize_fused_gather(h));
         HIP_TRY(hipSetDevice(h->device));
@@ -380,10 +380,6 @@ extern "C"
         h->reg_variable = variable_factor;
         if (type == 0) return LEXLS_OK;
         const size_t B = h->batch, nObj = h->nObj;
-        h->reg_stage.assign(B * nObj, 0.0);
-        if (h_factors)
-            for (size_t b = 0; b < B; b++)
-                for (size_t k = 0; k < nObj; k++) h->reg_stage[b * nObj + k] = per_problem ? h_factors[b * nObj + k] : h_factors[k];
         if (!h->d_reg_factor) HIP_TRY(hipMalloc((void **)&h->d_reg_factor, 8 * B * nObj));
         if (!h->d_reg_scratch)
         {
@@ -397,6 +393,20 @@ extern "C"
             HIP_TRY(hipMalloc((void **)&h->d_reg_mu, bytes));
             HIP_TRY(hipMemsetAsync(h->d_reg_mu, 0, bytes, h->stream));
         }
+        return LEXLS_OK;
+    }
+
+    /// lexls_lse_set_regularization / lexls_internal_set_regularization_block(_per_problem): the factors are staged in the handle (reg_stage) and
+    /// enqueued in its stream; wait: the stream is synchronised before returning
+    static int set_regularization(lexls_lse_t h, int type, const double *h_factors, int per_problem, double variable_factor, bool wait)
+    {
+        const int rc = prepare_regularization(h, type, variable_factor);
+        if (rc != LEXLS_OK || type == 0) return rc;
+        const size_t B = h->batch, nObj = h->nObj;
+        h->reg_stage.assign(B * nObj, 0.0);
+        if (h_factors)
+            for (size_t b = 0; b < B; b++)
+                for (size_t k = 0; k < nObj; k++) h->reg_stage[b * nObj + k] = per_problem ? h_factors[b * nObj + k] : h_factors[k];
         HIP_TRY(hipMemcpyAsync(h->d_reg_factor, h->reg_stage.data(), 8 * B * nObj, hipMemcpyHostToDevice, h->stream));
         if (wait) HIP_TRY(hipStreamSynchronize(h->stream));
         return LEXLS_OK;
@@ -423,6 +433,36 @@ extern "C"
         h->resume_armed = false;
         h->reg_cg_iters = cg_iterations;
         return set_regularization(h, type, h_level_factors, 0, variable_factor, false);
+    }
+
+    /* internal: lexls_internal_set_regularization_block with factors of its own for every problem — h_factors is batch x nObj, problem-major, the
+     * array the kernels read (they index it by problem already).  Enqueued only, like the shared form. */
+    int lexls_internal_set_regularization_block_per_problem(lexls_lse_t h, int type, const double *h_factors, double variable_factor, uint32_t cg_iterations)
+    {
+        CHECK_HANDLE(h);
+        if (type < 1 || type > 9) return fail(LEXLS_ERR_INVALID, "set_regularization_block: regularization type outside 1 .. 9");
+        if (!h_factors) return fail(LEXLS_ERR_INVALID, "set_regularization_block: null factors");
+        h->resume_valid = false;
+        h->resume_armed = false;
+        h->reg_cg_iters = cg_iterations;
+        return set_regularization(h, type, h_factors, 1, variable_factor, false);
+    }
+
+    /* internal: the regularization block of a run whose factors the CALLER writes on the device — type, variable factor and CG bound are set and
+     * the kept factor dropped as lexls_internal_set_regularization_block does, the arrays exist, and *d_factors is the batch x nObj array the
+     * kernels read: the caller fills it in the handle's stream before the first factorization.  No host staging: nothing of the handle's own
+     * staging copy is enqueued over what the caller writes. */
+    int lexls_internal_set_regularization_block_device(lexls_lse_t h, int type, double variable_factor, uint32_t cg_iterations, double **d_factors)
+    {
+        CHECK_HANDLE(h);
+        if (type < 1 || type > 9) return fail(LEXLS_ERR_INVALID, "set_regularization_block: regularization type outside 1 .. 9");
+        if (!d_factors) return fail(LEXLS_ERR_INVALID, "set_regularization_block: null output");
+        h->resume_valid = false;
+        h->resume_armed = false;
+        h->reg_cg_iters = cg_iterations;
+        const int rc = prepare_regularization(h, type, variable_factor);
+        if (rc == LEXLS_OK) *d_factors = h->d_reg_factor;
+        return rc;
     }
 
     /* internal (the lock-step LexLSI driver): can the resident iterations of this handle's batch run under regularization `type`?  Every type

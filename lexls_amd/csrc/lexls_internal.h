@@ -27,6 +27,10 @@ extern "C"
     void lexls_internal_arm_resume(lexls_lse_t h);
     /// the regularization of ONE run (type 1 .. 9, one factor per LexLSE level for every problem), only ENQUEUED in the handle's stream
     int lexls_internal_set_regularization_block(lexls_lse_t h, int type, const double *h_level_factors, double variable_factor, uint32_t cg_iterations);
+    /// the same with factors of its own for every problem (h_factors: batch x nObj, problem-major)
+    int lexls_internal_set_regularization_block_per_problem(lexls_lse_t h, int type, const double *h_factors, double variable_factor, uint32_t cg_iterations);
+    /// the same without factors: the caller writes them into *d_factors (batch x nObj, the array the kernels read) in the handle's stream
+    int lexls_internal_set_regularization_block_device(lexls_lse_t h, int type, double variable_factor, uint32_t cg_iterations, double **d_factors);
     /// 1 when the resident iterations of this handle's batch can run under regularization `type` (nothing is launched, nothing changes)
     int lexls_internal_resident_reg_serves(lexls_lse_t h, int type);
     /// ALL remaining resident iterations in one persistent launch (resident_args: a ResidentArgs); 1 = the shape has none, nothing changed

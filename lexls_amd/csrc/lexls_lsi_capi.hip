@@ -91,8 +91,10 @@ extern "C"
         return guarded([&]() {
             if (!b) throw Exception("lexls_lsi_batch_run: null handle");
             if (h_params && nparams != 9 && nparams != 12) throw Exception("lexls_lsi_batch_solve_ex: 9 or 12 parameters expected"); // (the name its callers have always seen)
-            b->run(h_data, h_var_index, h_active_guess, h_x0, h_v0, h_reg_factors, unpack(h_params, nparams), h_x, h_info6, h_active, h_v, h_rounds2);
-            return LEXLS_OK;
+            const ParametersLexLSI par = unpack(h_params, nparams);
+            if (const int refused = b->refuse_run("lexls_lsi_batch_run", h_reg_factors, par, h_v0 != NULL)) return refused; // (nothing launched, the outputs as they are)
+            b->run(h_data, h_var_index, h_active_guess, h_x0, h_v0, h_reg_factors, par, h_x, h_info6, h_active, h_v, h_rounds2);
+            return static_cast<int>(LEXLS_OK);
         });
     }
 
@@ -112,6 +114,7 @@ extern "C"
             if (!d_data || !d_x) throw Exception("lexls_lsi_batch_run_device: null data / x");
             if (b->off && !d_var_index) throw Exception("lexls_lsi_batch_run_device: a simple-bounds objective needs variable indices");
             const ParametersLexLSI par = unpack(h_params, nparams);
+            if (const int refused = b->refuse_run("lexls_lsi_batch_run_device", h_reg_factors, par, false)) return refused;
             if (!b->would_be_resident(par)) // no detour over the host: nothing is launched, the outputs stay as they are
             {
                 lexls_internal_set_error("lexls_lsi_batch_run_device: only runs that are resident on the device are served (not: LEXLS_LSI_RESIDENT=0, LEXLS_LSI_HOST_STAGING, "
@@ -129,6 +132,14 @@ extern "C"
             dev.cycling_counts = d_cycling_counts;
             b->run_device(dev, h_reg_factors, par);
             return d_lambda ? b->get_lambda(NULL, d_lambda) : static_cast<int>(LEXLS_OK);
+        });
+    }
+
+    int lexls_lsi_batch_set_instance_regularization(lexls_lsi_batch_t b, const double *factors, int in_device_memory)
+    {
+        return guarded([&]() {
+            if (!b) throw Exception("lexls_lsi_batch_set_instance_regularization: null handle");
+            return b->set_instance_regularization(factors, in_device_memory);
         });
     }
 

@@ -44,6 +44,18 @@ namespace
             for (uint32_t k = 0; k < nObjL; k++) o[u + (size_t)(off + k) * total] = m[(size_t)k * ldo + r];
         }
     }
+
+    /// lexls_lsi_batch_set_instance_regularization with the factors in device memory, for one group: row i of the group's handle array (B x nObjL,
+    /// what the regularized kernels read) takes the factors of the caller's row i (B x nObj, the group's first instance in front): LexLSE level k
+    /// = objective off + k.  One thread per (instance, level).
+    __global__ __launch_bounds__(256) void lsi_instance_factors_kernel(const double *__restrict__ factors, uint32_t B, uint32_t nObj, uint32_t nObjL, uint32_t off,
+                                                                      double *__restrict__ out)
+    {
+        const uint32_t t = blockIdx.x * blockDim.x + threadIdx.x;
+        if (t >= B * nObjL) return;
+        const uint32_t i = t / nObjL, k = t - i * nObjL;
+        out[t] = factors[(size_t)i * nObj + off + k];
+    }
 } // namespace
 
 /// A lock-step batch that outlives one solve (the reference constructs a LexLSI once and feeds it successive problems, lexlsi.h:56-112):
@@ -61,6 +73,12 @@ struct lexls_lsi_batch_s
     std::vector<uint32_t> lo, group_of;
     std::unique_ptr<WorkerPool> pool;
     bool resident_ok = false;
+    bool resident_shape = false; // resident_ok but for the environment's switches: the structure has resident iterations at all
+    // ---- lexls_lsi_batch_set_instance_regularization: batch x nObj factors that stand for h_reg_factors in every regularized run while set ----
+    enum : int { INST_NONE = 0, INST_HOST = 1, INST_DEVICE = 2 };
+    int inst_mode = INST_NONE;
+    std::vector<double> inst_factors;     // INST_HOST: the copy taken at the call
+    const double *d_inst_factors = NULL;  // INST_DEVICE: the caller's array, read in the groups' streams at the start of every run
     double t_create = 0.0;
     int32_t last_stats[4] = {0, 0, 0, 0}; // of the last run: factorize+solve stages, sensitivity stages, stages with the step on the device, groups
     // ---- getLambda of the last run (lexls_lsi_batch_get_lambda, lexlsi.h:552-605) ----
@@ -113,6 +131,7 @@ struct lexls_lsi_batch_s
         std::vector<runner::LsiProblem> prob;
         std::vector<std::atomic<uint32_t>> wants; // per group: WANT_* of the next stage
         double t_begin = 0.0, t_ctx = 0.0, t_setup = 0.0, t_host = 0.0;
+        const double *inst_rows = NULL, *d_inst_rows = NULL; // per-instance factors of this run (batch x nObj; host copy / caller's device array) or NULL
     };
 
     lexls_lsi_batch_s(int device_, uint32_t batch_, uint32_t nVar_, uint32_t nObj_, const uint32_t *h_dims, const int32_t *h_types)
@@ -184,6 +203,8 @@ struct lexls_lsi_batch_s
         // how many instances have stopped.  LEXLS_LSI_RESIDENT=0 keeps the active-set logic on the host (one synchronisation per stage).
         resident_ok = sw.resident && !step_ok && gather && nObj <= STEP_MAX_OBJ && 4 * resident_lds_per_wave(sh.SD, (uint32_t)total) <= 48 * 1024 && total <= 65535 && elems <= 0xffffffffull;
         for (uint32_t k = 1; k < nObj && resident_ok; k++) resident_ok = h_types[k] != 1; // (the driver itself only takes a simple-bounds objective first, lexlsi.h:402-405)
+        resident_shape = per_data < 0x7fffffffull && nObj <= STEP_MAX_OBJ && 4 * resident_lds_per_wave(sh.SD, (uint32_t)total) <= 48 * 1024 && total <= 65535 && elems <= 0xffffffffull;
+        for (uint32_t k = 1; k < nObj && resident_shape; k++) resident_shape = h_types[k] != 1;
         if (resident_ok)
             for (uint32_t g = 0; g < nGroups; g++) grp[g]->create_resident(sh, off);
         group_of.resize(batch);
@@ -369,7 +390,69 @@ struct lexls_lsi_batch_s
     runner::LsiProblem problem(const Run &r, uint32_t b) const
     {
         return {nVar, nObj, dims.data(), types.data(), r.h_data + (size_t)b * per_data, r.h_var_index ? r.h_var_index + (size_t)b * dims[0] : NULL,
-                r.h_active_guess ? r.h_active_guess + (size_t)b * total : NULL, r.h_x0 ? r.h_x0 + (size_t)b * nVar : NULL, r.h_v0 ? r.h_v0 + (size_t)b * total : NULL, r.h_reg_factors};
+                r.h_active_guess ? r.h_active_guess + (size_t)b * total : NULL, r.h_x0 ? r.h_x0 + (size_t)b * nVar : NULL, r.h_v0 ? r.h_v0 + (size_t)b * total : NULL,
+                r.inst_rows ? r.inst_rows + (size_t)b * nObj : r.h_reg_factors};
+    }
+
+    /// lexls_lsi_batch_set_instance_regularization
+    int set_instance_regularization(const double *factors, int in_device_memory)
+    {
+        if (!factors)
+        {
+            inst_mode      = INST_NONE;
+            d_inst_factors = NULL;
+            inst_factors.clear();
+            return LEXLS_OK;
+        }
+        if (in_device_memory)
+        {
+            bool served = false; // some regularization type has a register-resident kernel on this shape
+            for (int t = 1; t <= 9 && resident_shape && !served; t++) served = lexls_internal_resident_reg_serves(grp[0]->h, t) != 0;
+            if (!served)
+            {
+                lexls_internal_set_error("lexls_lsi_batch_set_instance_regularization: factors in device memory need a batch whose regularized runs can be resident "
+                                         "(no register-resident kernel for this shape): there is no detour over the host");
+                return LEXLS_ERR_UNSUPPORTED;
+            }
+            inst_factors.clear();
+            d_inst_factors = factors;
+            inst_mode      = INST_DEVICE;
+            return LEXLS_OK;
+        }
+        inst_factors.assign(factors, factors + (size_t)batch * nObj);
+        d_inst_factors = NULL;
+        inst_mode      = INST_HOST;
+        return LEXLS_OK;
+    }
+    /// the setting as a run with these parameters sees it (a run with regularization_type 0 ignores it, as it ignores h_reg_factors)
+    void take_instance_regularization(Run &r) const
+    {
+        if (r.par.regularization_type == REGULARIZATION_NONE) return;
+        r.inst_rows   = inst_mode == INST_HOST ? inst_factors.data() : NULL;
+        r.d_inst_rows = inst_mode == INST_DEVICE ? d_inst_factors : NULL;
+    }
+    /// what the entry points refuse before any work: 0, or the code with lexls_last_error() set.  `who`: the entry point; with_v0: lexls_lsi_batch_run got h_v0
+    int refuse_run(const char *who, const double *h_reg_factors, const ParametersLexLSI &par, bool with_v0) const
+    {
+        if (inst_mode == INST_NONE) return LEXLS_OK;
+        if (h_reg_factors)
+        {
+            lexls_internal_set_error((std::string(who) + ": h_reg_factors must be NULL while lexls_lsi_batch_set_instance_regularization holds factors for this batch").c_str());
+            return LEXLS_ERR_INVALID;
+        }
+        if (inst_mode != INST_DEVICE || par.regularization_type == REGULARIZATION_NONE) return LEXLS_OK;
+        if (!would_be_resident(par))
+        {
+            lexls_internal_set_error((std::string(who) + ": per-instance regularization factors in device memory are served on resident runs only (not: LEXLS_LSI_RESIDENT=0, "
+                                                         "regularization type 7, cycling handling of a regularized run); they are never copied to the host").c_str());
+            return LEXLS_ERR_UNSUPPORTED;
+        }
+        if (with_v0)
+        {
+            lexls_internal_set_error((std::string(who) + ": per-instance regularization factors in device memory make phase 1 device work, which does not take h_v0").c_str());
+            return LEXLS_ERR_UNSUPPORTED;
+        }
+        return LEXLS_OK;
     }
     BatchCtx &group_of_instance(uint32_t b, uint32_t &k)
     {
@@ -391,6 +474,7 @@ struct lexls_lsi_batch_s
                               : par.regularization_type != REGULARIZATION_NONE ? "lexls_lsi_batch_get_lambda: not available after a regularized run"
                                                                                 : "lexls_lsi_batch_get_lambda: not available when the constraint data is not resident on the device (or beyond 65535 constraints)";
         Run r{h_data, h_x0, h_v0, h_reg_factors, h_var_index, h_active_guess, par, h_x, h_v, h_info6, h_rounds2, h_active};
+        take_instance_regularization(r);
         // deactivate_first_wrong_sign is a removal rule the resident iterations know (collecting removal search + activation stamps, lexls_lsi_device.h);
         // the host-driven lock-step stages of a whole run do not: where the run would not be resident its instances go one by one
         if (par.deactivate_first_wrong_sign && !would_be_resident(par))
@@ -400,7 +484,9 @@ struct lexls_lsi_batch_s
             lam_msg = lam_rc == LEXLS_ERR_INVALID ? "lexls_lsi_batch_get_lambda: the run had no variable indices" : lam_why;
             return;
         }
-        if (r.sw.device_phase1 && !h_v0 && would_be_resident(par)) // LEXLS_LSI_DEVICE_PHASE1=1: no host objects, phase 1 is device work
+        // LEXLS_LSI_DEVICE_PHASE1=1: no host objects, phase 1 is device work; so it is with per-instance factors in device memory, which no host
+        // object may read (refuse_run has turned away the runs this cannot serve)
+        if ((r.sw.device_phase1 || r.d_inst_rows) && !h_v0 && would_be_resident(par))
         {
             run_phase1_on_device(r, NULL);
             lam_rc  = (off && !h_var_index) ? LEXLS_ERR_INVALID : lam_after;
@@ -502,18 +588,39 @@ struct lexls_lsi_batch_s
     /// factor of objective k + off (a simple-bounds objective 0 becomes fixed variables and has none: lexlsi.h formLexLSE), whatever the level
     /// holds in the working set of the moment.  The host copy the instances post into (SlotLSE::setRegularizationFactor) starts from the
     /// same values, so phase 1 finds nothing to upload again.
+    /// Per-instance factors (lexls_lsi_batch_set_instance_regularization): row lo[g] + i of the caller's array fills row i of group g's block, from the
+    /// host copy through the same staging, from a device array by lsi_instance_factors_kernel in the group's stream.  A run on a device array
+    /// has no host objects (phase 1 is device work), so nobody reads the host copy ctx.reg_factor, which does not hold its factors.
     void upload_regularization_block(Run &r)
     {
         const int reg_type = static_cast<int>(r.par.regularization_type);
         if (!r.resident || reg_type == 0) return;
-        std::vector<double> level_factor(nObj - off, 0.0);
+        const uint32_t nObjL = nObj - off;
+        std::vector<double> level_factor(nObjL, 0.0);
         if (r.h_reg_factors)
             for (uint32_t k = 0; k + off < nObj; k++) level_factor[k] = r.h_reg_factors[k + off];
         for (uint32_t g = 0; g < nGroups; g++)
         {
             BatchCtx &ctx = *grp[g];
-            hip_check(lexls_internal_set_regularization_block(ctx.h, reg_type, level_factor.data(), ctx.reg_variable, ctx.reg_cg_iters));
-            for (uint32_t b = 0; b < ctx.B; b++) std::copy(level_factor.begin(), level_factor.end(), ctx.reg_factor.begin() + (size_t)b * ctx.nObjL);
+            if (r.d_inst_rows)
+            {
+                double *d_block = NULL;
+                hip_check(lexls_internal_set_regularization_block_device(ctx.h, reg_type, ctx.reg_variable, ctx.reg_cg_iters, &d_block));
+                const uint32_t cells = ctx.B * nObjL;
+                hipLaunchKernelGGL(lsi_instance_factors_kernel, dim3((cells + 255) / 256), dim3(256), 0, ctx.stream, r.d_inst_rows + (size_t)lo[g] * nObj, ctx.B, nObj, nObjL, off, d_block);
+                if (hipGetLastError() != hipSuccess) throw Exception("lsi_instance_factors_kernel launch failed");
+            }
+            else if (r.inst_rows)
+            {
+                for (uint32_t i = 0; i < ctx.B; i++)
+                    std::copy(r.inst_rows + (size_t)(lo[g] + i) * nObj + off, r.inst_rows + (size_t)(lo[g] + i + 1) * nObj, ctx.reg_factor.begin() + (size_t)i * nObjL);
+                hip_check(lexls_internal_set_regularization_block_per_problem(ctx.h, reg_type, ctx.reg_factor.data(), ctx.reg_variable, ctx.reg_cg_iters));
+            }
+            else
+            {
+                hip_check(lexls_internal_set_regularization_block(ctx.h, reg_type, level_factor.data(), ctx.reg_variable, ctx.reg_cg_iters));
+                for (uint32_t b = 0; b < ctx.B; b++) std::copy(level_factor.begin(), level_factor.end(), ctx.reg_factor.begin() + (size_t)b * ctx.nObjL);
+            }
             ctx.reg_dirty.store(false);
         }
     }
@@ -815,6 +922,7 @@ struct lexls_lsi_batch_s
         last_kernel = "host";
         std::fill(cycling_count.begin(), cycling_count.end(), 0u);
         Run r{NULL, NULL, NULL, h_reg_factors, NULL, NULL, par, NULL, NULL, NULL, NULL, NULL};
+        take_instance_regularization(r);
         run_phase1_on_device(r, &dev);
         lam_rc  = lam_rc_after(par);
         lam_msg = par.cycling_handling_enabled ? "lexls_lsi_batch_get_lambda: not available after a run with cycling handling enabled (it may have relaxed bounds in the resident constraint data)"

@@ -239,6 +239,7 @@ class LsiBatch:
         self.types = np.ascontiguousarray(types, np.int32)
         self.total = int(self.dims.sum())
         self._h = C.c_void_p()
+        self._instance_factors = None  # the device tensor (or address) set_instance_regularization was given: kept alive while the library reads it
         capi.check(capi.lib().lexls_lsi_batch_create(C.byref(self._h), C.c_int(device), C.c_uint32(self.batch), C.c_uint32(self.nvar),
                                                      C.c_uint32(len(self.dims)), _p(self.dims, C.c_uint32), _p(self.types, C.c_int32)))
 
@@ -265,6 +266,28 @@ class LsiBatch:
         resident (LEXLS_LSI_RESIDENT=0, regularization type 7, cycling handling of a regularized run, ...)"""
         return capi.lib().lexls_lsi_batch_last_kernel(self._h).decode()
 
+    def set_instance_regularization(self, factors):
+        """lexls_lsi_batch_set_instance_regularization: regularization factors of its own for every instance, (batch, nObj), in place of the
+        shared `regularization_factors=` of run() / run_device() — which then must not be given (the library's error is raised).  A numpy array
+        (or anything array-like) is copied at the call; a torch tensor on the batch's device (float64, contiguous) or an integer device address
+        is KEPT and read at the start of every run, so it may be rewritten in place between runs — the caller keeps it alive.  None clears
+        the setting.  A run with regularization_type 0 ignores it."""
+        nobj, keep = len(self.dims), None
+        if factors is None:
+            ptr, on_device = None, 0
+        elif hasattr(factors, "data_ptr"):
+            import torch
+            ptr, on_device, keep = self._device_array("factors", factors, torch.float64, (self.batch, nobj), optional=False), 1, factors
+        elif isinstance(factors, int):
+            ptr, on_device, keep = C.c_void_p(factors), 1, factors
+        else:
+            f = np.ascontiguousarray(factors, np.float64)
+            if f.shape != (self.batch, nobj):
+                raise ValueError(f"set_instance_regularization: factors have shape {f.shape}, {(self.batch, nobj)} expected")
+            ptr, on_device = C.c_void_p(f.ctypes.data), 0
+        capi.check(capi.lib().lexls_lsi_batch_set_instance_regularization(self._h, ptr, C.c_int(on_device)))
+        self._instance_factors = keep  # (a tensor given earlier is let go of only now that the library has another source)
+
     def run(self, problems, active_guess=None, x0=None, regularization_factors=None, v0=None, **params):
         """`problems`: list of objective lists or a PackedBatch of this batch's structure; other arguments as lsi_batch_solve"""
         pk = problems if isinstance(problems, PackedBatch) else pack_batch(self.nvar, problems)
@@ -285,6 +308,9 @@ class LsiBatch:
         else:
             par = pack_params(**params)
         rfa = None if regularization_factors is None else np.ascontiguousarray(regularization_factors, np.float64)
+        if hasattr(self._instance_factors, "data_ptr"):
+            import torch
+            torch.cuda.synchronize(torch.device("cuda", self.device))  # what wrote the factor tensor is complete before the library's streams read it
         capi.check(capi.lib().lexls_lsi_batch_run(
             self._h, _p(pk.data, C.c_double), _p(pk.var_index, C.c_uint32), _p(guess, C.c_uint8), _p(x0a, C.c_double), _p(v0a, C.c_double), _p(rfa, C.c_double),
             _p(par, C.c_double), C.c_uint32(len(par)), _p(x, C.c_double), _p(info, C.c_int32), _p(active, C.c_uint8), _p(v, C.c_double),
