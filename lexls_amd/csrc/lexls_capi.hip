@@ -891,9 +891,7 @@ extern "C"
         }
         else if (plan.id == KernelId::large_fast)
         {
-            uint32_t md = 0;
-            for (uint32_t v : h->level_max) md = v > md ? v : md;
-            const size_t need = large_fast_workspace_bytes(h->batch, h->nVar, h->cap, md);
+            const size_t need = large_fast_workspace_bytes(h->batch, h->nVar, h->cap, large::max_level_dim(h->level_max.data(), h->nObj));
             if (need > h->large_ws_bytes)
             {
                 if (h->d_large_ws) HIP_TRY(hipFree(h->d_large_ws));

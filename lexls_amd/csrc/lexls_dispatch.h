@@ -7,6 +7,7 @@
 // under which it is taken to plan_lqr's helpers below — and re-record nothing: tests/dispatch_table.json shows what changed.
 #pragma once
 #include "lexls_lds.h"
+#include "lqr_large_plan.h"
 
 // X(id, name as lexls_lse_last_kernel reports it, launcher kind, launcher).  The ORDER carries meaning: the planner reaches the variants of a
 // shape by offset (x only, + 1 factor kept, + 2 fixed variables; lqr_qtol: + 5 estimating, + 10 ragged; lsi_fused: + 3 regularized).  Kinds (lqr_small.hip): PLAIN (a, s); EST (a, s, est, count) — the

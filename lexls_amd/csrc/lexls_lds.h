@@ -7,9 +7,6 @@
 #ifndef QT_WPB
 #define QT_WPB 4 // wavefronts per workgroup of lqr_qtol (1 or 4)
 #endif
-#ifndef LEXLS_LARGE_TC
-#define LEXLS_LARGE_TC 8 // trailing columns per apply-workgroup of the large path
-#endif
 
 namespace lexls
 {
@@ -192,18 +189,5 @@ namespace lexls
         return b;
     }
 
-    // ---- lqr_large (lqr_large.hip) ----
-    /// dynamic LDS of the three kernels that stage in LDS, for the largest level dimension of the batch
-    struct LargeLds
-    {
-        size_t piv, app, trsm;
-    };
-    inline LargeLds large_lds_bytes(uint32_t n, uint32_t maxdim)
-    {
-        LargeLds l;
-        l.piv  = 8 * ((size_t)((maxdim + 1) & ~1u) + 1024 + 16) + 4 * 1024;
-        l.app  = 8 * ((size_t)LEXLS_LARGE_TC * (maxdim | 1u) + maxdim + LEXLS_LARGE_TC + 2);
-        l.trsm = 8 * (size_t)((n < maxdim) ? n : maxdim) * 65;
-        return l;
-    }
+    // ---- lqr_large (lqr_large.hip): lqr_large_plan.h ----
 } // namespace lexls

@@ -14,6 +14,7 @@
 // the device from a small per-problem state record; the host only reads `exhausted` back once per level to stop launching.
 #include "lexls_kernels.h"
 #include "lexls_launch.h"
+#include "lqr_large_plan.h" // every shape constant, the host-sized records, the work-space layout, the per-level plan
 #include "lqr_wave_common.h"
 
 #include <cfloat>
@@ -23,17 +24,10 @@
 
 namespace lexls
 {
-    struct LargeState
-    {
-        uint32_t ColIndex, rank, exhausted, F, dim, Fc, last_id, cur, piv, row, R, degenerate, totalrank, stop_level;
-        double tau, diag, den;
-    };
+    using namespace large;
 
     namespace
     {
-        constexpr int TC = LEXLS_LARGE_TC; // trailing columns per apply-workgroup (lexls_lds.h)
-        constexpr int TJ = 8;  // trailing columns per lane in the Gauss update
-
         __device__ __forceinline__ bool skipped(const LseArgs &a, uint32_t b) { return a.skip && a.skip[b]; }
 
         __global__ __launch_bounds__(256) void large_init(LseArgs a, LargeState *st)
@@ -88,10 +82,6 @@ namespace lexls
         }
 
         /// serial part of one pivot (lexlse.h:205-242): one workgroup per problem
-#ifndef LEXLS_LARGE_NTP
-#define LEXLS_LARGE_NTP 1024
-#endif
-        constexpr uint32_t NTP = LEXLS_LARGE_NTP; // threads of the one-workgroup pivot kernel
         __global__ __launch_bounds__(NTP) void large_pivot(LseArgs a, LargeState *st, double *norms_all, uint32_t level, uint32_t counter)
         {
             extern __shared__ double smem[];
@@ -108,9 +98,9 @@ namespace lexls
             const uint32_t c = s->ColIndex, row = s->F + counter, R = s->dim - counter;
 
             double *colv    = smem;                 // R
-            double *red_v   = colv + ((R + 1) & ~1u); // 1024
-            uint32_t *red_i = reinterpret_cast<uint32_t *>(red_v + 1024);
-            double *sc      = reinterpret_cast<double *>(red_i + 1024); // fresh, tail, tau, diag, den, flags
+            double *red_v   = colv + ((R + 1) & ~1u); // NTP (large_lds_bytes)
+            uint32_t *red_i = reinterpret_cast<uint32_t *>(red_v + NTP);
+            double *sc      = reinterpret_cast<double *>(red_i + NTP); // fresh, tail, tau, diag, den, flags
 
             // first maximum of the down-dated norms
             double bv   = -INFINITY;
@@ -388,13 +378,12 @@ namespace lexls
                 for (uint32_t q = 0; q < rank; q++) W[gi + (size_t)(Fc + q) * cap] = L[q * 64 + lane];
         }
 
-        /// L <- A_left R^-1, column per thread (level dims <= 1024): thread q owns column q of the block for TRB rows held in registers.
+        /// L <- A_left R^-1, column per thread (level dims <= kTrsmColsMax): thread q owns column q of the block for TRB rows held in registers.
         /// Step p: thread p finalises L_.p = acc * (1/R_pp) and posts it in LDS; every thread q > p absorbs -L_.p * R[p][q].  Each element
         /// sees the same ordered chain as in the row-per-lane form above (p ascending, then the product with the reciprocal), so the result
         /// is bit-identical — but the chain of one row is spread over `rank` threads instead of being walked by one, and a thread streams
         /// its own (contiguous) column of R in chunks of TCH.
-        constexpr int TRB = 8, TCH = 16;
-        __global__ __launch_bounds__(1024) void large_trsm_cols(LseArgs a, const LargeState *st, uint32_t level)
+        __global__ __launch_bounds__(kTrsmColsMax) void large_trsm_cols(LseArgs a, const LargeState *st, uint32_t level)
         {
             __shared__ double Lb[2][TRB];
             const uint32_t b = blockIdx.y, tid = threadIdx.x;
@@ -547,17 +536,6 @@ namespace lexls
             return (rdlane(v, 0) + rdlane(v, 16)) + (rdlane(v, 32) + rdlane(v, 48));
         }
 
-#ifndef LEXLS_FAST_NW
-#define LEXLS_FAST_NW 4
-#endif
-#ifndef LEXLS_FAST_CPW
-#define LEXLS_FAST_CPW 1
-#endif
-        constexpr int FNW = LEXLS_FAST_NW, FNT = 64 * FNW; // wavefronts / threads per workgroup of the step kernel
-        constexpr int FCPW = LEXLS_FAST_CPW;                // columns per wavefront
-        constexpr int FTC  = FNW * FCPW;                    // columns per workgroup
-        constexpr int FRC = 4;         // rows a lane keeps in registers between the dot product and the update (R <= 64 * FRC)
-
         struct FastBuffers
         {
             double *W[2];          // factor-sized work buffers, W[0] == a.fac
@@ -626,7 +604,7 @@ namespace lexls
             uint32_t *pos_out      = fb.pos[pout] + (size_t)b * (n + 1);
             // Everything whose ADDRESS does not depend on the pivot is requested up front, so that a step is two dependent round trips to
             // L2 / memory (state + norms + positions + own tile, then the pivot column) instead of four: the search candidates of this thread
-            constexpr int NCAND = 1024 / FNT; // candidates per thread in registers (n <= 1024); beyond that the loop below reads again
+            constexpr int NCAND = kStepCandWindow / FNT; // candidates per thread in registers (n <= kStepCandWindow); beyond that the loop below reads again
             double cv[NCAND];
             uint32_t cp[NCAND];
 #pragma unroll
@@ -883,22 +861,7 @@ namespace lexls
         // The tags restart with every level, so the records and the column granules are cleared in front of every launch.  Every spin is bounded: a workgroup that gives up raises `abort`, which
         // every spin watches — the launch then ends WITHOUT committing anything and the host redoes the level with a launch per pivot.
         // -----------------------------------------------------------------------------------------------------------------
-        struct PersistCtl
-        {
-            uint32_t arrive; // monotonic over the pivots of the level
-            uint32_t abort;
-            uint32_t done;   // workgroups that have finished every pivot of the level without giving up: the commit waits for all G
-            uint32_t pad[13];
-        };
-        struct PersistCand
-        {
-            double norm;
-            uint32_t pos, idx;
-        };
-        /// records per mailbox row (a reader's row starts on a 256-byte boundary)
-        __host__ __device__ inline size_t persist_mailbox_stride(uint32_t G) { return ((size_t)G + 15u) & ~(size_t)15u; }
-        /// bytes of the two (pivot parity) sets of G mailbox rows
-        inline size_t persist_mailbox_bytes(uint32_t G) { return 2 * (size_t)G * persist_mailbox_stride(G) * sizeof(PersistCand); }
+        // (PersistCtl, PersistCand and the mailbox / column-buffer geometry: lqr_large_plan.h)
         __device__ __forceinline__ void st_sc1(double *p, double v)
         {
             __hip_atomic_store(reinterpret_cast<unsigned long long *>(p), (unsigned long long)__double_as_longlong(v), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
@@ -907,7 +870,6 @@ namespace lexls
         {
             return __longlong_as_double((long long)__hip_atomic_load(reinterpret_cast<const unsigned long long *>(p), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT));
         }
-        constexpr int PTC_MIN = 4; // fewest columns per workgroup (= wavefronts per workgroup) of the forms below: sizes the workspace
         /// 16-byte hand-off accesses: a record {norm, pos, tag | column} travels as ONE store and is read as ONE load (observed untorn on gfx950,
         /// MI355X_MICROARCH.md "R2's granule"); payload columns go one {value, tag} per lane.
         /// L2LOCAL = false: writers and readers on any XCD — system-scope store and load (sc0 sc1), served by memory.
@@ -978,11 +940,11 @@ namespace lexls
         /// publications, so any mixing of the payload's words will do.  Cost on configs[1]: 2.07 -> 2.20 ms; -DLEXLS_PERSIST_NOCHECK builds
         /// without, for A/B.  scripts/persist_stamps.py counts granules whose tag is there and whose checksum is not: none seen so far)
         /// record = {norm (8 bytes) | position (20 bits) + 12 checksum bits | tag (16 bits) + column inside the workgroup (8) + 8 checksum bits}
-        constexpr uint32_t kRecNoPos = 0xFFFFFu; // "no candidate"
+        /// (kRecNoPos, the all-ones position, = "no candidate")
         __device__ __forceinline__ uint32_t record_check20(uint32_t lo, uint32_t hi, uint32_t p20, uint32_t tag)
         {
             const uint32_t h = lo ^ hi ^ (p20 << 7) ^ tag;
-            return (h ^ (h >> 20)) & 0xFFFFFu;
+            return (h ^ (h >> 20)) & 0xFFFFFu; // (20 checksum bits: a mask, not the position field's limit)
         }
         __device__ __forceinline__ u32x4 record_pack(double norm, uint32_t pos, uint32_t tag, uint32_t idx)
         {
@@ -1215,7 +1177,8 @@ namespace lexls
                 // ---- wait for the G records of this pivot and pick the winner: wave 0, lane = workgroup (no counter: a record IS its flag) ----
                 if (wave == 0)
                 {
-                    // every lane keeps up to four records (G <= 256) in flight per poll: ONE round trip per poll, not one per record
+                    static_assert(kPersistMaxG == 4 * 64, "a poll holds four records per lane of one wavefront");
+                    // every lane keeps up to four records (G <= kPersistMaxG) in flight per poll: ONE round trip per poll, not one per record
                     const PersistCand *base = cand + ((size_t)par * G + t) * MBS; // this workgroup's row
                     u32x4 q[4] = {u32x4{0, 0, 0, 0}, u32x4{0, 0, 0, 0}, u32x4{0, 0, 0, 0}, u32x4{0, 0, 0, 0}};
                     uint32_t ok = 0;
@@ -1619,7 +1582,6 @@ namespace lexls
 
         /// Trailing -= L * Up (lexlse.h:454-469) on the matrix cores: 64 x 64 output block per workgroup, K in steps of 16 through LDS.
         /// acc = C, then for p ascending acc = fma(-L[i][p], U[p][j], acc): v_mfma_f64_16x16x4_f64 does exactly that for four p at a time.
-        constexpr int GBM = 64, GBN = 64, GBK = 16;
         __global__ __launch_bounds__(256) void large_gemm_mfma(LseArgs a, const LargeState *st, uint32_t level)
         {
             __shared__ double As[GBK * GBM]; // As[k][i] = -L[i][k]
@@ -1704,22 +1666,54 @@ namespace lexls
 
     size_t large_state_bytes(uint32_t batch) { return sizeof(LargeState) * (size_t)batch; }
 
+    // =================================================================================================================
+    // Host half.  What is decided from shapes alone — constants, work-space layout, the grids around a level — is lqr_large_plan.h's;
+    // here are the launches, the device queries and the stream operations.
+    // =================================================================================================================
+    namespace
+    {
+        /// a kernel may take more dynamic LDS than the runtime's default limit (64 KiB) only after it has been told so
+        hipError_t allow_lds(const void *kernel, size_t bytes)
+        {
+            return bytes > 64 * 1024 ? hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes) : hipSuccess;
+        }
+
+        /// the Gauss step below a level (lexlse.h:431-471): L <- A_left R^-1, then Trailing -= L Up on the matrix cores (bit-identical to
+        /// large_gemm).  A ragged batch may hold a problem with small early levels and many rows below: see plan_level for the grids
+        void launch_gauss_step(const LseArgs &a, const LargeState *st, uint32_t level, const LevelPlan &lp, size_t trsm_lds, hipStream_t s)
+        {
+            if (!lp.gauss) return;
+            if (lp.trsm_cols)
+                hipLaunchKernelGGL(large_trsm_cols, dim3(lp.trsm_grid, a.batch), dim3(lp.trsm_block), 0, s, a, st, level);
+            else
+                hipLaunchKernelGGL(large_trsm, dim3(lp.trsm_grid, a.batch), dim3(lp.trsm_block), trsm_lds, s, a, st, level);
+            hipLaunchKernelGGL(large_gemm_mfma, dim3(lp.gemm_grid[0], lp.gemm_grid[1], a.batch), dim3(256), 0, s, a, st, level);
+        }
+
+        /// one small read-back per level: stop launching pivots once no column is left anywhere (skipped problems carry stale state: never
+        /// stop early then)
+        hipError_t read_all_exhausted(const LseArgs &a, const LargeState *st, std::vector<LargeState> &host, hipStream_t s, bool &all_exhausted)
+        {
+            hipError_t e = hipMemcpyAsync(host.data(), st, sizeof(LargeState) * a.batch, hipMemcpyDeviceToHost, s);
+            if (e != hipSuccess) return e;
+            e = hipStreamSynchronize(s);
+            if (e != hipSuccess) return e;
+            all_exhausted = (a.skip == nullptr);
+            for (uint32_t b = 0; b < a.batch && all_exhausted; b++)
+                if (!host[b].exhausted) all_exhausted = false;
+            return hipSuccess;
+        }
+    } // namespace
+
     /// h_level_max[k] = max over the batch of dims[k]; h_rows_max = max rows of one problem
     hipError_t launch_lqr_large(const LseArgs &a, const uint32_t *h_level_max, uint32_t h_rows_max, void *d_state, double *d_norms, hipStream_t s)
     {
-        LargeState *st    = static_cast<LargeState *>(d_state);
-        const uint32_t B  = a.batch, n = a.nVar;
-        hipError_t e      = hipSuccess;
-        auto set_lds      = [&](const void *k, size_t bytes) {
-            if (e == hipSuccess && bytes > 64 * 1024) e = hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes);
-        };
-        uint32_t maxdim = 0;
-        for (uint32_t k = 0; k < a.nObj; k++) maxdim = h_level_max[k] > maxdim ? h_level_max[k] : maxdim;
-        const LargeLds lds    = large_lds_bytes(n, maxdim);
-        const size_t piv_lds = lds.piv, app_lds = lds.app, trsm_lds = lds.trsm;
-        set_lds(reinterpret_cast<const void *>(large_pivot), piv_lds);
-        set_lds(reinterpret_cast<const void *>(large_apply), app_lds);
-        set_lds(reinterpret_cast<const void *>(large_trsm), trsm_lds);
+        LargeState *st   = static_cast<LargeState *>(d_state);
+        const uint32_t B = a.batch, n = a.nVar;
+        const LargeLds lds = large_lds_bytes(n, max_level_dim(h_level_max, a.nObj));
+        hipError_t e       = allow_lds(reinterpret_cast<const void *>(large_pivot), lds.piv);
+        if (e == hipSuccess) e = allow_lds(reinterpret_cast<const void *>(large_apply), lds.app);
+        if (e == hipSuccess) e = allow_lds(reinterpret_cast<const void *>(large_trsm), lds.trsm);
         if (e != hipSuccess) return e;
 
         hipLaunchKernelGGL(large_init, dim3(64, B), dim3(256), 0, s, a, st);
@@ -1731,32 +1725,17 @@ namespace lexls
             if (!all_exhausted)
                 for (uint32_t counter = 0; counter < h_level_max[level]; counter++)
                 {
-                    hipLaunchKernelGGL(large_pivot, dim3(1, B), dim3(NTP), piv_lds, s, a, st, d_norms, level, counter);
-                    hipLaunchKernelGGL(large_apply, dim3((n + TC) / TC, B), dim3(256), app_lds, s, a, st, d_norms, level, counter);
+                    hipLaunchKernelGGL(large_pivot, dim3(1, B), dim3(NTP), lds.piv, s, a, st, d_norms, level, counter);
+                    hipLaunchKernelGGL(large_apply, dim3((n + TC) / TC, B), dim3(256), lds.app, s, a, st, d_norms, level, counter);
                 }
             hipLaunchKernelGGL(large_level_end, dim3((B + 63) / 64), dim3(64), 0, s, a, st, level);
-            // rows below the level: a ragged batch may hold a problem with small early levels and many rows below — the grid spans the
-            // largest row count of the batch, workgroups beyond a problem's own rows return at once (r0 >= M)
-            const uint32_t below = h_rows_max;
-            if (level + 1 < a.nObj && below > 0 && h_level_max[level] > 0) // (a level that is empty in every problem has rank 0: no Gauss step)
-            {
-                if (h_level_max[level] <= 1024)
-                    hipLaunchKernelGGL(large_trsm_cols, dim3((below + TRB - 1) / TRB, B), dim3(((h_level_max[level] + 63) / 64) * 64), 0, s, a, st, level);
-                else
-                    hipLaunchKernelGGL(large_trsm, dim3((below + 63) / 64, B), dim3(64), trsm_lds, s, a, st, level);
-                hipLaunchKernelGGL(large_gemm_mfma, dim3((below + GBM - 1) / GBM, (n + GBN) / GBN, B), dim3(256), 0, s, a, st, level); // bit-identical to large_gemm
-            }
+            launch_gauss_step(a, st, level, plan_level(h_level_max[level], h_rows_max, n, level + 1 == a.nObj), lds.trsm, s);
             e = hipGetLastError();
             if (e != hipSuccess) return e;
-            if (!all_exhausted && level + 1 < a.nObj) // one small read-back per level: stop launching pivots once no column is left anywhere
+            if (!all_exhausted && level + 1 < a.nObj)
             {
-                e = hipMemcpyAsync(host.data(), st, sizeof(LargeState) * B, hipMemcpyDeviceToHost, s);
+                e = read_all_exhausted(a, st, host, s, all_exhausted);
                 if (e != hipSuccess) return e;
-                e = hipStreamSynchronize(s);
-                if (e != hipSuccess) return e;
-                all_exhausted = (a.skip == nullptr); // skipped problems carry stale state: never stop early then
-                for (uint32_t b = 0; b < B && all_exhausted; b++)
-                    if (!host[b].exhausted) all_exhausted = false;
             }
         }
         hipLaunchKernelGGL(large_finish, dim3((B + 63) / 64), dim3(64), 0, s, a, st);
@@ -1764,6 +1743,18 @@ namespace lexls
     }
     namespace
     {
+        /// what a call reads from the environment, once, at its top (per call, not per process: LEXLS_LARGE_PERSIST is switched between solves)
+        struct LargeEnv
+        {
+            int persist; // LEXLS_LARGE_PERSIST: 0 = always a launch per pivot, 1 (default) = the one-launch form where it fits, 2 = raise its `abort` at once
+            bool debug;  // LEXLS_LARGE_DEBUG set: say on stderr what was chosen
+        };
+        LargeEnv read_large_env()
+        {
+            const char *p = std::getenv("LEXLS_LARGE_PERSIST");
+            return LargeEnv{p ? std::atoi(p) : 1, std::getenv("LEXLS_LARGE_DEBUG") != nullptr};
+        }
+
         __global__ __launch_bounds__(64) void persist_probe_xcc(uint32_t *out)
         {
             if (threadIdx.x == 0) out[blockIdx.x] = persist_xcc_id();
@@ -1802,44 +1793,38 @@ namespace lexls
             size_t lds;
             uint32_t G;
         };
-        size_t persist_lds_bytes(int ptc, uint32_t n, uint32_t maxdim) { return 8 * ((size_t)ptc * (maxdim | 1u) + 2 * (size_t)maxdim) + 8 * (size_t)(n + 1); }
-        inline uint32_t persist_colld(uint32_t maxdim) { return (maxdim + 3u) & ~1u; } // a column's granules + {fresh, tail} squared norms
-        template <int NW, int CPW, bool ONEXCD> bool persist_fits(uint32_t G, size_t lds, int xcds)
+        template <int NW, int CPW, bool ONEXCD> bool persist_fits(uint32_t G, size_t lds, int xcds, bool debug)
         {
             // The workgroups of the launch wait for each other, so ALL G of them must be resident at once — on the ONE XCD they run on, in the
             // one-XCD form: checked against what THIS device can hold (occupancy query x CU count; one workgroup fewer per CU than the query says
             // where more than one fits — MI355X_MICROARCH.md, "Residency and cooperative launch").  A plain launch has the same residency as a
             // cooperative one (same guide), and every spin is bounded, so a partitioned or busy device costs a fallback, never a hang.
             int dev = 0, cus = 0, per_cu = 0;
-            if (lds > kMaxLdsBytes || G > 256u) return false;
-            if (lds > 64 * 1024 &&
-                hipFuncSetAttribute(reinterpret_cast<const void *>(fast_level_persist<NW, CPW, ONEXCD>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess)
-                return false;
+            if (!persist_within_limits(G, lds)) return false;
+            if (allow_lds(reinterpret_cast<const void *>(fast_level_persist<NW, CPW, ONEXCD>), lds) != hipSuccess) return false;
             if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess ||
                 hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, fast_level_persist<NW, CPW, ONEXCD>, 64 * NW, lds) != hipSuccess)
                 return false;
             if (ONEXCD) cus /= xcds;
             static const int margin = std::getenv("LEXLS_PERSIST_MARGIN") ? std::atoi(std::getenv("LEXLS_PERSIST_MARGIN")) : 1;
             const long resident     = (long)cus * (per_cu > 1 ? per_cu - margin : per_cu);
-            if (std::getenv("LEXLS_LARGE_DEBUG")) std::fprintf(stderr, "lqr_large: form nw=%d cpw=%d one_xcd=%d: G=%u, %d per CU x %d CUs\n", NW, CPW, (int)ONEXCD, G, per_cu, cus);
+            if (debug) std::fprintf(stderr, "lqr_large: form nw=%d cpw=%d one_xcd=%d: G=%u, %d per CU x %d CUs\n", NW, CPW, (int)ONEXCD, G, per_cu, cus);
             return per_cu >= 1 && resident >= (long)G;
         }
-// the instantiated forms: (wavefronts per workgroup, columns per wavefront)
-#define LEXLS_PERSIST_FORMS(X) X(4, 1) X(4, 2) X(4, 4) X(8, 1) X(8, 2) X(16, 1)
-        PersistForm choose_persist_form(uint32_t n, uint32_t maxdim)
+        PersistForm choose_persist_form(uint32_t n, uint32_t maxdim, bool debug)
         {
             static const char *want   = std::getenv("LEXLS_PERSIST_FORM"); // "nw,cpw"
             static const int want_one = std::getenv("LEXLS_LARGE_ONE_XCD") ? std::atoi(std::getenv("LEXLS_LARGE_ONE_XCD")) : 0; // (measured: no gain, see the kernel's comment)
             const int xcds            = want_one ? persist_xcds() : 0;
             PersistForm f{0, 0, 0, 0, 0};
-            if (n + 1u >= 0xFFFFFu || maxdim >= 0xFFFFu) return f; // (the record's 20-bit position and 16-bit tag fields)
+            if (!persist_fields_fit(n, maxdim)) return f;
             auto try_form = [&](int nw, int cpw, bool one) {
                 if (f.nw) return;
-                const uint32_t ptc = (uint32_t)(nw * cpw), G = (n + ptc) / ptc;
+                const uint32_t ptc = (uint32_t)(nw * cpw), G = persist_grid(n, ptc);
                 const size_t lds   = persist_lds_bytes((int)ptc, n, maxdim);
                 bool ok            = false;
 #define LEXLS_X(NW_, CPW_) \
-    if (nw == NW_ && cpw == CPW_) ok = one ? persist_fits<NW_, CPW_, true>(G, lds, xcds) : persist_fits<NW_, CPW_, false>(G, lds, xcds);
+    if (nw == NW_ && cpw == CPW_) ok = one ? persist_fits<NW_, CPW_, true>(G, lds, xcds, debug) : persist_fits<NW_, CPW_, false>(G, lds, xcds, debug);
                 LEXLS_PERSIST_FORMS(LEXLS_X)
 #undef LEXLS_X
                 if (ok) f = PersistForm{nw, cpw, one ? xcds : 0, lds, G};
@@ -1857,83 +1842,62 @@ namespace lexls
             try_form(4, 1, false);
             return f;
         }
-        template <typename... Args> void launch_persist(const PersistForm &pf, size_t lds, hipStream_t s, Args... args)
+        template <typename... Args> void launch_persist(const PersistForm &pf, hipStream_t s, Args... args)
         {
             const dim3 grid(pf.xcds ? (uint32_t)pf.xcds * pf.G : pf.G);
 #define LEXLS_X(NW_, CPW_)                                                                                                      \
     if (pf.nw == NW_ && pf.cpw == CPW_)                                                                                         \
     {                                                                                                                           \
         if (pf.xcds)                                                                                                            \
-            hipLaunchKernelGGL((fast_level_persist<NW_, CPW_, true>), grid, dim3(64 * NW_), lds, s, args..., pf.G);             \
+            hipLaunchKernelGGL((fast_level_persist<NW_, CPW_, true>), grid, dim3(64 * NW_), pf.lds, s, args..., pf.G);          \
         else                                                                                                                    \
-            hipLaunchKernelGGL((fast_level_persist<NW_, CPW_, false>), grid, dim3(64 * NW_), lds, s, args..., pf.G);            \
+            hipLaunchKernelGGL((fast_level_persist<NW_, CPW_, false>), grid, dim3(64 * NW_), pf.lds, s, args..., pf.G);         \
     }
             LEXLS_PERSIST_FORMS(LEXLS_X)
 #undef LEXLS_X
         }
     } // namespace
 
-    size_t large_fast_workspace_bytes(uint32_t batch, uint32_t n, uint32_t cap, uint32_t maxdim)
-    {
-        const size_t ps = (size_t)cap * (n + 1);
-        const size_t G = (n + PTC_MIN) / PTC_MIN; // most workgroups of the one-launch-per-level forms
-        return 8 * ((size_t)batch * ps + 3 * (size_t)batch * n + (size_t)batch * maxdim * maxdim) + 4 * 2 * (size_t)batch * (n + 1) + 2 * sizeof(LargeState) * (size_t)batch + 256 +
-               sizeof(PersistCtl) + persist_mailbox_bytes((uint32_t)G) + 16 * 2 * G * (size_t)((maxdim + 3u) & ~1u) + 64;
-    }
+    size_t large_fast_workspace_bytes(uint32_t batch, uint32_t n, uint32_t cap, uint32_t maxdim) { return fast_workspace_layout(batch, n, cap, maxdim).total; }
 
-    /// the fast large path (see the comment above fast_level_begin); gemm_only_mfma: the bit-exact multi-launch path with its trailing update on the matrix cores
+    /// the fast large path (see the comment above fast_level_begin); d_ws: large_fast_workspace_bytes, aligned as hipMalloc aligns
     hipError_t launch_lqr_large_fast(const LseArgs &a, const uint32_t *h_level_max, uint32_t h_rows_max, void *d_ws, hipStream_t s, uint32_t *levels)
     {
         if (levels) levels[0] = levels[1] = 0u;
-        const uint32_t B = a.batch, n = a.nVar, cap = a.cap;
-        uint32_t maxdim  = 0;
-        for (uint32_t k = 0; k < a.nObj; k++) maxdim = h_level_max[k] > maxdim ? h_level_max[k] : maxdim;
-        const size_t ps = (size_t)cap * (n + 1);
+        const LargeEnv env = read_large_env();
+        const uint32_t B = a.batch, n = a.nVar;
+        const uint32_t maxdim  = max_level_dim(h_level_max, a.nObj);
+        const FastWorkspace ws = fast_workspace_layout(B, n, a.cap, maxdim);
+        char *w                = static_cast<char *>(d_ws);
         FastBuffers fb;
-        char *w      = static_cast<char *>(d_ws);
-        fb.W[0]      = a.fac;
-        fb.W[1]      = reinterpret_cast<double *>(w);
-        w += 8 * (size_t)B * ps;
-        fb.norms[0] = reinterpret_cast<double *>(w);
-        w += 8 * (size_t)B * n;
-        fb.norms[1] = reinterpret_cast<double *>(w);
-        w += 8 * (size_t)B * n;
-        fb.D = reinterpret_cast<double *>(w);
-        w += 8 * (size_t)B * n;
-        fb.E = reinterpret_cast<double *>(w);
-        w += 8 * (size_t)B * maxdim * maxdim;
-        fb.eld   = maxdim;
-        fb.st[0] = reinterpret_cast<LargeState *>(w);
-        w += sizeof(LargeState) * (size_t)B;
-        fb.st[1] = reinterpret_cast<LargeState *>(w);
-        w += sizeof(LargeState) * (size_t)B;
-        fb.pos[0] = reinterpret_cast<uint32_t *>(w);
-        w += 4 * (size_t)B * (n + 1);
-        fb.pos[1] = reinterpret_cast<uint32_t *>(w);
-        w += 4 * (size_t)B * (n + 1);
-        w = reinterpret_cast<char *>((reinterpret_cast<uintptr_t>(w) + 63) & ~(uintptr_t)63);
-        PersistCtl *ctl = reinterpret_cast<PersistCtl *>(w);
-        w += sizeof(PersistCtl);
+        fb.W[0] = a.fac;
+        fb.W[1] = reinterpret_cast<double *>(w + ws.W1);
+        fb.D    = reinterpret_cast<double *>(w + ws.D);
+        fb.E    = reinterpret_cast<double *>(w + ws.E);
+        fb.eld  = maxdim;
+        for (int i = 0; i < 2; i++)
+        {
+            fb.norms[i] = reinterpret_cast<double *>(w + ws.norms[i]);
+            fb.st[i]    = reinterpret_cast<LargeState *>(w + ws.st[i]);
+            fb.pos[i]   = reinterpret_cast<uint32_t *>(w + ws.pos[i]);
+        }
+        PersistCtl *ctl   = reinterpret_cast<PersistCtl *>(w + ws.ctl);
+        PersistCand *cand = reinterpret_cast<PersistCand *>(w + ws.mailbox);
+        double *colbuf    = reinterpret_cast<double *>(w + ws.colbuf);
         // single problems: the pivots of a level in ONE launch (fast_level_persist).  Its hand-offs spin (bounded); a launch whose spins ran out
         // raises `abort`, ends, and the level is redone with a launch per pivot (LEXLS_LARGE_PERSIST=0: always a launch per pivot; =2: raise
         // `abort` at once, for the tests).  Form of the launch: on ONE XCD when the device's workgroup placement was seen to be round robin
         // (persist_xcds) and that XCD can hold all workgroups (LEXLS_LARGE_ONE_XCD=0: never); LEXLS_PERSIST_FORM="nw,cpw" picks another instantiation.
-        const PersistForm pf = choose_persist_form(n, maxdim);
-        const uint32_t G     = pf.nw ? pf.G : 1u;
-        if (std::getenv("LEXLS_LARGE_DEBUG")) std::fprintf(stderr, "lqr_large: in-launch form nw=%d cpw=%d xcds=%d G=%u lds=%zu\n", pf.nw, pf.cpw, pf.xcds, pf.G, pf.lds);
-        PersistCand *cand    = reinterpret_cast<PersistCand *>(w);
-        w += persist_mailbox_bytes((n + PTC_MIN) / PTC_MIN);
-        double *colbuf           = reinterpret_cast<double *>(w);
-        const size_t persist_lds = pf.lds;
-        bool persist = B == 1 && pf.nw != 0 && a.skip == nullptr && !(std::getenv("LEXLS_LARGE_PERSIST") && std::atoi(std::getenv("LEXLS_LARGE_PERSIST")) == 0);
-        const bool persist_test_abort = persist && std::getenv("LEXLS_LARGE_PERSIST") && std::atoi(std::getenv("LEXLS_LARGE_PERSIST")) == 2;
+        const PersistForm pf = choose_persist_form(n, maxdim, env.debug);
+        if (env.debug) std::fprintf(stderr, "lqr_large: in-launch form nw=%d cpw=%d xcds=%d G=%u lds=%zu\n", pf.nw, pf.cpw, pf.xcds, pf.G, pf.lds);
+        const bool persist            = B == 1 && pf.nw != 0 && a.skip == nullptr && env.persist != 0;
+        const bool persist_test_abort = persist && env.persist == 2;
 
-        hipError_t e         = hipSuccess;
-        const size_t step_lds = 16 * (size_t)maxdim;
+        const size_t step_lds = step_lds_bytes(maxdim);
         const LargeLds lds    = large_lds_bytes(n, maxdim);
         if (step_lds > kMaxLdsBytes) return hipErrorInvalidValue;
-        if (step_lds > 64 * 1024) e = hipFuncSetAttribute(reinterpret_cast<const void *>(fast_step), hipFuncAttributeMaxDynamicSharedMemorySize, (int)step_lds);
-        if (e == hipSuccess && lds.trsm > 64 * 1024) e = hipFuncSetAttribute(reinterpret_cast<const void *>(large_trsm), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds.trsm);
+        hipError_t e = allow_lds(reinterpret_cast<const void *>(fast_step), step_lds);
+        if (e == hipSuccess) e = allow_lds(reinterpret_cast<const void *>(large_trsm), lds.trsm);
         if (e != hipSuccess) return e;
 
         hipLaunchKernelGGL(large_init, dim3(64, B), dim3(256), 0, s, a, fb.st[0]);
@@ -1942,12 +1906,13 @@ namespace lexls
         uint32_t cur = 0, pp = 0;
         for (uint32_t level = 0; level < a.nObj; level++)
         {
+            const LevelPlan lp = plan_level(h_level_max[level], h_rows_max, n, level + 1 == a.nObj);
             hipLaunchKernelGGL(fast_level_begin, dim3((n + 4) / 4, B), dim3(256), 0, s, a, fb, cur, pp, level);
             bool run_steps = false;
             if (!all_exhausted && persist && h_level_max[level] > 0) // (an empty level has no pivot: nothing to launch, no state parity to flip)
             {
                 // the tags restart with every level (and every call): records and column granules of earlier pivots must not match them
-                e = hipMemsetAsync(ctl, 0, sizeof(PersistCtl) + persist_mailbox_bytes((n + PTC_MIN) / PTC_MIN) + 16 * 2 * (size_t)G * persist_colld(maxdim), s);
+                e = hipMemsetAsync(ctl, 0, ws.clear_end(pf.G) - ws.ctl, s);
                 if (e != hipSuccess) return e;
                 if (persist_test_abort)
                 {
@@ -1955,13 +1920,13 @@ namespace lexls
                     e = hipMemcpyAsync(&ctl->abort, &one, 4, hipMemcpyHostToDevice, s);
                     if (e != hipSuccess) return e;
                 }
-                launch_persist(pf, persist_lds, s, a, fb, ctl, cand, colbuf, persist_colld(maxdim), cur, pp, level);
+                launch_persist(pf, s, a, fb, ctl, cand, colbuf, ws.colld, cur, pp, level);
                 PersistCtl hc;
                 e = hipMemcpyAsync(&hc, ctl, sizeof(hc), hipMemcpyDeviceToHost, s);
                 if (e != hipSuccess) return e;
                 e = hipStreamSynchronize(s);
                 if (e != hipSuccess) return e;
-                if (hc.abort && std::getenv("LEXLS_LARGE_DEBUG")) std::fprintf(stderr, "lqr_large: level %u: the in-launch form gave up, a launch per pivot instead\n", level);
+                if (hc.abort && env.debug) std::fprintf(stderr, "lqr_large: level %u: the in-launch form gave up, a launch per pivot instead\n", level);
                 if (hc.abort) // a hand-off ran out of spins (workgroups not co-resident?): nothing of the level was committed — a launch per pivot instead
                     run_steps = true;
                 else
@@ -1976,30 +1941,18 @@ namespace lexls
                     hipLaunchKernelGGL(fast_step, dim3((n + FTC) / FTC, B), dim3(FNT), step_lds, s, a, fb, cur, pp, counter);
                     pp ^= 1u;
                 }
-            hipLaunchKernelGGL(fast_level_end, dim3((h_rows_max + 1023) / 1024, n + 1, B), dim3(256), 0, s, a, fb, cur, pp, level);
+            hipLaunchKernelGGL(fast_level_end, dim3(lp.level_end_grid, n + 1, B), dim3(256), 0, s, a, fb, cur, pp, level);
             cur ^= 1u;
             hipLaunchKernelGGL(fast_level_commit, dim3((B + 63) / 64), dim3(64), 0, s, a, fb, pp);
-            if (level + 1 < a.nObj && h_rows_max > 0 && h_level_max[level] > 0) // (a level that is empty in every problem has rank 0: no Gauss step)
-            {
-                LseArgs ac = a;
-                ac.fac     = fb.W[cur];
-                if (h_level_max[level] <= 1024)
-                    hipLaunchKernelGGL(large_trsm_cols, dim3((h_rows_max + TRB - 1) / TRB, B), dim3(((h_level_max[level] + 63) / 64) * 64), 0, s, ac, fb.st[pp], level);
-                else
-                    hipLaunchKernelGGL(large_trsm, dim3((h_rows_max + 63) / 64, B), dim3(64), lds.trsm, s, ac, fb.st[pp], level);
-                hipLaunchKernelGGL(large_gemm_mfma, dim3((h_rows_max + GBM - 1) / GBM, (n + GBN) / GBN, B), dim3(256), 0, s, ac, fb.st[pp], level);
-            }
+            LseArgs ac = a;
+            ac.fac     = fb.W[cur];
+            launch_gauss_step(ac, fb.st[pp], level, lp, lds.trsm, s);
             e = hipGetLastError();
             if (e != hipSuccess) return e;
             if (!all_exhausted && level + 1 < a.nObj)
             {
-                e = hipMemcpyAsync(host.data(), fb.st[pp], sizeof(LargeState) * B, hipMemcpyDeviceToHost, s);
+                e = read_all_exhausted(a, fb.st[pp], host, s, all_exhausted);
                 if (e != hipSuccess) return e;
-                e = hipStreamSynchronize(s);
-                if (e != hipSuccess) return e;
-                all_exhausted = (a.skip == nullptr);
-                for (uint32_t b = 0; b < B && all_exhausted; b++)
-                    if (!host[b].exhausted) all_exhausted = false;
             }
         }
         if (cur != 0) hipLaunchKernelGGL(fast_copy_back, dim3(64, B), dim3(256), 0, s, a, fb, cur);

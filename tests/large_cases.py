@@ -55,10 +55,19 @@ CASES = {
     "edges128": dict(n=128, dims=EDGE_DIMS, seed=20280107, problems=[(EDGE_DIMS, EDGE_RANKS), ([99, 0, 0, 40, 24], [9, 0, 0, 16, 8])]),
 }
 
+# Work-space reuse (test_workspace_reuse of tests/test_gpu_large_cases.py): ONE handle of capacities [330, 100] solves reuse300, then reuse330
+# (largest level 330: the work space grows), then reuse300 again (the larger work space is kept and laid out for the smaller shape).  Not among
+# CASES: they sit on no new side of a switch; same shape of spec, built by build() like a case.
+REUSE = {
+    "reuse300": dict(n=60, dims=[330, 100], seed=20280108, problems=[([300, 100], [25, 20]), ([300, 100], [30, 15])]),
+    "reuse330": dict(n=60, dims=[330, 100], seed=20280109, problems=[([330, 70], [25, 20]), ([330, 70], [30, 15])]),
+}
+SPECS = {**CASES, **REUSE}
+
 
 def draw(name):
     """(lod (batch, n + 1, cap), dims (batch, nObj)) of a case"""
-    c = CASES[name]
+    c = SPECS[name]
     n, caps, seed = c["n"], list(c["dims"]), c["seed"]
     B, cap = len(c["problems"]), sum(caps)
     lod = np.full((B, n + 1, cap), np.nan)  # a problem's rows packed level after level; NaN behind them (never read)
@@ -77,7 +86,7 @@ def draw(name):
 
 
 def _run(name, lod, dims, tol=TOL):
-    c = CASES[name]
+    c = SPECS[name]
     return oracle.lse_run(lod, dims, c["n"], maxdim=np.asarray(c["dims"], np.uint32), tol=tol, nthreads=4)
 
 
@@ -90,7 +99,7 @@ def build(name):
     """the case `name`: dict(name, n, caps, lod, dims, ref (the oracle's result for the batch), stable (per problem: ranks, first columns and
     permutation the same at TOL / 10 and 10 TOL), sens (per problem: one-ulp sensitivity of x), forced (the ranks the data were built for, None:
     iid))"""
-    c = CASES[name]
+    c = SPECS[name]
     lod, dims = draw(name)
     ref = _run(name, lod, dims)
     lo, hi = _run(name, lod, dims, TOL / FACTOR), _run(name, lod, dims, TOL * FACTOR)

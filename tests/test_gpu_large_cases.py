@@ -11,24 +11,28 @@ tests/test_gpu_parity.py compares them.  lexls_lse_last_large_levels tells the o
 LEXLS_LARGE_PERSIST = 1 every level reached is committed inside its launch and none is redone (n1030: no form fits G = 258 workgroups, both
 counts 0), under 2 every level reached is redone, under 0 and for a batch both counts are 0.
 
-What would make which case fail (one-token slips in lqr_large.hip, by reasoning):
-    fast_step :818 `i = lane + 64u * FRC` -> `64u * (FRC + 1)`  rows 256 .. 319 leave the dot product: rows1030, rows1024, rows257 (R = 257), rows330 —
-                                        batches and modes 0 / 2 (x off by O(1); :828 likewise: rows of the trailing columns not updated)
-    fast_step :680 `k < n` -> `k < 1024`  columns 1024 .. 1029 are never candidates: n1030's first pivots (permutation); `p < bp` -> `p <= bp` at :686: the
-                                        tie 1000 / 1027 goes to the later position
-    large_pivot :118 `k += NTP` second trip dropped: n1030 under policy 5 (permutation); :163 / :208 `i += NTP`: rows1030 under policy 5 (rows 1024 ..
-                                        1029 leave the norm / the reflector)
-    fast_level_persist :1352 `i = tid + CR * NT` -> `(CR + 1) * NT`  rows 256 .. 511 of the pivot column are not fetched: rows257, rows330, rows1024, rows1030 alone
-                                        under mode 1; `i += NT` -> `i += 2 * NT`: rows1024 / rows1030 only
-    persist_fits :1814 `G > 256u` -> `G > 512u`  n1030 alone would run a form whose polls hold 4 x 64 records: the counters (in_launch 0 expected)
-    launchers :1743 / :1986 `<= 1024` -> `< 1024`  rows1024 would take large_trsm: same numbers, so only a fault in it would show — the boundary is pinned
-                                        from the other side by `<= 1024` -> `<= 1030`: rows1030 would launch large_trsm_cols with 1088 threads (launch error)
+What would make which case fail (one-token slips in lqr_large.hip and lqr_large_plan.h, by reasoning; the constants are lqr_large_plan.h's):
+    fast_step, tail loop of the dot product `i = lane + 64u * FRC` -> `64u * (FRC + 1)`  rows 256 .. 319 leave the dot product: rows1030, rows1024, rows257 (R = 257),
+                                        rows330 — batches and modes 0 / 2 (x off by O(1); the tail loop of the update likewise: rows of the trailing columns not updated)
+    fast_step, second search loop (beyond NCAND = kStepCandWindow / FNT candidates per thread) `k < n` -> `k < 1024`  columns 1024 .. 1029 are never candidates:
+                                        n1030's first pivots (permutation); `p < bp` -> `p <= bp` in that loop: the tie 1000 / 1027 goes to the later position
+    large_pivot, search loop `k += NTP` second trip dropped: n1030 under policy 5 (permutation); its column staging / column swap loops `i += NTP`: rows1030
+                                        under policy 5 (rows 1024 .. 1029 leave the norm / the reflector)
+    fast_level_persist, one-by-one granule loop `i = tid + CR * NT` -> `(CR + 1) * NT`  rows 256 .. 511 of the pivot column are not fetched: rows257, rows330, rows1024,
+                                        rows1030 alone under mode 1; `i += NT` -> `i += 2 * NT`: rows1024 / rows1030 only
+    persist_within_limits `G > kPersistMaxG` with kPersistMaxG 256 -> 512  n1030 alone would run a form whose polls hold 4 x 64 records: the counters (in_launch 0 expected)
+    plan_level `level_max <= kTrsmColsMax` -> `<`  rows1024 would take large_trsm: same numbers, so only a fault in it would show — the boundary is pinned
+                                        from the other side by kTrsmColsMax 1024 -> 1030: rows1030 would launch large_trsm_cols with 1088 threads (launch error)
     large_trsm (never run before)        any slip: rows1030 under both policies (the rows below level 0 feed level 1's ranks and x)
-    fast_level_end grid `(h_rows_max + 1023) / 1024` -> `/ 1024 + 0` or the stride `gridDim.x * 256` -> `256`  rows1030 / rows1024 (rows beyond 1024 not copied)
-    large_gemm_mfma grid `(n + GBN) / GBN` -> `(n + GBN - 1) / GBN`  edges128 loses the right-hand side column (n + 1 = 129): x; edges127 pins the exact fit
-    large_trsm_cols `(below + TRB - 1) / TRB` -> `below / TRB`  the 65th row below level 0 of edges127 / edges128; TCH chunks: ranks 17 and 5 there
-    all_exhausted :1759 / :2002 `!host[b].exhausted` -> `host[b].exhausted`  rows1030 / rows330 batches: level 1 of the live problems is never factorized (ranks)
+    plan_level level_end_grid `(rows_max + kLevelEndRows - 1) / kLevelEndRows` -> `rows_max / kLevelEndRows`, or fast_level_end's stride `gridDim.x * 256` -> `256`
+                                        rows1030 / rows1024 (rows beyond 1024 not copied)
+    plan_level gemm_grid[1] `(n + GBN) / GBN` -> `(n + GBN - 1) / GBN`  edges128 loses the right-hand side column (n + 1 = 129): x; edges127 pins the exact fit
+    plan_level trsm_grid `(rows_max + TRB - 1) / TRB` -> `rows_max / TRB`  the 65th row below level 0 of edges127 / edges128; TCH chunks: ranks 17 and 5 there
+    read_all_exhausted `!host[b].exhausted` -> `host[b].exhausted`  rows1030 / rows330 batches: level 1 of the live problems is never factorized (ranks)
     counters                            mode 1 silently falling back (abort on every level) gives redone > 0; mode 2 not aborting gives in_launch > 0
+    fast_workspace_layout, a piece short (st[1] taking one record for the batch, E taking maxdim x n, the column buffer one granule per row short) or
+                                        FastWorkspace::clear_end short of the column buffer: tests/test_large_plan.py on the CPU; on the GPU test_workspace_reuse — the third
+                                        solve runs in a work space that holds the second's records, tags and essential parts at other offsets
 
 MEASURED on MI355X (policy 0; error = |x - x_oracle|_inf / max(1, |x_oracle|_inf), largest over the case's problems; ratio = error / one-ulp
 sensitivity; every bit-exact comparison under policy 5 held):
@@ -185,3 +189,27 @@ def test_one_problem_in_launch(hip, monkeypatch, name):
         assert in_launch == 0
     else:
         assert in_launch == L.levels_reached(case) > 0
+
+
+# ---- one handle, three shapes: the work space grows, then is reused under a smaller layout ----
+@pytest.mark.parametrize("batch", [1, 2])
+def test_workspace_reuse(hip, monkeypatch, batch):
+    """One handle with n = 60 and capacities [330, 100] solves level dimensions [300, 100], [330, 70] and [300, 100] again (tests/large_cases.py,
+    REUSE): the work space is allocated for the first, grows for the second (largest level 330) and is kept for the third, whose layout
+    (fast_workspace_layout) is the first's again inside the larger allocation — every piece at an exact offset, nothing of the slack the sum
+    formula used to add.  Batch 1 takes the pivots of a level in one launch (the records, tags and column granules of the solve before are
+    cleared by the layout's range), batch 2 a launch per pivot.  Every result under contract (T) against the oracle; tests/test_large_cases.py
+    asserts on the CPU that all of them are planned lqr_large<step-per-pivot,mfma> and that 100 x sensitivity < 1e-10."""
+    monkeypatch.setenv("LEXLS_LARGE_PERSIST", "1")
+    sl = slice(0, batch)
+    first = L.build("reuse300")
+    s = hip.BatchedLexLSE(batch, first["n"], first["caps"])
+    s.set_kernel_policy(0)
+    for step, name in enumerate(("reuse300", "reuse330", "reuse300")):
+        case = L.build(name)
+        s.setObjDim(case["dims"][sl])
+        s.setProblem(case["lod"][sl])
+        s.factorize_solve(keep_factor=True)
+        assert s.last_kernel() == FAST
+        assert_tolerance_contract(outputs(s), case, f"work-space reuse, batch {batch}, solve {step} ({name})", sl)
+        assert s.last_large_levels() == ((L.levels_reached(case), 0) if batch == 1 else (0, 0))

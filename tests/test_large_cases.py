@@ -2,13 +2,14 @@
 tests/test_gpu_large_cases.py compare the large path's kernels with these cases, so a case that sat on the tested side of a switch after
 all — or whose ranks a kernel's rounding may legitimately move — would let them pass on anything.
 
-The constants below MIRROR lexls_amd/csrc/lqr_large.hip (and lexls_lds.h); side() computes from them, per case, which side of each switch of
+The constants below are READ from lexls_amd/csrc/lqr_large_plan.h (tests/large_plan.py runs tests/large_plan_check.cpp, which prints them: the
+header the kernels and launchers take them from is the only place that states a value); side() computes from them, per case, which side of each switch of
 the kernels and launchers the case is on, and the union of the cases must hold both sides of every row:
     step R>256     fast_step: rows left in the level beyond the 64 x FRC a lane keeps in registers (the tail loops of the dot product and of
                    the update) — every problem of a batch, and problem 0 alone under LEXLS_LARGE_PERSIST = 0 / 2
     persist R>256  fast_level_persist: beyond the one granule per thread of the batch (64 x NW), fetched one by one — problem 0 alone, default
     n>1024         fast_step's second search loop (candidates beyond NCAND per thread), large_pivot's second trip over the columns
-    G>256          persist_fits: no one-launch form, a single problem takes a launch per pivot
+    G>256          persist_within_limits (kPersistMaxG): no one-launch form, a single problem takes a launch per pivot
     level>1024     launchers: large_trsm (a row per lane, multipliers in LDS) instead of large_trsm_cols behind a level
     pivot R>1024   large_pivot's second trip over the rows of a level
     rows>1024      fast_level_end's second block of rows
@@ -41,18 +42,21 @@ import numpy as np
 import pytest
 
 import large_cases as L
+import large_plan as LP
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
-# ---- mirrors of lexls_amd/csrc/lqr_large.hip ----
-FRC, FNT = 4, 256             # fast_step: rows per lane in registers, threads (NCAND = 1024 / FNT candidates per thread: n <= 1024)
-NW = 4                        # fast_level_persist<4,1>: wavefronts = columns per workgroup; one granule per thread in the batch
-NTP = 1024                    # large_pivot's threads
-G_MAX = 256                   # persist_fits
-TRSM_COLS_MAX = 1024          # launchers: large_trsm_cols up to this level dimension
-LEVEL_END_ROWS = 1024         # fast_level_end: rows per block
-GBM = GBN = 64                # large_gemm_mfma's tile
-TRB, TCH = 8, 16              # large_trsm_cols: rows per workgroup, multipliers per chunk
+# ---- the constants of lexls_amd/csrc/lqr_large_plan.h, as tests/large_plan_check.cpp prints them ----
+K = LP.constants()
+FRC, FNT = K["FRC"], K["FNT"]            # fast_step: rows per lane in registers, threads
+NW = K["PTC_MIN"]                        # fast_level_persist<PTC_MIN,1>, the default form: wavefronts = columns per workgroup; one granule per thread in the batch
+NTP = K["NTP"]                           # large_pivot's threads
+ONE_TRIP = max(K["kStepCandWindow"], NTP)  # columns beyond BOTH fast_step's candidates in registers and one trip of large_pivot's search
+G_MAX = K["kPersistMaxG"]                # persist_within_limits
+TRSM_COLS_MAX = K["kTrsmColsMax"]        # plan_level: large_trsm_cols up to this level dimension
+LEVEL_END_ROWS = K["kLevelEndRows"]      # fast_level_end: rows per block
+GBM, GBN = K["GBM"], K["GBN"]            # large_gemm_mfma's tile
+TRB, TCH = K["TRB"], K["TCH"]            # large_trsm_cols: rows per workgroup, multipliers per chunk
 
 
 def pivots(case, b):
@@ -68,7 +72,7 @@ def side(case):
     s = {}
     s["step R>256"] = {R > 64 * FRC for b in range(B) for _, R in pivots(case, b)}
     s["persist R>256"] = {R > 64 * NW for _, R in pivots(case, 0)} if G <= G_MAX else set()
-    s["n>1024"] = {n > 1024 and max(case["ref"]["perm"][b, :int(rank[b].sum())].max() for b in range(B)) >= 1024}
+    s["n>1024"] = {n > ONE_TRIP and max(case["ref"]["perm"][b, :int(rank[b].sum())].max() for b in range(B)) >= ONE_TRIP}
     s["G>256"] = {G > G_MAX}
     level_max = dims.max(axis=0)
     s["level>1024"] = {int(level_max[k]) > TRSM_COLS_MAX for k in range(nobj - 1) if level_max[k] > 0}
@@ -155,9 +159,9 @@ def test_n1030_first_pivots_lie_beyond_1024_and_the_tie_goes_to_the_first_positi
     case = L.build("n1030")
     n, perm, lod = case["n"], case["ref"]["perm"], case["lod"]
     for b in range(lod.shape[0]):
-        assert (perm[b, :6] >= 1024).sum() >= 4, perm[b, :8]
+        assert (perm[b, :6] >= ONE_TRIP).sum() >= 4, perm[b, :8]
     first, second = case["tie"]
-    assert first < 1024 <= second and np.array_equal(lod[0, first], lod[0, second])
+    assert first < ONE_TRIP <= second and np.array_equal(lod[0, first], lod[0, second])
     at = list(range(n))  # physical column at every position, through the swaps of lexlse.h:222-232
     taken = []
     for c in range(int(case["ref"]["totalrank"][0])):
@@ -175,6 +179,31 @@ def query(i, n, caps, dims, policy):
     uniform = int(d.max()) if d.min() == d.max() else 0
     vals = ["lse", i, d.shape[0], n, len(caps), sum(caps), uniform, max(int(d.sum(axis=1).max()), 1), int(d.max()), 0, 0, 16, 1, 1, policy, 0, 0, 2048, 0]
     return " ".join(str(v) for v in vals)
+
+
+def test_the_reuse_cases_are_planned_on_the_step_per_pivot_path_and_well_conditioned(tmp_path):
+    """what test_workspace_reuse of tests/test_gpu_large_cases.py relies on: reuse300 / reuse330, as a batch of two and problem 0 alone, are planned
+    lqr_large<step-per-pivot,mfma> under policy 0, and the plain 1e-10 of contract (T) is their bound; pivots stable around the tolerance"""
+    cxx = shutil.which("g++")
+    if cxx is None:
+        pytest.skip("no g++ on this machine")
+    exe = str(tmp_path / "plan")
+    build = subprocess.run([cxx, "-std=c++17", "-O1", "-I", os.path.join(ROOT, "lexls_amd", "csrc"), os.path.join(ROOT, "tests", "dispatch_plan_check.cpp"), "-o", exe],
+                           capture_output=True, text=True)
+    assert build.returncode == 0, build.stderr
+    lines = []
+    for name in L.REUSE:
+        c = L.build(name)
+        print(L.summary(c))
+        assert (c["sens"] > 0).all() and (100.0 * c["sens"] < 1e-10).all(), (name, c["sens"])
+        assert c["stable"].all(), name
+        assert [r.tolist() for r in c["ref"]["rank"]] == c["forced"], name
+        assert L.levels_reached(c) == 2  # both levels look for pivots: the Gauss step below level 0 runs
+        for dims in (c["dims"], c["dims"][:1]):
+            lines.append(query(len(lines), c["n"], c["caps"], dims, 0))
+    run = subprocess.run([exe], input="\n".join(lines) + "\n", capture_output=True, text=True, timeout=60)
+    assert run.returncode == 0, run.stderr
+    assert [ln.split("|")[1] for ln in run.stdout.splitlines()] == ["lqr_large<step-per-pivot,mfma>"] * len(lines), run.stdout
 
 
 def test_planned_on_the_large_path(tmp_path):
