@@ -307,6 +307,7 @@ namespace LexLS
             Index getObjectivesCount() const { return nObj; }
             Index getObjDim(Index ObjIndex) const { return objectives[ObjIndex].getDim(); }
             std::vector<WorkingSetLogEntry> &getWorkingSetLog() { return working_set_log; }
+            const std::vector<WorkingSetLogEntry> &getWorkingSetLog() const { return working_set_log; }
             Index getTotalRank() { return lexlse.getTotalRank(); }
             TerminationStatus getStatus() const { return status; }
             LSE &getLexLSE() { return lexlse; }

@@ -514,6 +514,44 @@ int lexls_lsi_batch_get_lambda(lexls_lsi_batch_t b, double *h_lambda);
  * Whatever path served the run: host path, lock-step stages, persistent launch, one by one through the single-problem driver.  All zeros after a
  * run without cycling handling.  Errors: LEXLS_ERR_INVALID before the first run or after a failed one. */
 int lexls_lsi_batch_get_cycling_counters(lexls_lsi_batch_t b, uint32_t *h_counts);
+/* LexLSI::getWorkingSetLog() (lexlsi.h:739; the entries verifyWorkingSet makes at :1186-1230, which the MEX front end returns in its fifth output)
+ * for every instance of a batch: one entry per working-set change — which constraint of which objective was added or removed, with which type,
+ * at which step length or multiplier, whether the cycling handler relaxed a bound on it, and the rank of that iteration's factorization.
+ * Row layout of lexls_lsi_debug::log: LEXLS_LSI_LOG_FIELDS int32 per entry, at the indices below, plus one double (alpha_or_lambda).
+ *   ADD (lexlsi.h:1188-1194): the blocking constraint, its type (CTR_ACTIVE_LB / _UB), alpha_or_lambda = the step length alpha.
+ *   REMOVE (lexlsi.h:1214-1222): the constraint's index in its objective, ctr_type = CTR_INACTIVE (0), alpha_or_lambda = lambda_wrong_sign, the
+ *     largest wrong-sign multiplier of the removal search (lexlsi.h:1115-1139) — 0 under deactivate_first_wrong_sign (lexlsi.h:1069).
+ *   cycling_detected (lexlsi.h:1252-1259): 1 on the ADD that closed a REMOVE -> ADD circle and relaxed a bound; the ADD that ends the run at
+ *     cycling_max_counter (PROBLEM_SOLVED_CYCLING_HANDLING) is logged with 0, as CyclingHandler::update reports it (cycling.h:32-65).
+ * lexls_lsi_batch_set_working_set_log: max_entries > 0 switches the log on for every later run of the object — lexls_lsi_batch_run,
+ * lexls_lsi_batch_run_device, lexls_lsi_batch_run_device_ex — with room for max_entries entries per instance; 0 switches it off and frees the
+ * buffers (the batch is then what it is without this call).  Every path a run can take is served and none is refused because the log is on:
+ * the resident iterations (persistent launch, lock-step stages, phase 1 on the host or on the device) write their entries on the device where
+ * the working-set change is decided; what an instance does on the host before it becomes resident (iteration 0), and everything of an instance
+ * that never does (host path: LEXLS_LSI_RESIDENT=0, regularization type 7, cycling handling of a regularized run; the one-by-one path), is
+ * logged by its host LexLSI object (ParametersLexLSI::log_working_set_enabled) and merged in.  Results and kernels of a run are the same with
+ * the log on or off.  Errors: LEXLS_ERR_INVALID for a null handle. */
+#define LEXLS_LSI_LOG_FIELDS 5
+enum
+{
+    LEXLS_LSI_LOG_OBJ_INDEX        = 0,
+    LEXLS_LSI_LOG_CTR_INDEX        = 1,
+    LEXLS_LSI_LOG_CTR_TYPE         = 2,
+    LEXLS_LSI_LOG_CYCLING_DETECTED = 3,
+    LEXLS_LSI_LOG_RANK             = 4
+};
+int lexls_lsi_batch_set_working_set_log(lexls_lsi_batch_t b, uint32_t max_entries);
+/* The log of the LAST run: h_log receives batch x max_entries x LEXLS_LSI_LOG_FIELDS int32, h_alpha batch x max_entries doubles, h_counts
+ * `batch` values = the entries each instance produced (getWorkingSetLog().size()).  A count may exceed max_entries: the entries beyond the
+ * capacity are dropped, as lexls_lsi_solve_debug drops those beyond max_log; rows at and behind min(count, max_entries) are zero.  Any pointer
+ * may be NULL.  Errors: LEXLS_ERR_INVALID for a null handle, before the first run, after a failed one, and when the last run ran with the log off. */
+int lexls_lsi_batch_get_working_set_log(lexls_lsi_batch_t b, int32_t *h_log, double *h_alpha, uint32_t *h_counts);
+/* The same three arrays where the library keeps them, in the memory of the batch's device, for a consumer that stays there (lexls_lsi_batch_run_device_ex
+ * itself is unchanged): *d_log, *d_alpha, *d_counts (any may be NULL) receive pointers the library owns, in the layouts above, valid until the next
+ * lexls_lsi_batch_set_working_set_log or the destruction of the batch.  They describe the last run completely once the run call has returned — after
+ * a run whose instances did not all stay resident, the merged log has been uploaded before that.  Errors: LEXLS_ERR_INVALID for a null handle or
+ * while the log is off. */
+int lexls_lsi_batch_working_set_log_device(lexls_lsi_batch_t b, void **d_log, void **d_alpha, void **d_counts);
 /* lexls_lsi_solve plus what the MEX front end also passes (interfaces/matlab-octave/lexlsi.cpp:527-625): h_v0 = initial residuals,
  * sum(dims) doubles (set_v0 per objective) or NULL; h_reg_factors = one regularization factor per objective or NULL; h_params with
  * nparams == 9 (as lexls_lsi_solve) or 12: + regularization_type, variable_regularization_factor, max_number_of_CG_iterations. */

@@ -32,8 +32,13 @@ SYMBOLS = [
     "lexls_lse_sensitivity_collect", "lexls_lse_sensitivity_collect_resident", "lexls_lse_get_wrong_sign",
     "lexls_lsi_batch_get_cycling_counters", "lexls_lsi_batch_run_device", "lexls_lsi_batch_run_device_ex",
     "lexls_lsi_batch_set_instance_regularization",
+    "lexls_lsi_batch_set_working_set_log", "lexls_lsi_batch_get_working_set_log", "lexls_lsi_batch_working_set_log_device",
     "lexls_lsi_batch_last_kernel",
 ]
+
+# one entry of a working-set log (lexls_lsi_debug::log, lexls_lsi_batch_get_working_set_log): the int32 fields of a row, in the order of the
+# header's LEXLS_LSI_LOG_* indices; alpha_or_lambda travels in a double array of its own
+WORKING_SET_LOG_FIELDS = ("obj_index", "ctr_index", "ctr_type", "cycling_detected", "rank")
 
 ARRAY = dict(x=0, factor=1, hh=2, perm=3, rank=4, first_col=5, total_rank=6, v=7, lam=8, input=9, guard_estimate=10, guard_status=11,
              multipliers=12, wrong_sign=13)
@@ -82,6 +87,12 @@ def lib() -> C.CDLL:
                                                        C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]  # + d_v0; d_lambda, d_cycling_counts
         _lib.lexls_lsi_batch_set_instance_regularization.restype = C.c_int
         _lib.lexls_lsi_batch_set_instance_regularization.argtypes = [C.c_void_p, C.c_void_p, C.c_int]  # factors: host or device address
+        _lib.lexls_lsi_batch_set_working_set_log.restype = C.c_int
+        _lib.lexls_lsi_batch_set_working_set_log.argtypes = [C.c_void_p, C.c_uint32]
+        _lib.lexls_lsi_batch_get_working_set_log.restype = C.c_int
+        _lib.lexls_lsi_batch_get_working_set_log.argtypes = [C.c_void_p, C.POINTER(C.c_int32), C.POINTER(C.c_double), C.POINTER(C.c_uint32)]
+        _lib.lexls_lsi_batch_working_set_log_device.restype = C.c_int
+        _lib.lexls_lsi_batch_working_set_log_device.argtypes = [C.c_void_p, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), C.POINTER(C.c_void_p)]
     return _lib
 
 

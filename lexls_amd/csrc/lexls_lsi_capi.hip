@@ -159,6 +159,34 @@ extern "C"
         });
     }
 
+    int lexls_lsi_batch_set_working_set_log(lexls_lsi_batch_t b, uint32_t max_entries)
+    {
+        return guarded([&]() {
+            if (!b) throw Exception("lexls_lsi_batch_set_working_set_log: null handle");
+            return b->set_working_set_log(max_entries);
+        });
+    }
+
+    int lexls_lsi_batch_get_working_set_log(lexls_lsi_batch_t b, int32_t *h_log, double *h_alpha, uint32_t *h_counts)
+    {
+        return guarded([&]() {
+            if (!b) throw Exception("lexls_lsi_batch_get_working_set_log: null handle");
+            return b->get_working_set_log(h_log, h_alpha, h_counts);
+        });
+    }
+
+    int lexls_lsi_batch_working_set_log_device(lexls_lsi_batch_t b, void **d_log, void **d_alpha, void **d_counts)
+    {
+        return guarded([&]() {
+            if (!b) throw Exception("lexls_lsi_batch_working_set_log_device: null handle");
+            if (!b->wlog) throw Exception("lexls_lsi_batch_working_set_log_device: the working-set log is off (lexls_lsi_batch_set_working_set_log)");
+            if (d_log) *d_log = b->wlog->d_log;
+            if (d_alpha) *d_alpha = b->wlog->d_alpha;
+            if (d_counts) *d_counts = b->wlog->d_count;
+            return static_cast<int>(LEXLS_OK);
+        });
+    }
+
     int lexls_lsi_batch_solve_ex2(int device, uint32_t batch, uint32_t nVar, uint32_t nObj, const uint32_t *h_dims, const int32_t *h_types,
                                   const double *h_data, const uint32_t *h_var_index, const uint8_t *h_active_guess, const double *h_x0,
                                   const double *h_reg_factors, const double *h_params, uint32_t nparams, double *h_x, int32_t *h_info6,

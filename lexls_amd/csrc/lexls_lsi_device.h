@@ -248,7 +248,16 @@ namespace
         uint32_t cycling_max_counter;
         double cycling_relax_step;
         uint32_t *cyc;               // B x RESIDENT_CYC_STRIDE: valid, operation, objective, constraint, type, relaxations done, -, -
+        // working-set log (LexLSI::getWorkingSetLog, lexlsi.h:739; the entries of verifyWorkingSet, :1186-1230): one record per working-set change,
+        // written by lane 0 where the change is decided.  Every instance owns its rows and its counter; nothing inside the run reads them
+        int32_t *wlog;               // B x wlog_cap x RESIDENT_WLOG_FIELDS: obj_index, ctr_index, ctr_type, cycling_detected, rank.  NULL: off, nothing below is touched
+        double *wlog_alpha;          // B x wlog_cap: alpha_or_lambda
+        uint32_t *wlog_count;        // B: entries produced (counted on when there is no room left for the record)
+        uint32_t wlog_cap;
+        const double *maxabs;        // B: the removal search's largest wrong-sign multiplier (lambda_wrong_sign, lexlsi.h:1115-1139)
     };
+    /// int32 words of one record of ResidentArgs::wlog (the row of lexls_lsi_debug::log)
+    constexpr uint32_t RESIDENT_WLOG_FIELDS = 5;
 
     /// LDS of one instance's wavefront: [dx n | A dx total | dv total] doubles, u16 na[STEP_MAX_OBJ], then the working-set lists
     /// u16 [act | inact | inact_pos] and u8 [ctr_state]
@@ -416,6 +425,27 @@ namespace
         const bool done = (!blocked && !removed) || cyc_stop || nfact >= a.max_factorizations; // lexlsi.h:236-240
         if (lane == 0)
         {
+            // WorkingSetLogEntry (lexlsi.h:1188-1194 ADD, :1214-1222 REMOVE), before the lists change: an ADD is the blocking triple at step length
+            // alpha, a REMOVE the constraint's index in its objective with type CTR_INACTIVE at lambda_wrong_sign (0 under deactivate_first_wrong_sign,
+            // lexlsi.h:1069).  cycling_detected is what CyclingHandler::update reports (lexlsi.h:1252-1259): set on the relaxing iteration, clear on the
+            // one that ends the run at the relaxation limit — which is logged like any other.  Rank: this iteration's factorization
+            if (a.wlog && (blocked || removed)) // (wave-uniform)
+            {
+                const uint32_t cnt = a.wlog_count[b];
+                if (cnt < a.wlog_cap)
+                {
+                    const size_t row    = (size_t)b * a.wlog_cap + cnt;
+                    int32_t *e          = a.wlog + row * RESIDENT_WLOG_FIELDS;
+                    const uint32_t robj = blocked ? (uint32_t)blk_obj : (uint32_t)(rm_lvl + (int32_t)a.off);
+                    e[0]                = (int32_t)robj;
+                    e[1]                = (int32_t)(blocked ? blk_ctr : (uint32_t)act[sh.first[robj] + (uint32_t)rm_pos]);
+                    e[2]                = (int32_t)(blocked ? blk_type : (uint32_t)CTR_INACTIVE);
+                    e[3]                = cyc_relax ? 1 : 0;
+                    e[4]                = (int32_t)trank;
+                    a.wlog_alpha[row]   = blocked ? verdict.alpha : (a.first_wrong_sign ? 0.0 : a.maxabs[b]);
+                }
+                a.wlog_count[b] = cnt + 1u;
+            }
             if (blocked) // OPERATION_ADD: workingset.h:79-92
             {
                 const uint32_t f = sh.first[blk_obj], nak = na[blk_obj], nik = sh.dim[blk_obj] - nak;

@@ -109,6 +109,29 @@ struct lexls_lsi_batch_s
     };
     std::vector<std::unique_ptr<LambdaBufs>> lam_bufs;
     std::vector<uint32_t> cycling_count; // batch: LexLSI::getCyclingCounter() of every instance of the last run (lexls_lsi_batch_get_cycling_counters)
+    // ---- the working-set log of the last run (lexls_lsi_batch_set_working_set_log; LexLSI::getWorkingSetLog, lexlsi.h:739) ----
+    // One slab for the batch, on the device and as a pinned staging copy: batch x cap records, batch x cap values, batch counters; group g works on
+    // the rows from lo[g] on (BatchCtx::bind_working_set_log), so the caller of lexls_lsi_batch_working_set_log_device sees one array per part.
+    // The device copy is the log: resident iterations write it where they happen, what host objects logged is uploaded into it.
+    struct WlogBufs
+    {
+        uint32_t cap = 0;
+        int32_t *d_log    = NULL;
+        double *d_alpha   = NULL;
+        uint32_t *d_count = NULL;
+        Pinned<int32_t> log;
+        Pinned<double> alpha;
+        Pinned<uint32_t> count;
+        ~WlogBufs()
+        {
+            if (d_log) (void)hipFree(d_log);
+            if (d_alpha) (void)hipFree(d_alpha);
+            if (d_count) (void)hipFree(d_count);
+        }
+    };
+    std::unique_ptr<WlogBufs> wlog;      // NULL: logging is off
+    bool wlog_valid = false;             // the slab describes the last run (which ran with logging on and did not fail)
+    std::vector<uint8_t> wlog_from_host; // batch: this run's entries of the instance are all its host object's (it never became resident)
 
     /// what a group's next stage must serve (Run::wants): somebody alive, a factorize+solve, a sensitivity, a device-side step, a solve whose x the host needs
     enum : uint32_t { WANT_ALIVE = 1u, WANT_FS = 2u, WANT_SENS = 4u, WANT_STEP = 8u, WANT_X = 16u };
@@ -387,6 +410,101 @@ struct lexls_lsi_batch_s
         return LEXLS_OK;
     }
 
+    /// lexls_lsi_batch_set_working_set_log: max_entries records per instance for every later run; 0: off, the slab is freed
+    int set_working_set_log(uint32_t max_entries)
+    {
+        wlog_valid = false;
+        for (uint32_t g = 0; g < nGroups; g++) grp[g]->bind_working_set_log(0, NULL, NULL, NULL, NULL, NULL, NULL);
+        wlog.reset();
+        if (max_entries == 0) return LEXLS_OK;
+        std::unique_ptr<WlogBufs> w(new WlogBufs());
+        w->cap            = max_entries;
+        const size_t rows = (size_t)batch * max_entries;
+        if (hipSetDevice(device) != hipSuccess || hipMalloc((void **)&w->d_log, 4 * rows * RESIDENT_WLOG_FIELDS) != hipSuccess || hipMalloc((void **)&w->d_alpha, 8 * rows) != hipSuccess ||
+            hipMalloc((void **)&w->d_count, 4 * (size_t)batch) != hipSuccess)
+            throw Exception("hipMalloc failed (lexls_lsi_batch_set_working_set_log)");
+        w->log.assign(rows * RESIDENT_WLOG_FIELDS, 0);
+        w->alpha.assign(rows, 0.0);
+        w->count.assign(batch, 0u);
+        wlog_from_host.assign(batch, 0);
+        wlog = std::move(w);
+        for (uint32_t g = 0; g < nGroups; g++)
+        {
+            const size_t r0 = (size_t)lo[g] * max_entries;
+            grp[g]->bind_working_set_log(max_entries, wlog->d_log + r0 * RESIDENT_WLOG_FIELDS, wlog->d_alpha + r0, wlog->d_count + lo[g], wlog->log.data() + r0 * RESIDENT_WLOG_FIELDS,
+                                         wlog->alpha.data() + r0, wlog->count.data() + lo[g]);
+        }
+        return LEXLS_OK;
+    }
+    /// a run starts: the staging copy is empty (the groups clear their device rows in their streams, prepare_groups)
+    void begin_working_set_log()
+    {
+        wlog_valid = false;
+        if (!wlog) return;
+        std::fill(wlog->log.begin(), wlog->log.end(), 0);
+        std::fill(wlog->alpha.begin(), wlog->alpha.end(), 0.0);
+        std::fill(wlog->count.begin(), wlog->count.end(), 0u);
+        std::fill(wlog_from_host.begin(), wlog_from_host.end(), 0);
+    }
+    /// instance b never left the host (host path, one-by-one path, or it stopped before the hand-over): its rows are its host object's log
+    template <class LSI>
+    void keep_host_log(uint32_t b, const LSI &inst)
+    {
+        if (!wlog) return;
+        put_working_set_log(inst.getWorkingSetLog(), wlog->cap, b, wlog->log.data(), wlog->alpha.data(), wlog->count.data());
+        wlog_from_host[b] = 1;
+    }
+    /// the run is over (every stream is idle): rows that host objects made are merged into the device copy, which is then complete
+    void finish_working_set_log()
+    {
+        if (!wlog) return;
+        size_t from_host = 0;
+        for (uint32_t b = 0; b < batch; b++) from_host += wlog_from_host[b];
+        if (from_host)
+        {
+            const size_t cap = wlog->cap, rows = (size_t)batch * cap;
+            if (hipSetDevice(device) != hipSuccess) throw Exception("hipSetDevice failed (working-set log)");
+            if (from_host < batch) // the resident instances' rows as the device left them
+            {
+                std::vector<int32_t> log(rows * RESIDENT_WLOG_FIELDS);
+                std::vector<double> alpha(rows);
+                std::vector<uint32_t> count(batch);
+                if (hipMemcpy(log.data(), wlog->d_log, 4 * log.size(), hipMemcpyDeviceToHost) != hipSuccess || hipMemcpy(alpha.data(), wlog->d_alpha, 8 * rows, hipMemcpyDeviceToHost) != hipSuccess ||
+                    hipMemcpy(count.data(), wlog->d_count, 4 * (size_t)batch, hipMemcpyDeviceToHost) != hipSuccess)
+                    throw Exception("download of the working-set log failed");
+                for (uint32_t b = 0; b < batch; b++)
+                    if (!wlog_from_host[b])
+                    {
+                        std::copy(log.begin() + (size_t)b * cap * RESIDENT_WLOG_FIELDS, log.begin() + (size_t)(b + 1) * cap * RESIDENT_WLOG_FIELDS, wlog->log.begin() + (size_t)b * cap * RESIDENT_WLOG_FIELDS);
+                        std::copy(alpha.begin() + (size_t)b * cap, alpha.begin() + (size_t)(b + 1) * cap, wlog->alpha.begin() + (size_t)b * cap);
+                        wlog->count[b] = count[b];
+                    }
+            }
+            if (hipMemcpy(wlog->d_log, wlog->log.data(), 4 * rows * RESIDENT_WLOG_FIELDS, hipMemcpyHostToDevice) != hipSuccess ||
+                hipMemcpy(wlog->d_alpha, wlog->alpha.data(), 8 * rows, hipMemcpyHostToDevice) != hipSuccess || hipMemcpy(wlog->d_count, wlog->count.data(), 4 * (size_t)batch, hipMemcpyHostToDevice) != hipSuccess)
+                throw Exception("upload of the merged working-set log failed");
+        }
+        wlog_valid = true;
+    }
+    /// lexls_lsi_batch_get_working_set_log: the last run's log from the device copy (any pointer may be NULL)
+    int get_working_set_log(int32_t *h_log, double *h_alpha, uint32_t *h_counts) const
+    {
+        if (!wlog) throw Exception("lexls_lsi_batch_get_working_set_log: the working-set log is off (lexls_lsi_batch_set_working_set_log)");
+        if (!wlog_valid) throw Exception("lexls_lsi_batch_get_working_set_log: no completed run with the working-set log on");
+        const size_t rows = (size_t)batch * wlog->cap;
+        if (hipSetDevice(device) != hipSuccess || (h_log && hipMemcpy(h_log, wlog->d_log, 4 * rows * RESIDENT_WLOG_FIELDS, hipMemcpyDeviceToHost) != hipSuccess) ||
+            (h_alpha && hipMemcpy(h_alpha, wlog->d_alpha, 8 * rows, hipMemcpyDeviceToHost) != hipSuccess) ||
+            (h_counts && hipMemcpy(h_counts, wlog->d_count, 4 * (size_t)batch, hipMemcpyDeviceToHost) != hipSuccess))
+            throw Exception("lexls_lsi_batch_get_working_set_log: download failed");
+        return LEXLS_OK;
+    }
+    /// the parameters of a run as its host objects get them: with logging on they keep their working-set log (ParametersLexLSI::log_working_set_enabled)
+    ParametersLexLSI with_log_switch(ParametersLexLSI par) const
+    {
+        if (wlog) par.log_working_set_enabled = true;
+        return par;
+    }
+
     runner::LsiProblem problem(const Run &r, uint32_t b) const
     {
         return {nVar, nObj, dims.data(), types.data(), r.h_data + (size_t)b * per_data, r.h_var_index ? r.h_var_index + (size_t)b * dims[0] : NULL,
@@ -461,9 +579,11 @@ struct lexls_lsi_batch_s
     }
 
     void run(const double *h_data, const uint32_t *h_var_index, const uint8_t *h_active_guess, const double *h_x0, const double *h_v0,
-             const double *h_reg_factors, const ParametersLexLSI &par, double *h_x, int32_t *h_info6, uint8_t *h_active, double *h_v, int32_t *h_rounds2)
+             const double *h_reg_factors, const ParametersLexLSI &par_, double *h_x, int32_t *h_info6, uint8_t *h_active, double *h_v, int32_t *h_rounds2)
     {
         if (!h_data || !h_x) throw Exception("lexls_lsi_batch_run: null data / x");
+        const ParametersLexLSI par = with_log_switch(par_);
+        begin_working_set_log();
         lam_rc  = -1;
         lam_tol = par.tol_linear_dependence;
         last_kernel = "host";
@@ -480,6 +600,7 @@ struct lexls_lsi_batch_s
         if (par.deactivate_first_wrong_sign && !would_be_resident(par))
         {
             run_one_by_one(r, lam_after == LEXLS_OK);
+            finish_working_set_log();
             lam_rc  = (off && !h_var_index) ? LEXLS_ERR_INVALID : lam_after;
             lam_msg = lam_rc == LEXLS_ERR_INVALID ? "lexls_lsi_batch_get_lambda: the run had no variable indices" : lam_why;
             return;
@@ -489,6 +610,7 @@ struct lexls_lsi_batch_s
         if ((r.sw.device_phase1 || r.d_inst_rows) && !h_v0 && would_be_resident(par))
         {
             run_phase1_on_device(r, NULL);
+            finish_working_set_log();
             lam_rc  = (off && !h_var_index) ? LEXLS_ERR_INVALID : lam_after;
             lam_msg = lam_rc == LEXLS_ERR_INVALID ? "lexls_lsi_batch_get_lambda: the run had no variable indices" : lam_why;
             return;
@@ -501,6 +623,7 @@ struct lexls_lsi_batch_s
         host_rounds(r);
         if (r.resident) resident_rounds(r);
         collect(r);
+        finish_working_set_log();
         report(r);
         lam_rc  = lam_after;
         lam_msg = lam_why;
@@ -522,6 +645,7 @@ struct lexls_lsi_batch_s
             fs += solve_one(lsi, device, p, r.par, r.h_x + (size_t)b * nVar, r.h_info6 ? r.h_info6 + (size_t)b * 6 : NULL, r.h_active ? r.h_active + (size_t)b * total : NULL,
                             r.h_v ? r.h_v + (size_t)b * total : NULL).factorizations;
             keep_working_set(b, lsi, p.data, p.var_index);
+            keep_host_log(b, lsi);
             cycling_count[b] = static_cast<uint32_t>(lsi.getCyclingCounter());
         }
         last_stats[0] = fs, last_stats[1] = last_stats[2] = 0, last_stats[3] = 1;
@@ -569,6 +693,7 @@ struct lexls_lsi_batch_s
             ctx.gather    = r.gather;
             if (!r.gather) ctx.need_staging();
             ctx.reset();
+            ctx.clear_working_set_log();
             ctx.set_first_wrong_sign(r.par.deactivate_first_wrong_sign);
             ctx.set_cycling(r.par.cycling_handling_enabled && r.resident, r.par.cycling_relax_step, static_cast<uint32_t>(r.par.cycling_max_counter));
             hip_check(lexls_lse_set_tolerance(ctx.h, r.par.tol_linear_dependence));
@@ -917,6 +1042,7 @@ struct lexls_lsi_batch_s
     /// lexls_lsi_batch_run_device(_ex): the caller has checked would_be_resident(par)
     void run_device(const DeviceArrays &dev, const double *h_reg_factors, const ParametersLexLSI &par)
     {
+        begin_working_set_log(); // (no host objects: every entry is written on the device)
         lam_rc      = -1;
         lam_tol     = par.tol_linear_dependence;
         last_kernel = "host";
@@ -924,6 +1050,7 @@ struct lexls_lsi_batch_s
         Run r{NULL, NULL, NULL, h_reg_factors, NULL, NULL, par, NULL, NULL, NULL, NULL, NULL};
         take_instance_regularization(r);
         run_phase1_on_device(r, &dev);
+        finish_working_set_log();
         lam_rc  = lam_rc_after(par);
         lam_msg = par.cycling_handling_enabled ? "lexls_lsi_batch_get_lambda: not available after a run with cycling handling enabled (it may have relaxed bounds in the resident constraint data)"
                                                : "lexls_lsi_batch_get_lambda: not available after a regularized run";
@@ -948,6 +1075,7 @@ struct lexls_lsi_batch_s
         runner::collect(*r.lsi[b], r.prob[b], x, &info, r.h_active ? r.h_active + (size_t)b * total : NULL, v);
         if (r.h_info6) std::memcpy(r.h_info6 + (size_t)b * 6, &info, sizeof(info));
         keep_working_set(b, *r.lsi[b], r.prob[b].data, r.prob[b].var_index);
+        keep_host_log(b, *r.lsi[b]);
         cycling_count[b] = static_cast<uint32_t>(r.lsi[b]->getCyclingCounter());
         if (r.step && ctx.on_device[k]) unpack_state(ctx.state_host.data() + (size_t)k * ctx.shape.SD, nVar, total, x, v);
     }

@@ -188,6 +188,26 @@ namespace
         }
     }
 
+    /// a host driver's working-set log (getWorkingSetLog, lexlsi.h:739) into row b of log arrays of capacity `cap` per instance, in the row layout of
+    /// lexls_lsi_debug::log; the count is the number of entries made, those beyond the capacity are dropped (runner::collect_debug does the same)
+    inline void put_working_set_log(const std::vector<WorkingSetLogEntry> &wlog, uint32_t cap, size_t b, int32_t *log, double *alpha, uint32_t *count)
+    {
+        static_assert(RESIDENT_WLOG_FIELDS == LEXLS_LSI_LOG_FIELDS && LEXLS_LSI_LOG_OBJ_INDEX == 0 && LEXLS_LSI_LOG_CTR_INDEX == 1 && LEXLS_LSI_LOG_CTR_TYPE == 2 &&
+                          LEXLS_LSI_LOG_CYCLING_DETECTED == 3 && LEXLS_LSI_LOG_RANK == 4,
+                      "the record lsi_iterate_finish writes is the row include/lexls_hip.h declares");
+        for (size_t i = 0; i < wlog.size() && i < cap; i++)
+        {
+            int32_t *e = log + (b * cap + i) * RESIDENT_WLOG_FIELDS;
+            e[0]       = static_cast<int32_t>(wlog[i].obj_index);
+            e[1]       = static_cast<int32_t>(wlog[i].ctr_index);
+            e[2]       = static_cast<int32_t>(wlog[i].ctr_type);
+            e[3]       = wlog[i].cycling_detected ? 1 : 0;
+            e[4]       = static_cast<int32_t>(wlog[i].rank);
+            alpha[b * cap + i] = wlog[i].alpha_or_lambda;
+        }
+        count[b] = static_cast<uint32_t>(wlog.size());
+    }
+
     struct BatchCtx
     {
         lexls_lse_t h = NULL;
@@ -246,6 +266,12 @@ namespace
         bool cycling = false;              // this run handles cycling on the device: handler state in the slab, relaxed bounds in the resident constraint data
         double cycling_relax_step = 0.0;
         uint32_t cycling_max_counter = 0;
+        // ---- working-set log (lexls_lsi_batch_set_working_set_log): this group's rows of the batch's log slab, on the device and in the pinned
+        // staging copy — laid out like the cycling state, per instance wlog_cap records / values and one counter.  NULL: logging is off ----
+        uint32_t wlog_cap = 0;
+        int32_t *d_wlog = NULL, *wlog_host = NULL;
+        double *d_wlog_alpha = NULL, *wlog_alpha_host = NULL;
+        uint32_t *d_wlog_count = NULL, *wlog_count_host = NULL;
         // ---- phase 1 on the device (lsi_phase1_device.h): no host objects, the slabs are written where they live ----
         bool phase1_on_device = false;     // this run: the first resident stage finds its problem in the device's in slab
         uint32_t *d_p1_fault = NULL;       // the setup kernel's error word
@@ -362,6 +388,8 @@ namespace
                 c[CYC_COUNT]     = static_cast<uint32_t>(ch.get_counter());
                 if (ch.get_counter() != 0) throw Exception("lexls_lsi_batch_run: a bound was relaxed before the instance became resident");
             }
+            // what the instance logged on the host (iteration 0, with log_working_set_enabled) goes into its staging rows; the device counts on behind it
+            if (wlog_host) put_working_set_log(inst.getWorkingSetLog(), wlog_cap, b, wlog_host, wlog_alpha_host, wlog_count_host);
             rl.alive(base)[b] = 1;
             is_resident[b]    = 1; // (its staged equality problem is served by the first resident stage, followed by its removal sweep)
         }
@@ -398,6 +426,8 @@ namespace
             ra.first_wrong_sign = first_wrong_sign ? 1u : 0u;
             ra.wrong_sign = d_wrong_sign, ra.stamp = rl.stamp(d_rws), ra.next_stamp = rl.next_stamp(d_rws);
             ra.cycling = cycling ? 1u : 0u, ra.cycling_max_counter = cycling_max_counter, ra.cycling_relax_step = cycling_relax_step, ra.cyc = rl.cyc(d_rws);
+            ra.wlog = d_wlog, ra.wlog_alpha = d_wlog_alpha, ra.wlog_count = d_wlog_count, ra.wlog_cap = wlog_cap; // (NULL: off)
+            ra.maxabs = reinterpret_cast<const double *>(out + lay.max_abs);
             return ra;
         }
 
@@ -415,6 +445,22 @@ namespace
         /// cycling handling of the run that starts (on: the resident iterations do it; a run that handles cycling on the host passes off)
         void set_cycling(bool on, double relax_step, uint32_t max_counter) { cycling = on, cycling_relax_step = relax_step, cycling_max_counter = max_counter; }
 
+        /// this group's rows of the log slab (set_working_set_log of the batch object; NULL pointers: logging off)
+        void bind_working_set_log(uint32_t cap_, int32_t *d_log, double *d_alpha, uint32_t *d_count, int32_t *h_log, double *h_alpha, uint32_t *h_count)
+        {
+            wlog_cap = cap_;
+            d_wlog = d_log, d_wlog_alpha = d_alpha, d_wlog_count = d_count;
+            wlog_host = h_log, wlog_alpha_host = h_alpha, wlog_count_host = h_count;
+        }
+        /// a run starts: no entries, every row zero (rows behind an instance's last entry stay zero) — in the group's stream, ahead of everything that logs
+        void clear_working_set_log()
+        {
+            if (!d_wlog) return;
+            if (hipMemsetAsync(d_wlog, 0, 4 * (size_t)B * wlog_cap * RESIDENT_WLOG_FIELDS, stream) != hipSuccess || hipMemsetAsync(d_wlog_alpha, 0, 8 * (size_t)B * wlog_cap, stream) != hipSuccess ||
+                hipMemsetAsync(d_wlog_count, 0, 4 * (size_t)B, stream) != hipSuccess)
+                throw Exception("hipMemsetAsync failed (working-set log)");
+        }
+
         /// the handed-over instances start: slabs up, then `count` whole iterations are enqueued (nothing is waited for)
         void begin_resident()
         {
@@ -423,6 +469,10 @@ namespace
                 (cycling && hipMemcpyAsync(d_rws + rl.o_cyc, rws_host.data() + rl.o_cyc, rl.bytes_cyc, hipMemcpyHostToDevice, stream) != hipSuccess) ||
                 hipMemcpyAsync(d_rstate, rstate_host.data(), 8 * (size_t)B * rshape.SD, hipMemcpyHostToDevice, stream) != hipSuccess)
                 throw Exception("hipMemcpyAsync failed (resident hand-over)");
+            if (d_wlog && (hipMemcpyAsync(d_wlog, wlog_host, 4 * (size_t)B * wlog_cap * RESIDENT_WLOG_FIELDS, hipMemcpyHostToDevice, stream) != hipSuccess ||
+                           hipMemcpyAsync(d_wlog_alpha, wlog_alpha_host, 8 * (size_t)B * wlog_cap, hipMemcpyHostToDevice, stream) != hipSuccess ||
+                           hipMemcpyAsync(d_wlog_count, wlog_count_host, 4 * (size_t)B, hipMemcpyHostToDevice, stream) != hipSuccess))
+                throw Exception("hipMemcpyAsync failed (working-set log hand-over)");
             rounds_resident = 0;
             fused_all       = false;
             fused_refused   = false; // (decided per run: the next one may be of another kind — plain / regularized — or under another LEXLS_LSI_NO_FUSED)

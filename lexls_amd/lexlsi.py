@@ -239,6 +239,7 @@ class LsiBatch:
         self.types = np.ascontiguousarray(types, np.int32)
         self.total = int(self.dims.sum())
         self._h = C.c_void_p()
+        self._log_entries = 0  # capacity per instance of the working-set log (set_working_set_log); 0: off
         self._instance_factors = None  # the device tensor (or address) set_instance_regularization was given: kept alive while the library reads it
         capi.check(capi.lib().lexls_lsi_batch_create(C.byref(self._h), C.c_int(device), C.c_uint32(self.batch), C.c_uint32(self.nvar),
                                                      C.c_uint32(len(self.dims)), _p(self.dims, C.c_uint32), _p(self.types, C.c_int32)))
@@ -393,6 +394,50 @@ class LsiBatch:
         counts = np.zeros(self.batch, np.uint32)
         capi.check(capi.lib().lexls_lsi_batch_get_cycling_counters(self._h, _p(counts, C.c_uint32)))
         return counts
+
+    def set_working_set_log(self, max_entries: int):
+        """lexls_lsi_batch_set_working_set_log: every later run() / run_device() keeps the working-set log of each instance
+        (LexLSI::getWorkingSetLog), up to `max_entries` entries per instance; 0 switches the log off again and frees its buffers"""
+        max_entries = int(max_entries)
+        if max_entries < 0:
+            raise ValueError("set_working_set_log: max_entries must not be negative")
+        capi.check(capi.lib().lexls_lsi_batch_set_working_set_log(self._h, C.c_uint32(max_entries)))
+        self._log_entries = max_entries
+
+    def working_set_log_arrays(self):
+        """the raw arrays of lexls_lsi_batch_get_working_set_log for the last run: log (batch, max_entries, 5) int32 with the columns
+        capi.WORKING_SET_LOG_FIELDS, alpha_or_lambda (batch, max_entries) float64, counts (batch,) uint32 — the entries each instance produced,
+        which may exceed max_entries (the rest was dropped)"""
+        cap = self._log_entries
+        log = np.zeros((self.batch, cap, len(capi.WORKING_SET_LOG_FIELDS)), np.int32)
+        alpha, counts = np.zeros((self.batch, cap)), np.zeros(self.batch, np.uint32)
+        capi.check(capi.lib().lexls_lsi_batch_get_working_set_log(self._h, _p(log, C.c_int32), _p(alpha, C.c_double), _p(counts, C.c_uint32)))
+        return log, alpha, counts
+
+    def working_set_log(self):
+        """-> (logs, counts): per instance of the last run the list of entries that frontend.lexlsi(..., debug=True) returns as
+        d["working_set_log"] (dicts with obj_index, ctr_index, ctr_type, alpha_or_lambda, cycling_detected, rank), cut at max_entries, and the
+        (batch,) uint32 number of entries each instance produced"""
+        log, alpha, counts = self.working_set_log_arrays()
+        logs = [[dict(alpha_or_lambda=float(a), **{k: int(f) for k, f in zip(capi.WORKING_SET_LOG_FIELDS, e)}) for e, a in zip(log[b][:int(c)], alpha[b][:int(c)])]
+                for b, c in enumerate(counts)]
+        return logs, counts
+
+    def working_set_log_device(self):
+        """lexls_lsi_batch_working_set_log_device: {"log", "alpha_or_lambda", "counts"} as torch tensors over the library's own device arrays — no
+        copy; (batch, max_entries, 5) int32, (batch, max_entries) float64, (batch,) int32 holding the uint32 bits of the counts.  They describe
+        the last run once run() / run_device() has returned and are valid until the next set_working_set_log() or close()."""
+        import torch
+        ptr = [C.c_void_p(), C.c_void_p(), C.c_void_p()]
+        capi.check(capi.lib().lexls_lsi_batch_working_set_log_device(self._h, *(C.byref(p) for p in ptr)))
+        cap, dev = self._log_entries, torch.device("cuda", self.device)
+
+        class _Span:  # the CUDA array interface over memory this object does not own
+            def __init__(self, address, shape, typestr):
+                self.__cuda_array_interface__ = dict(shape=shape, typestr=typestr, data=(int(address), False), version=2, strides=None)
+
+        shapes = [((self.batch, cap, len(capi.WORKING_SET_LOG_FIELDS)), "<i4"), ((self.batch, cap), "<f8"), ((self.batch,), "<i4")]
+        return {k: torch.as_tensor(_Span(p.value, s, t), device=dev) for k, p, (s, t) in zip(("log", "alpha_or_lambda", "counts"), ptr, shapes)}
 
     def lambda_array(self) -> np.ndarray:
         """getLambda of every instance of the last run (lexls_lsi_batch_get_lambda): (batch, nObj, total) — instance b's total x nObj
