@@ -422,6 +422,45 @@ int lexls_lsi_batch_run_device_ex(lexls_lsi_batch_t b, const double *d_data, con
                                   const double *d_x0, const double *d_v0, const double *h_reg_factors, const double *h_params, uint32_t nparams,
                                   double *d_x, int32_t *d_info6, uint8_t *d_active, double *d_v,
                                   double *d_lambda, uint32_t *d_cycling_counts);
+/* lexls_lsi_batch_run_device_ex as work in a stream: the same arguments and layouts, the same bits in the outputs, but the call only ENQUEUES the run
+ * in hip_stream (a hipStream_t; NULL: the default stream) and returns.  It makes no host-synchronising HIP call, and no hipMalloc / hipFree once the
+ * batch has served one enqueue with the same options (the first such call may allocate).  What is enqueued is what the synchronous call enqueues —
+ * the device-to-device copy of the data, lsi_phase1_setup_kernel, the first stage, lsi_phase1_finish_kernel, the persistent launch of every remaining
+ * iteration, lsi_result_scatter, and with d_lambda the multipliers' stage — in the stream of the batch's group, which forks from hip_stream and joins it
+ * again by events.  The caller's inputs need only be complete in stream order; work enqueued later in hip_stream sees complete outputs.  The host
+ * arrays (h_params, h_reg_factors, host factors of lexls_lsi_batch_set_instance_regularization) are read during the call.
+ * Input errors are handled on the device: behind the setup kernels a small kernel reads the fault word (instance * 8 + code; 1 lb > ub, 2 variable
+ * index not below nVar, 3 repeated variable index, 4 guess flag above 3) and, if it is set, stops every instance of the run by the mechanism that
+ * stops a finished one — no later kernel touches the run's data and every output array is left as it was.  d_status (one word in device memory, or
+ * NULL) receives the word, 0xffffffff for a good run; the scatter step writes it on both outcomes.
+ * Served: the runs lexls_lsi_batch_run_device_ex serves whose resident iterations are ONE persistent launch (lexls_lsi_batch_last_kernel names
+ * lsi_fused<...> after the synchronous call): plain and regularized runs (types 1..6, 8, 9), deactivate_first_wrong_sign, cycling handling of an
+ * unregularized run, host or device per-instance factors, the working-set log.  Everything else returns LEXLS_ERR_UNSUPPORTED before any device work,
+ * every output left alone — what lexls_lsi_batch_run_device_ex refuses, LEXLS_LSI_NO_FUSED=1, a shape without a persistent instantiation or whose
+ * launch does not get its LDS, d_lambda where lexls_lsi_batch_get_lambda would refuse; this is decided on the host from the shape, not by trying the
+ * launch.  A batch split into several groups (only LEXLS_LSI_GROUPS does that to a batch whose runs are resident) is not served either.
+ * d_lambda: the final equality problems are formed by a kernel from the working sets where they live (lsi_lambda_form_kernel), then gathered, factorized
+ * and swept as lexls_lsi_batch_get_lambda does; with an input error the stage runs on empty problems and the array is left as it was.
+ * Between an enqueue and its finish lexls_lsi_batch_run*, _get_lambda, _get_cycling_counters, _stats and _get_working_set_log return LEXLS_ERR_INVALID.
+ * A further enqueue without a finish in between is allowed — the closed loop: solve, perturb on the device, solve again — and ordered behind the
+ * previous one when it goes into the same stream (host per-instance factors may not change between the two).
+ * Capture: after one uncaptured enqueue + finish with the same options, an enqueue on a capturing stream (hipStreamBeginCapture, torch.cuda.graph)
+ * is captured whole; a replay reads and writes the same device arrays with the parameters of the capturing call.  While a captured graph of a batch is
+ * in use, the only other call on that batch is lexls_lsi_batch_finish.  The library sets no queue count.
+ * A call that fails after it has begun to enqueue (LEXLS_ERR_HIP, an internal error) may leave part of a run in hip_stream; the batch then counts as
+ * enqueued: lexls_lsi_batch_finish brings it back to order. */
+int lexls_lsi_batch_enqueue_device(lexls_lsi_batch_t b, void *hip_stream, const double *d_data, const uint32_t *d_var_index, const uint8_t *d_active_guess,
+                                   const double *d_x0, const double *d_v0, const double *h_reg_factors, const double *h_params, uint32_t nparams,
+                                   double *d_x, int32_t *d_info6, uint8_t *d_active, double *d_v, double *d_lambda, uint32_t *d_cycling_counts,
+                                   uint32_t *d_status);
+/* Waits for hip_stream (NULL: the stream of the last lexls_lsi_batch_enqueue_device), then brings back what lexls_lsi_batch_run_device_ex downloads before
+ * it returns: the working-set lists and fixed bounds lexls_lsi_batch_get_lambda forms its problems from, cycling counts, iteration counters, the kernel
+ * name.  After it lexls_lsi_batch_get_lambda, _get_cycling_counters, _stats, _last_kernel, _get_working_set_log and _working_set_log_device answer as
+ * after the equivalent synchronous call.  LEXLS_ERR_INVALID when the run had an input error, lexls_last_error() naming the instance and the reason as
+ * the synchronous call does; the batch then takes the next enqueue normally.  It answers for the LAST enqueue only: in a loop of several enqueues
+ * behind one finish, an input error of an earlier step shows in that step's d_status alone (and in its untouched outputs).  After a replay of a captured enqueue, lexls_lsi_batch_finish(b,
+ * replay_stream) answers for that replay. */
+int lexls_lsi_batch_finish(lexls_lsi_batch_t b, void *hip_stream);
 /* Regularization factors of its own for every instance of the batch, in place of the one shared vector h_reg_factors of the runs: `factors` holds
  * batch x nObj doubles, instance-major — the layout of h_reg_factors repeated per instance; for objective k, instance b takes
  * factors[b * nObj + k] where the shared vector would have given h_reg_factors[k] (the entry of a simple-bounds objective 0 is ignored, as it is

@@ -33,6 +33,7 @@ SYMBOLS = [
     "lexls_lsi_batch_get_cycling_counters", "lexls_lsi_batch_run_device", "lexls_lsi_batch_run_device_ex",
     "lexls_lsi_batch_set_instance_regularization",
     "lexls_lsi_batch_set_working_set_log", "lexls_lsi_batch_get_working_set_log", "lexls_lsi_batch_working_set_log_device",
+    "lexls_lsi_batch_enqueue_device", "lexls_lsi_batch_finish",
     "lexls_lsi_batch_last_kernel",
 ]
 
@@ -85,6 +86,12 @@ def lib() -> C.CDLL:
         _lib.lexls_lsi_batch_run_device_ex.restype = C.c_int
         _lib.lexls_lsi_batch_run_device_ex.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_double), C.POINTER(C.c_double),
                                                        C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]  # + d_v0; d_lambda, d_cycling_counts
+        _lib.lexls_lsi_batch_enqueue_device.restype = C.c_int
+        _lib.lexls_lsi_batch_enqueue_device.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_double),
+                                                        C.POINTER(C.c_double), C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                                        C.c_void_p]  # handle, stream, then run_device_ex's arguments, d_status
+        _lib.lexls_lsi_batch_finish.restype = C.c_int
+        _lib.lexls_lsi_batch_finish.argtypes = [C.c_void_p, C.c_void_p]  # handle, stream
         _lib.lexls_lsi_batch_set_instance_regularization.restype = C.c_int
         _lib.lexls_lsi_batch_set_instance_regularization.argtypes = [C.c_void_p, C.c_void_p, C.c_int]  # factors: host or device address
         _lib.lexls_lsi_batch_set_working_set_log.restype = C.c_int

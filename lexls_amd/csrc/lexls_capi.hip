@@ -730,6 +730,19 @@ extern "C"
         return LEXLS_OK;
     }
 
+    /// The plan of the persistent LexLSI launch for a run of regularization `reg_type` on this handle's batch, from the capacities given at creation
+    /// and the environment's switch (none: not taken); q: the query it was made from.  lexls_internal_resident_fused launches by it and
+    /// lexls_internal_resident_fused_serves answers from it: one decision
+    static KernelId plan_resident_fused(const lexls_lse_s *h, bool has_fixed, uint32_t reg_type, DispatchQuery &q)
+    {
+        q               = resident_query_of(h, has_fixed, reg_type);
+        q.wave_capacity = resident_wave_capacity();
+        LseArgs a       = h->args(); // (the sweep's test reads the shape and the regularization type)
+        a.reg_type      = reg_type;
+        q.sweep_serves  = sensitivity_sweep_serves(a, q.max_level_dim);
+        return std::getenv("LEXLS_LSI_NO_FUSED") ? KernelId::none : plan_lsi_fused(q);
+    }
+
     /* internal (the lock-step LexLSI driver): ALL remaining resident iterations in one persistent launch — per instance l-QR (rows gathered by
      * reference, levels above the changed one read back) -> removal sweep -> lsi_iterate_body, until the instance stops (at most `count`
      * iterations).  Same preparation and the same bookkeeping as lexls_internal_round_resident + lexls_internal_arm_resume +
@@ -739,11 +752,11 @@ extern "C"
     {
         CHECK_HANDLE(h);
         if (!h->d_cdata || !h->d_in_owned) return fail(LEXLS_ERR_INVALID, "resident_fused: needs resident constraint data and one uploaded round");
-        if (std::getenv("LEXLS_LSI_NO_FUSED")) return 1;
         const bool reg = h->reg_type != 0; // the launch with the regularized l-QR: no prefix reuse (lqr_small_impl.h), so no resume levels either way
         HIP_TRY(hipSetDevice(h->device));
-        DispatchQuery q = resident_query_of(h, has_fixed != 0, h->reg_type);
-        q.wave_capacity = resident_wave_capacity();
+        DispatchQuery q;
+        const KernelId id = plan_resident_fused(h, has_fixed != 0, h->reg_type, q);
+        if (id == KernelId::none) return 1;
         // the arguments lexls_internal_round_resident + lexls_internal_arm_resume would leave — on a copy: nothing changes when the launch is not taken
         LseArgs pa      = h->args();
         pa.ldp          = odd_ld(q.max_rows);
@@ -753,9 +766,6 @@ extern "C"
         pa.skip         = h->d_skip;
         pa.g_cdata      = h->d_cdata;
         pa.resume_level = (h->resume_enabled && !reg && h->resume_valid) ? h->d_resume_level : nullptr;
-        q.sweep_serves  = sensitivity_sweep_serves(pa, q.max_level_dim);
-        const KernelId id = plan_lsi_fused(q);
-        if (id == KernelId::none) return 1;
         const FusedCall call{q.max_level_dim, h->d_objidx, tolW, tolC, h->sens_scan, resident_args, resident_args_bytes, count};
         LaunchExtras x;
         x.fused            = &call;
@@ -772,6 +782,22 @@ extern "C"
         h->x_epoch       = h->factor_epoch;
         h->factor_in_hbm = true;
         return LEXLS_OK;
+    }
+
+    /* internal (the lock-step LexLSI driver): would lexls_internal_resident_fused take the launch for a run of regularization `type` (0: none) on this
+     * handle's batch?  The launch's own plan (plan_resident_fused) and the launcher's own LDS sum (lsi_fused_lds_bytes of the planned instantiation;
+     * resident_lds: the driver's share, resident_lds_per_wave): nothing is launched, nothing changes. */
+    int lexls_internal_resident_fused_serves(lexls_lse_t h, int has_fixed, int type, size_t resident_lds)
+    {
+        if (!h || type < 0 || type > 9 || hipSetDevice(h->device) != hipSuccess) return 0;
+        DispatchQuery q;
+        const KernelId id = plan_resident_fused(h, has_fixed != 0, (uint32_t)type, q);
+        if (id == KernelId::none) return 0;
+        uint32_t reg_cfg = 0;
+        const size_t share = type != 0 ? wave_reg_lds_share() : 0;
+        const size_t lds   = !lsi_fused_is_64x16(id) ? lsi_fused_lds_bytes<41, 12>(h->nVar, h->nObj, h->cap, (uint32_t)type, share, resident_lds, reg_cfg)
+                                                          : lsi_fused_lds_bytes<64, 16>(h->nVar, h->nObj, h->cap, (uint32_t)type, share, resident_lds, reg_cfg);
+        return lds <= kLsiFusedMaxLdsBytes ? 1 : 0;
     }
 
     static int upload_round(lexls_lse_t h, const void *h_in, int gather, bool trusted);

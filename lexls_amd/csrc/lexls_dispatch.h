@@ -427,6 +427,9 @@ namespace lexls
         return dispatch::offset(KernelId::lsi_fused_41x12e, dispatch::wave_shape(q) + (q.reg_type != 0 ? 3 : 0));
     }
 
+    /// the instantiation behind a plan of plan_lsi_fused: <64, 16> (true) or <41, 12> — the launch table's own columns (X-list above), for whoever sums the LDS
+    inline bool lsi_fused_is_64x16(KernelId id) { return id == KernelId::lsi_fused_64x16 || id == KernelId::lsi_fused_64x16_R; }
+
     /// true when the REG instantiation a regularized batch of these capacities takes gets its LDS (the launcher's own test)
     inline bool wave_reg_kernel_fits(const DispatchQuery &q)
     {

@@ -35,6 +35,9 @@ extern "C"
     int lexls_internal_resident_reg_serves(lexls_lse_t h, int type);
     /// ALL remaining resident iterations in one persistent launch (resident_args: a ResidentArgs); 1 = the shape has none, nothing changed
     int lexls_internal_resident_fused(lexls_lse_t h, int has_fixed, int count, double tolW, double tolC, const void *resident_args, size_t resident_args_bytes);
+    /// 1 when lexls_internal_resident_fused would take the launch for a run of regularization `type` (0: none); resident_lds: the driver's LDS per
+    /// instance (resident_lds_per_wave).  A pure predicate: nothing is launched, nothing changes
+    int lexls_internal_resident_fused_serves(lexls_lse_t h, int has_fixed, int type, size_t resident_lds);
     /// the device buffer lexls_lse_multipliers filled last (NULL: none valid), and whether the sweep served it
     const double *lexls_internal_multipliers(lexls_lse_t h, int *swept);
     /// the handle's kernel policy (lexls_lse_set_kernel_policy), to put it back after a change

@@ -169,6 +169,24 @@ namespace lexls
     }
 
     // ---- the sensitivity sweep (lexls_sweep_impl.h) ----
+    inline size_t sweep_lds_bytes(uint32_t nVar, uint32_t cap);
+
+    // ---- the persistent LexLSI launch (lsi_fused_impl.h) ----
+    constexpr size_t kLsiFusedMaxLdsBytes = 64 * 1024;
+    /// dynamic LDS of one workgroup of the <NC, MD> instantiation: the largest of its phases' — the l-QR's (reg_type != 0: with the regularization
+    /// routines' pieces, reg_cfg as the body reads it), the removal sweep's and the driver's own (resident_lds: resident_lds_per_wave).  The ONE sum: the
+    /// launcher launches with it and lexls_internal_resident_fused_serves decides on it; above kLsiFusedMaxLdsBytes the launch is not taken
+    template <int NC, int MD>
+    inline size_t lsi_fused_lds_bytes(uint32_t nVar, uint32_t nObj, uint32_t cap, uint32_t reg_type, size_t reg_share, size_t resident_lds, uint32_t &reg_cfg)
+    {
+        size_t lds = wave_lds_bytes<NC, MD>(nObj, wave_img_doubles<MD>(nVar, nObj));
+        reg_cfg    = 0;
+        if (reg_type != 0) lds = wave_reg_lds_bytes<MD>(nVar, reg_type, reg_share, lds, reg_cfg);
+        const size_t l2 = sweep_lds_bytes(nVar, cap);
+        lds             = lds > l2 ? lds : l2;
+        return lds > resident_lds ? lds : resident_lds;
+    }
+
     /// dynamic LDS of one sweep: staged factor, Householder scalars, multipliers / right-hand sides / fixed-variable multipliers of 8 objectives, types
     inline size_t sweep_lds_bytes(uint32_t nVar, uint32_t cap)
     {

@@ -71,6 +71,7 @@ extern "C"
     {
         return guarded([&]() {
             if (!b || !h_stats4) throw Exception("lexls_lsi_batch_stats: null argument");
+            b->refuse_pending("lexls_lsi_batch_stats");
             std::memcpy(h_stats4, b->last_stats, sizeof(b->last_stats));
             return LEXLS_OK;
         });
@@ -90,6 +91,7 @@ extern "C"
     {
         return guarded([&]() {
             if (!b) throw Exception("lexls_lsi_batch_run: null handle");
+            b->refuse_pending("lexls_lsi_batch_run");
             if (h_params && nparams != 9 && nparams != 12) throw Exception("lexls_lsi_batch_solve_ex: 9 or 12 parameters expected"); // (the name its callers have always seen)
             const ParametersLexLSI par = unpack(h_params, nparams);
             if (const int refused = b->refuse_run("lexls_lsi_batch_run", h_reg_factors, par, h_v0 != NULL)) return refused; // (nothing launched, the outputs as they are)
@@ -110,6 +112,7 @@ extern "C"
     {
         return guarded([&]() {
             if (!b) throw Exception("lexls_lsi_batch_run_device: null handle");
+            b->refuse_pending("lexls_lsi_batch_run_device");
             if (h_params && nparams != 9 && nparams != 12) throw Exception("lexls_lsi_batch_run_device: 9 or 12 parameters expected");
             if (!d_data || !d_x) throw Exception("lexls_lsi_batch_run_device: null data / x");
             if (b->off && !d_var_index) throw Exception("lexls_lsi_batch_run_device: a simple-bounds objective needs variable indices");
@@ -135,6 +138,46 @@ extern "C"
         });
     }
 
+    int lexls_lsi_batch_enqueue_device(lexls_lsi_batch_t b, void *hip_stream, const double *d_data, const uint32_t *d_var_index, const uint8_t *d_active_guess,
+                                       const double *d_x0, const double *d_v0, const double *h_reg_factors, const double *h_params, uint32_t nparams, double *d_x,
+                                       int32_t *d_info6, uint8_t *d_active, double *d_v, double *d_lambda, uint32_t *d_cycling_counts, uint32_t *d_status)
+    {
+        return guarded([&]() {
+            if (!b) throw Exception("lexls_lsi_batch_enqueue_device: null handle");
+            if (h_params && nparams != 9 && nparams != 12) throw Exception("lexls_lsi_batch_enqueue_device: 9 or 12 parameters expected");
+            if (!d_data || !d_x) throw Exception("lexls_lsi_batch_enqueue_device: null data / x");
+            if (b->off && !d_var_index) throw Exception("lexls_lsi_batch_enqueue_device: a simple-bounds objective needs variable indices");
+            const ParametersLexLSI par = unpack(h_params, nparams);
+            if (const int refused = b->refuse_run("lexls_lsi_batch_enqueue_device", h_reg_factors, par, false)) return refused;
+            if (!b->would_be_fused(par)) // no detour: nothing is enqueued, the outputs stay as they are
+            {
+                lexls_internal_set_error("lexls_lsi_batch_enqueue_device: only runs that lexls_lsi_batch_run_device serves and whose resident iterations are one persistent launch "
+                                         "are served (not: LEXLS_LSI_NO_FUSED, shapes without a persistent instantiation or whose launch does not get its LDS, a batch "
+                                         "split into several groups by LEXLS_LSI_GROUPS)");
+                return static_cast<int>(LEXLS_ERR_UNSUPPORTED);
+            }
+            if (d_lambda && b->lam_rc_after(par) != LEXLS_OK) // as lexls_lsi_batch_run_device_ex: refused before any device work
+            {
+                lexls_internal_set_error("lexls_lsi_batch_enqueue_device: d_lambda is not served for a run with cycling handling enabled, a regularized run or more than 65535 "
+                                         "constraints (lexls_lsi_batch_get_lambda is not available after such a run)");
+                return static_cast<int>(LEXLS_ERR_UNSUPPORTED);
+            }
+            lexls_lsi_batch_s::DeviceArrays dev{d_data, d_var_index, d_active_guess, d_x0, d_x, d_info6, d_active, d_v};
+            dev.v0 = d_x0 ? d_v0 : NULL; // v0 without x0 is disregarded (lexlsi.h:695-701)
+            dev.cycling_counts = d_cycling_counts;
+            b->enqueue_device(static_cast<hipStream_t>(hip_stream), dev, h_reg_factors, par, d_status, d_lambda);
+            return static_cast<int>(LEXLS_OK);
+        });
+    }
+
+    int lexls_lsi_batch_finish(lexls_lsi_batch_t b, void *hip_stream)
+    {
+        return guarded([&]() {
+            if (!b) throw Exception("lexls_lsi_batch_finish: null handle");
+            return b->finish(static_cast<hipStream_t>(hip_stream));
+        });
+    }
+
     int lexls_lsi_batch_set_instance_regularization(lexls_lsi_batch_t b, const double *factors, int in_device_memory)
     {
         return guarded([&]() {
@@ -147,6 +190,7 @@ extern "C"
     {
         return guarded([&]() {
             if (!b) throw Exception("lexls_lsi_batch_get_lambda: null handle");
+            b->refuse_pending("lexls_lsi_batch_get_lambda");
             return b->get_lambda(h_lambda);
         });
     }
@@ -155,6 +199,7 @@ extern "C"
     {
         return guarded([&]() {
             if (!b) throw Exception("lexls_lsi_batch_get_cycling_counters: null handle");
+            b->refuse_pending("lexls_lsi_batch_get_cycling_counters");
             return b->get_cycling_counters(h_counts);
         });
     }
@@ -171,6 +216,7 @@ extern "C"
     {
         return guarded([&]() {
             if (!b) throw Exception("lexls_lsi_batch_get_working_set_log: null handle");
+            b->refuse_pending("lexls_lsi_batch_get_working_set_log");
             return b->get_working_set_log(h_log, h_alpha, h_counts);
         });
     }

@@ -27,9 +27,12 @@ namespace
     /// row r = r-th active constraint in working-set order, simple bounds first) go to the user's order — instance b's output is total x nObj,
     /// column-major, column off + k = LexLSE objective k, column 0 zero when objective 0 holds simple bounds, inactive rows zero.
     /// One workgroup per instance, lane = active constraint; map = [nact (B) | pos (B x total): user row of active constraint r].
+    /// fault (lexls_lsi_batch_enqueue_device; else NULL): the run's fault word — with it set nothing is written
     __global__ __launch_bounds__(64) void lsi_lambda_scatter_kernel(const double *__restrict__ mult, const uint32_t *__restrict__ map, uint32_t B, uint32_t total,
-                                                                    uint32_t nObj, uint32_t nObjL, uint32_t off, uint32_t ldo, double *__restrict__ out)
+                                                                    uint32_t nObj, uint32_t nObjL, uint32_t off, uint32_t ldo, double *__restrict__ out,
+                                                                    const uint32_t *__restrict__ fault)
     {
+        if (fault && *fault != 0xffffffffu) return;
         const uint32_t b = blockIdx.x;
         double *o        = out + (size_t)b * total * nObj;
         for (uint32_t i = threadIdx.x; i < total * nObj; i += blockDim.x) o[i] = 0.0;
@@ -55,6 +58,19 @@ namespace
         if (t >= B * nObjL) return;
         const uint32_t i = t / nObjL, k = t - i * nObjL;
         out[t] = factors[(size_t)i * nObj + off + k];
+    }
+
+    /// lexls_lsi_batch_enqueue_device with h_reg_factors: the factors of the LexLSE levels travel in the launch itself (nothing of the host is read
+    /// after the call returns; a captured launch keeps the capturing call's), every row of the group's handle array (B x nObjL) takes them
+    struct LevelFactors
+    {
+        double f[STEP_MAX_OBJ];
+    };
+    __global__ __launch_bounds__(256) void lsi_level_factors_kernel(LevelFactors lf, uint32_t B, uint32_t nObjL, double *__restrict__ out)
+    {
+        const uint32_t t = blockIdx.x * blockDim.x + threadIdx.x;
+        if (t >= B * nObjL) return;
+        out[t] = lf.f[t % nObjL];
     }
 } // namespace
 
@@ -132,6 +148,35 @@ struct lexls_lsi_batch_s
     std::unique_ptr<WlogBufs> wlog;      // NULL: logging is off
     bool wlog_valid = false;             // the slab describes the last run (which ran with logging on and did not fail)
     std::vector<uint8_t> wlog_from_host; // batch: this run's entries of the instance are all its host object's (it never became resident)
+
+    // ---- lexls_lsi_batch_enqueue_device / lexls_lsi_batch_finish: what the stream-ordered run keeps between the two calls ----
+    struct Async
+    {
+        uint32_t *d_fault = NULL;      // the fault word of the run (every group's setup kernel takes its minimum into it)
+        Pinned<uint32_t> fault_host;
+        hipEvent_t ev_fork = NULL;     // the caller's stream at the start of the run: the groups' streams wait for it
+        double *d_inst = NULL;         // INST_HOST factors on the device (batch x nObj) ...
+        Pinned<double> inst_stage;     // ... and the pinned copy they are uploaded from, when they have changed (inst_uploaded != inst_gen)
+        uint64_t inst_uploaded = 0;
+        bool pending = false;          // an enqueue without its finish
+        bool enqueued = false;         // there has been an enqueue (finish may be called again behind every replay of a captured one)
+        hipStream_t stream = NULL;     // of the last enqueue
+        ParametersLexLSI par;          // of the last enqueue
+        ~Async()
+        {
+            if (d_fault) (void)hipFree(d_fault);
+            if (d_inst) (void)hipFree(d_inst);
+            if (ev_fork) (void)hipEventDestroy(ev_fork);
+        }
+    };
+    std::unique_ptr<Async> async;
+    uint64_t inst_gen = 1; // counts the calls of lexls_lsi_batch_set_instance_regularization with host factors
+    bool pending() const { return async && async->pending; }
+    /// what every synchronous entry point and host getter answers between an enqueue and its finish
+    void refuse_pending(const char *who) const
+    {
+        if (pending()) throw Exception(std::string(who) + ": a lexls_lsi_batch_enqueue_device run of this batch is waiting for lexls_lsi_batch_finish");
+    }
 
     /// what a group's next stage must serve (Run::wants): somebody alive, a factorize+solve, a sensitivity, a device-side step, a solve whose x the host needs
     enum : uint32_t { WANT_ALIVE = 1u, WANT_FS = 2u, WANT_SENS = 4u, WANT_STEP = 8u, WANT_X = 16u };
@@ -324,6 +369,23 @@ struct lexls_lsi_batch_s
         ctx.objidx[k] = -1;
     }
 
+    /// the groups' buffers of get_lambda, made at the first call that needs them
+    void ensure_lambda_bufs()
+    {
+        if (!lam_bufs.empty()) return;
+        lam_bufs.resize(nGroups);
+        for (uint32_t g = 0; g < nGroups; g++)
+        {
+            lam_bufs[g].reset(new LambdaBufs());
+            LambdaBufs &lb    = *lam_bufs[g];
+            const size_t Bg   = grp[g]->B;
+            lb.map.assign(Bg + Bg * total, 0u);
+            if (hipSetDevice(device) != hipSuccess || hipMalloc((void **)&lb.d_map, 4 * (Bg + Bg * total)) != hipSuccess ||
+                hipMalloc((void **)&lb.d_out, 8 * Bg * total * nObj) != hipSuccess)
+                throw Exception("hipMalloc failed (lexls_lsi_batch_get_lambda)");
+        }
+    }
+
     /// LexLSI::getLambda (lexlsi.h:552-605) for every instance of the last run, on the device in each group's stream: the final equality
     /// problems are formed (rows gathered by reference, fixed variables posted), factorized with the factor kept on a bit-exact kernel, all
     /// objectives' multipliers taken in one sweep (lexls_lse_multipliers), scattered into the user's order, one copy back per group.
@@ -338,20 +400,7 @@ struct lexls_lsi_batch_s
         }
         if (!h_lambda && !d_lambda) throw Exception("lexls_lsi_batch_get_lambda: null output");
         const uint32_t nObjL = nObj - off;
-        if (lam_bufs.empty())
-        {
-            lam_bufs.resize(nGroups);
-            for (uint32_t g = 0; g < nGroups; g++)
-            {
-                lam_bufs[g].reset(new LambdaBufs());
-                LambdaBufs &lb    = *lam_bufs[g];
-                const size_t Bg   = grp[g]->B;
-                lb.map.assign(Bg + Bg * total, 0u);
-                if (hipSetDevice(device) != hipSuccess || hipMalloc((void **)&lb.d_map, 4 * (Bg + Bg * total)) != hipSuccess ||
-                    hipMalloc((void **)&lb.d_out, 8 * Bg * total * nObj) != hipSuccess)
-                    throw Exception("hipMalloc failed (lexls_lsi_batch_get_lambda)");
-            }
-        }
+        ensure_lambda_bufs();
         // LEXLS_LSI_TIMING: the stages one by one (a synchronisation behind each) and their times on stderr
         const bool timing = RunSwitches().timing;
         double ts[4] = {0, 0, 0, 0}, tp = BatchCtx::now();
@@ -386,7 +435,7 @@ struct lexls_lsi_batch_s
             if (hipMemcpyAsync(lb.d_map, lb.map.data(), 4 * ((size_t)ctx.B + (size_t)ctx.B * total), hipMemcpyHostToDevice, ctx.stream) != hipSuccess)
                 throw Exception("hipMemcpyAsync failed (lexls_lsi_batch_get_lambda)");
             hipLaunchKernelGGL(lsi_lambda_scatter_kernel, dim3(ctx.B), dim3(64), 0, ctx.stream, d_mult, lb.d_map, ctx.B, (uint32_t)total, nObj, nObjL, off,
-                               nVar + ctx.cap, d_lambda ? d_lambda + (size_t)lo[g] * total * nObj : lb.d_out);
+                               nVar + ctx.cap, d_lambda ? d_lambda + (size_t)lo[g] * total * nObj : lb.d_out, (const uint32_t *)NULL);
             if (hipGetLastError() != hipSuccess) throw Exception("lsi_lambda_scatter_kernel launch failed");
             if (!d_lambda && hipMemcpyAsync(h_lambda + (size_t)lo[g] * total * nObj, lb.d_out, 8 * (size_t)ctx.B * total * nObj, hipMemcpyDeviceToHost, ctx.stream) != hipSuccess)
                 throw Exception("hipMemcpyAsync failed (lexls_lsi_batch_get_lambda)");
@@ -538,6 +587,7 @@ struct lexls_lsi_batch_s
             return LEXLS_OK;
         }
         inst_factors.assign(factors, factors + (size_t)batch * nObj);
+        inst_gen++;
         d_inst_factors = NULL;
         inst_mode      = INST_HOST;
         return LEXLS_OK;
@@ -1033,6 +1083,12 @@ struct lexls_lsi_batch_s
         report(r);
     }
 
+    /// ... and why not, after a run_device / enqueue_device run
+    static const char *lam_msg_after_device_run(const ParametersLexLSI &par)
+    {
+        return par.cycling_handling_enabled ? "lexls_lsi_batch_get_lambda: not available after a run with cycling handling enabled (it may have relaxed bounds in the resident constraint data)"
+                                               : "lexls_lsi_batch_get_lambda: not available after a regularized run";
+    }
     /// what lexls_lsi_batch_get_lambda answers after a run with these parameters (LEXLS_OK: it is served)
     int lam_rc_after(const ParametersLexLSI &par) const
     {
@@ -1052,8 +1108,170 @@ struct lexls_lsi_batch_s
         run_phase1_on_device(r, &dev);
         finish_working_set_log();
         lam_rc  = lam_rc_after(par);
-        lam_msg = par.cycling_handling_enabled ? "lexls_lsi_batch_get_lambda: not available after a run with cycling handling enabled (it may have relaxed bounds in the resident constraint data)"
-                                               : "lexls_lsi_batch_get_lambda: not available after a regularized run";
+        lam_msg = lam_msg_after_device_run(par);
+    }
+
+    /// the runs lexls_lsi_batch_enqueue_device serves: those of run_device that the persistent launch takes, decided on numbers (every group's handle:
+    /// their batch sizes differ by one)
+    bool would_be_fused(const ParametersLexLSI &par) const
+    {
+        if (nGroups != 1 || !would_be_resident(par)) return false; // (several groups: only under LEXLS_LSI_GROUPS where runs are resident; not served)
+        for (uint32_t g = 0; g < nGroups; g++)
+            if (!lexls_internal_resident_fused_serves(grp[g]->h, off ? 1 : 0, static_cast<int>(par.regularization_type), resident_lds_per_wave(grp[g]->rshape.SD, grp[g]->rshape.total))) return false;
+        return true;
+    }
+
+    /// lexls_lsi_batch_enqueue_device (the caller has checked would_be_fused(par): one group): run_phase1_on_device with device arrays, without its waits.
+    /// The run forks from `s` into the group's stream and joins it again; the fault word stays on the device (lsi_phase1_gate_kernel acts on it); nothing
+    /// comes back to the host before finish().  No HIP call here waits for the device, and none allocates once a run with these options has been enqueued
+    void enqueue_device(hipStream_t s, const DeviceArrays &dev, const double *h_reg_factors, const ParametersLexLSI &par, uint32_t *d_status, double *d_lambda)
+    {
+        if (hipSetDevice(device) != hipSuccess) throw Exception("hipSetDevice failed (lexls_lsi_batch_enqueue_device)");
+        if (d_lambda) ensure_lambda_bufs();
+        if (!async)
+        {
+            std::unique_ptr<Async> a(new Async());
+            if (hipMalloc((void **)&a->d_fault, 16) != hipSuccess || hipEventCreateWithFlags(&a->ev_fork, hipEventDisableTiming) != hipSuccess)
+                throw Exception("hipMalloc / hipEventCreate failed (lexls_lsi_batch_enqueue_device)");
+            a->fault_host.assign(4, 0xffffffffu);
+            for (uint32_t g = 0; g < nGroups; g++)
+                if (hipEventCreateWithFlags(&grp[g]->ev_joined, hipEventDisableTiming) != hipSuccess)
+                    throw Exception("hipEventCreate failed (lexls_lsi_batch_enqueue_device)");
+            async = std::move(a);
+        }
+        Async &as = *async;
+        Run r{NULL, NULL, NULL, h_reg_factors, NULL, NULL, par, NULL, NULL, NULL, NULL, NULL};
+        take_instance_regularization(r);
+        const int reg_type     = static_cast<int>(par.regularization_type);
+        const uint32_t nObjL   = nObj - off, dim0 = off ? dims[0] : 0u;
+        const int32_t max_fact = static_cast<int32_t>(par.max_number_of_factorizations);
+        const double *d_rows   = r.d_inst_rows;
+        if (r.inst_rows) // host factors of every instance: one pinned copy, uploaded when they have changed
+        {
+            if (as.inst_uploaded != inst_gen)
+            {
+                if (as.pending) throw Exception("lexls_lsi_batch_enqueue_device: the host factors of lexls_lsi_batch_set_instance_regularization have changed while an enqueued run "
+                                                "may still read the previous ones: call lexls_lsi_batch_finish first");
+                if (!as.d_inst)
+                {
+                    if (hipMalloc((void **)&as.d_inst, 8 * (size_t)batch * nObj) != hipSuccess) throw Exception("hipMalloc failed (lexls_lsi_batch_enqueue_device)");
+                    as.inst_stage.assign((size_t)batch * nObj, 0.0);
+                }
+                std::copy(inst_factors.begin(), inst_factors.end(), as.inst_stage.begin());
+                if (hipMemcpyAsync(as.d_inst, as.inst_stage.data(), 8 * (size_t)batch * nObj, hipMemcpyHostToDevice, s) != hipSuccess)
+                    throw Exception("hipMemcpyAsync failed (per-instance regularization factors)");
+                as.inst_uploaded = inst_gen;
+            }
+            d_rows = as.d_inst;
+        }
+        // the host's record of the last run: nothing of it is valid until finish()
+        wlog_valid  = false;
+        lam_rc      = -1;
+        lam_tol     = par.tol_linear_dependence;
+        last_kernel = "host";
+        std::fill(cycling_count.begin(), cycling_count.end(), 0u);
+        as.pending = as.enqueued = true;
+        as.stream  = s;
+        as.par     = par;
+        hipLaunchKernelGGL(lsi_fault_reset_kernel, dim3(1), dim3(64), 0, s, as.d_fault);
+        if (hipGetLastError() != hipSuccess || hipEventRecord(as.ev_fork, s) != hipSuccess) throw Exception("lsi_fault_reset_kernel launch / hipEventRecord failed (lexls_lsi_batch_enqueue_device)");
+        for (uint32_t g = 0; g < nGroups; g++)
+        {
+            BatchCtx &ctx = *grp[g];
+            if (hipStreamWaitEvent(ctx.stream, as.ev_fork, 0) != hipSuccess) throw Exception("hipStreamWaitEvent failed (lexls_lsi_batch_enqueue_device)");
+            // prepare_groups, without BatchCtx::reset(): the pinned blocks it clears belong to the host-driven stages, which this run has none of
+            ctx.gather = true;
+            ctx.clear_working_set_log_by_kernel();
+            ctx.set_first_wrong_sign(par.deactivate_first_wrong_sign);
+            ctx.set_cycling(par.cycling_handling_enabled, par.cycling_relax_step, static_cast<uint32_t>(par.cycling_max_counter));
+            hip_check(lexls_lse_set_tolerance(ctx.h, par.tol_linear_dependence));
+            ctx.reg_type = reg_type, ctx.reg_variable = par.variable_regularization_factor, ctx.reg_cg_iters = par.max_number_of_CG_iterations;
+            ctx.reg_dirty.store(false);
+            ctx.rounds_fs = ctx.rounds_sens = ctx.rounds_step = 0;
+            ctx.t_enqueue = ctx.t_wait = 0.0;
+            ctx.stage_fs = ctx.stage_sens = false;
+            if (reg_type == 0)
+                hip_check(lexls_lse_set_regularization(ctx.h, 0, NULL, 0, 0.0));
+            else // upload_regularization_block, every kind of factors written by a kernel in the group's stream
+            {
+                double *d_block = NULL;
+                hip_check(lexls_internal_set_regularization_block_device(ctx.h, reg_type, ctx.reg_variable, ctx.reg_cg_iters, &d_block));
+                const uint32_t cells = ctx.B * nObjL;
+                if (d_rows)
+                    hipLaunchKernelGGL(lsi_instance_factors_kernel, dim3((cells + 255) / 256), dim3(256), 0, ctx.stream, d_rows + (size_t)lo[g] * nObj, ctx.B, nObj, nObjL, off, d_block);
+                else
+                {
+                    LevelFactors lf;
+                    for (uint32_t k = 0; k < STEP_MAX_OBJ; k++) lf.f[k] = (h_reg_factors && k + off < nObj) ? h_reg_factors[k + off] : 0.0;
+                    hipLaunchKernelGGL(lsi_level_factors_kernel, dim3((cells + 255) / 256), dim3(256), 0, ctx.stream, lf, ctx.B, nObjL, d_block);
+                }
+                if (hipGetLastError() != hipSuccess) throw Exception("launch of the regularization factors' kernel failed");
+            }
+            ctx.rshape.tol_feasibility = par.tol_feasibility;
+            hip_check(lexls_internal_set_constraint_data_device(ctx.h, dev.data + (size_t)lo[g] * per_data, per_data));
+            if (dim0 && hipMemcpyAsync(ctx.d_rvar, dev.var_index + (size_t)lo[g] * dim0, 4 * (size_t)ctx.B * dim0, hipMemcpyDeviceToDevice, ctx.stream) != hipSuccess)
+                throw Exception("copy of the variable indices failed");
+            ctx.enqueue_phase1_setup(dev.x0 ? dev.x0 + (size_t)lo[g] * nVar : NULL, dev.active_guess ? dev.active_guess + (size_t)lo[g] * total : NULL, lo[g], max_fact,
+                                     dev.v0 ? dev.v0 + (size_t)lo[g] * total : NULL, as.d_fault);
+            const bool keep_fixed_bounds = lam_rc_after(par) == LEXLS_OK;
+            ctx.enqueue_phase1_gate(as.d_fault, max_fact);
+            ctx.enqueue_phase1_stage(dev.x0 != NULL, par.tol_wrong_sign_lambda, par.tol_correct_sign_lambda, max_fact, false);
+            ctx.enqueue_fused(par.tol_wrong_sign_lambda, par.tol_correct_sign_lambda, max_fact);
+            ctx.scatter_results(dev.x + (size_t)lo[g] * nVar, dev.info6 ? dev.info6 + (size_t)lo[g] * 6 : NULL, dev.active ? dev.active + (size_t)lo[g] * total : NULL,
+                                dev.v ? dev.v + (size_t)lo[g] * total : NULL, keep_fixed_bounds, dev.cycling_counts ? dev.cycling_counts + lo[g] : NULL, as.d_fault, g == 0 ? d_status : NULL);
+            if (d_lambda) // get_lambda(NULL, d_lambda) with the final problems formed where the working sets live
+            {
+                const double *d_mult = ctx.enqueue_lambda(max_fact, lam_bufs[g]->d_map, as.d_fault);
+                hipLaunchKernelGGL(lsi_lambda_scatter_kernel, dim3(ctx.B), dim3(64), 0, ctx.stream, d_mult, lam_bufs[g]->d_map, ctx.B, (uint32_t)total, nObj, nObjL, off, nVar + ctx.cap,
+                                   d_lambda + (size_t)lo[g] * total * nObj, (const uint32_t *)as.d_fault);
+                if (hipGetLastError() != hipSuccess) throw Exception("lsi_lambda_scatter_kernel launch failed");
+            }
+            if (hipEventRecord(ctx.ev_joined, ctx.stream) != hipSuccess || hipStreamWaitEvent(s, ctx.ev_joined, 0) != hipSuccess)
+                throw Exception("hipEventRecord / hipStreamWaitEvent failed (lexls_lsi_batch_enqueue_device)");
+        }
+    }
+
+    /// lexls_lsi_batch_finish: waits for the stream (NULL: the one of the last enqueue), then fetches what run_phase1_on_device downloads before it returns —
+    /// the fault word, the slabs with the working sets, counters and cycling counts, the active simple bounds — and leaves the batch as run_device does
+    int finish(hipStream_t s)
+    {
+        if (!async || !async->enqueued) throw Exception("lexls_lsi_batch_finish: no lexls_lsi_batch_enqueue_device on this batch");
+        Async &as = *async;
+        if (hipSetDevice(device) != hipSuccess || hipStreamSynchronize(s ? s : as.stream) != hipSuccess) throw Exception("lexls_lsi_batch_finish: stream synchronisation failed");
+        as.pending  = false;
+        lam_rc      = -1;
+        last_kernel = "host";
+        wlog_valid  = false;
+        std::fill(cycling_count.begin(), cycling_count.end(), 0u);
+        if (hipMemcpyAsync(as.fault_host.data(), as.d_fault, 4, hipMemcpyDeviceToHost, grp[0]->stream) != hipSuccess || hipStreamSynchronize(grp[0]->stream) != hipSuccess)
+            throw Exception("lexls_lsi_batch_finish: download of the fault word failed");
+        const uint32_t fault = as.fault_host[0];
+        if (fault != 0xffffffffu) throw Exception("lexls_lsi_batch_run: instance " + std::to_string(fault >> 3) + ": " + p1_fault_text(fault & 7u));
+        const ParametersLexLSI &par = as.par;
+        const bool keep_fixed_bounds = lam_rc_after(par) == LEXLS_OK;
+        int rounds_fs = 0, rounds_sens = 0, rounds_step = 0;
+        for (uint32_t g = 0; g < nGroups; g++)
+        {
+            BatchCtx &ctx = *grp[g];
+            if (keep_fixed_bounds) ctx.fetch_fixed_bounds();
+            ctx.download_resident(false, false, true);
+            bool went = false; // some instance was alive behind iteration 0 (run_phase1_on_device: the group went into the persistent launch)
+            for (uint32_t k = 0; k < ctx.B && !went; k++) went = ctx.rl.info(ctx.rws_host.data(), k)[1] > 1;
+            if (went) last_kernel = ctx.resident_kernel;
+            rounds_fs += ctx.rounds_fs, rounds_sens += ctx.rounds_sens, rounds_step += ctx.rounds_step + ctx.rounds_resident;
+        }
+        for (uint32_t b = 0; b < batch; b++)
+        {
+            uint32_t k;
+            BatchCtx &ctx = group_of_instance(b, k);
+            if (ctx.cycling) cycling_count[b] = ctx.rl.cyc(ctx.rws_host.data(), k)[CYC_COUNT];
+            keep_working_set_resident(b, ctx, k, NULL, NULL);
+        }
+        last_stats[0] = rounds_fs, last_stats[1] = rounds_sens, last_stats[2] = rounds_step, last_stats[3] = (int32_t)nGroups;
+        wlog_valid = wlog != nullptr;
+        lam_rc     = lam_rc_after(par);
+        lam_msg    = lam_msg_after_device_run(par);
+        return LEXLS_OK;
     }
 
     /// instance b's results into the caller's arrays, and its final working set for get_lambda

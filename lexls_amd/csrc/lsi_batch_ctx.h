@@ -214,6 +214,7 @@ namespace
         hipStream_t stream = NULL; // every group of a lock-step batch has its own stream: group A's kernels run while group B's host logic does
         hipStream_t stream_sens = NULL; // the sensitivity kernel of a stage serves other instances than its l-QR kernel: they run side by side
         hipEvent_t ev_uploaded = NULL, ev_sens_done = NULL;
+        hipEvent_t ev_joined = NULL; // lexls_lsi_batch_enqueue_device: this group's whole run is complete (made at the first such call)
         bool stage_fs = false, stage_sens = false; // what the stage in flight serves
         uint32_t B = 0, n = 0, nObjL = 0, cap = 0;
         size_t pstride = 0;
@@ -461,6 +462,20 @@ namespace
                 throw Exception("hipMemsetAsync failed (working-set log)");
         }
 
+        /// the same by kernels (lexls_lsi_batch_enqueue_device: no memset nodes in a captured run, lsi_zero_words_kernel)
+        void clear_working_set_log_by_kernel()
+        {
+            if (!d_wlog) return;
+            auto zero = [&](void *p, size_t words) {
+                const size_t blocks = (words + 255) / 256;
+                hipLaunchKernelGGL(lsi_zero_words_kernel, dim3((uint32_t)(blocks < 1024 ? blocks : 1024)), dim3(256), 0, stream, static_cast<uint32_t *>(p), words);
+            };
+            zero(d_wlog, (size_t)B * wlog_cap * RESIDENT_WLOG_FIELDS);
+            zero(d_wlog_alpha, 2 * (size_t)B * wlog_cap);
+            zero(d_wlog_count, (size_t)B);
+            if (hipGetLastError() != hipSuccess) throw Exception("lsi_zero_words_kernel launch failed (working-set log)");
+        }
+
         /// the handed-over instances start: slabs up, then `count` whole iterations are enqueued (nothing is waited for)
         void begin_resident()
         {
@@ -541,14 +556,15 @@ namespace
                          sum[0] / sum[4], sum[1] / sum[4], sum[2] / sum[4], sum[3] / sum[4], sum[4], sum[5], most[0] / most[4], most[1] / most[4], most[2] / most[4], most[3] / most[4], most[4], most[5]);
         }
         /// with_state = false: x and v went from the device slab to device arrays of the caller (scatter_results)
-        void download_resident(bool stamps_dump, bool with_state = true)
+        /// keep_kernel_name: resident_kernel was taken when the launch was enqueued (enqueue_fused; other factorizations have followed it since)
+        void download_resident(bool stamps_dump, bool with_state = true, bool keep_kernel_name = false)
         {
             if (hipMemcpyAsync(rws_host.data(), d_rws, rl.bytes_core, hipMemcpyDeviceToHost, stream) != hipSuccess ||
                 (cycling && hipMemcpyAsync(rws_host.data() + rl.o_cyc, d_rws + rl.o_cyc, rl.bytes_cyc, hipMemcpyDeviceToHost, stream) != hipSuccess) || // the relaxations done
                 (with_state && hipMemcpyAsync(rstate_host.data(), d_rstate, 8 * (size_t)B * rshape.SD, hipMemcpyDeviceToHost, stream) != hipSuccess) ||
                 hipStreamSynchronize(stream) != hipSuccess)
                 throw Exception("download of the resident state failed");
-            resident_kernel = lexls_lse_last_kernel(h); // the persistent launch, or the l-QR kernel of the last stage
+            if (!keep_kernel_name) resident_kernel = lexls_lse_last_kernel(h); // the persistent launch, or the l-QR kernel of the last stage
             if (fused_all && stamps_dump) dump_stamps();
             if (fused_all) // the persistent launch: the stages it ran = the iterations of the instance that ran longest (statistics only)
             {
@@ -571,10 +587,11 @@ namespace
         /// d_x0 / d_guess / d_v0: device arrays of this group's instances or NULL (d_v0, the caller's initial residuals, is read where it lies and
         /// only together with d_x0); first: the group's first instance in the batch.  The constraint data
         /// and the variable indices are in the handle / d_rvar already (same stream).  The fault word comes back with the next synchronisation
-        void enqueue_phase1_setup(const double *d_x0, const uint8_t *d_guess, uint32_t first, int32_t max_factorizations, const double *d_v0 = NULL)
+        /// run_fault (lexls_lsi_batch_enqueue_device): the word of the whole run, shared by the groups and cleared by the caller — it stays on the device
+        void enqueue_phase1_setup(const double *d_x0, const uint8_t *d_guess, uint32_t first, int32_t max_factorizations, const double *d_v0 = NULL, uint32_t *run_fault = NULL)
         {
             const double t0 = now();
-            if (!d_p1_fault)
+            if (!d_p1_fault && !run_fault)
             {
                 if (hipMalloc((void **)&d_p1_fault, 16) != hipSuccess) throw Exception("hipMalloc failed (phase 1 on the device)");
                 p1_fault_host.assign(4, 0xffffffffu);
@@ -583,16 +600,34 @@ namespace
             phase1_on_device = true;
             Phase1Args pa;
             pa.ra = resident_args(max_factorizations);
-            pa.x0 = d_x0, pa.guess = d_guess, pa.v0 = d_v0, pa.fault = d_p1_fault, pa.first = first;
-            if (hipMemsetAsync(d_p1_fault, 0xff, 16, stream) != hipSuccess) throw Exception("hipMemsetAsync failed (phase 1 on the device)");
+            pa.x0 = d_x0, pa.guess = d_guess, pa.v0 = d_v0, pa.fault = run_fault ? run_fault : d_p1_fault, pa.first = first;
+            if (!run_fault && hipMemsetAsync(d_p1_fault, 0xff, 16, stream) != hipSuccess) throw Exception("hipMemsetAsync failed (phase 1 on the device)");
             hipLaunchKernelGGL(lsi_phase1_setup_kernel, dim3((B + 3) / 4), dim3(256), 4 * resident_lds_per_wave(rshape.SD, rshape.total), stream, pa);
-            if (hipGetLastError() != hipSuccess || hipMemcpyAsync(p1_fault_host.data(), d_p1_fault, 4, hipMemcpyDeviceToHost, stream) != hipSuccess)
+            if (hipGetLastError() != hipSuccess || (!run_fault && hipMemcpyAsync(p1_fault_host.data(), d_p1_fault, 4, hipMemcpyDeviceToHost, stream) != hipSuccess))
                 throw Exception("lsi_phase1_setup_kernel launch failed");
             t_enqueue += now() - t0;
         }
+        /// lexls_lsi_batch_enqueue_device, behind the setup kernel: a run whose fault word is set goes no further (lsi_phase1_gate_kernel)
+        void enqueue_phase1_gate(const uint32_t *run_fault, int32_t max_factorizations)
+        {
+            hipLaunchKernelGGL(lsi_phase1_gate_kernel, dim3((B + 255) / 256), dim3(256), 0, stream, resident_args(max_factorizations), run_fault);
+            if (hipGetLastError() != hipSuccess) throw Exception("lsi_phase1_gate_kernel launch failed");
+        }
+        /// ... and behind iteration 0 every iteration that is left, in the persistent launch: the caller has asked lexls_internal_resident_fused_serves
+        void enqueue_fused(double tolW, double tolC, int32_t max_factorizations)
+        {
+            const ResidentArgs ra = resident_args(max_factorizations);
+            const int rc          = lexls_internal_resident_fused(h, rshape.dim0 ? 1 : 0, max_factorizations > 0 ? max_factorizations : 1, tolW, tolC, &ra, sizeof(ra));
+            if (rc == 1) throw Exception("lexls_lsi_batch_enqueue_device: the persistent launch was refused after lexls_internal_resident_fused_serves had accepted it");
+            hip_check(rc);
+            fused_all = true;
+            rounds_resident++, rounds_fs++, rounds_sens++;
+            resident_kernel = lexls_lse_last_kernel(h);
+        }
         /// second half: the stage of every resident iteration on the first problem — row gather + l-QR, the speculative removal search — and
         /// lsi_phase1_finish_kernel (iteration 0).  Every instance is resident from here on; the count of stopped instances comes back
-        void enqueue_phase1_stage(bool has_x0, double tolW, double tolC, int32_t max_factorizations)
+        /// (poll = false, lexls_lsi_batch_enqueue_device: nobody waits for the count)
+        void enqueue_phase1_stage(bool has_x0, double tolW, double tolC, int32_t max_factorizations, bool poll = true)
         {
             const double t0       = now();
             const ResidentArgs ra = resident_args(max_factorizations);
@@ -602,7 +637,7 @@ namespace
             hipLaunchKernelGGL(lsi_phase1_finish_kernel, dim3((B + 3) / 4), dim3(256), 4 * resident_lds_per_wave(rshape.SD, rshape.total), stream, ra, has_x0 ? 1u : 0u);
             if (hipGetLastError() != hipSuccess) throw Exception("lsi_phase1_finish_kernel launch failed");
             rounds_fs++, rounds_sens++;
-            if (hipMemcpyAsync(fin_host.data(), rl.finished(d_rws), 4, hipMemcpyDeviceToHost, stream) != hipSuccess) throw Exception("hipMemcpyAsync failed (finished count)");
+            if (poll && hipMemcpyAsync(fin_host.data(), rl.finished(d_rws), 4, hipMemcpyDeviceToHost, stream) != hipSuccess) throw Exception("hipMemcpyAsync failed (finished count)");
             std::fill(is_resident.begin(), is_resident.end(), 1);
             n_resident      = B;
             rounds_resident = 0;
@@ -615,7 +650,10 @@ namespace
         /// x / info / active / v of this group's instances from the slabs into device arrays of the caller (d_info6 / d_active / d_v may be NULL);
         /// with_fixed: the active simple bounds for lexls_lsi_batch_get_lambda as well (fix_var_host / fix_val_host, behind the next synchronisation);
         /// d_cyc_count (B words or NULL): the relaxations of every instance's cycling handler, zeros for a run without cycling handling
-        void scatter_results(double *d_x, int32_t *d_info6, uint8_t *d_active, double *d_v, bool with_fixed, uint32_t *d_cyc_count = NULL)
+        /// run_fault (lexls_lsi_batch_enqueue_device): the run's fault word — with it set the kernel writes nothing but d_status (one word or NULL: the
+        /// fault word, 0xffffffff for a good run), and nothing comes back to the host here (fetch_fixed_bounds, when the caller has waited)
+        void scatter_results(double *d_x, int32_t *d_info6, uint8_t *d_active, double *d_v, bool with_fixed, uint32_t *d_cyc_count = NULL, const uint32_t *run_fault = NULL,
+                             uint32_t *d_status = NULL)
         {
             with_fixed = with_fixed && rshape.dim0 != 0;
             if (with_fixed && !d_fix_var)
@@ -633,10 +671,43 @@ namespace
             sa.x = d_x, sa.v = d_v, sa.info6 = d_info6, sa.active = d_active;
             sa.fix_var = with_fixed ? d_fix_var : NULL, sa.fix_val = with_fixed ? d_fix_val : NULL;
             sa.cyc = cycling ? rl.cyc(d_rws) : NULL, sa.cyc_count = d_cyc_count;
-            hipLaunchKernelGGL(lsi_result_scatter_kernel, dim3((B + 3) / 4), dim3(256), 0, stream, sa);
+            if (run_fault)
+                hipLaunchKernelGGL(lsi_result_scatter_gated_kernel, dim3((B + 3) / 4), dim3(256), 0, stream, sa, run_fault, d_status);
+            else
+                hipLaunchKernelGGL(lsi_result_scatter_kernel, dim3((B + 3) / 4), dim3(256), 0, stream, sa);
             if (hipGetLastError() != hipSuccess) throw Exception("lsi_result_scatter_kernel launch failed");
-            if (with_fixed && (hipMemcpyAsync(fix_var_host.data(), d_fix_var, 4 * (size_t)B * rshape.dim0, hipMemcpyDeviceToHost, stream) != hipSuccess ||
+            if (with_fixed && !run_fault && (hipMemcpyAsync(fix_var_host.data(), d_fix_var, 4 * (size_t)B * rshape.dim0, hipMemcpyDeviceToHost, stream) != hipSuccess ||
                                hipMemcpyAsync(fix_val_host.data(), d_fix_val, 8 * (size_t)B * rshape.dim0, hipMemcpyDeviceToHost, stream) != hipSuccess))
+                throw Exception("hipMemcpyAsync failed (active simple bounds)");
+        }
+        /// lexls_lsi_batch_enqueue_device with d_lambda, behind scatter_results: get_lambda's stage with the final equality problems formed on the device
+        /// (lsi_lambda_form_kernel; d_map: the group's [nact | pos]) — rows gathered, factorized with the factor kept on a bit-exact kernel, every
+        /// objective's multipliers in one sweep.  -> the multipliers (B x nObjL x (n + cap)) for lsi_lambda_scatter_kernel
+        const double *enqueue_lambda(int32_t max_factorizations, uint32_t *d_map, const uint32_t *run_fault)
+        {
+            void *d_rank = NULL, *d_fcol = NULL;
+            hip_check(lexls_lse_device_ptr(h, LEXLS_ARRAY_RANK, &d_rank));
+            hip_check(lexls_lse_device_ptr(h, LEXLS_ARRAY_FIRST_COL, &d_fcol));
+            hipLaunchKernelGGL(lsi_lambda_form_kernel, dim3((B + 3) / 4), dim3(256), 0, stream, resident_args(max_factorizations), d_map, static_cast<uint32_t *>(d_rank),
+                               static_cast<uint32_t *>(d_fcol), run_fault);
+            if (hipGetLastError() != hipSuccess) throw Exception("lsi_lambda_form_kernel launch failed");
+            const int policy = lexls_internal_kernel_policy(h);
+            hip_check(lexls_lse_set_kernel_policy(h, 5)); // bit-exact kernels whatever the shape (the factor of the reference's getLambda)
+            int rc = lexls_internal_round_resident(h, rshape.dim0 ? 1 : 0);
+            if (rc == LEXLS_OK) rc = lexls_lse_factorize(h);
+            hip_check(lexls_lse_set_kernel_policy(h, policy));
+            hip_check(rc);
+            hip_check(lexls_lse_multipliers(h));
+            const double *d_mult = lexls_internal_multipliers(h, NULL);
+            if (!d_mult) throw Exception("lexls_lsi_batch_enqueue_device: no multipliers");
+            return d_mult;
+        }
+        /// the active simple bounds scatter_results left on the device, for a caller that kept them there (enqueued; download_resident waits)
+        void fetch_fixed_bounds()
+        {
+            if (!d_fix_var || !rshape.dim0) return;
+            if (hipMemcpyAsync(fix_var_host.data(), d_fix_var, 4 * (size_t)B * rshape.dim0, hipMemcpyDeviceToHost, stream) != hipSuccess ||
+                hipMemcpyAsync(fix_val_host.data(), d_fix_val, 8 * (size_t)B * rshape.dim0, hipMemcpyDeviceToHost, stream) != hipSuccess)
                 throw Exception("hipMemcpyAsync failed (active simple bounds)");
         }
         /// a host caller's guess / x0 for the setup kernel: staged in device buffers of the group (NULL in, NULL out)
@@ -704,6 +775,7 @@ namespace
             if (stream_sens) (void)hipStreamDestroy(stream_sens);
             if (ev_uploaded) (void)hipEventDestroy(ev_uploaded);
             if (ev_sens_done) (void)hipEventDestroy(ev_sens_done);
+            if (ev_joined) (void)hipEventDestroy(ev_joined);
             if (lod) (void)hipHostFree(lod);
         }
 

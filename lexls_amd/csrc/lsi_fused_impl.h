@@ -184,20 +184,16 @@ namespace lexls
             fa.collect     = fa.ra.first_wrong_sign ? 1 : 0;
             if (fa.collect && (!a.wrong_sign || fa.ra.wrong_sign != a.wrong_sign || !fa.ra.stamp)) return hipErrorInvalidValue;
             fr.reg_cfg     = 0;
-            size_t lds      = wave_lds_bytes<NC, MD>(a.nObj, fa.img_doubles);
-            if constexpr (REG) // the regularization routines' LDS behind the l-QR image, by the rule of the stage path's launcher
+            if constexpr (REG)
             {
                 if (!a.reg_scratch || !a.reg_factor) return hipErrorInvalidValue;
                 fa.a.resume_level = nullptr;
                 fa.a.resume_state = nullptr;
                 fa.ra.resume      = nullptr;
-                lds               = wave_reg_lds_bytes<MD>(a.nVar, a.reg_type, wave_reg_lds_share(), lds, fr.reg_cfg);
             }
-            const size_t l2 = sweep_lds_bytes(a.nVar, a.cap);
-            const size_t l3 = resident_lds_per_wave(fa.ra.sh.SD, fa.ra.sh.total);
-            lds             = lds > l2 ? lds : l2;
-            lds             = lds > l3 ? lds : l3;
-            if (lds > 64 * 1024) return hipErrorNotSupported; // (the caller falls back to the three launches per stage)
+            // (REG: the regularization routines' LDS behind the l-QR image, by the rule of the stage path's launcher)
+            const size_t lds = lsi_fused_lds_bytes<NC, MD>(a.nVar, a.nObj, a.cap, REG ? a.reg_type : 0u, REG ? wave_reg_lds_share() : 0, resident_lds_per_wave(fa.ra.sh.SD, fa.ra.sh.total), fr.reg_cfg);
+            if (lds > kLsiFusedMaxLdsBytes) return hipErrorNotSupported; // (the caller falls back to the three launches per stage)
             if constexpr (REG)
             {
                 if (sweep_level_dim <= 12)

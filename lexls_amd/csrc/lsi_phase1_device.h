@@ -191,7 +191,7 @@ namespace
         const uint32_t *cyc;
         uint32_t *cyc_count;
     };
-    __global__ __launch_bounds__(256) void lsi_result_scatter_kernel(ScatterArgs s)
+    __device__ __forceinline__ void lsi_result_scatter_body(const ScatterArgs &s)
     {
         const uint32_t lane = threadIdx.x & 63u;
         const uint32_t b    = blockIdx.x * 4 + (threadIdx.x >> 6);
@@ -216,5 +216,86 @@ namespace
                 s.fix_val[(size_t)b * d0 + i] = t == CTR_ACTIVE_LB ? blk[c] : blk[c + d0];
             }
         }
+    }
+    __global__ __launch_bounds__(256) void lsi_result_scatter_kernel(ScatterArgs s) { lsi_result_scatter_body(s); }
+
+    /// lexls_lsi_batch_enqueue_device, at the head of the run in the caller's stream: the run's fault word says "no fault" (four words are kept for it)
+    __global__ __launch_bounds__(64) void lsi_fault_reset_kernel(uint32_t *fault)
+    {
+        if (threadIdx.x < 4) fault[threadIdx.x] = 0xffffffffu;
+    }
+    /// ... and the group's rows of the working-set log are empty.  Kernels, where the synchronous run has hipMemsetAsync: a captured memset node did not
+    /// keep its pattern over back-to-back replays of the graph on the MI355X runtime (the fault word read B * nVar), a kernel node does
+    __global__ __launch_bounds__(256) void lsi_zero_words_kernel(uint32_t *p, size_t words)
+    {
+        for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < words; i += (size_t)gridDim.x * blockDim.x) p[i] = 0u;
+    }
+    /// lexls_lsi_batch_enqueue_device: nobody on the host has looked at the setup kernels' fault word (Phase1Args::fault, one word for the whole run, every
+    /// group's setup kernel complete) when the rest of the run is enqueued, so the device acts on it.  Behind the setup kernel of a group: a run with
+    /// an input error has every instance of the group stopped the way lsi_iterate_finish stops one (alive 0, skip 1, no removal search, counted as
+    /// finished) — the l-QR, the removal sweep, lsi_phase1_finish_kernel and the persistent launch then pass over every instance
+    __global__ __launch_bounds__(256) void lsi_phase1_gate_kernel(ResidentArgs a, const uint32_t *fault)
+    {
+        if (*fault == 0xffffffffu) return;
+        const uint32_t b = blockIdx.x * blockDim.x + threadIdx.x;
+        if (b >= a.B) return;
+        a.alive[b]  = 0;
+        a.skip[b]   = 1;
+        a.objidx[b] = -1;
+        if (b == 0) *a.finished = a.B;
+    }
+    /// ... the multipliers of such a run (d_lambda): what lexls_lsi_batch_get_lambda's form_final_problem posts from the downloaded working sets, from
+    /// the slabs where they live — instance b's final equality problem into the in slab (lsi_form_equality_problem on its final working set), not
+    /// skipped, no removal search, and map = [nact (B) | pos (B x total)]: the user row of every active constraint in working-set order, for
+    /// lsi_lambda_scatter_kernel.  One wavefront per instance.  A run with an input error posts EMPTY problems, skipped, with the ranks and first
+    /// columns of a factorization of nothing (rank / fcol: the handle's arrays): the sweep of the multipliers, which passes over nobody, finds no rows
+    __global__ __launch_bounds__(256) void lsi_lambda_form_kernel(ResidentArgs a, uint32_t *map, uint32_t *rank, uint32_t *fcol, const uint32_t *fault)
+    {
+        const uint32_t lane = threadIdx.x & 63u;
+        const uint32_t b    = blockIdx.x * 4 + (threadIdx.x >> 6);
+        if (b >= a.B) return;
+        const StepShape &sh  = a.sh;
+        const uint32_t total = sh.total;
+        if (*fault != 0xffffffffu)
+        {
+            for (uint32_t k = lane; k < a.nObjL; k += 64)
+            {
+                a.dims[(size_t)b * a.nObjL + k] = 0u;
+                rank[(size_t)b * a.nObjL + k]   = 0u;
+                fcol[(size_t)b * a.nObjL + k]   = 0u;
+            }
+            for (uint32_t r = lane; r < a.cap; r += 64) a.row_ld[(size_t)b * a.cap + r] = 0u;
+            if (lane == 0)
+            {
+                a.nfixed[b] = 0u;
+                a.skip[b]   = 1;
+                a.objidx[b] = -1;
+                map[b]      = 0u;
+            }
+            return;
+        }
+        const uint16_t *na = a.na + (size_t)b * RESIDENT_NA_STRIDE, *act = a.act + (size_t)b * total;
+        const uint8_t *cs  = a.ctr_state + (size_t)b * total;
+        const EqualityProblemSlab slab = {a.dims, a.nfixed, a.fixed_idx, a.fixed_val, a.row_src, a.row_ld, a.fixed_type, a.ctr_type};
+        lsi_form_equality_problem(sh, a.off, a.nObjL, a.cap, b, a.cdata + (size_t)b * sh.per_data, a.var + (size_t)b * sh.dim0, na, act, cs, slab, lane, 64u);
+        if (lane == 0) // (the lists are short)
+        {
+            uint32_t *pos = map + a.B + (size_t)b * total;
+            uint32_t r    = 0;
+            for (uint32_t k = 0; k < sh.nObj; k++)
+                for (uint32_t i = 0; i < na[k] && r < total; i++) pos[r++] = sh.first[k] + act[sh.first[k] + i];
+            map[b]      = r;
+            a.skip[b]   = 0;
+            a.objidx[b] = -1;
+        }
+    }
+    /// ... and the scatter of such a run: with an input error nothing of the caller's arrays is written.  status (one word, or NULL; the launch of
+    /// the batch's first group gets it): the fault word on both outcomes, 0xffffffff for a good run
+    __global__ __launch_bounds__(256) void lsi_result_scatter_gated_kernel(ScatterArgs s, const uint32_t *fault, uint32_t *status)
+    {
+        const uint32_t f = *fault;
+        if (status && blockIdx.x == 0 && threadIdx.x == 0) *status = f;
+        if (f != 0xffffffffu) return;
+        lsi_result_scatter_body(s);
     }
 } // namespace

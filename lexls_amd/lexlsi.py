@@ -388,6 +388,67 @@ class LsiBatch:
                 C.c_void_p(r["cycling_counters"].data_ptr()) if with_cycling_counters else None))
         return r
 
+    def enqueue_device(self, data, var_index=None, active_guess=None, x0=None, regularization_factors=None, v0=None, with_lambda=False,
+                       with_cycling_counters=False, stream=None, status=None, out=None, **params):
+        """lexls_lsi_batch_enqueue_device: run_device() as work in a stream — the same tensors, keywords and results, but the call only enqueues
+        the run and returns; nothing is waited for, so the inputs need only be complete in stream order and the returned tensors are complete
+        for work enqueued later in the same stream.  `stream`: a torch.cuda.Stream or a raw hipStream_t address; None: torch's current stream.
+        `status`: an int32 tensor of one element on the device, or None — it receives -1 (0xffffffff) for a good run and instance * 8 + code for
+        a run with an input error, whose other outputs are left as they were.  `out`: {"x", "info", "active", "v"[, "cycling_counters"]} to
+        write into (shapes and dtypes of run_device's result) instead of new tensors.  The host's view of the run — stats(), last_kernel(),
+        lambdas(), cycling_counters(), the working-set log — is there after finish(); until then those calls raise.  Only runs whose resident
+        iterations are one persistent launch are served (LEXLS_ERR_UNSUPPORTED otherwise, nothing enqueued; so for a batch that LEXLS_LSI_GROUPS
+        splits into groups).  The call may be captured (torch.cuda.graph) once the batch has served one uncaptured
+        enqueue_device() + finish() with the same options; while the graph is in use, finish() is the only other call on the batch."""
+        import torch
+        batch, total, nvar = self.batch, self.total, self.nvar
+        per_data = int(sum(int(d) * (2 if t == 1 else nvar + 2) for d, t in zip(self.dims, self.types)))
+        simple = int(self.types[0]) == 1
+        d_data = self._device_array("data", data, torch.float64, (batch, per_data), optional=False)
+        d_var = self._device_array("var_index", var_index, torch.int32, (batch, int(self.dims[0])), optional=not simple) if simple else None
+        d_guess = self._device_array("active_guess", active_guess, torch.uint8, (batch, total))
+        d_x0 = self._device_array("x0", x0, torch.float64, (batch, nvar))
+        d_v0 = self._device_array("v0", v0, torch.float64, (batch, total))
+        d_status = self._device_array("status", status, torch.int32, (1,))
+        if regularization_factors is not None or any(k in REG_PARAM_KEYS for k in params):
+            par = pack_params_ex(**params)
+        else:
+            par = pack_params(**params)
+        rfa = None if regularization_factors is None else np.ascontiguousarray(regularization_factors, np.float64)
+        dev = torch.device("cuda", self.device)
+        if stream is None:
+            stream = torch.cuda.current_stream(dev)
+        shapes = dict(x=((batch, nvar), torch.float64), info=((batch, 6), torch.int32), active=((batch, total), torch.uint8), v=((batch, total), torch.float64))
+        if with_lambda:
+            shapes["lambda"] = ((batch, len(self.dims), total), torch.float64)
+        if with_cycling_counters:
+            shapes["cycling_counters"] = ((batch,), torch.int32)
+        r = {}
+        for k, (shape, dtype) in shapes.items():
+            if out is not None and k in out:
+                self._device_array(k, out[k], dtype, shape, optional=False)
+                r[k] = out[k]
+            elif isinstance(stream, torch.cuda.Stream):
+                with torch.cuda.stream(stream):  # the fill is ordered in front of the run
+                    r[k] = torch.zeros(shape, dtype=dtype, device=dev)
+            else:
+                r[k] = torch.empty(shape, dtype=dtype, device=dev)  # (a raw stream: torch cannot order a fill in it; a good run writes every element)
+        handle = stream.cuda_stream if isinstance(stream, torch.cuda.Stream) else int(stream)
+        capi.check(capi.lib().lexls_lsi_batch_enqueue_device(
+            self._h, C.c_void_p(handle), d_data, d_var, d_guess, d_x0, d_v0, _p(rfa, C.c_double), _p(par, C.c_double), C.c_uint32(len(par)),
+            *(C.c_void_p(r[k].data_ptr()) for k in ("x", "info", "active", "v")),
+            C.c_void_p(r["lambda"].data_ptr()) if with_lambda else None,
+            C.c_void_p(r["cycling_counters"].data_ptr()) if with_cycling_counters else None, d_status))
+        return r
+
+    def finish(self, stream=None):
+        """lexls_lsi_batch_finish: waits for `stream` (a torch.cuda.Stream or a raw address; None: the stream of the last enqueue_device()) and
+        fetches what stats(), last_kernel(), lambdas(), cycling_counters() and the working-set log answer from.  Raises (LEXLS_ERR_INVALID, the
+        instance and the reason in the message) when the run had an input error; the batch then takes the next run normally.  After a replay
+        of a captured enqueue_device(), finish(replay_stream) answers for that replay."""
+        handle = None if stream is None else C.c_void_p(stream.cuda_stream if hasattr(stream, "cuda_stream") else int(stream))
+        capi.check(capi.lib().lexls_lsi_batch_finish(self._h, handle))
+
     def cycling_counters(self) -> np.ndarray:
         """LexLSI::getCyclingCounter() of every instance of the last run (lexls_lsi_batch_get_cycling_counters): (batch,) uint32, the bounds each
         instance's cycling handler relaxed; zeros after a run without cycling_handling_enabled"""
