@@ -492,6 +492,27 @@ int lexls_lsi_batch_finish(lexls_lsi_batch_t b, void *hip_stream);
  * LEXLS_LSI_RESIDENT=0 — with host factors the same run proceeds on the host path); LEXLS_ERR_UNSUPPORTED when device factors are set and
  * lexls_lsi_batch_run is given h_v0. */
 int lexls_lsi_batch_set_instance_regularization(lexls_lsi_batch_t b, const double *factors, int in_device_memory);
+/* Instance mask of the device entries: "not this instance, this run".  d_mask holds `batch` bytes in the memory of the batch's device; a byte of 0
+ * skips the instance for that run, any other value solves it.  The pointer is kept — no copy is made, on the host or on the device, and no run
+ * reads the mask on the host — alive until the setting is cleared or the batch destroyed.  The mask is read per run: on the device, at the start
+ * of every run and in the run's stream (the rule of lexls_lsi_batch_set_instance_regularization with in_device_memory = 1), so the caller may
+ * rewrite the bytes in place between two runs, and a captured run reads them again at every replay.  d_mask == NULL clears the setting: the batch
+ * is then what it was before the call.
+ * A skipped instance is not touched.  None of its input data is interpreted: it gets no input checks and cannot raise a fault word, and NaNs in
+ * its data, x0 or v0 reach no arithmetic whose result is stored anywhere.  Its caller-owned rows are untouched: d_x, d_info6, d_active, d_v,
+ * d_lambda and d_cycling_counts keep the bits they had before the run.  What the library owns describes the run, a skipped instance as an empty
+ * entry: working-set log count 0 and rows zero, lexls_lsi_batch_get_lambda rows zero, lexls_lsi_batch_get_cycling_counters 0.
+ * A solved instance gets the bits it gets without a mask, every output row, on the persistent launch and on the lock-step stages; an input error
+ * in a solved instance is reported as always (LEXLS_ERR_INVALID from the synchronous entries, d_status from the enqueued one) and names it.
+ * A mask whose bytes are all 0 is a valid run that solves nothing: LEXLS_OK, a good status word, every caller-owned output untouched.
+ * Served by exactly the device entries — lexls_lsi_batch_run_device, lexls_lsi_batch_run_device_ex, lexls_lsi_batch_enqueue_device — for every run
+ * they serve (a batch that LEXLS_LSI_GROUPS splits: the synchronous two; the group whose first instance is lo reads the mask from byte lo).
+ * lexls_lsi_batch_run is refused while the mask is set: LEXLS_ERR_UNSUPPORTED before any work, its outputs left alone — its phase 1 builds host
+ * objects from host data and cannot read a device mask (no detour, as for device factors).  The one-shot lexls_lsi_batch_solve* calls make their
+ * own batch object and are not concerned.  How it works: lsi_phase1_setup_kernel reads the instance's byte and leaves a skipped instance stopped
+ * (not alive, the equality solver's skip byte set), so every later kernel passes over it as over a finished one; the result scatter kernels do
+ * not store its rows.  Errors of this call: LEXLS_ERR_INVALID for a null handle or between lexls_lsi_batch_enqueue_device and its finish. */
+int lexls_lsi_batch_set_instance_mask(lexls_lsi_batch_t b, const uint8_t *d_mask);
 /* How a run executes: phase 1 of every instance on the host; from then on the instance's active-set iterations are resident on the
  * device (LEXLS_LSI_RESIDENT=0: host logic, lock-step stages).  Where the batch's shape has a persistent instantiation (the register-resident l-QR shapes:
  * nVar + 1 <= 41 with levels of up to 12 rows, nVar + 1 <= 64 with levels of up to 16 — except 42..48 columns), everything behind the first resident

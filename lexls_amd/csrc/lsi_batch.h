@@ -28,12 +28,14 @@ namespace
     /// column-major, column off + k = LexLSE objective k, column 0 zero when objective 0 holds simple bounds, inactive rows zero.
     /// One workgroup per instance, lane = active constraint; map = [nact (B) | pos (B x total): user row of active constraint r].
     /// fault (lexls_lsi_batch_enqueue_device; else NULL): the run's fault word — with it set nothing is written
+    /// mask (the group's bytes of lexls_lsi_batch_set_instance_mask, or NULL): `out` is the caller's d_lambda and the rows of a skipped instance stay as they are
     __global__ __launch_bounds__(64) void lsi_lambda_scatter_kernel(const double *__restrict__ mult, const uint32_t *__restrict__ map, uint32_t B, uint32_t total,
                                                                     uint32_t nObj, uint32_t nObjL, uint32_t off, uint32_t ldo, double *__restrict__ out,
-                                                                    const uint32_t *__restrict__ fault)
+                                                                    const uint32_t *__restrict__ fault, const uint8_t *mask)
     {
         if (fault && *fault != 0xffffffffu) return;
         const uint32_t b = blockIdx.x;
+        if (lsi_mask_byte(mask, b) == 0) return; // (block-uniform)
         double *o        = out + (size_t)b * total * nObj;
         for (uint32_t i = threadIdx.x; i < total * nObj; i += blockDim.x) o[i] = 0.0;
         __syncthreads();
@@ -95,6 +97,9 @@ struct lexls_lsi_batch_s
     int inst_mode = INST_NONE;
     std::vector<double> inst_factors;     // INST_HOST: the copy taken at the call
     const double *d_inst_factors = NULL;  // INST_DEVICE: the caller's array, read in the groups' streams at the start of every run
+    // ---- lexls_lsi_batch_set_instance_mask: batch bytes in device memory, the caller's; read by the kernels of every device run while set, never on the host ----
+    const uint8_t *d_mask = NULL;
+    const uint8_t *group_mask(uint32_t g) const { return d_mask ? d_mask + lo[g] : NULL; }
     double t_create = 0.0;
     int32_t last_stats[4] = {0, 0, 0, 0}; // of the last run: factorize+solve stages, sensitivity stages, stages with the step on the device, groups
     // ---- getLambda of the last run (lexls_lsi_batch_get_lambda, lexlsi.h:552-605) ----
@@ -417,25 +422,28 @@ struct lexls_lsi_batch_s
             LambdaBufs &lb = *lam_bufs[g];
             pool->run(ctx.B, [&](uint32_t k) { form_final_problem(g, k, lb); });
             stage(0, ctx);
+            bool any_active = false; // (a run whose mask skipped every instance of the group, or whose instances all ended with empty working sets)
+            for (uint32_t k = 0; k < ctx.B && !any_active; k++) any_active = lb.map[k] != 0;
             // the equality solver's parameters of this run, whichever path it took (the one-by-one path of a non-resident deactivate_first_wrong_sign run never set
             // them on these handles; an earlier run of the batch object may have left a regularization there): lam_rc == LEXLS_OK means unregularized
             hip_check(lexls_lse_set_tolerance(ctx.h, lam_tol));
             hip_check(lexls_lse_set_regularization(ctx.h, 0, NULL, 0, 0.0));
             const int policy = lexls_internal_kernel_policy(ctx.h);
             hip_check(lexls_lse_set_kernel_policy(ctx.h, 5)); // bit-exact kernels whatever the shape (the factor of the reference's getLambda)
-            int rc = lexls_internal_upload_round_trusted(ctx.h, ctx.in_block.data(), 1);
-            if (rc == LEXLS_OK) rc = lexls_lse_factorize(ctx.h);
+            int rc = any_active ? lexls_internal_upload_round_trusted(ctx.h, ctx.in_block.data(), 1) : LEXLS_OK;
+            if (rc == LEXLS_OK && any_active) rc = lexls_lse_factorize(ctx.h);
             hip_check(lexls_lse_set_kernel_policy(ctx.h, policy));
             hip_check(rc);
             stage(1, ctx);
-            hip_check(lexls_lse_multipliers(ctx.h));
+            if (any_active) hip_check(lexls_lse_multipliers(ctx.h));
             stage(2, ctx);
-            const double *d_mult = lexls_internal_multipliers(ctx.h, NULL);
+            // nobody has an active constraint: there is nothing to factorize and every row is zero — the scatter kernel reads no multiplier (nact = 0)
+            const double *d_mult = any_active ? lexls_internal_multipliers(ctx.h, NULL) : lb.d_out;
             if (!d_mult) throw Exception("lexls_lsi_batch_get_lambda: no multipliers");
             if (hipMemcpyAsync(lb.d_map, lb.map.data(), 4 * ((size_t)ctx.B + (size_t)ctx.B * total), hipMemcpyHostToDevice, ctx.stream) != hipSuccess)
                 throw Exception("hipMemcpyAsync failed (lexls_lsi_batch_get_lambda)");
             hipLaunchKernelGGL(lsi_lambda_scatter_kernel, dim3(ctx.B), dim3(64), 0, ctx.stream, d_mult, lb.d_map, ctx.B, (uint32_t)total, nObj, nObjL, off,
-                               nVar + ctx.cap, d_lambda ? d_lambda + (size_t)lo[g] * total * nObj : lb.d_out, (const uint32_t *)NULL);
+                               nVar + ctx.cap, d_lambda ? d_lambda + (size_t)lo[g] * total * nObj : lb.d_out, (const uint32_t *)NULL, d_lambda ? group_mask(g) : (const uint8_t *)NULL);
             if (hipGetLastError() != hipSuccess) throw Exception("lsi_lambda_scatter_kernel launch failed");
             if (!d_lambda && hipMemcpyAsync(h_lambda + (size_t)lo[g] * total * nObj, lb.d_out, 8 * (size_t)ctx.B * total * nObj, hipMemcpyDeviceToHost, ctx.stream) != hipSuccess)
                 throw Exception("hipMemcpyAsync failed (lexls_lsi_batch_get_lambda)");
@@ -591,6 +599,20 @@ struct lexls_lsi_batch_s
         d_inst_factors = NULL;
         inst_mode      = INST_HOST;
         return LEXLS_OK;
+    }
+    /// lexls_lsi_batch_set_instance_mask: the pointer is kept (NULL: no mask); nothing is read or copied here
+    int set_instance_mask(const uint8_t *d_mask_)
+    {
+        d_mask = d_mask_;
+        return LEXLS_OK;
+    }
+    /// lexls_lsi_batch_run while a mask is set: its phase 1 builds host objects from host data and cannot read a device mask — refused before any work
+    int refuse_masked_run(const char *who) const
+    {
+        if (!d_mask) return LEXLS_OK;
+        lexls_internal_set_error((std::string(who) + ": not served while lexls_lsi_batch_set_instance_mask holds an instance mask for this batch (the mask is device memory, read by "
+                                                     "the kernels of lexls_lsi_batch_run_device / lexls_lsi_batch_enqueue_device only): clear it with a NULL mask first").c_str());
+        return LEXLS_ERR_UNSUPPORTED;
     }
     /// the setting as a run with these parameters sees it (a run with regularization_type 0 ignores it, as it ignores h_reg_factors)
     void take_instance_regularization(Run &r) const
@@ -1035,7 +1057,8 @@ struct lexls_lsi_batch_s
                 throw Exception("copy of the variable indices failed");
             const uint8_t *gg = guess ? guess + (size_t)lo[g] * total : NULL;
             const double *xg  = x0 ? x0 + (size_t)lo[g] * nVar : NULL;
-            ctx.enqueue_phase1_setup(dev ? xg : ctx.stage_x0(xg), dev ? gg : ctx.stage_guess(gg), lo[g], max_fact, v0 ? v0 + (size_t)lo[g] * total : NULL);
+            ctx.enqueue_phase1_setup(dev ? xg : ctx.stage_x0(xg), dev ? gg : ctx.stage_guess(gg), lo[g], max_fact, v0 ? v0 + (size_t)lo[g] * total : NULL, NULL,
+                                     dev ? group_mask(g) : NULL); // (a mask is the device entries' alone: lexls_lsi_batch_run is refused while one is set)
         }
         r.t_ctx = BatchCtx::now() - r.t_begin;
         uint32_t fault = 0xffffffffu;
@@ -1062,7 +1085,7 @@ struct lexls_lsi_batch_s
             BatchCtx &ctx = *grp[g];
             if (dev)
                 ctx.scatter_results(dev->x + (size_t)lo[g] * nVar, dev->info6 ? dev->info6 + (size_t)lo[g] * 6 : NULL, dev->active ? dev->active + (size_t)lo[g] * total : NULL,
-                                    dev->v ? dev->v + (size_t)lo[g] * total : NULL, keep_fixed_bounds, dev->cycling_counts ? dev->cycling_counts + lo[g] : NULL);
+                                    dev->v ? dev->v + (size_t)lo[g] * total : NULL, keep_fixed_bounds, dev->cycling_counts ? dev->cycling_counts + lo[g] : NULL, NULL, NULL, group_mask(g));
             ctx.download_resident(r.sw.stamps_dump, dev == NULL);
             if (went[g]) last_kernel = ctx.resident_kernel;
         }
@@ -1212,18 +1235,18 @@ struct lexls_lsi_batch_s
             if (dim0 && hipMemcpyAsync(ctx.d_rvar, dev.var_index + (size_t)lo[g] * dim0, 4 * (size_t)ctx.B * dim0, hipMemcpyDeviceToDevice, ctx.stream) != hipSuccess)
                 throw Exception("copy of the variable indices failed");
             ctx.enqueue_phase1_setup(dev.x0 ? dev.x0 + (size_t)lo[g] * nVar : NULL, dev.active_guess ? dev.active_guess + (size_t)lo[g] * total : NULL, lo[g], max_fact,
-                                     dev.v0 ? dev.v0 + (size_t)lo[g] * total : NULL, as.d_fault);
+                                     dev.v0 ? dev.v0 + (size_t)lo[g] * total : NULL, as.d_fault, group_mask(g));
             const bool keep_fixed_bounds = lam_rc_after(par) == LEXLS_OK;
             ctx.enqueue_phase1_gate(as.d_fault, max_fact);
             ctx.enqueue_phase1_stage(dev.x0 != NULL, par.tol_wrong_sign_lambda, par.tol_correct_sign_lambda, max_fact, false);
             ctx.enqueue_fused(par.tol_wrong_sign_lambda, par.tol_correct_sign_lambda, max_fact);
             ctx.scatter_results(dev.x + (size_t)lo[g] * nVar, dev.info6 ? dev.info6 + (size_t)lo[g] * 6 : NULL, dev.active ? dev.active + (size_t)lo[g] * total : NULL,
-                                dev.v ? dev.v + (size_t)lo[g] * total : NULL, keep_fixed_bounds, dev.cycling_counts ? dev.cycling_counts + lo[g] : NULL, as.d_fault, g == 0 ? d_status : NULL);
+                                dev.v ? dev.v + (size_t)lo[g] * total : NULL, keep_fixed_bounds, dev.cycling_counts ? dev.cycling_counts + lo[g] : NULL, as.d_fault, g == 0 ? d_status : NULL, group_mask(g));
             if (d_lambda) // get_lambda(NULL, d_lambda) with the final problems formed where the working sets live
             {
-                const double *d_mult = ctx.enqueue_lambda(max_fact, lam_bufs[g]->d_map, as.d_fault);
+                const double *d_mult = ctx.enqueue_lambda(max_fact, lam_bufs[g]->d_map, as.d_fault, group_mask(g));
                 hipLaunchKernelGGL(lsi_lambda_scatter_kernel, dim3(ctx.B), dim3(64), 0, ctx.stream, d_mult, lam_bufs[g]->d_map, ctx.B, (uint32_t)total, nObj, nObjL, off, nVar + ctx.cap,
-                                   d_lambda + (size_t)lo[g] * total * nObj, (const uint32_t *)as.d_fault);
+                                   d_lambda + (size_t)lo[g] * total * nObj, (const uint32_t *)as.d_fault, group_mask(g));
                 if (hipGetLastError() != hipSuccess) throw Exception("lsi_lambda_scatter_kernel launch failed");
             }
             if (hipEventRecord(ctx.ev_joined, ctx.stream) != hipSuccess || hipStreamWaitEvent(s, ctx.ev_joined, 0) != hipSuccess)

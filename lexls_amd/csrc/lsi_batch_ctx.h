@@ -588,7 +588,9 @@ namespace
         /// only together with d_x0); first: the group's first instance in the batch.  The constraint data
         /// and the variable indices are in the handle / d_rvar already (same stream).  The fault word comes back with the next synchronisation
         /// run_fault (lexls_lsi_batch_enqueue_device): the word of the whole run, shared by the groups and cleared by the caller — it stays on the device
-        void enqueue_phase1_setup(const double *d_x0, const uint8_t *d_guess, uint32_t first, int32_t max_factorizations, const double *d_v0 = NULL, uint32_t *run_fault = NULL)
+        /// d_mask (lexls_lsi_batch_set_instance_mask): this group's bytes of the caller's instance mask or NULL, read by the kernel where they lie
+        void enqueue_phase1_setup(const double *d_x0, const uint8_t *d_guess, uint32_t first, int32_t max_factorizations, const double *d_v0 = NULL, uint32_t *run_fault = NULL,
+                                  const uint8_t *d_mask = NULL)
         {
             const double t0 = now();
             if (!d_p1_fault && !run_fault)
@@ -600,7 +602,7 @@ namespace
             phase1_on_device = true;
             Phase1Args pa;
             pa.ra = resident_args(max_factorizations);
-            pa.x0 = d_x0, pa.guess = d_guess, pa.v0 = d_v0, pa.fault = run_fault ? run_fault : d_p1_fault, pa.first = first;
+            pa.x0 = d_x0, pa.guess = d_guess, pa.v0 = d_v0, pa.fault = run_fault ? run_fault : d_p1_fault, pa.first = first, pa.mask = d_mask;
             if (!run_fault && hipMemsetAsync(d_p1_fault, 0xff, 16, stream) != hipSuccess) throw Exception("hipMemsetAsync failed (phase 1 on the device)");
             hipLaunchKernelGGL(lsi_phase1_setup_kernel, dim3((B + 3) / 4), dim3(256), 4 * resident_lds_per_wave(rshape.SD, rshape.total), stream, pa);
             if (hipGetLastError() != hipSuccess || (!run_fault && hipMemcpyAsync(p1_fault_host.data(), d_p1_fault, 4, hipMemcpyDeviceToHost, stream) != hipSuccess))
@@ -652,8 +654,9 @@ namespace
         /// d_cyc_count (B words or NULL): the relaxations of every instance's cycling handler, zeros for a run without cycling handling
         /// run_fault (lexls_lsi_batch_enqueue_device): the run's fault word — with it set the kernel writes nothing but d_status (one word or NULL: the
         /// fault word, 0xffffffff for a good run), and nothing comes back to the host here (fetch_fixed_bounds, when the caller has waited)
+        /// d_mask: this group's bytes of the instance mask or NULL — the rows of a skipped instance are not stored
         void scatter_results(double *d_x, int32_t *d_info6, uint8_t *d_active, double *d_v, bool with_fixed, uint32_t *d_cyc_count = NULL, const uint32_t *run_fault = NULL,
-                             uint32_t *d_status = NULL)
+                             uint32_t *d_status = NULL, const uint8_t *d_mask = NULL)
         {
             with_fixed = with_fixed && rshape.dim0 != 0;
             if (with_fixed && !d_fix_var)
@@ -671,6 +674,7 @@ namespace
             sa.x = d_x, sa.v = d_v, sa.info6 = d_info6, sa.active = d_active;
             sa.fix_var = with_fixed ? d_fix_var : NULL, sa.fix_val = with_fixed ? d_fix_val : NULL;
             sa.cyc = cycling ? rl.cyc(d_rws) : NULL, sa.cyc_count = d_cyc_count;
+            sa.mask = d_mask;
             if (run_fault)
                 hipLaunchKernelGGL(lsi_result_scatter_gated_kernel, dim3((B + 3) / 4), dim3(256), 0, stream, sa, run_fault, d_status);
             else
@@ -683,13 +687,14 @@ namespace
         /// lexls_lsi_batch_enqueue_device with d_lambda, behind scatter_results: get_lambda's stage with the final equality problems formed on the device
         /// (lsi_lambda_form_kernel; d_map: the group's [nact | pos]) — rows gathered, factorized with the factor kept on a bit-exact kernel, every
         /// objective's multipliers in one sweep.  -> the multipliers (B x nObjL x (n + cap)) for lsi_lambda_scatter_kernel
-        const double *enqueue_lambda(int32_t max_factorizations, uint32_t *d_map, const uint32_t *run_fault)
+        /// d_mask: this group's bytes of the instance mask or NULL — a skipped instance posts an empty problem
+        const double *enqueue_lambda(int32_t max_factorizations, uint32_t *d_map, const uint32_t *run_fault, const uint8_t *d_mask = NULL)
         {
             void *d_rank = NULL, *d_fcol = NULL;
             hip_check(lexls_lse_device_ptr(h, LEXLS_ARRAY_RANK, &d_rank));
             hip_check(lexls_lse_device_ptr(h, LEXLS_ARRAY_FIRST_COL, &d_fcol));
             hipLaunchKernelGGL(lsi_lambda_form_kernel, dim3((B + 3) / 4), dim3(256), 0, stream, resident_args(max_factorizations), d_map, static_cast<uint32_t *>(d_rank),
-                               static_cast<uint32_t *>(d_fcol), run_fault);
+                               static_cast<uint32_t *>(d_fcol), run_fault, d_mask);
             if (hipGetLastError() != hipSuccess) throw Exception("lsi_lambda_form_kernel launch failed");
             const int policy = lexls_internal_kernel_policy(h);
             hip_check(lexls_lse_set_kernel_policy(h, 5)); // bit-exact kernels whatever the shape (the factor of the reference's getLambda)

@@ -18,7 +18,12 @@ namespace
         const double *v0;     // B x total, or NULL: with x0 the instances' v is this array as it stands (set_v0, objective.h:226-236); read only with x0
         uint32_t *fault;      // one word for the run: min over the faulty instances of (index in the batch) * 8 + P1_* code
         uint32_t first;       // index in the batch of this group's instance 0
+        const uint8_t *mask;  // B bytes, or NULL (lexls_lsi_batch_set_instance_mask): 0 = the instance is skipped in this run
     };
+
+    /// byte b of an instance mask (NULL: every instance is solved).  The bytes are the caller's, rewritten in place between two runs and between two
+    /// replays of a captured run: read where they lie by a vector load of every lane (volatile: never a load through the scalar cache)
+    __device__ __forceinline__ uint32_t lsi_mask_byte(const uint8_t *mask, uint32_t b) { return mask ? (uint32_t) * reinterpret_cast<const volatile uint8_t *>(mask + b) : 1u; }
 
     /// Objective::initialize_Ax + initialize_v0 (objective.h:162-196, set_min_init_ctr_violation) for the x in x_s (LDS, n doubles), lane =
     /// constraint: st = [x | v | A x].  A x is apply_A's ordered chain per row (objective.h:435-455).  cs: the activation types (LDS).
@@ -83,6 +88,32 @@ namespace
         uint32_t *stamp_s    = reinterpret_cast<uint32_t *>(v.adx_s); // total words
         const uint8_t *guess = p.guess ? p.guess + (size_t)b * total : nullptr;
 
+        // ---- the instance mask: the wavefront of instance 0 counts the skipped instances of the group — they are stopped from the start — into
+        // `finished`, which it resets anyway (everything that counts on runs in later kernels) ----
+        uint32_t nskip = 0;
+        if (p.mask && b == 0)
+            for (uint32_t i = 0; i < a.B; i += 64) nskip += (uint32_t)__popcll(__ballot(i + lane < a.B && lsi_mask_byte(p.mask, i + lane) == 0));
+        if (lsi_mask_byte(p.mask, b) == 0) // (wave-uniform)
+        {
+            // A skipped instance: none of its data is read.  It is left as lsi_iterate_finish leaves a stopped one (not alive, passed over by the l-QR
+            // and the removal search) with an empty working set, an empty equality problem and zero counters: what the host downloads of it and
+            // what lexls_lsi_batch_get_lambda forms of it is an empty entry
+            for (uint32_t k = lane; k < a.nObjL; k += 64) a.dims[(size_t)b * a.nObjL + k] = 0u;
+            for (uint32_t r = lane; r < a.cap; r += 64) a.row_ld[(size_t)b * a.cap + r] = 0u;
+            if (lane < STEP_MAX_OBJ) v.g_na[lane] = 0;
+            if (lane < RESIDENT_INFO_STRIDE) v.info[lane] = lane == 0 ? (int32_t)TERMINATION_STATUS_UNKNOWN : 0;
+            if (lane < RESIDENT_CYC_STRIDE) a.cyc[(size_t)b * RESIDENT_CYC_STRIDE + lane] = 0u;
+            if (lane == 0)
+            {
+                a.nfixed[b] = 0u;
+                a.alive[b]  = 0;
+                a.skip[b]   = 1;
+                a.objidx[b] = -1;
+                if (b == 0) *a.finished = nskip;
+            }
+            return;
+        }
+
         // ---- the checks, lane = constraint ----
         uint32_t fault = 0xffffffffu;
         for (uint32_t g = lane; g < total; g += 64)
@@ -117,7 +148,7 @@ namespace
             a.alive[b]      = 1;
             a.skip[b]       = 0;
             a.objidx[b]     = 0; // the removal search runs behind the factorization (speculative)
-            if (b == 0) *a.finished = 0u;
+            if (b == 0) *a.finished = nskip; // (0 without a mask)
         }
         __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
         asm volatile("" ::: "memory");
@@ -190,12 +221,14 @@ namespace
         double *fix_val;
         const uint32_t *cyc;
         uint32_t *cyc_count;
+        const uint8_t *mask; // B bytes or NULL: the rows of an instance whose byte is 0 are not stored (lexls_lsi_batch_set_instance_mask)
     };
     __device__ __forceinline__ void lsi_result_scatter_body(const ScatterArgs &s)
     {
         const uint32_t lane = threadIdx.x & 63u;
         const uint32_t b    = blockIdx.x * 4 + (threadIdx.x >> 6);
         if (b >= s.B) return;
+        if (lsi_mask_byte(s.mask, b) == 0) return; // a skipped instance: the caller's rows keep their bits
         const uint32_t n = s.sh.n, total = s.sh.total;
         const double *st = s.state + (size_t)b * s.sh.SD;
         for (uint32_t j = lane; j < n; j += 64) s.x[(size_t)b * n + j] = st[j];
@@ -248,15 +281,16 @@ namespace
     /// the slabs where they live — instance b's final equality problem into the in slab (lsi_form_equality_problem on its final working set), not
     /// skipped, no removal search, and map = [nact (B) | pos (B x total)]: the user row of every active constraint in working-set order, for
     /// lsi_lambda_scatter_kernel.  One wavefront per instance.  A run with an input error posts EMPTY problems, skipped, with the ranks and first
-    /// columns of a factorization of nothing (rank / fcol: the handle's arrays): the sweep of the multipliers, which passes over nobody, finds no rows
-    __global__ __launch_bounds__(256) void lsi_lambda_form_kernel(ResidentArgs a, uint32_t *map, uint32_t *rank, uint32_t *fcol, const uint32_t *fault)
+    /// columns of a factorization of nothing (rank / fcol: the handle's arrays): the sweep of the multipliers, which passes over nobody, finds no rows.
+    /// So does every instance an instance mask skips (mask: the group's bytes or NULL)
+    __global__ __launch_bounds__(256) void lsi_lambda_form_kernel(ResidentArgs a, uint32_t *map, uint32_t *rank, uint32_t *fcol, const uint32_t *fault, const uint8_t *mask)
     {
         const uint32_t lane = threadIdx.x & 63u;
         const uint32_t b    = blockIdx.x * 4 + (threadIdx.x >> 6);
         if (b >= a.B) return;
         const StepShape &sh  = a.sh;
         const uint32_t total = sh.total;
-        if (*fault != 0xffffffffu)
+        if (*fault != 0xffffffffu || lsi_mask_byte(mask, b) == 0)
         {
             for (uint32_t k = lane; k < a.nObjL; k += 64)
             {

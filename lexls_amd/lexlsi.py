@@ -241,6 +241,7 @@ class LsiBatch:
         self._h = C.c_void_p()
         self._log_entries = 0  # capacity per instance of the working-set log (set_working_set_log); 0: off
         self._instance_factors = None  # the device tensor (or address) set_instance_regularization was given: kept alive while the library reads it
+        self._instance_mask = None  # the device tensor set_instance_mask was given: kept alive while the library reads it
         capi.check(capi.lib().lexls_lsi_batch_create(C.byref(self._h), C.c_int(device), C.c_uint32(self.batch), C.c_uint32(self.nvar),
                                                      C.c_uint32(len(self.dims)), _p(self.dims, C.c_uint32), _p(self.types, C.c_int32)))
 
@@ -288,6 +289,23 @@ class LsiBatch:
             ptr, on_device = C.c_void_p(f.ctypes.data), 0
         capi.check(capi.lib().lexls_lsi_batch_set_instance_regularization(self._h, ptr, C.c_int(on_device)))
         self._instance_factors = keep  # (a tensor given earlier is let go of only now that the library has another source)
+
+    def set_instance_mask(self, mask):
+        """lexls_lsi_batch_set_instance_mask: `mask` is a torch uint8 or bool tensor of `batch` elements on the batch's device (contiguous), or None to
+        clear the setting.  An instance whose byte is 0 is skipped by every later run_device() / enqueue_device(): nothing of its inputs is read and
+        its rows of the caller's outputs keep their bits (run_device() makes new, zeroed tensors: pass the previous ones through enqueue_device's
+        `out` to keep answers); the host's view of the run shows it as an empty entry.  The tensor is KEPT — a reference is held so the memory stays
+        alive — and read on the device at the start of every run, so it may be rewritten in place between runs and between replays of a captured
+        enqueue_device().  While a mask is set, run() raises (LEXLS_ERR_UNSUPPORTED)."""
+        if mask is None:
+            ptr = None
+        else:
+            import torch
+            if not hasattr(mask, "data_ptr") or mask.dtype not in (torch.uint8, torch.bool):
+                raise TypeError("set_instance_mask: mask must be a torch uint8 or bool tensor on the batch's device, or None")
+            ptr = self._device_array("mask", mask, mask.dtype, (self.batch,), optional=False)
+        capi.check(capi.lib().lexls_lsi_batch_set_instance_mask(self._h, ptr))
+        self._instance_mask = mask  # (a tensor given earlier is let go of only now that the library has another source)
 
     def run(self, problems, active_guess=None, x0=None, regularization_factors=None, v0=None, **params):
         """`problems`: list of objective lists or a PackedBatch of this batch's structure; other arguments as lsi_batch_solve"""
