@@ -513,6 +513,30 @@ int lexls_lsi_batch_set_instance_regularization(lexls_lsi_batch_t b, const doubl
  * (not alive, the equality solver's skip byte set), so every later kernel passes over it as over a finished one; the result scatter kernels do
  * not store its rows.  Errors of this call: LEXLS_ERR_INVALID for a null handle or between lexls_lsi_batch_enqueue_device and its finish. */
 int lexls_lsi_batch_set_instance_mask(lexls_lsi_batch_t b, const uint8_t *d_mask);
+/* Factorization budgets per instance of the device entries: max_number_of_factorizations, the one run parameter left that was one host value for
+ * the whole batch.  d_limits holds `batch` int32 in the memory of the batch's device.  The pointer is kept — no copy is made on the host and no
+ * run reads the limits on the host — alive until the setting is cleared or the batch destroyed.  The limits are read per run: on the device, in
+ * stream order, at the start of every lexls_lsi_batch_run_device / _run_device_ex / _enqueue_device run and of every replay of a captured one, so
+ * the caller may rewrite them in place between two runs and between two replays.  d_limits == NULL clears the setting: the batch is then what it
+ * was before the call.
+ * An entry L >= 1: the instance runs exactly as one LexLSI object with max_number_of_factorizations = min(L, the run's parameter) — the test is
+ * the reference's nFactorizations >= max (lexlsi.h:238), the status MAX_NUMBER_OF_FACTORIZATIONS_EXCEEDED where it ends the run, and x, v, the
+ * working set, the info6 counters, the cycling counter, the working-set log and the multipliers are that object's, bit for bit.  An instance that
+ * ends on its limit continues in the next run from its own active / x / v (the reference's anytime behaviour).  An entry L <= 0: the instance
+ * has no budget of its own and takes the run's parameter.  The run's parameter stays the upper bound for everyone (it is the loop bound of the
+ * persistent launch; the host knows nothing of the array).
+ * The value that counts for a run is the one present when the run starts in stream order: lsi_phase1_setup_kernel, the first kernel that
+ * touches the instance, copies it into the instance's resident state (a vector load of every lane), and every later kernel of the run — the
+ * resident iterations' stop test, on the persistent launch and on the lock-step stages — reads that copy.  A caller kernel that rewrites the array
+ * behind the enqueue in the same stream cannot change a run in flight.  The entry of an instance that an instance mask skips is not read.
+ * PROBLEM_SOLVED_CYCLING_HANDLING is still tested before the limit.  With the setting off no kernel loads anything new.
+ * Served by exactly the device entries, for every run they serve and with every option of theirs (deactivate_first_wrong_sign, regularized
+ * runs, d_v0, d_lambda, d_cycling_counts, the working-set log, an instance mask; a batch that LEXLS_LSI_GROUPS splits: the group whose first
+ * instance is lo reads the limits from word lo); lexls_lsi_batch_get_lambda, _stats, _last_kernel and _get_cycling_counters answer afterwards as
+ * after any device run.  While the setting is on lexls_lsi_batch_run returns LEXLS_ERR_UNSUPPORTED before any work, its outputs left alone: its
+ * phase 1 is host work and reads no device memory (the mask's rule); runs that would not be resident are refused by the device entries as always.
+ * Errors of this call: LEXLS_ERR_INVALID for a null handle or between lexls_lsi_batch_enqueue_device and its finish. */
+int lexls_lsi_batch_set_instance_max_factorizations(lexls_lsi_batch_t b, const int32_t *d_limits);
 /* How a run executes: phase 1 of every instance on the host; from then on the instance's active-set iterations are resident on the
  * device (LEXLS_LSI_RESIDENT=0: host logic, lock-step stages).  Where the batch's shape has a persistent instantiation (the register-resident l-QR shapes:
  * nVar + 1 <= 41 with levels of up to 12 rows, nVar + 1 <= 64 with levels of up to 16 — except 42..48 columns), everything behind the first resident

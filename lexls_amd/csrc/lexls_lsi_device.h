@@ -255,7 +255,13 @@ namespace
         uint32_t *wlog_count;        // B: entries produced (counted on when there is no room left for the record)
         uint32_t wlog_cap;
         const double *maxabs;        // B: the removal search's largest wrong-sign multiplier (lambda_wrong_sign, lexlsi.h:1115-1139)
+        // per-instance factorization budgets (lexls_lsi_batch_set_instance_max_factorizations): the limit every instance runs under in THIS run,
+        // min(its own entry, max_factorizations), written by lsi_phase1_setup_kernel from the caller's array when the run starts — the array may be
+        // rewritten behind the enqueue without touching a run in flight.  NULL: off, every instance stops at max_factorizations and nothing is loaded
+        int32_t *inst_max_fact;      // B
     };
+    /// the factorization limit of instance b in this run (lexlsi.h:238: the run stops when nFactorizations >= it)
+    __device__ __forceinline__ int32_t resident_max_factorizations(const ResidentArgs &a, const uint32_t b) { return a.inst_max_fact ? a.inst_max_fact[b] : a.max_factorizations; }
     /// int32 words of one record of ResidentArgs::wlog (the row of lexls_lsi_debug::log)
     constexpr uint32_t RESIDENT_WLOG_FIELDS = 5;
 
@@ -422,7 +428,7 @@ namespace
             cyc_stop  = circle && cyc[CYC_COUNT] >= a.cycling_max_counter; // PROBLEM_SOLVED_CYCLING_HANDLING: tested before the factorization limit (lexlsi.h:650-658)
             cyc_relax = circle && !cyc_stop;
         }
-        const bool done = (!blocked && !removed) || cyc_stop || nfact >= a.max_factorizations; // lexlsi.h:236-240
+        const bool done = (!blocked && !removed) || cyc_stop || nfact >= resident_max_factorizations(a, b); // lexlsi.h:236-240
         if (lane == 0)
         {
             // WorkingSetLogEntry (lexlsi.h:1188-1194 ADD, :1214-1222 REMOVE), before the lists change: an ADD is the blocking triple at step length

@@ -283,6 +283,8 @@ namespace
         double *d_fix_val = NULL;
         Pinned<uint32_t> fix_var_host;
         Pinned<double> fix_val_host;
+        int32_t *d_inst_limit = NULL;      // B: every instance's factorization limit of this run (ResidentArgs::inst_max_fact), the setup kernel's copy
+        bool inst_limits = false;          // this run has per-instance limits (lexls_lsi_batch_set_instance_max_factorizations): the resident kernels read d_inst_limit
         bool fused_all = false, fused_refused = false; // the rest of the resident iterations is one persistent launch / the shape has none
         const char *resident_kernel = "";              // the kernel that served the resident iterations of this run (download_resident)
         int rounds_fs = 0, rounds_sens = 0, rounds_step = 0;
@@ -339,7 +341,7 @@ namespace
             r_off  = off;
             rl     = ResidentSlab(B, sh.total);
             if (hipMalloc((void **)&d_rstate, 8 * (size_t)B * sh.SD) != hipSuccess || hipMalloc((void **)&d_rws, rl.bytes) != hipSuccess ||
-                hipMalloc((void **)&d_rvar, 4 * (size_t)B * (sh.dim0 ? sh.dim0 : 1)) != hipSuccess)
+                hipMalloc((void **)&d_rvar, 4 * (size_t)B * (sh.dim0 ? sh.dim0 : 1)) != hipSuccess || hipMalloc((void **)&d_inst_limit, 4 * (size_t)B) != hipSuccess)
                 throw Exception("hipMalloc failed (resident LSI iterations)");
             rws_host.assign(rl.bytes, 0);
             rstate_host.assign((size_t)B * sh.SD, 0.0);
@@ -429,6 +431,7 @@ namespace
             ra.cycling = cycling ? 1u : 0u, ra.cycling_max_counter = cycling_max_counter, ra.cycling_relax_step = cycling_relax_step, ra.cyc = rl.cyc(d_rws);
             ra.wlog = d_wlog, ra.wlog_alpha = d_wlog_alpha, ra.wlog_count = d_wlog_count, ra.wlog_cap = wlog_cap; // (NULL: off)
             ra.maxabs = reinterpret_cast<const double *>(out + lay.max_abs);
+            ra.inst_max_fact = inst_limits ? d_inst_limit : NULL;
             return ra;
         }
 
@@ -589,8 +592,10 @@ namespace
         /// and the variable indices are in the handle / d_rvar already (same stream).  The fault word comes back with the next synchronisation
         /// run_fault (lexls_lsi_batch_enqueue_device): the word of the whole run, shared by the groups and cleared by the caller — it stays on the device
         /// d_mask (lexls_lsi_batch_set_instance_mask): this group's bytes of the caller's instance mask or NULL, read by the kernel where they lie
+        /// d_limits (lexls_lsi_batch_set_instance_max_factorizations): this group's words of the caller's limits or NULL; the kernel copies what counts
+        /// for this run into d_inst_limit, which every later kernel of the run reads (resident_args)
         void enqueue_phase1_setup(const double *d_x0, const uint8_t *d_guess, uint32_t first, int32_t max_factorizations, const double *d_v0 = NULL, uint32_t *run_fault = NULL,
-                                  const uint8_t *d_mask = NULL)
+                                  const uint8_t *d_mask = NULL, const int32_t *d_limits = NULL)
         {
             const double t0 = now();
             if (!d_p1_fault && !run_fault)
@@ -600,9 +605,10 @@ namespace
             }
             hip_check(lexls_internal_ensure_gather_buffer(h));
             phase1_on_device = true;
+            inst_limits      = d_limits != NULL;
             Phase1Args pa;
             pa.ra = resident_args(max_factorizations);
-            pa.x0 = d_x0, pa.guess = d_guess, pa.v0 = d_v0, pa.fault = run_fault ? run_fault : d_p1_fault, pa.first = first, pa.mask = d_mask;
+            pa.x0 = d_x0, pa.guess = d_guess, pa.v0 = d_v0, pa.fault = run_fault ? run_fault : d_p1_fault, pa.first = first, pa.mask = d_mask, pa.limits = d_limits;
             if (!run_fault && hipMemsetAsync(d_p1_fault, 0xff, 16, stream) != hipSuccess) throw Exception("hipMemsetAsync failed (phase 1 on the device)");
             hipLaunchKernelGGL(lsi_phase1_setup_kernel, dim3((B + 3) / 4), dim3(256), 4 * resident_lds_per_wave(rshape.SD, rshape.total), stream, pa);
             if (hipGetLastError() != hipSuccess || (!run_fault && hipMemcpyAsync(p1_fault_host.data(), d_p1_fault, 4, hipMemcpyDeviceToHost, stream) != hipSuccess))
@@ -762,6 +768,7 @@ namespace
             }
             stage_fs = stage_sens = false;
             phase1_on_device = false;
+            inst_limits      = false;
             if (resident)
             {
                 std::fill(rws_host.begin(), rws_host.begin() + rl.bytes_core, 0); // (the stamps behind: hand_over writes every one a run reads)
@@ -773,7 +780,7 @@ namespace
         ~BatchCtx()
         {
             if (h) lexls_lse_destroy(h);
-            void *dev[] = {d_state, d_state_in, d_res, d_var, d_wset, d_rstate, d_rvar, d_rws, d_p1_fault, d_p1_guess, d_p1_x0, d_fix_var, d_fix_val};
+            void *dev[] = {d_state, d_state_in, d_res, d_var, d_wset, d_rstate, d_rvar, d_rws, d_p1_fault, d_p1_guess, d_p1_x0, d_fix_var, d_fix_val, d_inst_limit};
             for (void *q : dev)
                 if (q) (void)hipFree(q);
             if (stream) (void)hipStreamDestroy(stream);

@@ -19,11 +19,21 @@ namespace
         uint32_t *fault;      // one word for the run: min over the faulty instances of (index in the batch) * 8 + P1_* code
         uint32_t first;       // index in the batch of this group's instance 0
         const uint8_t *mask;  // B bytes, or NULL (lexls_lsi_batch_set_instance_mask): 0 = the instance is skipped in this run
+        const int32_t *limits; // B words, or NULL (lexls_lsi_batch_set_instance_max_factorizations): the instance's own factorization limit, <= 0 = none
     };
 
     /// byte b of an instance mask (NULL: every instance is solved).  The bytes are the caller's, rewritten in place between two runs and between two
     /// replays of a captured run: read where they lie by a vector load of every lane (volatile: never a load through the scalar cache)
     __device__ __forceinline__ uint32_t lsi_mask_byte(const uint8_t *mask, uint32_t b) { return mask ? (uint32_t) * reinterpret_cast<const volatile uint8_t *>(mask + b) : 1u; }
+
+    /// the limit instance b runs under: its entry of the caller's array when that is 1 .. max_factorizations - 1, the run's parameter otherwise (an
+    /// entry <= 0 is "no budget of its own"; the run's parameter bounds everyone: it is the persistent launch's loop count).  The words are the
+    /// caller's, rewritten in place between runs and replays like the mask's bytes: a volatile vector load, never through the scalar cache
+    __device__ __forceinline__ int32_t lsi_instance_limit(const int32_t *limits, uint32_t b, int32_t max_factorizations)
+    {
+        const int32_t L = *reinterpret_cast<const volatile int32_t *>(limits + b);
+        return (L >= 1 && L < max_factorizations) ? L : max_factorizations;
+    }
 
     /// Objective::initialize_Ax + initialize_v0 (objective.h:162-196, set_min_init_ctr_violation) for the x in x_s (LDS, n doubles), lane =
     /// constraint: st = [x | v | A x].  A x is apply_A's ordered chain per row (objective.h:435-455).  cs: the activation types (LDS).
@@ -149,6 +159,9 @@ namespace
             a.skip[b]       = 0;
             a.objidx[b]     = 0; // the removal search runs behind the factorization (speculative)
             if (b == 0) *a.finished = nskip; // (0 without a mask)
+            // the budget of this run is the one that stands in the caller's array now: every later kernel reads this copy (a skipped or a faulty
+            // instance has returned above: its entry is not read)
+            if (p.limits) a.inst_max_fact[b] = lsi_instance_limit(p.limits, b, a.max_factorizations);
         }
         __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
         asm volatile("" ::: "memory");

@@ -242,6 +242,7 @@ class LsiBatch:
         self._log_entries = 0  # capacity per instance of the working-set log (set_working_set_log); 0: off
         self._instance_factors = None  # the device tensor (or address) set_instance_regularization was given: kept alive while the library reads it
         self._instance_mask = None  # the device tensor set_instance_mask was given: kept alive while the library reads it
+        self._instance_limits = None  # the device tensor set_instance_max_factorizations was given: kept alive while the library reads it
         capi.check(capi.lib().lexls_lsi_batch_create(C.byref(self._h), C.c_int(device), C.c_uint32(self.batch), C.c_uint32(self.nvar),
                                                      C.c_uint32(len(self.dims)), _p(self.dims, C.c_uint32), _p(self.types, C.c_int32)))
 
@@ -306,6 +307,23 @@ class LsiBatch:
             ptr = self._device_array("mask", mask, mask.dtype, (self.batch,), optional=False)
         capi.check(capi.lib().lexls_lsi_batch_set_instance_mask(self._h, ptr))
         self._instance_mask = mask  # (a tensor given earlier is let go of only now that the library has another source)
+
+    def set_instance_max_factorizations(self, limits):
+        """lexls_lsi_batch_set_instance_max_factorizations: `limits` is a torch int32 tensor of shape (batch,) on the batch's device (contiguous), or
+        None to clear the setting.  In every later run_device() / enqueue_device() an instance whose entry L is >= 1 runs as one LexLSI object with
+        max_number_of_factorizations = min(L, the run's parameter); an entry <= 0 leaves it the run's parameter.  The tensor is KEPT — a reference is
+        held so the memory stays alive — and read on the device at the start of every run, so it may be rewritten in place between runs and between
+        replays of a captured enqueue_device(); a run in flight keeps the values it started with.  While limits are set, run() raises
+        (LEXLS_ERR_UNSUPPORTED)."""
+        if limits is None:
+            ptr = None
+        else:
+            import torch
+            if not hasattr(limits, "data_ptr") or limits.dtype != torch.int32:
+                raise TypeError("set_instance_max_factorizations: limits must be a torch int32 tensor on the batch's device, or None")
+            ptr = self._device_array("limits", limits, torch.int32, (self.batch,), optional=False)
+        capi.check(capi.lib().lexls_lsi_batch_set_instance_max_factorizations(self._h, ptr))
+        self._instance_limits = limits  # (a tensor given earlier is let go of only now that the library has another source)
 
     def run(self, problems, active_guess=None, x0=None, regularization_factors=None, v0=None, **params):
         """`problems`: list of objective lists or a PackedBatch of this batch's structure; other arguments as lsi_batch_solve"""
