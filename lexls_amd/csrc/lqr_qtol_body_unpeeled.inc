@@ -1,9 +1,8 @@
 // Body of lqr_qtol_kernel / lqr_qtol_est_kernel / lqr_qtol_rag_kernel (lqr_qtol_impl.h), included inside each: template parameters NS, MD, SIG, NV;
 // arguments a, img_doubles, group_bytes, stagger; EST (constexpr bool), est_out, count_reset; RAG (constexpr bool): levels of up to MD rows.
-// The phases of a level (head, staging, elimination, factor_level, level end) are local lambdas that take the level's block and the compile-time
-// fact "this is level 0".  Level 0 is peeled: a straight-line section in front of the level loop on its own block blk0 (the direct load, identity
-// layout, no staging, no elimination, factor_level<0>).  The loop runs the levels 1 .. nObj-1 on a block that is local to the iteration and first
-// touched by the staging read: no value of a block is live into or out of an iteration, so none is carried round the back edge.
+// THE BODY AS IT WAS BEFORE LEVEL 0 WAS PEELED (lqr_qtol_body.inc): one loop over all levels, the block carried round it.  Kept for ONE instantiation,
+// lqr_qtol_est_kernel<3,12,0,0>, which uses the whole register file: on the phase lambdas of lqr_qtol_body.inc, peeled or not, it spills two vector
+// registers, which scripts/check_qtol_regs.py refuses.  To be removed with the first change that lets that instantiation build from lqr_qtol_body.inc.
             static_assert(NS >= 1 && NS <= 4 && MD <= 16 && (MD % 4) == 0, "shape limits of the row layout / two row parts of even size");
             constexpr int NH  = 2;        // row parts of the staging transposition
             constexpr int RP  = MD / NH;  // rows per part
@@ -63,7 +62,7 @@
             //      this burst at its full rate, and nothing can be computed before it lands).  Its position layout is the identity, so lane = column
             //      loads the block directly, no staging; for such a burst this pattern is also the fastest of those measured
             //      (scripts/ubench/loadpat.hip: 7.7-8.4 k cycles per level against 9.5 k for the 48-byte pieces) ----
-            double blk0[NS][MD]; // level 0's block, position layout (the later levels' blocks are local to the level loop's body)
+            double blk[NS][MD]; // the level block, position layout
 #pragma unroll
             for (int s = 0; s < NS; s++)
             {
@@ -78,7 +77,7 @@
                     {
                         const int Rc  = 2 * r < cap - 2 ? 2 * r : cap - 2;
                         const qt_d2 v = *reinterpret_cast<const qt_d2u *>(colp + Rc); // (8-byte aligned when cap is odd)
-                        rag_rows(v, 2 * r, 2 * r, d0, blk0[s][2 * r], blk0[s][2 * r + 1]);
+                        rag_rows(v, 2 * r, 2 * r, d0, blk[s][2 * r], blk[s][2 * r + 1]);
                     }
                 }
                 else
@@ -87,9 +86,9 @@
 #pragma unroll
                     for (int r = 0; r < MD / 2; r++)
                     {
-                        const qt_d2 v      = src2[r];
-                        blk0[s][2 * r]     = v.x;
-                        blk0[s][2 * r + 1] = v.y;
+                        const qt_d2 v     = src2[r];
+                        blk[s][2 * r]     = v.x;
+                        blk[s][2 * r + 1] = v.y;
                     }
                 }
             }
@@ -193,58 +192,32 @@
             unsigned long long lst_t0 = clock64();
 #endif
 
-            // ---- the phases of one level, as lambdas: each takes the level's block and (l0c) the compile-time fact "this is level 0", the peeled
-            //      section in front of the level loop (L0: no look-ups, no staging, no elimination, k == 0; QT_LMARK names its parts "level0-...") ----
-            // PEEL is off for the estimating instantiation with three slots of twelve rows (<3,12,7,40> with EST): peeled it spills four vector
-            // registers (scripts/check_qtol_regs.py refuses that).  It keeps the single loop over all levels, the block carried round it, on the
-            // same lambdas (never L0: the k > 0 tests are then run-time tests).  (<3,12,0,0> with EST spills two in either shape and is compiled
-            // from lqr_qtol_body_unpeeled.inc: lqr_qtol_impl.h)
-            constexpr bool PEEL = !(EST && NS == 3 && MD == 12);
-            struct qt_level // what the phases of one level hand to each other (per row, uniform inside a row; prefetch: wave-uniform)
+            for (int k = 0; k < nObj; k++)
             {
-                bool work;     // x only: once the columns are exhausted nothing below matters
-                int F;         // first row of the level
-                int dlev;      // its rows (RAG: per problem)
-                int Fc;        // its first column
-                int rank;
-                bool prefetch; // the next level's rows are requested inside this level's pivot steps
-            };
-
-            // level head: false when no row of the wavefront has work left (the level's meta entry is written, nothing else of the level runs)
-            auto level_head = [&](auto l0c, const int k, qt_level &L) __attribute__((always_inline)) {
-                constexpr bool L0 = decltype(l0c)::value;
-                QT_LMARK("level-top")
-                L.work = live && !exh;
-                L.F    = RAG ? Frow : k * MD;
-                L.dlev = RAG ? (int)((dpack >> (4 * k)) & 15u) : MD;
-                if constexpr (RAG) Frow += L.dlev;
-                L.Fc   = ColIndex;
-                L.rank = 0;
-                if (__ballot(L.work) == 0ull)
+                QT_MARK("level-top")
+                const bool work = live && !exh; // x only: once the columns are exhausted nothing below matters
+                const int F     = RAG ? Frow : k * MD;                       // first row of the level
+                const int dlev  = RAG ? (int)((dpack >> (4 * k)) & 15u) : MD; // its rows (RAG: per problem)
+                if constexpr (RAG) Frow += dlev;
+                const int Fc    = ColIndex;
+                int rank        = 0;
+                if (__ballot(work) == 0ull)
                 {
                     if (gl == 0)
                     {
-                        U32(o_meta + 16 * k)      = (uint32_t)L.Fc;
+                        U32(o_meta + 16 * k)      = (uint32_t)Fc;
                         U32(o_meta + 16 * k + 4)  = 0u;
                         U32(o_meta + 16 * k + 8)  = (uint32_t)imgoff;
-                        U32(o_meta + 16 * k + 12) = (uint32_t)(n + 1 - L.Fc);
+                        U32(o_meta + 16 * k + 12) = (uint32_t)(n + 1 - Fc);
                     }
-                    return false;
+                    continue;
                 }
-                if constexpr (!L0)
-                {
-                    if ((PEEL || k > 0) && !have_next) // a level whose predecessor could have exhausted the columns: all pieces at once
-                        for_each_index<0, NH * NIH>([&](auto tt) __attribute__((always_inline)) { prefetch_piece(tt, L.F); });
-                }
-                return true;
-            };
+                if (k > 0 && !have_next) // a level whose predecessor could have exhausted the columns: all pieces at once
+                    for_each_index<0, NH * NIH>([&](auto tt) __attribute__((always_inline)) { prefetch_piece(tt, F); });
 
-            // =====================================================================================
-            // position layout of the level; staged pieces -> block (levels behind level 0: every entry of blk is written here before anything reads it)
-            // =====================================================================================
-            auto level_start = [&](const int k, const qt_level &L, double (&blk)[NS][MD]) __attribute__((always_inline)) {
-                const int F = L.F, dlev = L.dlev;
-                (void)F, (void)dlev;
+                // =====================================================================================
+                // position layout of the level; staged pieces -> block
+                // =====================================================================================
                 QT_MARK("level-start")
 #pragma unroll
                 for (int s = 0; s < NS; s++)
@@ -256,7 +229,7 @@
                 }
 #pragma unroll
                 for (int s = 0; s < NS; s++) em[s] = U64(o_emap + 8 * pc[s]);
-                if (PEEL || k > 0) // (the unpeeled shape: level 0's block came by the direct load)
+                if (k > 0)
                 for_each_index<0, NH>([&](auto hh) __attribute__((always_inline)) {
                     constexpr int h = decltype(hh)::value;
                     QT_MARK1("level-stage", h)
@@ -290,17 +263,9 @@
                     }
                     quad_lds_fence();
                 });
-            };
-
-            // behind the block's arrival: (EST) the raw column norms; whether the next level's rows are requested inside this level's pivot steps
-            auto level_post = [&](auto l0c, const int k, qt_level &L, double (&blk)[NS][MD]) __attribute__((always_inline)) {
-                constexpr bool L0 = decltype(l0c)::value;
-                const bool work = L.work;
-                const int Fc    = L.Fc;
-                (void)k;
                 STAMP(1)
                 LSTAMP(0)
-                QT_LMARK("level-post")
+                QT_MARK("level-post")
                 if constexpr (EST)
                 {
 #pragma unroll
@@ -314,16 +279,13 @@
                 }
                 // the next level's rows: requested while this level is factorised (two pieces per pivot step, below), unless this level can
                 // exhaust the columns
-                L.prefetch = (k + 1 < nObj) && (rows_min(work ? Fc : 0x3fffffff) + MD < n);
-                have_next  = L.prefetch;
-            };
+                const bool prefetch = (k + 1 < nObj) && (rows_min(work ? Fc : 0x3fffffff) + MD < n);
+                have_next           = prefetch;
 
-            // =====================================================================================
-            // Gauss elimination of these rows by every finished pivot c' (lexlse.h:431-471, left-looking, normalised pivot rows).  Level 0 has none
-            // =====================================================================================
-            auto eliminate = [&](const int k, const qt_level &L, double (&blk)[NS][MD]) __attribute__((always_inline)) {
-                (void)k;
-                const int Fcmax = rows_max(L.work ? L.Fc : 0);
+                // =====================================================================================
+                // Gauss elimination of these rows by every finished pivot c' (lexlse.h:431-471, left-looking, normalised pivot rows)
+                // =====================================================================================
+                const int Fcmax = rows_max(work ? Fc : 0);
                 {
                     // U'[c'][P] of this lane's columns is fetched one pivot ahead of its use (the read depends on a row-broadcast address)
                     auto fetch_u = [&](auto cc, double (&u)[NS]) __attribute__((always_inline)) {
@@ -391,7 +353,7 @@
                 }
                 STAMP(7)
                 LSTAMP(1)
-            };
+                QT_MARK("hh-select")
 
                 // =====================================================================================
                 // Householder QR with column pivoting of the level (lexlse.h:182-268), slots S0 .. NS-1.
@@ -403,15 +365,10 @@
                 // below (beside the butterflies), then every lane stores the column of its local best slot in its own LDS slot — the store
                 // does not wait for the decision, only the next step's read address does.
                 // =====================================================================================
-                auto factor_level = [&](auto l0c, auto s0c, qt_level &L, double (&blk)[NS][MD]) __attribute__((always_inline)) {
-                    constexpr bool L0 = decltype(l0c)::value;
+                auto factor_level = [&](auto s0c) __attribute__((always_inline)) {
                     constexpr int S0 = decltype(s0c)::value;
                     constexpr int SL = NS - S0; // live slots
-                    static_assert(!L0 || S0 == 0, "level 0 starts at column 0: every slot is live");
-                    const bool work = L.work, prefetch = L.prefetch;
-                    const int F = L.F, dlev = L.dlev;
-                    int &rank = L.rank;
-                    QT_LMARK1("hh-pro", S0)
+                    QT_MARK1("hh-pro", S0)
                     double nrm[NS];
 #pragma unroll
                     for (int s = S0; s < NS; s++)
@@ -492,7 +449,7 @@
                         constexpr int j   = decltype(cnt)::value;
                         constexpr int ce  = j & ~1;       // first (even) row of this step's hand-off
                         constexpr int cen = (j + 1) & ~1; // ... of the next step's
-                        QT_LMARK2("hh-step", S0, j)
+                        QT_MARK2("hh-step", S0, j)
                         // the next level's pieces: PF_PER per pivot step from the first step on (what an early end leaves over is requested behind the loop)
                         {
                             constexpr int TOT = NH * NIH, PF_PER = (TOT + PF_STEPS - 1) / PF_STEPS;
@@ -676,24 +633,31 @@
                         CSTAMP(6, __double2loint(blk[NS - 1][MD - 1]))
                         FSTAMP(5)
                     });
-                    QT_LMARK1("hh-end", S0)
+                    QT_MARK1("hh-end", S0)
                     if (prefetch)
                         for_each_index<0, NH * NIH>([&](auto tt) __attribute__((always_inline)) {
                             if (decltype(tt)::value >= pf_issued) prefetch_piece(tt, F + dlev);
                         });
                     (void)SL;
                 };
-
-            // =====================================================================================
-            // level end: triangular image [R_k T_k | rhs_k] / diag in end-of-level position order, maps
-            // =====================================================================================
-            auto level_end = [&](auto l0c, const int k, const qt_level &L, double (&blk)[NS][MD]) __attribute__((always_inline)) {
-                constexpr bool L0 = decltype(l0c)::value;
-                const bool work = L.work;
-                const int Fc = L.Fc, rank = L.rank;
+                {
+                    const int s0 = (rows_min(work ? Fc : 0x3fffffff) + SIG) >> 4;
+                    if (NS > 3 && s0 >= 3)
+                        factor_level(std::integral_constant<int, (NS > 3 ? 3 : 0)>{});
+                    else if (NS > 2 && s0 >= 2)
+                        factor_level(std::integral_constant<int, (NS > 2 ? 2 : 0)>{});
+                    else if (NS > 1 && s0 >= 1)
+                        factor_level(std::integral_constant<int, (NS > 1 ? 1 : 0)>{});
+                    else
+                        factor_level(std::integral_constant<int, 0>{});
+                }
                 STAMP(5)
                 LSTAMP(2)
-                QT_LMARK("level-end")
+
+                // =====================================================================================
+                // level end: triangular image [R_k T_k | rhs_k] / diag in end-of-level position order, maps
+                // =====================================================================================
+                QT_MARK("level-end")
                 const int wk   = n + 1 - Fc;
                 const int dump = o_stage + 8 * gl; // stores that do not apply go to a dump slot of the lane's own (the staging block is idle here): no divergent regions, no bank conflicts
                 int roff[MD];          // byte offset of image row p (triangular packing), the same for every slot
@@ -709,13 +673,13 @@
                     const int base = o_img + 8 * (imgoff + e);
                     if (mv)
                     {
-                        QT_LMARK1("level-end-store", s)
+                        QT_MARK1("level-end-store", s)
 #pragma unroll
                         for (int p = 0; p < MD; p++) D(sel(p <= lim, base + roff[p], dump)) = blk[s][p];
                         B8(o_emap + 8 * pc[s] + k) = (uint8_t)e;
                         if (P0 < n) B8(o_phys + pos[s]) = (uint8_t)pc[s];
                     }
-                    QT_LMARK1("level-end-maps", s)
+                    QT_MARK1("level-end-maps", s)
                     // pivot position P0 of this level: its image row and the selector of this level's index byte
                     const bool piv = work && P0 >= Fc && P0 < Fc + rank;
                     const int p    = P0 - Fc;
@@ -734,68 +698,6 @@
                 quad_lds_fence();
                 imgoff += wk * rank - rank * (rank - 1) / 2;
                 TotalRank += rank;
-            };
-
-            // ---- level 0, peeled: its block is blk0 (requested at the top of the kernel); the layout is the identity, which is also what o_phys
-            //      and o_emap hold (set above; the levels behind and the solve read them), so pos / pc / em come without look-ups; nothing is
-            //      staged and nothing eliminated (no finished pivot: ColIndex == 0), every slot is live: factor_level<0>.  The next level's pieces
-            //      are requested inside its pivot steps as inside any level's ----
-            if constexpr (PEEL)
-            {
-                qt_level L;
-                if (level_head(std::true_type{}, 0, L)) // (nObj >= 1: lexls_lse_create)
-                {
-#pragma unroll
-                    for (int s = 0; s < NS; s++)
-                    {
-                        const int P = 16 * s + gl - SIG;
-                        pc[s]       = (P >= 0 && P <= n) ? P : 0;
-                        pos[s]      = (P >= 0 && P <= n) ? P : 0x3fffff;
-                        em[s]       = 0ull;
-                    }
-                    level_post(std::true_type{}, 0, L, blk0);
-                    { // (no elimination: its stamps read zero)
-                        constexpr int k = 0;
-                        (void)k;
-                        STAMP(7)
-                        LSTAMP(1)
-                    }
-                    factor_level(std::true_type{}, std::integral_constant<int, 0>{}, L, blk0);
-                    level_end(std::true_type{}, 0, L, blk0);
-                }
-            }
-            // LDS order across the boundary, as between any two levels: the fence that ends level_end (behind the meta store) stands between
-            // level 0's image / o_emap / o_phys / o_perm / meta stores and what the loop's first level reads — the o_phys / o_emap look-ups of
-            // level_start, the image rows of the elimination — and between level 0's last hand-off reads of the staging block and the first staged
-            // pieces written over it.  The fence behind the LDS set-up covers the o_phys / o_emap / o_xs initialisation for every later reader.
-            // The s_nop that ends the elimination (DPP reads behind qt_gauss_dpp_self's writes) belongs to the loop's levels alone: level 0's
-            // block is written by compiler-visible instructions only, whose hazards the compiler counts itself.
-
-            // ---- the levels behind it.  The block is local to the iteration: level_start writes all of it (both row parts) before anything
-            //      reads it, level_end reads it last — nothing of it crosses the back edge ----
-            for (int k = PEEL ? 1 : 0; k < nObj; k++)
-            {
-                qt_level L;
-                if (!level_head(std::false_type{}, k, L)) continue;
-                double blk_k[NS][MD];                                // the level block, position layout
-                double(&blk)[NS][MD] = *(PEEL ? &blk_k : &blk0);     // (the unpeeled shape: one block for all levels, carried round the loop)
-                level_start(k, L, blk);
-                level_post(std::false_type{}, k, L, blk);
-                eliminate(k, L, blk);
-                QT_MARK("hh-select")
-                {
-                    // (a rank-deficient level 0 leaves level 1 at column < 16 - SIG: all four choices stay)
-                    const int s0 = (rows_min(L.work ? L.Fc : 0x3fffffff) + SIG) >> 4;
-                    if (NS > 3 && s0 >= 3)
-                        factor_level(std::false_type{}, std::integral_constant<int, (NS > 3 ? 3 : 0)>{}, L, blk);
-                    else if (NS > 2 && s0 >= 2)
-                        factor_level(std::false_type{}, std::integral_constant<int, (NS > 2 ? 2 : 0)>{}, L, blk);
-                    else if (NS > 1 && s0 >= 1)
-                        factor_level(std::false_type{}, std::integral_constant<int, (NS > 1 ? 1 : 0)>{}, L, blk);
-                    else
-                        factor_level(std::false_type{}, std::integral_constant<int, 0>{}, L, blk);
-                }
-                level_end(std::false_type{}, k, L, blk);
             }
 
             // ---- solve(): block back-substitution on the normalised images (lexlse.h:1015-1045); lane p <-> row p of a level.  Straight-line

@@ -121,6 +121,10 @@ namespace lexls
 #define QT_MARK1(name, i)
 #define QT_MARK2(name, i, j)
 #endif
+// ... of a phase that exists twice, in the peeled level 0 (constexpr bool L0 in scope: "level0-<name>") and in the level loop ("<name>")
+#define QT_LMARK(name)        if constexpr (L0) { QT_MARK("level0-" name) } else { QT_MARK(name) }
+#define QT_LMARK1(name, i)    if constexpr (L0) { QT_MARK1("level0-" name, i) } else { QT_MARK1(name, i) }
+#define QT_LMARK2(name, i, j) if constexpr (L0) { QT_MARK2("level0-" name, i, j) } else { QT_MARK2(name, i, j) }
         /// f(integral_constant<int, I>) for I = B, B+1, ... while pred(I) holds: the first failing test leaves the whole remainder behind one branch
         template <int B, int E, class P, class F>
         __device__ __forceinline__ void qt_for_each_while(P &&pred, F &&f)
@@ -262,7 +266,14 @@ namespace lexls
         {
             constexpr bool EST = true;
             constexpr bool RAG = false;
+            if constexpr (NS == 3 && MD == 12 && NV == 0)
+            {
+#include "lqr_qtol_body_unpeeled.inc" // (the single-loop shape: this instantiation spills vector registers on the peeled body's lambdas)
+            }
+            else
+            {
 #include "lqr_qtol_body.inc"
+            }
         }
 
         template <int NS, int MD, int SIG, int NV, bool EST = false, bool RAG = false>

@@ -52,32 +52,42 @@ ACC = [N - (FC[k] + RANKS[k]) if RANKS[k] else 0 for k in range(len(RANKS))]  # 
 
 
 def trips(name, idx):
-    """how often the shape runs a part"""
+    """how often the shape runs a part.  Level 0 is a peeled section in front of the level loop: its parts are marked "level0-<name>" and run
+    once; the same name without the prefix is the part of the loop's body, which serves the levels behind level 0"""
     if name in ("prologue", "solve-top", "output"):
         return 1
-    if name in ("level-top", "solve-level"):
-        return len(RANKS)  # (a level that does not start leaves at once)
-    if name in ("level-start", "level-post", "hh-select", "level-end", "level-end-maps"):
-        return len(WORKED)
-    if name == "level-end-store":  # slot s holds a live column (position 16 s + l - SIG >= Fc) in some lane: otherwise the pass is branched over
-        return sum(1 for k in WORKED if 16 * idx[0] + 15 - SIG >= FC[k])
-    if name == "level-stage":
-        return len(WORKED) - 1  # level 0 is loaded in the position layout directly
-    if name == "elim":
-        return sum(1 for k in WORKED if idx[0] < FC[k])
-    if name in ("hh-pro", "hh-end"):
-        return S0.count(idx[0])
-    if name == "hh-step":  # a level leaves at the first test (every fourth step) behind its last pivot
-        s0, j = idx
-        return sum(1 for k, s in zip(WORKED, S0) if s == s0 and j < min(MD, -(-min(RANKS[k] + (FC[k] + RANKS[k] < N), MD) // 4) * 4))
+    if name in ("solve-level",):
+        return len(RANKS)
     if name == "solve-tail":
         return sum(1 for r in RANKS if r)
     if name == "solve-trip":
         return sum(-(-a // 16) for a in ACC)
+    l0 = name.startswith(L0_PREFIX)
+    if l0:
+        name = name[len(L0_PREFIX):]
+    levels = [k for k in WORKED if (k == 0) == l0]  # the levels that run this copy of the part
+    if name == "level-top":
+        return 1 if l0 else len(RANKS) - 1  # (a level that does not start leaves at once)
+    if name in ("level-start", "level-stage", "level-post", "hh-select", "level-end", "level-end-maps"):
+        return len(levels)  # (level-start, level-stage, hh-select: the loop only — level 0 is loaded in the position layout directly and has one instantiation)
+    if name == "level-end-store":  # slot s holds a live column (position 16 s + l - SIG >= Fc) in some lane: otherwise the pass is branched over
+        return sum(1 for k in levels if 16 * idx[0] + 15 - SIG >= FC[k])
+    if name == "elim":
+        return sum(1 for k in levels if idx[0] < FC[k])
+    if name in ("hh-pro", "hh-end"):
+        return sum(1 for k in levels if S0[WORKED.index(k)] == idx[0])
+    if name == "hh-step":  # a level leaves at the first test (every fourth step) behind its last pivot
+        s0, j = idx
+        return sum(1 for k in levels if S0[WORKED.index(k)] == s0 and j < min(MD, -(-min(RANKS[k] + (FC[k] + RANKS[k] < N), MD) // 4) * 4))
     raise SystemExit(f"unknown region {name}")
 
 
+L0_PREFIX = "level0-"
+
+
 def group(name, idx):
+    if name.startswith(L0_PREFIX):
+        return "level 0 (peeled): " + group(name[len(L0_PREFIX):], idx)
     if name == "elim":
         sc = (idx[0] + SIG) // 16
         return f"elimination, {NS - sc} slot step"
@@ -149,7 +159,7 @@ def main():
         r = rows.setdefault(g, collections.Counter())
         for k, v in c.items():
             r[k] += n * v
-        if name in ("elim", "hh-step"):
+        if name in ("elim", "hh-step", L0_PREFIX + "hh-step"):
             steps[g] += n
     total = collections.Counter()
     for r in rows.values():
