@@ -537,6 +537,40 @@ int lexls_lsi_batch_set_instance_mask(lexls_lsi_batch_t b, const uint8_t *d_mask
  * phase 1 is host work and reads no device memory (the mask's rule); runs that would not be resident are refused by the device entries as always.
  * Errors of this call: LEXLS_ERR_INVALID for a null handle or between lexls_lsi_batch_enqueue_device and its finish. */
 int lexls_lsi_batch_set_instance_max_factorizations(lexls_lsi_batch_t b, const int32_t *d_limits);
+/* Objective row counts per instance of the device entries: the structure, the last quantity that was one value for the whole batch.  d_dims holds
+ * batch x nObj uint32 in the memory of the batch's device, instance-major.  The pointer is kept — no copy is made on the host and no run reads the
+ * counts on the host — alive until the setting is cleared or the batch destroyed.  The counts are read per run: on the device, in stream order, at
+ * the start of every lexls_lsi_batch_run_device / _run_device_ex / _enqueue_device run and of every replay of a captured one, so the caller may
+ * rewrite them in place between two runs and between two replays.  d_dims == NULL clears the setting: the batch is then what it was before the
+ * call.
+ * The dims of lexls_lsi_batch_create become capacities: instance i is the LexLSI problem whose objective k consists of the FIRST
+ * d_dims[i * nObj + k] rows of its objective-k block.  Every layout stays the capacity layout: in d_data the leading dimension of a block is
+ * still dims[k]; d_var_index holds the instance's indices in the first d_dims[i * nObj] entries of its row of dims[0] (a simple-bounds objective
+ * 0); in d_active_guess, d_v0, d_active, d_v and d_lambda objective k starts at the capacity offset dims[0] + .. + dims[k-1]; d_x, d_info6 and
+ * d_cycling_counts are per instance as always.
+ * Rows at and beyond an instance's count are absent.  None of their data, bounds, guess, v0 or variable indices is interpreted: a NaN, lb > ub
+ * or a bad index there raises no fault word and reaches no stored result.
+ * Result: for every solved instance x, info6, the cycling counter and the working-set log are what ONE LexLSI object built with the instance's
+ * own dims on the present rows only produces, and so are the present rows of active, v and lambda — bit for bit, on the persistent launch and
+ * on the lock-step stages.  The absent rows of d_active, d_v and d_lambda are written as 0; the absent rows of lexls_lsi_batch_get_lambda are 0
+ * as well; the working-set log never names an absent row.
+ * A count of 0 is an empty objective and is served: the reference solves a problem with an objective of no rows (its level of the equality
+ * problems is empty in every iteration), and the instance gets that object's bits.
+ * An entry above its capacity is an input fault, code 5 ("objective row count above the batch's capacity"), reported like the codes 1 - 4:
+ * LEXLS_ERR_INVALID from the synchronous entries with lexls_last_error() naming the instance, d_status = instance * 8 + 5 from the enqueued one;
+ * nothing is solved and every output is left as it was.  It is the only check made of such an instance (its rows are not known).
+ * The counts that hold for a run are those present when the run starts in stream order: lsi_phase1_setup_kernel reads them right after the mask
+ * byte (a vector load), checks them and copies them into the instance's resident state, and every later kernel of the run — the resident
+ * iterations' ratio test, state update and working-set lists — reads that copy.  A caller kernel that rewrites the array behind the enqueue in the
+ * same stream cannot change a run in flight.  The counts of an instance that an instance mask skips are not read.  The batch is dispatched by its
+ * capacities: lexls_lsi_batch_last_kernel names what a run without the setting names.  With the setting off no kernel loads anything new.
+ * Served by exactly the device entries, for every run they serve and with every option of theirs (deactivate_first_wrong_sign, cycling handling
+ * of an unregularized run, regularized runs with shared, host or device factors, d_x0 / d_v0, d_lambda, d_cycling_counts, the working-set log, an
+ * instance mask, per-instance budgets, LEXLS_LSI_NO_FUSED=1; a batch that LEXLS_LSI_GROUPS splits: the group whose first instance is lo reads from
+ * row lo).  While the setting is on lexls_lsi_batch_run returns LEXLS_ERR_UNSUPPORTED before any work, its outputs left alone: its phase 1 builds
+ * host objects and reads no device memory (the mask's rule).
+ * Errors of this call: LEXLS_ERR_INVALID for a null handle or between lexls_lsi_batch_enqueue_device and its finish. */
+int lexls_lsi_batch_set_instance_obj_dims(lexls_lsi_batch_t b, const uint32_t *d_dims);
 /* How a run executes: phase 1 of every instance on the host; from then on the instance's active-set iterations are resident on the
  * device (LEXLS_LSI_RESIDENT=0: host logic, lock-step stages).  Where the batch's shape has a persistent instantiation (the register-resident l-QR shapes:
  * nVar + 1 <= 41 with levels of up to 12 rows, nVar + 1 <= 64 with levels of up to 16 — except 42..48 columns), everything behind the first resident

@@ -34,7 +34,7 @@ SYMBOLS = [
     "lexls_lsi_batch_set_instance_regularization",
     "lexls_lsi_batch_set_working_set_log", "lexls_lsi_batch_get_working_set_log", "lexls_lsi_batch_working_set_log_device",
     "lexls_lsi_batch_enqueue_device", "lexls_lsi_batch_finish",
-    "lexls_lsi_batch_set_instance_mask", "lexls_lsi_batch_set_instance_max_factorizations",
+    "lexls_lsi_batch_set_instance_mask", "lexls_lsi_batch_set_instance_max_factorizations", "lexls_lsi_batch_set_instance_obj_dims",
     "lexls_lsi_batch_last_kernel",
 ]
 
@@ -99,6 +99,8 @@ def lib() -> C.CDLL:
         _lib.lexls_lsi_batch_set_instance_mask.argtypes = [C.c_void_p, C.c_void_p]  # d_mask: a device address
         _lib.lexls_lsi_batch_set_instance_max_factorizations.restype = C.c_int
         _lib.lexls_lsi_batch_set_instance_max_factorizations.argtypes = [C.c_void_p, C.c_void_p]  # d_limits: a device address
+        _lib.lexls_lsi_batch_set_instance_obj_dims.restype = C.c_int
+        _lib.lexls_lsi_batch_set_instance_obj_dims.argtypes = [C.c_void_p, C.c_void_p]  # d_dims: a device address
         _lib.lexls_lsi_batch_set_working_set_log.restype = C.c_int
         _lib.lexls_lsi_batch_set_working_set_log.argtypes = [C.c_void_p, C.c_uint32]
         _lib.lexls_lsi_batch_get_working_set_log.restype = C.c_int

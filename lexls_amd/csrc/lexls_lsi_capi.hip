@@ -96,6 +96,7 @@ extern "C"
             const ParametersLexLSI par = unpack(h_params, nparams);
             if (const int refused = b->refuse_masked_run("lexls_lsi_batch_run")) return refused; // (nothing launched, the outputs as they are)
             if (const int refused = b->refuse_limited_run("lexls_lsi_batch_run")) return refused;
+            if (const int refused = b->refuse_ragged_run("lexls_lsi_batch_run")) return refused;
             if (const int refused = b->refuse_run("lexls_lsi_batch_run", h_reg_factors, par, h_v0 != NULL)) return refused;
             b->run(h_data, h_var_index, h_active_guess, h_x0, h_v0, h_reg_factors, par, h_x, h_info6, h_active, h_v, h_rounds2);
             return static_cast<int>(LEXLS_OK);
@@ -203,6 +204,15 @@ extern "C"
             if (!b) throw Exception("lexls_lsi_batch_set_instance_max_factorizations: null handle");
             b->refuse_pending("lexls_lsi_batch_set_instance_max_factorizations"); // (an enqueued run reads the array it was given; a captured one goes on reading it)
             return b->set_instance_max_factorizations(d_limits);
+        });
+    }
+
+    int lexls_lsi_batch_set_instance_obj_dims(lexls_lsi_batch_t b, const uint32_t *d_dims)
+    {
+        return guarded([&]() {
+            if (!b) throw Exception("lexls_lsi_batch_set_instance_obj_dims: null handle");
+            b->refuse_pending("lexls_lsi_batch_set_instance_obj_dims"); // (an enqueued run reads the array it was given; a captured one goes on reading it)
+            return b->set_instance_obj_dims(d_dims);
         });
     }
 

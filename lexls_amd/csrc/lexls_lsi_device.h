@@ -33,9 +33,12 @@ namespace
 
     /// One wavefront, one instance: dx = x_lse - x, A*dx, dv, the ratio test over the inactive constraints (first minimum in working-set
     /// scan order) and the update of x / v / A*x in `st` (read from `src`).  Every lane returns the verdict.
+    /// RAGGED, cnt: the instance's row counts (p1_rows) — an absent row is passed over: nothing of it is read, its v and A x stay what they are (0).
+    /// Without RAGGED cnt is not looked at: the loop is the one a batch without per-instance counts has always run
+    template <bool RAGGED = false>
     __device__ __forceinline__ void lsi_step_wave(const StepShape &sh, const double *data, const uint32_t *var_b, const double *x_lse_b, const double *src, double *st,
                                                   const uint8_t *ctr_state_b, const uint16_t *inact_pos_b, double *dx_s, double *adx_s, double *dv_s, double &alpha,
-                                                  int &blk_obj, uint32_t &blk_ctr, uint32_t &blk_type)
+                                                  int &blk_obj, uint32_t &blk_ctr, uint32_t &blk_type, const uint32_t *cnt = nullptr)
     {
         const uint32_t lane = threadIdx.x & 63u;
         const uint32_t n = sh.n, total = sh.total;
@@ -51,6 +54,13 @@ namespace
             uint32_t k = 0;
             while (k + 1 < sh.nObj && g >= sh.first[k + 1]) k++;
             const uint32_t dim = sh.dim[k], c = g - sh.first[k];
+            if constexpr (RAGGED)
+                if (c >= cnt[k]) // an absent row
+                {
+                    adx_s[g] = 0.0;
+                    dv_s[g]  = 0.0;
+                    continue;
+                }
             const double *blk  = data + sh.off[k];
             double adx, lb, ub;
             if (sh.simple[k])
@@ -259,7 +269,27 @@ namespace
         // min(its own entry, max_factorizations), written by lsi_phase1_setup_kernel from the caller's array when the run starts — the array may be
         // rewritten behind the enqueue without touching a run in flight.  NULL: off, every instance stops at max_factorizations and nothing is loaded
         int32_t *inst_max_fact;      // B
+        // per-instance objective row counts (lexls_lsi_batch_set_instance_obj_dims): the counts every instance runs with in THIS run, copied by
+        // lsi_phase1_setup_kernel from the caller's array when the run starts, as the budget above.  sh.dim[k] is then the capacity of objective k —
+        // the leading dimension of its block and the room of its lists — and instance b's objective k is its first inst_dims[b][k] rows.
+        // NULL: off, every objective has sh.dim[k] rows and nothing is loaded
+        uint32_t *inst_dims;         // B x RESIDENT_DIMS_STRIDE
     };
+    /// entries of ResidentArgs::inst_dims per instance
+    constexpr uint32_t RESIDENT_DIMS_STRIDE = STEP_MAX_OBJ;
+    /// the row counts of instance b in a run that has them (a.inst_dims != NULL), for the RAGGED loops.  Wave-uniform; written by an earlier kernel
+    /// of the run and by nobody since
+    __device__ __forceinline__ const uint32_t *resident_counts(const ResidentArgs &a, const uint32_t b) { return a.inst_dims + (size_t)b * RESIDENT_DIMS_STRIDE; }
+    /// the rows objective k of instance b has in this run: its count, or the capacity.  The capacity is read as a VALUE on both sides and the count
+    /// replaces it — a choice between the ADDRESS of a field of the kernel's by-value argument and a pointer to global memory makes the compiler keep
+    /// a copy of the whole argument in scratch memory (132 VGPRs, 704 bytes of scratch per lane and occupancy 3 in lsi_iterate_kernel and
+    /// lsi_phase1_finish_kernel, with or without counts, where this gives 128 / 0 / 4)
+    __device__ __forceinline__ uint32_t resident_rows(const ResidentArgs &a, const uint32_t b, const uint32_t k)
+    {
+        uint32_t rows = a.sh.dim[k];
+        if (a.inst_dims) rows = a.inst_dims[(size_t)b * RESIDENT_DIMS_STRIDE + k]; // (wave-uniform)
+        return rows;
+    }
     /// the factorization limit of instance b in this run (lexlsi.h:238: the run stops when nFactorizations >= it)
     __device__ __forceinline__ int32_t resident_max_factorizations(const ResidentArgs &a, const uint32_t b) { return a.inst_max_fact ? a.inst_max_fact[b] : a.max_factorizations; }
     /// int32 words of one record of ResidentArgs::wlog (the row of lexls_lsi_debug::log)
@@ -343,7 +373,11 @@ namespace
         const ResidentView v  = resident_view(a, b, wib);
         resident_load_lists(a, v, lane);
         StepVerdict r;
-        lsi_step_wave(a.sh, v.data, v.var, a.x_lse + (size_t)b * a.sh.n, v.st, v.st, v.cs, v.ipos, v.dx_s, v.adx_s, v.dv_s, r.alpha, r.blk_obj, r.blk_ctr, r.blk_type);
+        if (a.inst_dims) // (wave-uniform)
+            lsi_step_wave<true>(a.sh, v.data, v.var, a.x_lse + (size_t)b * a.sh.n, v.st, v.st, v.cs, v.ipos, v.dx_s, v.adx_s, v.dv_s, r.alpha, r.blk_obj, r.blk_ctr, r.blk_type,
+                                resident_counts(a, b));
+        else
+            lsi_step_wave(a.sh, v.data, v.var, a.x_lse + (size_t)b * a.sh.n, v.st, v.st, v.cs, v.ipos, v.dx_s, v.adx_s, v.dv_s, r.alpha, r.blk_obj, r.blk_ctr, r.blk_type);
         return r;
     }
 
@@ -437,10 +471,10 @@ namespace
             // one that ends the run at the relaxation limit — which is logged like any other.  Rank: this iteration's factorization
             if (a.wlog && (blocked || removed)) // (wave-uniform)
             {
-                const uint32_t cnt = a.wlog_count[b];
-                if (cnt < a.wlog_cap)
+                const uint32_t nlog = a.wlog_count[b];
+                if (nlog < a.wlog_cap)
                 {
-                    const size_t row    = (size_t)b * a.wlog_cap + cnt;
+                    const size_t row    = (size_t)b * a.wlog_cap + nlog;
                     int32_t *e          = a.wlog + row * RESIDENT_WLOG_FIELDS;
                     const uint32_t robj = blocked ? (uint32_t)blk_obj : (uint32_t)(rm_lvl + (int32_t)a.off);
                     e[0]                = (int32_t)robj;
@@ -450,11 +484,11 @@ namespace
                     e[4]                = (int32_t)trank;
                     a.wlog_alpha[row]   = blocked ? verdict.alpha : (a.first_wrong_sign ? 0.0 : a.maxabs[b]);
                 }
-                a.wlog_count[b] = cnt + 1u;
+                a.wlog_count[b] = nlog + 1u;
             }
             if (blocked) // OPERATION_ADD: workingset.h:79-92
             {
-                const uint32_t f = sh.first[blk_obj], nak = na[blk_obj], nik = sh.dim[blk_obj] - nak;
+                const uint32_t f = sh.first[blk_obj], nak = na[blk_obj], nik = resident_rows(a, b, (uint32_t)blk_obj) - nak;
                 const uint32_t pos = ipos[f + blk_ctr], last = ina[f + nik - 1];
                 ina[f + pos]       = (uint16_t)last;
                 ipos[f + last]     = (uint16_t)pos;
@@ -466,7 +500,7 @@ namespace
             else if (removed) // OPERATION_REMOVE: workingset.h:99-108
             {
                 const uint32_t k = (uint32_t)(rm_lvl + (int32_t)a.off), p = (uint32_t)rm_pos;
-                const uint32_t f = sh.first[k], nak = na[k], nik = sh.dim[k] - nak;
+                const uint32_t f = sh.first[k], nak = na[k], nik = resident_rows(a, b, k) - nak;
                 const uint32_t c = act[f + p];
                 for (uint32_t i = p; i + 1 < nak; i++) act[f + i] = act[f + i + 1];
                 cs[f + c]    = (uint8_t)CTR_INACTIVE;

@@ -103,6 +103,9 @@ struct lexls_lsi_batch_s
     // ---- lexls_lsi_batch_set_instance_max_factorizations: batch int32 in device memory, the caller's; read by the setup kernel of every device run while set ----
     const int32_t *d_limits = NULL;
     const int32_t *group_limits(uint32_t g) const { return d_limits ? d_limits + lo[g] : NULL; }
+    // ---- lexls_lsi_batch_set_instance_obj_dims: batch x nObj uint32 in device memory, the caller's; read by the setup kernel of every device run while set ----
+    const uint32_t *d_obj_dims = NULL;
+    const uint32_t *group_obj_dims(uint32_t g) const { return d_obj_dims ? d_obj_dims + (size_t)lo[g] * nObj : NULL; }
     double t_create = 0.0;
     int32_t last_stats[4] = {0, 0, 0, 0}; // of the last run: factorize+solve stages, sensitivity stages, stages with the step on the device, groups
     // ---- getLambda of the last run (lexls_lsi_batch_get_lambda, lexlsi.h:552-605) ----
@@ -615,6 +618,20 @@ struct lexls_lsi_batch_s
         d_limits = d_limits_;
         return LEXLS_OK;
     }
+    /// lexls_lsi_batch_set_instance_obj_dims: the pointer is kept (NULL: every instance has the batch's dims); nothing is read or copied here
+    int set_instance_obj_dims(const uint32_t *d_dims_)
+    {
+        d_obj_dims = d_dims_;
+        return LEXLS_OK;
+    }
+    /// lexls_lsi_batch_run while row counts are set: the mask's rule (refuse_masked_run)
+    int refuse_ragged_run(const char *who) const
+    {
+        if (!d_obj_dims) return LEXLS_OK;
+        lexls_internal_set_error((std::string(who) + ": not served while lexls_lsi_batch_set_instance_obj_dims holds per-instance objective row counts for this batch (they are device "
+                                                     "memory, read by the kernels of lexls_lsi_batch_run_device / lexls_lsi_batch_enqueue_device only): clear them with a NULL pointer first").c_str());
+        return LEXLS_ERR_UNSUPPORTED;
+    }
     /// lexls_lsi_batch_run while limits are set: the mask's rule (refuse_masked_run) — its phase 1 is host work and reads no device memory
     int refuse_limited_run(const char *who) const
     {
@@ -1075,7 +1092,7 @@ struct lexls_lsi_batch_s
             const uint8_t *gg = guess ? guess + (size_t)lo[g] * total : NULL;
             const double *xg  = x0 ? x0 + (size_t)lo[g] * nVar : NULL;
             ctx.enqueue_phase1_setup(dev ? xg : ctx.stage_x0(xg), dev ? gg : ctx.stage_guess(gg), lo[g], max_fact, v0 ? v0 + (size_t)lo[g] * total : NULL, NULL,
-                                     dev ? group_mask(g) : NULL, dev ? group_limits(g) : NULL); // (mask and limits are the device entries' alone: lexls_lsi_batch_run is refused while one is set)
+                                     dev ? group_mask(g) : NULL, dev ? group_limits(g) : NULL, dev ? group_obj_dims(g) : NULL); // (mask, limits and row counts are the device entries' alone: lexls_lsi_batch_run is refused while one is set)
         }
         r.t_ctx = BatchCtx::now() - r.t_begin;
         uint32_t fault = 0xffffffffu;
@@ -1252,7 +1269,7 @@ struct lexls_lsi_batch_s
             if (dim0 && hipMemcpyAsync(ctx.d_rvar, dev.var_index + (size_t)lo[g] * dim0, 4 * (size_t)ctx.B * dim0, hipMemcpyDeviceToDevice, ctx.stream) != hipSuccess)
                 throw Exception("copy of the variable indices failed");
             ctx.enqueue_phase1_setup(dev.x0 ? dev.x0 + (size_t)lo[g] * nVar : NULL, dev.active_guess ? dev.active_guess + (size_t)lo[g] * total : NULL, lo[g], max_fact,
-                                     dev.v0 ? dev.v0 + (size_t)lo[g] * total : NULL, as.d_fault, group_mask(g), group_limits(g));
+                                     dev.v0 ? dev.v0 + (size_t)lo[g] * total : NULL, as.d_fault, group_mask(g), group_limits(g), group_obj_dims(g));
             const bool keep_fixed_bounds = lam_rc_after(par) == LEXLS_OK;
             ctx.enqueue_phase1_gate(as.d_fault, max_fact);
             ctx.enqueue_phase1_stage(dev.x0 != NULL, par.tol_wrong_sign_lambda, par.tol_correct_sign_lambda, max_fact, false);

@@ -285,6 +285,8 @@ namespace
         Pinned<double> fix_val_host;
         int32_t *d_inst_limit = NULL;      // B: every instance's factorization limit of this run (ResidentArgs::inst_max_fact), the setup kernel's copy
         bool inst_limits = false;          // this run has per-instance limits (lexls_lsi_batch_set_instance_max_factorizations): the resident kernels read d_inst_limit
+        uint32_t *d_inst_dims = NULL;      // B x RESIDENT_DIMS_STRIDE: every instance's objective row counts of this run (ResidentArgs::inst_dims), the setup kernel's copy
+        bool inst_dims = false;            // this run has per-instance row counts (lexls_lsi_batch_set_instance_obj_dims): the resident kernels read d_inst_dims
         bool fused_all = false, fused_refused = false; // the rest of the resident iterations is one persistent launch / the shape has none
         const char *resident_kernel = "";              // the kernel that served the resident iterations of this run (download_resident)
         int rounds_fs = 0, rounds_sens = 0, rounds_step = 0;
@@ -341,7 +343,8 @@ namespace
             r_off  = off;
             rl     = ResidentSlab(B, sh.total);
             if (hipMalloc((void **)&d_rstate, 8 * (size_t)B * sh.SD) != hipSuccess || hipMalloc((void **)&d_rws, rl.bytes) != hipSuccess ||
-                hipMalloc((void **)&d_rvar, 4 * (size_t)B * (sh.dim0 ? sh.dim0 : 1)) != hipSuccess || hipMalloc((void **)&d_inst_limit, 4 * (size_t)B) != hipSuccess)
+                hipMalloc((void **)&d_rvar, 4 * (size_t)B * (sh.dim0 ? sh.dim0 : 1)) != hipSuccess || hipMalloc((void **)&d_inst_limit, 4 * (size_t)B) != hipSuccess ||
+                hipMalloc((void **)&d_inst_dims, 4 * (size_t)B * RESIDENT_DIMS_STRIDE) != hipSuccess)
                 throw Exception("hipMalloc failed (resident LSI iterations)");
             rws_host.assign(rl.bytes, 0);
             rstate_host.assign((size_t)B * sh.SD, 0.0);
@@ -432,6 +435,7 @@ namespace
             ra.wlog = d_wlog, ra.wlog_alpha = d_wlog_alpha, ra.wlog_count = d_wlog_count, ra.wlog_cap = wlog_cap; // (NULL: off)
             ra.maxabs = reinterpret_cast<const double *>(out + lay.max_abs);
             ra.inst_max_fact = inst_limits ? d_inst_limit : NULL;
+            ra.inst_dims     = inst_dims ? d_inst_dims : NULL;
             return ra;
         }
 
@@ -594,8 +598,10 @@ namespace
         /// d_mask (lexls_lsi_batch_set_instance_mask): this group's bytes of the caller's instance mask or NULL, read by the kernel where they lie
         /// d_limits (lexls_lsi_batch_set_instance_max_factorizations): this group's words of the caller's limits or NULL; the kernel copies what counts
         /// for this run into d_inst_limit, which every later kernel of the run reads (resident_args)
+        /// d_obj_dims (lexls_lsi_batch_set_instance_obj_dims): this group's rows of the caller's counts (B x nObj) or NULL; the kernel checks them against
+        /// the capacities and copies them into d_inst_dims, likewise
         void enqueue_phase1_setup(const double *d_x0, const uint8_t *d_guess, uint32_t first, int32_t max_factorizations, const double *d_v0 = NULL, uint32_t *run_fault = NULL,
-                                  const uint8_t *d_mask = NULL, const int32_t *d_limits = NULL)
+                                  const uint8_t *d_mask = NULL, const int32_t *d_limits = NULL, const uint32_t *d_obj_dims = NULL)
         {
             const double t0 = now();
             if (!d_p1_fault && !run_fault)
@@ -606,11 +612,12 @@ namespace
             hip_check(lexls_internal_ensure_gather_buffer(h));
             phase1_on_device = true;
             inst_limits      = d_limits != NULL;
+            inst_dims        = d_obj_dims != NULL;
             Phase1Args pa;
             pa.ra = resident_args(max_factorizations);
-            pa.x0 = d_x0, pa.guess = d_guess, pa.v0 = d_v0, pa.fault = run_fault ? run_fault : d_p1_fault, pa.first = first, pa.mask = d_mask, pa.limits = d_limits;
+            pa.x0 = d_x0, pa.guess = d_guess, pa.v0 = d_v0, pa.fault = run_fault ? run_fault : d_p1_fault, pa.first = first, pa.mask = d_mask, pa.limits = d_limits, pa.obj_dims = d_obj_dims;
             if (!run_fault && hipMemsetAsync(d_p1_fault, 0xff, 16, stream) != hipSuccess) throw Exception("hipMemsetAsync failed (phase 1 on the device)");
-            hipLaunchKernelGGL(lsi_phase1_setup_kernel, dim3((B + 3) / 4), dim3(256), 4 * resident_lds_per_wave(rshape.SD, rshape.total), stream, pa);
+            hipLaunchKernelGGL(lsi_phase1_setup_kernel, dim3((B + 3) / 4), dim3(256), 4 * resident_lds_per_wave(rshape.SD, rshape.total) + (d_obj_dims ? P1_COUNTS_LDS : 0), stream, pa);
             if (hipGetLastError() != hipSuccess || (!run_fault && hipMemcpyAsync(p1_fault_host.data(), d_p1_fault, 4, hipMemcpyDeviceToHost, stream) != hipSuccess))
                 throw Exception("lsi_phase1_setup_kernel launch failed");
             t_enqueue += now() - t0;
@@ -769,6 +776,7 @@ namespace
             stage_fs = stage_sens = false;
             phase1_on_device = false;
             inst_limits      = false;
+            inst_dims        = false;
             if (resident)
             {
                 std::fill(rws_host.begin(), rws_host.begin() + rl.bytes_core, 0); // (the stamps behind: hand_over writes every one a run reads)
@@ -780,7 +788,7 @@ namespace
         ~BatchCtx()
         {
             if (h) lexls_lse_destroy(h);
-            void *dev[] = {d_state, d_state_in, d_res, d_var, d_wset, d_rstate, d_rvar, d_rws, d_p1_fault, d_p1_guess, d_p1_x0, d_fix_var, d_fix_val, d_inst_limit};
+            void *dev[] = {d_state, d_state_in, d_res, d_var, d_wset, d_rstate, d_rvar, d_rws, d_p1_fault, d_p1_guess, d_p1_x0, d_fix_var, d_fix_val, d_inst_limit, d_inst_dims};
             for (void *q : dev)
                 if (q) (void)hipFree(q);
             if (stream) (void)hipStreamDestroy(stream);

@@ -20,6 +20,7 @@ namespace
         uint32_t first;       // index in the batch of this group's instance 0
         const uint8_t *mask;  // B bytes, or NULL (lexls_lsi_batch_set_instance_mask): 0 = the instance is skipped in this run
         const int32_t *limits; // B words, or NULL (lexls_lsi_batch_set_instance_max_factorizations): the instance's own factorization limit, <= 0 = none
+        const uint32_t *obj_dims; // B x nObj words, or NULL (lexls_lsi_batch_set_instance_obj_dims): the rows every objective of the instance has, <= sh.dim[k]
     };
 
     /// byte b of an instance mask (NULL: every instance is solved).  The bytes are the caller's, rewritten in place between two runs and between two
@@ -35,11 +36,21 @@ namespace
         return (L >= 1 && L < max_factorizations) ? L : max_factorizations;
     }
 
+    /// count k of instance b (lexls_lsi_batch_set_instance_obj_dims).  The words are the caller's, rewritten in place between runs and replays like the
+    /// mask's bytes: a volatile vector load, never through the scalar cache
+    __device__ __forceinline__ uint32_t lsi_instance_obj_dim(const uint32_t *obj_dims, uint32_t b, uint32_t nObj, uint32_t k)
+    {
+        return *reinterpret_cast<const volatile uint32_t *>(obj_dims + (size_t)b * nObj + k);
+    }
+
     /// Objective::initialize_Ax + initialize_v0 (objective.h:162-196, set_min_init_ctr_violation) for the x in x_s (LDS, n doubles), lane =
     /// constraint: st = [x | v | A x].  A x is apply_A's ordered chain per row (objective.h:435-455).  cs: the activation types (LDS).
     /// v0 (the instance's total doubles, or NULL): Objective::phase1 with v0_is_specified — A x is formed, initialize_v0 is not run, v is v0
+    /// RAGGED, cnt: the instance's row counts (p1_rows) — the v and A x of an absent row are 0 (the slab may hold an earlier run's), nothing of it is
+    /// read.  Without RAGGED cnt is not looked at, as in lsi_step_wave
+    template <bool RAGGED = false>
     __device__ __forceinline__ void lsi_phase1_state(const StepShape &sh, const double *data, const uint32_t *var_b, const double *x_s, const uint8_t *cs, double *st,
-                                                     const double *v0 = nullptr)
+                                                     const double *v0 = nullptr, const uint32_t *cnt = nullptr)
     {
         const uint32_t lane = threadIdx.x & 63u;
         const uint32_t n = sh.n, total = sh.total;
@@ -49,6 +60,13 @@ namespace
             uint32_t k = 0;
             while (k + 1 < sh.nObj && g >= sh.first[k + 1]) k++;
             const uint32_t dim = sh.dim[k], c = g - sh.first[k];
+            if constexpr (RAGGED)
+                if (c >= cnt[k]) // an absent row (cnt: wave-uniform)
+                {
+                    st[n + g]         = 0.0;
+                    st[n + total + g] = 0.0;
+                    continue;
+                }
             const double *blk  = data + sh.off[k];
             double ax, lb, ub;
             if (sh.simple[k])
@@ -85,7 +103,12 @@ namespace
         }
     }
 
-    __global__ __launch_bounds__(256) void lsi_phase1_setup_kernel(Phase1Args p)
+    /// dynamic LDS lsi_phase1_setup_kernel takes on top of the four wavefronts' slices when the run has row counts (Phase1Args::obj_dims)
+    constexpr size_t P1_COUNTS_LDS = 4 * 4 * (size_t)STEP_MAX_OBJ;
+
+    /// RAGGED: the run has row counts (p.obj_dims != NULL).  Without it nothing of them is compiled in: the kernel a batch without counts has always run
+    template <bool RAGGED>
+    __device__ __forceinline__ void lsi_phase1_setup_body(const Phase1Args &p)
     {
         const ResidentArgs &a = p.ra;
         const uint32_t lane = threadIdx.x & 63u, wib = threadIdx.x >> 6;
@@ -124,20 +147,51 @@ namespace
             return;
         }
 
-        // ---- the checks, lane = constraint ----
+        // ---- the instance's row counts: lane = objective, into LDS (STEP_MAX_OBJ words per wavefront behind the four wavefronts' slices: a launch
+        // with counts asks for them, P1_COUNTS_LDS), where every lane and the serial part below read them.  A count above its capacity ends the
+        // instance here: with it the rows to check are not even known ----
+        const uint32_t *cnt = nullptr;
+        if constexpr (RAGGED)
+        {
+            extern __shared__ double smem[];
+            uint32_t *cnt_s = reinterpret_cast<uint32_t *>(reinterpret_cast<char *>(smem) + 4 * resident_lds_per_wave(sh.SD, total)) + wib * STEP_MAX_OBJ;
+            bool above      = false;
+            if (lane < sh.nObj)
+            {
+                const uint32_t c = lsi_instance_obj_dim(p.obj_dims, b, sh.nObj, lane);
+                above            = c > sh.dim[lane];
+                cnt_s[lane]      = c;
+            }
+            if (__ballot(above))
+            {
+                if (lane == 0) atomicMin(p.fault, (p.first + b) * 8u + (uint32_t)P1_OBJ_DIM);
+                return;
+            }
+            __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
+            asm volatile("" ::: "memory");
+            cnt = cnt_s;
+        }
+
+        // ---- the checks, lane = constraint (present rows only) ----
         uint32_t fault = 0xffffffffu;
         for (uint32_t g = lane; g < total; g += 64)
         {
             uint32_t k = 0;
             while (k + 1 < sh.nObj && g >= sh.first[k + 1]) k++;
+            if constexpr (RAGGED)
+                if (g - sh.first[k] >= cnt[k])
+                {
+                    cls[g] = 0;
+                    continue;
+                }
             const uint8_t rc = p1_row_class(sh, v.data, k, g - sh.first[k]);
             cls[g]           = rc;
             if (rc == P1_ROW_FAULT) fault = min(fault, (uint32_t)P1_LB_ABOVE_UB);
             if (guess && p1_guess_fault(guess[g]) != P1_OK) fault = min(fault, (uint32_t)P1_GUESS_TYPE);
         }
-        for (uint32_t c = lane; c < sh.dim0; c += 64)
+        for (uint32_t c = lane; c < (sh.dim0 ? p1_rows<RAGGED>(sh, cnt, 0) : 0u); c += 64) // (dim0: 0 without a simple-bounds objective)
         {
-            const uint32_t f = p1_var_fault(sh, v.var, c);
+            const uint32_t f = p1_var_fault<RAGGED>(sh, v.var, c, cnt);
             if (f != P1_OK) fault = min(fault, f);
         }
         const uint32_t worst = (uint32_t)(-lexls::wave_maxi(-(int)min(fault, 0xffffu))); // (wave-uniform)
@@ -153,7 +207,7 @@ namespace
         if (lane == 0)
         {
             uint32_t next = 0;
-            p1_build_working_set(sh, cls, guess, v.cs, v.act, v.ina, v.ipos, v.na, stamp_s, &next);
+            p1_build_working_set<RAGGED>(sh, cls, guess, v.cs, v.act, v.ina, v.ipos, v.na, stamp_s, &next, cnt);
             a.next_stamp[b] = next;
             a.alive[b]      = 1;
             a.skip[b]       = 0;
@@ -163,6 +217,8 @@ namespace
             // instance has returned above: its entry is not read)
             if (p.limits) a.inst_max_fact[b] = lsi_instance_limit(p.limits, b, a.max_factorizations);
         }
+        // ... and so are its row counts (the LDS copy: the values the checks above were made with)
+        if (RAGGED && lane < RESIDENT_DIMS_STRIDE) a.inst_dims[(size_t)b * RESIDENT_DIMS_STRIDE + lane] = lane < sh.nObj ? cnt[lane] : 0u;
         __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
         asm volatile("" ::: "memory");
         for (uint32_t g = lane; g < total; g += 64)
@@ -183,12 +239,21 @@ namespace
             for (uint32_t j = lane; j < n; j += 64) v.dx_s[j] = p.x0[(size_t)b * n + j];
             __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
             asm volatile("" ::: "memory");
-            lsi_phase1_state(sh, v.data, v.var, v.dx_s, v.cs, v.st, p.v0 ? p.v0 + (size_t)b * total : nullptr);
+            const double *v0 = p.v0 ? p.v0 + (size_t)b * total : nullptr;
+            lsi_phase1_state<RAGGED>(sh, v.data, v.var, v.dx_s, v.cs, v.st, v0, cnt);
         }
 
         // ---- the first equality problem ----
         const EqualityProblemSlab slab = {a.dims, a.nfixed, a.fixed_idx, a.fixed_val, a.row_src, a.row_ld, a.fixed_type, a.ctr_type};
         lsi_form_equality_problem(sh, a.off, a.nObjL, a.cap, b, v.data, v.var, v.na, v.act, v.cs, slab, lane, 64u);
+    }
+
+    __global__ __launch_bounds__(256) void lsi_phase1_setup_kernel(Phase1Args p)
+    {
+        if (p.obj_dims) // (uniform over the launch)
+            lsi_phase1_setup_body<true>(p);
+        else
+            lsi_phase1_setup_body<false>(p);
     }
 
     /// behind the first factorization and its removal search: iteration 0.  has_x0 == 0: phase 1 takes x = x_lse first (lexlsi.h:350-357), the step
@@ -207,7 +272,10 @@ namespace
             for (uint32_t g = lane; g < a.sh.total; g += 64) v.cs[g] = v.g_cs[g];
             __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
             asm volatile("" ::: "memory");
-            lsi_phase1_state(a.sh, v.data, v.var, v.dx_s, v.cs, v.st);
+            if (a.inst_dims) // (wave-uniform)
+                lsi_phase1_state<true>(a.sh, v.data, v.var, v.dx_s, v.cs, v.st, nullptr, resident_counts(a, b));
+            else
+                lsi_phase1_state(a.sh, v.data, v.var, v.dx_s, v.cs, v.st);
             __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "workgroup"); // the step reads the state back from memory
             asm volatile("" ::: "memory");
         }

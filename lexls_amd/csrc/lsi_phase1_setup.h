@@ -32,7 +32,7 @@ namespace
     };
 
     /// what is wrong with an instance's input (the smallest code an instance has is the one reported)
-    enum : uint32_t { P1_OK = 0, P1_LB_ABOVE_UB = 1, P1_VAR_RANGE = 2, P1_VAR_DUPLICATE = 3, P1_GUESS_TYPE = 4 };
+    enum : uint32_t { P1_OK = 0, P1_LB_ABOVE_UB = 1, P1_VAR_RANGE = 2, P1_VAR_DUPLICATE = 3, P1_GUESS_TYPE = 4, P1_OBJ_DIM = 5 };
     inline const char *p1_fault_text(uint32_t fault)
     {
         switch (fault)
@@ -41,9 +41,24 @@ namespace
         case P1_VAR_RANGE: return "An element of VarIndex is not below the number of variables.";
         case P1_VAR_DUPLICATE: return "Elements of VarIndex are not unique.";
         case P1_GUESS_TYPE: return "An entry of the active-set guess is not an activation type (0 .. 3).";
+        case P1_OBJ_DIM: return "An objective row count is above the batch's capacity.";
         default: return "";
         }
     }
+    /// Per-instance objective row counts (lexls_lsi_batch_set_instance_obj_dims).  RAGGED and `cnt`, wherever they appear below: the instance's nObj
+    /// counts; without RAGGED cnt is not looked at and every objective has its capacity sh.dim[k] rows — the code a batch without counts has always
+    /// run.  Objective k of the instance is the first cnt[k] rows of its block; sh.dim[k] stays the leading dimension of the block and sh.first[k]
+    /// its first row among the instance's `total`.  Rows from cnt[k] on are absent: nothing of them is read.  (The resident iteration has
+    /// resident_rows, lexls_lsi_device.h)
+    template <bool RAGGED = false>
+    LEXLS_P1_FN uint32_t p1_rows(const StepShape &sh, const uint32_t *cnt, uint32_t k)
+    {
+        if constexpr (RAGGED)
+            return cnt[k];
+        else
+            return sh.dim[k];
+    }
+
     /// p1_row_class: the row's bounds are in the wrong order
     constexpr uint8_t P1_ROW_FAULT = 0x80;
 
@@ -70,10 +85,13 @@ namespace
     }
 
     /// entry c of the variable indices of a simple-bounds objective 0 (lexlsi.h:201-203, and the range the host takes for granted)
-    LEXLS_P1_FN uint32_t p1_var_fault(const StepShape &sh, const uint32_t *var, uint32_t c)
+    template <bool RAGGED = false>
+    LEXLS_P1_FN uint32_t p1_var_fault(const StepShape &sh, const uint32_t *var, uint32_t c, const uint32_t *cnt = nullptr)
     {
         if (var[c] >= sh.n) return P1_VAR_RANGE;
-        for (uint32_t j = 0; j < sh.dim0; j++)
+        uint32_t d0 = sh.dim0;
+        if constexpr (RAGGED) d0 = cnt[0];
+        for (uint32_t j = 0; j < d0; j++)
             if (j != c && var[j] == var[c]) return P1_VAR_DUPLICATE;
         return P1_OK;
     }
@@ -104,9 +122,11 @@ namespace
 
     /// WorkingSet::activate (workingset.h:60-69) on the lists of objective k (f = its first constraint, nak = its active constraints so far): swap
     /// with last in the inactive list, append to the active one.  The same statements as the ADD of lsi_iterate_finish
-    LEXLS_P1_FN void p1_activate(const StepShape &sh, uint32_t k, uint32_t c, uint8_t type, uint8_t *cs, uint16_t *act, uint16_t *ina, uint16_t *ipos, uint16_t *na)
+    template <bool RAGGED = false>
+    LEXLS_P1_FN void p1_activate(const StepShape &sh, uint32_t k, uint32_t c, uint8_t type, uint8_t *cs, uint16_t *act, uint16_t *ina, uint16_t *ipos, uint16_t *na,
+                                 const uint32_t *cnt = nullptr)
     {
-        const uint32_t f = sh.first[k], nak = na[k], nik = sh.dim[k] - nak;
+        const uint32_t f = sh.first[k], nak = na[k], nik = p1_rows<RAGGED>(sh, cnt, k) - nak;
         const uint32_t pos = ipos[f + c], last = ina[f + nik - 1];
         ina[f + pos]   = (uint16_t)last;
         ipos[f + last] = (uint16_t)pos;
@@ -119,33 +139,44 @@ namespace
     /// activation flags or NULL.  The reference's list WS (lexlsi.h:148-173) receives the equality activations of setData first, objective by
     /// objective and row by row, then the guess's LB / UB activations in (objective, row) order — rows that are active already and guess flags
     /// of type EQ are passed over (api_activate, lexlsi.h:120-136); a constraint's position in WS is its stamp.  cs / act / ina / ipos: total
-    /// entries each, objective k from first[k] on; na: STEP_MAX_OBJ entries; stamp: total entries (written for the active constraints only)
+    /// entries each, objective k from first[k] on; na: STEP_MAX_OBJ entries; stamp: total entries (written for the active constraints only).
+    /// With cnt the lists are those of the object that has the present rows only; an absent row is inactive and in no list (its entries are 0)
+    template <bool RAGGED = false>
     LEXLS_P1_FN void p1_build_working_set(const StepShape &sh, const uint8_t *cls, const uint8_t *guess, uint8_t *cs, uint16_t *act, uint16_t *ina, uint16_t *ipos,
-                                          uint16_t *na, uint32_t *stamp, uint32_t *next_stamp)
+                                          uint16_t *na, uint32_t *stamp, uint32_t *next_stamp, const uint32_t *cnt = nullptr)
     {
         for (uint32_t k = 0; k < STEP_MAX_OBJ; k++) na[k] = 0;
         for (uint32_t k = 0; k < sh.nObj; k++) // WorkingSet::reset (workingset.h:51-58)
-            for (uint32_t c = 0; c < sh.dim[k]; c++)
+        {
+            const uint32_t rk = p1_rows<RAGGED>(sh, cnt, k);
+            for (uint32_t c = 0; c < rk; c++)
             {
                 const uint32_t g = sh.first[k] + c;
                 cs[g] = (uint8_t)CTR_INACTIVE, act[g] = 0, ina[g] = (uint16_t)c, ipos[g] = (uint16_t)c;
             }
+            if constexpr (RAGGED)
+                for (uint32_t c = rk; c < sh.dim[k]; c++) // absent rows
+                {
+                    const uint32_t g = sh.first[k] + c;
+                    cs[g] = (uint8_t)CTR_INACTIVE, act[g] = 0, ina[g] = 0, ipos[g] = 0;
+                }
+        }
         uint32_t next = 0;
         for (uint32_t k = 0; k < sh.nObj; k++)
-            for (uint32_t c = 0; c < sh.dim[k]; c++)
+            for (uint32_t c = 0, rk = p1_rows<RAGGED>(sh, cnt, k); c < rk; c++)
                 if (cls[sh.first[k] + c] == (uint8_t)CTR_ACTIVE_EQ)
                 {
-                    p1_activate(sh, k, c, (uint8_t)CTR_ACTIVE_EQ, cs, act, ina, ipos, na);
+                    p1_activate<RAGGED>(sh, k, c, (uint8_t)CTR_ACTIVE_EQ, cs, act, ina, ipos, na, cnt);
                     stamp[sh.first[k] + c] = next++;
                 }
         if (guess)
             for (uint32_t k = 0; k < sh.nObj; k++)
-                for (uint32_t c = 0; c < sh.dim[k]; c++)
+                for (uint32_t c = 0, rk = p1_rows<RAGGED>(sh, cnt, k); c < rk; c++)
                 {
                     const uint8_t t = guess[sh.first[k] + c];
                     if ((t == (uint8_t)CTR_ACTIVE_LB || t == (uint8_t)CTR_ACTIVE_UB) && cs[sh.first[k] + c] == (uint8_t)CTR_INACTIVE)
                     {
-                        p1_activate(sh, k, c, t, cs, act, ina, ipos, na);
+                        p1_activate<RAGGED>(sh, k, c, t, cs, act, ina, ipos, na, cnt);
                         stamp[sh.first[k] + c] = next++;
                     }
                 }

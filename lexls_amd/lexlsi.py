@@ -243,6 +243,7 @@ class LsiBatch:
         self._instance_factors = None  # the device tensor (or address) set_instance_regularization was given: kept alive while the library reads it
         self._instance_mask = None  # the device tensor set_instance_mask was given: kept alive while the library reads it
         self._instance_limits = None  # the device tensor set_instance_max_factorizations was given: kept alive while the library reads it
+        self._instance_obj_dims = None  # the device tensor set_instance_obj_dims was given: kept alive while the library reads it
         capi.check(capi.lib().lexls_lsi_batch_create(C.byref(self._h), C.c_int(device), C.c_uint32(self.batch), C.c_uint32(self.nvar),
                                                      C.c_uint32(len(self.dims)), _p(self.dims, C.c_uint32), _p(self.types, C.c_int32)))
 
@@ -324,6 +325,26 @@ class LsiBatch:
             ptr = self._device_array("limits", limits, torch.int32, (self.batch,), optional=False)
         capi.check(capi.lib().lexls_lsi_batch_set_instance_max_factorizations(self._h, ptr))
         self._instance_limits = limits  # (a tensor given earlier is let go of only now that the library has another source)
+
+    def set_instance_obj_dims(self, dims):
+        """lexls_lsi_batch_set_instance_obj_dims: `dims` is a torch uint32 or int32 tensor of shape (batch, nObj) on the batch's device (contiguous), or
+        None to clear the setting.  In every later run_device() / enqueue_device() objective k of instance i consists of the first dims[i, k] rows of
+        its block; the batch's own dims are the capacities and stay the layout of every array (data, var_index, active_guess, v0 and the outputs).
+        Rows beyond an instance's count are absent: nothing of them is read, their rows of active / v / lambda are written as 0.  A count above its
+        capacity is an input error of the run (code 5), 0 is an empty objective.  The tensor is KEPT — a reference is held so the memory stays alive —
+        and read on the device at the start of every run, so it may be rewritten in place between runs and between replays of a captured
+        enqueue_device(); a run in flight keeps the values it started with.  While counts are set, run() raises (LEXLS_ERR_UNSUPPORTED)."""
+        if dims is None:
+            ptr = None
+        else:
+            import torch
+            if not hasattr(dims, "data_ptr") or dims.dtype not in (torch.uint32, torch.int32):
+                raise TypeError("set_instance_obj_dims: dims must be a torch uint32 or int32 tensor on the batch's device, or None")
+            if tuple(dims.shape) != (self.batch, len(self.dims)):
+                raise ValueError(f"set_instance_obj_dims: dims have shape {tuple(dims.shape)}, {(self.batch, len(self.dims))} expected")
+            ptr = self._device_array("dims", dims, dims.dtype, (self.batch, len(self.dims)), optional=False)
+        capi.check(capi.lib().lexls_lsi_batch_set_instance_obj_dims(self._h, ptr))
+        self._instance_obj_dims = dims  # (a tensor given earlier is let go of only now that the library has another source)
 
     def run(self, problems, active_guess=None, x0=None, regularization_factors=None, v0=None, **params):
         """`problems`: list of objective lists or a PackedBatch of this batch's structure; other arguments as lsi_batch_solve"""
