@@ -240,6 +240,13 @@ int lexls_lse_last_consumer_kernel(lexls_lse_t h, char *buf, size_t len);
  * LEXLS_LARGE_PERSIST=0 and where no form of the launch fits the device; LEXLS_LARGE_PERSIST=2 gives up on every level it is tried on).  Read on the host from
  * the flag the launcher reads anyway: diagnostics, no kernel and no launch depends on it */
 int lexls_lse_last_large_levels(lexls_lse_t h, uint32_t *in_launch, uint32_t *redone);
+/* lqr_wave<..,regularized> keeps the regularization routines' optional pieces in LDS as far as the launcher finds room for them
+ * (wave_reg_lds_bytes, lexls_lds.h); what does not fit stays in the handle's scratch in HBM: same routines, same bits, other address space.
+ * Of the last factorization: *window_order = order of the LDS window of the routines' work matrix (a level whose normal equations have a
+ * larger order works in HBM; 0: no window), *basis_in_lds = 1 when the accumulated null-space basis was kept in LDS (both 0 on every
+ * other kernel — the generic kernel keeps all of it in HBM — and without regularization).  Stored on the host by the launcher, the value it
+ * passed to the launch: diagnostics, no kernel and no launch depends on it */
+int lexls_lse_last_reg_placement(lexls_lse_t h, uint32_t *window_order, uint32_t *basis_in_lds);
 /* Kernel policy — which CONTRACT a solve is held to, and which kernel family serves it.
  *   Contracts: (B) bit-identical to the arithmetic contract of oracle/lexlse_oracle.h (pivots, ranks, Householder scalars, factor, x, multipliers);
  *              (T) BASELINE north_star's: column permutation, ranks and first columns exact, x (and factor MAGNITUDES) within 1e-10

@@ -24,7 +24,7 @@ SYMBOLS = [
     "lexls_lse_residual", "lexls_lse_sensitivity",
     "lexls_lse_get_x", "lexls_lse_get_factor", "lexls_lse_get_hh_scalars", "lexls_lse_get_permutation", "lexls_lse_get_ranks",
     "lexls_lse_get_v", "lexls_lse_get_mu", "lexls_lse_get_lambda", "lexls_lse_get_sensitivity", "lexls_lse_get_ctr_type",
-    "lexls_lse_device_ptr", "lexls_lse_last_kernel", "lexls_lse_last_consumer_kernel", "lexls_lse_last_large_levels", "lexls_lse_set_kernel_policy",
+    "lexls_lse_device_ptr", "lexls_lse_last_kernel", "lexls_lse_last_consumer_kernel", "lexls_lse_last_large_levels", "lexls_lse_last_reg_placement", "lexls_lse_set_kernel_policy",
     "lexls_lse_set_accuracy_guard", "lexls_lse_get_accuracy",
     "lexls_lse_set_prefix_reuse", "lexls_lse_prefix_reuse_ready", "lexls_lse_set_resume_levels",
     "lexls_lsi_solve", "lexls_lsi_solve_dat", "lexls_lsi_batch_solve",
@@ -67,6 +67,8 @@ def lib() -> C.CDLL:
         _lib.lexls_lse_last_consumer_kernel.argtypes = [C.c_void_p, C.c_char_p, C.c_size_t]
         _lib.lexls_lse_last_large_levels.restype = C.c_int
         _lib.lexls_lse_last_large_levels.argtypes = [C.c_void_p, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]
+        _lib.lexls_lse_last_reg_placement.restype = C.c_int
+        _lib.lexls_lse_last_reg_placement.argtypes = [C.c_void_p, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]
         _lib.lexls_lsi_batch_last_kernel.restype = C.c_char_p
         _lib.lexls_lsi_batch_last_kernel.argtypes = [C.c_void_p]
         _lib.lexls_lse_set_accuracy_guard.restype = C.c_int

@@ -55,6 +55,7 @@ struct lexls_lse_s
     bool solve_reciprocal = false; // the plan of the last factorization: a later lexls_lse_solve may use the reciprocal diagonal
     const char *last_consumer = ""; // lexls_lse_last_consumer_kernel: the variant the last post-factorization launcher took
     uint32_t large_levels[2] = {0, 0}; // lexls_lse_last_large_levels: levels of the last factorization the one-launch form committed / gave up
+    uint32_t reg_cfg = 0; // lexls_lse_last_reg_placement: what the regularized wave kernel of the last factorization was launched with (0: another kernel)
 
     double *d_in_owned;
     bool deferred_sync;       // lexls_lse_set_deferred_sync: copies are enqueued, not waited for
@@ -909,6 +910,8 @@ extern "C"
         LaunchExtras x;
         x.est = h->d_guard_est, x.ind = h->d_guard_ind;
         h->large_levels[0] = h->large_levels[1] = 0u;
+        h->reg_cfg = 0u;
+        x.reg_cfg  = &h->reg_cfg;
         if (plan.id == KernelId::large_multi)
         {
             if (!h->d_large_state) HIP_TRY(hipMalloc(&h->d_large_state, large_state_bytes(h->batch)));
@@ -1196,6 +1199,15 @@ extern "C"
         CHECK_HANDLE(h);
         if (!buf || len == 0) return fail(LEXLS_ERR_INVALID, "lexls_lse_last_consumer_kernel: no buffer");
         std::snprintf(buf, len, "%s", h->last_consumer);
+        return LEXLS_OK;
+    }
+
+    int lexls_lse_last_reg_placement(lexls_lse_t h, uint32_t *window_order, uint32_t *basis_in_lds)
+    {
+        CHECK_HANDLE(h);
+        if (!window_order || !basis_in_lds) return fail(LEXLS_ERR_INVALID, "lexls_lse_last_reg_placement: no output");
+        *window_order = h->reg_cfg & 0xffu;
+        *basis_in_lds = (h->reg_cfg >> 8) & 1u;
         return LEXLS_OK;
     }
 

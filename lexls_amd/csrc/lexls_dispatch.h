@@ -11,7 +11,8 @@
 
 // X(id, name as lexls_lse_last_kernel reports it, launcher kind, launcher).  The ORDER carries meaning: the planner reaches the variants of a
 // shape by offset (x only, + 1 factor kept, + 2 fixed variables; lqr_qtol: + 5 estimating, + 10 ragged; lsi_fused: + 3 regularized).  Kinds (lqr_small.hip): PLAIN (a, s); EST (a, s, est, count) — the
-// accuracy guard's estimating form; IND (a, s, ind) — over a list of problems; FUSED — the persistent LexLSI launch; NONE — launched by name
+// accuracy guard's estimating form; IND (a, s, ind) — over a list of problems; REG (a, s, reg_cfg) — the regularized wave kernel, which reports the
+// placement it launched with; FUSED — the persistent LexLSI launch; NONE — launched by name
 // in lexls_capi.hip (the generic kernel's and the large path's launchers take more than a table entry carries)
 #define LEXLS_KERNEL_LIST(X)                                                                                  \
     X(none, "", NONE, 0)                                                                                      \
@@ -21,8 +22,8 @@
     X(wave_41x12_f, "lqr_wave<41,12>", PLAIN, launch_wave_41x12_f)                                            \
     X(wave_64x16_x, "lqr_wave<64,16>", PLAIN, launch_wave_64x16_x)                                            \
     X(wave_64x16_f, "lqr_wave<64,16>", PLAIN, launch_wave_64x16_f)                                            \
-    X(wave_41x12_fR, "lqr_wave<41,12,regularized>", PLAIN, launch_wave_41x12_fR)                              \
-    X(wave_64x16_fR, "lqr_wave<64,16,regularized>", PLAIN, launch_wave_64x16_fR)                              \
+    X(wave_41x12_fR, "lqr_wave<41,12,regularized>", REG, launch_wave_41x12_fR)                                \
+    X(wave_64x16_fR, "lqr_wave<64,16,regularized>", REG, launch_wave_64x16_fR)                                \
     X(lwave_41x12e_x, "lqr_lwave<41,12,exact>", PLAIN, launch_lwave_41x12e_x)                                 \
     X(lwave_41x12e_f, "lqr_lwave<41,12,exact>", PLAIN, launch_lwave_41x12e_f)                                 \
     X(lwave_41x12_x, "lqr_lwave<41,12>", PLAIN, launch_lwave_41x12_x)                                         \

@@ -42,6 +42,7 @@ namespace lexls
         double *est              = nullptr; // estimating lqr_qtol: batch doubles
         uint32_t *ind            = nullptr; // ... its compaction counter (cleared); indirect lqr_quad: [count, problem list]
         const FusedCall *fused   = nullptr;
+        uint32_t *reg_cfg        = nullptr; // out, regularized lqr_wave: the reg_cfg the kernel was launched with (lexls_lse_last_reg_placement; host bookkeeping only)
     };
     /// hipErrorNotSupported for ids the table has no launcher for (none, lqr_generic, lqr_large); the persistent launch also returns it when
     /// its LDS does not fit (the caller enqueues the three kernels per stage instead)

@@ -14,6 +14,7 @@ namespace lexls
 #define LEXLS_LAUNCH_PLAIN(fn) [](const LseArgs &a, hipStream_t s, const LaunchExtras &) { hipError_t fn(const LseArgs &, hipStream_t); return fn(a, s); }
 #define LEXLS_LAUNCH_EST(fn) [](const LseArgs &a, hipStream_t s, const LaunchExtras &x) { hipError_t fn(const LseArgs &, hipStream_t, double *, uint32_t *); return fn(a, s, x.est, x.ind); }
 #define LEXLS_LAUNCH_IND(fn) [](const LseArgs &a, hipStream_t s, const LaunchExtras &x) { hipError_t fn(const LseArgs &, hipStream_t, const uint32_t *); return fn(a, s, x.ind); }
+#define LEXLS_LAUNCH_REG(fn) [](const LseArgs &a, hipStream_t s, const LaunchExtras &x) { hipError_t fn(const LseArgs &, hipStream_t, uint32_t *); return fn(a, s, x.reg_cfg); }
 #define LEXLS_LAUNCH_FUSED(fn)                                                                                                                  \
     [](const LseArgs &a, hipStream_t s, const LaunchExtras &x) {                                                                                \
         hipError_t fn(const LseArgs &, uint32_t, const int32_t *, double, double, bool, const void *, size_t, int, hipStream_t);                \

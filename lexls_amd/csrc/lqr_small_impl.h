@@ -993,7 +993,7 @@ namespace lexls
     namespace
     {
         template <int NC, int MD, bool EXACT, bool WF, bool REG = false>
-        hipError_t launch_wave_t2(const LseArgs &a, hipStream_t s)
+        hipError_t launch_wave_t2(const LseArgs &a, hipStream_t s, uint32_t *reg_cfg_out = nullptr)
         {
             const uint32_t img = wave_img_doubles<MD>(a.nVar, a.nObj);
             size_t lds         = wave_lds_bytes<NC, MD>(a.nObj, img);
@@ -1007,6 +1007,7 @@ namespace lexls
             }
             if (REG && !a.reg_scratch) return hipErrorInvalidValue;
             hipLaunchKernelGGL((lqr_wave_kernel<NC, MD, EXACT, WF, REG>), dim3(a.batch), dim3(64), lds, s, a, img, reg_cfg);
+            if (reg_cfg_out) *reg_cfg_out = reg_cfg; // (what the launch was given: lexls_lse_last_reg_placement)
             return hipGetLastError();
         }
 
@@ -1017,4 +1018,4 @@ namespace lexls
 #define LEXLS_WAVE_INSTANCE(NAME, NC, MD, EXACT, WF) \
     namespace lexls { hipError_t NAME(const LseArgs &a, hipStream_t s) { return launch_wave_t2<NC, MD, EXACT, WF>(a, s); } }
 #define LEXLS_WAVE_INSTANCE_REG(NAME, NC, MD) \
-    namespace lexls { hipError_t NAME(const LseArgs &a, hipStream_t s) { return launch_wave_t2<NC, MD, false, true, true>(a, s); } }
+    namespace lexls { hipError_t NAME(const LseArgs &a, hipStream_t s, uint32_t *reg_cfg_out) { return launch_wave_t2<NC, MD, false, true, true>(a, s, reg_cfg_out); } }

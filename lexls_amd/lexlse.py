@@ -323,6 +323,14 @@ class BatchedLexLSE:
         capi.check(capi.lib().lexls_lse_last_large_levels(self._h, C.byref(a), C.byref(r)))
         return int(a.value), int(r.value)
 
+    def last_reg_placement(self):
+        """(window_order, basis_in_lds) of the last factorization (lexls_lse_last_reg_placement): the order of the LDS window the regularized
+        wave kernel gave its routines' work matrix (0: none) and whether it kept the null-space basis in LDS; (0, False) on every other kernel
+        and without regularization"""
+        w, b = C.c_uint32(0), C.c_uint32(0)
+        capi.check(capi.lib().lexls_lse_last_reg_placement(self._h, C.byref(w), C.byref(b)))
+        return int(w.value), bool(b.value)
+
     def set_accuracy_guard(self, mode: int, threshold: float = 0.0):
         """lexls_lse_set_accuracy_guard: 0 off (default), 1 report, 2 report and re-solve the flagged problems on the bit-exact kernel
         (include/lexls_hip.h, policy comment); threshold <= 0: the calibrated default"""

@@ -57,3 +57,12 @@ def test_product_never_imports_the_oracle():
     # comments that merely cite the contract file are allowed; imports / includes / dlopen of the oracle are not
     real = [p for p in offenders if re.search(r"(import\s+oracle|from\s+oracle|liblexls_oracle|#include\s+[\"<].*oracle)", open(p, errors="ignore").read())]
     assert not real, real
+
+
+def test_reg_placement_accessor_is_exported_and_checks_its_arguments():
+    from lexls_amd import capi
+    lib = capi.lib()
+    assert "lexls_lse_last_reg_placement" in header_functions() and "lexls_lse_last_reg_placement" in capi.SYMBOLS
+    w, b = C.c_uint32(7), C.c_uint32(7)
+    assert lib.lexls_lse_last_reg_placement(None, C.byref(w), C.byref(b)) == 1  # LEXLS_ERR_INVALID: no handle
+    assert (w.value, b.value) == (7, 7)

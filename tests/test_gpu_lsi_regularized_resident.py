@@ -263,3 +263,24 @@ def test_what_stays_on_the_host(hip, oracle, par):
     b.close()
     assert name == "host"
     assert_equals_oracle(r, oracle_refs(oracle, s["n"], probs, s["factors"], **par))
+
+
+@pytest.mark.parametrize("n", [22, 29])
+@pytest.mark.parametrize("reg_type", [1, 3])
+def test_three_paths_across_the_placement_of_the_routines_pieces(hip, oracle, monkeypatch, n, reg_type):
+    """The persistent launch runs the regularized body with the placement lsi_fused_lds_bytes finds (wave_reg_lds_bytes behind its own carve-up):
+    two LexLSE levels under a simple-bounds objective on the 41 x 12 shape, at n = 22, where the launcher of lqr_wave<41,12,regularized> keeps
+    work matrix and null-space basis in LDS, and at n = 29, where type 1 keeps the window alone and type 3 loses its basis
+    (tests/reg_cases.py, switch 1): persistent launch, stages and host path give the same bits, and the oracle-backed driver's"""
+    dims, factors, count = [8, 8, 8] if n == 22 else [8, 12, 12], [0, 0.2, 0.3], 8  # (more rows than that at n = 22 and half of the instances cycle to the limit)
+    probs = [P.lsi_problem(20281000 + 100 * n + i, n, dims) for i in range(count)]
+    par = dict(regularization_factors=factors, regularization_type=reg_type)
+    b, pk = new_batch(probs, n)
+    b.run(pk, **par)
+    assert b.last_kernel() == "lsi_fused<lqr_wave<41,12,regularized>>", b.last_kernel()
+    b.close()
+    r = three_paths(monkeypatch, probs, n, **par)
+    refs = oracle_refs(oracle, n, probs, factors, regularization_type=reg_type)
+    assert_equals_oracle(r, refs)
+    plain = oracle_refs(oracle, n, probs, None)
+    assert max(np.abs(o["x"] - p["x"]).max() for o, p in zip(refs, plain)) > 1e-6  # (the factors do something)

@@ -4,6 +4,7 @@ exact, x within 1e-10; what is asserted here is stronger (bitwise equality) wher
 import numpy as np
 import pytest
 
+from factor_checks import assert_factor_equal  # noqa: F401  (other test modules import it from here as well)
 from lexls_amd import problems as P
 
 pytestmark = pytest.mark.gpu
@@ -25,20 +26,6 @@ def run_both(hip, oracle, lod, dims, nvar, maxdim=None, keep_factor=True, force_
     s.setProblem(lod)
     s.factorize_solve(keep_factor=keep_factor)
     return s, ref
-
-
-def assert_factor_equal(s, ref, dims, nvar):
-    r, fc, tr = s.getRanks()
-    np.testing.assert_array_equal(r, ref["rank"])
-    np.testing.assert_array_equal(fc, ref["fcol"])
-    np.testing.assert_array_equal(tr, ref["totalrank"])
-    np.testing.assert_array_equal(s.get_column_permutations(), ref["perm"])
-    np.testing.assert_array_equal(s.get_hh_scalars(), ref["hh"])
-    f = s.get_lexqr()
-    dims_a = np.asarray(dims)
-    m = dims_a.sum(axis=-1) if dims_a.ndim == 2 else np.full(f.shape[0], dims_a.sum())
-    for b in range(f.shape[0]):
-        np.testing.assert_array_equal(f[b, :, :m[b]], ref["factor"][b, :, :m[b]])
 
 
 def assert_factor_close(s, ref, dims, nvar, tol=1e-10):
