@@ -110,7 +110,7 @@ namespace LexLS
                 if (ObjIndex >= nObj) throw Exception("ObjIndex >= nObj");
                 typename std::vector<ConstraintInfo>::iterator it =
                     std::find(WS.begin(), WS.end(), ConstraintInfo(ObjIndex, objectives[ObjIndex].getActiveCtrIndex(CtrIndexActive)));
-                WS.erase(it);
+                if (it != WS.end()) WS.erase(it); // (the reference erases WS.end() when the entry is missing: undefined behaviour)
                 objectives[ObjIndex].deactivate(CtrIndexActive);
                 nDeactivations++;
             }
@@ -356,9 +356,7 @@ namespace LexLS
                     lexlse_rank = getTotalRank();
                     x           = lexlse.get_x();
                 }
-                for (Index k = 0; k < nObj; k++)
-                    objectives[k].phase1(x, x_guess_is_specified, parameters.modify_type_active_enabled, parameters.modify_type_inactive_enabled,
-                                         parameters.modify_x_guess_enabled, parameters.set_min_init_ctr_violation, parameters.tol_feasibility);
+                phase1_objectives();
                 if (x_guess_is_specified)
                 {
                     formLexLSE();
@@ -377,9 +375,7 @@ namespace LexLS
             {
                 if (!x_guess_is_specified) throw Exception("when use_phase1_v0 = true, x_guess has to be specified");
                 hot_start_related_tests();
-                for (Index k = 0; k < nObj; k++)
-                    objectives[k].phase1(x, x_guess_is_specified, parameters.modify_type_active_enabled, parameters.modify_type_inactive_enabled,
-                                         parameters.modify_x_guess_enabled, parameters.set_min_init_ctr_violation, parameters.tol_feasibility);
+                phase1_objectives();
                 for (Index k = 0; k < nObj; k++) objectives[k].formStep(dx);
             }
 
@@ -563,11 +559,47 @@ namespace LexLS
                 PC_DONE
             };
 
-            void phase1_objectives_then_maybe_solve()
+            /// The objectives' phase 1 (lexlsi.h:838-846 / :892-900), and the activation-order list behind it.  Objective::formInitialWorkingSet
+            /// (modify_type_active_enabled / modify_type_inactive_enabled with an x guess) activates, deactivates and re-types constraints at objective
+            /// level, behind the back of WS, the list findFirstCtrWrongSign walks.  The reference leaves WS as it was: a later removal of a
+            /// constraint activated there erases WS.end(), and under deactivate_first_wrong_sign the walk runs off the list — undefined behaviour
+            /// both.  Here WS is rebuilt behind the loop: first the entries that are still active with the type they had, in their order; then the
+            /// constraints formInitialWorkingSet activated or re-activated, objective by objective, in the order they entered the objective's
+            /// active list.  nActivations / nDeactivations are not touched and nothing is logged, as in the reference.  For modify_type_*
+            /// combined with deactivate_first_wrong_sign the reference has no defined result and this order is ours; for every other
+            /// combination x, v, the active set and the counters are the reference's.  With the flags off nothing is done.
+            void phase1_objectives()
             {
+                const bool hot = x_guess_is_specified && (parameters.modify_type_active_enabled || parameters.modify_type_inactive_enabled);
+                std::vector<ConstraintActivationType> before;
+                if (hot)
+                    for (size_t p = 0; p < WS.size(); p++)
+                        before.push_back(objectives[WS[p].get_obj_index()].getCtrType(static_cast<Index>(WS[p].get_ctr_index())));
                 for (Index k = 0; k < nObj; k++)
                     objectives[k].phase1(x, x_guess_is_specified, parameters.modify_type_active_enabled, parameters.modify_type_inactive_enabled,
                                          parameters.modify_x_guess_enabled, parameters.set_min_init_ctr_violation, parameters.tol_feasibility);
+                if (!hot) return;
+                std::vector<ConstraintInfo> order;
+                std::vector<std::vector<char>> kept(nObj);
+                for (Index k = 0; k < nObj; k++) kept[k].assign(objectives[k].getDim(), 0);
+                for (size_t p = 0; p < WS.size(); p++)
+                {
+                    const Index o = static_cast<Index>(WS[p].get_obj_index()), c = static_cast<Index>(WS[p].get_ctr_index());
+                    if (objectives[o].getCtrType(c) != CTR_INACTIVE && objectives[o].getCtrType(c) == before[p])
+                    {
+                        order.push_back(WS[p]);
+                        kept[o][c] = 1;
+                    }
+                }
+                for (Index k = 0; k < nObj; k++)
+                    for (Index a = 0; a < objectives[k].getActiveCtrCount(); a++)
+                        if (!kept[k][objectives[k].getActiveCtrIndex(a)]) order.push_back(ConstraintInfo(k, objectives[k].getActiveCtrIndex(a)));
+                WS.swap(order);
+            }
+
+            void phase1_objectives_then_maybe_solve()
+            {
+                phase1_objectives();
                 if (x_guess_is_specified)
                 {
                     formLexLSE();

@@ -352,6 +352,19 @@ int lexls_lse_set_resume_levels(lexls_lse_t h, const int32_t *h_levels);
  *   h_params9: {max_number_of_factorizations, tol_linear_dependence, tol_wrong_sign_lambda, tol_correct_sign_lambda,
  *               tol_feasibility, cycling_handling_enabled, cycling_max_counter, cycling_relax_step,
  *               deactivate_first_wrong_sign} or NULL for the defaults of typedefs.h:268-294;
+ *   h_params of the entries that take nparams: nparams == 9 holds the above; 12 adds {regularization_type, variable_regularization_factor,
+ *               max_number_of_CG_iterations}; 17 adds the hot-start options behind those, 0 / 1 each, in the order of typedefs.h:213-217:
+ *               [12] modify_x_guess_enabled (0), [13] modify_type_active_enabled (0), [14] modify_type_inactive_enabled (0),
+ *               [15] set_min_init_ctr_violation (1), [16] use_phase1_v0 (0) (defaults in brackets).  Every other count is LEXLS_ERR_INVALID.
+ *               Slots 12 .. 15 are honoured by every entry, by the device's phase 1 (lexls_lsi_batch_run_device(_ex), lexls_lsi_batch_enqueue_device)
+ *               in a setup kernel of their own; a run with the defaults launches what it always has.  use_phase1_v0 is served by every entry as well:
+ *               on the device iteration 0 runs without a factorization (dx = 0, blocking test, no removal search) in place of the first stage.
+ *               Without x0 every entry answers LEXLS_ERR_INVALID ("when use_phase1_v0 = true, x_guess has to be specified") before any device
+ *               work.  A run that an entry refuses without the options is refused with them, with the same code.  Activation order: modify_type_* lets phase 1 activate and re-type constraints behind the list
+ *               deactivate_first_wrong_sign walks; the reference leaves that list stale (its walk and its erase are then undefined).  Here the
+ *               list is rebuilt behind phase 1: the entries still active with their type, in their order, then the constraints phase 1 activated,
+ *               objective by objective in working-set order.  For modify_type_* with deactivate_first_wrong_sign this order is ours; for every
+ *               other combination x, v, the active set and h_info6 are the reference's;
  *   outputs: h_x[nVar]; h_info6 = {status, iterations, activations, deactivations, factorizations, total_rank};
  *            h_active[sum(dims)] final working set; h_v[sum(dims)] constraint violations (either may be NULL). */
 int lexls_lsi_solve(int device, uint32_t nVar, uint32_t nObj, const uint32_t *h_dims, const int32_t *h_types, const double *h_data,
@@ -368,7 +381,8 @@ int lexls_lsi_batch_solve(int device, uint32_t batch, uint32_t nVar, uint32_t nO
                           const double *h_data, const uint32_t *h_var_index, const uint8_t *h_active_guess, const double *h_x0,
                           const double *h_params9, double *h_x, int32_t *h_info6, uint8_t *h_active, double *h_v, int32_t *h_rounds2);
 /* lexls_lsi_batch_solve with the regularization inputs of lexls_lsi_solve_ex: h_reg_factors = one factor per objective, shared by the batch,
- * or NULL; h_params with nparams == 9 or 12 (+ regularization_type, variable_regularization_factor, max_number_of_CG_iterations).
+ * or NULL; h_params with nparams == 9, 12 (+ regularization_type, variable_regularization_factor, max_number_of_CG_iterations) or 17 (+ the
+ * hot-start options, see lexls_lsi_solve).
  * Regularized batches (every regularization_type but the experimental 7) run their active-set iterations resident on the device like plain ones,
  * on the REG instantiations of the register-resident l-QR where the shape has one ("How a run executes" below); type 7 and the other shapes
  * keep the host-driven lock-step stages, their factorizations on the generic kernel. */
@@ -679,7 +693,8 @@ int lexls_lsi_batch_get_working_set_log(lexls_lsi_batch_t b, int32_t *h_log, dou
 int lexls_lsi_batch_working_set_log_device(lexls_lsi_batch_t b, void **d_log, void **d_alpha, void **d_counts);
 /* lexls_lsi_solve plus what the MEX front end also passes (interfaces/matlab-octave/lexlsi.cpp:527-625): h_v0 = initial residuals,
  * sum(dims) doubles (set_v0 per objective) or NULL; h_reg_factors = one regularization factor per objective or NULL; h_params with
- * nparams == 9 (as lexls_lsi_solve) or 12: + regularization_type, variable_regularization_factor, max_number_of_CG_iterations. */
+ * nparams == 9 (as lexls_lsi_solve), 12: + regularization_type, variable_regularization_factor, max_number_of_CG_iterations, or 17: + the five
+ * hot-start options (the 17-slot form, described at lexls_lsi_solve). */
 int lexls_lsi_solve_ex(int device, uint32_t nVar, uint32_t nObj, const uint32_t *h_dims, const int32_t *h_types, const double *h_data,
                        const uint32_t *h_var_index, const uint8_t *h_active_guess, const double *h_x0, const double *h_v0,
                        const double *h_reg_factors, const double *h_params, uint32_t nparams, double *h_x, int32_t *h_info6, uint8_t *h_active,

@@ -7,7 +7,8 @@
 namespace
 {
     /// p[0..9): see lexls_lsi_solve; p[9..12) (only read when nparams >= 12): regularization_type, variable_regularization_factor,
-    /// max_number_of_CG_iterations (typedefs.h:185-187)
+    /// max_number_of_CG_iterations (typedefs.h:185-187); p[12..17) (only read when nparams == 17): modify_x_guess_enabled, modify_type_active_enabled,
+    /// modify_type_inactive_enabled, set_min_init_ctr_violation, use_phase1_v0 (typedefs.h:213-217), 0 / 1 each
     ParametersLexLSI unpack(const double *p, uint32_t nparams = 9)
     {
         ParametersLexLSI par;
@@ -28,8 +29,25 @@ namespace
                 par.variable_regularization_factor = p[10];
                 par.max_number_of_CG_iterations    = static_cast<Index>(p[11]);
             }
+            if (nparams >= 17) // the hot-start options, 0 / 1 each, in the order of typedefs.h:213-217
+            {
+                par.modify_x_guess_enabled       = p[12] != 0;
+                par.modify_type_active_enabled   = p[13] != 0;
+                par.modify_type_inactive_enabled = p[14] != 0;
+                par.set_min_init_ctr_violation   = p[15] != 0;
+                par.use_phase1_v0                = p[16] != 0;
+            }
         }
         return par;
+    }
+
+    /// use_phase1_v0 without x0 at the entries whose phase 1 is device work: the reference's own complaint (lexlsi.h:882), before any device work — nothing
+    /// is launched, the outputs stay as they are
+    int refuse_phase1_v0(const ParametersLexLSI &par, bool has_x0)
+    {
+        if (!par.use_phase1_v0 || has_x0) return LEXLS_OK;
+        lexls_internal_set_error("when use_phase1_v0 = true, x_guess has to be specified");
+        return LEXLS_ERR_INVALID;
     }
 
     /// runs f and reports what it throws through lexls_last_error()
@@ -92,7 +110,7 @@ extern "C"
         return guarded([&]() {
             if (!b) throw Exception("lexls_lsi_batch_run: null handle");
             b->refuse_pending("lexls_lsi_batch_run");
-            if (h_params && nparams != 9 && nparams != 12) throw Exception("lexls_lsi_batch_solve_ex: 9 or 12 parameters expected"); // (the name its callers have always seen)
+            if (h_params && nparams != 9 && nparams != 12 && nparams != 17) throw Exception("lexls_lsi_batch_solve_ex: 9, 12 or 17 parameters expected"); // (the name its callers have always seen)
             const ParametersLexLSI par = unpack(h_params, nparams);
             if (const int refused = b->refuse_masked_run("lexls_lsi_batch_run")) return refused; // (nothing launched, the outputs as they are)
             if (const int refused = b->refuse_limited_run("lexls_lsi_batch_run")) return refused;
@@ -116,11 +134,12 @@ extern "C"
         return guarded([&]() {
             if (!b) throw Exception("lexls_lsi_batch_run_device: null handle");
             b->refuse_pending("lexls_lsi_batch_run_device");
-            if (h_params && nparams != 9 && nparams != 12) throw Exception("lexls_lsi_batch_run_device: 9 or 12 parameters expected");
+            if (h_params && nparams != 9 && nparams != 12 && nparams != 17) throw Exception("lexls_lsi_batch_run_device: 9, 12 or 17 parameters expected");
             if (!d_data || !d_x) throw Exception("lexls_lsi_batch_run_device: null data / x");
             if (b->off && !d_var_index) throw Exception("lexls_lsi_batch_run_device: a simple-bounds objective needs variable indices");
             const ParametersLexLSI par = unpack(h_params, nparams);
             if (const int refused = b->refuse_run("lexls_lsi_batch_run_device", h_reg_factors, par, false)) return refused;
+            if (const int refused = refuse_phase1_v0(par, d_x0 != NULL)) return refused;
             if (!b->would_be_resident(par)) // no detour over the host: nothing is launched, the outputs stay as they are
             {
                 lexls_internal_set_error("lexls_lsi_batch_run_device: only runs that are resident on the device are served (not: LEXLS_LSI_RESIDENT=0, LEXLS_LSI_HOST_STAGING, "
@@ -147,11 +166,12 @@ extern "C"
     {
         return guarded([&]() {
             if (!b) throw Exception("lexls_lsi_batch_enqueue_device: null handle");
-            if (h_params && nparams != 9 && nparams != 12) throw Exception("lexls_lsi_batch_enqueue_device: 9 or 12 parameters expected");
+            if (h_params && nparams != 9 && nparams != 12 && nparams != 17) throw Exception("lexls_lsi_batch_enqueue_device: 9, 12 or 17 parameters expected");
             if (!d_data || !d_x) throw Exception("lexls_lsi_batch_enqueue_device: null data / x");
             if (b->off && !d_var_index) throw Exception("lexls_lsi_batch_enqueue_device: a simple-bounds objective needs variable indices");
             const ParametersLexLSI par = unpack(h_params, nparams);
             if (const int refused = b->refuse_run("lexls_lsi_batch_enqueue_device", h_reg_factors, par, false)) return refused;
+            if (const int refused = refuse_phase1_v0(par, d_x0 != NULL)) return refused;
             if (!b->would_be_fused(par)) // no detour: nothing is enqueued, the outputs stay as they are
             {
                 lexls_internal_set_error("lexls_lsi_batch_enqueue_device: only runs that lexls_lsi_batch_run_device serves and whose resident iterations are one persistent launch "
@@ -298,7 +318,7 @@ extern "C"
                            double *h_v)
     {
         return guarded([&]() {
-            if (h_params && nparams != 9 && nparams != 12) throw Exception("lexls_lsi_solve_ex: 9 or 12 parameters expected");
+            if (h_params && nparams != 9 && nparams != 12 && nparams != 17) throw Exception("lexls_lsi_solve_ex: 9, 12 or 17 parameters expected");
             internal::LexLSI lsi;
             solve_one(lsi, device, {nVar, nObj, h_dims, h_types, h_data, h_var_index, h_active_guess, h_x0, h_v0, h_reg_factors}, unpack(h_params, nparams), h_x, h_info6, h_active, h_v);
             return LEXLS_OK;
@@ -311,7 +331,7 @@ extern "C"
                               double *h_v, const lexls_lsi_debug *debug)
     {
         return guarded([&]() {
-            if (h_params && nparams != 9 && nparams != 12) throw Exception("lexls_lsi_solve_debug: 9 or 12 parameters expected");
+            if (h_params && nparams != 9 && nparams != 12 && nparams != 17) throw Exception("lexls_lsi_solve_debug: 9, 12 or 17 parameters expected");
             if (!debug) throw Exception("lexls_lsi_solve_debug: debug is NULL (use lexls_lsi_solve_ex)");
             const runner::LsiProblem p = {nVar, nObj, h_dims, h_types, h_data, h_var_index, h_active_guess, h_x0, h_v0, h_reg_factors};
             ParametersLexLSI par        = unpack(h_params, nparams);

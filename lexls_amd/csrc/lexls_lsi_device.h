@@ -385,7 +385,10 @@ namespace
     /// stops), the counters, the next equality problem.  The removal search's verdict (a.sens) is read only when the step was not blocked —
     /// a caller that runs the search between the two halves may skip it for a blocked step, as the reference does (lexlsi.h:1181-1232).
     /// RELOAD: the working-set lists are not in LDS any more (something else used it since lsi_iterate_step)
-    template <bool RELOAD>
+    /// V0: iteration 0 of a use_phase1_v0 run (lexlsi.h: begin() -> phase1_v0, iteration_prepare with nIterations == 0): no equality problem was solved —
+    /// no factorization is counted, the rank is 0, there is no removal search (it_normal = false: a.sens is not read) and a step that is not
+    /// blocked changes nothing and ends nothing; nothing of an earlier factorization may be read back (resume level 0)
+    template <bool RELOAD, bool V0 = false>
     __device__ __forceinline__ void lsi_iterate_finish(const ResidentArgs &a, const uint32_t b, const uint32_t wib, const StepVerdict &verdict)
     {
         const uint32_t lane  = threadIdx.x & 63u;
@@ -401,8 +404,8 @@ namespace
         const int blk_obj       = verdict.blk_obj;
         const uint32_t blk_ctr  = verdict.blk_ctr, blk_type = verdict.blk_type;
         const bool blocked      = blk_obj >= 0;
-        const int32_t found_i = blocked ? 0 : a.sens[(size_t)b * 3];
-        int32_t rm_pos = blocked ? -1 : a.sens[(size_t)b * 3 + 1], rm_lvl = blocked ? -2 : a.sens[(size_t)b * 3 + 2];
+        const int32_t found_i = (blocked || V0) ? 0 : a.sens[(size_t)b * 3];
+        int32_t rm_pos = (blocked || V0) ? -1 : a.sens[(size_t)b * 3 + 1], rm_lvl = (blocked || V0) ? -2 : a.sens[(size_t)b * 3 + 2];
         if (a.first_wrong_sign && found_i != 0) // (wave-uniform)
         {
             // findFirstCtrWrongSign (lexlsi.h:1034-1046) over the set: row i of LexLSE level k is the i-th active constraint of objective k + off, fixed
@@ -432,9 +435,9 @@ namespace
             rm_pos = __builtin_amdgcn_readlane(best_pos, win);
             rm_lvl = __builtin_amdgcn_readlane(best_lvl, win);
         }
-        const int32_t nfact   = info[4] + 1; // lexlsi.h:1172
+        const int32_t nfact   = info[4] + (V0 ? 0 : 1); // lexlsi.h:1172
         const int32_t niter = info[1], nact = info[2], ndeact = info[3];
-        const uint32_t trank = a.totalrank[b];
+        const uint32_t trank = V0 ? 0u : a.totalrank[b];
         (void)n;
 
         // ---- one working-set change (lexlsi.h:1181-1232) and the counters; lane 0 on the LDS copy ----
@@ -462,7 +465,7 @@ namespace
             cyc_stop  = circle && cyc[CYC_COUNT] >= a.cycling_max_counter; // PROBLEM_SOLVED_CYCLING_HANDLING: tested before the factorization limit (lexlsi.h:650-658)
             cyc_relax = circle && !cyc_stop;
         }
-        const bool done = (!blocked && !removed) || cyc_stop || nfact >= resident_max_factorizations(a, b); // lexlsi.h:236-240
+        const bool done = (!V0 && !blocked && !removed) || cyc_stop || nfact >= resident_max_factorizations(a, b); // lexlsi.h:236-240
         if (lane == 0)
         {
             // WorkingSetLogEntry (lexlsi.h:1188-1194 ADD, :1214-1222 REMOVE), before the lists change: an ADD is the blocking triple at step length
@@ -524,12 +527,12 @@ namespace
             // simple-bounds objective changes the fixed variables: everything again.
             if (a.resume)
             {
-                const int32_t K = blocked ? (blk_obj >= (int)a.off ? blk_obj - (int)a.off : 0) : (removed && rm_lvl > 0 ? rm_lvl : 0);
+                const int32_t K = V0 ? 0 : (blocked ? (blk_obj >= (int)a.off ? blk_obj - (int)a.off : 0) : (removed && rm_lvl > 0 ? rm_lvl : 0));
                 a.resume[b]     = K;
-                if (!done) info[6] += K, info[7] += 1;
+                if (!done && !V0) info[6] += K, info[7] += 1;
             }
             info[0] = cyc_stop ? (int32_t)PROBLEM_SOLVED_CYCLING_HANDLING
-                               : ((!blocked && !removed) ? (int32_t)PROBLEM_SOLVED : (done ? (int32_t)MAX_NUMBER_OF_FACTORIZATIONS_EXCEEDED : info[0]));
+                               : ((!V0 && !blocked && !removed) ? (int32_t)PROBLEM_SOLVED : (done ? (int32_t)MAX_NUMBER_OF_FACTORIZATIONS_EXCEEDED : info[0]));
             info[1] = niter + 1;
             info[2] = nact + (blocked ? 1 : 0);
             info[3] = ndeact + (removed ? 1 : 0);

@@ -688,6 +688,7 @@ struct lexls_lsi_batch_s
              const double *h_reg_factors, const ParametersLexLSI &par_, double *h_x, int32_t *h_info6, uint8_t *h_active, double *h_v, int32_t *h_rounds2)
     {
         if (!h_data || !h_x) throw Exception("lexls_lsi_batch_run: null data / x");
+        if (par_.use_phase1_v0 && !h_x0) throw Exception("when use_phase1_v0 = true, x_guess has to be specified"); // (lexlsi.h:882, before any work)
         const ParametersLexLSI par = with_log_switch(par_);
         begin_working_set_log();
         lam_rc  = -1;
@@ -1082,6 +1083,7 @@ struct lexls_lsi_batch_s
         const uint32_t dim0    = off ? dims[0] : 0u;
         const int32_t max_fact = static_cast<int32_t>(r.par.max_number_of_factorizations);
         if (dim0 && !var) throw Exception("lexls_lsi_batch_run: a simple-bounds objective needs variable indices");
+        if (r.par.use_phase1_v0 && !x0) throw Exception("when use_phase1_v0 = true, x_guess has to be specified"); // (the entry points have said so already)
         for (uint32_t g = 0; g < nGroups; g++)
         {
             BatchCtx &ctx              = *grp[g];
@@ -1092,7 +1094,7 @@ struct lexls_lsi_batch_s
             const uint8_t *gg = guess ? guess + (size_t)lo[g] * total : NULL;
             const double *xg  = x0 ? x0 + (size_t)lo[g] * nVar : NULL;
             ctx.enqueue_phase1_setup(dev ? xg : ctx.stage_x0(xg), dev ? gg : ctx.stage_guess(gg), lo[g], max_fact, v0 ? v0 + (size_t)lo[g] * total : NULL, NULL,
-                                     dev ? group_mask(g) : NULL, dev ? group_limits(g) : NULL, dev ? group_obj_dims(g) : NULL); // (mask, limits and row counts are the device entries' alone: lexls_lsi_batch_run is refused while one is set)
+                                     dev ? group_mask(g) : NULL, dev ? group_limits(g) : NULL, dev ? group_obj_dims(g) : NULL, p1_hot_word(r.par)); // (mask, limits and row counts are the device entries' alone: lexls_lsi_batch_run is refused while one is set)
         }
         r.t_ctx = BatchCtx::now() - r.t_begin;
         uint32_t fault = 0xffffffffu;
@@ -1103,7 +1105,11 @@ struct lexls_lsi_batch_s
         }
         if (fault != 0xffffffffu) // nothing else is launched for this run
             throw Exception("lexls_lsi_batch_run: instance " + std::to_string(fault >> 3) + ": " + p1_fault_text(fault & 7u));
-        for (uint32_t g = 0; g < nGroups; g++) grp[g]->enqueue_phase1_stage(x0 != NULL, r.par.tol_wrong_sign_lambda, r.par.tol_correct_sign_lambda, max_fact);
+        for (uint32_t g = 0; g < nGroups; g++)
+            if (r.par.use_phase1_v0)
+                grp[g]->enqueue_phase1_v0(max_fact);
+            else
+                grp[g]->enqueue_phase1_stage(x0 != NULL, r.par.tol_wrong_sign_lambda, r.par.tol_correct_sign_lambda, max_fact, true, p1_hot_word(r.par));
         r.t_setup = BatchCtx::now() - r.t_begin;
         std::vector<char> going(nGroups, 0), went(nGroups, 0);
         bool more = false;
@@ -1269,10 +1275,13 @@ struct lexls_lsi_batch_s
             if (dim0 && hipMemcpyAsync(ctx.d_rvar, dev.var_index + (size_t)lo[g] * dim0, 4 * (size_t)ctx.B * dim0, hipMemcpyDeviceToDevice, ctx.stream) != hipSuccess)
                 throw Exception("copy of the variable indices failed");
             ctx.enqueue_phase1_setup(dev.x0 ? dev.x0 + (size_t)lo[g] * nVar : NULL, dev.active_guess ? dev.active_guess + (size_t)lo[g] * total : NULL, lo[g], max_fact,
-                                     dev.v0 ? dev.v0 + (size_t)lo[g] * total : NULL, as.d_fault, group_mask(g), group_limits(g), group_obj_dims(g));
+                                     dev.v0 ? dev.v0 + (size_t)lo[g] * total : NULL, as.d_fault, group_mask(g), group_limits(g), group_obj_dims(g), p1_hot_word(par));
             const bool keep_fixed_bounds = lam_rc_after(par) == LEXLS_OK;
             ctx.enqueue_phase1_gate(as.d_fault, max_fact);
-            ctx.enqueue_phase1_stage(dev.x0 != NULL, par.tol_wrong_sign_lambda, par.tol_correct_sign_lambda, max_fact, false);
+            if (par.use_phase1_v0)
+                ctx.enqueue_phase1_v0(max_fact, false);
+            else
+                ctx.enqueue_phase1_stage(dev.x0 != NULL, par.tol_wrong_sign_lambda, par.tol_correct_sign_lambda, max_fact, false, p1_hot_word(par));
             ctx.enqueue_fused(par.tol_wrong_sign_lambda, par.tol_correct_sign_lambda, max_fact);
             ctx.scatter_results(dev.x + (size_t)lo[g] * nVar, dev.info6 ? dev.info6 + (size_t)lo[g] * 6 : NULL, dev.active ? dev.active + (size_t)lo[g] * total : NULL,
                                 dev.v ? dev.v + (size_t)lo[g] * total : NULL, keep_fixed_bounds, dev.cycling_counts ? dev.cycling_counts + lo[g] : NULL, as.d_fault, g == 0 ? d_status : NULL, group_mask(g));

@@ -600,8 +600,9 @@ namespace
         /// for this run into d_inst_limit, which every later kernel of the run reads (resident_args)
         /// d_obj_dims (lexls_lsi_batch_set_instance_obj_dims): this group's rows of the caller's counts (B x nObj) or NULL; the kernel checks them against
         /// the capacities and copies them into d_inst_dims, likewise
+        /// hot (P1_HOT_*, lsi_phase1_setup.h): the run's hot-start options where they act — with d_x0 and without d_v0; 0: lsi_phase1_setup_kernel as ever
         void enqueue_phase1_setup(const double *d_x0, const uint8_t *d_guess, uint32_t first, int32_t max_factorizations, const double *d_v0 = NULL, uint32_t *run_fault = NULL,
-                                  const uint8_t *d_mask = NULL, const int32_t *d_limits = NULL, const uint32_t *d_obj_dims = NULL)
+                                  const uint8_t *d_mask = NULL, const int32_t *d_limits = NULL, const uint32_t *d_obj_dims = NULL, uint32_t hot = 0)
         {
             const double t0 = now();
             if (!d_p1_fault && !run_fault)
@@ -616,8 +617,12 @@ namespace
             Phase1Args pa;
             pa.ra = resident_args(max_factorizations);
             pa.x0 = d_x0, pa.guess = d_guess, pa.v0 = d_v0, pa.fault = run_fault ? run_fault : d_p1_fault, pa.first = first, pa.mask = d_mask, pa.limits = d_limits, pa.obj_dims = d_obj_dims;
+            pa.hot = (d_x0 && !d_v0) ? hot : 0u;
             if (!run_fault && hipMemsetAsync(d_p1_fault, 0xff, 16, stream) != hipSuccess) throw Exception("hipMemsetAsync failed (phase 1 on the device)");
-            hipLaunchKernelGGL(lsi_phase1_setup_kernel, dim3((B + 3) / 4), dim3(256), 4 * resident_lds_per_wave(rshape.SD, rshape.total) + (d_obj_dims ? P1_COUNTS_LDS : 0), stream, pa);
+            if (pa.hot)
+                hipLaunchKernelGGL(lsi_phase1_setup_hot_kernel, dim3((B + 3) / 4), dim3(256), 4 * resident_lds_per_wave(rshape.SD, rshape.total) + (d_obj_dims ? P1_COUNTS_LDS : 0), stream, pa);
+            else
+                hipLaunchKernelGGL(lsi_phase1_setup_kernel, dim3((B + 3) / 4), dim3(256), 4 * resident_lds_per_wave(rshape.SD, rshape.total) + (d_obj_dims ? P1_COUNTS_LDS : 0), stream, pa);
             if (hipGetLastError() != hipSuccess || (!run_fault && hipMemcpyAsync(p1_fault_host.data(), d_p1_fault, 4, hipMemcpyDeviceToHost, stream) != hipSuccess))
                 throw Exception("lsi_phase1_setup_kernel launch failed");
             t_enqueue += now() - t0;
@@ -639,20 +644,9 @@ namespace
             rounds_resident++, rounds_fs++, rounds_sens++;
             resident_kernel = lexls_lse_last_kernel(h);
         }
-        /// second half: the stage of every resident iteration on the first problem — row gather + l-QR, the speculative removal search — and
-        /// lsi_phase1_finish_kernel (iteration 0).  Every instance is resident from here on; the count of stopped instances comes back
-        /// (poll = false, lexls_lsi_batch_enqueue_device: nobody waits for the count)
-        void enqueue_phase1_stage(bool has_x0, double tolW, double tolC, int32_t max_factorizations, bool poll = true)
+        /// the books behind a device phase 1 (enqueue_phase1_stage, enqueue_phase1_v0): every instance is resident, iteration 0 was phase 1's
+        void every_instance_resident_behind_iteration_0()
         {
-            const double t0       = now();
-            const ResidentArgs ra = resident_args(max_factorizations);
-            hip_check(lexls_internal_round_resident(h, rshape.dim0 ? 1 : 0)); // (no resume levels: nothing has been factorized yet)
-            hip_check(lexls_lse_factorize_solve(h, 1));
-            hip_check(first_wrong_sign ? lexls_lse_sensitivity_collect_resident(h, tolW, tolC) : lexls_lse_sensitivity_resident(h, tolW, tolC));
-            hipLaunchKernelGGL(lsi_phase1_finish_kernel, dim3((B + 3) / 4), dim3(256), 4 * resident_lds_per_wave(rshape.SD, rshape.total), stream, ra, has_x0 ? 1u : 0u);
-            if (hipGetLastError() != hipSuccess) throw Exception("lsi_phase1_finish_kernel launch failed");
-            rounds_fs++, rounds_sens++;
-            if (poll && hipMemcpyAsync(fin_host.data(), rl.finished(d_rws), 4, hipMemcpyDeviceToHost, stream) != hipSuccess) throw Exception("hipMemcpyAsync failed (finished count)");
             std::fill(is_resident.begin(), is_resident.end(), 1);
             n_resident      = B;
             rounds_resident = 0;
@@ -660,6 +654,37 @@ namespace
             rounds_fs_at_handover   = rounds_fs;
             rounds_sens_at_handover = rounds_sens;
             iterations_at_handover.assign(B, 1); // iteration 0 belongs to phase 1
+        }
+        /// second half: the stage of every resident iteration on the first problem — row gather + l-QR, the speculative removal search — and
+        /// lsi_phase1_finish_kernel (iteration 0).  Every instance is resident from here on; the count of stopped instances comes back
+        /// (poll = false, lexls_lsi_batch_enqueue_device: nobody waits for the count)
+        /// hot: as enqueue_phase1_setup's; without x0 the state is formed here, and P1_HOT_V_MIDPOINT is the one option that acts on it
+        void enqueue_phase1_stage(bool has_x0, double tolW, double tolC, int32_t max_factorizations, bool poll = true, uint32_t hot = 0)
+        {
+            const double t0       = now();
+            const ResidentArgs ra = resident_args(max_factorizations);
+            hip_check(lexls_internal_round_resident(h, rshape.dim0 ? 1 : 0)); // (no resume levels: nothing has been factorized yet)
+            hip_check(lexls_lse_factorize_solve(h, 1));
+            hip_check(first_wrong_sign ? lexls_lse_sensitivity_collect_resident(h, tolW, tolC) : lexls_lse_sensitivity_resident(h, tolW, tolC));
+            if (!has_x0 && (hot & P1_HOT_V_MIDPOINT))
+                hipLaunchKernelGGL(lsi_phase1_finish_hot_kernel, dim3((B + 3) / 4), dim3(256), 4 * resident_lds_per_wave(rshape.SD, rshape.total), stream, ra, 0u);
+            else
+                hipLaunchKernelGGL(lsi_phase1_finish_kernel, dim3((B + 3) / 4), dim3(256), 4 * resident_lds_per_wave(rshape.SD, rshape.total), stream, ra, has_x0 ? 1u : 0u);
+            if (hipGetLastError() != hipSuccess) throw Exception("lsi_phase1_finish_kernel launch failed");
+            rounds_fs++, rounds_sens++;
+            if (poll && hipMemcpyAsync(fin_host.data(), rl.finished(d_rws), 4, hipMemcpyDeviceToHost, stream) != hipSuccess) throw Exception("hipMemcpyAsync failed (finished count)");
+            every_instance_resident_behind_iteration_0();
+            t_enqueue += now() - t0;
+        }
+        /// use_phase1_v0: in the place of enqueue_phase1_stage — no factorization, no removal search, lsi_phase1_v0_kernel (iteration 0 on dx = 0)
+        void enqueue_phase1_v0(int32_t max_factorizations, bool poll = true)
+        {
+            const double t0       = now();
+            const ResidentArgs ra = resident_args(max_factorizations);
+            hipLaunchKernelGGL(lsi_phase1_v0_kernel, dim3((B + 3) / 4), dim3(256), 4 * resident_lds_per_wave(rshape.SD, rshape.total), stream, ra);
+            if (hipGetLastError() != hipSuccess) throw Exception("lsi_phase1_v0_kernel launch failed");
+            if (poll && hipMemcpyAsync(fin_host.data(), rl.finished(d_rws), 4, hipMemcpyDeviceToHost, stream) != hipSuccess) throw Exception("hipMemcpyAsync failed (finished count)");
+            every_instance_resident_behind_iteration_0();
             t_enqueue += now() - t0;
         }
         /// x / info / active / v of this group's instances from the slabs into device arrays of the caller (d_info6 / d_active / d_v may be NULL);

@@ -1,6 +1,7 @@
 // Phase 1 of a lock-step LexLSI batch as device work (lsi_batch.h: run_phase1_device): what the host worker pool otherwise does over host LexLSI
-// objects in front of the first resident stage.  With the default modify_* parameters and set_min_init_ctr_violation = true (the C ABI has no
-// slot for others) it is
+// objects in front of the first resident stage.  With the default modify_* parameters and set_min_init_ctr_violation = true it is the three steps
+// below; other values of those four (h_params slots 12 .. 15) make lsi_phase1_setup_hot_kernel the first of them, which repairs the working set of
+// the guess against x0 (lsi_phase1_setup.h: p1_hot_working_set) before it forms the state.  use_phase1_v0 (slot 16) puts lsi_phase1_v0_kernel in the place of the second and third step: iteration 0 without a factorization
 //     lsi_phase1_setup_kernel   checks, working set, stamps, counters, [x | v | A x] from x0, the first equality problem
 //     l-QR + removal search     the stage every resident iteration runs (lexls_lse_factorize_solve, lexls_lse_sensitivity_*_resident)
 //     lsi_phase1_finish_kernel  without x0: x = x_lse, A x, v; then iteration 0 = lsi_iterate_body, the resident iteration itself
@@ -21,6 +22,7 @@ namespace
         const uint8_t *mask;  // B bytes, or NULL (lexls_lsi_batch_set_instance_mask): 0 = the instance is skipped in this run
         const int32_t *limits; // B words, or NULL (lexls_lsi_batch_set_instance_max_factorizations): the instance's own factorization limit, <= 0 = none
         const uint32_t *obj_dims; // B x nObj words, or NULL (lexls_lsi_batch_set_instance_obj_dims): the rows every objective of the instance has, <= sh.dim[k]
+        uint32_t hot;             // P1_HOT_* (lsi_phase1_setup.h): the run's hot-start options, 0 = the defaults (lsi_phase1_setup_kernel; else lsi_phase1_setup_hot_kernel)
     };
 
     /// byte b of an instance mask (NULL: every instance is solved).  The bytes are the caller's, rewritten in place between two runs and between two
@@ -48,7 +50,8 @@ namespace
     /// v0 (the instance's total doubles, or NULL): Objective::phase1 with v0_is_specified — A x is formed, initialize_v0 is not run, v is v0
     /// RAGGED, cnt: the instance's row counts (p1_rows) — the v and A x of an absent row are 0 (the slab may hold an earlier run's), nothing of it is
     /// read.  Without RAGGED cnt is not looked at, as in lsi_step_wave
-    template <bool RAGGED = false>
+    /// HOT: set_min_init_ctr_violation = false (P1_HOT_V_MIDPOINT) — the inactive rows take p1_initial_v's other branch (objective.h:188-191)
+    template <bool RAGGED = false, bool HOT = false>
     __device__ __forceinline__ void lsi_phase1_state(const StepShape &sh, const double *data, const uint32_t *var_b, const double *x_s, const uint8_t *cs, double *st,
                                                      const double *v0 = nullptr, const uint32_t *cnt = nullptr)
     {
@@ -86,6 +89,8 @@ namespace
             double v;
             if (v0)
                 v = v0[g];
+            else if (HOT)
+                v = p1_initial_v(t, ax, lb, ub, true, sh.tol_feasibility);
             else if (t == CTR_ACTIVE_LB)
                 v = ax - lb;
             else if (t == CTR_ACTIVE_UB)
@@ -107,7 +112,10 @@ namespace
     constexpr size_t P1_COUNTS_LDS = 4 * 4 * (size_t)STEP_MAX_OBJ;
 
     /// RAGGED: the run has row counts (p.obj_dims != NULL).  Without it nothing of them is compiled in: the kernel a batch without counts has always run
-    template <bool RAGGED>
+    /// HOT: the run's hot-start options are not the defaults (p.hot != 0).  With an x0 and no v0 lane 0 runs p1_hot_working_set behind the working set
+    /// of the guess — on the copy of x0 in LDS, which P1_HOT_MODIFY_X rewrites; the caller's x0, guess and v0 are only read — and the state is formed
+    /// from that copy.  Without HOT nothing of it is compiled in
+    template <bool RAGGED, bool HOT = false>
     __device__ __forceinline__ void lsi_phase1_setup_body(const Phase1Args &p)
     {
         const ResidentArgs &a = p.ra;
@@ -204,10 +212,20 @@ namespace
         asm volatile("" ::: "memory");
 
         // ---- the working set: one lane, in the reference's order ----
+        const bool repair = HOT && p.x0 && !p.v0 && (p.hot & (P1_HOT_MODIFY_X | P1_HOT_TYPE_ACTIVE | P1_HOT_TYPE_INACTIVE)); // (uniform over the launch)
+        if constexpr (HOT)
+            if (repair)
+            {
+                for (uint32_t j = lane; j < n; j += 64) v.dx_s[j] = p.x0[(size_t)b * n + j];
+                __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
+                asm volatile("" ::: "memory");
+            }
         if (lane == 0)
         {
             uint32_t next = 0;
             p1_build_working_set<RAGGED>(sh, cls, guess, v.cs, v.act, v.ina, v.ipos, v.na, stamp_s, &next, cnt);
+            if constexpr (HOT)
+                if (repair) p1_hot_working_set<RAGGED>(sh, v.data, v.var, v.dx_s, p.hot, v.cs, v.act, v.ina, v.ipos, v.na, stamp_s, &next, cls, cnt); // (cls is read no more: the marks)
             a.next_stamp[b] = next;
             a.alive[b]      = 1;
             a.skip[b]       = 0;
@@ -236,11 +254,15 @@ namespace
         // ---- [x | v | A x] of a given x0 (without one: after the first solve, lsi_phase1_finish_kernel) ----
         if (p.x0)
         {
-            for (uint32_t j = lane; j < n; j += 64) v.dx_s[j] = p.x0[(size_t)b * n + j];
+            if (!repair) // (with it the copy is there already, and may have been rewritten)
+                for (uint32_t j = lane; j < n; j += 64) v.dx_s[j] = p.x0[(size_t)b * n + j];
             __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
             asm volatile("" ::: "memory");
             const double *v0 = p.v0 ? p.v0 + (size_t)b * total : nullptr;
-            lsi_phase1_state<RAGGED>(sh, v.data, v.var, v.dx_s, v.cs, v.st, v0, cnt);
+            if (HOT && (p.hot & P1_HOT_V_MIDPOINT))
+                lsi_phase1_state<RAGGED, HOT>(sh, v.data, v.var, v.dx_s, v.cs, v.st, v0, cnt);
+            else
+                lsi_phase1_state<RAGGED>(sh, v.data, v.var, v.dx_s, v.cs, v.st, v0, cnt);
         }
 
         // ---- the first equality problem ----
@@ -256,10 +278,21 @@ namespace
             lsi_phase1_setup_body<false>(p);
     }
 
+    /// ... of a run whose hot-start options are not the defaults (Phase1Args::hot != 0): a kernel of its own, so that the one above stays what it is
+    __global__ __launch_bounds__(256) void lsi_phase1_setup_hot_kernel(Phase1Args p)
+    {
+        if (p.obj_dims) // (uniform over the launch)
+            lsi_phase1_setup_body<true, true>(p);
+        else
+            lsi_phase1_setup_body<false, true>(p);
+    }
+
     /// behind the first factorization and its removal search: iteration 0.  has_x0 == 0: phase 1 takes x = x_lse first (lexlsi.h:350-357), the step
     /// that follows is then dx = 0.  The rest is the resident iteration: nFactorizations = 1, the blocking test or the removal, iteration_finish
     /// with its termination tests, the next equality problem
-    __global__ __launch_bounds__(256) void lsi_phase1_finish_kernel(ResidentArgs a, uint32_t has_x0)
+    /// HOT: set_min_init_ctr_violation = false (P1_HOT_V_MIDPOINT) in a run without x0 — lsi_phase1_finish_hot_kernel; lsi_phase1_finish_kernel is what it was
+    template <bool HOT>
+    __device__ __forceinline__ void lsi_phase1_finish_body(const ResidentArgs &a, uint32_t has_x0)
     {
         const uint32_t lane = threadIdx.x & 63u, wib = threadIdx.x >> 6;
         const uint32_t b    = blockIdx.x * 4 + wib;
@@ -273,13 +306,35 @@ namespace
             __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
             asm volatile("" ::: "memory");
             if (a.inst_dims) // (wave-uniform)
-                lsi_phase1_state<true>(a.sh, v.data, v.var, v.dx_s, v.cs, v.st, nullptr, resident_counts(a, b));
+                lsi_phase1_state<true, HOT>(a.sh, v.data, v.var, v.dx_s, v.cs, v.st, nullptr, resident_counts(a, b));
             else
-                lsi_phase1_state(a.sh, v.data, v.var, v.dx_s, v.cs, v.st);
+                lsi_phase1_state<false, HOT>(a.sh, v.data, v.var, v.dx_s, v.cs, v.st);
             __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "workgroup"); // the step reads the state back from memory
             asm volatile("" ::: "memory");
         }
         lsi_iterate_body(a, b, wib);
+    }
+    __global__ __launch_bounds__(256) void lsi_phase1_finish_kernel(ResidentArgs a, uint32_t has_x0) { lsi_phase1_finish_body<false>(a, has_x0); }
+    __global__ __launch_bounds__(256) void lsi_phase1_finish_hot_kernel(ResidentArgs a, uint32_t has_x0) { lsi_phase1_finish_body<true>(a, has_x0); }
+
+    /// use_phase1_v0 (lexlsi.h:880-915, :1175): behind the setup kernel, in place of the first stage and lsi_phase1_finish_kernel — iteration 0 without an
+    /// equality problem solved.  The step is dx = 0 (the "solution" handed to lsi_step_wave is the state's own x), formStep and the blocking test
+    /// run on it, the blocking constraint joins or nothing changes, and the next equality problem — the first one this run factorizes — is formed
+    /// (lsi_iterate_finish<., true>)
+    __global__ __launch_bounds__(256) void lsi_phase1_v0_kernel(ResidentArgs a)
+    {
+        const uint32_t lane = threadIdx.x & 63u, wib = threadIdx.x >> 6;
+        const uint32_t b    = blockIdx.x * 4 + wib;
+        if (b >= a.B) return;
+        if (!a.alive[b]) return;
+        const ResidentView v = resident_view(a, b, wib);
+        resident_load_lists(a, v, lane);
+        StepVerdict r;
+        if (a.inst_dims) // (wave-uniform)
+            lsi_step_wave<true>(a.sh, v.data, v.var, v.st, v.st, v.st, v.cs, v.ipos, v.dx_s, v.adx_s, v.dv_s, r.alpha, r.blk_obj, r.blk_ctr, r.blk_type, resident_counts(a, b));
+        else
+            lsi_step_wave(a.sh, v.data, v.var, v.st, v.st, v.st, v.cs, v.ipos, v.dx_s, v.adx_s, v.dv_s, r.alpha, r.blk_obj, r.blk_ctr, r.blk_type);
+        lsi_iterate_finish<false, true>(a, b, wib, r);
     }
 
     /// where the results of a run go when the caller's arrays are device memory (lexls_lsi_batch_run_device); fix_var / fix_val: what

@@ -183,6 +183,176 @@ namespace
         *next_stamp = next;
     }
 
+    // ---------------------------------------------------------------------------------------------------------------------------------------
+    // The hot-start options of phase 1 (typedefs.h:213-216; h_params slots 12 .. 15): what Objective::phase1 (objective.h:226-236) does with them,
+    // objective by objective, on the lists above.  HOT, wherever it appears as a template parameter: some option differs from its default; a run
+    // with the defaults compiles none of this in.
+    // ---------------------------------------------------------------------------------------------------------------------------------------
+    enum : uint32_t { P1_HOT_MODIFY_X = 1u, P1_HOT_TYPE_ACTIVE = 2u, P1_HOT_TYPE_INACTIVE = 4u, P1_HOT_V_MIDPOINT = 8u /* set_min_init_ctr_violation = false */ };
+    /// the word a run's options make (0: the defaults)
+    inline uint32_t p1_hot_word(const ParametersLexLSI &par)
+    {
+        return (par.modify_x_guess_enabled ? (uint32_t)P1_HOT_MODIFY_X : 0u) | (par.modify_type_active_enabled ? (uint32_t)P1_HOT_TYPE_ACTIVE : 0u) |
+               (par.modify_type_inactive_enabled ? (uint32_t)P1_HOT_TYPE_INACTIVE : 0u) | (par.set_min_init_ctr_violation ? 0u : (uint32_t)P1_HOT_V_MIDPOINT);
+    }
+
+    /// the branches of formInitialWorkingSet, of the simple-bounds x rewrite and of initialize_v0, for callers that count them (NULL: nobody does)
+    enum : uint32_t
+    {
+        P1B_INA_LB = 0, P1B_INA_UB, P1B_LB_KEPT, P1B_LB_INA, P1B_LB_UB, P1B_UB_KEPT, P1B_UB_INA, P1B_UB_LB, P1B_EQ, // formInitialWorkingSet
+        P1B_X_MID, P1B_X_LB, P1B_X_UB,                                                                             // ensureZeroCtrViolationForSimpleBounds
+        P1B_V_ZERO, P1B_V_MID,                                                                                     // initialize_v0, set_min_init_ctr_violation = false
+        P1B_COUNT
+    };
+
+    /// WorkingSet::deactivate (workingset.h:71-79) on the lists of objective k: ordered erase of entry p of the active list, append to the inactive one.
+    /// The same statements as the REMOVE of lsi_iterate_finish
+    template <bool RAGGED = false>
+    LEXLS_P1_FN void p1_deactivate(const StepShape &sh, uint32_t k, uint32_t p, uint8_t *cs, uint16_t *act, uint16_t *ina, uint16_t *ipos, uint16_t *na, const uint32_t *cnt = nullptr)
+    {
+        const uint32_t f = sh.first[k], nak = na[k], nik = p1_rows<RAGGED>(sh, cnt, k) - nak;
+        const uint32_t c = act[f + p];
+        for (uint32_t i = p; i + 1 < nak; i++) act[f + i] = act[f + i + 1];
+        cs[f + c]    = (uint8_t)CTR_INACTIVE;
+        ina[f + nik] = (uint16_t)c;
+        ipos[f + c]  = (uint16_t)nik;
+        na[k]        = (uint16_t)(nak - 1);
+    }
+
+    /// lb (which = 0) or ub (1) of row c of objective k
+    LEXLS_P1_FN double p1_bound(const StepShape &sh, const double *data, uint32_t k, uint32_t c, uint32_t which)
+    {
+        const uint32_t dim = sh.dim[k];
+        return data[sh.off[k] + c + (size_t)(sh.simple[k] ? which : sh.n + which) * dim];
+    }
+
+    /// entry c of A x of objective k (Objective::apply_A, objective.h:435-455): x(var(c)) for simple bounds, the ordered fma chain of the row otherwise
+    LEXLS_P1_FN double p1_ax(const StepShape &sh, const double *data, const uint32_t *var, const double *x, uint32_t k, uint32_t c)
+    {
+        if (sh.simple[k]) return x[var[c]];
+        const uint32_t dim = sh.dim[k];
+        const double *blk  = data + sh.off[k];
+        double s           = 0.0;
+        for (uint32_t j = 0; j < sh.n; j++) s = __builtin_fma(blk[c + (size_t)j * dim], x[j], s);
+        return s;
+    }
+
+    /// Objective::formInitialWorkingSet (objective.h:123-159) on objective k for the x guess in x (n doubles, rewritten for a simple-bounds objective
+    /// with P1_HOT_MODIFY_X: ensureZeroCtrViolationForSimpleBounds, objective.h:98-120 — the objectives behind see the new x).  ONE thread's work: every
+    /// re-typing is an erase from the active list plus an append, and the list order is the row order of the equality problem.  hotmark (total
+    /// bytes, zero on entry of objective 0): set for every constraint activated or re-activated here (p1_rebuild_stamps).  branch: P1B_COUNT counters or NULL
+    template <bool RAGGED = false>
+    LEXLS_P1_FN void p1_form_initial_working_set(const StepShape &sh, const double *data, const uint32_t *var, double *x, uint32_t hot, uint32_t k, uint8_t *cs, uint16_t *act,
+                                                 uint16_t *ina, uint16_t *ipos, uint16_t *na, uint8_t *hotmark, const uint32_t *cnt = nullptr, uint32_t *branch = nullptr)
+    {
+        const uint32_t f = sh.first[k], rk = p1_rows<RAGGED>(sh, cnt, k);
+        if (hot & (P1_HOT_TYPE_ACTIVE | P1_HOT_TYPE_INACTIVE))
+            for (uint32_t c = 0; c < rk; c++)
+            {
+                const uint8_t t = cs[f + c];
+                if (t == (uint8_t)CTR_ACTIVE_EQ)
+                {
+                    if (branch) branch[P1B_EQ]++;
+                    continue;
+                }
+                if (t == (uint8_t)CTR_INACTIVE ? !(hot & P1_HOT_TYPE_INACTIVE) : !(hot & P1_HOT_TYPE_ACTIVE)) continue;
+                const double ax = p1_ax(sh, data, var, x, k, c), lb = p1_bound(sh, data, k, c, 0), ub = p1_bound(sh, data, k, c, 1);
+                uint8_t to = t; // the type the constraint ends with
+                if (t == (uint8_t)CTR_INACTIVE)
+                    to = ax <= lb ? (uint8_t)CTR_ACTIVE_LB : (ax >= ub ? (uint8_t)CTR_ACTIVE_UB : (uint8_t)CTR_INACTIVE);
+                else if (t == (uint8_t)CTR_ACTIVE_LB)
+                    to = ax > lb ? (ax >= ub ? (uint8_t)CTR_ACTIVE_UB : (uint8_t)CTR_INACTIVE) : t;
+                else
+                    to = ax < ub ? (ax <= lb ? (uint8_t)CTR_ACTIVE_LB : (uint8_t)CTR_INACTIVE) : t;
+                if (branch)
+                {
+                    if (t == (uint8_t)CTR_INACTIVE && to != t) branch[to == (uint8_t)CTR_ACTIVE_LB ? P1B_INA_LB : P1B_INA_UB]++;
+                    if (t == (uint8_t)CTR_ACTIVE_LB) branch[to == t ? P1B_LB_KEPT : (to == (uint8_t)CTR_INACTIVE ? P1B_LB_INA : P1B_LB_UB)]++;
+                    if (t == (uint8_t)CTR_ACTIVE_UB) branch[to == t ? P1B_UB_KEPT : (to == (uint8_t)CTR_INACTIVE ? P1B_UB_INA : P1B_UB_LB)]++;
+                }
+                if (to == t) continue;
+                if (t != (uint8_t)CTR_INACTIVE)
+                {
+                    uint32_t p = 0; // WorkingSet::getCtrIndex (workingset.h:90-94)
+                    while (act[f + p] != c) p++;
+                    p1_deactivate<RAGGED>(sh, k, p, cs, act, ina, ipos, na, cnt);
+                }
+                if (to != (uint8_t)CTR_INACTIVE)
+                {
+                    p1_activate<RAGGED>(sh, k, c, to, cs, act, ina, ipos, na, cnt);
+                    hotmark[f + c] = 1;
+                }
+            }
+        if (sh.simple[k] && (hot & P1_HOT_MODIFY_X))
+            for (uint32_t c = 0; c < rk; c++)
+            {
+                const uint8_t t = cs[f + c];
+                const double lb = p1_bound(sh, data, k, c, 0), ub = p1_bound(sh, data, k, c, 1);
+                x[var[c]]       = t == (uint8_t)CTR_INACTIVE ? 0.5 * (lb + ub) : (t == (uint8_t)CTR_ACTIVE_LB ? lb : ub);
+                if (branch) branch[t == (uint8_t)CTR_INACTIVE ? P1B_X_MID : (t == (uint8_t)CTR_ACTIVE_LB ? P1B_X_LB : P1B_X_UB)]++;
+            }
+    }
+
+    /// The activation order behind formInitialWorkingSet (LexLSI_T::phase1_objectives, lexlsi.h): first the constraints that are still active with the
+    /// type they had (hotmark clear), in the order of their stamps; then the marked ones, objective by objective in active-list order.  In place: the
+    /// stamps of the first kind are tagged with the top bit and replaced, smallest first, by 0, 1, ...  ONE thread's work, at most total^2 steps
+    LEXLS_P1_FN void p1_rebuild_stamps(const StepShape &sh, const uint16_t *act, const uint16_t *na, const uint8_t *hotmark, uint32_t *stamp, uint32_t *next_stamp)
+    {
+        uint32_t kept = 0;
+        for (uint32_t k = 0; k < sh.nObj; k++)
+            for (uint32_t a = 0; a < na[k]; a++)
+            {
+                const uint32_t g = sh.first[k] + act[sh.first[k] + a];
+                if (!hotmark[g]) stamp[g] |= 0x80000000u, kept++;
+            }
+        for (uint32_t r = 0; r < kept; r++)
+        {
+            uint32_t best = 0xffffffffu, at = 0;
+            for (uint32_t k = 0; k < sh.nObj; k++)
+                for (uint32_t a = 0; a < na[k]; a++)
+                {
+                    const uint32_t g = sh.first[k] + act[sh.first[k] + a];
+                    if (!hotmark[g] && (stamp[g] & 0x80000000u) && stamp[g] < best) best = stamp[g], at = g;
+                }
+            stamp[at] = r;
+        }
+        uint32_t next = kept;
+        for (uint32_t k = 0; k < sh.nObj; k++)
+            for (uint32_t a = 0; a < na[k]; a++)
+            {
+                const uint32_t g = sh.first[k] + act[sh.first[k] + a];
+                if (hotmark[g]) stamp[g] = next++;
+            }
+        *next_stamp = next;
+    }
+
+    /// Every objective's formInitialWorkingSet in order, then the activation order: what LexLSI_T::phase1_objectives leaves of a given x guess when
+    /// no v0 is given.  ONE thread's work.  x: the guess, rewritten where P1_HOT_MODIFY_X says so (the caller's array is never this one).  hotmark: total
+    /// bytes of scratch
+    template <bool RAGGED = false>
+    LEXLS_P1_FN void p1_hot_working_set(const StepShape &sh, const double *data, const uint32_t *var, double *x, uint32_t hot, uint8_t *cs, uint16_t *act, uint16_t *ina,
+                                        uint16_t *ipos, uint16_t *na, uint32_t *stamp, uint32_t *next_stamp, uint8_t *hotmark, const uint32_t *cnt = nullptr,
+                                        uint32_t *branch = nullptr)
+    {
+        for (uint32_t g = 0; g < sh.total; g++) hotmark[g] = 0;
+        for (uint32_t k = 0; k < sh.nObj; k++) p1_form_initial_working_set<RAGGED>(sh, data, var, x, hot, k, cs, act, ina, ipos, na, hotmark, cnt, branch);
+        if (hot & (P1_HOT_TYPE_ACTIVE | P1_HOT_TYPE_INACTIVE)) p1_rebuild_stamps(sh, act, na, hotmark, stamp, next_stamp);
+    }
+
+    /// Objective::initialize_v0 (objective.h:162-193) for one constraint of activation type t: A x minus the active bound, minus the midpoint for an
+    /// equality; an inactive one takes its violation (set_min_init_ctr_violation) or, with P1_HOT_V_MIDPOINT, zero inside [lb - tol, ub + tol] and the
+    /// midpoint residual outside.  Independent per row: on the device lane = row
+    LEXLS_P1_FN double p1_initial_v(uint32_t t, double ax, double lb, double ub, bool midpoint, double tol_feasibility, uint32_t *branch = nullptr)
+    {
+        if (t == CTR_ACTIVE_LB) return ax - lb;
+        if (t == CTR_ACTIVE_UB) return ax - ub;
+        if (t != CTR_INACTIVE) return ax - 0.5 * (lb + ub);
+        if (!midpoint) return ax <= lb ? ax - lb : (ax >= ub ? ax - ub : 0.0);
+        const bool inside = ax >= lb - tol_feasibility && ax <= ub + tol_feasibility;
+        if (branch) branch[inside ? P1B_V_ZERO : P1B_V_MID]++;
+        return inside ? 0.0 : ax - 0.5 * (lb + ub);
+    }
+
     /// where an equality problem is posted: the arrays of the equality solver's in slab (lexls_lse_round_layout), all instances
     struct EqualityProblemSlab
     {

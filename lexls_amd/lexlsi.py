@@ -17,6 +17,9 @@ PARAM_DEFAULTS = [200, 1e-12, 1e-8, 1e-12, 1e-13, 0, 50, 1e-8, 0]  # typedefs.h:
 # the three regularization parameters of ParametersLexLSI (typedefs.h:185-187) travel only through the *_ex entry points
 REG_PARAM_KEYS = ["regularization_type", "variable_regularization_factor", "max_number_of_CG_iterations"]
 REG_PARAM_DEFAULTS = [0, 0.0, 10]
+# the five hot-start options of ParametersLexLSI (typedefs.h:213-217), 0 / 1 each: the 17-value form of h_params
+HOT_PARAM_KEYS = ["modify_x_guess_enabled", "modify_type_active_enabled", "modify_type_inactive_enabled", "set_min_init_ctr_violation", "use_phase1_v0"]
+HOT_PARAM_DEFAULTS = [0, 0, 0, 1, 0]
 INFO_KEYS = ["status", "iterations", "activations", "deactivations", "factorizations", "total_rank"]
 
 
@@ -75,6 +78,19 @@ def pack_params_ex(**kw) -> np.ndarray:
     return np.array(vals, dtype=np.float64)
 
 
+def pack_params_hot(**kw) -> np.ndarray:
+    """the 12 parameters of pack_params_ex followed by the hot-start options HOT_PARAM_KEYS"""
+    keys = PARAM_KEYS + REG_PARAM_KEYS + HOT_PARAM_KEYS
+    vals = list(PARAM_DEFAULTS) + list(REG_PARAM_DEFAULTS) + list(HOT_PARAM_DEFAULTS)
+    for k, v in kw.items():
+        vals[keys.index(k)] = float(v)
+    return np.array(vals, dtype=np.float64)
+
+
+def _names_hot(params) -> bool:
+    return any(k in HOT_PARAM_KEYS for k in params)
+
+
 def flatten(nvar: int, objectives):
     """-> dims (uint32), types (int32), data (float64, objectives back to back, column-major), var_index (uint32)"""
     dims, types, chunks, var_index = [], [], [], np.zeros(0, np.uint32)
@@ -122,11 +138,11 @@ def lsi_solve(nvar: int, objectives, active_guess=None, x0=None, device: int = 0
     active, v = np.zeros(total, np.uint8), np.zeros(total)
     guess = None if active_guess is None else np.ascontiguousarray(np.concatenate([np.asarray(g, np.uint8) for g in active_guess]))
     x0a = None if x0 is None else np.ascontiguousarray(x0, np.float64)
-    extended = v0 is not None or regularization_factors is not None or any(k in REG_PARAM_KEYS for k in params)
+    extended = v0 is not None or regularization_factors is not None or any(k in REG_PARAM_KEYS for k in params) or _names_hot(params)
     if extended:
         v0a = None if v0 is None else np.ascontiguousarray(np.concatenate([np.asarray(a, np.float64) for a in v0]))
         rfa = None if regularization_factors is None else np.ascontiguousarray(regularization_factors, np.float64)
-        par = pack_params_ex(**params)
+        par = pack_params_hot(**params) if _names_hot(params) else pack_params_ex(**params)
         capi.check(capi.lib().lexls_lsi_solve_ex(
             C.c_int(device), C.c_uint32(nvar), C.c_uint32(len(dims)), _p(dims, C.c_uint32), _p(types, C.c_int32), _p(data, C.c_double),
             _p(var_index if var_index.size else None, C.c_uint32), _p(guess, C.c_uint8), _p(x0a, C.c_double), _p(v0a, C.c_double),
@@ -186,7 +202,7 @@ def lsi_solve_debug(nvar: int, objectives, active_guess=None, x0=None, device: i
     x0a = None if x0 is None else np.ascontiguousarray(x0, np.float64)
     v0a = None if v0 is None else np.ascontiguousarray(np.concatenate([np.asarray(a, np.float64) for a in v0]))
     rfa = None if regularization_factors is None else np.ascontiguousarray(regularization_factors, np.float64)
-    par = pack_params_ex(**params)
+    par = pack_params_hot(**params) if _names_hot(params) else pack_params_ex(**params)
     buf = debug_buffers(nvar, dims, max_log)
     ds = _DebugStruct(buf["lam"].ctypes.data, buf["lexqr"].ctypes.data, buf["data"].ctypes.data, buf["x_star"].ctypes.data, buf["active_ctr"].ctypes.data,
                       buf["log"].ctypes.data, buf["log_alpha"].ctypes.data, max_log, buf["x_mu"].ctypes.data, buf["x_mu_rhs"].ctypes.data,
@@ -361,7 +377,9 @@ class LsiBatch:
         v0a = None if v0 is None else np.ascontiguousarray(np.asarray(v0, np.float64).reshape(batch, total))  # initial residuals, (batch, sum(dims))
         x, info = np.zeros((batch, nvar)), np.zeros((batch, 6), np.int32)
         active, v, rounds = np.zeros((batch, total), np.uint8), np.zeros((batch, total)), np.zeros(2, np.int32)
-        if regularization_factors is not None or any(k in REG_PARAM_KEYS for k in params):
+        if _names_hot(params):
+            par = pack_params_hot(**params)
+        elif regularization_factors is not None or any(k in REG_PARAM_KEYS for k in params):
             par = pack_params_ex(**params)
         else:
             par = pack_params(**params)
@@ -418,7 +436,9 @@ class LsiBatch:
         d_guess = self._device_array("active_guess", active_guess, torch.uint8, (batch, total))
         d_x0 = self._device_array("x0", x0, torch.float64, (batch, nvar))
         d_v0 = self._device_array("v0", v0, torch.float64, (batch, total))
-        if regularization_factors is not None or any(k in REG_PARAM_KEYS for k in params):
+        if _names_hot(params):
+            par = pack_params_hot(**params)
+        elif regularization_factors is not None or any(k in REG_PARAM_KEYS for k in params):
             par = pack_params_ex(**params)
         else:
             par = pack_params(**params)
@@ -467,7 +487,9 @@ class LsiBatch:
         d_x0 = self._device_array("x0", x0, torch.float64, (batch, nvar))
         d_v0 = self._device_array("v0", v0, torch.float64, (batch, total))
         d_status = self._device_array("status", status, torch.int32, (1,))
-        if regularization_factors is not None or any(k in REG_PARAM_KEYS for k in params):
+        if _names_hot(params):
+            par = pack_params_hot(**params)
+        elif regularization_factors is not None or any(k in REG_PARAM_KEYS for k in params):
             par = pack_params_ex(**params)
         else:
             par = pack_params(**params)
