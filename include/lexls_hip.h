@@ -108,7 +108,10 @@ int lexls_lse_set_ctr_type(lexls_lse_t h, const uint8_t *h_types);
 int lexls_lse_set_skip(lexls_lse_t h, const uint8_t *h_skip);
 /* replaces setProblem / setData (lexlse.h:1511-1530): copies batch x cap x (nVar+1) doubles H2D */
 int lexls_lse_set_problem_host(lexls_lse_t h, const double *h_lod);
-/* zero-copy variant: the caller's device buffer becomes the (read-only) input of later factorizations */
+/* zero-copy variant: the caller's device buffer becomes the (read-only) input of later factorizations.  d_lod must be a multiple of
+ * 8 bytes (anything else: LEXLS_ERR_INVALID, the handle keeps the input and the factor it had); any such address inside a larger
+ * buffer serves, every kernel reads it in the handle's stream.  lqr_qtol's uniform instantiations and lqr_mfma need 16 bytes: on a
+ * pointer that is 8 mod 16 they give way to the bit-exact kernel of the shape (lqr_qtol's ragged instantiations, policy 10, do not). */
 int lexls_lse_set_problem_device(lexls_lse_t h, const double *d_lod);
 /* Device-side assembly of the equality problems of a LexLSI iteration — replaces the row copies of Objective::formLexLSE
  * (objective.h:434-494).  set_constraint_data keeps, per problem, `per_problem` doubles of constraint data

@@ -885,6 +885,8 @@ extern "C"
     {
         CHECK_HANDLE(h);
         if (!d_lod) return fail(LEXLS_ERR_INVALID, "set_problem_device: null");
+        // the kernels read doubles: no launch on a pointer that is not one's (the handle keeps what it had bound, and its factor)
+        if (reinterpret_cast<uintptr_t>(d_lod) & 7u) return fail(LEXLS_ERR_INVALID, "set_problem_device: the pointer must be a multiple of 8 bytes");
         h->d_in         = d_lod;
         h->fused_gather = false;
         h->factor_valid = false;

@@ -98,7 +98,9 @@ class BatchedLexLSE:
         capi.check(capi.lib().lexls_lse_set_problem_host(self._h, _ptr(lod, C.c_double)))
 
     def setProblemDevice(self, device_ptr: int):
-        """Bind a device buffer (e.g. torch_tensor.data_ptr()) holding batch x cap x (nVar+1) doubles as the input."""
+        """Bind a device buffer (e.g. torch_tensor.data_ptr()) holding batch x cap x (nVar+1) doubles as the input: zero-copy, read in the
+        handle's stream, never written.  The address must be a multiple of 8 bytes (LexlsError otherwise, the handle keeps what it had);
+        lqr_qtol's uniform form and lqr_mfma need 16 and give way to the bit-exact kernel on a pointer that is 8 mod 16."""
         capi.check(capi.lib().lexls_lse_set_problem_device(self._h, C.c_void_p(device_ptr)))
 
     # ---- one copy each way per round (lock-step active-set batches) -----------------------------

@@ -37,8 +37,15 @@ LEVELS = {
 }
 
 
+def caps_of(e):
+    """capacities of entry e: LEVELS' (every entry of grid()), or the entry's own "caps" (entries made outside the grid: tests/device_input_cases.py)"""
+    return list(e["caps"]) if "caps" in e else LEVELS[e["levels"]][0]
+
+
 def dims_of(e):
-    """(batch, nObj) uint32 dimensions of entry e (batch resolved)"""
+    """(batch, nObj) uint32 dimensions of entry e (batch resolved); an entry with its own "caps" is at capacity or carries "dims" (batch, nObj)"""
+    if "caps" in e:
+        return np.asarray(e["dims"], np.uint32) if "dims" in e else np.tile(np.asarray(e["caps"], np.uint32), (e["batch"], 1))
     caps, spec = LEVELS[e["levels"]]
     B = e["batch"]
     d = np.tile(np.asarray(caps, np.uint32), (B, 1))
@@ -243,9 +250,9 @@ def query_line(e, cus):
         vals = ["lsi", e["id"], sh["count"], sh["n"], len(sh["dims"]), cap, 0, cap, max(sh["dims"]), 1, e["reg"], 16, 1, 1, int(e["env"].get("LEXLS_KERNEL_POLICY", 0)), 0, 0,
                 cus * 8, 1]
         return " ".join(str(v) for v in vals)
-    caps, _ = LEVELS[e["levels"]]
+    caps = caps_of(e)
     d = dims_of(e)
-    uniform = int(d.max()) if d.min() == d.max() else 0
+    uniform =int(d.max()) if d.min() == d.max() else 0
     keep, do_solve = (e["keep"], 1) if e["mode"] == "fs" else (1, 0)
     vals = ["lse", e["id"], e["batch"], e["n"], len(caps), int(sum(caps)), uniform, max(int(d.sum(axis=1).max()), 1), int(d.max()), e["fixed"], e["reg"], 8 if e["align8"] else 16,
             keep, do_solve, e["policy"], e["guard"], e["qtol0"], cus * 8, 0]
