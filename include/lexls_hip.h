@@ -209,6 +209,30 @@ int lexls_lse_sensitivity_collect_resident(lexls_lse_t h, double tol_wrong_sign_
 int lexls_lse_multipliers(lexls_lse_t h);
 int lexls_lse_get_multipliers(lexls_lse_t h, double *h_L);
 
+/* Adjoint of the solve with respect to the right-hand sides and the fixed values, the matrix A HELD FIXED.  factorize() chooses its pivots and
+ * tests the ranks on the columns of A alone (the column norms never see the right-hand-side column), so for fixed A the basic solution is
+ * exactly affine in the right-hand sides b and in the values of the fixed variables: x = M b + N x_fixed.  Given g = dloss/dx these calls
+ * return grad_rhs = M^T g and grad_fixed = N^T g from one pass over the kept factor (R_k, T_k, the reflectors and their scalars, the Gauss
+ * multipliers left in the pivot columns of the lower rows, the permutation, ranks and first columns, the untouched columns of the fixed
+ * variables): the reverse of factorize()'s right-hand-side updates and of solve().  There are NO derivatives with respect to A: x is not
+ * continuous in A where a rank changes.  Tolerance contract (no reference arithmetic exists); the same bits from run to run.
+ * Layouts: g is batch x nVar in the user's variable order (that of lexls_lse_get_x); grad_rhs is batch x cap in LOD row order, zero in the
+ * rows behind a problem's own; grad_fixed is batch x nVar, entry j < nfixed the fixed variable of slot j in fixVariable order, zero from
+ * nfixed on.
+ * lexls_lse_solve_adjoint copies h_g in, launches and keeps the results in buffers of the handle (allocated at the first call);
+ * lexls_lse_get_adjoint synchronises and copies them out, either output may be NULL; both follow lexls_lse_set_deferred_sync like the other
+ * set / get calls.  lexls_lse_get_adjoint answers only while the results belong to the current factor: after a later factorization, or any
+ * call that invalidates the factor, it fails with LEXLS_ERR_INVALID until lexls_lse_solve_adjoint runs again.
+ * lexls_lse_solve_adjoint_device reads d_g and writes d_grad_rhs and d_grad_fixed (NULL: not wanted) in device memory: it only enqueues in
+ * the handle's stream and makes no host-synchronising call; d_g has to be complete in stream order.
+ * Errors, each returned before any device work and with every output left alone: LEXLS_ERR_INVALID for a null handle or a null g (or a
+ * null d_grad_rhs); LEXLS_ERR_INVALID when there is no kept factor (an x-only solve, keep_factor = 0, or a tolerance-contract kernel leaves
+ * none); LEXLS_ERR_UNSUPPORTED when the factorization ran with regularization_type != 0 (the damping rewrites the right-hand side).
+ * Kernel variant: "solve_adjoint<64>" (lexls_lse_last_consumer_kernel). */
+int lexls_lse_solve_adjoint(lexls_lse_t h, const double *h_g);
+int lexls_lse_get_adjoint(lexls_lse_t h, double *h_grad_rhs, double *h_grad_fixed);
+int lexls_lse_solve_adjoint_device(lexls_lse_t h, const double *d_g, double *d_grad_rhs, double *d_grad_fixed);
+
 /* ---- results (synchronise the stream, then D2H) ------------------------------------------------- */
 int lexls_lse_get_x(lexls_lse_t h, double *h_x);                    /* get_x()      lexlse.h:1587 */
 int lexls_lse_get_factor(lexls_lse_t h, double *h_lod);             /* get_lexqr()  lexlse.h:1626 */

@@ -28,7 +28,8 @@ SYMBOLS = [
     "lexls_lse_set_accuracy_guard", "lexls_lse_get_accuracy",
     "lexls_lse_set_prefix_reuse", "lexls_lse_prefix_reuse_ready", "lexls_lse_set_resume_levels",
     "lexls_lsi_solve", "lexls_lsi_solve_dat", "lexls_lsi_batch_solve",
-    "lexls_lse_multipliers", "lexls_lse_get_multipliers", "lexls_lsi_batch_get_lambda", "lexls_lsi_batch_solve_ex2",
+    "lexls_lse_multipliers", "lexls_lse_get_multipliers", "lexls_lse_solve_adjoint", "lexls_lse_get_adjoint", "lexls_lse_solve_adjoint_device",
+    "lexls_lsi_batch_get_lambda", "lexls_lsi_batch_solve_ex2",
     "lexls_lse_sensitivity_collect", "lexls_lse_sensitivity_collect_resident", "lexls_lse_get_wrong_sign",
     "lexls_lsi_batch_get_cycling_counters", "lexls_lsi_batch_run_device", "lexls_lsi_batch_run_device_ex",
     "lexls_lsi_batch_set_instance_regularization",
@@ -109,6 +110,12 @@ def lib() -> C.CDLL:
         _lib.lexls_lsi_batch_get_working_set_log.argtypes = [C.c_void_p, C.POINTER(C.c_int32), C.POINTER(C.c_double), C.POINTER(C.c_uint32)]
         _lib.lexls_lsi_batch_working_set_log_device.restype = C.c_int
         _lib.lexls_lsi_batch_working_set_log_device.argtypes = [C.c_void_p, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), C.POINTER(C.c_void_p)]
+        _lib.lexls_lse_solve_adjoint.restype = C.c_int
+        _lib.lexls_lse_solve_adjoint.argtypes = [C.c_void_p, C.POINTER(C.c_double)]
+        _lib.lexls_lse_get_adjoint.restype = C.c_int
+        _lib.lexls_lse_get_adjoint.argtypes = [C.c_void_p, C.POINTER(C.c_double), C.POINTER(C.c_double)]
+        _lib.lexls_lse_solve_adjoint_device.restype = C.c_int
+        _lib.lexls_lse_solve_adjoint_device.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]  # d_g, d_grad_rhs, d_grad_fixed: device addresses
     return _lib
 
 

@@ -91,6 +91,10 @@ struct lexls_lse_s
     bool mult_valid       = false;
     uint64_t mult_epoch   = 0;      // factor_epoch the multipliers belong to
     bool mult_swept       = false;
+    // lexls_lse_solve_adjoint: g (batch x nVar), grad_rhs (batch x cap), grad_fixed (batch x nVar), allocated at its first call
+    double *d_adj_g = nullptr, *d_adj_rhs = nullptr, *d_adj_fixed = nullptr;
+    bool adj_valid     = false;
+    uint64_t adj_epoch = 0; // factor_epoch the gradients belong to
     // accuracy guard (lexls_lse_set_accuracy_guard): mode 0 off, 1 report, 2 report + re-solve; arrays allocated when first switched on
     int guard_mode           = 0;
     double guard_threshold   = 0.0;
@@ -285,7 +289,7 @@ extern "C"
         (void)hipSetDevice(h->device);
         void *ptrs[] = {h->d_in_owned, h->d_fac, h->d_hh, h->d_v, h->d_lambda, h->d_scratch, h->d_perm, h->d_rank, h->d_fcol, h->d_round_in, h->d_round_out,
                         h->d_large_state, h->d_large_ws, h->d_norms, h->d_cdata, h->d_reg_factor, h->d_reg_scratch, h->d_reg_mu, h->d_resume_level, h->d_resume_state,
-                        h->d_guard_est, h->d_guard_status, h->d_guard_ind, h->d_mult, h->d_mult_scratch, h->d_wrong_sign};
+                        h->d_guard_est, h->d_guard_status, h->d_guard_ind, h->d_mult, h->d_mult_scratch, h->d_wrong_sign, h->d_adj_g, h->d_adj_rhs, h->d_adj_fixed};
         for (void *p : ptrs)
             if (p) (void)hipFree(p);
         if (h->h_dims_pinned) (void)hipHostFree(h->h_dims_pinned);
@@ -1009,6 +1013,55 @@ extern "C"
         if (int rc = need_factor(h, "lexls_lse_residual")) return rc;
         HIP_TRY(hipSetDevice(h->device));
         HIP_TRY(launch_residual(h->args(), h->stream, &h->last_consumer));
+        return LEXLS_OK;
+    }
+
+    /// what every form of the adjoint checks before any device work: a kept, unregularized factor
+    static int need_adjoint_factor(lexls_lse_t h, const char *who, const void *g)
+    {
+        CHECK_HANDLE(h);
+        if (!g) return fail(LEXLS_ERR_INVALID, std::string(who) + ": null g");
+        if (int rc = need_factor(h, who)) return rc;
+        if (h->reg_type != 0)
+            return fail(LEXLS_ERR_UNSUPPORTED, std::string(who) + ": the factorization ran with regularization_type != 0 (the damping rewrites the right-hand side: x is not the affine map of the kept factor)");
+        return LEXLS_OK;
+    }
+
+    int lexls_lse_solve_adjoint(lexls_lse_t h, const double *h_g)
+    {
+        if (int rc = need_adjoint_factor(h, "lexls_lse_solve_adjoint", h_g)) return rc;
+        HIP_TRY(hipSetDevice(h->device));
+        const size_t B = h->batch, n = h->nVar, cap = h->cap;
+        if (!h->d_adj_g) HIP_TRY(hipMalloc((void **)&h->d_adj_g, 8 * B * n));
+        if (!h->d_adj_rhs) HIP_TRY(hipMalloc((void **)&h->d_adj_rhs, 8 * B * cap));
+        if (!h->d_adj_fixed) HIP_TRY(hipMalloc((void **)&h->d_adj_fixed, 8 * B * n));
+        HIP_TRY(hipMemcpyAsync(h->d_adj_g, h_g, 8 * B * n, hipMemcpyHostToDevice, h->stream));
+        if (!h->deferred_sync) HIP_TRY(hipStreamSynchronize(h->stream)); // h_g may be reused by the caller
+        HIP_TRY(launch_solve_adjoint(h->args(), h->d_adj_g, h->d_adj_rhs, h->d_adj_fixed, h->stream, &h->last_consumer));
+        h->adj_valid = true;
+        h->adj_epoch = h->factor_epoch;
+        return LEXLS_OK;
+    }
+
+    int lexls_lse_solve_adjoint_device(lexls_lse_t h, const double *d_g, double *d_grad_rhs, double *d_grad_fixed)
+    {
+        if (int rc = need_adjoint_factor(h, "lexls_lse_solve_adjoint_device", d_g)) return rc;
+        if (!d_grad_rhs) return fail(LEXLS_ERR_INVALID, "lexls_lse_solve_adjoint_device: null d_grad_rhs");
+        HIP_TRY(hipSetDevice(h->device));
+        HIP_TRY(launch_solve_adjoint(h->args(), d_g, d_grad_rhs, d_grad_fixed, h->stream, &h->last_consumer));
+        return LEXLS_OK;
+    }
+
+    int lexls_lse_get_adjoint(lexls_lse_t h, double *h_grad_rhs, double *h_grad_fixed)
+    {
+        CHECK_HANDLE(h);
+        if (!h->adj_valid) return fail(LEXLS_ERR_INVALID, "lexls_lse_get_adjoint: call lexls_lse_solve_adjoint first");
+        if (!h->factor_valid || h->adj_epoch != h->factor_epoch)
+            return fail(LEXLS_ERR_INVALID, "lexls_lse_get_adjoint: the problem or its factorization changed since lexls_lse_solve_adjoint (call it again)");
+        HIP_TRY(hipSetDevice(h->device));
+        if (h_grad_rhs) HIP_TRY(hipMemcpyAsync(h_grad_rhs, h->d_adj_rhs, 8 * (size_t)h->batch * h->cap, hipMemcpyDeviceToHost, h->stream));
+        if (h_grad_fixed) HIP_TRY(hipMemcpyAsync(h_grad_fixed, h->d_adj_fixed, 8 * (size_t)h->batch * h->nVar, hipMemcpyDeviceToHost, h->stream));
+        if (!h->deferred_sync) HIP_TRY(hipStreamSynchronize(h->stream));
         return LEXLS_OK;
     }
 

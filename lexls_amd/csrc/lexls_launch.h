@@ -10,6 +10,9 @@ namespace lexls
     // (variant, where given: the name of the kernel variant launched — lexls_lse_last_consumer_kernel; host bookkeeping only)
     hipError_t launch_solve_generic(const LseArgs &a, hipStream_t s, bool reciprocal_diagonal = false, const char **variant = nullptr);
     hipError_t launch_residual(const LseArgs &a, hipStream_t s, const char **variant = nullptr);
+    /// lexls_lse_solve_adjoint: d_grad_rhs (batch x cap) = M^T g, d_grad_fixed (batch x nVar, may be NULL) = N^T g for x = M b + N x_fixed of the
+    /// kept factor; d_g is batch x nVar in the order of x.  One wavefront per problem, enqueued only
+    hipError_t launch_solve_adjoint(const LseArgs &a, const double *d_g, double *d_grad_rhs, double *d_grad_fixed, hipStream_t s, const char **variant = nullptr);
     hipError_t launch_sensitivity(const LseArgs &a, const int32_t *d_obj_index, int32_t obj_all, double tolW, double tolC, hipStream_t s, bool scan_up = false,
                                   uint32_t sweep_level_dim_hint = 0, // hint = largest level dimension of the batch (enables the single-sweep kernel)
                                   bool collect = false,              // the wrong-sign SET into a.wrong_sign instead of one candidate (lexls_lse_sensitivity_collect)

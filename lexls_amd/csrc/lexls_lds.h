@@ -207,5 +207,9 @@ namespace lexls
         return b;
     }
 
+    // ---- solve_adjoint (lqr_generic.hip) ----
+    /// g in factor column order (nVar doubles), the gradient of the right-hand side with y inside it (cap doubles), the transpositions (nVar words)
+    inline size_t adjoint_lds_bytes(uint32_t nVar, uint32_t cap) { return (8 * ((size_t)nVar + cap) + 4 * (size_t)nVar + 15) & ~(size_t)15; }
+
     // ---- lqr_large (lqr_large.hip): lqr_large_plan.h ----
 } // namespace lexls

@@ -1059,6 +1059,198 @@ namespace lexls
             for (uint32_t i = tid; i < cap; i += NT) a.v[(size_t)b * cap + i] = v[i];
         }
 
+        // -----------------------------------------------------------------------------------------
+        // adjoint of factorize()'s right-hand-side updates + solve(): grad_rhs = M^T g, grad_fixed = N^T g  (x = M b + N x_fixed for fixed A)
+        // -----------------------------------------------------------------------------------------
+        /// sum over the 64 lanes of a wavefront, the same bits in every lane and from run to run (xor butterfly: the two partners of a step
+        /// add the same two values)
+        __device__ __forceinline__ double wave_sum(double v)
+        {
+#pragma unroll
+            for (int o = 32; o >= 1; o >>= 1) v += __shfl_xor(v, o, 64);
+            return v;
+        }
+
+        /// sum_{i < len} col[i] * vec[i], col in the stored factor (consecutive rows of ONE column: the lanes read consecutive addresses), vec in
+        /// LDS; w0 = this lane's entry of the first 64 rows (0 beyond len), fetched by the caller ahead of the chain it sits on
+        __device__ __forceinline__ double column_dot(const double *col, const double *vec, uint32_t len, double w0, uint32_t lane)
+        {
+            double p = lane < len ? w0 * vec[lane] : 0.0;
+            for (uint32_t i = lane + 64; i < len; i += 64) p = dfma(col[i], vec[i], p);
+            return wave_sum(p);
+        }
+
+        /// One wavefront per problem, the factor read where it is kept (never staged): every pass has the lanes along the ROWS of one factor
+        /// column — consecutive addresses — and ends in a wavefront sum, so no step sends 64 requests a column apart.  Columns go AU at a time:
+        /// their first 64 rows are requested together, then the (dependent) steps consume them.
+        /// LDS (adjoint_lds_bytes): gh = g in factor column order (nVar), cb = the gradient of the right-hand side, LOD row order (cap; y of
+        /// level k = R_k^-T gh_k is written straight into rows F .. F + rank of it), the transpositions (nVar words).
+        /// Tolerance contract (no reference arithmetic exists for this); no atomics: same bits run to run.
+        template <int NT>
+        __global__ __launch_bounds__(NT) void solve_adjoint_kernel(LseArgs a, const double *__restrict__ g, double *__restrict__ grad_rhs, double *__restrict__ grad_fixed)
+        {
+            static_assert(NT == 64, "one wavefront per problem: the reductions are wavefront sums");
+            constexpr uint32_t AU = 4;
+            extern __shared__ double smem[];
+            const uint32_t b = blockIdx.x, lane = threadIdx.x;
+            const uint32_t n = a.nVar, cap = a.cap, nObj = a.nObj;
+            const double *__restrict__ W = a.fac + (size_t)b * cap * (n + 1);
+            const double *hh     = a.hh + (size_t)b * cap;
+            const uint32_t *dims = a.dims + (size_t)b * nObj;
+            const uint32_t *rk = a.rank + (size_t)b * nObj, *fc = a.fcol + (size_t)b * nObj;
+            double *gh       = smem;
+            double *cb       = smem + n;
+            uint32_t *perm_l = reinterpret_cast<uint32_t *>(cb + cap);
+            const uint32_t nf = a.nfixed ? (a.nfixed[b] < n ? a.nfixed[b] : n) : 0;
+            const uint32_t T  = a.totalrank[b] < n ? a.totalrank[b] : n; // pivot columns: [nf, T)
+            uint32_t M = 0;
+            for (uint32_t k = 0; k < nObj; k++) M += dims[k];
+            if (M > cap) M = cap;
+            // (a level's rank and first column as the loops below may trust them: inside the level's rows and the pivot columns)
+            auto level = [&](uint32_t k, uint32_t dim, uint32_t &rank, uint32_t &Fc) __attribute__((always_inline)) {
+                Fc   = fc[k];
+                rank = (nf < n && Fc < T) ? rk[k] : 0; // (every variable fixed: factorize() returns before the levels)
+                if (rank > dim) rank = dim;
+                if (rank > T - (Fc < T ? Fc : T)) rank = T - (Fc < T ? Fc : T);
+            };
+
+            // ---- (a) gh = P^T g: variable i sits at the position it reaches by following the transpositions first to last ----
+            for (uint32_t i = lane; i < n; i += NT) perm_l[i] = a.perm[(size_t)b * n + i];
+            for (uint32_t i = lane; i < cap; i += NT) cb[i] = 0.0;
+            __syncthreads();
+            for (uint32_t i = lane; i < n; i += NT)
+            {
+                uint32_t p = i;
+                for (uint32_t k = 0; k < T; k++)
+                {
+                    const uint32_t pk = perm_l[k];
+                    p                 = (p == k) ? pk : ((p == pk) ? k : p);
+                }
+                if (p < n) gh[p] = g[(size_t)b * n + i];
+            }
+            __syncthreads();
+
+            // ---- (b) the reverse of solve(), levels ascending: y = R_k^-T gh_k, then gh -= [T_k]^T y on the pivot columns of the later levels.
+            // Column c of [R_k | T_k] takes the dot product of its rows above the diagonal (all `rank` rows behind the triangle) with y ----
+            uint32_t F = 0;
+            for (uint32_t k = 0; k < nObj; k++)
+            {
+                const uint32_t dim = dims[k];
+                uint32_t rank, Fc;
+                level(k, dim, rank, Fc);
+                if (rank > 0 && F + dim <= M)
+                {
+                    double *y = cb + F;
+                    for (uint32_t c0 = Fc; c0 < T; c0 += AU)
+                    {
+                        double w[AU], dg[AU];
+#pragma unroll
+                        for (uint32_t u = 0; u < AU; u++)
+                        {
+                            const uint32_t c = c0 + u, j = c - Fc;
+                            const uint32_t len = c < T ? (j < rank ? j : rank) : 0;
+                            w[u]  = lane < len ? W[F + lane + (size_t)c * cap] : 0.0;
+                            dg[u] = (c < T && j < rank) ? W[F + j + (size_t)c * cap] : 1.0;
+                        }
+#pragma unroll
+                        for (uint32_t u = 0; u < AU; u++)
+                        {
+                            const uint32_t c = c0 + u, j = c - Fc;
+                            if (c >= T) break;
+                            const uint32_t len = j < rank ? j : rank;
+                            const double s     = column_dot(W + F + (size_t)c * cap, y, len, w[u], lane);
+                            if (j < rank) // (uniform) inside the triangle: the next column reads this y
+                            {
+                                if (lane == 0) y[j] = (gh[c] - s) / dg[u];
+                                __syncthreads();
+                            }
+                            else if (lane == 0)
+                                gh[c] -= s;
+                        }
+                    }
+                    __syncthreads();
+                }
+                F += dim;
+            }
+
+            // ---- (c) the reverse of factorize()'s right-hand-side updates, levels descending: the transposed Gauss step (the multipliers L sit in
+            // the level's pivot columns, rows of the later levels), then the level's reflectors, last first ----
+            uint32_t Fend = 0;
+            for (uint32_t k = 0; k < nObj; k++) Fend += dims[k];
+            for (uint32_t k = nObj; k--;)
+            {
+                const uint32_t dim = dims[k];
+                F                  = Fend - dim;
+                Fend               = F;
+                uint32_t rank, Fc;
+                level(k, dim, rank, Fc);
+                if (rank == 0 || F + dim > M) continue;
+                const uint32_t Fn = F + dim;
+                if (k + 1 < nObj && Fn < M)
+                {
+                    for (uint32_t p0 = 0; p0 < rank; p0 += AU)
+                    {
+                        double w[AU], s[AU];
+#pragma unroll
+                        for (uint32_t u = 0; u < AU; u++) w[u] = (p0 + u < rank && lane < M - Fn) ? W[Fn + lane + (size_t)(Fc + p0 + u) * cap] : 0.0;
+#pragma unroll
+                        for (uint32_t u = 0; u < AU; u++) s[u] = p0 + u < rank ? column_dot(W + Fn + (size_t)(Fc + p0 + u) * cap, cb + Fn, M - Fn, w[u], lane) : 0.0;
+#pragma unroll
+                        for (uint32_t u = 0; u < AU; u++)
+                            if (lane == 0 && p0 + u < rank) cb[F + p0 + u] -= s[u];
+                    }
+                    __syncthreads();
+                }
+                // H = I - tau [1; ess] [1; ess]^T on rows F + j .. F + dim - 1; none where factorize() made none (one row left, or tau == 0)
+                for (uint32_t j0 = rank; j0 > 0; j0 -= (j0 < AU ? j0 : AU))
+                {
+                    double e[AU], tau[AU];
+#pragma unroll
+                    for (uint32_t u = 0; u < AU; u++)
+                    {
+                        const bool on = u < j0;
+                        const uint32_t j = on ? j0 - 1 - u : 0;
+                        tau[u] = on ? hh[F + j] : 0.0;
+                        e[u]   = (on && lane + 1 < dim - j) ? W[F + j + 1 + lane + (size_t)(Fc + j) * cap] : 0.0;
+                    }
+#pragma unroll
+                    for (uint32_t u = 0; u < AU; u++)
+                    {
+                        if (u >= j0) break;
+                        const uint32_t j = j0 - 1 - u, rows = dim - j;
+                        if (rows == 1 || tau[u] == 0.0) continue; // (uniform)
+                        const double *ess = W + F + j + 1 + (size_t)(Fc + j) * cap;
+                        double *v         = cb + F + j;
+                        const double t    = column_dot(ess, v + 1, rows - 1, e[u], lane) + v[0];
+                        __syncthreads(); // (every lane has read v[0])
+                        if (lane == 0) v[0] = dfma(-tau[u], t, v[0]);
+                        if (lane + 1 < rows) v[1 + lane] = dfma(-(tau[u] * e[u]), t, v[1 + lane]);
+                        for (uint32_t i = lane + 64; i + 1 < rows; i += 64) v[1 + i] = dfma(-(tau[u] * ess[i]), t, v[1 + i]);
+                        __syncthreads();
+                    }
+                }
+            }
+            __syncthreads();
+
+            // ---- (d) grad_rhs = cb (rows behind the problem's own stay 0); grad_fixed_j = gh_j - (column j of the fixed variables)^T cb ----
+            for (uint32_t i = lane; i < cap; i += NT) grad_rhs[(size_t)b * cap + i] = cb[i];
+            if (grad_fixed)
+            {
+                for (uint32_t j0 = 0; j0 < nf; j0 += AU)
+                {
+                    double w[AU], s[AU];
+#pragma unroll
+                    for (uint32_t u = 0; u < AU; u++) w[u] = (j0 + u < nf && lane < M) ? W[lane + (size_t)(j0 + u) * cap] : 0.0;
+#pragma unroll
+                    for (uint32_t u = 0; u < AU; u++) s[u] = j0 + u < nf ? column_dot(W + (size_t)(j0 + u) * cap, cb, M, w[u], lane) : 0.0;
+#pragma unroll
+                    for (uint32_t u = 0; u < AU; u++)
+                        if (lane == 0 && j0 + u < nf) grad_fixed[(size_t)b * n + j0 + u] = gh[j0 + u] - s[u];
+                }
+                for (uint32_t j = nf + lane; j < n; j += NT) grad_fixed[(size_t)b * n + j] = 0.0;
+            }
+        }
+
         /// One coalesced pass over a problem's stored factor (cap x (nVar+1), column-major) into LDS, odd leading dimension so that
         /// "thread = row" and "thread = column" walks are conflict-free.  For kernels that walk the factor along dependent chains
         /// when latency, not occupancy, is what counts (few problems per CU; several levels per launch).
@@ -1875,6 +2067,17 @@ namespace lexls
         if (e != hipSuccess) return e;
         hipLaunchKernelGGL((residual_kernel<64>), dim3(a.batch), dim3(64), lds, s, a);
         if (variant) *variant = "residual<64>";
+        return hipGetLastError();
+    }
+
+    hipError_t launch_solve_adjoint(const LseArgs &a, const double *d_g, double *d_grad_rhs, double *d_grad_fixed, hipStream_t s, const char **variant)
+    {
+        const size_t lds = adjoint_lds_bytes(a.nVar, a.cap);
+        if (lds > kMaxLdsBytes) return hipErrorInvalidValue;
+        hipError_t e = set_lds(solve_adjoint_kernel<64>, lds);
+        if (e != hipSuccess) return e;
+        hipLaunchKernelGGL((solve_adjoint_kernel<64>), dim3(a.batch), dim3(64), lds, s, a, d_g, d_grad_rhs, d_grad_fixed);
+        if (variant) *variant = "solve_adjoint<64>";
         return hipGetLastError();
     }
 

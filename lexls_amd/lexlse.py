@@ -269,6 +269,37 @@ class BatchedLexLSE:
         capi.check(capi.lib().lexls_lse_get_multipliers(self._h, _ptr(L, C.c_double)))
         return L
 
+    # ---- adjoint of the solve (A held fixed) ------------------------------------------------------
+    def solve_adjoint(self, g):
+        """lexls_lse_solve_adjoint + lexls_lse_get_adjoint: for fixed A the basic solution is affine in the right-hand sides and the fixed
+        values, x = M b + N x_fixed; with g = dloss/dx, (batch, nVar) in the order of get_x(), returns (grad_rhs, grad_fixed) = (M^T g, N^T g)
+        as numpy arrays: (batch, cap) in LOD row order (zero behind a problem's own rows) and (batch, nVar), entry j < nfixed the fixed variable
+        of slot j in fixVariable order, zero from nfixed on.  Needs a kept, unregularized factor.  No derivatives with respect to A."""
+        g = np.ascontiguousarray(g, np.float64)
+        if g.shape != (self.batch, self.nVar):
+            raise ValueError(f"g must have shape {(self.batch, self.nVar)}, got {g.shape}")
+        capi.check(capi.lib().lexls_lse_solve_adjoint(self._h, _ptr(g, C.c_double)))
+        grad_rhs = np.zeros((self.batch, self.cap))
+        grad_fixed = np.zeros((self.batch, self.nVar))
+        capi.check(capi.lib().lexls_lse_get_adjoint(self._h, _ptr(grad_rhs, C.c_double), _ptr(grad_fixed, C.c_double)))
+        return grad_rhs, grad_fixed
+
+    def solve_adjoint_device(self, g, grad_rhs, grad_fixed=None):
+        """lexls_lse_solve_adjoint_device: g (batch, nVar), grad_rhs (batch, cap) and grad_fixed (batch, nVar; None: not wanted) in device memory —
+        contiguous float64 torch tensors (anything with data_ptr()) or raw addresses.  Only enqueued in the handle's stream (set_stream): g has
+        to be complete in stream order, nothing is waited for."""
+        def address(name, t, shape):
+            if t is None:
+                return None
+            if not hasattr(t, "data_ptr"):
+                return C.c_void_p(int(t))
+            if str(t.dtype) != "torch.float64" or not t.is_contiguous() or tuple(t.shape) != shape:
+                raise ValueError(f"solve_adjoint_device: {name} must be a contiguous float64 tensor of shape {shape}")
+            return C.c_void_p(t.data_ptr())
+        capi.check(capi.lib().lexls_lse_solve_adjoint_device(self._h, address("g", g, (self.batch, self.nVar)),
+                                                              address("grad_rhs", grad_rhs, (self.batch, self.cap)),
+                                                              address("grad_fixed", grad_fixed, (self.batch, self.nVar))))
+
     def getCtrType(self):
         t = np.zeros((self.batch, self.cap), np.uint8)
         capi.check(capi.lib().lexls_lse_get_ctr_type(self._h, _ptr(t, C.c_uint8)))
