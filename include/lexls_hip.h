@@ -675,6 +675,36 @@ int lexls_lsi_batch_destroy(lexls_lsi_batch_t b);
  * problems are not re-formed from relaxed data after the run), after a regularized run (regularization_type != 0), or when the batch's constraint data is not resident
  * (LEXLS_LSI_HOST_STAGING, data beyond 2^31 doubles per instance) or holds more than 65535 constraints per instance.  A later run replaces the multipliers of the previous one. */
 int lexls_lsi_batch_get_lambda(lexls_lsi_batch_t b, double *h_lambda);
+/* Gradients of the LAST completed run's solutions with respect to the bounds, the matrices A HELD FIXED.  At an instance that ended
+ * PROBLEM_SOLVED, x is the basic solution of the equality problem of its final working set W: the right-hand sides are the active bounds (lb or
+ * ub by activation type), the fixed values the active simple bounds.  While W does not change x is exactly affine in the bounds, so with
+ * g = dloss/dx these calls return dloss/dlb and dloss/dub: the final equality problems are formed and factorized with the factor kept as for
+ * lexls_lsi_batch_get_lambda (once per run: whichever of the two is called first pays for it, every later call of either reuses the factor),
+ * lexls_lse_solve_adjoint_device gives M^T g and N^T g, and lsi_adjoint_scatter_kernel takes them from LOD-row / fixed-slot order back to the
+ * user's constraint order.  There are NO derivatives with respect to A (see lexls_lse_solve_adjoint).
+ * Layouts: g is batch x nVar, dloss/dx in the user's variable order; grad_lb and grad_ub are batch x sum(dims) each, in the constraint order of
+ * h_active / h_v (objective by objective).  Either output may be NULL (not wanted).  lexls_lsi_batch_solve_adjoint takes and fills host arrays;
+ * lexls_lsi_batch_solve_adjoint_device takes memory of the batch's device, and no gradient, g or factor passes through host memory.  Both are
+ * host-synchronous like lexls_lsi_batch_run_device: the inputs have to be complete at the call, the outputs are complete at the return.
+ * Solved instances (status PROBLEM_SOLVED), per constraint of the final working set: CTR_ACTIVE_LB — the value goes to grad_lb, grad_ub is 0;
+ * CTR_ACTIVE_UB — the value goes to grad_ub, grad_lb is 0; CTR_ACTIVE_EQ — the value goes to grad_ub, the bound the final equality problem
+ * reads, and grad_lb is 0 (with lb = ub = c the caller's dloss/dc is the sum of the two either way).  Active simple bounds of objective 0 take
+ * grad_fixed of their slot, by the same rule.  Every constraint that is not in the working set is exactly 0, and so are the rows that are absent
+ * under lexls_lsi_batch_set_instance_obj_dims.
+ * Status rule: an instance with ANY OTHER status (stopped by a factorization budget, for instance) gets zeros in all its rows of both outputs —
+ * its x is an intermediate iterate, not the solution of its working set's equality problem.  The status is the one the run left behind (its host
+ * object's, or the resident slab's), never read from an array of the caller.
+ * Mask rule: an instance that the instance mask (lexls_lsi_batch_set_instance_mask) skips keeps the bits of its rows in both outputs, like every
+ * other output under the mask.
+ * The gradient is that of the piece of the piecewise-affine map the solve ended on: where a constraint sits at its bound without being in the
+ * working set it is one-sided.  Tolerance contract, as for lexls_lse_solve_adjoint; the same bits from run to run and from the host and the
+ * device form.  x, active, v and the multipliers of the run are not touched.
+ * Errors, each returned before any device work and with every output left alone: LEXLS_ERR_INVALID for a null handle, a null g, or both
+ * outputs null; LEXLS_ERR_INVALID when the batch has no completed run, or a lexls_lsi_batch_enqueue_device run is waiting for
+ * lexls_lsi_batch_finish; LEXLS_ERR_UNSUPPORTED after exactly the runs for which lexls_lsi_batch_get_lambda answers LEXLS_ERR_UNSUPPORTED (cycling
+ * handling, a regularized run, more than 65535 constraints, constraint data not resident), with that call's reason in lexls_last_error(). */
+int lexls_lsi_batch_solve_adjoint(lexls_lsi_batch_t b, const double *h_g, double *h_grad_lb, double *h_grad_ub);
+int lexls_lsi_batch_solve_adjoint_device(lexls_lsi_batch_t b, const double *d_g, double *d_grad_lb, double *d_grad_ub);
 /* LexLSI::getCyclingCounter() (lexlsi.h, CyclingHandler::get_counter, cycling.h) of every instance of the LAST lexls_lsi_batch_run on this batch:
  * h_counts receives `batch` values, the bounds each instance's cycling handler relaxed (the working-set log's cycling_detected entries, counted).
  * Whatever path served the run: host path, lock-step stages, persistent launch, one by one through the single-problem driver.  All zeros after a

@@ -36,6 +36,7 @@ SYMBOLS = [
     "lexls_lsi_batch_set_working_set_log", "lexls_lsi_batch_get_working_set_log", "lexls_lsi_batch_working_set_log_device",
     "lexls_lsi_batch_enqueue_device", "lexls_lsi_batch_finish",
     "lexls_lsi_batch_set_instance_mask", "lexls_lsi_batch_set_instance_max_factorizations", "lexls_lsi_batch_set_instance_obj_dims",
+    "lexls_lsi_batch_solve_adjoint", "lexls_lsi_batch_solve_adjoint_device",
     "lexls_lsi_batch_last_kernel",
 ]
 
@@ -116,6 +117,10 @@ def lib() -> C.CDLL:
         _lib.lexls_lse_get_adjoint.argtypes = [C.c_void_p, C.POINTER(C.c_double), C.POINTER(C.c_double)]
         _lib.lexls_lse_solve_adjoint_device.restype = C.c_int
         _lib.lexls_lse_solve_adjoint_device.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]  # d_g, d_grad_rhs, d_grad_fixed: device addresses
+        _lib.lexls_lsi_batch_solve_adjoint.restype = C.c_int
+        _lib.lexls_lsi_batch_solve_adjoint.argtypes = [C.c_void_p, C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_double)]
+        _lib.lexls_lsi_batch_solve_adjoint_device.restype = C.c_int
+        _lib.lexls_lsi_batch_solve_adjoint_device.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]  # d_g, d_grad_lb, d_grad_ub: device addresses
     return _lib
 
 

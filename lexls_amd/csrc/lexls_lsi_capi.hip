@@ -245,6 +245,29 @@ extern "C"
         });
     }
 
+    /// both forms of the adjoint: every refusal comes before any device work and leaves the outputs alone
+    static int lsi_batch_solve_adjoint(lexls_lsi_batch_t b, const double *g, double *grad_lb, double *grad_ub, bool on_device)
+    {
+        return guarded([&]() {
+            const std::string who = on_device ? "lexls_lsi_batch_solve_adjoint_device" : "lexls_lsi_batch_solve_adjoint";
+            if (!b) throw Exception(who + ": null handle");
+            if (!g) throw Exception(who + ": null g");
+            if (!grad_lb && !grad_ub) throw Exception(who + ": both outputs are null");
+            b->refuse_pending(who.c_str());
+            return b->solve_adjoint(g, grad_lb, grad_ub, on_device);
+        });
+    }
+
+    int lexls_lsi_batch_solve_adjoint(lexls_lsi_batch_t b, const double *h_g, double *h_grad_lb, double *h_grad_ub)
+    {
+        return lsi_batch_solve_adjoint(b, h_g, h_grad_lb, h_grad_ub, false);
+    }
+
+    int lexls_lsi_batch_solve_adjoint_device(lexls_lsi_batch_t b, const double *d_g, double *d_grad_lb, double *d_grad_ub)
+    {
+        return lsi_batch_solve_adjoint(b, d_g, d_grad_lb, d_grad_ub, true);
+    }
+
     int lexls_lsi_batch_get_cycling_counters(lexls_lsi_batch_t b, uint32_t *h_counts)
     {
         return guarded([&]() {

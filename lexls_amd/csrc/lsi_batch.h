@@ -50,6 +50,54 @@ namespace
         }
     }
 
+    /// lexls_lsi_batch_solve_adjoint for a whole group: the adjoint of the final equality problems (lexls_lse_solve_adjoint_device: grad_rhs B x cap in
+    /// LOD row order, grad_fixed B x n in fixVariable order) goes to the user's constraint order — instance b's `total` entries of out_lb / out_ub
+    /// (either may be NULL).  One wavefront per instance.  map = [nact (B) | pos (B x total)] as for lsi_lambda_scatter_kernel: row r of the final
+    /// problem (the nf fixed variables first, then the LOD rows) is user row pos[r]; types (B x total) = its activation type, in the same row order;
+    /// meta (B x 2) = the instance's status of the run and nf.  CTR_ACTIVE_LB goes to out_lb, CTR_ACTIVE_UB and CTR_ACTIVE_EQ to out_ub (the bound
+    /// form_final_problem posts); an instance that did not end PROBLEM_SOLVED has no active rows here.  The zeros and the active values meet in an LDS
+    /// tile of ADJ_TILE user rows (pos is injective: no two rows of the map claim one entry, no atomics), then the lanes run along the user rows:
+    /// every entry of the outputs is stored once, by consecutive lanes.
+    /// mask (the group's bytes of lexls_lsi_batch_set_instance_mask, or NULL): the entries of a skipped instance stay as they are
+    constexpr uint32_t ADJ_TILE = 1024;
+    __global__ __launch_bounds__(64) void lsi_adjoint_scatter_kernel(const double *__restrict__ grad_rhs, const double *__restrict__ grad_fixed, const uint32_t *__restrict__ map,
+                                                                     const uint8_t *__restrict__ types, const int32_t *__restrict__ meta, uint32_t B, uint32_t total, uint32_t n,
+                                                                     uint32_t cap, double *__restrict__ out_lb, double *__restrict__ out_ub, const uint8_t *mask)
+    {
+        __shared__ double s_lb[ADJ_TILE], s_ub[ADJ_TILE];
+        const uint32_t b = blockIdx.x, lane = threadIdx.x;
+        if (b >= B || lsi_mask_byte(mask, b) == 0) return; // (block-uniform)
+        const uint32_t nf   = min((uint32_t)max(meta[2 * b + 1], 0), n);
+        const uint32_t na   = meta[2 * b] == (int32_t)PROBLEM_SOLVED ? min(map[b], min(total, nf + cap)) : 0u;
+        const uint32_t *pos = map + B + (size_t)b * total;
+        const uint8_t *ty   = types + (size_t)b * total;
+        const double *gr = grad_rhs + (size_t)b * cap, *gf = grad_fixed + (size_t)b * n;
+        for (uint32_t u0 = 0; u0 < total; u0 += ADJ_TILE)
+        {
+            const uint32_t len = min(ADJ_TILE, total - u0);
+            for (uint32_t i = lane; i < len; i += 64) s_lb[i] = s_ub[i] = 0.0;
+            __syncthreads();
+            for (uint32_t r = lane; r < na; r += 64)
+            {
+                const uint32_t u = pos[r];
+                if (u < u0 || u - u0 >= len) continue;
+                const double val = r < nf ? gf[r] : gr[r - nf];
+                const uint8_t t  = ty[r];
+                if (t == CTR_ACTIVE_LB)
+                    s_lb[u - u0] = val;
+                else if (t == CTR_ACTIVE_UB || t == CTR_ACTIVE_EQ)
+                    s_ub[u - u0] = val;
+            }
+            __syncthreads();
+            for (uint32_t i = lane; i < len; i += 64)
+            {
+                if (out_lb) out_lb[(size_t)b * total + u0 + i] = s_lb[i];
+                if (out_ub) out_ub[(size_t)b * total + u0 + i] = s_ub[i];
+            }
+            __syncthreads();
+        }
+    }
+
     /// lexls_lsi_batch_set_instance_regularization with the factors in device memory, for one group: row i of the group's handle array (B x nObjL,
     /// what the regularized kernels read) takes the factors of the caller's row i (B x nObj, the group's first instance in front): LexLSE level k
     /// = objective off + k.  One thread per (instance, level).
@@ -128,13 +176,34 @@ struct lexls_lsi_batch_s
         Pinned<uint32_t> map;         // [nact (B) | pos (B x total)]
         uint32_t *d_map = NULL;
         double *d_out   = NULL;       // B x total x nObj
+        // lexls_lsi_batch_solve_adjoint (made at its first call, ensure_adjoint_bufs): the activation type of every row of the map and
+        // [status of the run | nfixed] per instance, for lsi_adjoint_scatter_kernel; g and the two outputs of a host caller; the adjoint of the
+        // final equality problems (grad_rhs B x cap, grad_fixed B x nVar)
+        Pinned<uint8_t> types;        // B x total
+        Pinned<int32_t> meta;         // B x 2
+        uint8_t *d_types = NULL;
+        int32_t *d_meta  = NULL;
+        double *d_g = NULL, *d_grad_rhs = NULL, *d_grad_fixed = NULL, *d_grad_lb = NULL, *d_grad_ub = NULL;
         ~LambdaBufs()
         {
-            if (d_map) (void)hipFree(d_map);
-            if (d_out) (void)hipFree(d_out);
+            void *dev[] = {d_map, d_out, d_types, d_meta, d_g, d_grad_rhs, d_grad_fixed, d_grad_lb, d_grad_ub};
+            for (void *q : dev)
+                if (q) (void)hipFree(q);
         }
     };
     std::vector<std::unique_ptr<LambdaBufs>> lam_bufs;
+    // What a group's handle holds of the last run: final_kept — its final equality problems, formed and factorized with the factor kept
+    // (ensure_final_factor; get_lambda and solve_adjoint both start there, whichever comes first pays for it), final_any — some instance of the
+    // group has an active constraint (else nothing was factorized), adj_uploaded — map, types and meta of that formation are on the device.
+    // Every new run drops all three (forget_final_factor).
+    std::vector<char> final_kept, final_any, adj_uploaded;
+    std::vector<int32_t> ws_status;   // batch: every instance's TerminationStatus of the last run, from its host object or the resident slab
+    void forget_final_factor()
+    {
+        std::fill(final_kept.begin(), final_kept.end(), 0);
+        std::fill(final_any.begin(), final_any.end(), 0);
+        std::fill(adj_uploaded.begin(), adj_uploaded.end(), 0);
+    }
     std::vector<uint32_t> cycling_count; // batch: LexLSI::getCyclingCounter() of every instance of the last run (lexls_lsi_batch_get_cycling_counters)
     // ---- the working-set log of the last run (lexls_lsi_batch_set_working_set_log; LexLSI::getWorkingSetLog, lexlsi.h:739) ----
     // One slab for the batch, on the device and as a pinned staging copy: batch x cap records, batch x cap values, batch counters; group g works on
@@ -232,6 +301,7 @@ struct lexls_lsi_batch_s
         ws_idx.assign((size_t)batch * total, 0);
         ws_type.assign((size_t)batch * total, 0);
         cycling_count.assign(batch, 0u);
+        ws_status.assign(batch, static_cast<int32_t>(TERMINATION_STATUS_UNKNOWN));
         if (off)
         {
             ws_fixvar.assign((size_t)batch * h_dims[0], 0);
@@ -250,6 +320,7 @@ struct lexls_lsi_batch_s
         nGroups = std::min(nGroups, batch);
         gather = per_data < 0x7fffffffull && !sw.host_staging; // (LEXLS_LSI_HOST_STAGING, a diagnostic switch: assemble on the host, stage over PCIe)
         grp.resize(nGroups);
+        final_kept.assign(nGroups, 0), final_any.assign(nGroups, 0), adj_uploaded.assign(nGroups, 0);
         lo.assign(nGroups + 1, 0);
         for (uint32_t g = 0; g < nGroups; g++) lo[g + 1] = lo[g] + batch / nGroups + (g < batch % nGroups ? 1u : 0u);
         for (uint32_t g = 0; g < nGroups; g++)
@@ -299,6 +370,7 @@ struct lexls_lsi_batch_s
     {
         uint16_t *ix = &ws_idx[(size_t)b * total];
         uint8_t *ty  = &ws_type[(size_t)b * total];
+        ws_status[b] = static_cast<int32_t>(inst.getStatus());
         for (uint32_t k = 0; k < nObj; k++) ws_na[(size_t)b * nObj + k] = static_cast<uint16_t>(inst.getObjectives()[k].getActiveCtrCount());
         walk_working_set(inst.getObjectives(), nObj, [&](uint32_t k, Index a, Index c, ConstraintActivationType t) { ix[first[k] + a] = static_cast<uint16_t>(c), ty[first[k] + a] = static_cast<uint8_t>(t); }, [](uint32_t, Index, Index) {});
         keep_fixed(b, data, var_index);
@@ -309,6 +381,7 @@ struct lexls_lsi_batch_s
         char *base          = ctx.rws_host.data();
         const uint8_t *cs   = ctx.rl.ctr_state(base, k);
         const uint16_t *act = ctx.rl.act(base, k), *na = ctx.rl.na(base, k);
+        ws_status[b]        = ctx.rl.info(base, k)[0];
         for (uint32_t o = 0; o < nObj; o++)
         {
             ws_na[(size_t)b * nObj + o] = na[o];
@@ -397,6 +470,127 @@ struct lexls_lsi_batch_s
         }
     }
 
+    /// The final equality problems of group g's instances (the downloaded working sets of the last run, form_final_problem) formed, uploaded and
+    /// factorized with the factor kept on a bit-exact kernel, in the group's stream — once per run: the handle then holds that factor until the
+    /// next run (final_kept), and lb.map the rows' user positions.  -> some instance has an active constraint (else nothing is factorized).
+    /// formed(): called between the host's formation and the device work (get_lambda's stage clock)
+    template <class Formed>
+    bool ensure_final_factor(uint32_t g, Formed formed)
+    {
+        if (final_kept[g]) return final_any[g] != 0;
+        BatchCtx &ctx  = *grp[g];
+        LambdaBufs &lb = *lam_bufs[g];
+        pool->run(ctx.B, [&](uint32_t k) { form_final_problem(g, k, lb); });
+        formed();
+        bool any_active = false; // (a run whose mask skipped every instance of the group, or whose instances all ended with empty working sets)
+        for (uint32_t k = 0; k < ctx.B && !any_active; k++) any_active = lb.map[k] != 0;
+        // the equality solver's parameters of this run, whichever path it took (the one-by-one path of a non-resident deactivate_first_wrong_sign run never set
+        // them on these handles; an earlier run of the batch object may have left a regularization there): lam_rc == LEXLS_OK means unregularized
+        hip_check(lexls_lse_set_tolerance(ctx.h, lam_tol));
+        hip_check(lexls_lse_set_regularization(ctx.h, 0, NULL, 0, 0.0));
+        const int policy = lexls_internal_kernel_policy(ctx.h);
+        hip_check(lexls_lse_set_kernel_policy(ctx.h, 5)); // bit-exact kernels whatever the shape (the factor of the reference's getLambda)
+        int rc = any_active ? lexls_internal_upload_round_trusted(ctx.h, ctx.in_block.data(), 1) : LEXLS_OK;
+        if (rc == LEXLS_OK && any_active) rc = lexls_lse_factorize(ctx.h);
+        hip_check(lexls_lse_set_kernel_policy(ctx.h, policy));
+        hip_check(rc);
+        final_kept[g] = 1, final_any[g] = any_active ? 1 : 0;
+        return any_active;
+    }
+
+    /// the groups' buffers of solve_adjoint, made at the first call
+    void ensure_adjoint_bufs()
+    {
+        ensure_lambda_bufs();
+        if (lam_bufs[0]->d_meta) return;
+        if (hipSetDevice(device) != hipSuccess) throw Exception("hipSetDevice failed (lexls_lsi_batch_solve_adjoint)");
+        for (uint32_t g = 0; g < nGroups; g++)
+        {
+            LambdaBufs &lb  = *lam_bufs[g];
+            const size_t Bg = grp[g]->B, cap = grp[g]->cap;
+            lb.types.assign(Bg * total, 0);
+            lb.meta.assign(2 * Bg, 0);
+            if (hipMalloc((void **)&lb.d_types, Bg * total ? Bg * total : 1) != hipSuccess || hipMalloc((void **)&lb.d_g, 8 * Bg * nVar) != hipSuccess ||
+                hipMalloc((void **)&lb.d_grad_rhs, 8 * Bg * (cap ? cap : 1)) != hipSuccess || hipMalloc((void **)&lb.d_grad_fixed, 8 * Bg * nVar) != hipSuccess ||
+                hipMalloc((void **)&lb.d_grad_lb, 8 * Bg * total) != hipSuccess || hipMalloc((void **)&lb.d_grad_ub, 8 * Bg * total) != hipSuccess ||
+                hipMalloc((void **)&lb.d_meta, 8 * Bg) != hipSuccess) // (last: its presence says that the others are there)
+                throw Exception("hipMalloc failed (lexls_lsi_batch_solve_adjoint)");
+        }
+    }
+
+    /// what lsi_adjoint_scatter_kernel reads next to the map, for instance k of group g: the activation type of every row of its final problem in
+    /// form_final_problem's row order, its status of the run and its number of fixed variables
+    void form_adjoint_routes(uint32_t g, uint32_t k, LambdaBufs &lb)
+    {
+        const uint32_t b   = lo[g] + k;
+        const uint16_t *na = ws_na.data() + (size_t)b * nObj;
+        const uint8_t *ty  = ws_type.data() + (size_t)b * total;
+        uint8_t *out       = lb.types.data() + (size_t)k * total;
+        const uint32_t nf  = off ? std::min<uint32_t>(na[0], nVar) : 0u;
+        uint32_t r         = 0;
+        for (uint32_t a = 0; a < nf; a++) out[r++] = ty[a];
+        for (uint32_t o = off; o < nObj; o++)
+            for (uint32_t a = 0; a < na[o]; a++) out[r++] = ty[first[o] + a];
+        lb.meta[2 * k]     = ws_status[b];
+        lb.meta[2 * k + 1] = static_cast<int32_t>(nf);
+    }
+
+    /// lexls_lsi_batch_solve_adjoint(_device): d loss / d lb and d loss / d ub of the last run from g = d loss / d x.  Per group, in its stream: the
+    /// final equality problems factorized with the factor kept (ensure_final_factor: get_lambda's stage, shared with it), their adjoint
+    /// (lexls_lse_solve_adjoint_device on the group's rows of g), lsi_adjoint_scatter_kernel into the user's constraint order.
+    /// on_device: g and the outputs are memory of the batch's device (nothing of them passes through the host); else the host's, staged in the
+    /// groups' buffers.  Either output may be NULL.  Waits for the groups' streams before it returns.
+    int solve_adjoint(const double *g_in, double *grad_lb, double *grad_ub, bool on_device)
+    {
+        const char *who = on_device ? "lexls_lsi_batch_solve_adjoint_device" : "lexls_lsi_batch_solve_adjoint";
+        if (lam_rc < 0) throw Exception(std::string(who) + ": no completed lexls_lsi_batch_run on this batch");
+        if (lam_rc != LEXLS_OK) // the rules of lexls_lsi_batch_get_lambda, and its reason
+        {
+            lexls_internal_set_error(lam_msg.c_str());
+            return lam_rc;
+        }
+        if (hipSetDevice(device) != hipSuccess) throw Exception(std::string(who) + ": hipSetDevice failed");
+        ensure_adjoint_bufs();
+        for (uint32_t g = 0; g < nGroups; g++)
+        {
+            BatchCtx &ctx         = *grp[g];
+            LambdaBufs &lb        = *lam_bufs[g];
+            const size_t rows     = (size_t)ctx.B * total, r0 = (size_t)lo[g] * total;
+            const bool any_active = ensure_final_factor(g, []() {});
+            if (!adj_uploaded[g])
+            {
+                pool->run(ctx.B, [&](uint32_t k) { form_adjoint_routes(g, k, lb); });
+                if (hipMemcpyAsync(lb.d_map, lb.map.data(), 4 * ((size_t)ctx.B + rows), hipMemcpyHostToDevice, ctx.stream) != hipSuccess ||
+                    hipMemcpyAsync(lb.d_types, lb.types.data(), rows, hipMemcpyHostToDevice, ctx.stream) != hipSuccess ||
+                    hipMemcpyAsync(lb.d_meta, lb.meta.data(), 8 * (size_t)ctx.B, hipMemcpyHostToDevice, ctx.stream) != hipSuccess)
+                    throw Exception(std::string(who) + ": hipMemcpyAsync failed (row map)");
+                adj_uploaded[g] = 1;
+            }
+            const double *d_g = g_in + (size_t)lo[g] * nVar;
+            double *d_lb = grad_lb ? grad_lb + r0 : NULL, *d_ub = grad_ub ? grad_ub + r0 : NULL;
+            if (!on_device)
+            {
+                // with an instance mask the entries of a skipped instance keep the caller's bits: they travel to the staging buffers first
+                if (hipMemcpyAsync(lb.d_g, d_g, 8 * (size_t)ctx.B * nVar, hipMemcpyHostToDevice, ctx.stream) != hipSuccess ||
+                    (group_mask(g) && grad_lb && hipMemcpyAsync(lb.d_grad_lb, grad_lb + r0, 8 * rows, hipMemcpyHostToDevice, ctx.stream) != hipSuccess) ||
+                    (group_mask(g) && grad_ub && hipMemcpyAsync(lb.d_grad_ub, grad_ub + r0, 8 * rows, hipMemcpyHostToDevice, ctx.stream) != hipSuccess))
+                    throw Exception(std::string(who) + ": hipMemcpyAsync failed (g)");
+                d_g = lb.d_g, d_lb = grad_lb ? lb.d_grad_lb : NULL, d_ub = grad_ub ? lb.d_grad_ub : NULL;
+            }
+            // nobody has an active constraint: nothing was factorized, every entry is zero — the scatter kernel reads no gradient (nact = 0)
+            if (any_active) hip_check(lexls_lse_solve_adjoint_device(ctx.h, d_g, lb.d_grad_rhs, lb.d_grad_fixed));
+            hipLaunchKernelGGL(lsi_adjoint_scatter_kernel, dim3(ctx.B), dim3(64), 0, ctx.stream, lb.d_grad_rhs, lb.d_grad_fixed, lb.d_map, lb.d_types, lb.d_meta, ctx.B,
+                               (uint32_t)total, nVar, ctx.cap, d_lb, d_ub, group_mask(g));
+            if (hipGetLastError() != hipSuccess) throw Exception("lsi_adjoint_scatter_kernel launch failed");
+            if (!on_device && ((grad_lb && hipMemcpyAsync(grad_lb + r0, lb.d_grad_lb, 8 * rows, hipMemcpyDeviceToHost, ctx.stream) != hipSuccess) ||
+                               (grad_ub && hipMemcpyAsync(grad_ub + r0, lb.d_grad_ub, 8 * rows, hipMemcpyDeviceToHost, ctx.stream) != hipSuccess)))
+                throw Exception(std::string(who) + ": hipMemcpyAsync failed (results)");
+        }
+        for (uint32_t g = 0; g < nGroups; g++)
+            if (hipStreamSynchronize(grp[g]->stream) != hipSuccess) throw Exception(std::string(who) + ": stream synchronisation failed");
+        return LEXLS_OK;
+    }
+
     /// LexLSI::getLambda (lexlsi.h:552-605) for every instance of the last run, on the device in each group's stream: the final equality
     /// problems are formed (rows gathered by reference, fixed variables posted), factorized with the factor kept on a bit-exact kernel, all
     /// objectives' multipliers taken in one sweep (lexls_lse_multipliers), scattered into the user's order, one copy back per group.
@@ -426,20 +620,7 @@ struct lexls_lsi_batch_s
         {
             BatchCtx &ctx  = *grp[g];
             LambdaBufs &lb = *lam_bufs[g];
-            pool->run(ctx.B, [&](uint32_t k) { form_final_problem(g, k, lb); });
-            stage(0, ctx);
-            bool any_active = false; // (a run whose mask skipped every instance of the group, or whose instances all ended with empty working sets)
-            for (uint32_t k = 0; k < ctx.B && !any_active; k++) any_active = lb.map[k] != 0;
-            // the equality solver's parameters of this run, whichever path it took (the one-by-one path of a non-resident deactivate_first_wrong_sign run never set
-            // them on these handles; an earlier run of the batch object may have left a regularization there): lam_rc == LEXLS_OK means unregularized
-            hip_check(lexls_lse_set_tolerance(ctx.h, lam_tol));
-            hip_check(lexls_lse_set_regularization(ctx.h, 0, NULL, 0, 0.0));
-            const int policy = lexls_internal_kernel_policy(ctx.h);
-            hip_check(lexls_lse_set_kernel_policy(ctx.h, 5)); // bit-exact kernels whatever the shape (the factor of the reference's getLambda)
-            int rc = any_active ? lexls_internal_upload_round_trusted(ctx.h, ctx.in_block.data(), 1) : LEXLS_OK;
-            if (rc == LEXLS_OK && any_active) rc = lexls_lse_factorize(ctx.h);
-            hip_check(lexls_lse_set_kernel_policy(ctx.h, policy));
-            hip_check(rc);
+            const bool any_active = ensure_final_factor(g, [&]() { stage(0, ctx); });
             stage(1, ctx);
             if (any_active) hip_check(lexls_lse_multipliers(ctx.h));
             stage(2, ctx);
@@ -692,6 +873,7 @@ struct lexls_lsi_batch_s
         const ParametersLexLSI par = with_log_switch(par_);
         begin_working_set_log();
         lam_rc  = -1;
+        forget_final_factor();
         lam_tol = par.tol_linear_dependence;
         last_kernel = "host";
         std::fill(cycling_count.begin(), cycling_count.end(), 0u);
@@ -1163,6 +1345,7 @@ struct lexls_lsi_batch_s
     {
         begin_working_set_log(); // (no host objects: every entry is written on the device)
         lam_rc      = -1;
+        forget_final_factor();
         lam_tol     = par.tol_linear_dependence;
         last_kernel = "host";
         std::fill(cycling_count.begin(), cycling_count.end(), 0u);
@@ -1230,6 +1413,7 @@ struct lexls_lsi_batch_s
         // the host's record of the last run: nothing of it is valid until finish()
         wlog_valid  = false;
         lam_rc      = -1;
+        forget_final_factor();
         lam_tol     = par.tol_linear_dependence;
         last_kernel = "host";
         std::fill(cycling_count.begin(), cycling_count.end(), 0u);
@@ -1306,6 +1490,7 @@ struct lexls_lsi_batch_s
         if (hipSetDevice(device) != hipSuccess || hipStreamSynchronize(s ? s : as.stream) != hipSuccess) throw Exception("lexls_lsi_batch_finish: stream synchronisation failed");
         as.pending  = false;
         lam_rc      = -1;
+        forget_final_factor();
         last_kernel = "host";
         wlog_valid  = false;
         std::fill(cycling_count.begin(), cycling_count.end(), 0u);

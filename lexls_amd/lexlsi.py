@@ -255,6 +255,7 @@ class LsiBatch:
         self.types = np.ascontiguousarray(types, np.int32)
         self.total = int(self.dims.sum())
         self._h = C.c_void_p()
+        self._run_serial = 0  # counts the runs started on this batch (run / run_device / enqueue_device): what a backward pass checks its forward run by
         self._log_entries = 0  # capacity per instance of the working-set log (set_working_set_log); 0: off
         self._instance_factors = None  # the device tensor (or address) set_instance_regularization was given: kept alive while the library reads it
         self._instance_mask = None  # the device tensor set_instance_mask was given: kept alive while the library reads it
@@ -387,6 +388,7 @@ class LsiBatch:
         if hasattr(self._instance_factors, "data_ptr"):
             import torch
             torch.cuda.synchronize(torch.device("cuda", self.device))  # what wrote the factor tensor is complete before the library's streams read it
+        self._run_serial += 1
         capi.check(capi.lib().lexls_lsi_batch_run(
             self._h, _p(pk.data, C.c_double), _p(pk.var_index, C.c_uint32), _p(guess, C.c_uint8), _p(x0a, C.c_double), _p(v0a, C.c_double), _p(rfa, C.c_double),
             _p(par, C.c_double), C.c_uint32(len(par)), _p(x, C.c_double), _p(info, C.c_int32), _p(active, C.c_uint8), _p(v, C.c_double),
@@ -453,6 +455,7 @@ class LsiBatch:
             r["lambda"] = torch.zeros((batch, len(self.dims), total), dtype=torch.float64, device=dev)
         if with_cycling_counters:
             r["cycling_counters"] = torch.zeros((batch,), dtype=torch.int32, device=dev)
+        self._run_serial += 1
         torch.cuda.synchronize(dev)  # the inputs (and the zeroed outputs) are complete before the library's own streams read and write them
         out = [C.c_void_p(x.data_ptr()), C.c_void_p(info.data_ptr()), C.c_void_p(active.data_ptr()), C.c_void_p(v.data_ptr())]
         if v0 is None and not with_lambda and not with_cycling_counters:
@@ -512,6 +515,7 @@ class LsiBatch:
                     r[k] = torch.zeros(shape, dtype=dtype, device=dev)
             else:
                 r[k] = torch.empty(shape, dtype=dtype, device=dev)  # (a raw stream: torch cannot order a fill in it; a good run writes every element)
+        self._run_serial += 1
         handle = stream.cuda_stream if isinstance(stream, torch.cuda.Stream) else int(stream)
         capi.check(capi.lib().lexls_lsi_batch_enqueue_device(
             self._h, C.c_void_p(handle), d_data, d_var, d_guess, d_x0, d_v0, _p(rfa, C.c_double), _p(par, C.c_double), C.c_uint32(len(par)),
@@ -585,6 +589,36 @@ class LsiBatch:
         lam = np.zeros((self.batch, len(self.dims), self.total))
         capi.check(capi.lib().lexls_lsi_batch_get_lambda(self._h, _p(lam, C.c_double)))
         return lam
+
+    def solve_adjoint(self, g):
+        """lexls_lsi_batch_solve_adjoint: `g` = dloss/dx of the last run, (batch, nvar).  Returns (grad_lb, grad_ub), numpy arrays of shape
+        (batch, total) in the constraint order of `active` / `v`: dloss/dlb and dloss/dub with the matrices held fixed.  An active constraint's
+        value is in grad_lb (active at its lower bound) or grad_ub (upper bound, equality); everything outside the final working set, and every
+        row of an instance that did not end PROBLEM_SOLVED, is exactly 0.  Raises after the runs lambdas() raises after."""
+        g = np.ascontiguousarray(g, np.float64)
+        if g.shape != (self.batch, self.nvar):
+            raise ValueError(f"solve_adjoint: g has shape {g.shape}, {(self.batch, self.nvar)} expected")
+        grad_lb, grad_ub = np.zeros((self.batch, self.total)), np.zeros((self.batch, self.total))
+        capi.check(capi.lib().lexls_lsi_batch_solve_adjoint(self._h, _p(g, C.c_double), _p(grad_lb, C.c_double), _p(grad_ub, C.c_double)))
+        return grad_lb, grad_ub
+
+    def solve_adjoint_device(self, g, grad_lb=None, grad_ub=None):
+        """lexls_lsi_batch_solve_adjoint_device: solve_adjoint() on torch tensors of the batch's device — `g` float64 (batch, nvar), `grad_lb` and
+        `grad_ub` float64 (batch, total), contiguous; an output that is not given is allocated (zeroed).  Returns (grad_lb, grad_ub).  Nothing of
+        them passes through host memory.  Under an instance mask the rows of a skipped instance keep their bits: pass the tensors that hold
+        them.  The call waits for the device, like run_device()."""
+        import torch
+        d_g = self._device_array("g", g, torch.float64, (self.batch, self.nvar), optional=False)
+        dev = torch.device("cuda", self.device)
+        if grad_lb is None:
+            grad_lb = torch.zeros((self.batch, self.total), dtype=torch.float64, device=dev)
+        if grad_ub is None:
+            grad_ub = torch.zeros((self.batch, self.total), dtype=torch.float64, device=dev)
+        d_lb = self._device_array("grad_lb", grad_lb, torch.float64, (self.batch, self.total), optional=False)
+        d_ub = self._device_array("grad_ub", grad_ub, torch.float64, (self.batch, self.total), optional=False)
+        torch.cuda.synchronize(dev)  # g (and the zeroed outputs) are complete before the library's own streams read and write them
+        capi.check(capi.lib().lexls_lsi_batch_solve_adjoint_device(self._h, d_g, d_lb, d_ub))
+        return grad_lb, grad_ub
 
     def lambdas(self):
         """per instance the list of per-objective (dim_k x nObj) multiplier matrices that frontend.lexlsi(..., debug=True) returns as

@@ -5,6 +5,10 @@ right-hand sides: x = M b (+ N x_fixed).  ``SolveRhs`` solves on the device from
 M^T (dloss/dx) from one pass over the kept factor (lexls_lse_solve_adjoint_device).  There are no derivatives with respect to A — x is not
 continuous in A where a rank changes — and asking for them raises instead of returning zeros.
 
+``SolveBounds`` is the same for a batch of LexLSI problems in their bounds: at a solved instance x is the basic solution of the equality
+problem of the final working set, affine in the active bounds while that set holds.  Forward is LsiBatch.run_device, backward
+LsiBatch.solve_adjoint_device (lexls_lsi_batch_solve_adjoint_device).
+
 torch is imported when the operation is first used, not with the package.
 """
 from __future__ import annotations
@@ -59,12 +63,82 @@ def _solve_rhs_class():
     return SolveRhs
 
 
+_SOLVE_BOUNDS = None
+
+
+def _solve_bounds_class():
+    global _SOLVE_BOUNDS
+    if _SOLVE_BOUNDS is not None:
+        return _SOLVE_BOUNDS
+    import torch
+    from torch.autograd.function import once_differentiable
+
+    def write_bounds_and_run(lb, ub, batch, data, var_index, active_guess, x0, params):
+        """lb / ub into the bound columns of data (per objective a column-major dim x w block, the last two columns), then run_device"""
+        off = first = 0
+        for d, t in zip((int(d) for d in batch.dims), (int(t) for t in batch.types)):
+            w = 2 if t == 1 else batch.nvar + 2
+            data[:, off + (w - 2) * d:off + (w - 1) * d] = lb[:, first:first + d]
+            data[:, off + (w - 1) * d:off + w * d] = ub[:, first:first + d]
+            off, first = off + d * w, first + d
+        return batch.run_device(data, var_index=var_index, active_guess=active_guess, x0=x0, **params)
+
+    class SolveBounds(torch.autograd.Function):
+        """x = SolveBounds.apply(lb, ub, batch, data, var_index, active_guess, x0, params, out): lb and ub (batch, sum(dims)) float64 on the device,
+        batch an LsiBatch, data (batch, per-instance data) float64 on the same device in the layout of LsiBatch.run_device — lb and ub are written
+        into its bound columns, in place.  var_index / active_guess / x0 as for run_device (or None), params a dict of its keyword parameters (or
+        None), out a dict that receives run_device's result (or None).  Forward: run_device; x (batch, nVar) comes back.  Backward:
+        solve_adjoint_device — the gradient of the piece of the piecewise-affine map the solve ended on, zero for instances that did not end
+        PROBLEM_SOLVED.  Gradients: lb and ub only.  The backward pass reads the state the forward run left in `batch`; when the batch has run
+        again in between, the forward run is repeated from the saved bounds first (data is written again)."""
+
+        @staticmethod
+        def forward(ctx, lb, ub, batch, data, var_index=None, active_guess=None, x0=None, params=None, out=None):
+            if data.requires_grad:
+                raise ValueError("SolveBounds: data requires grad, but the solve has no derivatives with respect to A (x is not continuous in A "
+                                 "at rank changes); detach data")
+            shape = (batch.batch, batch.total)
+            for name, t in (("lb", lb), ("ub", ub)):
+                if tuple(t.shape) != shape or t.dtype != torch.float64 or t.device != data.device:
+                    raise ValueError(f"SolveBounds: {name} must be a float64 tensor of shape {shape} on data's device")
+            params = dict(params or {})
+            lb0, ub0 = lb.detach().clone(), ub.detach().clone()
+            r = write_bounds_and_run(lb0, ub0, batch, data, var_index, active_guess, x0, params)
+            if out is not None:
+                out.update(r)
+            ctx.batch, ctx.serial = batch, batch._run_serial
+            ctx.rerun = (lb0, ub0, data, var_index, active_guess, x0, params)
+            return r["x"]
+
+        @staticmethod
+        @once_differentiable
+        def backward(ctx, grad_x):
+            batch = ctx.batch
+            if batch._run_serial != ctx.serial:  # another run has replaced the state this pass reads: the same run again
+                lb0, ub0, data, var_index, active_guess, x0, params = ctx.rerun
+                write_bounds_and_run(lb0, ub0, batch, data, var_index, active_guess, x0, params)
+                ctx.serial = batch._run_serial
+            grad_lb, grad_ub = batch.solve_adjoint_device(grad_x.contiguous())
+            return grad_lb, grad_ub, None, None, None, None, None, None, None
+
+    _SOLVE_BOUNDS = SolveBounds
+    return SolveBounds
+
+
 def __getattr__(name):
     if name == "SolveRhs":
         return _solve_rhs_class()
+    if name == "SolveBounds":
+        return _solve_bounds_class()
     raise AttributeError(f"module {__name__!r} has no attribute {name!r}")
 
 
 def solve_rhs(rhs, lse, lod):
     """SolveRhs.apply(rhs, lse, lod)"""
     return _solve_rhs_class().apply(rhs, lse, lod)
+
+
+def solve_bounds(lb, ub, batch, data, var_index=None, active_guess=None, x0=None, out=None, **params):
+    """SolveBounds.apply(lb, ub, batch, data, var_index, active_guess, x0, params, out): the solutions of a LexLSI batch, differentiable in the
+    bounds.  `params`: the keyword parameters of LsiBatch.run_device; `out`: a dict that receives its result ("x", "info", "active", "v")."""
+    return _solve_bounds_class().apply(lb, ub, batch, data, var_index, active_guess, x0, params, out)
