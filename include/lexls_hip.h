@@ -233,6 +233,29 @@ int lexls_lse_solve_adjoint(lexls_lse_t h, const double *h_g);
 int lexls_lse_get_adjoint(lexls_lse_t h, double *h_grad_rhs, double *h_grad_fixed);
 int lexls_lse_solve_adjoint_device(lexls_lse_t h, const double *d_g, double *d_grad_rhs, double *d_grad_fixed);
 
+/* The same adjoint for MANY cotangents per problem in one pass over the kept factor: ncot vector-Jacobian products, the Jacobian dx/db with the
+ * identity as cotangents (ncot = nVar), batched gradients.  One wavefront serves a problem and a tile of up to 64 cotangents, lane = cotangent.
+ * Layouts: G is batch x ncot x nVar, cotangent c of problem b in the variable order of lexls_lse_get_x; grad_rhs is batch x ncot x cap in LOD
+ * row order, zero in the rows behind a problem's own; grad_fixed is batch x ncot x nVar, zero from nfixed on (NULL: not wanted).
+ * lexls_lse_solve_adjoint_multi copies h_G in, launches and keeps the results in buffers of the handle; lexls_lse_get_adjoint_multi copies them
+ * out (batch x ncot x cap and batch x ncot x nVar for the ncot of that call, either output may be NULL); both follow
+ * lexls_lse_set_deferred_sync, and lexls_lse_get_adjoint_multi answers only while the results belong to the current factor, as
+ * lexls_lse_get_adjoint does.  lexls_lse_solve_adjoint_multi_device reads d_G and writes d_grad_rhs and d_grad_fixed in device memory: it only
+ * enqueues in the handle's stream and makes no host-synchronising call (the buffers of the per-cotangent form below are allocated at the first
+ * call that needs them); d_G has to be complete in stream order.
+ * Independence contract: the result of a cotangent does not depend on ncot, on its position in G, or on the other cotangents — it is bit for
+ * bit the same; the same bits come back from run to run and from the host and the device form.  It is NOT promised to be bit-equal to
+ * lexls_lse_solve_adjoint (the summation order differs): against that call, and against any reference, the contract is the tolerance one.
+ * Errors, each returned before any device work and with every output left alone: LEXLS_ERR_INVALID for a null handle, a null G or a null
+ * d_grad_rhs; LEXLS_ERR_INVALID for ncot == 0; LEXLS_ERR_INVALID when there is no kept factor; LEXLS_ERR_UNSUPPORTED when the factorization
+ * ran with regularization_type != 0.
+ * Kernel variant (lexls_lse_last_consumer_kernel), decided on the host from nVar and cap alone: "solve_adjoint_multi<64,staged>" — the
+ * per-lane state and the staged factor fit one workgroup's 160 KiB of LDS; "solve_adjoint_multi<64,hbm>" — the state alone fits, the factor
+ * is read where it is kept; "solve_adjoint<64> x K" — neither: the single-cotangent kernel once per cotangent. */
+int lexls_lse_solve_adjoint_multi(lexls_lse_t h, const double *h_G, uint32_t ncot);
+int lexls_lse_get_adjoint_multi(lexls_lse_t h, double *h_grad_rhs, double *h_grad_fixed);
+int lexls_lse_solve_adjoint_multi_device(lexls_lse_t h, const double *d_G, uint32_t ncot, double *d_grad_rhs, double *d_grad_fixed);
+
 /* ---- results (synchronise the stream, then D2H) ------------------------------------------------- */
 int lexls_lse_get_x(lexls_lse_t h, double *h_x);                    /* get_x()      lexlse.h:1587 */
 int lexls_lse_get_factor(lexls_lse_t h, double *h_lod);             /* get_lexqr()  lexlse.h:1626 */
@@ -705,6 +728,15 @@ int lexls_lsi_batch_get_lambda(lexls_lsi_batch_t b, double *h_lambda);
  * handling, a regularized run, more than 65535 constraints, constraint data not resident), with that call's reason in lexls_last_error(). */
 int lexls_lsi_batch_solve_adjoint(lexls_lsi_batch_t b, const double *h_g, double *h_grad_lb, double *h_grad_ub);
 int lexls_lsi_batch_solve_adjoint_device(lexls_lsi_batch_t b, const double *d_g, double *d_grad_lb, double *d_grad_ub);
+/* lexls_lsi_batch_solve_adjoint(_device) for ncot cotangents per instance in one pass: lexls_lse_solve_adjoint_multi_device on the final factor
+ * (shared with lexls_lsi_batch_get_lambda and lexls_lsi_batch_solve_adjoint in every call order: nothing is factorized twice), then
+ * lsi_adjoint_scatter_multi_kernel.  Layouts: G is batch x ncot x nVar; grad_lb and grad_ub are batch x ncot x sum(dims), row c of instance b
+ * what lexls_lsi_batch_solve_adjoint returns for g = G[b][c] (tolerance contract; the exact zeros at the same entries).  Either output may be
+ * NULL.  The status rule (exact zeros unless PROBLEM_SOLVED), the mask rule (a skipped instance keeps the bits of all its ncot rows) and the
+ * absent-row rule are those of lexls_lsi_batch_solve_adjoint, and so are the errors, with LEXLS_ERR_INVALID for ncot == 0 added: each is
+ * returned before any device work and with every output left alone.  The independence contract of lexls_lse_solve_adjoint_multi holds. */
+int lexls_lsi_batch_solve_adjoint_multi(lexls_lsi_batch_t b, const double *h_G, uint32_t ncot, double *h_grad_lb, double *h_grad_ub);
+int lexls_lsi_batch_solve_adjoint_multi_device(lexls_lsi_batch_t b, const double *d_G, uint32_t ncot, double *d_grad_lb, double *d_grad_ub);
 /* LexLSI::getCyclingCounter() (lexlsi.h, CyclingHandler::get_counter, cycling.h) of every instance of the LAST lexls_lsi_batch_run on this batch:
  * h_counts receives `batch` values, the bounds each instance's cycling handler relaxed (the working-set log's cycling_detected entries, counted).
  * Whatever path served the run: host path, lock-step stages, persistent launch, one by one through the single-problem driver.  All zeros after a

@@ -29,6 +29,7 @@ SYMBOLS = [
     "lexls_lse_set_prefix_reuse", "lexls_lse_prefix_reuse_ready", "lexls_lse_set_resume_levels",
     "lexls_lsi_solve", "lexls_lsi_solve_dat", "lexls_lsi_batch_solve",
     "lexls_lse_multipliers", "lexls_lse_get_multipliers", "lexls_lse_solve_adjoint", "lexls_lse_get_adjoint", "lexls_lse_solve_adjoint_device",
+    "lexls_lse_solve_adjoint_multi", "lexls_lse_get_adjoint_multi", "lexls_lse_solve_adjoint_multi_device",
     "lexls_lsi_batch_get_lambda", "lexls_lsi_batch_solve_ex2",
     "lexls_lse_sensitivity_collect", "lexls_lse_sensitivity_collect_resident", "lexls_lse_get_wrong_sign",
     "lexls_lsi_batch_get_cycling_counters", "lexls_lsi_batch_run_device", "lexls_lsi_batch_run_device_ex",
@@ -37,6 +38,7 @@ SYMBOLS = [
     "lexls_lsi_batch_enqueue_device", "lexls_lsi_batch_finish",
     "lexls_lsi_batch_set_instance_mask", "lexls_lsi_batch_set_instance_max_factorizations", "lexls_lsi_batch_set_instance_obj_dims",
     "lexls_lsi_batch_solve_adjoint", "lexls_lsi_batch_solve_adjoint_device",
+    "lexls_lsi_batch_solve_adjoint_multi", "lexls_lsi_batch_solve_adjoint_multi_device",
     "lexls_lsi_batch_last_kernel",
 ]
 
@@ -121,6 +123,16 @@ def lib() -> C.CDLL:
         _lib.lexls_lsi_batch_solve_adjoint.argtypes = [C.c_void_p, C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_double)]
         _lib.lexls_lsi_batch_solve_adjoint_device.restype = C.c_int
         _lib.lexls_lsi_batch_solve_adjoint_device.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]  # d_g, d_grad_lb, d_grad_ub: device addresses
+        _lib.lexls_lse_solve_adjoint_multi.restype = C.c_int
+        _lib.lexls_lse_solve_adjoint_multi.argtypes = [C.c_void_p, C.POINTER(C.c_double), C.c_uint32]
+        _lib.lexls_lse_get_adjoint_multi.restype = C.c_int
+        _lib.lexls_lse_get_adjoint_multi.argtypes = [C.c_void_p, C.POINTER(C.c_double), C.POINTER(C.c_double)]
+        _lib.lexls_lse_solve_adjoint_multi_device.restype = C.c_int
+        _lib.lexls_lse_solve_adjoint_multi_device.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p]  # d_G, ncot, d_grad_rhs, d_grad_fixed
+        _lib.lexls_lsi_batch_solve_adjoint_multi.restype = C.c_int
+        _lib.lexls_lsi_batch_solve_adjoint_multi.argtypes = [C.c_void_p, C.POINTER(C.c_double), C.c_uint32, C.POINTER(C.c_double), C.POINTER(C.c_double)]
+        _lib.lexls_lsi_batch_solve_adjoint_multi_device.restype = C.c_int
+        _lib.lexls_lsi_batch_solve_adjoint_multi_device.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p]  # d_G, ncot, d_grad_lb, d_grad_ub
     return _lib
 
 

@@ -95,6 +95,12 @@ struct lexls_lse_s
     double *d_adj_g = nullptr, *d_adj_rhs = nullptr, *d_adj_fixed = nullptr;
     bool adj_valid     = false;
     uint64_t adj_epoch = 0; // factor_epoch the gradients belong to
+    // lexls_lse_solve_adjoint_multi: G (batch x ncot x nVar), grad_rhs (batch x ncot x cap), grad_fixed (batch x ncot x nVar) of a host caller, made
+    // for the largest ncot so far; d_adjm_work: the buffers of the per-cotangent form (launch_solve_adjoint_multi), made at the first call that needs them
+    double *d_adjm_G = nullptr, *d_adjm_rhs = nullptr, *d_adjm_fixed = nullptr, *d_adjm_work = nullptr;
+    uint32_t adjm_room = 0, adjm_ncot = 0; // cotangents the three buffers have room for; cotangents of the last lexls_lse_solve_adjoint_multi
+    bool adjm_valid     = false;
+    uint64_t adjm_epoch = 0;
     // accuracy guard (lexls_lse_set_accuracy_guard): mode 0 off, 1 report, 2 report + re-solve; arrays allocated when first switched on
     int guard_mode           = 0;
     double guard_threshold   = 0.0;
@@ -289,7 +295,8 @@ extern "C"
         (void)hipSetDevice(h->device);
         void *ptrs[] = {h->d_in_owned, h->d_fac, h->d_hh, h->d_v, h->d_lambda, h->d_scratch, h->d_perm, h->d_rank, h->d_fcol, h->d_round_in, h->d_round_out,
                         h->d_large_state, h->d_large_ws, h->d_norms, h->d_cdata, h->d_reg_factor, h->d_reg_scratch, h->d_reg_mu, h->d_resume_level, h->d_resume_state,
-                        h->d_guard_est, h->d_guard_status, h->d_guard_ind, h->d_mult, h->d_mult_scratch, h->d_wrong_sign, h->d_adj_g, h->d_adj_rhs, h->d_adj_fixed};
+                        h->d_guard_est, h->d_guard_status, h->d_guard_ind, h->d_mult, h->d_mult_scratch, h->d_wrong_sign, h->d_adj_g, h->d_adj_rhs, h->d_adj_fixed,
+                        h->d_adjm_G, h->d_adjm_rhs, h->d_adjm_fixed, h->d_adjm_work};
         for (void *p : ptrs)
             if (p) (void)hipFree(p);
         if (h->h_dims_pinned) (void)hipHostFree(h->h_dims_pinned);
@@ -1061,6 +1068,74 @@ extern "C"
         HIP_TRY(hipSetDevice(h->device));
         if (h_grad_rhs) HIP_TRY(hipMemcpyAsync(h_grad_rhs, h->d_adj_rhs, 8 * (size_t)h->batch * h->cap, hipMemcpyDeviceToHost, h->stream));
         if (h_grad_fixed) HIP_TRY(hipMemcpyAsync(h_grad_fixed, h->d_adj_fixed, 8 * (size_t)h->batch * h->nVar, hipMemcpyDeviceToHost, h->stream));
+        if (!h->deferred_sync) HIP_TRY(hipStreamSynchronize(h->stream));
+        return LEXLS_OK;
+    }
+
+    /// what both multi-cotangent forms check before any device work, and the per-cotangent form's buffers (made at the first call that needs them)
+    static int need_adjoint_multi(lexls_lse_t h, const char *who, const void *G, uint32_t ncot)
+    {
+        CHECK_HANDLE(h);
+        if (!G) return fail(LEXLS_ERR_INVALID, std::string(who) + ": null G");
+        if (ncot == 0) return fail(LEXLS_ERR_INVALID, std::string(who) + ": ncot == 0");
+        return need_adjoint_factor(h, who, G);
+    }
+    static int adjoint_multi_work(lexls_lse_t h)
+    {
+        const size_t bytes = adjoint_multi_work_bytes(h->args());
+        if (bytes && !h->d_adjm_work) HIP_TRY(hipMalloc((void **)&h->d_adjm_work, bytes));
+        return LEXLS_OK;
+    }
+
+    int lexls_lse_solve_adjoint_multi(lexls_lse_t h, const double *h_G, uint32_t ncot)
+    {
+        if (int rc = need_adjoint_multi(h, "lexls_lse_solve_adjoint_multi", h_G, ncot)) return rc;
+        HIP_TRY(hipSetDevice(h->device));
+        const size_t B = h->batch, n = h->nVar, cap = h->cap;
+        if (ncot > h->adjm_room)
+        {
+            h->adjm_valid = false;
+            h->adjm_room  = 0;
+            for (double **p : {&h->d_adjm_G, &h->d_adjm_rhs, &h->d_adjm_fixed})
+            {
+                if (*p) (void)hipFree(*p); // (waits for whatever still reads it)
+                *p = nullptr;
+            }
+            HIP_TRY(hipMalloc((void **)&h->d_adjm_G, 8 * B * ncot * n));
+            HIP_TRY(hipMalloc((void **)&h->d_adjm_rhs, 8 * B * ncot * cap));
+            HIP_TRY(hipMalloc((void **)&h->d_adjm_fixed, 8 * B * ncot * n));
+            h->adjm_room = ncot;
+        }
+        if (int rc = adjoint_multi_work(h)) return rc;
+        HIP_TRY(hipMemcpyAsync(h->d_adjm_G, h_G, 8 * B * ncot * n, hipMemcpyHostToDevice, h->stream));
+        if (!h->deferred_sync) HIP_TRY(hipStreamSynchronize(h->stream)); // h_G may be reused by the caller
+        HIP_TRY(launch_solve_adjoint_multi(h->args(), h->d_adjm_G, ncot, h->d_adjm_rhs, h->d_adjm_fixed, h->d_adjm_work, h->stream, &h->last_consumer));
+        h->adjm_valid = true;
+        h->adjm_ncot  = ncot;
+        h->adjm_epoch = h->factor_epoch;
+        return LEXLS_OK;
+    }
+
+    int lexls_lse_solve_adjoint_multi_device(lexls_lse_t h, const double *d_G, uint32_t ncot, double *d_grad_rhs, double *d_grad_fixed)
+    {
+        if (int rc = need_adjoint_multi(h, "lexls_lse_solve_adjoint_multi_device", d_G, ncot)) return rc;
+        if (!d_grad_rhs) return fail(LEXLS_ERR_INVALID, "lexls_lse_solve_adjoint_multi_device: null d_grad_rhs");
+        HIP_TRY(hipSetDevice(h->device));
+        if (int rc = adjoint_multi_work(h)) return rc;
+        HIP_TRY(launch_solve_adjoint_multi(h->args(), d_G, ncot, d_grad_rhs, d_grad_fixed, h->d_adjm_work, h->stream, &h->last_consumer));
+        return LEXLS_OK;
+    }
+
+    int lexls_lse_get_adjoint_multi(lexls_lse_t h, double *h_grad_rhs, double *h_grad_fixed)
+    {
+        CHECK_HANDLE(h);
+        if (!h->adjm_valid) return fail(LEXLS_ERR_INVALID, "lexls_lse_get_adjoint_multi: call lexls_lse_solve_adjoint_multi first");
+        if (!h->factor_valid || h->adjm_epoch != h->factor_epoch)
+            return fail(LEXLS_ERR_INVALID, "lexls_lse_get_adjoint_multi: the problem or its factorization changed since lexls_lse_solve_adjoint_multi (call it again)");
+        HIP_TRY(hipSetDevice(h->device));
+        const size_t rows = (size_t)h->batch * h->adjm_ncot;
+        if (h_grad_rhs) HIP_TRY(hipMemcpyAsync(h_grad_rhs, h->d_adjm_rhs, 8 * rows * h->cap, hipMemcpyDeviceToHost, h->stream));
+        if (h_grad_fixed) HIP_TRY(hipMemcpyAsync(h_grad_fixed, h->d_adjm_fixed, 8 * rows * h->nVar, hipMemcpyDeviceToHost, h->stream));
         if (!h->deferred_sync) HIP_TRY(hipStreamSynchronize(h->stream));
         return LEXLS_OK;
     }

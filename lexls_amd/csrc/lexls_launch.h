@@ -13,6 +13,13 @@ namespace lexls
     /// lexls_lse_solve_adjoint: d_grad_rhs (batch x cap) = M^T g, d_grad_fixed (batch x nVar, may be NULL) = N^T g for x = M b + N x_fixed of the
     /// kept factor; d_g is batch x nVar in the order of x.  One wavefront per problem, enqueued only
     hipError_t launch_solve_adjoint(const LseArgs &a, const double *d_g, double *d_grad_rhs, double *d_grad_fixed, hipStream_t s, const char **variant = nullptr);
+    /// lexls_lse_solve_adjoint_multi: ncot cotangents per problem in one pass, d_G batch x ncot x nVar, d_grad_rhs batch x ncot x cap, d_grad_fixed
+    /// batch x ncot x nVar (may be NULL).  The form follows from the shape (adjoint_multi_form, lexls_lds.h): lane = cotangent with the factor staged
+    /// in LDS, the same with the factor read where it is kept, or launch_solve_adjoint once per cotangent through d_work (adjoint_multi_work_bytes,
+    /// 0 where the shape needs none).  Enqueued only
+    size_t adjoint_multi_work_bytes(const LseArgs &a);
+    hipError_t launch_solve_adjoint_multi(const LseArgs &a, const double *d_G, uint32_t ncot, double *d_grad_rhs, double *d_grad_fixed, double *d_work, hipStream_t s,
+                                          const char **variant = nullptr);
     hipError_t launch_sensitivity(const LseArgs &a, const int32_t *d_obj_index, int32_t obj_all, double tolW, double tolC, hipStream_t s, bool scan_up = false,
                                   uint32_t sweep_level_dim_hint = 0, // hint = largest level dimension of the batch (enables the single-sweep kernel)
                                   bool collect = false,              // the wrong-sign SET into a.wrong_sign instead of one candidate (lexls_lse_sensitivity_collect)

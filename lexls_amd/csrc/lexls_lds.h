@@ -211,5 +211,30 @@ namespace lexls
     /// g in factor column order (nVar doubles), the gradient of the right-hand side with y inside it (cap doubles), the transpositions (nVar words)
     inline size_t adjoint_lds_bytes(uint32_t nVar, uint32_t cap) { return (8 * ((size_t)nVar + cap) + 4 * (size_t)nVar + 15) & ~(size_t)15; }
 
+    // ---- solve_adjoint_multi (lqr_generic.hip): lane = cotangent ----
+    constexpr uint32_t kAdjointMultiLd = 65; // odd leading dimension of the per-lane state, stored [index][lane]
+    /// the per-lane state gh (nVar) and cb (cap), [index][lane] with leading dimension 65; the transpositions and the position every variable
+    /// reaches by them (2 x nVar words, shared by the lanes); staged: + the problem's factor without its right-hand-side column (odd leading
+    /// dimension, as stage_factor writes it) and hh (cap doubles)
+    inline size_t adjoint_multi_lds_bytes(uint32_t nVar, uint32_t cap, bool staged)
+    {
+        size_t b = 8 * (size_t)kAdjointMultiLd * ((size_t)nVar + cap) + 8 * (size_t)nVar;
+        if (staged) b += 8 * ((size_t)odd_ld(cap) * nVar + cap);
+        return (b + 15) & ~(size_t)15;
+    }
+    /// the fit rule of lexls_lse_solve_adjoint_multi, decided from the shape alone: state + staged factor in one workgroup's LDS; else the state
+    /// alone (the factor read from global memory at wavefront-uniform addresses); else the single-cotangent kernel once per cotangent
+    enum class AdjointMultiForm { staged, hbm, per_cotangent };
+    inline AdjointMultiForm adjoint_multi_form(uint32_t nVar, uint32_t cap)
+    {
+        if (adjoint_multi_lds_bytes(nVar, cap, true) <= kMaxLdsBytes) return AdjointMultiForm::staged;
+        if (adjoint_multi_lds_bytes(nVar, cap, false) <= kMaxLdsBytes) return AdjointMultiForm::hbm;
+        return AdjointMultiForm::per_cotangent;
+    }
+    inline const char *adjoint_multi_form_name(AdjointMultiForm f)
+    {
+        return f == AdjointMultiForm::staged ? "solve_adjoint_multi<64,staged>" : f == AdjointMultiForm::hbm ? "solve_adjoint_multi<64,hbm>" : "solve_adjoint<64> x K";
+    }
+
     // ---- lqr_large (lqr_large.hip): lqr_large_plan.h ----
 } // namespace lexls

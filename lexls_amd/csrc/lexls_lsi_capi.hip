@@ -268,6 +268,30 @@ extern "C"
         return lsi_batch_solve_adjoint(b, d_g, d_grad_lb, d_grad_ub, true);
     }
 
+    /// both forms of the multi-cotangent adjoint: the refusals of lsi_batch_solve_adjoint, and ncot == 0
+    static int lsi_batch_solve_adjoint_multi(lexls_lsi_batch_t b, const double *G, uint32_t ncot, double *grad_lb, double *grad_ub, bool on_device)
+    {
+        return guarded([&]() {
+            const std::string who = on_device ? "lexls_lsi_batch_solve_adjoint_multi_device" : "lexls_lsi_batch_solve_adjoint_multi";
+            if (!b) throw Exception(who + ": null handle");
+            if (!G) throw Exception(who + ": null G");
+            if (ncot == 0) throw Exception(who + ": ncot == 0");
+            if (!grad_lb && !grad_ub) throw Exception(who + ": both outputs are null");
+            b->refuse_pending(who.c_str());
+            return b->solve_adjoint_multi(G, ncot, grad_lb, grad_ub, on_device);
+        });
+    }
+
+    int lexls_lsi_batch_solve_adjoint_multi(lexls_lsi_batch_t b, const double *h_G, uint32_t ncot, double *h_grad_lb, double *h_grad_ub)
+    {
+        return lsi_batch_solve_adjoint_multi(b, h_G, ncot, h_grad_lb, h_grad_ub, false);
+    }
+
+    int lexls_lsi_batch_solve_adjoint_multi_device(lexls_lsi_batch_t b, const double *d_G, uint32_t ncot, double *d_grad_lb, double *d_grad_ub)
+    {
+        return lsi_batch_solve_adjoint_multi(b, d_G, ncot, d_grad_lb, d_grad_ub, true);
+    }
+
     int lexls_lsi_batch_get_cycling_counters(lexls_lsi_batch_t b, uint32_t *h_counts)
     {
         return guarded([&]() {

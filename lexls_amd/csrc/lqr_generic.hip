@@ -21,6 +21,7 @@
 
 #include <cfloat>
 #include <cstdlib>
+#include <cstring>
 
 namespace lexls
 {
@@ -1282,6 +1283,184 @@ namespace lexls
             __syncthreads();
         }
 
+        /// solve_adjoint_kernel's steps (a)-(d) for up to 64 cotangents of one problem at once, LANE = COTANGENT: one wavefront per (problem,
+        /// tile of 64 cotangents), lane l of tile t owns cotangent 64 t + l; lanes beyond ncot compute on zeros and store nothing.  Everything
+        /// that steers the control flow (dims, ranks, first columns, tau == 0) belongs to the problem, so it is wavefront-uniform; every factor
+        /// entry is the same for all lanes (STAGED: a broadcast read of the image stage_factor left in LDS; else a read of the stored factor at
+        /// a wavefront-uniform address); every dot product is the lane's own serial dfma chain in ascending row order — no cross-lane
+        /// reduction and no barrier between the steps, and a cotangent's bits do not depend on its lane, its tile or its neighbours.
+        /// LDS (adjoint_multi_lds_bytes): gh[nVar][LD], cb[cap][LD], LD = 65 (odd: "lane = cotangent" walks take consecutive words, the
+        /// transposed walks of the load and store phases a stride of 65 words — both conflict-free), the transpositions and the position
+        /// each variable reaches (2 nVar words), then STAGED the factor's nVar columns (odd leading dimension) and hh.
+        /// Global traffic: a tile's rows of G, grad_rhs and grad_fixed are contiguous; consecutive lanes take consecutive addresses and the
+        /// transposition happens in LDS.  No atomics.
+        template <int NT, bool STAGED>
+        __global__ __launch_bounds__(NT) void solve_adjoint_multi_kernel(LseArgs a, const double *__restrict__ G, uint32_t ncot, double *__restrict__ grad_rhs,
+                                                                         double *__restrict__ grad_fixed)
+        {
+            static_assert(NT == 64, "one wavefront per (problem, tile): lane = cotangent");
+            constexpr uint32_t LD = kAdjointMultiLd, AU = 4;
+            extern __shared__ double smem[];
+            const uint32_t b = blockIdx.x, tile = blockIdx.y, lane = threadIdx.x;
+            const uint32_t n = a.nVar, cap = a.cap, nObj = a.nObj;
+            if (b >= a.batch || tile * 64u >= ncot) return; // (block-uniform)
+            const uint32_t kt = ncot - tile * 64u < 64u ? ncot - tile * 64u : 64u; // live cotangents of this tile
+            const double *__restrict__ W = a.fac + (size_t)b * cap * (n + 1);
+            const uint32_t *dims = a.dims + (size_t)b * nObj;
+            const uint32_t *rk = a.rank + (size_t)b * nObj, *fc = a.fcol + (size_t)b * nObj;
+            double *gh       = smem;
+            double *cb       = gh + (size_t)n * LD;
+            uint32_t *perm_l = reinterpret_cast<uint32_t *>(cb + (size_t)cap * LD);
+            uint32_t *pos_l  = perm_l + n;
+            double *L        = reinterpret_cast<double *>(pos_l + n); // (2 n words: still 8-byte aligned)
+            const uint32_t ldl = cap | 1u; // odd_ld(cap)
+            double *hh_l       = L + (size_t)ldl * n;
+            const double *hh_g = a.hh + (size_t)b * cap;
+            const uint32_t nf = a.nfixed ? (a.nfixed[b] < n ? a.nfixed[b] : n) : 0;
+            const uint32_t T  = a.totalrank[b] < n ? a.totalrank[b] : n; // pivot columns: [nf, T)
+            uint32_t M = 0;
+            for (uint32_t k = 0; k < nObj; k++) M += dims[k];
+            if (M > cap) M = cap;
+            auto level = [&](uint32_t k, uint32_t dim, uint32_t &rank, uint32_t &Fc) __attribute__((always_inline)) {
+                Fc   = fc[k];
+                rank = (nf < n && Fc < T) ? rk[k] : 0; // (every variable fixed: factorize() returns before the levels)
+                if (rank > dim) rank = dim;
+                if (rank > T - (Fc < T ? Fc : T)) rank = T - (Fc < T ? Fc : T);
+            };
+            // entry (r, c) of the factor, r < M <= cap, c < T <= nVar; the Householder scalar of row r < cap
+            auto Wat = [&](uint32_t r, uint32_t c) __attribute__((always_inline)) -> double { return STAGED ? L[r + c * ldl] : W[r + (size_t)c * cap]; };
+            auto tau_at = [&](uint32_t r) __attribute__((always_inline)) -> double { return STAGED ? hh_l[r] : hh_g[r]; };
+
+            // ---- staging, and (a) gh = P^T g for every cotangent of the tile ----
+            for (uint32_t i = lane; i < n; i += NT) perm_l[i] = a.perm[(size_t)b * n + i];
+            for (uint32_t i = lane; i < (n + cap) * LD; i += NT) smem[i] = 0.0; // gh and cb (dead lanes, absent rows, unreached positions: zeros)
+            if (STAGED)
+            {
+                for (uint32_t i = lane; i < cap; i += NT) hh_l[i] = hh_g[i];
+                stage_factor<NT>(W, L, cap, n, ldl, lane); // (ends in a barrier)
+            }
+            else
+                __syncthreads();
+            for (uint32_t i = lane; i < n; i += NT)
+            {
+                uint32_t p = i;
+                for (uint32_t k = 0; k < T; k++)
+                {
+                    const uint32_t pk = perm_l[k];
+                    p                 = (p == k) ? pk : ((p == pk) ? k : p);
+                }
+                pos_l[i] = p;
+            }
+            __syncthreads();
+            {
+                const double *Gt = G + ((size_t)b * ncot + (size_t)tile * 64u) * n; // kt rows of n doubles, contiguous
+                for (uint32_t e = lane; e < kt * n; e += NT)
+                {
+                    const uint32_t c = e / n, i = e - c * n, p = pos_l[i];
+                    if (p < n) gh[p * LD + c] = Gt[e];
+                }
+            }
+            __syncthreads();
+            double *ghl = gh + lane, *cbl = cb + lane; // this lane's column of the state
+
+            // ---- (b) the reverse of solve(), levels ascending ----
+            uint32_t F = 0;
+            for (uint32_t k = 0; k < nObj; k++)
+            {
+                const uint32_t dim = dims[k];
+                uint32_t rank, Fc;
+                level(k, dim, rank, Fc);
+                if (rank > 0 && F + dim <= M)
+                {
+                    double *y = cbl + F * LD;
+                    for (uint32_t c = Fc; c < T; c++)
+                    {
+                        const uint32_t j = c - Fc, len = j < rank ? j : rank;
+                        double s = 0.0;
+                        for (uint32_t i = 0; i < len; i++) s = dfma(Wat(F + i, c), y[i * LD], s);
+                        if (j < rank) // (uniform) inside the triangle
+                            y[j * LD] = (ghl[c * LD] - s) / Wat(F + j, c);
+                        else
+                            ghl[c * LD] -= s;
+                    }
+                }
+                F += dim;
+            }
+
+            // ---- (c) the reverse of factorize()'s right-hand-side updates, levels descending ----
+            uint32_t Fend = 0;
+            for (uint32_t k = 0; k < nObj; k++) Fend += dims[k];
+            for (uint32_t k = nObj; k--;)
+            {
+                const uint32_t dim = dims[k];
+                F                  = Fend - dim;
+                Fend               = F;
+                uint32_t rank, Fc;
+                level(k, dim, rank, Fc);
+                if (rank == 0 || F + dim > M) continue;
+                const uint32_t Fn = F + dim;
+                if (k + 1 < nObj && Fn < M)
+                {
+                    // the transposed Gauss step: AU multiplier columns share one read of the lane's cb rows (each sum in ascending row order)
+                    for (uint32_t p0 = 0; p0 < rank; p0 += AU)
+                    {
+                        double s[AU];
+#pragma unroll
+                        for (uint32_t u = 0; u < AU; u++) s[u] = 0.0;
+                        for (uint32_t i = Fn; i < M; i++)
+                        {
+                            const double ci = cbl[i * LD];
+#pragma unroll
+                            for (uint32_t u = 0; u < AU; u++)
+                                if (p0 + u < rank) s[u] = dfma(Wat(i, Fc + p0 + u), ci, s[u]);
+                        }
+#pragma unroll
+                        for (uint32_t u = 0; u < AU; u++)
+                            if (p0 + u < rank) cbl[(F + p0 + u) * LD] -= s[u];
+                    }
+                }
+                for (uint32_t j = rank; j--;) // the level's reflectors, last first; none where factorize() made none
+                {
+                    const uint32_t rows = dim - j;
+                    const double tau    = tau_at(F + j);
+                    if (rows == 1 || tau == 0.0) continue; // (uniform)
+                    double *v = cbl + (F + j) * LD;
+                    double t  = 0.0;
+                    for (uint32_t i = 1; i < rows; i++) t = dfma(Wat(F + j + i, Fc + j), v[i * LD], t);
+                    t += v[0];
+                    v[0] = dfma(-tau, t, v[0]);
+                    for (uint32_t i = 1; i < rows; i++) v[i * LD] = dfma(-(tau * Wat(F + j + i, Fc + j)), t, v[i * LD]);
+                }
+            }
+
+            // ---- (d) grad_fixed_j = gh_j - (column j of the fixed variables)^T cb, left in gh_j; then both outputs, transposed through LDS ----
+            if (grad_fixed)
+                for (uint32_t j = 0; j < nf; j++)
+                {
+                    double s = 0.0;
+                    for (uint32_t r = 0; r < M; r++) s = dfma(Wat(r, j), cbl[r * LD], s);
+                    ghl[j * LD] -= s;
+                }
+            __syncthreads();
+            {
+                double *out = grad_rhs + ((size_t)b * ncot + (size_t)tile * 64u) * cap;
+                for (uint32_t e = lane; e < kt * cap; e += NT)
+                {
+                    const uint32_t c = e / cap, r = e - c * cap;
+                    out[e]           = cb[r * LD + c]; // (rows behind the problem's own were never touched: 0)
+                }
+            }
+            if (grad_fixed)
+            {
+                double *out = grad_fixed + ((size_t)b * ncot + (size_t)tile * 64u) * n;
+                for (uint32_t e = lane; e < kt * n; e += NT)
+                {
+                    const uint32_t c = e / n, j = e - c * n;
+                    out[e]           = j < nf ? gh[j * LD + c] : 0.0;
+                }
+            }
+        }
+
         // -----------------------------------------------------------------------------------------
         // ObjectiveSensitivity (lexlse.h:611-762) + findDescentDirection (:935-987)
         // -----------------------------------------------------------------------------------------
@@ -2078,6 +2257,60 @@ namespace lexls
         if (e != hipSuccess) return e;
         hipLaunchKernelGGL((solve_adjoint_kernel<64>), dim3(a.batch), dim3(64), lds, s, a, d_g, d_grad_rhs, d_grad_fixed);
         if (variant) *variant = "solve_adjoint<64>";
+        return hipGetLastError();
+    }
+
+    /// the form launch_solve_adjoint_multi takes for a shape: adjoint_multi_form (lexls_lds.h), unless LEXLS_ADJOINT_MULTI_FORM = staged | hbm |
+    /// single names a later form of the list (measurements: a form whose LDS does not fit is never forced)
+    static AdjointMultiForm adjoint_multi_form_for(uint32_t nVar, uint32_t cap)
+    {
+        AdjointMultiForm f = adjoint_multi_form(nVar, cap);
+        if (const char *e = std::getenv("LEXLS_ADJOINT_MULTI_FORM"))
+        {
+            if (!std::strcmp(e, "single")) f = AdjointMultiForm::per_cotangent;
+            if (!std::strcmp(e, "hbm") && f == AdjointMultiForm::staged) f = AdjointMultiForm::hbm;
+        }
+        return f;
+    }
+
+    size_t adjoint_multi_work_bytes(const LseArgs &a)
+    {
+        return adjoint_multi_form_for(a.nVar, a.cap) == AdjointMultiForm::per_cotangent ? 8 * (size_t)a.batch * (2 * (size_t)a.nVar + a.cap) : 0;
+    }
+
+    hipError_t launch_solve_adjoint_multi(const LseArgs &a, const double *d_G, uint32_t ncot, double *d_grad_rhs, double *d_grad_fixed, double *d_work, hipStream_t s,
+                                          const char **variant)
+    {
+        const AdjointMultiForm f = adjoint_multi_form_for(a.nVar, a.cap);
+        const uint32_t tiles     = (ncot + 63u) / 64u;
+        if (ncot == 0 || tiles > 65535u) return hipErrorInvalidValue;
+        if (variant) *variant = adjoint_multi_form_name(f);
+        if (f == AdjointMultiForm::per_cotangent)
+        {
+            // the single-cotangent kernel reads and writes one row per problem, a problem after the other: cotangent c's rows (a stride of ncot
+            // rows apart) travel through three buffers of that layout
+            if (!d_work) return hipErrorInvalidValue;
+            const size_t B = a.batch, n = a.nVar, cap = a.cap;
+            double *w_g = d_work, *w_rhs = w_g + B * n, *w_fixed = w_rhs + B * cap;
+            for (uint32_t c = 0; c < ncot; c++)
+            {
+                hipError_t e = hipMemcpy2DAsync(w_g, 8 * n, d_G + (size_t)c * n, 8 * n * ncot, 8 * n, B, hipMemcpyDeviceToDevice, s);
+                if (e == hipSuccess) e = launch_solve_adjoint(a, w_g, w_rhs, d_grad_fixed ? w_fixed : nullptr, s);
+                if (e == hipSuccess) e = hipMemcpy2DAsync(d_grad_rhs + (size_t)c * cap, 8 * cap * ncot, w_rhs, 8 * cap, 8 * cap, B, hipMemcpyDeviceToDevice, s);
+                if (e == hipSuccess && d_grad_fixed) e = hipMemcpy2DAsync(d_grad_fixed + (size_t)c * n, 8 * n * ncot, w_fixed, 8 * n, 8 * n, B, hipMemcpyDeviceToDevice, s);
+                if (e != hipSuccess) return e;
+            }
+            return hipSuccess;
+        }
+        const bool staged = f == AdjointMultiForm::staged;
+        const size_t lds  = adjoint_multi_lds_bytes(a.nVar, a.cap, staged);
+        if (lds > kMaxLdsBytes) return hipErrorInvalidValue;
+        hipError_t e = staged ? set_lds(solve_adjoint_multi_kernel<64, true>, lds) : set_lds(solve_adjoint_multi_kernel<64, false>, lds);
+        if (e != hipSuccess) return e;
+        if (staged)
+            hipLaunchKernelGGL((solve_adjoint_multi_kernel<64, true>), dim3(a.batch, tiles), dim3(64), lds, s, a, d_G, ncot, d_grad_rhs, d_grad_fixed);
+        else
+            hipLaunchKernelGGL((solve_adjoint_multi_kernel<64, false>), dim3(a.batch, tiles), dim3(64), lds, s, a, d_G, ncot, d_grad_rhs, d_grad_fixed);
         return hipGetLastError();
     }
 

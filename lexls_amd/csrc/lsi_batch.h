@@ -98,6 +98,49 @@ namespace
         }
     }
 
+    /// lsi_adjoint_scatter_kernel for ncot cotangents per instance (lexls_lsi_batch_solve_adjoint_multi): block (b, c) serves cotangent c of instance b —
+    /// the same map, types, meta and mask (all per instance), row b * ncot + c of grad_rhs (B x ncot x cap), grad_fixed (B x ncot x n) and of the
+    /// outputs (B x ncot x total).  Every output entry is stored once, by consecutive lanes; a masked instance writes none of its ncot rows
+    __global__ __launch_bounds__(64) void lsi_adjoint_scatter_multi_kernel(const double *__restrict__ grad_rhs, const double *__restrict__ grad_fixed,
+                                                                           const uint32_t *__restrict__ map, const uint8_t *__restrict__ types,
+                                                                           const int32_t *__restrict__ meta, uint32_t B, uint32_t ncot, uint32_t total, uint32_t n, uint32_t cap,
+                                                                           double *__restrict__ out_lb, double *__restrict__ out_ub, const uint8_t *mask)
+    {
+        __shared__ double s_lb[ADJ_TILE], s_ub[ADJ_TILE];
+        const uint32_t b = blockIdx.x, c = blockIdx.y, lane = threadIdx.x;
+        if (b >= B || c >= ncot || lsi_mask_byte(mask, b) == 0) return; // (block-uniform)
+        const uint32_t nf   = min((uint32_t)max(meta[2 * b + 1], 0), n);
+        const uint32_t na   = meta[2 * b] == (int32_t)PROBLEM_SOLVED ? min(map[b], min(total, nf + cap)) : 0u;
+        const uint32_t *pos = map + B + (size_t)b * total;
+        const uint8_t *ty   = types + (size_t)b * total;
+        const size_t row    = (size_t)b * ncot + c;
+        const double *gr = grad_rhs + row * cap, *gf = grad_fixed + row * n;
+        for (uint32_t u0 = 0; u0 < total; u0 += ADJ_TILE)
+        {
+            const uint32_t len = min(ADJ_TILE, total - u0);
+            for (uint32_t i = lane; i < len; i += 64) s_lb[i] = s_ub[i] = 0.0;
+            __syncthreads();
+            for (uint32_t r = lane; r < na; r += 64)
+            {
+                const uint32_t u = pos[r];
+                if (u < u0 || u - u0 >= len) continue;
+                const double val = r < nf ? gf[r] : gr[r - nf];
+                const uint8_t t  = ty[r];
+                if (t == CTR_ACTIVE_LB)
+                    s_lb[u - u0] = val;
+                else if (t == CTR_ACTIVE_UB || t == CTR_ACTIVE_EQ)
+                    s_ub[u - u0] = val;
+            }
+            __syncthreads();
+            for (uint32_t i = lane; i < len; i += 64)
+            {
+                if (out_lb) out_lb[row * total + u0 + i] = s_lb[i];
+                if (out_ub) out_ub[row * total + u0 + i] = s_ub[i];
+            }
+            __syncthreads();
+        }
+    }
+
     /// lexls_lsi_batch_set_instance_regularization with the factors in device memory, for one group: row i of the group's handle array (B x nObjL,
     /// what the regularized kernels read) takes the factors of the caller's row i (B x nObj, the group's first instance in front): LexLSE level k
     /// = objective off + k.  One thread per (instance, level).
@@ -184,9 +227,12 @@ struct lexls_lsi_batch_s
         uint8_t *d_types = NULL;
         int32_t *d_meta  = NULL;
         double *d_g = NULL, *d_grad_rhs = NULL, *d_grad_fixed = NULL, *d_grad_lb = NULL, *d_grad_ub = NULL;
+        // lexls_lsi_batch_solve_adjoint_multi: the same five with room for m_room cotangents per instance (ensure_adjoint_multi_bufs)
+        double *d_mg = NULL, *d_mgrad_rhs = NULL, *d_mgrad_fixed = NULL, *d_mgrad_lb = NULL, *d_mgrad_ub = NULL;
+        uint32_t m_room = 0;
         ~LambdaBufs()
         {
-            void *dev[] = {d_map, d_out, d_types, d_meta, d_g, d_grad_rhs, d_grad_fixed, d_grad_lb, d_grad_ub};
+            void *dev[] = {d_map, d_out, d_types, d_meta, d_g, d_grad_rhs, d_grad_fixed, d_grad_lb, d_grad_ub, d_mg, d_mgrad_rhs, d_mgrad_fixed, d_mgrad_lb, d_mgrad_ub};
             for (void *q : dev)
                 if (q) (void)hipFree(q);
         }
@@ -584,6 +630,84 @@ struct lexls_lsi_batch_s
             if (hipGetLastError() != hipSuccess) throw Exception("lsi_adjoint_scatter_kernel launch failed");
             if (!on_device && ((grad_lb && hipMemcpyAsync(grad_lb + r0, lb.d_grad_lb, 8 * rows, hipMemcpyDeviceToHost, ctx.stream) != hipSuccess) ||
                                (grad_ub && hipMemcpyAsync(grad_ub + r0, lb.d_grad_ub, 8 * rows, hipMemcpyDeviceToHost, ctx.stream) != hipSuccess)))
+                throw Exception(std::string(who) + ": hipMemcpyAsync failed (results)");
+        }
+        for (uint32_t g = 0; g < nGroups; g++)
+            if (hipStreamSynchronize(grp[g]->stream) != hipSuccess) throw Exception(std::string(who) + ": stream synchronisation failed");
+        return LEXLS_OK;
+    }
+
+    /// the groups' buffers of solve_adjoint_multi: made for the largest ncot so far
+    void ensure_adjoint_multi_bufs(uint32_t ncot)
+    {
+        ensure_adjoint_bufs();
+        for (uint32_t g = 0; g < nGroups; g++)
+        {
+            LambdaBufs &lb = *lam_bufs[g];
+            if (ncot <= lb.m_room) continue;
+            const size_t rows = (size_t)grp[g]->B * ncot, cap = grp[g]->cap;
+            lb.m_room = 0;
+            for (double **q : {&lb.d_mg, &lb.d_mgrad_rhs, &lb.d_mgrad_fixed, &lb.d_mgrad_lb, &lb.d_mgrad_ub})
+            {
+                if (*q) (void)hipFree(*q);
+                *q = NULL;
+            }
+            if (hipMalloc((void **)&lb.d_mg, 8 * rows * nVar) != hipSuccess || hipMalloc((void **)&lb.d_mgrad_rhs, 8 * rows * (cap ? cap : 1)) != hipSuccess ||
+                hipMalloc((void **)&lb.d_mgrad_fixed, 8 * rows * nVar) != hipSuccess || hipMalloc((void **)&lb.d_mgrad_lb, 8 * rows * (total ? total : 1)) != hipSuccess ||
+                hipMalloc((void **)&lb.d_mgrad_ub, 8 * rows * (total ? total : 1)) != hipSuccess)
+                throw Exception("hipMalloc failed (lexls_lsi_batch_solve_adjoint_multi)");
+            lb.m_room = ncot;
+        }
+    }
+
+    /// lexls_lsi_batch_solve_adjoint_multi(_device): solve_adjoint for ncot cotangents per instance — G batch x ncot x nVar, the outputs batch x ncot x
+    /// total.  The same stages: ensure_final_factor (shared with get_lambda and solve_adjoint), the routes of the scatter (uploaded once per run),
+    /// lexls_lse_solve_adjoint_multi_device on the group's rows of G, lsi_adjoint_scatter_multi_kernel.
+    int solve_adjoint_multi(const double *G_in, uint32_t ncot, double *grad_lb, double *grad_ub, bool on_device)
+    {
+        const char *who = on_device ? "lexls_lsi_batch_solve_adjoint_multi_device" : "lexls_lsi_batch_solve_adjoint_multi";
+        if (lam_rc < 0) throw Exception(std::string(who) + ": no completed lexls_lsi_batch_run on this batch");
+        if (lam_rc != LEXLS_OK) // the rules of lexls_lsi_batch_get_lambda, and its reason
+        {
+            lexls_internal_set_error(lam_msg.c_str());
+            return lam_rc;
+        }
+        if (ncot > 65535u) throw Exception(std::string(who) + ": more than 65535 cotangents per instance");
+        if (hipSetDevice(device) != hipSuccess) throw Exception(std::string(who) + ": hipSetDevice failed");
+        ensure_adjoint_multi_bufs(ncot);
+        for (uint32_t g = 0; g < nGroups; g++)
+        {
+            BatchCtx &ctx         = *grp[g];
+            LambdaBufs &lb        = *lam_bufs[g];
+            const size_t rows     = (size_t)ctx.B * total, r0 = (size_t)lo[g] * ncot * total, orows = (size_t)ctx.B * ncot * total;
+            const bool any_active = ensure_final_factor(g, []() {});
+            if (!adj_uploaded[g])
+            {
+                pool->run(ctx.B, [&](uint32_t k) { form_adjoint_routes(g, k, lb); });
+                if (hipMemcpyAsync(lb.d_map, lb.map.data(), 4 * ((size_t)ctx.B + rows), hipMemcpyHostToDevice, ctx.stream) != hipSuccess ||
+                    hipMemcpyAsync(lb.d_types, lb.types.data(), rows, hipMemcpyHostToDevice, ctx.stream) != hipSuccess ||
+                    hipMemcpyAsync(lb.d_meta, lb.meta.data(), 8 * (size_t)ctx.B, hipMemcpyHostToDevice, ctx.stream) != hipSuccess)
+                    throw Exception(std::string(who) + ": hipMemcpyAsync failed (row map)");
+                adj_uploaded[g] = 1;
+            }
+            const double *d_G = G_in + (size_t)lo[g] * ncot * nVar;
+            double *d_lb = grad_lb ? grad_lb + r0 : NULL, *d_ub = grad_ub ? grad_ub + r0 : NULL;
+            if (!on_device)
+            {
+                // with an instance mask the entries of a skipped instance keep the caller's bits: they travel to the staging buffers first
+                if (hipMemcpyAsync(lb.d_mg, d_G, 8 * (size_t)ctx.B * ncot * nVar, hipMemcpyHostToDevice, ctx.stream) != hipSuccess ||
+                    (group_mask(g) && grad_lb && hipMemcpyAsync(lb.d_mgrad_lb, grad_lb + r0, 8 * orows, hipMemcpyHostToDevice, ctx.stream) != hipSuccess) ||
+                    (group_mask(g) && grad_ub && hipMemcpyAsync(lb.d_mgrad_ub, grad_ub + r0, 8 * orows, hipMemcpyHostToDevice, ctx.stream) != hipSuccess))
+                    throw Exception(std::string(who) + ": hipMemcpyAsync failed (G)");
+                d_G = lb.d_mg, d_lb = grad_lb ? lb.d_mgrad_lb : NULL, d_ub = grad_ub ? lb.d_mgrad_ub : NULL;
+            }
+            // nobody has an active constraint: nothing was factorized, every entry is zero — the scatter kernel reads no gradient (nact = 0)
+            if (any_active) hip_check(lexls_lse_solve_adjoint_multi_device(ctx.h, d_G, ncot, lb.d_mgrad_rhs, lb.d_mgrad_fixed));
+            hipLaunchKernelGGL(lsi_adjoint_scatter_multi_kernel, dim3(ctx.B, ncot), dim3(64), 0, ctx.stream, lb.d_mgrad_rhs, lb.d_mgrad_fixed, lb.d_map, lb.d_types, lb.d_meta,
+                               ctx.B, ncot, (uint32_t)total, nVar, ctx.cap, d_lb, d_ub, group_mask(g));
+            if (hipGetLastError() != hipSuccess) throw Exception("lsi_adjoint_scatter_multi_kernel launch failed");
+            if (!on_device && ((grad_lb && hipMemcpyAsync(grad_lb + r0, lb.d_mgrad_lb, 8 * orows, hipMemcpyDeviceToHost, ctx.stream) != hipSuccess) ||
+                               (grad_ub && hipMemcpyAsync(grad_ub + r0, lb.d_mgrad_ub, 8 * orows, hipMemcpyDeviceToHost, ctx.stream) != hipSuccess)))
                 throw Exception(std::string(who) + ": hipMemcpyAsync failed (results)");
         }
         for (uint32_t g = 0; g < nGroups; g++)

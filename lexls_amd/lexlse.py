@@ -26,7 +26,7 @@ def _ptr(a, t):
 class BatchedLexLSE:
     def __init__(self, batch: int, nVar: int, maxObjDim, device: int = 0):
         self._h = C.c_void_p()
-        self.batch, self.nVar = int(batch), int(nVar)
+        self.batch, self.nVar, self.device = int(batch), int(nVar), int(device)
         self.maxObjDim = np.ascontiguousarray(maxObjDim, dtype=np.uint32)
         self.nObj = int(self.maxObjDim.size)
         self.cap = int(self.maxObjDim.sum())
@@ -299,6 +299,58 @@ class BatchedLexLSE:
         capi.check(capi.lib().lexls_lse_solve_adjoint_device(self._h, address("g", g, (self.batch, self.nVar)),
                                                               address("grad_rhs", grad_rhs, (self.batch, self.cap)),
                                                               address("grad_fixed", grad_fixed, (self.batch, self.nVar))))
+
+    # ---- the same adjoint for many cotangents per problem in one pass (lane = cotangent) --------------
+    def solve_adjoint_multi(self, G):
+        """lexls_lse_solve_adjoint_multi + lexls_lse_get_adjoint_multi: G (batch, K, nVar), K cotangents per problem in the order of get_x().
+        Returns (grad_rhs (batch, K, cap), grad_fixed (batch, K, nVar)), row c what solve_adjoint(G[:, c]) returns (tolerance contract); a
+        cotangent's bits do not depend on K, on its position or on its neighbours.  One cotangent goes to the single-cotangent entry."""
+        G = np.ascontiguousarray(G, np.float64)
+        if G.ndim != 3 or G.shape[0] != self.batch or G.shape[1] == 0 or G.shape[2] != self.nVar:
+            raise ValueError(f"G must have shape ({self.batch}, K >= 1, {self.nVar}), got {G.shape}")
+        K = G.shape[1]
+        if K == 1:
+            grad_rhs, grad_fixed = self.solve_adjoint(G[:, 0, :])
+            return grad_rhs[:, None, :], grad_fixed[:, None, :]
+        capi.check(capi.lib().lexls_lse_solve_adjoint_multi(self._h, _ptr(G, C.c_double), K))
+        grad_rhs = np.zeros((self.batch, K, self.cap))
+        grad_fixed = np.zeros((self.batch, K, self.nVar))
+        capi.check(capi.lib().lexls_lse_get_adjoint_multi(self._h, _ptr(grad_rhs, C.c_double), _ptr(grad_fixed, C.c_double)))
+        return grad_rhs, grad_fixed
+
+    def solve_adjoint_multi_device(self, G, grad_rhs, grad_fixed=None):
+        """lexls_lse_solve_adjoint_multi_device: G (batch, K, nVar), grad_rhs (batch, K, cap) and grad_fixed (batch, K, nVar; None: not wanted) in
+        device memory, contiguous float64 torch tensors.  Only enqueued in the handle's stream.  K == 1 goes to solve_adjoint_device (the
+        single-cotangent kernel: one live lane of the multi-cotangent one would be slower)."""
+        if not hasattr(G, "data_ptr") or G.dim() != 3 or G.shape[1] == 0:
+            raise ValueError("solve_adjoint_multi_device: G must be a tensor of shape (batch, K >= 1, nVar)")
+        K = int(G.shape[1])
+
+        def address(name, t, shape):
+            if t is None:
+                return None
+            if not hasattr(t, "data_ptr") or str(t.dtype) != "torch.float64" or not t.is_contiguous() or tuple(t.shape) != shape:
+                raise ValueError(f"solve_adjoint_multi_device: {name} must be a contiguous float64 tensor of shape {shape}")
+            return C.c_void_p(t.data_ptr())
+        args = (address("G", G, (self.batch, K, self.nVar)), address("grad_rhs", grad_rhs, (self.batch, K, self.cap)),
+                address("grad_fixed", grad_fixed, (self.batch, K, self.nVar)))
+        if K == 1:
+            capi.check(capi.lib().lexls_lse_solve_adjoint_device(self._h, *args))
+        else:
+            capi.check(capi.lib().lexls_lse_solve_adjoint_multi_device(self._h, args[0], K, args[1], args[2]))
+
+    def jacobian_device(self):
+        """(dx_db (batch, nVar, cap), dx_dfixed (batch, nVar, nVar)) of the kept factor as torch tensors on the handle's device: the identity
+        cotangents are built there and go through solve_adjoint_multi_device, so dx_db[b, i, r] = d x_i / d b_r (LOD row order) and
+        dx_dfixed[b, i, j] = d x_i / d x_fixed_j (fixVariable order, zero from nfixed on).  Enqueued in the handle's stream, not waited for."""
+        import torch
+        dev = torch.device("cuda", self.device)
+        G = torch.eye(self.nVar, dtype=torch.float64, device=dev).expand(self.batch, self.nVar, self.nVar).contiguous()
+        dx_db = torch.empty((self.batch, self.nVar, self.cap), dtype=torch.float64, device=dev)
+        dx_dfixed = torch.empty((self.batch, self.nVar, self.nVar), dtype=torch.float64, device=dev)
+        torch.cuda.current_stream(dev).synchronize()  # the cotangents are complete before the handle's stream reads them
+        self.solve_adjoint_multi_device(G, dx_db, dx_dfixed)
+        return dx_db, dx_dfixed
 
     def getCtrType(self):
         t = np.zeros((self.batch, self.cap), np.uint8)

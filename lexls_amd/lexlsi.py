@@ -620,6 +620,54 @@ class LsiBatch:
         capi.check(capi.lib().lexls_lsi_batch_solve_adjoint_device(self._h, d_g, d_lb, d_ub))
         return grad_lb, grad_ub
 
+    def solve_adjoint_multi(self, G):
+        """lexls_lsi_batch_solve_adjoint_multi: `G` (batch, K, nvar), K cotangents dloss/dx per instance.  Returns (grad_lb, grad_ub), numpy arrays of
+        shape (batch, K, total): row c what solve_adjoint(G[:, c]) returns (tolerance contract, the exact zeros at the same entries).  One
+        cotangent goes to solve_adjoint."""
+        G = np.ascontiguousarray(G, np.float64)
+        if G.ndim != 3 or G.shape[0] != self.batch or G.shape[1] == 0 or G.shape[2] != self.nvar:
+            raise ValueError(f"solve_adjoint_multi: G has shape {G.shape}, ({self.batch}, K >= 1, {self.nvar}) expected")
+        K = G.shape[1]
+        if K == 1:
+            grad_lb, grad_ub = self.solve_adjoint(G[:, 0, :])
+            return grad_lb[:, None, :], grad_ub[:, None, :]
+        grad_lb, grad_ub = np.zeros((self.batch, K, self.total)), np.zeros((self.batch, K, self.total))
+        capi.check(capi.lib().lexls_lsi_batch_solve_adjoint_multi(self._h, _p(G, C.c_double), K, _p(grad_lb, C.c_double), _p(grad_ub, C.c_double)))
+        return grad_lb, grad_ub
+
+    def solve_adjoint_multi_device(self, G, grad_lb=None, grad_ub=None):
+        """lexls_lsi_batch_solve_adjoint_multi_device: solve_adjoint_multi() on torch tensors of the batch's device — `G` float64 (batch, K, nvar),
+        `grad_lb` and `grad_ub` float64 (batch, K, total), contiguous; an output that is not given is allocated (zeroed).  Returns
+        (grad_lb, grad_ub).  Under an instance mask all K rows of a skipped instance keep their bits.  One cotangent goes to
+        solve_adjoint_device.  The call waits for the device."""
+        import torch
+        if not hasattr(G, "data_ptr") or G.dim() != 3 or G.shape[1] == 0:
+            raise ValueError("solve_adjoint_multi_device: G must be a tensor of shape (batch, K >= 1, nvar)")
+        K = int(G.shape[1])
+        d_G = self._device_array("G", G, torch.float64, (self.batch, K, self.nvar), optional=False)
+        dev = torch.device("cuda", self.device)
+        if grad_lb is None:
+            grad_lb = torch.zeros((self.batch, K, self.total), dtype=torch.float64, device=dev)
+        if grad_ub is None:
+            grad_ub = torch.zeros((self.batch, K, self.total), dtype=torch.float64, device=dev)
+        d_lb = self._device_array("grad_lb", grad_lb, torch.float64, (self.batch, K, self.total), optional=False)
+        d_ub = self._device_array("grad_ub", grad_ub, torch.float64, (self.batch, K, self.total), optional=False)
+        torch.cuda.synchronize(dev)  # G (and the zeroed outputs) are complete before the library's own streams read and write them
+        if K == 1:
+            capi.check(capi.lib().lexls_lsi_batch_solve_adjoint_device(self._h, d_G, d_lb, d_ub))
+        else:
+            capi.check(capi.lib().lexls_lsi_batch_solve_adjoint_multi_device(self._h, d_G, K, d_lb, d_ub))
+        return grad_lb, grad_ub
+
+    def jacobian_bounds_device(self):
+        """(dx_dlb, dx_dub), torch tensors of shape (batch, nvar, total) on the batch's device: d x_i / d lb_r and d x_i / d ub_r of the last run
+        with the matrices held fixed, from the identity cotangents through solve_adjoint_multi_device — the Jacobian of the piece of the
+        piecewise-affine map the solve ended on; zero for instances that did not end PROBLEM_SOLVED."""
+        import torch
+        dev = torch.device("cuda", self.device)
+        G = torch.eye(self.nvar, dtype=torch.float64, device=dev).expand(self.batch, self.nvar, self.nvar).contiguous()
+        return self.solve_adjoint_multi_device(G)
+
     def lambdas(self):
         """per instance the list of per-objective (dim_k x nObj) multiplier matrices that frontend.lexlsi(..., debug=True) returns as
         d["lambda"] (LexLSI::getLambda, lexlsi.h:552-605), for the last run"""

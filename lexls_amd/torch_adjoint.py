@@ -9,6 +9,9 @@ continuous in A where a rank changes — and asking for them raises instead of r
 problem of the final working set, affine in the active bounds while that set holds.  Forward is LsiBatch.run_device, backward
 LsiBatch.solve_adjoint_device (lexls_lsi_batch_solve_adjoint_device).
 
+``jacobian_rhs`` and ``jacobian_bounds`` return the whole Jacobians, dx/db and dx/dlb, dx/dub, from one multi-cotangent pass
+(lexls_lse_solve_adjoint_multi_device: lane = cotangent) instead of nVar backward passes.
+
 torch is imported when the operation is first used, not with the package.
 """
 from __future__ import annotations
@@ -142,3 +145,15 @@ def solve_bounds(lb, ub, batch, data, var_index=None, active_guess=None, x0=None
     """SolveBounds.apply(lb, ub, batch, data, var_index, active_guess, x0, params, out): the solutions of a LexLSI batch, differentiable in the
     bounds.  `params`: the keyword parameters of LsiBatch.run_device; `out`: a dict that receives its result ("x", "info", "active", "v")."""
     return _solve_bounds_class().apply(lb, ub, batch, data, var_index, active_guess, x0, params, out)
+
+
+def jacobian_rhs(lse):
+    """(dx_db (batch, nVar, cap), dx_dfixed (batch, nVar, nVar)) of the factor `lse` keeps (BatchedLexLSE.jacobian_device): what nVar backward
+    passes of SolveRhs with the unit cotangents would return, from one multi-cotangent pass.  The matrix is held fixed."""
+    return lse.jacobian_device()
+
+
+def jacobian_bounds(batch):
+    """(dx_dlb, dx_dub), each (batch, nVar, total), of the last run of the LsiBatch `batch` (LsiBatch.jacobian_bounds_device): what nVar backward
+    passes of SolveBounds with the unit cotangents would return, from one multi-cotangent pass.  The matrices are held fixed."""
+    return batch.jacobian_bounds_device()
