@@ -22,22 +22,36 @@ Cases — the smallest shapes at which each branch can go wrong:
     large       edges127, the smallest case of tests/large_cases.py (n = 127, [100, 1, 0, 40, 24], rank-deficient, a one-row and an empty
                 level; reflectors over more than 64 rows and 65 rows below level 0: a second trip of the lanes over the rows), under kernel
                 policy 5: the large path's kept factor — (B) + identities
+Fixed variables at the other edges (reference (A), the unit solves, for all four):
+    fixed_wide      n = 70 (20, 40, 30), batch 3, nfixed (6, 9, 0), indices a prefix of a fixed permutation: step (d)'s second and third groups
+                    of four fixed columns on live data, its dot products over 90 > 64 rows, step (a) with pivot columns [nf, T) at n > 64, a
+                    problem without fixed variables beside two with
+    fixed_rank_def  n = 7 (3, 3, 3), ranks (2, 0, 2) behind nfixed (2, 1, 3): a rank-0 level and rank < dim behind fixed columns, another T
+                    per problem
+    fixed_ragged    n = 5, capacities (2, 3, 2), the dimensions of `ragged`, nfixed (2, 0, 4, 1): empty levels, one free variable, a level
+                    that finds the columns used up (its first column >= T)
+    fixed_tall      n = 12 (70, 30), batch 2, nfixed (5, 7): reflectors over 70 rows, a Gauss step and step (d) over 100 rows, the second
+                    level at rank 0 because the columns are gone
 
 D_CPU is the largest discrepancy the CPU test finds — (A) against (B), and both sides of the identities with (B)'s grad_rhs — each relative to
 max(1, largest magnitude of the reference).  The GPU tolerance is TOL = max(10 * D_CPU, 1e-12): the factor 10 allows for fma contraction and
 summation orders that differ from numpy's.  It has to stay at or below 1e-10, the project's tolerance contract; data that would need more are
 too ill-conditioned and get replaced, the tolerance is not raised.
 MEASURED (`python tests/adjoint_cases.py`, the oracle and numpy alone; gap = the case's largest discrepancy):
-    base      n=3    [2,2,3]            batch 4  ranks [2,1,0] x 4                                   gap 2.2e-16
-    used_up   n=4    [3,3,3]            batch 4  ranks [3,1,0] x 4                                   gap 2.2e-16
-    one_row   n=5    [1,3,2]            batch 4  ranks [1,3,1] x 4                                   gap 2.2e-16
-    rank_def  n=7    [3,3,3]            batch 3  ranks [2,0,2] x 3                                   gap 2.2e-16
-    ragged    n=5    [2,3,2]            batch 4  ranks [2,3,0] [2,0,2] [1,3,0] [0,3,2]               gap 3.8e-16
-    fixed     n=5    [2,2,3]            batch 4  ranks [2,1,0] [2,1,0] [0,0,0] [2,2,0]               gap 6.7e-16
-    ik        n=40   [12,12,12,12,12]   batch 8  ranks [12,12,12,4,0] x 8                            gap 1.2e-15
-    wide      n=70   [20,40,30]         batch 3  ranks [20,40,10] x 3                                gap 2.8e-16
-    large     n=127  [100,1,0,40,24]    batch 2  ranks [17,1,0,5,10] [9,0,0,16,8]                    gap 1.6e-16
-    D_CPU = 1.21e-15 (ik)  ->  TOL = max(10 D_CPU, 1e-12) = 1e-12, a hundredth of the 1e-10 of the tolerance contract.
+    base            n=3    [2,2,3]            batch 4  ranks [2,1,0] x 4                                   gap 2.2e-16
+    used_up         n=4    [3,3,3]            batch 4  ranks [3,1,0] x 4                                   gap 2.2e-16
+    one_row         n=5    [1,3,2]            batch 4  ranks [1,3,1] x 4                                   gap 2.2e-16
+    rank_def        n=7    [3,3,3]            batch 3  ranks [2,0,2] x 3                                   gap 2.2e-16
+    ragged          n=5    [2,3,2]            batch 4  ranks [2,3,0] [2,0,2] [1,3,0] [0,3,2]               gap 3.8e-16
+    fixed           n=5    [2,2,3]            batch 4  ranks [2,1,0] [2,1,0] [0,0,0] [2,2,0]               gap 6.7e-16
+    ik              n=40   [12,12,12,12,12]   batch 8  ranks [12,12,12,4,0] x 8                            gap 1.2e-15
+    wide            n=70   [20,40,30]         batch 3  ranks [20,40,10] x 3                                gap 2.8e-16
+    large           n=127  [100,1,0,40,24]    batch 2  ranks [17,1,0,5,10] [9,0,0,16,8]                    gap 1.6e-16
+    fixed_wide      n=70   [20,40,30]         batch 3  ranks [20,40,4] [20,40,1] [20,40,10]                gap 2.6e-15
+    fixed_rank_def  n=7    [3,3,3]            batch 3  ranks [2,0,2] x 3                                   gap 1.1e-15
+    fixed_ragged    n=5    [2,3,2]            batch 4  ranks [2,1,0] [2,0,2] [1,0,0] [0,3,1]               gap 2.0e-16
+    fixed_tall      n=12   [70,30]            batch 2  ranks [7,0] [5,0]                                   gap 2.2e-16
+    D_CPU = 2.58e-15 (fixed_wide)  ->  TOL = max(10 D_CPU, 1e-12) = 1e-12, a hundredth of the 1e-10 of the tolerance contract.
 """
 import functools
 import os
@@ -54,24 +68,43 @@ if os.path.dirname(os.path.abspath(__file__)) not in sys.path:
 from lexls_amd import problems as P  # noqa: E402
 from oracle import oracle_ctypes as oracle  # noqa: E402
 
-D_CPU = 1.21e-15  # measured: the table above (tests/test_adjoint_cases.py re-measures it and asserts that TOL still follows from it)
+D_CPU = 2.58e-15  # measured: the table above (tests/test_adjoint_cases.py re-measures it and asserts that TOL still follows from it)
 TOL = max(10.0 * D_CPU, 1e-12)
 
 RAGGED_DIMS = np.array([[2, 3, 2], [2, 0, 2], [1, 3, 0], [0, 3, 2]], np.uint32)
-FIXED_N = [2, 2, 5, 1]
-FIXED_IDX = [[1, 0], [3, 1], [2, 0, 4, 1, 3], [4]]
+WIDE_ORDER = [(37 * j + 11) % 70 for j in range(70)]  # a fixed permutation of the 70 variables of fixed_wide (37 and 70 are coprime)
 
-# name -> n, dims (capacities), batch, seed; policies: kernel policy -> the producer of the kept factor (tests/test_gpu_lse_adjoint.py)
+# name -> n, dims (capacities), batch, seed; fixed: per problem the indices of its fixed variables, in fixVariables order (their number is nfixed);
+# ranks: P.rank_deficient_problem; per_problem: ragged dimensions; large: reference (B) + identities instead of the unit solves
 CASES = {
     "base": dict(n=3, dims=[2, 2, 3], batch=4, seed=20290101),
     "used_up": dict(n=4, dims=[3, 3, 3], batch=4, seed=20290102),
     "one_row": dict(n=5, dims=[1, 3, 2], batch=4, seed=20290103),
     "rank_def": dict(n=7, dims=[3, 3, 3], batch=3, seed=20290104, ranks=[2, 0, 2]),
     "ragged": dict(n=5, dims=[2, 3, 2], batch=4, seed=20290105, per_problem=RAGGED_DIMS),
-    "fixed": dict(n=5, dims=[2, 2, 3], batch=4, seed=20290106, fixed=True),
+    "fixed": dict(n=5, dims=[2, 2, 3], batch=4, seed=20290106, fixed=[[1, 0], [3, 1], [2, 0, 4, 1, 3], [4]]),
     "ik": dict(n=40, dims=[12] * 5, batch=8, seed=20290107),
     "wide": dict(n=70, dims=[20, 40, 30], batch=3, seed=20290108, large=True),
     "large": dict(n=127, dims=[100, 1, 0, 40, 24], batch=2, seed=20280106, large=True, large_case="edges127"),
+    "fixed_wide": dict(n=70, dims=[20, 40, 30], batch=3, seed=20310101, fixed=[WIDE_ORDER[:6], WIDE_ORDER[:9], []]),
+    "fixed_rank_def": dict(n=7, dims=[3, 3, 3], batch=3, seed=20310102, ranks=[2, 0, 2], fixed=[[4, 1], [6], [0, 5, 2]]),
+    "fixed_ragged": dict(n=5, dims=[2, 3, 2], batch=4, seed=20310103, per_problem=RAGGED_DIMS, fixed=[[3, 0], [], [4, 2, 0, 1], [2]]),
+    "fixed_tall": dict(n=12, dims=[70, 30], batch=2, seed=20310104, fixed=[[7, 2, 11, 0, 5], [1, 9, 4, 10, 6, 3, 8]]),
+}
+
+# case -> kernel policy -> the producer of the kept factor: every policy that gives the shape a distinct one (register-resident: lqr_wave;
+# four-per-wavefront: lqr_quad; left-looking: lqr_lwave; bit-exact large: lqr_large<multi-launch>).  The names are the host-side dispatch plan's
+# (lexls_amd/csrc/lexls_dispatch.h); tests/test_adjoint_multi_cases.py holds them to it on the CPU, tests/test_gpu_lse_adjoint.py on the device
+QUAD1, GENERIC64, GENERIC256, LWAVE = "lqr_quad<1,12,factor>", "lqr_generic<64,lds>", "lqr_generic<256,lds>", "lqr_lwave<41,12>"
+SMALL = {0: QUAD1, 1: GENERIC64, 3: LWAVE}
+SMALL_FIXED = {0: "lqr_wave<41,12>", 1: GENERIC64, 4: "lqr_quad<3,12,factor,fixed>"}
+PRODUCERS = {
+    "base": SMALL, "used_up": SMALL, "one_row": SMALL, "rank_def": SMALL, "ragged": SMALL,
+    "fixed": SMALL_FIXED,
+    "ik": {0: "lqr_wave<41,12,exact>", 3: "lqr_lwave<41,12,exact>", 4: "lqr_quad<3,12,shift 7,factor>", 1: GENERIC64},
+    "wide": {0: GENERIC256},
+    "large": {5: "lqr_large<multi-launch>", 1: "lqr_generic<1024,hbm>"},
+    "fixed_wide": {0: GENERIC256}, "fixed_rank_def": SMALL_FIXED, "fixed_ragged": SMALL_FIXED, "fixed_tall": {0: GENERIC256},
 }
 
 
@@ -97,12 +130,13 @@ def draw(name):
     else:
         lod = P.lse_batch(seed, B, n, caps)
     fixed = {}
-    if c.get("fixed"):
+    if c.get("fixed"):  # with any of the draws above: the fixed variables are columns of whatever matrix was drawn
         idx, val = np.zeros((B, n), np.uint32), np.zeros((B, n))
+        nfix = [len(c["fixed"][b]) for b in range(B)]
         for b in range(B):
-            idx[b, :FIXED_N[b]] = FIXED_IDX[b]
-            val[b, :FIXED_N[b]] = P.normal(seed + 500 + b, n)[:FIXED_N[b]]
-        fixed = dict(nfixed=np.asarray(FIXED_N, np.uint32), fixed_idx=idx, fixed_val=val)
+            idx[b, :nfix[b]] = c["fixed"][b]
+            val[b, :nfix[b]] = P.normal(seed + 500 + b, n)[:nfix[b]]
+        fixed = dict(nfixed=np.asarray(nfix, np.uint32), fixed_idx=idx, fixed_val=val)
     g = P.normal(seed + 900, B * n).reshape(B, n)
     return dict(name=name, n=n, caps=caps, lod=lod, dims=dims, fixed=fixed, g=g, large=bool(c.get("large")))
 
@@ -227,7 +261,7 @@ def expected(case):
 
 
 def summary(case):
-    return (f"    {case['name']:<9} n={case['n']:<4} {str(case['caps']).replace(' ', ''):<18} batch {case['lod'].shape[0]}  ranks "
+    return (f"    {case['name']:<15} n={case['n']:<4} {str(case['caps']).replace(' ', ''):<18} batch {case['lod'].shape[0]}  ranks "
             f"{' '.join(str(r.tolist()).replace(' ', '') for r in case['ref']['rank']):<44} gap {case['gap']:.1e}  |grad_rhs| {np.abs(expected(case)[0]).max():.1e}")
 
 

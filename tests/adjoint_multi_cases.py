@@ -3,9 +3,14 @@ solve_adjoint_multi_kernel, lane = cotangent) to the references of tests/adjoint
 (tests/test_adjoint_multi_cases.py asserts on the CPU that the references agree; tests/test_gpu_lse_adjoint_multi.py compares the device
 with them).
 
-The cases are those of adjoint_cases.py plus one:
+The cases are those of adjoint_cases.py (NAMES) plus:
     beyond      n = 200 (150, 50), batch 2, iid data, full rank: the per-lane state alone (65 x 400 doubles = 208 KB) exceeds one workgroup's
                 160 KiB, so the launcher takes the single-cotangent kernel once per cotangent — (B) + identities, as the large cases
+    fit_*       (FIT_NAMES, a test of their own) n = 40, batch 2, iid data in levels of 12 rows, on both sides of the fit rule's two switches
+                as lds_bytes() below restates them: fit_staged_last cap = 167 ([12] x 13 + [11]: 162736 of 163840 bytes), fit_hbm_first cap =
+                168 (staged it would need 163904), fit_hbm_last cap = 274 (163600), fit_single_first cap = 275 (the state alone 164128).  The
+                kernel carves exactly adjoint_multi_lds_bytes out of LDS, so an off-by-one in the rule or in the carving shows here or
+                nowhere.  The first four levels take the 40 columns; reference (A), the unit solves.
 
 Cotangent sets per case, cut from ONE master set R of 65 cotangents per problem (R[:, 0] = the case's own g, the rest iid normal) so that the
 reference is computed once:
@@ -24,17 +29,25 @@ D_CPU_MULTI is the largest discrepancy of the CPU test — (A) against (B), iden
 (B)'s grad_rhs — each relative to max(1, largest magnitude of the problem's reference).  TOL_MULTI = max(10 * D_CPU_MULTI, 1e-12), the
 rule of adjoint_cases.py; it has to stay at or below 1e-10: data that would need more are replaced, the tolerance is not raised.
 MEASURED (`python tests/adjoint_multi_cases.py`, the oracle and numpy alone):
-    base      n=3    [2,2,3]            batch 4  ranks [2,1,0] x 4                                   gap 2.9e-16
-    used_up   n=4    [3,3,3]            batch 4  ranks [3,1,0] x 4                                   gap 4.8e-16
-    one_row   n=5    [1,3,2]            batch 4  ranks [1,3,1] x 4                                   gap 5.6e-16
-    rank_def  n=7    [3,3,3]            batch 3  ranks [2,0,2] x 3                                   gap 5.2e-16
-    ragged    n=5    [2,3,2]            batch 4  ranks [2,3,0] [2,0,2] [1,3,0] [0,3,2]               gap 3.6e-16
-    fixed     n=5    [2,2,3]            batch 4  ranks [2,1,0] [2,1,0] [0,0,0] [2,2,0]               gap 5.2e-16
-    ik        n=40   [12,12,12,12,12]   batch 8  ranks [12,12,12,4,0] x 8                            gap 1.5e-15
-    wide      n=70   [20,40,30]         batch 3  ranks [20,40,10] x 3                                gap 7.6e-16
-    large     n=127  [100,1,0,40,24]    batch 2  ranks [17,1,0,5,10] [9,0,0,16,8]                    gap 7.5e-16
-    beyond    n=200  [150,50]           batch 2  ranks [150,50] x 2                                  gap 1.1e-15
-    D_CPU_MULTI = 1.47e-15 (ik)  ->  TOL_MULTI = max(10 D_CPU_MULTI, 1e-12) = 1e-12, a hundredth of the 1e-10 of the tolerance contract.
+    base              n=3    [2,2,3]            batch 4  ranks [2,1,0] x 4                                   gap 2.9e-16
+    used_up           n=4    [3,3,3]            batch 4  ranks [3,1,0] x 4                                   gap 4.8e-16
+    one_row           n=5    [1,3,2]            batch 4  ranks [1,3,1] x 4                                   gap 5.6e-16
+    rank_def          n=7    [3,3,3]            batch 3  ranks [2,0,2] x 3                                   gap 5.2e-16
+    ragged            n=5    [2,3,2]            batch 4  ranks [2,3,0] [2,0,2] [1,3,0] [0,3,2]               gap 3.6e-16
+    fixed             n=5    [2,2,3]            batch 4  ranks [2,1,0] [2,1,0] [0,0,0] [2,2,0]               gap 5.2e-16
+    ik                n=40   [12,12,12,12,12]   batch 8  ranks [12,12,12,4,0] x 8                            gap 1.5e-15
+    wide              n=70   [20,40,30]         batch 3  ranks [20,40,10] x 3                                gap 7.6e-16
+    large             n=127  [100,1,0,40,24]    batch 2  ranks [17,1,0,5,10] [9,0,0,16,8]                    gap 7.5e-16
+    fixed_wide        n=70   [20,40,30]         batch 3  ranks [20,40,4] [20,40,1] [20,40,10]                gap 1.8e-15
+    fixed_rank_def    n=7    [3,3,3]            batch 3  ranks [2,0,2] x 3                                   gap 1.8e-15
+    fixed_ragged      n=5    [2,3,2]            batch 4  ranks [2,1,0] [2,0,2] [1,0,0] [0,3,1]               gap 4.6e-16
+    fixed_tall        n=12   [70,30]            batch 2  ranks [7,0] [5,0]                                   gap 2.6e-16
+    beyond            n=200  [150,50]           batch 2  ranks [150,50] x 2                                  gap 1.1e-15
+    fit_staged_last   n=40   [12]x13+[11]       batch 2  ranks [12,12,12,4,0,...] x 2                        gap 1.2e-15
+    fit_hbm_first     n=40   [12]x14            batch 2  ranks [12,12,12,4,0,...] x 2                        gap 1.2e-15
+    fit_hbm_last      n=40   [12]x22+[10]       batch 2  ranks [12,12,12,4,0,...] x 2                        gap 1.1e-15
+    fit_single_first  n=40   [12]x22+[11]       batch 2  ranks [12,12,12,4,0,...] x 2                        gap 1.3e-15
+    D_CPU_MULTI = 1.80e-15 (fixed_rank_def)  ->  TOL_MULTI = max(10 D_CPU_MULTI, 1e-12) = 1e-12, a hundredth of the 1e-10 of the tolerance contract.
 """
 import functools
 import os
@@ -52,29 +65,75 @@ import adjoint_cases as AC  # noqa: E402
 from lexls_amd import problems as P  # noqa: E402
 from oracle import oracle_ctypes as oracle  # noqa: E402
 
-D_CPU_MULTI = 1.47e-15  # measured: the table above (tests/test_adjoint_multi_cases.py re-measures it)
+D_CPU_MULTI = 1.80e-15  # measured: the table above (tests/test_adjoint_multi_cases.py re-measures it)
 TOL_MULTI = max(10.0 * D_CPU_MULTI, 1e-12)
 
-BEYOND = dict(n=200, dims=[150, 50], batch=2, seed=20290301)
+# cases of this file alone: name -> n, dims, batch, seed; large: reference (B) + identities, else the unit solves
+EXTRA = {"beyond": dict(n=200, dims=[150, 50], batch=2, seed=20290301, large=True)}
 NAMES = list(AC.CASES) + ["beyond"]
 SETS = ("1", "3", "64", "65", "identity")
 NR = 65  # cotangents of the master set
+
+# ---- the fit rule, restated from lexls_amd/csrc/lexls_lds.h (adjoint_multi_lds_bytes, adjoint_multi_form); tests/test_adjoint_multi_cases.py holds
+# the restatement to tests/adjoint_multi_fit_check.cpp's numbers ----
+LDS_LIMIT = 160 * 1024  # kMaxLdsBytes: one workgroup's LDS
+STAGED, HBM, SINGLE = "solve_adjoint_multi<64,staged>", "solve_adjoint_multi<64,hbm>", "solve_adjoint<64> x K"
+
+
+def lds_bytes(n, cap, staged):
+    """the per-lane state gh (n) and cb (cap), [index][lane] with leading dimension 65, and 2 n words of transpositions and positions; staged:
+    + the factor's n columns (odd leading dimension cap | 1) and hh (cap)"""
+    b = 8 * 65 * (n + cap) + 8 * n
+    if staged:
+        b += 8 * ((cap | 1) * n + cap)
+    return (b + 15) & ~15
+
+
+def form(n, cap):
+    return STAGED if lds_bytes(n, cap, True) <= LDS_LIMIT else (HBM if lds_bytes(n, cap, False) <= LDS_LIMIT else SINGLE)
+
+
+def last_cap(n, form_name):
+    """the largest cap the rule still sends to `form_name` at n variables (the rule is monotone in cap)"""
+    cap = 1
+    while form(n, cap + 1) == form_name or form(n, cap) != form_name:
+        cap += 1
+    return cap
+
+
+def levels_of(cap, dim=12):
+    """cap rows in levels of `dim`, the rest in a last shorter one"""
+    return [dim] * (cap // dim) + ([cap % dim] if cap % dim else [])
+
+
+# device runs on both sides of the rule's two switches at n = 40: the last staged shape, the first hbm shape, the last hbm shape, the first
+# per-cotangent shape.  iid data, batch 2; the first four levels take the 40 columns (ranks 12, 12, 12, 4)
+FIT_N = 40
+FIT_CAPS = {"fit_staged_last": last_cap(FIT_N, STAGED), "fit_hbm_first": last_cap(FIT_N, STAGED) + 1, "fit_hbm_last": last_cap(FIT_N, HBM),
+            "fit_single_first": last_cap(FIT_N, HBM) + 1}
+FIT_NAMES = list(FIT_CAPS)
+for _i, (_name, _cap) in enumerate(FIT_CAPS.items()):
+    EXTRA[_name] = dict(n=FIT_N, dims=levels_of(_cap), batch=2, seed=20310201 + _i, large=False)
+
 # the form the host-side fit rule (lexls_lds.h: adjoint_multi_form) has to give each case
-FORMS = {name: "solve_adjoint_multi<64,staged>" for name in AC.CASES}
-FORMS.update(large="solve_adjoint_multi<64,hbm>", beyond="solve_adjoint<64> x K")
+FORMS = {name: STAGED for name in AC.CASES}
+FORMS.update(large=HBM, beyond=SINGLE)
+FORMS.update({name: form(FIT_N, cap) for name, cap in FIT_CAPS.items()})
+# case -> kernel policy -> the producer of the kept factor (adjoint_cases.PRODUCERS and this file's own cases)
+PRODUCERS = dict(AC.PRODUCERS, beyond={5: "lqr_large<multi-launch>"}, **{name: {0: AC.GENERIC256} for name in FIT_NAMES})
 
 
 def _base(name):
     """the case's inputs, the oracle's run on them and, for the large cases, the three pairs of the identities"""
-    if name != "beyond":
+    if name not in EXTRA:
         return AC.build(name)
-    c = BEYOND
+    c = EXTRA[name]
     n, caps, B, seed = c["n"], list(c["dims"]), c["batch"], c["seed"]
     cap = sum(caps)
     case = dict(name=name, n=n, caps=caps, lod=P.lse_batch(seed, B, n, caps), dims=np.tile(np.asarray(caps, np.uint32), (B, 1)), fixed={},
-                g=P.normal(seed + 900, B * n).reshape(B, n), large=True, A=None, pairs=[])
+                g=P.normal(seed + 900, B * n).reshape(B, n), large=c["large"], A=None, pairs=[])
     case["ref"] = oracle.lse_run(case["lod"], case["dims"], n, maxdim=np.asarray(caps, np.uint32), nthreads=4)
-    for t in range(3):
+    for t in range(3 if c["large"] else 0):
         b0 = P.normal(seed + 7000 + 2 * t, B * cap).reshape(B, cap)
         b1 = P.normal(seed + 7001 + 2 * t, B * cap).reshape(B, cap)
         case["pairs"].append((b1 - b0, AC._solve(case, b1)["x"] - AC._solve(case, b0)["x"]))
@@ -84,7 +143,7 @@ def _base(name):
 def cotangents(case):
     """the master set R (batch, 65, n): R[:, 0] = the case's g"""
     B, n = case["g"].shape
-    seed = BEYOND["seed"] if case["name"] == "beyond" else AC.CASES[case["name"]]["seed"]
+    seed = (EXTRA.get(case["name"]) or AC.CASES[case["name"]])["seed"]
     R = P.normal(seed + 4000, B * NR * n).reshape(B, NR, n)
     R[:, 0, :] = case["g"]
     return R
@@ -173,13 +232,13 @@ def build(name):
 
 
 def summary(case):
-    return (f"    {case['name']:<9} n={case['n']:<4} {str(case['caps']).replace(' ', ''):<18} batch {case['lod'].shape[0]}  ranks "
+    return (f"    {case['name']:<15} n={case['n']:<4} {str(case['caps']).replace(' ', ''):<18} batch {case['lod'].shape[0]}  ranks "
             f"{' '.join(str(r.tolist()).replace(' ', '') for r in case['ref']['rank']):<44} gap {case['gap']:.1e}")
 
 
 if __name__ == "__main__":
     worst = 0.0
-    for nm in NAMES:
+    for nm in NAMES + FIT_NAMES:
         c = build(nm)
         worst = max(worst, c["gap"])
         print(summary(c))

@@ -23,6 +23,10 @@ Cases — small on purpose:
     budget      (status rule, tests/test_gpu_lsi_adjoint.py) small_sb's shape, batch 6, run cold with max_number_of_factorizations = 1: instances
                 0, 2, 4 have inequality bounds too wide to be reached and end PROBLEM_SOLVED on the equalities alone, the others are stopped by the
                 budget (the oracle's statuses, asserted on the CPU)
+    tile        (scatter tile, tests/test_gpu_lsi_adjoint_groups.py) n = 4, simple bounds (4), general (1030), general (2, equalities), batch 2:
+                1036 user rows, more than the 1024 the scatter kernels take per tile.  Rows 5 and 1027 of the second objective are equalities, its
+                other rows inequalities 100 away from anything |x_i| <= 1 reaches: the working set has rows on both sides of user row 1024.
+                Reference (A) alone
 
 D_CPU is the largest discrepancy the CPU test finds — the two sides of (B)'s identities with (A)'s gradients, per instance relative to
 max(1, the larger sum of magnitudes of the two products) (adjoint_cases.identity_gap).  The GPU tolerance is TOL = max(10 * D_CPU, 1e-12), the rule
@@ -35,6 +39,7 @@ MEASURED (`python tests/lsi_adjoint_cases.py`, the oracle and numpy alone; gap =
     empty_ws  n=4   [3,3]              batch 4  |W| [4,0,5,0]                  held True  gap 8.4e-16  |grad| 1.7e+00
     ik        n=40  [12,12,12,12,12]   batch 8  |W| [42,42,47,42,42,41,45,43]  held True  gap 8.8e-15  |grad| 3.6e+00
     budget    statuses [0, 2, 0, 2, 0, 2]
+    tile      n=4   [4,1030,2]  batch 2  statuses [0, 0]  active user rows [0,9,1031,1034,1035] [0,2,3,9,1031,1034,1035]  |grad| 4.1e+00
     D_CPU = 8.79e-15 (ik)  ->  TOL = max(10 D_CPU, 1e-12) = 1e-12, a hundredth of the 1e-10 of the tolerance contract.
 """
 import functools
@@ -68,11 +73,14 @@ CASES = {
     "ik": dict(n=40, dims=(12, 12, 12, 12, 12), simple=True, batch=8, seed=20300514),
 }
 BUDGET = dict(n=4, dims=(4, 2, 2), simple=True, batch=6, seed=20300601, wide=(0, 2, 4))
+# the scatter kernels tile the user rows by ADJ_TILE = 1024 (lexls_amd/csrc/lsi_batch.h): 1036 rows, with active ones on both sides of row 1024
+TILE = dict(n=4, dims=(4, 1030, 2), simple=True, batch=2, seed=20310301, equalities=(5, 1027), far=100.0)
+ADJ_TILE = 1024
 
 
 def problems_of(name):
     """the objective lists of a case's instances (lexls_amd.problems.lsi_problem, then the case's own changes)"""
-    c = BUDGET if name == "budget" else CASES[name]
+    c = BUDGET if name == "budget" else TILE if name == "tile" else CASES[name]
     out = []
     for i in range(c["batch"]):
         objs = P.lsi_problem(c["seed"] + i, c["n"], c["dims"], simple_bounds=c["simple"])
@@ -84,6 +92,12 @@ def problems_of(name):
             for o in objs:
                 w = 1.0 + P.uniform(c["seed"] + 50 + i, len(o["lb"]))
                 o["lb"], o["ub"] = -w, w[::-1].copy()
+        if c.get("equalities"):  # level 1: inequalities far away from anything x can reach (|x_i| <= 1), but for two equalities
+            o = objs[1]
+            keep = np.zeros(len(o["lb"]), bool)
+            keep[list(c["equalities"])] = True
+            mid = 0.5 * (o["lb"] + o["ub"])
+            o["lb"], o["ub"] = np.where(keep, mid, o["lb"] - c["far"]), np.where(keep, mid, o["ub"] + c["far"])
         if i in c.get("wide", ()):  # the inequalities out of reach: the equalities of the last level alone decide
             for o in objs[:-1]:
                 o["lb"], o["ub"] = o["lb"] - 100.0, o["ub"] + 100.0
@@ -210,6 +224,21 @@ def build_budget():
     return dict(name="budget", n=n, probs=probs, runs=runs, status=status, g=g, A=(glb, gub), active=np.stack([np.concatenate(r["active"]) for r in runs]))
 
 
+@functools.lru_cache(maxsize=None)
+def build_tile():
+    """the scatter-tile case: 4 simple bounds, 1030 general rows of which rows 5 and 1027 are equalities and the rest out of reach, 2 equalities;
+    user rows 0 .. 1035, so the scatter kernels run a second tile of ADJ_TILE rows.  A = reference (A) on the oracle's final working sets"""
+    c = TILE
+    n, B = c["n"], c["batch"]
+    probs = problems_of("tile")
+    runs = [oracle.lsi_run(n, objs) for objs in probs]
+    status = np.asarray([r["info"]["status"] for r in runs])
+    g = P.normal(c["seed"] + 900, B * n).reshape(B, n)
+    glb, gub, ranks = reference_a(n, probs, [r["active"] for r in runs], status, g)
+    return dict(name="tile", n=n, dims=np.asarray(c["dims"], np.uint32), probs=probs, runs=runs, status=status, g=g, A=(glb, gub), ranks=ranks,
+                active=np.stack([np.concatenate(r["active"]) for r in runs]))
+
+
 def summary(case):
     nact = (case["active"] != 0).sum(axis=1)
     return (f"    {case['name']:<9} n={case['n']:<3} {str(case['dims'].tolist()).replace(' ', ''):<18} batch {len(case['probs'])}  |W| {str(nact.tolist()).replace(' ', ''):<26} "
@@ -224,4 +253,7 @@ if __name__ == "__main__":
         print(summary(cs))
     bd = build_budget()
     print(f"    budget    statuses {bd['status'].tolist()}")
+    tl = build_tile()
+    print(f"    tile      n=4   [4,1030,2]  batch 2  statuses {tl['status'].tolist()}  active user rows {[np.flatnonzero(a).tolist() for a in tl['active']]}  "
+          f"|grad| {max(np.abs(tl['A'][0]).max(), np.abs(tl['A'][1]).max()):.1e}")
     print(f"    D_CPU (largest gap) {worst:.2e}  ->  TOL = max(10 D_CPU, 1e-12) = {max(10 * worst, 1e-12):.2e}")

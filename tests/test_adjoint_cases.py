@@ -37,6 +37,50 @@ def test_every_case_is_what_it_is_for(cases):
     assert (rank["large"] == [[17, 1, 0, 5, 10], [9, 0, 0, 16, 8]]).all()
 
 
+def test_the_fixed_cases_meet_the_other_edges(cases):
+    """what fixed_wide, fixed_rank_def, fixed_ragged and fixed_tall are named for, from the oracle's rank / fcol / totalrank"""
+    def of(name):
+        c = cases[name]
+        r = c["ref"]
+        return c, c["fixed"]["nfixed"].astype(int), r["rank"].astype(int), r["fcol"].astype(int), r["totalrank"].astype(int), c["dims"].sum(axis=1).astype(int)
+
+    for name in ("fixed_wide", "fixed_rank_def", "fixed_ragged", "fixed_tall"):
+        c, nf, rank, fcol, T, m = of(name)
+        assert c["A"] is not None and not c["large"]                       # reference (A): the unit solves
+        np.testing.assert_array_equal(fcol[:, 0], nf)                      # the pivot columns start behind the fixed ones ...
+        np.testing.assert_array_equal(T, nf + rank.sum(axis=1))            # ... and end at T
+        for b in range(len(nf)):
+            assert sorted(c["fixed"]["fixed_idx"][b, :nf[b]].tolist()) == sorted(set(c["fixed"]["fixed_idx"][b, :nf[b]].tolist()))
+            if nf[b]:
+                assert np.abs(AC.expected(c)[1][b, :nf[b]]).max() > 1e-2, (name, b)  # grad_fixed is not 0: step (d) has something to get wrong
+
+    c, nf, rank, fcol, T, m = of("fixed_wide")
+    assert c["n"] > 64 and nf.tolist() == [6, 9, 0]                        # nfixed == 0 beside nfixed > 0; pivot columns [nf, T) at n > 64
+    assert nf[0] > 4 and nf[1] > 8                                         # step (d): a second and a third group of AU = 4 columns
+    assert (m > 64).all() and (T == c["n"]).all()                          # column_dot makes a second trip; every column is a pivot or fixed
+    assert (rank == [[20, 40, 4], [20, 40, 1], [20, 40, 10]]).all()
+    assert np.abs(AC.expected(c)[0][:, 64:]).min(axis=1).min() > 0         # cb is live behind row 64
+    assert [c["fixed"]["fixed_idx"][b, :nf[b]].tolist() for b in range(3)] == [AC.WIDE_ORDER[:6], AC.WIDE_ORDER[:9], []]
+    assert sorted(AC.WIDE_ORDER) == list(range(70))
+
+    c, nf, rank, fcol, T, m = of("fixed_rank_def")
+    assert nf.tolist() == [2, 1, 3] and (rank == [2, 0, 2]).all()          # a rank-0 level, rank < dim, behind fixed columns
+    assert len(set(T.tolist())) == 3 and (T <= c["n"]).all()               # another T per problem
+    assert (rank < c["dims"]).all()
+
+    c, nf, rank, fcol, T, m = of("fixed_ragged")
+    assert nf.tolist() == [2, 0, 4, 1] and (c["dims"] == AC.RAGGED_DIMS).all() and (c["dims"] == 0).any()
+    assert (c["dims"][nf > 0] == 0).any()                                  # an empty level in a problem with fixed variables
+    assert c["n"] - nf[2] == 1 and rank[2].tolist() == [1, 0, 0]           # one free variable
+    assert ((fcol >= T[:, None]) & (c["dims"] > 0) & (nf[:, None] > 0)).any()  # a level with rows finds the columns used up
+    assert (rank == [[2, 1, 0], [2, 0, 2], [1, 0, 0], [0, 3, 1]]).all()
+
+    c, nf, rank, fcol, T, m = of("fixed_tall")
+    assert nf.tolist() == [5, 7] and c["caps"] == [70, 30] and (m == 100).all()  # reflectors over 70 rows, step (d) over 100
+    assert (rank[:, 0] == c["n"] - nf).all() and (rank[:, 1] == 0).all() and (fcol[:, 1] == c["n"]).all()  # the columns are gone
+    assert (c["ref"]["hh"][:, :5] != 0).all()                              # the reflectors over 70, 69, ... rows exist
+
+
 def test_absent_rows_and_slots_are_zero_and_the_rest_is_not(cases):
     for c in cases.values():
         grad_rhs, grad_fixed = AC.expected(c)

@@ -17,16 +17,7 @@ pytestmark = pytest.mark.gpu
 
 INVALID, UNSUPPORTED = 1, 3
 CONSUMER = "solve_adjoint<64>"
-QUAD1, GENERIC64, LWAVE = "lqr_quad<1,12,factor>", "lqr_generic<64,lds>", "lqr_lwave<41,12>"
-SMALL = {0: QUAD1, 1: GENERIC64, 3: LWAVE}  # four-per-wavefront, generic-only, left-looking
-# case -> kernel policy -> the producer of the kept factor (register-resident: lqr_wave; bit-exact large: lqr_large<multi-launch>)
-PRODUCERS = {
-    "base": SMALL, "used_up": SMALL, "one_row": SMALL, "rank_def": SMALL, "ragged": SMALL,
-    "fixed": {0: "lqr_wave<41,12>", 1: GENERIC64, 4: "lqr_quad<3,12,factor,fixed>"},
-    "ik": {0: "lqr_wave<41,12,exact>", 3: "lqr_lwave<41,12,exact>", 4: "lqr_quad<3,12,shift 7,factor>", 1: GENERIC64},
-    "wide": {0: "lqr_generic<256,lds>"},
-    "large": {5: "lqr_large<multi-launch>", 1: "lqr_generic<1024,hbm>"},
-}
+PRODUCERS = AC.PRODUCERS  # case -> kernel policy -> the producer of the kept factor, as the host-side dispatch plan names it
 
 
 def handle(hip, case, policy=None):

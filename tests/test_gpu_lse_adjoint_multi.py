@@ -2,7 +2,9 @@
 cotangent) against the references of tests/adjoint_multi_cases.py, within MC.TOL_MULTI (derived there from the references' own disagreement
 on the CPU, never from the device's figures): every case x every cotangent set behind every producer of a kept factor that
 tests/test_gpu_lse_adjoint.py uses; the form the fit rule takes is named (last_consumer_kernel); the independence contract is held bit for
-bit; NaN sentinels around G and the outputs stay intact; the error rules leave the outputs alone."""
+bit; NaN sentinels around G and the outputs stay intact; the error rules leave the outputs alone.  Every case also runs with the form moved
+down the launcher's list by LEXLS_ADJOINT_MULTI_FORM (read at every call): `hbm` bit-equal to the staged run, `single` bit-equal to K calls of
+the single-cotangent entry; and four shapes sit on both sides of the fit rule's two switches (MC.FIT_NAMES)."""
 import ctypes as C
 
 import numpy as np
@@ -11,13 +13,13 @@ import torch  # (before the HIP library loads: one process, one HIP runtime)
 
 import adjoint_multi_cases as MC
 from lexls_amd import capi
-from test_gpu_lse_adjoint import PRODUCERS as SINGLE_PRODUCERS, handle
+from test_gpu_lse_adjoint import handle
 
 pytestmark = pytest.mark.gpu
 
 INVALID, UNSUPPORTED = 1, 3
 PAD = 96  # sentinel doubles in front of and behind every device array
-PRODUCERS = dict(SINGLE_PRODUCERS, beyond={5: "lqr_large<multi-launch>"})
+PRODUCERS = MC.PRODUCERS
 
 
 def ptr(a):
@@ -150,6 +152,128 @@ def test_a_cotangent_is_independent_of_its_company_bit_for_bit(hip, oracle, name
     same(host_form(s, R[:, order]), order, "a permuted set")
     same(host_form(s, R[:, :3]), [0, 1, 2], "the first three")
     s.close()
+
+
+FORM_SWITCH = "LEXLS_ADJOINT_MULTI_FORM"
+
+
+def assert_within_tol(case, st, G, rhs, fixed, ctx):
+    """within TOL_MULTI of the reference, the identities of the large cases, exact zeros in the absent rows and slots"""
+    m = case["dims"].sum(axis=1)
+    nf = case["fixed"]["nfixed"] if case["fixed"] else np.zeros(len(m), np.uint32)
+    e_rhs, e_fixed = MC.gap(rhs, MC.select_ref(st, case, 0)), MC.gap(fixed, MC.select_ref(st, case, 1))
+    ident = MC.identities(case, G, rhs)
+    print(f"{ctx}grad_rhs {e_rhs:.2e} grad_fixed {e_fixed:.2e} identities {ident:.2e} (TOL_MULTI {MC.TOL_MULTI:.1e})")
+    assert e_rhs <= MC.TOL_MULTI and e_fixed <= MC.TOL_MULTI, ctx + f"{e_rhs:.3e} {e_fixed:.3e}"
+    assert ident <= MC.TOL_MULTI, ctx + f"identities {ident:.3e}"
+    for b in range(len(m)):
+        assert not rhs[b, :, m[b]:].any() and not fixed[b, :, nf[b]:].any(), ctx + f"problem {b}"
+
+
+@pytest.mark.parametrize("name", MC.NAMES)
+def test_forced_hbm_is_the_staged_run_bit_for_bit(hip, oracle, monkeypatch, name):
+    """the two instantiations run the same dfma chains on the same values; only where a factor entry is read from differs — so bits, not a tolerance"""
+    case = MC.build(name)
+    natural = MC.FORMS[name]
+    forced = MC.HBM if natural == MC.STAGED else natural  # (the switch only moves a shape down the list)
+    s = handle(hip, case, next(iter(PRODUCERS[name])))
+    s.factorize_solve(keep_factor=True)
+    before = (s.get_x(), s.get_lexqr(), s.get_hh_scalars())
+    sets = {st: MC.select(st, case["R"]) for st in ("3", "65", "identity")}
+    monkeypatch.delenv(FORM_SWITCH, raising=False)
+    base = {}
+    for st, G in sets.items():
+        base[st] = host_form(s, G)
+        assert s.last_consumer_kernel() == natural
+    monkeypatch.setenv(FORM_SWITCH, "hbm")
+    for st, G in sets.items():
+        ctx = f"{name}, hbm forced, K = {st}: "
+        rhs, fixed = host_form(s, G)
+        assert s.last_consumer_kernel() == forced, ctx + s.last_consumer_kernel()
+        np.testing.assert_array_equal(rhs, base[st][0], err_msg=ctx + "grad_rhs against the natural form")
+        np.testing.assert_array_equal(fixed, base[st][1], err_msg=ctx + "grad_fixed against the natural form")
+        assert_within_tol(case, st, G, rhs, fixed, ctx)
+        d_rhs, d_fixed = device_form(s, G)  # NaN frames around G and both outputs
+        assert s.last_consumer_kernel() == forced
+        np.testing.assert_array_equal(d_rhs, rhs, err_msg=ctx + "device form")
+        np.testing.assert_array_equal(d_fixed, fixed, err_msg=ctx + "device form")
+    np.testing.assert_array_equal(device_form(s, sets["3"], with_fixed=False)[0], base["3"][0])
+    if case["fixed"]:
+        assert all(base["65"][1][b].any() for b in np.flatnonzero(case["fixed"]["nfixed"])), "grad_fixed is 0: the fixed columns were not read"
+    monkeypatch.delenv(FORM_SWITCH)
+    np.testing.assert_array_equal(host_form(s, sets["65"])[0], base["65"][0])
+    assert s.last_consumer_kernel() == natural
+    for a, b_, what in zip((s.get_x(), s.get_lexqr(), s.get_hh_scalars()), before, ("x", "factor", "hh")):
+        np.testing.assert_array_equal(a, b_, err_msg=f"{name}: {what} changed")
+    s.close()
+
+
+@pytest.mark.parametrize("name", MC.NAMES)
+def test_forced_single_is_k_calls_of_the_single_cotangent_entry_bit_for_bit(hip, oracle, monkeypatch, name):
+    """the per-cotangent form runs solve_adjoint<64> itself: only its three strided copies can differ from a call on that cotangent alone"""
+    case = MC.build(name)
+    s = handle(hip, case, next(iter(PRODUCERS[name])))
+    s.factorize_solve(keep_factor=True)
+    before = (s.get_x(), s.get_lexqr(), s.get_hh_scalars())
+    R = np.ascontiguousarray(case["R"])
+    monkeypatch.delenv(FORM_SWITCH, raising=False)
+    natural = host_form(s, R[:, :3])  # the natural form first: where it is not per-cotangent the handle has no work buffer yet
+    assert s.last_consumer_kernel() == MC.FORMS[name]
+    monkeypatch.setenv(FORM_SWITCH, "single")
+    ctx = f"{name}, single forced, K = 65: "
+    rhs, fixed = host_form(s, R)
+    assert s.last_consumer_kernel() == MC.SINGLE, ctx + s.last_consumer_kernel()
+    assert_within_tol(case, "65", R, rhs, fixed, ctx)
+    assert_within_tol(case, "3", R[:, :3], natural[0], natural[1], f"{name}, natural form, K = 3: ")
+    d_rhs, d_fixed = device_form(s, R)  # NaN frames around G and both outputs
+    assert s.last_consumer_kernel() == MC.SINGLE
+    np.testing.assert_array_equal(d_rhs, rhs, err_msg=ctx + "device form")
+    np.testing.assert_array_equal(d_fixed, fixed, err_msg=ctx + "device form")
+    np.testing.assert_array_equal(device_form(s, R, with_fixed=False)[0], rhs, err_msg=ctx + "device form without grad_fixed")  # (grad_fixed stays NaN)
+    one_rhs = torch.empty((s.batch, s.cap), dtype=torch.float64, device="cuda")
+    one_fixed = torch.empty((s.batch, s.nVar), dtype=torch.float64, device="cuda")
+    for c in range(R.shape[1]):
+        s.solve_adjoint_device(torch.from_numpy(np.ascontiguousarray(R[:, c])).cuda(), one_rhs, one_fixed)
+        s.synchronize()
+        assert s.last_consumer_kernel() == "solve_adjoint<64>"
+        np.testing.assert_array_equal(rhs[:, c], one_rhs.cpu().numpy(), err_msg=ctx + f"grad_rhs of cotangent {c}")
+        np.testing.assert_array_equal(fixed[:, c], one_fixed.cpu().numpy(), err_msg=ctx + f"grad_fixed of cotangent {c}")
+    if case["fixed"]:
+        for b in np.flatnonzero(case["fixed"]["nfixed"]):
+            assert fixed[b].any(axis=1).all(), ctx + f"grad_fixed of problem {b} is 0 for some cotangent"
+    ident = MC.select("identity", R)  # another K behind it: the pitches follow ncot
+    i_rhs, i_fixed = host_form(s, ident)
+    assert s.last_consumer_kernel() == MC.SINGLE
+    assert_within_tol(case, "identity", ident, i_rhs, i_fixed, f"{name}, single forced, K = identity: ")
+    for a, b_, what in zip((s.get_x(), s.get_lexqr(), s.get_hh_scalars()), before, ("x", "factor", "hh")):
+        np.testing.assert_array_equal(a, b_, err_msg=f"{name}: {what} changed")
+    s.close()
+
+
+@pytest.mark.parametrize("name", MC.FIT_NAMES)
+def test_both_sides_of_the_fit_rule(hip, oracle, monkeypatch, name):
+    """n = 40 at the last staged, first hbm, last hbm and first per-cotangent capacity: the kernel carves gh | cb | perm | pos | L | hh out of
+    exactly adjoint_multi_lds_bytes, so an off-by-one in the rule or in the carving is an LDS overrun at these shapes"""
+    monkeypatch.delenv(FORM_SWITCH, raising=False)
+    case = MC.build(name)
+    for policy, producer in PRODUCERS[name].items():
+        s = handle(hip, case, policy)
+        s.factorize_solve(keep_factor=True)
+        assert s.last_kernel() == producer
+        assert float(np.abs(s.get_x() - case["ref"]["x"]).max()) <= 1e-10
+        before = (s.get_x(), s.get_lexqr(), s.get_hh_scalars())
+        for st in ("3", "65"):
+            ctx = f"{name} (cap {s.cap}) on {producer}, K = {st}: "
+            G = MC.select(st, case["R"])
+            rhs, fixed = host_form(s, G)
+            assert s.last_consumer_kernel() == MC.FORMS[name], ctx + s.last_consumer_kernel()
+            assert_within_tol(case, st, G, rhs, fixed, ctx)
+            d_rhs, d_fixed = device_form(s, G)
+            np.testing.assert_array_equal(d_rhs, rhs, err_msg=ctx + "device form")
+            np.testing.assert_array_equal(d_fixed, fixed, err_msg=ctx + "device form")
+        for a, b_, what in zip((s.get_x(), s.get_lexqr(), s.get_hh_scalars()), before, ("x", "factor", "hh")):
+            np.testing.assert_array_equal(a, b_, err_msg=f"{name} on {producer}: {what} changed")
+        s.close()
 
 
 @pytest.mark.parametrize("name", [n for n in MC.NAMES if n not in ("wide", "large", "beyond")])  # the cases with unit solves

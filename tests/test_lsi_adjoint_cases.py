@@ -81,3 +81,18 @@ def test_the_budget_case_has_both_kinds_of_instances():
         assert bd["active"][b].any()  # a working set, but not a solved one: zeros are the status rule's, not an empty set's
     for b in wide:
         assert np.abs(bd["A"][1][b]).max() > 1e-3
+
+
+def test_the_tile_case_has_active_rows_on_both_sides_of_the_tile_edge():
+    tl = LC.build_tile()
+    total = int(tl["dims"].sum())
+    assert LC.ADJ_TILE < total < 2 * LC.ADJ_TILE and tl["active"].shape == (2, total) and (tl["status"] == LC.SOLVED).all()
+    eq = [4 + r for r in LC.TILE["equalities"]]  # user rows of the two equalities of the second objective
+    assert eq[0] < LC.ADJ_TILE < eq[1]
+    glb, gub = tl["A"]
+    for b in range(2):
+        rows = np.flatnonzero(tl["active"][b])
+        assert set(eq) <= set(rows.tolist()) and set(rows.tolist()) <= set(range(4)) | set(eq) | {total - 2, total - 1}  # the far inequalities stay out
+        assert (tl["active"][b, eq] == LC.EQ).all() and (np.abs(gub[b, eq]) > 1e-3).all()                         # values on both sides of row 1024
+        assert not glb[b, tl["active"][b] != LC.LB].any() and not gub[b, (tl["active"][b] != LC.UB) & (tl["active"][b] != LC.EQ)].any()
+    assert (tl["active"][:, :4] != 0).any() and np.abs(gub[:, total - 2:]).max() > 1e-3  # a simple bound (grad_fixed) and the last tile's last rows
