@@ -104,7 +104,10 @@ int lexls_lse_set_fixed_type(lexls_lse_t h, const uint8_t *h_type);
 /* replaces setCtrType (lexlse.h:1548): batch x cap ConstraintActivationType bytes, row order of LOD */
 int lexls_lse_set_ctr_type(lexls_lse_t h, const uint8_t *h_types);
 /* lock-step batches (batched LexLSI): problems whose flag is non-zero are left untouched by the next
- * factorize / factorize_solve calls (their previous results stay valid).  NULL clears the mask. */
+ * factorize / factorize_solve calls (their previous results stay valid).  NULL clears the mask; a mask whose bytes are all zero is no
+ * mask (the dispatch of an unmasked run, the same bits).  The guarantee covers problems whose dims / fixed variables are those of the
+ * skipped run: x, pivots, ranks, the kept factor with its Householder scalars and the accuracy guard's report keep their bits, and the
+ * post-factorization calls read the kept factor as the old one.  A skipped problem's input is not read (it may hold anything). */
 int lexls_lse_set_skip(lexls_lse_t h, const uint8_t *h_skip);
 /* replaces setProblem / setData (lexlse.h:1511-1530): copies batch x cap x (nVar+1) doubles H2D */
 int lexls_lse_set_problem_host(lexls_lse_t h, const double *h_lod);
@@ -368,7 +371,10 @@ int lexls_lse_set_accuracy_guard(lexls_lse_t h, int mode, double threshold);
  * 1 (T) and estimate below the threshold, 2 (T) flagged and not re-solved (mode 1),
  * 3 flagged and re-solved under (B) (mode 2).  *h_flagged = number of problems with status 2 or 3. Any pointer may be NULL.
  * Describes the last factorization; all zeros when it ran with the guard off.  Waits for the handle's stream (also under deferred sync).
- * Status 0 problems report estimate 0. */
+ * Status 0 problems report estimate 0.
+ * Under a skip mask (lexls_lse_set_skip) the report of a skipped problem is KEPT: estimate and status stay those of the factorization that
+ * produced its results, on the estimating kernel and on a bit-exact plan alike, and mode 2 does not re-solve it (its input is not read).
+ * The same guard mode and threshold are assumed from run to run: the status of a kept estimate is re-derived under the current ones. */
 int lexls_lse_get_accuracy(lexls_lse_t h, double *h_estimate, uint8_t *h_status, uint32_t *h_flagged);
 
 /* ---- prefix reuse ------------------------------------------------------------------------------

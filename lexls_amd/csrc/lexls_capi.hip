@@ -640,7 +640,8 @@ extern "C"
         HIP_TRY(hipSetDevice(h->device));
         HIP_TRY(hipMemcpyAsync(h->d_skip, h_skip, (size_t)h->batch, hipMemcpyHostToDevice, h->stream));
         if (!h->deferred_sync) HIP_TRY(hipStreamSynchronize(h->stream));
-        h->has_skip = true;
+        h->has_skip = false; // as upload_round: kernels look at the mask only when some problem is masked (an all-zero mask is no mask)
+        for (uint32_t b = 0; b < h->batch && !h->has_skip; b++) h->has_skip = h_skip[b] != 0;
         return LEXLS_OK;
     }
 
@@ -956,6 +957,8 @@ extern "C"
                 HIP_TRY(launch_guard_compact(h->d_guard_est, h->d_guard_status, h->d_guard_ind, h->batch, h->guard_threshold, h->guard_mode, h->stream));
                 if (h->guard_mode == 2) HIP_TRY(launch_kernel(plan_guard_resolve(q), a, h->stream, x));
             }
+            else if (a.skip) // a bit-exact kernel solved the problems the mask leaves: status 0, no estimate; a skipped problem keeps its report
+                HIP_TRY(launch_guard_clear(h->d_guard_est, h->d_guard_status, a.skip, h->batch, h->stream));
             else // a bit-exact kernel solved: status 0, no estimate
             {
                 HIP_TRY(hipMemsetAsync(h->d_guard_est, 0, 8 * (size_t)h->batch, h->stream));

@@ -30,7 +30,20 @@ namespace lexls
             base = (uint32_t)__builtin_amdgcn_readlane((int)base, first);
             if (flagged) ind[1 + base + below] = b;
         }
+
+        /// a bit-exact kernel solved under a skip mask: status 0 and no estimate for the problems it solved, the report of a skipped problem kept
+        __global__ __launch_bounds__(256) void guard_clear_kernel(double *est, uint8_t *status, const uint8_t *skip, uint32_t batch)
+        {
+            const uint32_t b = blockIdx.x * 256u + threadIdx.x;
+            if (b < batch && !skip[b]) est[b] = 0.0, status[b] = (uint8_t)0;
+        }
     } // namespace
+
+    hipError_t launch_guard_clear(double *est, uint8_t *status, const uint8_t *skip, uint32_t batch, hipStream_t s)
+    {
+        hipLaunchKernelGGL(guard_clear_kernel, dim3((batch + 255u) / 256u), dim3(256), 0, s, est, status, skip, batch);
+        return hipGetLastError();
+    }
 
     hipError_t launch_guard_compact(const double *est, uint8_t *status, uint32_t *ind, uint32_t batch, double threshold, int mode, hipStream_t s)
     {

@@ -63,6 +63,8 @@ namespace lexls
     // lexls_guard.hip — the accuracy guard's compaction: status[b] from est[b] against the threshold (1 below it; 2 flagged, mode 1; 3 flagged,
     // mode 2) and, in mode 2, ind = [count, flagged problems] (ind[0] cleared by the estimating kernel in front of it in the stream)
     hipError_t launch_guard_compact(const double *est, uint8_t *status, uint32_t *ind, uint32_t batch, double threshold, int mode, hipStream_t s);
+    // ... and the report of a bit-exact solve under a skip mask: estimate 0 and status 0 where skip[b] == 0, a skipped problem's report kept
+    hipError_t launch_guard_clear(double *est, uint8_t *status, const uint8_t *skip, uint32_t batch, hipStream_t s);
 
     // lqr_large.hip — problems too large for one CU's LDS: one launch per stage, the whole chip per problem
     size_t large_state_bytes(uint32_t batch);

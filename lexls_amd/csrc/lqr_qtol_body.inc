@@ -879,7 +879,7 @@
             if constexpr (EST)
             {
                 const double e2 = row_max16(est2);
-                if (gl == 0 && b < a.batch) est_out[b] = (live && e2 > 0.0) ? 2.0 * qt_sqrt(e2) : 0.0; // (no pivot at all: nothing to vouch for)
+                if (gl == 0 && live) est_out[b] = e2 > 0.0 ? 2.0 * qt_sqrt(e2) : 0.0; // (no pivot at all: nothing to vouch for; a skipped problem keeps its estimate)
             }
             STAMP(10)
             STAMP_WRITE

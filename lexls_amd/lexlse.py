@@ -90,6 +90,18 @@ class BatchedLexLSE:
         assert types.shape == (self.batch, self.cap)
         capi.check(capi.lib().lexls_lse_set_ctr_type(self._h, _ptr(types, C.c_uint8)))
 
+    def set_skip(self, mask):
+        """lexls_lse_set_skip: mask (batch,) uint8 — problems whose byte is non-zero are left untouched by the following factorize /
+        factorize_solve calls (their previous results stay valid: x, pivots, ranks, the kept factor, the accuracy guard's report); None
+        clears the mask.  Holds for problems whose dimensions and fixed variables are those of the run their results come from."""
+        if mask is None:
+            capi.check(capi.lib().lexls_lse_set_skip(self._h, None))
+            return
+        mask = np.ascontiguousarray(mask, np.uint8)
+        if mask.shape != (self.batch,):
+            raise ValueError(f"mask must have shape {(self.batch,)}, got {mask.shape}")
+        capi.check(capi.lib().lexls_lse_set_skip(self._h, _ptr(mask, C.c_uint8)))
+
     def setProblem(self, lod):
         """lod: host array (batch, nVar+1, cap); copied to the device."""
         lod = np.ascontiguousarray(lod, np.float64)

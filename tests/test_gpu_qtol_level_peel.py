@@ -5,14 +5,11 @@ eliminates by fewer than nine pivots, or none), rows of one wavefront that cross
 the other instantiations, the ragged form with an empty level 0, the estimating form.  Acceptance = tests/test_gpu_qtol.py::check /
 tests/test_gpu_qtol_ragged.py::check (contract (T) of include/lexls_hip.h): column permutation, ranks, first columns and total rank EXACT, x
 within 1e-10 relative to max(1, |x|_inf).  The ranks every constructed problem is meant to have are asserted on the oracle's result."""
-import ctypes as C
-
 import numpy as np
 import pytest
 
 import test_gpu_qtol as Q
 import test_gpu_qtol_ragged as R
-from lexls_amd import capi
 from lexls_amd import problems as P
 
 pytestmark = pytest.mark.gpu
@@ -81,8 +78,7 @@ def test_skipped_problem_inside_the_quad(hip, oracle):
     x0, perm0, r0 = s.get_x().copy(), s.get_column_permutations().copy(), s.getRanks()[0].copy()
     lod2 = lod[[1, 0, 3, 2]].copy()
     ref = oracle.lse_run(lod2, dims, 20, nthreads=8)
-    skip = np.array([0, 0, 1, 0], np.uint8)
-    capi.check(capi.lib().lexls_lse_set_skip(s._h, skip.ctypes.data_as(C.POINTER(C.c_uint8))))
+    s.set_skip(np.array([0, 0, 1, 0], np.uint8))
     s.setProblem(lod2)
     s.factorize_solve(keep_factor=False)
     assert s.last_kernel() == "lqr_qtol<2,12>"
