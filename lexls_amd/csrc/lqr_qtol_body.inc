@@ -200,6 +200,19 @@
             // same lambdas (never L0: the k > 0 tests are then run-time tests).  (<3,12,0,0> with EST spills two in either shape and is compiled
             // from lqr_qtol_body_unpeeled.inc: lqr_qtol_impl.h)
             constexpr bool PEEL = !(EST && NS == 3 && MD == 12);
+            // RETIRE: a level that starts with two live slots, the lower of which (slot NS - 2) holds ONE live column per problem — the column at
+            // position Fc, in lane 15; every other lane of the slot holds a finished pivot — drops that slot after its first pivot step.  The
+            // columns of a level do not move, only pos[] swaps, so that one physical column would keep the whole slot in every pivot step until it
+            // wins.  Behind step 0 the winner's register place is finished (what the level end stores of it is written then and there); the lone
+            // column moves into that place through LDS with its norm, position and physical column (lane 15 writes, the winner's lane reads), and
+            // the steps 1 .. MD-1 and the level end run on the upper slot alone.  No operand and no order of operations changes and positions are
+            // unique in the decision key, so pivots, ranks and x are bit for bit those of the unretired level.  Taken only when all four problems
+            // of the wavefront work and start the level at the same such column (hh-select); anything else takes factor_level<S0> as before.
+            // Off (same code as without it) for the estimating and ragged forms, for an n known at run time only (the staging block has the
+            // room for the move's 8 MD + 16 bytes behind the hand-off slots when (n + 1) RP doubles say so) and for shapes whose full-rank levels
+            // never start at such a column (qt_retire_reachable).
+            constexpr int kRetireSlot = NS - 2;
+            constexpr bool RETIRE     = !EST && !RAG && PEEL && NV > 0 && qt_retire_reachable(NS, MD, SIG, NV) && 8 * (NV + 1) * RP >= 17 * kHandoffStride;
             struct qt_level // what the phases of one level hand to each other (per row, uniform inside a row; prefetch: wave-uniform)
             {
                 bool work;     // x only: once the columns are exhausted nothing below matters
@@ -403,15 +416,20 @@
                 // below (beside the butterflies), then every lane stores the column of its local best slot in its own LDS slot — the store
                 // does not wait for the decision, only the next step's read address does.
                 // =====================================================================================
-                auto factor_level = [&](auto l0c, auto s0c, qt_level &L, double (&blk)[NS][MD]) __attribute__((always_inline)) {
+                // retc (RETIRE): slot S0 is dropped behind pivot step 0 — steps 1 .. MD-1 run on the slots S0 + 1 .. NS-1 (k: the level, for the
+                // winner's index byte)
+                auto factor_level = [&](auto l0c, auto s0c, auto retc, const int k, qt_level &L, double (&blk)[NS][MD]) __attribute__((always_inline)) {
                     constexpr bool L0 = decltype(l0c)::value;
                     constexpr int S0 = decltype(s0c)::value;
+                    constexpr bool RET = decltype(retc)::value;
                     constexpr int SL = NS - S0; // live slots
                     static_assert(!L0 || S0 == 0, "level 0 starts at column 0: every slot is live");
+                    static_assert(!RET || (RETIRE && !L0 && S0 == kRetireSlot && SL == 2), "the retiring form: two live slots, one behind step 0");
+                    (void)k;
                     const bool work = L.work, prefetch = L.prefetch;
                     const int F = L.F, dlev = L.dlev;
                     int &rank = L.rank;
-                    QT_LMARK1("hh-pro", S0)
+                    if constexpr (RET) { QT_MARK1("hh-ret-pro", S0) } else { QT_LMARK1("hh-pro", S0) }
                     double nrm[NS];
 #pragma unroll
                     for (int s = S0; s < NS; s++)
@@ -435,13 +453,14 @@
                     bool cur_ispl = false, nxt_ispl = false; // this lane holds the pivot column
                     unsigned cur_w = 0, nxt_w = 0;      // the winner's 12-bit key (position << 6 | slot << 4 | lane)
                     double pbest = 0.0;                 // the lane's local best, packed
-                    auto decide_local = [&]() __attribute__((always_inline)) {
+                    auto decide_local = [&](auto loc) __attribute__((always_inline)) { // loc: the lowest live slot
+                        constexpr int LO = decltype(loc)::value;
 #pragma unroll
-                        for (int s = S0; s < NS; s++)
+                        for (int s = LO; s < NS; s++)
                         {
                             const int kinv  = (0xFFF - ((s << 4) | gl)) - (pos[s] << 6);
                             const double pv = __hiloint2double(__double2hiint(nrm[s]), (__double2loint(nrm[s]) & ~0xFFF) | kinv);
-                            pbest           = s == S0 ? pv : vmax(pbest, pv);
+                            pbest           = s == LO ? pv : vmax(pbest, pv);
                         }
                         nxt_lbs = ((0xFFF - (__double2loint(pbest) & 0xFFF)) >> 4) & 3;
                     };
@@ -452,7 +471,7 @@
                     };
                     // prologue: decision for pivot 0, every lane's best column to its hand-off slot
                     {
-                        decide_local();
+                        decide_local(std::integral_constant<int, S0>{});
                         decide_finish(row_max16(pbest));
                         double colv[MD];
 #pragma unroll
@@ -492,7 +511,13 @@
                         constexpr int j   = decltype(cnt)::value;
                         constexpr int ce  = j & ~1;       // first (even) row of this step's hand-off
                         constexpr int cen = (j + 1) & ~1; // ... of the next step's
-                        QT_LMARK2("hh-step", S0, j)
+                        constexpr int SJ  = (RET && j >= 1) ? S0 + 1 : S0; // lowest live slot of this step
+                        constexpr int SLJ = NS - SJ;
+                        if constexpr (RET) { QT_MARK2("hh-ret-step", S0, j) } else { QT_LMARK2("hh-step", S0, j) }
+                        // (RET) the pivot of step 0, for the move behind it
+                        const unsigned w0 = cur_w;
+                        const bool ispl0  = cur_ispl;
+                        (void)w0, (void)ispl0;
                         // the next level's pieces: PF_PER per pivot step from the first step on (what an early end leaves over is requested behind the loop)
                         {
                             constexpr int TOT = NH * NIH, PF_PER = (TOT + PF_STEPS - 1) / PF_STEPS;
@@ -548,7 +573,7 @@
                         // raw dot products col . a of every live column (beside the chain above)
                         double dw[NS];
 #pragma unroll
-                        for (int s = S0; s < NS; s++)
+                        for (int s = SJ; s < NS; s++)
                         {
                             double d0 = 0.0, d1 = 0.0;
 #pragma unroll
@@ -567,7 +592,7 @@
                         // gs = (R_js - a_s[j]) / (c0 - beta)   (= a_s - tau v v.a_s, lexlse.h:243-246)
                         double gs[NS];
 #pragma unroll
-                        for (int s = S0; s < NS; s++)
+                        for (int s = SJ; s < NS; s++)
                         {
                             const double t = dw[s] * ibet;
                             gs[s]          = (t - blk[s][j]) * rden;
@@ -579,7 +604,7 @@
                         // column "swap": update the position map (lexlse.h:222-232)
                         const int ppos = (int)(cur_w >> 6);
 #pragma unroll
-                        for (int s = S0; s < NS; s++)
+                        for (int s = SJ; s < NS; s++)
                         {
                             const bool front = cont && pos[s] == ColIndex;
                             pos[s]           = sel(front, ppos, pos[s]);
@@ -589,9 +614,9 @@
                         if constexpr (EST)
                         {
                             // the pivot's lane: its raw squared norm times h^2 = 1 / (4 fresh)
-                            double r2 = rsq[S0];
+                            double r2 = rsq[SJ];
 #pragma unroll
-                            for (int s = S0 + 1; s < NS; s++) r2 = sel(cur_lbs == s, rsq[s], r2);
+                            for (int s = SJ + 1; s < NS; s++) r2 = sel(cur_lbs == s, rsq[s], r2);
                             est2 = sel(cont && cur_ispl, vmax(est2, r2 * (h * h)), est2);
                         }
                         ColIndex += cont ? 1 : 0;
@@ -600,16 +625,16 @@
                         exh             = exh || full;
                         go              = go && !full;
                         FSTAMP(4)
-                        if constexpr (j + 1 < MD && SL == 1)
+                        if constexpr (j + 1 < MD && SLJ == 1)
                         {
                             // one live slot: the lane's best column IS the slot — update it (in the stalls of the butterfly), store it
-                            decide_local();
+                            decide_local(std::integral_constant<int, SJ>{});
                             double m = pbest;
                             auto upd_rows = [&](auto qq) __attribute__((always_inline)) {
                                 constexpr int q = decltype(qq)::value;
 #pragma unroll
                                 for (int r = j + 1; r < MD; r++)
-                                    if ((r - j - 1) % 4 == q) blk[S0][r] = dfma(gs[S0], col[r], blk[S0][r]);
+                                    if ((r - j - 1) % 4 == q) blk[SJ][r] = dfma(gs[SJ], col[r], blk[SJ][r]);
                             };
                             m = dpp_max<0xB1>(m);
                             upd_rows(std::integral_constant<int, 0>{});
@@ -620,7 +645,7 @@
                             m = dpp_max<0x140>(m);
                             upd_rows(std::integral_constant<int, 3>{});
 #pragma unroll
-                            for (int r = cen; r < MD; r += 2) D2(o_stage + gl * kHandoffStride + 8 * r) = qt_d2{blk[S0][r], blk[S0][r + 1]};
+                            for (int r = cen; r < MD; r += 2) D2(o_stage + gl * kHandoffStride + 8 * r) = qt_d2{blk[SJ][r], blk[SJ][r + 1]};
                             decide_finish(m);
                             fetch_column(std::integral_constant<int, j + 1>{}, nxt_w);
                         }
@@ -629,9 +654,9 @@
                             // The decision for the next pivot: local part, then the four butterfly stages.  In the stalls of the stages: the lane's
                             // best column (for the next hand-off) is picked out of the slots BEFORE the rank-one update, updated on its own and
                             // stored — the store does not wait for the decision, only the next step's read address does
-                            decide_local();
+                            decide_local(std::integral_constant<int, SJ>{});
                             double colv[MD];
-                            double gsb = gs[S0];
+                            double gsb = gs[SJ];
                             double m   = pbest;
                             auto pick_rows = [&](auto qq) __attribute__((always_inline)) {
                                 constexpr int q = decltype(qq)::value;
@@ -639,9 +664,9 @@
                                 for (int r = cen; r < MD; r++)
                                     if ((r - cen) % 4 == q)
                                     {
-                                        colv[r] = blk[S0][r];
+                                        colv[r] = blk[SJ][r];
 #pragma unroll
-                                        for (int s = S0 + 1; s < NS; s++) colv[r] = sel(nxt_lbs == s, blk[s][r], colv[r]);
+                                        for (int s = SJ + 1; s < NS; s++) colv[r] = sel(nxt_lbs == s, blk[s][r], colv[r]);
                                     }
                             };
                             m = dpp_max<0xB1>(m);
@@ -653,7 +678,7 @@
                             m = dpp_max<0x140>(m);
                             pick_rows(std::integral_constant<int, 3>{});
 #pragma unroll
-                            for (int s = S0 + 1; s < NS; s++) gsb = sel(nxt_lbs == s, gs[s], gsb);
+                            for (int s = SJ + 1; s < NS; s++) gsb = sel(nxt_lbs == s, gs[s], gsb);
 #pragma unroll
                             for (int r = (cen > j + 1 ? cen : j + 1); r < MD; r++) colv[r] = dfma(gsb, col[r], colv[r]);
 #pragma unroll
@@ -663,20 +688,81 @@
                         }
                         CSTAMP(5, (int)nxt_w)
                         // rows below of every live column
-                        if constexpr (!(j + 1 < MD && SL == 1))
+                        if constexpr (!(j + 1 < MD && SLJ == 1))
                         {
 #pragma unroll
-                            for (int s = S0; s < NS; s++)
+                            for (int s = SJ; s < NS; s++)
                             {
 #pragma unroll
                                 for (int r = j + 1; r < MD; r++) blk[s][r] = dfma(gs[s], col[r], blk[s][r]);
                             }
                         }
                         cur_lbs = nxt_lbs, cur_ispl = nxt_ispl, cur_w = nxt_w;
+                        if constexpr (RET && j == 0)
+                        {
+                            // Slot S0 retires (see RETIRE).  Per problem, where step 0 made a pivot (cont; a problem that stopped keeps its
+                            // registers as they are: nothing of its block is read again, and the level end stores its maps as before):
+                            QT_MARK1("hh-retire", S0)
+                            const int x0  = (int)(w0 & 15u);        // the pivot's lane and slot (uniform inside the problem)
+                            const int ws0 = (int)((w0 >> 4) & 3u);
+                            // (a) the pivot's place is finished: what the level end stores of it — row 0 of the image at the level's index 0, its
+                            //     index byte, its physical column at position Fc — is stored now, by its lane
+                            {
+                                double w00 = blk[S0][0];
+                                int wpc    = pc[S0];
+#pragma unroll
+                                for (int s = S0 + 1; s < NS; s++)
+                                {
+                                    w00 = sel(ws0 == s, blk[s][0], w00);
+                                    wpc = sel(ws0 == s, pc[s], wpc);
+                                }
+                                if (cont && ispl0)
+                                {
+                                    D(o_img + 8 * imgoff)     = w00;
+                                    B8(o_emap + 8 * wpc + k)  = (uint8_t)0;
+                                    B8(o_phys + L.Fc)         = (uint8_t)wpc;
+                                }
+                            }
+                            // (b) the pivot sits in an upper slot: the lone column (slot S0, lane 15) moves into its place — block, norm, position,
+                            //     physical column — through the 8 MD + 16 bytes behind the sixteen hand-off slots
+                            const int o_mv  = o_stage + 16 * kHandoffStride;
+                            const bool mrow = cont && ws0 != S0;
+                            if (mrow && gl == 15)
+                            {
+#pragma unroll
+                                for (int r = 0; r < MD; r += 2) D2(o_mv + 8 * r) = qt_d2{blk[S0][r], blk[S0][r + 1]};
+                                D2(o_mv + 8 * MD) = qt_d2{nrm[S0], __hiloint2double(pc[S0], pos[S0])};
+                            }
+                            quad_lds_fence();
+                            double mc[MD];
+#pragma unroll
+                            for (int r = 0; r < MD; r += 2)
+                            {
+                                const qt_d2 v = D2(o_mv + 8 * r);
+                                mc[r]         = v.x;
+                                mc[r + 1]     = v.y;
+                            }
+                            const qt_d2 mt  = D2(o_mv + 8 * MD);
+                            const bool recv = mrow && gl == x0;
+#pragma unroll
+                            for (int s = S0 + 1; s < NS; s++)
+                            {
+                                const bool hit = SL == 2 ? recv : (recv && ws0 == s);
+#pragma unroll
+                                for (int r = 0; r < MD; r++) blk[s][r] = sel(hit, mc[r], blk[s][r]);
+                                nrm[s] = sel(hit, mt.x, nrm[s]);
+                                pos[s] = sel(hit, __double2loint(mt.y), pos[s]);
+                                pc[s]  = sel(hit, __double2hiint(mt.y), pc[s]);
+                            }
+                            // the decision for step 1 was made on the old places: where it chose the lone column, the pivot is now in lane x0
+                            const bool lone1 = mrow && (int)((cur_w >> 4) & 3u) == S0;
+                            cur_ispl         = lone1 ? gl == x0 : cur_ispl;
+                            cur_lbs          = lone1 ? ws0 : cur_lbs;
+                        }
                         CSTAMP(6, __double2loint(blk[NS - 1][MD - 1]))
                         FSTAMP(5)
                     });
-                    QT_LMARK1("hh-end", S0)
+                    if constexpr (RET) { QT_MARK1("hh-ret-end", S0) } else { QT_LMARK1("hh-end", S0) }
                     if (prefetch)
                         for_each_index<0, NH * NIH>([&](auto tt) __attribute__((always_inline)) {
                             if (decltype(tt)::value >= pf_issued) prefetch_piece(tt, F + dlev);
@@ -687,8 +773,12 @@
             // =====================================================================================
             // level end: triangular image [R_k T_k | rhs_k] / diag in end-of-level position order, maps
             // =====================================================================================
-            auto level_end = [&](auto l0c, const int k, const qt_level &L, double (&blk)[NS][MD]) __attribute__((always_inline)) {
+            // retired (RETIRE, wave-uniform): the level dropped slot kRetireSlot behind its first pivot step.  That slot's registers are stale where
+            // the level made a pivot — its one live column was stored from the pivot's place or moved to it — and its store pass is skipped
+            // there; a problem of rank 0 made no move and stores the slot's maps as ever
+            auto level_end = [&](auto l0c, const int k, const qt_level &L, double (&blk)[NS][MD], const bool retired) __attribute__((always_inline)) {
                 constexpr bool L0 = decltype(l0c)::value;
+                (void)retired;
                 const bool work = L.work;
                 const int Fc = L.Fc, rank = L.rank;
                 STAMP(5)
@@ -703,7 +793,11 @@
                 for (int s = 0; s < NS; s++)
                 {
                     const int P0  = 16 * s + gl - SIG;
-                    const bool mv = work && P0 <= n && P0 >= Fc; // columns that were live in this level (the RHS included)
+                    bool mv       = work && P0 <= n && P0 >= Fc; // columns that were live in this level (the RHS included)
+                    if constexpr (RETIRE && !L0)
+                    {
+                        if (s == kRetireSlot) mv = mv && !(retired && rank > 0);
+                    }
                     const int e   = pos[s] - Fc;                 // index of this column in the level's image: end-of-level position order
                     const int lim = mv ? (e < rank - 1 ? e : rank - 1) : -1; // rows 0 .. lim of the column go to the image (p < rank, p <= e)
                     const int base = o_img + 8 * (imgoff + e);
@@ -760,8 +854,8 @@
                         STAMP(7)
                         LSTAMP(1)
                     }
-                    factor_level(std::true_type{}, std::integral_constant<int, 0>{}, L, blk0);
-                    level_end(std::true_type{}, 0, L, blk0);
+                    factor_level(std::true_type{}, std::integral_constant<int, 0>{}, std::false_type{}, 0, L, blk0);
+                    level_end(std::true_type{}, 0, L, blk0, false);
                 }
             }
             // LDS order across the boundary, as between any two levels: the fence that ends level_end (behind the meta store) stands between
@@ -783,19 +877,27 @@
                 level_post(std::false_type{}, k, L, blk);
                 eliminate(k, L, blk);
                 QT_MARK("hh-select")
+                bool retired = false; // (wave-uniform)
                 {
                     // (a rank-deficient level 0 leaves level 1 at column < 16 - SIG: all four choices stay)
-                    const int s0 = (rows_min(L.work ? L.Fc : 0x3fffffff) + SIG) >> 4;
-                    if (NS > 3 && s0 >= 3)
-                        factor_level(std::false_type{}, std::integral_constant<int, (NS > 3 ? 3 : 0)>{}, L, blk);
+                    const int fcmin = rows_min(L.work ? L.Fc : 0x3fffffff);
+                    const int s0    = (fcmin + SIG) >> 4;
+                    // (RETIRE) all four problems work and start the level at the same column, whose place is lane 15 of slot NS - 2: that slot
+                    // holds one live column per problem (the right-hand side sits in the top slot)
+                    if constexpr (RETIRE)
+                        retired = __ballot(!L.work) == 0ull && rows_max(L.Fc) == fcmin && s0 == kRetireSlot && ((fcmin + SIG) & 15) == 15;
+                    if (RETIRE && retired)
+                        factor_level(std::false_type{}, std::integral_constant<int, (RETIRE ? kRetireSlot : 0)>{}, std::integral_constant<bool, RETIRE>{}, k, L, blk);
+                    else if (NS > 3 && s0 >= 3)
+                        factor_level(std::false_type{}, std::integral_constant<int, (NS > 3 ? 3 : 0)>{}, std::false_type{}, k, L, blk);
                     else if (NS > 2 && s0 >= 2)
-                        factor_level(std::false_type{}, std::integral_constant<int, (NS > 2 ? 2 : 0)>{}, L, blk);
+                        factor_level(std::false_type{}, std::integral_constant<int, (NS > 2 ? 2 : 0)>{}, std::false_type{}, k, L, blk);
                     else if (NS > 1 && s0 >= 1)
-                        factor_level(std::false_type{}, std::integral_constant<int, (NS > 1 ? 1 : 0)>{}, L, blk);
+                        factor_level(std::false_type{}, std::integral_constant<int, (NS > 1 ? 1 : 0)>{}, std::false_type{}, k, L, blk);
                     else
-                        factor_level(std::false_type{}, std::integral_constant<int, 0>{}, L, blk);
+                        factor_level(std::false_type{}, std::integral_constant<int, 0>{}, std::false_type{}, k, L, blk);
                 }
-                level_end(std::false_type{}, k, L, blk);
+                level_end(std::false_type{}, k, L, blk, retired);
             }
 
             // ---- solve(): block back-substitution on the normalised images (lexlse.h:1015-1045); lane p <-> row p of a level.  Straight-line

@@ -219,6 +219,19 @@ namespace lexls
 
         constexpr int kQtSentinelHi = (int)0xFFE00000; // -2^1023 * 1.x: below every down-dated norm, finite whatever the low word
 
+        /// Slot retirement (lqr_qtol_body.inc, RETIRE): true when some level of a batch of full-rank levels of MD rows starts at a column Fc whose
+        /// place is the LAST lane of slot NS - 2 — the level then starts with two live slots, the lower one holding one live column per problem.
+        /// Instantiations for which no such level exists do not carry the path.
+        constexpr bool qt_retire_reachable(int NS, int MD, int SIG, int NV)
+        {
+            for (int k = 1; k < kQuadMaxObj; k++)
+            {
+                const int fc = k * MD;
+                if (fc < NV && ((fc + SIG) & 15) == 15 && ((fc + SIG) >> 4) == NS - 2) return true;
+            }
+            return false;
+        }
+
         /// NV: the number of variables when the instantiation serves ONE n (0: taken from the arguments) — the piece counts of the level loads and
         /// the layout tests then fold at compile time.
         /// EST: the accuracy guard's instantiation (lexls_lse_set_accuracy_guard).  Per problem it writes est_out[b] = the maximum over its

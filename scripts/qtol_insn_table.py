@@ -48,6 +48,9 @@ RANKS = [12, 12, 12, 4, 0]
 FC = [sum(RANKS[:k]) for k in range(len(RANKS))]          # first column of every level: 0, 12, 24, 36, 40
 WORKED = [k for k in range(len(RANKS)) if FC[k] < N]      # levels that start (x only: once the columns are exhausted nothing is done)
 S0 = [min((FC[k] + SIG) // 16, NS - 1) for k in WORKED]   # first live slot = the factor_level instantiation of the level
+# levels that retire their low slot behind the first pivot step (the body's RETIRE): two live slots, the level's first column in lane 15 of the
+# lower one.  They run the "hh-ret-*" parts (the retiring form of factor_level<S0>) instead of "hh-*"
+RET = [k != 0 and S0[WORKED.index(k)] == NS - 2 and (FC[k] + SIG) % 16 == 15 for k in WORKED]
 ACC = [N - (FC[k] + RANKS[k]) if RANKS[k] else 0 for k in range(len(RANKS))]  # solved positions behind a level's pivots (back-substitution)
 
 
@@ -74,6 +77,12 @@ def trips(name, idx):
         return sum(1 for k in levels if 16 * idx[0] + 15 - SIG >= FC[k])
     if name == "elim":
         return sum(1 for k in levels if idx[0] < FC[k])
+    ret = name.startswith("hh-ret")  # the retiring form's parts; "hh-retire": the move behind its step 0 (run with that step)
+    if ret:
+        name = {"hh-ret-pro": "hh-pro", "hh-ret-end": "hh-end", "hh-ret-step": "hh-step", "hh-retire": "hh-step"}[name]
+        if len(idx) == 1 and name == "hh-step":
+            idx = (idx[0], 0)
+    levels = [k for k in levels if RET[WORKED.index(k)] == ret] if name.startswith("hh-") else levels
     if name in ("hh-pro", "hh-end"):
         return sum(1 for k in levels if S0[WORKED.index(k)] == idx[0])
     if name == "hh-step":  # a level leaves at the first test (every fourth step) behind its last pivot
@@ -91,6 +100,8 @@ def group(name, idx):
     if name == "elim":
         sc = (idx[0] + SIG) // 16
         return f"elimination, {NS - sc} slot step"
+    if name.startswith("hh-ret"):
+        return f"Householder, factor_level<{idx[0]}> retiring slot {idx[0]} behind step 0"
     if name.startswith("hh-"):
         return f"Householder, factor_level<{idx[0]}>" if name != "hh-select" else "Householder, choice of the instantiation"
     if name.startswith("level-st"):
@@ -159,7 +170,7 @@ def main():
         r = rows.setdefault(g, collections.Counter())
         for k, v in c.items():
             r[k] += n * v
-        if name in ("elim", "hh-step", L0_PREFIX + "hh-step"):
+        if name in ("elim", "hh-step", "hh-ret-step", L0_PREFIX + "hh-step"):
             steps[g] += n
     total = collections.Counter()
     for r in rows.values():
