@@ -259,6 +259,44 @@ int lexls_lse_solve_adjoint_multi(lexls_lse_t h, const double *h_G, uint32_t nco
 int lexls_lse_get_adjoint_multi(lexls_lse_t h, double *h_grad_rhs, double *h_grad_fixed);
 int lexls_lse_solve_adjoint_multi_device(lexls_lse_t h, const double *d_G, uint32_t ncot, double *d_grad_rhs, double *d_grad_fixed);
 
+/* Gradient of the solve with respect to the MATRIX A (and, with it, the right-hand sides): the derivative the calls above do not give.  x is
+ * not continuous in A where a rank changes, so the derivative exists for RANK-STABLE problems only, and the call says per problem whether it
+ * returned one.
+ * Rank-stability rule, as the kernel evaluates it: a problem with every variable fixed is rank-stable; any other problem is rank-stable when
+ * rank_k == min(dim_k, nVar - Fc_k) for every level k, with Fc_k the first column of level k (fixed variables included) and
+ * min(dim_k, nVar - Fc_k) = 0 where Fc_k >= nVar — every level took all the rank it could; a level that finds the columns used up has rank 0
+ * and passes.  Small perturbations of A move neither the ranks nor the pivots of such a problem.  For any other problem a generic perturbation
+ * raises a rank and no derivative exists.
+ * Formula: for a rank-stable problem the levels above k*, the last level of non-zero rank, act as equalities C x = d, level k* is a
+ * least-squares objective min |E x - f|, the later levels do not touch x, free and fixed variables are further equalities.  With g = dloss/dx,
+ * for every level k in the user's row and column order
+ *     dloss/dA_k = - y_k x^T - lambda_k u^T,      dloss/db = y
+ * x = the solution (lexls_lse_get_x order, fixed variables included); y = M^T g, the grad_rhs of lexls_lse_solve_adjoint; lambda = the
+ * multipliers of level k* (its own rows hold its residual r = A_k* x - b_k*, the rows of the levels above hold nu with A_k*^T r + sum_j A_j^T
+ * nu_j = 0 on the pivot variables, the rows below are zero: column k* of lexls_lse_multipliers); u = M y~ with y~ = y on the rows of level k*
+ * and zero elsewhere, fixed values zero (u is zero on fixed and free variables).
+ * Layouts: g is batch x nVar in the order of lexls_lse_get_x.  grad_lod is batch x (nVar + 1) x cap doubles, the layout of
+ * lexls_lse_set_problem_host: entry (row i, column j) of problem b at b * (nVar + 1) * cap + j * cap + i; column j < nVar is the gradient of
+ * column j of A, column nVar is y, the gradient of the right-hand side; rows behind the problem's own are zero.  differentiable is one byte
+ * per problem: 1 = rank-stable, 0 = not — and where the flag is 0 the whole of that problem's grad_lod is exact zeros (the convention of
+ * lexls_lsi_batch_solve_adjoint for instances that did not end PROBLEM_SOLVED).
+ * The call needs the x of the current factor: lexls_lse_factorize_solve(keep_factor = 1), or lexls_lse_factorize + lexls_lse_solve.
+ * lexls_lse_solve_adjoint_matrix copies h_g in, launches and keeps the results in buffers of the handle (allocated at the first call);
+ * lexls_lse_get_adjoint_matrix copies them out, either output may be NULL; both follow lexls_lse_set_deferred_sync, and
+ * lexls_lse_get_adjoint_matrix answers only while the results belong to the current factor, as lexls_lse_get_adjoint does.
+ * lexls_lse_solve_adjoint_matrix_device reads d_g and writes d_grad_lod and d_differentiable (NULL: not wanted; d_grad_lod may not be NULL) in
+ * device memory: it only enqueues in the handle's stream and makes no host-synchronising call (its work buffers are allocated at the first
+ * call).  What lexls_lse_get_multipliers, lexls_lse_get_v, lexls_lse_get_lambda and lexls_lse_get_sensitivity answer is not changed by these
+ * calls.
+ * Tolerance contract (no reference arithmetic exists); no atomics, the same bits from run to run and from the host and the device form.
+ * Errors, each returned before any device work and with every output left alone: LEXLS_ERR_INVALID for a null handle, a null g or a null
+ * d_grad_lod; LEXLS_ERR_INVALID when there is no kept factor; LEXLS_ERR_INVALID when no x belongs to the current factor (lexls_lse_factorize
+ * alone, or a least-norm solve); LEXLS_ERR_UNSUPPORTED when the factorization ran with regularization_type != 0.
+ * Kernel variant: "solve_adjoint_matrix<64>" (lexls_lse_last_consumer_kernel). */
+int lexls_lse_solve_adjoint_matrix(lexls_lse_t h, const double *h_g);
+int lexls_lse_get_adjoint_matrix(lexls_lse_t h, double *h_grad_lod, uint8_t *h_differentiable);
+int lexls_lse_solve_adjoint_matrix_device(lexls_lse_t h, const double *d_g, double *d_grad_lod, uint8_t *d_differentiable);
+
 /* ---- results (synchronise the stream, then D2H) ------------------------------------------------- */
 int lexls_lse_get_x(lexls_lse_t h, double *h_x);                    /* get_x()      lexlse.h:1587 */
 int lexls_lse_get_factor(lexls_lse_t h, double *h_lod);             /* get_lexqr()  lexlse.h:1626 */

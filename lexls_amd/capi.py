@@ -30,6 +30,7 @@ SYMBOLS = [
     "lexls_lsi_solve", "lexls_lsi_solve_dat", "lexls_lsi_batch_solve",
     "lexls_lse_multipliers", "lexls_lse_get_multipliers", "lexls_lse_solve_adjoint", "lexls_lse_get_adjoint", "lexls_lse_solve_adjoint_device",
     "lexls_lse_solve_adjoint_multi", "lexls_lse_get_adjoint_multi", "lexls_lse_solve_adjoint_multi_device",
+    "lexls_lse_solve_adjoint_matrix", "lexls_lse_get_adjoint_matrix", "lexls_lse_solve_adjoint_matrix_device",
     "lexls_lsi_batch_get_lambda", "lexls_lsi_batch_solve_ex2",
     "lexls_lse_sensitivity_collect", "lexls_lse_sensitivity_collect_resident", "lexls_lse_get_wrong_sign",
     "lexls_lsi_batch_get_cycling_counters", "lexls_lsi_batch_run_device", "lexls_lsi_batch_run_device_ex",
@@ -129,6 +130,14 @@ def lib() -> C.CDLL:
         _lib.lexls_lse_get_adjoint_multi.argtypes = [C.c_void_p, C.POINTER(C.c_double), C.POINTER(C.c_double)]
         _lib.lexls_lse_solve_adjoint_multi_device.restype = C.c_int
         _lib.lexls_lse_solve_adjoint_multi_device.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p]  # d_G, ncot, d_grad_rhs, d_grad_fixed
+        _lib.lexls_lse_solve_adjoint_matrix.restype = C.c_int
+        _lib.lexls_lse_solve_adjoint_matrix.argtypes = [C.c_void_p, C.POINTER(C.c_double)]
+        _lib.lexls_lse_get_adjoint_matrix.restype = C.c_int
+        _lib.lexls_lse_get_adjoint_matrix.argtypes = [C.c_void_p, C.POINTER(C.c_double), C.POINTER(C.c_uint8)]
+        _lib.lexls_lse_solve_adjoint_matrix_device.restype = C.c_int
+        _lib.lexls_lse_solve_adjoint_matrix_device.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]  # d_g, d_grad_lod, d_differentiable
+        _lib.lexls_internal_apply_solve_map.restype = C.c_int
+        _lib.lexls_internal_apply_solve_map.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]  # d_rhs, d_out: device addresses
         _lib.lexls_lsi_batch_solve_adjoint_multi.restype = C.c_int
         _lib.lexls_lsi_batch_solve_adjoint_multi.argtypes = [C.c_void_p, C.POINTER(C.c_double), C.c_uint32, C.POINTER(C.c_double), C.POINTER(C.c_double)]
         _lib.lexls_lsi_batch_solve_adjoint_multi_device.restype = C.c_int

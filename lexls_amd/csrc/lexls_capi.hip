@@ -101,6 +101,13 @@ struct lexls_lse_s
     uint32_t adjm_room = 0, adjm_ncot = 0; // cotangents the three buffers have room for; cotangents of the last lexls_lse_solve_adjoint_multi
     bool adjm_valid     = false;
     uint64_t adjm_epoch = 0;
+    // lexls_lse_solve_adjoint_matrix: g (batch x nVar), the gradient (batch x (nVar + 1) x cap) and the flags (batch) of a host caller, the work
+    // buffers of the chain (launch_solve_adjoint_matrix), all made at the first call that needs them
+    double *d_adjA_g = nullptr, *d_adjA_grad = nullptr;
+    uint8_t *d_adjA_flag = nullptr;
+    void *d_adjA_work    = nullptr;
+    bool adjA_valid      = false;
+    uint64_t adjA_epoch  = 0;
     // accuracy guard (lexls_lse_set_accuracy_guard): mode 0 off, 1 report, 2 report + re-solve; arrays allocated when first switched on
     int guard_mode           = 0;
     double guard_threshold   = 0.0;
@@ -296,7 +303,7 @@ extern "C"
         void *ptrs[] = {h->d_in_owned, h->d_fac, h->d_hh, h->d_v, h->d_lambda, h->d_scratch, h->d_perm, h->d_rank, h->d_fcol, h->d_round_in, h->d_round_out,
                         h->d_large_state, h->d_large_ws, h->d_norms, h->d_cdata, h->d_reg_factor, h->d_reg_scratch, h->d_reg_mu, h->d_resume_level, h->d_resume_state,
                         h->d_guard_est, h->d_guard_status, h->d_guard_ind, h->d_mult, h->d_mult_scratch, h->d_wrong_sign, h->d_adj_g, h->d_adj_rhs, h->d_adj_fixed,
-                        h->d_adjm_G, h->d_adjm_rhs, h->d_adjm_fixed, h->d_adjm_work};
+                        h->d_adjm_G, h->d_adjm_rhs, h->d_adjm_fixed, h->d_adjm_work, h->d_adjA_g, h->d_adjA_grad, h->d_adjA_flag, h->d_adjA_work};
         for (void *p : ptrs)
             if (p) (void)hipFree(p);
         if (h->h_dims_pinned) (void)hipHostFree(h->h_dims_pinned);
@@ -1140,6 +1147,69 @@ extern "C"
         if (h_grad_rhs) HIP_TRY(hipMemcpyAsync(h_grad_rhs, h->d_adjm_rhs, 8 * rows * h->cap, hipMemcpyDeviceToHost, h->stream));
         if (h_grad_fixed) HIP_TRY(hipMemcpyAsync(h_grad_fixed, h->d_adjm_fixed, 8 * rows * h->nVar, hipMemcpyDeviceToHost, h->stream));
         if (!h->deferred_sync) HIP_TRY(hipStreamSynchronize(h->stream));
+        return LEXLS_OK;
+    }
+
+    /// what both forms of the matrix gradient check before any device work: a kept, unregularized factor and the x that belongs to it
+    static int need_adjoint_matrix(lexls_lse_t h, const char *who, const void *g)
+    {
+        if (int rc = need_adjoint_factor(h, who, g)) return rc;
+        if (h->x_epoch != h->factor_epoch)
+            return fail(LEXLS_ERR_INVALID, std::string(who) + ": no x belongs to the current factor (lexls_lse_factorize_solve(keep_factor = 1), or lexls_lse_factorize + lexls_lse_solve)");
+        return LEXLS_OK;
+    }
+    static int adjoint_matrix_work(lexls_lse_t h)
+    {
+        if (!h->d_adjA_work) HIP_TRY(hipMalloc(&h->d_adjA_work, adjoint_matrix_work_bytes(h->args())));
+        return LEXLS_OK;
+    }
+
+    int lexls_lse_solve_adjoint_matrix(lexls_lse_t h, const double *h_g)
+    {
+        if (int rc = need_adjoint_matrix(h, "lexls_lse_solve_adjoint_matrix", h_g)) return rc;
+        HIP_TRY(hipSetDevice(h->device));
+        const size_t B = h->batch, n = h->nVar, cap = h->cap;
+        if (!h->d_adjA_g) HIP_TRY(hipMalloc((void **)&h->d_adjA_g, 8 * B * n));
+        if (!h->d_adjA_grad) HIP_TRY(hipMalloc((void **)&h->d_adjA_grad, 8 * B * (n + 1) * cap));
+        if (!h->d_adjA_flag) HIP_TRY(hipMalloc((void **)&h->d_adjA_flag, B));
+        if (int rc = adjoint_matrix_work(h)) return rc;
+        HIP_TRY(hipMemcpyAsync(h->d_adjA_g, h_g, 8 * B * n, hipMemcpyHostToDevice, h->stream));
+        if (!h->deferred_sync) HIP_TRY(hipStreamSynchronize(h->stream)); // h_g may be reused by the caller
+        HIP_TRY(launch_solve_adjoint_matrix(h->args(), h->d_adjA_g, h->d_adjA_grad, h->d_adjA_flag, h->d_adjA_work, h->max_level_dim, h->stream, &h->last_consumer));
+        h->adjA_valid = true;
+        h->adjA_epoch = h->factor_epoch;
+        return LEXLS_OK;
+    }
+
+    int lexls_lse_solve_adjoint_matrix_device(lexls_lse_t h, const double *d_g, double *d_grad_lod, uint8_t *d_differentiable)
+    {
+        if (int rc = need_adjoint_matrix(h, "lexls_lse_solve_adjoint_matrix_device", d_g)) return rc;
+        if (!d_grad_lod) return fail(LEXLS_ERR_INVALID, "lexls_lse_solve_adjoint_matrix_device: null d_grad_lod");
+        HIP_TRY(hipSetDevice(h->device));
+        if (int rc = adjoint_matrix_work(h)) return rc;
+        HIP_TRY(launch_solve_adjoint_matrix(h->args(), d_g, d_grad_lod, d_differentiable, h->d_adjA_work, h->max_level_dim, h->stream, &h->last_consumer));
+        return LEXLS_OK;
+    }
+
+    int lexls_lse_get_adjoint_matrix(lexls_lse_t h, double *h_grad_lod, uint8_t *h_differentiable)
+    {
+        CHECK_HANDLE(h);
+        if (!h->adjA_valid) return fail(LEXLS_ERR_INVALID, "lexls_lse_get_adjoint_matrix: call lexls_lse_solve_adjoint_matrix first");
+        if (!h->factor_valid || h->adjA_epoch != h->factor_epoch)
+            return fail(LEXLS_ERR_INVALID, "lexls_lse_get_adjoint_matrix: the problem or its factorization changed since lexls_lse_solve_adjoint_matrix (call it again)");
+        HIP_TRY(hipSetDevice(h->device));
+        if (h_grad_lod) HIP_TRY(hipMemcpyAsync(h_grad_lod, h->d_adjA_grad, 8 * (size_t)h->batch * h->problem_elems(), hipMemcpyDeviceToHost, h->stream));
+        if (h_differentiable) HIP_TRY(hipMemcpyAsync(h_differentiable, h->d_adjA_flag, (size_t)h->batch, hipMemcpyDeviceToHost, h->stream));
+        if (!h->deferred_sync) HIP_TRY(hipStreamSynchronize(h->stream));
+        return LEXLS_OK;
+    }
+
+    int lexls_internal_apply_solve_map(lexls_lse_t h, const double *d_rhs, double *d_out)
+    {
+        if (int rc = need_adjoint_factor(h, "lexls_internal_apply_solve_map", d_rhs)) return rc;
+        if (!d_out) return fail(LEXLS_ERR_INVALID, "lexls_internal_apply_solve_map: null d_out");
+        HIP_TRY(hipSetDevice(h->device));
+        HIP_TRY(launch_apply_solve_map(h->args(), d_rhs, nullptr, d_out, h->stream));
         return LEXLS_OK;
     }
 

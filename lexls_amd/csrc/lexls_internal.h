@@ -42,4 +42,7 @@ extern "C"
     const double *lexls_internal_multipliers(lexls_lse_t h, int *swept);
     /// the handle's kernel policy (lexls_lse_set_kernel_policy), to put it back after a change
     int lexls_internal_kernel_policy(lexls_lse_t h);
+    /// d_out (batch x nVar, the order of x) = M d_rhs (batch x cap, LOD row order) for x = M b + N x_fixed of the kept, unregularized factor, fixed
+    /// values zero (apply_solve_map_kernel, the piece of lexls_lse_solve_adjoint_matrix that has no public entry); both in device memory, enqueued only
+    int lexls_internal_apply_solve_map(lexls_lse_t h, const double *d_rhs, double *d_out);
 }

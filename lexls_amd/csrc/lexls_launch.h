@@ -20,6 +20,18 @@ namespace lexls
     size_t adjoint_multi_work_bytes(const LseArgs &a);
     hipError_t launch_solve_adjoint_multi(const LseArgs &a, const double *d_G, uint32_t ncot, double *d_grad_rhs, double *d_grad_fixed, double *d_work, hipStream_t s,
                                           const char **variant = nullptr);
+    /// d_out (batch x nVar, the order of x) = M d_rhs (batch x cap, LOD row order) for x = M b + N x_fixed of the kept factor, fixed values zero:
+    /// the transpose of launch_solve_adjoint.  d_only_level (may be NULL): rows outside level d_only_level[b] of problem b count as zero.
+    /// One wavefront per problem, enqueued only.  Internal: the public header has no forward entry for new right-hand sides
+    hipError_t launch_apply_solve_map(const LseArgs &a, const double *d_rhs, const int32_t *d_only_level, double *d_out, hipStream_t s);
+    /// lexls_lse_solve_adjoint_matrix: d_grad_lod (batch x (nVar + 1) x cap, the layout of the problem data) = the gradient with respect to A and
+    /// b for the cotangent d_g (batch x nVar), d_differentiable (batch bytes, may be NULL) = the rank-stability flags; a.x holds the solution of the
+    /// kept factor.  Chains, in the stream: launch_solve_adjoint (y), the level search (k*), launch_sensitivity for level k* (lambda; its own rows
+    /// are the residual), launch_apply_solve_map (u) and the assembly — everything they write goes to d_work (adjoint_matrix_work_bytes): a.lambda,
+    /// a.v, a.sens, a.maxabs and the activation types stay as they are.  Enqueued only
+    size_t adjoint_matrix_work_bytes(const LseArgs &a);
+    hipError_t launch_solve_adjoint_matrix(const LseArgs &a, const double *d_g, double *d_grad_lod, uint8_t *d_differentiable, void *d_work, uint32_t sweep_level_dim_hint,
+                                           hipStream_t s, const char **variant = nullptr);
     hipError_t launch_sensitivity(const LseArgs &a, const int32_t *d_obj_index, int32_t obj_all, double tolW, double tolC, hipStream_t s, bool scan_up = false,
                                   uint32_t sweep_level_dim_hint = 0, // hint = largest level dimension of the batch (enables the single-sweep kernel)
                                   bool collect = false,              // the wrong-sign SET into a.wrong_sign instead of one candidate (lexls_lse_sensitivity_collect)

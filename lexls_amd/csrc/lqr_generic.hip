@@ -1252,6 +1252,259 @@ namespace lexls
             }
         }
 
+        // -----------------------------------------------------------------------------------------
+        // gradient with respect to the matrix (lexls_lse_solve_adjoint_matrix): the solve map on a new right-hand side, the assembly
+        // -----------------------------------------------------------------------------------------
+        /// out = M rhs for x = M b + N x_fixed of the kept factor (fixed values zero): the transpose of solve_adjoint_kernel's steps (c), (b), (a),
+        /// in that order.  One wavefront per problem, the factor read where it is kept, the right-hand side a cap-vector in LDS.  Every pass has
+        /// the LANES ALONG THE ROWS of one factor column (consecutive addresses); the reflector dot products are the only cross-lane traffic
+        /// (wave_sum).  rhs is batch x cap in LOD row order; only_level (may be NULL): rows outside level only_level[b] are read as zero (< 0: all
+        /// of them).  out is batch x nVar in the order of x, zero on fixed and free variables.
+        /// LDS (adjoint_lds_bytes): z = the solution in factor column order (nVar), t = the right-hand side (cap), the transpositions (nVar words).
+        /// Tolerance contract; no atomics: same bits run to run.
+        template <int NT>
+        __global__ __launch_bounds__(NT) void apply_solve_map_kernel(LseArgs a, const double *__restrict__ rhs, const int32_t *__restrict__ only_level, double *__restrict__ out)
+        {
+            static_assert(NT == 64, "one wavefront per problem: the reductions are wavefront sums");
+            constexpr uint32_t AU = 4;
+            extern __shared__ double smem[];
+            const uint32_t b = blockIdx.x, lane = threadIdx.x;
+            const uint32_t n = a.nVar, cap = a.cap, nObj = a.nObj;
+            const double *__restrict__ W = a.fac + (size_t)b * cap * (n + 1);
+            const double *hh     = a.hh + (size_t)b * cap;
+            const uint32_t *dims = a.dims + (size_t)b * nObj;
+            const uint32_t *rk = a.rank + (size_t)b * nObj, *fc = a.fcol + (size_t)b * nObj;
+            double *z        = smem;
+            double *t        = smem + n;
+            uint32_t *perm_l = reinterpret_cast<uint32_t *>(t + cap);
+            const uint32_t nf = a.nfixed ? (a.nfixed[b] < n ? a.nfixed[b] : n) : 0;
+            const uint32_t T  = a.totalrank[b] < n ? a.totalrank[b] : n; // pivot columns: [nf, T)
+            uint32_t M = 0;
+            for (uint32_t k = 0; k < nObj; k++) M += dims[k];
+            if (M > cap) M = cap;
+            // (a level's rank and first column as the loops below may trust them: solve_adjoint_kernel's rule)
+            auto level = [&](uint32_t k, uint32_t dim, uint32_t &rank, uint32_t &Fc) __attribute__((always_inline)) {
+                Fc   = fc[k];
+                rank = (nf < n && Fc < T) ? rk[k] : 0;
+                if (rank > dim) rank = dim;
+                if (rank > T - (Fc < T ? Fc : T)) rank = T - (Fc < T ? Fc : T);
+            };
+            uint32_t lo = 0, hi = M; // the rows of rhs that count
+            if (only_level)
+            {
+                const int32_t ks = only_level[b];
+                lo = hi = 0;
+                if (ks >= 0 && (uint32_t)ks < nObj)
+                {
+                    for (uint32_t k = 0; k < (uint32_t)ks; k++) lo += dims[k];
+                    hi = lo + dims[ks];
+                    if (hi > M) hi = M;
+                }
+            }
+            for (uint32_t i = lane; i < n; i += NT) perm_l[i] = a.perm[(size_t)b * n + i];
+            for (uint32_t i = lane; i < n; i += NT) z[i] = 0.0;
+            for (uint32_t i = lane; i < cap; i += NT) t[i] = (i >= lo && i < hi) ? rhs[(size_t)b * cap + i] : 0.0;
+            __syncthreads();
+
+            // ---- (c)^T factorize()'s right-hand-side updates, levels ascending: the level's reflectors, first to last, then the Gauss step (the
+            // multipliers L sit in the level's pivot columns, rows of the later levels) ----
+            uint32_t F = 0;
+            for (uint32_t k = 0; k < nObj; k++)
+            {
+                const uint32_t dim = dims[k];
+                uint32_t rank, Fc;
+                level(k, dim, rank, Fc);
+                if (rank > 0 && F + dim <= M)
+                {
+                    // H = I - tau [1; ess] [1; ess]^T on rows F + j .. F + dim - 1; none where factorize() made none (one row left, or tau == 0)
+                    for (uint32_t j0 = 0; j0 < rank; j0 += AU)
+                    {
+                        double e[AU], tau[AU];
+#pragma unroll
+                        for (uint32_t u = 0; u < AU; u++)
+                        {
+                            const uint32_t j = j0 + u;
+                            const bool on    = j < rank;
+                            tau[u] = on ? hh[F + j] : 0.0;
+                            e[u]   = (on && lane + 1 < dim - j) ? W[F + j + 1 + lane + (size_t)(Fc + j) * cap] : 0.0;
+                        }
+#pragma unroll
+                        for (uint32_t u = 0; u < AU; u++)
+                        {
+                            const uint32_t j = j0 + u;
+                            if (j >= rank) break;
+                            const uint32_t rows = dim - j;
+                            if (rows == 1 || tau[u] == 0.0) continue; // (uniform)
+                            const double *ess = W + F + j + 1 + (size_t)(Fc + j) * cap;
+                            double *v         = t + F + j;
+                            const double s    = column_dot(ess, v + 1, rows - 1, e[u], lane) + v[0];
+                            __syncthreads(); // (every lane has read v[0])
+                            if (lane == 0) v[0] = dfma(-tau[u], s, v[0]);
+                            if (lane + 1 < rows) v[1 + lane] = dfma(-(tau[u] * e[u]), s, v[1 + lane]);
+                            for (uint32_t i = lane + 64; i + 1 < rows; i += 64) v[1 + i] = dfma(-(tau[u] * ess[i]), s, v[1 + i]);
+                            __syncthreads();
+                        }
+                    }
+                    const uint32_t Fn = F + dim;
+                    if (k + 1 < nObj && Fn < M)
+                    {
+                        for (uint32_t i = lane; i < M - Fn; i += NT) // a row of the later levels: its multipliers against the level's top
+                        {
+                            double acc = t[Fn + i];
+                            uint32_t p = 0;
+                            for (; p + AU <= rank; p += AU)
+                            {
+                                double w[AU];
+#pragma unroll
+                                for (uint32_t u = 0; u < AU; u++) w[u] = W[Fn + i + (size_t)(Fc + p + u) * cap];
+#pragma unroll
+                                for (uint32_t u = 0; u < AU; u++) acc = dfma(-w[u], t[F + p + u], acc);
+                            }
+                            for (; p < rank; p++) acc = dfma(-W[Fn + i + (size_t)(Fc + p) * cap], t[F + p], acc);
+                            t[Fn + i] = acc;
+                        }
+                        __syncthreads();
+                    }
+                }
+                F += dim;
+            }
+
+            // ---- (b)^T solve(), levels descending: the top of the level minus [T_k] z on the pivot columns of the later levels, then the
+            // triangle column by column, last first: z_c = t_c / R_cc, t[rows above] -= W[rows, c] z_c ----
+            uint32_t Fend = F;
+            for (uint32_t k = nObj; k--;)
+            {
+                const uint32_t dim = dims[k];
+                F                  = Fend - dim;
+                Fend               = F;
+                uint32_t rank, Fc;
+                level(k, dim, rank, Fc);
+                if (rank == 0 || F + dim > M) continue;
+                for (uint32_t i = lane; i < rank; i += NT)
+                {
+                    double acc = t[F + i];
+                    uint32_t c = T;
+                    for (; c >= Fc + rank + AU; c -= AU)
+                    {
+                        double w[AU];
+#pragma unroll
+                        for (uint32_t u = 0; u < AU; u++) w[u] = W[F + i + (size_t)(c - 1 - u) * cap];
+#pragma unroll
+                        for (uint32_t u = 0; u < AU; u++) acc = dfma(-w[u], z[c - 1 - u], acc);
+                    }
+                    for (; c > Fc + rank; c--) acc = dfma(-W[F + i + (size_t)(c - 1) * cap], z[c - 1], acc);
+                    t[F + i] = acc;
+                }
+                __syncthreads();
+                // (the column and the diagonal entry of the NEXT step are requested before the division of the current one)
+                double wcur = (lane + 1 < rank) ? W[F + lane + (size_t)(Fc + rank - 1) * cap] : 0.0;
+                double dcur = W[F + rank - 1 + (size_t)(Fc + rank - 1) * cap];
+                for (uint32_t j = rank; j--;)
+                {
+                    const double wnext = (j >= 1 && lane + 1 < j) ? W[F + lane + (size_t)(Fc + j - 1) * cap] : 0.0;
+                    const double dnext = j >= 1 ? W[F + j - 1 + (size_t)(Fc + j - 1) * cap] : 1.0;
+                    const double zc    = t[F + j] / dcur; // every lane for itself: no hand-off (row j is not written in this step)
+                    if (lane == 0) z[Fc + j] = zc;
+                    if (lane < j) t[F + lane] = dfma(-wcur, zc, t[F + lane]);
+                    for (uint32_t i = lane + 64; i < j; i += 64) t[F + i] = dfma(-W[F + i + (size_t)(Fc + j) * cap], zc, t[F + i]);
+                    __syncthreads();
+                    wcur = wnext;
+                    dcur = dnext;
+                }
+            }
+            __syncthreads();
+
+            // ---- (a)^T out = P z: variable i takes the entry of the position it reaches by following the transpositions first to last ----
+            for (uint32_t i = lane; i < n; i += NT)
+            {
+                uint32_t p = i;
+                for (uint32_t k = 0; k < T; k++)
+                {
+                    const uint32_t pk = perm_l[k];
+                    p                 = (p == k) ? pk : ((p == pk) ? k : p);
+                }
+                out[(size_t)b * n + i] = (p >= nf && p < T) ? z[p] : 0.0;
+            }
+        }
+
+        /// k*[b] = the last level of non-zero rank as apply_solve_map_kernel trusts the ranks (-1: none — every variable fixed, or no pivot at all):
+        /// the level whose multipliers and whose share of y the matrix gradient needs.  One thread per problem.
+        __global__ __launch_bounds__(64) void adjoint_matrix_level_kernel(LseArgs a, int32_t *__restrict__ kstar)
+        {
+            const uint32_t b = blockIdx.x * 64 + threadIdx.x;
+            if (b >= a.batch) return;
+            const uint32_t n = a.nVar, nObj = a.nObj;
+            const uint32_t *dims = a.dims + (size_t)b * nObj, *rk = a.rank + (size_t)b * nObj, *fc = a.fcol + (size_t)b * nObj;
+            const uint32_t nf = a.nfixed ? (a.nfixed[b] < n ? a.nfixed[b] : n) : 0;
+            const uint32_t T  = a.totalrank[b] < n ? a.totalrank[b] : n;
+            uint32_t M = 0;
+            for (uint32_t k = 0; k < nObj; k++) M += dims[k];
+            if (M > a.cap) M = a.cap;
+            int32_t ks = -1;
+            uint32_t F = 0;
+            for (uint32_t k = 0; k < nObj; k++)
+            {
+                const uint32_t dim = dims[k], Fc = fc[k];
+                uint32_t rank = (nf < n && Fc < T) ? rk[k] : 0;
+                if (rank > dim) rank = dim;
+                if (rank > T - (Fc < T ? Fc : T)) rank = T - (Fc < T ? Fc : T);
+                if (rank > 0 && F + dim <= M) ks = (int32_t)k;
+                F += dim;
+            }
+            kstar[b] = ks;
+        }
+
+        /// G[b] (nVar + 1 columns of cap rows, the layout of the problem data: entry (row i, column j) at j * cap + i):
+        ///     column j < nVar = - y x_j - lambda u_j,   column nVar = y
+        /// with x the solution (a.x), y = M^T g (batch x cap), lambda the multipliers of level kstar[b] as sensitivity_kernel leaves them (batch x
+        /// (nVar + cap): row i at nfixed + i), u = M y~ (batch x nVar).  Rows behind the problem's own are zero.
+        /// differentiable[b] (may be NULL) = 1 where the problem is RANK-STABLE: every variable fixed, or rank_k == min(dim_k, nVar - Fc_k) for every
+        /// level k (Fc_k the level's first column; 0 where Fc_k >= nVar) — else 0, and the whole of G[b] is exact zeros.
+        /// One workgroup of NT / 64 wavefronts per problem: a wavefront takes every (NT / 64)-th column, its lanes run along the rows, so every store
+        /// is a run of consecutive addresses.  LDS: x and u (2 nVar doubles).  No atomics: same bits run to run.
+        template <int NT>
+        __global__ __launch_bounds__(NT) void adjoint_matrix_kernel(LseArgs a, const double *__restrict__ y, const double *__restrict__ lam, const double *__restrict__ u,
+                                                                    const int32_t *__restrict__ kstar, double *__restrict__ G, uint8_t *__restrict__ differentiable)
+        {
+            extern __shared__ double smem[];
+            const uint32_t b = blockIdx.x, tid = threadIdx.x, lane = tid & 63u, wave = tid >> 6;
+            const uint32_t n = a.nVar, cap = a.cap, nObj = a.nObj;
+            const uint32_t *dims = a.dims + (size_t)b * nObj, *rk = a.rank + (size_t)b * nObj, *fc = a.fcol + (size_t)b * nObj;
+            const uint32_t nf = a.nfixed ? a.nfixed[b] : 0;
+            double *xs = smem, *us = smem + n;
+            for (uint32_t i = tid; i < n; i += NT)
+            {
+                xs[i] = a.x[(size_t)b * n + i];
+                us[i] = u[(size_t)b * n + i];
+            }
+            uint32_t M   = 0;
+            bool stable  = true; // (uniform: every thread evaluates the rule for itself)
+            for (uint32_t k = 0; k < nObj; k++)
+            {
+                const uint32_t room = fc[k] < n ? n - fc[k] : 0;
+                if (rk[k] != (dims[k] < room ? dims[k] : room)) stable = false;
+                M += dims[k];
+            }
+            if (nf >= n) stable = true;
+            if (M > cap) M = cap;
+            if (tid == 0 && differentiable) differentiable[b] = stable ? 1 : 0;
+            const bool with_lambda = kstar[b] >= 0;
+            __syncthreads();
+            double *Gb = G + (size_t)b * cap * (n + 1);
+            for (uint32_t i = lane; i < cap; i += 64)
+            {
+                const bool own  = stable && i < M;
+                const double yi = own ? y[(size_t)b * cap + i] : 0.0;
+                const double li = (own && with_lambda) ? lam[(size_t)b * (n + cap) + (nf < n ? nf : n) + i] : 0.0;
+                for (uint32_t j = wave; j <= n; j += NT / 64)
+                {
+                    double val = 0.0;
+                    if (own) val = j < n ? dfma(-li, us[j], -(yi * xs[j])) : yi;
+                    Gb[(size_t)j * cap + i] = val;
+                }
+            }
+        }
+
         /// One coalesced pass over a problem's stored factor (cap x (nVar+1), column-major) into LDS, odd leading dimension so that
         /// "thread = row" and "thread = column" walks are conflict-free.  For kernels that walk the factor along dependent chains
         /// when latency, not occupancy, is what counts (few problems per CU; several levels per launch).
@@ -2311,6 +2564,61 @@ namespace lexls
             hipLaunchKernelGGL((solve_adjoint_multi_kernel<64, true>), dim3(a.batch, tiles), dim3(64), lds, s, a, d_G, ncot, d_grad_rhs, d_grad_fixed);
         else
             hipLaunchKernelGGL((solve_adjoint_multi_kernel<64, false>), dim3(a.batch, tiles), dim3(64), lds, s, a, d_G, ncot, d_grad_rhs, d_grad_fixed);
+        return hipGetLastError();
+    }
+
+    hipError_t launch_apply_solve_map(const LseArgs &a, const double *d_rhs, const int32_t *d_only_level, double *d_out, hipStream_t s)
+    {
+        const size_t lds = adjoint_lds_bytes(a.nVar, a.cap);
+        if (lds > kMaxLdsBytes) return hipErrorInvalidValue;
+        hipError_t e = set_lds(apply_solve_map_kernel<64>, lds);
+        if (e != hipSuccess) return e;
+        hipLaunchKernelGGL((apply_solve_map_kernel<64>), dim3(a.batch), dim3(64), lds, s, a, d_rhs, d_only_level, d_out);
+        return hipGetLastError();
+    }
+
+    /// y (batch x cap) | u (batch x nVar) | the scratch of the sensitivity launch, as launch_multipliers lays it out | k* (batch words)
+    size_t adjoint_matrix_work_bytes(const LseArgs &a)
+    {
+        const size_t B = a.batch;
+        return 8 * B * ((size_t)a.cap + a.nVar) + ((multipliers_scratch_bytes(a) + 7) & ~(size_t)7) + 4 * B;
+    }
+
+    hipError_t launch_solve_adjoint_matrix(const LseArgs &a, const double *d_g, double *d_grad_lod, uint8_t *d_differentiable, void *d_work, uint32_t sweep_level_dim_hint,
+                                           hipStream_t s, const char **variant)
+    {
+        if (!d_work || !d_grad_lod) return hipErrorInvalidValue;
+        const size_t B = a.batch, n = a.nVar, cap = a.cap;
+        const size_t lds = 8 * 2 * n;
+        if (lds > kMaxLdsBytes) return hipErrorInvalidValue;
+        double *w_y     = static_cast<double *>(d_work);
+        double *w_u     = w_y + B * cap;
+        char *w_sens    = reinterpret_cast<char *>(w_u + B * n);
+        int32_t *w_star = reinterpret_cast<int32_t *>(w_sens + ((multipliers_scratch_bytes(a) + 7) & ~(size_t)7));
+        // y = M^T g
+        hipError_t e = launch_solve_adjoint(a, d_g, w_y, nullptr, s);
+        if (e != hipSuccess) return e;
+        hipLaunchKernelGGL(adjoint_matrix_level_kernel, dim3((a.batch + 63u) / 64u), dim3(64), 0, s, a, w_star);
+        if ((e = hipGetLastError()) != hipSuccess) return e;
+        // the multipliers of level k* — its own rows hold the residual, so no residual launch in front of it — written, with the decisions and
+        // the marks of the removal search, into this call's work buffers (the types are copied there first): what get_lambda, get_v and
+        // get_multipliers answer stays what it was
+        LseArgs t    = a;
+        t.lambda     = reinterpret_cast<double *>(w_sens);
+        t.maxabs     = t.lambda + B * (n + cap);
+        t.sens       = reinterpret_cast<int32_t *>(t.maxabs + B);
+        t.ctr_type   = reinterpret_cast<uint8_t *>(t.sens + 3 * B);
+        t.fixed_type = t.ctr_type + B * cap;
+        t.wrong_sign = nullptr;
+        e = hipMemcpyAsync(t.ctr_type, a.ctr_type, B * cap, hipMemcpyDeviceToDevice, s);
+        if (e == hipSuccess) e = hipMemcpyAsync(t.fixed_type, a.fixed_type, B * n, hipMemcpyDeviceToDevice, s);
+        if (e == hipSuccess) e = launch_sensitivity(t, w_star, 0, 1e-8, 1e-12, s, false, sweep_level_dim_hint);
+        // u = M y~, y~ = y on the rows of level k*
+        if (e == hipSuccess) e = launch_apply_solve_map(a, w_y, w_star, w_u, s);
+        if (e != hipSuccess) return e;
+        if ((e = set_lds(adjoint_matrix_kernel<256>, lds)) != hipSuccess) return e;
+        hipLaunchKernelGGL((adjoint_matrix_kernel<256>), dim3(a.batch), dim3(256), lds, s, a, w_y, t.lambda, w_u, w_star, d_grad_lod, d_differentiable);
+        if (variant) *variant = "solve_adjoint_matrix<64>";
         return hipGetLastError();
     }
 

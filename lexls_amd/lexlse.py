@@ -351,6 +351,39 @@ class BatchedLexLSE:
         else:
             capi.check(capi.lib().lexls_lse_solve_adjoint_multi_device(self._h, args[0], K, args[1], args[2]))
 
+    # ---- gradient with respect to the matrix (rank-stable problems) ---------------------------------
+    def solve_adjoint_matrix(self, g):
+        """lexls_lse_solve_adjoint_matrix + lexls_lse_get_adjoint_matrix: g = dloss/dx, (batch, nVar) in the order of get_x().  Returns
+        (grad_lod, differentiable): grad_lod (batch, nVar + 1, cap) in the layout of the problem data — grad_lod[b, j, i] the gradient of entry
+        (row i, column j) of A for j < nVar, grad_lod[b, nVar] the gradient of the right-hand side, zero behind a problem's own rows — and
+        differentiable (batch,) uint8: 1 where the problem is rank-stable (rank_k == min(dim_k, nVar - Fc_k) for every level, or every variable
+        fixed), 0 where it is not and no derivative exists; there grad_lod[b] is entirely zero.  Needs a kept, unregularized factor and its x
+        (factorize_solve(keep_factor=True), or factorize() + solve())."""
+        g = np.ascontiguousarray(g, np.float64)
+        if g.shape != (self.batch, self.nVar):
+            raise ValueError(f"g must have shape {(self.batch, self.nVar)}, got {g.shape}")
+        capi.check(capi.lib().lexls_lse_solve_adjoint_matrix(self._h, _ptr(g, C.c_double)))
+        grad_lod = np.zeros((self.batch, self.nVar + 1, self.cap))
+        differentiable = np.zeros(self.batch, np.uint8)
+        capi.check(capi.lib().lexls_lse_get_adjoint_matrix(self._h, _ptr(grad_lod, C.c_double), _ptr(differentiable, C.c_uint8)))
+        return grad_lod, differentiable
+
+    def solve_adjoint_matrix_device(self, g, grad_lod, differentiable=None):
+        """lexls_lse_solve_adjoint_matrix_device: g (batch, nVar) float64, grad_lod (batch, nVar + 1, cap) float64 and differentiable (batch,)
+        uint8 (None: not wanted) in device memory — contiguous torch tensors or raw addresses.  Only enqueued in the handle's stream (set_stream):
+        g has to be complete in stream order, nothing is waited for."""
+        def address(name, t, shape, dtype="torch.float64"):
+            if t is None:
+                return None
+            if not hasattr(t, "data_ptr"):
+                return C.c_void_p(int(t))
+            if str(t.dtype) != dtype or not t.is_contiguous() or tuple(t.shape) != shape:
+                raise ValueError(f"solve_adjoint_matrix_device: {name} must be a contiguous {dtype.split('.')[1]} tensor of shape {shape}")
+            return C.c_void_p(t.data_ptr())
+        capi.check(capi.lib().lexls_lse_solve_adjoint_matrix_device(self._h, address("g", g, (self.batch, self.nVar)),
+                                                                     address("grad_lod", grad_lod, (self.batch, self.nVar + 1, self.cap)),
+                                                                     address("differentiable", differentiable, (self.batch,), "torch.uint8")))
+
     def jacobian_device(self):
         """(dx_db (batch, nVar, cap), dx_dfixed (batch, nVar, nVar)) of the kept factor as torch tensors on the handle's device: the identity
         cotangents are built there and go through solve_adjoint_multi_device, so dx_db[b, i, r] = d x_i / d b_r (LOD row order) and

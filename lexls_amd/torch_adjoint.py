@@ -5,6 +5,10 @@ right-hand sides: x = M b (+ N x_fixed).  ``SolveRhs`` solves on the device from
 M^T (dloss/dx) from one pass over the kept factor (lexls_lse_solve_adjoint_device).  There are no derivatives with respect to A — x is not
 continuous in A where a rank changes — and asking for them raises instead of returning zeros.
 
+``SolveLod`` is the operation that does differentiate with respect to A: it takes the whole problem data (matrices and right-hand sides) as one
+tensor and returns, in the backward pass, the gradient of both (lexls_lse_solve_adjoint_matrix_device) for the rank-stable problems of the
+batch, with a per-problem flag and zeros for the others.
+
 ``SolveBounds`` is the same for a batch of LexLSI problems in their bounds: at a solved instance x is the basic solution of the equality
 problem of the final working set, affine in the active bounds while that set holds.  Forward is LsiBatch.run_device, backward
 LsiBatch.solve_adjoint_device (lexls_lsi_batch_solve_adjoint_device).
@@ -128,9 +132,61 @@ def _solve_bounds_class():
     return SolveBounds
 
 
+_SOLVE_LOD = None
+
+
+def _solve_lod_class():
+    global _SOLVE_LOD
+    if _SOLVE_LOD is not None:
+        return _SOLVE_LOD
+    import torch
+    from torch.autograd.function import once_differentiable
+
+    class _Span:  # the CUDA array interface over memory this object does not own
+        def __init__(self, address, shape):
+            self.__cuda_array_interface__ = dict(shape=shape, typestr="<f8", data=(int(address), False), version=2, strides=None)
+
+    class SolveLod(torch.autograd.Function):
+        """x = SolveLod.apply(lod, lse): lod (batch, nVar + 1, cap) float64 on the device, the matrices and the right-hand sides in the layout of
+        setProblem; lse a BatchedLexLSE of that shape (dimensions, fixed variables and tolerance set by the caller; no regularization).  Forward
+        binds lod as the handle's input without a copy (setProblemDevice: it must stay alive and unchanged until backward has run), factorizes
+        with the factor kept and solves; x (batch, nVar) comes back as a new tensor.  Backward returns grad_lod (batch, nVar + 1, cap) from
+        lexls_lse_solve_adjoint_matrix_device: one tensor carries the gradients of both A and b.  A problem that is not rank-stable has no
+        derivative with respect to A: its slice of grad_lod is zero, and `lse.differentiable` — a (batch,) uint8 device tensor set by backward —
+        is 0 there."""
+
+        @staticmethod
+        def forward(ctx, lod, lse):
+            shape = (lse.batch, lse.nVar + 1, lse.cap)
+            if tuple(lod.shape) != shape or lod.dtype != torch.float64 or not lod.is_cuda or not lod.is_contiguous():
+                raise ValueError(f"SolveLod: lod must be a contiguous float64 device tensor of shape {shape}")
+            lse.set_stream(torch.cuda.current_stream(lod.device).cuda_stream)
+            lse.setProblemDevice(lod.data_ptr())
+            lse.factorize_solve(keep_factor=True)
+            x = torch.as_tensor(_Span(lse.device_ptr("x"), (lse.batch, lse.nVar)), device=lod.device).clone()
+            ctx.lse, ctx.lod = lse, lod
+            return x
+
+        @staticmethod
+        @once_differentiable
+        def backward(ctx, grad_x):
+            lse = ctx.lse
+            g = grad_x.contiguous()
+            grad_lod = torch.empty((lse.batch, lse.nVar + 1, lse.cap), dtype=torch.float64, device=g.device)
+            lse.differentiable = torch.empty((lse.batch,), dtype=torch.uint8, device=g.device)
+            lse.set_stream(torch.cuda.current_stream(g.device).cuda_stream)
+            lse.solve_adjoint_matrix_device(g, grad_lod, lse.differentiable)
+            return grad_lod, None
+
+    _SOLVE_LOD = SolveLod
+    return SolveLod
+
+
 def __getattr__(name):
     if name == "SolveRhs":
         return _solve_rhs_class()
+    if name == "SolveLod":
+        return _solve_lod_class()
     if name == "SolveBounds":
         return _solve_bounds_class()
     raise AttributeError(f"module {__name__!r} has no attribute {name!r}")
@@ -139,6 +195,12 @@ def __getattr__(name):
 def solve_rhs(rhs, lse, lod):
     """SolveRhs.apply(rhs, lse, lod)"""
     return _solve_rhs_class().apply(rhs, lse, lod)
+
+
+def solve_lod(solver, lod):
+    """SolveLod.apply(lod, solver): the solutions of the batch `lod` (batch, nVar + 1, cap) on the BatchedLexLSE `solver`, differentiable in the
+    matrices and the right-hand sides where the problems are rank-stable"""
+    return _solve_lod_class().apply(lod, solver)
 
 
 def solve_bounds(lb, ub, batch, data, var_index=None, active_guess=None, x0=None, out=None, **params):
