@@ -5,11 +5,17 @@
 
 namespace lexls
 {
+    template <typename K>
+    inline hipError_t set_lds(K kernel, size_t bytes) // a launcher's request for dynamic LDS: above the 64 KiB every kernel may have, the kernel is told so
+    {
+        return bytes <= 64 * 1024 ? hipSuccess : hipFuncSetAttribute(reinterpret_cast<const void *>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes);
+    }
     // lqr_generic.hip — any shape, one workgroup per problem (id: one of the generic_* forms, dispatch::generic_choice)
     hipError_t launch_lqr_generic(LseArgs a, uint32_t max_rows, KernelId id, bool write_factor, bool do_solve, hipStream_t s);
     // (variant, where given: the name of the kernel variant launched — lexls_lse_last_consumer_kernel; host bookkeeping only)
     hipError_t launch_solve_generic(const LseArgs &a, hipStream_t s, bool reciprocal_diagonal = false, const char **variant = nullptr);
     hipError_t launch_residual(const LseArgs &a, hipStream_t s, const char **variant = nullptr);
+    // lse_adjoint.hip — the adjoint family of the kept factor (the view and the trust rule its kernels share: lse_kept_factor.h)
     /// lexls_lse_solve_adjoint: d_grad_rhs (batch x cap) = M^T g, d_grad_fixed (batch x nVar, may be NULL) = N^T g for x = M b + N x_fixed of the
     /// kept factor; d_g is batch x nVar in the order of x.  One wavefront per problem, enqueued only
     hipError_t launch_solve_adjoint(const LseArgs &a, const double *d_g, double *d_grad_rhs, double *d_grad_fixed, hipStream_t s, const char **variant = nullptr);
@@ -32,6 +38,7 @@ namespace lexls
     size_t adjoint_matrix_work_bytes(const LseArgs &a);
     hipError_t launch_solve_adjoint_matrix(const LseArgs &a, const double *d_g, double *d_grad_lod, uint8_t *d_differentiable, void *d_work, uint32_t sweep_level_dim_hint,
                                            hipStream_t s, const char **variant = nullptr);
+    // lqr_generic.hip again — the sensitivity, multiplier and least-norm kernels
     hipError_t launch_sensitivity(const LseArgs &a, const int32_t *d_obj_index, int32_t obj_all, double tolW, double tolC, hipStream_t s, bool scan_up = false,
                                   uint32_t sweep_level_dim_hint = 0, // hint = largest level dimension of the batch (enables the single-sweep kernel)
                                   bool collect = false,              // the wrong-sign SET into a.wrong_sign instead of one candidate (lexls_lse_sensitivity_collect)
@@ -41,6 +48,9 @@ namespace lexls
     /// sweep's emitting form where multipliers_sweep_serves, else nObj sensitivity_kernel launches (d_scratch: multipliers_scratch_bytes)
     bool multipliers_sweep_serves(const LseArgs &a, uint32_t sweep_level_dim_hint);
     size_t multipliers_scratch_bytes(const LseArgs &a);
+    /// *out = a with lambda | maxabs | sens | ctr_type | fixed_type carved out of d_scratch (multipliers_scratch_bytes counts them in this order; THE layout, for
+    /// launch_multipliers and launch_solve_adjoint_matrix) and the copies of the two type arrays enqueued (the launch marks them; the handle's own stay); wrong_sign as in a
+    hipError_t sensitivity_scratch_args(const LseArgs &a, void *d_scratch, hipStream_t s, LseArgs *out);
     hipError_t launch_multipliers(const LseArgs &a, double *d_out, uint32_t sweep_level_dim_hint, hipStream_t s, void *d_scratch, bool *swept, const char **variant = nullptr);
     hipError_t launch_leastnorm(const LseArgs &a, hipStream_t s, const char **variant = nullptr);
     hipError_t launch_leastnorm2(const LseArgs &a, hipStream_t s, const char **variant = nullptr);

@@ -207,15 +207,15 @@ namespace lexls
         return b;
     }
 
-    // ---- solve_adjoint (lqr_generic.hip) ----
+    // ---- solve_adjoint, apply_solve_map (lse_adjoint.hip) ----
     /// g in factor column order (nVar doubles), the gradient of the right-hand side with y inside it (cap doubles), the transpositions (nVar words)
     inline size_t adjoint_lds_bytes(uint32_t nVar, uint32_t cap) { return (8 * ((size_t)nVar + cap) + 4 * (size_t)nVar + 15) & ~(size_t)15; }
 
-    // ---- solve_adjoint_multi (lqr_generic.hip): lane = cotangent ----
+    // ---- solve_adjoint_multi (lse_adjoint.hip): lane = cotangent ----
     constexpr uint32_t kAdjointMultiLd = 65; // odd leading dimension of the per-lane state, stored [index][lane]
     /// the per-lane state gh (nVar) and cb (cap), [index][lane] with leading dimension 65; the transpositions and the position every variable
     /// reaches by them (2 x nVar words, shared by the lanes); staged: + the problem's factor without its right-hand-side column (odd leading
-    /// dimension, as stage_factor writes it) and hh (cap doubles)
+    /// dimension, as stage_factor — lse_kept_factor.h — writes it) and hh (cap doubles)
     inline size_t adjoint_multi_lds_bytes(uint32_t nVar, uint32_t cap, bool staged)
     {
         size_t b = 8 * (size_t)kAdjointMultiLd * ((size_t)nVar + cap) + 8 * (size_t)nVar;

@@ -18,10 +18,10 @@
 #include "lqr_wave_common.h"
 #include "lexls_regularize.h"
 #include "lexls_sweep_impl.h"
+#include "lse_kept_factor.h" // (stage_factor)
 
 #include <cfloat>
 #include <cstdlib>
-#include <cstring>
 
 namespace lexls
 {
@@ -1061,660 +1061,6 @@ namespace lexls
         }
 
         // -----------------------------------------------------------------------------------------
-        // adjoint of factorize()'s right-hand-side updates + solve(): grad_rhs = M^T g, grad_fixed = N^T g  (x = M b + N x_fixed for fixed A)
-        // -----------------------------------------------------------------------------------------
-        /// sum over the 64 lanes of a wavefront, the same bits in every lane and from run to run (xor butterfly: the two partners of a step
-        /// add the same two values)
-        __device__ __forceinline__ double wave_sum(double v)
-        {
-#pragma unroll
-            for (int o = 32; o >= 1; o >>= 1) v += __shfl_xor(v, o, 64);
-            return v;
-        }
-
-        /// sum_{i < len} col[i] * vec[i], col in the stored factor (consecutive rows of ONE column: the lanes read consecutive addresses), vec in
-        /// LDS; w0 = this lane's entry of the first 64 rows (0 beyond len), fetched by the caller ahead of the chain it sits on
-        __device__ __forceinline__ double column_dot(const double *col, const double *vec, uint32_t len, double w0, uint32_t lane)
-        {
-            double p = lane < len ? w0 * vec[lane] : 0.0;
-            for (uint32_t i = lane + 64; i < len; i += 64) p = dfma(col[i], vec[i], p);
-            return wave_sum(p);
-        }
-
-        /// One wavefront per problem, the factor read where it is kept (never staged): every pass has the lanes along the ROWS of one factor
-        /// column — consecutive addresses — and ends in a wavefront sum, so no step sends 64 requests a column apart.  Columns go AU at a time:
-        /// their first 64 rows are requested together, then the (dependent) steps consume them.
-        /// LDS (adjoint_lds_bytes): gh = g in factor column order (nVar), cb = the gradient of the right-hand side, LOD row order (cap; y of
-        /// level k = R_k^-T gh_k is written straight into rows F .. F + rank of it), the transpositions (nVar words).
-        /// Tolerance contract (no reference arithmetic exists for this); no atomics: same bits run to run.
-        template <int NT>
-        __global__ __launch_bounds__(NT) void solve_adjoint_kernel(LseArgs a, const double *__restrict__ g, double *__restrict__ grad_rhs, double *__restrict__ grad_fixed)
-        {
-            static_assert(NT == 64, "one wavefront per problem: the reductions are wavefront sums");
-            constexpr uint32_t AU = 4;
-            extern __shared__ double smem[];
-            const uint32_t b = blockIdx.x, lane = threadIdx.x;
-            const uint32_t n = a.nVar, cap = a.cap, nObj = a.nObj;
-            const double *__restrict__ W = a.fac + (size_t)b * cap * (n + 1);
-            const double *hh     = a.hh + (size_t)b * cap;
-            const uint32_t *dims = a.dims + (size_t)b * nObj;
-            const uint32_t *rk = a.rank + (size_t)b * nObj, *fc = a.fcol + (size_t)b * nObj;
-            double *gh       = smem;
-            double *cb       = smem + n;
-            uint32_t *perm_l = reinterpret_cast<uint32_t *>(cb + cap);
-            const uint32_t nf = a.nfixed ? (a.nfixed[b] < n ? a.nfixed[b] : n) : 0;
-            const uint32_t T  = a.totalrank[b] < n ? a.totalrank[b] : n; // pivot columns: [nf, T)
-            uint32_t M = 0;
-            for (uint32_t k = 0; k < nObj; k++) M += dims[k];
-            if (M > cap) M = cap;
-            // (a level's rank and first column as the loops below may trust them: inside the level's rows and the pivot columns)
-            auto level = [&](uint32_t k, uint32_t dim, uint32_t &rank, uint32_t &Fc) __attribute__((always_inline)) {
-                Fc   = fc[k];
-                rank = (nf < n && Fc < T) ? rk[k] : 0; // (every variable fixed: factorize() returns before the levels)
-                if (rank > dim) rank = dim;
-                if (rank > T - (Fc < T ? Fc : T)) rank = T - (Fc < T ? Fc : T);
-            };
-
-            // ---- (a) gh = P^T g: variable i sits at the position it reaches by following the transpositions first to last ----
-            for (uint32_t i = lane; i < n; i += NT) perm_l[i] = a.perm[(size_t)b * n + i];
-            for (uint32_t i = lane; i < cap; i += NT) cb[i] = 0.0;
-            __syncthreads();
-            for (uint32_t i = lane; i < n; i += NT)
-            {
-                uint32_t p = i;
-                for (uint32_t k = 0; k < T; k++)
-                {
-                    const uint32_t pk = perm_l[k];
-                    p                 = (p == k) ? pk : ((p == pk) ? k : p);
-                }
-                if (p < n) gh[p] = g[(size_t)b * n + i];
-            }
-            __syncthreads();
-
-            // ---- (b) the reverse of solve(), levels ascending: y = R_k^-T gh_k, then gh -= [T_k]^T y on the pivot columns of the later levels.
-            // Column c of [R_k | T_k] takes the dot product of its rows above the diagonal (all `rank` rows behind the triangle) with y ----
-            uint32_t F = 0;
-            for (uint32_t k = 0; k < nObj; k++)
-            {
-                const uint32_t dim = dims[k];
-                uint32_t rank, Fc;
-                level(k, dim, rank, Fc);
-                if (rank > 0 && F + dim <= M)
-                {
-                    double *y = cb + F;
-                    for (uint32_t c0 = Fc; c0 < T; c0 += AU)
-                    {
-                        double w[AU], dg[AU];
-#pragma unroll
-                        for (uint32_t u = 0; u < AU; u++)
-                        {
-                            const uint32_t c = c0 + u, j = c - Fc;
-                            const uint32_t len = c < T ? (j < rank ? j : rank) : 0;
-                            w[u]  = lane < len ? W[F + lane + (size_t)c * cap] : 0.0;
-                            dg[u] = (c < T && j < rank) ? W[F + j + (size_t)c * cap] : 1.0;
-                        }
-#pragma unroll
-                        for (uint32_t u = 0; u < AU; u++)
-                        {
-                            const uint32_t c = c0 + u, j = c - Fc;
-                            if (c >= T) break;
-                            const uint32_t len = j < rank ? j : rank;
-                            const double s     = column_dot(W + F + (size_t)c * cap, y, len, w[u], lane);
-                            if (j < rank) // (uniform) inside the triangle: the next column reads this y
-                            {
-                                if (lane == 0) y[j] = (gh[c] - s) / dg[u];
-                                __syncthreads();
-                            }
-                            else if (lane == 0)
-                                gh[c] -= s;
-                        }
-                    }
-                    __syncthreads();
-                }
-                F += dim;
-            }
-
-            // ---- (c) the reverse of factorize()'s right-hand-side updates, levels descending: the transposed Gauss step (the multipliers L sit in
-            // the level's pivot columns, rows of the later levels), then the level's reflectors, last first ----
-            uint32_t Fend = 0;
-            for (uint32_t k = 0; k < nObj; k++) Fend += dims[k];
-            for (uint32_t k = nObj; k--;)
-            {
-                const uint32_t dim = dims[k];
-                F                  = Fend - dim;
-                Fend               = F;
-                uint32_t rank, Fc;
-                level(k, dim, rank, Fc);
-                if (rank == 0 || F + dim > M) continue;
-                const uint32_t Fn = F + dim;
-                if (k + 1 < nObj && Fn < M)
-                {
-                    for (uint32_t p0 = 0; p0 < rank; p0 += AU)
-                    {
-                        double w[AU], s[AU];
-#pragma unroll
-                        for (uint32_t u = 0; u < AU; u++) w[u] = (p0 + u < rank && lane < M - Fn) ? W[Fn + lane + (size_t)(Fc + p0 + u) * cap] : 0.0;
-#pragma unroll
-                        for (uint32_t u = 0; u < AU; u++) s[u] = p0 + u < rank ? column_dot(W + Fn + (size_t)(Fc + p0 + u) * cap, cb + Fn, M - Fn, w[u], lane) : 0.0;
-#pragma unroll
-                        for (uint32_t u = 0; u < AU; u++)
-                            if (lane == 0 && p0 + u < rank) cb[F + p0 + u] -= s[u];
-                    }
-                    __syncthreads();
-                }
-                // H = I - tau [1; ess] [1; ess]^T on rows F + j .. F + dim - 1; none where factorize() made none (one row left, or tau == 0)
-                for (uint32_t j0 = rank; j0 > 0; j0 -= (j0 < AU ? j0 : AU))
-                {
-                    double e[AU], tau[AU];
-#pragma unroll
-                    for (uint32_t u = 0; u < AU; u++)
-                    {
-                        const bool on = u < j0;
-                        const uint32_t j = on ? j0 - 1 - u : 0;
-                        tau[u] = on ? hh[F + j] : 0.0;
-                        e[u]   = (on && lane + 1 < dim - j) ? W[F + j + 1 + lane + (size_t)(Fc + j) * cap] : 0.0;
-                    }
-#pragma unroll
-                    for (uint32_t u = 0; u < AU; u++)
-                    {
-                        if (u >= j0) break;
-                        const uint32_t j = j0 - 1 - u, rows = dim - j;
-                        if (rows == 1 || tau[u] == 0.0) continue; // (uniform)
-                        const double *ess = W + F + j + 1 + (size_t)(Fc + j) * cap;
-                        double *v         = cb + F + j;
-                        const double t    = column_dot(ess, v + 1, rows - 1, e[u], lane) + v[0];
-                        __syncthreads(); // (every lane has read v[0])
-                        if (lane == 0) v[0] = dfma(-tau[u], t, v[0]);
-                        if (lane + 1 < rows) v[1 + lane] = dfma(-(tau[u] * e[u]), t, v[1 + lane]);
-                        for (uint32_t i = lane + 64; i + 1 < rows; i += 64) v[1 + i] = dfma(-(tau[u] * ess[i]), t, v[1 + i]);
-                        __syncthreads();
-                    }
-                }
-            }
-            __syncthreads();
-
-            // ---- (d) grad_rhs = cb (rows behind the problem's own stay 0); grad_fixed_j = gh_j - (column j of the fixed variables)^T cb ----
-            for (uint32_t i = lane; i < cap; i += NT) grad_rhs[(size_t)b * cap + i] = cb[i];
-            if (grad_fixed)
-            {
-                for (uint32_t j0 = 0; j0 < nf; j0 += AU)
-                {
-                    double w[AU], s[AU];
-#pragma unroll
-                    for (uint32_t u = 0; u < AU; u++) w[u] = (j0 + u < nf && lane < M) ? W[lane + (size_t)(j0 + u) * cap] : 0.0;
-#pragma unroll
-                    for (uint32_t u = 0; u < AU; u++) s[u] = j0 + u < nf ? column_dot(W + (size_t)(j0 + u) * cap, cb, M, w[u], lane) : 0.0;
-#pragma unroll
-                    for (uint32_t u = 0; u < AU; u++)
-                        if (lane == 0 && j0 + u < nf) grad_fixed[(size_t)b * n + j0 + u] = gh[j0 + u] - s[u];
-                }
-                for (uint32_t j = nf + lane; j < n; j += NT) grad_fixed[(size_t)b * n + j] = 0.0;
-            }
-        }
-
-        // -----------------------------------------------------------------------------------------
-        // gradient with respect to the matrix (lexls_lse_solve_adjoint_matrix): the solve map on a new right-hand side, the assembly
-        // -----------------------------------------------------------------------------------------
-        /// out = M rhs for x = M b + N x_fixed of the kept factor (fixed values zero): the transpose of solve_adjoint_kernel's steps (c), (b), (a),
-        /// in that order.  One wavefront per problem, the factor read where it is kept, the right-hand side a cap-vector in LDS.  Every pass has
-        /// the LANES ALONG THE ROWS of one factor column (consecutive addresses); the reflector dot products are the only cross-lane traffic
-        /// (wave_sum).  rhs is batch x cap in LOD row order; only_level (may be NULL): rows outside level only_level[b] are read as zero (< 0: all
-        /// of them).  out is batch x nVar in the order of x, zero on fixed and free variables.
-        /// LDS (adjoint_lds_bytes): z = the solution in factor column order (nVar), t = the right-hand side (cap), the transpositions (nVar words).
-        /// Tolerance contract; no atomics: same bits run to run.
-        template <int NT>
-        __global__ __launch_bounds__(NT) void apply_solve_map_kernel(LseArgs a, const double *__restrict__ rhs, const int32_t *__restrict__ only_level, double *__restrict__ out)
-        {
-            static_assert(NT == 64, "one wavefront per problem: the reductions are wavefront sums");
-            constexpr uint32_t AU = 4;
-            extern __shared__ double smem[];
-            const uint32_t b = blockIdx.x, lane = threadIdx.x;
-            const uint32_t n = a.nVar, cap = a.cap, nObj = a.nObj;
-            const double *__restrict__ W = a.fac + (size_t)b * cap * (n + 1);
-            const double *hh     = a.hh + (size_t)b * cap;
-            const uint32_t *dims = a.dims + (size_t)b * nObj;
-            const uint32_t *rk = a.rank + (size_t)b * nObj, *fc = a.fcol + (size_t)b * nObj;
-            double *z        = smem;
-            double *t        = smem + n;
-            uint32_t *perm_l = reinterpret_cast<uint32_t *>(t + cap);
-            const uint32_t nf = a.nfixed ? (a.nfixed[b] < n ? a.nfixed[b] : n) : 0;
-            const uint32_t T  = a.totalrank[b] < n ? a.totalrank[b] : n; // pivot columns: [nf, T)
-            uint32_t M = 0;
-            for (uint32_t k = 0; k < nObj; k++) M += dims[k];
-            if (M > cap) M = cap;
-            // (a level's rank and first column as the loops below may trust them: solve_adjoint_kernel's rule)
-            auto level = [&](uint32_t k, uint32_t dim, uint32_t &rank, uint32_t &Fc) __attribute__((always_inline)) {
-                Fc   = fc[k];
-                rank = (nf < n && Fc < T) ? rk[k] : 0;
-                if (rank > dim) rank = dim;
-                if (rank > T - (Fc < T ? Fc : T)) rank = T - (Fc < T ? Fc : T);
-            };
-            uint32_t lo = 0, hi = M; // the rows of rhs that count
-            if (only_level)
-            {
-                const int32_t ks = only_level[b];
-                lo = hi = 0;
-                if (ks >= 0 && (uint32_t)ks < nObj)
-                {
-                    for (uint32_t k = 0; k < (uint32_t)ks; k++) lo += dims[k];
-                    hi = lo + dims[ks];
-                    if (hi > M) hi = M;
-                }
-            }
-            for (uint32_t i = lane; i < n; i += NT) perm_l[i] = a.perm[(size_t)b * n + i];
-            for (uint32_t i = lane; i < n; i += NT) z[i] = 0.0;
-            for (uint32_t i = lane; i < cap; i += NT) t[i] = (i >= lo && i < hi) ? rhs[(size_t)b * cap + i] : 0.0;
-            __syncthreads();
-
-            // ---- (c)^T factorize()'s right-hand-side updates, levels ascending: the level's reflectors, first to last, then the Gauss step (the
-            // multipliers L sit in the level's pivot columns, rows of the later levels) ----
-            uint32_t F = 0;
-            for (uint32_t k = 0; k < nObj; k++)
-            {
-                const uint32_t dim = dims[k];
-                uint32_t rank, Fc;
-                level(k, dim, rank, Fc);
-                if (rank > 0 && F + dim <= M)
-                {
-                    // H = I - tau [1; ess] [1; ess]^T on rows F + j .. F + dim - 1; none where factorize() made none (one row left, or tau == 0)
-                    for (uint32_t j0 = 0; j0 < rank; j0 += AU)
-                    {
-                        double e[AU], tau[AU];
-#pragma unroll
-                        for (uint32_t u = 0; u < AU; u++)
-                        {
-                            const uint32_t j = j0 + u;
-                            const bool on    = j < rank;
-                            tau[u] = on ? hh[F + j] : 0.0;
-                            e[u]   = (on && lane + 1 < dim - j) ? W[F + j + 1 + lane + (size_t)(Fc + j) * cap] : 0.0;
-                        }
-#pragma unroll
-                        for (uint32_t u = 0; u < AU; u++)
-                        {
-                            const uint32_t j = j0 + u;
-                            if (j >= rank) break;
-                            const uint32_t rows = dim - j;
-                            if (rows == 1 || tau[u] == 0.0) continue; // (uniform)
-                            const double *ess = W + F + j + 1 + (size_t)(Fc + j) * cap;
-                            double *v         = t + F + j;
-                            const double s    = column_dot(ess, v + 1, rows - 1, e[u], lane) + v[0];
-                            __syncthreads(); // (every lane has read v[0])
-                            if (lane == 0) v[0] = dfma(-tau[u], s, v[0]);
-                            if (lane + 1 < rows) v[1 + lane] = dfma(-(tau[u] * e[u]), s, v[1 + lane]);
-                            for (uint32_t i = lane + 64; i + 1 < rows; i += 64) v[1 + i] = dfma(-(tau[u] * ess[i]), s, v[1 + i]);
-                            __syncthreads();
-                        }
-                    }
-                    const uint32_t Fn = F + dim;
-                    if (k + 1 < nObj && Fn < M)
-                    {
-                        for (uint32_t i = lane; i < M - Fn; i += NT) // a row of the later levels: its multipliers against the level's top
-                        {
-                            double acc = t[Fn + i];
-                            uint32_t p = 0;
-                            for (; p + AU <= rank; p += AU)
-                            {
-                                double w[AU];
-#pragma unroll
-                                for (uint32_t u = 0; u < AU; u++) w[u] = W[Fn + i + (size_t)(Fc + p + u) * cap];
-#pragma unroll
-                                for (uint32_t u = 0; u < AU; u++) acc = dfma(-w[u], t[F + p + u], acc);
-                            }
-                            for (; p < rank; p++) acc = dfma(-W[Fn + i + (size_t)(Fc + p) * cap], t[F + p], acc);
-                            t[Fn + i] = acc;
-                        }
-                        __syncthreads();
-                    }
-                }
-                F += dim;
-            }
-
-            // ---- (b)^T solve(), levels descending: the top of the level minus [T_k] z on the pivot columns of the later levels, then the
-            // triangle column by column, last first: z_c = t_c / R_cc, t[rows above] -= W[rows, c] z_c ----
-            uint32_t Fend = F;
-            for (uint32_t k = nObj; k--;)
-            {
-                const uint32_t dim = dims[k];
-                F                  = Fend - dim;
-                Fend               = F;
-                uint32_t rank, Fc;
-                level(k, dim, rank, Fc);
-                if (rank == 0 || F + dim > M) continue;
-                for (uint32_t i = lane; i < rank; i += NT)
-                {
-                    double acc = t[F + i];
-                    uint32_t c = T;
-                    for (; c >= Fc + rank + AU; c -= AU)
-                    {
-                        double w[AU];
-#pragma unroll
-                        for (uint32_t u = 0; u < AU; u++) w[u] = W[F + i + (size_t)(c - 1 - u) * cap];
-#pragma unroll
-                        for (uint32_t u = 0; u < AU; u++) acc = dfma(-w[u], z[c - 1 - u], acc);
-                    }
-                    for (; c > Fc + rank; c--) acc = dfma(-W[F + i + (size_t)(c - 1) * cap], z[c - 1], acc);
-                    t[F + i] = acc;
-                }
-                __syncthreads();
-                // (the column and the diagonal entry of the NEXT step are requested before the division of the current one)
-                double wcur = (lane + 1 < rank) ? W[F + lane + (size_t)(Fc + rank - 1) * cap] : 0.0;
-                double dcur = W[F + rank - 1 + (size_t)(Fc + rank - 1) * cap];
-                for (uint32_t j = rank; j--;)
-                {
-                    const double wnext = (j >= 1 && lane + 1 < j) ? W[F + lane + (size_t)(Fc + j - 1) * cap] : 0.0;
-                    const double dnext = j >= 1 ? W[F + j - 1 + (size_t)(Fc + j - 1) * cap] : 1.0;
-                    const double zc    = t[F + j] / dcur; // every lane for itself: no hand-off (row j is not written in this step)
-                    if (lane == 0) z[Fc + j] = zc;
-                    if (lane < j) t[F + lane] = dfma(-wcur, zc, t[F + lane]);
-                    for (uint32_t i = lane + 64; i < j; i += 64) t[F + i] = dfma(-W[F + i + (size_t)(Fc + j) * cap], zc, t[F + i]);
-                    __syncthreads();
-                    wcur = wnext;
-                    dcur = dnext;
-                }
-            }
-            __syncthreads();
-
-            // ---- (a)^T out = P z: variable i takes the entry of the position it reaches by following the transpositions first to last ----
-            for (uint32_t i = lane; i < n; i += NT)
-            {
-                uint32_t p = i;
-                for (uint32_t k = 0; k < T; k++)
-                {
-                    const uint32_t pk = perm_l[k];
-                    p                 = (p == k) ? pk : ((p == pk) ? k : p);
-                }
-                out[(size_t)b * n + i] = (p >= nf && p < T) ? z[p] : 0.0;
-            }
-        }
-
-        /// k*[b] = the last level of non-zero rank as apply_solve_map_kernel trusts the ranks (-1: none — every variable fixed, or no pivot at all):
-        /// the level whose multipliers and whose share of y the matrix gradient needs.  One thread per problem.
-        __global__ __launch_bounds__(64) void adjoint_matrix_level_kernel(LseArgs a, int32_t *__restrict__ kstar)
-        {
-            const uint32_t b = blockIdx.x * 64 + threadIdx.x;
-            if (b >= a.batch) return;
-            const uint32_t n = a.nVar, nObj = a.nObj;
-            const uint32_t *dims = a.dims + (size_t)b * nObj, *rk = a.rank + (size_t)b * nObj, *fc = a.fcol + (size_t)b * nObj;
-            const uint32_t nf = a.nfixed ? (a.nfixed[b] < n ? a.nfixed[b] : n) : 0;
-            const uint32_t T  = a.totalrank[b] < n ? a.totalrank[b] : n;
-            uint32_t M = 0;
-            for (uint32_t k = 0; k < nObj; k++) M += dims[k];
-            if (M > a.cap) M = a.cap;
-            int32_t ks = -1;
-            uint32_t F = 0;
-            for (uint32_t k = 0; k < nObj; k++)
-            {
-                const uint32_t dim = dims[k], Fc = fc[k];
-                uint32_t rank = (nf < n && Fc < T) ? rk[k] : 0;
-                if (rank > dim) rank = dim;
-                if (rank > T - (Fc < T ? Fc : T)) rank = T - (Fc < T ? Fc : T);
-                if (rank > 0 && F + dim <= M) ks = (int32_t)k;
-                F += dim;
-            }
-            kstar[b] = ks;
-        }
-
-        /// G[b] (nVar + 1 columns of cap rows, the layout of the problem data: entry (row i, column j) at j * cap + i):
-        ///     column j < nVar = - y x_j - lambda u_j,   column nVar = y
-        /// with x the solution (a.x), y = M^T g (batch x cap), lambda the multipliers of level kstar[b] as sensitivity_kernel leaves them (batch x
-        /// (nVar + cap): row i at nfixed + i), u = M y~ (batch x nVar).  Rows behind the problem's own are zero.
-        /// differentiable[b] (may be NULL) = 1 where the problem is RANK-STABLE: every variable fixed, or rank_k == min(dim_k, nVar - Fc_k) for every
-        /// level k (Fc_k the level's first column; 0 where Fc_k >= nVar) — else 0, and the whole of G[b] is exact zeros.
-        /// One workgroup of NT / 64 wavefronts per problem: a wavefront takes every (NT / 64)-th column, its lanes run along the rows, so every store
-        /// is a run of consecutive addresses.  LDS: x and u (2 nVar doubles).  No atomics: same bits run to run.
-        template <int NT>
-        __global__ __launch_bounds__(NT) void adjoint_matrix_kernel(LseArgs a, const double *__restrict__ y, const double *__restrict__ lam, const double *__restrict__ u,
-                                                                    const int32_t *__restrict__ kstar, double *__restrict__ G, uint8_t *__restrict__ differentiable)
-        {
-            extern __shared__ double smem[];
-            const uint32_t b = blockIdx.x, tid = threadIdx.x, lane = tid & 63u, wave = tid >> 6;
-            const uint32_t n = a.nVar, cap = a.cap, nObj = a.nObj;
-            const uint32_t *dims = a.dims + (size_t)b * nObj, *rk = a.rank + (size_t)b * nObj, *fc = a.fcol + (size_t)b * nObj;
-            const uint32_t nf = a.nfixed ? a.nfixed[b] : 0;
-            double *xs = smem, *us = smem + n;
-            for (uint32_t i = tid; i < n; i += NT)
-            {
-                xs[i] = a.x[(size_t)b * n + i];
-                us[i] = u[(size_t)b * n + i];
-            }
-            uint32_t M   = 0;
-            bool stable  = true; // (uniform: every thread evaluates the rule for itself)
-            for (uint32_t k = 0; k < nObj; k++)
-            {
-                const uint32_t room = fc[k] < n ? n - fc[k] : 0;
-                if (rk[k] != (dims[k] < room ? dims[k] : room)) stable = false;
-                M += dims[k];
-            }
-            if (nf >= n) stable = true;
-            if (M > cap) M = cap;
-            if (tid == 0 && differentiable) differentiable[b] = stable ? 1 : 0;
-            const bool with_lambda = kstar[b] >= 0;
-            __syncthreads();
-            double *Gb = G + (size_t)b * cap * (n + 1);
-            for (uint32_t i = lane; i < cap; i += 64)
-            {
-                const bool own  = stable && i < M;
-                const double yi = own ? y[(size_t)b * cap + i] : 0.0;
-                const double li = (own && with_lambda) ? lam[(size_t)b * (n + cap) + (nf < n ? nf : n) + i] : 0.0;
-                for (uint32_t j = wave; j <= n; j += NT / 64)
-                {
-                    double val = 0.0;
-                    if (own) val = j < n ? dfma(-li, us[j], -(yi * xs[j])) : yi;
-                    Gb[(size_t)j * cap + i] = val;
-                }
-            }
-        }
-
-        /// One coalesced pass over a problem's stored factor (cap x (nVar+1), column-major) into LDS, odd leading dimension so that
-        /// "thread = row" and "thread = column" walks are conflict-free.  For kernels that walk the factor along dependent chains
-        /// when latency, not occupancy, is what counts (few problems per CU; several levels per launch).
-        template <int NT>
-        __device__ __forceinline__ void stage_factor(const double *__restrict__ G, double *L, uint32_t cap, uint32_t ncol, uint32_t ldl, uint32_t tid)
-        {
-            constexpr uint32_t U = NT <= 64 ? 20 : 8; // loads in flight per thread (one wavefront staging for itself: the rounds are latency, not bandwidth)
-            const uint32_t total = cap * ncol;
-            for (uint32_t base = tid; base < total; base += NT * U)
-            {
-                double v[U];
-#pragma unroll
-                for (uint32_t u = 0; u < U; u++)
-                {
-                    const uint32_t e = base + u * NT;
-                    v[u]             = e < total ? G[e] : 0.0;
-                }
-#pragma unroll
-                for (uint32_t u = 0; u < U; u++)
-                {
-                    const uint32_t e = base + u * NT;
-                    if (e < total)
-                    {
-                        const uint32_t j = e / cap;
-                        L[(e - j * cap) + j * ldl] = v[u];
-                    }
-                }
-            }
-            __syncthreads();
-        }
-
-        /// solve_adjoint_kernel's steps (a)-(d) for up to 64 cotangents of one problem at once, LANE = COTANGENT: one wavefront per (problem,
-        /// tile of 64 cotangents), lane l of tile t owns cotangent 64 t + l; lanes beyond ncot compute on zeros and store nothing.  Everything
-        /// that steers the control flow (dims, ranks, first columns, tau == 0) belongs to the problem, so it is wavefront-uniform; every factor
-        /// entry is the same for all lanes (STAGED: a broadcast read of the image stage_factor left in LDS; else a read of the stored factor at
-        /// a wavefront-uniform address); every dot product is the lane's own serial dfma chain in ascending row order — no cross-lane
-        /// reduction and no barrier between the steps, and a cotangent's bits do not depend on its lane, its tile or its neighbours.
-        /// LDS (adjoint_multi_lds_bytes): gh[nVar][LD], cb[cap][LD], LD = 65 (odd: "lane = cotangent" walks take consecutive words, the
-        /// transposed walks of the load and store phases a stride of 65 words — both conflict-free), the transpositions and the position
-        /// each variable reaches (2 nVar words), then STAGED the factor's nVar columns (odd leading dimension) and hh.
-        /// Global traffic: a tile's rows of G, grad_rhs and grad_fixed are contiguous; consecutive lanes take consecutive addresses and the
-        /// transposition happens in LDS.  No atomics.
-        template <int NT, bool STAGED>
-        __global__ __launch_bounds__(NT) void solve_adjoint_multi_kernel(LseArgs a, const double *__restrict__ G, uint32_t ncot, double *__restrict__ grad_rhs,
-                                                                         double *__restrict__ grad_fixed)
-        {
-            static_assert(NT == 64, "one wavefront per (problem, tile): lane = cotangent");
-            constexpr uint32_t LD = kAdjointMultiLd, AU = 4;
-            extern __shared__ double smem[];
-            const uint32_t b = blockIdx.x, tile = blockIdx.y, lane = threadIdx.x;
-            const uint32_t n = a.nVar, cap = a.cap, nObj = a.nObj;
-            if (b >= a.batch || tile * 64u >= ncot) return; // (block-uniform)
-            const uint32_t kt = ncot - tile * 64u < 64u ? ncot - tile * 64u : 64u; // live cotangents of this tile
-            const double *__restrict__ W = a.fac + (size_t)b * cap * (n + 1);
-            const uint32_t *dims = a.dims + (size_t)b * nObj;
-            const uint32_t *rk = a.rank + (size_t)b * nObj, *fc = a.fcol + (size_t)b * nObj;
-            double *gh       = smem;
-            double *cb       = gh + (size_t)n * LD;
-            uint32_t *perm_l = reinterpret_cast<uint32_t *>(cb + (size_t)cap * LD);
-            uint32_t *pos_l  = perm_l + n;
-            double *L        = reinterpret_cast<double *>(pos_l + n); // (2 n words: still 8-byte aligned)
-            const uint32_t ldl = cap | 1u; // odd_ld(cap)
-            double *hh_l       = L + (size_t)ldl * n;
-            const double *hh_g = a.hh + (size_t)b * cap;
-            const uint32_t nf = a.nfixed ? (a.nfixed[b] < n ? a.nfixed[b] : n) : 0;
-            const uint32_t T  = a.totalrank[b] < n ? a.totalrank[b] : n; // pivot columns: [nf, T)
-            uint32_t M = 0;
-            for (uint32_t k = 0; k < nObj; k++) M += dims[k];
-            if (M > cap) M = cap;
-            auto level = [&](uint32_t k, uint32_t dim, uint32_t &rank, uint32_t &Fc) __attribute__((always_inline)) {
-                Fc   = fc[k];
-                rank = (nf < n && Fc < T) ? rk[k] : 0; // (every variable fixed: factorize() returns before the levels)
-                if (rank > dim) rank = dim;
-                if (rank > T - (Fc < T ? Fc : T)) rank = T - (Fc < T ? Fc : T);
-            };
-            // entry (r, c) of the factor, r < M <= cap, c < T <= nVar; the Householder scalar of row r < cap
-            auto Wat = [&](uint32_t r, uint32_t c) __attribute__((always_inline)) -> double { return STAGED ? L[r + c * ldl] : W[r + (size_t)c * cap]; };
-            auto tau_at = [&](uint32_t r) __attribute__((always_inline)) -> double { return STAGED ? hh_l[r] : hh_g[r]; };
-
-            // ---- staging, and (a) gh = P^T g for every cotangent of the tile ----
-            for (uint32_t i = lane; i < n; i += NT) perm_l[i] = a.perm[(size_t)b * n + i];
-            for (uint32_t i = lane; i < (n + cap) * LD; i += NT) smem[i] = 0.0; // gh and cb (dead lanes, absent rows, unreached positions: zeros)
-            if (STAGED)
-            {
-                for (uint32_t i = lane; i < cap; i += NT) hh_l[i] = hh_g[i];
-                stage_factor<NT>(W, L, cap, n, ldl, lane); // (ends in a barrier)
-            }
-            else
-                __syncthreads();
-            for (uint32_t i = lane; i < n; i += NT)
-            {
-                uint32_t p = i;
-                for (uint32_t k = 0; k < T; k++)
-                {
-                    const uint32_t pk = perm_l[k];
-                    p                 = (p == k) ? pk : ((p == pk) ? k : p);
-                }
-                pos_l[i] = p;
-            }
-            __syncthreads();
-            {
-                const double *Gt = G + ((size_t)b * ncot + (size_t)tile * 64u) * n; // kt rows of n doubles, contiguous
-                for (uint32_t e = lane; e < kt * n; e += NT)
-                {
-                    const uint32_t c = e / n, i = e - c * n, p = pos_l[i];
-                    if (p < n) gh[p * LD + c] = Gt[e];
-                }
-            }
-            __syncthreads();
-            double *ghl = gh + lane, *cbl = cb + lane; // this lane's column of the state
-
-            // ---- (b) the reverse of solve(), levels ascending ----
-            uint32_t F = 0;
-            for (uint32_t k = 0; k < nObj; k++)
-            {
-                const uint32_t dim = dims[k];
-                uint32_t rank, Fc;
-                level(k, dim, rank, Fc);
-                if (rank > 0 && F + dim <= M)
-                {
-                    double *y = cbl + F * LD;
-                    for (uint32_t c = Fc; c < T; c++)
-                    {
-                        const uint32_t j = c - Fc, len = j < rank ? j : rank;
-                        double s = 0.0;
-                        for (uint32_t i = 0; i < len; i++) s = dfma(Wat(F + i, c), y[i * LD], s);
-                        if (j < rank) // (uniform) inside the triangle
-                            y[j * LD] = (ghl[c * LD] - s) / Wat(F + j, c);
-                        else
-                            ghl[c * LD] -= s;
-                    }
-                }
-                F += dim;
-            }
-
-            // ---- (c) the reverse of factorize()'s right-hand-side updates, levels descending ----
-            uint32_t Fend = 0;
-            for (uint32_t k = 0; k < nObj; k++) Fend += dims[k];
-            for (uint32_t k = nObj; k--;)
-            {
-                const uint32_t dim = dims[k];
-                F                  = Fend - dim;
-                Fend               = F;
-                uint32_t rank, Fc;
-                level(k, dim, rank, Fc);
-                if (rank == 0 || F + dim > M) continue;
-                const uint32_t Fn = F + dim;
-                if (k + 1 < nObj && Fn < M)
-                {
-                    // the transposed Gauss step: AU multiplier columns share one read of the lane's cb rows (each sum in ascending row order)
-                    for (uint32_t p0 = 0; p0 < rank; p0 += AU)
-                    {
-                        double s[AU];
-#pragma unroll
-                        for (uint32_t u = 0; u < AU; u++) s[u] = 0.0;
-                        for (uint32_t i = Fn; i < M; i++)
-                        {
-                            const double ci = cbl[i * LD];
-#pragma unroll
-                            for (uint32_t u = 0; u < AU; u++)
-                                if (p0 + u < rank) s[u] = dfma(Wat(i, Fc + p0 + u), ci, s[u]);
-                        }
-#pragma unroll
-                        for (uint32_t u = 0; u < AU; u++)
-                            if (p0 + u < rank) cbl[(F + p0 + u) * LD] -= s[u];
-                    }
-                }
-                for (uint32_t j = rank; j--;) // the level's reflectors, last first; none where factorize() made none
-                {
-                    const uint32_t rows = dim - j;
-                    const double tau    = tau_at(F + j);
-                    if (rows == 1 || tau == 0.0) continue; // (uniform)
-                    double *v = cbl + (F + j) * LD;
-                    double t  = 0.0;
-                    for (uint32_t i = 1; i < rows; i++) t = dfma(Wat(F + j + i, Fc + j), v[i * LD], t);
-                    t += v[0];
-                    v[0] = dfma(-tau, t, v[0]);
-                    for (uint32_t i = 1; i < rows; i++) v[i * LD] = dfma(-(tau * Wat(F + j + i, Fc + j)), t, v[i * LD]);
-                }
-            }
-
-            // ---- (d) grad_fixed_j = gh_j - (column j of the fixed variables)^T cb, left in gh_j; then both outputs, transposed through LDS ----
-            if (grad_fixed)
-                for (uint32_t j = 0; j < nf; j++)
-                {
-                    double s = 0.0;
-                    for (uint32_t r = 0; r < M; r++) s = dfma(Wat(r, j), cbl[r * LD], s);
-                    ghl[j * LD] -= s;
-                }
-            __syncthreads();
-            {
-                double *out = grad_rhs + ((size_t)b * ncot + (size_t)tile * 64u) * cap;
-                for (uint32_t e = lane; e < kt * cap; e += NT)
-                {
-                    const uint32_t c = e / cap, r = e - c * cap;
-                    out[e]           = cb[r * LD + c]; // (rows behind the problem's own were never touched: 0)
-                }
-            }
-            if (grad_fixed)
-            {
-                double *out = grad_fixed + ((size_t)b * ncot + (size_t)tile * 64u) * n;
-                for (uint32_t e = lane; e < kt * n; e += NT)
-                {
-                    const uint32_t c = e / n, j = e - c * n;
-                    out[e]           = j < nf ? gh[j * LD + c] : 0.0;
-                }
-            }
-        }
-
-        // -----------------------------------------------------------------------------------------
         // ObjectiveSensitivity (lexlse.h:611-762) + findDescentDirection (:935-987)
         // -----------------------------------------------------------------------------------------
         struct SensState
@@ -2402,13 +1748,6 @@ namespace lexls
     // ---------------------------------------------------------------------------------------------
     namespace
     {
-        template <typename K>
-        hipError_t set_lds(K kernel, size_t bytes)
-        {
-            if (bytes <= 64 * 1024) return hipSuccess;
-            return hipFuncSetAttribute(reinterpret_cast<const void *>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes);
-        }
-
         static_assert(sizeof(Shared) == kGenericSharedBytes, "generic_lds_bytes (lexls_lds.h) counts the Shared block");
 
         template <int NT, bool LDSMAT>
@@ -2502,126 +1841,6 @@ namespace lexls
         return hipGetLastError();
     }
 
-    hipError_t launch_solve_adjoint(const LseArgs &a, const double *d_g, double *d_grad_rhs, double *d_grad_fixed, hipStream_t s, const char **variant)
-    {
-        const size_t lds = adjoint_lds_bytes(a.nVar, a.cap);
-        if (lds > kMaxLdsBytes) return hipErrorInvalidValue;
-        hipError_t e = set_lds(solve_adjoint_kernel<64>, lds);
-        if (e != hipSuccess) return e;
-        hipLaunchKernelGGL((solve_adjoint_kernel<64>), dim3(a.batch), dim3(64), lds, s, a, d_g, d_grad_rhs, d_grad_fixed);
-        if (variant) *variant = "solve_adjoint<64>";
-        return hipGetLastError();
-    }
-
-    /// the form launch_solve_adjoint_multi takes for a shape: adjoint_multi_form (lexls_lds.h), unless LEXLS_ADJOINT_MULTI_FORM = staged | hbm |
-    /// single names a later form of the list (measurements: a form whose LDS does not fit is never forced)
-    static AdjointMultiForm adjoint_multi_form_for(uint32_t nVar, uint32_t cap)
-    {
-        AdjointMultiForm f = adjoint_multi_form(nVar, cap);
-        if (const char *e = std::getenv("LEXLS_ADJOINT_MULTI_FORM"))
-        {
-            if (!std::strcmp(e, "single")) f = AdjointMultiForm::per_cotangent;
-            if (!std::strcmp(e, "hbm") && f == AdjointMultiForm::staged) f = AdjointMultiForm::hbm;
-        }
-        return f;
-    }
-
-    size_t adjoint_multi_work_bytes(const LseArgs &a)
-    {
-        return adjoint_multi_form_for(a.nVar, a.cap) == AdjointMultiForm::per_cotangent ? 8 * (size_t)a.batch * (2 * (size_t)a.nVar + a.cap) : 0;
-    }
-
-    hipError_t launch_solve_adjoint_multi(const LseArgs &a, const double *d_G, uint32_t ncot, double *d_grad_rhs, double *d_grad_fixed, double *d_work, hipStream_t s,
-                                          const char **variant)
-    {
-        const AdjointMultiForm f = adjoint_multi_form_for(a.nVar, a.cap);
-        const uint32_t tiles     = (ncot + 63u) / 64u;
-        if (ncot == 0 || tiles > 65535u) return hipErrorInvalidValue;
-        if (variant) *variant = adjoint_multi_form_name(f);
-        if (f == AdjointMultiForm::per_cotangent)
-        {
-            // the single-cotangent kernel reads and writes one row per problem, a problem after the other: cotangent c's rows (a stride of ncot
-            // rows apart) travel through three buffers of that layout
-            if (!d_work) return hipErrorInvalidValue;
-            const size_t B = a.batch, n = a.nVar, cap = a.cap;
-            double *w_g = d_work, *w_rhs = w_g + B * n, *w_fixed = w_rhs + B * cap;
-            for (uint32_t c = 0; c < ncot; c++)
-            {
-                hipError_t e = hipMemcpy2DAsync(w_g, 8 * n, d_G + (size_t)c * n, 8 * n * ncot, 8 * n, B, hipMemcpyDeviceToDevice, s);
-                if (e == hipSuccess) e = launch_solve_adjoint(a, w_g, w_rhs, d_grad_fixed ? w_fixed : nullptr, s);
-                if (e == hipSuccess) e = hipMemcpy2DAsync(d_grad_rhs + (size_t)c * cap, 8 * cap * ncot, w_rhs, 8 * cap, 8 * cap, B, hipMemcpyDeviceToDevice, s);
-                if (e == hipSuccess && d_grad_fixed) e = hipMemcpy2DAsync(d_grad_fixed + (size_t)c * n, 8 * n * ncot, w_fixed, 8 * n, 8 * n, B, hipMemcpyDeviceToDevice, s);
-                if (e != hipSuccess) return e;
-            }
-            return hipSuccess;
-        }
-        const bool staged = f == AdjointMultiForm::staged;
-        const size_t lds  = adjoint_multi_lds_bytes(a.nVar, a.cap, staged);
-        if (lds > kMaxLdsBytes) return hipErrorInvalidValue;
-        hipError_t e = staged ? set_lds(solve_adjoint_multi_kernel<64, true>, lds) : set_lds(solve_adjoint_multi_kernel<64, false>, lds);
-        if (e != hipSuccess) return e;
-        if (staged)
-            hipLaunchKernelGGL((solve_adjoint_multi_kernel<64, true>), dim3(a.batch, tiles), dim3(64), lds, s, a, d_G, ncot, d_grad_rhs, d_grad_fixed);
-        else
-            hipLaunchKernelGGL((solve_adjoint_multi_kernel<64, false>), dim3(a.batch, tiles), dim3(64), lds, s, a, d_G, ncot, d_grad_rhs, d_grad_fixed);
-        return hipGetLastError();
-    }
-
-    hipError_t launch_apply_solve_map(const LseArgs &a, const double *d_rhs, const int32_t *d_only_level, double *d_out, hipStream_t s)
-    {
-        const size_t lds = adjoint_lds_bytes(a.nVar, a.cap);
-        if (lds > kMaxLdsBytes) return hipErrorInvalidValue;
-        hipError_t e = set_lds(apply_solve_map_kernel<64>, lds);
-        if (e != hipSuccess) return e;
-        hipLaunchKernelGGL((apply_solve_map_kernel<64>), dim3(a.batch), dim3(64), lds, s, a, d_rhs, d_only_level, d_out);
-        return hipGetLastError();
-    }
-
-    /// y (batch x cap) | u (batch x nVar) | the scratch of the sensitivity launch, as launch_multipliers lays it out | k* (batch words)
-    size_t adjoint_matrix_work_bytes(const LseArgs &a)
-    {
-        const size_t B = a.batch;
-        return 8 * B * ((size_t)a.cap + a.nVar) + ((multipliers_scratch_bytes(a) + 7) & ~(size_t)7) + 4 * B;
-    }
-
-    hipError_t launch_solve_adjoint_matrix(const LseArgs &a, const double *d_g, double *d_grad_lod, uint8_t *d_differentiable, void *d_work, uint32_t sweep_level_dim_hint,
-                                           hipStream_t s, const char **variant)
-    {
-        if (!d_work || !d_grad_lod) return hipErrorInvalidValue;
-        const size_t B = a.batch, n = a.nVar, cap = a.cap;
-        const size_t lds = 8 * 2 * n;
-        if (lds > kMaxLdsBytes) return hipErrorInvalidValue;
-        double *w_y     = static_cast<double *>(d_work);
-        double *w_u     = w_y + B * cap;
-        char *w_sens    = reinterpret_cast<char *>(w_u + B * n);
-        int32_t *w_star = reinterpret_cast<int32_t *>(w_sens + ((multipliers_scratch_bytes(a) + 7) & ~(size_t)7));
-        // y = M^T g
-        hipError_t e = launch_solve_adjoint(a, d_g, w_y, nullptr, s);
-        if (e != hipSuccess) return e;
-        hipLaunchKernelGGL(adjoint_matrix_level_kernel, dim3((a.batch + 63u) / 64u), dim3(64), 0, s, a, w_star);
-        if ((e = hipGetLastError()) != hipSuccess) return e;
-        // the multipliers of level k* — its own rows hold the residual, so no residual launch in front of it — written, with the decisions and
-        // the marks of the removal search, into this call's work buffers (the types are copied there first): what get_lambda, get_v and
-        // get_multipliers answer stays what it was
-        LseArgs t    = a;
-        t.lambda     = reinterpret_cast<double *>(w_sens);
-        t.maxabs     = t.lambda + B * (n + cap);
-        t.sens       = reinterpret_cast<int32_t *>(t.maxabs + B);
-        t.ctr_type   = reinterpret_cast<uint8_t *>(t.sens + 3 * B);
-        t.fixed_type = t.ctr_type + B * cap;
-        t.wrong_sign = nullptr;
-        e = hipMemcpyAsync(t.ctr_type, a.ctr_type, B * cap, hipMemcpyDeviceToDevice, s);
-        if (e == hipSuccess) e = hipMemcpyAsync(t.fixed_type, a.fixed_type, B * n, hipMemcpyDeviceToDevice, s);
-        if (e == hipSuccess) e = launch_sensitivity(t, w_star, 0, 1e-8, 1e-12, s, false, sweep_level_dim_hint);
-        // u = M y~, y~ = y on the rows of level k*
-        if (e == hipSuccess) e = launch_apply_solve_map(a, w_y, w_star, w_u, s);
-        if (e != hipSuccess) return e;
-        if ((e = set_lds(adjoint_matrix_kernel<256>, lds)) != hipSuccess) return e;
-        hipLaunchKernelGGL((adjoint_matrix_kernel<256>), dim3(a.batch), dim3(256), lds, s, a, w_y, t.lambda, w_u, w_star, d_grad_lod, d_differentiable);
-        if (variant) *variant = "solve_adjoint_matrix<64>";
-        return hipGetLastError();
-    }
-
     namespace
     {
         int cus_of_current_device() // (a process may drive several)
@@ -2703,6 +1922,20 @@ namespace lexls
         return 8 * B * ((size_t)a.nVar + a.cap) + 8 * B + 4 * 3 * B + B * ((size_t)a.cap + a.nVar);
     }
 
+    hipError_t sensitivity_scratch_args(const LseArgs &a, void *d_scratch, hipStream_t s, LseArgs *out)
+    {
+        LseArgs &t     = *out = a;
+        const size_t B = a.batch;
+        t.lambda       = static_cast<double *>(d_scratch);
+        t.maxabs       = t.lambda + B * ((size_t)a.nVar + a.cap);
+        t.sens         = reinterpret_cast<int32_t *>(t.maxabs + B);
+        t.ctr_type     = reinterpret_cast<uint8_t *>(t.sens + 3 * B);
+        t.fixed_type   = t.ctr_type + B * a.cap;
+        hipError_t e   = hipMemcpyAsync(t.ctr_type, a.ctr_type, B * a.cap, hipMemcpyDeviceToDevice, s);
+        if (e == hipSuccess) e = hipMemcpyAsync(t.fixed_type, a.fixed_type, B * a.nVar, hipMemcpyDeviceToDevice, s);
+        return e;
+    }
+
     hipError_t launch_multipliers(const LseArgs &a, double *d_out, uint32_t sweep_level_dim_hint, hipStream_t s, void *d_scratch, bool *swept, const char **variant)
     {
         const size_t ldo = (size_t)a.nVar + a.cap;
@@ -2721,19 +1954,12 @@ namespace lexls
         // one sensitivity_kernel launch per objective, each copied into its column; the launches write the multipliers, decisions and marks into
         // scratch (the types are copied there first: the handle's own arrays stay as they are, as they do under the sweep)
         if (!d_scratch) return hipErrorInvalidValue;
-        LseArgs t      = a;
-        const size_t B = a.batch;
-        t.lambda       = static_cast<double *>(d_scratch);
-        t.maxabs       = t.lambda + B * ldo;
-        t.sens         = reinterpret_cast<int32_t *>(t.maxabs + B);
-        t.ctr_type     = reinterpret_cast<uint8_t *>(t.sens + 3 * B);
-        t.fixed_type   = t.ctr_type + B * a.cap;
-        hipError_t e   = hipMemcpyAsync(t.ctr_type, a.ctr_type, B * a.cap, hipMemcpyDeviceToDevice, s);
-        if (e == hipSuccess) e = hipMemcpyAsync(t.fixed_type, a.fixed_type, B * a.nVar, hipMemcpyDeviceToDevice, s);
+        LseArgs t;
+        hipError_t e = sensitivity_scratch_args(a, d_scratch, s, &t);
         for (uint32_t k = 0; k < a.nObj && e == hipSuccess; k++)
         {
             e = launch_sensitivity(t, nullptr, (int32_t)k, 1e-8, 1e-12, s, false, 0);
-            if (e == hipSuccess) e = hipMemcpy2DAsync(d_out + k * ldo, 8 * ldo * a.nObj, t.lambda, 8 * ldo, 8 * ldo, B, hipMemcpyDeviceToDevice, s);
+            if (e == hipSuccess) e = hipMemcpy2DAsync(d_out + k * ldo, 8 * ldo * a.nObj, t.lambda, 8 * ldo, 8 * ldo, a.batch, hipMemcpyDeviceToDevice, s);
         }
         return e;
     }

@@ -1,4 +1,4 @@
-"""Cases that hold the adjoint of the LexLSE solve (lexls_lse_solve_adjoint, lexls_amd/csrc/lqr_generic.hip: solve_adjoint_kernel) to two
+"""Cases that hold the adjoint of the LexLSE solve (lexls_lse_solve_adjoint, lexls_amd/csrc/lse_adjoint.hip: solve_adjoint_kernel) to two
 references, both built from oracle.oracle_ctypes.lse_run alone (tests/test_adjoint_cases.py asserts on the CPU that they agree;
 tests/test_gpu_lse_adjoint.py compares the device with them).
 

@@ -1,4 +1,4 @@
-"""Cases that hold the gradient of the LexLSE solve with respect to the matrix (lexls_lse_solve_adjoint_matrix, lexls_amd/csrc/lqr_generic.hip:
+"""Cases that hold the gradient of the LexLSE solve with respect to the matrix (lexls_lse_solve_adjoint_matrix, lexls_amd/csrc/lse_adjoint.hip:
 apply_solve_map + adjoint_matrix_kernel) to two references (tests/test_adjoint_matrix_cases.py asserts on the CPU that they agree;
 tests/test_gpu_lse_adjoint_matrix.py compares the device with reference (A)).
 

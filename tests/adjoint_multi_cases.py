@@ -1,4 +1,4 @@
-"""Cases that hold the multi-cotangent adjoint of the LexLSE solve (lexls_lse_solve_adjoint_multi, lexls_amd/csrc/lqr_generic.hip:
+"""Cases that hold the multi-cotangent adjoint of the LexLSE solve (lexls_lse_solve_adjoint_multi, lexls_amd/csrc/lse_adjoint.hip:
 solve_adjoint_multi_kernel, lane = cotangent) to the references of tests/adjoint_cases.py, cotangent by cotangent
 (tests/test_adjoint_multi_cases.py asserts on the CPU that the references agree; tests/test_gpu_lse_adjoint_multi.py compares the device
 with them).
