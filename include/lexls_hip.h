@@ -748,7 +748,7 @@ int lexls_lsi_batch_get_lambda(lexls_lsi_batch_t b, double *h_lambda);
  * g = dloss/dx these calls return dloss/dlb and dloss/dub: the final equality problems are formed and factorized with the factor kept as for
  * lexls_lsi_batch_get_lambda (once per run: whichever of the two is called first pays for it, every later call of either reuses the factor),
  * lexls_lse_solve_adjoint_device gives M^T g and N^T g, and lsi_adjoint_scatter_kernel takes them from LOD-row / fixed-slot order back to the
- * user's constraint order.  There are NO derivatives with respect to A (see lexls_lse_solve_adjoint).
+ * user's constraint order.  These calls give NO derivatives with respect to A: lexls_lsi_batch_solve_adjoint_matrix, below, does.
  * Layouts: g is batch x nVar, dloss/dx in the user's variable order; grad_lb and grad_ub are batch x sum(dims) each, in the constraint order of
  * h_active / h_v (objective by objective).  Either output may be NULL (not wanted).  lexls_lsi_batch_solve_adjoint takes and fills host arrays;
  * lexls_lsi_batch_solve_adjoint_device takes memory of the batch's device, and no gradient, g or factor passes through host memory.  Both are
@@ -781,6 +781,39 @@ int lexls_lsi_batch_solve_adjoint_device(lexls_lsi_batch_t b, const double *d_g,
  * returned before any device work and with every output left alone.  The independence contract of lexls_lse_solve_adjoint_multi holds. */
 int lexls_lsi_batch_solve_adjoint_multi(lexls_lsi_batch_t b, const double *h_G, uint32_t ncot, double *h_grad_lb, double *h_grad_ub);
 int lexls_lsi_batch_solve_adjoint_multi_device(lexls_lsi_batch_t b, const double *d_G, uint32_t ncot, double *d_grad_lb, double *d_grad_ub);
+/* Gradients of the LAST completed run's solutions with respect to ALL constraint data — the matrices A and the bounds — in the caller's layout.
+ * At an instance that ended PROBLEM_SOLVED, x is the basic solution of the equality problem of its final working set W; while W holds, x as a
+ * function of the active rows' A and bounds is the LexLSE solve map of that final problem, so the gradient is lexls_lse_solve_adjoint_matrix's,
+ * applied to the final problem and carried back to the user's constraint order: the final factor is the one lexls_lsi_batch_get_lambda and
+ * lexls_lsi_batch_solve_adjoint keep (shared in every call order: nothing is factorized twice), its x is solved for once per run, the matrix chain
+ * of the equality solver runs on it (N^T g comes out of the chain's own solve_adjoint launch), lsi_adjoint_matrix_scatter_kernel writes the result.
+ * Layouts: g is batch x nVar, dloss/dx in the user's variable order.  grad_data is batch x the per-instance data length, exactly the layout
+ * lexls_lsi_batch_run_device reads: per objective a column-major dim x w block, w = nVar + 2 for a general objective ([A | lb | ub]), w = 2 for
+ * simple bounds ([lb | ub]).  differentiable is one byte per instance (NULL: not wanted); grad_data may not be NULL.
+ * Per constraint of the final working set of a differentiable instance: an active general row gets its row of - y x^T - lambda u^T in the A
+ * columns and its entry of y = M^T g in the lb column (CTR_ACTIVE_LB) or the ub column (CTR_ACTIVE_UB, CTR_ACTIVE_EQ: the bound the final problem
+ * reads, as in lexls_lsi_batch_solve_adjoint), the other bound column 0; an active simple bound of objective 0 gets its slot of N^T g by the same
+ * type rule.  Every row that is not in W, and every row absent under lexls_lsi_batch_set_instance_obj_dims, is exact zeros.  As for the bounds,
+ * this is the gradient of the piece of the map the solve ended on.
+ * Flag rule: differentiable = 1 when the instance's status is PROBLEM_SOLVED and its final equality problem is rank-stable by the rule of
+ * lexls_lse_solve_adjoint_matrix, evaluated by that call's kernel on the final problem's levels, ranks and fixed count; an instance with an empty
+ * working set is differentiable (and all zeros).  Otherwise the flag is 0 and the WHOLE slice of the instance is exact zeros, bound columns
+ * included — the convention of grad_lod.  lexls_lsi_batch_solve_adjoint still gives a solved instance whose final problem is not rank-stable its
+ * bound gradients (they exist for A held fixed).
+ * Mask rule: an instance that the instance mask skips keeps the bits of its slice and of its flag.
+ * lexls_lsi_batch_solve_adjoint_matrix takes and fills host arrays (staged in buffers of the groups); the _device form takes memory of the
+ * batch's device, and no gradient, g or factor passes through host memory.  Both are host-synchronous like lexls_lsi_batch_solve_adjoint(_device).
+ * Tolerance contract; no atomics, the same bits from run to run and from the host and the device form.  What lexls_lsi_batch_get_lambda,
+ * lexls_lsi_batch_solve_adjoint(_multi) and the run's x / active / v answer is unchanged, bit for bit, before and after these calls.
+ * Errors, each returned before any device work and with every output left alone: LEXLS_ERR_INVALID for a null handle, a null g or a null
+ * grad_data; otherwise exactly those of lexls_lsi_batch_solve_adjoint (no completed run, an enqueue_device run waiting for finish; cycling
+ * handling, a regularized run, more than 65535 constraints, constraint data not resident: LEXLS_ERR_UNSUPPORTED). */
+int lexls_lsi_batch_solve_adjoint_matrix(lexls_lsi_batch_t b, const double *h_g, double *h_grad_data, uint8_t *h_differentiable);
+int lexls_lsi_batch_solve_adjoint_matrix_device(lexls_lsi_batch_t b, const double *d_g, double *d_grad_data, uint8_t *d_differentiable);
+/* How often, since the batch was created, the final equality problems of a group were formed and factorized: the stage lexls_lsi_batch_get_lambda,
+ * lexls_lsi_batch_solve_adjoint(_multi) and lexls_lsi_batch_solve_adjoint_matrix share.  It grows by the number of groups at the first of these
+ * calls behind a run and not at all at the later ones, in every call order.  Host bookkeeping only.  LEXLS_ERR_INVALID for a null argument. */
+int lexls_lsi_batch_final_factorizations(lexls_lsi_batch_t b, uint32_t *h_count);
 /* LexLSI::getCyclingCounter() (lexlsi.h, CyclingHandler::get_counter, cycling.h) of every instance of the LAST lexls_lsi_batch_run on this batch:
  * h_counts receives `batch` values, the bounds each instance's cycling handler relaxed (the working-set log's cycling_detected entries, counted).
  * Whatever path served the run: host path, lock-step stages, persistent launch, one by one through the single-problem driver.  All zeros after a

@@ -40,6 +40,7 @@ SYMBOLS = [
     "lexls_lsi_batch_set_instance_mask", "lexls_lsi_batch_set_instance_max_factorizations", "lexls_lsi_batch_set_instance_obj_dims",
     "lexls_lsi_batch_solve_adjoint", "lexls_lsi_batch_solve_adjoint_device",
     "lexls_lsi_batch_solve_adjoint_multi", "lexls_lsi_batch_solve_adjoint_multi_device",
+    "lexls_lsi_batch_solve_adjoint_matrix", "lexls_lsi_batch_solve_adjoint_matrix_device", "lexls_lsi_batch_final_factorizations",
     "lexls_lsi_batch_last_kernel",
 ]
 
@@ -142,6 +143,12 @@ def lib() -> C.CDLL:
         _lib.lexls_lsi_batch_solve_adjoint_multi.argtypes = [C.c_void_p, C.POINTER(C.c_double), C.c_uint32, C.POINTER(C.c_double), C.POINTER(C.c_double)]
         _lib.lexls_lsi_batch_solve_adjoint_multi_device.restype = C.c_int
         _lib.lexls_lsi_batch_solve_adjoint_multi_device.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p]  # d_G, ncot, d_grad_lb, d_grad_ub
+        _lib.lexls_lsi_batch_solve_adjoint_matrix.restype = C.c_int
+        _lib.lexls_lsi_batch_solve_adjoint_matrix.argtypes = [C.c_void_p, C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_uint8)]
+        _lib.lexls_lsi_batch_final_factorizations.restype = C.c_int
+        _lib.lexls_lsi_batch_final_factorizations.argtypes = [C.c_void_p, C.POINTER(C.c_uint32)]
+        _lib.lexls_lsi_batch_solve_adjoint_matrix_device.restype = C.c_int
+        _lib.lexls_lsi_batch_solve_adjoint_matrix_device.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]  # d_g, d_grad_data, d_differentiable
     return _lib
 
 

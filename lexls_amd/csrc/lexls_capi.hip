@@ -1191,6 +1191,16 @@ extern "C"
         return LEXLS_OK;
     }
 
+    int lexls_internal_solve_adjoint_matrix(lexls_lse_t h, const double *d_g, double *d_grad_lod, double *d_grad_fixed, uint8_t *d_differentiable)
+    {
+        if (int rc = need_adjoint_matrix(h, "lexls_internal_solve_adjoint_matrix", d_g)) return rc;
+        if (!d_grad_lod) return fail(LEXLS_ERR_INVALID, "lexls_internal_solve_adjoint_matrix: null d_grad_lod");
+        HIP_TRY(hipSetDevice(h->device));
+        if (int rc = adjoint_matrix_work(h)) return rc;
+        HIP_TRY(launch_solve_adjoint_matrix(h->args(), d_g, d_grad_lod, d_differentiable, h->d_adjA_work, h->max_level_dim, h->stream, &h->last_consumer, d_grad_fixed));
+        return LEXLS_OK;
+    }
+
     int lexls_lse_get_adjoint_matrix(lexls_lse_t h, double *h_grad_lod, uint8_t *h_differentiable)
     {
         CHECK_HANDLE(h);

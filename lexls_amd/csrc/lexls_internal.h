@@ -45,4 +45,7 @@ extern "C"
     /// d_out (batch x nVar, the order of x) = M d_rhs (batch x cap, LOD row order) for x = M b + N x_fixed of the kept, unregularized factor, fixed
     /// values zero (apply_solve_map_kernel, the piece of lexls_lse_solve_adjoint_matrix that has no public entry); both in device memory, enqueued only
     int lexls_internal_apply_solve_map(lexls_lse_t h, const double *d_rhs, double *d_out);
+    /// lexls_lse_solve_adjoint_matrix_device with N^T g as a further output (d_grad_fixed: batch x nVar, fixVariable order, zero from nfixed on; may
+    /// be NULL) from the chain's own solve_adjoint launch: what lexls_lsi_batch_solve_adjoint_matrix routes to the active simple bounds
+    int lexls_internal_solve_adjoint_matrix(lexls_lse_t h, const double *d_g, double *d_grad_lod, double *d_grad_fixed, uint8_t *d_differentiable);
 }

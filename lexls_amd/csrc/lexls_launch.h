@@ -34,10 +34,11 @@ namespace lexls
     /// b for the cotangent d_g (batch x nVar), d_differentiable (batch bytes, may be NULL) = the rank-stability flags; a.x holds the solution of the
     /// kept factor.  Chains, in the stream: launch_solve_adjoint (y), the level search (k*), launch_sensitivity for level k* (lambda; its own rows
     /// are the residual), launch_apply_solve_map (u) and the assembly — everything they write goes to d_work (adjoint_matrix_work_bytes): a.lambda,
-    /// a.v, a.sens, a.maxabs and the activation types stay as they are.  Enqueued only
+    /// a.v, a.sens, a.maxabs and the activation types stay as they are.  d_grad_fixed (batch x nVar, may be NULL: what the public calls pass) =
+    /// N^T g, from the chain's own launch_solve_adjoint (lexls_lsi_batch_solve_adjoint_matrix routes it to the simple bounds).  Enqueued only
     size_t adjoint_matrix_work_bytes(const LseArgs &a);
     hipError_t launch_solve_adjoint_matrix(const LseArgs &a, const double *d_g, double *d_grad_lod, uint8_t *d_differentiable, void *d_work, uint32_t sweep_level_dim_hint,
-                                           hipStream_t s, const char **variant = nullptr);
+                                           hipStream_t s, const char **variant = nullptr, double *d_grad_fixed = nullptr);
     // lqr_generic.hip again — the sensitivity, multiplier and least-norm kernels
     hipError_t launch_sensitivity(const LseArgs &a, const int32_t *d_obj_index, int32_t obj_all, double tolW, double tolC, hipStream_t s, bool scan_up = false,
                                   uint32_t sweep_level_dim_hint = 0, // hint = largest level dimension of the batch (enables the single-sweep kernel)

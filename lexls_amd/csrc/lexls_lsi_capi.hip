@@ -292,6 +292,38 @@ extern "C"
         return lsi_batch_solve_adjoint_multi(b, d_G, ncot, d_grad_lb, d_grad_ub, true);
     }
 
+    /// both forms of the matrix gradient: the refusals of lsi_batch_solve_adjoint, with grad_data the output that may not be null
+    static int lsi_batch_solve_adjoint_matrix(lexls_lsi_batch_t b, const double *g, double *grad_data, uint8_t *differentiable, bool on_device)
+    {
+        return guarded([&]() {
+            const std::string who = on_device ? "lexls_lsi_batch_solve_adjoint_matrix_device" : "lexls_lsi_batch_solve_adjoint_matrix";
+            if (!b) throw Exception(who + ": null handle");
+            if (!g) throw Exception(who + ": null g");
+            if (!grad_data) throw Exception(who + ": null grad_data");
+            b->refuse_pending(who.c_str());
+            return b->solve_adjoint_matrix(g, grad_data, differentiable, on_device);
+        });
+    }
+
+    int lexls_lsi_batch_solve_adjoint_matrix(lexls_lsi_batch_t b, const double *h_g, double *h_grad_data, uint8_t *h_differentiable)
+    {
+        return lsi_batch_solve_adjoint_matrix(b, h_g, h_grad_data, h_differentiable, false);
+    }
+
+    int lexls_lsi_batch_solve_adjoint_matrix_device(lexls_lsi_batch_t b, const double *d_g, double *d_grad_data, uint8_t *d_differentiable)
+    {
+        return lsi_batch_solve_adjoint_matrix(b, d_g, d_grad_data, d_differentiable, true);
+    }
+
+    int lexls_lsi_batch_final_factorizations(lexls_lsi_batch_t b, uint32_t *h_count)
+    {
+        return guarded([&]() {
+            if (!b || !h_count) throw Exception("lexls_lsi_batch_final_factorizations: null argument");
+            *h_count = b->final_formations;
+            return LEXLS_OK;
+        });
+    }
+
     int lexls_lsi_batch_get_cycling_counters(lexls_lsi_batch_t b, uint32_t *h_counts)
     {
         return guarded([&]() {

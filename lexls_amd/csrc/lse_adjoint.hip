@@ -606,7 +606,7 @@ namespace lexls
     }
 
     hipError_t launch_solve_adjoint_matrix(const LseArgs &a, const double *d_g, double *d_grad_lod, uint8_t *d_differentiable, void *d_work, uint32_t sweep_level_dim_hint,
-                                           hipStream_t s, const char **variant)
+                                           hipStream_t s, const char **variant, double *d_grad_fixed)
     {
         if (!d_work || !d_grad_lod) return hipErrorInvalidValue;
         const size_t B = a.batch, n = a.nVar, cap = a.cap;
@@ -616,8 +616,8 @@ namespace lexls
         double *w_u     = w_y + B * cap;
         char *w_sens    = reinterpret_cast<char *>(w_u + B * n);
         int32_t *w_star = reinterpret_cast<int32_t *>(w_sens + ((multipliers_scratch_bytes(a) + 7) & ~(size_t)7));
-        // y = M^T g
-        hipError_t e = launch_solve_adjoint(a, d_g, w_y, nullptr, s);
+        // y = M^T g (and, where the caller wants it, N^T g from the same launch)
+        hipError_t e = launch_solve_adjoint(a, d_g, w_y, d_grad_fixed, s);
         if (e != hipSuccess) return e;
         hipLaunchKernelGGL(adjoint_matrix_level_kernel, dim3((a.batch + 63u) / 64u), dim3(64), 0, s, a, w_star);
         if ((e = hipGetLastError()) != hipSuccess) return e;

@@ -141,6 +141,81 @@ namespace
         }
     }
 
+    /// lexls_lsi_batch_solve_adjoint_matrix for a whole group: the matrix gradient of the final equality problems (launch_solve_adjoint_matrix:
+    /// grad_lod B x (n + 1) x cap in the layout of the problem data — entry (LOD row i, column j) at j * cap + i, column n = y = M^T g — and grad_fixed
+    /// B x n = N^T g in fixVariable order) goes to the caller's constraint data layout: instance b's slice of `out` is per_data doubles, per
+    /// objective o a column-major dim x w block at shape[4 o + 2] (w = n + 2, [A | lb | ub], where shape[4 o + 1] != 0: a general objective; else
+    /// w = 2, [lb | ub]); shape (nObj x 4) = {dim, general, offset of the block, first user row} of every objective.  map, types and meta are
+    /// lsi_adjoint_scatter_kernel's (one upload per run serves both): row r of the final problem (the nf fixed variables first, then the LOD rows)
+    /// is user row pos[r].  An active general row takes its row of grad_lod in the A columns and its y in the lb (CTR_ACTIVE_LB) or ub column
+    /// (CTR_ACTIVE_UB, CTR_ACTIVE_EQ); an active simple bound takes its slot of grad_fixed by the same rule; every other entry is an exact zero.
+    /// differentiable[b] (may be NULL) = lse_flag[b] (the rank-stability flag of the final problem, launch_solve_adjoint_matrix's; NULL: the group
+    /// launched no chain, nobody has an active constraint) && status PROBLEM_SOLVED — where it is 0 the whole slice is exact zeros.
+    /// One workgroup of ADJM_NT threads per instance.  Per objective and tile of ADJM_TILE user rows the inverse of pos is formed in LDS (one word
+    /// per user row: final-problem row + 1 | type << 24; pos is injective: no two rows claim one word, no atomics), then the threads run along the
+    /// tile's entries in the order they are stored — along the user rows of one data column, column after column, consecutive threads at
+    /// consecutive addresses (an objective of at most ADJM_TILE rows is one contiguous run) — so every entry of the slice is stored exactly once,
+    /// zeros and values alike; the reads of grad_lod are the scattered side.
+    /// mask (the group's bytes of lexls_lsi_batch_set_instance_mask, or NULL): slice and flag of a skipped instance stay as they are
+    constexpr uint32_t ADJM_TILE = 1024, ADJM_NT = 256;
+    __global__ __launch_bounds__(ADJM_NT) void lsi_adjoint_matrix_scatter_kernel(const double *__restrict__ grad_lod, const double *__restrict__ grad_fixed,
+                                                                                 const uint8_t *__restrict__ lse_flag, const uint32_t *__restrict__ map,
+                                                                                 const uint8_t *__restrict__ types, const int32_t *__restrict__ meta,
+                                                                                 const uint32_t *__restrict__ shape, uint32_t B, uint32_t nObj, uint32_t total, uint32_t n,
+                                                                                 uint32_t cap, size_t per_data, double *__restrict__ out,
+                                                                                 uint8_t *__restrict__ differentiable, const uint8_t *mask)
+    {
+        __shared__ uint32_t s_row[ADJM_TILE];
+        const uint32_t b = blockIdx.x, tid = threadIdx.x;
+        if (b >= B || lsi_mask_byte(mask, b) == 0) return; // (block-uniform)
+        const uint32_t nf     = min((uint32_t)max(meta[2 * b + 1], 0), n);
+        const uint32_t na_all = min(map[b], min(total, nf + cap));
+        const bool diff       = meta[2 * b] == (int32_t)PROBLEM_SOLVED && (na_all == 0 || (lse_flag && lse_flag[b] != 0)); // (an empty working set: x = 0 whatever the data)
+        const uint32_t na     = diff ? na_all : 0u;
+        if (tid == 0 && differentiable) differentiable[b] = diff ? 1 : 0;
+        const uint32_t *pos = map + B + (size_t)b * total;
+        const uint8_t *ty   = types + (size_t)b * total;
+        const double *gl = grad_lod + (size_t)b * cap * (n + 1), *gf = grad_fixed + (size_t)b * n;
+        double *o_b      = out + (size_t)b * per_data;
+        for (uint32_t o = 0; o < nObj; o++)
+        {
+            const uint32_t dim = shape[4 * o], general = shape[4 * o + 1], first = shape[4 * o + 3];
+            const uint32_t w   = general ? n + 2 : 2u, col_lb = w - 2;
+            double *o_k        = o_b + shape[4 * o + 2];
+            for (uint32_t t0 = 0; t0 < dim; t0 += ADJM_TILE)
+            {
+                const uint32_t len = min(ADJM_TILE, dim - t0), u0 = first + t0;
+                for (uint32_t i = tid; i < len; i += ADJM_NT) s_row[i] = 0u;
+                __syncthreads();
+                for (uint32_t r = tid; r < na; r += ADJM_NT)
+                {
+                    const uint32_t u = pos[r];
+                    if (u < u0 || u - u0 >= len) continue;
+                    s_row[u - u0] = (r + 1) | ((uint32_t)ty[r] << 24);
+                }
+                __syncthreads();
+                for (uint32_t e = tid; e < len * w; e += ADJM_NT)
+                {
+                    const uint32_t j = e / len, i = e - j * len, code = s_row[i];
+                    double val = 0.0;
+                    if (code)
+                    {
+                        const uint32_t r = (code & 0xffffffu) - 1, t = code >> 24;
+                        const bool to_lb = t == CTR_ACTIVE_LB, to_ub = t == CTR_ACTIVE_UB || t == CTR_ACTIVE_EQ;
+                        if (j < col_lb)
+                        {
+                            if (r >= nf && (to_lb || to_ub)) val = gl[(size_t)j * cap + (r - nf)];
+                        }
+                        else if (j == col_lb ? to_lb : to_ub)
+                            val = r < nf ? gf[r] : gl[(size_t)n * cap + (r - nf)];
+                    }
+                    o_k[(size_t)j * dim + t0 + i] = val;
+                }
+                __syncthreads();
+            }
+        }
+    }
+
     /// lexls_lsi_batch_set_instance_regularization with the factors in device memory, for one group: row i of the group's handle array (B x nObjL,
     /// what the regularized kernels read) takes the factors of the caller's row i (B x nObj, the group's first instance in front): LexLSE level k
     /// = objective off + k.  One thread per (instance, level).
@@ -230,9 +305,16 @@ struct lexls_lsi_batch_s
         // lexls_lsi_batch_solve_adjoint_multi: the same five with room for m_room cotangents per instance (ensure_adjoint_multi_bufs)
         double *d_mg = NULL, *d_mgrad_rhs = NULL, *d_mgrad_fixed = NULL, *d_mgrad_lb = NULL, *d_mgrad_ub = NULL;
         uint32_t m_room = 0;
+        // lexls_lsi_batch_solve_adjoint_matrix (ensure_adjoint_matrix_bufs): the matrix gradient of the final equality problems (B x (nVar + 1) x cap)
+        // and their rank-stability flags (B), the objectives' {dim, general, offset, first row} for lsi_adjoint_matrix_scatter_kernel (the same for every
+        // group; uploaded when made); grad_data (B x per_data) and the flags (B) of a host caller, made at the first host call
+        double *d_grad_lod = NULL, *d_mat_out = NULL;
+        uint8_t *d_lse_flag = NULL, *d_mat_flag = NULL;
+        uint32_t *d_shape = NULL;
         ~LambdaBufs()
         {
-            void *dev[] = {d_map, d_out, d_types, d_meta, d_g, d_grad_rhs, d_grad_fixed, d_grad_lb, d_grad_ub, d_mg, d_mgrad_rhs, d_mgrad_fixed, d_mgrad_lb, d_mgrad_ub};
+            void *dev[] = {d_map, d_out, d_types, d_meta, d_g, d_grad_rhs, d_grad_fixed, d_grad_lb, d_grad_ub, d_mg, d_mgrad_rhs, d_mgrad_fixed, d_mgrad_lb, d_mgrad_ub,
+                           d_grad_lod, d_mat_out, d_lse_flag, d_mat_flag, d_shape};
             for (void *q : dev)
                 if (q) (void)hipFree(q);
         }
@@ -240,15 +322,18 @@ struct lexls_lsi_batch_s
     std::vector<std::unique_ptr<LambdaBufs>> lam_bufs;
     // What a group's handle holds of the last run: final_kept — its final equality problems, formed and factorized with the factor kept
     // (ensure_final_factor; get_lambda and solve_adjoint both start there, whichever comes first pays for it), final_any — some instance of the
-    // group has an active constraint (else nothing was factorized), adj_uploaded — map, types and meta of that formation are on the device.
-    // Every new run drops all three (forget_final_factor).
-    std::vector<char> final_kept, final_any, adj_uploaded;
+    // group has an active constraint (else nothing was factorized), adj_uploaded — map, types and meta of that formation are on the device,
+    // final_solved — the handle holds the x of that factor (solve_adjoint_matrix's chain needs it; the stage factorizes only).
+    // Every new run drops all four (forget_final_factor).
+    std::vector<char> final_kept, final_any, adj_uploaded, final_solved;
+    uint32_t final_formations = 0; // since creation: how often ensure_final_factor formed and factorized a group's final problems (lexls_lsi_batch_final_factorizations)
     std::vector<int32_t> ws_status;   // batch: every instance's TerminationStatus of the last run, from its host object or the resident slab
     void forget_final_factor()
     {
         std::fill(final_kept.begin(), final_kept.end(), 0);
         std::fill(final_any.begin(), final_any.end(), 0);
         std::fill(adj_uploaded.begin(), adj_uploaded.end(), 0);
+        std::fill(final_solved.begin(), final_solved.end(), 0);
     }
     std::vector<uint32_t> cycling_count; // batch: LexLSI::getCyclingCounter() of every instance of the last run (lexls_lsi_batch_get_cycling_counters)
     // ---- the working-set log of the last run (lexls_lsi_batch_set_working_set_log; LexLSI::getWorkingSetLog, lexlsi.h:739) ----
@@ -366,7 +451,7 @@ struct lexls_lsi_batch_s
         nGroups = std::min(nGroups, batch);
         gather = per_data < 0x7fffffffull && !sw.host_staging; // (LEXLS_LSI_HOST_STAGING, a diagnostic switch: assemble on the host, stage over PCIe)
         grp.resize(nGroups);
-        final_kept.assign(nGroups, 0), final_any.assign(nGroups, 0), adj_uploaded.assign(nGroups, 0);
+        final_kept.assign(nGroups, 0), final_any.assign(nGroups, 0), adj_uploaded.assign(nGroups, 0), final_solved.assign(nGroups, 0);
         lo.assign(nGroups + 1, 0);
         for (uint32_t g = 0; g < nGroups; g++) lo[g + 1] = lo[g] + batch / nGroups + (g < batch % nGroups ? 1u : 0u);
         for (uint32_t g = 0; g < nGroups; g++)
@@ -541,6 +626,7 @@ struct lexls_lsi_batch_s
         hip_check(lexls_lse_set_kernel_policy(ctx.h, policy));
         hip_check(rc);
         final_kept[g] = 1, final_any[g] = any_active ? 1 : 0;
+        final_formations++;
         return any_active;
     }
 
@@ -581,6 +667,22 @@ struct lexls_lsi_batch_s
         lb.meta[2 * k + 1] = static_cast<int32_t>(nf);
     }
 
+    /// the routes of the scatter kernels (map, types, meta: form_final_problem's and form_adjoint_routes') on the device, in the group's stream —
+    /// once per run, whichever adjoint call comes first (behind ensure_final_factor, which forms the map)
+    void upload_adjoint_routes(uint32_t g, const char *who)
+    {
+        if (adj_uploaded[g]) return;
+        BatchCtx &ctx     = *grp[g];
+        LambdaBufs &lb    = *lam_bufs[g];
+        const size_t rows = (size_t)ctx.B * total;
+        pool->run(ctx.B, [&](uint32_t k) { form_adjoint_routes(g, k, lb); });
+        if (hipMemcpyAsync(lb.d_map, lb.map.data(), 4 * ((size_t)ctx.B + rows), hipMemcpyHostToDevice, ctx.stream) != hipSuccess ||
+            hipMemcpyAsync(lb.d_types, lb.types.data(), rows, hipMemcpyHostToDevice, ctx.stream) != hipSuccess ||
+            hipMemcpyAsync(lb.d_meta, lb.meta.data(), 8 * (size_t)ctx.B, hipMemcpyHostToDevice, ctx.stream) != hipSuccess)
+            throw Exception(std::string(who) + ": hipMemcpyAsync failed (row map)");
+        adj_uploaded[g] = 1;
+    }
+
     /// lexls_lsi_batch_solve_adjoint(_device): d loss / d lb and d loss / d ub of the last run from g = d loss / d x.  Per group, in its stream: the
     /// final equality problems factorized with the factor kept (ensure_final_factor: get_lambda's stage, shared with it), their adjoint
     /// (lexls_lse_solve_adjoint_device on the group's rows of g), lsi_adjoint_scatter_kernel into the user's constraint order.
@@ -603,15 +705,7 @@ struct lexls_lsi_batch_s
             LambdaBufs &lb        = *lam_bufs[g];
             const size_t rows     = (size_t)ctx.B * total, r0 = (size_t)lo[g] * total;
             const bool any_active = ensure_final_factor(g, []() {});
-            if (!adj_uploaded[g])
-            {
-                pool->run(ctx.B, [&](uint32_t k) { form_adjoint_routes(g, k, lb); });
-                if (hipMemcpyAsync(lb.d_map, lb.map.data(), 4 * ((size_t)ctx.B + rows), hipMemcpyHostToDevice, ctx.stream) != hipSuccess ||
-                    hipMemcpyAsync(lb.d_types, lb.types.data(), rows, hipMemcpyHostToDevice, ctx.stream) != hipSuccess ||
-                    hipMemcpyAsync(lb.d_meta, lb.meta.data(), 8 * (size_t)ctx.B, hipMemcpyHostToDevice, ctx.stream) != hipSuccess)
-                    throw Exception(std::string(who) + ": hipMemcpyAsync failed (row map)");
-                adj_uploaded[g] = 1;
-            }
+            upload_adjoint_routes(g, who);
             const double *d_g = g_in + (size_t)lo[g] * nVar;
             double *d_lb = grad_lb ? grad_lb + r0 : NULL, *d_ub = grad_ub ? grad_ub + r0 : NULL;
             if (!on_device)
@@ -679,17 +773,9 @@ struct lexls_lsi_batch_s
         {
             BatchCtx &ctx         = *grp[g];
             LambdaBufs &lb        = *lam_bufs[g];
-            const size_t rows     = (size_t)ctx.B * total, r0 = (size_t)lo[g] * ncot * total, orows = (size_t)ctx.B * ncot * total;
+            const size_t r0 = (size_t)lo[g] * ncot * total, orows = (size_t)ctx.B * ncot * total;
             const bool any_active = ensure_final_factor(g, []() {});
-            if (!adj_uploaded[g])
-            {
-                pool->run(ctx.B, [&](uint32_t k) { form_adjoint_routes(g, k, lb); });
-                if (hipMemcpyAsync(lb.d_map, lb.map.data(), 4 * ((size_t)ctx.B + rows), hipMemcpyHostToDevice, ctx.stream) != hipSuccess ||
-                    hipMemcpyAsync(lb.d_types, lb.types.data(), rows, hipMemcpyHostToDevice, ctx.stream) != hipSuccess ||
-                    hipMemcpyAsync(lb.d_meta, lb.meta.data(), 8 * (size_t)ctx.B, hipMemcpyHostToDevice, ctx.stream) != hipSuccess)
-                    throw Exception(std::string(who) + ": hipMemcpyAsync failed (row map)");
-                adj_uploaded[g] = 1;
-            }
+            upload_adjoint_routes(g, who);
             const double *d_G = G_in + (size_t)lo[g] * ncot * nVar;
             double *d_lb = grad_lb ? grad_lb + r0 : NULL, *d_ub = grad_ub ? grad_ub + r0 : NULL;
             if (!on_device)
@@ -708,6 +794,87 @@ struct lexls_lsi_batch_s
             if (hipGetLastError() != hipSuccess) throw Exception("lsi_adjoint_scatter_multi_kernel launch failed");
             if (!on_device && ((grad_lb && hipMemcpyAsync(grad_lb + r0, lb.d_mgrad_lb, 8 * orows, hipMemcpyDeviceToHost, ctx.stream) != hipSuccess) ||
                                (grad_ub && hipMemcpyAsync(grad_ub + r0, lb.d_mgrad_ub, 8 * orows, hipMemcpyDeviceToHost, ctx.stream) != hipSuccess)))
+                throw Exception(std::string(who) + ": hipMemcpyAsync failed (results)");
+        }
+        for (uint32_t g = 0; g < nGroups; g++)
+            if (hipStreamSynchronize(grp[g]->stream) != hipSuccess) throw Exception(std::string(who) + ": stream synchronisation failed");
+        return LEXLS_OK;
+    }
+
+    /// the groups' buffers of solve_adjoint_matrix, made at the first call; host_form: also the staging buffers of a host caller
+    void ensure_adjoint_matrix_bufs(bool host_form)
+    {
+        ensure_adjoint_bufs();
+        std::vector<uint32_t> shape(4 * (size_t)nObj);
+        for (uint32_t k = 0; k < nObj; k++) shape[4 * k] = dims[k], shape[4 * k + 1] = types[k] == 1 ? 0u : 1u, shape[4 * k + 2] = data_off[k], shape[4 * k + 3] = first[k];
+        for (uint32_t g = 0; g < nGroups; g++)
+        {
+            LambdaBufs &lb  = *lam_bufs[g];
+            const size_t Bg = grp[g]->B, cap = grp[g]->cap;
+            if (!lb.d_shape)
+            {
+                if (hipMalloc((void **)&lb.d_grad_lod, 8 * Bg * (nVar + 1) * (cap ? cap : 1)) != hipSuccess || hipMalloc((void **)&lb.d_lse_flag, Bg) != hipSuccess ||
+                    hipMalloc((void **)&lb.d_shape, 16 * (size_t)nObj) != hipSuccess) // (last: its presence says that the others are there)
+                    throw Exception("hipMalloc failed (lexls_lsi_batch_solve_adjoint_matrix)");
+                if (hipMemcpy(lb.d_shape, shape.data(), 16 * (size_t)nObj, hipMemcpyHostToDevice) != hipSuccess)
+                    throw Exception("hipMemcpy failed (lexls_lsi_batch_solve_adjoint_matrix)");
+            }
+            if (host_form && !lb.d_mat_flag &&
+                (hipMalloc((void **)&lb.d_mat_out, 8 * Bg * (per_data ? per_data : 1)) != hipSuccess || hipMalloc((void **)&lb.d_mat_flag, Bg) != hipSuccess))
+                throw Exception("hipMalloc failed (lexls_lsi_batch_solve_adjoint_matrix)");
+        }
+    }
+
+    /// lexls_lsi_batch_solve_adjoint_matrix(_device): d loss / d (constraint data) of the last run from g = d loss / d x, in the layout
+    /// lexls_lsi_batch_run_device reads, and the instances' differentiable flags (may be NULL).  Per group, in its stream: the final equality
+    /// problems factorized with the factor kept (ensure_final_factor, shared with get_lambda and solve_adjoint), their x once per run
+    /// (lexls_lse_solve on that factor: final_solved), the matrix chain of the equality solver on the group's rows of g (grad_lod, N^T g from the
+    /// chain's own solve_adjoint launch, the rank-stability flags), lsi_adjoint_matrix_scatter_kernel into the caller's layout.
+    /// on_device: g and the outputs are memory of the batch's device; else the host's, staged in the groups' buffers.  Waits for the groups' streams.
+    int solve_adjoint_matrix(const double *g_in, double *grad_data, uint8_t *differentiable, bool on_device)
+    {
+        const char *who = on_device ? "lexls_lsi_batch_solve_adjoint_matrix_device" : "lexls_lsi_batch_solve_adjoint_matrix";
+        if (lam_rc < 0) throw Exception(std::string(who) + ": no completed lexls_lsi_batch_run on this batch");
+        if (lam_rc != LEXLS_OK) // the rules of lexls_lsi_batch_get_lambda, and its reason
+        {
+            lexls_internal_set_error(lam_msg.c_str());
+            return lam_rc;
+        }
+        if (hipSetDevice(device) != hipSuccess) throw Exception(std::string(who) + ": hipSetDevice failed");
+        ensure_adjoint_matrix_bufs(!on_device);
+        for (uint32_t g = 0; g < nGroups; g++)
+        {
+            BatchCtx &ctx         = *grp[g];
+            LambdaBufs &lb        = *lam_bufs[g];
+            const size_t elems    = (size_t)ctx.B * per_data, e0 = (size_t)lo[g] * per_data;
+            const bool any_active = ensure_final_factor(g, []() {});
+            upload_adjoint_routes(g, who);
+            if (any_active && !final_solved[g])
+            {
+                hip_check(lexls_lse_solve(ctx.h)); // the stage factorizes only: the chain wants the x of this factor
+                final_solved[g] = 1;
+            }
+            const double *d_g = g_in + (size_t)lo[g] * nVar;
+            double *d_out     = grad_data + e0;
+            uint8_t *d_flag   = differentiable ? differentiable + lo[g] : NULL;
+            if (!on_device)
+            {
+                // with an instance mask the slice and the flag of a skipped instance keep the caller's bits: they travel to the staging buffers first
+                if (hipMemcpyAsync(lb.d_g, d_g, 8 * (size_t)ctx.B * nVar, hipMemcpyHostToDevice, ctx.stream) != hipSuccess ||
+                    (group_mask(g) && hipMemcpyAsync(lb.d_mat_out, grad_data + e0, 8 * elems, hipMemcpyHostToDevice, ctx.stream) != hipSuccess) ||
+                    (group_mask(g) && differentiable && hipMemcpyAsync(lb.d_mat_flag, differentiable + lo[g], ctx.B, hipMemcpyHostToDevice, ctx.stream) != hipSuccess))
+                    throw Exception(std::string(who) + ": hipMemcpyAsync failed (g)");
+                d_g = lb.d_g, d_out = lb.d_mat_out, d_flag = differentiable ? lb.d_mat_flag : NULL;
+            }
+            // nobody has an active constraint: nothing was factorized, every entry is zero and every solved instance differentiable — the scatter
+            // kernel reads no gradient and no flag of the equality solver
+            if (any_active) hip_check(lexls_internal_solve_adjoint_matrix(ctx.h, d_g, lb.d_grad_lod, lb.d_grad_fixed, lb.d_lse_flag));
+            hipLaunchKernelGGL(lsi_adjoint_matrix_scatter_kernel, dim3(ctx.B), dim3(ADJM_NT), 0, ctx.stream, lb.d_grad_lod, lb.d_grad_fixed,
+                               any_active ? lb.d_lse_flag : (const uint8_t *)NULL, lb.d_map, lb.d_types, lb.d_meta, lb.d_shape, ctx.B, nObj, (uint32_t)total, nVar, ctx.cap,
+                               per_data, d_out, d_flag, group_mask(g));
+            if (hipGetLastError() != hipSuccess) throw Exception("lsi_adjoint_matrix_scatter_kernel launch failed");
+            if (!on_device && (hipMemcpyAsync(grad_data + e0, lb.d_mat_out, 8 * elems, hipMemcpyDeviceToHost, ctx.stream) != hipSuccess ||
+                               (differentiable && hipMemcpyAsync(differentiable + lo[g], lb.d_mat_flag, ctx.B, hipMemcpyDeviceToHost, ctx.stream) != hipSuccess)))
                 throw Exception(std::string(who) + ": hipMemcpyAsync failed (results)");
         }
         for (uint32_t g = 0; g < nGroups; g++)

@@ -281,6 +281,13 @@ class LsiBatch:
         capi.check(capi.lib().lexls_lsi_batch_stats(self._h, _p(st, C.c_int32)))
         return dict(factorize_solve=int(st[0]), sensitivity=int(st[1]), device_step=int(st[2]), groups=int(st[3]))
 
+    def final_factorizations(self) -> int:
+        """lexls_lsi_batch_final_factorizations: how often, since creation, a group's final equality problems were formed and factorized — the
+        stage lambdas(), solve_adjoint*() and solve_adjoint_matrix*() share (once per run and group, whichever call comes first)"""
+        count = C.c_uint32(0)
+        capi.check(capi.lib().lexls_lsi_batch_final_factorizations(self._h, C.byref(count)))
+        return int(count.value)
+
     def last_kernel(self) -> str:
         """the kernel that served the resident active-set iterations of the last run (lexls_lsi_batch_last_kernel): the persistent launch
         ("lsi_fused<...>", with "regularized" for a regularized run), the l-QR kernel of the lock-step stages, or "host" when the run was not
@@ -658,6 +665,49 @@ class LsiBatch:
         else:
             capi.check(capi.lib().lexls_lsi_batch_solve_adjoint_multi_device(self._h, d_G, K, d_lb, d_ub))
         return grad_lb, grad_ub
+
+    @property
+    def per_data(self) -> int:
+        """the length of one instance's constraint data in the flat layout of PackedBatch.data (what run_device reads and solve_adjoint_matrix writes)"""
+        return int(sum(int(d) * (2 if t == 1 else self.nvar + 2) for d, t in zip(self.dims, self.types)))
+
+    def solve_adjoint_matrix(self, g):
+        """lexls_lsi_batch_solve_adjoint_matrix: `g` = dloss/dx of the last run, (batch, nvar).  Returns (grad_data, differentiable): grad_data
+        (batch, per_data) float64 in the layout of PackedBatch.data — dloss/d(A, lb, ub) of every objective (split_grad_data gives the
+        per-objective views) — and differentiable (batch,) uint8: 1 where the instance ended PROBLEM_SOLVED on a rank-stable final equality
+        problem, else 0 with the whole row of grad_data exactly 0 (the bound columns included).  Rows outside the final working set are exactly
+        0.  Raises after the runs lambdas() raises after."""
+        g = np.ascontiguousarray(g, np.float64)
+        if g.shape != (self.batch, self.nvar):
+            raise ValueError(f"solve_adjoint_matrix: g has shape {g.shape}, {(self.batch, self.nvar)} expected")
+        grad_data, differentiable = np.zeros((self.batch, self.per_data)), np.zeros(self.batch, np.uint8)
+        capi.check(capi.lib().lexls_lsi_batch_solve_adjoint_matrix(self._h, _p(g, C.c_double), _p(grad_data, C.c_double), _p(differentiable, C.c_uint8)))
+        return grad_data, differentiable
+
+    def solve_adjoint_matrix_device(self, g, grad_data=None, differentiable=None):
+        """lexls_lsi_batch_solve_adjoint_matrix_device: solve_adjoint_matrix() on torch tensors of the batch's device — `g` float64 (batch, nvar),
+        `grad_data` float64 (batch, per_data), `differentiable` uint8 (batch,), contiguous; an output that is not given is allocated (zeroed).
+        Returns (grad_data, differentiable).  Nothing of them passes through host memory.  Under an instance mask the row and the flag of a
+        skipped instance keep their bits: pass the tensors that hold them.  The call waits for the device, like run_device()."""
+        import torch
+        d_g = self._device_array("g", g, torch.float64, (self.batch, self.nvar), optional=False)
+        dev = torch.device("cuda", self.device)
+        if grad_data is None:
+            grad_data = torch.zeros((self.batch, self.per_data), dtype=torch.float64, device=dev)
+        if differentiable is None:
+            differentiable = torch.zeros((self.batch,), dtype=torch.uint8, device=dev)
+        d_out = self._device_array("grad_data", grad_data, torch.float64, (self.batch, self.per_data), optional=False)
+        d_flag = self._device_array("differentiable", differentiable, torch.uint8, (self.batch,), optional=False)
+        torch.cuda.synchronize(dev)  # g (and the zeroed outputs) are complete before the library's own streams read and write them
+        capi.check(capi.lib().lexls_lsi_batch_solve_adjoint_matrix_device(self._h, d_g, d_out, d_flag))
+        return grad_data, differentiable
+
+    def split_grad_data(self, row):
+        """one instance's row of grad_data (or of the data itself) as the list of per-objective dict(A=, lb=, ub=) (simple bounds: lb, ub): the
+        inverse of flatten(), by unflatten()"""
+        row = row.detach().cpu().numpy() if hasattr(row, "detach") else np.asarray(row, float)
+        objs = unflatten(self.nvar, self.dims, self.types, row, var_index=np.zeros(int(self.dims[0]), np.uint32))
+        return [{k: v for k, v in o.items() if k != "var"} for o in objs]
 
     def jacobian_bounds_device(self):
         """(dx_dlb, dx_dub), torch tensors of shape (batch, nvar, total) on the batch's device: d x_i / d lb_r and d x_i / d ub_r of the last run

@@ -13,6 +13,10 @@ batch, with a per-problem flag and zeros for the others.
 problem of the final working set, affine in the active bounds while that set holds.  Forward is LsiBatch.run_device, backward
 LsiBatch.solve_adjoint_device (lexls_lsi_batch_solve_adjoint_device).
 
+``SolveData`` differentiates a LexLSI batch with respect to ALL its constraint data — the matrices A and the bounds, one tensor in the layout of
+LsiBatch.run_device — where the final equality problem of an instance is rank-stable (lexls_lsi_batch_solve_adjoint_matrix_device), with a
+per-instance flag and zeros for the others.
+
 ``jacobian_rhs`` and ``jacobian_bounds`` return the whole Jacobians, dx/db and dx/dlb, dx/dub, from one multi-cotangent pass
 (lexls_lse_solve_adjoint_multi_device: lane = cotangent) instead of nVar backward passes.
 
@@ -102,8 +106,8 @@ def _solve_bounds_class():
         @staticmethod
         def forward(ctx, lb, ub, batch, data, var_index=None, active_guess=None, x0=None, params=None, out=None):
             if data.requires_grad:
-                raise ValueError("SolveBounds: data requires grad, but the solve has no derivatives with respect to A (x is not continuous in A "
-                                 "at rank changes); detach data")
+                raise ValueError("SolveBounds: data requires grad, but the solve has no derivatives with respect to A here (the matrices are held "
+                                 "fixed); detach data, or use solve_data for the gradient with respect to the whole constraint data")
             shape = (batch.batch, batch.total)
             for name, t in (("lb", lb), ("ub", ub)):
                 if tuple(t.shape) != shape or t.dtype != torch.float64 or t.device != data.device:
@@ -130,6 +134,55 @@ def _solve_bounds_class():
 
     _SOLVE_BOUNDS = SolveBounds
     return SolveBounds
+
+
+_SOLVE_DATA = None
+
+
+def _solve_data_class():
+    global _SOLVE_DATA
+    if _SOLVE_DATA is not None:
+        return _SOLVE_DATA
+    import torch
+    from torch.autograd.function import once_differentiable
+
+    class SolveData(torch.autograd.Function):
+        """x = SolveData.apply(data, batch, var_index, active_guess, x0, params, out): data (batch, per-instance data) float64 on the device in the
+        layout of LsiBatch.run_device — the matrices and the bounds of every objective; batch an LsiBatch; var_index / active_guess / x0 as for
+        run_device (or None), params a dict of its keyword parameters (or None), out a dict that receives run_device's result (or None).
+        Forward: run_device on a copy of data (kept for the backward pass); x (batch, nVar) comes back.  Backward: solve_adjoint_matrix_device —
+        grad_data, one tensor for A, lb and ub: the gradient of the piece of the map the solve ended on.  An instance that did not end
+        PROBLEM_SOLVED, or whose final equality problem is not rank-stable, has a zero row, and `batch.differentiable` — a (batch,) uint8 device
+        tensor set by backward — is 0 there.  The backward pass reads the state the forward run left in `batch`; when the batch has run again
+        in between, the forward run is repeated from the saved data first."""
+
+        @staticmethod
+        def forward(ctx, data, batch, var_index=None, active_guess=None, x0=None, params=None, out=None):
+            shape = (batch.batch, batch.per_data)
+            if tuple(data.shape) != shape or data.dtype != torch.float64 or not data.is_cuda:
+                raise ValueError(f"SolveData: data must be a float64 device tensor of shape {shape}")
+            params = dict(params or {})
+            data0 = data.detach().clone().contiguous()
+            r = batch.run_device(data0, var_index=var_index, active_guess=active_guess, x0=x0, **params)
+            if out is not None:
+                out.update(r)
+            ctx.batch, ctx.serial = batch, batch._run_serial
+            ctx.rerun = (data0, var_index, active_guess, x0, params)
+            return r["x"]
+
+        @staticmethod
+        @once_differentiable
+        def backward(ctx, grad_x):
+            batch = ctx.batch
+            if batch._run_serial != ctx.serial:  # another run has replaced the state this pass reads: the same run again
+                data0, var_index, active_guess, x0, params = ctx.rerun
+                batch.run_device(data0, var_index=var_index, active_guess=active_guess, x0=x0, **params)
+                ctx.serial = batch._run_serial
+            grad_data, batch.differentiable = batch.solve_adjoint_matrix_device(grad_x.contiguous())
+            return grad_data, None, None, None, None, None, None
+
+    _SOLVE_DATA = SolveData
+    return SolveData
 
 
 _SOLVE_LOD = None
@@ -189,6 +242,8 @@ def __getattr__(name):
         return _solve_lod_class()
     if name == "SolveBounds":
         return _solve_bounds_class()
+    if name == "SolveData":
+        return _solve_data_class()
     raise AttributeError(f"module {__name__!r} has no attribute {name!r}")
 
 
@@ -207,6 +262,13 @@ def solve_bounds(lb, ub, batch, data, var_index=None, active_guess=None, x0=None
     """SolveBounds.apply(lb, ub, batch, data, var_index, active_guess, x0, params, out): the solutions of a LexLSI batch, differentiable in the
     bounds.  `params`: the keyword parameters of LsiBatch.run_device; `out`: a dict that receives its result ("x", "info", "active", "v")."""
     return _solve_bounds_class().apply(lb, ub, batch, data, var_index, active_guess, x0, params, out)
+
+
+def solve_data(batch, data, var_index=None, active_guess=None, x0=None, out=None, **params):
+    """SolveData.apply(data, batch, var_index, active_guess, x0, params, out): the solutions of a LexLSI batch, differentiable in the whole
+    constraint data (A, lb and ub of every objective) where the final equality problems are rank-stable; the flags are left in
+    `batch.differentiable` by the backward pass.  `params`: the keyword parameters of LsiBatch.run_device; `out`: a dict that receives its result."""
+    return _solve_data_class().apply(data, batch, var_index, active_guess, x0, params, out)
 
 
 def jacobian_rhs(lse):
