@@ -230,11 +230,28 @@ int lexls_lse_get_multipliers(lexls_lse_t h, double *h_L);
  * the handle's stream and makes no host-synchronising call; d_g has to be complete in stream order.
  * Errors, each returned before any device work and with every output left alone: LEXLS_ERR_INVALID for a null handle or a null g (or a
  * null d_grad_rhs); LEXLS_ERR_INVALID when there is no kept factor (an x-only solve, keep_factor = 0, or a tolerance-contract kernel leaves
- * none); LEXLS_ERR_UNSUPPORTED when the factorization ran with regularization_type != 0 (the damping rewrites the right-hand side).
- * Kernel variant: "solve_adjoint<64>" (lexls_lse_last_consumer_kernel). */
+ * none); LEXLS_ERR_UNSUPPORTED when the factorization ran with regularization_type != 0 and the damped solve is not an affine map of the
+ * right-hand side: the CG types 2 and 6 (CGLS from x = 0 with a fixed iteration count), the experimental type 7, and any type with
+ * variable_regularization_factor != 0 (the factor then depends on the right-hand side); the message names the condition.
+ * After lexls_lse_set_adjoint_regularized(h, 1) — off by default, so that a caller who takes LEXLS_ERR_UNSUPPORTED after a regularized
+ * factorization as the sign to differentiate some other way keeps getting it — regularized factorizations of type 1 (TIKHONOV), 3 (R),
+ * 4 (R_NO_Z), 5 (RT_NO_Z), 8 (TIKHONOV_2) and 9 (TEST) with variable_regularization_factor == 0 ARE served: their damping is a routine of the level's R and T, the accumulated null-space basis and the
+ * factor alone, so with A and the regularization factors held fixed x = M_reg b + N_reg x_fixed is still exactly affine, and the calls return
+ * M_reg^T g and N_reg^T g.  The factors are held fixed as A is (those the factorization ran with, shared or per problem, are read from the
+ * handle); no gradient with respect to the factors is returned.  They are read from the handle's device array AT THE TIME OF THE ADJOINT CALL:
+ * lexls_lse_set_regularization drops the kept factor, so the public setters cannot change them under a factor, but a caller who writes into that
+ * array in place (through lexls_lse_device_ptr, or the per-instance device rows of a LexLSI batch) between the factorization and the adjoint gets the adjoint of the
+ * rewritten factors, and no error is raised.  Where the hbm variant serves the shape, the first lexls_lse_solve_adjoint(_device) call on the
+ * handle allocates its work buffer (a hipMalloc: that one call of the device form is not enqueue-only).
+ * Kernel variant (lexls_lse_last_consumer_kernel): "solve_adjoint<64>" without regularization; "solve_adjoint_reg<64,lds>" or
+ * "solve_adjoint_reg<64,hbm>" for a served regularized factor — the rebuilt basis, the level's normal equations and the per-level snapshots of
+ * the basis in LDS, or in a work buffer of the handle where they exceed one workgroup's 160 KiB (decided from nVar, cap and nObj alone). */
 int lexls_lse_solve_adjoint(lexls_lse_t h, const double *h_g);
 int lexls_lse_get_adjoint(lexls_lse_t h, double *h_grad_rhs, double *h_grad_fixed);
 int lexls_lse_solve_adjoint_device(lexls_lse_t h, const double *d_g, double *d_grad_rhs, double *d_grad_fixed);
+/* on != 0: the three calls above serve damped factorizations as their comment says; 0 (the default): LEXLS_ERR_UNSUPPORTED after every
+ * regularized factorization.  Takes effect at the next call; the kept factor stays valid.  LEXLS_ERR_INVALID for a null handle. */
+int lexls_lse_set_adjoint_regularized(lexls_lse_t h, int on);
 
 /* The same adjoint for MANY cotangents per problem in one pass over the kept factor: ncot vector-Jacobian products, the Jacobian dx/db with the
  * identity as cotangents (ncot = nVar), batched gradients.  One wavefront serves a problem and a tile of up to 64 cotangents, lane = cotangent.
@@ -251,7 +268,7 @@ int lexls_lse_solve_adjoint_device(lexls_lse_t h, const double *d_g, double *d_g
  * lexls_lse_solve_adjoint (the summation order differs): against that call, and against any reference, the contract is the tolerance one.
  * Errors, each returned before any device work and with every output left alone: LEXLS_ERR_INVALID for a null handle, a null G or a null
  * d_grad_rhs; LEXLS_ERR_INVALID for ncot == 0; LEXLS_ERR_INVALID when there is no kept factor; LEXLS_ERR_UNSUPPORTED when the factorization
- * ran with regularization_type != 0.
+ * ran with regularization_type != 0 (every type: the single-cotangent call lexls_lse_solve_adjoint serves types 1, 3, 4, 5, 8 and 9 once switched on).
  * Kernel variant (lexls_lse_last_consumer_kernel), decided on the host from nVar and cap alone: "solve_adjoint_multi<64,staged>" — the
  * per-lane state and the staged factor fit one workgroup's 160 KiB of LDS; "solve_adjoint_multi<64,hbm>" — the state alone fits, the factor
  * is read where it is kept; "solve_adjoint<64> x K" — neither: the single-cotangent kernel once per cotangent. */
@@ -291,7 +308,8 @@ int lexls_lse_solve_adjoint_multi_device(lexls_lse_t h, const double *d_G, uint3
  * Tolerance contract (no reference arithmetic exists); no atomics, the same bits from run to run and from the host and the device form.
  * Errors, each returned before any device work and with every output left alone: LEXLS_ERR_INVALID for a null handle, a null g or a null
  * d_grad_lod; LEXLS_ERR_INVALID when there is no kept factor; LEXLS_ERR_INVALID when no x belongs to the current factor (lexls_lse_factorize
- * alone, or a least-norm solve); LEXLS_ERR_UNSUPPORTED when the factorization ran with regularization_type != 0.
+ * alone, or a least-norm solve); LEXLS_ERR_UNSUPPORTED when the factorization ran with regularization_type != 0
+ * (every type: the single-cotangent call lexls_lse_solve_adjoint serves types 1, 3, 4, 5, 8 and 9, for the right-hand sides only).
  * Kernel variant: "solve_adjoint_matrix<64>" (lexls_lse_last_consumer_kernel). */
 int lexls_lse_solve_adjoint_matrix(lexls_lse_t h, const double *h_g);
 int lexls_lse_get_adjoint_matrix(lexls_lse_t h, double *h_grad_lod, uint8_t *h_differentiable);
@@ -772,6 +790,17 @@ int lexls_lsi_batch_get_lambda(lexls_lsi_batch_t b, double *h_lambda);
  * handling, a regularized run, more than 65535 constraints, constraint data not resident), with that call's reason in lexls_last_error(). */
 int lexls_lsi_batch_solve_adjoint(lexls_lsi_batch_t b, const double *h_g, double *h_grad_lb, double *h_grad_ub);
 int lexls_lsi_batch_solve_adjoint_device(lexls_lsi_batch_t b, const double *d_g, double *d_grad_lb, double *d_grad_ub);
+/* on != 0: from the NEXT run on, the two calls above also answer after a regularized run that was resident on the device, of regularization
+ * type 1, 3, 4, 5, 8 or 9 with variable_regularization_factor == 0: the final equality problems are then factorized WITH the run's regularization
+ * (type, and the shared or per-instance factors, host or device rows, whichever the run used: they are on the groups' handles since the run),
+ * once per run as before, and the gradient is that of the damped solve, the factors held fixed as the matrices are.  Per-instance factors in
+ * device memory are read again at that factorization: rows rewritten in place between the run and the first adjoint call give the adjoint of the
+ * rewritten factors, and no error is raised.  0 (the default, so that a caller who takes LEXLS_ERR_UNSUPPORTED after a regularized run as the
+ * sign to differentiate some other way keeps getting it): every regularized run is refused.  Types 2, 6, 7, a variable factor, cycling handling,
+ * a run that was not resident and more than 65535 constraints stay LEXLS_ERR_UNSUPPORTED, and so do lexls_lsi_batch_get_lambda,
+ * lexls_lsi_batch_solve_adjoint_multi* and lexls_lsi_batch_solve_adjoint_matrix* after every regularized run.
+ * Errors: LEXLS_ERR_INVALID for a null handle, and between lexls_lsi_batch_enqueue_device and lexls_lsi_batch_finish. */
+int lexls_lsi_batch_set_adjoint_regularized(lexls_lsi_batch_t b, int on);
 /* lexls_lsi_batch_solve_adjoint(_device) for ncot cotangents per instance in one pass: lexls_lse_solve_adjoint_multi_device on the final factor
  * (shared with lexls_lsi_batch_get_lambda and lexls_lsi_batch_solve_adjoint in every call order: nothing is factorized twice), then
  * lsi_adjoint_scatter_multi_kernel.  Layouts: G is batch x ncot x nVar; grad_lb and grad_ub are batch x ncot x sum(dims), row c of instance b

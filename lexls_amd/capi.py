@@ -28,7 +28,7 @@ SYMBOLS = [
     "lexls_lse_set_accuracy_guard", "lexls_lse_get_accuracy",
     "lexls_lse_set_prefix_reuse", "lexls_lse_prefix_reuse_ready", "lexls_lse_set_resume_levels",
     "lexls_lsi_solve", "lexls_lsi_solve_dat", "lexls_lsi_batch_solve",
-    "lexls_lse_multipliers", "lexls_lse_get_multipliers", "lexls_lse_solve_adjoint", "lexls_lse_get_adjoint", "lexls_lse_solve_adjoint_device",
+    "lexls_lse_multipliers", "lexls_lse_get_multipliers", "lexls_lse_solve_adjoint", "lexls_lse_set_adjoint_regularized", "lexls_lse_get_adjoint", "lexls_lse_solve_adjoint_device",
     "lexls_lse_solve_adjoint_multi", "lexls_lse_get_adjoint_multi", "lexls_lse_solve_adjoint_multi_device",
     "lexls_lse_solve_adjoint_matrix", "lexls_lse_get_adjoint_matrix", "lexls_lse_solve_adjoint_matrix_device",
     "lexls_lsi_batch_get_lambda", "lexls_lsi_batch_solve_ex2",
@@ -38,7 +38,7 @@ SYMBOLS = [
     "lexls_lsi_batch_set_working_set_log", "lexls_lsi_batch_get_working_set_log", "lexls_lsi_batch_working_set_log_device",
     "lexls_lsi_batch_enqueue_device", "lexls_lsi_batch_finish",
     "lexls_lsi_batch_set_instance_mask", "lexls_lsi_batch_set_instance_max_factorizations", "lexls_lsi_batch_set_instance_obj_dims",
-    "lexls_lsi_batch_solve_adjoint", "lexls_lsi_batch_solve_adjoint_device",
+    "lexls_lsi_batch_solve_adjoint", "lexls_lsi_batch_solve_adjoint_device", "lexls_lsi_batch_set_adjoint_regularized",
     "lexls_lsi_batch_solve_adjoint_multi", "lexls_lsi_batch_solve_adjoint_multi_device",
     "lexls_lsi_batch_solve_adjoint_matrix", "lexls_lsi_batch_solve_adjoint_matrix_device", "lexls_lsi_batch_final_factorizations",
     "lexls_lsi_batch_last_kernel",
@@ -115,6 +115,10 @@ def lib() -> C.CDLL:
         _lib.lexls_lsi_batch_get_working_set_log.argtypes = [C.c_void_p, C.POINTER(C.c_int32), C.POINTER(C.c_double), C.POINTER(C.c_uint32)]
         _lib.lexls_lsi_batch_working_set_log_device.restype = C.c_int
         _lib.lexls_lsi_batch_working_set_log_device.argtypes = [C.c_void_p, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), C.POINTER(C.c_void_p)]
+        _lib.lexls_lsi_batch_set_adjoint_regularized.restype = C.c_int
+        _lib.lexls_lsi_batch_set_adjoint_regularized.argtypes = [C.c_void_p, C.c_int]
+        _lib.lexls_lse_set_adjoint_regularized.restype = C.c_int
+        _lib.lexls_lse_set_adjoint_regularized.argtypes = [C.c_void_p, C.c_int]
         _lib.lexls_lse_solve_adjoint.restype = C.c_int
         _lib.lexls_lse_solve_adjoint.argtypes = [C.c_void_p, C.POINTER(C.c_double)]
         _lib.lexls_lse_get_adjoint.restype = C.c_int

@@ -92,8 +92,10 @@ struct lexls_lse_s
     uint64_t mult_epoch   = 0;      // factor_epoch the multipliers belong to
     bool mult_swept       = false;
     // lexls_lse_solve_adjoint: g (batch x nVar), grad_rhs (batch x cap), grad_fixed (batch x nVar), allocated at its first call
-    double *d_adj_g = nullptr, *d_adj_rhs = nullptr, *d_adj_fixed = nullptr;
+    // d_adj_work: the matrices of the regularized adjoint where they do not fit in LDS (adjoint_reg_work_bytes)
+    double *d_adj_g = nullptr, *d_adj_rhs = nullptr, *d_adj_fixed = nullptr, *d_adj_work = nullptr;
     bool adj_valid     = false;
+    bool adj_regularized = false; // lexls_lse_set_adjoint_regularized: the single-cotangent calls serve damped factorizations (off: UNSUPPORTED, as before)
     uint64_t adj_epoch = 0; // factor_epoch the gradients belong to
     // lexls_lse_solve_adjoint_multi: G (batch x ncot x nVar), grad_rhs (batch x ncot x cap), grad_fixed (batch x ncot x nVar) of a host caller, made
     // for the largest ncot so far; d_adjm_work: the buffers of the per-cotangent form (launch_solve_adjoint_multi), made at the first call that needs them
@@ -303,7 +305,7 @@ extern "C"
         void *ptrs[] = {h->d_in_owned, h->d_fac, h->d_hh, h->d_v, h->d_lambda, h->d_scratch, h->d_perm, h->d_rank, h->d_fcol, h->d_round_in, h->d_round_out,
                         h->d_large_state, h->d_large_ws, h->d_norms, h->d_cdata, h->d_reg_factor, h->d_reg_scratch, h->d_reg_mu, h->d_resume_level, h->d_resume_state,
                         h->d_guard_est, h->d_guard_status, h->d_guard_ind, h->d_mult, h->d_mult_scratch, h->d_wrong_sign, h->d_adj_g, h->d_adj_rhs, h->d_adj_fixed,
-                        h->d_adjm_G, h->d_adjm_rhs, h->d_adjm_fixed, h->d_adjm_work, h->d_adjA_g, h->d_adjA_grad, h->d_adjA_flag, h->d_adjA_work};
+                        h->d_adj_work, h->d_adjm_G, h->d_adjm_rhs, h->d_adjm_fixed, h->d_adjm_work, h->d_adjA_g, h->d_adjA_grad, h->d_adjA_flag, h->d_adjA_work};
         for (void *p : ptrs)
             if (p) (void)hipFree(p);
         if (h->h_dims_pinned) (void)hipHostFree(h->h_dims_pinned);
@@ -1033,28 +1035,56 @@ extern "C"
         return LEXLS_OK;
     }
 
-    /// what every form of the adjoint checks before any device work: a kept, unregularized factor
-    static int need_adjoint_factor(lexls_lse_t h, const char *who, const void *g)
+    /// what every form of the adjoint checks before any device work: a kept factor — unregularized, or (single_cotangent: lexls_lse_solve_adjoint
+    /// and its device form, once lexls_lse_set_adjoint_regularized switched it on) regularized with one of the types whose damped solve is an
+    /// affine map of the kept factor, the factors constant
+    static int need_adjoint_factor(lexls_lse_t h, const char *who, const void *g, bool single_cotangent = false)
     {
         CHECK_HANDLE(h);
         if (!g) return fail(LEXLS_ERR_INVALID, std::string(who) + ": null g");
         if (int rc = need_factor(h, who)) return rc;
-        if (h->reg_type != 0)
-            return fail(LEXLS_ERR_UNSUPPORTED, std::string(who) + ": the factorization ran with regularization_type != 0 (the damping rewrites the right-hand side: x is not the affine map of the kept factor)");
+        if (h->reg_type == 0) return LEXLS_OK;
+        if (!single_cotangent)
+            return fail(LEXLS_ERR_UNSUPPORTED, std::string(who) + ": the factorization ran with regularization_type != 0 (lexls_lse_solve_adjoint, the single-cotangent call, serves "
+                                                                  "regularization types 1, 3, 4, 5, 8 and 9; this call serves none)");
+        if (!h->adj_regularized)
+            return fail(LEXLS_ERR_UNSUPPORTED, std::string(who) + ": the factorization ran with regularization_type != 0 and the adjoint of damped solves is not switched on "
+                                                                  "for this handle (lexls_lse_set_adjoint_regularized; it serves regularization types 1, 3, 4, 5, 8 and 9)");
+        if (!adjoint_reg_serves(h->reg_type))
+            return fail(LEXLS_ERR_UNSUPPORTED, std::string(who) + ": regularization_type " + std::to_string(h->reg_type) +
+                                                   " is not an affine map of the right-hand side (the CG types 2 and 6 iterate from x = 0, type 7 is experimental); served: 1, 3, 4, 5, 8, 9");
+        if (h->reg_variable != 0.0)
+            return fail(LEXLS_ERR_UNSUPPORTED, std::string(who) + ": variable_regularization_factor != 0 under regularization_type " + std::to_string(h->reg_type) +
+                                                   " (the factor depends on the right-hand side: x is not an affine map of it)");
+        return LEXLS_OK;
+    }
+    /// the work buffer of the regularized adjoint where its matrices do not fit in LDS (adjoint_reg_work_bytes), made at the first call that needs it
+    static int adjoint_reg_work(lexls_lse_t h)
+    {
+        const size_t bytes = adjoint_reg_work_bytes(h->args());
+        if (bytes && !h->d_adj_work) HIP_TRY(hipMalloc((void **)&h->d_adj_work, bytes));
+        return LEXLS_OK;
+    }
+
+    int lexls_lse_set_adjoint_regularized(lexls_lse_t h, int on)
+    {
+        CHECK_HANDLE(h);
+        h->adj_regularized = on != 0;
         return LEXLS_OK;
     }
 
     int lexls_lse_solve_adjoint(lexls_lse_t h, const double *h_g)
     {
-        if (int rc = need_adjoint_factor(h, "lexls_lse_solve_adjoint", h_g)) return rc;
+        if (int rc = need_adjoint_factor(h, "lexls_lse_solve_adjoint", h_g, true)) return rc;
         HIP_TRY(hipSetDevice(h->device));
         const size_t B = h->batch, n = h->nVar, cap = h->cap;
         if (!h->d_adj_g) HIP_TRY(hipMalloc((void **)&h->d_adj_g, 8 * B * n));
         if (!h->d_adj_rhs) HIP_TRY(hipMalloc((void **)&h->d_adj_rhs, 8 * B * cap));
         if (!h->d_adj_fixed) HIP_TRY(hipMalloc((void **)&h->d_adj_fixed, 8 * B * n));
+        if (int rc = adjoint_reg_work(h)) return rc;
         HIP_TRY(hipMemcpyAsync(h->d_adj_g, h_g, 8 * B * n, hipMemcpyHostToDevice, h->stream));
         if (!h->deferred_sync) HIP_TRY(hipStreamSynchronize(h->stream)); // h_g may be reused by the caller
-        HIP_TRY(launch_solve_adjoint(h->args(), h->d_adj_g, h->d_adj_rhs, h->d_adj_fixed, h->stream, &h->last_consumer));
+        HIP_TRY(launch_solve_adjoint(h->args(), h->d_adj_g, h->d_adj_rhs, h->d_adj_fixed, h->stream, &h->last_consumer, h->d_adj_work));
         h->adj_valid = true;
         h->adj_epoch = h->factor_epoch;
         return LEXLS_OK;
@@ -1062,10 +1092,11 @@ extern "C"
 
     int lexls_lse_solve_adjoint_device(lexls_lse_t h, const double *d_g, double *d_grad_rhs, double *d_grad_fixed)
     {
-        if (int rc = need_adjoint_factor(h, "lexls_lse_solve_adjoint_device", d_g)) return rc;
+        if (int rc = need_adjoint_factor(h, "lexls_lse_solve_adjoint_device", d_g, true)) return rc;
         if (!d_grad_rhs) return fail(LEXLS_ERR_INVALID, "lexls_lse_solve_adjoint_device: null d_grad_rhs");
         HIP_TRY(hipSetDevice(h->device));
-        HIP_TRY(launch_solve_adjoint(h->args(), d_g, d_grad_rhs, d_grad_fixed, h->stream, &h->last_consumer));
+        if (int rc = adjoint_reg_work(h)) return rc;
+        HIP_TRY(launch_solve_adjoint(h->args(), d_g, d_grad_rhs, d_grad_fixed, h->stream, &h->last_consumer, h->d_adj_work));
         return LEXLS_OK;
     }
 

@@ -16,9 +16,15 @@ namespace lexls
     hipError_t launch_solve_generic(const LseArgs &a, hipStream_t s, bool reciprocal_diagonal = false, const char **variant = nullptr);
     hipError_t launch_residual(const LseArgs &a, hipStream_t s, const char **variant = nullptr);
     // lse_adjoint.hip — the adjoint family of the kept factor (the view and the trust rule its kernels share: lse_kept_factor.h)
+    /// the work buffer launch_solve_adjoint needs for a regularized factor whose matrices do not fit in LDS (0 where none is needed)
+    size_t adjoint_reg_work_bytes(const LseArgs &a);
     /// lexls_lse_solve_adjoint: d_grad_rhs (batch x cap) = M^T g, d_grad_fixed (batch x nVar, may be NULL) = N^T g for x = M b + N x_fixed of the
-    /// kept factor; d_g is batch x nVar in the order of x.  One wavefront per problem, enqueued only
-    hipError_t launch_solve_adjoint(const LseArgs &a, const double *d_g, double *d_grad_rhs, double *d_grad_fixed, hipStream_t s, const char **variant = nullptr);
+    /// kept factor; d_g is batch x nVar in the order of x.  One wavefront per problem, enqueued only.  a.reg_type == 0: solve_adjoint_kernel.  A
+    /// regularized factor of type 1, 3, 4, 5, 8 or 9 with a.reg_variable == 0 (anything else: hipErrorInvalidValue): solve_adjoint_reg_kernel, M and
+    /// N those of the damped solve with a.reg_factor (read at the time of this call) held fixed; its matrices sit in LDS when adjoint_reg_in_lds
+    /// (lexls_lds.h) says so, else in d_work (adjoint_reg_work_bytes)
+    hipError_t launch_solve_adjoint(const LseArgs &a, const double *d_g, double *d_grad_rhs, double *d_grad_fixed, hipStream_t s, const char **variant = nullptr,
+                                    double *d_work = nullptr);
     /// lexls_lse_solve_adjoint_multi: ncot cotangents per problem in one pass, d_G batch x ncot x nVar, d_grad_rhs batch x ncot x cap, d_grad_fixed
     /// batch x ncot x nVar (may be NULL).  The form follows from the shape (adjoint_multi_form, lexls_lds.h): lane = cotangent with the factor staged
     /// in LDS, the same with the factor read where it is kept, or launch_solve_adjoint once per cotangent through d_work (adjoint_multi_work_bytes,

@@ -236,5 +236,29 @@ namespace lexls
         return f == AdjointMultiForm::staged ? "solve_adjoint_multi<64,staged>" : f == AdjointMultiForm::hbm ? "solve_adjoint_multi<64,hbm>" : "solve_adjoint<64> x K";
     }
 
+    // ---- solve_adjoint_reg (lse_adjoint.hip): the adjoint of a regularized solve ----
+    /// the doubles of one problem's matrices: the null-space basis rebuilt from the factor (nVar x nVar), the work matrix D of the level's normal
+    /// equations (order <= nVar), the snapshots of the basis at entry to each level — a level of non-zero rank keeps m0 x (nVar - Fc) entries,
+    /// m0 <= Fc, so at most nVar^2 / 4, and there are at most min(nObj, nVar) such levels
+    constexpr size_t adjoint_reg_matrix_doubles(uint32_t nVar, uint32_t nObj) // (constexpr: the kernel lays its work buffer out by it)
+    {
+        const size_t n = nVar, levels = nObj < nVar ? nObj : nVar;
+        return 2 * n * n + levels * ((n / 2) * ((n + 1) / 2));
+    }
+    /// the vectors every form keeps in LDS: g in factor column order, the cotangent r of the basis' right-hand-side column, the level's
+    /// right-hand side of D (nVar doubles each), the gradient of the right-hand side (cap doubles), the transpositions (nVar words);
+    /// in_lds: + the matrices
+    inline size_t adjoint_reg_lds_bytes(uint32_t nVar, uint32_t cap, uint32_t nObj, bool in_lds)
+    {
+        const size_t b = 8 * (3 * (size_t)nVar + cap + (in_lds ? adjoint_reg_matrix_doubles(nVar, nObj) : 0)) + 4 * (size_t)nVar;
+        return (b + 15) & ~(size_t)15;
+    }
+    /// the fit rule of the regularized lexls_lse_solve_adjoint, decided from the shape alone: the matrices in one workgroup's LDS, else in a
+    /// work buffer of the call (adjoint_reg_matrix_doubles per problem)
+    inline bool adjoint_reg_in_lds(uint32_t nVar, uint32_t cap, uint32_t nObj) { return adjoint_reg_lds_bytes(nVar, cap, nObj, true) <= kMaxLdsBytes; }
+    inline const char *adjoint_reg_form_name(bool in_lds) { return in_lds ? "solve_adjoint_reg<64,lds>" : "solve_adjoint_reg<64,hbm>"; }
+    /// the regularization types whose damped solve is an affine map of the kept factor (TIKHONOV, R, R_NO_Z, RT_NO_Z, TIKHONOV_2, TEST)
+    inline bool adjoint_reg_serves(uint32_t reg_type) { return reg_type == 1 || reg_type == 3 || reg_type == 4 || reg_type == 5 || reg_type == 8 || reg_type == 9; }
+
     // ---- lqr_large (lqr_large.hip): lqr_large_plan.h ----
 } // namespace lexls

@@ -152,6 +152,384 @@ namespace lexls
             }
         }
 
+        /// LL^T of the lower triangle of D (order N, leading dimension ldd) in place, then D z = d in place, by one wavefront.  N <= 64: the panel
+        /// scheme of reg_cholesky_solve_wave (lexls_regularize.h) — lane i owns row i, 16 columns at a time in registers, a finished column's
+        /// entries reach the other lanes by v_readlane —; beyond that the lanes take every 64th row, column by column.  Ends in a barrier
+        __device__ __forceinline__ void adjoint_cholesky_solve(double *D, uint32_t ldd, double *d, uint32_t N, uint32_t lane)
+        {
+            auto dd = [&](uint32_t i, uint32_t j) __attribute__((always_inline)) -> double & { return D[i + (size_t)j * ldd]; };
+            if (N <= 64)
+            {
+                constexpr int PB = 16;
+                const bool on    = lane < N;
+                double row[PB];
+                for (uint32_t c0 = 0; c0 < N; c0 += PB)
+                {
+#pragma unroll
+                    for (int jj = 0; jj < PB; jj++) row[jj] = (on && c0 + jj <= lane && c0 + jj < N) ? dd(lane, c0 + jj) : 0.0;
+                    for (uint32_t k = 0; k < c0; k++)
+                    {
+                        const double lik = (on && lane >= c0) ? dd(lane, k) : 0.0;
+#pragma unroll
+                        for (int jj = 0; jj < PB; jj++) row[jj] = dfma(-lik, rdlane(lik, (int)(c0 + jj) & 63), row[jj]);
+                    }
+#pragma unroll
+                    for (int kk = 0; kk < PB; kk++)
+                        if (c0 + kk < N) // uniform
+                        {
+                            const double lkk = sqrt(rdlane(row[kk], (int)(c0 + kk)));
+                            const double lik = (lane == c0 + kk) ? lkk : row[kk] / lkk; // (zeros above the diagonal and beyond N)
+                            row[kk]          = lik;
+#pragma unroll
+                            for (int jj = kk + 1; jj < PB; jj++) row[jj] = dfma(-lik, rdlane(lik, (int)(c0 + jj) & 63), row[jj]);
+                        }
+#pragma unroll
+                    for (int jj = 0; jj < PB; jj++)
+                        if (on && c0 + jj <= lane && c0 + jj < N) dd(lane, c0 + jj) = row[jj];
+                }
+                double di = on ? d[lane] : 0.0;
+                for (uint32_t c0 = 0; c0 < N; c0 += PB)
+                {
+#pragma unroll
+                    for (int jj = 0; jj < PB; jj++) row[jj] = (on && c0 + jj <= lane && c0 + jj < N) ? dd(lane, c0 + jj) : 0.0;
+#pragma unroll
+                    for (int jj = 0; jj < PB; jj++)
+                        if (c0 + jj < N)
+                        {
+                            const uint32_t j = c0 + jj;
+                            const double yj  = rdlane(di, (int)j) / rdlane(row[jj], (int)j);
+                            di               = (lane == j) ? yj : (lane > j ? dfma(-row[jj], yj, di) : di);
+                        }
+                }
+                __syncthreads(); // the factor's columns are read across lanes from here on
+                for (uint32_t c0 = ((N - 1) / PB) * PB; N > 0; c0 -= PB)
+                {
+#pragma unroll
+                    for (int jj = 0; jj < PB; jj++) row[jj] = (on && c0 + jj >= lane && c0 + jj < N) ? dd(c0 + jj, lane) : 0.0;
+#pragma unroll
+                    for (int jj = PB - 1; jj >= 0; jj--)
+                        if (c0 + jj < N)
+                        {
+                            const uint32_t j = c0 + jj;
+                            const double zj  = rdlane(di, (int)j) / rdlane(row[jj], (int)j);
+                            di               = (lane == j) ? zj : (lane < j ? dfma(-row[jj], zj, di) : di);
+                        }
+                    if (c0 == 0) break;
+                }
+                if (on) d[lane] = di;
+                __syncthreads();
+                return;
+            }
+            for (uint32_t j = 0; j < N; j++) // left-looking, column by column
+            {
+                double sjj = dd(j, j); // (every lane for itself: the same chain, the same bits)
+                for (uint32_t k = 0; k < j; k++) sjj = dfma(-dd(j, k), dd(j, k), sjj);
+                const double ljj = sqrt(sjj);
+                __syncthreads(); // (every lane has read the diagonal entry)
+                if (lane == 0) dd(j, j) = ljj;
+                for (uint32_t i = j + 1 + lane; i < N; i += 64)
+                {
+                    double t = dd(i, j);
+                    for (uint32_t k = 0; k < j; k++) t = dfma(-dd(i, k), dd(j, k), t);
+                    dd(i, j) = t / ljj;
+                }
+                __syncthreads();
+            }
+            for (uint32_t j = 0; j < N; j++)
+            {
+                const double yj = d[j] / dd(j, j);
+                __syncthreads();
+                if (lane == 0) d[j] = yj;
+                for (uint32_t i = j + 1 + lane; i < N; i += 64) d[i] = dfma(-dd(i, j), yj, d[i]);
+                __syncthreads();
+            }
+            for (uint32_t j = N; j--;)
+            {
+                const double zj = d[j] / dd(j, j);
+                __syncthreads();
+                if (lane == 0) d[j] = zj;
+                for (uint32_t i = lane; i < j; i += 64) d[i] = dfma(-dd(j, i), zj, d[i]);
+                __syncthreads();
+            }
+        }
+
+        /// solve_adjoint_kernel for a factor of a REGULARIZED factorize() of type 1, 3, 4, 5, 8 or 9 with a constant factor per level (f = a.reg_factor,
+        /// held fixed as A is): x = M_reg b + N_reg x_fixed is still affine, and grad_rhs = M_reg^T g, grad_fixed = N_reg^T g.  Forward, level k
+        /// replaces its right-hand side y (rows F .. F + rank, behind the reflectors) by y' = P y + Q r when rank > 0 and |f| >= 1e-15 (P = W D^-1 W^T,
+        /// Q = mu W D^-1 U^T, D = W^T W + mu U^T U + mu I, mu = f^2; W = [R | T] for types 1, 5, 8 and R for 3, 4; U = the rows of the null-space
+        /// basis NS above the level's columns at entry to the level, absent for 4 and 5; type 9: y' = f y), and types 1, 3, 8 then give NS's right-hand
+        /// side column r new rows and subtract L y' from it, L = [U_R ; I] R^-1.  Steps (a), (b), (d) and the Gauss and reflector parts of (c) are
+        /// solve_adjoint_kernel's.  New: the rebuild of NS from the factor (types 1, 3, 8; A side only — in the factor's FINAL column order: the
+        /// forward column swaps act on NS and on T alike, and D, W t and U t do not change under a common permutation of their columns) with a
+        /// snapshot of U per level; in (c) behind the transposed Gauss step, with r~ the cotangent of r (zero behind the last level):
+        ///     types 1, 3, 8:  y~' -= R^-T (U_R^T r~[0, m0) + r~[m0, m0 + rank)), the level's own rows of r~ dropped
+        ///     damped:         t = D^-1 W^T y~',  y~ = W t,  r~[0, m0) += mu U t           (type 9: y~ = f y~')
+        /// IN_LDS: NS, D and the snapshots in LDS (adjoint_reg_lds_bytes), else in `work` (adjoint_reg_matrix_doubles per problem).  No atomics
+        template <int NT, bool IN_LDS>
+        __global__ __launch_bounds__(NT) void solve_adjoint_reg_kernel(LseArgs a, const double *__restrict__ g, double *__restrict__ grad_rhs, double *__restrict__ grad_fixed,
+                                                                       double *__restrict__ work)
+        {
+            static_assert(NT == 64, "one wavefront per problem: the reductions are wavefront sums");
+            constexpr uint32_t AU = 4;
+            extern __shared__ double smem[];
+            const uint32_t b = blockIdx.x, lane = threadIdx.x;
+            const KeptFactor kf = kept_factor_of(a, b);
+            const uint32_t n = kf.n, cap = kf.cap, nObj = kf.nObj, nf = kf.nf, T = kf.T, M = kf.M;
+            const double *__restrict__ W = kf.W, *hh = kf.hh;
+            const uint32_t *dims = kf.dims;
+            const uint32_t type  = a.reg_type;
+            const bool accum = type == 1 || type == 3 || type == 8; // the types that accumulate NS (and read it)
+            const bool wideW = type == 1 || type == 5 || type == 8; // W = [R | T] (else R)
+            const double *fac = a.reg_factor + (size_t)b * nObj;
+            double *gh = smem, *cb = gh + n, *rbar = cb + cap, *dv = rbar + n;
+            uint32_t *perm_l = reinterpret_cast<uint32_t *>(dv + n);
+            // (n words behind 3 n + cap doubles: the matrices start on an 8-byte boundary at perm_l + 2 ((n + 1) / 2))
+            double *mat = IN_LDS ? reinterpret_cast<double *>(perm_l + 2 * ((n + 1) / 2)) : work + (size_t)b * adjoint_reg_matrix_doubles(n, nObj);
+            double *NS = mat, *D = NS + (size_t)n * n, *SN = D + (size_t)n * n;
+            auto ns = [&](uint32_t i, uint32_t j) __attribute__((always_inline)) -> double & { return NS[i + (size_t)j * n]; };
+            auto w  = [&](uint32_t i, uint32_t j) __attribute__((always_inline)) -> double { return W[i + (size_t)j * cap]; };
+
+            // ---- (a) gh = P^T g ----
+            for (uint32_t i = lane; i < n; i += NT) perm_l[i] = a.perm[(size_t)b * n + i];
+            for (uint32_t i = lane; i < cap; i += NT) cb[i] = 0.0;
+            for (uint32_t i = lane; i < n; i += NT) rbar[i] = 0.0;
+            if (accum)
+                for (uint32_t i = lane; i < n * n; i += NT) NS[i] = 0.0;
+            __syncthreads();
+            for (uint32_t i = lane; i < n; i += NT)
+            {
+                const uint32_t p = position_after_transpositions(perm_l, T, i);
+                if (p < n) gh[p] = g[(size_t)b * n + i];
+            }
+            __syncthreads();
+
+            // ---- (b) the reverse of solve(), levels ascending (solve() reads the regularized right-hand sides: cb rows F .. F + rank are y~') ----
+            uint32_t F = 0;
+            for (uint32_t k = 0; k < nObj; k++)
+            {
+                const uint32_t dim = dims[k];
+                const auto [rank, Fc] = kf.level(k, dim);
+                if (rank > 0 && F + dim <= M)
+                {
+                    double *y = cb + F;
+                    for (uint32_t c0 = Fc; c0 < T; c0 += AU)
+                    {
+                        double wv[AU], dg[AU];
+#pragma unroll
+                        for (uint32_t u = 0; u < AU; u++)
+                        {
+                            const uint32_t c = c0 + u, j = c - Fc;
+                            const uint32_t len = c < T ? (j < rank ? j : rank) : 0;
+                            wv[u] = lane < len ? W[F + lane + (size_t)c * cap] : 0.0;
+                            dg[u] = (c < T && j < rank) ? W[F + j + (size_t)c * cap] : 1.0;
+                        }
+#pragma unroll
+                        for (uint32_t u = 0; u < AU; u++)
+                        {
+                            const uint32_t c = c0 + u, j = c - Fc;
+                            if (c >= T) break;
+                            const uint32_t len = j < rank ? j : rank;
+                            const double s     = column_dot(W + F + (size_t)c * cap, y, len, wv[u], lane);
+                            if (j < rank)
+                            {
+                                if (lane == 0) y[j] = (gh[c] - s) / dg[u];
+                                __syncthreads();
+                            }
+                            else if (lane == 0)
+                                gh[c] -= s;
+                        }
+                    }
+                    __syncthreads();
+                }
+                F += dim;
+            }
+
+            // ---- the rebuild of NS, levels ascending (reg_accumulate_nullspace without the right-hand-side column), U snapshot first ----
+            uint32_t soff = 0; // doubles of SN in use
+            if (accum)
+            {
+                F = 0;
+                for (uint32_t k = 0; k < nObj; k++)
+                {
+                    const uint32_t dim = dims[k];
+                    const auto [rank, Fc] = kf.level(k, dim);
+                    if (rank > 0 && F + dim <= M)
+                    {
+                        const uint32_t m0 = Fc > nf ? Fc - nf : 0, rows = m0 + rank, RC = n - Fc - rank, wc = wideW ? n - Fc : rank;
+                        for (uint32_t e = lane; e < m0 * wc; e += NT) SN[soff + e] = ns(e % m0, Fc + e / m0);
+                        soff += m0 * wc;
+                        for (uint32_t e = lane; e < rank * rank; e += NT) ns(m0 + e % rank, Fc + e / rank) = (e % rank == e / rank) ? 1.0 : 0.0;
+                        __syncthreads();
+                        for (uint32_t i = lane; i < rows; i += NT) // Left <- Left R^-1, a row per lane
+                            for (uint32_t p = 0; p < rank; p++)
+                            {
+                                double sv = ns(i, Fc + p);
+                                for (uint32_t q = 0; q < p; q++) sv = dfma(-ns(i, Fc + q), w(F + q, Fc + p), sv);
+                                ns(i, Fc + p) = sv / w(F + p, Fc + p);
+                            }
+                        __syncthreads();
+                        for (uint32_t e = lane; e < rows * RC; e += NT) // Trailing -= Left T
+                        {
+                            const uint32_t i = e % rows, c = Fc + rank + e / rows;
+                            double t = ns(i, c);
+                            for (uint32_t p = 0; p < rank; p++) t = dfma(-ns(i, Fc + p), w(F + p, c), t);
+                            ns(i, c) = t;
+                        }
+                        __syncthreads();
+                    }
+                    F += dim;
+                }
+            }
+
+            // ---- (c) the reverse of factorize()'s right-hand-side updates, levels descending ----
+            uint32_t Fend = 0;
+            for (uint32_t k = 0; k < nObj; k++) Fend += dims[k];
+            for (uint32_t k = nObj; k--;)
+            {
+                const uint32_t dim = dims[k];
+                F                  = Fend - dim;
+                Fend               = F;
+                const auto [rank, Fc] = kf.level(k, dim);
+                if (rank == 0 || F + dim > M) continue;
+                const uint32_t Fn = F + dim;
+                if (k + 1 < nObj && Fn < M)
+                {
+                    for (uint32_t p0 = 0; p0 < rank; p0 += AU)
+                    {
+                        double wv[AU], s[AU];
+#pragma unroll
+                        for (uint32_t u = 0; u < AU; u++) wv[u] = (p0 + u < rank && lane < M - Fn) ? W[Fn + lane + (size_t)(Fc + p0 + u) * cap] : 0.0;
+#pragma unroll
+                        for (uint32_t u = 0; u < AU; u++) s[u] = p0 + u < rank ? column_dot(W + Fn + (size_t)(Fc + p0 + u) * cap, cb + Fn, M - Fn, wv[u], lane) : 0.0;
+#pragma unroll
+                        for (uint32_t u = 0; u < AU; u++)
+                            if (lane == 0 && p0 + u < rank) cb[F + p0 + u] -= s[u];
+                    }
+                    __syncthreads();
+                }
+                const uint32_t m0 = Fc > nf ? Fc - nf : 0, N = wideW ? n - Fc : rank;
+                const double *U   = SN; // the level's snapshot: m0 x N, leading dimension m0
+                double *yb        = cb + F;
+                if (accum)
+                {
+                    soff -= m0 * N;
+                    U = SN + soff;
+                    // y~' -= R^-T (U_R^T r~[0, m0) + r~[m0, m0 + rank)): the sum into dv, then R^T column by column as step (b) does
+                    for (uint32_t j = lane; j < rank; j += NT)
+                    {
+                        double acc = rbar[m0 + j];
+                        for (uint32_t s = 0; s < m0; s++) acc = dfma(U[s + (size_t)j * m0], rbar[s], acc);
+                        dv[j] = acc;
+                    }
+                    __syncthreads();
+                    for (uint32_t j = 0; j < rank; j++)
+                    {
+                        const double *col = W + F + (size_t)(Fc + j) * cap;
+                        const double s    = column_dot(col, dv, j, lane < j ? col[lane] : 0.0, lane);
+                        const double vj   = (dv[j] - s) / col[j];
+                        __syncthreads(); // (every lane has read dv[j])
+                        if (lane == 0)
+                        {
+                            dv[j] = vj;
+                            yb[j] -= vj;
+                        }
+                        __syncthreads();
+                    }
+                }
+                const double f = fac[k];
+                if (!(fabs(f - 0.0) < 1e-15)) // the gate of regularize_level
+                {
+                    if (type == 9)
+                    {
+                        for (uint32_t i = lane; i < rank; i += NT) yb[i] *= f;
+                    }
+                    else
+                    {
+                        const double mu = f * f;
+                        // D = W^T W + mu U^T U + mu I (lower triangle), dv = W^T y~'; column c of W has min(c + 1, rank) rows
+                        for (uint32_t e = lane; e < N * N; e += NT)
+                        {
+                            const uint32_t i = e % N, j = e / N;
+                            if (i < j) continue;
+                            const uint32_t len = j < rank ? j + 1 : rank;
+                            double acc = 0.0;
+                            for (uint32_t r = 0; r < len; r++) acc = dfma(w(F + r, Fc + i), w(F + r, Fc + j), acc);
+                            if (accum)
+                            {
+                                double up = 0.0;
+                                for (uint32_t s = 0; s < m0; s++) up = dfma(U[s + (size_t)i * m0], U[s + (size_t)j * m0], up);
+                                acc = dfma(mu, up, acc);
+                            }
+                            D[i + (size_t)j * n] = i == j ? acc + mu : acc;
+                        }
+                        for (uint32_t c = lane; c < N; c += NT)
+                        {
+                            const uint32_t len = c < rank ? c + 1 : rank;
+                            double acc = 0.0;
+                            for (uint32_t r = 0; r < len; r++) acc = dfma(w(F + r, Fc + c), yb[r], acc);
+                            dv[c] = acc;
+                        }
+                        __syncthreads();
+                        adjoint_cholesky_solve(D, n, dv, N, lane); // dv = t
+                        for (uint32_t i = lane; i < rank; i += NT) // y~ = W t
+                        {
+                            double acc = 0.0;
+                            for (uint32_t c = i; c < N; c++) acc = dfma(w(F + i, Fc + c), dv[c], acc);
+                            yb[i] = acc;
+                        }
+                        if (accum)
+                            for (uint32_t s = lane; s < m0; s += NT) // r~ += mu U t
+                            {
+                                double acc = 0.0;
+                                for (uint32_t c = 0; c < N; c++) acc = dfma(U[s + (size_t)c * m0], dv[c], acc);
+                                rbar[s] = dfma(mu, acc, rbar[s]);
+                            }
+                    }
+                    __syncthreads();
+                }
+                // the reflectors on rows F + j .. F + dim - 1, AU at a time
+                for (uint32_t j0 = rank; j0 > 0; j0 -= (j0 < AU ? j0 : AU))
+                {
+                    double e[AU], tau[AU];
+#pragma unroll
+                    for (uint32_t u = 0; u < AU; u++)
+                    {
+                        const bool on = u < j0;
+                        const uint32_t j = on ? j0 - 1 - u : 0;
+                        tau[u] = on ? hh[F + j] : 0.0;
+                        e[u]   = (on && lane + 1 < dim - j) ? W[F + j + 1 + lane + (size_t)(Fc + j) * cap] : 0.0;
+                    }
+#pragma unroll
+                    for (uint32_t u = 0; u < AU; u++)
+                    {
+                        if (u >= j0) break;
+                        const uint32_t j = j0 - 1 - u;
+                        apply_stored_reflector(W + F + j + 1 + (size_t)(Fc + j) * cap, cb + F + j, dim - j, tau[u], e[u], lane);
+                    }
+                }
+            }
+            __syncthreads();
+
+            // ---- (d) grad_rhs = cb; grad_fixed_j = gh_j - (column j of the fixed variables)^T cb (the fixed values enter the right-hand side
+            // in front of every level, and r through y' alone) ----
+            for (uint32_t i = lane; i < cap; i += NT) grad_rhs[(size_t)b * cap + i] = cb[i];
+            if (grad_fixed)
+            {
+                for (uint32_t j0 = 0; j0 < nf; j0 += AU)
+                {
+                    double wv[AU], s[AU];
+#pragma unroll
+                    for (uint32_t u = 0; u < AU; u++) wv[u] = (j0 + u < nf && lane < M) ? W[lane + (size_t)(j0 + u) * cap] : 0.0;
+#pragma unroll
+                    for (uint32_t u = 0; u < AU; u++) s[u] = j0 + u < nf ? column_dot(W + (size_t)(j0 + u) * cap, cb, M, wv[u], lane) : 0.0;
+#pragma unroll
+                    for (uint32_t u = 0; u < AU; u++)
+                        if (lane == 0 && j0 + u < nf) grad_fixed[(size_t)b * n + j0 + u] = gh[j0 + u] - s[u];
+                }
+                for (uint32_t j = nf + lane; j < n; j += NT) grad_fixed[(size_t)b * n + j] = 0.0;
+            }
+        }
+
         // gradient with respect to the matrix (lexls_lse_solve_adjoint_matrix): the solve map on a new right-hand side, the assembly
         /// out = M rhs for x = M b + N x_fixed of the kept factor (fixed values zero): the transpose of solve_adjoint_kernel's steps (c), (b), (a),
         /// in that order.  One wavefront per problem, the factor read where it is kept, the right-hand side a cap-vector in LDS.  Every pass has
@@ -523,8 +901,28 @@ namespace lexls
         }
     } // namespace
 
-    hipError_t launch_solve_adjoint(const LseArgs &a, const double *d_g, double *d_grad_rhs, double *d_grad_fixed, hipStream_t s, const char **variant)
+    size_t adjoint_reg_work_bytes(const LseArgs &a)
     {
+        return (a.reg_type == 0 || adjoint_reg_in_lds(a.nVar, a.cap, a.nObj)) ? 0 : 8 * (size_t)a.batch * adjoint_reg_matrix_doubles(a.nVar, a.nObj);
+    }
+
+    hipError_t launch_solve_adjoint(const LseArgs &a, const double *d_g, double *d_grad_rhs, double *d_grad_fixed, hipStream_t s, const char **variant, double *d_work)
+    {
+        if (a.reg_type != 0) // a regularized factor: the served types with a constant factor per level (the callers refuse the others)
+        {
+            if (!adjoint_reg_serves(a.reg_type) || a.reg_variable != 0.0 || !a.reg_factor) return hipErrorInvalidValue;
+            const bool in_lds = adjoint_reg_in_lds(a.nVar, a.cap, a.nObj);
+            const size_t lds  = adjoint_reg_lds_bytes(a.nVar, a.cap, a.nObj, in_lds);
+            if (lds > kMaxLdsBytes || (!in_lds && !d_work)) return hipErrorInvalidValue;
+            hipError_t e = in_lds ? set_lds(solve_adjoint_reg_kernel<64, true>, lds) : set_lds(solve_adjoint_reg_kernel<64, false>, lds);
+            if (e != hipSuccess) return e;
+            if (in_lds)
+                hipLaunchKernelGGL((solve_adjoint_reg_kernel<64, true>), dim3(a.batch), dim3(64), lds, s, a, d_g, d_grad_rhs, d_grad_fixed, nullptr);
+            else
+                hipLaunchKernelGGL((solve_adjoint_reg_kernel<64, false>), dim3(a.batch), dim3(64), lds, s, a, d_g, d_grad_rhs, d_grad_fixed, d_work);
+            if (variant) *variant = adjoint_reg_form_name(in_lds);
+            return hipGetLastError();
+        }
         const size_t lds = adjoint_lds_bytes(a.nVar, a.cap);
         if (lds > kMaxLdsBytes) return hipErrorInvalidValue;
         hipError_t e = set_lds(solve_adjoint_kernel<64>, lds);

@@ -326,6 +326,12 @@ struct lexls_lsi_batch_s
     // final_solved — the handle holds the x of that factor (solve_adjoint_matrix's chain needs it; the stage factorizes only).
     // Every new run drops all four (forget_final_factor).
     std::vector<char> final_kept, final_any, adj_uploaded, final_solved;
+    // lexls_lsi_batch_set_adjoint_regularized: solve_adjoint answers after a resident regularized run of type 1, 3, 4, 5, 8, 9 (constant factors); off:
+    // the rules of get_lambda, as before.  adj_rc / adj_msg: what solve_adjoint answers after the last run (set_adjoint_rule); final_reg: the run was such
+    // a run, and ensure_final_factor leaves the run's regularization on the groups' handles
+    bool adj_regularized = false, final_reg = false;
+    int adj_rc           = -1;
+    std::string adj_msg;
     uint32_t final_formations = 0; // since creation: how often ensure_final_factor formed and factorized a group's final problems (lexls_lsi_batch_final_factorizations)
     std::vector<int32_t> ws_status;   // batch: every instance's TerminationStatus of the last run, from its host object or the resident slab
     void forget_final_factor()
@@ -584,6 +590,33 @@ struct lexls_lsi_batch_s
         ctx.objidx[k] = -1;
     }
 
+    /// what lexls_lsi_batch_solve_adjoint(_device) answers after the run that just set lam_rc / lam_msg: get_lambda's answer, except that a regularized
+    /// run is served when the batch asked for it (adj_regularized), the run was resident (its regularization is on the groups' handles), its type is
+    /// one of the six whose damped solve is affine in the bounds and its variable factor is zero
+    void set_adjoint_rule(const ParametersLexLSI &par, bool resident)
+    {
+        adj_rc = lam_rc, adj_msg = lam_msg, final_reg = false;
+        const int t = static_cast<int>(par.regularization_type);
+        if (lam_rc != LEXLS_ERR_UNSUPPORTED || t == 0 || par.cycling_handling_enabled || !gather || total > 65535) return;
+        const std::string who = "lexls_lsi_batch_solve_adjoint: ";
+        if (!adj_regularized)
+            adj_msg = lam_msg + " (lexls_lsi_batch_set_adjoint_regularized, called before the run, lets lexls_lsi_batch_solve_adjoint serve regularization types 1, 3, 4, 5, 8, 9)";
+        else if (!resident)
+            adj_msg = who + "not available after a regularized run that was not resident on the device";
+        else if (!(t == 1 || t == 3 || t == 4 || t == 5 || t == 8 || t == 9))
+            adj_msg = who + "not available after a regularized run of regularization_type " + std::to_string(t) + " (served: 1, 3, 4, 5, 8, 9)";
+        else if (par.variable_regularization_factor != 0.0)
+            adj_msg = who + "not available after a regularized run with variable_regularization_factor != 0";
+        else
+            adj_rc = LEXLS_OK, adj_msg.clear(), final_reg = true;
+    }
+    /// the fixed bounds of a device run are fetched for get_lambda and for the adjoint calls
+    bool needs_final_problem(const ParametersLexLSI &par) const
+    {
+        const int t = static_cast<int>(par.regularization_type);
+        return lam_rc_after(par) == LEXLS_OK || (adj_regularized && t != 0 && !par.cycling_handling_enabled && gather && total <= 65535);
+    }
+
     /// the groups' buffers of get_lambda, made at the first call that needs them
     void ensure_lambda_bufs()
     {
@@ -618,7 +651,12 @@ struct lexls_lsi_batch_s
         // the equality solver's parameters of this run, whichever path it took (the one-by-one path of a non-resident deactivate_first_wrong_sign run never set
         // them on these handles; an earlier run of the batch object may have left a regularization there): lam_rc == LEXLS_OK means unregularized
         hip_check(lexls_lse_set_tolerance(ctx.h, lam_tol));
-        hip_check(lexls_lse_set_regularization(ctx.h, 0, NULL, 0, 0.0));
+        // (final_reg: a resident regularized run whose adjoint is served — its type and factors, shared or per instance, host or device rows, are on the
+        // handle since the run's upload_regularization_block and stay there: the final factor is the damped one)
+        if (final_reg)
+            hip_check(lexls_lse_set_adjoint_regularized(ctx.h, 1));
+        else
+            hip_check(lexls_lse_set_regularization(ctx.h, 0, NULL, 0, 0.0));
         const int policy = lexls_internal_kernel_policy(ctx.h);
         hip_check(lexls_lse_set_kernel_policy(ctx.h, 5)); // bit-exact kernels whatever the shape (the factor of the reference's getLambda)
         int rc = any_active ? lexls_internal_upload_round_trusted(ctx.h, ctx.in_block.data(), 1) : LEXLS_OK;
@@ -692,10 +730,10 @@ struct lexls_lsi_batch_s
     {
         const char *who = on_device ? "lexls_lsi_batch_solve_adjoint_device" : "lexls_lsi_batch_solve_adjoint";
         if (lam_rc < 0) throw Exception(std::string(who) + ": no completed lexls_lsi_batch_run on this batch");
-        if (lam_rc != LEXLS_OK) // the rules of lexls_lsi_batch_get_lambda, and its reason
+        if (adj_rc != LEXLS_OK) // the rules of lexls_lsi_batch_get_lambda and its reason, but for the regularized runs set_adjoint_rule serves
         {
-            lexls_internal_set_error(lam_msg.c_str());
-            return lam_rc;
+            lexls_internal_set_error(adj_msg.c_str());
+            return adj_rc;
         }
         if (hipSetDevice(device) != hipSuccess) throw Exception(std::string(who) + ": hipSetDevice failed");
         ensure_adjoint_bufs();
@@ -1183,6 +1221,7 @@ struct lexls_lsi_batch_s
             finish_working_set_log();
             lam_rc  = (off && !h_var_index) ? LEXLS_ERR_INVALID : lam_after;
             lam_msg = lam_rc == LEXLS_ERR_INVALID ? "lexls_lsi_batch_get_lambda: the run had no variable indices" : lam_why;
+            set_adjoint_rule(par, false);
             return;
         }
         // LEXLS_LSI_DEVICE_PHASE1=1: no host objects, phase 1 is device work; so it is with per-instance factors in device memory, which no host
@@ -1193,6 +1232,7 @@ struct lexls_lsi_batch_s
             finish_working_set_log();
             lam_rc  = (off && !h_var_index) ? LEXLS_ERR_INVALID : lam_after;
             lam_msg = lam_rc == LEXLS_ERR_INVALID ? "lexls_lsi_batch_get_lambda: the run had no variable indices" : lam_why;
+            set_adjoint_rule(par, true);
             return;
         }
         r.t_begin = BatchCtx::now();
@@ -1207,6 +1247,7 @@ struct lexls_lsi_batch_s
         report(r);
         lam_rc  = lam_after;
         lam_msg = lam_why;
+        set_adjoint_rule(par, r.resident);
         bool any_left = false;
         for (uint32_t b = 0; b < batch && !any_left; b++) any_left = r.lsi[b] != nullptr;
         if (any_left) pool->run(batch, [&](uint32_t b) { r.lsi[b].reset(); }); // a thousand LexLSI objects (dozens of vectors each): freed in parallel, not serially on return
@@ -1592,7 +1633,7 @@ struct lexls_lsi_batch_s
             more               = more || going[g];
         }
         resident_chunks(r, going, more);
-        const bool keep_fixed_bounds = lam_rc_after(r.par) == LEXLS_OK;
+        const bool keep_fixed_bounds = needs_final_problem(r.par);
         for (uint32_t g = 0; g < nGroups; g++)
         {
             BatchCtx &ctx = *grp[g];
@@ -1646,6 +1687,7 @@ struct lexls_lsi_batch_s
         finish_working_set_log();
         lam_rc  = lam_rc_after(par);
         lam_msg = lam_msg_after_device_run(par);
+        set_adjoint_rule(par, true);
     }
 
     /// the runs lexls_lsi_batch_enqueue_device serves: those of run_device that the persistent launch takes, decided on numbers (every group's handle:
@@ -1751,7 +1793,7 @@ struct lexls_lsi_batch_s
                 throw Exception("copy of the variable indices failed");
             ctx.enqueue_phase1_setup(dev.x0 ? dev.x0 + (size_t)lo[g] * nVar : NULL, dev.active_guess ? dev.active_guess + (size_t)lo[g] * total : NULL, lo[g], max_fact,
                                      dev.v0 ? dev.v0 + (size_t)lo[g] * total : NULL, as.d_fault, group_mask(g), group_limits(g), group_obj_dims(g), p1_hot_word(par));
-            const bool keep_fixed_bounds = lam_rc_after(par) == LEXLS_OK;
+            const bool keep_fixed_bounds = needs_final_problem(par);
             ctx.enqueue_phase1_gate(as.d_fault, max_fact);
             if (par.use_phase1_v0)
                 ctx.enqueue_phase1_v0(max_fact, false);
@@ -1790,7 +1832,7 @@ struct lexls_lsi_batch_s
         const uint32_t fault = as.fault_host[0];
         if (fault != 0xffffffffu) throw Exception("lexls_lsi_batch_run: instance " + std::to_string(fault >> 3) + ": " + p1_fault_text(fault & 7u));
         const ParametersLexLSI &par = as.par;
-        const bool keep_fixed_bounds = lam_rc_after(par) == LEXLS_OK;
+        const bool keep_fixed_bounds = needs_final_problem(par);
         int rounds_fs = 0, rounds_sens = 0, rounds_step = 0;
         for (uint32_t g = 0; g < nGroups; g++)
         {
@@ -1813,6 +1855,7 @@ struct lexls_lsi_batch_s
         wlog_valid = wlog != nullptr;
         lam_rc     = lam_rc_after(par);
         lam_msg    = lam_msg_after_device_run(par);
+        set_adjoint_rule(par, true);
         return LEXLS_OK;
     }
 

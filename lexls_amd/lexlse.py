@@ -282,11 +282,19 @@ class BatchedLexLSE:
         return L
 
     # ---- adjoint of the solve (A held fixed) ------------------------------------------------------
+    def set_adjoint_regularized(self, on: bool = True):
+        """lexls_lse_set_adjoint_regularized: let solve_adjoint and solve_adjoint_device answer after a damped factorization (regularization
+        type 1, 3, 4, 5, 8 or 9 with variable_factor == 0).  Off by default: they then raise LEXLS_ERR_UNSUPPORTED after every regularized
+        factorization, as they always did."""
+        capi.check(capi.lib().lexls_lse_set_adjoint_regularized(self._h, C.c_int(1 if on else 0)))
+
     def solve_adjoint(self, g):
         """lexls_lse_solve_adjoint + lexls_lse_get_adjoint: for fixed A the basic solution is affine in the right-hand sides and the fixed
         values, x = M b + N x_fixed; with g = dloss/dx, (batch, nVar) in the order of get_x(), returns (grad_rhs, grad_fixed) = (M^T g, N^T g)
         as numpy arrays: (batch, cap) in LOD row order (zero behind a problem's own rows) and (batch, nVar), entry j < nfixed the fixed variable
-        of slot j in fixVariable order, zero from nfixed on.  Needs a kept, unregularized factor.  No derivatives with respect to A."""
+        of slot j in fixVariable order, zero from nfixed on.  Needs a kept factor: unregularized, or (after set_adjoint_regularized()) regularized with type 1, 3, 4, 5, 8 or 9 and
+        variable_factor == 0 — then M and N are those of the damped solve, the factors held fixed as A is (no gradient with respect to them);
+        types 2, 6, 7 and a variable factor raise (LEXLS_ERR_UNSUPPORTED).  No derivatives with respect to A."""
         g = np.ascontiguousarray(g, np.float64)
         if g.shape != (self.batch, self.nVar):
             raise ValueError(f"g must have shape {(self.batch, self.nVar)}, got {g.shape}")
@@ -299,7 +307,7 @@ class BatchedLexLSE:
     def solve_adjoint_device(self, g, grad_rhs, grad_fixed=None):
         """lexls_lse_solve_adjoint_device: g (batch, nVar), grad_rhs (batch, cap) and grad_fixed (batch, nVar; None: not wanted) in device memory —
         contiguous float64 torch tensors (anything with data_ptr()) or raw addresses.  Only enqueued in the handle's stream (set_stream): g has
-        to be complete in stream order, nothing is waited for."""
+        to be complete in stream order, nothing is waited for.  Serves the same factors as solve_adjoint (regularization types 1, 3, 4, 5, 8, 9)."""
         def address(name, t, shape):
             if t is None:
                 return None

@@ -546,6 +546,13 @@ class LsiBatch:
         capi.check(capi.lib().lexls_lsi_batch_get_cycling_counters(self._h, _p(counts, C.c_uint32)))
         return counts
 
+    def set_adjoint_regularized(self, on: bool = True):
+        """lexls_lsi_batch_set_adjoint_regularized: from the next run on, solve_adjoint / solve_adjoint_device also answer after a regularized run
+        that was resident on the device, of regularization type 1, 3, 4, 5, 8 or 9 with variable_regularization_factor == 0: the gradient of the
+        damped final equality problem, the factors (shared or per instance) held fixed as the matrices are.  Off by default: every regularized
+        run is refused, as before.  lambdas(), solve_adjoint_multi and solve_adjoint_matrix refuse regularized runs either way."""
+        capi.check(capi.lib().lexls_lsi_batch_set_adjoint_regularized(self._h, C.c_int(1 if on else 0)))
+
     def set_working_set_log(self, max_entries: int):
         """lexls_lsi_batch_set_working_set_log: every later run() / run_device() keeps the working-set log of each instance
         (LexLSI::getWorkingSetLog), up to `max_entries` entries per instance; 0 switches the log off again and frees its buffers"""
@@ -601,7 +608,9 @@ class LsiBatch:
         """lexls_lsi_batch_solve_adjoint: `g` = dloss/dx of the last run, (batch, nvar).  Returns (grad_lb, grad_ub), numpy arrays of shape
         (batch, total) in the constraint order of `active` / `v`: dloss/dlb and dloss/dub with the matrices held fixed.  An active constraint's
         value is in grad_lb (active at its lower bound) or grad_ub (upper bound, equality); everything outside the final working set, and every
-        row of an instance that did not end PROBLEM_SOLVED, is exactly 0.  Raises after the runs lambdas() raises after."""
+        row of an instance that did not end PROBLEM_SOLVED, is exactly 0.  Raises after the runs lambdas() raises after — except, once
+        set_adjoint_regularized() is on, after a resident regularized run of type 1, 3, 4, 5, 8 or 9 with constant factors: then the gradient is
+        that of the damped final problem, the factors held fixed."""
         g = np.ascontiguousarray(g, np.float64)
         if g.shape != (self.batch, self.nvar):
             raise ValueError(f"solve_adjoint: g has shape {g.shape}, {(self.batch, self.nvar)} expected")

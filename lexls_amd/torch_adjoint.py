@@ -3,7 +3,10 @@
 factorize() chooses its pivots and tests the ranks on the columns of A alone, so for fixed A the basic solution is exactly affine in the
 right-hand sides: x = M b (+ N x_fixed).  ``SolveRhs`` solves on the device from torch tensors and, in the backward pass, returns
 M^T (dloss/dx) from one pass over the kept factor (lexls_lse_solve_adjoint_device).  There are no derivatives with respect to A — x is not
-continuous in A where a rank changes — and asking for them raises instead of returning zeros.
+continuous in A where a rank changes — and asking for them raises instead of returning zeros.  A damped solve (regularization type 1, 3, 4, 5, 8
+or 9 with constant factors) is still affine in b with A and the factors held fixed, and ``SolveRhs`` differentiates it the same way once
+the handle's ``set_adjoint_regularized()`` switched that on; the
+factors are constants of the graph.
 
 ``SolveLod`` is the operation that does differentiate with respect to A: it takes the whole problem data (matrices and right-hand sides) as one
 tensor and returns, in the backward pass, the gradient of both (lexls_lse_solve_adjoint_matrix_device) for the rank-stable problems of the
@@ -39,7 +42,10 @@ def _solve_rhs_class():
 
     class SolveRhs(torch.autograd.Function):
         """x = SolveRhs.apply(rhs, lse, lod): rhs (batch, cap) float64 on the device, lse a BatchedLexLSE of that shape (dimensions, fixed
-        variables and tolerance set by the caller; no regularization), lod (batch, nVar + 1, cap) float64 on the same device.  rhs is copied
+        variables, tolerance and regularization set by the caller: none, or, after lse.set_adjoint_regularized(), type 1, 3, 4, 5, 8 or 9 with
+        constant factors — the factors are
+        constants of the graph, held fixed as A is, and get no gradient; the CG types 2 and 6, type 7 and a variable factor make backward
+        raise), lod (batch, nVar + 1, cap) float64 on the same device.  rhs is copied
         into the last column of lod (lod is the handle's input from then on: it must stay alive and unchanged until backward has run), the
         batch is factorized and solved with the factor kept, and x (batch, nVar) comes back as a new tensor.  Gradient: rhs only."""
 
@@ -101,7 +107,9 @@ def _solve_bounds_class():
         None), out a dict that receives run_device's result (or None).  Forward: run_device; x (batch, nVar) comes back.  Backward:
         solve_adjoint_device — the gradient of the piece of the piecewise-affine map the solve ended on, zero for instances that did not end
         PROBLEM_SOLVED.  Gradients: lb and ub only.  The backward pass reads the state the forward run left in `batch`; when the batch has run
-        again in between, the forward run is repeated from the saved bounds first (data is written again)."""
+        again in between, the forward run is repeated from the saved bounds first (data is written again).  Regularized runs: after
+        batch.set_adjoint_regularized(), types 1, 3, 4, 5, 8 and 9 with constant factors are differentiated too (the damped final problem);
+        the factors, shared or per instance, are constants of the graph.  Without it, and for the other types, backward raises."""
 
         @staticmethod
         def forward(ctx, lb, ub, batch, data, var_index=None, active_guess=None, x0=None, params=None, out=None):
