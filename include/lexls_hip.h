@@ -765,8 +765,8 @@ int lexls_lsi_batch_get_lambda(lexls_lsi_batch_t b, double *h_lambda);
  * ub by activation type), the fixed values the active simple bounds.  While W does not change x is exactly affine in the bounds, so with
  * g = dloss/dx these calls return dloss/dlb and dloss/dub: the final equality problems are formed and factorized with the factor kept as for
  * lexls_lsi_batch_get_lambda (once per run: whichever of the two is called first pays for it, every later call of either reuses the factor),
- * lexls_lse_solve_adjoint_device gives M^T g and N^T g, and lsi_adjoint_scatter_kernel takes them from LOD-row / fixed-slot order back to the
- * user's constraint order.  These calls give NO derivatives with respect to A: lexls_lsi_batch_solve_adjoint_matrix, below, does.
+ * lexls_lse_solve_adjoint_device gives M^T g and N^T g, and lsi_adjoint_scatter_multi_kernel (with one cotangent) takes them from LOD-row /
+ * fixed-slot order back to the user's constraint order.  These calls give NO derivatives with respect to A: lexls_lsi_batch_solve_adjoint_matrix, below, does.
  * Layouts: g is batch x nVar, dloss/dx in the user's variable order; grad_lb and grad_ub are batch x sum(dims) each, in the constraint order of
  * h_active / h_v (objective by objective).  Either output may be NULL (not wanted).  lexls_lsi_batch_solve_adjoint takes and fills host arrays;
  * lexls_lsi_batch_solve_adjoint_device takes memory of the batch's device, and no gradient, g or factor passes through host memory.  Both are

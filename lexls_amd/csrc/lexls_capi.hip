@@ -1073,18 +1073,49 @@ extern "C"
         return LEXLS_OK;
     }
 
+    /// the host form of an adjoint call, ahead of the function its device form runs too (whose checks it has run before it touches h or h_g): h_g into the handle's buffer
+    static int upload_adjoint_g(lexls_lse_t h, double *d_g, const double *h_g, size_t bytes)
+    {
+        HIP_TRY(hipMemcpyAsync(d_g, h_g, bytes, hipMemcpyHostToDevice, h->stream));
+        if (!h->deferred_sync) HIP_TRY(hipStreamSynchronize(h->stream)); // h_g may be reused by the caller
+        return LEXLS_OK;
+    }
+    /// lexls_lse_get_adjoint, _multi and _matrix (family: "", "_multi", "_matrix"): the results of the host form's last call, while they belong to the factor
+    struct AdjointCopy { void *dst; const void *src; size_t bytes; };
+    static int get_adjoint_results(lexls_lse_t h, const char *family, bool valid, uint64_t epoch, std::initializer_list<AdjointCopy> copies)
+    {
+        const std::string who = std::string("lexls_lse_get_adjoint") + family, call = std::string("lexls_lse_solve_adjoint") + family;
+        if (!valid) return fail(LEXLS_ERR_INVALID, who + ": call " + call + " first");
+        if (!h->factor_valid || epoch != h->factor_epoch) return fail(LEXLS_ERR_INVALID, who + ": the problem or its factorization changed since " + call + " (call it again)");
+        HIP_TRY(hipSetDevice(h->device));
+        for (const AdjointCopy &c : copies)
+            if (c.dst) HIP_TRY(hipMemcpyAsync(c.dst, c.src, c.bytes, hipMemcpyDeviceToHost, h->stream));
+        if (!h->deferred_sync) HIP_TRY(hipStreamSynchronize(h->stream));
+        return LEXLS_OK;
+    }
+
+    /// every form of lexls_lse_solve_adjoint on device memory: the checks, the work buffer, the launch
+    static int run_solve_adjoint(lexls_lse_t h, const char *who, const double *d_g, double *d_grad_rhs, double *d_grad_fixed)
+    {
+        if (int rc = need_adjoint_factor(h, who, d_g, true)) return rc;
+        if (!d_grad_rhs) return fail(LEXLS_ERR_INVALID, std::string(who) + ": null d_grad_rhs");
+        HIP_TRY(hipSetDevice(h->device));
+        if (int rc = adjoint_reg_work(h)) return rc;
+        HIP_TRY(launch_solve_adjoint(h->args(), d_g, d_grad_rhs, d_grad_fixed, h->stream, &h->last_consumer, h->d_adj_work));
+        return LEXLS_OK;
+    }
+
     int lexls_lse_solve_adjoint(lexls_lse_t h, const double *h_g)
     {
-        if (int rc = need_adjoint_factor(h, "lexls_lse_solve_adjoint", h_g, true)) return rc;
+        const char *who = "lexls_lse_solve_adjoint";
+        if (int rc = need_adjoint_factor(h, who, h_g, true)) return rc;
         HIP_TRY(hipSetDevice(h->device));
         const size_t B = h->batch, n = h->nVar, cap = h->cap;
         if (!h->d_adj_g) HIP_TRY(hipMalloc((void **)&h->d_adj_g, 8 * B * n));
         if (!h->d_adj_rhs) HIP_TRY(hipMalloc((void **)&h->d_adj_rhs, 8 * B * cap));
         if (!h->d_adj_fixed) HIP_TRY(hipMalloc((void **)&h->d_adj_fixed, 8 * B * n));
-        if (int rc = adjoint_reg_work(h)) return rc;
-        HIP_TRY(hipMemcpyAsync(h->d_adj_g, h_g, 8 * B * n, hipMemcpyHostToDevice, h->stream));
-        if (!h->deferred_sync) HIP_TRY(hipStreamSynchronize(h->stream)); // h_g may be reused by the caller
-        HIP_TRY(launch_solve_adjoint(h->args(), h->d_adj_g, h->d_adj_rhs, h->d_adj_fixed, h->stream, &h->last_consumer, h->d_adj_work));
+        if (int rc = upload_adjoint_g(h, h->d_adj_g, h_g, 8 * B * n)) return rc;
+        if (int rc = run_solve_adjoint(h, who, h->d_adj_g, h->d_adj_rhs, h->d_adj_fixed)) return rc;
         h->adj_valid = true;
         h->adj_epoch = h->factor_epoch;
         return LEXLS_OK;
@@ -1092,28 +1123,17 @@ extern "C"
 
     int lexls_lse_solve_adjoint_device(lexls_lse_t h, const double *d_g, double *d_grad_rhs, double *d_grad_fixed)
     {
-        if (int rc = need_adjoint_factor(h, "lexls_lse_solve_adjoint_device", d_g, true)) return rc;
-        if (!d_grad_rhs) return fail(LEXLS_ERR_INVALID, "lexls_lse_solve_adjoint_device: null d_grad_rhs");
-        HIP_TRY(hipSetDevice(h->device));
-        if (int rc = adjoint_reg_work(h)) return rc;
-        HIP_TRY(launch_solve_adjoint(h->args(), d_g, d_grad_rhs, d_grad_fixed, h->stream, &h->last_consumer, h->d_adj_work));
-        return LEXLS_OK;
+        return run_solve_adjoint(h, "lexls_lse_solve_adjoint_device", d_g, d_grad_rhs, d_grad_fixed);
     }
 
     int lexls_lse_get_adjoint(lexls_lse_t h, double *h_grad_rhs, double *h_grad_fixed)
     {
         CHECK_HANDLE(h);
-        if (!h->adj_valid) return fail(LEXLS_ERR_INVALID, "lexls_lse_get_adjoint: call lexls_lse_solve_adjoint first");
-        if (!h->factor_valid || h->adj_epoch != h->factor_epoch)
-            return fail(LEXLS_ERR_INVALID, "lexls_lse_get_adjoint: the problem or its factorization changed since lexls_lse_solve_adjoint (call it again)");
-        HIP_TRY(hipSetDevice(h->device));
-        if (h_grad_rhs) HIP_TRY(hipMemcpyAsync(h_grad_rhs, h->d_adj_rhs, 8 * (size_t)h->batch * h->cap, hipMemcpyDeviceToHost, h->stream));
-        if (h_grad_fixed) HIP_TRY(hipMemcpyAsync(h_grad_fixed, h->d_adj_fixed, 8 * (size_t)h->batch * h->nVar, hipMemcpyDeviceToHost, h->stream));
-        if (!h->deferred_sync) HIP_TRY(hipStreamSynchronize(h->stream));
-        return LEXLS_OK;
+        return get_adjoint_results(h, "", h->adj_valid, h->adj_epoch,
+                                   {{h_grad_rhs, h->d_adj_rhs, 8 * (size_t)h->batch * h->cap}, {h_grad_fixed, h->d_adj_fixed, 8 * (size_t)h->batch * h->nVar}});
     }
 
-    /// what both multi-cotangent forms check before any device work, and the per-cotangent form's buffers (made at the first call that needs them)
+    /// what both multi-cotangent forms check before any device work
     static int need_adjoint_multi(lexls_lse_t h, const char *who, const void *G, uint32_t ncot)
     {
         CHECK_HANDLE(h);
@@ -1121,19 +1141,25 @@ extern "C"
         if (ncot == 0) return fail(LEXLS_ERR_INVALID, std::string(who) + ": ncot == 0");
         return need_adjoint_factor(h, who, G);
     }
-    static int adjoint_multi_work(lexls_lse_t h)
+    /// every form of lexls_lse_solve_adjoint_multi on device memory: the checks, the work buffer, the launch
+    static int run_solve_adjoint_multi(lexls_lse_t h, const char *who, const double *d_G, uint32_t ncot, double *d_grad_rhs, double *d_grad_fixed)
     {
+        if (int rc = need_adjoint_multi(h, who, d_G, ncot)) return rc;
+        if (!d_grad_rhs) return fail(LEXLS_ERR_INVALID, std::string(who) + ": null d_grad_rhs");
+        HIP_TRY(hipSetDevice(h->device));
         const size_t bytes = adjoint_multi_work_bytes(h->args());
         if (bytes && !h->d_adjm_work) HIP_TRY(hipMalloc((void **)&h->d_adjm_work, bytes));
+        HIP_TRY(launch_solve_adjoint_multi(h->args(), d_G, ncot, d_grad_rhs, d_grad_fixed, h->d_adjm_work, h->stream, &h->last_consumer));
         return LEXLS_OK;
     }
 
     int lexls_lse_solve_adjoint_multi(lexls_lse_t h, const double *h_G, uint32_t ncot)
     {
-        if (int rc = need_adjoint_multi(h, "lexls_lse_solve_adjoint_multi", h_G, ncot)) return rc;
+        const char *who = "lexls_lse_solve_adjoint_multi";
+        if (int rc = need_adjoint_multi(h, who, h_G, ncot)) return rc;
         HIP_TRY(hipSetDevice(h->device));
         const size_t B = h->batch, n = h->nVar, cap = h->cap;
-        if (ncot > h->adjm_room)
+        if (ncot > h->adjm_room) // the buffers hold the largest ncot so far
         {
             h->adjm_valid = false;
             h->adjm_room  = 0;
@@ -1147,10 +1173,8 @@ extern "C"
             HIP_TRY(hipMalloc((void **)&h->d_adjm_fixed, 8 * B * ncot * n));
             h->adjm_room = ncot;
         }
-        if (int rc = adjoint_multi_work(h)) return rc;
-        HIP_TRY(hipMemcpyAsync(h->d_adjm_G, h_G, 8 * B * ncot * n, hipMemcpyHostToDevice, h->stream));
-        if (!h->deferred_sync) HIP_TRY(hipStreamSynchronize(h->stream)); // h_G may be reused by the caller
-        HIP_TRY(launch_solve_adjoint_multi(h->args(), h->d_adjm_G, ncot, h->d_adjm_rhs, h->d_adjm_fixed, h->d_adjm_work, h->stream, &h->last_consumer));
+        if (int rc = upload_adjoint_g(h, h->d_adjm_G, h_G, 8 * B * ncot * n)) return rc;
+        if (int rc = run_solve_adjoint_multi(h, who, h->d_adjm_G, ncot, h->d_adjm_rhs, h->d_adjm_fixed)) return rc;
         h->adjm_valid = true;
         h->adjm_ncot  = ncot;
         h->adjm_epoch = h->factor_epoch;
@@ -1159,29 +1183,17 @@ extern "C"
 
     int lexls_lse_solve_adjoint_multi_device(lexls_lse_t h, const double *d_G, uint32_t ncot, double *d_grad_rhs, double *d_grad_fixed)
     {
-        if (int rc = need_adjoint_multi(h, "lexls_lse_solve_adjoint_multi_device", d_G, ncot)) return rc;
-        if (!d_grad_rhs) return fail(LEXLS_ERR_INVALID, "lexls_lse_solve_adjoint_multi_device: null d_grad_rhs");
-        HIP_TRY(hipSetDevice(h->device));
-        if (int rc = adjoint_multi_work(h)) return rc;
-        HIP_TRY(launch_solve_adjoint_multi(h->args(), d_G, ncot, d_grad_rhs, d_grad_fixed, h->d_adjm_work, h->stream, &h->last_consumer));
-        return LEXLS_OK;
+        return run_solve_adjoint_multi(h, "lexls_lse_solve_adjoint_multi_device", d_G, ncot, d_grad_rhs, d_grad_fixed);
     }
 
     int lexls_lse_get_adjoint_multi(lexls_lse_t h, double *h_grad_rhs, double *h_grad_fixed)
     {
         CHECK_HANDLE(h);
-        if (!h->adjm_valid) return fail(LEXLS_ERR_INVALID, "lexls_lse_get_adjoint_multi: call lexls_lse_solve_adjoint_multi first");
-        if (!h->factor_valid || h->adjm_epoch != h->factor_epoch)
-            return fail(LEXLS_ERR_INVALID, "lexls_lse_get_adjoint_multi: the problem or its factorization changed since lexls_lse_solve_adjoint_multi (call it again)");
-        HIP_TRY(hipSetDevice(h->device));
         const size_t rows = (size_t)h->batch * h->adjm_ncot;
-        if (h_grad_rhs) HIP_TRY(hipMemcpyAsync(h_grad_rhs, h->d_adjm_rhs, 8 * rows * h->cap, hipMemcpyDeviceToHost, h->stream));
-        if (h_grad_fixed) HIP_TRY(hipMemcpyAsync(h_grad_fixed, h->d_adjm_fixed, 8 * rows * h->nVar, hipMemcpyDeviceToHost, h->stream));
-        if (!h->deferred_sync) HIP_TRY(hipStreamSynchronize(h->stream));
-        return LEXLS_OK;
+        return get_adjoint_results(h, "_multi", h->adjm_valid, h->adjm_epoch, {{h_grad_rhs, h->d_adjm_rhs, 8 * rows * h->cap}, {h_grad_fixed, h->d_adjm_fixed, 8 * rows * h->nVar}});
     }
 
-    /// what both forms of the matrix gradient check before any device work: a kept, unregularized factor and the x that belongs to it
+    /// what every form of the matrix gradient checks before any device work: a kept, unregularized factor and the x that belongs to it
     static int need_adjoint_matrix(lexls_lse_t h, const char *who, const void *g)
     {
         if (int rc = need_adjoint_factor(h, who, g)) return rc;
@@ -1189,24 +1201,28 @@ extern "C"
             return fail(LEXLS_ERR_INVALID, std::string(who) + ": no x belongs to the current factor (lexls_lse_factorize_solve(keep_factor = 1), or lexls_lse_factorize + lexls_lse_solve)");
         return LEXLS_OK;
     }
-    static int adjoint_matrix_work(lexls_lse_t h)
+    /// every form of lexls_lse_solve_adjoint_matrix on device memory: the checks, the work buffer, the launch (d_grad_fixed: lexls_internal_solve_adjoint_matrix's)
+    static int run_solve_adjoint_matrix(lexls_lse_t h, const char *who, const double *d_g, double *d_grad_lod, uint8_t *d_differentiable, double *d_grad_fixed)
     {
+        if (int rc = need_adjoint_matrix(h, who, d_g)) return rc;
+        if (!d_grad_lod) return fail(LEXLS_ERR_INVALID, std::string(who) + ": null d_grad_lod");
+        HIP_TRY(hipSetDevice(h->device));
         if (!h->d_adjA_work) HIP_TRY(hipMalloc(&h->d_adjA_work, adjoint_matrix_work_bytes(h->args())));
+        HIP_TRY(launch_solve_adjoint_matrix(h->args(), d_g, d_grad_lod, d_differentiable, h->d_adjA_work, h->max_level_dim, h->stream, &h->last_consumer, d_grad_fixed));
         return LEXLS_OK;
     }
 
     int lexls_lse_solve_adjoint_matrix(lexls_lse_t h, const double *h_g)
     {
-        if (int rc = need_adjoint_matrix(h, "lexls_lse_solve_adjoint_matrix", h_g)) return rc;
+        const char *who = "lexls_lse_solve_adjoint_matrix";
+        if (int rc = need_adjoint_matrix(h, who, h_g)) return rc;
         HIP_TRY(hipSetDevice(h->device));
         const size_t B = h->batch, n = h->nVar, cap = h->cap;
         if (!h->d_adjA_g) HIP_TRY(hipMalloc((void **)&h->d_adjA_g, 8 * B * n));
         if (!h->d_adjA_grad) HIP_TRY(hipMalloc((void **)&h->d_adjA_grad, 8 * B * (n + 1) * cap));
         if (!h->d_adjA_flag) HIP_TRY(hipMalloc((void **)&h->d_adjA_flag, B));
-        if (int rc = adjoint_matrix_work(h)) return rc;
-        HIP_TRY(hipMemcpyAsync(h->d_adjA_g, h_g, 8 * B * n, hipMemcpyHostToDevice, h->stream));
-        if (!h->deferred_sync) HIP_TRY(hipStreamSynchronize(h->stream)); // h_g may be reused by the caller
-        HIP_TRY(launch_solve_adjoint_matrix(h->args(), h->d_adjA_g, h->d_adjA_grad, h->d_adjA_flag, h->d_adjA_work, h->max_level_dim, h->stream, &h->last_consumer));
+        if (int rc = upload_adjoint_g(h, h->d_adjA_g, h_g, 8 * B * n)) return rc;
+        if (int rc = run_solve_adjoint_matrix(h, who, h->d_adjA_g, h->d_adjA_grad, h->d_adjA_flag, nullptr)) return rc;
         h->adjA_valid = true;
         h->adjA_epoch = h->factor_epoch;
         return LEXLS_OK;
@@ -1214,35 +1230,19 @@ extern "C"
 
     int lexls_lse_solve_adjoint_matrix_device(lexls_lse_t h, const double *d_g, double *d_grad_lod, uint8_t *d_differentiable)
     {
-        if (int rc = need_adjoint_matrix(h, "lexls_lse_solve_adjoint_matrix_device", d_g)) return rc;
-        if (!d_grad_lod) return fail(LEXLS_ERR_INVALID, "lexls_lse_solve_adjoint_matrix_device: null d_grad_lod");
-        HIP_TRY(hipSetDevice(h->device));
-        if (int rc = adjoint_matrix_work(h)) return rc;
-        HIP_TRY(launch_solve_adjoint_matrix(h->args(), d_g, d_grad_lod, d_differentiable, h->d_adjA_work, h->max_level_dim, h->stream, &h->last_consumer));
-        return LEXLS_OK;
+        return run_solve_adjoint_matrix(h, "lexls_lse_solve_adjoint_matrix_device", d_g, d_grad_lod, d_differentiable, nullptr);
     }
 
     int lexls_internal_solve_adjoint_matrix(lexls_lse_t h, const double *d_g, double *d_grad_lod, double *d_grad_fixed, uint8_t *d_differentiable)
     {
-        if (int rc = need_adjoint_matrix(h, "lexls_internal_solve_adjoint_matrix", d_g)) return rc;
-        if (!d_grad_lod) return fail(LEXLS_ERR_INVALID, "lexls_internal_solve_adjoint_matrix: null d_grad_lod");
-        HIP_TRY(hipSetDevice(h->device));
-        if (int rc = adjoint_matrix_work(h)) return rc;
-        HIP_TRY(launch_solve_adjoint_matrix(h->args(), d_g, d_grad_lod, d_differentiable, h->d_adjA_work, h->max_level_dim, h->stream, &h->last_consumer, d_grad_fixed));
-        return LEXLS_OK;
+        return run_solve_adjoint_matrix(h, "lexls_internal_solve_adjoint_matrix", d_g, d_grad_lod, d_differentiable, d_grad_fixed);
     }
 
     int lexls_lse_get_adjoint_matrix(lexls_lse_t h, double *h_grad_lod, uint8_t *h_differentiable)
     {
         CHECK_HANDLE(h);
-        if (!h->adjA_valid) return fail(LEXLS_ERR_INVALID, "lexls_lse_get_adjoint_matrix: call lexls_lse_solve_adjoint_matrix first");
-        if (!h->factor_valid || h->adjA_epoch != h->factor_epoch)
-            return fail(LEXLS_ERR_INVALID, "lexls_lse_get_adjoint_matrix: the problem or its factorization changed since lexls_lse_solve_adjoint_matrix (call it again)");
-        HIP_TRY(hipSetDevice(h->device));
-        if (h_grad_lod) HIP_TRY(hipMemcpyAsync(h_grad_lod, h->d_adjA_grad, 8 * (size_t)h->batch * h->problem_elems(), hipMemcpyDeviceToHost, h->stream));
-        if (h_differentiable) HIP_TRY(hipMemcpyAsync(h_differentiable, h->d_adjA_flag, (size_t)h->batch, hipMemcpyDeviceToHost, h->stream));
-        if (!h->deferred_sync) HIP_TRY(hipStreamSynchronize(h->stream));
-        return LEXLS_OK;
+        return get_adjoint_results(h, "_matrix", h->adjA_valid, h->adjA_epoch,
+                                   {{h_grad_lod, h->d_adjA_grad, 8 * (size_t)h->batch * h->problem_elems()}, {h_differentiable, h->d_adjA_flag, (size_t)h->batch}});
     }
 
     int lexls_internal_apply_solve_map(lexls_lse_t h, const double *d_rhs, double *d_out)

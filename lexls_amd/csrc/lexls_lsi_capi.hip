@@ -146,7 +146,7 @@ extern "C"
                                          "regularization type 7, cycling handling of a regularized run, shapes without a register-resident kernel)");
                 return static_cast<int>(LEXLS_ERR_UNSUPPORTED);
             }
-            if (d_lambda && b->lam_rc_after(par) != LEXLS_OK) // what lexls_lsi_batch_get_lambda would answer after this run: refused now, before any device work
+            if (d_lambda && b->fin.lam_rc_after(par) != LEXLS_OK) // what lexls_lsi_batch_get_lambda would answer after this run: refused now, before any device work
             {
                 lexls_internal_set_error("lexls_lsi_batch_run_device_ex: d_lambda is not served for a run with cycling handling enabled, a regularized run or more than 65535 "
                                          "constraints (lexls_lsi_batch_get_lambda is not available after such a run)");
@@ -156,7 +156,7 @@ extern "C"
             dev.v0 = d_x0 ? d_v0 : NULL; // v0 without x0 is disregarded (lexlsi.h:695-701)
             dev.cycling_counts = d_cycling_counts;
             b->run_device(dev, h_reg_factors, par);
-            return d_lambda ? b->get_lambda(NULL, d_lambda) : static_cast<int>(LEXLS_OK);
+            return d_lambda ? b->fin.get_lambda(NULL, d_lambda) : static_cast<int>(LEXLS_OK);
         });
     }
 
@@ -179,7 +179,7 @@ extern "C"
                                          "split into several groups by LEXLS_LSI_GROUPS)");
                 return static_cast<int>(LEXLS_ERR_UNSUPPORTED);
             }
-            if (d_lambda && b->lam_rc_after(par) != LEXLS_OK) // as lexls_lsi_batch_run_device_ex: refused before any device work
+            if (d_lambda && b->fin.lam_rc_after(par) != LEXLS_OK) // as lexls_lsi_batch_run_device_ex: refused before any device work
             {
                 lexls_internal_set_error("lexls_lsi_batch_enqueue_device: d_lambda is not served for a run with cycling handling enabled, a regularized run or more than 65535 "
                                          "constraints (lexls_lsi_batch_get_lambda is not available after such a run)");
@@ -241,7 +241,7 @@ extern "C"
         return guarded([&]() {
             if (!b) throw Exception("lexls_lsi_batch_get_lambda: null handle");
             b->refuse_pending("lexls_lsi_batch_get_lambda");
-            return b->get_lambda(h_lambda);
+            return b->fin.get_lambda(h_lambda);
         });
     }
 
@@ -254,7 +254,7 @@ extern "C"
             if (!g) throw Exception(who + ": null g");
             if (!grad_lb && !grad_ub) throw Exception(who + ": both outputs are null");
             b->refuse_pending(who.c_str());
-            return b->solve_adjoint(g, grad_lb, grad_ub, on_device);
+            return b->fin.solve_adjoint(g, grad_lb, grad_ub, on_device);
         });
     }
 
@@ -278,7 +278,7 @@ extern "C"
             if (ncot == 0) throw Exception(who + ": ncot == 0");
             if (!grad_lb && !grad_ub) throw Exception(who + ": both outputs are null");
             b->refuse_pending(who.c_str());
-            return b->solve_adjoint_multi(G, ncot, grad_lb, grad_ub, on_device);
+            return b->fin.solve_adjoint_multi(G, ncot, grad_lb, grad_ub, on_device);
         });
     }
 
@@ -301,7 +301,7 @@ extern "C"
             if (!g) throw Exception(who + ": null g");
             if (!grad_data) throw Exception(who + ": null grad_data");
             b->refuse_pending(who.c_str());
-            return b->solve_adjoint_matrix(g, grad_data, differentiable, on_device);
+            return b->fin.solve_adjoint_matrix(g, grad_data, differentiable, on_device);
         });
     }
 
@@ -319,7 +319,7 @@ extern "C"
     {
         return guarded([&]() {
             if (!b || !h_count) throw Exception("lexls_lsi_batch_final_factorizations: null argument");
-            *h_count = b->final_formations;
+            *h_count = b->fin.final_formations;
             return LEXLS_OK;
         });
     }
@@ -346,7 +346,7 @@ extern "C"
         return guarded([&]() {
             if (!b) throw Exception("lexls_lsi_batch_set_adjoint_regularized: null handle");
             b->refuse_pending("lexls_lsi_batch_set_adjoint_regularized");
-            b->adj_regularized = on != 0; // (the rule of the last run stands: the next run is the first one it applies to)
+            b->fin.adj_regularized = on != 0; // (the rule of the last run stands: the next run is the first one it applies to)
             return static_cast<int>(LEXLS_OK);
         });
     }

@@ -4,7 +4,7 @@
 #include <memory>
 #include <thread>
 #include "lsi_slot.h"
-#include "lsi_worker_pool.h"
+#include "lsi_final.h"
 
 namespace
 {
@@ -21,199 +21,6 @@ namespace
         runner::collect(lsi, p, h_x, &info, h_active, h_v);
         if (h_info6) std::memcpy(h_info6, &info, sizeof(info));
         return info;
-    }
-
-    /// getLambda's last loop (lexlsi.h:592-604) for a whole group: the rows of the multiplier matrices (lexls_lse_multipliers: B x nObjL x ldo,
-    /// row r = r-th active constraint in working-set order, simple bounds first) go to the user's order — instance b's output is total x nObj,
-    /// column-major, column off + k = LexLSE objective k, column 0 zero when objective 0 holds simple bounds, inactive rows zero.
-    /// One workgroup per instance, lane = active constraint; map = [nact (B) | pos (B x total): user row of active constraint r].
-    /// fault (lexls_lsi_batch_enqueue_device; else NULL): the run's fault word — with it set nothing is written
-    /// mask (the group's bytes of lexls_lsi_batch_set_instance_mask, or NULL): `out` is the caller's d_lambda and the rows of a skipped instance stay as they are
-    __global__ __launch_bounds__(64) void lsi_lambda_scatter_kernel(const double *__restrict__ mult, const uint32_t *__restrict__ map, uint32_t B, uint32_t total,
-                                                                    uint32_t nObj, uint32_t nObjL, uint32_t off, uint32_t ldo, double *__restrict__ out,
-                                                                    const uint32_t *__restrict__ fault, const uint8_t *mask)
-    {
-        if (fault && *fault != 0xffffffffu) return;
-        const uint32_t b = blockIdx.x;
-        if (lsi_mask_byte(mask, b) == 0) return; // (block-uniform)
-        double *o        = out + (size_t)b * total * nObj;
-        for (uint32_t i = threadIdx.x; i < total * nObj; i += blockDim.x) o[i] = 0.0;
-        __syncthreads();
-        const uint32_t na   = min(map[b], min(total, ldo));
-        const uint32_t *pos = map + B + (size_t)b * total;
-        const double *m     = mult + (size_t)b * nObjL * ldo;
-        for (uint32_t r = threadIdx.x; r < na; r += blockDim.x)
-        {
-            const uint32_t u = pos[r];
-            if (u >= total) continue;
-            for (uint32_t k = 0; k < nObjL; k++) o[u + (size_t)(off + k) * total] = m[(size_t)k * ldo + r];
-        }
-    }
-
-    /// lexls_lsi_batch_solve_adjoint for a whole group: the adjoint of the final equality problems (lexls_lse_solve_adjoint_device: grad_rhs B x cap in
-    /// LOD row order, grad_fixed B x n in fixVariable order) goes to the user's constraint order — instance b's `total` entries of out_lb / out_ub
-    /// (either may be NULL).  One wavefront per instance.  map = [nact (B) | pos (B x total)] as for lsi_lambda_scatter_kernel: row r of the final
-    /// problem (the nf fixed variables first, then the LOD rows) is user row pos[r]; types (B x total) = its activation type, in the same row order;
-    /// meta (B x 2) = the instance's status of the run and nf.  CTR_ACTIVE_LB goes to out_lb, CTR_ACTIVE_UB and CTR_ACTIVE_EQ to out_ub (the bound
-    /// form_final_problem posts); an instance that did not end PROBLEM_SOLVED has no active rows here.  The zeros and the active values meet in an LDS
-    /// tile of ADJ_TILE user rows (pos is injective: no two rows of the map claim one entry, no atomics), then the lanes run along the user rows:
-    /// every entry of the outputs is stored once, by consecutive lanes.
-    /// mask (the group's bytes of lexls_lsi_batch_set_instance_mask, or NULL): the entries of a skipped instance stay as they are
-    constexpr uint32_t ADJ_TILE = 1024;
-    __global__ __launch_bounds__(64) void lsi_adjoint_scatter_kernel(const double *__restrict__ grad_rhs, const double *__restrict__ grad_fixed, const uint32_t *__restrict__ map,
-                                                                     const uint8_t *__restrict__ types, const int32_t *__restrict__ meta, uint32_t B, uint32_t total, uint32_t n,
-                                                                     uint32_t cap, double *__restrict__ out_lb, double *__restrict__ out_ub, const uint8_t *mask)
-    {
-        __shared__ double s_lb[ADJ_TILE], s_ub[ADJ_TILE];
-        const uint32_t b = blockIdx.x, lane = threadIdx.x;
-        if (b >= B || lsi_mask_byte(mask, b) == 0) return; // (block-uniform)
-        const uint32_t nf   = min((uint32_t)max(meta[2 * b + 1], 0), n);
-        const uint32_t na   = meta[2 * b] == (int32_t)PROBLEM_SOLVED ? min(map[b], min(total, nf + cap)) : 0u;
-        const uint32_t *pos = map + B + (size_t)b * total;
-        const uint8_t *ty   = types + (size_t)b * total;
-        const double *gr = grad_rhs + (size_t)b * cap, *gf = grad_fixed + (size_t)b * n;
-        for (uint32_t u0 = 0; u0 < total; u0 += ADJ_TILE)
-        {
-            const uint32_t len = min(ADJ_TILE, total - u0);
-            for (uint32_t i = lane; i < len; i += 64) s_lb[i] = s_ub[i] = 0.0;
-            __syncthreads();
-            for (uint32_t r = lane; r < na; r += 64)
-            {
-                const uint32_t u = pos[r];
-                if (u < u0 || u - u0 >= len) continue;
-                const double val = r < nf ? gf[r] : gr[r - nf];
-                const uint8_t t  = ty[r];
-                if (t == CTR_ACTIVE_LB)
-                    s_lb[u - u0] = val;
-                else if (t == CTR_ACTIVE_UB || t == CTR_ACTIVE_EQ)
-                    s_ub[u - u0] = val;
-            }
-            __syncthreads();
-            for (uint32_t i = lane; i < len; i += 64)
-            {
-                if (out_lb) out_lb[(size_t)b * total + u0 + i] = s_lb[i];
-                if (out_ub) out_ub[(size_t)b * total + u0 + i] = s_ub[i];
-            }
-            __syncthreads();
-        }
-    }
-
-    /// lsi_adjoint_scatter_kernel for ncot cotangents per instance (lexls_lsi_batch_solve_adjoint_multi): block (b, c) serves cotangent c of instance b —
-    /// the same map, types, meta and mask (all per instance), row b * ncot + c of grad_rhs (B x ncot x cap), grad_fixed (B x ncot x n) and of the
-    /// outputs (B x ncot x total).  Every output entry is stored once, by consecutive lanes; a masked instance writes none of its ncot rows
-    __global__ __launch_bounds__(64) void lsi_adjoint_scatter_multi_kernel(const double *__restrict__ grad_rhs, const double *__restrict__ grad_fixed,
-                                                                           const uint32_t *__restrict__ map, const uint8_t *__restrict__ types,
-                                                                           const int32_t *__restrict__ meta, uint32_t B, uint32_t ncot, uint32_t total, uint32_t n, uint32_t cap,
-                                                                           double *__restrict__ out_lb, double *__restrict__ out_ub, const uint8_t *mask)
-    {
-        __shared__ double s_lb[ADJ_TILE], s_ub[ADJ_TILE];
-        const uint32_t b = blockIdx.x, c = blockIdx.y, lane = threadIdx.x;
-        if (b >= B || c >= ncot || lsi_mask_byte(mask, b) == 0) return; // (block-uniform)
-        const uint32_t nf   = min((uint32_t)max(meta[2 * b + 1], 0), n);
-        const uint32_t na   = meta[2 * b] == (int32_t)PROBLEM_SOLVED ? min(map[b], min(total, nf + cap)) : 0u;
-        const uint32_t *pos = map + B + (size_t)b * total;
-        const uint8_t *ty   = types + (size_t)b * total;
-        const size_t row    = (size_t)b * ncot + c;
-        const double *gr = grad_rhs + row * cap, *gf = grad_fixed + row * n;
-        for (uint32_t u0 = 0; u0 < total; u0 += ADJ_TILE)
-        {
-            const uint32_t len = min(ADJ_TILE, total - u0);
-            for (uint32_t i = lane; i < len; i += 64) s_lb[i] = s_ub[i] = 0.0;
-            __syncthreads();
-            for (uint32_t r = lane; r < na; r += 64)
-            {
-                const uint32_t u = pos[r];
-                if (u < u0 || u - u0 >= len) continue;
-                const double val = r < nf ? gf[r] : gr[r - nf];
-                const uint8_t t  = ty[r];
-                if (t == CTR_ACTIVE_LB)
-                    s_lb[u - u0] = val;
-                else if (t == CTR_ACTIVE_UB || t == CTR_ACTIVE_EQ)
-                    s_ub[u - u0] = val;
-            }
-            __syncthreads();
-            for (uint32_t i = lane; i < len; i += 64)
-            {
-                if (out_lb) out_lb[row * total + u0 + i] = s_lb[i];
-                if (out_ub) out_ub[row * total + u0 + i] = s_ub[i];
-            }
-            __syncthreads();
-        }
-    }
-
-    /// lexls_lsi_batch_solve_adjoint_matrix for a whole group: the matrix gradient of the final equality problems (launch_solve_adjoint_matrix:
-    /// grad_lod B x (n + 1) x cap in the layout of the problem data — entry (LOD row i, column j) at j * cap + i, column n = y = M^T g — and grad_fixed
-    /// B x n = N^T g in fixVariable order) goes to the caller's constraint data layout: instance b's slice of `out` is per_data doubles, per
-    /// objective o a column-major dim x w block at shape[4 o + 2] (w = n + 2, [A | lb | ub], where shape[4 o + 1] != 0: a general objective; else
-    /// w = 2, [lb | ub]); shape (nObj x 4) = {dim, general, offset of the block, first user row} of every objective.  map, types and meta are
-    /// lsi_adjoint_scatter_kernel's (one upload per run serves both): row r of the final problem (the nf fixed variables first, then the LOD rows)
-    /// is user row pos[r].  An active general row takes its row of grad_lod in the A columns and its y in the lb (CTR_ACTIVE_LB) or ub column
-    /// (CTR_ACTIVE_UB, CTR_ACTIVE_EQ); an active simple bound takes its slot of grad_fixed by the same rule; every other entry is an exact zero.
-    /// differentiable[b] (may be NULL) = lse_flag[b] (the rank-stability flag of the final problem, launch_solve_adjoint_matrix's; NULL: the group
-    /// launched no chain, nobody has an active constraint) && status PROBLEM_SOLVED — where it is 0 the whole slice is exact zeros.
-    /// One workgroup of ADJM_NT threads per instance.  Per objective and tile of ADJM_TILE user rows the inverse of pos is formed in LDS (one word
-    /// per user row: final-problem row + 1 | type << 24; pos is injective: no two rows claim one word, no atomics), then the threads run along the
-    /// tile's entries in the order they are stored — along the user rows of one data column, column after column, consecutive threads at
-    /// consecutive addresses (an objective of at most ADJM_TILE rows is one contiguous run) — so every entry of the slice is stored exactly once,
-    /// zeros and values alike; the reads of grad_lod are the scattered side.
-    /// mask (the group's bytes of lexls_lsi_batch_set_instance_mask, or NULL): slice and flag of a skipped instance stay as they are
-    constexpr uint32_t ADJM_TILE = 1024, ADJM_NT = 256;
-    __global__ __launch_bounds__(ADJM_NT) void lsi_adjoint_matrix_scatter_kernel(const double *__restrict__ grad_lod, const double *__restrict__ grad_fixed,
-                                                                                 const uint8_t *__restrict__ lse_flag, const uint32_t *__restrict__ map,
-                                                                                 const uint8_t *__restrict__ types, const int32_t *__restrict__ meta,
-                                                                                 const uint32_t *__restrict__ shape, uint32_t B, uint32_t nObj, uint32_t total, uint32_t n,
-                                                                                 uint32_t cap, size_t per_data, double *__restrict__ out,
-                                                                                 uint8_t *__restrict__ differentiable, const uint8_t *mask)
-    {
-        __shared__ uint32_t s_row[ADJM_TILE];
-        const uint32_t b = blockIdx.x, tid = threadIdx.x;
-        if (b >= B || lsi_mask_byte(mask, b) == 0) return; // (block-uniform)
-        const uint32_t nf     = min((uint32_t)max(meta[2 * b + 1], 0), n);
-        const uint32_t na_all = min(map[b], min(total, nf + cap));
-        const bool diff       = meta[2 * b] == (int32_t)PROBLEM_SOLVED && (na_all == 0 || (lse_flag && lse_flag[b] != 0)); // (an empty working set: x = 0 whatever the data)
-        const uint32_t na     = diff ? na_all : 0u;
-        if (tid == 0 && differentiable) differentiable[b] = diff ? 1 : 0;
-        const uint32_t *pos = map + B + (size_t)b * total;
-        const uint8_t *ty   = types + (size_t)b * total;
-        const double *gl = grad_lod + (size_t)b * cap * (n + 1), *gf = grad_fixed + (size_t)b * n;
-        double *o_b      = out + (size_t)b * per_data;
-        for (uint32_t o = 0; o < nObj; o++)
-        {
-            const uint32_t dim = shape[4 * o], general = shape[4 * o + 1], first = shape[4 * o + 3];
-            const uint32_t w   = general ? n + 2 : 2u, col_lb = w - 2;
-            double *o_k        = o_b + shape[4 * o + 2];
-            for (uint32_t t0 = 0; t0 < dim; t0 += ADJM_TILE)
-            {
-                const uint32_t len = min(ADJM_TILE, dim - t0), u0 = first + t0;
-                for (uint32_t i = tid; i < len; i += ADJM_NT) s_row[i] = 0u;
-                __syncthreads();
-                for (uint32_t r = tid; r < na; r += ADJM_NT)
-                {
-                    const uint32_t u = pos[r];
-                    if (u < u0 || u - u0 >= len) continue;
-                    s_row[u - u0] = (r + 1) | ((uint32_t)ty[r] << 24);
-                }
-                __syncthreads();
-                for (uint32_t e = tid; e < len * w; e += ADJM_NT)
-                {
-                    const uint32_t j = e / len, i = e - j * len, code = s_row[i];
-                    double val = 0.0;
-                    if (code)
-                    {
-                        const uint32_t r = (code & 0xffffffu) - 1, t = code >> 24;
-                        const bool to_lb = t == CTR_ACTIVE_LB, to_ub = t == CTR_ACTIVE_UB || t == CTR_ACTIVE_EQ;
-                        if (j < col_lb)
-                        {
-                            if (r >= nf && (to_lb || to_ub)) val = gl[(size_t)j * cap + (r - nf)];
-                        }
-                        else if (j == col_lb ? to_lb : to_ub)
-                            val = r < nf ? gf[r] : gl[(size_t)n * cap + (r - nf)];
-                    }
-                    o_k[(size_t)j * dim + t0 + i] = val;
-                }
-                __syncthreads();
-            }
-        }
     }
 
     /// lexls_lsi_batch_set_instance_regularization with the factors in device memory, for one group: row i of the group's handle array (B x nObjL,
@@ -244,18 +51,9 @@ namespace
 
 /// A lock-step batch that outlives one solve (the reference constructs a LexLSI once and feeds it successive problems, lexlsi.h:56-112):
 /// device buffers, pinned blocks, streams and the worker pool are made once; every run() re-reads the problem data.
-struct lexls_lsi_batch_s
+struct lexls_lsi_batch_s : LsiBatchShape
 {
-    int device;
-    uint32_t batch, nVar, nObj, off;
-    std::vector<uint32_t> dims;
-    std::vector<int32_t> types;
-    size_t per_data = 0, total = 0;
-    bool gather = false;
-    uint32_t nGroups = 1;
-    std::vector<std::unique_ptr<BatchCtx>> grp;
-    std::vector<uint32_t> lo, group_of;
-    std::unique_ptr<WorkerPool> pool;
+    LsiFinal fin{*this}; // what follows a run: its working sets, get_lambda and the gradient calls (lsi_final.h)
     bool resident_ok = false;
     bool resident_shape = false; // resident_ok but for the environment's switches: the structure has resident iterations at all
     // ---- lexls_lsi_batch_set_instance_regularization: batch x nObj factors that stand for h_reg_factors in every regularized run while set ----
@@ -263,9 +61,6 @@ struct lexls_lsi_batch_s
     int inst_mode = INST_NONE;
     std::vector<double> inst_factors;     // INST_HOST: the copy taken at the call
     const double *d_inst_factors = NULL;  // INST_DEVICE: the caller's array, read in the groups' streams at the start of every run
-    // ---- lexls_lsi_batch_set_instance_mask: batch bytes in device memory, the caller's; read by the kernels of every device run while set, never on the host ----
-    const uint8_t *d_mask = NULL;
-    const uint8_t *group_mask(uint32_t g) const { return d_mask ? d_mask + lo[g] : NULL; }
     // ---- lexls_lsi_batch_set_instance_max_factorizations: batch int32 in device memory, the caller's; read by the setup kernel of every device run while set ----
     const int32_t *d_limits = NULL;
     const int32_t *group_limits(uint32_t g) const { return d_limits ? d_limits + lo[g] : NULL; }
@@ -274,73 +69,7 @@ struct lexls_lsi_batch_s
     const uint32_t *group_obj_dims(uint32_t g) const { return d_obj_dims ? d_obj_dims + (size_t)lo[g] * nObj : NULL; }
     double t_create = 0.0;
     int32_t last_stats[4] = {0, 0, 0, 0}; // of the last run: factorize+solve stages, sensitivity stages, stages with the step on the device, groups
-    // ---- getLambda of the last run (lexls_lsi_batch_get_lambda, lexlsi.h:552-605) ----
-    // What the run leaves behind for it: every instance's final working set in working-set order and its active simple bounds (variable and
-    // bound value, the fixed variables of formLexLSE, objective.h:255-272); the general rows are gathered from the constraint data that stays
-    // resident in the group handles.  lam_rc: -1 no run yet (or the last one failed), LEXLS_OK, or the code get_lambda returns (lam_msg).
-    int lam_rc = -1;
-    std::string lam_msg;
     const char *last_kernel = ""; // lexls_lsi_batch_last_kernel: what served the resident iterations of the last run ("host": nothing did)
-    double lam_tol = 1e-12;           // tol_linear_dependence of that run (the factorizations of getLambda use it, as the reference's do)
-    std::vector<uint32_t> data_off;   // per objective: offset of its block in one instance's constraint data
-    std::vector<uint32_t> first;      // per objective: its first row among an instance's `total` constraints
-    std::vector<uint16_t> ws_na;      // batch x nObj: active constraints per objective
-    std::vector<uint16_t> ws_idx;     // batch x total: per objective (from its first row on) the active constraints in working-set order
-    std::vector<uint8_t> ws_type;     // batch x total: their activation types
-    std::vector<uint32_t> ws_fixvar;  // batch x dims[0] (simple bounds only): variables of the active simple bounds, working-set order
-    std::vector<double> ws_fixval;    // batch x dims[0]: the bound each one is fixed at
-    struct LambdaBufs                 // per group, made at the first get_lambda
-    {
-        Pinned<uint32_t> map;         // [nact (B) | pos (B x total)]
-        uint32_t *d_map = NULL;
-        double *d_out   = NULL;       // B x total x nObj
-        // lexls_lsi_batch_solve_adjoint (made at its first call, ensure_adjoint_bufs): the activation type of every row of the map and
-        // [status of the run | nfixed] per instance, for lsi_adjoint_scatter_kernel; g and the two outputs of a host caller; the adjoint of the
-        // final equality problems (grad_rhs B x cap, grad_fixed B x nVar)
-        Pinned<uint8_t> types;        // B x total
-        Pinned<int32_t> meta;         // B x 2
-        uint8_t *d_types = NULL;
-        int32_t *d_meta  = NULL;
-        double *d_g = NULL, *d_grad_rhs = NULL, *d_grad_fixed = NULL, *d_grad_lb = NULL, *d_grad_ub = NULL;
-        // lexls_lsi_batch_solve_adjoint_multi: the same five with room for m_room cotangents per instance (ensure_adjoint_multi_bufs)
-        double *d_mg = NULL, *d_mgrad_rhs = NULL, *d_mgrad_fixed = NULL, *d_mgrad_lb = NULL, *d_mgrad_ub = NULL;
-        uint32_t m_room = 0;
-        // lexls_lsi_batch_solve_adjoint_matrix (ensure_adjoint_matrix_bufs): the matrix gradient of the final equality problems (B x (nVar + 1) x cap)
-        // and their rank-stability flags (B), the objectives' {dim, general, offset, first row} for lsi_adjoint_matrix_scatter_kernel (the same for every
-        // group; uploaded when made); grad_data (B x per_data) and the flags (B) of a host caller, made at the first host call
-        double *d_grad_lod = NULL, *d_mat_out = NULL;
-        uint8_t *d_lse_flag = NULL, *d_mat_flag = NULL;
-        uint32_t *d_shape = NULL;
-        ~LambdaBufs()
-        {
-            void *dev[] = {d_map, d_out, d_types, d_meta, d_g, d_grad_rhs, d_grad_fixed, d_grad_lb, d_grad_ub, d_mg, d_mgrad_rhs, d_mgrad_fixed, d_mgrad_lb, d_mgrad_ub,
-                           d_grad_lod, d_mat_out, d_lse_flag, d_mat_flag, d_shape};
-            for (void *q : dev)
-                if (q) (void)hipFree(q);
-        }
-    };
-    std::vector<std::unique_ptr<LambdaBufs>> lam_bufs;
-    // What a group's handle holds of the last run: final_kept — its final equality problems, formed and factorized with the factor kept
-    // (ensure_final_factor; get_lambda and solve_adjoint both start there, whichever comes first pays for it), final_any — some instance of the
-    // group has an active constraint (else nothing was factorized), adj_uploaded — map, types and meta of that formation are on the device,
-    // final_solved — the handle holds the x of that factor (solve_adjoint_matrix's chain needs it; the stage factorizes only).
-    // Every new run drops all four (forget_final_factor).
-    std::vector<char> final_kept, final_any, adj_uploaded, final_solved;
-    // lexls_lsi_batch_set_adjoint_regularized: solve_adjoint answers after a resident regularized run of type 1, 3, 4, 5, 8, 9 (constant factors); off:
-    // the rules of get_lambda, as before.  adj_rc / adj_msg: what solve_adjoint answers after the last run (set_adjoint_rule); final_reg: the run was such
-    // a run, and ensure_final_factor leaves the run's regularization on the groups' handles
-    bool adj_regularized = false, final_reg = false;
-    int adj_rc           = -1;
-    std::string adj_msg;
-    uint32_t final_formations = 0; // since creation: how often ensure_final_factor formed and factorized a group's final problems (lexls_lsi_batch_final_factorizations)
-    std::vector<int32_t> ws_status;   // batch: every instance's TerminationStatus of the last run, from its host object or the resident slab
-    void forget_final_factor()
-    {
-        std::fill(final_kept.begin(), final_kept.end(), 0);
-        std::fill(final_any.begin(), final_any.end(), 0);
-        std::fill(adj_uploaded.begin(), adj_uploaded.end(), 0);
-        std::fill(final_solved.begin(), final_solved.end(), 0);
-    }
     std::vector<uint32_t> cycling_count; // batch: LexLSI::getCyclingCounter() of every instance of the last run (lexls_lsi_batch_get_cycling_counters)
     // ---- the working-set log of the last run (lexls_lsi_batch_set_working_set_log; LexLSI::getWorkingSetLog, lexlsi.h:739) ----
     // One slab for the batch, on the device and as a pinned staging copy: batch x cap records, batch x cap values, batch counters; group g works on
@@ -420,7 +149,7 @@ struct lexls_lsi_batch_s
     };
 
     lexls_lsi_batch_s(int device_, uint32_t batch_, uint32_t nVar_, uint32_t nObj_, const uint32_t *h_dims, const int32_t *h_types)
-    : device(device_), batch(batch_), nVar(nVar_), nObj(nObj_)
+    : LsiBatchShape(device_, batch_, nVar_, nObj_)
     {
         if (batch == 0 || nObj == 0) throw Exception("lexls_lsi_batch_solve: empty batch");
         dims.assign(h_dims, h_dims + nObj);
@@ -429,21 +158,10 @@ struct lexls_lsi_batch_s
         if (nObj - off == 0) throw Exception("Problems consisting of one level of simple bounds are not supported."); // lexlsi.cpp:417
         for (uint32_t k = 0; k < nObj; k++)
         {
-            data_off.push_back(static_cast<uint32_t>(per_data));
-            first.push_back(static_cast<uint32_t>(total));
             per_data += objective_elems(h_dims[k], h_types[k], nVar);
             total += h_dims[k];
         }
-        ws_na.assign((size_t)batch * nObj, 0);
-        ws_idx.assign((size_t)batch * total, 0);
-        ws_type.assign((size_t)batch * total, 0);
         cycling_count.assign(batch, 0u);
-        ws_status.assign(batch, static_cast<int32_t>(TERMINATION_STATUS_UNKNOWN));
-        if (off)
-        {
-            ws_fixvar.assign((size_t)batch * h_dims[0], 0);
-            ws_fixval.assign((size_t)batch * h_dims[0], 0.0);
-        }
         const double t_begin = BatchCtx::now();
         const CreateSwitches sw;
         // The instances can be split into groups that take turns: while one group's stage runs on the GPU (its own stream), the host
@@ -457,7 +175,7 @@ struct lexls_lsi_batch_s
         nGroups = std::min(nGroups, batch);
         gather = per_data < 0x7fffffffull && !sw.host_staging; // (LEXLS_LSI_HOST_STAGING, a diagnostic switch: assemble on the host, stage over PCIe)
         grp.resize(nGroups);
-        final_kept.assign(nGroups, 0), final_any.assign(nGroups, 0), adj_uploaded.assign(nGroups, 0), final_solved.assign(nGroups, 0);
+        fin.create();
         lo.assign(nGroups + 1, 0);
         for (uint32_t g = 0; g < nGroups; g++) lo[g + 1] = lo[g] + batch / nGroups + (g < batch % nGroups ? 1u : 0u);
         for (uint32_t g = 0; g < nGroups; g++)
@@ -501,483 +219,10 @@ struct lexls_lsi_batch_s
         t_create = BatchCtx::now() - t_begin;
     }
 
-    /// instance b's final working set from its host objects (workingset.h order)
-    template <class LSI>
-    void keep_working_set(uint32_t b, const LSI &inst, const double *data, const uint32_t *var_index)
-    {
-        uint16_t *ix = &ws_idx[(size_t)b * total];
-        uint8_t *ty  = &ws_type[(size_t)b * total];
-        ws_status[b] = static_cast<int32_t>(inst.getStatus());
-        for (uint32_t k = 0; k < nObj; k++) ws_na[(size_t)b * nObj + k] = static_cast<uint16_t>(inst.getObjectives()[k].getActiveCtrCount());
-        walk_working_set(inst.getObjectives(), nObj, [&](uint32_t k, Index a, Index c, ConstraintActivationType t) { ix[first[k] + a] = static_cast<uint16_t>(c), ty[first[k] + a] = static_cast<uint8_t>(t); }, [](uint32_t, Index, Index) {});
-        keep_fixed(b, data, var_index);
-    }
-    /// the same from the resident slabs a run downloaded (lists in working-set order, types by constraint)
-    void keep_working_set_resident(uint32_t b, BatchCtx &ctx, uint32_t k, const double *data, const uint32_t *var_index)
-    {
-        char *base          = ctx.rws_host.data();
-        const uint8_t *cs   = ctx.rl.ctr_state(base, k);
-        const uint16_t *act = ctx.rl.act(base, k), *na = ctx.rl.na(base, k);
-        ws_status[b]        = ctx.rl.info(base, k)[0];
-        for (uint32_t o = 0; o < nObj; o++)
-        {
-            ws_na[(size_t)b * nObj + o] = na[o];
-            for (uint32_t a = 0; a < na[o]; a++)
-            {
-                ws_idx[(size_t)b * total + first[o] + a]  = act[first[o] + a];
-                ws_type[(size_t)b * total + first[o] + a] = cs[first[o] + act[first[o] + a]];
-            }
-        }
-        if (data)
-            keep_fixed(b, data, var_index);
-        else if (off && ctx.fix_var_host.n) // (a lexls_lsi_batch_run_device run: the scatter kernel read them from the resident data)
-            for (uint32_t a = 0; a < na[0] && a < dims[0]; a++)
-            {
-                ws_fixvar[(size_t)b * dims[0] + a] = ctx.fix_var_host[(size_t)k * dims[0] + a];
-                ws_fixval[(size_t)b * dims[0] + a] = ctx.fix_val_host[(size_t)k * dims[0] + a];
-            }
-    }
-    /// fixVariable(var, bound) of formLexLSE for the active simple bounds (objective.h:257-271): lb, or ub for CTR_ACTIVE_UB / CTR_ACTIVE_EQ
-    void keep_fixed(uint32_t b, const double *data, const uint32_t *var_index)
-    {
-        if (!off) return;
-        const uint32_t d0 = dims[0], na = ws_na[(size_t)b * nObj];
-        for (uint32_t a = 0; a < na && a < d0; a++)
-        {
-            const uint32_t c = ws_idx[(size_t)b * total + a];
-            ws_fixvar[(size_t)b * d0 + a] = var_index ? var_index[c] : 0u;
-            ws_fixval[(size_t)b * d0 + a] = ws_type[(size_t)b * total + a] == CTR_ACTIVE_LB ? data[c] : data[d0 + c];
-        }
-    }
-
-    /// instance k of group g: the in block of its final equality problem (lexls_lse_round_layout), as formLexLSE posts it (objective.h:255-294),
-    /// and the user row of every active constraint
-    void form_final_problem(uint32_t g, uint32_t k, LambdaBufs &lb)
-    {
-        BatchCtx &ctx        = *grp[g];
-        const uint32_t nObjL = nObj - off, d0 = off ? dims[0] : 0u;
-        const uint32_t b  = lo[g] + k;
-        const uint16_t *na = ws_na.data() + (size_t)b * nObj;
-        const uint16_t *ix = ws_idx.data() + (size_t)b * total;
-        const uint8_t *ty  = ws_type.data() + (size_t)b * total;
-        uint32_t *pos      = lb.map.data() + ctx.B + (size_t)k * total;
-        uint32_t r = 0, row = 0;
-        const uint32_t nf = off ? std::min<uint32_t>(na[0], nVar) : 0u; // (formLexLSE fixes each variable once: at most nVar, lexlse.h:1453)
-        ctx.nfixed[k]     = nf;
-        for (uint32_t a = 0; a < nf; a++)
-        {
-            ctx.fixed_idx[(size_t)k * nVar + a]  = ws_fixvar[(size_t)b * d0 + a];
-            ctx.fixed_val[(size_t)k * nVar + a]  = ws_fixval[(size_t)b * d0 + a];
-            ctx.fixed_type[(size_t)k * nVar + a] = ty[a];
-            pos[r++]                             = ix[a];
-        }
-        std::fill(ctx.row_ld.begin() + (size_t)k * ctx.cap, ctx.row_ld.begin() + (size_t)(k + 1) * ctx.cap, 0u);
-        for (uint32_t o = off; o < nObj; o++)
-        {
-            ctx.dims[(size_t)k * nObjL + (o - off)] = na[o];
-            for (uint32_t a = 0; a < na[o]; a++)
-            {
-                const uint8_t t                      = ty[first[o] + a];
-                ctx.row_src[(size_t)k * ctx.cap + row] = data_off[o] + ix[first[o] + a];
-                ctx.row_ld[(size_t)k * ctx.cap + row]  = dims[o] | (t == CTR_ACTIVE_LB ? 0u : 0x80000000u);
-                ctx.ctr_type[(size_t)k * ctx.cap + row] = t;
-                row++;
-                pos[r++] = first[o] + ix[first[o] + a];
-            }
-        }
-        lb.map[k]     = r;
-        ctx.skip[k]   = 0;
-        ctx.objidx[k] = -1;
-    }
-
-    /// what lexls_lsi_batch_solve_adjoint(_device) answers after the run that just set lam_rc / lam_msg: get_lambda's answer, except that a regularized
-    /// run is served when the batch asked for it (adj_regularized), the run was resident (its regularization is on the groups' handles), its type is
-    /// one of the six whose damped solve is affine in the bounds and its variable factor is zero
-    void set_adjoint_rule(const ParametersLexLSI &par, bool resident)
-    {
-        adj_rc = lam_rc, adj_msg = lam_msg, final_reg = false;
-        const int t = static_cast<int>(par.regularization_type);
-        if (lam_rc != LEXLS_ERR_UNSUPPORTED || t == 0 || par.cycling_handling_enabled || !gather || total > 65535) return;
-        const std::string who = "lexls_lsi_batch_solve_adjoint: ";
-        if (!adj_regularized)
-            adj_msg = lam_msg + " (lexls_lsi_batch_set_adjoint_regularized, called before the run, lets lexls_lsi_batch_solve_adjoint serve regularization types 1, 3, 4, 5, 8, 9)";
-        else if (!resident)
-            adj_msg = who + "not available after a regularized run that was not resident on the device";
-        else if (!(t == 1 || t == 3 || t == 4 || t == 5 || t == 8 || t == 9))
-            adj_msg = who + "not available after a regularized run of regularization_type " + std::to_string(t) + " (served: 1, 3, 4, 5, 8, 9)";
-        else if (par.variable_regularization_factor != 0.0)
-            adj_msg = who + "not available after a regularized run with variable_regularization_factor != 0";
-        else
-            adj_rc = LEXLS_OK, adj_msg.clear(), final_reg = true;
-    }
-    /// the fixed bounds of a device run are fetched for get_lambda and for the adjoint calls
-    bool needs_final_problem(const ParametersLexLSI &par) const
-    {
-        const int t = static_cast<int>(par.regularization_type);
-        return lam_rc_after(par) == LEXLS_OK || (adj_regularized && t != 0 && !par.cycling_handling_enabled && gather && total <= 65535);
-    }
-
-    /// the groups' buffers of get_lambda, made at the first call that needs them
-    void ensure_lambda_bufs()
-    {
-        if (!lam_bufs.empty()) return;
-        lam_bufs.resize(nGroups);
-        for (uint32_t g = 0; g < nGroups; g++)
-        {
-            lam_bufs[g].reset(new LambdaBufs());
-            LambdaBufs &lb    = *lam_bufs[g];
-            const size_t Bg   = grp[g]->B;
-            lb.map.assign(Bg + Bg * total, 0u);
-            if (hipSetDevice(device) != hipSuccess || hipMalloc((void **)&lb.d_map, 4 * (Bg + Bg * total)) != hipSuccess ||
-                hipMalloc((void **)&lb.d_out, 8 * Bg * total * nObj) != hipSuccess)
-                throw Exception("hipMalloc failed (lexls_lsi_batch_get_lambda)");
-        }
-    }
-
-    /// The final equality problems of group g's instances (the downloaded working sets of the last run, form_final_problem) formed, uploaded and
-    /// factorized with the factor kept on a bit-exact kernel, in the group's stream — once per run: the handle then holds that factor until the
-    /// next run (final_kept), and lb.map the rows' user positions.  -> some instance has an active constraint (else nothing is factorized).
-    /// formed(): called between the host's formation and the device work (get_lambda's stage clock)
-    template <class Formed>
-    bool ensure_final_factor(uint32_t g, Formed formed)
-    {
-        if (final_kept[g]) return final_any[g] != 0;
-        BatchCtx &ctx  = *grp[g];
-        LambdaBufs &lb = *lam_bufs[g];
-        pool->run(ctx.B, [&](uint32_t k) { form_final_problem(g, k, lb); });
-        formed();
-        bool any_active = false; // (a run whose mask skipped every instance of the group, or whose instances all ended with empty working sets)
-        for (uint32_t k = 0; k < ctx.B && !any_active; k++) any_active = lb.map[k] != 0;
-        // the equality solver's parameters of this run, whichever path it took (the one-by-one path of a non-resident deactivate_first_wrong_sign run never set
-        // them on these handles; an earlier run of the batch object may have left a regularization there): lam_rc == LEXLS_OK means unregularized
-        hip_check(lexls_lse_set_tolerance(ctx.h, lam_tol));
-        // (final_reg: a resident regularized run whose adjoint is served — its type and factors, shared or per instance, host or device rows, are on the
-        // handle since the run's upload_regularization_block and stay there: the final factor is the damped one)
-        if (final_reg)
-            hip_check(lexls_lse_set_adjoint_regularized(ctx.h, 1));
-        else
-            hip_check(lexls_lse_set_regularization(ctx.h, 0, NULL, 0, 0.0));
-        const int policy = lexls_internal_kernel_policy(ctx.h);
-        hip_check(lexls_lse_set_kernel_policy(ctx.h, 5)); // bit-exact kernels whatever the shape (the factor of the reference's getLambda)
-        int rc = any_active ? lexls_internal_upload_round_trusted(ctx.h, ctx.in_block.data(), 1) : LEXLS_OK;
-        if (rc == LEXLS_OK && any_active) rc = lexls_lse_factorize(ctx.h);
-        hip_check(lexls_lse_set_kernel_policy(ctx.h, policy));
-        hip_check(rc);
-        final_kept[g] = 1, final_any[g] = any_active ? 1 : 0;
-        final_formations++;
-        return any_active;
-    }
-
-    /// the groups' buffers of solve_adjoint, made at the first call
-    void ensure_adjoint_bufs()
-    {
-        ensure_lambda_bufs();
-        if (lam_bufs[0]->d_meta) return;
-        if (hipSetDevice(device) != hipSuccess) throw Exception("hipSetDevice failed (lexls_lsi_batch_solve_adjoint)");
-        for (uint32_t g = 0; g < nGroups; g++)
-        {
-            LambdaBufs &lb  = *lam_bufs[g];
-            const size_t Bg = grp[g]->B, cap = grp[g]->cap;
-            lb.types.assign(Bg * total, 0);
-            lb.meta.assign(2 * Bg, 0);
-            if (hipMalloc((void **)&lb.d_types, Bg * total ? Bg * total : 1) != hipSuccess || hipMalloc((void **)&lb.d_g, 8 * Bg * nVar) != hipSuccess ||
-                hipMalloc((void **)&lb.d_grad_rhs, 8 * Bg * (cap ? cap : 1)) != hipSuccess || hipMalloc((void **)&lb.d_grad_fixed, 8 * Bg * nVar) != hipSuccess ||
-                hipMalloc((void **)&lb.d_grad_lb, 8 * Bg * total) != hipSuccess || hipMalloc((void **)&lb.d_grad_ub, 8 * Bg * total) != hipSuccess ||
-                hipMalloc((void **)&lb.d_meta, 8 * Bg) != hipSuccess) // (last: its presence says that the others are there)
-                throw Exception("hipMalloc failed (lexls_lsi_batch_solve_adjoint)");
-        }
-    }
-
-    /// what lsi_adjoint_scatter_kernel reads next to the map, for instance k of group g: the activation type of every row of its final problem in
-    /// form_final_problem's row order, its status of the run and its number of fixed variables
-    void form_adjoint_routes(uint32_t g, uint32_t k, LambdaBufs &lb)
-    {
-        const uint32_t b   = lo[g] + k;
-        const uint16_t *na = ws_na.data() + (size_t)b * nObj;
-        const uint8_t *ty  = ws_type.data() + (size_t)b * total;
-        uint8_t *out       = lb.types.data() + (size_t)k * total;
-        const uint32_t nf  = off ? std::min<uint32_t>(na[0], nVar) : 0u;
-        uint32_t r         = 0;
-        for (uint32_t a = 0; a < nf; a++) out[r++] = ty[a];
-        for (uint32_t o = off; o < nObj; o++)
-            for (uint32_t a = 0; a < na[o]; a++) out[r++] = ty[first[o] + a];
-        lb.meta[2 * k]     = ws_status[b];
-        lb.meta[2 * k + 1] = static_cast<int32_t>(nf);
-    }
-
-    /// the routes of the scatter kernels (map, types, meta: form_final_problem's and form_adjoint_routes') on the device, in the group's stream —
-    /// once per run, whichever adjoint call comes first (behind ensure_final_factor, which forms the map)
-    void upload_adjoint_routes(uint32_t g, const char *who)
-    {
-        if (adj_uploaded[g]) return;
-        BatchCtx &ctx     = *grp[g];
-        LambdaBufs &lb    = *lam_bufs[g];
-        const size_t rows = (size_t)ctx.B * total;
-        pool->run(ctx.B, [&](uint32_t k) { form_adjoint_routes(g, k, lb); });
-        if (hipMemcpyAsync(lb.d_map, lb.map.data(), 4 * ((size_t)ctx.B + rows), hipMemcpyHostToDevice, ctx.stream) != hipSuccess ||
-            hipMemcpyAsync(lb.d_types, lb.types.data(), rows, hipMemcpyHostToDevice, ctx.stream) != hipSuccess ||
-            hipMemcpyAsync(lb.d_meta, lb.meta.data(), 8 * (size_t)ctx.B, hipMemcpyHostToDevice, ctx.stream) != hipSuccess)
-            throw Exception(std::string(who) + ": hipMemcpyAsync failed (row map)");
-        adj_uploaded[g] = 1;
-    }
-
-    /// lexls_lsi_batch_solve_adjoint(_device): d loss / d lb and d loss / d ub of the last run from g = d loss / d x.  Per group, in its stream: the
-    /// final equality problems factorized with the factor kept (ensure_final_factor: get_lambda's stage, shared with it), their adjoint
-    /// (lexls_lse_solve_adjoint_device on the group's rows of g), lsi_adjoint_scatter_kernel into the user's constraint order.
-    /// on_device: g and the outputs are memory of the batch's device (nothing of them passes through the host); else the host's, staged in the
-    /// groups' buffers.  Either output may be NULL.  Waits for the groups' streams before it returns.
-    int solve_adjoint(const double *g_in, double *grad_lb, double *grad_ub, bool on_device)
-    {
-        const char *who = on_device ? "lexls_lsi_batch_solve_adjoint_device" : "lexls_lsi_batch_solve_adjoint";
-        if (lam_rc < 0) throw Exception(std::string(who) + ": no completed lexls_lsi_batch_run on this batch");
-        if (adj_rc != LEXLS_OK) // the rules of lexls_lsi_batch_get_lambda and its reason, but for the regularized runs set_adjoint_rule serves
-        {
-            lexls_internal_set_error(adj_msg.c_str());
-            return adj_rc;
-        }
-        if (hipSetDevice(device) != hipSuccess) throw Exception(std::string(who) + ": hipSetDevice failed");
-        ensure_adjoint_bufs();
-        for (uint32_t g = 0; g < nGroups; g++)
-        {
-            BatchCtx &ctx         = *grp[g];
-            LambdaBufs &lb        = *lam_bufs[g];
-            const size_t rows     = (size_t)ctx.B * total, r0 = (size_t)lo[g] * total;
-            const bool any_active = ensure_final_factor(g, []() {});
-            upload_adjoint_routes(g, who);
-            const double *d_g = g_in + (size_t)lo[g] * nVar;
-            double *d_lb = grad_lb ? grad_lb + r0 : NULL, *d_ub = grad_ub ? grad_ub + r0 : NULL;
-            if (!on_device)
-            {
-                // with an instance mask the entries of a skipped instance keep the caller's bits: they travel to the staging buffers first
-                if (hipMemcpyAsync(lb.d_g, d_g, 8 * (size_t)ctx.B * nVar, hipMemcpyHostToDevice, ctx.stream) != hipSuccess ||
-                    (group_mask(g) && grad_lb && hipMemcpyAsync(lb.d_grad_lb, grad_lb + r0, 8 * rows, hipMemcpyHostToDevice, ctx.stream) != hipSuccess) ||
-                    (group_mask(g) && grad_ub && hipMemcpyAsync(lb.d_grad_ub, grad_ub + r0, 8 * rows, hipMemcpyHostToDevice, ctx.stream) != hipSuccess))
-                    throw Exception(std::string(who) + ": hipMemcpyAsync failed (g)");
-                d_g = lb.d_g, d_lb = grad_lb ? lb.d_grad_lb : NULL, d_ub = grad_ub ? lb.d_grad_ub : NULL;
-            }
-            // nobody has an active constraint: nothing was factorized, every entry is zero — the scatter kernel reads no gradient (nact = 0)
-            if (any_active) hip_check(lexls_lse_solve_adjoint_device(ctx.h, d_g, lb.d_grad_rhs, lb.d_grad_fixed));
-            hipLaunchKernelGGL(lsi_adjoint_scatter_kernel, dim3(ctx.B), dim3(64), 0, ctx.stream, lb.d_grad_rhs, lb.d_grad_fixed, lb.d_map, lb.d_types, lb.d_meta, ctx.B,
-                               (uint32_t)total, nVar, ctx.cap, d_lb, d_ub, group_mask(g));
-            if (hipGetLastError() != hipSuccess) throw Exception("lsi_adjoint_scatter_kernel launch failed");
-            if (!on_device && ((grad_lb && hipMemcpyAsync(grad_lb + r0, lb.d_grad_lb, 8 * rows, hipMemcpyDeviceToHost, ctx.stream) != hipSuccess) ||
-                               (grad_ub && hipMemcpyAsync(grad_ub + r0, lb.d_grad_ub, 8 * rows, hipMemcpyDeviceToHost, ctx.stream) != hipSuccess)))
-                throw Exception(std::string(who) + ": hipMemcpyAsync failed (results)");
-        }
-        for (uint32_t g = 0; g < nGroups; g++)
-            if (hipStreamSynchronize(grp[g]->stream) != hipSuccess) throw Exception(std::string(who) + ": stream synchronisation failed");
-        return LEXLS_OK;
-    }
-
-    /// the groups' buffers of solve_adjoint_multi: made for the largest ncot so far
-    void ensure_adjoint_multi_bufs(uint32_t ncot)
-    {
-        ensure_adjoint_bufs();
-        for (uint32_t g = 0; g < nGroups; g++)
-        {
-            LambdaBufs &lb = *lam_bufs[g];
-            if (ncot <= lb.m_room) continue;
-            const size_t rows = (size_t)grp[g]->B * ncot, cap = grp[g]->cap;
-            lb.m_room = 0;
-            for (double **q : {&lb.d_mg, &lb.d_mgrad_rhs, &lb.d_mgrad_fixed, &lb.d_mgrad_lb, &lb.d_mgrad_ub})
-            {
-                if (*q) (void)hipFree(*q);
-                *q = NULL;
-            }
-            if (hipMalloc((void **)&lb.d_mg, 8 * rows * nVar) != hipSuccess || hipMalloc((void **)&lb.d_mgrad_rhs, 8 * rows * (cap ? cap : 1)) != hipSuccess ||
-                hipMalloc((void **)&lb.d_mgrad_fixed, 8 * rows * nVar) != hipSuccess || hipMalloc((void **)&lb.d_mgrad_lb, 8 * rows * (total ? total : 1)) != hipSuccess ||
-                hipMalloc((void **)&lb.d_mgrad_ub, 8 * rows * (total ? total : 1)) != hipSuccess)
-                throw Exception("hipMalloc failed (lexls_lsi_batch_solve_adjoint_multi)");
-            lb.m_room = ncot;
-        }
-    }
-
-    /// lexls_lsi_batch_solve_adjoint_multi(_device): solve_adjoint for ncot cotangents per instance — G batch x ncot x nVar, the outputs batch x ncot x
-    /// total.  The same stages: ensure_final_factor (shared with get_lambda and solve_adjoint), the routes of the scatter (uploaded once per run),
-    /// lexls_lse_solve_adjoint_multi_device on the group's rows of G, lsi_adjoint_scatter_multi_kernel.
-    int solve_adjoint_multi(const double *G_in, uint32_t ncot, double *grad_lb, double *grad_ub, bool on_device)
-    {
-        const char *who = on_device ? "lexls_lsi_batch_solve_adjoint_multi_device" : "lexls_lsi_batch_solve_adjoint_multi";
-        if (lam_rc < 0) throw Exception(std::string(who) + ": no completed lexls_lsi_batch_run on this batch");
-        if (lam_rc != LEXLS_OK) // the rules of lexls_lsi_batch_get_lambda, and its reason
-        {
-            lexls_internal_set_error(lam_msg.c_str());
-            return lam_rc;
-        }
-        if (ncot > 65535u) throw Exception(std::string(who) + ": more than 65535 cotangents per instance");
-        if (hipSetDevice(device) != hipSuccess) throw Exception(std::string(who) + ": hipSetDevice failed");
-        ensure_adjoint_multi_bufs(ncot);
-        for (uint32_t g = 0; g < nGroups; g++)
-        {
-            BatchCtx &ctx         = *grp[g];
-            LambdaBufs &lb        = *lam_bufs[g];
-            const size_t r0 = (size_t)lo[g] * ncot * total, orows = (size_t)ctx.B * ncot * total;
-            const bool any_active = ensure_final_factor(g, []() {});
-            upload_adjoint_routes(g, who);
-            const double *d_G = G_in + (size_t)lo[g] * ncot * nVar;
-            double *d_lb = grad_lb ? grad_lb + r0 : NULL, *d_ub = grad_ub ? grad_ub + r0 : NULL;
-            if (!on_device)
-            {
-                // with an instance mask the entries of a skipped instance keep the caller's bits: they travel to the staging buffers first
-                if (hipMemcpyAsync(lb.d_mg, d_G, 8 * (size_t)ctx.B * ncot * nVar, hipMemcpyHostToDevice, ctx.stream) != hipSuccess ||
-                    (group_mask(g) && grad_lb && hipMemcpyAsync(lb.d_mgrad_lb, grad_lb + r0, 8 * orows, hipMemcpyHostToDevice, ctx.stream) != hipSuccess) ||
-                    (group_mask(g) && grad_ub && hipMemcpyAsync(lb.d_mgrad_ub, grad_ub + r0, 8 * orows, hipMemcpyHostToDevice, ctx.stream) != hipSuccess))
-                    throw Exception(std::string(who) + ": hipMemcpyAsync failed (G)");
-                d_G = lb.d_mg, d_lb = grad_lb ? lb.d_mgrad_lb : NULL, d_ub = grad_ub ? lb.d_mgrad_ub : NULL;
-            }
-            // nobody has an active constraint: nothing was factorized, every entry is zero — the scatter kernel reads no gradient (nact = 0)
-            if (any_active) hip_check(lexls_lse_solve_adjoint_multi_device(ctx.h, d_G, ncot, lb.d_mgrad_rhs, lb.d_mgrad_fixed));
-            hipLaunchKernelGGL(lsi_adjoint_scatter_multi_kernel, dim3(ctx.B, ncot), dim3(64), 0, ctx.stream, lb.d_mgrad_rhs, lb.d_mgrad_fixed, lb.d_map, lb.d_types, lb.d_meta,
-                               ctx.B, ncot, (uint32_t)total, nVar, ctx.cap, d_lb, d_ub, group_mask(g));
-            if (hipGetLastError() != hipSuccess) throw Exception("lsi_adjoint_scatter_multi_kernel launch failed");
-            if (!on_device && ((grad_lb && hipMemcpyAsync(grad_lb + r0, lb.d_mgrad_lb, 8 * orows, hipMemcpyDeviceToHost, ctx.stream) != hipSuccess) ||
-                               (grad_ub && hipMemcpyAsync(grad_ub + r0, lb.d_mgrad_ub, 8 * orows, hipMemcpyDeviceToHost, ctx.stream) != hipSuccess)))
-                throw Exception(std::string(who) + ": hipMemcpyAsync failed (results)");
-        }
-        for (uint32_t g = 0; g < nGroups; g++)
-            if (hipStreamSynchronize(grp[g]->stream) != hipSuccess) throw Exception(std::string(who) + ": stream synchronisation failed");
-        return LEXLS_OK;
-    }
-
-    /// the groups' buffers of solve_adjoint_matrix, made at the first call; host_form: also the staging buffers of a host caller
-    void ensure_adjoint_matrix_bufs(bool host_form)
-    {
-        ensure_adjoint_bufs();
-        std::vector<uint32_t> shape(4 * (size_t)nObj);
-        for (uint32_t k = 0; k < nObj; k++) shape[4 * k] = dims[k], shape[4 * k + 1] = types[k] == 1 ? 0u : 1u, shape[4 * k + 2] = data_off[k], shape[4 * k + 3] = first[k];
-        for (uint32_t g = 0; g < nGroups; g++)
-        {
-            LambdaBufs &lb  = *lam_bufs[g];
-            const size_t Bg = grp[g]->B, cap = grp[g]->cap;
-            if (!lb.d_shape)
-            {
-                if (hipMalloc((void **)&lb.d_grad_lod, 8 * Bg * (nVar + 1) * (cap ? cap : 1)) != hipSuccess || hipMalloc((void **)&lb.d_lse_flag, Bg) != hipSuccess ||
-                    hipMalloc((void **)&lb.d_shape, 16 * (size_t)nObj) != hipSuccess) // (last: its presence says that the others are there)
-                    throw Exception("hipMalloc failed (lexls_lsi_batch_solve_adjoint_matrix)");
-                if (hipMemcpy(lb.d_shape, shape.data(), 16 * (size_t)nObj, hipMemcpyHostToDevice) != hipSuccess)
-                    throw Exception("hipMemcpy failed (lexls_lsi_batch_solve_adjoint_matrix)");
-            }
-            if (host_form && !lb.d_mat_flag &&
-                (hipMalloc((void **)&lb.d_mat_out, 8 * Bg * (per_data ? per_data : 1)) != hipSuccess || hipMalloc((void **)&lb.d_mat_flag, Bg) != hipSuccess))
-                throw Exception("hipMalloc failed (lexls_lsi_batch_solve_adjoint_matrix)");
-        }
-    }
-
-    /// lexls_lsi_batch_solve_adjoint_matrix(_device): d loss / d (constraint data) of the last run from g = d loss / d x, in the layout
-    /// lexls_lsi_batch_run_device reads, and the instances' differentiable flags (may be NULL).  Per group, in its stream: the final equality
-    /// problems factorized with the factor kept (ensure_final_factor, shared with get_lambda and solve_adjoint), their x once per run
-    /// (lexls_lse_solve on that factor: final_solved), the matrix chain of the equality solver on the group's rows of g (grad_lod, N^T g from the
-    /// chain's own solve_adjoint launch, the rank-stability flags), lsi_adjoint_matrix_scatter_kernel into the caller's layout.
-    /// on_device: g and the outputs are memory of the batch's device; else the host's, staged in the groups' buffers.  Waits for the groups' streams.
-    int solve_adjoint_matrix(const double *g_in, double *grad_data, uint8_t *differentiable, bool on_device)
-    {
-        const char *who = on_device ? "lexls_lsi_batch_solve_adjoint_matrix_device" : "lexls_lsi_batch_solve_adjoint_matrix";
-        if (lam_rc < 0) throw Exception(std::string(who) + ": no completed lexls_lsi_batch_run on this batch");
-        if (lam_rc != LEXLS_OK) // the rules of lexls_lsi_batch_get_lambda, and its reason
-        {
-            lexls_internal_set_error(lam_msg.c_str());
-            return lam_rc;
-        }
-        if (hipSetDevice(device) != hipSuccess) throw Exception(std::string(who) + ": hipSetDevice failed");
-        ensure_adjoint_matrix_bufs(!on_device);
-        for (uint32_t g = 0; g < nGroups; g++)
-        {
-            BatchCtx &ctx         = *grp[g];
-            LambdaBufs &lb        = *lam_bufs[g];
-            const size_t elems    = (size_t)ctx.B * per_data, e0 = (size_t)lo[g] * per_data;
-            const bool any_active = ensure_final_factor(g, []() {});
-            upload_adjoint_routes(g, who);
-            if (any_active && !final_solved[g])
-            {
-                hip_check(lexls_lse_solve(ctx.h)); // the stage factorizes only: the chain wants the x of this factor
-                final_solved[g] = 1;
-            }
-            const double *d_g = g_in + (size_t)lo[g] * nVar;
-            double *d_out     = grad_data + e0;
-            uint8_t *d_flag   = differentiable ? differentiable + lo[g] : NULL;
-            if (!on_device)
-            {
-                // with an instance mask the slice and the flag of a skipped instance keep the caller's bits: they travel to the staging buffers first
-                if (hipMemcpyAsync(lb.d_g, d_g, 8 * (size_t)ctx.B * nVar, hipMemcpyHostToDevice, ctx.stream) != hipSuccess ||
-                    (group_mask(g) && hipMemcpyAsync(lb.d_mat_out, grad_data + e0, 8 * elems, hipMemcpyHostToDevice, ctx.stream) != hipSuccess) ||
-                    (group_mask(g) && differentiable && hipMemcpyAsync(lb.d_mat_flag, differentiable + lo[g], ctx.B, hipMemcpyHostToDevice, ctx.stream) != hipSuccess))
-                    throw Exception(std::string(who) + ": hipMemcpyAsync failed (g)");
-                d_g = lb.d_g, d_out = lb.d_mat_out, d_flag = differentiable ? lb.d_mat_flag : NULL;
-            }
-            // nobody has an active constraint: nothing was factorized, every entry is zero and every solved instance differentiable — the scatter
-            // kernel reads no gradient and no flag of the equality solver
-            if (any_active) hip_check(lexls_internal_solve_adjoint_matrix(ctx.h, d_g, lb.d_grad_lod, lb.d_grad_fixed, lb.d_lse_flag));
-            hipLaunchKernelGGL(lsi_adjoint_matrix_scatter_kernel, dim3(ctx.B), dim3(ADJM_NT), 0, ctx.stream, lb.d_grad_lod, lb.d_grad_fixed,
-                               any_active ? lb.d_lse_flag : (const uint8_t *)NULL, lb.d_map, lb.d_types, lb.d_meta, lb.d_shape, ctx.B, nObj, (uint32_t)total, nVar, ctx.cap,
-                               per_data, d_out, d_flag, group_mask(g));
-            if (hipGetLastError() != hipSuccess) throw Exception("lsi_adjoint_matrix_scatter_kernel launch failed");
-            if (!on_device && (hipMemcpyAsync(grad_data + e0, lb.d_mat_out, 8 * elems, hipMemcpyDeviceToHost, ctx.stream) != hipSuccess ||
-                               (differentiable && hipMemcpyAsync(differentiable + lo[g], lb.d_mat_flag, ctx.B, hipMemcpyDeviceToHost, ctx.stream) != hipSuccess)))
-                throw Exception(std::string(who) + ": hipMemcpyAsync failed (results)");
-        }
-        for (uint32_t g = 0; g < nGroups; g++)
-            if (hipStreamSynchronize(grp[g]->stream) != hipSuccess) throw Exception(std::string(who) + ": stream synchronisation failed");
-        return LEXLS_OK;
-    }
-
-    /// LexLSI::getLambda (lexlsi.h:552-605) for every instance of the last run, on the device in each group's stream: the final equality
-    /// problems are formed (rows gathered by reference, fixed variables posted), factorized with the factor kept on a bit-exact kernel, all
-    /// objectives' multipliers taken in one sweep (lexls_lse_multipliers), scattered into the user's order, one copy back per group.
-    /// d_lambda (lexls_lsi_batch_run_device_ex): memory of the batch's device instead — the scatter kernel writes there, nothing is copied back
-    int get_lambda(double *h_lambda, double *d_lambda = NULL)
-    {
-        if (lam_rc < 0) throw Exception("lexls_lsi_batch_get_lambda: no completed lexls_lsi_batch_run on this batch");
-        if (lam_rc != LEXLS_OK)
-        {
-            lexls_internal_set_error(lam_msg.c_str());
-            return lam_rc;
-        }
-        if (!h_lambda && !d_lambda) throw Exception("lexls_lsi_batch_get_lambda: null output");
-        const uint32_t nObjL = nObj - off;
-        ensure_lambda_bufs();
-        // LEXLS_LSI_TIMING: the stages one by one (a synchronisation behind each) and their times on stderr
-        const bool timing = RunSwitches().timing;
-        double ts[4] = {0, 0, 0, 0}, tp = BatchCtx::now();
-        auto stage = [&](int i, BatchCtx &c) {
-            if (!timing) return;
-            hip_check(lexls_lse_synchronize(c.h));
-            const double t = BatchCtx::now();
-            ts[i] += t - tp;
-            tp = t;
-        };
-        for (uint32_t g = 0; g < nGroups; g++)
-        {
-            BatchCtx &ctx  = *grp[g];
-            LambdaBufs &lb = *lam_bufs[g];
-            const bool any_active = ensure_final_factor(g, [&]() { stage(0, ctx); });
-            stage(1, ctx);
-            if (any_active) hip_check(lexls_lse_multipliers(ctx.h));
-            stage(2, ctx);
-            // nobody has an active constraint: there is nothing to factorize and every row is zero — the scatter kernel reads no multiplier (nact = 0)
-            const double *d_mult = any_active ? lexls_internal_multipliers(ctx.h, NULL) : lb.d_out;
-            if (!d_mult) throw Exception("lexls_lsi_batch_get_lambda: no multipliers");
-            if (hipMemcpyAsync(lb.d_map, lb.map.data(), 4 * ((size_t)ctx.B + (size_t)ctx.B * total), hipMemcpyHostToDevice, ctx.stream) != hipSuccess)
-                throw Exception("hipMemcpyAsync failed (lexls_lsi_batch_get_lambda)");
-            hipLaunchKernelGGL(lsi_lambda_scatter_kernel, dim3(ctx.B), dim3(64), 0, ctx.stream, d_mult, lb.d_map, ctx.B, (uint32_t)total, nObj, nObjL, off,
-                               nVar + ctx.cap, d_lambda ? d_lambda + (size_t)lo[g] * total * nObj : lb.d_out, (const uint32_t *)NULL, d_lambda ? group_mask(g) : (const uint8_t *)NULL);
-            if (hipGetLastError() != hipSuccess) throw Exception("lsi_lambda_scatter_kernel launch failed");
-            if (!d_lambda && hipMemcpyAsync(h_lambda + (size_t)lo[g] * total * nObj, lb.d_out, 8 * (size_t)ctx.B * total * nObj, hipMemcpyDeviceToHost, ctx.stream) != hipSuccess)
-                throw Exception("hipMemcpyAsync failed (lexls_lsi_batch_get_lambda)");
-            stage(3, ctx);
-        }
-        for (uint32_t g = 0; g < nGroups; g++)
-            if (hipStreamSynchronize(grp[g]->stream) != hipSuccess) throw Exception("lexls_lsi_batch_get_lambda: stream synchronisation failed");
-        if (timing)
-            std::fprintf(stderr, "lexls_lsi_batch_get_lambda: %.4f ms = form the problems (host) %.4f + upload, gather, factorize %.4f + multipliers %.4f + scatter, copy back %.4f (%u groups)\n",
-                         1e3 * (ts[0] + ts[1] + ts[2] + ts[3]), 1e3 * ts[0], 1e3 * ts[1], 1e3 * ts[2], 1e3 * ts[3], nGroups);
-        return LEXLS_OK;
-    }
-
-
     /// LexLSI::getCyclingCounter() of every instance of the last run, whichever path served it
     int get_cycling_counters(uint32_t *h_counts) const
     {
-        if (lam_rc < 0) throw Exception("lexls_lsi_batch_get_cycling_counters: no completed lexls_lsi_batch_run on this batch");
+        if (!fin.ran()) throw Exception("lexls_lsi_batch_get_cycling_counters: no completed lexls_lsi_batch_run on this batch");
         if (!h_counts) throw Exception("lexls_lsi_batch_get_cycling_counters: null output");
         std::copy(cycling_count.begin(), cycling_count.end(), h_counts);
         return LEXLS_OK;
@@ -1201,9 +446,7 @@ struct lexls_lsi_batch_s
         if (par_.use_phase1_v0 && !h_x0) throw Exception("when use_phase1_v0 = true, x_guess has to be specified"); // (lexlsi.h:882, before any work)
         const ParametersLexLSI par = with_log_switch(par_);
         begin_working_set_log();
-        lam_rc  = -1;
-        forget_final_factor();
-        lam_tol = par.tol_linear_dependence;
+        fin.begin_run(par);
         last_kernel = "host";
         std::fill(cycling_count.begin(), cycling_count.end(), 0u);
         // getLambda of this run needs the rows gathered from resident constraint data, unrelaxed bounds and unregularized factorizations
@@ -1219,9 +462,8 @@ struct lexls_lsi_batch_s
         {
             run_one_by_one(r, lam_after == LEXLS_OK);
             finish_working_set_log();
-            lam_rc  = (off && !h_var_index) ? LEXLS_ERR_INVALID : lam_after;
-            lam_msg = lam_rc == LEXLS_ERR_INVALID ? "lexls_lsi_batch_get_lambda: the run had no variable indices" : lam_why;
-            set_adjoint_rule(par, false);
+            const bool no_indices = off && !h_var_index;
+            fin.set_rule(no_indices ? LEXLS_ERR_INVALID : lam_after, no_indices ? "lexls_lsi_batch_get_lambda: the run had no variable indices" : lam_why, par, false);
             return;
         }
         // LEXLS_LSI_DEVICE_PHASE1=1: no host objects, phase 1 is device work; so it is with per-instance factors in device memory, which no host
@@ -1230,9 +472,8 @@ struct lexls_lsi_batch_s
         {
             run_phase1_on_device(r, NULL);
             finish_working_set_log();
-            lam_rc  = (off && !h_var_index) ? LEXLS_ERR_INVALID : lam_after;
-            lam_msg = lam_rc == LEXLS_ERR_INVALID ? "lexls_lsi_batch_get_lambda: the run had no variable indices" : lam_why;
-            set_adjoint_rule(par, true);
+            const bool no_indices = off && !h_var_index;
+            fin.set_rule(no_indices ? LEXLS_ERR_INVALID : lam_after, no_indices ? "lexls_lsi_batch_get_lambda: the run had no variable indices" : lam_why, par, true);
             return;
         }
         r.t_begin = BatchCtx::now();
@@ -1245,9 +486,7 @@ struct lexls_lsi_batch_s
         collect(r);
         finish_working_set_log();
         report(r);
-        lam_rc  = lam_after;
-        lam_msg = lam_why;
-        set_adjoint_rule(par, r.resident);
+        fin.set_rule(lam_after, lam_why, par, r.resident);
         bool any_left = false;
         for (uint32_t b = 0; b < batch && !any_left; b++) any_left = r.lsi[b] != nullptr;
         if (any_left) pool->run(batch, [&](uint32_t b) { r.lsi[b].reset(); }); // a thousand LexLSI objects (dozens of vectors each): freed in parallel, not serially on return
@@ -1265,7 +504,7 @@ struct lexls_lsi_batch_s
             internal::LexLSI lsi;
             fs += solve_one(lsi, device, p, r.par, r.h_x + (size_t)b * nVar, r.h_info6 ? r.h_info6 + (size_t)b * 6 : NULL, r.h_active ? r.h_active + (size_t)b * total : NULL,
                             r.h_v ? r.h_v + (size_t)b * total : NULL).factorizations;
-            keep_working_set(b, lsi, p.data, p.var_index);
+            fin.keep_working_set(b, lsi, p.data, p.var_index);
             keep_host_log(b, lsi);
             cycling_count[b] = static_cast<uint32_t>(lsi.getCyclingCounter());
         }
@@ -1633,7 +872,7 @@ struct lexls_lsi_batch_s
             more               = more || going[g];
         }
         resident_chunks(r, going, more);
-        const bool keep_fixed_bounds = needs_final_problem(r.par);
+        const bool keep_fixed_bounds = fin.needs_final_problem(r.par);
         for (uint32_t g = 0; g < nGroups; g++)
         {
             BatchCtx &ctx = *grp[g];
@@ -1649,7 +888,7 @@ struct lexls_lsi_batch_s
                 uint32_t k;
                 BatchCtx &ctx = group_of_instance(b, k);
                 if (ctx.cycling) cycling_count[b] = ctx.rl.cyc(ctx.rws_host.data(), k)[CYC_COUNT];
-                keep_working_set_resident(b, ctx, k, NULL, NULL);
+                fin.keep_working_set_resident(b, ctx, k, NULL, NULL);
             }
         else
         {
@@ -1666,28 +905,18 @@ struct lexls_lsi_batch_s
         return par.cycling_handling_enabled ? "lexls_lsi_batch_get_lambda: not available after a run with cycling handling enabled (it may have relaxed bounds in the resident constraint data)"
                                                : "lexls_lsi_batch_get_lambda: not available after a regularized run";
     }
-    /// what lexls_lsi_batch_get_lambda answers after a run with these parameters (LEXLS_OK: it is served)
-    int lam_rc_after(const ParametersLexLSI &par) const
-    {
-        return (par.cycling_handling_enabled || par.regularization_type != REGULARIZATION_NONE || !gather || total > 65535) ? LEXLS_ERR_UNSUPPORTED : LEXLS_OK;
-    }
-
     /// lexls_lsi_batch_run_device(_ex): the caller has checked would_be_resident(par)
     void run_device(const DeviceArrays &dev, const double *h_reg_factors, const ParametersLexLSI &par)
     {
         begin_working_set_log(); // (no host objects: every entry is written on the device)
-        lam_rc      = -1;
-        forget_final_factor();
-        lam_tol     = par.tol_linear_dependence;
+        fin.begin_run(par);
         last_kernel = "host";
         std::fill(cycling_count.begin(), cycling_count.end(), 0u);
         Run r{NULL, NULL, NULL, h_reg_factors, NULL, NULL, par, NULL, NULL, NULL, NULL, NULL};
         take_instance_regularization(r);
         run_phase1_on_device(r, &dev);
         finish_working_set_log();
-        lam_rc  = lam_rc_after(par);
-        lam_msg = lam_msg_after_device_run(par);
-        set_adjoint_rule(par, true);
+        fin.set_rule(fin.lam_rc_after(par), lam_msg_after_device_run(par), par, true);
     }
 
     /// the runs lexls_lsi_batch_enqueue_device serves: those of run_device that the persistent launch takes, decided on numbers (every group's handle:
@@ -1706,7 +935,7 @@ struct lexls_lsi_batch_s
     void enqueue_device(hipStream_t s, const DeviceArrays &dev, const double *h_reg_factors, const ParametersLexLSI &par, uint32_t *d_status, double *d_lambda)
     {
         if (hipSetDevice(device) != hipSuccess) throw Exception("hipSetDevice failed (lexls_lsi_batch_enqueue_device)");
-        if (d_lambda) ensure_lambda_bufs();
+        if (d_lambda) fin.ensure_lambda_bufs();
         if (!async)
         {
             std::unique_ptr<Async> a(new Async());
@@ -1745,9 +974,7 @@ struct lexls_lsi_batch_s
         }
         // the host's record of the last run: nothing of it is valid until finish()
         wlog_valid  = false;
-        lam_rc      = -1;
-        forget_final_factor();
-        lam_tol     = par.tol_linear_dependence;
+        fin.begin_run(par);
         last_kernel = "host";
         std::fill(cycling_count.begin(), cycling_count.end(), 0u);
         as.pending = as.enqueued = true;
@@ -1793,7 +1020,7 @@ struct lexls_lsi_batch_s
                 throw Exception("copy of the variable indices failed");
             ctx.enqueue_phase1_setup(dev.x0 ? dev.x0 + (size_t)lo[g] * nVar : NULL, dev.active_guess ? dev.active_guess + (size_t)lo[g] * total : NULL, lo[g], max_fact,
                                      dev.v0 ? dev.v0 + (size_t)lo[g] * total : NULL, as.d_fault, group_mask(g), group_limits(g), group_obj_dims(g), p1_hot_word(par));
-            const bool keep_fixed_bounds = needs_final_problem(par);
+            const bool keep_fixed_bounds = fin.needs_final_problem(par);
             ctx.enqueue_phase1_gate(as.d_fault, max_fact);
             if (par.use_phase1_v0)
                 ctx.enqueue_phase1_v0(max_fact, false);
@@ -1802,13 +1029,7 @@ struct lexls_lsi_batch_s
             ctx.enqueue_fused(par.tol_wrong_sign_lambda, par.tol_correct_sign_lambda, max_fact);
             ctx.scatter_results(dev.x + (size_t)lo[g] * nVar, dev.info6 ? dev.info6 + (size_t)lo[g] * 6 : NULL, dev.active ? dev.active + (size_t)lo[g] * total : NULL,
                                 dev.v ? dev.v + (size_t)lo[g] * total : NULL, keep_fixed_bounds, dev.cycling_counts ? dev.cycling_counts + lo[g] : NULL, as.d_fault, g == 0 ? d_status : NULL, group_mask(g));
-            if (d_lambda) // get_lambda(NULL, d_lambda) with the final problems formed where the working sets live
-            {
-                const double *d_mult = ctx.enqueue_lambda(max_fact, lam_bufs[g]->d_map, as.d_fault, group_mask(g));
-                hipLaunchKernelGGL(lsi_lambda_scatter_kernel, dim3(ctx.B), dim3(64), 0, ctx.stream, d_mult, lam_bufs[g]->d_map, ctx.B, (uint32_t)total, nObj, nObjL, off, nVar + ctx.cap,
-                                   d_lambda + (size_t)lo[g] * total * nObj, (const uint32_t *)as.d_fault, group_mask(g));
-                if (hipGetLastError() != hipSuccess) throw Exception("lsi_lambda_scatter_kernel launch failed");
-            }
+            if (d_lambda) fin.enqueue_lambda(g, max_fact, as.d_fault, d_lambda);
             if (hipEventRecord(ctx.ev_joined, ctx.stream) != hipSuccess || hipStreamWaitEvent(s, ctx.ev_joined, 0) != hipSuccess)
                 throw Exception("hipEventRecord / hipStreamWaitEvent failed (lexls_lsi_batch_enqueue_device)");
         }
@@ -1822,8 +1043,7 @@ struct lexls_lsi_batch_s
         Async &as = *async;
         if (hipSetDevice(device) != hipSuccess || hipStreamSynchronize(s ? s : as.stream) != hipSuccess) throw Exception("lexls_lsi_batch_finish: stream synchronisation failed");
         as.pending  = false;
-        lam_rc      = -1;
-        forget_final_factor();
+        fin.forget();
         last_kernel = "host";
         wlog_valid  = false;
         std::fill(cycling_count.begin(), cycling_count.end(), 0u);
@@ -1832,7 +1052,7 @@ struct lexls_lsi_batch_s
         const uint32_t fault = as.fault_host[0];
         if (fault != 0xffffffffu) throw Exception("lexls_lsi_batch_run: instance " + std::to_string(fault >> 3) + ": " + p1_fault_text(fault & 7u));
         const ParametersLexLSI &par = as.par;
-        const bool keep_fixed_bounds = needs_final_problem(par);
+        const bool keep_fixed_bounds = fin.needs_final_problem(par);
         int rounds_fs = 0, rounds_sens = 0, rounds_step = 0;
         for (uint32_t g = 0; g < nGroups; g++)
         {
@@ -1849,13 +1069,11 @@ struct lexls_lsi_batch_s
             uint32_t k;
             BatchCtx &ctx = group_of_instance(b, k);
             if (ctx.cycling) cycling_count[b] = ctx.rl.cyc(ctx.rws_host.data(), k)[CYC_COUNT];
-            keep_working_set_resident(b, ctx, k, NULL, NULL);
+            fin.keep_working_set_resident(b, ctx, k, NULL, NULL);
         }
         last_stats[0] = rounds_fs, last_stats[1] = rounds_sens, last_stats[2] = rounds_step, last_stats[3] = (int32_t)nGroups;
         wlog_valid = wlog != nullptr;
-        lam_rc     = lam_rc_after(par);
-        lam_msg    = lam_msg_after_device_run(par);
-        set_adjoint_rule(par, true);
+        fin.set_rule(fin.lam_rc_after(par), lam_msg_after_device_run(par), par, true);
         return LEXLS_OK;
     }
 
@@ -1871,13 +1089,13 @@ struct lexls_lsi_batch_s
             if (r.h_active) std::copy(ctx.rl.ctr_state(ctx.rws_host.data(), k), ctx.rl.ctr_state(ctx.rws_host.data(), k) + total, r.h_active + (size_t)b * total);
             if (r.h_info6) std::memcpy(r.h_info6 + (size_t)b * 6, ctx.rl.info(ctx.rws_host.data(), k), 6 * sizeof(int32_t));
             if (ctx.cycling) cycling_count[b] = ctx.rl.cyc(ctx.rws_host.data(), k)[CYC_COUNT];
-            keep_working_set_resident(b, ctx, k, r.prob[b].data, r.prob[b].var_index);
+            fin.keep_working_set_resident(b, ctx, k, r.prob[b].data, r.prob[b].var_index);
             return;
         }
         runner::LsiInfo info;
         runner::collect(*r.lsi[b], r.prob[b], x, &info, r.h_active ? r.h_active + (size_t)b * total : NULL, v);
         if (r.h_info6) std::memcpy(r.h_info6 + (size_t)b * 6, &info, sizeof(info));
-        keep_working_set(b, *r.lsi[b], r.prob[b].data, r.prob[b].var_index);
+        fin.keep_working_set(b, *r.lsi[b], r.prob[b].data, r.prob[b].var_index);
         keep_host_log(b, *r.lsi[b]);
         cycling_count[b] = static_cast<uint32_t>(r.lsi[b]->getCyclingCounter());
         if (r.step && ctx.on_device[k]) unpack_state(ctx.state_host.data() + (size_t)k * ctx.shape.SD, nVar, total, x, v);

@@ -1,5 +1,5 @@
-"""Cases that hold the gradients of batched LexLSI solutions with respect to the bounds (lexls_lsi_batch_solve_adjoint, lexls_amd/csrc/lsi_batch.h:
-lsi_adjoint_scatter_kernel behind get_lambda's final-problem stage and solve_adjoint_kernel) to two references, both built from the oracle alone
+"""Cases that hold the gradients of batched LexLSI solutions with respect to the bounds (lexls_lsi_batch_solve_adjoint, lexls_amd/csrc/lsi_final.h:
+lsi_adjoint_scatter_multi_kernel behind get_lambda's final-problem stage and solve_adjoint_kernel) to two references, both built from the oracle alone
 (tests/test_lsi_adjoint_cases.py asserts on the CPU that they agree; tests/test_gpu_lsi_adjoint.py compares the device with them).
 
 At an instance that ended PROBLEM_SOLVED x is the basic solution of the equality problem of its final working set W: right-hand sides = the active
@@ -73,7 +73,7 @@ CASES = {
     "ik": dict(n=40, dims=(12, 12, 12, 12, 12), simple=True, batch=8, seed=20300514),
 }
 BUDGET = dict(n=4, dims=(4, 2, 2), simple=True, batch=6, seed=20300601, wide=(0, 2, 4))
-# the scatter kernels tile the user rows by ADJ_TILE = 1024 (lexls_amd/csrc/lsi_batch.h): 1036 rows, with active ones on both sides of row 1024
+# the scatter kernels tile the user rows by ADJ_TILE = 1024 (lexls_amd/csrc/lsi_final.h): 1036 rows, with active ones on both sides of row 1024
 TILE = dict(n=4, dims=(4, 1030, 2), simple=True, batch=2, seed=20310301, equalities=(5, 1027), far=100.0)
 ADJ_TILE = 1024
 

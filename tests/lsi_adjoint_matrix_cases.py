@@ -1,5 +1,5 @@
 """Cases that hold the gradients of batched LexLSI solutions with respect to the whole constraint data (lexls_lsi_batch_solve_adjoint_matrix,
-lexls_amd/csrc/lsi_batch.h: lsi_adjoint_matrix_scatter_kernel behind the final-problem stage and the matrix chain of the equality solver) to two
+lexls_amd/csrc/lsi_final.h: lsi_adjoint_matrix_scatter_kernel behind the final-problem stage and the matrix chain of the equality solver) to two
 references, both built from the oracle alone (tests/test_lsi_adjoint_matrix_cases.py asserts on the CPU that they agree;
 tests/test_gpu_lsi_adjoint_matrix.py compares the device with reference (A)).
 

@@ -9,7 +9,7 @@ arithmetic decides what a cotangent meets, on the cases of tests/lsi_adjoint_cas
              limit of its own, that writes its arrays for the parent to compare.
     forms    LEXLS_ADJOINT_MULTI_FORM (read by the launcher at every call) = hbm: the bits of the default run; = single: the bits of K calls of
              solve_adjoint_device.
-    tile     lsi_adjoint_scatter(_multi)_kernel tile the user rows by 1024: the `tile` case has 1036 and a working set on both sides of row 1024.
+    tile     lsi_adjoint_scatter_multi_kernel (the single call: ncot = 1) tiles the user rows by 1024: the `tile` case has 1036 and a working set on both sides of row 1024.
              Reference (A) of tests/lsi_adjoint_cases.py within its TOL, exact zeros everywhere else in both tiles."""
 import ctypes as C
 import os
