@@ -12,6 +12,7 @@ namespace lexls
     }
     // lqr_generic.hip — any shape, one workgroup per problem (id: one of the generic_* forms, dispatch::generic_choice)
     hipError_t launch_lqr_generic(LseArgs a, uint32_t max_rows, KernelId id, bool write_factor, bool do_solve, hipStream_t s);
+    // lse_postfactor.hip — solve() and the residuals on a kept factor
     // (variant, where given: the name of the kernel variant launched — lexls_lse_last_consumer_kernel; host bookkeeping only)
     hipError_t launch_solve_generic(const LseArgs &a, hipStream_t s, bool reciprocal_diagonal = false, const char **variant = nullptr);
     hipError_t launch_residual(const LseArgs &a, hipStream_t s, const char **variant = nullptr);
@@ -45,7 +46,7 @@ namespace lexls
     size_t adjoint_matrix_work_bytes(const LseArgs &a);
     hipError_t launch_solve_adjoint_matrix(const LseArgs &a, const double *d_g, double *d_grad_lod, uint8_t *d_differentiable, void *d_work, uint32_t sweep_level_dim_hint,
                                            hipStream_t s, const char **variant = nullptr, double *d_grad_fixed = nullptr);
-    // lqr_generic.hip again — the sensitivity, multiplier and least-norm kernels
+    // lse_postfactor.hip — the sensitivity, multiplier and least-norm kernels
     hipError_t launch_sensitivity(const LseArgs &a, const int32_t *d_obj_index, int32_t obj_all, double tolW, double tolC, hipStream_t s, bool scan_up = false,
                                   uint32_t sweep_level_dim_hint = 0, // hint = largest level dimension of the batch (enables the single-sweep kernel)
                                   bool collect = false,              // the wrong-sign SET into a.wrong_sign instead of one candidate (lexls_lse_sensitivity_collect)

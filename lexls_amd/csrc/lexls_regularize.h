@@ -8,13 +8,12 @@
 // factorization because solveLeastNorm_3 reads it], D n x n, D0 n x n, d n, out n, 8 scalars.
 #pragma once
 #include "lexls_kernels.h"
+#include "lse_spd_solve.h"
 
 namespace lexls
 {
     namespace
     {
-        __device__ __forceinline__ double rfma(double a, double b, double c) { return __builtin_fma(a, b, c); }
-
         __host__ __device__ inline size_t reg_scratch_doubles(uint32_t n) { return (size_t)n * (n + 1) + 2 * (size_t)n * n + 2 * (size_t)n + 8 + 10 * (size_t)n; }
 
         /// by-products of the experimental type 7 per problem (lexlse.h:96-99): X_mu nObj x n (a column per level, contiguous),
@@ -103,13 +102,6 @@ namespace lexls
             return v;
         }
 
-        __device__ __forceinline__ double reg_rdlane(double v, int lane)
-        {
-            const int lo = __builtin_amdgcn_readlane(__double2loint(v), lane);
-            const int hi = __builtin_amdgcn_readlane(__double2hiint(v), lane);
-            return __hiloint2double(hi, lo);
-        }
-
         /// acc + sum of x[i]^2, i = 0 .. len-1 in that order, by ONE wavefront (len <= 64): one load per lane, then the ordered fma chain on
         /// values read across lanes — every lane ends with the same sum (what thread 0's loop over the vector gave, without its load per term)
         __device__ __forceinline__ double reg_wave_sumsq(const double *x, uint32_t len, uint32_t lane, double acc)
@@ -117,123 +109,18 @@ namespace lexls
             const double xi = lane < len ? x[lane] : 0.0;
             for (uint32_t i = 0; i < len; i++)
             {
-                const double t = reg_rdlane(xi, (int)i);
-                acc            = rfma(t, t, acc);
+                const double t = rdlane(xi, (int)i);
+                acc            = dfma(t, t, acc);
             }
             return acc;
         }
 
-        /// reg_cholesky_solve for ONE wavefront (the register-resident kernel), N <= 64: lane i owns row i of the lower triangle and d_i.
-        /// Panels of 16 columns at a time in registers; a finished column's entries reach the other lanes by v_readlane, the columns of
-        /// earlier panels come back from the work matrix as the lane's OWN row (no lane reads what another lane wrote until the backward
-        /// substitution) — so the 3 N dependent steps (square root / division each) cost their arithmetic, not a memory round trip plus a loop
-        /// of unknown trip count each, which is where the routine's time went.  Same operations on the same operands in the same order as
-        /// the workgroup form below (entry (i, j) receives the products k = 0 .. j-1 in that order; substitutions column by column), so the
-        /// results are the same bits.  The panel loops have run-time trip counts and a fixed body: ~70 registers, a few KB of code.
-        __device__ __noinline__ void reg_cholesky_solve_wave(const RegView &v, uint32_t N, uint32_t lane)
-        {
-            constexpr int PB = 16;
-            const bool on    = lane < N;
-            double row[PB];
-            for (uint32_t c0 = 0; c0 < N; c0 += PB)
-            {
-#pragma unroll
-                for (int jj = 0; jj < PB; jj++) row[jj] = (on && c0 + jj <= lane && c0 + jj < N) ? v.dd(lane, c0 + jj) : 0.0;
-                for (uint32_t k = 0; k < c0; k++) // the columns of the panels before: own entry from the matrix, the panel rows' entries from their lanes
-                {
-                    const double lik = (on && lane >= c0) ? v.dd(lane, k) : 0.0;
-#pragma unroll
-                    for (int jj = 0; jj < PB; jj++) row[jj] = rfma(-lik, reg_rdlane(lik, (int)(c0 + jj) & 63), row[jj]);
-                }
-#pragma unroll
-                for (int kk = 0; kk < PB; kk++)
-                    if (c0 + kk < N) // uniform
-                    {
-                        const double lkk = sqrt(reg_rdlane(row[kk], (int)(c0 + kk)));
-                        const double lik = (lane == c0 + kk) ? lkk : row[kk] / lkk; // (zeros above the diagonal and beyond N)
-                        row[kk]          = lik;
-#pragma unroll
-                        for (int jj = kk + 1; jj < PB; jj++) row[jj] = rfma(-lik, reg_rdlane(lik, (int)(c0 + jj) & 63), row[jj]);
-                    }
-#pragma unroll
-                for (int jj = 0; jj < PB; jj++)
-                    if (on && c0 + jj <= lane && c0 + jj < N) v.dd(lane, c0 + jj) = row[jj];
-            }
-            double di = on ? v.d[lane] : 0.0;
-            for (uint32_t c0 = 0; c0 < N; c0 += PB)
-            {
-#pragma unroll
-                for (int jj = 0; jj < PB; jj++) row[jj] = (on && c0 + jj <= lane && c0 + jj < N) ? v.dd(lane, c0 + jj) : 0.0;
-#pragma unroll
-                for (int jj = 0; jj < PB; jj++)
-                    if (c0 + jj < N)
-                    {
-                        const uint32_t j = c0 + jj;
-                        const double yj  = reg_rdlane(di, (int)j) / reg_rdlane(row[jj], (int)j);
-                        di               = (lane == j) ? yj : (lane > j ? rfma(-row[jj], yj, di) : di);
-                    }
-            }
-            __syncthreads(); // the factor's columns are read across lanes from here on
-            for (uint32_t c0 = ((N - 1) / PB) * PB; N > 0; c0 -= PB)
-            {
-#pragma unroll
-                for (int jj = 0; jj < PB; jj++) row[jj] = (on && c0 + jj >= lane && c0 + jj < N) ? v.dd(c0 + jj, lane) : 0.0;
-#pragma unroll
-                for (int jj = PB - 1; jj >= 0; jj--)
-                    if (c0 + jj < N)
-                    {
-                        const uint32_t j = c0 + jj;
-                        const double zj  = reg_rdlane(di, (int)j) / reg_rdlane(row[jj], (int)j);
-                        di               = (lane == j) ? zj : (lane < j ? rfma(-row[jj], zj, di) : di);
-                    }
-                if (c0 == 0) break;
-            }
-            if (on) v.d[lane] = di;
-            __syncthreads();
-        }
-
-        /// LLT of the lower triangle of D (N x N) in place, then D z = d in place (oracle: cholesky_solve)
+        /// LLT of the lower triangle of D (N x N) in place, then D z = d in place (oracle: cholesky_solve): spd_solve, its one-wavefront form as a
+        /// call — the register-resident kernels run it once per level and pay for every inlined copy in code size
         template <int NT>
         __device__ void reg_cholesky_solve(const RegView &v, uint32_t N, uint32_t tid)
         {
-            if constexpr (NT == 64)
-            {
-                if (N <= 64) return reg_cholesky_solve_wave(v, N, tid);
-            }
-            for (uint32_t j = 0; j < N; j++)
-            {
-                if (tid == 0)
-                {
-                    double sjj = v.dd(j, j);
-                    for (uint32_t k = 0; k < j; k++) sjj = rfma(-v.dd(j, k), v.dd(j, k), sjj);
-                    v.dd(j, j) = sqrt(sjj);
-                }
-                __syncthreads();
-                const double ljj = v.dd(j, j);
-                for (uint32_t i = j + 1 + tid; i < N; i += NT)
-                {
-                    double t = v.dd(i, j);
-                    for (uint32_t k = 0; k < j; k++) t = rfma(-v.dd(i, k), v.dd(j, k), t);
-                    v.dd(i, j) = t / ljj;
-                }
-                __syncthreads();
-            }
-            for (uint32_t j = 0; j < N; j++)
-            {
-                if (tid == 0) v.d[j] = v.d[j] / v.dd(j, j);
-                __syncthreads();
-                const double yj = v.d[j];
-                for (uint32_t i = j + 1 + tid; i < N; i += NT) v.d[i] = rfma(-v.dd(i, j), yj, v.d[i]);
-                __syncthreads();
-            }
-            for (uint32_t j = N; j--;)
-            {
-                if (tid == 0) v.d[j] = v.d[j] / v.dd(j, j);
-                __syncthreads();
-                const double zj = v.d[j];
-                for (uint32_t i = tid; i < j; i += NT) v.d[i] = rfma(-v.dd(j, i), zj, v.d[i]);
-                __syncthreads();
-            }
+            spd_solve<NT, true>(v.D, v.ldd, v.d, N, tid);
         }
 
         /// d <- sym(D0) d (lower triangle stored)
@@ -243,7 +130,7 @@ namespace lexls
             for (uint32_t i = tid; i < N; i += NT)
             {
                 double acc = 0.0;
-                for (uint32_t j = 0; j < N; j++) acc = rfma(i >= j ? v.d0(i, j) : v.d0(j, i), v.d[j], acc);
+                for (uint32_t j = 0; j < N; j++) acc = dfma(i >= j ? v.d0(i, j) : v.d0(j, i), v.d[j], acc);
                 v.out[i] = acc;
             }
             __syncthreads();
@@ -273,7 +160,7 @@ namespace lexls
                 uint32_t i, j;
                 reg_lower_entry(e, rank, i, j);
                 double acc = 0.0;
-                for (uint32_t k = 0; k <= j; k++) acc = rfma(v.w(F + k, Fc + i), v.w(F + k, Fc + j), acc);
+                for (uint32_t k = 0; k <= j; k++) acc = dfma(v.w(F + k, Fc + i), v.w(F + k, Fc + j), acc);
                 v.dd(i, j) = acc;
             }
         }
@@ -286,22 +173,22 @@ namespace lexls
                 uint32_t i, j;
                 reg_lower_entry(e, rank, i, j);
                 double acc = 0.0;
-                for (uint32_t k = i; k < rank; k++) acc = rfma(v.w(F + i, Fc + k), v.w(F + j, Fc + k), acc);
+                for (uint32_t k = i; k < rank; k++) acc = dfma(v.w(F + i, Fc + k), v.w(F + j, Fc + k), acc);
                 double t = 0.0;
-                for (uint32_t c = 0; c < RC; c++) t = rfma(v.w(F + i, Fc + rank + c), v.w(F + j, Fc + rank + c), t);
+                for (uint32_t c = 0; c < RC; c++) t = dfma(v.w(F + i, Fc + rank + c), v.w(F + j, Fc + rank + c), t);
                 v.dd(i, j) = acc + t;
             }
         }
         __device__ inline double reg_Rt_rhs(const RegView &v, uint32_t F, uint32_t Fc, uint32_t i)
         {
             double acc = 0.0;
-            for (uint32_t k = 0; k <= i; k++) acc = rfma(v.w(F + k, Fc + i), v.w(F + k, v.n), acc);
+            for (uint32_t k = 0; k <= i; k++) acc = dfma(v.w(F + k, Fc + i), v.w(F + k, v.n), acc);
             return acc;
         }
         __device__ inline double reg_R_times_d(const RegView &v, uint32_t F, uint32_t Fc, uint32_t rank, uint32_t i)
         {
             double acc = 0.0;
-            for (uint32_t j = i; j < rank; j++) acc = rfma(v.w(F + i, Fc + j), v.d[j], acc);
+            for (uint32_t j = i; j < rank; j++) acc = dfma(v.w(F + i, Fc + j), v.d[j], acc);
             return acc;
         }
         template <int NT>
@@ -335,14 +222,14 @@ namespace lexls
                 uint32_t a, b2;
                 reg_lower_entry(e, RC, a, b2);
                 double acc = 0.0;
-                for (uint32_t k = 0; k < rank; k++) acc = rfma(v.w(F + k, Fc + rank + a), v.w(F + k, Fc + rank + b2), acc);
+                for (uint32_t k = 0; k < rank; k++) acc = dfma(v.w(F + k, Fc + rank + a), v.w(F + k, Fc + rank + b2), acc);
                 v.dd(rank + a, rank + b2) = acc;
             }
             for (uint32_t e = tid; e < RC * rank; e += NT) // Tk'*triu(Rk)
             {
                 const uint32_t a = e % RC, j = e / RC;
                 double acc = 0.0;
-                for (uint32_t k = 0; k <= j; k++) acc = rfma(v.w(F + k, Fc + rank + a), v.w(F + k, Fc + j), acc);
+                for (uint32_t k = 0; k <= j; k++) acc = dfma(v.w(F + k, Fc + rank + a), v.w(F + k, Fc + j), acc);
                 v.dd(rank + a, j) = acc;
             }
             __syncthreads();
@@ -352,8 +239,8 @@ namespace lexls
                 reg_lower_entry(e, N, i, j);
                 double acc = 0.0;
                 #pragma unroll 4
-                for (uint32_t r = 0; r < m0; r++) acc = rfma(v.ns(r, Fc + i), v.ns(r, Fc + j), acc);
-                double t = rfma(mu, acc, v.dd(i, j));
+                for (uint32_t r = 0; r < m0; r++) acc = dfma(v.ns(r, Fc + i), v.ns(r, Fc + j), acc);
+                double t = dfma(mu, acc, v.dd(i, j));
                 if (i == j) t += mu;
                 v.dd(i, j) = t;
             }
@@ -365,20 +252,20 @@ namespace lexls
                 else
                 {
                     double acc = 0.0;
-                    for (uint32_t k = 0; k < rank; k++) acc = rfma(v.w(F + k, Fc + i), v.w(F + k, v.n), acc);
+                    for (uint32_t k = 0; k < rank; k++) acc = dfma(v.w(F + k, Fc + i), v.w(F + k, v.n), acc);
                     base = acc;
                 }
                 double acc = 0.0;
                 #pragma unroll 4
-                for (uint32_t r = 0; r < m0; r++) acc = rfma(v.ns(r, Fc + i), v.ns(r, v.n), acc);
-                v.d[i] = rfma(mu, acc, base);
+                for (uint32_t r = 0; r < m0; r++) acc = dfma(v.ns(r, Fc + i), v.ns(r, v.n), acc);
+                v.d[i] = dfma(mu, acc, base);
             }
             __syncthreads();
             reg_cholesky_solve<NT>(v, N, tid);
             for (uint32_t i = tid; i < rank; i += NT)
             {
                 double t = 0.0;
-                for (uint32_t c = 0; c < RC; c++) t = rfma(v.w(F + i, Fc + rank + c), v.d[rank + c], t);
+                for (uint32_t c = 0; c < RC; c++) t = dfma(v.w(F + i, Fc + rank + c), v.d[rank + c], t);
                 v.out[i] = reg_R_times_d(v, F, Fc, rank, i) + t;
             }
             reg_store_rhs<NT>(v, F, rank, v.out, tid);
@@ -397,7 +284,7 @@ namespace lexls
                 reg_lower_entry(e, m0, s2, t);
                 double acc = 0.0;
                 #pragma unroll 4
-                for (uint32_t c = 0; c < Wd; c++) acc = rfma(v.ns(s2, Fc + c), v.ns(t, Fc + c), acc);
+                for (uint32_t c = 0; c < Wd; c++) acc = dfma(v.ns(s2, Fc + c), v.ns(t, Fc + c), acc);
                 v.dd(rank + s2, rank + t) = mu * acc;
             }
             for (uint32_t e = tid; e < m0 * rank; e += NT) // f * (up.leftCols(rank)*triu(Rk)' + up.rightCols(RC)*Tk')
@@ -405,11 +292,11 @@ namespace lexls
                 const uint32_t s2 = e % m0, i = e / m0;
                 double a1 = 0.0;
                 #pragma unroll 4
-                for (uint32_t c = i; c < rank; c++) a1 = rfma(v.ns(s2, Fc + c), v.w(F + i, Fc + c), a1);
+                for (uint32_t c = i; c < rank; c++) a1 = dfma(v.ns(s2, Fc + c), v.w(F + i, Fc + c), a1);
                 double a2 = 0.0;
                 #pragma unroll 4
-                for (uint32_t c = 0; c < RC; c++) a2 = rfma(v.ns(s2, Fc + rank + c), v.w(F + i, Fc + rank + c), a2);
-                v.dd(rank + s2, i) = rfma(f, a2, f * a1);
+                for (uint32_t c = 0; c < RC; c++) a2 = dfma(v.ns(s2, Fc + rank + c), v.w(F + i, Fc + rank + c), a2);
+                v.dd(rank + s2, i) = dfma(f, a2, f * a1);
             }
             __syncthreads();
             for (uint32_t i = tid; i < N; i += NT)
@@ -445,8 +332,8 @@ namespace lexls
                 {
                     double acc = 0.0;
                     #pragma unroll 4
-                    for (uint32_t r = 0; r < m0; r++) acc = rfma(v.ns(r, Fc + i), v.ns(r, Fc + j), acc);
-                    t = rfma(mu, acc, t);
+                    for (uint32_t r = 0; r < m0; r++) acc = dfma(v.ns(r, Fc + i), v.ns(r, Fc + j), acc);
+                    t = dfma(mu, acc, t);
                 }
                 if (i == j) t += mu;
                 v.dd(i, j) = t;
@@ -457,7 +344,7 @@ namespace lexls
                 {
                     double acc = 0.0;
                     #pragma unroll 4
-                    for (uint32_t r = 0; r < m0; r++) acc = rfma(v.ns(r, Fc + i), v.ns(r, v.n), acc);
+                    for (uint32_t r = 0; r < m0; r++) acc = dfma(v.ns(r, Fc + i), v.ns(r, v.n), acc);
                     v.d[i] = mu * acc + reg_Rt_rhs(v, F, Fc, i);
                 }
                 else
@@ -503,13 +390,13 @@ namespace lexls
             auto T_times = [&](const double *vec, uint32_t i) {
                 double t = 0.0;
                 #pragma unroll 4
-                for (uint32_t c = 0; c < RC; c++) t = rfma(v.w(F + i, Fc + rank + c), vec[rank + c], t);
+                for (uint32_t c = 0; c < RC; c++) t = dfma(v.w(F + i, Fc + rank + c), vec[rank + c], t);
                 return t;
             };
             auto R_times = [&](const double *vec, uint32_t i) {
                 double rr = 0.0;
                 #pragma unroll 4
-                for (uint32_t j = i; j < rank; j++) rr = rfma(v.w(F + i, Fc + j), vec[j], rr);
+                for (uint32_t j = i; j < rank; j++) rr = dfma(v.w(F + i, Fc + j), vec[j], rr);
                 return rr;
             };
             auto compute_s = [&]() {
@@ -517,15 +404,15 @@ namespace lexls
                 {
                     double acc = 0.0;
                     #pragma unroll 4
-                    for (uint32_t k = 0; k < m0; k++) acc = rfma(v.ns(k, Fc + i), r2[k], acc);
+                    for (uint32_t k = 0; k < m0; k++) acc = dfma(v.ns(k, Fc + i), r2[k], acc);
                     double sval = with_z ? (acc + r3[i]) * f : f * r3[i];
                     double add  = 0.0;
                     if (i < rank)
                         #pragma unroll 4
-                        for (uint32_t k = 0; k <= i; k++) add = rfma(v.w(F + k, Fc + i), r1[k], add);
+                        for (uint32_t k = 0; k <= i; k++) add = dfma(v.w(F + k, Fc + i), r1[k], add);
                     else
                         #pragma unroll 4
-                        for (uint32_t k = 0; k < rank; k++) add = rfma(v.w(F + k, Fc + i), r1[k], add);
+                        for (uint32_t k = 0; k < rank; k++) add = dfma(v.w(F + k, Fc + i), r1[k], add);
                     sv[i] = sval + add;
                 }
                 __syncthreads();
@@ -542,7 +429,7 @@ namespace lexls
             {
                 double acc = 0.0;
                 #pragma unroll 4
-                for (uint32_t i = 0; i < N; i++) acc = rfma(v.ns(k, Fc + i), x[i], acc);
+                for (uint32_t i = 0; i < N; i++) acc = dfma(v.ns(k, Fc + i), x[i], acc);
                 r2[k] = (v.ns(k, n) - acc) * f;
             }
             for (uint32_t i = tid; i < N; i += NT) r3[i] = -f * x[i];
@@ -558,7 +445,7 @@ namespace lexls
                 {
                     double g = 0.0;
                     #pragma unroll 4
-                    for (uint32_t i = 0; i < N; i++) g = rfma(sv[i], sv[i], g);
+                    for (uint32_t i = 0; i < N; i++) g = dfma(sv[i], sv[i], g);
                     v.scal[1] = g;
                 }
                 __syncthreads();
@@ -578,7 +465,7 @@ namespace lexls
                 {
                     double acc = 0.0;
                     #pragma unroll 4
-                    for (uint32_t i = 0; i < N; i++) acc = rfma(v.ns(k, Fc + i), pv[i], acc);
+                    for (uint32_t i = 0; i < N; i++) acc = dfma(v.ns(k, Fc + i), pv[i], acc);
                     q2[k] = acc * f;
                 }
                 for (uint32_t i = tid; i < N; i += NT) q3[i] = f * pv[i];
@@ -592,11 +479,11 @@ namespace lexls
                     {
                         double qq = 0.0;
                         #pragma unroll 4
-                        for (uint32_t i = 0; i < rank; i++) qq = rfma(q1[i], q1[i], qq);
+                        for (uint32_t i = 0; i < rank; i++) qq = dfma(q1[i], q1[i], qq);
                         #pragma unroll 4
-                        for (uint32_t k = 0; k < m0; k++) qq = rfma(q2[k], q2[k], qq);
+                        for (uint32_t k = 0; k < m0; k++) qq = dfma(q2[k], q2[k], qq);
                         #pragma unroll 4
-                        for (uint32_t i = 0; i < N; i++) qq = rfma(q3[i], q3[i], qq);
+                        for (uint32_t i = 0; i < N; i++) qq = dfma(q3[i], q3[i], qq);
                         v.scal[2] = gamma / qq;
                     }
                     __syncthreads();
@@ -604,11 +491,11 @@ namespace lexls
                 }
                 for (uint32_t i = tid; i < N; i += NT)
                 {
-                    x[i]  = rfma(alpha, pv[i], x[i]);
-                    r3[i] = rfma(-alpha, q3[i], r3[i]);
+                    x[i]  = dfma(alpha, pv[i], x[i]);
+                    r3[i] = dfma(-alpha, q3[i], r3[i]);
                 }
-                for (uint32_t i = tid; i < rank; i += NT) r1[i] = rfma(-alpha, q1[i], r1[i]);
-                for (uint32_t k = tid; k < m0; k += NT) r2[k] = rfma(-alpha, q2[k], r2[k]);
+                for (uint32_t i = tid; i < rank; i += NT) r1[i] = dfma(-alpha, q1[i], r1[i]);
+                for (uint32_t k = tid; k < m0; k += NT) r2[k] = dfma(-alpha, q2[k], r2[k]);
                 __syncthreads();
                 compute_s();
                 const double gamma_previous = gamma;
@@ -620,14 +507,14 @@ namespace lexls
                     {
                         double g = 0.0;
                         #pragma unroll 4
-                        for (uint32_t i = 0; i < N; i++) g = rfma(sv[i], sv[i], g);
+                        for (uint32_t i = 0; i < N; i++) g = dfma(sv[i], sv[i], g);
                         v.scal[1] = g;
                     }
                     __syncthreads();
                     gamma = v.scal[1];
                 }
                 const double beta           = gamma / gamma_previous;
-                for (uint32_t i = tid; i < N; i += NT) pv[i] = rfma(beta, pv[i], sv[i]);
+                for (uint32_t i = tid; i < N; i += NT) pv[i] = dfma(beta, pv[i], sv[i]);
                 __syncthreads();
                 iter++;
             }
@@ -652,7 +539,7 @@ namespace lexls
                 {
                     double sv = v.ns(i, Fc + p);
                     #pragma unroll 4
-                    for (uint32_t q = 0; q < p; q++) sv = rfma(-v.ns(i, Fc + q), v.w(F + q, Fc + p), sv);
+                    for (uint32_t q = 0; q < p; q++) sv = dfma(-v.ns(i, Fc + q), v.w(F + q, Fc + p), sv);
                     v.ns(i, Fc + p) = sv * (1.0 / v.w(F + p, Fc + p));
                 }
             __syncthreads();
@@ -661,7 +548,7 @@ namespace lexls
                 const uint32_t i = e % rows, k = e / rows;
                 double t = v.ns(i, Fc + rank + k);
                 #pragma unroll 4
-                for (uint32_t p = 0; p < rank; p++) t = rfma(-v.ns(i, Fc + p), v.w(F + p, Fc + rank + k), t);
+                for (uint32_t p = 0; p < rank; p++) t = dfma(-v.ns(i, Fc + p), v.w(F + p, Fc + rank + k), t);
                 v.ns(i, Fc + rank + k) = t;
             }
             __syncthreads();
@@ -675,10 +562,10 @@ namespace lexls
             else if (tau != 0.0)
             {
                 double tmp = 0.0;
-                for (uint32_t i = 1; i < len; i++) tmp = rfma(ess[i - 1], x[i], tmp);
+                for (uint32_t i = 1; i < len; i++) tmp = dfma(ess[i - 1], x[i], tmp);
                 tmp += x[0];
-                x[0] = rfma(-tau, tmp, x[0]);
-                for (uint32_t i = 1; i < len; i++) x[i] = rfma(-(tau * ess[i - 1]), tmp, x[i]);
+                x[0] = dfma(-tau, tmp, x[0]);
+                for (uint32_t i = 1; i < len; i++) x[i] = dfma(-(tau * ess[i - 1]), tmp, x[i]);
             }
         }
 
@@ -708,7 +595,7 @@ namespace lexls
                     for (uint32_t r = 0; r < ri; r++)
                     {
                         double acc = 0.0;
-                        for (uint32_t c = 0; c < N; c++) acc = rfma(v.w(Fi + r, n - N + c), X[n - N + c], acc);
+                        for (uint32_t c = 0; c < N; c++) acc = dfma(v.w(Fi + r, n - N + c), X[n - N + c], acc);
                         X[Fci + r] = v.w(Fi + r, n) - acc;
                     }
                 }
@@ -723,14 +610,14 @@ namespace lexls
                         for (uint32_t i = 0; i < rk; i++)
                         {
                             double s = X[Fck + i];
-                            for (uint32_t j = 0; j < acc_ranks; j++) s = rfma(-v.w(Fk + i, c0 + j), X[c0 + j], s);
+                            for (uint32_t j = 0; j < acc_ranks; j++) s = dfma(-v.w(Fk + i, c0 + j), X[c0 + j], s);
                             X[Fck + i] = s;
                         }
                     }
                     for (uint32_t j = rk; j--;)
                     {
                         X[Fck + j] = X[Fck + j] / v.w(Fk + j, Fck + j);
-                        for (uint32_t i = 0; i < j; i++) X[Fck + i] = rfma(-v.w(Fk + i, Fck + j), X[Fck + j], X[Fck + i]);
+                        for (uint32_t i = 0; i < j; i++) X[Fck + i] = dfma(-v.w(Fk + i, Fck + j), X[Fck + j], X[Fck + i]);
                     }
                     acc_ranks += rk;
                 }
@@ -767,15 +654,15 @@ namespace lexls
                         for (uint32_t i = 0; i < rank; i++)
                         {
                             v.out[i] = v.w(F + i, v.n);
-                            ce       = rfma(v.out[i], v.out[i], ce);
+                            ce       = dfma(v.out[i], v.out[i], ce);
                         }
                         for (uint32_t j = rank; j--;)
                         {
                             v.out[j] = v.out[j] / v.w(F + j, Fc + j);
-                            for (uint32_t i = 0; i < j; i++) v.out[i] = rfma(-v.w(F + i, Fc + j), v.out[j], v.out[i]);
+                            for (uint32_t i = 0; i < j; i++) v.out[i] = dfma(-v.w(F + i, Fc + j), v.out[j], v.out[i]);
                         }
                         double q = 0.0;
-                        for (uint32_t i = 0; i < rank; i++) q = rfma(v.out[i], v.out[i], q);
+                        for (uint32_t i = 0; i < rank; i++) q = dfma(v.out[i], v.out[i], q);
                         ce /= q;
                         const double eps = a.reg_variable;
                         if (ce < eps)

@@ -1,5 +1,5 @@
 // The removal search of a lock-step LexLSI stage as one wavefront per problem (sensitivity_sweep_kernel) — a header because two translation
-// units run it: lqr_generic.hip launches it as a kernel of its own, lsi_fused_*.hip runs its body inside the persistent iteration kernel.
+// units run it: lse_postfactor.hip launches it as a kernel of its own, lsi_fused_*.hip runs its body inside the persistent iteration kernel.
 #pragma once
 #include "lexls_kernels.h"
 #include "lexls_launch.h"

@@ -1,4 +1,5 @@
-// Device helpers shared by the one-wavefront-per-problem kernels (lqr_small_impl.h, lqr_lwave_impl.h).
+// Device helpers shared by the one-wavefront-per-problem kernels (lqr_small_impl.h, lqr_lwave_impl.h) and by every unit that spells out an fma
+// or reads across lanes (dfma, rdlane).
 #pragma once
 #include "lexls_kernels.h"
 #include "lexls_launch.h"
@@ -120,7 +121,7 @@ namespace lexls
 
         __device__ __forceinline__ int uni(int v) { return __builtin_amdgcn_readfirstlane(v); }
 
-        // ---- a problem per 16-lane DPP row (lqr_quad_impl.h, the removal-search sweep of lqr_generic.hip) ----
+        // ---- a problem per 16-lane DPP row (lqr_quad_impl.h, the removal-search sweep of lse_postfactor.hip) ----
         extern "C" __device__ double lexls_update_dpp_f64(double, double, int, int, int, bool) __asm("llvm.amdgcn.update.dpp.f64");
 
         /// value of lane L of this lane's 16-lane row (v_mov_b64_dpp row_newbcast:L)

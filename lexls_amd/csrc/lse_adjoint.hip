@@ -3,6 +3,7 @@
 // them, each on ONE view of the factor and ONE rule for a level's rank (KeptFactor, trusted_rank: lse_kept_factor.h).  Tolerance contract; no atomics.
 #include "lexls_launch.h"
 #include "lse_kept_factor.h"
+#include "lse_spd_solve.h"
 #include <cstdlib>
 #include <cstring>
 
@@ -149,107 +150,6 @@ namespace lexls
                         if (lane == 0 && j0 + u < nf) grad_fixed[(size_t)b * n + j0 + u] = gh[j0 + u] - s[u];
                 }
                 for (uint32_t j = nf + lane; j < n; j += NT) grad_fixed[(size_t)b * n + j] = 0.0;
-            }
-        }
-
-        /// LL^T of the lower triangle of D (order N, leading dimension ldd) in place, then D z = d in place, by one wavefront.  N <= 64: the panel
-        /// scheme of reg_cholesky_solve_wave (lexls_regularize.h) — lane i owns row i, 16 columns at a time in registers, a finished column's
-        /// entries reach the other lanes by v_readlane —; beyond that the lanes take every 64th row, column by column.  Ends in a barrier
-        __device__ __forceinline__ void adjoint_cholesky_solve(double *D, uint32_t ldd, double *d, uint32_t N, uint32_t lane)
-        {
-            auto dd = [&](uint32_t i, uint32_t j) __attribute__((always_inline)) -> double & { return D[i + (size_t)j * ldd]; };
-            if (N <= 64)
-            {
-                constexpr int PB = 16;
-                const bool on    = lane < N;
-                double row[PB];
-                for (uint32_t c0 = 0; c0 < N; c0 += PB)
-                {
-#pragma unroll
-                    for (int jj = 0; jj < PB; jj++) row[jj] = (on && c0 + jj <= lane && c0 + jj < N) ? dd(lane, c0 + jj) : 0.0;
-                    for (uint32_t k = 0; k < c0; k++)
-                    {
-                        const double lik = (on && lane >= c0) ? dd(lane, k) : 0.0;
-#pragma unroll
-                        for (int jj = 0; jj < PB; jj++) row[jj] = dfma(-lik, rdlane(lik, (int)(c0 + jj) & 63), row[jj]);
-                    }
-#pragma unroll
-                    for (int kk = 0; kk < PB; kk++)
-                        if (c0 + kk < N) // uniform
-                        {
-                            const double lkk = sqrt(rdlane(row[kk], (int)(c0 + kk)));
-                            const double lik = (lane == c0 + kk) ? lkk : row[kk] / lkk; // (zeros above the diagonal and beyond N)
-                            row[kk]          = lik;
-#pragma unroll
-                            for (int jj = kk + 1; jj < PB; jj++) row[jj] = dfma(-lik, rdlane(lik, (int)(c0 + jj) & 63), row[jj]);
-                        }
-#pragma unroll
-                    for (int jj = 0; jj < PB; jj++)
-                        if (on && c0 + jj <= lane && c0 + jj < N) dd(lane, c0 + jj) = row[jj];
-                }
-                double di = on ? d[lane] : 0.0;
-                for (uint32_t c0 = 0; c0 < N; c0 += PB)
-                {
-#pragma unroll
-                    for (int jj = 0; jj < PB; jj++) row[jj] = (on && c0 + jj <= lane && c0 + jj < N) ? dd(lane, c0 + jj) : 0.0;
-#pragma unroll
-                    for (int jj = 0; jj < PB; jj++)
-                        if (c0 + jj < N)
-                        {
-                            const uint32_t j = c0 + jj;
-                            const double yj  = rdlane(di, (int)j) / rdlane(row[jj], (int)j);
-                            di               = (lane == j) ? yj : (lane > j ? dfma(-row[jj], yj, di) : di);
-                        }
-                }
-                __syncthreads(); // the factor's columns are read across lanes from here on
-                for (uint32_t c0 = ((N - 1) / PB) * PB; N > 0; c0 -= PB)
-                {
-#pragma unroll
-                    for (int jj = 0; jj < PB; jj++) row[jj] = (on && c0 + jj >= lane && c0 + jj < N) ? dd(c0 + jj, lane) : 0.0;
-#pragma unroll
-                    for (int jj = PB - 1; jj >= 0; jj--)
-                        if (c0 + jj < N)
-                        {
-                            const uint32_t j = c0 + jj;
-                            const double zj  = rdlane(di, (int)j) / rdlane(row[jj], (int)j);
-                            di               = (lane == j) ? zj : (lane < j ? dfma(-row[jj], zj, di) : di);
-                        }
-                    if (c0 == 0) break;
-                }
-                if (on) d[lane] = di;
-                __syncthreads();
-                return;
-            }
-            for (uint32_t j = 0; j < N; j++) // left-looking, column by column
-            {
-                double sjj = dd(j, j); // (every lane for itself: the same chain, the same bits)
-                for (uint32_t k = 0; k < j; k++) sjj = dfma(-dd(j, k), dd(j, k), sjj);
-                const double ljj = sqrt(sjj);
-                __syncthreads(); // (every lane has read the diagonal entry)
-                if (lane == 0) dd(j, j) = ljj;
-                for (uint32_t i = j + 1 + lane; i < N; i += 64)
-                {
-                    double t = dd(i, j);
-                    for (uint32_t k = 0; k < j; k++) t = dfma(-dd(i, k), dd(j, k), t);
-                    dd(i, j) = t / ljj;
-                }
-                __syncthreads();
-            }
-            for (uint32_t j = 0; j < N; j++)
-            {
-                const double yj = d[j] / dd(j, j);
-                __syncthreads();
-                if (lane == 0) d[j] = yj;
-                for (uint32_t i = j + 1 + lane; i < N; i += 64) d[i] = dfma(-dd(i, j), yj, d[i]);
-                __syncthreads();
-            }
-            for (uint32_t j = N; j--;)
-            {
-                const double zj = d[j] / dd(j, j);
-                __syncthreads();
-                if (lane == 0) d[j] = zj;
-                for (uint32_t i = lane; i < j; i += 64) d[i] = dfma(-dd(j, i), zj, d[i]);
-                __syncthreads();
             }
         }
 
@@ -470,7 +370,7 @@ namespace lexls
                             dv[c] = acc;
                         }
                         __syncthreads();
-                        adjoint_cholesky_solve(D, n, dv, N, lane); // dv = t
+                        spd_solve<NT>(D, n, dv, N, lane); // dv = t
                         for (uint32_t i = lane; i < rank; i += NT) // y~ = W t
                         {
                             double acc = 0.0;

@@ -1,5 +1,5 @@
 // The kept factor of a LexLSE solve as the kernels behind it read it: the per-problem view, the rule for how far a level's stored rank may be
-// trusted, and the steps that more than one of those kernels takes (lse_adjoint.hip: the adjoint family; lqr_generic.hip: sensitivity_kernel
+// trusted, and the steps that more than one of those kernels takes (lse_adjoint.hip: the adjoint family; lse_postfactor.hip: sensitivity_kernel
 // stages the factor with stage_factor).  trusted_rank is plain C++ as well (tests/kept_factor_check.cpp runs the very same rule on the host).
 #pragma once
 #include <cstdint>

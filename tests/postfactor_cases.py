@@ -1,4 +1,4 @@
-"""Batches that hold the POST-FACTORIZATION kernels (lexls_amd/csrc/lqr_generic.hip: solve_generic, residual, sensitivity<64,staged|hbm>, the
+"""Batches that hold the POST-FACTORIZATION kernels (lexls_amd/csrc/lse_postfactor.hip: solve_generic, residual, sensitivity<64,staged|hbm>, the
 two sweeps, leastnorm 1 / 2 / 3) to the oracle beyond the small shapes (tests/test_gpu_postfactor.py runs them on the GPU, bit for bit;
 tests/test_postfactor_cases.py asserts the conditions below on the CPU, from the oracle alone).
 
@@ -28,9 +28,15 @@ Cases (what each is for):
     ragged            n = 40, capacity [12]x5, per-problem dimensions with empty levels, fixed variables with activation types: nfixed = dims[0] + 1
                       (problems 2 and 5), every variable fixed (problem 4: nVarRank = nVarFree = 0)
     ik, wide          n = 40 [12]x5 and n = 55 [14,9,16,5], batch 5: the producer matrix (every l-QR kernel's factor under every consumer)
+    ln_panel, ln_switch   the least-norm group (LEAST_NORM_CASES, build_least_norm): n = 20 and n = 70, a handful of problems each whose nVarFree —
+                      the order of the SPD system solveLeastNorm_2 and _3 solve (lexls_amd/csrc/lse_spd_solve.h) — is 1, 15, 16, 17 / 48, 64, 65:
+                      the smallest order, both sides of a 16-column panel edge, a boundary behind three full panels, both sides of the switch
+                      from the one-wavefront panel form to the column-by-column form; fixed variables in the last problem of each.  The cases
+                      above leave nVarFree at about `dup` (at most 20)
 
 Conditions (tests/test_postfactor_cases.py): (a) at least half of a case's problems have ranks of the levels + nfixed < n and solveLeastNorm_1 moves
-some entry of theirs by more than 1e-3 (ragged: exempt, it is there for the other end); (b) at least two objectives have non-zero multipliers, found is 1 for some (problem, level) pairs and 0 for others, CORRECT_SIGN marks occur, a scan from level 0 stops at more than one
+some entry of theirs by more than 1e-3 (ragged: exempt, it is there for the other end; the least-norm group: EVERY problem has free variables and
+solveLeastNorm_2 and _3 each move some entry by more than 1e-3, it is exempt from (b) — equalities only, no multipliers asked for — and of (c) the agreement of its two solutions is held); (b) at least two objectives have non-zero multipliers, found is 1 for some (problem, level) pairs and 0 for others, CORRECT_SIGN marks occur, a scan from level 0 stops at more than one
 level (large, one problem: it stops somewhere); (c) the oracle against mathematics: stationarity of the multipliers and
 lambda_k = residual of level k to 1e-12, get_v = A x - b and the agreement of the three least-norm solutions to 1e-10, x orthogonal to the null
 space of the stacked matrix (no fixed variables) to 1e-10, each times max(1, largest magnitude of the quantity).
@@ -39,7 +45,7 @@ MEASURED (oracle alone, `python tests/postfactor_cases.py`; free = problems whos
 multiplier block; found = (problem, level) pairs with / without a candidate; stops = levels a scan from 0 stops at; marks = CORRECT_SIGN marks
 of the scan; the oracle's own figures for (c), relative as above: stat = stationarity, lam-v = lambda_k against the residual, v = get_v against
 A x - b, ln = largest disagreement of the three least-norm solutions, orth = x against the null space; |ln1-x| = smallest over the free
-problems of the largest entry solveLeastNorm_1 moves):
+problems of the largest entry solveLeastNorm_1 moves; the least-norm group: nVarFree per problem, and the same figure for _2 and _3):
     n63     n=63  [16,16,16,16,8]  batch 5    free 4    lam!=0 [3,4]         found 8/17 stops [3,4]     marks 69   stat 6.2e-15 lam-v 9.1e-15 v 1.6e-15 ln 1.2e-15 orth 4.0e-15 |ln1-x| 1.0e-01
     n64     n=64  [16,16,16,16,8]  batch 5    free 4    lam!=0 [3,4]         found 8/17 stops [3,4]     marks 57   stat 6.3e-15 lam-v 1.5e-14 v 1.9e-15 ln 7.0e-16 orth 8.4e-15 |ln1-x| 2.0e-01
     n65     n=65  [16,16,16,16,8]  batch 5    free 4    lam!=0 [3,4]         found 8/17 stops [3,4]     marks 75   stat 7.7e-15 lam-v 1.3e-14 v 1.8e-15 ln 9.3e-16 orth 9.9e-15 |ln1-x| 1.4e-01
@@ -52,6 +58,8 @@ problems of the largest entry solveLeastNorm_1 moves):
     ragged  n=40  [12,12,12,12,12] batch 6    free 4    lam!=0 [0,1,2,3,4]   found 14/16 stops [0,2,3,4] marks 42   stat 3.1e-15 lam-v 3.1e-14 v 1.0e-15 ln 9.4e-16 orth 5.8e-16 |ln1-x| 2.4e-01
     ik      n=40  [12,12,12,12,12] batch 5    free 4    lam!=0 [3,4]         found 8/17 stops [3,4]     marks 50   stat 3.7e-15 lam-v 1.1e-14 v 7.9e-16 ln 6.6e-16 orth 4.0e-15 |ln1-x| 7.5e-02
     wide    n=55  [14,9,16,5]      batch 5    free 5    lam!=0 [2,3]         found 6/14 stops [2,3]     marks 35   stat 4.5e-15 lam-v 7.8e-15 v 6.1e-15 ln 1.4e-15 orth 9.0e-15 |ln1-x| 5.7e-01
+    ln_panel  n=20  nVarFree [1, 15, 16, 17, 16] |ln2-x| 8.3e-02 |ln3-x| 8.3e-02
+    ln_switch n=70  nVarFree [48, 64, 65, 65] |ln2-x| 2.3e-01 |ln3-x| 2.3e-01
 """
 import functools
 import os
@@ -131,6 +139,45 @@ def draw(name, batch=None):
             typ[b, :nf] = 1 + (P.uniform(seed + 500000 + b, n)[:nf] * 3).astype(np.uint8)
         fixed = dict(nfixed=nfixed, fixed_idx=idx, fixed_val=val, fixed_type=typ)
     return dict(name=name, n=n, caps=caps, lod=lod, dims=dims, types=types, fixed=fixed, policy=c.get("policy"))
+
+
+# The least-norm group: the orders nVarFree of the SPD system D z = d that solveLeastNorm_2 and _3 solve (lse_spd_solve.h: the panel form takes
+# 16 columns at a time up to order 64, the column-by-column form any order).  Dense data of full row rank and fewer rows than free columns, so
+# nVarFree = n - nfixed - (the problem's rows), set per problem by its level dimensions: both sides of a panel edge, a boundary behind three
+# full panels, both sides of the switch; fixed variables in the last problem of each.  name -> n, dims (capacities), seed, per_problem, nfixed
+LEAST_NORM_CASES = {
+    "ln_panel": dict(n=20, dims=[10, 9], seed=20270113, per_problem=[[10, 9], [3, 2], [2, 2], [2, 1], [1, 1]], nfixed=[0, 0, 0, 0, 2]),  # 1, 15, 16, 17, 16
+    "ln_switch": dict(n=70, dims=[12, 10], seed=20270114, per_problem=[[12, 10], [3, 3], [3, 2], [2, 2]], nfixed=[0, 0, 0, 1]),          # 48, 64, 65, 65
+}
+LEAST_NORM_ORDERS = (1, 15, 16, 17, 48, 64, 65)  # smallest; a panel edge; three full panels; the switch to the workgroup form
+
+
+@functools.lru_cache(maxsize=None)
+def build_least_norm(name):
+    """a case of the least-norm group: the inputs as draw() names them, the oracle's x, ranks, solveLeastNorm_2 (ln2) and solveLeastNorm_3 behind
+    regularization type 1 with zero factors (ln3), and nvarfree per problem from the oracle's ranks"""
+    c = LEAST_NORM_CASES[name]
+    n, caps, seed = c["n"], list(c["dims"]), c["seed"]
+    dims, nfixed = np.asarray(c["per_problem"], np.uint32), np.asarray(c["nfixed"], np.uint32)
+    B = len(dims)
+    lod = P.lse_batch(seed, B, n, caps)
+    idx, val = np.zeros((B, n), np.uint32), np.zeros((B, n))
+    for b in range(B):
+        lod[b, :, int(dims[b].sum()):] = np.nan  # a problem's rows packed level after level; NaN behind them (never read)
+        nf = int(nfixed[b])
+        idx[b, :nf] = np.argsort(P.uniform(seed + 300000 + b, n))[:nf]
+        val[b, :nf] = P.normal(seed + 400000 + b, n)[:nf]
+    fixed = dict(nfixed=nfixed, fixed_idx=idx, fixed_val=val, fixed_type=np.full((B, n), EQ, np.uint8))
+    case = dict(name=name, n=n, caps=caps, lod=lod, dims=dims, types=np.full((B, sum(caps)), EQ, np.uint8), fixed=fixed, policy=None)
+    run = functools.partial(oracle.lse_run, lod, dims, n, maxdim=np.asarray(caps, np.uint32), **fixed)
+    basic = run()
+    case["x"], case["rank"] = basic["x"], basic["rank"]
+    case["ln2"] = run(solve_option=2)["x"]
+    case["ln3"] = run(solve_option=3, reg_type=1, reg_factors=[0.0] * len(caps))["x"]
+    case["nvarfree"] = n - nfixed.astype(int) - case["rank"].sum(axis=1).astype(int)
+    for a in [v for v in case.values() if isinstance(v, np.ndarray)] + list(fixed.values()):
+        a.setflags(write=False)
+    return case
 
 
 def _one(fixed, b):
@@ -292,6 +339,13 @@ def summary(case):
             f"|ln1-x| {moves.min() if moves.size else 0.0:.1e}")
 
 
+def summary_least_norm(ln):
+    moves = [np.abs(ln[k] - ln["x"]).max(axis=1).min() for k in ("ln2", "ln3")]
+    return f"    {ln['name']:<9} n={ln['n']:<3} nVarFree {ln['nvarfree'].tolist()} |ln2-x| {moves[0]:.1e} |ln3-x| {moves[1]:.1e}"
+
+
 if __name__ == "__main__":
     for nm in CASES:
         print(summary(build(nm)))
+    for nm in LEAST_NORM_CASES:
+        print(summary_least_norm(build_least_norm(nm)))

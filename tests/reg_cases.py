@@ -19,10 +19,10 @@ The switches, and the case on each side of each:
     tikhonov_1 otherwise, so its order n - Fc <= ceil(n / 2) - 1 + rank < n / 2 + MD + 1, the window's (tests/test_reg_cases.py walks every
     n, Fc, rank, nf of both shapes).  `window` (n = 29, [12,12,12], window 27) takes both Tikhonov branches in one problem (0, 2 and 3; problem 1's level 0 has the factor 0.0) and reaches the
     largest order the shape can produce, 26 (problem 4: three fixed variables send level 0 to tikhonov_1); the scratch side of with_order is the side of the cases without a window.
- 2. reg_cholesky_solve_wave's panels of 16: `panel`, n = 63 [16,1,15,1,15,1,14], type 8: problem 0 (full ranks, no zero factor) has the orders
+ 2. spd_solve_wave's panels of 16 (lse_spd_solve.h, behind reg_cholesky_solve): `panel`, n = 63 [16,1,15,1,15,1,14], type 8: problem 0 (full ranks, no zero factor) has the orders
     16, 17, 32, 33, 48, 49, 63; the same hierarchy under types 1 (orders 14 .. 46 by tikhonov_1, 16, 17, 31 by tikhonov_2) and 5; again under
     policy 1, where the same routine runs inside lqr_generic<64,lds>.
- 3. reg_cholesky_solve<NT>, workgroup form: g64 (n = 64 [20,20], the first shape past the wave family), g100, g130 ([70,40,30]: a level over 64
+ 3. spd_solve<NT> (behind reg_cholesky_solve<NT>), workgroup form: g64 (n = 64 [20,20], the first shape past the wave family), g100, g130 ([70,40,30]: a level over 64
     rows, last rank 20; orders 130 (type 1), 70 .. 130 (type 8), 70 (types 3, 5)), g70r (per-problem dimensions, an empty level, fixed
     variables) on lqr_generic<256,lds>; g150 on lqr_generic<1024,hbm>; `tall` (n = 20, 520 rows) on lqr_generic<1024,lds>, which a regularized
     shape does reach: more than 512 rows of a problem whose matrix still fits the LDS.  Orders within 64 on NT = 256 / 1024: g100 types 3 - 5.
@@ -166,7 +166,7 @@ PLAN = {
     "vf_g": {1: (G256, 0, 0), 3: (G256, 0, 0)},
 }
 WAVE_CASES = tuple(nm for nm, p in PLAN.items() if next(iter(p.values()))[0] in (W41, W64))
-POLICY_1 = G64  # what every wave case takes under kernel policy 1: the generic kernel of one wavefront, where reg_cholesky_solve_wave runs again
+POLICY_1 = G64  # what every wave case takes under kernel policy 1: the generic kernel of one wavefront, where spd_solve_wave runs again
 
 # the flips of the placement (DOCSTRING, switch 1): (type, what flips, case on the LDS side, case on the other side)
 FLIPS = (

@@ -100,7 +100,7 @@ def test_collect_on_the_sweep(hip, oracle, monkeypatch, case, scan):
 @pytest.mark.parametrize("scan", [False, True], ids=["one_objective", "scan"])
 @pytest.mark.parametrize("case", ["no_fixed", "fixed_mixed"])
 def test_collect_on_sensitivity_kernel(hip, oracle, monkeypatch, case, scan):
-    """the per-objective kernel of lqr_generic.hip (the shapes the sweep does not serve): forced with LEXLS_SENS_NO_SWEEP"""
+    """the per-objective kernel of lse_postfactor.hip (the shapes the sweep does not serve): forced with LEXLS_SENS_NO_SWEEP"""
     run_case(hip, oracle, monkeypatch, case, 0 if scan else 3, scan, no_sweep=True)
 
 

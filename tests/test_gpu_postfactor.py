@@ -216,6 +216,22 @@ def test_every_producer_feeds_every_consumer_the_same_bits(hip, oracle, name):
     check_least_norm_3(hip, case)
 
 
+@pytest.mark.parametrize("name", list(PC.LEAST_NORM_CASES))
+def test_least_norm_orders_of_the_spd_solve(hip, oracle, name):
+    """solveLeastNorm_2 and _3 with nVarFree = 1, on both sides of 16, at 48 and on both sides of 64 — the panel edges and the switch of spd_solve
+    (tests/postfactor_cases.py: the least-norm group) —, bit for bit"""
+    case = PC.build_least_norm(name)
+    s = handle(hip, case)
+    s.factorize_solve(keep_factor=True)
+    np.testing.assert_array_equal(s.getRanks()[0], case["rank"])
+    np.testing.assert_array_equal(s.get_x(), case["x"])
+    s.solveLeastNorm_2()
+    assert s.last_consumer_kernel() == "leastnorm_2<64>"
+    np.testing.assert_array_equal(s.get_x(), case["ln2"], err_msg="solveLeastNorm_2")
+    s.close()
+    check_least_norm_3(hip, case)
+
+
 def test_consumer_name_follows_the_factor(hip, oracle):
     """"" until a consumer launches on the current factor; a solve() the factorization kernel answered already launches nothing"""
     case = PC.build("ik")

@@ -23,7 +23,7 @@ What would make each test fail (each kernel's own copy of the reference's rank t
   test_small*, test_handle* lqr_small_impl.h:411 (:526 is the lane hand-off variant, compiled out); lexls_capi.hip lexls_lse_set_tolerance: without
                             `factor_valid = false` solve() serves the old x; without dropping the prefix-reuse state the levels read back keep
                             the ranks of the old tolerance (FOUND by test_handle_state[wave-prefix-reuse]; fixed with it)
-  test_generic*             lqr_generic.hip:594
+  test_generic*             lqr_generic.hip:421
   test_large*               lqr_large.hip:184 (multi-launch), :761 (launch per pivot: a batch), :1406 (pivots of a level in one launch: one problem)
 A kernel that ignored `tol` altogether passes no case: every case asserts that the oracle's own ranks differ between tol_keep and tol_drop.
 

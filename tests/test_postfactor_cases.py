@@ -72,6 +72,25 @@ def test_a_free_variables(case):
     assert free.any() and (case["ln1_moves"][free] > 1e-3).all()
 
 
+def test_least_norm_group_covers_the_orders_of_the_spd_solve():
+    """from the oracle's ranks alone: every listed nVarFree occurs, and in EVERY problem of the group solveLeastNorm_2 and _3 each move some entry
+    of x by more than 1e-3 (condition (a): a routine that does nothing cannot pass); fixed variables occur"""
+    seen = set()
+    for name in C.LEAST_NORM_CASES:
+        ln = C.build_least_norm(name)
+        print(C.summary_least_norm(ln))
+        assert C.summary_least_norm(ln) in C.__doc__
+        np.testing.assert_array_equal(ln["nvarfree"], ln["n"] - ln["fixed"]["nfixed"].astype(int) - ln["rank"].sum(axis=1).astype(int))
+        assert (ln["nvarfree"] > 0).all() and (ln["fixed"]["nfixed"] > 0).any()
+        for key in ("ln2", "ln3"):
+            assert np.isfinite(ln[key]).all()
+            assert (np.abs(ln[key] - ln["x"]).max(axis=1) > 1e-3).all(), (name, key)
+        assert C._rel(np.abs(ln["ln2"] - ln["ln3"]).max(), ln["ln2"]) <= C.BOUND_X  # (of condition (c))
+        seen |= set(ln["nvarfree"].tolist())
+    assert set(C.LEAST_NORM_ORDERS) <= seen, seen
+    assert C.LEAST_NORM_ORDERS == (1, 15, 16, 17, 48, 64, 65)
+
+
 def test_b_multipliers_are_not_vacuous(case):
     """(b) non-zero multipliers at two objectives at least, found and not found, CORRECT_SIGN marks, a scan that stops at more than one level"""
     assert len(case["nonzero_objectives"]) >= 2

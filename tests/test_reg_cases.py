@@ -147,7 +147,7 @@ def test_b_orders_meet_the_panel_edges_and_pass_64():
     case = C.build("panel")
     assert case["plain"]["rank"][0].tolist() == case["caps"] and not case["fixed"] and (case["fac"][0] != 0.0).all()
     in_problem_0 = sorted(N for b, _, N, _ in case["orders"][8] if b == 0)
-    assert in_problem_0 == list(C.PANEL_ORDERS)  # reg_cholesky_solve_wave: 16 | 17, 32 | 33, 48 | 49 and 63
+    assert in_problem_0 == list(C.PANEL_ORDERS)  # spd_solve_wave (lse_spd_solve.h): 16 | 17, 32 | 33, 48 | 49 and 63
     assert set(C.CASES["panel"]["types"]) == {8, 1, 5}
     assert {N for _, _, N, _ in case["orders"][1]} & {16, 17, 32}  # ... and under type 1
     big = {(nm, t): max([N for _, _, N, _ in C.build(nm)["orders"][t]] or [0]) for nm in ("g100", "g130", "g150", "g70r") for t in C.CASES[nm]["types"]}
