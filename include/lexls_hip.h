@@ -268,13 +268,37 @@ int lexls_lse_set_adjoint_regularized(lexls_lse_t h, int on);
  * lexls_lse_solve_adjoint (the summation order differs): against that call, and against any reference, the contract is the tolerance one.
  * Errors, each returned before any device work and with every output left alone: LEXLS_ERR_INVALID for a null handle, a null G or a null
  * d_grad_rhs; LEXLS_ERR_INVALID for ncot == 0; LEXLS_ERR_INVALID when there is no kept factor; LEXLS_ERR_UNSUPPORTED when the factorization
- * ran with regularization_type != 0 (every type: the single-cotangent call lexls_lse_solve_adjoint serves types 1, 3, 4, 5, 8 and 9 once switched on).
+ * ran with regularization_type != 0 and lexls_lse_set_adjoint_regularized_multi (below) is off, or the type or the variable factor is not served.
  * Kernel variant (lexls_lse_last_consumer_kernel), decided on the host from nVar and cap alone: "solve_adjoint_multi<64,staged>" — the
  * per-lane state and the staged factor fit one workgroup's 160 KiB of LDS; "solve_adjoint_multi<64,hbm>" — the state alone fits, the factor
  * is read where it is kept; "solve_adjoint<64> x K" — neither: the single-cotangent kernel once per cotangent. */
 int lexls_lse_solve_adjoint_multi(lexls_lse_t h, const double *h_G, uint32_t ncot);
 int lexls_lse_get_adjoint_multi(lexls_lse_t h, double *h_grad_rhs, double *h_grad_fixed);
 int lexls_lse_solve_adjoint_multi_device(lexls_lse_t h, const double *d_G, uint32_t ncot, double *d_grad_rhs, double *d_grad_fixed);
+/* on != 0: the three calls above serve a factor of regularization type 1, 3, 4, 5, 8 or 9 with variable_regularization_factor == 0 and return
+ * M_reg^T g_c and N_reg^T g_c of the damped solve for every cotangent, with exactly the layouts, zero conventions, deferred-sync behaviour and
+ * validity rule they have without regularization.  0 (the default): LEXLS_ERR_UNSUPPORTED after every regularized factorization, as before; the
+ * message names this switch.  Independent of lexls_lse_set_adjoint_regularized (either, both or neither may be on).  Takes effect at the next
+ * call; the kept factor stays valid.  LEXLS_ERR_INVALID for a null handle.  Types 2, 6 and 7 and a non-zero variable factor stay
+ * LEXLS_ERR_UNSUPPORTED (the message names the condition); every refusal happens before any device work and leaves the outputs untouched.
+ * lexls_lse_solve_adjoint_matrix* keeps refusing every regularized factorization.
+ * The factors are read from the handle's device array AT THE TIME OF THE ADJOINT CALL, as in the single-cotangent call: a caller who rewrites
+ * that array in place between the factorization and the call gets the adjoint of the rewritten factors, and no error is raised.
+ * The independence contract above holds: a cotangent's bits do not depend on ncot, on its position in G or on its company; the same bits come
+ * back run to run and from the host and the device form.  NOT promised bit-equal to lexls_lse_solve_adjoint: against it the contract is the
+ * tolerance one.
+ * One wavefront serves a problem and a tile of up to 64 cotangents, lane = cotangent; the grid is batch x tiles, and EVERY TILE REPEATS the
+ * work of the problem (the rebuild of the null-space basis, the per-level snapshots, the formation of D and its Cholesky factorization): 65
+ * cotangents cost two tiles' shared work.  Kernel variant (lexls_lse_last_consumer_kernel), decided on the host from nVar, cap and nObj alone:
+ * "solve_adjoint_reg_multi<64,lds>" — the per-lane state and the problem's matrices fit one workgroup's 160 KiB of LDS;
+ * "solve_adjoint_reg_multi<64,hbm>" — the state alone fits, the matrices sit in a work buffer of the handle (allocated at the first call that
+ * needs it, and again when a call brings more tiles: that call of the device form is not enqueue-only); "solve_adjoint_reg<64,lds> x K" or
+ * "solve_adjoint_reg<64,hbm> x K" — the state alone exceeds the limit: the single-cotangent kernel once per cotangent.
+ * When it pays: the time of a call hardly depends on the number of live lanes of a tile — on 4096 IK problems (nVar 40, 5 x 12, type 1) 11.0 ms
+ * for 1 cotangent, 11.4 ms for 40, 11.7 ms for 64 and 22.6 ms for 65 (MI355X), against 1.69 ms per call of
+ * lexls_lse_solve_adjoint_device — so from about SEVEN cotangents per problem on it is faster than that many single-cotangent calls (5.9 times
+ * at 40), and below that it is slower. */
+int lexls_lse_set_adjoint_regularized_multi(lexls_lse_t h, int on);
 
 /* Gradient of the solve with respect to the MATRIX A (and, with it, the right-hand sides): the derivative the calls above do not give.  x is
  * not continuous in A where a rank changes, so the derivative exists for RANK-STABLE problems only, and the call says per problem whether it
@@ -797,8 +821,9 @@ int lexls_lsi_batch_solve_adjoint_device(lexls_lsi_batch_t b, const double *d_g,
  * device memory are read again at that factorization: rows rewritten in place between the run and the first adjoint call give the adjoint of the
  * rewritten factors, and no error is raised.  0 (the default, so that a caller who takes LEXLS_ERR_UNSUPPORTED after a regularized run as the
  * sign to differentiate some other way keeps getting it): every regularized run is refused.  Types 2, 6, 7, a variable factor, cycling handling,
- * a run that was not resident and more than 65535 constraints stay LEXLS_ERR_UNSUPPORTED, and so do lexls_lsi_batch_get_lambda,
- * lexls_lsi_batch_solve_adjoint_multi* and lexls_lsi_batch_solve_adjoint_matrix* after every regularized run.
+ * a run that was not resident and more than 65535 constraints stay LEXLS_ERR_UNSUPPORTED, and so do lexls_lsi_batch_get_lambda and
+ * lexls_lsi_batch_solve_adjoint_matrix* after every regularized run, and lexls_lsi_batch_solve_adjoint_multi* unless
+ * lexls_lsi_batch_set_adjoint_regularized_multi (below) was on for the run.
  * Errors: LEXLS_ERR_INVALID for a null handle, and between lexls_lsi_batch_enqueue_device and lexls_lsi_batch_finish. */
 int lexls_lsi_batch_set_adjoint_regularized(lexls_lsi_batch_t b, int on);
 /* lexls_lsi_batch_solve_adjoint(_device) for ncot cotangents per instance in one pass: lexls_lse_solve_adjoint_multi_device on the final factor
@@ -810,6 +835,13 @@ int lexls_lsi_batch_set_adjoint_regularized(lexls_lsi_batch_t b, int on);
  * returned before any device work and with every output left alone.  The independence contract of lexls_lse_solve_adjoint_multi holds. */
 int lexls_lsi_batch_solve_adjoint_multi(lexls_lsi_batch_t b, const double *h_G, uint32_t ncot, double *h_grad_lb, double *h_grad_ub);
 int lexls_lsi_batch_solve_adjoint_multi_device(lexls_lsi_batch_t b, const double *d_G, uint32_t ncot, double *d_grad_lb, double *d_grad_ub);
+/* on != 0: from the NEXT run on, the two calls above also answer after a regularized run, under the conditions
+ * lexls_lsi_batch_set_adjoint_regularized states for the single call (a resident run of type 1, 3, 4, 5, 8 or 9, a zero variable factor, no
+ * cycling handling, at most 65535 constraints), through lexls_lse_set_adjoint_regularized_multi on the groups' handles.  The final factor is
+ * the damped one, factorized once per run and shared with lexls_lsi_batch_solve_adjoint when both switches are on.  Independent of that
+ * switch.  0 (the default): the refusal of a regularized run is the one of lexls_lsi_batch_get_lambda, with this switch named.
+ * Errors: LEXLS_ERR_INVALID for a null handle, and between lexls_lsi_batch_enqueue_device and lexls_lsi_batch_finish. */
+int lexls_lsi_batch_set_adjoint_regularized_multi(lexls_lsi_batch_t b, int on);
 /* Gradients of the LAST completed run's solutions with respect to ALL constraint data — the matrices A and the bounds — in the caller's layout.
  * At an instance that ended PROBLEM_SOLVED, x is the basic solution of the equality problem of its final working set W; while W holds, x as a
  * function of the active rows' A and bounds is the LexLSE solve map of that final problem, so the gradient is lexls_lse_solve_adjoint_matrix's,

@@ -29,7 +29,7 @@ SYMBOLS = [
     "lexls_lse_set_prefix_reuse", "lexls_lse_prefix_reuse_ready", "lexls_lse_set_resume_levels",
     "lexls_lsi_solve", "lexls_lsi_solve_dat", "lexls_lsi_batch_solve",
     "lexls_lse_multipliers", "lexls_lse_get_multipliers", "lexls_lse_solve_adjoint", "lexls_lse_set_adjoint_regularized", "lexls_lse_get_adjoint", "lexls_lse_solve_adjoint_device",
-    "lexls_lse_solve_adjoint_multi", "lexls_lse_get_adjoint_multi", "lexls_lse_solve_adjoint_multi_device",
+    "lexls_lse_solve_adjoint_multi", "lexls_lse_get_adjoint_multi", "lexls_lse_solve_adjoint_multi_device", "lexls_lse_set_adjoint_regularized_multi",
     "lexls_lse_solve_adjoint_matrix", "lexls_lse_get_adjoint_matrix", "lexls_lse_solve_adjoint_matrix_device",
     "lexls_lsi_batch_get_lambda", "lexls_lsi_batch_solve_ex2",
     "lexls_lse_sensitivity_collect", "lexls_lse_sensitivity_collect_resident", "lexls_lse_get_wrong_sign",
@@ -39,7 +39,7 @@ SYMBOLS = [
     "lexls_lsi_batch_enqueue_device", "lexls_lsi_batch_finish",
     "lexls_lsi_batch_set_instance_mask", "lexls_lsi_batch_set_instance_max_factorizations", "lexls_lsi_batch_set_instance_obj_dims",
     "lexls_lsi_batch_solve_adjoint", "lexls_lsi_batch_solve_adjoint_device", "lexls_lsi_batch_set_adjoint_regularized",
-    "lexls_lsi_batch_solve_adjoint_multi", "lexls_lsi_batch_solve_adjoint_multi_device",
+    "lexls_lsi_batch_solve_adjoint_multi", "lexls_lsi_batch_solve_adjoint_multi_device", "lexls_lsi_batch_set_adjoint_regularized_multi",
     "lexls_lsi_batch_solve_adjoint_matrix", "lexls_lsi_batch_solve_adjoint_matrix_device", "lexls_lsi_batch_final_factorizations",
     "lexls_lsi_batch_last_kernel",
 ]
@@ -119,6 +119,10 @@ def lib() -> C.CDLL:
         _lib.lexls_lsi_batch_set_adjoint_regularized.argtypes = [C.c_void_p, C.c_int]
         _lib.lexls_lse_set_adjoint_regularized.restype = C.c_int
         _lib.lexls_lse_set_adjoint_regularized.argtypes = [C.c_void_p, C.c_int]
+        _lib.lexls_lsi_batch_set_adjoint_regularized_multi.restype = C.c_int
+        _lib.lexls_lsi_batch_set_adjoint_regularized_multi.argtypes = [C.c_void_p, C.c_int]
+        _lib.lexls_lse_set_adjoint_regularized_multi.restype = C.c_int
+        _lib.lexls_lse_set_adjoint_regularized_multi.argtypes = [C.c_void_p, C.c_int]
         _lib.lexls_lse_solve_adjoint.restype = C.c_int
         _lib.lexls_lse_solve_adjoint.argtypes = [C.c_void_p, C.POINTER(C.c_double)]
         _lib.lexls_lse_get_adjoint.restype = C.c_int

@@ -99,7 +99,10 @@ struct lexls_lse_s
     uint64_t adj_epoch = 0; // factor_epoch the gradients belong to
     // lexls_lse_solve_adjoint_multi: G (batch x ncot x nVar), grad_rhs (batch x ncot x cap), grad_fixed (batch x ncot x nVar) of a host caller, made
     // for the largest ncot so far; d_adjm_work: the buffers of the per-cotangent form (launch_solve_adjoint_multi), made at the first call that needs them
-    double *d_adjm_G = nullptr, *d_adjm_rhs = nullptr, *d_adjm_fixed = nullptr, *d_adjm_work = nullptr;
+    // d_adjrm_work: the matrices of the regularized multi kernel where they do not fit in LDS (adjoint_reg_multi_work_bytes), with room for adjrm_tiles tiles
+    double *d_adjm_G = nullptr, *d_adjm_rhs = nullptr, *d_adjm_fixed = nullptr, *d_adjm_work = nullptr, *d_adjrm_work = nullptr;
+    uint32_t adjrm_tiles      = 0;
+    bool adj_regularized_multi = false; // lexls_lse_set_adjoint_regularized_multi: the multi-cotangent calls serve damped factorizations (off: UNSUPPORTED, as before)
     uint32_t adjm_room = 0, adjm_ncot = 0; // cotangents the three buffers have room for; cotangents of the last lexls_lse_solve_adjoint_multi
     bool adjm_valid     = false;
     uint64_t adjm_epoch = 0;
@@ -305,7 +308,7 @@ extern "C"
         void *ptrs[] = {h->d_in_owned, h->d_fac, h->d_hh, h->d_v, h->d_lambda, h->d_scratch, h->d_perm, h->d_rank, h->d_fcol, h->d_round_in, h->d_round_out,
                         h->d_large_state, h->d_large_ws, h->d_norms, h->d_cdata, h->d_reg_factor, h->d_reg_scratch, h->d_reg_mu, h->d_resume_level, h->d_resume_state,
                         h->d_guard_est, h->d_guard_status, h->d_guard_ind, h->d_mult, h->d_mult_scratch, h->d_wrong_sign, h->d_adj_g, h->d_adj_rhs, h->d_adj_fixed,
-                        h->d_adj_work, h->d_adjm_G, h->d_adjm_rhs, h->d_adjm_fixed, h->d_adjm_work, h->d_adjA_g, h->d_adjA_grad, h->d_adjA_flag, h->d_adjA_work};
+                        h->d_adj_work, h->d_adjm_G, h->d_adjm_rhs, h->d_adjm_fixed, h->d_adjm_work, h->d_adjrm_work, h->d_adjA_g, h->d_adjA_grad, h->d_adjA_flag, h->d_adjA_work};
         for (void *p : ptrs)
             if (p) (void)hipFree(p);
         if (h->h_dims_pinned) (void)hipHostFree(h->h_dims_pinned);
@@ -1035,19 +1038,25 @@ extern "C"
         return LEXLS_OK;
     }
 
-    /// what every form of the adjoint checks before any device work: a kept factor — unregularized, or (single_cotangent: lexls_lse_solve_adjoint
-    /// and its device form, once lexls_lse_set_adjoint_regularized switched it on) regularized with one of the types whose damped solve is an
-    /// affine map of the kept factor, the factors constant
-    static int need_adjoint_factor(lexls_lse_t h, const char *who, const void *g, bool single_cotangent = false)
+    /// what every form of the adjoint checks before any device work: a kept factor — unregularized, or (AdjointCall::single: lexls_lse_solve_adjoint
+    /// and its device form, once lexls_lse_set_adjoint_regularized switched it on; AdjointCall::multi: the multi-cotangent calls, once
+    /// lexls_lse_set_adjoint_regularized_multi did) regularized with one of the types whose damped solve is an affine map of the kept factor, the
+    /// factors constant
+    enum class AdjointCall { other, single, multi };
+    static int need_adjoint_factor(lexls_lse_t h, const char *who, const void *g, AdjointCall call = AdjointCall::other)
     {
         CHECK_HANDLE(h);
         if (!g) return fail(LEXLS_ERR_INVALID, std::string(who) + ": null g");
         if (int rc = need_factor(h, who)) return rc;
         if (h->reg_type == 0) return LEXLS_OK;
-        if (!single_cotangent)
+        if (call == AdjointCall::other)
             return fail(LEXLS_ERR_UNSUPPORTED, std::string(who) + ": the factorization ran with regularization_type != 0 (lexls_lse_solve_adjoint, the single-cotangent call, serves "
                                                                   "regularization types 1, 3, 4, 5, 8 and 9; this call serves none)");
-        if (!h->adj_regularized)
+        if (call == AdjointCall::multi && !h->adj_regularized_multi)
+            return fail(LEXLS_ERR_UNSUPPORTED, std::string(who) + ": the factorization ran with regularization_type != 0 and the many-cotangent adjoint of damped solves is not "
+                                                                  "switched on for this handle (lexls_lse_set_adjoint_regularized_multi; it serves regularization types 1, 3, 4, 5, 8 "
+                                                                  "and 9, as lexls_lse_solve_adjoint, the single-cotangent call, does under lexls_lse_set_adjoint_regularized)");
+        if (call == AdjointCall::single && !h->adj_regularized)
             return fail(LEXLS_ERR_UNSUPPORTED, std::string(who) + ": the factorization ran with regularization_type != 0 and the adjoint of damped solves is not switched on "
                                                                   "for this handle (lexls_lse_set_adjoint_regularized; it serves regularization types 1, 3, 4, 5, 8 and 9)");
         if (!adjoint_reg_serves(h->reg_type))
@@ -1070,6 +1079,13 @@ extern "C"
     {
         CHECK_HANDLE(h);
         h->adj_regularized = on != 0;
+        return LEXLS_OK;
+    }
+
+    int lexls_lse_set_adjoint_regularized_multi(lexls_lse_t h, int on)
+    {
+        CHECK_HANDLE(h);
+        h->adj_regularized_multi = on != 0;
         return LEXLS_OK;
     }
 
@@ -1097,7 +1113,7 @@ extern "C"
     /// every form of lexls_lse_solve_adjoint on device memory: the checks, the work buffer, the launch
     static int run_solve_adjoint(lexls_lse_t h, const char *who, const double *d_g, double *d_grad_rhs, double *d_grad_fixed)
     {
-        if (int rc = need_adjoint_factor(h, who, d_g, true)) return rc;
+        if (int rc = need_adjoint_factor(h, who, d_g, AdjointCall::single)) return rc;
         if (!d_grad_rhs) return fail(LEXLS_ERR_INVALID, std::string(who) + ": null d_grad_rhs");
         HIP_TRY(hipSetDevice(h->device));
         if (int rc = adjoint_reg_work(h)) return rc;
@@ -1108,7 +1124,7 @@ extern "C"
     int lexls_lse_solve_adjoint(lexls_lse_t h, const double *h_g)
     {
         const char *who = "lexls_lse_solve_adjoint";
-        if (int rc = need_adjoint_factor(h, who, h_g, true)) return rc;
+        if (int rc = need_adjoint_factor(h, who, h_g, AdjointCall::single)) return rc;
         HIP_TRY(hipSetDevice(h->device));
         const size_t B = h->batch, n = h->nVar, cap = h->cap;
         if (!h->d_adj_g) HIP_TRY(hipMalloc((void **)&h->d_adj_g, 8 * B * n));
@@ -1139,7 +1155,7 @@ extern "C"
         CHECK_HANDLE(h);
         if (!G) return fail(LEXLS_ERR_INVALID, std::string(who) + ": null G");
         if (ncot == 0) return fail(LEXLS_ERR_INVALID, std::string(who) + ": ncot == 0");
-        return need_adjoint_factor(h, who, G);
+        return need_adjoint_factor(h, who, G, AdjointCall::multi);
     }
     /// every form of lexls_lse_solve_adjoint_multi on device memory: the checks, the work buffer, the launch
     static int run_solve_adjoint_multi(lexls_lse_t h, const char *who, const double *d_G, uint32_t ncot, double *d_grad_rhs, double *d_grad_fixed)
@@ -1149,7 +1165,17 @@ extern "C"
         HIP_TRY(hipSetDevice(h->device));
         const size_t bytes = adjoint_multi_work_bytes(h->args());
         if (bytes && !h->d_adjm_work) HIP_TRY(hipMalloc((void **)&h->d_adjm_work, bytes));
-        HIP_TRY(launch_solve_adjoint_multi(h->args(), d_G, ncot, d_grad_rhs, d_grad_fixed, h->d_adjm_work, h->stream, &h->last_consumer));
+        if (bytes) // (the per-cotangent form runs lexls_lse_solve_adjoint's launch: a regularized factor may want its work buffer)
+            if (int rc = adjoint_reg_work(h)) return rc;
+        const uint32_t tiles = (ncot + 63u) / 64u;
+        if (adjoint_reg_multi_work_bytes(h->args(), ncot) && tiles > h->adjrm_tiles) // the matrices of the hbm form, for the most tiles so far
+        {
+            if (h->d_adjrm_work) (void)hipFree(h->d_adjrm_work); // (waits for whatever still reads it)
+            h->d_adjrm_work = nullptr, h->adjrm_tiles = 0;
+            HIP_TRY(hipMalloc((void **)&h->d_adjrm_work, adjoint_reg_multi_work_bytes(h->args(), ncot)));
+            h->adjrm_tiles = tiles;
+        }
+        HIP_TRY(launch_solve_adjoint_multi(h->args(), d_G, ncot, d_grad_rhs, d_grad_fixed, h->d_adjm_work, h->stream, &h->last_consumer, h->d_adj_work, h->d_adjrm_work));
         return LEXLS_OK;
     }
 

@@ -29,10 +29,17 @@ namespace lexls
     /// lexls_lse_solve_adjoint_multi: ncot cotangents per problem in one pass, d_G batch x ncot x nVar, d_grad_rhs batch x ncot x cap, d_grad_fixed
     /// batch x ncot x nVar (may be NULL).  The form follows from the shape (adjoint_multi_form, lexls_lds.h): lane = cotangent with the factor staged
     /// in LDS, the same with the factor read where it is kept, or launch_solve_adjoint once per cotangent through d_work (adjoint_multi_work_bytes,
-    /// 0 where the shape needs none).  Enqueued only
+    /// 0 where the shape needs none).  Enqueued only.
+    /// A regularized factor (the types and the condition of launch_solve_adjoint; anything else: hipErrorInvalidValue) takes one of
+    /// adjoint_reg_multi_form's forms (lexls_lds.h), from nVar, cap and nObj alone: solve_adjoint_reg_multi_kernel with the problem's matrices in
+    /// LDS, the same with them in d_reg_multi_work (adjoint_reg_multi_work_bytes: one set per problem and TILE of 64 cotangents — the grid is batch x
+    /// tiles and every tile repeats the work of the problem: basis, snapshots, D and its factorization), or launch_solve_adjoint once per
+    /// cotangent through d_work, with d_reg_work what that launch wants (adjoint_reg_work_bytes).  a.reg_factor is read at the time of this call.
+    /// LEXLS_ADJOINT_REG_MULTI_FORM = hbm | single in the environment names a later form of the list (measurements)
     size_t adjoint_multi_work_bytes(const LseArgs &a);
+    size_t adjoint_reg_multi_work_bytes(const LseArgs &a, uint32_t ncot);
     hipError_t launch_solve_adjoint_multi(const LseArgs &a, const double *d_G, uint32_t ncot, double *d_grad_rhs, double *d_grad_fixed, double *d_work, hipStream_t s,
-                                          const char **variant = nullptr);
+                                          const char **variant = nullptr, double *d_reg_work = nullptr, double *d_reg_multi_work = nullptr);
     /// d_out (batch x nVar, the order of x) = M d_rhs (batch x cap, LOD row order) for x = M b + N x_fixed of the kept factor, fixed values zero:
     /// the transpose of launch_solve_adjoint.  d_only_level (may be NULL): rows outside level d_only_level[b] of problem b count as zero.
     /// One wavefront per problem, enqueued only.  Internal: the public header has no forward entry for new right-hand sides

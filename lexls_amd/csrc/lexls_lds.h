@@ -260,5 +260,33 @@ namespace lexls
     /// the regularization types whose damped solve is an affine map of the kept factor (TIKHONOV, R, R_NO_Z, RT_NO_Z, TIKHONOV_2, TEST)
     inline bool adjoint_reg_serves(uint32_t reg_type) { return reg_type == 1 || reg_type == 3 || reg_type == 4 || reg_type == 5 || reg_type == 8 || reg_type == 9; }
 
+    // ---- solve_adjoint_reg_multi (lse_adjoint.hip): the adjoint of a regularized solve, lane = cotangent ----
+    /// the per-lane state gh, the cotangent r~ of the basis' right-hand-side column, the level's right-hand side of D (nVar each) and cb (cap),
+    /// [index][lane] with leading dimension 65; the transpositions and the position every variable reaches by them (2 x nVar words, shared by
+    /// the lanes); in_lds: + the problem's matrices (adjoint_reg_matrix_doubles: the basis, D and the snapshots, shared by the lanes)
+    inline size_t adjoint_reg_multi_lds_bytes(uint32_t nVar, uint32_t cap, uint32_t nObj, bool in_lds)
+    {
+        const size_t b = 8 * (size_t)kAdjointMultiLd * (3 * (size_t)nVar + cap) + 8 * (size_t)nVar + (in_lds ? 8 * adjoint_reg_matrix_doubles(nVar, nObj) : 0);
+        return (b + 15) & ~(size_t)15;
+    }
+    /// the fit rule of the regularized lexls_lse_solve_adjoint_multi, decided from the shape alone: state + matrices in one workgroup's LDS; else
+    /// the state alone, ALL THREE matrices (D too: one rule, one carve-up) in a work buffer of the handle, adjoint_reg_matrix_doubles per
+    /// (problem, tile) and read at wavefront-uniform addresses; else the single-cotangent kernel once per cotangent
+    enum class AdjointRegMultiForm { lds, hbm, per_cotangent };
+    inline AdjointRegMultiForm adjoint_reg_multi_form(uint32_t nVar, uint32_t cap, uint32_t nObj)
+    {
+        if (adjoint_reg_multi_lds_bytes(nVar, cap, nObj, true) <= kMaxLdsBytes) return AdjointRegMultiForm::lds;
+        if (adjoint_reg_multi_lds_bytes(nVar, cap, nObj, false) <= kMaxLdsBytes) return AdjointRegMultiForm::hbm;
+        return AdjointRegMultiForm::per_cotangent;
+    }
+    /// (the per-cotangent form is named after the single-cotangent kernel it runs: adjoint_reg_in_lds of the same shape)
+    inline const char *adjoint_reg_multi_form_name(AdjointRegMultiForm f, bool single_in_lds)
+    {
+        return f == AdjointRegMultiForm::lds   ? "solve_adjoint_reg_multi<64,lds>"
+               : f == AdjointRegMultiForm::hbm ? "solve_adjoint_reg_multi<64,hbm>"
+               : single_in_lds                 ? "solve_adjoint_reg<64,lds> x K"
+                                               : "solve_adjoint_reg<64,hbm> x K";
+    }
+
     // ---- lqr_large (lqr_large.hip): lqr_large_plan.h ----
 } // namespace lexls

@@ -351,6 +351,16 @@ extern "C"
         });
     }
 
+    int lexls_lsi_batch_set_adjoint_regularized_multi(lexls_lsi_batch_t b, int on)
+    {
+        return guarded([&]() {
+            if (!b) throw Exception("lexls_lsi_batch_set_adjoint_regularized_multi: null handle");
+            b->refuse_pending("lexls_lsi_batch_set_adjoint_regularized_multi");
+            b->fin.adj_regularized_multi = on != 0; // (the rule of the last run stands: the next run is the first one it applies to)
+            return static_cast<int>(LEXLS_OK);
+        });
+    }
+
     int lexls_lsi_batch_get_working_set_log(lexls_lsi_batch_t b, int32_t *h_log, double *h_alpha, uint32_t *h_counts)
     {
         return guarded([&]() {

@@ -799,6 +799,288 @@ namespace lexls
                 }
             }
         }
+
+        /// solve_adjoint_reg_kernel's steps (a)-(d) for up to 64 cotangents of one problem at once, LANE = COTANGENT, the way
+        /// solve_adjoint_multi_kernel recasts solve_adjoint_kernel: one wavefront per (problem, tile of 64 cotangents); lanes beyond ncot compute on
+        /// zeros and store nothing.  Two kinds of phases alternate, with barriers between them:
+        ///   SHARED (work of the problem, the lanes spread over rows and entries exactly as in solve_adjoint_reg_kernel): the rebuild of NS with a
+        ///     snapshot of U per level (types 1, 3, 8), and per damped level the formation of D = W^T W + mu U^T U + mu I and its LL^T (spd_factor<NT>,
+        ///     lse_spd_solve.h: either form).  EVERY TILE REPEATS THIS WORK.
+        ///   PER LANE (work of the cotangent): steps (b), (c), (d) on the lane's own column of gh, cb, r~ and dv (LDS, [index][lane], leading
+        ///     dimension 65); every dot product, substitution and matrix-vector product is the lane's own serial dfma chain in a fixed order — among
+        ///     them the two triangular substitutions against the shared L, row by row (entry i receives the products j = 0 .. i-1, backwards
+        ///     j = N-1 .. i+1, the order of spd_solve's column sweeps).  No cross-lane reduction on cotangent data: a cotangent's bits do not depend
+        ///     on its lane, its tile or its neighbours.  Not promised bit-equal to solve_adjoint_reg_kernel (whose dot products are wavefront sums).
+        /// Everything that steers the control flow (dims, ranks, first columns, tau == 0, the |f| < 1e-15 gate, the type) belongs to the problem:
+        /// wavefront-uniform.  The factor is read where it is kept, at wavefront-uniform addresses.
+        /// IN_LDS: NS, D and the snapshots behind the state in LDS (adjoint_reg_multi_lds_bytes), read by broadcast; else in `work`,
+        /// adjoint_reg_matrix_doubles per (problem, tile), at wavefront-uniform addresses.  No atomics.
+        template <int NT, bool IN_LDS>
+        __global__ __launch_bounds__(NT) void solve_adjoint_reg_multi_kernel(LseArgs a, const double *__restrict__ G, uint32_t ncot, double *__restrict__ grad_rhs,
+                                                                             double *__restrict__ grad_fixed, double *__restrict__ work)
+        {
+            static_assert(NT == 64, "one wavefront per (problem, tile): lane = cotangent");
+            constexpr uint32_t LD = kAdjointMultiLd, AU = 4;
+            extern __shared__ double smem[];
+            const uint32_t b = blockIdx.x, tile = blockIdx.y, lane = threadIdx.x;
+            if (b >= a.batch || tile * 64u >= ncot) return; // (block-uniform)
+            const uint32_t kt = ncot - tile * 64u < 64u ? ncot - tile * 64u : 64u; // live cotangents of this tile
+            const KeptFactor kf = kept_factor_of(a, b);
+            const uint32_t n = kf.n, cap = kf.cap, nObj = kf.nObj, nf = kf.nf, T = kf.T, M = kf.M;
+            const double *__restrict__ W = kf.W, *hh = kf.hh;
+            const uint32_t *dims = kf.dims;
+            const uint32_t type  = a.reg_type;
+            const bool accum = type == 1 || type == 3 || type == 8; // the types that accumulate NS (and read it)
+            const bool wideW = type == 1 || type == 5 || type == 8; // W = [R | T] (else R)
+            const double *fac = a.reg_factor + (size_t)b * nObj;
+            double *gh = smem, *cb = gh + (size_t)n * LD, *rbar = cb + (size_t)cap * LD, *dv = rbar + (size_t)n * LD;
+            uint32_t *perm_l = reinterpret_cast<uint32_t *>(dv + (size_t)n * LD);
+            uint32_t *pos_l  = perm_l + n;
+            // (2 n words: the matrices start on an 8-byte boundary)
+            double *mat = IN_LDS ? reinterpret_cast<double *>(pos_l + n) : work + ((size_t)b * gridDim.y + tile) * adjoint_reg_matrix_doubles(n, nObj);
+            double *NS = mat, *D = NS + (size_t)n * n, *SN = D + (size_t)n * n;
+            auto ns = [&](uint32_t i, uint32_t j) __attribute__((always_inline)) -> double & { return NS[i + (size_t)j * n]; };
+            auto w  = [&](uint32_t i, uint32_t j) __attribute__((always_inline)) -> double { return W[i + (size_t)j * cap]; };
+
+            // ---- (a) gh = P^T g for every cotangent of the tile; the rest of the state zero ----
+            for (uint32_t i = lane; i < n; i += NT) perm_l[i] = a.perm[(size_t)b * n + i];
+            for (uint32_t i = lane; i < (3 * n + cap) * LD; i += NT) smem[i] = 0.0;
+            if (accum)
+                for (uint32_t i = lane; i < n * n; i += NT) NS[i] = 0.0;
+            __syncthreads();
+            for (uint32_t i = lane; i < n; i += NT) pos_l[i] = position_after_transpositions(perm_l, T, i);
+            __syncthreads();
+            {
+                const double *Gt = G + ((size_t)b * ncot + (size_t)tile * 64u) * n; // kt rows of n doubles, contiguous
+                for (uint32_t e = lane; e < kt * n; e += NT)
+                {
+                    const uint32_t c = e / n, i = e - c * n, p = pos_l[i];
+                    if (p < n) gh[p * LD + c] = Gt[e];
+                }
+            }
+            __syncthreads();
+            double *ghl = gh + lane, *cbl = cb + lane, *rbl = rbar + lane, *dvl = dv + lane; // this lane's column of the state
+
+            // ---- (b) the reverse of solve(), levels ascending (cb rows F .. F + rank are y~'), per lane ----
+            uint32_t F = 0;
+            for (uint32_t k = 0; k < nObj; k++)
+            {
+                const uint32_t dim = dims[k];
+                const auto [rank, Fc] = kf.level(k, dim);
+                if (rank > 0 && F + dim <= M)
+                {
+                    double *y = cbl + F * LD;
+                    for (uint32_t c = Fc; c < T; c++)
+                    {
+                        const uint32_t j = c - Fc, len = j < rank ? j : rank;
+                        double s = 0.0;
+                        for (uint32_t i = 0; i < len; i++) s = dfma(w(F + i, c), y[i * LD], s);
+                        if (j < rank) // (uniform) inside the triangle
+                            y[j * LD] = (ghl[c * LD] - s) / w(F + j, c);
+                        else
+                            ghl[c * LD] -= s;
+                    }
+                }
+                F += dim;
+            }
+
+            // ---- SHARED: the rebuild of NS, levels ascending, U snapshot first (solve_adjoint_reg_kernel's, statement for statement) ----
+            uint32_t soff = 0; // doubles of SN in use
+            if (accum)
+            {
+                F = 0;
+                for (uint32_t k = 0; k < nObj; k++)
+                {
+                    const uint32_t dim = dims[k];
+                    const auto [rank, Fc] = kf.level(k, dim);
+                    if (rank > 0 && F + dim <= M)
+                    {
+                        const uint32_t m0 = Fc > nf ? Fc - nf : 0, rows = m0 + rank, RC = n - Fc - rank, wc = wideW ? n - Fc : rank;
+                        for (uint32_t e = lane; e < m0 * wc; e += NT) SN[soff + e] = ns(e % m0, Fc + e / m0);
+                        soff += m0 * wc;
+                        for (uint32_t e = lane; e < rank * rank; e += NT) ns(m0 + e % rank, Fc + e / rank) = (e % rank == e / rank) ? 1.0 : 0.0;
+                        __syncthreads();
+                        for (uint32_t i = lane; i < rows; i += NT) // Left <- Left R^-1, a row per lane
+                            for (uint32_t p = 0; p < rank; p++)
+                            {
+                                double sv = ns(i, Fc + p);
+                                for (uint32_t q = 0; q < p; q++) sv = dfma(-ns(i, Fc + q), w(F + q, Fc + p), sv);
+                                ns(i, Fc + p) = sv / w(F + p, Fc + p);
+                            }
+                        __syncthreads();
+                        for (uint32_t e = lane; e < rows * RC; e += NT) // Trailing -= Left T
+                        {
+                            const uint32_t i = e % rows, c = Fc + rank + e / rows;
+                            double t = ns(i, c);
+                            for (uint32_t p = 0; p < rank; p++) t = dfma(-ns(i, Fc + p), w(F + p, c), t);
+                            ns(i, c) = t;
+                        }
+                        __syncthreads();
+                    }
+                    F += dim;
+                }
+            }
+
+            // ---- (c) the reverse of factorize()'s right-hand-side updates, levels descending ----
+            uint32_t Fend = 0;
+            for (uint32_t k = 0; k < nObj; k++) Fend += dims[k];
+            for (uint32_t k = nObj; k--;)
+            {
+                const uint32_t dim = dims[k];
+                F                  = Fend - dim;
+                Fend               = F;
+                const auto [rank, Fc] = kf.level(k, dim);
+                if (rank == 0 || F + dim > M) continue;
+                const uint32_t Fn = F + dim;
+                if (k + 1 < nObj && Fn < M)
+                {
+                    // the transposed Gauss step: AU multiplier columns share one read of the lane's cb rows (each sum in ascending row order)
+                    for (uint32_t p0 = 0; p0 < rank; p0 += AU)
+                    {
+                        double s[AU];
+#pragma unroll
+                        for (uint32_t u = 0; u < AU; u++) s[u] = 0.0;
+                        for (uint32_t i = Fn; i < M; i++)
+                        {
+                            const double ci = cbl[i * LD];
+#pragma unroll
+                            for (uint32_t u = 0; u < AU; u++)
+                                if (p0 + u < rank) s[u] = dfma(w(i, Fc + p0 + u), ci, s[u]);
+                        }
+#pragma unroll
+                        for (uint32_t u = 0; u < AU; u++)
+                            if (p0 + u < rank) cbl[(F + p0 + u) * LD] -= s[u];
+                    }
+                }
+                const uint32_t m0 = Fc > nf ? Fc - nf : 0, N = wideW ? n - Fc : rank;
+                const double *U   = SN; // the level's snapshot: m0 x N, leading dimension m0
+                double *yb        = cbl + F * LD;
+                if (accum)
+                {
+                    soff -= m0 * N;
+                    U = SN + soff;
+                    // y~' -= R^-T (U_R^T r~[0, m0) + r~[m0, m0 + rank)): the sum into dv, then R^T row by row
+                    for (uint32_t j = 0; j < rank; j++)
+                    {
+                        double acc = rbl[(m0 + j) * LD];
+                        for (uint32_t s = 0; s < m0; s++) acc = dfma(U[s + (size_t)j * m0], rbl[s * LD], acc);
+                        dvl[j * LD] = acc;
+                    }
+                    for (uint32_t j = 0; j < rank; j++)
+                    {
+                        double s = 0.0;
+                        for (uint32_t i = 0; i < j; i++) s = dfma(w(F + i, Fc + j), dvl[i * LD], s);
+                        const double vj = (dvl[j * LD] - s) / w(F + j, Fc + j);
+                        dvl[j * LD]     = vj;
+                        yb[j * LD] -= vj;
+                    }
+                }
+                const double f = fac[k];
+                if (!(fabs(f - 0.0) < 1e-15)) // the gate of regularize_level (uniform)
+                {
+                    if (type == 9)
+                    {
+                        for (uint32_t i = 0; i < rank; i++) yb[i * LD] *= f;
+                    }
+                    else
+                    {
+                        const double mu = f * f;
+                        // SHARED: D = W^T W + mu U^T U + mu I (lower triangle; column c of W has min(c + 1, rank) rows) and its LL^T
+                        for (uint32_t e = lane; e < N * N; e += NT)
+                        {
+                            const uint32_t i = e % N, j = e / N;
+                            if (i < j) continue;
+                            const uint32_t len = j < rank ? j + 1 : rank;
+                            double acc = 0.0;
+                            for (uint32_t r = 0; r < len; r++) acc = dfma(w(F + r, Fc + i), w(F + r, Fc + j), acc);
+                            if (accum)
+                            {
+                                double up = 0.0;
+                                for (uint32_t s = 0; s < m0; s++) up = dfma(U[s + (size_t)i * m0], U[s + (size_t)j * m0], up);
+                                acc = dfma(mu, up, acc);
+                            }
+                            D[i + (size_t)j * n] = i == j ? acc + mu : acc;
+                        }
+                        __syncthreads();
+                        spd_factor<NT>(D, n, N, lane); // (ends in a barrier: every lane reads all of L from here on)
+                        // PER LANE: dv = W^T y~', then L z = dv and L^T t = z in place, row by row against the shared factor
+                        for (uint32_t c = 0; c < N; c++)
+                        {
+                            const uint32_t len = c < rank ? c + 1 : rank;
+                            double acc = 0.0;
+                            for (uint32_t r = 0; r < len; r++) acc = dfma(w(F + r, Fc + c), yb[r * LD], acc);
+                            dvl[c * LD] = acc;
+                        }
+                        for (uint32_t i = 0; i < N; i++)
+                        {
+                            double acc = dvl[i * LD];
+                            for (uint32_t j = 0; j < i; j++) acc = dfma(-D[i + (size_t)j * n], dvl[j * LD], acc);
+                            dvl[i * LD] = acc / D[i + (size_t)i * n];
+                        }
+                        for (uint32_t i = N; i--;)
+                        {
+                            double acc = dvl[i * LD];
+                            for (uint32_t j = N - 1; j > i; j--) acc = dfma(-D[j + (size_t)i * n], dvl[j * LD], acc);
+                            dvl[i * LD] = acc / D[i + (size_t)i * n];
+                        }
+                        for (uint32_t i = 0; i < rank; i++) // y~ = W t
+                        {
+                            double acc = 0.0;
+                            for (uint32_t c = i; c < N; c++) acc = dfma(w(F + i, Fc + c), dvl[c * LD], acc);
+                            yb[i * LD] = acc;
+                        }
+                        if (accum)
+                            for (uint32_t s = 0; s < m0; s++) // r~ += mu U t
+                            {
+                                double acc = 0.0;
+                                for (uint32_t c = 0; c < N; c++) acc = dfma(U[s + (size_t)c * m0], dvl[c * LD], acc);
+                                rbl[s * LD] = dfma(mu, acc, rbl[s * LD]);
+                            }
+                        __syncthreads(); // (every lane has read L: the next damped level overwrites D)
+                    }
+                }
+                // the level's reflectors, last first (a serial chain per lane, no barrier)
+                for (uint32_t j = rank; j--;)
+                {
+                    const uint32_t rows = dim - j;
+                    const double tau    = hh[F + j];
+                    if (rows == 1 || tau == 0.0) continue; // (uniform)
+                    double *v = cbl + (F + j) * LD;
+                    double t  = 0.0;
+                    for (uint32_t i = 1; i < rows; i++) t = dfma(w(F + j + i, Fc + j), v[i * LD], t);
+                    t += v[0];
+                    v[0] = dfma(-tau, t, v[0]);
+                    for (uint32_t i = 1; i < rows; i++) v[i * LD] = dfma(-(tau * w(F + j + i, Fc + j)), t, v[i * LD]);
+                }
+            }
+
+            // ---- (d) grad_fixed_j = gh_j - (column j of the fixed variables)^T cb, left in gh_j; then both outputs, transposed through LDS ----
+            if (grad_fixed)
+                for (uint32_t j = 0; j < nf; j++)
+                {
+                    double s = 0.0;
+                    for (uint32_t r = 0; r < M; r++) s = dfma(w(r, j), cbl[r * LD], s);
+                    ghl[j * LD] -= s;
+                }
+            __syncthreads();
+            {
+                double *out = grad_rhs + ((size_t)b * ncot + (size_t)tile * 64u) * cap;
+                for (uint32_t e = lane; e < kt * cap; e += NT)
+                {
+                    const uint32_t c = e / cap, r = e - c * cap;
+                    out[e]           = cb[r * LD + c]; // (rows behind the problem's own were never touched: 0)
+                }
+            }
+            if (grad_fixed)
+            {
+                double *out = grad_fixed + ((size_t)b * ncot + (size_t)tile * 64u) * n;
+                for (uint32_t e = lane; e < kt * n; e += NT)
+                {
+                    const uint32_t c = e / n, j = e - c * n;
+                    out[e]           = j < nf ? gh[j * LD + c] : 0.0;
+                }
+            }
+        }
     } // namespace
 
     size_t adjoint_reg_work_bytes(const LseArgs &a)
@@ -845,19 +1127,43 @@ namespace lexls
         return f;
     }
 
-    size_t adjoint_multi_work_bytes(const LseArgs &a)
+    /// the same for a regularized factor: adjoint_reg_multi_form (lexls_lds.h), unless LEXLS_ADJOINT_REG_MULTI_FORM = hbm | single names a later form
+    /// of the list (measurements)
+    static AdjointRegMultiForm adjoint_reg_multi_form_for(uint32_t nVar, uint32_t cap, uint32_t nObj)
     {
-        return adjoint_multi_form_for(a.nVar, a.cap) == AdjointMultiForm::per_cotangent ? 8 * (size_t)a.batch * (2 * (size_t)a.nVar + a.cap) : 0;
+        AdjointRegMultiForm f = adjoint_reg_multi_form(nVar, cap, nObj);
+        if (const char *e = std::getenv("LEXLS_ADJOINT_REG_MULTI_FORM"))
+        {
+            if (!std::strcmp(e, "single")) f = AdjointRegMultiForm::per_cotangent;
+            if (!std::strcmp(e, "hbm") && f == AdjointRegMultiForm::lds) f = AdjointRegMultiForm::hbm;
+        }
+        return f;
+    }
+    static bool adjoint_multi_per_cotangent(const LseArgs &a)
+    {
+        return a.reg_type != 0 ? adjoint_reg_multi_form_for(a.nVar, a.cap, a.nObj) == AdjointRegMultiForm::per_cotangent
+                               : adjoint_multi_form_for(a.nVar, a.cap) == AdjointMultiForm::per_cotangent;
+    }
+
+    size_t adjoint_multi_work_bytes(const LseArgs &a) { return adjoint_multi_per_cotangent(a) ? 8 * (size_t)a.batch * (2 * (size_t)a.nVar + a.cap) : 0; }
+
+    size_t adjoint_reg_multi_work_bytes(const LseArgs &a, uint32_t ncot)
+    {
+        if (a.reg_type == 0 || adjoint_reg_multi_form_for(a.nVar, a.cap, a.nObj) != AdjointRegMultiForm::hbm) return 0;
+        return 8 * (size_t)a.batch * ((ncot + 63u) / 64u) * adjoint_reg_matrix_doubles(a.nVar, a.nObj);
     }
 
     hipError_t launch_solve_adjoint_multi(const LseArgs &a, const double *d_G, uint32_t ncot, double *d_grad_rhs, double *d_grad_fixed, double *d_work, hipStream_t s,
-                                          const char **variant)
+                                          const char **variant, double *d_reg_work, double *d_reg_multi_work)
     {
-        const AdjointMultiForm f = adjoint_multi_form_for(a.nVar, a.cap);
-        const uint32_t tiles     = (ncot + 63u) / 64u;
+        const uint32_t tiles = (ncot + 63u) / 64u;
         if (ncot == 0 || tiles > 65535u) return hipErrorInvalidValue;
-        if (variant) *variant = adjoint_multi_form_name(f);
-        if (f == AdjointMultiForm::per_cotangent)
+        const bool reg = a.reg_type != 0;
+        if (reg && (!adjoint_reg_serves(a.reg_type) || a.reg_variable != 0.0 || !a.reg_factor)) return hipErrorInvalidValue;
+        const AdjointRegMultiForm rf = adjoint_reg_multi_form_for(a.nVar, a.cap, a.nObj);
+        const AdjointMultiForm f     = adjoint_multi_form_for(a.nVar, a.cap);
+        if (variant) *variant = reg ? adjoint_reg_multi_form_name(rf, adjoint_reg_in_lds(a.nVar, a.cap, a.nObj)) : adjoint_multi_form_name(f);
+        if (adjoint_multi_per_cotangent(a))
         {
             // the single-cotangent kernel reads and writes one row per problem, a problem after the other: cotangent c's rows (a stride of ncot
             // rows apart) travel through three buffers of that layout
@@ -867,12 +1173,25 @@ namespace lexls
             for (uint32_t c = 0; c < ncot; c++)
             {
                 hipError_t e = hipMemcpy2DAsync(w_g, 8 * n, d_G + (size_t)c * n, 8 * n * ncot, 8 * n, B, hipMemcpyDeviceToDevice, s);
-                if (e == hipSuccess) e = launch_solve_adjoint(a, w_g, w_rhs, d_grad_fixed ? w_fixed : nullptr, s);
+                if (e == hipSuccess) e = launch_solve_adjoint(a, w_g, w_rhs, d_grad_fixed ? w_fixed : nullptr, s, nullptr, d_reg_work);
                 if (e == hipSuccess) e = hipMemcpy2DAsync(d_grad_rhs + (size_t)c * cap, 8 * cap * ncot, w_rhs, 8 * cap, 8 * cap, B, hipMemcpyDeviceToDevice, s);
                 if (e == hipSuccess && d_grad_fixed) e = hipMemcpy2DAsync(d_grad_fixed + (size_t)c * n, 8 * n * ncot, w_fixed, 8 * n, 8 * n, B, hipMemcpyDeviceToDevice, s);
                 if (e != hipSuccess) return e;
             }
             return hipSuccess;
+        }
+        if (reg)
+        {
+            const bool in_lds = rf == AdjointRegMultiForm::lds;
+            const size_t lds  = adjoint_reg_multi_lds_bytes(a.nVar, a.cap, a.nObj, in_lds);
+            if (lds > kMaxLdsBytes || (!in_lds && !d_reg_multi_work)) return hipErrorInvalidValue;
+            hipError_t e = in_lds ? set_lds(solve_adjoint_reg_multi_kernel<64, true>, lds) : set_lds(solve_adjoint_reg_multi_kernel<64, false>, lds);
+            if (e != hipSuccess) return e;
+            if (in_lds)
+                hipLaunchKernelGGL((solve_adjoint_reg_multi_kernel<64, true>), dim3(a.batch, tiles), dim3(64), lds, s, a, d_G, ncot, d_grad_rhs, d_grad_fixed, nullptr);
+            else
+                hipLaunchKernelGGL((solve_adjoint_reg_multi_kernel<64, false>), dim3(a.batch, tiles), dim3(64), lds, s, a, d_G, ncot, d_grad_rhs, d_grad_fixed, d_reg_multi_work);
+            return hipGetLastError();
         }
         const bool staged = f == AdjointMultiForm::staged;
         const size_t lds  = adjoint_multi_lds_bytes(a.nVar, a.cap, staged);

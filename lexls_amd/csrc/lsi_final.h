@@ -240,9 +240,11 @@ struct LsiFinal
     // lexls_lsi_batch_set_adjoint_regularized: solve_adjoint answers after a resident regularized run of type 1, 3, 4, 5, 8, 9 (constant factors); off:
     // the rules of get_lambda, as before.  adj_rc / adj_msg: what solve_adjoint answers after the last run (set_rule); final_reg: the run was such
     // a run, and ensure_final_factor leaves the run's regularization on the groups' handles
-    bool adj_regularized = false, final_reg = false;
-    int adj_rc           = -1;
-    std::string adj_msg;
+    // lexls_lsi_batch_set_adjoint_regularized_multi: the same for solve_adjoint_multi (adjm_rc / adjm_msg), independent of the first switch;
+    // final_reg: either call is served after a regularized run
+    bool adj_regularized = false, adj_regularized_multi = false, final_reg = false;
+    int adj_rc = -1, adjm_rc = -1;
+    std::string adj_msg, adjm_msg;
     uint32_t final_formations = 0; // since creation: how often ensure_final_factor formed and factorized a group's final problems (lexls_lsi_batch_final_factorizations)
 
     explicit LsiFinal(const LsiBatchShape &shape) : s(shape) {}
@@ -347,29 +349,33 @@ struct LsiFinal
     bool needs_final_problem(const ParametersLexLSI &par) const
     {
         const int t = static_cast<int>(par.regularization_type);
-        return lam_rc_after(par) == LEXLS_OK || (adj_regularized && t != 0 && !par.cycling_handling_enabled && s.gather && s.total <= 65535);
+        return lam_rc_after(par) == LEXLS_OK || ((adj_regularized || adj_regularized_multi) && t != 0 && !par.cycling_handling_enabled && s.gather && s.total <= 65535);
     }
     /// The run is over and its working sets are kept: what get_lambda answers from now on (rc, and why not: msg), and what
-    /// lexls_lsi_batch_solve_adjoint(_device) answers — the same, except that a regularized run is served when the batch asked for it (adj_regularized),
-    /// the run was resident (its regularization is on the groups' handles), its type is one of the six whose damped solve is affine in the bounds and
-    /// its variable factor is zero
+    /// lexls_lsi_batch_solve_adjoint(_device) and lexls_lsi_batch_solve_adjoint_multi(_device) answer — the same, except that a regularized run is
+    /// served when the batch asked for it for that call (adj_regularized, adj_regularized_multi), the run was resident (its regularization is on the
+    /// groups' handles), its type is one of the six whose damped solve is affine in the bounds and its variable factor is zero
     void set_rule(int rc, const char *msg, const ParametersLexLSI &par, bool resident)
     {
         lam_rc = rc, lam_msg = msg;
-        adj_rc = lam_rc, adj_msg = lam_msg, final_reg = false;
+        adj_rc = adjm_rc = lam_rc, adj_msg = adjm_msg = lam_msg, final_reg = false;
         const int t = static_cast<int>(par.regularization_type);
         if (lam_rc != LEXLS_ERR_UNSUPPORTED || t == 0 || par.cycling_handling_enabled || !s.gather || s.total > 65535) return;
-        const std::string who = "lexls_lsi_batch_solve_adjoint: ";
-        if (!adj_regularized)
-            adj_msg = lam_msg + " (lexls_lsi_batch_set_adjoint_regularized, called before the run, lets lexls_lsi_batch_solve_adjoint serve regularization types 1, 3, 4, 5, 8, 9)";
-        else if (!resident)
-            adj_msg = who + "not available after a regularized run that was not resident on the device";
-        else if (!(t == 1 || t == 3 || t == 4 || t == 5 || t == 8 || t == 9))
-            adj_msg = who + "not available after a regularized run of regularization_type " + std::to_string(t) + " (served: 1, 3, 4, 5, 8, 9)";
-        else if (par.variable_regularization_factor != 0.0)
-            adj_msg = who + "not available after a regularized run with variable_regularization_factor != 0";
-        else
-            adj_rc = LEXLS_OK, adj_msg.clear(), final_reg = true;
+        auto rule = [&](bool on, const std::string &setter, const std::string &call, int &call_rc, std::string &call_msg) {
+            const std::string who = call + ": ";
+            if (!on)
+                call_msg = lam_msg + " (" + setter + ", called before the run, lets " + call + " serve regularization types 1, 3, 4, 5, 8, 9)";
+            else if (!resident)
+                call_msg = who + "not available after a regularized run that was not resident on the device";
+            else if (!(t == 1 || t == 3 || t == 4 || t == 5 || t == 8 || t == 9))
+                call_msg = who + "not available after a regularized run of regularization_type " + std::to_string(t) + " (served: 1, 3, 4, 5, 8, 9)";
+            else if (par.variable_regularization_factor != 0.0)
+                call_msg = who + "not available after a regularized run with variable_regularization_factor != 0";
+            else
+                call_rc = LEXLS_OK, call_msg.clear(), final_reg = true;
+        };
+        rule(adj_regularized, "lexls_lsi_batch_set_adjoint_regularized", "lexls_lsi_batch_solve_adjoint", adj_rc, adj_msg);
+        rule(adj_regularized_multi, "lexls_lsi_batch_set_adjoint_regularized_multi", "lexls_lsi_batch_solve_adjoint_multi", adjm_rc, adjm_msg);
     }
 
     // ---- the final equality problems ----
@@ -452,7 +458,10 @@ struct LsiFinal
         // (final_reg: a resident regularized run whose adjoint is served — its type and factors, shared or per instance, host or device rows, are on the
         // handle since the run's upload_regularization_block and stay there: the final factor is the damped one)
         if (final_reg)
-            hip_check(lexls_lse_set_adjoint_regularized(ctx.h, 1));
+        {
+            hip_check(lexls_lse_set_adjoint_regularized(ctx.h, adj_rc == LEXLS_OK));
+            hip_check(lexls_lse_set_adjoint_regularized_multi(ctx.h, adjm_rc == LEXLS_OK));
+        }
         else
             hip_check(lexls_lse_set_regularization(ctx.h, 0, NULL, 0, 0.0));
         const int policy = lexls_internal_kernel_policy(ctx.h);
@@ -671,12 +680,12 @@ struct LsiFinal
     }
 
     /// solve_adjoint and solve_adjoint_multi: d loss / d lb and d loss / d ub for ncot cotangents per instance — G batch x ncot x nVar, the outputs
-    /// batch x ncot x total, either may be NULL.  `single`: the call of one cotangent, which alone serves the regularized runs of set_rule — its own rule,
-    /// and lexls_lse_solve_adjoint_device; else lexls_lse_solve_adjoint_multi_device.  lsi_adjoint_scatter_multi_kernel serves both.
+    /// batch x ncot x total, either may be NULL.  `single`: the call of one cotangent — its own rule of set_rule (adj_rc), and
+    /// lexls_lse_solve_adjoint_device; else the multi call's rule (adjm_rc) and lexls_lse_solve_adjoint_multi_device.  lsi_adjoint_scatter_multi_kernel serves both.
     int bounds_gradient(const char *who, bool single, const double *G_in, uint32_t ncot, double *grad_lb, double *grad_ub, bool on_device)
     {
         const size_t total = s.total;
-        const GradientForm f = {who, single ? "g" : "G", single ? adj_rc : lam_rc, single ? adj_msg : lam_msg, ncot, 8 * (size_t)ncot * s.nVar, {8 * (size_t)ncot * total, 8 * (size_t)ncot * total}, false};
+        const GradientForm f = {who, single ? "g" : "G", single ? adj_rc : adjm_rc, single ? adj_msg : adjm_msg, ncot, 8 * (size_t)ncot * s.nVar, {8 * (size_t)ncot * total, 8 * (size_t)ncot * total}, false};
         void *const out[2]   = {grad_lb, grad_ub};
         return gradient(
             f, G_in, out, on_device, [&]() { ensure_adjoint_bufs(ncot, single ? "lexls_lsi_batch_solve_adjoint" : "lexls_lsi_batch_solve_adjoint_multi"); },

@@ -287,6 +287,20 @@ class BatchedLexLSE:
         type 1, 3, 4, 5, 8 or 9 with variable_factor == 0).  Off by default: they then raise LEXLS_ERR_UNSUPPORTED after every regularized
         factorization, as they always did."""
         capi.check(capi.lib().lexls_lse_set_adjoint_regularized(self._h, C.c_int(1 if on else 0)))
+        self._adj_reg = bool(on)
+
+    def set_adjoint_regularized_multi(self, on: bool = True):
+        """lexls_lse_set_adjoint_regularized_multi: let solve_adjoint_multi, solve_adjoint_multi_device and jacobian_device() answer after a damped
+        factorization (regularization type 1, 3, 4, 5, 8 or 9 with variable_factor == 0): M_reg^T g_c and N_reg^T g_c for every cotangent, the
+        factors held fixed.  Off by default, and independent of set_adjoint_regularized(): they then raise LEXLS_ERR_UNSUPPORTED after every
+        regularized factorization, as they always did."""
+        capi.check(capi.lib().lexls_lse_set_adjoint_regularized_multi(self._h, C.c_int(1 if on else 0)))
+        self._adj_reg_multi = bool(on)
+
+    def _one_cotangent_on_the_multi_entry(self):
+        """K == 1 goes to the single-cotangent entry (one live lane of the multi-cotangent kernel is slower) — unless this handle switched the
+        damped adjoint on for the multi calls alone: the single entry would refuse a damped factor then"""
+        return getattr(self, "_adj_reg_multi", False) and not getattr(self, "_adj_reg", False)
 
     def solve_adjoint(self, g):
         """lexls_lse_solve_adjoint + lexls_lse_get_adjoint: for fixed A the basic solution is affine in the right-hand sides and the fixed
@@ -324,12 +338,13 @@ class BatchedLexLSE:
     def solve_adjoint_multi(self, G):
         """lexls_lse_solve_adjoint_multi + lexls_lse_get_adjoint_multi: G (batch, K, nVar), K cotangents per problem in the order of get_x().
         Returns (grad_rhs (batch, K, cap), grad_fixed (batch, K, nVar)), row c what solve_adjoint(G[:, c]) returns (tolerance contract); a
-        cotangent's bits do not depend on K, on its position or on its neighbours.  One cotangent goes to the single-cotangent entry."""
+        cotangent's bits do not depend on K, on its position or on its neighbours.  One cotangent goes to the single-cotangent entry (to the multi
+        entry where set_adjoint_regularized_multi() alone is on).  A damped factor needs set_adjoint_regularized_multi()."""
         G = np.ascontiguousarray(G, np.float64)
         if G.ndim != 3 or G.shape[0] != self.batch or G.shape[1] == 0 or G.shape[2] != self.nVar:
             raise ValueError(f"G must have shape ({self.batch}, K >= 1, {self.nVar}), got {G.shape}")
         K = G.shape[1]
-        if K == 1:
+        if K == 1 and not self._one_cotangent_on_the_multi_entry():
             grad_rhs, grad_fixed = self.solve_adjoint(G[:, 0, :])
             return grad_rhs[:, None, :], grad_fixed[:, None, :]
         capi.check(capi.lib().lexls_lse_solve_adjoint_multi(self._h, _ptr(G, C.c_double), K))
@@ -354,7 +369,7 @@ class BatchedLexLSE:
             return C.c_void_p(t.data_ptr())
         args = (address("G", G, (self.batch, K, self.nVar)), address("grad_rhs", grad_rhs, (self.batch, K, self.cap)),
                 address("grad_fixed", grad_fixed, (self.batch, K, self.nVar)))
-        if K == 1:
+        if K == 1 and not self._one_cotangent_on_the_multi_entry():
             capi.check(capi.lib().lexls_lse_solve_adjoint_device(self._h, *args))
         else:
             capi.check(capi.lib().lexls_lse_solve_adjoint_multi_device(self._h, args[0], K, args[1], args[2]))
@@ -395,7 +410,8 @@ class BatchedLexLSE:
     def jacobian_device(self):
         """(dx_db (batch, nVar, cap), dx_dfixed (batch, nVar, nVar)) of the kept factor as torch tensors on the handle's device: the identity
         cotangents are built there and go through solve_adjoint_multi_device, so dx_db[b, i, r] = d x_i / d b_r (LOD row order) and
-        dx_dfixed[b, i, j] = d x_i / d x_fixed_j (fixVariable order, zero from nfixed on).  Enqueued in the handle's stream, not waited for."""
+        dx_dfixed[b, i, j] = d x_i / d x_fixed_j (fixVariable order, zero from nfixed on).  Enqueued in the handle's stream, not waited for.
+        After a damped factorization on a handle with set_adjoint_regularized_multi(): M_reg and N_reg of the damped solve."""
         import torch
         dev = torch.device("cuda", self.device)
         G = torch.eye(self.nVar, dtype=torch.float64, device=dev).expand(self.batch, self.nVar, self.nVar).contiguous()

@@ -550,8 +550,22 @@ class LsiBatch:
         """lexls_lsi_batch_set_adjoint_regularized: from the next run on, solve_adjoint / solve_adjoint_device also answer after a regularized run
         that was resident on the device, of regularization type 1, 3, 4, 5, 8 or 9 with variable_regularization_factor == 0: the gradient of the
         damped final equality problem, the factors (shared or per instance) held fixed as the matrices are.  Off by default: every regularized
-        run is refused, as before.  lambdas(), solve_adjoint_multi and solve_adjoint_matrix refuse regularized runs either way."""
+        run is refused, as before.  lambdas() and solve_adjoint_matrix refuse regularized runs either way; solve_adjoint_multi has a switch of its
+        own (set_adjoint_regularized_multi)."""
         capi.check(capi.lib().lexls_lsi_batch_set_adjoint_regularized(self._h, C.c_int(1 if on else 0)))
+        self._adj_reg = bool(on)
+
+    def set_adjoint_regularized_multi(self, on: bool = True):
+        """lexls_lsi_batch_set_adjoint_regularized_multi: from the next run on, solve_adjoint_multi / solve_adjoint_multi_device (and
+        jacobian_bounds_device) also answer after a regularized run, under the conditions of set_adjoint_regularized().  Off by default and
+        independent of that switch; the damped final factor is built once per run and shared by both calls."""
+        capi.check(capi.lib().lexls_lsi_batch_set_adjoint_regularized_multi(self._h, C.c_int(1 if on else 0)))
+        self._adj_reg_multi = bool(on)
+
+    def _one_cotangent_on_the_multi_entry(self):
+        """K == 1 goes to solve_adjoint — unless the batch switched the damped adjoint on for the multi calls alone (solve_adjoint would refuse a
+        regularized run then)"""
+        return getattr(self, "_adj_reg_multi", False) and not getattr(self, "_adj_reg", False)
 
     def set_working_set_log(self, max_entries: int):
         """lexls_lsi_batch_set_working_set_log: every later run() / run_device() keeps the working-set log of each instance
@@ -644,7 +658,7 @@ class LsiBatch:
         if G.ndim != 3 or G.shape[0] != self.batch or G.shape[1] == 0 or G.shape[2] != self.nvar:
             raise ValueError(f"solve_adjoint_multi: G has shape {G.shape}, ({self.batch}, K >= 1, {self.nvar}) expected")
         K = G.shape[1]
-        if K == 1:
+        if K == 1 and not self._one_cotangent_on_the_multi_entry():
             grad_lb, grad_ub = self.solve_adjoint(G[:, 0, :])
             return grad_lb[:, None, :], grad_ub[:, None, :]
         grad_lb, grad_ub = np.zeros((self.batch, K, self.total)), np.zeros((self.batch, K, self.total))
@@ -669,7 +683,7 @@ class LsiBatch:
         d_lb = self._device_array("grad_lb", grad_lb, torch.float64, (self.batch, K, self.total), optional=False)
         d_ub = self._device_array("grad_ub", grad_ub, torch.float64, (self.batch, K, self.total), optional=False)
         torch.cuda.synchronize(dev)  # G (and the zeroed outputs) are complete before the library's own streams read and write them
-        if K == 1:
+        if K == 1 and not self._one_cotangent_on_the_multi_entry():
             capi.check(capi.lib().lexls_lsi_batch_solve_adjoint_device(self._h, d_G, d_lb, d_ub))
         else:
             capi.check(capi.lib().lexls_lsi_batch_solve_adjoint_multi_device(self._h, d_G, K, d_lb, d_ub))

@@ -281,11 +281,13 @@ def solve_data(batch, data, var_index=None, active_guess=None, x0=None, out=None
 
 def jacobian_rhs(lse):
     """(dx_db (batch, nVar, cap), dx_dfixed (batch, nVar, nVar)) of the factor `lse` keeps (BatchedLexLSE.jacobian_device): what nVar backward
-    passes of SolveRhs with the unit cotangents would return, from one multi-cotangent pass.  The matrix is held fixed."""
+    passes of SolveRhs with the unit cotangents would return, from one multi-cotangent pass.  The matrix is held fixed.  A damped factor (regularization
+    type 1, 3, 4, 5, 8 or 9, constant factors) is served once lse.set_adjoint_regularized_multi() is on: the Jacobians of the damped solve."""
     return lse.jacobian_device()
 
 
 def jacobian_bounds(batch):
     """(dx_dlb, dx_dub), each (batch, nVar, total), of the last run of the LsiBatch `batch` (LsiBatch.jacobian_bounds_device): what nVar backward
-    passes of SolveBounds with the unit cotangents would return, from one multi-cotangent pass.  The matrices are held fixed."""
+    passes of SolveBounds with the unit cotangents would return, from one multi-cotangent pass.  The matrices are held fixed.  A regularized
+    run is served when batch.set_adjoint_regularized_multi() was on before it: the Jacobians of the damped final problem."""
     return batch.jacobian_bounds_device()
