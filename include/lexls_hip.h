@@ -339,6 +339,40 @@ int lexls_lse_solve_adjoint_matrix(lexls_lse_t h, const double *h_g);
 int lexls_lse_get_adjoint_matrix(lexls_lse_t h, double *h_grad_lod, uint8_t *h_differentiable);
 int lexls_lse_solve_adjoint_matrix_device(lexls_lse_t h, const double *d_g, double *d_grad_lod, uint8_t *d_differentiable);
 
+/* FORWARD-MODE tangents of the solve with respect to its data: how x moves along ntan directions d[A | b] (and dx_fixed) per problem, in one
+ * pass over the directions and two over the kept factor — the transpose of lexls_lse_solve_adjoint_matrix, which needs nVar calls on unit
+ * cotangents for the same quantity.  It exists where that gradient exists: for the RANK-STABLE problems of the rule above.
+ * Formula, in the symbols above (M the solve map x = M b + N x_fixed, k* the last level of non-zero rank, E_k* = keep the rows of level k*,
+ * lambda the multipliers of level k*), signs fixed against the dense KKT solve (tests/tangent_cases.py):
+ *     dx = M [ (db - dA x - A_fixed dx_fixed) - E_k* M^T (dA^T lambda) ]  on the pivot variables,
+ *     dx = dx_fixed on the fixed variables,  dx = 0 on the free variables (beyond the total rank).
+ * Layouts: dlod is ntan x batch x (nVar + 1) x cap doubles, direction c of problem b in the layout of lexls_lse_set_problem_host (what grad_lod
+ * has): entry (row i, column j) at ((c * batch + b) * (nVar + 1) + j) * cap + i, column nVar = db.  Entries of rows behind a problem's own
+ * dimensions are never read (a NaN there does not reach dx).  dfixed is ntan x batch x nVar in the layout of grad_fixed of
+ * lexls_lse_solve_adjoint: slot j < nfixed is the tangent of the j-th fixed value; NULL = zeros; the slots from nfixed on are never read.  dx is
+ * ntan x batch x nVar in the variable order of lexls_lse_get_x.  differentiable is one byte per problem, the bits
+ * lexls_lse_solve_adjoint_matrix writes; a problem with flag 0 gets exact zeros in all its rows of dx.
+ * The call needs what lexls_lse_solve_adjoint_matrix needs: a kept, unregularized factor and the x that belongs to it.
+ * lexls_lse_solve_tangent copies the directions in, launches and keeps the results in buffers of the handle (made for the largest ntan so far);
+ * lexls_lse_get_tangent copies them out (ntan x batch x nVar for the ntan of that call, and the flags; either output may be NULL); both follow
+ * lexls_lse_set_deferred_sync, and lexls_lse_get_tangent answers only while the results belong to the current factor.
+ * lexls_lse_solve_tangent_device reads d_dlod and d_dfixed (NULL: zeros) and writes d_dx and d_differentiable (NULL: not wanted) in device
+ * memory: it only enqueues in the handle's stream and makes no host-synchronising call (its work buffers are allocated at the first call and
+ * whenever ntan exceeds every earlier one).  What lexls_lse_get_multipliers, lexls_lse_get_v, lexls_lse_get_lambda and
+ * lexls_lse_get_sensitivity answer is not changed by these calls.
+ * Independence contract: for ntan >= 2 the tangent of a direction does not depend on ntan, on its position or on the other directions, bit for
+ * bit (one lane per direction, no cross-lane sums); the same bits come back from run to run and from the host and the device form.  ntan == 1
+ * computes M^T (dA^T lambda) with the single-cotangent kernel, whose sums are ordered differently: between ntan == 1 and ntan >= 2, and against
+ * any reference, the contract is the tolerance one.  No atomics.
+ * Errors, each returned before any device work and with every output left alone: LEXLS_ERR_INVALID for a null handle, a null dlod, a null
+ * d_dx, ntan == 0 or ntan > 65535; LEXLS_ERR_INVALID when there is no kept factor or no x belongs to it; LEXLS_ERR_UNSUPPORTED when the
+ * factorization ran with regularization_type != 0.
+ * Kernel variant (lexls_lse_last_consumer_kernel): "solve_tangent<64,staged>", "solve_tangent<64,lds>" or "solve_tangent<64,work>" — where the
+ * per-direction vectors of the solve map live, decided from nVar, cap and nObj alone. */
+int lexls_lse_solve_tangent(lexls_lse_t h, const double *h_dlod, const double *h_dfixed, uint32_t ntan);
+int lexls_lse_get_tangent(lexls_lse_t h, double *h_dx, uint8_t *h_differentiable);
+int lexls_lse_solve_tangent_device(lexls_lse_t h, const double *d_dlod, const double *d_dfixed, uint32_t ntan, double *d_dx, uint8_t *d_differentiable);
+
 /* ---- results (synchronise the stream, then D2H) ------------------------------------------------- */
 int lexls_lse_get_x(lexls_lse_t h, double *h_x);                    /* get_x()      lexlse.h:1587 */
 int lexls_lse_get_factor(lexls_lse_t h, double *h_lod);             /* get_lexqr()  lexlse.h:1626 */
@@ -871,6 +905,25 @@ int lexls_lsi_batch_set_adjoint_regularized_multi(lexls_lsi_batch_t b, int on);
  * handling, a regularized run, more than 65535 constraints, constraint data not resident: LEXLS_ERR_UNSUPPORTED). */
 int lexls_lsi_batch_solve_adjoint_matrix(lexls_lsi_batch_t b, const double *h_g, double *h_grad_data, uint8_t *h_differentiable);
 int lexls_lsi_batch_solve_adjoint_matrix_device(lexls_lsi_batch_t b, const double *d_g, double *d_grad_data, uint8_t *d_differentiable);
+/* FORWARD-MODE tangents of a batch's solutions with respect to its constraint data: how x of the last run moves along ntan directions per
+ * instance, while the working set holds — lexls_lse_solve_tangent on the final equality problem of every instance, the transpose of
+ * lexls_lsi_batch_solve_adjoint_matrix.
+ * Layouts: ddata is ntan x batch x per-instance data doubles, direction c of instance b in exactly the layout lexls_lsi_batch_run_device reads
+ * (per objective a column-major dim x w block, [dA | dlb | dub], or [dlb | dub] for simple bounds); dx is ntan x batch x nVar; differentiable
+ * (may be NULL) is one byte per instance, the flags lexls_lsi_batch_solve_adjoint_matrix writes.
+ * An active general row contributes its dA row and its dlb (CTR_ACTIVE_LB) or dub (CTR_ACTIVE_UB, CTR_ACTIVE_EQ: the bound the final problem
+ * reads); an active simple bound contributes its entry of dlb / dub by the same rule as the tangent of that fixed value.  Rows outside the
+ * working set, and rows absent under lexls_lsi_batch_set_instance_obj_dims, are never read: a NaN there changes nothing.
+ * An instance that did not end PROBLEM_SOLVED, or whose final problem is not rank-stable, gets flag 0 and exact zeros in its rows of dx; an
+ * empty working set is differentiable with dx = 0; with an instance mask set a skipped instance keeps the bits of its rows and of its flag.
+ * The final factor and its x are shared with lexls_lsi_batch_get_lambda and every adjoint call, in any call order
+ * (lexls_lsi_batch_final_factorizations still counts one formation per run and group).  Both forms are host-synchronous like
+ * lexls_lsi_batch_solve_adjoint_matrix(_device); the _device form takes memory of the batch's device and nothing passes through host memory.
+ * Tolerance contract; no atomics, the same bits from run to run and from the host and the device form.
+ * Errors, each returned before any device work and with every output left alone: LEXLS_ERR_INVALID for a null handle, a null ddata, a null dx
+ * or ntan == 0; otherwise exactly those of lexls_lsi_batch_solve_adjoint_matrix. */
+int lexls_lsi_batch_solve_tangent(lexls_lsi_batch_t b, const double *h_ddata, uint32_t ntan, double *h_dx, uint8_t *h_differentiable);
+int lexls_lsi_batch_solve_tangent_device(lexls_lsi_batch_t b, const double *d_ddata, uint32_t ntan, double *d_dx, uint8_t *d_differentiable);
 /* How often, since the batch was created, the final equality problems of a group were formed and factorized: the stage lexls_lsi_batch_get_lambda,
  * lexls_lsi_batch_solve_adjoint(_multi) and lexls_lsi_batch_solve_adjoint_matrix share.  It grows by the number of groups at the first of these
  * calls behind a run and not at all at the later ones, in every call order.  Host bookkeeping only.  LEXLS_ERR_INVALID for a null argument. */

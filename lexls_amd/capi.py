@@ -31,6 +31,7 @@ SYMBOLS = [
     "lexls_lse_multipliers", "lexls_lse_get_multipliers", "lexls_lse_solve_adjoint", "lexls_lse_set_adjoint_regularized", "lexls_lse_get_adjoint", "lexls_lse_solve_adjoint_device",
     "lexls_lse_solve_adjoint_multi", "lexls_lse_get_adjoint_multi", "lexls_lse_solve_adjoint_multi_device", "lexls_lse_set_adjoint_regularized_multi",
     "lexls_lse_solve_adjoint_matrix", "lexls_lse_get_adjoint_matrix", "lexls_lse_solve_adjoint_matrix_device",
+    "lexls_lse_solve_tangent", "lexls_lse_get_tangent", "lexls_lse_solve_tangent_device",
     "lexls_lsi_batch_get_lambda", "lexls_lsi_batch_solve_ex2",
     "lexls_lse_sensitivity_collect", "lexls_lse_sensitivity_collect_resident", "lexls_lse_get_wrong_sign",
     "lexls_lsi_batch_get_cycling_counters", "lexls_lsi_batch_run_device", "lexls_lsi_batch_run_device_ex",
@@ -41,6 +42,7 @@ SYMBOLS = [
     "lexls_lsi_batch_solve_adjoint", "lexls_lsi_batch_solve_adjoint_device", "lexls_lsi_batch_set_adjoint_regularized",
     "lexls_lsi_batch_solve_adjoint_multi", "lexls_lsi_batch_solve_adjoint_multi_device", "lexls_lsi_batch_set_adjoint_regularized_multi",
     "lexls_lsi_batch_solve_adjoint_matrix", "lexls_lsi_batch_solve_adjoint_matrix_device", "lexls_lsi_batch_final_factorizations",
+    "lexls_lsi_batch_solve_tangent", "lexls_lsi_batch_solve_tangent_device",
     "lexls_lsi_batch_last_kernel",
 ]
 
@@ -145,6 +147,12 @@ def lib() -> C.CDLL:
         _lib.lexls_lse_get_adjoint_matrix.argtypes = [C.c_void_p, C.POINTER(C.c_double), C.POINTER(C.c_uint8)]
         _lib.lexls_lse_solve_adjoint_matrix_device.restype = C.c_int
         _lib.lexls_lse_solve_adjoint_matrix_device.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]  # d_g, d_grad_lod, d_differentiable
+        _lib.lexls_lse_solve_tangent.restype = C.c_int
+        _lib.lexls_lse_solve_tangent.argtypes = [C.c_void_p, C.POINTER(C.c_double), C.POINTER(C.c_double), C.c_uint32]  # h_dlod, h_dfixed, ntan
+        _lib.lexls_lse_get_tangent.restype = C.c_int
+        _lib.lexls_lse_get_tangent.argtypes = [C.c_void_p, C.POINTER(C.c_double), C.POINTER(C.c_uint8)]
+        _lib.lexls_lse_solve_tangent_device.restype = C.c_int
+        _lib.lexls_lse_solve_tangent_device.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p]  # d_dlod, d_dfixed, ntan, d_dx, d_differentiable
         _lib.lexls_internal_apply_solve_map.restype = C.c_int
         _lib.lexls_internal_apply_solve_map.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]  # d_rhs, d_out: device addresses
         _lib.lexls_lsi_batch_solve_adjoint_multi.restype = C.c_int
@@ -153,6 +161,10 @@ def lib() -> C.CDLL:
         _lib.lexls_lsi_batch_solve_adjoint_multi_device.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p]  # d_G, ncot, d_grad_lb, d_grad_ub
         _lib.lexls_lsi_batch_solve_adjoint_matrix.restype = C.c_int
         _lib.lexls_lsi_batch_solve_adjoint_matrix.argtypes = [C.c_void_p, C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_uint8)]
+        _lib.lexls_lsi_batch_solve_tangent.restype = C.c_int
+        _lib.lexls_lsi_batch_solve_tangent.argtypes = [C.c_void_p, C.POINTER(C.c_double), C.c_uint32, C.POINTER(C.c_double), C.POINTER(C.c_uint8)]
+        _lib.lexls_lsi_batch_solve_tangent_device.restype = C.c_int
+        _lib.lexls_lsi_batch_solve_tangent_device.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p]  # d_ddata, ntan, d_dx, d_differentiable
         _lib.lexls_lsi_batch_final_factorizations.restype = C.c_int
         _lib.lexls_lsi_batch_final_factorizations.argtypes = [C.c_void_p, C.POINTER(C.c_uint32)]
         _lib.lexls_lsi_batch_solve_adjoint_matrix_device.restype = C.c_int

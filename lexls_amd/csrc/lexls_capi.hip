@@ -113,6 +113,15 @@ struct lexls_lse_s
     void *d_adjA_work    = nullptr;
     bool adjA_valid      = false;
     uint64_t adjA_epoch  = 0;
+    // lexls_lse_solve_tangent: the directions (ntan x batch x (nVar + 1) x cap, ntan x batch x nVar), dx (ntan x batch x nVar) and the flags (batch)
+    // of a host caller, made for the largest ntan so far; d_tan_work: the work buffers of the chain (launch_solve_tangent), likewise
+    double *d_tan_dlod = nullptr, *d_tan_dfixed = nullptr, *d_tan_dx = nullptr;
+    uint8_t *d_tan_flag = nullptr;
+    void *d_tan_work    = nullptr;
+    uint32_t tan_room = 0, tan_ntan = 0; // tangents the host buffers have room for; tangents of the last host call
+    size_t tan_work_bytes = 0;           // bytes of d_tan_work
+    bool tan_valid     = false;
+    uint64_t tan_epoch = 0;
     // accuracy guard (lexls_lse_set_accuracy_guard): mode 0 off, 1 report, 2 report + re-solve; arrays allocated when first switched on
     int guard_mode           = 0;
     double guard_threshold   = 0.0;
@@ -308,7 +317,8 @@ extern "C"
         void *ptrs[] = {h->d_in_owned, h->d_fac, h->d_hh, h->d_v, h->d_lambda, h->d_scratch, h->d_perm, h->d_rank, h->d_fcol, h->d_round_in, h->d_round_out,
                         h->d_large_state, h->d_large_ws, h->d_norms, h->d_cdata, h->d_reg_factor, h->d_reg_scratch, h->d_reg_mu, h->d_resume_level, h->d_resume_state,
                         h->d_guard_est, h->d_guard_status, h->d_guard_ind, h->d_mult, h->d_mult_scratch, h->d_wrong_sign, h->d_adj_g, h->d_adj_rhs, h->d_adj_fixed,
-                        h->d_adj_work, h->d_adjm_G, h->d_adjm_rhs, h->d_adjm_fixed, h->d_adjm_work, h->d_adjrm_work, h->d_adjA_g, h->d_adjA_grad, h->d_adjA_flag, h->d_adjA_work};
+                        h->d_adj_work, h->d_adjm_G, h->d_adjm_rhs, h->d_adjm_fixed, h->d_adjm_work, h->d_adjrm_work, h->d_adjA_g, h->d_adjA_grad, h->d_adjA_flag, h->d_adjA_work,
+                        h->d_tan_dlod, h->d_tan_dfixed, h->d_tan_dx, h->d_tan_flag, h->d_tan_work};
         for (void *p : ptrs)
             if (p) (void)hipFree(p);
         if (h->h_dims_pinned) (void)hipHostFree(h->h_dims_pinned);
@@ -1269,6 +1279,84 @@ extern "C"
         CHECK_HANDLE(h);
         return get_adjoint_results(h, "_matrix", h->adjA_valid, h->adjA_epoch,
                                    {{h_grad_lod, h->d_adjA_grad, 8 * (size_t)h->batch * h->problem_elems()}, {h_differentiable, h->d_adjA_flag, (size_t)h->batch}});
+    }
+
+    /// what every form of lexls_lse_solve_tangent checks before any device work: lexls_lse_solve_adjoint_matrix's preconditions, ntan
+    static int need_tangent(lexls_lse_t h, const char *who, const void *dlod, uint32_t ntan)
+    {
+        CHECK_HANDLE(h);
+        if (!dlod) return fail(LEXLS_ERR_INVALID, std::string(who) + ": null dlod");
+        if (ntan == 0) return fail(LEXLS_ERR_INVALID, std::string(who) + ": ntan == 0");
+        if (ntan > 65535u) return fail(LEXLS_ERR_INVALID, std::string(who) + ": ntan > 65535 (split the directions over several calls)");
+        return need_adjoint_matrix(h, who, dlod);
+    }
+    /// every form of lexls_lse_solve_tangent on device memory: the checks, the work buffers, the launch
+    static int run_solve_tangent(lexls_lse_t h, const char *who, const double *d_dlod, const double *d_dfixed, uint32_t ntan, double *d_dx, uint8_t *d_differentiable)
+    {
+        if (int rc = need_tangent(h, who, d_dlod, ntan)) return rc;
+        if (!d_dx) return fail(LEXLS_ERR_INVALID, std::string(who) + ": null d_dx");
+        HIP_TRY(hipSetDevice(h->device));
+        const size_t need = tangent_work_bytes(h->args(), ntan);
+        if (need > h->tan_work_bytes) // the work buffer holds the largest request so far (it grows with ntan, and with the placement)
+        {
+            if (h->d_tan_work) (void)hipFree(h->d_tan_work); // (waits for whatever still reads it)
+            h->d_tan_work = nullptr, h->tan_work_bytes = 0;
+            HIP_TRY(hipMalloc(&h->d_tan_work, need));
+            h->tan_work_bytes = need;
+        }
+        const size_t bytes = ntan > 1 ? adjoint_multi_work_bytes(h->args()) : 0; // (M^T w of several tangents: the per-cotangent form's buffers)
+        if (bytes && !h->d_adjm_work) HIP_TRY(hipMalloc((void **)&h->d_adjm_work, bytes));
+        HIP_TRY(launch_solve_tangent(h->args(), d_dlod, d_dfixed, ntan, d_dx, d_differentiable, h->d_tan_work, h->d_adjm_work, h->max_level_dim, h->stream, &h->last_consumer));
+        return LEXLS_OK;
+    }
+
+    int lexls_lse_solve_tangent(lexls_lse_t h, const double *h_dlod, const double *h_dfixed, uint32_t ntan)
+    {
+        const char *who = "lexls_lse_solve_tangent";
+        if (int rc = need_tangent(h, who, h_dlod, ntan)) return rc;
+        HIP_TRY(hipSetDevice(h->device));
+        const size_t B = h->batch, n = h->nVar;
+        if (ntan > h->tan_room) // the buffers hold the largest ntan so far
+        {
+            h->tan_valid = false;
+            h->tan_room  = 0;
+            for (double **p : {&h->d_tan_dlod, &h->d_tan_dfixed, &h->d_tan_dx})
+            {
+                if (*p) (void)hipFree(*p); // (waits for whatever still reads it)
+                *p = nullptr;
+            }
+            HIP_TRY(hipMalloc((void **)&h->d_tan_dlod, 8 * B * ntan * h->problem_elems()));
+            HIP_TRY(hipMalloc((void **)&h->d_tan_dfixed, 8 * B * ntan * n));
+            HIP_TRY(hipMalloc((void **)&h->d_tan_dx, 8 * B * ntan * n));
+            h->tan_room = ntan;
+        }
+        if (!h->d_tan_flag) HIP_TRY(hipMalloc((void **)&h->d_tan_flag, B));
+        if (h_dfixed) HIP_TRY(hipMemcpyAsync(h->d_tan_dfixed, h_dfixed, 8 * B * ntan * n, hipMemcpyHostToDevice, h->stream));
+        if (int rc = upload_adjoint_g(h, h->d_tan_dlod, h_dlod, 8 * B * ntan * h->problem_elems())) return rc;
+        if (int rc = run_solve_tangent(h, who, h->d_tan_dlod, h_dfixed ? h->d_tan_dfixed : nullptr, ntan, h->d_tan_dx, h->d_tan_flag)) return rc;
+        h->tan_valid = true;
+        h->tan_ntan  = ntan;
+        h->tan_epoch = h->factor_epoch;
+        return LEXLS_OK;
+    }
+
+    int lexls_lse_solve_tangent_device(lexls_lse_t h, const double *d_dlod, const double *d_dfixed, uint32_t ntan, double *d_dx, uint8_t *d_differentiable)
+    {
+        return run_solve_tangent(h, "lexls_lse_solve_tangent_device", d_dlod, d_dfixed, ntan, d_dx, d_differentiable);
+    }
+
+    int lexls_lse_get_tangent(lexls_lse_t h, double *h_dx, uint8_t *h_differentiable)
+    {
+        CHECK_HANDLE(h);
+        const std::string who = "lexls_lse_get_tangent";
+        if (!h->tan_valid) return fail(LEXLS_ERR_INVALID, who + ": call lexls_lse_solve_tangent first");
+        if (!h->factor_valid || h->tan_epoch != h->factor_epoch)
+            return fail(LEXLS_ERR_INVALID, who + ": the problem or its factorization changed since lexls_lse_solve_tangent (call it again)");
+        HIP_TRY(hipSetDevice(h->device));
+        if (h_dx) HIP_TRY(hipMemcpyAsync(h_dx, h->d_tan_dx, 8 * (size_t)h->batch * h->tan_ntan * h->nVar, hipMemcpyDeviceToHost, h->stream));
+        if (h_differentiable) HIP_TRY(hipMemcpyAsync(h_differentiable, h->d_tan_flag, (size_t)h->batch, hipMemcpyDeviceToHost, h->stream));
+        if (!h->deferred_sync) HIP_TRY(hipStreamSynchronize(h->stream));
+        return LEXLS_OK;
     }
 
     int lexls_internal_apply_solve_map(lexls_lse_t h, const double *d_rhs, double *d_out)

@@ -53,6 +53,17 @@ namespace lexls
     size_t adjoint_matrix_work_bytes(const LseArgs &a);
     hipError_t launch_solve_adjoint_matrix(const LseArgs &a, const double *d_g, double *d_grad_lod, uint8_t *d_differentiable, void *d_work, uint32_t sweep_level_dim_hint,
                                            hipStream_t s, const char **variant = nullptr, double *d_grad_fixed = nullptr);
+    /// lexls_lse_solve_tangent: d_dx (ntan x batch x nVar) = the tangents of x along the directions d_dlod (ntan x batch x the layout of the
+    /// problem data, [dA | db]; rows behind a problem's own are not read) and d_dfixed (ntan x batch x nVar, slot j < nfixed; may be NULL: zeros),
+    /// d_differentiable (batch bytes, may be NULL) = launch_solve_adjoint_matrix's flags; a.x holds the solution of the kept factor.
+    ///     dx = M [(db - dA x - A_fixed dfixed) - E_k* M^T (dA^T lambda)] on the pivot variables, dfixed on the fixed ones, 0 on the free
+    /// Chains, in the stream: the level search (k*), launch_sensitivity for level k* (lambda), tangent_rhs_kernel (the one pass over d_dlod: r and
+    /// w), launch_solve_adjoint (ntan == 1) or launch_solve_adjoint_multi (M^T w; d_adjoint_multi_work: what that launch wants,
+    /// adjoint_multi_work_bytes), apply_solve_map_multi_kernel with the per-lane vectors where tangent_map_placement (lexls_lds.h) puts them.
+    /// Everything they write goes to d_work (tangent_work_bytes for this ntan).  Enqueued only; no atomics
+    size_t tangent_work_bytes(const LseArgs &a, uint32_t ntan);
+    hipError_t launch_solve_tangent(const LseArgs &a, const double *d_dlod, const double *d_dfixed, uint32_t ntan, double *d_dx, uint8_t *d_differentiable, void *d_work,
+                                    double *d_adjoint_multi_work, uint32_t sweep_level_dim_hint, hipStream_t s, const char **variant = nullptr);
     // lse_postfactor.hip — the sensitivity, multiplier and least-norm kernels
     hipError_t launch_sensitivity(const LseArgs &a, const int32_t *d_obj_index, int32_t obj_all, double tolW, double tolC, hipStream_t s, bool scan_up = false,
                                   uint32_t sweep_level_dim_hint = 0, // hint = largest level dimension of the batch (enables the single-sweep kernel)

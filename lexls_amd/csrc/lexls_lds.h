@@ -288,5 +288,34 @@ namespace lexls
                                                : "solve_adjoint_reg<64,hbm> x K";
     }
 
+    // ---- apply_solve_map_multi (lse_adjoint.hip): the solve map on many right-hand sides, lane = right-hand side (lexls_lse_solve_tangent) ----
+    /// where the per-lane vectors z (nVar) and t (cap) of a wavefront's 64 right-hand sides live: in LDS beside the staged factor, in LDS with
+    /// the factor read where it is kept, or in a work buffer of the call ([index][lane], leading dimension 64: a lane's walk and the
+    /// load and store phases both take consecutive words) where one workgroup's LDS does not hold them
+    enum class TangentPlacement { staged, lds, work };
+    constexpr uint32_t kTangentWorkLd = 64;
+    /// the carve-up is solve_adjoint_multi's (z for gh, t for cb); the work placement keeps only the transpositions and the positions in LDS
+    inline size_t tangent_map_lds_bytes(uint32_t nVar, uint32_t cap, uint32_t /*nObj*/, TangentPlacement p)
+    {
+        if (p == TangentPlacement::work) return (8 * (size_t)nVar + 15) & ~(size_t)15;
+        return adjoint_multi_lds_bytes(nVar, cap, p == TangentPlacement::staged);
+    }
+    /// the placement rule of lexls_lse_solve_tangent, decided from the shape alone (the launcher and tests/tangent_fit_check.cpp read it here)
+    inline TangentPlacement tangent_map_placement(uint32_t nVar, uint32_t cap, uint32_t nObj)
+    {
+        if (tangent_map_lds_bytes(nVar, cap, nObj, TangentPlacement::staged) <= kMaxLdsBytes) return TangentPlacement::staged;
+        if (tangent_map_lds_bytes(nVar, cap, nObj, TangentPlacement::lds) <= kMaxLdsBytes) return TangentPlacement::lds;
+        return TangentPlacement::work;
+    }
+    /// doubles of the work buffer per (problem, tile of 64 right-hand sides) under the work placement
+    /// (constexpr: the kernel lays its work buffer out by it)
+    constexpr size_t tangent_map_work_doubles(uint32_t nVar, uint32_t cap) { return (size_t)kTangentWorkLd * ((size_t)nVar + cap); }
+    inline const char *tangent_placement_name(TangentPlacement p)
+    {
+        return p == TangentPlacement::staged ? "solve_tangent<64,staged>" : p == TangentPlacement::lds ? "solve_tangent<64,lds>" : "solve_tangent<64,work>";
+    }
+    /// tangent_rhs_kernel: x, the multipliers of level k*, the column sums w and the fixed slots' tangents
+    inline size_t tangent_rhs_lds_bytes(uint32_t nVar, uint32_t cap) { return 8 * (3 * (size_t)nVar + cap); }
+
     // ---- lqr_large (lqr_large.hip): lqr_large_plan.h ----
 } // namespace lexls

@@ -315,6 +315,30 @@ extern "C"
         return lsi_batch_solve_adjoint_matrix(b, d_g, d_grad_data, d_differentiable, true);
     }
 
+    /// both forms of the forward-mode tangent: the refusals of lsi_batch_solve_adjoint_matrix, plus ntan == 0 and a null dx
+    static int lsi_batch_solve_tangent(lexls_lsi_batch_t b, const double *ddata, uint32_t ntan, double *dx, uint8_t *differentiable, bool on_device)
+    {
+        return guarded([&]() {
+            const std::string who = on_device ? "lexls_lsi_batch_solve_tangent_device" : "lexls_lsi_batch_solve_tangent";
+            if (!b) throw Exception(who + ": null handle");
+            if (!ddata) throw Exception(who + ": null ddata");
+            if (!dx) throw Exception(who + ": null dx");
+            if (ntan == 0) throw Exception(who + ": ntan == 0");
+            b->refuse_pending(who.c_str());
+            return b->fin.solve_tangent(ddata, ntan, dx, differentiable, on_device);
+        });
+    }
+
+    int lexls_lsi_batch_solve_tangent(lexls_lsi_batch_t b, const double *h_ddata, uint32_t ntan, double *h_dx, uint8_t *h_differentiable)
+    {
+        return lsi_batch_solve_tangent(b, h_ddata, ntan, h_dx, h_differentiable, false);
+    }
+
+    int lexls_lsi_batch_solve_tangent_device(lexls_lsi_batch_t b, const double *d_ddata, uint32_t ntan, double *d_dx, uint8_t *d_differentiable)
+    {
+        return lsi_batch_solve_tangent(b, d_ddata, ntan, d_dx, d_differentiable, true);
+    }
+
     int lexls_lsi_batch_final_factorizations(lexls_lsi_batch_t b, uint32_t *h_count)
     {
         return guarded([&]() {

@@ -1081,6 +1081,268 @@ namespace lexls
                 }
             }
         }
+
+        // forward-mode tangents (lexls_lse_solve_tangent): the two right-hand sides from the direction, the solve map on many right-hand sides
+        /// One pass over the direction d[A | b] of tangent c = blockIdx.y of problem b = blockIdx.x (dlod: ntan x batch x the layout of the problem
+        /// data): per row i of the problem's own   r_i = db_i - sum_j dA_ij x_j - sum_{j < nf} W(i, j) dfixed_j   (the last sum is the fixed
+        /// slots' share of the right-hand side: the transpose of solve_adjoint_kernel's step (d), the untouched columns j < nf of the factor),
+        /// per column j   w_j = sum_i dA_ij lambda_i   (lambda: the multipliers of level kstar[b] as sensitivity_kernel leaves them, row i at
+        /// nfixed + i; zero without such a level).  R is batch x ntan x cap (zero behind the problem's own rows), Wv batch x ntan x nVar in the
+        /// order of x: the layouts launch_solve_adjoint_multi reads and writes.
+        /// One wavefront, the LANES ALONG THE ROWS of one column of the direction (consecutive addresses), AU columns requested together; every
+        /// entry of the problem's own rows is loaded exactly once, no entry behind them is loaded at all.  r_i is the lane's own dfma chain over
+        /// the columns in ascending order; w_j is one wavefront sum per column and trip of 64 rows, the trips added in ascending order by lane 0.
+        /// LDS (tangent_rhs_lds_bytes): x, w, the fixed slots' tangents (nVar each), lambda (cap).  No atomics.
+        template <int NT>
+        __global__ __launch_bounds__(NT) void tangent_rhs_kernel(LseArgs a, const double *__restrict__ dlod, const double *__restrict__ dfixed, const double *__restrict__ lam,
+                                                                 const int32_t *__restrict__ kstar, uint32_t ntan, double *__restrict__ R, double *__restrict__ Wv)
+        {
+            static_assert(NT == 64, "one wavefront per (problem, tangent): the column sums are wavefront sums");
+            constexpr uint32_t AU = 8;
+            extern __shared__ double smem[];
+            const uint32_t b = blockIdx.x, c = blockIdx.y, lane = threadIdx.x;
+            if (b >= a.batch || c >= ntan) return; // (block-uniform)
+            const KeptFactor kf = kept_factor_of(a, b);
+            const uint32_t n = kf.n, cap = kf.cap, nf = kf.nf, M = kf.M;
+            const double *__restrict__ W = kf.W;
+            double *xs = smem, *ws = xs + n, *df = ws + n, *ls = df + n;
+            const bool with_lambda = kstar[b] >= 0;
+            const size_t slot      = (size_t)c * a.batch + b; // tangent-major inputs
+            for (uint32_t i = lane; i < n; i += NT)
+            {
+                xs[i] = a.x[(size_t)b * n + i];
+                ws[i] = 0.0;
+                df[i] = (dfixed && i < nf) ? dfixed[slot * n + i] : 0.0;
+            }
+            for (uint32_t i = lane; i < cap; i += NT) ls[i] = (with_lambda && i < M) ? lam[(size_t)b * (n + cap) + nf + i] : 0.0;
+            __syncthreads();
+            const double *__restrict__ D = dlod + slot * (size_t)cap * (n + 1);
+            double *Rb = R + ((size_t)b * ntan + c) * cap;
+            for (uint32_t i0 = 0; i0 < cap; i0 += NT)
+            {
+                const uint32_t i = i0 + lane;
+                const bool live  = i < M;
+                if (i0 < M) // (uniform) a trip with rows of the problem's own
+                {
+                    double acc      = live ? D[(size_t)n * cap + i] : 0.0;
+                    const double li = live ? ls[i] : 0.0;
+                    for (uint32_t j0 = 0; j0 < n; j0 += AU)
+                    {
+                        double v[AU], s[AU];
+#pragma unroll
+                        for (uint32_t u = 0; u < AU; u++) v[u] = (live && j0 + u < n) ? D[(size_t)(j0 + u) * cap + i] : 0.0;
+#pragma unroll
+                        for (uint32_t u = 0; u < AU; u++)
+                        {
+                            if (j0 + u < n) acc = dfma(-v[u], xs[j0 + u], acc);
+                            s[u] = wave_sum(v[u] * li);
+                        }
+#pragma unroll
+                        for (uint32_t u = 0; u < AU; u++)
+                            if (lane == 0 && j0 + u < n) ws[j0 + u] += s[u];
+                    }
+                    for (uint32_t j0 = 0; j0 < nf; j0 += AU)
+                    {
+                        double v[AU];
+#pragma unroll
+                        for (uint32_t u = 0; u < AU; u++) v[u] = (live && j0 + u < nf) ? W[i + (size_t)(j0 + u) * cap] : 0.0;
+#pragma unroll
+                        for (uint32_t u = 0; u < AU; u++)
+                            if (j0 + u < nf) acc = dfma(-v[u], df[j0 + u], acc);
+                    }
+                    if (i < cap) Rb[i] = live ? acc : 0.0;
+                }
+                else if (i < cap)
+                    Rb[i] = 0.0;
+            }
+            __syncthreads();
+            for (uint32_t j = lane; j < n; j += NT) Wv[((size_t)b * ntan + c) * n + j] = ws[j];
+        }
+
+        /// dx = M (R - E_k* Y) + the fixed slots, for up to 64 right-hand sides of one problem at once, LANE = RIGHT-HAND SIDE: the transpose of
+        /// solve_adjoint_multi_kernel's steps (c), (b), (a), in that order — apply_solve_map_kernel's mathematics, solve_adjoint_multi_kernel's
+        /// division of the work.  One wavefront per (problem, tile of 64 tangents), lane l of tile t owns tangent 64 t + l; lanes beyond ntan
+        /// compute on zeros and store nothing.  Everything that steers the control flow belongs to the problem (wavefront-uniform); every factor
+        /// entry is the same for all lanes; every sum is the lane's own serial dfma chain in a fixed order — no cross-lane sum, no barrier
+        /// between the steps, and a tangent's bits do not depend on its lane, its tile or its neighbours.
+        /// R, Y: batch x ntan x cap (tangent_rhs_kernel's r; M^T w as launch_solve_adjoint(_multi) leaves it: only its rows of level kstar[b] are
+        /// read and subtracted).  dfixed (may be NULL: zeros), dx: ntan x batch x nVar; dx_i = the fixed slot's tangent where variable i is
+        /// fixed, z of its pivot column, 0 where it is free.  differentiable[b] (may be NULL; written by tile 0) = adjoint_matrix_kernel's
+        /// rank-stability rule on the STORED ranks; a problem that fails it gets exact zeros in all its rows of dx.
+        /// PLACE (TangentPlacement, lexls_lds.h): 0 the state z[nVar][LD], t[cap][LD] (LD = 65) and the staged factor in LDS, 1 the state in LDS
+        /// and the factor read where it is kept, 2 the state in `work` (tangent_map_work_doubles per (problem, tile), LD = 64).  No atomics.
+        template <int NT, int PLACE>
+        __global__ __launch_bounds__(NT) void apply_solve_map_multi_kernel(LseArgs a, const double *__restrict__ R, const double *__restrict__ Y, const int32_t *__restrict__ kstar,
+                                                                           const double *__restrict__ dfixed, uint32_t ntan, double *__restrict__ dx,
+                                                                           uint8_t *__restrict__ differentiable, double *work)
+        {
+            static_assert(NT == 64, "one wavefront per (problem, tile): lane = right-hand side");
+            constexpr bool STAGED = PLACE == 0, IN_WORK = PLACE == 2;
+            constexpr uint32_t LD = IN_WORK ? kTangentWorkLd : kAdjointMultiLd, AU = 4;
+            extern __shared__ double smem[];
+            const uint32_t b = blockIdx.x, tile = blockIdx.y, lane = threadIdx.x;
+            if (b >= a.batch || tile * 64u >= ntan) return; // (block-uniform)
+            const uint32_t kt = ntan - tile * 64u < 64u ? ntan - tile * 64u : 64u; // live tangents of this tile
+            const KeptFactor kf = kept_factor_of(a, b);
+            const uint32_t n = kf.n, cap = kf.cap, nObj = kf.nObj, nf = kf.nf, T = kf.T, M = kf.M;
+            const double *__restrict__ W = kf.W;
+            const uint32_t *dims = kf.dims;
+            double *state    = IN_WORK ? work + ((size_t)b * gridDim.y + tile) * tangent_map_work_doubles(n, cap) : smem;
+            double *z        = state;
+            double *t        = z + (size_t)n * LD;
+            uint32_t *perm_l = reinterpret_cast<uint32_t *>(IN_WORK ? smem : t + (size_t)cap * LD);
+            uint32_t *pos_l  = perm_l + n;
+            double *L        = reinterpret_cast<double *>(pos_l + n); // (2 n words: still 8-byte aligned)
+            const uint32_t ldl = cap | 1u;                            // odd_ld(cap)
+            double *hh_l       = L + (size_t)ldl * n;
+            auto Wat = [&](uint32_t r, uint32_t c) __attribute__((always_inline)) -> double { return STAGED ? L[r + c * ldl] : W[r + (size_t)c * cap]; };
+            auto tau_at = [&](uint32_t r) __attribute__((always_inline)) -> double { return STAGED ? hh_l[r] : kf.hh[r]; };
+
+            // the rank-stability rule of adjoint_matrix_kernel (the STORED ranks and nfixed as stored; uniform)
+            bool stable = true;
+            for (uint32_t k = 0; k < nObj; k++)
+            {
+                const uint32_t room = kf.fc[k] < n ? n - kf.fc[k] : 0;
+                if (kf.rk[k] != (dims[k] < room ? dims[k] : room)) stable = false;
+            }
+            if ((a.nfixed ? a.nfixed[b] : 0u) >= n) stable = true;
+            if (tile == 0 && lane == 0 && differentiable) differentiable[b] = stable ? 1 : 0;
+            const size_t B = a.batch;
+            if (!stable) // (uniform) no derivative: exact zeros
+            {
+                for (uint32_t e = lane; e < kt * n; e += NT)
+                {
+                    const uint32_t c = e / n, i = e - c * n;
+                    dx[(((size_t)tile * 64u + c) * B + b) * n + i] = 0.0;
+                }
+                return;
+            }
+            uint32_t lo = 0, hi = 0; // the rows of level k*: Y counts there alone
+            {
+                const int32_t ks = kstar[b];
+                if (ks >= 0 && (uint32_t)ks < nObj)
+                {
+                    for (uint32_t k = 0; k < (uint32_t)ks; k++) lo += dims[k];
+                    hi = lo + dims[ks];
+                    if (hi > M) hi = M;
+                }
+            }
+
+            // ---- staging; t = R - E_k* Y for every tangent of the tile, z = 0 ----
+            for (uint32_t i = lane; i < n; i += NT) perm_l[i] = a.perm[(size_t)b * n + i];
+            for (uint32_t i = lane; i < (n + cap) * LD; i += NT) state[i] = 0.0; // (dead lanes, absent rows, unreached columns: zeros)
+            if (STAGED)
+            {
+                for (uint32_t i = lane; i < cap; i += NT) hh_l[i] = kf.hh[i];
+                stage_factor<NT>(W, L, cap, n, ldl, lane); // (ends in a barrier)
+            }
+            else
+                __syncthreads();
+            for (uint32_t i = lane; i < n; i += NT) pos_l[i] = position_after_transpositions(perm_l, T, i);
+            {
+                const size_t off = ((size_t)b * ntan + (size_t)tile * 64u) * cap; // kt rows of cap doubles, contiguous
+                for (uint32_t e = lane; e < kt * cap; e += NT)
+                {
+                    const uint32_t c = e / cap, r = e - c * cap;
+                    if (r < M) t[r * LD + c] = (r >= lo && r < hi) ? R[off + e] - Y[off + e] : R[off + e];
+                }
+            }
+            __syncthreads();
+            double *zl = z + lane, *tl = t + lane; // this lane's column of the state
+
+            // ---- (c)^T factorize()'s right-hand-side updates, levels ascending: the level's reflectors, first to last, then the Gauss step ----
+            uint32_t F = 0;
+            for (uint32_t k = 0; k < nObj; k++)
+            {
+                const uint32_t dim = dims[k];
+                const auto [rank, Fc] = kf.level(k, dim);
+                if (rank > 0 && F + dim <= M)
+                {
+                    for (uint32_t j = 0; j < rank; j++)
+                    {
+                        const uint32_t rows = dim - j;
+                        const double tau    = tau_at(F + j);
+                        if (rows == 1 || tau == 0.0) continue; // (uniform)
+                        double *v = tl + (F + j) * LD;
+                        double s  = 0.0;
+                        for (uint32_t i = 1; i < rows; i++) s = dfma(Wat(F + j + i, Fc + j), v[i * LD], s);
+                        s += v[0];
+                        v[0] = dfma(-tau, s, v[0]);
+                        for (uint32_t i = 1; i < rows; i++) v[i * LD] = dfma(-(tau * Wat(F + j + i, Fc + j)), s, v[i * LD]);
+                    }
+                    const uint32_t Fn = F + dim;
+                    if (k + 1 < nObj && Fn < M)
+                    {
+                        // the Gauss step: AU rows of the later levels share one read of the level's top (each chain in ascending column order)
+                        for (uint32_t i0 = Fn; i0 < M; i0 += AU)
+                        {
+                            double acc[AU];
+#pragma unroll
+                            for (uint32_t u = 0; u < AU; u++) acc[u] = i0 + u < M ? tl[(i0 + u) * LD] : 0.0;
+                            for (uint32_t p = 0; p < rank; p++)
+                            {
+                                const double tp = tl[(F + p) * LD];
+#pragma unroll
+                                for (uint32_t u = 0; u < AU; u++)
+                                    if (i0 + u < M) acc[u] = dfma(-Wat(i0 + u, Fc + p), tp, acc[u]);
+                            }
+#pragma unroll
+                            for (uint32_t u = 0; u < AU; u++)
+                                if (i0 + u < M) tl[(i0 + u) * LD] = acc[u];
+                        }
+                    }
+                }
+                F += dim;
+            }
+
+            // ---- (b)^T solve(), levels descending: the top of the level minus [T_k] z on the pivot columns of the later levels (descending
+            // column order, as apply_solve_map_kernel), then the triangle, last column first ----
+            uint32_t Fend = F;
+            for (uint32_t k = nObj; k--;)
+            {
+                const uint32_t dim = dims[k];
+                F                  = Fend - dim;
+                Fend               = F;
+                const auto [rank, Fc] = kf.level(k, dim);
+                if (rank == 0 || F + dim > M) continue;
+                for (uint32_t i0 = 0; i0 < rank; i0 += AU)
+                {
+                    double acc[AU];
+#pragma unroll
+                    for (uint32_t u = 0; u < AU; u++) acc[u] = i0 + u < rank ? tl[(F + i0 + u) * LD] : 0.0;
+                    for (uint32_t c = T; c > Fc + rank; c--)
+                    {
+                        const double zc = zl[(c - 1) * LD];
+#pragma unroll
+                        for (uint32_t u = 0; u < AU; u++)
+                            if (i0 + u < rank) acc[u] = dfma(-Wat(F + i0 + u, c - 1), zc, acc[u]);
+                    }
+#pragma unroll
+                    for (uint32_t u = 0; u < AU; u++)
+                        if (i0 + u < rank) tl[(F + i0 + u) * LD] = acc[u];
+                }
+                for (uint32_t j = rank; j--;)
+                {
+                    const double zc     = tl[(F + j) * LD] / Wat(F + j, Fc + j);
+                    zl[(Fc + j) * LD] = zc;
+                    for (uint32_t i = 0; i < j; i++) tl[(F + i) * LD] = dfma(-Wat(F + i, Fc + j), zc, tl[(F + i) * LD]);
+                }
+            }
+            __syncthreads();
+
+            // ---- (a)^T dx = P z, and the fixed slots: variable i takes the entry of the position it reaches by the transpositions ----
+            for (uint32_t e = lane; e < kt * n; e += NT)
+            {
+                const uint32_t c = e / n, i = e - c * n, p = pos_l[i];
+                const size_t row = ((size_t)tile * 64u + c) * B + b;
+                double val       = 0.0;
+                if (p < nf)
+                    val = dfixed ? dfixed[row * n + p] : 0.0;
+                else if (p < T)
+                    val = z[p * LD + c];
+                dx[row * n + i] = val;
+            }
+        }
     } // namespace
 
     size_t adjoint_reg_work_bytes(const LseArgs &a)
@@ -1251,6 +1513,85 @@ namespace lexls
         if ((e = set_lds(adjoint_matrix_kernel<256>, lds)) != hipSuccess) return e;
         hipLaunchKernelGGL((adjoint_matrix_kernel<256>), dim3(a.batch), dim3(256), lds, s, a, w_y, t.lambda, w_u, w_star, d_grad_lod, d_differentiable);
         if (variant) *variant = "solve_adjoint_matrix<64>";
+        return hipGetLastError();
+    }
+
+    /// the placement launch_solve_tangent takes for a shape: tangent_map_placement (lexls_lds.h), unless LEXLS_TANGENT_PLACEMENT = lds | work names
+    /// a later placement of the list (measurements and tests: nothing moves a shape up)
+    static TangentPlacement tangent_placement_for(uint32_t nVar, uint32_t cap, uint32_t nObj)
+    {
+        TangentPlacement p = tangent_map_placement(nVar, cap, nObj);
+        if (const char *e = std::getenv("LEXLS_TANGENT_PLACEMENT"))
+        {
+            if (!std::strcmp(e, "work")) p = TangentPlacement::work;
+            if (!std::strcmp(e, "lds") && p == TangentPlacement::staged) p = TangentPlacement::lds;
+        }
+        return p;
+    }
+
+    /// r (batch x ntan x cap) | w (batch x ntan x nVar) | M^T w (batch x ntan x cap) | the scratch of the sensitivity launch | k* (batch words,
+    /// padded to 8 bytes) | under the work placement the per-lane vectors of every (problem, tile)
+    size_t tangent_work_bytes(const LseArgs &a, uint32_t ntan)
+    {
+        const size_t B = a.batch, tiles = (ntan + 63u) / 64u;
+        size_t bytes = 8 * B * ntan * (2 * (size_t)a.cap + a.nVar) + ((multipliers_scratch_bytes(a) + 7) & ~(size_t)7) + ((4 * B + 7) & ~(size_t)7);
+        if (tangent_placement_for(a.nVar, a.cap, a.nObj) == TangentPlacement::work) bytes += 8 * B * tiles * tangent_map_work_doubles(a.nVar, a.cap);
+        return bytes;
+    }
+
+    hipError_t launch_solve_tangent(const LseArgs &a, const double *d_dlod, const double *d_dfixed, uint32_t ntan, double *d_dx, uint8_t *d_differentiable, void *d_work,
+                                    double *d_adjoint_multi_work, uint32_t sweep_level_dim_hint, hipStream_t s, const char **variant)
+    {
+        const uint32_t tiles = (ntan + 63u) / 64u;
+        if (!d_work || !d_dlod || !d_dx || ntan == 0 || ntan > 65535u) return hipErrorInvalidValue;
+        const size_t B = a.batch, n = a.nVar, cap = a.cap;
+        const TangentPlacement place = tangent_placement_for(a.nVar, a.cap, a.nObj);
+        const size_t lds = tangent_map_lds_bytes(a.nVar, a.cap, a.nObj, place), lds_rhs = tangent_rhs_lds_bytes(a.nVar, a.cap);
+        if (lds > kMaxLdsBytes || lds_rhs > kMaxLdsBytes) return hipErrorInvalidValue;
+        // what the M^T w step will ask for, checked here so that a shape it cannot serve is refused before anything is enqueued: the
+        // single-cotangent kernel's LDS (ntan == 1, and every cotangent of the per-cotangent form) and that form's buffers
+        const bool per_cotangent = ntan > 1 && adjoint_multi_per_cotangent(a);
+        if ((ntan == 1 || per_cotangent) && adjoint_lds_bytes(a.nVar, a.cap) > kMaxLdsBytes) return hipErrorInvalidValue;
+        if (per_cotangent && !d_adjoint_multi_work) return hipErrorInvalidValue;
+        double *w_r     = static_cast<double *>(d_work);
+        double *w_w     = w_r + B * ntan * cap;
+        double *w_y     = w_w + B * ntan * n;
+        char *w_sens    = reinterpret_cast<char *>(w_y + B * ntan * cap);
+        int32_t *w_star = reinterpret_cast<int32_t *>(w_sens + ((multipliers_scratch_bytes(a) + 7) & ~(size_t)7));
+        double *w_state = reinterpret_cast<double *>(reinterpret_cast<char *>(w_star) + ((4 * B + 7) & ~(size_t)7));
+        // k*, and the multipliers of level k* into this call's buffers (launch_solve_adjoint_matrix's two steps: the getters answer what they did)
+        hipLaunchKernelGGL(adjoint_matrix_level_kernel, dim3((a.batch + 63u) / 64u), dim3(64), 0, s, a, w_star);
+        hipError_t e = hipGetLastError();
+        if (e != hipSuccess) return e;
+        LseArgs t;
+        e            = sensitivity_scratch_args(a, w_sens, s, &t);
+        t.wrong_sign = nullptr;
+        if (e == hipSuccess) e = launch_sensitivity(t, w_star, 0, 1e-8, 1e-12, s, false, sweep_level_dim_hint);
+        if (e == hipSuccess) e = set_lds(tangent_rhs_kernel<64>, lds_rhs);
+        if (e != hipSuccess) return e;
+        // r = db - dA x - A_fixed dfixed, w = dA^T lambda: the one pass over the direction
+        hipLaunchKernelGGL((tangent_rhs_kernel<64>), dim3(a.batch, ntan), dim3(64), lds_rhs, s, a, d_dlod, d_dfixed, t.lambda, w_star, ntan, w_r, w_w);
+        if ((e = hipGetLastError()) != hipSuccess) return e;
+        // M^T w
+        e = ntan == 1 ? launch_solve_adjoint(a, w_w, w_y, nullptr, s) : launch_solve_adjoint_multi(a, w_w, ntan, w_y, nullptr, d_adjoint_multi_work, s);
+        if (e != hipSuccess) return e;
+        // dx = M (r - E_k* M^T w) + the fixed slots
+        switch (place)
+        {
+        case TangentPlacement::staged:
+            if ((e = set_lds(apply_solve_map_multi_kernel<64, 0>, lds)) != hipSuccess) return e;
+            hipLaunchKernelGGL((apply_solve_map_multi_kernel<64, 0>), dim3(a.batch, tiles), dim3(64), lds, s, a, w_r, w_y, w_star, d_dfixed, ntan, d_dx, d_differentiable, nullptr);
+            break;
+        case TangentPlacement::lds:
+            if ((e = set_lds(apply_solve_map_multi_kernel<64, 1>, lds)) != hipSuccess) return e;
+            hipLaunchKernelGGL((apply_solve_map_multi_kernel<64, 1>), dim3(a.batch, tiles), dim3(64), lds, s, a, w_r, w_y, w_star, d_dfixed, ntan, d_dx, d_differentiable, nullptr);
+            break;
+        case TangentPlacement::work:
+            if ((e = set_lds(apply_solve_map_multi_kernel<64, 2>, lds)) != hipSuccess) return e;
+            hipLaunchKernelGGL((apply_solve_map_multi_kernel<64, 2>), dim3(a.batch, tiles), dim3(64), lds, s, a, w_r, w_y, w_star, d_dfixed, ntan, d_dx, d_differentiable, w_state);
+            break;
+        }
+        if (variant) *variant = tangent_placement_name(place);
         return hipGetLastError();
     }
 } // namespace lexls

@@ -160,6 +160,79 @@ namespace
             }
         }
     }
+    /// lexls_lsi_batch_solve_tangent for a whole group: the transpose of lsi_adjoint_matrix_scatter_kernel, with its routes (map, types, meta, shape).
+    /// Direction c = blockIdx.y of instance b = blockIdx.x (the caller's ddata: ntan x batch x per_data, the layout lexls_lsi_batch_run_device reads;
+    /// the group's instances start at instance lo of the batch) becomes the direction of its final equality problem, in the layouts
+    /// lexls_lse_solve_tangent_device reads: dlod (ntan x B x (n + 1) x cap: entry (LOD row i, column j) at j * cap + i) and dfixed (ntan x B x n).
+    /// Row r of the final problem (the nf fixed variables first, then the LOD rows) is user row pos[r]: an active general row contributes its dA row
+    /// and dlb (CTR_ACTIVE_LB) or dub (CTR_ACTIVE_UB, CTR_ACTIVE_EQ) — the bound the final problem reads —, an active simple bound its slot of
+    /// dfixed by the same rule.  Rows outside the working set, and rows absent under lexls_lsi_batch_set_instance_obj_dims, are never read; LOD rows
+    /// behind the problem's own and slots behind nf are not written (the equality solver does not read them).
+    /// The threads run along the LOD rows of one column of dlod, column after column: consecutive threads store at consecutive addresses; the
+    /// reads of ddata are the scattered side.  No atomics.  A masked instance is skipped.
+    __global__ __launch_bounds__(ADJM_NT) void lsi_tangent_gather_kernel(const double *__restrict__ ddata, const uint32_t *__restrict__ map, const uint8_t *__restrict__ types,
+                                                                         const int32_t *__restrict__ meta, const uint32_t *__restrict__ shape, uint32_t B, uint32_t batch,
+                                                                         uint32_t lo, uint32_t ntan, uint32_t nObj, uint32_t total, uint32_t n, uint32_t cap, size_t per_data,
+                                                                         double *__restrict__ dlod, double *__restrict__ dfixed, const uint8_t *mask)
+    {
+        const uint32_t b = blockIdx.x, c = blockIdx.y, tid = threadIdx.x;
+        if (b >= B || c >= ntan || lsi_mask_byte(mask, b) == 0) return; // (block-uniform)
+        const uint32_t nf = min((uint32_t)max(meta[2 * b + 1], 0), n);
+        const uint32_t na = min(map[b], min(total, nf + cap));
+        if (na == 0) return;
+        const uint32_t *pos = map + B + (size_t)b * total;
+        const uint8_t *ty   = types + (size_t)b * total;
+        const double *d_b   = ddata + ((size_t)c * batch + lo + b) * per_data;
+        double *lod = dlod + ((size_t)c * B + b) * cap * (n + 1), *fx = dfixed + ((size_t)c * B + b) * n;
+        const uint32_t M = na - nf; // LOD rows of the final problem
+        // (entry e: LOD row i of column j, j == n + 1 standing for the fixed slots)
+        for (uint32_t e = tid; e < M * (n + 1) + nf; e += ADJM_NT)
+        {
+            const bool fixed_slot = e >= M * (n + 1);
+            const uint32_t j = fixed_slot ? n : e / M, r = fixed_slot ? e - M * (n + 1) : nf + (e - j * M);
+            const uint32_t u = pos[r], t = ty[r];
+            const bool from_lb = t == CTR_ACTIVE_LB, from_ub = t == CTR_ACTIVE_UB || t == CTR_ACTIVE_EQ;
+            double val = 0.0;
+            for (uint32_t o = 0; o < nObj; o++) // the objective of user row u
+            {
+                const uint32_t dim = shape[4 * o], first = shape[4 * o + 3];
+                if (u < first || u - first >= dim) continue;
+                const uint32_t w = shape[4 * o + 1] ? n + 2 : 2u;
+                const double *blk = d_b + shape[4 * o + 2];
+                if (j < n)
+                {
+                    if (w > 2 && (from_lb || from_ub)) val = blk[(size_t)j * dim + (u - first)];
+                }
+                else if (from_lb)
+                    val = blk[(size_t)(w - 2) * dim + (u - first)];
+                else if (from_ub)
+                    val = blk[(size_t)(w - 1) * dim + (u - first)];
+                break;
+            }
+            if (fixed_slot)
+                fx[r] = val;
+            else
+                lod[(size_t)j * cap + (r - nf)] = val;
+        }
+    }
+
+    /// The tangents of the final equality problems (dx_lse: ntan x B x n, lexls_lse_solve_tangent_device's) into the caller's dx (ntan x batch x n) with
+    /// the conventions of lsi_adjoint_matrix_scatter_kernel: differentiable[b] = status PROBLEM_SOLVED && (empty working set || lse_flag[b]); where it
+    /// is 0, and for an empty working set (x = 0 whatever the data), the instance's rows of dx are exact zeros.  lse_flag / dx_lse NULL: the group
+    /// launched no chain.  A masked instance keeps the bits of its rows and of its flag.  Consecutive threads at consecutive addresses.
+    __global__ __launch_bounds__(64) void lsi_tangent_finish_kernel(const double *__restrict__ dx_lse, const uint8_t *__restrict__ lse_flag, const uint32_t *__restrict__ map,
+                                                                    const int32_t *__restrict__ meta, uint32_t B, uint32_t batch, uint32_t lo, uint32_t ntan, uint32_t total,
+                                                                    uint32_t n, uint32_t cap, double *__restrict__ dx, uint8_t *__restrict__ differentiable, const uint8_t *mask)
+    {
+        const uint32_t b = blockIdx.x, c = blockIdx.y, tid = threadIdx.x;
+        if (b >= B || c >= ntan || lsi_mask_byte(mask, b) == 0) return; // (block-uniform)
+        const uint32_t nf = min((uint32_t)max(meta[2 * b + 1], 0), n);
+        const uint32_t na = min(map[b], min(total, nf + cap));
+        const bool diff   = meta[2 * b] == (int32_t)PROBLEM_SOLVED && (na == 0 || (lse_flag && lse_flag[b] != 0));
+        if (c == 0 && tid == 0 && differentiable) differentiable[b] = diff ? 1 : 0;
+        const bool live = diff && na != 0 && dx_lse;
+        for (uint32_t i = tid; i < n; i += 64) dx[((size_t)c * batch + lo + b) * n + i] = live ? dx_lse[((size_t)c * B + b) * n + i] : 0.0;
+    }
 } // namespace
 
 /// What the after-run stage reads of the batch object (lexls_lsi_batch_s derives from it): its shape, the groups with their equality-solver handles and
@@ -223,9 +296,14 @@ struct LsiFinal
         double *d_grad_lod = NULL, *d_mat_out = NULL;
         uint8_t *d_lse_flag = NULL, *d_mat_flag = NULL;
         uint32_t *d_shape = NULL;
+        // lexls_lsi_batch_solve_tangent (ensure_tangent_bufs): the directions of the final equality problems (t_room x B x (nVar + 1) x cap and t_room x B x
+        // nVar) and their tangents (t_room x B x nVar), made for the largest ntan so far
+        double *d_tan_dlod = NULL, *d_tan_dfixed = NULL, *d_tan_dx = NULL;
+        uint32_t t_room = 0;
         ~Bufs()
         {
-            void *dev[] = {d_map, d_out, d_types, d_meta, d_g, d_grad_rhs, d_grad_fixed, d_grad_lb, d_grad_ub, d_grad_lod, d_mat_out, d_lse_flag, d_mat_flag, d_shape};
+            void *dev[] = {d_map, d_out, d_types, d_meta, d_g, d_grad_rhs, d_grad_fixed, d_grad_lb, d_grad_ub, d_grad_lod, d_mat_out, d_lse_flag, d_mat_flag, d_shape,
+                           d_tan_dlod, d_tan_dfixed, d_tan_dx};
             for (void *q : dev)
                 if (q) (void)hipFree(q);
         }
@@ -756,5 +834,121 @@ struct LsiFinal
                                    s.per_data, static_cast<double *>(d_out[0]), static_cast<uint8_t *>(d_out[1]), s.group_mask(g));
                 if (hipGetLastError() != hipSuccess) throw Exception("lsi_adjoint_matrix_scatter_kernel launch failed");
             });
+    }
+    // ---- forward mode ----
+    /// the groups' buffers of solve_tangent (behind those of solve_adjoint_matrix: the routes, the shape, the equality solver's flags), for the largest
+    /// ntan so far
+    void ensure_tangent_bufs(uint32_t ntan)
+    {
+        ensure_adjoint_matrix_bufs(false);
+        for (uint32_t g = 0; g < s.nGroups; g++)
+        {
+            Bufs &lb = *bufs[g];
+            if (ntan <= lb.t_room) continue;
+            const size_t Bg = s.grp[g]->B, cap = s.grp[g]->cap, rows = Bg * ntan;
+            lb.t_room = 0;
+            for (double **q : {&lb.d_tan_dlod, &lb.d_tan_dfixed, &lb.d_tan_dx})
+            {
+                if (*q) (void)hipFree(*q);
+                *q = NULL;
+            }
+            if (hipMalloc((void **)&lb.d_tan_dlod, 8 * rows * (s.nVar + 1) * (cap ? cap : 1)) != hipSuccess || hipMalloc((void **)&lb.d_tan_dfixed, 8 * rows * s.nVar) != hipSuccess ||
+                hipMalloc((void **)&lb.d_tan_dx, 8 * rows * s.nVar) != hipSuccess)
+                throw Exception("hipMalloc failed (lexls_lsi_batch_solve_tangent)");
+            lb.t_room = ntan;
+        }
+    }
+    /// a host caller's directions, tangents and flags on the device (made for the largest request so far)
+    struct TangentStage
+    {
+        double *d_ddata = NULL, *d_dx = NULL;
+        uint8_t *d_flag = NULL;
+        size_t ddata_bytes = 0, dx_bytes = 0;
+        ~TangentStage()
+        {
+            for (void *q : {(void *)d_ddata, (void *)d_dx, (void *)d_flag})
+                if (q) (void)hipFree(q);
+        }
+    } tan_stage;
+
+    /// lexls_lsi_batch_solve_tangent(_device): how x of the last run moves along ntan directions of the constraint data per instance (ddata: ntan x
+    /// batch x per_data, the layout lexls_lsi_batch_run_device reads; dx: ntan x batch x nVar; differentiable: batch bytes, may be NULL), while the
+    /// working set holds: the tangent of the final equality problem.  Per group, in its stream: the final factor (ensure_final_factor, shared with
+    /// get_lambda and every adjoint call: nothing is factorized twice), its x and the routes once per run, lsi_tangent_gather_kernel,
+    /// lexls_lse_solve_tangent_device, lsi_tangent_finish_kernel.  The rule of the last run is solve_adjoint_matrix's (lam_rc).  The host form stages in
+    /// buffers of the batch (under a mask the caller's dx and flags travel there first).  Waits for the groups' streams before it returns.
+    int solve_tangent(const double *ddata, uint32_t ntan, double *dx, uint8_t *differentiable, bool on_device)
+    {
+        const std::string who = on_device ? "lexls_lsi_batch_solve_tangent_device" : "lexls_lsi_batch_solve_tangent";
+        if (lam_rc < 0) throw Exception(who + ": no completed lexls_lsi_batch_run on this batch");
+        if (lam_rc != LEXLS_OK)
+        {
+            lexls_internal_set_error(lam_msg.c_str());
+            return lam_rc;
+        }
+        if (ntan > 65535u) throw Exception(who + ": more than 65535 directions per instance");
+        if (hipSetDevice(s.device) != hipSuccess) throw Exception(who + ": hipSetDevice failed");
+        ensure_tangent_bufs(ntan);
+        const size_t in_bytes = 8 * (size_t)ntan * s.batch * s.per_data, out_bytes = 8 * (size_t)ntan * s.batch * s.nVar;
+        const double *d_ddata = ddata;
+        double *d_dx          = dx;
+        uint8_t *d_flag       = differentiable;
+        if (!on_device)
+        {
+            TangentStage &st = tan_stage;
+            if (in_bytes > st.ddata_bytes)
+            {
+                if (st.d_ddata) (void)hipFree(st.d_ddata);
+                st.d_ddata = NULL, st.ddata_bytes = 0;
+                if (hipMalloc((void **)&st.d_ddata, in_bytes ? in_bytes : 8) != hipSuccess) throw Exception(who + ": hipMalloc failed");
+                st.ddata_bytes = in_bytes;
+            }
+            if (out_bytes > st.dx_bytes)
+            {
+                if (st.d_dx) (void)hipFree(st.d_dx);
+                st.d_dx = NULL, st.dx_bytes = 0;
+                if (hipMalloc((void **)&st.d_dx, out_bytes) != hipSuccess) throw Exception(who + ": hipMalloc failed");
+                st.dx_bytes = out_bytes;
+            }
+            if (!st.d_flag && hipMalloc((void **)&st.d_flag, s.batch) != hipSuccess) throw Exception(who + ": hipMalloc failed");
+            bool ok = hipMemcpy(st.d_ddata, ddata, in_bytes, hipMemcpyHostToDevice) == hipSuccess;
+            if (ok && s.d_mask) ok = hipMemcpy(st.d_dx, dx, out_bytes, hipMemcpyHostToDevice) == hipSuccess; // a skipped instance keeps the caller's bits
+            if (ok && s.d_mask && differentiable) ok = hipMemcpy(st.d_flag, differentiable, s.batch, hipMemcpyHostToDevice) == hipSuccess;
+            if (!ok) throw Exception(who + ": hipMemcpy failed (ddata)");
+            d_ddata = st.d_ddata, d_dx = st.d_dx, d_flag = differentiable ? st.d_flag : NULL;
+        }
+        for (uint32_t g = 0; g < s.nGroups; g++)
+        {
+            BatchCtx &ctx         = *s.grp[g];
+            Bufs &lb              = *bufs[g];
+            const bool any_active = ensure_final_factor(g, []() {});
+            upload_adjoint_routes(g, who.c_str());
+            if (any_active && !final_solved[g])
+            {
+                hip_check(lexls_lse_solve(ctx.h)); // the stage factorizes only: the chain wants the x of this factor
+                final_solved[g] = 1;
+            }
+            // nobody has an active constraint: nothing was factorized, every tangent is zero (and every solved instance differentiable)
+            if (any_active)
+            {
+                hipLaunchKernelGGL(lsi_tangent_gather_kernel, dim3(ctx.B, ntan), dim3(ADJM_NT), 0, ctx.stream, d_ddata, lb.d_map, lb.d_types, lb.d_meta, lb.d_shape, ctx.B, s.batch,
+                                   s.lo[g], ntan, s.nObj, (uint32_t)s.total, s.nVar, ctx.cap, s.per_data, lb.d_tan_dlod, lb.d_tan_dfixed, s.group_mask(g));
+                if (hipGetLastError() != hipSuccess) throw Exception("lsi_tangent_gather_kernel launch failed");
+                hip_check(lexls_lse_solve_tangent_device(ctx.h, lb.d_tan_dlod, lb.d_tan_dfixed, ntan, lb.d_tan_dx, lb.d_lse_flag));
+            }
+            hipLaunchKernelGGL(lsi_tangent_finish_kernel, dim3(ctx.B, ntan), dim3(64), 0, ctx.stream, any_active ? lb.d_tan_dx : (const double *)NULL,
+                               any_active ? lb.d_lse_flag : (const uint8_t *)NULL, lb.d_map, lb.d_meta, ctx.B, s.batch, s.lo[g], ntan, (uint32_t)s.total, s.nVar, ctx.cap, d_dx,
+                               d_flag ? d_flag + s.lo[g] : (uint8_t *)NULL, s.group_mask(g));
+            if (hipGetLastError() != hipSuccess) throw Exception("lsi_tangent_finish_kernel launch failed");
+        }
+        for (uint32_t g = 0; g < s.nGroups; g++)
+            if (hipStreamSynchronize(s.grp[g]->stream) != hipSuccess) throw Exception(who + ": stream synchronisation failed");
+        if (!on_device)
+        {
+            bool ok = hipMemcpy(dx, d_dx, out_bytes, hipMemcpyDeviceToHost) == hipSuccess;
+            if (ok && differentiable) ok = hipMemcpy(differentiable, d_flag, s.batch, hipMemcpyDeviceToHost) == hipSuccess;
+            if (!ok) throw Exception(who + ": hipMemcpy failed (results)");
+        }
+        return LEXLS_OK;
     }
 };

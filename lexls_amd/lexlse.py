@@ -407,6 +407,50 @@ class BatchedLexLSE:
                                                                      address("grad_lod", grad_lod, (self.batch, self.nVar + 1, self.cap)),
                                                                      address("differentiable", differentiable, (self.batch,), "torch.uint8")))
 
+    # ---- forward-mode tangents of the solve with respect to its data (rank-stable problems) ----------
+    def solve_tangent(self, dlod, dfixed=None):
+        """lexls_lse_solve_tangent + lexls_lse_get_tangent: dlod (K, batch, nVar + 1, cap), K directions d[A | b] in the layout of the problem
+        data (rows behind a problem's own are not read), or (batch, nVar + 1, cap) for one; dfixed (K, batch, nVar) / (batch, nVar), slot j <
+        nfixed the tangent of the j-th fixed value (None: zeros).  Returns (dx, differentiable): dx (K, batch, nVar) — (batch, nVar) for a
+        single direction given without the leading axis — in the order of get_x(), and differentiable (batch,) uint8, the flags of
+        solve_adjoint_matrix; where the flag is 0 the problem's rows of dx are exact zeros.  Needs what solve_adjoint_matrix needs."""
+        dlod = np.ascontiguousarray(dlod, np.float64)
+        single = dlod.ndim == 3
+        if single:
+            dlod = dlod[None]
+        if dlod.ndim != 4 or dlod.shape[0] == 0 or dlod.shape[1:] != (self.batch, self.nVar + 1, self.cap):
+            raise ValueError(f"dlod must have shape (K >= 1, {self.batch}, {self.nVar + 1}, {self.cap}) or lack the leading axis, got {dlod.shape}")
+        K = dlod.shape[0]
+        if dfixed is not None:
+            dfixed = np.ascontiguousarray(dfixed, np.float64).reshape((K, self.batch, self.nVar))
+        capi.check(capi.lib().lexls_lse_solve_tangent(self._h, _ptr(dlod, C.c_double), None if dfixed is None else _ptr(dfixed, C.c_double), K))
+        dx = np.zeros((K, self.batch, self.nVar))
+        differentiable = np.zeros(self.batch, np.uint8)
+        capi.check(capi.lib().lexls_lse_get_tangent(self._h, _ptr(dx, C.c_double), _ptr(differentiable, C.c_uint8)))
+        return (dx[0] if single else dx), differentiable
+
+    def solve_tangent_device(self, dlod, dx, dfixed=None, differentiable=None):
+        """lexls_lse_solve_tangent_device: dlod (K, batch, nVar + 1, cap), dx (K, batch, nVar), dfixed (K, batch, nVar; None: zeros) float64 and
+        differentiable (batch,) uint8 (None: not wanted) in device memory, contiguous torch tensors; a single direction may lack the leading
+        axis in all three.  Only enqueued in the handle's stream (set_stream): the directions have to be complete in stream order."""
+        if not hasattr(dlod, "data_ptr") or dlod.dim() not in (3, 4):
+            raise ValueError("solve_tangent_device: dlod must be a tensor of shape (K >= 1, batch, nVar + 1, cap) or (batch, nVar + 1, cap)")
+        lead = () if dlod.dim() == 3 else (int(dlod.shape[0]),)
+        K = lead[0] if lead else 1
+        if K == 0:
+            raise ValueError("solve_tangent_device: K == 0")
+
+        def address(name, t, shape, dtype="torch.float64"):
+            if t is None:
+                return None
+            if not hasattr(t, "data_ptr") or str(t.dtype) != dtype or not t.is_contiguous() or tuple(t.shape) != shape:
+                raise ValueError(f"solve_tangent_device: {name} must be a contiguous {dtype.split('.')[1]} tensor of shape {shape}")
+            return C.c_void_p(t.data_ptr())
+        capi.check(capi.lib().lexls_lse_solve_tangent_device(self._h, address("dlod", dlod, lead + (self.batch, self.nVar + 1, self.cap)),
+                                                              address("dfixed", dfixed, lead + (self.batch, self.nVar)), K,
+                                                              address("dx", dx, lead + (self.batch, self.nVar)),
+                                                              address("differentiable", differentiable, (self.batch,), "torch.uint8")))
+
     def jacobian_device(self):
         """(dx_db (batch, nVar, cap), dx_dfixed (batch, nVar, nVar)) of the kept factor as torch tensors on the handle's device: the identity
         cotangents are built there and go through solve_adjoint_multi_device, so dx_db[b, i, r] = d x_i / d b_r (LOD row order) and

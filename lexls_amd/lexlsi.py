@@ -725,6 +725,48 @@ class LsiBatch:
         capi.check(capi.lib().lexls_lsi_batch_solve_adjoint_matrix_device(self._h, d_g, d_out, d_flag))
         return grad_data, differentiable
 
+    def solve_tangent(self, ddata):
+        """lexls_lsi_batch_solve_tangent: `ddata` (K, batch, per_data), K directions of the constraint data per instance in the layout of
+        PackedBatch.data, or (batch, per_data) for one.  Returns (dx, differentiable): dx (K, batch, nvar) — (batch, nvar) for a single direction
+        given without the leading axis —, how x of the last run moves along each direction while the working set holds, and differentiable
+        (batch,) uint8, the flags of solve_adjoint_matrix: 0 where the instance did not end PROBLEM_SOLVED or its final problem is not
+        rank-stable, with exact zeros in its rows of dx.  Rows outside the final working set are never read.  Raises after the runs
+        solve_adjoint_matrix() raises after."""
+        ddata = np.ascontiguousarray(ddata, np.float64)
+        single = ddata.ndim == 2
+        if single:
+            ddata = ddata[None]
+        if ddata.ndim != 3 or ddata.shape[0] == 0 or ddata.shape[1:] != (self.batch, self.per_data):
+            raise ValueError(f"solve_tangent: ddata has shape {ddata.shape}, (K >= 1, {self.batch}, {self.per_data}) expected")
+        K = ddata.shape[0]
+        dx, differentiable = np.zeros((K, self.batch, self.nvar)), np.zeros(self.batch, np.uint8)
+        capi.check(capi.lib().lexls_lsi_batch_solve_tangent(self._h, _p(ddata, C.c_double), K, _p(dx, C.c_double), _p(differentiable, C.c_uint8)))
+        return (dx[0] if single else dx), differentiable
+
+    def solve_tangent_device(self, ddata, dx=None, differentiable=None):
+        """lexls_lsi_batch_solve_tangent_device: solve_tangent() on torch tensors of the batch's device — `ddata` float64 (K, batch, per_data) or
+        (batch, per_data), `dx` float64 with the same leading axis and (batch, nvar), `differentiable` uint8 (batch,), contiguous; an output that
+        is not given is allocated (zeroed).  Returns (dx, differentiable).  Nothing of them passes through host memory.  Under an instance mask
+        the rows and the flag of a skipped instance keep their bits: pass the tensors that hold them.  The call waits for the device."""
+        import torch
+        if not hasattr(ddata, "dim") or ddata.dim() not in (2, 3):
+            raise ValueError("solve_tangent_device: ddata must be a tensor of shape (K >= 1, batch, per_data) or (batch, per_data)")
+        lead = () if ddata.dim() == 2 else (int(ddata.shape[0]),)
+        K = lead[0] if lead else 1
+        if K == 0:
+            raise ValueError("solve_tangent_device: K == 0")
+        d_in = self._device_array("ddata", ddata, torch.float64, lead + (self.batch, self.per_data), optional=False)
+        dev = torch.device("cuda", self.device)
+        if dx is None:
+            dx = torch.zeros(lead + (self.batch, self.nvar), dtype=torch.float64, device=dev)
+        if differentiable is None:
+            differentiable = torch.zeros((self.batch,), dtype=torch.uint8, device=dev)
+        d_out = self._device_array("dx", dx, torch.float64, lead + (self.batch, self.nvar), optional=False)
+        d_flag = self._device_array("differentiable", differentiable, torch.uint8, (self.batch,), optional=False)
+        torch.cuda.synchronize(dev)  # ddata (and the zeroed outputs) are complete before the library's own streams read and write them
+        capi.check(capi.lib().lexls_lsi_batch_solve_tangent_device(self._h, d_in, K, d_out, d_flag))
+        return dx, differentiable
+
     def split_grad_data(self, row):
         """one instance's row of grad_data (or of the data itself) as the list of per-objective dict(A=, lb=, ub=) (simple bounds: lb, ub): the
         inverse of flatten(), by unflatten()"""

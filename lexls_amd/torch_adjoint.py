@@ -23,9 +23,19 @@ per-instance flag and zeros for the others.
 ``jacobian_rhs`` and ``jacobian_bounds`` return the whole Jacobians, dx/db and dx/dlb, dx/dub, from one multi-cotangent pass
 (lexls_lse_solve_adjoint_multi_device: lane = cotangent) instead of nVar backward passes.
 
+``jvp_lod`` is the forward mode of ``SolveLod``: the tangents of x along K directions of the problem data in one pass
+(lexls_lse_solve_tangent_device), where ``SolveLod`` would need nVar backward passes for the same quantity; ``jvp_data`` is the same for
+``SolveData`` (lexls_lsi_batch_solve_tangent_device).
+
 torch is imported when the operation is first used, not with the package.
 """
 from __future__ import annotations
+
+
+class _Span:  # the CUDA array interface over memory this object does not own
+    def __init__(self, address, shape):
+        self.__cuda_array_interface__ = dict(shape=shape, typestr="<f8", data=(int(address), False), version=2, strides=None)
+
 
 _SOLVE_RHS = None
 
@@ -35,10 +45,6 @@ def _solve_rhs_class():
     if _SOLVE_RHS is not None:
         return _SOLVE_RHS
     import torch
-
-    class _Span:  # the CUDA array interface over memory this object does not own
-        def __init__(self, address, shape):
-            self.__cuda_array_interface__ = dict(shape=shape, typestr="<f8", data=(int(address), False), version=2, strides=None)
 
     class SolveRhs(torch.autograd.Function):
         """x = SolveRhs.apply(rhs, lse, lod): rhs (batch, cap) float64 on the device, lse a BatchedLexLSE of that shape (dimensions, fixed
@@ -203,10 +209,6 @@ def _solve_lod_class():
     import torch
     from torch.autograd.function import once_differentiable
 
-    class _Span:  # the CUDA array interface over memory this object does not own
-        def __init__(self, address, shape):
-            self.__cuda_array_interface__ = dict(shape=shape, typestr="<f8", data=(int(address), False), version=2, strides=None)
-
     class SolveLod(torch.autograd.Function):
         """x = SolveLod.apply(lod, lse): lod (batch, nVar + 1, cap) float64 on the device, the matrices and the right-hand sides in the layout of
         setProblem; lse a BatchedLexLSE of that shape (dimensions, fixed variables and tolerance set by the caller; no regularization).  Forward
@@ -264,6 +266,43 @@ def solve_lod(solver, lod):
     """SolveLod.apply(lod, solver): the solutions of the batch `lod` (batch, nVar + 1, cap) on the BatchedLexLSE `solver`, differentiable in the
     matrices and the right-hand sides where the problems are rank-stable"""
     return _solve_lod_class().apply(lod, solver)
+
+
+def jvp_lod(solver, lod, dlod, dfixed=None):
+    """Forward mode of solve_lod: (x, dx) for the batch `lod` (batch, nVar + 1, cap) on the BatchedLexLSE `solver` and the directions `dlod`
+    (K, batch, nVar + 1, cap) — or (batch, nVar + 1, cap) for one —, float64 device tensors; `dfixed` (the same leading axis, batch, nVar): the
+    tangents of the fixed values, None for zeros.  dx (K, batch, nVar) / (batch, nVar) is the Jacobian-vector product dx/d[A | b] . dlod of the
+    rank-stable problems (lexls_lse_solve_tangent_device: one pass over the directions, no host copy); the flags are left in
+    `solver.differentiable`, where solve_lod's backward pass leaves them, and a problem with flag 0 has dx = 0.  `lod` is bound without a copy and
+    has to stay alive and unchanged while the solver keeps this factor."""
+    import torch
+    shape = (solver.batch, solver.nVar + 1, solver.cap)
+    if tuple(lod.shape) != shape or lod.dtype != torch.float64 or not lod.is_cuda or not lod.is_contiguous():
+        raise ValueError(f"jvp_lod: lod must be a contiguous float64 device tensor of shape {shape}")
+    dev = lod.device
+    solver.set_stream(torch.cuda.current_stream(dev).cuda_stream)
+    solver.setProblemDevice(lod.data_ptr())
+    solver.factorize_solve(keep_factor=True)
+    x = torch.as_tensor(_Span(solver.device_ptr("x"), (solver.batch, solver.nVar)), device=dev).clone()
+    dlod = dlod.contiguous()
+    dx = torch.empty(tuple(dlod.shape[:-2]) + (solver.nVar,), dtype=torch.float64, device=dev)
+    solver.differentiable = torch.empty((solver.batch,), dtype=torch.uint8, device=dev)
+    solver.solve_tangent_device(dlod, dx, None if dfixed is None else dfixed.contiguous(), solver.differentiable)
+    return x, dx
+
+
+def jvp_data(batch, data, ddata, var_index=None, active_guess=None, x0=None, out=None, **params):
+    """Forward mode of solve_data: (x, dx) for the LexLSI batch `batch` on the constraint data `data` (batch, per_data) and the directions `ddata`
+    (K, batch, per_data) — or (batch, per_data) for one —, float64 device tensors.  run_device on a copy of `data` (`params`: its keyword
+    parameters; `out`: a dict that receives its result), then lexls_lsi_batch_solve_tangent_device: dx (K, batch, nVar) / (batch, nVar) is the
+    Jacobian-vector product of the instances that ended PROBLEM_SOLVED on a rank-stable final problem, while their working sets hold; nothing
+    passes through host memory.  The flags are left in `batch.differentiable`, where solve_data's backward pass leaves them; an instance with
+    flag 0 has dx = 0."""
+    res = batch.run_device(data.detach().clone(), var_index=var_index, active_guess=active_guess, x0=x0, **params)
+    if out is not None:
+        out.update(res)
+    dx, batch.differentiable = batch.solve_tangent_device(ddata.contiguous())
+    return res["x"], dx
 
 
 def solve_bounds(lb, ub, batch, data, var_index=None, active_guess=None, x0=None, out=None, **params):
