@@ -373,6 +373,43 @@ int lexls_lse_solve_tangent(lexls_lse_t h, const double *h_dlod, const double *h
 int lexls_lse_get_tangent(lexls_lse_t h, double *h_dx, uint8_t *h_differentiable);
 int lexls_lse_solve_tangent_device(lexls_lse_t h, const double *d_dlod, const double *d_dfixed, uint32_t ntan, double *d_dx, uint8_t *d_differentiable);
 
+/* NEW RIGHT-HAND SIDES on the kept factor: the nrhs solutions x = M rhs + N fixed of every problem for the matrix that was factorized, without
+ * factorizing again.  factorize() chooses pivots and ranks from A alone, so x is exactly affine in b and in the fixed values; the same holds
+ * after a damped factorization of type 1, 3, 4, 5, 8 or 9 with constant factors (the regularization settings of the factorization stay).
+ * Column c of problem b is the x lexls_lse_factorize_solve returns for that problem with its right-hand-side column replaced by rhs[c, b] and
+ * its fixed values by fixed[c, b] — within the tolerance contract (no reference arithmetic exists for this path).  With the handle's own b and
+ * fixed = NULL the result equals lexls_lse_get_x within that tolerance.
+ * Layouts: rhs is nrhs x batch x cap, right-hand side c of problem b in LOD row order (the order of grad_rhs of lexls_lse_solve_adjoint); rows
+ * behind a problem's own dimensions are never read (a NaN there reaches nothing).  fixed is nrhs x batch x nVar, slot j < nfixed the j-th fixed
+ * value (as dfixed of lexls_lse_solve_tangent); NULL = the fixed values the handle holds; slots from nfixed on are never read.  x is nrhs x batch
+ * x nVar in the order of lexls_lse_get_x: fixed variables carry their value, variables beyond the total rank what lexls_lse_solve leaves there
+ * (zero).
+ * Served: every problem of every kept factor from every producer (rank-deficient problems and problems with every variable fixed too: there is
+ * no per-problem flag), plain and damped (types 1, 3, 4, 5, 8, 9), behind no switch.  No x of the current factor is needed: lexls_lse_factorize
+ * alone is enough.
+ * lexls_lse_solve_rhs copies the inputs in, launches and keeps the results in buffers of the handle (made for the largest nrhs so far);
+ * lexls_lse_get_solve_rhs copies them out (nrhs x batch x nVar for the nrhs of that call); both follow lexls_lse_set_deferred_sync, and
+ * lexls_lse_get_solve_rhs answers only while the results belong to the current factor.  lexls_lse_solve_rhs_device reads d_rhs and d_fixed
+ * (NULL: the handle's) and writes d_x in device memory: it only enqueues in the handle's stream and makes no host-synchronising call (its work
+ * buffer is allocated at the first call and whenever nrhs exceeds every earlier one).  What lexls_lse_get_x, _get_v, _get_lambda,
+ * _get_multipliers, _get_sensitivity and _get_adjoint* answer is not changed by these calls.
+ * Independence contract: for nrhs >= 2 the solution of a right-hand side does not depend on nrhs, on its position or on its company, bit for bit
+ * (one lane per right-hand side, no cross-lane sums); the same bits come back from run to run and from the host and the device form.  On a plain
+ * factor nrhs == 1 takes the single-vector kernel, whose sums are ordered differently: between nrhs == 1 and nrhs >= 2 the contract is the
+ * tolerance one.  No atomics.
+ * Errors, each returned before any device work and with every output left alone: LEXLS_ERR_INVALID for a null handle, a null rhs, a null d_x,
+ * nrhs == 0 or nrhs > 65535, or no kept factor; LEXLS_ERR_UNSUPPORTED after a factorization with regularization_type 2, 6 or 7 or with
+ * variable_regularization_factor != 0 (x is not an affine map of b there; the message names the condition).
+ * Kernel variant (lexls_lse_last_consumer_kernel): plain "solve_rhs<64,single>" (nrhs == 1), "solve_rhs<64,staged>", "solve_rhs<64,lds>" or
+ * "solve_rhs<64,work>"; damped "solve_rhs_reg<64,lds>", "solve_rhs_reg<64,hbm>" or "solve_rhs_reg<64,work>" — where the per-right-hand-side
+ * vectors and the problem's matrices live, decided from nVar, cap and nObj alone.
+ * Cost: a call costs about the same for 1 as for 64 right-hand sides (one wavefront per problem and tile of 64, lane = right-hand side).  On
+ * the IK shape it is cheaper than refactorizing [A | b_new] from about 12 right-hand sides on for a plain factor, and only from
+ * about 16 on for a damped one, where a single right-hand side costs as much as some 16 damped factorizations: below that, refactorize. */
+int lexls_lse_solve_rhs(lexls_lse_t h, const double *h_rhs, const double *h_fixed, uint32_t nrhs);
+int lexls_lse_get_solve_rhs(lexls_lse_t h, double *h_x);
+int lexls_lse_solve_rhs_device(lexls_lse_t h, const double *d_rhs, const double *d_fixed, uint32_t nrhs, double *d_x);
+
 /* ---- results (synchronise the stream, then D2H) ------------------------------------------------- */
 int lexls_lse_get_x(lexls_lse_t h, double *h_x);                    /* get_x()      lexlse.h:1587 */
 int lexls_lse_get_factor(lexls_lse_t h, double *h_lod);             /* get_lexqr()  lexlse.h:1626 */

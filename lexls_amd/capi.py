@@ -32,6 +32,7 @@ SYMBOLS = [
     "lexls_lse_solve_adjoint_multi", "lexls_lse_get_adjoint_multi", "lexls_lse_solve_adjoint_multi_device", "lexls_lse_set_adjoint_regularized_multi",
     "lexls_lse_solve_adjoint_matrix", "lexls_lse_get_adjoint_matrix", "lexls_lse_solve_adjoint_matrix_device",
     "lexls_lse_solve_tangent", "lexls_lse_get_tangent", "lexls_lse_solve_tangent_device",
+    "lexls_lse_solve_rhs", "lexls_lse_get_solve_rhs", "lexls_lse_solve_rhs_device",
     "lexls_lsi_batch_get_lambda", "lexls_lsi_batch_solve_ex2",
     "lexls_lse_sensitivity_collect", "lexls_lse_sensitivity_collect_resident", "lexls_lse_get_wrong_sign",
     "lexls_lsi_batch_get_cycling_counters", "lexls_lsi_batch_run_device", "lexls_lsi_batch_run_device_ex",
@@ -153,6 +154,12 @@ def lib() -> C.CDLL:
         _lib.lexls_lse_get_tangent.argtypes = [C.c_void_p, C.POINTER(C.c_double), C.POINTER(C.c_uint8)]
         _lib.lexls_lse_solve_tangent_device.restype = C.c_int
         _lib.lexls_lse_solve_tangent_device.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p]  # d_dlod, d_dfixed, ntan, d_dx, d_differentiable
+        _lib.lexls_lse_solve_rhs.restype = C.c_int
+        _lib.lexls_lse_solve_rhs.argtypes = [C.c_void_p, C.POINTER(C.c_double), C.POINTER(C.c_double), C.c_uint32]  # h_rhs, h_fixed, nrhs
+        _lib.lexls_lse_get_solve_rhs.restype = C.c_int
+        _lib.lexls_lse_get_solve_rhs.argtypes = [C.c_void_p, C.POINTER(C.c_double)]
+        _lib.lexls_lse_solve_rhs_device.restype = C.c_int
+        _lib.lexls_lse_solve_rhs_device.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p]  # d_rhs, d_fixed, nrhs, d_x
         _lib.lexls_internal_apply_solve_map.restype = C.c_int
         _lib.lexls_internal_apply_solve_map.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]  # d_rhs, d_out: device addresses
         _lib.lexls_lsi_batch_solve_adjoint_multi.restype = C.c_int

@@ -122,6 +122,14 @@ struct lexls_lse_s
     size_t tan_work_bytes = 0;           // bytes of d_tan_work
     bool tan_valid     = false;
     uint64_t tan_epoch = 0;
+    // lexls_lse_solve_rhs: the right-hand sides (nrhs x batch x cap), fixed values and solutions (nrhs x batch x nVar) of a host caller, made for the
+    // largest nrhs so far; d_srhs_work: the work buffer of the chain (launch_solve_rhs), likewise
+    double *d_srhs_rhs = nullptr, *d_srhs_fixed = nullptr, *d_srhs_x = nullptr;
+    void *d_srhs_work   = nullptr;
+    uint32_t srhs_room = 0, srhs_nrhs = 0; // right-hand sides the host buffers have room for; right-hand sides of the last host call
+    size_t srhs_work_bytes = 0;            // bytes of d_srhs_work
+    bool srhs_valid     = false;
+    uint64_t srhs_epoch = 0;
     // accuracy guard (lexls_lse_set_accuracy_guard): mode 0 off, 1 report, 2 report + re-solve; arrays allocated when first switched on
     int guard_mode           = 0;
     double guard_threshold   = 0.0;
@@ -318,7 +326,7 @@ extern "C"
                         h->d_large_state, h->d_large_ws, h->d_norms, h->d_cdata, h->d_reg_factor, h->d_reg_scratch, h->d_reg_mu, h->d_resume_level, h->d_resume_state,
                         h->d_guard_est, h->d_guard_status, h->d_guard_ind, h->d_mult, h->d_mult_scratch, h->d_wrong_sign, h->d_adj_g, h->d_adj_rhs, h->d_adj_fixed,
                         h->d_adj_work, h->d_adjm_G, h->d_adjm_rhs, h->d_adjm_fixed, h->d_adjm_work, h->d_adjrm_work, h->d_adjA_g, h->d_adjA_grad, h->d_adjA_flag, h->d_adjA_work,
-                        h->d_tan_dlod, h->d_tan_dfixed, h->d_tan_dx, h->d_tan_flag, h->d_tan_work};
+                        h->d_tan_dlod, h->d_tan_dfixed, h->d_tan_dx, h->d_tan_flag, h->d_tan_work, h->d_srhs_rhs, h->d_srhs_fixed, h->d_srhs_x, h->d_srhs_work};
         for (void *p : ptrs)
             if (p) (void)hipFree(p);
         if (h->h_dims_pinned) (void)hipHostFree(h->h_dims_pinned);
@@ -1355,6 +1363,89 @@ extern "C"
         HIP_TRY(hipSetDevice(h->device));
         if (h_dx) HIP_TRY(hipMemcpyAsync(h_dx, h->d_tan_dx, 8 * (size_t)h->batch * h->tan_ntan * h->nVar, hipMemcpyDeviceToHost, h->stream));
         if (h_differentiable) HIP_TRY(hipMemcpyAsync(h_differentiable, h->d_tan_flag, (size_t)h->batch, hipMemcpyDeviceToHost, h->stream));
+        if (!h->deferred_sync) HIP_TRY(hipStreamSynchronize(h->stream));
+        return LEXLS_OK;
+    }
+
+    /// what every form of lexls_lse_solve_rhs checks before any device work: the arguments, a kept factor — unregularized, or regularized with one
+    /// of the types whose damped solve is an affine map of the kept factor, the factors constant (behind no switch: a new entry)
+    static int need_solve_rhs(lexls_lse_t h, const char *who, const void *rhs, uint32_t nrhs)
+    {
+        CHECK_HANDLE(h);
+        if (!rhs) return fail(LEXLS_ERR_INVALID, std::string(who) + ": null rhs");
+        if (nrhs == 0) return fail(LEXLS_ERR_INVALID, std::string(who) + ": nrhs == 0");
+        if (nrhs > 65535u) return fail(LEXLS_ERR_INVALID, std::string(who) + ": nrhs > 65535 (split the right-hand sides over several calls)");
+        if (int rc = need_factor(h, who)) return rc;
+        if (h->reg_type == 0) return LEXLS_OK;
+        if (!adjoint_reg_serves(h->reg_type))
+            return fail(LEXLS_ERR_UNSUPPORTED, std::string(who) + ": regularization_type " + std::to_string(h->reg_type) +
+                                                   " is not an affine map of the right-hand side (the CG types 2 and 6 iterate from x = 0, type 7 is experimental); served: 1, 3, 4, 5, 8, 9");
+        if (h->reg_variable != 0.0)
+            return fail(LEXLS_ERR_UNSUPPORTED, std::string(who) + ": variable_regularization_factor != 0 under regularization_type " + std::to_string(h->reg_type) +
+                                                   " (the factor depends on the right-hand side: x is not an affine map of it)");
+        return LEXLS_OK;
+    }
+    /// every form of lexls_lse_solve_rhs on device memory: the checks, the work buffer, the launch
+    static int run_solve_rhs(lexls_lse_t h, const char *who, const double *d_rhs, const double *d_fixed, uint32_t nrhs, double *d_x)
+    {
+        if (int rc = need_solve_rhs(h, who, d_rhs, nrhs)) return rc;
+        if (!d_x) return fail(LEXLS_ERR_INVALID, std::string(who) + ": null d_x");
+        HIP_TRY(hipSetDevice(h->device));
+        const size_t need = solve_rhs_work_bytes(h->args(), nrhs);
+        if (need > h->srhs_work_bytes) // the work buffer holds the largest request so far (it grows with nrhs, and with the placement)
+        {
+            if (h->d_srhs_work) (void)hipFree(h->d_srhs_work); // (waits for whatever still reads it)
+            h->d_srhs_work = nullptr, h->srhs_work_bytes = 0;
+            HIP_TRY(hipMalloc(&h->d_srhs_work, need));
+            h->srhs_work_bytes = need;
+        }
+        HIP_TRY(launch_solve_rhs(h->args(), d_rhs, d_fixed, nrhs, d_x, h->d_srhs_work, h->stream, &h->last_consumer));
+        return LEXLS_OK;
+    }
+
+    int lexls_lse_solve_rhs(lexls_lse_t h, const double *h_rhs, const double *h_fixed, uint32_t nrhs)
+    {
+        const char *who = "lexls_lse_solve_rhs";
+        if (int rc = need_solve_rhs(h, who, h_rhs, nrhs)) return rc;
+        HIP_TRY(hipSetDevice(h->device));
+        const size_t B = h->batch, n = h->nVar, cap = h->cap;
+        if (nrhs > h->srhs_room) // the buffers hold the largest nrhs so far
+        {
+            h->srhs_valid = false;
+            h->srhs_room  = 0;
+            for (double **p : {&h->d_srhs_rhs, &h->d_srhs_fixed, &h->d_srhs_x})
+            {
+                if (*p) (void)hipFree(*p); // (waits for whatever still reads it)
+                *p = nullptr;
+            }
+            HIP_TRY(hipMalloc((void **)&h->d_srhs_rhs, 8 * B * nrhs * cap));
+            HIP_TRY(hipMalloc((void **)&h->d_srhs_fixed, 8 * B * nrhs * n));
+            HIP_TRY(hipMalloc((void **)&h->d_srhs_x, 8 * B * nrhs * n));
+            h->srhs_room = nrhs;
+        }
+        if (h_fixed) HIP_TRY(hipMemcpyAsync(h->d_srhs_fixed, h_fixed, 8 * B * nrhs * n, hipMemcpyHostToDevice, h->stream));
+        if (int rc = upload_adjoint_g(h, h->d_srhs_rhs, h_rhs, 8 * B * nrhs * cap)) return rc;
+        if (int rc = run_solve_rhs(h, who, h->d_srhs_rhs, h_fixed ? h->d_srhs_fixed : nullptr, nrhs, h->d_srhs_x)) return rc;
+        h->srhs_valid = true;
+        h->srhs_nrhs  = nrhs;
+        h->srhs_epoch = h->factor_epoch;
+        return LEXLS_OK;
+    }
+
+    int lexls_lse_solve_rhs_device(lexls_lse_t h, const double *d_rhs, const double *d_fixed, uint32_t nrhs, double *d_x)
+    {
+        return run_solve_rhs(h, "lexls_lse_solve_rhs_device", d_rhs, d_fixed, nrhs, d_x);
+    }
+
+    int lexls_lse_get_solve_rhs(lexls_lse_t h, double *h_x)
+    {
+        CHECK_HANDLE(h);
+        const std::string who = "lexls_lse_get_solve_rhs";
+        if (!h->srhs_valid) return fail(LEXLS_ERR_INVALID, who + ": call lexls_lse_solve_rhs first");
+        if (!h->factor_valid || h->srhs_epoch != h->factor_epoch)
+            return fail(LEXLS_ERR_INVALID, who + ": the problem or its factorization changed since lexls_lse_solve_rhs (call it again)");
+        HIP_TRY(hipSetDevice(h->device));
+        if (h_x) HIP_TRY(hipMemcpyAsync(h_x, h->d_srhs_x, 8 * (size_t)h->batch * h->srhs_nrhs * h->nVar, hipMemcpyDeviceToHost, h->stream));
         if (!h->deferred_sync) HIP_TRY(hipStreamSynchronize(h->stream));
         return LEXLS_OK;
     }

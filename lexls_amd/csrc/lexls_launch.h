@@ -42,8 +42,21 @@ namespace lexls
                                           const char **variant = nullptr, double *d_reg_work = nullptr, double *d_reg_multi_work = nullptr);
     /// d_out (batch x nVar, the order of x) = M d_rhs (batch x cap, LOD row order) for x = M b + N x_fixed of the kept factor, fixed values zero:
     /// the transpose of launch_solve_adjoint.  d_only_level (may be NULL): rows outside level d_only_level[b] of problem b count as zero.
-    /// One wavefront per problem, enqueued only.  Internal: the public header has no forward entry for new right-hand sides
+    /// One wavefront per problem, enqueued only.  Internal (the matrix gradient's u); the public forward entry is launch_solve_rhs
     hipError_t launch_apply_solve_map(const LseArgs &a, const double *d_rhs, const int32_t *d_only_level, double *d_out, hipStream_t s);
+    /// lexls_lse_solve_rhs: d_x (nrhs x batch x nVar, the order of x) = M d_rhs + N d_fixed for x = M b + N x_fixed of the kept factor, d_rhs
+    /// nrhs x batch x cap (LOD row order; rows behind a problem's own are not read), d_fixed nrhs x batch x nVar (slot j < nfixed; NULL: a.fixed_val
+    /// for every right-hand side).  Every problem is served (no rank-stability rule); a.x is not read.  Chains, in the stream: solve_rhs_front_kernel
+    /// (R = rhs - A_fixed fixed, the fixed slots), then
+    ///     a.reg_type == 0: apply_solve_map_kernel (nrhs == 1) or apply_solve_map_multi_kernel under tangent_map_placement (lexls_lds.h);
+    ///     a regularized factor of type 1, 3, 4, 5, 8 or 9 with a.reg_variable == 0 (anything else: hipErrorInvalidValue):
+    ///     apply_solve_map_reg_multi_kernel under solve_rhs_reg_form (every nrhs), a.reg_factor read at the time of this call.
+    /// Everything they write besides d_x goes to d_work (solve_rhs_work_bytes for this nrhs).  Enqueued only; no atomics
+    /// LEXLS_TANGENT_PLACEMENT = lds | work (plain) and LEXLS_SOLVE_RHS_REG_FORM = hbm | work (damped) in the environment name a later placement
+    /// of the list (measurements and tests; nothing moves a shape up)
+    size_t solve_rhs_work_bytes(const LseArgs &a, uint32_t nrhs);
+    hipError_t launch_solve_rhs(const LseArgs &a, const double *d_rhs, const double *d_fixed, uint32_t nrhs, double *d_x, void *d_work, hipStream_t s,
+                                const char **variant = nullptr);
     /// lexls_lse_solve_adjoint_matrix: d_grad_lod (batch x (nVar + 1) x cap, the layout of the problem data) = the gradient with respect to A and
     /// b for the cotangent d_g (batch x nVar), d_differentiable (batch bytes, may be NULL) = the rank-stability flags; a.x holds the solution of the
     /// kept factor.  Chains, in the stream: launch_solve_adjoint (y), the level search (k*), launch_sensitivity for level k* (lambda; its own rows

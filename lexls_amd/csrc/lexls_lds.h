@@ -317,5 +317,45 @@ namespace lexls
     /// tangent_rhs_kernel: x, the multipliers of level k*, the column sums w and the fixed slots' tangents
     inline size_t tangent_rhs_lds_bytes(uint32_t nVar, uint32_t cap) { return 8 * (3 * (size_t)nVar + cap); }
 
+    // ---- lexls_lse_solve_rhs (lse_adjoint.hip): new right-hand sides on the kept factor, lane = right-hand side ----
+    /// plain factors: apply_solve_map_multi_kernel under tangent_map_placement, named after this call
+    inline const char *solve_rhs_placement_name(TangentPlacement p)
+    {
+        return p == TangentPlacement::staged ? "solve_rhs<64,staged>" : p == TangentPlacement::lds ? "solve_rhs<64,lds>" : "solve_rhs<64,work>";
+    }
+    /// damped factors (apply_solve_map_reg_multi_kernel): the per-lane state t (cap), z, r, the right-hand side of D (nVar each), [index][lane];
+    /// the problem's matrices, shared by the lanes: the null-space basis and D (nVar x nVar each — the forward pass reads the basis as it
+    /// stands at a level's entry, so it keeps no snapshots)
+    constexpr size_t solve_rhs_reg_matrix_doubles(uint32_t nVar) { return 2 * (size_t)nVar * nVar; }
+    constexpr size_t solve_rhs_reg_state_doubles(uint32_t nVar, uint32_t cap, uint32_t ld) { return (size_t)ld * (3 * (size_t)nVar + cap); }
+    /// where they live: state (leading dimension 65) and matrices in LDS; the state in LDS, the matrices in a work buffer of the handle (read at
+    /// wavefront-uniform addresses); both in the work buffer (state: leading dimension 64, a lane's walk takes consecutive words) where one
+    /// workgroup's LDS does not hold the state.  The transpositions and positions (2 x nVar words) are in LDS under every form
+    enum class SolveRhsRegForm { lds, hbm, work };
+    inline size_t solve_rhs_reg_lds_bytes(uint32_t nVar, uint32_t cap, uint32_t /*nObj*/, SolveRhsRegForm f)
+    {
+        size_t b = 8 * (size_t)nVar;
+        if (f != SolveRhsRegForm::work) b += 8 * solve_rhs_reg_state_doubles(nVar, cap, kAdjointMultiLd);
+        if (f == SolveRhsRegForm::lds) b += 8 * solve_rhs_reg_matrix_doubles(nVar);
+        return (b + 15) & ~(size_t)15;
+    }
+    /// the placement rule of lexls_lse_solve_rhs on damped factors, decided from the shape alone (the launcher and tests/solve_rhs_fit_check.cpp
+    /// read it here)
+    inline SolveRhsRegForm solve_rhs_reg_form(uint32_t nVar, uint32_t cap, uint32_t nObj)
+    {
+        if (solve_rhs_reg_lds_bytes(nVar, cap, nObj, SolveRhsRegForm::lds) <= kMaxLdsBytes) return SolveRhsRegForm::lds;
+        if (solve_rhs_reg_lds_bytes(nVar, cap, nObj, SolveRhsRegForm::hbm) <= kMaxLdsBytes) return SolveRhsRegForm::hbm;
+        return SolveRhsRegForm::work;
+    }
+    /// doubles of the work buffer per (problem, tile of 64 right-hand sides): the matrices first, then (work form) the state
+    inline size_t solve_rhs_reg_work_doubles(uint32_t nVar, uint32_t cap, SolveRhsRegForm f)
+    {
+        return f == SolveRhsRegForm::lds ? 0 : solve_rhs_reg_matrix_doubles(nVar) + (f == SolveRhsRegForm::work ? solve_rhs_reg_state_doubles(nVar, cap, kTangentWorkLd) : 0);
+    }
+    inline const char *solve_rhs_reg_form_name(SolveRhsRegForm f)
+    {
+        return f == SolveRhsRegForm::lds ? "solve_rhs_reg<64,lds>" : f == SolveRhsRegForm::hbm ? "solve_rhs_reg<64,hbm>" : "solve_rhs_reg<64,work>";
+    }
+
     // ---- lqr_large (lqr_large.hip): lqr_large_plan.h ----
 } // namespace lexls

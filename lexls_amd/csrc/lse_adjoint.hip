@@ -437,8 +437,10 @@ namespace lexls
         /// (wave_sum).  rhs is batch x cap in LOD row order; only_level (may be NULL): rows outside level only_level[b] are read as zero (< 0: all
         /// of them).  out is batch x nVar in the order of x, zero on fixed and free variables.
         /// LDS (adjoint_lds_bytes): z = the solution in factor column order (nVar), t = the right-hand side (cap), the transpositions (nVar words).
-        template <int NT>
-        __global__ __launch_bounds__(NT) void apply_solve_map_kernel(LseArgs a, const double *__restrict__ rhs, const int32_t *__restrict__ only_level, double *__restrict__ out)
+        /// FIXED (lexls_lse_solve_rhs): a fixed variable takes its slot of fixed (batch x nVar, slot j < nfixed) instead of zero.
+        template <int NT, bool FIXED = false>
+        __global__ __launch_bounds__(NT) void apply_solve_map_kernel(LseArgs a, const double *__restrict__ rhs, const int32_t *__restrict__ only_level, double *__restrict__ out,
+                                                                     const double *__restrict__ fixed)
         {
             static_assert(NT == 64, "one wavefront per problem: the reductions are wavefront sums");
             constexpr uint32_t AU = 4;
@@ -568,7 +570,10 @@ namespace lexls
             for (uint32_t i = lane; i < n; i += NT)
             {
                 const uint32_t p       = position_after_transpositions(perm_l, T, i);
-                out[(size_t)b * n + i] = (p >= nf && p < T) ? z[p] : 0.0;
+                if constexpr (FIXED)
+                    out[(size_t)b * n + i] = p < nf ? fixed[(size_t)b * n + p] : (p < T ? z[p] : 0.0);
+                else
+                    out[(size_t)b * n + i] = (p >= nf && p < T) ? z[p] : 0.0;
             }
         }
 
@@ -1171,7 +1176,8 @@ namespace lexls
         /// rank-stability rule on the STORED ranks; a problem that fails it gets exact zeros in all its rows of dx.
         /// PLACE (TangentPlacement, lexls_lds.h): 0 the state z[nVar][LD], t[cap][LD] (LD = 65) and the staged factor in LDS, 1 the state in LDS
         /// and the factor read where it is kept, 2 the state in `work` (tangent_map_work_doubles per (problem, tile), LD = 64).  No atomics.
-        template <int NT, int PLACE>
+        /// TANGENT == false (lexls_lse_solve_rhs): x = M R + the fixed slots for EVERY problem — no rank-stability rule, no flags, Y and kstar unread.
+        template <int NT, int PLACE, bool TANGENT = true>
         __global__ __launch_bounds__(NT) void apply_solve_map_multi_kernel(LseArgs a, const double *__restrict__ R, const double *__restrict__ Y, const int32_t *__restrict__ kstar,
                                                                            const double *__restrict__ dfixed, uint32_t ntan, double *__restrict__ dx,
                                                                            uint8_t *__restrict__ differentiable, double *work)
@@ -1200,13 +1206,16 @@ namespace lexls
 
             // the rank-stability rule of adjoint_matrix_kernel (the STORED ranks and nfixed as stored; uniform)
             bool stable = true;
-            for (uint32_t k = 0; k < nObj; k++)
+            if constexpr (TANGENT)
             {
-                const uint32_t room = kf.fc[k] < n ? n - kf.fc[k] : 0;
-                if (kf.rk[k] != (dims[k] < room ? dims[k] : room)) stable = false;
+                for (uint32_t k = 0; k < nObj; k++)
+                {
+                    const uint32_t room = kf.fc[k] < n ? n - kf.fc[k] : 0;
+                    if (kf.rk[k] != (dims[k] < room ? dims[k] : room)) stable = false;
+                }
+                if ((a.nfixed ? a.nfixed[b] : 0u) >= n) stable = true;
+                if (tile == 0 && lane == 0 && differentiable) differentiable[b] = stable ? 1 : 0;
             }
-            if ((a.nfixed ? a.nfixed[b] : 0u) >= n) stable = true;
-            if (tile == 0 && lane == 0 && differentiable) differentiable[b] = stable ? 1 : 0;
             const size_t B = a.batch;
             if (!stable) // (uniform) no derivative: exact zeros
             {
@@ -1218,6 +1227,7 @@ namespace lexls
                 return;
             }
             uint32_t lo = 0, hi = 0; // the rows of level k*: Y counts there alone
+            if constexpr (TANGENT)
             {
                 const int32_t ks = kstar[b];
                 if (ks >= 0 && (uint32_t)ks < nObj)
@@ -1341,6 +1351,315 @@ namespace lexls
                 else if (p < T)
                     val = z[p * LD + c];
                 dx[row * n + i] = val;
+            }
+        }
+
+        // new right-hand sides on the kept factor (lexls_lse_solve_rhs): the kernel in front of the map, the map of a damped factor
+        /// Right-hand side c = blockIdx.y of problem b = blockIdx.x (rhs: nrhs x batch x cap, LOD row order; fixed: nrhs x batch x nVar, slot
+        /// j < nfixed, NULL: the values the handle holds, a.fixed_val): per row i of the problem's own
+        ///     R_i = rhs_i - sum_{j < nf} W(i, j) fixed_j
+        /// (the untouched columns j < nf of the factor are A_fixed: where tangent_rhs_kernel takes it), R batch x nrhs x cap with zeros behind the
+        /// problem's own rows, and Fx (nrhs x batch x nVar) = the fixed values in their slots, zero behind them: the layouts the map kernels read.
+        /// Rows behind the problem's own and slots behind nfixed are never loaded.  One wavefront, the LANES ALONG THE ROWS of one factor column;
+        /// R_i is the lane's own dfma chain over the fixed columns in ascending order.  LDS: the fixed values (nVar doubles).  No atomics.
+        template <int NT>
+        __global__ __launch_bounds__(NT) void solve_rhs_front_kernel(LseArgs a, const double *__restrict__ rhs, const double *__restrict__ fixed, uint32_t nrhs,
+                                                                     double *__restrict__ R, double *__restrict__ Fx)
+        {
+            constexpr uint32_t AU = 8;
+            extern __shared__ double smem[];
+            const uint32_t b = blockIdx.x, c = blockIdx.y, lane = threadIdx.x;
+            if (b >= a.batch || c >= nrhs) return; // (block-uniform)
+            const KeptFactor kf = kept_factor_of(a, b);
+            const uint32_t n = kf.n, cap = kf.cap, nf = kf.nf, M = kf.M;
+            const double *__restrict__ W = kf.W;
+            const size_t slot = (size_t)c * a.batch + b; // right-hand-side-major inputs
+            double *fx = smem;
+            for (uint32_t j = lane; j < n; j += NT)
+            {
+                const double v   = j < nf ? (fixed ? fixed[slot * n + j] : a.fixed_val[(size_t)b * n + j]) : 0.0;
+                fx[j]            = v;
+                Fx[slot * n + j] = v;
+            }
+            __syncthreads();
+            double *Rb = R + ((size_t)b * nrhs + c) * cap;
+            for (uint32_t i = lane; i < cap; i += NT)
+            {
+                double acc = 0.0;
+                if (i < M)
+                {
+                    acc = rhs[slot * cap + i];
+                    for (uint32_t j0 = 0; j0 < nf; j0 += AU)
+                    {
+                        double v[AU];
+#pragma unroll
+                        for (uint32_t u = 0; u < AU; u++) v[u] = j0 + u < nf ? W[i + (size_t)(j0 + u) * cap] : 0.0;
+#pragma unroll
+                        for (uint32_t u = 0; u < AU; u++)
+                            if (j0 + u < nf) acc = dfma(-v[u], fx[j0 + u], acc);
+                    }
+                }
+                Rb[i] = acc;
+            }
+        }
+
+        /// x = M_reg R + the fixed slots for up to 64 right-hand sides of one problem at once on a factor of a REGULARIZED factorize() of type 1,
+        /// 3, 4, 5, 8 or 9 with a constant factor per level: the transpose of solve_adjoint_reg_multi_kernel, with its mapping — one wavefront
+        /// per (problem, tile of 64 right-hand sides), LANE = RIGHT-HAND SIDE; lanes beyond nrhs compute on zeros and store nothing.  The forward
+        /// pass of the damped solve on the kept factor alone, levels ascending; per level of rank > 0:
+        ///     the level's reflectors on the lane's column t, first to last; y = t[F, F + rank)
+        ///     |f| >= 1e-15:  y' = W D^-1 (W^T y + mu U^T r)  (types 4, 5: no U; type 9: y' = f y), D = W^T W + mu U^T U + mu I, mu = f^2
+        ///     types 1, 3, 8:  s = R^-1 y',  r[0, m0) -= U_R s,  r[m0, m0 + rank) = -s   (r = the right-hand-side column of the basis)
+        ///     the Gauss step with y' on the rows of the later levels
+        /// then the block back-substitution and the permutation (apply_solve_map_multi_kernel's).  U = the rows [0, m0) of the null-space basis
+        /// NS above the level's columns AS IT STANDS — the levels are walked in the order in which the basis grows, so no snapshot is kept — and
+        /// the basis takes the level's step (solve_adjoint_reg_kernel's rebuild: A side only, the factor's final column order) behind the lanes' work.
+        ///   SHARED phases (work of the problem, lanes over entries): D and its LL^T (spd_factor<NT>), the step of NS.  EVERY TILE REPEATS THEM.
+        ///   PER LANE phases: everything on t, z, r and dv ([index][lane]): the lane's own serial dfma chains in a fixed order, no cross-lane
+        ///     sum — a right-hand side's bits do not depend on its lane, its tile or its neighbours.
+        /// Everything that steers the control flow belongs to the problem (wavefront-uniform).  The factor is read where it is kept.
+        /// PLACE (SolveRhsRegForm, lexls_lds.h): 0 state (LD = 65) and NS, D in LDS; 1 the state in LDS, NS and D in `work`; 2 both in `work`
+        /// (state LD = 64).  R: batch x nrhs x cap, fixed and x: nrhs x batch x nVar.  No atomics.
+        template <int NT, int PLACE>
+        __global__ __launch_bounds__(NT) void apply_solve_map_reg_multi_kernel(LseArgs a, const double *__restrict__ R, const double *__restrict__ fixed, uint32_t nrhs,
+                                                                               double *__restrict__ x, double *work)
+        {
+            static_assert(NT == 64, "one wavefront per (problem, tile): lane = right-hand side");
+            constexpr bool MAT_LDS = PLACE == 0, IN_WORK = PLACE == 2;
+            constexpr uint32_t LD = IN_WORK ? kTangentWorkLd : kAdjointMultiLd, AU = 4;
+            extern __shared__ double smem[];
+            const uint32_t b = blockIdx.x, tile = blockIdx.y, lane = threadIdx.x;
+            if (b >= a.batch || tile * 64u >= nrhs) return; // (block-uniform)
+            const uint32_t kt = nrhs - tile * 64u < 64u ? nrhs - tile * 64u : 64u; // live right-hand sides of this tile
+            const KeptFactor kf = kept_factor_of(a, b);
+            const uint32_t n = kf.n, cap = kf.cap, nObj = kf.nObj, nf = kf.nf, T = kf.T, M = kf.M;
+            const double *__restrict__ W = kf.W, *hh = kf.hh;
+            const uint32_t *dims = kf.dims;
+            const uint32_t type  = a.reg_type;
+            const bool accum = type == 1 || type == 3 || type == 8; // the types that accumulate NS (and read it)
+            const bool wideW = type == 1 || type == 5 || type == 8; // W = [R | T] (else R)
+            const double *fac = a.reg_factor + (size_t)b * nObj;
+            const size_t per_tile = MAT_LDS ? 0 : solve_rhs_reg_matrix_doubles(n) + (IN_WORK ? solve_rhs_reg_state_doubles(n, cap, LD) : 0);
+            double *wb       = MAT_LDS ? nullptr : work + ((size_t)b * gridDim.y + tile) * per_tile;
+            double *state    = IN_WORK ? wb + solve_rhs_reg_matrix_doubles(n) : smem;
+            double *t = state, *z = t + (size_t)cap * LD, *rv = z + (size_t)n * LD, *dv = rv + (size_t)n * LD;
+            uint32_t *perm_l = reinterpret_cast<uint32_t *>(IN_WORK ? smem : dv + (size_t)n * LD);
+            uint32_t *pos_l  = perm_l + n;
+            double *mat      = MAT_LDS ? reinterpret_cast<double *>(pos_l + n) : wb; // (2 n words: still 8-byte aligned)
+            double *NS = mat, *D = NS + (size_t)n * n;
+            auto ns = [&](uint32_t i, uint32_t j) __attribute__((always_inline)) -> double & { return NS[i + (size_t)j * n]; };
+            auto w  = [&](uint32_t i, uint32_t j) __attribute__((always_inline)) -> double { return W[i + (size_t)j * cap]; };
+
+            // ---- t = R for every right-hand side of the tile, the rest of the state zero ----
+            for (uint32_t i = lane; i < n; i += NT) perm_l[i] = a.perm[(size_t)b * n + i];
+            for (uint32_t i = lane; i < (3 * n + cap) * LD; i += NT) state[i] = 0.0; // (dead lanes, absent rows, unreached columns: zeros)
+            if (accum)
+                for (uint32_t i = lane; i < n * n; i += NT) NS[i] = 0.0;
+            __syncthreads();
+            for (uint32_t i = lane; i < n; i += NT) pos_l[i] = position_after_transpositions(perm_l, T, i);
+            {
+                const size_t off = ((size_t)b * nrhs + (size_t)tile * 64u) * cap; // kt rows of cap doubles, contiguous
+                for (uint32_t e = lane; e < kt * cap; e += NT)
+                {
+                    const uint32_t c = e / cap, r = e - c * cap;
+                    if (r < M) t[r * LD + c] = R[off + e];
+                }
+            }
+            __syncthreads();
+            double *tl = t + lane, *zl = z + lane, *rl = rv + lane, *dvl = dv + lane; // this lane's column of the state
+
+            // ---- the forward pass of factorize()'s right-hand-side updates, levels ascending ----
+            uint32_t F = 0;
+            for (uint32_t k = 0; k < nObj; k++)
+            {
+                const uint32_t dim = dims[k];
+                const auto [rank, Fc] = kf.level(k, dim);
+                if (rank > 0 && F + dim <= M)
+                {
+                    // PER LANE: the level's reflectors, first to last
+                    for (uint32_t j = 0; j < rank; j++)
+                    {
+                        const uint32_t rows = dim - j;
+                        const double tau    = hh[F + j];
+                        if (rows == 1 || tau == 0.0) continue; // (uniform)
+                        double *v = tl + (F + j) * LD;
+                        double s  = 0.0;
+                        for (uint32_t i = 1; i < rows; i++) s = dfma(w(F + j + i, Fc + j), v[i * LD], s);
+                        s += v[0];
+                        v[0] = dfma(-tau, s, v[0]);
+                        for (uint32_t i = 1; i < rows; i++) v[i * LD] = dfma(-(tau * w(F + j + i, Fc + j)), s, v[i * LD]);
+                    }
+                    const uint32_t m0 = Fc > nf ? Fc - nf : 0, N = wideW ? n - Fc : rank;
+                    double *yb        = tl + F * LD;
+                    const double f    = fac[k];
+                    if (!(fabs(f - 0.0) < 1e-15)) // the gate of regularize_level (uniform)
+                    {
+                        if (type == 9)
+                        {
+                            for (uint32_t i = 0; i < rank; i++) yb[i * LD] *= f;
+                        }
+                        else
+                        {
+                            const double mu = f * f;
+                            // SHARED: D = W^T W + mu U^T U + mu I (lower triangle; column c of W has min(c + 1, rank) rows) and its LL^T
+                            for (uint32_t e = lane; e < N * N; e += NT)
+                            {
+                                const uint32_t i = e % N, j = e / N;
+                                if (i < j) continue;
+                                const uint32_t len = j < rank ? j + 1 : rank;
+                                double acc = 0.0;
+                                for (uint32_t r = 0; r < len; r++) acc = dfma(w(F + r, Fc + i), w(F + r, Fc + j), acc);
+                                if (accum)
+                                {
+                                    double up = 0.0;
+                                    for (uint32_t s = 0; s < m0; s++) up = dfma(ns(s, Fc + i), ns(s, Fc + j), up);
+                                    acc = dfma(mu, up, acc);
+                                }
+                                D[i + (size_t)j * n] = i == j ? acc + mu : acc;
+                            }
+                            __syncthreads();
+                            spd_factor<NT>(D, n, N, lane); // (ends in a barrier: every lane reads all of L from here on)
+                            // PER LANE: dv = W^T y + mu U^T r, then L q = dv and L^T p = q in place, row by row against the shared factor
+                            for (uint32_t c = 0; c < N; c++)
+                            {
+                                const uint32_t len = c < rank ? c + 1 : rank;
+                                double acc = 0.0;
+                                for (uint32_t r = 0; r < len; r++) acc = dfma(w(F + r, Fc + c), yb[r * LD], acc);
+                                if (accum)
+                                {
+                                    double up = 0.0;
+                                    for (uint32_t s = 0; s < m0; s++) up = dfma(ns(s, Fc + c), rl[s * LD], up);
+                                    acc = dfma(mu, up, acc);
+                                }
+                                dvl[c * LD] = acc;
+                            }
+                            for (uint32_t i = 0; i < N; i++)
+                            {
+                                double acc = dvl[i * LD];
+                                for (uint32_t j = 0; j < i; j++) acc = dfma(-D[i + (size_t)j * n], dvl[j * LD], acc);
+                                dvl[i * LD] = acc / D[i + (size_t)i * n];
+                            }
+                            for (uint32_t i = N; i--;)
+                            {
+                                double acc = dvl[i * LD];
+                                for (uint32_t j = N - 1; j > i; j--) acc = dfma(-D[j + (size_t)i * n], dvl[j * LD], acc);
+                                dvl[i * LD] = acc / D[i + (size_t)i * n];
+                            }
+                            for (uint32_t i = 0; i < rank; i++) // y' = W p
+                            {
+                                double acc = 0.0;
+                                for (uint32_t c = i; c < N; c++) acc = dfma(w(F + i, Fc + c), dvl[c * LD], acc);
+                                yb[i * LD] = acc;
+                            }
+                        }
+                    }
+                    if (accum)
+                    {
+                        // PER LANE: s = R^-1 y' (into dv, last row first), r[0, m0) -= U_R s, r[m0, m0 + rank) = -s
+                        for (uint32_t j = rank; j--;)
+                        {
+                            double acc = yb[j * LD];
+                            for (uint32_t q = j + 1; q < rank; q++) acc = dfma(-w(F + j, Fc + q), dvl[q * LD], acc);
+                            dvl[j * LD] = acc / w(F + j, Fc + j);
+                        }
+                        for (uint32_t s = 0; s < m0; s++)
+                        {
+                            double acc = rl[s * LD];
+                            for (uint32_t j = 0; j < rank; j++) acc = dfma(-ns(s, Fc + j), dvl[j * LD], acc);
+                            rl[s * LD] = acc;
+                        }
+                        for (uint32_t j = 0; j < rank; j++) rl[(m0 + j) * LD] = -dvl[j * LD];
+                    }
+                    __syncthreads(); // (every lane has read L and U: the step of NS and the next damped level overwrite them)
+                    if (accum)
+                    {
+                        // SHARED: the level's step of NS (reg_accumulate_nullspace without the right-hand-side column)
+                        const uint32_t rows = m0 + rank, RC = n - Fc - rank;
+                        for (uint32_t e = lane; e < rank * rank; e += NT) ns(m0 + e % rank, Fc + e / rank) = (e % rank == e / rank) ? 1.0 : 0.0;
+                        __syncthreads();
+                        for (uint32_t i = lane; i < rows; i += NT) // Left <- Left R^-1, a row per lane
+                            for (uint32_t p = 0; p < rank; p++)
+                            {
+                                double sv = ns(i, Fc + p);
+                                for (uint32_t q = 0; q < p; q++) sv = dfma(-ns(i, Fc + q), w(F + q, Fc + p), sv);
+                                ns(i, Fc + p) = sv / w(F + p, Fc + p);
+                            }
+                        __syncthreads();
+                        for (uint32_t e = lane; e < rows * RC; e += NT) // Trailing -= Left T
+                        {
+                            const uint32_t i = e % rows, c = Fc + rank + e / rows;
+                            double tv = ns(i, c);
+                            for (uint32_t p = 0; p < rank; p++) tv = dfma(-ns(i, Fc + p), w(F + p, c), tv);
+                            ns(i, c) = tv;
+                        }
+                        __syncthreads();
+                    }
+                    const uint32_t Fn = F + dim;
+                    if (k + 1 < nObj && Fn < M)
+                    {
+                        // PER LANE: the Gauss step, AU rows of the later levels share one read of the level's top (ascending column order)
+                        for (uint32_t i0 = Fn; i0 < M; i0 += AU)
+                        {
+                            double acc[AU];
+#pragma unroll
+                            for (uint32_t u = 0; u < AU; u++) acc[u] = i0 + u < M ? tl[(i0 + u) * LD] : 0.0;
+                            for (uint32_t p = 0; p < rank; p++)
+                            {
+                                const double tp = tl[(F + p) * LD];
+#pragma unroll
+                                for (uint32_t u = 0; u < AU; u++)
+                                    if (i0 + u < M) acc[u] = dfma(-w(i0 + u, Fc + p), tp, acc[u]);
+                            }
+#pragma unroll
+                            for (uint32_t u = 0; u < AU; u++)
+                                if (i0 + u < M) tl[(i0 + u) * LD] = acc[u];
+                        }
+                    }
+                }
+                F += dim;
+            }
+
+            // ---- solve(), levels descending (apply_solve_map_multi_kernel's step (b)^T on the damped right-hand sides), per lane ----
+            uint32_t Fend = F;
+            for (uint32_t k = nObj; k--;)
+            {
+                const uint32_t dim = dims[k];
+                F                  = Fend - dim;
+                Fend               = F;
+                const auto [rank, Fc] = kf.level(k, dim);
+                if (rank == 0 || F + dim > M) continue;
+                for (uint32_t i0 = 0; i0 < rank; i0 += AU)
+                {
+                    double acc[AU];
+#pragma unroll
+                    for (uint32_t u = 0; u < AU; u++) acc[u] = i0 + u < rank ? tl[(F + i0 + u) * LD] : 0.0;
+                    for (uint32_t c = T; c > Fc + rank; c--)
+                    {
+                        const double zc = zl[(c - 1) * LD];
+#pragma unroll
+                        for (uint32_t u = 0; u < AU; u++)
+                            if (i0 + u < rank) acc[u] = dfma(-w(F + i0 + u, c - 1), zc, acc[u]);
+                    }
+#pragma unroll
+                    for (uint32_t u = 0; u < AU; u++)
+                        if (i0 + u < rank) tl[(F + i0 + u) * LD] = acc[u];
+                }
+                for (uint32_t j = rank; j--;)
+                {
+                    const double zc   = tl[(F + j) * LD] / w(F + j, Fc + j);
+                    zl[(Fc + j) * LD] = zc;
+                    for (uint32_t i = 0; i < j; i++) tl[(F + i) * LD] = dfma(-w(F + i, Fc + j), zc, tl[(F + i) * LD]);
+                }
+            }
+            __syncthreads();
+
+            // ---- x = P z, and the fixed slots ----
+            const size_t B = a.batch;
+            for (uint32_t e = lane; e < kt * n; e += NT)
+            {
+                const uint32_t c = e / n, i = e - c * n, p = pos_l[i];
+                const size_t row = ((size_t)tile * 64u + c) * B + b;
+                x[row * n + i]   = p < nf ? fixed[row * n + p] : (p < T ? z[p * LD + c] : 0.0);
             }
         }
     } // namespace
@@ -1473,7 +1792,7 @@ namespace lexls
         if (lds > kMaxLdsBytes) return hipErrorInvalidValue;
         hipError_t e = set_lds(apply_solve_map_kernel<64>, lds);
         if (e != hipSuccess) return e;
-        hipLaunchKernelGGL((apply_solve_map_kernel<64>), dim3(a.batch), dim3(64), lds, s, a, d_rhs, d_only_level, d_out);
+        hipLaunchKernelGGL((apply_solve_map_kernel<64>), dim3(a.batch), dim3(64), lds, s, a, d_rhs, d_only_level, d_out, nullptr);
         return hipGetLastError();
     }
 
@@ -1592,6 +1911,95 @@ namespace lexls
             break;
         }
         if (variant) *variant = tangent_placement_name(place);
+        return hipGetLastError();
+    }
+
+    /// the form launch_solve_rhs takes on a damped factor: solve_rhs_reg_form (lexls_lds.h), unless LEXLS_SOLVE_RHS_REG_FORM = hbm | work names a
+    /// later form of the list (measurements and tests: nothing moves a shape up)
+    static SolveRhsRegForm solve_rhs_reg_form_for(uint32_t nVar, uint32_t cap, uint32_t nObj)
+    {
+        SolveRhsRegForm f = solve_rhs_reg_form(nVar, cap, nObj);
+        if (const char *e = std::getenv("LEXLS_SOLVE_RHS_REG_FORM"))
+        {
+            if (!std::strcmp(e, "work")) f = SolveRhsRegForm::work;
+            if (!std::strcmp(e, "hbm") && f == SolveRhsRegForm::lds) f = SolveRhsRegForm::hbm;
+        }
+        return f;
+    }
+
+    /// R (batch x nrhs x cap) | the fixed slots (nrhs x batch x nVar) | what the map keeps per (problem, tile) outside LDS
+    size_t solve_rhs_work_bytes(const LseArgs &a, uint32_t nrhs)
+    {
+        const size_t B = a.batch, tiles = (nrhs + 63u) / 64u;
+        size_t bytes = 8 * B * nrhs * ((size_t)a.cap + a.nVar);
+        if (a.reg_type != 0)
+            bytes += 8 * B * tiles * solve_rhs_reg_work_doubles(a.nVar, a.cap, solve_rhs_reg_form_for(a.nVar, a.cap, a.nObj));
+        else if (nrhs > 1 && tangent_placement_for(a.nVar, a.cap, a.nObj) == TangentPlacement::work)
+            bytes += 8 * B * tiles * tangent_map_work_doubles(a.nVar, a.cap);
+        return bytes;
+    }
+
+    hipError_t launch_solve_rhs(const LseArgs &a, const double *d_rhs, const double *d_fixed, uint32_t nrhs, double *d_x, void *d_work, hipStream_t s, const char **variant)
+    {
+        const uint32_t tiles = (nrhs + 63u) / 64u;
+        if (!d_work || !d_rhs || !d_x || nrhs == 0 || nrhs > 65535u) return hipErrorInvalidValue;
+        const bool reg = a.reg_type != 0;
+        if (reg && (!adjoint_reg_serves(a.reg_type) || a.reg_variable != 0.0 || !a.reg_factor)) return hipErrorInvalidValue;
+        const size_t B = a.batch, n = a.nVar, cap = a.cap;
+        const TangentPlacement place = tangent_placement_for(a.nVar, a.cap, a.nObj);
+        const SolveRhsRegForm form   = solve_rhs_reg_form_for(a.nVar, a.cap, a.nObj);
+        const size_t lds_front = 8 * n;
+        const size_t lds = reg ? solve_rhs_reg_lds_bytes(a.nVar, a.cap, a.nObj, form) : nrhs == 1 ? adjoint_lds_bytes(a.nVar, a.cap) : tangent_map_lds_bytes(a.nVar, a.cap, a.nObj, place);
+        if (lds > kMaxLdsBytes || lds_front > kMaxLdsBytes) return hipErrorInvalidValue; // (before anything is enqueued)
+        double *w_r = static_cast<double *>(d_work), *w_f = w_r + B * nrhs * cap, *w_state = w_f + B * nrhs * n;
+        hipError_t e = set_lds(solve_rhs_front_kernel<64>, lds_front);
+        if (e != hipSuccess) return e;
+        // R = rhs - A_fixed fixed, and the fixed slots
+        hipLaunchKernelGGL((solve_rhs_front_kernel<64>), dim3(a.batch, nrhs), dim3(64), lds_front, s, a, d_rhs, d_fixed, nrhs, w_r, w_f);
+        if ((e = hipGetLastError()) != hipSuccess) return e;
+        if (reg)
+        {
+            switch (form)
+            {
+            case SolveRhsRegForm::lds:
+                if ((e = set_lds(apply_solve_map_reg_multi_kernel<64, 0>, lds)) != hipSuccess) return e;
+                hipLaunchKernelGGL((apply_solve_map_reg_multi_kernel<64, 0>), dim3(a.batch, tiles), dim3(64), lds, s, a, w_r, w_f, nrhs, d_x, nullptr);
+                break;
+            case SolveRhsRegForm::hbm:
+                if ((e = set_lds(apply_solve_map_reg_multi_kernel<64, 1>, lds)) != hipSuccess) return e;
+                hipLaunchKernelGGL((apply_solve_map_reg_multi_kernel<64, 1>), dim3(a.batch, tiles), dim3(64), lds, s, a, w_r, w_f, nrhs, d_x, w_state);
+                break;
+            case SolveRhsRegForm::work:
+                if ((e = set_lds(apply_solve_map_reg_multi_kernel<64, 2>, lds)) != hipSuccess) return e;
+                hipLaunchKernelGGL((apply_solve_map_reg_multi_kernel<64, 2>), dim3(a.batch, tiles), dim3(64), lds, s, a, w_r, w_f, nrhs, d_x, w_state);
+                break;
+            }
+            if (variant) *variant = solve_rhs_reg_form_name(form);
+            return hipGetLastError();
+        }
+        if (nrhs == 1) // the single-vector kernel (its sums are wavefront sums: against the lane-per-vector kernels the contract is the tolerance)
+        {
+            if ((e = set_lds(apply_solve_map_kernel<64, true>, lds)) != hipSuccess) return e;
+            hipLaunchKernelGGL((apply_solve_map_kernel<64, true>), dim3(a.batch), dim3(64), lds, s, a, w_r, nullptr, d_x, w_f);
+            if (variant) *variant = "solve_rhs<64,single>";
+            return hipGetLastError();
+        }
+        switch (place)
+        {
+        case TangentPlacement::staged:
+            if ((e = set_lds(apply_solve_map_multi_kernel<64, 0, false>, lds)) != hipSuccess) return e;
+            hipLaunchKernelGGL((apply_solve_map_multi_kernel<64, 0, false>), dim3(a.batch, tiles), dim3(64), lds, s, a, w_r, nullptr, nullptr, w_f, nrhs, d_x, nullptr, nullptr);
+            break;
+        case TangentPlacement::lds:
+            if ((e = set_lds(apply_solve_map_multi_kernel<64, 1, false>, lds)) != hipSuccess) return e;
+            hipLaunchKernelGGL((apply_solve_map_multi_kernel<64, 1, false>), dim3(a.batch, tiles), dim3(64), lds, s, a, w_r, nullptr, nullptr, w_f, nrhs, d_x, nullptr, nullptr);
+            break;
+        case TangentPlacement::work:
+            if ((e = set_lds(apply_solve_map_multi_kernel<64, 2, false>, lds)) != hipSuccess) return e;
+            hipLaunchKernelGGL((apply_solve_map_multi_kernel<64, 2, false>), dim3(a.batch, tiles), dim3(64), lds, s, a, w_r, nullptr, nullptr, w_f, nrhs, d_x, nullptr, w_state);
+            break;
+        }
+        if (variant) *variant = solve_rhs_placement_name(place);
         return hipGetLastError();
     }
 } // namespace lexls

@@ -451,6 +451,48 @@ class BatchedLexLSE:
                                                               address("dx", dx, lead + (self.batch, self.nVar)),
                                                               address("differentiable", differentiable, (self.batch,), "torch.uint8")))
 
+    # ---- new right-hand sides on the kept factor (every problem; plain and damped factors) ----------
+    def solve_rhs(self, rhs, fixed=None):
+        """lexls_lse_solve_rhs + lexls_lse_get_solve_rhs: rhs (K, batch, cap), K right-hand sides per problem in LOD row order (rows behind a
+        problem's own are not read), or (batch, cap) for one; fixed (K, batch, nVar) / (batch, nVar), slot j < nfixed the j-th fixed value
+        (None: the values the handle holds).  Returns x (K, batch, nVar) — (batch, nVar) for a 2-D rhs — in the order of get_x(): what
+        factorize_solve() gives for the same matrices under that right-hand side and those fixed values, within the tolerance contract.
+        Needs a kept factor only (factorize() is enough); after setRegularization: types 1, 3, 4, 5, 8, 9 with constant factors."""
+        rhs = np.ascontiguousarray(rhs, np.float64)
+        single = rhs.ndim == 2
+        if single:
+            rhs = rhs[None]
+        if rhs.ndim != 3 or rhs.shape[0] == 0 or rhs.shape[1:] != (self.batch, self.cap):
+            raise ValueError(f"rhs must have shape (K >= 1, {self.batch}, {self.cap}) or lack the leading axis, got {rhs.shape}")
+        K = rhs.shape[0]
+        if fixed is not None:
+            fixed = np.ascontiguousarray(fixed, np.float64).reshape((K, self.batch, self.nVar))
+        capi.check(capi.lib().lexls_lse_solve_rhs(self._h, _ptr(rhs, C.c_double), None if fixed is None else _ptr(fixed, C.c_double), K))
+        x = np.zeros((K, self.batch, self.nVar))
+        capi.check(capi.lib().lexls_lse_get_solve_rhs(self._h, _ptr(x, C.c_double)))
+        return x[0] if single else x
+
+    def solve_rhs_device(self, rhs, x, fixed=None):
+        """lexls_lse_solve_rhs_device: rhs (K, batch, cap), x (K, batch, nVar), fixed (K, batch, nVar; None: the handle's values) float64 in
+        device memory, contiguous torch tensors; a single right-hand side may lack the leading axis in all three.  Only enqueued in the
+        handle's stream (set_stream): the inputs have to be complete in stream order."""
+        if not hasattr(rhs, "data_ptr") or rhs.dim() not in (2, 3):
+            raise ValueError("solve_rhs_device: rhs must be a tensor of shape (K >= 1, batch, cap) or (batch, cap)")
+        lead = () if rhs.dim() == 2 else (int(rhs.shape[0]),)
+        K = lead[0] if lead else 1
+        if K == 0:
+            raise ValueError("solve_rhs_device: K == 0")
+
+        def address(name, t, shape):
+            if t is None:
+                return None
+            if not hasattr(t, "data_ptr") or str(t.dtype) != "torch.float64" or not t.is_contiguous() or tuple(t.shape) != shape:
+                raise ValueError(f"solve_rhs_device: {name} must be a contiguous float64 tensor of shape {shape}")
+            return C.c_void_p(t.data_ptr())
+        capi.check(capi.lib().lexls_lse_solve_rhs_device(self._h, address("rhs", rhs, lead + (self.batch, self.cap)),
+                                                          address("fixed", fixed, lead + (self.batch, self.nVar)), K,
+                                                          address("x", x, lead + (self.batch, self.nVar))))
+
     def jacobian_device(self):
         """(dx_db (batch, nVar, cap), dx_dfixed (batch, nVar, nVar)) of the kept factor as torch tensors on the handle's device: the identity
         cotangents are built there and go through solve_adjoint_multi_device, so dx_db[b, i, r] = d x_i / d b_r (LOD row order) and

@@ -248,6 +248,8 @@ def _solve_lod_class():
 def __getattr__(name):
     if name == "SolveRhs":
         return _solve_rhs_class()
+    if name == "SolveNewRhs":
+        return _solve_new_rhs_class()
     if name == "SolveLod":
         return _solve_lod_class()
     if name == "SolveBounds":
@@ -260,6 +262,69 @@ def __getattr__(name):
 def solve_rhs(rhs, lse, lod):
     """SolveRhs.apply(rhs, lse, lod)"""
     return _solve_rhs_class().apply(rhs, lse, lod)
+
+
+_SOLVE_NEW_RHS = None
+
+
+def _solve_new_rhs_class():
+    global _SOLVE_NEW_RHS
+    if _SOLVE_NEW_RHS is not None:
+        return _SOLVE_NEW_RHS
+    import torch
+
+    class SolveNewRhs(torch.autograd.Function):
+        """x = SolveNewRhs.apply(rhs, fixed, solver): rhs (K, batch, cap) float64 on the device, fixed (K, batch, nVar) or None (the values the
+        handle holds), solver a BatchedLexLSE that keeps a factor (plain, or damped with type 1, 3, 4, 5, 8 or 9 and constant factors).  Forward
+        is lexls_lse_solve_rhs_device — no factorization —, backward lexls_lse_solve_adjoint_multi_device on the same factor (after a damped
+        factorization the handle needs set_adjoint_regularized_multi()).  Gradients: rhs and fixed; first order only."""
+
+        @staticmethod
+        def forward(ctx, rhs, fixed, solver):
+            rhs = rhs.detach().contiguous()
+            x = torch.empty(tuple(rhs.shape[:-1]) + (solver.nVar,), dtype=torch.float64, device=rhs.device)
+            solver.set_stream(torch.cuda.current_stream(rhs.device).cuda_stream)
+            solver.solve_rhs_device(rhs, x, None if fixed is None else fixed.detach().contiguous())
+            ctx.solver, ctx.with_fixed = solver, fixed is not None
+            return x
+
+        @staticmethod
+        def backward(ctx, grad_x):
+            solver = ctx.solver
+            G = grad_x.reshape((-1, solver.batch, solver.nVar)).transpose(0, 1).contiguous()  # (batch, K, nVar): the adjoint's layout
+            K = G.shape[1]
+            grad_rhs = torch.empty((solver.batch, K, solver.cap), dtype=torch.float64, device=G.device)
+            grad_fixed = torch.empty((solver.batch, K, solver.nVar), dtype=torch.float64, device=G.device) if ctx.with_fixed else None
+            solver.set_stream(torch.cuda.current_stream(G.device).cuda_stream)
+            solver.solve_adjoint_multi_device(G, grad_rhs, grad_fixed)
+            lead = tuple(grad_x.shape[:-1])
+            return (grad_rhs.transpose(0, 1).reshape(lead + (solver.cap,)),
+                    grad_fixed.transpose(0, 1).reshape(lead + (solver.nVar,)) if ctx.with_fixed else None, None)
+
+    _SOLVE_NEW_RHS = SolveNewRhs
+    return SolveNewRhs
+
+
+def solve_new_rhs(solver, rhs, fixed=None):
+    """The solutions of K new right-hand sides `rhs` (K, batch, cap) — or (batch, cap) for one — and fixed values `fixed` (the same leading
+    axis, batch, nVar; None: the handle's) on the factor the BatchedLexLSE `solver` keeps, differentiable in both (SolveNewRhs).  Named
+    solve_new_rhs because solve_rhs(rhs, lse, lod), the factorizing operation, keeps its name and signature."""
+    return _solve_new_rhs_class().apply(rhs, fixed, solver)
+
+
+def jvp_rhs(solver, drhs, dfixed=None):
+    """Forward-mode derivative of the kept factor's solve with respect to b and the fixed values, valid on damped factors too: x = M b + N x_fixed
+    is linear, so its derivative along (drhs, dfixed) is THE SAME CALL with the constant part removed — lexls_lse_solve_rhs_device on drhs with
+    zeros passed for the fixed values where dfixed is None (None would mean the handle's own values, which are the constant part).  drhs
+    (K, batch, cap) / (batch, cap), dfixed the same leading axis x (batch, nVar); returns dx of drhs' leading shape x nVar."""
+    import torch
+    drhs = drhs.contiguous()
+    lead = tuple(drhs.shape[:-1])
+    dfixed = torch.zeros(lead + (solver.nVar,), dtype=torch.float64, device=drhs.device) if dfixed is None else dfixed.contiguous()
+    dx = torch.empty(lead + (solver.nVar,), dtype=torch.float64, device=drhs.device)
+    solver.set_stream(torch.cuda.current_stream(drhs.device).cuda_stream)
+    solver.solve_rhs_device(drhs, dx, dfixed)
+    return dx
 
 
 def solve_lod(solver, lod):
