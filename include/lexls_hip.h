@@ -961,8 +961,52 @@ int lexls_lsi_batch_solve_adjoint_matrix_device(lexls_lsi_batch_t b, const doubl
  * or ntan == 0; otherwise exactly those of lexls_lsi_batch_solve_adjoint_matrix. */
 int lexls_lsi_batch_solve_tangent(lexls_lsi_batch_t b, const double *h_ddata, uint32_t ntan, double *h_dx, uint8_t *h_differentiable);
 int lexls_lsi_batch_solve_tangent_device(lexls_lsi_batch_t b, const double *d_ddata, uint32_t ntan, double *d_dx, uint8_t *d_differentiable);
+/* NEW BOUNDS on the final working set: the finite-step counterpart of the gradient calls.  While an instance's working set W holds, its x is an
+ * affine map of the bounds; these calls apply that map to nrhs other bound sets per instance and say how far each answer leaves the region where
+ * W can be valid: lsi_bounds_gather_kernel turns the bound sets into right-hand sides of the final equality problems, lexls_lse_solve_rhs_device
+ * solves them on the kept final factor (nothing is factorized again), lsi_bounds_check_kernel writes x and measures every answer against ALL rows
+ * of the instance in the constraint data that stayed resident from the run.
+ * Layouts: lb and ub are nrhs x batch x sum(dims) each, in the user's constraint order (the row order of grad_lb / grad_ub of
+ * lexls_lsi_batch_solve_adjoint); x is nrhs x batch x nVar; violation is nrhs x batch (NULL: not wanted); valid is batch bytes (NULL: not wanted).
+ * Meaning: x[c, i] solves the final equality problem of instance i's last run — its final working set as lexls_lsi_batch_get_lambda forms it —
+ * with the bounds replaced by bound set c: an active general row of type CTR_ACTIVE_LB takes lb[c, i, row], CTR_ACTIVE_UB and CTR_ACTIVE_EQ take
+ * ub[c, i, row] (the bound the final problem reads, as in lexls_lsi_batch_solve_adjoint); an active simple bound fixes its variable at the bound
+ * chosen by the same rule.  Rows outside the working set contribute nothing to x.  With the run's own bounds x is the run's x within the
+ * tolerance contract of lexls_lse_solve_rhs.
+ * valid[i] = 1 when instance i ended PROBLEM_SOLVED, else 0 — and then all its rows of x and of violation are exact zeros (the convention of
+ * `differentiable`, without the rank-stability condition: lexls_lse_solve_rhs serves rank-deficient factors, and so does this call).  An empty
+ * working set gives x = 0, and its violation is measured against that x.
+ * violation[c, i] is the largest amount by which x[c, i] breaks a bound of bound set c, over all sum(dims) rows of all objectives, in or out of
+ * W: for a general row max(lb - a.x, a.x - ub, 0), for a simple bound the same with x[var] for a.x, and for every row, active ones included,
+ * max(lb - ub, 0).  a.x is one ordered fma chain over the variables 0 .. nVar - 1.  Rows absent under lexls_lsi_batch_set_instance_obj_dims are
+ * never read (a NaN in lb / ub there reaches nothing).
+ * WHAT THE VIOLATION DOES NOT SAY: violation <= tol is NECESSARY for the working set to remain the LexLSI answer under the new bounds, NOT
+ * SUFFICIENT.  The signs of the multipliers under the new bounds are not re-examined: an answer with violation 0 may still be one that the
+ * active-set method would leave by dropping a constraint.  A caller who needs certainty warm-starts lexls_lsi_batch_run_device from the working
+ * set.  Rows of lower priority that the lexicographic optimum itself leaves unmet count as well: the figure to compare with is the violation of
+ * the run's own bounds, not 0.  Thresholding is the caller's: the library fixes no tolerance.
+ * Mask rule: an instance that the instance mask skips keeps the bits of its rows of all three outputs (the host form copies the caller's arrays
+ * in first).  The final factor is shared with lexls_lsi_batch_get_lambda and every gradient call, in any call order
+ * (lexls_lsi_batch_final_factorizations still counts one formation per run and group); what those calls answer is unchanged by this one.
+ * Both forms are host-synchronous like lexls_lsi_batch_solve_tangent(_device); the _device form takes memory of the batch's device and nothing
+ * passes through host memory.
+ * Independence contract, inherited from lexls_lse_solve_rhs and kept by both kernels: for nrhs >= 2, x and violation of a bound set do not depend
+ * on nrhs, on its position or on its company, bit for bit (one lane per bound set, no cross-lane sums, no atomics); the same bits come back from
+ * run to run and from the host and the device form.  Between nrhs == 1 and nrhs >= 2 the contract is the tolerance one.
+ * Errors, each returned before any device work and with every output left alone: LEXLS_ERR_INVALID for a null handle, a null lb, ub or x,
+ * nrhs == 0 or nrhs > 65535, when the batch has no completed run, or when a lexls_lsi_batch_enqueue_device run is waiting for
+ * lexls_lsi_batch_finish; LEXLS_ERR_UNSUPPORTED after exactly the runs for which lexls_lsi_batch_solve_tangent answers it (cycling handling, a
+ * regularized run, more than 65535 constraints, constraint data not resident).
+ * Kernel variant (lexls_lsi_batch_last_consumer_kernel): "lsi_bounds_check<lds>" — the x vectors of a wavefront's 64 bound sets transposed in
+ * LDS — or "lsi_bounds_check<hbm>" — each lane reads its own where the solver left it —, decided from nVar alone (lds up to nVar 46).
+ * Cost: a call costs about the same for 1 as for 64 bound sets. */
+int lexls_lsi_batch_solve_bounds(lexls_lsi_batch_t b, const double *h_lb, const double *h_ub, uint32_t nrhs, double *h_x, double *h_violation, uint8_t *h_valid);
+int lexls_lsi_batch_solve_bounds_device(lexls_lsi_batch_t b, const double *d_lb, const double *d_ub, uint32_t nrhs, double *d_x, double *d_violation, uint8_t *d_valid);
+/* The kernel variant that served the LAST lexls_lsi_batch_solve_bounds(_device) call on this batch (a string the library owns); "" before the
+ * first such call or for a null handle. */
+const char *lexls_lsi_batch_last_consumer_kernel(lexls_lsi_batch_t b);
 /* How often, since the batch was created, the final equality problems of a group were formed and factorized: the stage lexls_lsi_batch_get_lambda,
- * lexls_lsi_batch_solve_adjoint(_multi) and lexls_lsi_batch_solve_adjoint_matrix share.  It grows by the number of groups at the first of these
+ * lexls_lsi_batch_solve_adjoint(_multi), lexls_lsi_batch_solve_adjoint_matrix, lexls_lsi_batch_solve_tangent and lexls_lsi_batch_solve_bounds share.  It grows by the number of groups at the first of these
  * calls behind a run and not at all at the later ones, in every call order.  Host bookkeeping only.  LEXLS_ERR_INVALID for a null argument. */
 int lexls_lsi_batch_final_factorizations(lexls_lsi_batch_t b, uint32_t *h_count);
 /* LexLSI::getCyclingCounter() (lexlsi.h, CyclingHandler::get_counter, cycling.h) of every instance of the LAST lexls_lsi_batch_run on this batch:

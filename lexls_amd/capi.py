@@ -44,6 +44,7 @@ SYMBOLS = [
     "lexls_lsi_batch_solve_adjoint_multi", "lexls_lsi_batch_solve_adjoint_multi_device", "lexls_lsi_batch_set_adjoint_regularized_multi",
     "lexls_lsi_batch_solve_adjoint_matrix", "lexls_lsi_batch_solve_adjoint_matrix_device", "lexls_lsi_batch_final_factorizations",
     "lexls_lsi_batch_solve_tangent", "lexls_lsi_batch_solve_tangent_device",
+    "lexls_lsi_batch_solve_bounds", "lexls_lsi_batch_solve_bounds_device", "lexls_lsi_batch_last_consumer_kernel",
     "lexls_lsi_batch_last_kernel",
 ]
 
@@ -172,6 +173,13 @@ def lib() -> C.CDLL:
         _lib.lexls_lsi_batch_solve_tangent.argtypes = [C.c_void_p, C.POINTER(C.c_double), C.c_uint32, C.POINTER(C.c_double), C.POINTER(C.c_uint8)]
         _lib.lexls_lsi_batch_solve_tangent_device.restype = C.c_int
         _lib.lexls_lsi_batch_solve_tangent_device.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p]  # d_ddata, ntan, d_dx, d_differentiable
+        _lib.lexls_lsi_batch_solve_bounds.restype = C.c_int
+        _lib.lexls_lsi_batch_solve_bounds.argtypes = [C.c_void_p, C.POINTER(C.c_double), C.POINTER(C.c_double), C.c_uint32, C.POINTER(C.c_double), C.POINTER(C.c_double),
+                                                      C.POINTER(C.c_uint8)]  # h_lb, h_ub, nrhs, h_x, h_violation, h_valid
+        _lib.lexls_lsi_batch_solve_bounds_device.restype = C.c_int
+        _lib.lexls_lsi_batch_solve_bounds_device.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p]  # d_lb, d_ub, nrhs, d_x, d_violation, d_valid
+        _lib.lexls_lsi_batch_last_consumer_kernel.restype = C.c_char_p
+        _lib.lexls_lsi_batch_last_consumer_kernel.argtypes = [C.c_void_p]
         _lib.lexls_lsi_batch_final_factorizations.restype = C.c_int
         _lib.lexls_lsi_batch_final_factorizations.argtypes = [C.c_void_p, C.POINTER(C.c_uint32)]
         _lib.lexls_lsi_batch_solve_adjoint_matrix_device.restype = C.c_int

@@ -357,5 +357,25 @@ namespace lexls
         return f == SolveRhsRegForm::lds ? "solve_rhs_reg<64,lds>" : f == SolveRhsRegForm::hbm ? "solve_rhs_reg<64,hbm>" : "solve_rhs_reg<64,work>";
     }
 
+    // ---- lexls_lsi_batch_solve_bounds (lsi_final.h): lsi_bounds_check_kernel, lane = bound set ----
+    /// rows of one chunk of the caller's lb / ub that a wavefront turns from "along the rows" (how they are loaded) to "along the bound sets" (how
+    /// the lanes read them), through LDS: two tiles of kBoundsCheckRows x kAdjointMultiLd doubles under either placement
+    constexpr uint32_t kBoundsCheckRows = 16;
+    /// what one workgroup may ask for: a quarter of a CU's LDS, so that four wavefronts of it share a CU whatever nVar is
+    constexpr size_t kBoundsCheckLdsBudget = 40 * 1024;
+    /// where the x vectors of a wavefront's 64 bound sets live: transposed in LDS ([variable][lane], odd leading dimension 65), or where
+    /// lexls_lse_solve_rhs_device left them (global memory, each lane its own vector)
+    enum class BoundsCheckPlacement { lds, hbm };
+    inline size_t bounds_check_lds_bytes(uint32_t nVar, BoundsCheckPlacement p)
+    {
+        return 8 * (size_t)kAdjointMultiLd * (2 * (size_t)kBoundsCheckRows + (p == BoundsCheckPlacement::lds ? (size_t)nVar : 0));
+    }
+    /// the placement rule of lexls_lsi_batch_solve_bounds, decided from nVar alone (the launcher and tests/lsi_bounds_fit_check.cpp read it here)
+    inline BoundsCheckPlacement bounds_check_placement(uint32_t nVar)
+    {
+        return bounds_check_lds_bytes(nVar, BoundsCheckPlacement::lds) <= kBoundsCheckLdsBudget ? BoundsCheckPlacement::lds : BoundsCheckPlacement::hbm;
+    }
+    inline const char *bounds_check_placement_name(BoundsCheckPlacement p) { return p == BoundsCheckPlacement::lds ? "lsi_bounds_check<lds>" : "lsi_bounds_check<hbm>"; }
+
     // ---- lqr_large (lqr_large.hip): lqr_large_plan.h ----
 } // namespace lexls

@@ -916,7 +916,7 @@ struct lexls_lsi_batch_s : LsiBatchShape
         take_instance_regularization(r);
         run_phase1_on_device(r, &dev);
         finish_working_set_log();
-        fin.set_rule(fin.lam_rc_after(par), lam_msg_after_device_run(par), par, true);
+        fin.set_rule(fin.lam_rc_after(par), lam_msg_after_device_run(par), par, true, d_obj_dims != NULL);
     }
 
     /// the runs lexls_lsi_batch_enqueue_device serves: those of run_device that the persistent launch takes, decided on numbers (every group's handle:
@@ -1073,7 +1073,7 @@ struct lexls_lsi_batch_s : LsiBatchShape
         }
         last_stats[0] = rounds_fs, last_stats[1] = rounds_sens, last_stats[2] = rounds_step, last_stats[3] = (int32_t)nGroups;
         wlog_valid = wlog != nullptr;
-        fin.set_rule(fin.lam_rc_after(par), lam_msg_after_device_run(par), par, true);
+        fin.set_rule(fin.lam_rc_after(par), lam_msg_after_device_run(par), par, true, d_obj_dims != NULL);
         return LEXLS_OK;
     }
 

@@ -2,6 +2,7 @@
 // them with the factor kept, and the calls that work on that factor — getLambda and the gradients of the solutions (bounds, many cotangents, matrices).
 #pragma once
 #include <array>
+#include <atomic>
 #include <memory>
 #include "lsi_batch_ctx.h"
 #include "lsi_worker_pool.h"
@@ -233,6 +234,144 @@ namespace
         const bool live = diff && na != 0 && dx_lse;
         for (uint32_t i = tid; i < n; i += 64) dx[((size_t)c * batch + lo + b) * n + i] = live ? dx_lse[((size_t)c * B + b) * n + i] : 0.0;
     }
+
+    /// lexls_lsi_batch_solve_bounds for a whole group, first half: the transpose of lsi_adjoint_scatter_multi_kernel, with the routes of
+    /// lsi_tangent_gather_kernel (map, types, meta).  Bound set c = blockIdx.y of instance b = blockIdx.x (the caller's lb / ub: nrhs x batch x total,
+    /// user's constraint order; the group's instances start at instance lo of the batch) becomes the right-hand side of its final equality problem in
+    /// the layouts lexls_lse_solve_rhs_device reads: rhs (nrhs x B x cap, LOD row order) and fixed (nrhs x B x n, fixVariable order).  Row r of the
+    /// final problem (the nf fixed variables first, then the LOD rows) is user row pos[r] and takes lb (CTR_ACTIVE_LB) or ub (CTR_ACTIVE_UB,
+    /// CTR_ACTIVE_EQ) of that row — the bound form_final_problem posts.  Rows outside the working set (and so every row absent under
+    /// lexls_lsi_batch_set_instance_obj_dims) are never read; rows behind the problem's own and slots behind nf are not written (the equality solver
+    /// does not read them).  The threads run along the rows of the final problem: consecutive threads store at consecutive addresses, the reads of
+    /// lb / ub are the scattered side.  No atomics.  A masked instance is skipped.
+    __global__ __launch_bounds__(64) void lsi_bounds_gather_kernel(const double *__restrict__ lbq, const double *__restrict__ ubq, const uint32_t *__restrict__ map,
+                                                                   const uint8_t *__restrict__ types, const int32_t *__restrict__ meta, uint32_t B, uint32_t batch, uint32_t lo,
+                                                                   uint32_t nrhs, uint32_t total, uint32_t n, uint32_t cap, double *__restrict__ rhs, double *__restrict__ fixed,
+                                                                   const uint8_t *mask)
+    {
+        const uint32_t b = blockIdx.x, c = blockIdx.y, tid = threadIdx.x;
+        if (b >= B || c >= nrhs || lsi_mask_byte(mask, b) == 0) return; // (block-uniform)
+        const uint32_t nf   = min((uint32_t)max(meta[2 * b + 1], 0), n);
+        const uint32_t na   = min(map[b], min(total, nf + cap));
+        const uint32_t *pos = map + B + (size_t)b * total;
+        const uint8_t *ty   = types + (size_t)b * total;
+        const size_t in     = ((size_t)c * batch + lo + b) * total;
+        double *r_b = rhs + ((size_t)c * B + b) * cap, *f_b = fixed + ((size_t)c * B + b) * n;
+        for (uint32_t r = tid; r < na; r += 64)
+        {
+            const uint32_t u = pos[r], t = ty[r];
+            double val = 0.0;
+            if (u < total)
+            {
+                if (t == CTR_ACTIVE_LB)
+                    val = lbq[in + u];
+                else if (t == CTR_ACTIVE_UB || t == CTR_ACTIVE_EQ)
+                    val = ubq[in + u];
+            }
+            if (r < nf)
+                f_b[r] = val;
+            else
+                r_b[r - nf] = val;
+        }
+    }
+
+    /// lexls_lsi_batch_solve_bounds for a whole group, second half: x into the caller's layout, the valid flags and the violations.  One wavefront per
+    /// instance b = blockIdx.x and tile of 64 bound sets (blockIdx.y), lane = bound set c.
+    /// x_lse (nrhs x B x n, lexls_lse_solve_rhs_device's; NULL: the group factorized nothing) goes to x (nrhs x batch x n) — exact zeros where the
+    /// instance did not end PROBLEM_SOLVED, and for an empty working set —, the lanes running along the tile's vectors one after the other: runs of n
+    /// consecutive addresses on both sides.
+    /// XLDS: on the way the tile's vectors are transposed into LDS ([variable][lane], leading dimension 65); else each lane reads its own from x.
+    /// violation[c, b] = the largest of max(lb - a.x, a.x - ub, lb - ub, 0) over all present rows of all objectives (a simple bound: x[var] for a.x),
+    /// 0 where the instance did not end PROBLEM_SOLVED.  The rows of the resident constraint data (cdata: B x per_data, lexls_lsi_batch_run_device's
+    /// layout; shape: the objectives' {dim, general, offset, first row}; var: B x dims[0] variable indices; counts: B x counts_ld present rows per
+    /// objective, or NULL) are read once per tile at wavefront-uniform addresses; every lane accumulates a.x as its own ordered fma chain over
+    /// j = 0 .. n - 1 (no cross-lane sums: a bound set's bits do not depend on nrhs, its position or its company).  lb / ub of kBoundsCheckRows rows
+    /// at a time are loaded along the rows (consecutive lanes at consecutive addresses) and turned to [row][lane] in LDS.  Rows at and behind an
+    /// instance's count are never read.  valid[b] = status PROBLEM_SOLVED, written by tile 0.  A masked instance keeps the bits of all three outputs.
+    template <bool XLDS>
+    __global__ __launch_bounds__(64) void lsi_bounds_check_kernel(const double *__restrict__ x_lse, const double *__restrict__ lbq, const double *__restrict__ ubq,
+                                                                  const double *__restrict__ cdata, const uint32_t *__restrict__ var, const uint32_t *__restrict__ counts,
+                                                                  uint32_t counts_ld, const uint32_t *__restrict__ map, const int32_t *__restrict__ meta,
+                                                                  const uint32_t *__restrict__ shape, uint32_t B, uint32_t batch, uint32_t lo, uint32_t nrhs, uint32_t nObj,
+                                                                  uint32_t total, uint32_t n, uint32_t cap, size_t per_data, double *__restrict__ x, double *__restrict__ violation,
+                                                                  uint8_t *__restrict__ valid, const uint8_t *mask)
+    {
+        extern __shared__ double s_bounds[];
+        constexpr uint32_t LD = lexls::kAdjointMultiLd, ROWS = lexls::kBoundsCheckRows;
+        double *s_lb = s_bounds, *s_ub = s_bounds + ROWS * LD, *s_x = s_bounds + 2 * ROWS * LD; // (s_x: XLDS only)
+        const uint32_t b = blockIdx.x, c0 = blockIdx.y * 64u, lane = threadIdx.x;
+        if (b >= B || c0 >= nrhs || lsi_mask_byte(mask, b) == 0) return; // (block-uniform)
+        const uint32_t nc   = min(64u, nrhs - c0), c = c0 + lane;
+        const bool solved   = meta[2 * b] == (int32_t)PROBLEM_SOLVED;
+        const uint32_t nf   = min((uint32_t)max(meta[2 * b + 1], 0), n);
+        const uint32_t na   = min(map[b], min(total, nf + cap));
+        const bool live     = solved && na != 0 && x_lse; // (else x = 0: an empty working set, or no answer)
+        if (blockIdx.y == 0 && lane == 0 && valid) valid[b] = solved ? 1 : 0;
+        // ---- x: the tile's nc vectors, element e of vector cc at a time ----
+        for (uint32_t e = lane; e < nc * n; e += 64)
+        {
+            const uint32_t cc = e / n, j = e - cc * n;
+            const double val  = live ? x_lse[((size_t)(c0 + cc) * B + b) * n + j] : 0.0;
+            x[((size_t)(c0 + cc) * batch + lo + b) * n + j] = val;
+            if (XLDS) s_x[j * LD + cc] = val;
+        }
+        if (!solved) // (block-uniform: exact zeros)
+        {
+            if (violation && lane < nc) violation[(size_t)c * batch + lo + b] = 0.0;
+            return;
+        }
+        if (!violation) return;
+        __syncthreads();
+        const double *xg    = live ? x_lse + ((size_t)min(c, nrhs - 1) * B + b) * n : NULL; // (!XLDS: the lane's own vector)
+        const double *d_b   = cdata + (size_t)b * per_data;
+        const size_t in     = ((size_t)c0 * batch + lo + b) * total;         // bound set c0's rows of this instance
+        const size_t in_ld  = (size_t)batch * total;                          // from one bound set to the next
+        double viol = 0.0;
+        for (uint32_t o = 0; o < nObj; o++)
+        {
+            const uint32_t dim = shape[4 * o], general = shape[4 * o + 1], first = shape[4 * o + 3];
+            const uint32_t cnt = counts && o < counts_ld ? min(counts[(size_t)b * counts_ld + o], dim) : dim;
+            const double *blk  = d_b + shape[4 * o + 2];
+            for (uint32_t i0 = 0; i0 < cnt; i0 += ROWS)
+            {
+                const uint32_t len = min(ROWS, cnt - i0);
+                // the chunk's bounds: ROWS consecutive rows of 64 / ROWS bound sets per pass
+                for (uint32_t e = lane; e < ROWS * 64u; e += 64)
+                {
+                    const uint32_t cc = e / ROWS, rr = e % ROWS;
+                    if (cc < nc && rr < len)
+                    {
+                        const size_t at = in + (size_t)cc * in_ld + first + i0 + rr;
+                        s_lb[rr * LD + cc] = lbq[at];
+                        s_ub[rr * LD + cc] = ubq[at];
+                    }
+                }
+                __syncthreads();
+                for (uint32_t rr = 0; rr < len; rr++)
+                {
+                    const uint32_t i = i0 + rr;
+                    double ax = 0.0;
+                    if (general)
+                    {
+                        if (live)
+                            for (uint32_t j = 0; j < n; j++) ax = fma(blk[(size_t)j * dim + i], XLDS ? s_x[j * LD + lane] : xg[j], ax);
+                    }
+                    else if (live && o == 0)
+                    {
+                        const uint32_t vi = var ? var[(size_t)b * dim + i] : n; // (objective 0 alone holds simple bounds: dim = dims[0])
+                        if (vi < n) ax = XLDS ? s_x[vi * LD + lane] : xg[vi];
+                    }
+                    if (lane < nc)
+                    {
+                        const double l = s_lb[rr * LD + lane], u = s_ub[rr * LD + lane];
+                        viol = fmax(viol, fmax(fmax(l - ax, ax - u), l - u));
+                    }
+                }
+                __syncthreads();
+            }
+        }
+        if (lane < nc) violation[(size_t)c * batch + lo + b] = viol;
+    }
 } // namespace
 
 /// What the after-run stage reads of the batch object (lexls_lsi_batch_s derives from it): its shape, the groups with their equality-solver handles and
@@ -275,6 +414,7 @@ struct LsiFinal
     std::vector<uint32_t> ws_fixvar;  // batch x dims[0] (simple bounds only): variables of the active simple bounds, working-set order
     std::vector<double> ws_fixval;    // batch x dims[0]: the bound each one is fixed at
     std::vector<int32_t> ws_status;   // batch: every instance's TerminationStatus of the last run, from its host object or the resident slab
+    std::vector<uint32_t> ws_var;     // batch x dims[0] (simple bounds only): the variable of every simple bound, where the run had them on the host (keep_fixed)
     struct Bufs                       // per group, made at the first get_lambda
     {
         Pinned<uint32_t> map;         // [nact (B) | pos (B x total)]
@@ -300,10 +440,16 @@ struct LsiFinal
         // nVar) and their tangents (t_room x B x nVar), made for the largest ntan so far
         double *d_tan_dlod = NULL, *d_tan_dfixed = NULL, *d_tan_dx = NULL;
         uint32_t t_room = 0;
+        // lexls_lsi_batch_solve_bounds (ensure_bounds_bufs): the right-hand sides of the final equality problems (b_room x B x cap and b_room x B x nVar)
+        // and their solutions (b_room x B x nVar), made for the largest nrhs so far; the variable indices of objective 0's simple bounds (B x dims[0])
+        // after a run that had them on the host (a device run left them in the group's d_rvar)
+        double *d_bnd_rhs = NULL, *d_bnd_fixed = NULL, *d_bnd_x = NULL;
+        uint32_t *d_bnd_var = NULL;
+        uint32_t b_room = 0;
         ~Bufs()
         {
             void *dev[] = {d_map, d_out, d_types, d_meta, d_g, d_grad_rhs, d_grad_fixed, d_grad_lb, d_grad_ub, d_grad_lod, d_mat_out, d_lse_flag, d_mat_flag, d_shape,
-                           d_tan_dlod, d_tan_dfixed, d_tan_dx};
+                           d_tan_dlod, d_tan_dfixed, d_tan_dx, d_bnd_rhs, d_bnd_fixed, d_bnd_x, d_bnd_var};
             for (void *q : dev)
                 if (q) (void)hipFree(q);
         }
@@ -315,6 +461,13 @@ struct LsiFinal
     // final_solved — the handle holds the x of that factor (solve_adjoint_matrix's chain needs it; the stage factorizes only).
     // Every new run drops all four (forget).
     std::vector<char> final_kept, final_any, adj_uploaded, final_solved;
+    // lexls_lsi_batch_solve_bounds reads every row of every instance, not the working set alone: var_on_host — the last run's variable indices are in
+    // ws_var (else, a device run: in the groups' d_rvar), var_uploaded — and on the device for this run; run_counts — the run had per-instance row
+    // counts (lexls_lsi_batch_set_instance_obj_dims: the groups' d_inst_dims hold the copies it made); bounds_kernel — the variant of the last call
+    std::atomic<bool> var_on_host{false};
+    std::vector<char> var_uploaded;
+    bool run_counts = false;
+    const char *bounds_kernel = "";
     // lexls_lsi_batch_set_adjoint_regularized: solve_adjoint answers after a resident regularized run of type 1, 3, 4, 5, 8, 9 (constant factors); off:
     // the rules of get_lambda, as before.  adj_rc / adj_msg: what solve_adjoint answers after the last run (set_rule); final_reg: the run was such
     // a run, and ensure_final_factor leaves the run's regularization on the groups' handles
@@ -345,8 +498,10 @@ struct LsiFinal
         {
             ws_fixvar.assign((size_t)s.batch * s.dims[0], 0);
             ws_fixval.assign((size_t)s.batch * s.dims[0], 0.0);
+            ws_var.assign((size_t)s.batch * s.dims[0], 0);
         }
         final_kept.assign(s.nGroups, 0), final_any.assign(s.nGroups, 0), adj_uploaded.assign(s.nGroups, 0), final_solved.assign(s.nGroups, 0);
+        var_uploaded.assign(s.nGroups, 0);
     }
 
     // ---- what the run calls ----
@@ -358,6 +513,8 @@ struct LsiFinal
         std::fill(final_any.begin(), final_any.end(), 0);
         std::fill(adj_uploaded.begin(), adj_uploaded.end(), 0);
         std::fill(final_solved.begin(), final_solved.end(), 0);
+        std::fill(var_uploaded.begin(), var_uploaded.end(), 0);
+        var_on_host = false, run_counts = false;
     }
     /// a run starts
     void begin_run(const ParametersLexLSI &par)
@@ -410,6 +567,11 @@ struct LsiFinal
     {
         if (!s.off) return;
         const uint32_t d0 = s.dims[0], na = ws_na[(size_t)b * s.nObj];
+        if (var_index)
+        {
+            std::copy(var_index, var_index + d0, ws_var.begin() + (size_t)b * d0);
+            var_on_host = true;
+        }
         for (uint32_t a = 0; a < na && a < d0; a++)
         {
             const uint32_t c = ws_idx[(size_t)b * s.total + a];
@@ -433,9 +595,10 @@ struct LsiFinal
     /// lexls_lsi_batch_solve_adjoint(_device) and lexls_lsi_batch_solve_adjoint_multi(_device) answer — the same, except that a regularized run is
     /// served when the batch asked for it for that call (adj_regularized, adj_regularized_multi), the run was resident (its regularization is on the
     /// groups' handles), its type is one of the six whose damped solve is affine in the bounds and its variable factor is zero
-    void set_rule(int rc, const char *msg, const ParametersLexLSI &par, bool resident)
+    /// counts: the run read per-instance row counts (a device run under lexls_lsi_batch_set_instance_obj_dims)
+    void set_rule(int rc, const char *msg, const ParametersLexLSI &par, bool resident, bool counts = false)
     {
-        lam_rc = rc, lam_msg = msg;
+        lam_rc = rc, lam_msg = msg, run_counts = counts;
         adj_rc = adjm_rc = lam_rc, adj_msg = adjm_msg = lam_msg, final_reg = false;
         const int t = static_cast<int>(par.regularization_type);
         if (lam_rc != LEXLS_ERR_UNSUPPORTED || t == 0 || par.cycling_handling_enabled || !s.gather || s.total > 65535) return;
@@ -947,6 +1110,144 @@ struct LsiFinal
         {
             bool ok = hipMemcpy(dx, d_dx, out_bytes, hipMemcpyDeviceToHost) == hipSuccess;
             if (ok && differentiable) ok = hipMemcpy(differentiable, d_flag, s.batch, hipMemcpyDeviceToHost) == hipSuccess;
+            if (!ok) throw Exception(who + ": hipMemcpy failed (results)");
+        }
+        return LEXLS_OK;
+    }
+
+    // ---- new bounds on the final working set ----
+    /// the groups' buffers of solve_bounds (behind those of solve_adjoint_matrix: the routes and the shape), for the largest nrhs so far
+    void ensure_bounds_bufs(uint32_t nrhs)
+    {
+        ensure_adjoint_matrix_bufs(false);
+        for (uint32_t g = 0; g < s.nGroups; g++)
+        {
+            Bufs &lb        = *bufs[g];
+            const size_t Bg = s.grp[g]->B, cap = s.grp[g]->cap, rows = Bg * nrhs;
+            if (s.off && !lb.d_bnd_var && hipMalloc((void **)&lb.d_bnd_var, 4 * Bg * (s.dims[0] ? s.dims[0] : 1)) != hipSuccess)
+                throw Exception("hipMalloc failed (lexls_lsi_batch_solve_bounds)");
+            if (nrhs <= lb.b_room) continue;
+            lb.b_room = 0;
+            for (double **q : {&lb.d_bnd_rhs, &lb.d_bnd_fixed, &lb.d_bnd_x})
+            {
+                if (*q) (void)hipFree(*q);
+                *q = NULL;
+            }
+            if (hipMalloc((void **)&lb.d_bnd_rhs, 8 * rows * (cap ? cap : 1)) != hipSuccess || hipMalloc((void **)&lb.d_bnd_fixed, 8 * rows * s.nVar) != hipSuccess ||
+                hipMalloc((void **)&lb.d_bnd_x, 8 * rows * s.nVar) != hipSuccess)
+                throw Exception("hipMalloc failed (lexls_lsi_batch_solve_bounds)");
+            lb.b_room = nrhs;
+        }
+    }
+    /// a host caller's bounds, solutions, violations and flags on the device (made for the largest request so far)
+    struct BoundsStage
+    {
+        double *d_lb = NULL, *d_ub = NULL, *d_x = NULL, *d_viol = NULL;
+        uint8_t *d_valid = NULL;
+        uint32_t room = 0;
+        void release()
+        {
+            for (void *q : {(void *)d_lb, (void *)d_ub, (void *)d_x, (void *)d_viol})
+                if (q) (void)hipFree(q);
+            d_lb = d_ub = d_x = d_viol = NULL, room = 0;
+        }
+        ~BoundsStage()
+        {
+            release();
+            if (d_valid) (void)hipFree(d_valid);
+        }
+    } bnd_stage;
+
+    /// lexls_lsi_batch_solve_bounds(_device): x of the last run's final working sets under nrhs other bound sets per instance (lb, ub: nrhs x batch x
+    /// total, user's constraint order; x: nrhs x batch x nVar), how far each answer breaks the instance's bounds (violation: nrhs x batch, may be NULL)
+    /// and which instances ended PROBLEM_SOLVED (valid: batch bytes, may be NULL).  Per group, in its stream: the final factor (ensure_final_factor,
+    /// shared with get_lambda and every gradient call: nothing is factorized twice) and the routes once per run, lsi_bounds_gather_kernel,
+    /// lexls_lse_solve_rhs_device, lsi_bounds_check_kernel on the constraint data resident in the group's handle.  The rule of the last run is
+    /// solve_tangent's (lam_rc).  The host form stages in buffers of the batch (under a mask the caller's outputs travel there first).  Waits for the
+    /// groups' streams before it returns.
+    int solve_bounds(const double *lbq, const double *ubq, uint32_t nrhs, double *x, double *violation, uint8_t *valid, bool on_device)
+    {
+        const std::string who = on_device ? "lexls_lsi_batch_solve_bounds_device" : "lexls_lsi_batch_solve_bounds";
+        if (lam_rc < 0) throw Exception(who + ": no completed lexls_lsi_batch_run on this batch");
+        if (lam_rc != LEXLS_OK)
+        {
+            lexls_internal_set_error(lam_msg.c_str());
+            return lam_rc;
+        }
+        if (hipSetDevice(s.device) != hipSuccess) throw Exception(who + ": hipSetDevice failed");
+        ensure_bounds_bufs(nrhs);
+        const size_t total = s.total, in_bytes = 8 * (size_t)nrhs * s.batch * total, x_bytes = 8 * (size_t)nrhs * s.batch * s.nVar, v_bytes = 8 * (size_t)nrhs * s.batch;
+        const double *d_lbq = lbq, *d_ubq = ubq;
+        double *d_x = x, *d_viol = violation;
+        uint8_t *d_valid = valid;
+        if (!on_device)
+        {
+            BoundsStage &st = bnd_stage;
+            if (nrhs > st.room)
+            {
+                st.release();
+                if (hipMalloc((void **)&st.d_lb, in_bytes ? in_bytes : 8) != hipSuccess || hipMalloc((void **)&st.d_ub, in_bytes ? in_bytes : 8) != hipSuccess ||
+                    hipMalloc((void **)&st.d_x, x_bytes) != hipSuccess || hipMalloc((void **)&st.d_viol, v_bytes) != hipSuccess)
+                    throw Exception(who + ": hipMalloc failed");
+                st.room = nrhs;
+            }
+            if (!st.d_valid && hipMalloc((void **)&st.d_valid, s.batch) != hipSuccess) throw Exception(who + ": hipMalloc failed");
+            bool ok = hipMemcpy(st.d_lb, lbq, in_bytes, hipMemcpyHostToDevice) == hipSuccess && hipMemcpy(st.d_ub, ubq, in_bytes, hipMemcpyHostToDevice) == hipSuccess;
+            if (ok && s.d_mask) ok = hipMemcpy(st.d_x, x, x_bytes, hipMemcpyHostToDevice) == hipSuccess; // a skipped instance keeps the caller's bits
+            if (ok && s.d_mask && violation) ok = hipMemcpy(st.d_viol, violation, v_bytes, hipMemcpyHostToDevice) == hipSuccess;
+            if (ok && s.d_mask && valid) ok = hipMemcpy(st.d_valid, valid, s.batch, hipMemcpyHostToDevice) == hipSuccess;
+            if (!ok) throw Exception(who + ": hipMemcpy failed (bounds)");
+            d_lbq = st.d_lb, d_ubq = st.d_ub, d_x = st.d_x, d_viol = violation ? st.d_viol : NULL, d_valid = valid ? st.d_valid : NULL;
+        }
+        const lexls::BoundsCheckPlacement place = lexls::bounds_check_placement(s.nVar);
+        const size_t lds                        = lexls::bounds_check_lds_bytes(s.nVar, place);
+        const uint32_t tiles                    = (nrhs + 63) / 64;
+        for (uint32_t g = 0; g < s.nGroups; g++)
+        {
+            BatchCtx &ctx         = *s.grp[g];
+            Bufs &lb              = *bufs[g];
+            const bool any_active = ensure_final_factor(g, []() {});
+            upload_adjoint_routes(g, who.c_str());
+            const uint32_t *d_var = NULL; // the variables of objective 0's simple bounds, every row's
+            if (s.off)
+            {
+                if (var_on_host && !var_uploaded[g])
+                {
+                    if (hipMemcpyAsync(lb.d_bnd_var, ws_var.data() + (size_t)s.lo[g] * s.dims[0], 4 * (size_t)ctx.B * s.dims[0], hipMemcpyHostToDevice, ctx.stream) != hipSuccess)
+                        throw Exception(who + ": hipMemcpyAsync failed (variable indices)");
+                    var_uploaded[g] = 1;
+                }
+                d_var = var_on_host ? lb.d_bnd_var : ctx.d_rvar;
+            }
+            // nobody has an active constraint: nothing was factorized, every x is zero
+            if (any_active)
+            {
+                hipLaunchKernelGGL(lsi_bounds_gather_kernel, dim3(ctx.B, nrhs), dim3(64), 0, ctx.stream, d_lbq, d_ubq, lb.d_map, lb.d_types, lb.d_meta, ctx.B, s.batch, s.lo[g], nrhs,
+                                   (uint32_t)total, s.nVar, ctx.cap, lb.d_bnd_rhs, lb.d_bnd_fixed, s.group_mask(g));
+                if (hipGetLastError() != hipSuccess) throw Exception("lsi_bounds_gather_kernel launch failed");
+                hip_check(lexls_lse_solve_rhs_device(ctx.h, lb.d_bnd_rhs, lb.d_bnd_fixed, nrhs, lb.d_bnd_x));
+            }
+            const double *x_lse    = any_active ? lb.d_bnd_x : (const double *)NULL;
+            const uint32_t *counts = run_counts ? ctx.d_inst_dims : (const uint32_t *)NULL;
+            uint8_t *flag          = d_valid ? d_valid + s.lo[g] : (uint8_t *)NULL;
+            if (place == lexls::BoundsCheckPlacement::lds)
+                hipLaunchKernelGGL(lsi_bounds_check_kernel<true>, dim3(ctx.B, tiles), dim3(64), lds, ctx.stream, x_lse, d_lbq, d_ubq, lexls_internal_cdata(ctx.h), d_var, counts,
+                                   (uint32_t)RESIDENT_DIMS_STRIDE, lb.d_map, lb.d_meta, lb.d_shape, ctx.B, s.batch, s.lo[g], nrhs, s.nObj, (uint32_t)total, s.nVar, ctx.cap, s.per_data, d_x,
+                                   d_viol, flag, s.group_mask(g));
+            else
+                hipLaunchKernelGGL(lsi_bounds_check_kernel<false>, dim3(ctx.B, tiles), dim3(64), lds, ctx.stream, x_lse, d_lbq, d_ubq, lexls_internal_cdata(ctx.h), d_var, counts,
+                                   (uint32_t)RESIDENT_DIMS_STRIDE, lb.d_map, lb.d_meta, lb.d_shape, ctx.B, s.batch, s.lo[g], nrhs, s.nObj, (uint32_t)total, s.nVar, ctx.cap, s.per_data, d_x,
+                                   d_viol, flag, s.group_mask(g));
+            if (hipGetLastError() != hipSuccess) throw Exception("lsi_bounds_check_kernel launch failed");
+        }
+        bounds_kernel = lexls::bounds_check_placement_name(place);
+        for (uint32_t g = 0; g < s.nGroups; g++)
+            if (hipStreamSynchronize(s.grp[g]->stream) != hipSuccess) throw Exception(who + ": stream synchronisation failed");
+        if (!on_device)
+        {
+            bool ok = hipMemcpy(x, d_x, x_bytes, hipMemcpyDeviceToHost) == hipSuccess;
+            if (ok && violation) ok = hipMemcpy(violation, d_viol, v_bytes, hipMemcpyDeviceToHost) == hipSuccess;
+            if (ok && valid) ok = hipMemcpy(valid, d_valid, s.batch, hipMemcpyDeviceToHost) == hipSuccess;
             if (!ok) throw Exception(who + ": hipMemcpy failed (results)");
         }
         return LEXLS_OK;

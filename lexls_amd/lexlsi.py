@@ -767,6 +767,60 @@ class LsiBatch:
         capi.check(capi.lib().lexls_lsi_batch_solve_tangent_device(self._h, d_in, K, d_out, d_flag))
         return dx, differentiable
 
+    def solve_bounds(self, lb, ub):
+        """lexls_lsi_batch_solve_bounds: `lb`, `ub` (K, batch, total), K other bound sets per instance in the constraint order of `active` / `v`, or
+        (batch, total) for one.  Returns (x, violation, valid): x (K, batch, nvar) — (batch, nvar) for a single set given without the leading
+        axis —, the solution of every instance's final working set of the last run with its bounds replaced; violation (K, batch) / (batch,), the
+        largest amount by which that x breaks a bound of the set, over all rows of all objectives; valid (batch,) uint8, 1 where the instance
+        ended PROBLEM_SOLVED, else 0 with exact zeros in its rows of x and violation.  A small violation is necessary for the working set to
+        remain the answer under the new bounds, not sufficient: the multipliers' signs are not re-examined.  Nothing is factorized again.
+        Raises after the runs solve_tangent() raises after."""
+        lb, ub = np.ascontiguousarray(lb, np.float64), np.ascontiguousarray(ub, np.float64)
+        single = lb.ndim == 2
+        if single:
+            lb, ub = lb[None], (ub[None] if ub.ndim == 2 else ub)
+        if lb.ndim != 3 or lb.shape[0] == 0 or lb.shape[1:] != (self.batch, self.total) or ub.shape != lb.shape:
+            raise ValueError(f"solve_bounds: lb / ub have shapes {lb.shape} / {ub.shape}, (K >= 1, {self.batch}, {self.total}) expected for both")
+        K = lb.shape[0]
+        x, violation, valid = np.zeros((K, self.batch, self.nvar)), np.zeros((K, self.batch)), np.zeros(self.batch, np.uint8)
+        capi.check(capi.lib().lexls_lsi_batch_solve_bounds(self._h, _p(lb, C.c_double), _p(ub, C.c_double), K, _p(x, C.c_double), _p(violation, C.c_double),
+                                                           _p(valid, C.c_uint8)))
+        return (x[0], violation[0], valid) if single else (x, violation, valid)
+
+    def solve_bounds_device(self, lb, ub, x=None, violation=None, valid=None):
+        """lexls_lsi_batch_solve_bounds_device: solve_bounds() on torch tensors of the batch's device — `lb`, `ub` float64 (K, batch, total) or
+        (batch, total), `x` float64 with the same leading axis and (batch, nvar), `violation` float64 of the leading axis and (batch,), `valid`
+        uint8 (batch,), contiguous; an output that is not given is allocated (zeroed).  Returns (x, violation, valid).  Nothing of them passes
+        through host memory.  Under an instance mask the rows and the flag of a skipped instance keep their bits: pass the tensors that hold
+        them.  The call waits for the device."""
+        import torch
+        if not hasattr(lb, "dim") or lb.dim() not in (2, 3) or not hasattr(ub, "dim") or ub.dim() != lb.dim():
+            raise ValueError("solve_bounds_device: lb and ub must be tensors of shape (K >= 1, batch, total) or (batch, total)")
+        lead = () if lb.dim() == 2 else (int(lb.shape[0]),)
+        K = lead[0] if lead else 1
+        if K == 0:
+            raise ValueError("solve_bounds_device: K == 0")
+        d_lb = self._device_array("lb", lb, torch.float64, lead + (self.batch, self.total), optional=False)
+        d_ub = self._device_array("ub", ub, torch.float64, lead + (self.batch, self.total), optional=False)
+        dev = torch.device("cuda", self.device)
+        if x is None:
+            x = torch.zeros(lead + (self.batch, self.nvar), dtype=torch.float64, device=dev)
+        if violation is None:
+            violation = torch.zeros(lead + (self.batch,), dtype=torch.float64, device=dev)
+        if valid is None:
+            valid = torch.zeros((self.batch,), dtype=torch.uint8, device=dev)
+        d_x = self._device_array("x", x, torch.float64, lead + (self.batch, self.nvar), optional=False)
+        d_viol = self._device_array("violation", violation, torch.float64, lead + (self.batch,), optional=False)
+        d_valid = self._device_array("valid", valid, torch.uint8, (self.batch,), optional=False)
+        torch.cuda.synchronize(dev)  # the bounds (and the zeroed outputs) are complete before the library's own streams read and write them
+        capi.check(capi.lib().lexls_lsi_batch_solve_bounds_device(self._h, d_lb, d_ub, K, d_x, d_viol, d_valid))
+        return x, violation, valid
+
+    def last_consumer_kernel(self) -> str:
+        """the kernel variant of the last solve_bounds() / solve_bounds_device() call (lexls_lsi_batch_last_consumer_kernel):
+        "lsi_bounds_check<lds>" or "lsi_bounds_check<hbm>"; "" before the first such call"""
+        return capi.lib().lexls_lsi_batch_last_consumer_kernel(self._h).decode()
+
     def split_grad_data(self, row):
         """one instance's row of grad_data (or of the data itself) as the list of per-objective dict(A=, lb=, ub=) (simple bounds: lb, ub): the
         inverse of flatten(), by unflatten()"""

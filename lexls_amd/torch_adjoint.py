@@ -27,6 +27,10 @@ per-instance flag and zeros for the others.
 (lexls_lse_solve_tangent_device), where ``SolveLod`` would need nVar backward passes for the same quantity; ``jvp_data`` is the same for
 ``SolveData`` (lexls_lsi_batch_solve_tangent_device).
 
+``solve_new_bounds`` is the finite-step counterpart of ``SolveBounds`` on a batch that has run: x of the final working sets under K other bound
+sets per instance (lexls_lsi_batch_solve_bounds_device, nothing is factorized again) with the violation of each answer, differentiable in the
+bounds through one lexls_lsi_batch_solve_adjoint_multi_device call.
+
 torch is imported when the operation is first used, not with the package.
 """
 from __future__ import annotations
@@ -256,6 +260,8 @@ def __getattr__(name):
         return _solve_bounds_class()
     if name == "SolveData":
         return _solve_data_class()
+    if name == "SolveNewBounds":
+        return _solve_new_bounds_class()
     raise AttributeError(f"module {__name__!r} has no attribute {name!r}")
 
 
@@ -374,6 +380,50 @@ def solve_bounds(lb, ub, batch, data, var_index=None, active_guess=None, x0=None
     """SolveBounds.apply(lb, ub, batch, data, var_index, active_guess, x0, params, out): the solutions of a LexLSI batch, differentiable in the
     bounds.  `params`: the keyword parameters of LsiBatch.run_device; `out`: a dict that receives its result ("x", "info", "active", "v")."""
     return _solve_bounds_class().apply(lb, ub, batch, data, var_index, active_guess, x0, params, out)
+
+
+_SOLVE_NEW_BOUNDS = None
+
+
+def _solve_new_bounds_class():
+    global _SOLVE_NEW_BOUNDS
+    if _SOLVE_NEW_BOUNDS is not None:
+        return _SOLVE_NEW_BOUNDS
+    import torch
+
+    class SolveNewBounds(torch.autograd.Function):
+        """x, violation = SolveNewBounds.apply(lb, ub, batch): lb, ub (K, batch, total) float64 on the device, batch an LsiBatch whose last run
+        lexls_lsi_batch_solve_bounds serves.  Forward is lexls_lsi_batch_solve_bounds_device — no factorization, no active-set iteration —; the
+        flags are left in `batch.valid`.  The map from the bounds to x is the run's own while the working set holds, so backward is one
+        lexls_lsi_batch_solve_adjoint_multi_device call with K cotangents per instance.  Gradients: lb and ub, of x only — violation is not
+        differentiable; first order only."""
+
+        @staticmethod
+        def forward(ctx, lb, ub, batch):
+            x, violation, batch.valid = batch.solve_bounds_device(lb.detach().contiguous(), ub.detach().contiguous())
+            ctx.batch = batch
+            ctx.mark_non_differentiable(violation)
+            return x, violation
+
+        @staticmethod
+        def backward(ctx, grad_x, _grad_violation):
+            batch = ctx.batch
+            G = grad_x.reshape((-1, batch.batch, batch.nvar)).transpose(0, 1).contiguous()  # (batch, K, nvar): the adjoint's layout
+            grad_lb, grad_ub = batch.solve_adjoint_multi_device(G)
+            shape = tuple(grad_x.shape[:-1]) + (batch.total,)
+            return grad_lb.transpose(0, 1).reshape(shape), grad_ub.transpose(0, 1).reshape(shape), None
+
+    _SOLVE_NEW_BOUNDS = SolveNewBounds
+    return SolveNewBounds
+
+
+def solve_new_bounds(batch, lb, ub):
+    """(x, violation) of the LsiBatch `batch`'s last run under K other bound sets per instance: `lb`, `ub` (K, batch, total) — or (batch, total) for
+    one — float64 device tensors in the constraint order of `active`; x has their leading shape x nvar, violation their leading shape
+    (LsiBatch.solve_bounds_device; the flags are left in `batch.valid`).  x is differentiable in lb and ub (SolveNewBounds); violation is not.  A
+    small violation is necessary for the working set to remain the answer, not sufficient.  Named solve_new_bounds because
+    solve_bounds(lb, ub, batch, data, ...), the operation that runs the active-set method, keeps its name and signature."""
+    return _solve_new_bounds_class().apply(lb, ub, batch)
 
 
 def solve_data(batch, data, var_index=None, active_guess=None, x0=None, out=None, **params):
