@@ -1,8 +1,11 @@
 // The adjoint family of the LexLSE solve: gradients of x = M b + N x_fixed of a KEPT factor with respect to the right-hand sides and the fixed
 // values (one cotangent or many per pass), the solve map M on a new right-hand side, and the gradient with respect to the matrix that chains
-// them, each on ONE view of the factor and ONE rule for a level's rank (KeptFactor, trusted_rank: lse_kept_factor.h).  Tolerance contract; no atomics.
+// them, each on ONE view of the factor and ONE rule for a level's rank (KeptFactor, trusted_rank: lse_kept_factor.h), each a sequence of the
+// steps that lse_kept_steps.h states once (wave_*: one vector per wavefront; lane_*: lane = vector; shared_*: work of the problem).
+// Tolerance contract; no atomics.
 #include "lexls_launch.h"
 #include "lse_kept_factor.h"
+#include "lse_kept_steps.h"
 #include "lse_spd_solve.h"
 #include <cstdlib>
 #include <cstring>
@@ -21,145 +24,42 @@ namespace lexls
         __global__ __launch_bounds__(NT) void solve_adjoint_kernel(LseArgs a, const double *__restrict__ g, double *__restrict__ grad_rhs, double *__restrict__ grad_fixed)
         {
             static_assert(NT == 64, "one wavefront per problem: the reductions are wavefront sums");
-            constexpr uint32_t AU = 4;
             extern __shared__ double smem[];
             const uint32_t b = blockIdx.x, lane = threadIdx.x;
             const KeptFactor kf = kept_factor_of(a, b);
-            const uint32_t n = kf.n, cap = kf.cap, nObj = kf.nObj, nf = kf.nf, T = kf.T, M = kf.M;
+            const uint32_t n = kf.n, cap = kf.cap, nObj = kf.nObj, T = kf.T, M = kf.M;
             const double *__restrict__ W = kf.W, *hh = kf.hh;
-            const uint32_t *dims = kf.dims;
             double *gh = smem, *cb = smem + n;
             uint32_t *perm_l = reinterpret_cast<uint32_t *>(cb + cap);
 
             // ---- (a) gh = P^T g: variable i sits at the position it reaches by following the transpositions first to last ----
-            for (uint32_t i = lane; i < n; i += NT) perm_l[i] = a.perm[(size_t)b * n + i];
-            for (uint32_t i = lane; i < cap; i += NT) cb[i] = 0.0;
-            __syncthreads();
-            for (uint32_t i = lane; i < n; i += NT)
-            {
-                const uint32_t p = position_after_transpositions(perm_l, T, i);
-                if (p < n) gh[p] = g[(size_t)b * n + i];
-            }
-            __syncthreads();
+            wave_step_a<NT>(a.perm + (size_t)b * n, g + (size_t)b * n, perm_l, gh, cb, n, cap, T, lane);
 
-            // ---- (b) the reverse of solve(), levels ascending: y = R_k^-T gh_k, then gh -= [T_k]^T y on the pivot columns of the later levels.
-            // Column c of [R_k | T_k] takes the dot product of its rows above the diagonal (all `rank` rows behind the triangle) with y ----
-            uint32_t F = 0;
-            for (uint32_t k = 0; k < nObj; k++)
-            {
-                const uint32_t dim = dims[k];
-                const auto [rank, Fc] = kf.level(k, dim);
-                if (rank > 0 && F + dim <= M)
-                {
-                    double *y = cb + F;
-                    for (uint32_t c0 = Fc; c0 < T; c0 += AU)
-                    {
-                        double w[AU], dg[AU];
-#pragma unroll
-                        for (uint32_t u = 0; u < AU; u++)
-                        {
-                            const uint32_t c = c0 + u, j = c - Fc;
-                            const uint32_t len = c < T ? (j < rank ? j : rank) : 0;
-                            w[u]  = lane < len ? W[F + lane + (size_t)c * cap] : 0.0;
-                            dg[u] = (c < T && j < rank) ? W[F + j + (size_t)c * cap] : 1.0;
-                        }
-#pragma unroll
-                        for (uint32_t u = 0; u < AU; u++)
-                        {
-                            const uint32_t c = c0 + u, j = c - Fc;
-                            if (c >= T) break;
-                            const uint32_t len = j < rank ? j : rank;
-                            const double s     = column_dot(W + F + (size_t)c * cap, y, len, w[u], lane);
-                            if (j < rank) // (uniform) inside the triangle: the next column reads this y
-                            {
-                                if (lane == 0) y[j] = (gh[c] - s) / dg[u];
-                                __syncthreads();
-                            }
-                            else if (lane == 0)
-                                gh[c] -= s;
-                        }
-                    }
-                    __syncthreads();
-                }
-                F += dim;
-            }
+            // ---- (b) the reverse of solve(), levels ascending: y = R_k^-T gh_k, then gh -= [T_k]^T y on the pivot columns of the later levels ----
+            kf.for_levels_ascending([&](uint32_t, uint32_t, uint32_t F, uint32_t rank, uint32_t Fc) __attribute__((always_inline)) {
+                wave_reverse_solve_level<NT>(W, cap, gh, cb, F, Fc, rank, T, lane);
+            });
 
             // ---- (c) the reverse of factorize()'s right-hand-side updates, levels descending: the transposed Gauss step (the multipliers L sit in
             // the level's pivot columns, rows of the later levels), then the level's reflectors, last first ----
-            uint32_t Fend = 0;
-            for (uint32_t k = 0; k < nObj; k++) Fend += dims[k];
-            for (uint32_t k = nObj; k--;)
-            {
-                const uint32_t dim = dims[k];
-                F                  = Fend - dim;
-                Fend               = F;
-                const auto [rank, Fc] = kf.level(k, dim);
-                if (rank == 0 || F + dim > M) continue;
+            kf.for_levels_descending(kf.total_rows(), [&](uint32_t k, uint32_t dim, uint32_t F, uint32_t rank, uint32_t Fc) __attribute__((always_inline)) {
                 const uint32_t Fn = F + dim;
-                if (k + 1 < nObj && Fn < M)
-                {
-                    for (uint32_t p0 = 0; p0 < rank; p0 += AU)
-                    {
-                        double w[AU], s[AU];
-#pragma unroll
-                        for (uint32_t u = 0; u < AU; u++) w[u] = (p0 + u < rank && lane < M - Fn) ? W[Fn + lane + (size_t)(Fc + p0 + u) * cap] : 0.0;
-#pragma unroll
-                        for (uint32_t u = 0; u < AU; u++) s[u] = p0 + u < rank ? column_dot(W + Fn + (size_t)(Fc + p0 + u) * cap, cb + Fn, M - Fn, w[u], lane) : 0.0;
-#pragma unroll
-                        for (uint32_t u = 0; u < AU; u++)
-                            if (lane == 0 && p0 + u < rank) cb[F + p0 + u] -= s[u];
-                    }
-                    __syncthreads();
-                }
-                // the reflectors on rows F + j .. F + dim - 1, AU at a time: their scalars and first 64 rows are requested together
-                for (uint32_t j0 = rank; j0 > 0; j0 -= (j0 < AU ? j0 : AU))
-                {
-                    double e[AU], tau[AU];
-#pragma unroll
-                    for (uint32_t u = 0; u < AU; u++)
-                    {
-                        const bool on = u < j0;
-                        const uint32_t j = on ? j0 - 1 - u : 0;
-                        tau[u] = on ? hh[F + j] : 0.0;
-                        e[u]   = (on && lane + 1 < dim - j) ? W[F + j + 1 + lane + (size_t)(Fc + j) * cap] : 0.0;
-                    }
-#pragma unroll
-                    for (uint32_t u = 0; u < AU; u++)
-                    {
-                        if (u >= j0) break;
-                        const uint32_t j = j0 - 1 - u;
-                        apply_stored_reflector(W + F + j + 1 + (size_t)(Fc + j) * cap, cb + F + j, dim - j, tau[u], e[u], lane);
-                    }
-                }
-            }
+                if (k + 1 < nObj && Fn < M) wave_gauss_transposed<NT>(W, cap, cb, F, Fn, M, Fc, rank, lane);
+                wave_reflectors_reversed<NT>(W, hh, cap, cb, F, Fc, dim, rank, lane);
+            });
             __syncthreads();
 
             // ---- (d) grad_rhs = cb (rows behind the problem's own stay 0); grad_fixed_j = gh_j - (column j of the fixed variables)^T cb ----
-            for (uint32_t i = lane; i < cap; i += NT) grad_rhs[(size_t)b * cap + i] = cb[i];
-            if (grad_fixed)
-            {
-                for (uint32_t j0 = 0; j0 < nf; j0 += AU)
-                {
-                    double w[AU], s[AU];
-#pragma unroll
-                    for (uint32_t u = 0; u < AU; u++) w[u] = (j0 + u < nf && lane < M) ? W[lane + (size_t)(j0 + u) * cap] : 0.0;
-#pragma unroll
-                    for (uint32_t u = 0; u < AU; u++) s[u] = j0 + u < nf ? column_dot(W + (size_t)(j0 + u) * cap, cb, M, w[u], lane) : 0.0;
-#pragma unroll
-                    for (uint32_t u = 0; u < AU; u++)
-                        if (lane == 0 && j0 + u < nf) grad_fixed[(size_t)b * n + j0 + u] = gh[j0 + u] - s[u];
-                }
-                for (uint32_t j = nf + lane; j < n; j += NT) grad_fixed[(size_t)b * n + j] = 0.0;
-            }
+            wave_step_d<NT>(W, gh, cb, grad_rhs, grad_fixed, b, n, cap, kf.nf, M, lane);
         }
 
         /// solve_adjoint_kernel for a factor of a REGULARIZED factorize() of type 1, 3, 4, 5, 8 or 9 with a constant factor per level (f = a.reg_factor,
         /// held fixed as A is): x = M_reg b + N_reg x_fixed is still affine, and grad_rhs = M_reg^T g, grad_fixed = N_reg^T g.  Forward, level k
         /// replaces its right-hand side y (rows F .. F + rank, behind the reflectors) by y' = P y + Q r when rank > 0 and |f| >= 1e-15 (P = W D^-1 W^T,
-        /// Q = mu W D^-1 U^T, D = W^T W + mu U^T U + mu I, mu = f^2; W = [R | T] for types 1, 5, 8 and R for 3, 4; U = the rows of the null-space
-        /// basis NS above the level's columns at entry to the level, absent for 4 and 5; type 9: y' = f y), and types 1, 3, 8 then give NS's right-hand
-        /// side column r new rows and subtract L y' from it, L = [U_R ; I] R^-1.  Steps (a), (b), (d) and the Gauss and reflector parts of (c) are
-        /// solve_adjoint_kernel's.  New: the rebuild of NS from the factor (types 1, 3, 8; A side only — in the factor's FINAL column order: the
+        /// Q = mu W D^-1 U^T, D the level's damped normal matrix (shared_damped_normal_matrix), mu = f^2; W = [R | T] for types 1, 5, 8 and R for 3, 4;
+        /// U = the rows of the null-space basis NS above the level's columns at entry to the level, absent for 4 and 5; type 9: y' = f y), and types
+        /// 1, 3, 8 then give NS's right-hand side column r new rows and subtract L y' from it, L = [U_R ; I] R^-1.  Steps (a), (b), (d) and the Gauss
+        /// and reflector parts of (c) are solve_adjoint_kernel's.  New: the rebuild of NS from the factor (types 1, 3, 8; A side only — in the factor's FINAL column order: the
         /// forward column swaps act on NS and on T alike, and D, W t and U t do not change under a common permutation of their columns) with a
         /// snapshot of U per level; in (c) behind the transposed Gauss step, with r~ the cotangent of r (zero behind the last level):
         ///     types 1, 3, 8:  y~' -= R^-T (U_R^T r~[0, m0) + r~[m0, m0 + rank)), the level's own rows of r~ dropped
@@ -170,147 +70,50 @@ namespace lexls
                                                                        double *__restrict__ work)
         {
             static_assert(NT == 64, "one wavefront per problem: the reductions are wavefront sums");
-            constexpr uint32_t AU = 4;
             extern __shared__ double smem[];
             const uint32_t b = blockIdx.x, lane = threadIdx.x;
             const KeptFactor kf = kept_factor_of(a, b);
             const uint32_t n = kf.n, cap = kf.cap, nObj = kf.nObj, nf = kf.nf, T = kf.T, M = kf.M;
             const double *__restrict__ W = kf.W, *hh = kf.hh;
-            const uint32_t *dims = kf.dims;
-            const uint32_t type  = a.reg_type;
-            const bool accum = type == 1 || type == 3 || type == 8; // the types that accumulate NS (and read it)
-            const bool wideW = type == 1 || type == 5 || type == 8; // W = [R | T] (else R)
-            const double *fac = a.reg_factor + (size_t)b * nObj;
+            const RegularizedLevels reg = regularized_levels_of(a, b);
             double *gh = smem, *cb = gh + n, *rbar = cb + cap, *dv = rbar + n;
             uint32_t *perm_l = reinterpret_cast<uint32_t *>(dv + n);
             // (n words behind 3 n + cap doubles: the matrices start on an 8-byte boundary at perm_l + 2 ((n + 1) / 2))
             double *mat = IN_LDS ? reinterpret_cast<double *>(perm_l + 2 * ((n + 1) / 2)) : work + (size_t)b * adjoint_reg_matrix_doubles(n, nObj);
             double *NS = mat, *D = NS + (size_t)n * n, *SN = D + (size_t)n * n;
-            auto ns = [&](uint32_t i, uint32_t j) __attribute__((always_inline)) -> double & { return NS[i + (size_t)j * n]; };
-            auto w  = [&](uint32_t i, uint32_t j) __attribute__((always_inline)) -> double { return W[i + (size_t)j * cap]; };
+            auto w = [&](uint32_t i, uint32_t j) __attribute__((always_inline)) -> double { return W[i + (size_t)j * cap]; };
 
             // ---- (a) gh = P^T g ----
-            for (uint32_t i = lane; i < n; i += NT) perm_l[i] = a.perm[(size_t)b * n + i];
-            for (uint32_t i = lane; i < cap; i += NT) cb[i] = 0.0;
             for (uint32_t i = lane; i < n; i += NT) rbar[i] = 0.0;
-            if (accum)
+            if (reg.accum)
                 for (uint32_t i = lane; i < n * n; i += NT) NS[i] = 0.0;
-            __syncthreads();
-            for (uint32_t i = lane; i < n; i += NT)
-            {
-                const uint32_t p = position_after_transpositions(perm_l, T, i);
-                if (p < n) gh[p] = g[(size_t)b * n + i];
-            }
-            __syncthreads();
+            wave_step_a<NT>(a.perm + (size_t)b * n, g + (size_t)b * n, perm_l, gh, cb, n, cap, T, lane);
 
             // ---- (b) the reverse of solve(), levels ascending (solve() reads the regularized right-hand sides: cb rows F .. F + rank are y~') ----
-            uint32_t F = 0;
-            for (uint32_t k = 0; k < nObj; k++)
-            {
-                const uint32_t dim = dims[k];
-                const auto [rank, Fc] = kf.level(k, dim);
-                if (rank > 0 && F + dim <= M)
-                {
-                    double *y = cb + F;
-                    for (uint32_t c0 = Fc; c0 < T; c0 += AU)
-                    {
-                        double wv[AU], dg[AU];
-#pragma unroll
-                        for (uint32_t u = 0; u < AU; u++)
-                        {
-                            const uint32_t c = c0 + u, j = c - Fc;
-                            const uint32_t len = c < T ? (j < rank ? j : rank) : 0;
-                            wv[u] = lane < len ? W[F + lane + (size_t)c * cap] : 0.0;
-                            dg[u] = (c < T && j < rank) ? W[F + j + (size_t)c * cap] : 1.0;
-                        }
-#pragma unroll
-                        for (uint32_t u = 0; u < AU; u++)
-                        {
-                            const uint32_t c = c0 + u, j = c - Fc;
-                            if (c >= T) break;
-                            const uint32_t len = j < rank ? j : rank;
-                            const double s     = column_dot(W + F + (size_t)c * cap, y, len, wv[u], lane);
-                            if (j < rank)
-                            {
-                                if (lane == 0) y[j] = (gh[c] - s) / dg[u];
-                                __syncthreads();
-                            }
-                            else if (lane == 0)
-                                gh[c] -= s;
-                        }
-                    }
-                    __syncthreads();
-                }
-                F += dim;
-            }
+            kf.for_levels_ascending([&](uint32_t, uint32_t, uint32_t F, uint32_t rank, uint32_t Fc) __attribute__((always_inline)) {
+                wave_reverse_solve_level<NT>(W, cap, gh, cb, F, Fc, rank, T, lane);
+            });
 
-            // ---- the rebuild of NS, levels ascending (reg_accumulate_nullspace without the right-hand-side column), U snapshot first ----
-            uint32_t soff = 0; // doubles of SN in use
-            if (accum)
-            {
-                F = 0;
-                for (uint32_t k = 0; k < nObj; k++)
-                {
-                    const uint32_t dim = dims[k];
-                    const auto [rank, Fc] = kf.level(k, dim);
-                    if (rank > 0 && F + dim <= M)
-                    {
-                        const uint32_t m0 = Fc > nf ? Fc - nf : 0, rows = m0 + rank, RC = n - Fc - rank, wc = wideW ? n - Fc : rank;
-                        for (uint32_t e = lane; e < m0 * wc; e += NT) SN[soff + e] = ns(e % m0, Fc + e / m0);
-                        soff += m0 * wc;
-                        for (uint32_t e = lane; e < rank * rank; e += NT) ns(m0 + e % rank, Fc + e / rank) = (e % rank == e / rank) ? 1.0 : 0.0;
-                        __syncthreads();
-                        for (uint32_t i = lane; i < rows; i += NT) // Left <- Left R^-1, a row per lane
-                            for (uint32_t p = 0; p < rank; p++)
-                            {
-                                double sv = ns(i, Fc + p);
-                                for (uint32_t q = 0; q < p; q++) sv = dfma(-ns(i, Fc + q), w(F + q, Fc + p), sv);
-                                ns(i, Fc + p) = sv / w(F + p, Fc + p);
-                            }
-                        __syncthreads();
-                        for (uint32_t e = lane; e < rows * RC; e += NT) // Trailing -= Left T
-                        {
-                            const uint32_t i = e % rows, c = Fc + rank + e / rows;
-                            double t = ns(i, c);
-                            for (uint32_t p = 0; p < rank; p++) t = dfma(-ns(i, Fc + p), w(F + p, c), t);
-                            ns(i, c) = t;
-                        }
-                        __syncthreads();
-                    }
-                    F += dim;
-                }
-            }
+            // ---- the rebuild of NS, levels ascending, U snapshot first ----
+            uint32_t soff = reg.accum ? shared_rebuild_nullspace<NT>(kf, reg, w, NS, SN, lane) : 0; // doubles of SN in use
 
             // ---- (c) the reverse of factorize()'s right-hand-side updates, levels descending ----
+            // (a plain loop, not KeptFactor's walk: under the walk this instantiation takes 134 registers instead of 117 and loses a wavefront per SIMD)
             uint32_t Fend = 0;
-            for (uint32_t k = 0; k < nObj; k++) Fend += dims[k];
+            for (uint32_t k = 0; k < nObj; k++) Fend += kf.dims[k];
             for (uint32_t k = nObj; k--;)
             {
-                const uint32_t dim = dims[k];
-                F                  = Fend - dim;
+                const uint32_t dim = kf.dims[k];
+                const uint32_t F   = Fend - dim;
                 Fend               = F;
                 const auto [rank, Fc] = kf.level(k, dim);
                 if (rank == 0 || F + dim > M) continue;
                 const uint32_t Fn = F + dim;
-                if (k + 1 < nObj && Fn < M)
-                {
-                    for (uint32_t p0 = 0; p0 < rank; p0 += AU)
-                    {
-                        double wv[AU], s[AU];
-#pragma unroll
-                        for (uint32_t u = 0; u < AU; u++) wv[u] = (p0 + u < rank && lane < M - Fn) ? W[Fn + lane + (size_t)(Fc + p0 + u) * cap] : 0.0;
-#pragma unroll
-                        for (uint32_t u = 0; u < AU; u++) s[u] = p0 + u < rank ? column_dot(W + Fn + (size_t)(Fc + p0 + u) * cap, cb + Fn, M - Fn, wv[u], lane) : 0.0;
-#pragma unroll
-                        for (uint32_t u = 0; u < AU; u++)
-                            if (lane == 0 && p0 + u < rank) cb[F + p0 + u] -= s[u];
-                    }
-                    __syncthreads();
-                }
-                const uint32_t m0 = Fc > nf ? Fc - nf : 0, N = wideW ? n - Fc : rank;
+                if (k + 1 < nObj && Fn < M) wave_gauss_transposed<NT>(W, cap, cb, F, Fn, M, Fc, rank, lane);
+                const uint32_t m0 = Fc > nf ? Fc - nf : 0, N = reg.width(n, Fc, rank);
                 const double *U   = SN; // the level's snapshot: m0 x N, leading dimension m0
                 double *yb        = cb + F;
-                if (accum)
+                if (reg.accum)
                 {
                     soff -= m0 * N;
                     U = SN + soff;
@@ -336,39 +139,18 @@ namespace lexls
                         __syncthreads();
                     }
                 }
-                const double f = fac[k];
-                if (!(fabs(f - 0.0) < 1e-15)) // the gate of regularize_level
+                const double f = reg.fac[k];
+                if (reg.acts(f))
                 {
-                    if (type == 9)
+                    if (reg.type == 9)
                     {
                         for (uint32_t i = lane; i < rank; i += NT) yb[i] *= f;
                     }
                     else
                     {
                         const double mu = f * f;
-                        // D = W^T W + mu U^T U + mu I (lower triangle), dv = W^T y~'; column c of W has min(c + 1, rank) rows
-                        for (uint32_t e = lane; e < N * N; e += NT)
-                        {
-                            const uint32_t i = e % N, j = e / N;
-                            if (i < j) continue;
-                            const uint32_t len = j < rank ? j + 1 : rank;
-                            double acc = 0.0;
-                            for (uint32_t r = 0; r < len; r++) acc = dfma(w(F + r, Fc + i), w(F + r, Fc + j), acc);
-                            if (accum)
-                            {
-                                double up = 0.0;
-                                for (uint32_t s = 0; s < m0; s++) up = dfma(U[s + (size_t)i * m0], U[s + (size_t)j * m0], up);
-                                acc = dfma(mu, up, acc);
-                            }
-                            D[i + (size_t)j * n] = i == j ? acc + mu : acc;
-                        }
-                        for (uint32_t c = lane; c < N; c += NT)
-                        {
-                            const uint32_t len = c < rank ? c + 1 : rank;
-                            double acc = 0.0;
-                            for (uint32_t r = 0; r < len; r++) acc = dfma(w(F + r, Fc + c), yb[r], acc);
-                            dv[c] = acc;
-                        }
+                        shared_damped_normal_matrix<NT>(w, U, m0, reg.accum, mu, D, n, F, Fc, rank, N, m0, lane);
+                        for (uint32_t c = lane; c < N; c += NT) dv[c] = lane_wt_y<1>(w, yb, F, Fc, rank, c); // dv = W^T y~' (y~' dense: LD 1)
                         __syncthreads();
                         spd_solve<NT>(D, n, dv, N, lane); // dv = t
                         for (uint32_t i = lane; i < rank; i += NT) // y~ = W t
@@ -377,7 +159,7 @@ namespace lexls
                             for (uint32_t c = i; c < N; c++) acc = dfma(w(F + i, Fc + c), dv[c], acc);
                             yb[i] = acc;
                         }
-                        if (accum)
+                        if (reg.accum)
                             for (uint32_t s = lane; s < m0; s += NT) // r~ += mu U t
                             {
                                 double acc = 0.0;
@@ -387,47 +169,13 @@ namespace lexls
                     }
                     __syncthreads();
                 }
-                // the reflectors on rows F + j .. F + dim - 1, AU at a time
-                for (uint32_t j0 = rank; j0 > 0; j0 -= (j0 < AU ? j0 : AU))
-                {
-                    double e[AU], tau[AU];
-#pragma unroll
-                    for (uint32_t u = 0; u < AU; u++)
-                    {
-                        const bool on = u < j0;
-                        const uint32_t j = on ? j0 - 1 - u : 0;
-                        tau[u] = on ? hh[F + j] : 0.0;
-                        e[u]   = (on && lane + 1 < dim - j) ? W[F + j + 1 + lane + (size_t)(Fc + j) * cap] : 0.0;
-                    }
-#pragma unroll
-                    for (uint32_t u = 0; u < AU; u++)
-                    {
-                        if (u >= j0) break;
-                        const uint32_t j = j0 - 1 - u;
-                        apply_stored_reflector(W + F + j + 1 + (size_t)(Fc + j) * cap, cb + F + j, dim - j, tau[u], e[u], lane);
-                    }
-                }
+                wave_reflectors_reversed<NT>(W, hh, cap, cb, F, Fc, dim, rank, lane);
             }
             __syncthreads();
 
             // ---- (d) grad_rhs = cb; grad_fixed_j = gh_j - (column j of the fixed variables)^T cb (the fixed values enter the right-hand side
             // in front of every level, and r through y' alone) ----
-            for (uint32_t i = lane; i < cap; i += NT) grad_rhs[(size_t)b * cap + i] = cb[i];
-            if (grad_fixed)
-            {
-                for (uint32_t j0 = 0; j0 < nf; j0 += AU)
-                {
-                    double wv[AU], s[AU];
-#pragma unroll
-                    for (uint32_t u = 0; u < AU; u++) wv[u] = (j0 + u < nf && lane < M) ? W[lane + (size_t)(j0 + u) * cap] : 0.0;
-#pragma unroll
-                    for (uint32_t u = 0; u < AU; u++) s[u] = j0 + u < nf ? column_dot(W + (size_t)(j0 + u) * cap, cb, M, wv[u], lane) : 0.0;
-#pragma unroll
-                    for (uint32_t u = 0; u < AU; u++)
-                        if (lane == 0 && j0 + u < nf) grad_fixed[(size_t)b * n + j0 + u] = gh[j0 + u] - s[u];
-                }
-                for (uint32_t j = nf + lane; j < n; j += NT) grad_fixed[(size_t)b * n + j] = 0.0;
-            }
+            wave_step_d<NT>(W, gh, cb, grad_rhs, grad_fixed, b, n, cap, nf, M, lane);
         }
 
         // gradient with respect to the matrix (lexls_lse_solve_adjoint_matrix): the solve map on a new right-hand side, the assembly
@@ -665,15 +413,14 @@ namespace lexls
                                                                          double *__restrict__ grad_fixed)
         {
             static_assert(NT == 64, "one wavefront per (problem, tile): lane = cotangent");
-            constexpr uint32_t LD = kAdjointMultiLd, AU = 4;
+            constexpr uint32_t LD = kAdjointMultiLd;
             extern __shared__ double smem[];
             const uint32_t b = blockIdx.x, tile = blockIdx.y, lane = threadIdx.x;
             if (b >= a.batch || tile * 64u >= ncot) return; // (block-uniform)
             const uint32_t kt = ncot - tile * 64u < 64u ? ncot - tile * 64u : 64u; // live cotangents of this tile
             const KeptFactor kf = kept_factor_of(a, b);
-            const uint32_t n = kf.n, cap = kf.cap, nObj = kf.nObj, nf = kf.nf, T = kf.T, M = kf.M;
+            const uint32_t n = kf.n, cap = kf.cap, nObj = kf.nObj, T = kf.T, M = kf.M;
             const double *__restrict__ W = kf.W;
-            const uint32_t *dims = kf.dims;
             double *gh       = smem;
             double *cb       = gh + (size_t)n * LD;
             uint32_t *perm_l = reinterpret_cast<uint32_t *>(cb + (size_t)cap * LD);
@@ -684,6 +431,7 @@ namespace lexls
             // entry (r, c) of the factor, r < M <= cap, c < T <= nVar; the Householder scalar of row r < cap
             auto Wat = [&](uint32_t r, uint32_t c) __attribute__((always_inline)) -> double { return STAGED ? L[r + c * ldl] : W[r + (size_t)c * cap]; };
             auto tau_at = [&](uint32_t r) __attribute__((always_inline)) -> double { return STAGED ? hh_l[r] : kf.hh[r]; };
+            const size_t row0 = (size_t)b * ncot + (size_t)tile * 64u; // the tile's kt rows of G, grad_rhs and grad_fixed are contiguous from here
 
             // ---- staging, and (a) gh = P^T g for every cotangent of the tile ----
             for (uint32_t i = lane; i < n; i += NT) perm_l[i] = a.perm[(size_t)b * n + i];
@@ -697,119 +445,32 @@ namespace lexls
                 __syncthreads();
             for (uint32_t i = lane; i < n; i += NT) pos_l[i] = position_after_transpositions(perm_l, T, i);
             __syncthreads();
-            {
-                const double *Gt = G + ((size_t)b * ncot + (size_t)tile * 64u) * n; // kt rows of n doubles, contiguous
-                for (uint32_t e = lane; e < kt * n; e += NT)
-                {
-                    const uint32_t c = e / n, i = e - c * n, p = pos_l[i];
-                    if (p < n) gh[p * LD + c] = Gt[e];
-                }
-            }
+            lane_gather_by_position<NT, LD>(G + row0 * n, pos_l, gh, kt, n, lane);
             __syncthreads();
             double *ghl = gh + lane, *cbl = cb + lane; // this lane's column of the state
 
             // ---- (b) the reverse of solve(), levels ascending ----
-            uint32_t F = 0;
-            for (uint32_t k = 0; k < nObj; k++)
-            {
-                const uint32_t dim = dims[k];
-                const auto [rank, Fc] = kf.level(k, dim);
-                if (rank > 0 && F + dim <= M)
-                {
-                    double *y = cbl + F * LD;
-                    for (uint32_t c = Fc; c < T; c++)
-                    {
-                        const uint32_t j = c - Fc, len = j < rank ? j : rank;
-                        double s = 0.0;
-                        for (uint32_t i = 0; i < len; i++) s = dfma(Wat(F + i, c), y[i * LD], s);
-                        if (j < rank) // (uniform) inside the triangle
-                            y[j * LD] = (ghl[c * LD] - s) / Wat(F + j, c);
-                        else
-                            ghl[c * LD] -= s;
-                    }
-                }
-                F += dim;
-            }
+            kf.for_levels_ascending([&](uint32_t, uint32_t, uint32_t F, uint32_t rank, uint32_t Fc) __attribute__((always_inline)) {
+                lane_reverse_solve_level<LD>(Wat, ghl, cbl, F, Fc, rank, T);
+            });
 
-            // ---- (c) the reverse of factorize()'s right-hand-side updates, levels descending ----
-            uint32_t Fend = 0;
-            for (uint32_t k = 0; k < nObj; k++) Fend += dims[k];
-            for (uint32_t k = nObj; k--;)
-            {
-                const uint32_t dim = dims[k];
-                F                  = Fend - dim;
-                Fend               = F;
-                const auto [rank, Fc] = kf.level(k, dim);
-                if (rank == 0 || F + dim > M) continue;
+            // ---- (c) the reverse of factorize()'s right-hand-side updates, levels descending: the transposed Gauss step, then the level's
+            // reflectors, last first ----
+            kf.for_levels_descending(kf.total_rows(), [&](uint32_t k, uint32_t dim, uint32_t F, uint32_t rank, uint32_t Fc) __attribute__((always_inline)) {
                 const uint32_t Fn = F + dim;
-                if (k + 1 < nObj && Fn < M)
-                {
-                    // the transposed Gauss step: AU multiplier columns share one read of the lane's cb rows (each sum in ascending row order)
-                    for (uint32_t p0 = 0; p0 < rank; p0 += AU)
-                    {
-                        double s[AU];
-#pragma unroll
-                        for (uint32_t u = 0; u < AU; u++) s[u] = 0.0;
-                        for (uint32_t i = Fn; i < M; i++)
-                        {
-                            const double ci = cbl[i * LD];
-#pragma unroll
-                            for (uint32_t u = 0; u < AU; u++)
-                                if (p0 + u < rank) s[u] = dfma(Wat(i, Fc + p0 + u), ci, s[u]);
-                        }
-#pragma unroll
-                        for (uint32_t u = 0; u < AU; u++)
-                            if (p0 + u < rank) cbl[(F + p0 + u) * LD] -= s[u];
-                    }
-                }
-                // the level's reflectors, last first (lane = cotangent: a serial chain per lane, no barrier — not apply_stored_reflector's shape)
-                for (uint32_t j = rank; j--;)
-                {
-                    const uint32_t rows = dim - j;
-                    const double tau    = tau_at(F + j);
-                    if (rows == 1 || tau == 0.0) continue; // (uniform)
-                    double *v = cbl + (F + j) * LD;
-                    double t  = 0.0;
-                    for (uint32_t i = 1; i < rows; i++) t = dfma(Wat(F + j + i, Fc + j), v[i * LD], t);
-                    t += v[0];
-                    v[0] = dfma(-tau, t, v[0]);
-                    for (uint32_t i = 1; i < rows; i++) v[i * LD] = dfma(-(tau * Wat(F + j + i, Fc + j)), t, v[i * LD]);
-                }
-            }
+                if (k + 1 < nObj && Fn < M) lane_gauss_transposed<LD>(Wat, cbl, F, Fn, M, Fc, rank);
+                lane_reflectors_reversed<LD>(Wat, tau_at, cbl, F, Fc, dim, rank);
+            });
 
             // ---- (d) grad_fixed_j = gh_j - (column j of the fixed variables)^T cb, left in gh_j; then both outputs, transposed through LDS ----
-            if (grad_fixed)
-                for (uint32_t j = 0; j < nf; j++)
-                {
-                    double s = 0.0;
-                    for (uint32_t r = 0; r < M; r++) s = dfma(Wat(r, j), cbl[r * LD], s);
-                    ghl[j * LD] -= s;
-                }
-            __syncthreads();
-            {
-                double *out = grad_rhs + ((size_t)b * ncot + (size_t)tile * 64u) * cap;
-                for (uint32_t e = lane; e < kt * cap; e += NT)
-                {
-                    const uint32_t c = e / cap, r = e - c * cap;
-                    out[e]           = cb[r * LD + c]; // (rows behind the problem's own were never touched: 0)
-                }
-            }
-            if (grad_fixed)
-            {
-                double *out = grad_fixed + ((size_t)b * ncot + (size_t)tile * 64u) * n;
-                for (uint32_t e = lane; e < kt * n; e += NT)
-                {
-                    const uint32_t c = e / n, j = e - c * n;
-                    out[e]           = j < nf ? gh[j * LD + c] : 0.0;
-                }
-            }
+            lane_step_d<NT, LD>(Wat, gh, cb, grad_rhs, grad_fixed, row0, kt, n, cap, kf.nf, M, lane);
         }
 
         /// solve_adjoint_reg_kernel's steps (a)-(d) for up to 64 cotangents of one problem at once, LANE = COTANGENT, the way
         /// solve_adjoint_multi_kernel recasts solve_adjoint_kernel: one wavefront per (problem, tile of 64 cotangents); lanes beyond ncot compute on
         /// zeros and store nothing.  Two kinds of phases alternate, with barriers between them:
-        ///   SHARED (work of the problem, the lanes spread over rows and entries exactly as in solve_adjoint_reg_kernel): the rebuild of NS with a
-        ///     snapshot of U per level (types 1, 3, 8), and per damped level the formation of D = W^T W + mu U^T U + mu I and its LL^T (spd_factor<NT>,
+        ///   SHARED (work of the problem, the lanes spread over rows and entries: the shared_* steps solve_adjoint_reg_kernel calls too): the rebuild
+        ///     of NS with a snapshot of U per level (types 1, 3, 8), and per damped level the formation of D and its LL^T (spd_factor<NT>,
         ///     lse_spd_solve.h: either form).  EVERY TILE REPEATS THIS WORK.
         ///   PER LANE (work of the cotangent): steps (b), (c), (d) on the lane's own column of gh, cb, r~ and dv (LDS, [index][lane], leading
         ///     dimension 65); every dot product, substitution and matrix-vector product is the lane's own serial dfma chain in a fixed order — among
@@ -825,7 +486,7 @@ namespace lexls
                                                                              double *__restrict__ grad_fixed, double *__restrict__ work)
         {
             static_assert(NT == 64, "one wavefront per (problem, tile): lane = cotangent");
-            constexpr uint32_t LD = kAdjointMultiLd, AU = 4;
+            constexpr uint32_t LD = kAdjointMultiLd;
             extern __shared__ double smem[];
             const uint32_t b = blockIdx.x, tile = blockIdx.y, lane = threadIdx.x;
             if (b >= a.batch || tile * 64u >= ncot) return; // (block-uniform)
@@ -833,134 +494,45 @@ namespace lexls
             const KeptFactor kf = kept_factor_of(a, b);
             const uint32_t n = kf.n, cap = kf.cap, nObj = kf.nObj, nf = kf.nf, T = kf.T, M = kf.M;
             const double *__restrict__ W = kf.W, *hh = kf.hh;
-            const uint32_t *dims = kf.dims;
-            const uint32_t type  = a.reg_type;
-            const bool accum = type == 1 || type == 3 || type == 8; // the types that accumulate NS (and read it)
-            const bool wideW = type == 1 || type == 5 || type == 8; // W = [R | T] (else R)
-            const double *fac = a.reg_factor + (size_t)b * nObj;
+            const RegularizedLevels reg = regularized_levels_of(a, b);
             double *gh = smem, *cb = gh + (size_t)n * LD, *rbar = cb + (size_t)cap * LD, *dv = rbar + (size_t)n * LD;
             uint32_t *perm_l = reinterpret_cast<uint32_t *>(dv + (size_t)n * LD);
             uint32_t *pos_l  = perm_l + n;
             // (2 n words: the matrices start on an 8-byte boundary)
             double *mat = IN_LDS ? reinterpret_cast<double *>(pos_l + n) : work + ((size_t)b * gridDim.y + tile) * adjoint_reg_matrix_doubles(n, nObj);
             double *NS = mat, *D = NS + (size_t)n * n, *SN = D + (size_t)n * n;
-            auto ns = [&](uint32_t i, uint32_t j) __attribute__((always_inline)) -> double & { return NS[i + (size_t)j * n]; };
-            auto w  = [&](uint32_t i, uint32_t j) __attribute__((always_inline)) -> double { return W[i + (size_t)j * cap]; };
+            auto w = [&](uint32_t i, uint32_t j) __attribute__((always_inline)) -> double { return W[i + (size_t)j * cap]; };
+            auto tau_at = [&](uint32_t r) __attribute__((always_inline)) -> double { return hh[r]; };
+            const size_t row0 = (size_t)b * ncot + (size_t)tile * 64u; // the tile's kt rows of G, grad_rhs and grad_fixed are contiguous from here
 
             // ---- (a) gh = P^T g for every cotangent of the tile; the rest of the state zero ----
             for (uint32_t i = lane; i < n; i += NT) perm_l[i] = a.perm[(size_t)b * n + i];
             for (uint32_t i = lane; i < (3 * n + cap) * LD; i += NT) smem[i] = 0.0;
-            if (accum)
+            if (reg.accum)
                 for (uint32_t i = lane; i < n * n; i += NT) NS[i] = 0.0;
             __syncthreads();
             for (uint32_t i = lane; i < n; i += NT) pos_l[i] = position_after_transpositions(perm_l, T, i);
             __syncthreads();
-            {
-                const double *Gt = G + ((size_t)b * ncot + (size_t)tile * 64u) * n; // kt rows of n doubles, contiguous
-                for (uint32_t e = lane; e < kt * n; e += NT)
-                {
-                    const uint32_t c = e / n, i = e - c * n, p = pos_l[i];
-                    if (p < n) gh[p * LD + c] = Gt[e];
-                }
-            }
+            lane_gather_by_position<NT, LD>(G + row0 * n, pos_l, gh, kt, n, lane);
             __syncthreads();
             double *ghl = gh + lane, *cbl = cb + lane, *rbl = rbar + lane, *dvl = dv + lane; // this lane's column of the state
 
             // ---- (b) the reverse of solve(), levels ascending (cb rows F .. F + rank are y~'), per lane ----
-            uint32_t F = 0;
-            for (uint32_t k = 0; k < nObj; k++)
-            {
-                const uint32_t dim = dims[k];
-                const auto [rank, Fc] = kf.level(k, dim);
-                if (rank > 0 && F + dim <= M)
-                {
-                    double *y = cbl + F * LD;
-                    for (uint32_t c = Fc; c < T; c++)
-                    {
-                        const uint32_t j = c - Fc, len = j < rank ? j : rank;
-                        double s = 0.0;
-                        for (uint32_t i = 0; i < len; i++) s = dfma(w(F + i, c), y[i * LD], s);
-                        if (j < rank) // (uniform) inside the triangle
-                            y[j * LD] = (ghl[c * LD] - s) / w(F + j, c);
-                        else
-                            ghl[c * LD] -= s;
-                    }
-                }
-                F += dim;
-            }
+            kf.for_levels_ascending([&](uint32_t, uint32_t, uint32_t F, uint32_t rank, uint32_t Fc) __attribute__((always_inline)) {
+                lane_reverse_solve_level<LD>(w, ghl, cbl, F, Fc, rank, T);
+            });
 
-            // ---- SHARED: the rebuild of NS, levels ascending, U snapshot first (solve_adjoint_reg_kernel's, statement for statement) ----
-            uint32_t soff = 0; // doubles of SN in use
-            if (accum)
-            {
-                F = 0;
-                for (uint32_t k = 0; k < nObj; k++)
-                {
-                    const uint32_t dim = dims[k];
-                    const auto [rank, Fc] = kf.level(k, dim);
-                    if (rank > 0 && F + dim <= M)
-                    {
-                        const uint32_t m0 = Fc > nf ? Fc - nf : 0, rows = m0 + rank, RC = n - Fc - rank, wc = wideW ? n - Fc : rank;
-                        for (uint32_t e = lane; e < m0 * wc; e += NT) SN[soff + e] = ns(e % m0, Fc + e / m0);
-                        soff += m0 * wc;
-                        for (uint32_t e = lane; e < rank * rank; e += NT) ns(m0 + e % rank, Fc + e / rank) = (e % rank == e / rank) ? 1.0 : 0.0;
-                        __syncthreads();
-                        for (uint32_t i = lane; i < rows; i += NT) // Left <- Left R^-1, a row per lane
-                            for (uint32_t p = 0; p < rank; p++)
-                            {
-                                double sv = ns(i, Fc + p);
-                                for (uint32_t q = 0; q < p; q++) sv = dfma(-ns(i, Fc + q), w(F + q, Fc + p), sv);
-                                ns(i, Fc + p) = sv / w(F + p, Fc + p);
-                            }
-                        __syncthreads();
-                        for (uint32_t e = lane; e < rows * RC; e += NT) // Trailing -= Left T
-                        {
-                            const uint32_t i = e % rows, c = Fc + rank + e / rows;
-                            double t = ns(i, c);
-                            for (uint32_t p = 0; p < rank; p++) t = dfma(-ns(i, Fc + p), w(F + p, c), t);
-                            ns(i, c) = t;
-                        }
-                        __syncthreads();
-                    }
-                    F += dim;
-                }
-            }
+            // ---- SHARED: the rebuild of NS, levels ascending, U snapshot first ----
+            uint32_t soff = reg.accum ? shared_rebuild_nullspace<NT>(kf, reg, w, NS, SN, lane) : 0; // doubles of SN in use
 
             // ---- (c) the reverse of factorize()'s right-hand-side updates, levels descending ----
-            uint32_t Fend = 0;
-            for (uint32_t k = 0; k < nObj; k++) Fend += dims[k];
-            for (uint32_t k = nObj; k--;)
-            {
-                const uint32_t dim = dims[k];
-                F                  = Fend - dim;
-                Fend               = F;
-                const auto [rank, Fc] = kf.level(k, dim);
-                if (rank == 0 || F + dim > M) continue;
+            kf.for_levels_descending(kf.total_rows(), [&](uint32_t k, uint32_t dim, uint32_t F, uint32_t rank, uint32_t Fc) __attribute__((always_inline)) {
                 const uint32_t Fn = F + dim;
-                if (k + 1 < nObj && Fn < M)
-                {
-                    // the transposed Gauss step: AU multiplier columns share one read of the lane's cb rows (each sum in ascending row order)
-                    for (uint32_t p0 = 0; p0 < rank; p0 += AU)
-                    {
-                        double s[AU];
-#pragma unroll
-                        for (uint32_t u = 0; u < AU; u++) s[u] = 0.0;
-                        for (uint32_t i = Fn; i < M; i++)
-                        {
-                            const double ci = cbl[i * LD];
-#pragma unroll
-                            for (uint32_t u = 0; u < AU; u++)
-                                if (p0 + u < rank) s[u] = dfma(w(i, Fc + p0 + u), ci, s[u]);
-                        }
-#pragma unroll
-                        for (uint32_t u = 0; u < AU; u++)
-                            if (p0 + u < rank) cbl[(F + p0 + u) * LD] -= s[u];
-                    }
-                }
-                const uint32_t m0 = Fc > nf ? Fc - nf : 0, N = wideW ? n - Fc : rank;
+                if (k + 1 < nObj && Fn < M) lane_gauss_transposed<LD>(w, cbl, F, Fn, M, Fc, rank);
+                const uint32_t m0 = Fc > nf ? Fc - nf : 0, N = reg.width(n, Fc, rank);
                 const double *U   = SN; // the level's snapshot: m0 x N, leading dimension m0
                 double *yb        = cbl + F * LD;
-                if (accum)
+                if (reg.accum)
                 {
                     soff -= m0 * N;
                     U = SN + soff;
@@ -980,62 +552,26 @@ namespace lexls
                         yb[j * LD] -= vj;
                     }
                 }
-                const double f = fac[k];
-                if (!(fabs(f - 0.0) < 1e-15)) // the gate of regularize_level (uniform)
+                const double f = reg.fac[k];
+                if (reg.acts(f)) // (uniform)
                 {
-                    if (type == 9)
+                    if (reg.type == 9)
                     {
                         for (uint32_t i = 0; i < rank; i++) yb[i * LD] *= f;
                     }
                     else
                     {
                         const double mu = f * f;
-                        // SHARED: D = W^T W + mu U^T U + mu I (lower triangle; column c of W has min(c + 1, rank) rows) and its LL^T
-                        for (uint32_t e = lane; e < N * N; e += NT)
-                        {
-                            const uint32_t i = e % N, j = e / N;
-                            if (i < j) continue;
-                            const uint32_t len = j < rank ? j + 1 : rank;
-                            double acc = 0.0;
-                            for (uint32_t r = 0; r < len; r++) acc = dfma(w(F + r, Fc + i), w(F + r, Fc + j), acc);
-                            if (accum)
-                            {
-                                double up = 0.0;
-                                for (uint32_t s = 0; s < m0; s++) up = dfma(U[s + (size_t)i * m0], U[s + (size_t)j * m0], up);
-                                acc = dfma(mu, up, acc);
-                            }
-                            D[i + (size_t)j * n] = i == j ? acc + mu : acc;
-                        }
+                        // SHARED: D and its LL^T
+                        shared_damped_normal_matrix<NT>(w, U, m0, reg.accum, mu, D, n, F, Fc, rank, N, m0, lane);
                         __syncthreads();
                         spd_factor<NT>(D, n, N, lane); // (ends in a barrier: every lane reads all of L from here on)
-                        // PER LANE: dv = W^T y~', then L z = dv and L^T t = z in place, row by row against the shared factor
-                        for (uint32_t c = 0; c < N; c++)
-                        {
-                            const uint32_t len = c < rank ? c + 1 : rank;
-                            double acc = 0.0;
-                            for (uint32_t r = 0; r < len; r++) acc = dfma(w(F + r, Fc + c), yb[r * LD], acc);
-                            dvl[c * LD] = acc;
-                        }
-                        for (uint32_t i = 0; i < N; i++)
-                        {
-                            double acc = dvl[i * LD];
-                            for (uint32_t j = 0; j < i; j++) acc = dfma(-D[i + (size_t)j * n], dvl[j * LD], acc);
-                            dvl[i * LD] = acc / D[i + (size_t)i * n];
-                        }
-                        for (uint32_t i = N; i--;)
-                        {
-                            double acc = dvl[i * LD];
-                            for (uint32_t j = N - 1; j > i; j--) acc = dfma(-D[j + (size_t)i * n], dvl[j * LD], acc);
-                            dvl[i * LD] = acc / D[i + (size_t)i * n];
-                        }
-                        for (uint32_t i = 0; i < rank; i++) // y~ = W t
-                        {
-                            double acc = 0.0;
-                            for (uint32_t c = i; c < N; c++) acc = dfma(w(F + i, Fc + c), dvl[c * LD], acc);
-                            yb[i * LD] = acc;
-                        }
-                        if (accum)
-                            for (uint32_t s = 0; s < m0; s++) // r~ += mu U t
+                        // PER LANE: dv = W^T y~', then L z = dv and L^T t = z in place, y~ = W t, r~ += mu U t
+                        for (uint32_t c = 0; c < N; c++) dvl[c * LD] = lane_wt_y<LD>(w, yb, F, Fc, rank, c);
+                        lane_spd_substitute<LD>(D, n, dvl, N);
+                        lane_w_t<LD>(w, yb, dvl, F, Fc, rank, N);
+                        if (reg.accum)
+                            for (uint32_t s = 0; s < m0; s++)
                             {
                                 double acc = 0.0;
                                 for (uint32_t c = 0; c < N; c++) acc = dfma(U[s + (size_t)c * m0], dvl[c * LD], acc);
@@ -1044,47 +580,11 @@ namespace lexls
                         __syncthreads(); // (every lane has read L: the next damped level overwrites D)
                     }
                 }
-                // the level's reflectors, last first (a serial chain per lane, no barrier)
-                for (uint32_t j = rank; j--;)
-                {
-                    const uint32_t rows = dim - j;
-                    const double tau    = hh[F + j];
-                    if (rows == 1 || tau == 0.0) continue; // (uniform)
-                    double *v = cbl + (F + j) * LD;
-                    double t  = 0.0;
-                    for (uint32_t i = 1; i < rows; i++) t = dfma(w(F + j + i, Fc + j), v[i * LD], t);
-                    t += v[0];
-                    v[0] = dfma(-tau, t, v[0]);
-                    for (uint32_t i = 1; i < rows; i++) v[i * LD] = dfma(-(tau * w(F + j + i, Fc + j)), t, v[i * LD]);
-                }
-            }
+                lane_reflectors_reversed<LD>(w, tau_at, cbl, F, Fc, dim, rank);
+            });
 
             // ---- (d) grad_fixed_j = gh_j - (column j of the fixed variables)^T cb, left in gh_j; then both outputs, transposed through LDS ----
-            if (grad_fixed)
-                for (uint32_t j = 0; j < nf; j++)
-                {
-                    double s = 0.0;
-                    for (uint32_t r = 0; r < M; r++) s = dfma(w(r, j), cbl[r * LD], s);
-                    ghl[j * LD] -= s;
-                }
-            __syncthreads();
-            {
-                double *out = grad_rhs + ((size_t)b * ncot + (size_t)tile * 64u) * cap;
-                for (uint32_t e = lane; e < kt * cap; e += NT)
-                {
-                    const uint32_t c = e / cap, r = e - c * cap;
-                    out[e]           = cb[r * LD + c]; // (rows behind the problem's own were never touched: 0)
-                }
-            }
-            if (grad_fixed)
-            {
-                double *out = grad_fixed + ((size_t)b * ncot + (size_t)tile * 64u) * n;
-                for (uint32_t e = lane; e < kt * n; e += NT)
-                {
-                    const uint32_t c = e / n, j = e - c * n;
-                    out[e]           = j < nf ? gh[j * LD + c] : 0.0;
-                }
-            }
+            lane_step_d<NT, LD>(w, gh, cb, grad_rhs, grad_fixed, row0, kt, n, cap, nf, M, lane);
         }
 
         // forward-mode tangents (lexls_lse_solve_tangent): the two right-hand sides from the direction, the solve map on many right-hand sides
@@ -1184,7 +684,7 @@ namespace lexls
         {
             static_assert(NT == 64, "one wavefront per (problem, tile): lane = right-hand side");
             constexpr bool STAGED = PLACE == 0, IN_WORK = PLACE == 2;
-            constexpr uint32_t LD = IN_WORK ? kTangentWorkLd : kAdjointMultiLd, AU = 4;
+            constexpr uint32_t LD = IN_WORK ? kTangentWorkLd : kAdjointMultiLd;
             extern __shared__ double smem[];
             const uint32_t b = blockIdx.x, tile = blockIdx.y, lane = threadIdx.x;
             if (b >= a.batch || tile * 64u >= ntan) return; // (block-uniform)
@@ -1249,95 +749,22 @@ namespace lexls
             else
                 __syncthreads();
             for (uint32_t i = lane; i < n; i += NT) pos_l[i] = position_after_transpositions(perm_l, T, i);
-            {
-                const size_t off = ((size_t)b * ntan + (size_t)tile * 64u) * cap; // kt rows of cap doubles, contiguous
-                for (uint32_t e = lane; e < kt * cap; e += NT)
-                {
-                    const uint32_t c = e / cap, r = e - c * cap;
-                    if (r < M) t[r * LD + c] = (r >= lo && r < hi) ? R[off + e] - Y[off + e] : R[off + e];
-                }
-            }
+            lane_load_rhs<NT, LD>(R, Y, ((size_t)b * ntan + (size_t)tile * 64u) * cap, lo, hi, t, kt, cap, M, lane);
             __syncthreads();
             double *zl = z + lane, *tl = t + lane; // this lane's column of the state
 
             // ---- (c)^T factorize()'s right-hand-side updates, levels ascending: the level's reflectors, first to last, then the Gauss step ----
-            uint32_t F = 0;
-            for (uint32_t k = 0; k < nObj; k++)
-            {
-                const uint32_t dim = dims[k];
-                const auto [rank, Fc] = kf.level(k, dim);
-                if (rank > 0 && F + dim <= M)
-                {
-                    for (uint32_t j = 0; j < rank; j++)
-                    {
-                        const uint32_t rows = dim - j;
-                        const double tau    = tau_at(F + j);
-                        if (rows == 1 || tau == 0.0) continue; // (uniform)
-                        double *v = tl + (F + j) * LD;
-                        double s  = 0.0;
-                        for (uint32_t i = 1; i < rows; i++) s = dfma(Wat(F + j + i, Fc + j), v[i * LD], s);
-                        s += v[0];
-                        v[0] = dfma(-tau, s, v[0]);
-                        for (uint32_t i = 1; i < rows; i++) v[i * LD] = dfma(-(tau * Wat(F + j + i, Fc + j)), s, v[i * LD]);
-                    }
-                    const uint32_t Fn = F + dim;
-                    if (k + 1 < nObj && Fn < M)
-                    {
-                        // the Gauss step: AU rows of the later levels share one read of the level's top (each chain in ascending column order)
-                        for (uint32_t i0 = Fn; i0 < M; i0 += AU)
-                        {
-                            double acc[AU];
-#pragma unroll
-                            for (uint32_t u = 0; u < AU; u++) acc[u] = i0 + u < M ? tl[(i0 + u) * LD] : 0.0;
-                            for (uint32_t p = 0; p < rank; p++)
-                            {
-                                const double tp = tl[(F + p) * LD];
-#pragma unroll
-                                for (uint32_t u = 0; u < AU; u++)
-                                    if (i0 + u < M) acc[u] = dfma(-Wat(i0 + u, Fc + p), tp, acc[u]);
-                            }
-#pragma unroll
-                            for (uint32_t u = 0; u < AU; u++)
-                                if (i0 + u < M) tl[(i0 + u) * LD] = acc[u];
-                        }
-                    }
-                }
-                F += dim;
-            }
+            const uint32_t rows = kf.for_levels_ascending([&](uint32_t k, uint32_t dim, uint32_t F, uint32_t rank, uint32_t Fc) __attribute__((always_inline)) {
+                lane_reflectors_forward<LD>(Wat, tau_at, tl, F, Fc, dim, rank);
+                const uint32_t Fn = F + dim;
+                if (k + 1 < nObj && Fn < M) lane_gauss<LD>(Wat, tl, F, Fn, M, Fc, rank);
+            });
 
-            // ---- (b)^T solve(), levels descending: the top of the level minus [T_k] z on the pivot columns of the later levels (descending
-            // column order, as apply_solve_map_kernel), then the triangle, last column first ----
-            uint32_t Fend = F;
-            for (uint32_t k = nObj; k--;)
-            {
-                const uint32_t dim = dims[k];
-                F                  = Fend - dim;
-                Fend               = F;
-                const auto [rank, Fc] = kf.level(k, dim);
-                if (rank == 0 || F + dim > M) continue;
-                for (uint32_t i0 = 0; i0 < rank; i0 += AU)
-                {
-                    double acc[AU];
-#pragma unroll
-                    for (uint32_t u = 0; u < AU; u++) acc[u] = i0 + u < rank ? tl[(F + i0 + u) * LD] : 0.0;
-                    for (uint32_t c = T; c > Fc + rank; c--)
-                    {
-                        const double zc = zl[(c - 1) * LD];
-#pragma unroll
-                        for (uint32_t u = 0; u < AU; u++)
-                            if (i0 + u < rank) acc[u] = dfma(-Wat(F + i0 + u, c - 1), zc, acc[u]);
-                    }
-#pragma unroll
-                    for (uint32_t u = 0; u < AU; u++)
-                        if (i0 + u < rank) tl[(F + i0 + u) * LD] = acc[u];
-                }
-                for (uint32_t j = rank; j--;)
-                {
-                    const double zc     = tl[(F + j) * LD] / Wat(F + j, Fc + j);
-                    zl[(Fc + j) * LD] = zc;
-                    for (uint32_t i = 0; i < j; i++) tl[(F + i) * LD] = dfma(-Wat(F + i, Fc + j), zc, tl[(F + i) * LD]);
-                }
-            }
+            // ---- (b)^T solve(), levels descending: the top of the level minus [T_k] z on the pivot columns of the later levels, then the
+            // triangle, last column first ----
+            kf.for_levels_descending(rows, [&](uint32_t, uint32_t, uint32_t F, uint32_t rank, uint32_t Fc) __attribute__((always_inline)) {
+                lane_back_substitute_level<LD>(Wat, tl, zl, F, Fc, rank, T);
+            });
             __syncthreads();
 
             // ---- (a)^T dx = P z, and the fixed slots: variable i takes the entry of the position it reaches by the transpositions ----
@@ -1408,12 +835,12 @@ namespace lexls
         /// per (problem, tile of 64 right-hand sides), LANE = RIGHT-HAND SIDE; lanes beyond nrhs compute on zeros and store nothing.  The forward
         /// pass of the damped solve on the kept factor alone, levels ascending; per level of rank > 0:
         ///     the level's reflectors on the lane's column t, first to last; y = t[F, F + rank)
-        ///     |f| >= 1e-15:  y' = W D^-1 (W^T y + mu U^T r)  (types 4, 5: no U; type 9: y' = f y), D = W^T W + mu U^T U + mu I, mu = f^2
+        ///     |f| >= 1e-15:  y' = W D^-1 (W^T y + mu U^T r)  (types 4, 5: no U; type 9: y' = f y), D the level's damped normal matrix, mu = f^2
         ///     types 1, 3, 8:  s = R^-1 y',  r[0, m0) -= U_R s,  r[m0, m0 + rank) = -s   (r = the right-hand-side column of the basis)
         ///     the Gauss step with y' on the rows of the later levels
-        /// then the block back-substitution and the permutation (apply_solve_map_multi_kernel's).  U = the rows [0, m0) of the null-space basis
+        /// then the block back-substitution and the permutation.  U = the rows [0, m0) of the null-space basis
         /// NS above the level's columns AS IT STANDS — the levels are walked in the order in which the basis grows, so no snapshot is kept — and
-        /// the basis takes the level's step (solve_adjoint_reg_kernel's rebuild: A side only, the factor's final column order) behind the lanes' work.
+        /// the basis takes the level's step (shared_nullspace_level: A side only, the factor's final column order) behind the lanes' work.
         ///   SHARED phases (work of the problem, lanes over entries): D and its LL^T (spd_factor<NT>), the step of NS.  EVERY TILE REPEATS THEM.
         ///   PER LANE phases: everything on t, z, r and dv ([index][lane]): the lane's own serial dfma chains in a fixed order, no cross-lane
         ///     sum — a right-hand side's bits do not depend on its lane, its tile or its neighbours.
@@ -1426,7 +853,7 @@ namespace lexls
         {
             static_assert(NT == 64, "one wavefront per (problem, tile): lane = right-hand side");
             constexpr bool MAT_LDS = PLACE == 0, IN_WORK = PLACE == 2;
-            constexpr uint32_t LD = IN_WORK ? kTangentWorkLd : kAdjointMultiLd, AU = 4;
+            constexpr uint32_t LD = IN_WORK ? kTangentWorkLd : kAdjointMultiLd;
             extern __shared__ double smem[];
             const uint32_t b = blockIdx.x, tile = blockIdx.y, lane = threadIdx.x;
             if (b >= a.batch || tile * 64u >= nrhs) return; // (block-uniform)
@@ -1434,11 +861,7 @@ namespace lexls
             const KeptFactor kf = kept_factor_of(a, b);
             const uint32_t n = kf.n, cap = kf.cap, nObj = kf.nObj, nf = kf.nf, T = kf.T, M = kf.M;
             const double *__restrict__ W = kf.W, *hh = kf.hh;
-            const uint32_t *dims = kf.dims;
-            const uint32_t type  = a.reg_type;
-            const bool accum = type == 1 || type == 3 || type == 8; // the types that accumulate NS (and read it)
-            const bool wideW = type == 1 || type == 5 || type == 8; // W = [R | T] (else R)
-            const double *fac = a.reg_factor + (size_t)b * nObj;
+            const RegularizedLevels reg = regularized_levels_of(a, b);
             const size_t per_tile = MAT_LDS ? 0 : solve_rhs_reg_matrix_doubles(n) + (IN_WORK ? solve_rhs_reg_state_doubles(n, cap, LD) : 0);
             double *wb       = MAT_LDS ? nullptr : work + ((size_t)b * gridDim.y + tile) * per_tile;
             double *state    = IN_WORK ? wb + solve_rhs_reg_matrix_doubles(n) : smem;
@@ -1449,208 +872,81 @@ namespace lexls
             double *NS = mat, *D = NS + (size_t)n * n;
             auto ns = [&](uint32_t i, uint32_t j) __attribute__((always_inline)) -> double & { return NS[i + (size_t)j * n]; };
             auto w  = [&](uint32_t i, uint32_t j) __attribute__((always_inline)) -> double { return W[i + (size_t)j * cap]; };
+            auto tau_at = [&](uint32_t r) __attribute__((always_inline)) -> double { return hh[r]; };
 
             // ---- t = R for every right-hand side of the tile, the rest of the state zero ----
             for (uint32_t i = lane; i < n; i += NT) perm_l[i] = a.perm[(size_t)b * n + i];
             for (uint32_t i = lane; i < (3 * n + cap) * LD; i += NT) state[i] = 0.0; // (dead lanes, absent rows, unreached columns: zeros)
-            if (accum)
+            if (reg.accum)
                 for (uint32_t i = lane; i < n * n; i += NT) NS[i] = 0.0;
             __syncthreads();
             for (uint32_t i = lane; i < n; i += NT) pos_l[i] = position_after_transpositions(perm_l, T, i);
-            {
-                const size_t off = ((size_t)b * nrhs + (size_t)tile * 64u) * cap; // kt rows of cap doubles, contiguous
-                for (uint32_t e = lane; e < kt * cap; e += NT)
-                {
-                    const uint32_t c = e / cap, r = e - c * cap;
-                    if (r < M) t[r * LD + c] = R[off + e];
-                }
-            }
+            lane_load_rhs<NT, LD>(R, nullptr, ((size_t)b * nrhs + (size_t)tile * 64u) * cap, 0, 0, t, kt, cap, M, lane);
             __syncthreads();
             double *tl = t + lane, *zl = z + lane, *rl = rv + lane, *dvl = dv + lane; // this lane's column of the state
 
             // ---- the forward pass of factorize()'s right-hand-side updates, levels ascending ----
-            uint32_t F = 0;
-            for (uint32_t k = 0; k < nObj; k++)
-            {
-                const uint32_t dim = dims[k];
-                const auto [rank, Fc] = kf.level(k, dim);
-                if (rank > 0 && F + dim <= M)
+            const uint32_t rows = kf.for_levels_ascending([&](uint32_t k, uint32_t dim, uint32_t F, uint32_t rank, uint32_t Fc) __attribute__((always_inline)) {
+                lane_reflectors_forward<LD>(w, tau_at, tl, F, Fc, dim, rank); // PER LANE
+                const uint32_t m0 = Fc > nf ? Fc - nf : 0, N = reg.width(n, Fc, rank);
+                double *yb        = tl + F * LD;
+                const double f    = reg.fac[k];
+                if (reg.acts(f)) // (uniform)
                 {
-                    // PER LANE: the level's reflectors, first to last
-                    for (uint32_t j = 0; j < rank; j++)
+                    if (reg.type == 9)
                     {
-                        const uint32_t rows = dim - j;
-                        const double tau    = hh[F + j];
-                        if (rows == 1 || tau == 0.0) continue; // (uniform)
-                        double *v = tl + (F + j) * LD;
-                        double s  = 0.0;
-                        for (uint32_t i = 1; i < rows; i++) s = dfma(w(F + j + i, Fc + j), v[i * LD], s);
-                        s += v[0];
-                        v[0] = dfma(-tau, s, v[0]);
-                        for (uint32_t i = 1; i < rows; i++) v[i * LD] = dfma(-(tau * w(F + j + i, Fc + j)), s, v[i * LD]);
+                        for (uint32_t i = 0; i < rank; i++) yb[i * LD] *= f;
                     }
-                    const uint32_t m0 = Fc > nf ? Fc - nf : 0, N = wideW ? n - Fc : rank;
-                    double *yb        = tl + F * LD;
-                    const double f    = fac[k];
-                    if (!(fabs(f - 0.0) < 1e-15)) // the gate of regularize_level (uniform)
+                    else
                     {
-                        if (type == 9)
-                        {
-                            for (uint32_t i = 0; i < rank; i++) yb[i * LD] *= f;
-                        }
-                        else
-                        {
-                            const double mu = f * f;
-                            // SHARED: D = W^T W + mu U^T U + mu I (lower triangle; column c of W has min(c + 1, rank) rows) and its LL^T
-                            for (uint32_t e = lane; e < N * N; e += NT)
-                            {
-                                const uint32_t i = e % N, j = e / N;
-                                if (i < j) continue;
-                                const uint32_t len = j < rank ? j + 1 : rank;
-                                double acc = 0.0;
-                                for (uint32_t r = 0; r < len; r++) acc = dfma(w(F + r, Fc + i), w(F + r, Fc + j), acc);
-                                if (accum)
-                                {
-                                    double up = 0.0;
-                                    for (uint32_t s = 0; s < m0; s++) up = dfma(ns(s, Fc + i), ns(s, Fc + j), up);
-                                    acc = dfma(mu, up, acc);
-                                }
-                                D[i + (size_t)j * n] = i == j ? acc + mu : acc;
-                            }
-                            __syncthreads();
-                            spd_factor<NT>(D, n, N, lane); // (ends in a barrier: every lane reads all of L from here on)
-                            // PER LANE: dv = W^T y + mu U^T r, then L q = dv and L^T p = q in place, row by row against the shared factor
-                            for (uint32_t c = 0; c < N; c++)
-                            {
-                                const uint32_t len = c < rank ? c + 1 : rank;
-                                double acc = 0.0;
-                                for (uint32_t r = 0; r < len; r++) acc = dfma(w(F + r, Fc + c), yb[r * LD], acc);
-                                if (accum)
-                                {
-                                    double up = 0.0;
-                                    for (uint32_t s = 0; s < m0; s++) up = dfma(ns(s, Fc + c), rl[s * LD], up);
-                                    acc = dfma(mu, up, acc);
-                                }
-                                dvl[c * LD] = acc;
-                            }
-                            for (uint32_t i = 0; i < N; i++)
-                            {
-                                double acc = dvl[i * LD];
-                                for (uint32_t j = 0; j < i; j++) acc = dfma(-D[i + (size_t)j * n], dvl[j * LD], acc);
-                                dvl[i * LD] = acc / D[i + (size_t)i * n];
-                            }
-                            for (uint32_t i = N; i--;)
-                            {
-                                double acc = dvl[i * LD];
-                                for (uint32_t j = N - 1; j > i; j--) acc = dfma(-D[j + (size_t)i * n], dvl[j * LD], acc);
-                                dvl[i * LD] = acc / D[i + (size_t)i * n];
-                            }
-                            for (uint32_t i = 0; i < rank; i++) // y' = W p
-                            {
-                                double acc = 0.0;
-                                for (uint32_t c = i; c < N; c++) acc = dfma(w(F + i, Fc + c), dvl[c * LD], acc);
-                                yb[i * LD] = acc;
-                            }
-                        }
-                    }
-                    if (accum)
-                    {
-                        // PER LANE: s = R^-1 y' (into dv, last row first), r[0, m0) -= U_R s, r[m0, m0 + rank) = -s
-                        for (uint32_t j = rank; j--;)
-                        {
-                            double acc = yb[j * LD];
-                            for (uint32_t q = j + 1; q < rank; q++) acc = dfma(-w(F + j, Fc + q), dvl[q * LD], acc);
-                            dvl[j * LD] = acc / w(F + j, Fc + j);
-                        }
-                        for (uint32_t s = 0; s < m0; s++)
-                        {
-                            double acc = rl[s * LD];
-                            for (uint32_t j = 0; j < rank; j++) acc = dfma(-ns(s, Fc + j), dvl[j * LD], acc);
-                            rl[s * LD] = acc;
-                        }
-                        for (uint32_t j = 0; j < rank; j++) rl[(m0 + j) * LD] = -dvl[j * LD];
-                    }
-                    __syncthreads(); // (every lane has read L and U: the step of NS and the next damped level overwrite them)
-                    if (accum)
-                    {
-                        // SHARED: the level's step of NS (reg_accumulate_nullspace without the right-hand-side column)
-                        const uint32_t rows = m0 + rank, RC = n - Fc - rank;
-                        for (uint32_t e = lane; e < rank * rank; e += NT) ns(m0 + e % rank, Fc + e / rank) = (e % rank == e / rank) ? 1.0 : 0.0;
+                        const double mu = f * f;
+                        // SHARED: D (U = the basis in place) and its LL^T
+                        shared_damped_normal_matrix<NT>(w, NS + (size_t)Fc * n, n, reg.accum, mu, D, n, F, Fc, rank, N, m0, lane);
                         __syncthreads();
-                        for (uint32_t i = lane; i < rows; i += NT) // Left <- Left R^-1, a row per lane
-                            for (uint32_t p = 0; p < rank; p++)
-                            {
-                                double sv = ns(i, Fc + p);
-                                for (uint32_t q = 0; q < p; q++) sv = dfma(-ns(i, Fc + q), w(F + q, Fc + p), sv);
-                                ns(i, Fc + p) = sv / w(F + p, Fc + p);
-                            }
-                        __syncthreads();
-                        for (uint32_t e = lane; e < rows * RC; e += NT) // Trailing -= Left T
+                        spd_factor<NT>(D, n, N, lane); // (ends in a barrier: every lane reads all of L from here on)
+                        // PER LANE: dv = W^T y + mu U^T r, then L q = dv and L^T p = q in place, y' = W p
+                        for (uint32_t c = 0; c < N; c++)
                         {
-                            const uint32_t i = e % rows, c = Fc + rank + e / rows;
-                            double tv = ns(i, c);
-                            for (uint32_t p = 0; p < rank; p++) tv = dfma(-ns(i, Fc + p), w(F + p, c), tv);
-                            ns(i, c) = tv;
-                        }
-                        __syncthreads();
-                    }
-                    const uint32_t Fn = F + dim;
-                    if (k + 1 < nObj && Fn < M)
-                    {
-                        // PER LANE: the Gauss step, AU rows of the later levels share one read of the level's top (ascending column order)
-                        for (uint32_t i0 = Fn; i0 < M; i0 += AU)
-                        {
-                            double acc[AU];
-#pragma unroll
-                            for (uint32_t u = 0; u < AU; u++) acc[u] = i0 + u < M ? tl[(i0 + u) * LD] : 0.0;
-                            for (uint32_t p = 0; p < rank; p++)
+                            double acc = lane_wt_y<LD>(w, yb, F, Fc, rank, c);
+                            if (reg.accum)
                             {
-                                const double tp = tl[(F + p) * LD];
-#pragma unroll
-                                for (uint32_t u = 0; u < AU; u++)
-                                    if (i0 + u < M) acc[u] = dfma(-w(i0 + u, Fc + p), tp, acc[u]);
+                                double up = 0.0;
+                                for (uint32_t s = 0; s < m0; s++) up = dfma(ns(s, Fc + c), rl[s * LD], up);
+                                acc = dfma(mu, up, acc);
                             }
-#pragma unroll
-                            for (uint32_t u = 0; u < AU; u++)
-                                if (i0 + u < M) tl[(i0 + u) * LD] = acc[u];
+                            dvl[c * LD] = acc;
                         }
+                        lane_spd_substitute<LD>(D, n, dvl, N);
+                        lane_w_t<LD>(w, yb, dvl, F, Fc, rank, N);
                     }
                 }
-                F += dim;
-            }
+                if (reg.accum)
+                {
+                    // PER LANE: s = R^-1 y' (into dv, last row first), r[0, m0) -= U_R s, r[m0, m0 + rank) = -s
+                    for (uint32_t j = rank; j--;)
+                    {
+                        double acc = yb[j * LD];
+                        for (uint32_t q = j + 1; q < rank; q++) acc = dfma(-w(F + j, Fc + q), dvl[q * LD], acc);
+                        dvl[j * LD] = acc / w(F + j, Fc + j);
+                    }
+                    for (uint32_t s = 0; s < m0; s++)
+                    {
+                        double acc = rl[s * LD];
+                        for (uint32_t j = 0; j < rank; j++) acc = dfma(-ns(s, Fc + j), dvl[j * LD], acc);
+                        rl[s * LD] = acc;
+                    }
+                    for (uint32_t j = 0; j < rank; j++) rl[(m0 + j) * LD] = -dvl[j * LD];
+                }
+                __syncthreads(); // (every lane has read L and U: the step of NS and the next damped level overwrite them)
+                if (reg.accum) shared_nullspace_level<NT>(w, NS, n, F, Fc, m0, rank, lane); // SHARED: the basis takes the level's step
+                const uint32_t Fn = F + dim;
+                if (k + 1 < nObj && Fn < M) lane_gauss<LD>(w, tl, F, Fn, M, Fc, rank); // PER LANE
+            });
 
-            // ---- solve(), levels descending (apply_solve_map_multi_kernel's step (b)^T on the damped right-hand sides), per lane ----
-            uint32_t Fend = F;
-            for (uint32_t k = nObj; k--;)
-            {
-                const uint32_t dim = dims[k];
-                F                  = Fend - dim;
-                Fend               = F;
-                const auto [rank, Fc] = kf.level(k, dim);
-                if (rank == 0 || F + dim > M) continue;
-                for (uint32_t i0 = 0; i0 < rank; i0 += AU)
-                {
-                    double acc[AU];
-#pragma unroll
-                    for (uint32_t u = 0; u < AU; u++) acc[u] = i0 + u < rank ? tl[(F + i0 + u) * LD] : 0.0;
-                    for (uint32_t c = T; c > Fc + rank; c--)
-                    {
-                        const double zc = zl[(c - 1) * LD];
-#pragma unroll
-                        for (uint32_t u = 0; u < AU; u++)
-                            if (i0 + u < rank) acc[u] = dfma(-w(F + i0 + u, c - 1), zc, acc[u]);
-                    }
-#pragma unroll
-                    for (uint32_t u = 0; u < AU; u++)
-                        if (i0 + u < rank) tl[(F + i0 + u) * LD] = acc[u];
-                }
-                for (uint32_t j = rank; j--;)
-                {
-                    const double zc   = tl[(F + j) * LD] / w(F + j, Fc + j);
-                    zl[(Fc + j) * LD] = zc;
-                    for (uint32_t i = 0; i < j; i++) tl[(F + i) * LD] = dfma(-w(F + i, Fc + j), zc, tl[(F + i) * LD]);
-                }
-            }
+            // ---- solve(), levels descending, on the damped right-hand sides, per lane ----
+            kf.for_levels_descending(rows, [&](uint32_t, uint32_t, uint32_t F, uint32_t rank, uint32_t Fc) __attribute__((always_inline)) {
+                lane_back_substitute_level<LD>(w, tl, zl, F, Fc, rank, T);
+            });
             __syncthreads();
 
             // ---- x = P z, and the fixed slots ----

@@ -1,6 +1,7 @@
 // The kept factor of a LexLSE solve as the kernels behind it read it: the per-problem view, the rule for how far a level's stored rank may be
-// trusted, and the steps that more than one of those kernels takes (lse_adjoint.hip: the adjoint family; lse_postfactor.hip: sensitivity_kernel
-// stages the factor with stage_factor).  trusted_rank is plain C++ as well (tests/kept_factor_check.cpp runs the very same rule on the host).
+// trusted, the walk over the levels a kernel works on, and the wavefront-wide helpers that more than one of those kernels takes (lse_adjoint.hip:
+// the adjoint family, whose steps on top of these are stated once in lse_kept_steps.h; lse_postfactor.hip: sensitivity_kernel stages the factor
+// with stage_factor).  trusted_rank is plain C++ as well (tests/kept_factor_check.cpp runs the very same rule on the host).
 #pragma once
 #include <cstdint>
 
@@ -40,6 +41,40 @@ namespace lexls
         struct Level { uint32_t rank, Fc; };
         /// level k (of dim rows): its rank as the loops may trust it (trusted_rank) and its first column
         __device__ __forceinline__ Level level(uint32_t k, uint32_t dim) const { return {trusted_rank(n, nf, T, dim, rk + k, fc[k]), fc[k]}; }
+        /// THE LEVEL WALK: body(k, dim, F, rank, Fc) for every level a kernel works on — rank > 0 and all of its rows F .. F + dim among the
+        /// problem's own — first to last; body is an always-inlined callable (it may hold workgroup-uniform barriers: the walk is uniform).
+        /// Returns the sum of all the levels' rows (not held to cap): where the walk from the last level starts
+        template <class BODY>
+        __device__ __forceinline__ uint32_t for_levels_ascending(const BODY &body) const
+        {
+            uint32_t F = 0;
+            for (uint32_t k = 0; k < nObj; k++)
+            {
+                const uint32_t dim = dims[k];
+                const Level lv     = level(k, dim);
+                if (lv.rank > 0 && F + dim <= M) body(k, dim, F, lv.rank, lv.Fc);
+                F += dim;
+            }
+            return F;
+        }
+        /// the same levels, last to first; Fend = the sum of all the levels' rows (for_levels_ascending's, or total_rows())
+        __device__ __forceinline__ uint32_t total_rows() const
+        {
+            uint32_t Fend = 0;
+            for (uint32_t k = 0; k < nObj; k++) Fend += dims[k];
+            return Fend;
+        }
+        template <class BODY>
+        __device__ __forceinline__ void for_levels_descending(uint32_t Fend, const BODY &body) const
+        {
+            for (uint32_t k = nObj; k--;)
+            {
+                const uint32_t dim = dims[k], F = Fend - dim;
+                Fend               = F;
+                const Level lv     = level(k, dim);
+                if (lv.rank > 0 && F + dim <= M) body(k, dim, F, lv.rank, lv.Fc);
+            }
+        }
     };
     __device__ __forceinline__ KeptFactor kept_factor_of(const LseArgs &a, uint32_t b)
     {

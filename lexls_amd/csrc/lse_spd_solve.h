@@ -1,7 +1,8 @@
 // The dense symmetric positive-definite solve of the LexLSE device code — THE ONLY IMPLEMENTATION: LL^T of a lower triangle in place, then
 // L y = d, then L^T z = y in place (oracle: cholesky_solve).  Its consumers: the regularization family (lexls_regularize.h), the adjoint of
-// regularized solves (lse_adjoint.hip), solveLeastNorm_2 and _3 (lse_postfactor.hip); spd_factor<NT> is the factorization alone, for the
-// many-cotangent adjoint of regularized solves, which substitutes per lane.  Two forms behind one entry, spd_solve<NT>; both do the same
+// regularized solves (solve_adjoint_reg_kernel, lse_adjoint.hip), solveLeastNorm_2 and _3 (lse_postfactor.hip); spd_factor<NT> is the
+// factorization alone, for the lane = vector kernels on regularized factors (solve_adjoint_reg_multi_kernel, apply_solve_map_reg_multi_kernel),
+// which substitute per lane in the same order (lane_spd_substitute, lse_kept_steps.h).  Two forms behind one entry, spd_solve<NT>; both do the same
 // operations on the same operands in the same order (entry (i, j) receives the products k = 0 .. j-1 in that order; the substitutions go
 // column by column), so the results are the same bits whichever form runs.
 #pragma once
@@ -118,8 +119,8 @@ namespace lexls
             }
         }
 
-        /// THE FACTORIZATION ALONE, for a consumer that substitutes for itself (solve_adjoint_reg_multi_kernel: one substitution pair per lane
-        /// against the shared factor): LL^T of the lower triangle of D in place — the very operations spd_solve<NT> does before its substitutions,
+        /// THE FACTORIZATION ALONE, for a consumer that substitutes for itself (lane_spd_substitute, lse_kept_steps.h: one substitution pair per
+        /// lane against the shared factor): LL^T of the lower triangle of D in place — the very operations spd_solve<NT> does before its substitutions,
         /// in either form — and a barrier behind it (workgroup-uniform; the last statement for N > 0): every thread may then read all of L
         template <int NT>
         __device__ __forceinline__ void spd_factor(double *D, uint32_t ldd, uint32_t N, uint32_t tid)
