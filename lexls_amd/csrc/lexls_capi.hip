@@ -35,6 +35,60 @@ namespace
 
 #define CHECK_HANDLE(h) \
     if (!(h)) return fail(LEXLS_ERR_INVALID, "null handle")
+
+    /// a device buffer that only grows: what the kept-factor calls (lse_kept_capi.h) keep in the handle between calls
+    struct DeviceBuffer
+    {
+        void *ptr    = nullptr;
+        size_t bytes = 0;
+        /// room for `need` bytes: a buffer that holds fewer is freed (which waits for whatever still reads it) and made anew, its contents lost
+        hipError_t reserve(size_t need)
+        {
+            if (need <= bytes) return hipSuccess;
+            release();
+            hipError_t e = hipMalloc(&ptr, need);
+            if (e != hipSuccess) ptr = nullptr;
+            else bytes = need;
+            return e;
+        }
+        void release()
+        {
+            if (ptr) (void)hipFree(ptr);
+            ptr = nullptr, bytes = 0;
+        }
+        template <class T> T *as() const { return static_cast<T *>(ptr); }
+    };
+
+    /// what the host form of a kept-factor call leaves in the handle for its getter: three device buffers (the call's input, then its results) with
+    /// room for `room` items, the `count` items of the last call, and the factor_epoch they belong to
+    struct HostResults
+    {
+        DeviceBuffer buf[3];
+        uint32_t room = 0, count = 0;
+        bool valid     = false;
+        uint64_t epoch = 0;
+        struct Copy { void *dst; const void *src; size_t bytes; };
+        /// room for n items, bytes[i] in buffer i: more than the buffers hold drops the results, frees all three and makes all three
+        hipError_t make_room(uint32_t n, const size_t (&bytes)[3])
+        {
+            if (n <= room) return hipSuccess;
+            valid = false, room = 0;
+            release();
+            for (int i = 0; i < 3; i++)
+                if (hipError_t e = buf[i].reserve(bytes[i])) return e;
+            room = n;
+            return hipSuccess;
+        }
+        /// after a successful run on the buffers
+        void stamp(uint32_t n, uint64_t factor_epoch) { valid = true, count = n, epoch = factor_epoch; }
+        /// `getter`: the results of the last `call`, while they belong to the factor, to the host (a null dst is skipped)
+        int fetch(lexls_lse_s *h, const char *getter, const char *call, std::initializer_list<Copy> copies) const;
+        void release()
+        {
+            for (DeviceBuffer &b : buf) b.release();
+        }
+        template <class T> T *at(int i) const { return buf[i].as<T>(); }
+    };
 } // namespace
 
 struct lexls_lse_s
@@ -91,45 +145,22 @@ struct lexls_lse_s
     bool mult_valid       = false;
     uint64_t mult_epoch   = 0;      // factor_epoch the multipliers belong to
     bool mult_swept       = false;
-    // lexls_lse_solve_adjoint: g (batch x nVar), grad_rhs (batch x cap), grad_fixed (batch x nVar), allocated at its first call
-    // d_adj_work: the matrices of the regularized adjoint where they do not fit in LDS (adjoint_reg_work_bytes)
-    double *d_adj_g = nullptr, *d_adj_rhs = nullptr, *d_adj_fixed = nullptr, *d_adj_work = nullptr;
-    bool adj_valid     = false;
-    bool adj_regularized = false; // lexls_lse_set_adjoint_regularized: the single-cotangent calls serve damped factorizations (off: UNSUPPORTED, as before)
-    uint64_t adj_epoch = 0; // factor_epoch the gradients belong to
-    // lexls_lse_solve_adjoint_multi: G (batch x ncot x nVar), grad_rhs (batch x ncot x cap), grad_fixed (batch x ncot x nVar) of a host caller, made
-    // for the largest ncot so far; d_adjm_work: the buffers of the per-cotangent form (launch_solve_adjoint_multi), made at the first call that needs them
-    // d_adjrm_work: the matrices of the regularized multi kernel where they do not fit in LDS (adjoint_reg_multi_work_bytes), with room for adjrm_tiles tiles
-    double *d_adjm_G = nullptr, *d_adjm_rhs = nullptr, *d_adjm_fixed = nullptr, *d_adjm_work = nullptr, *d_adjrm_work = nullptr;
-    uint32_t adjrm_tiles      = 0;
+    // the kept-factor calls (lse_kept_capi.h).  A HostResults per family holds what its host form uploads and leaves for its getter, buffers in this order:
+    //   adj   lexls_lse_solve_adjoint         g (batch x nVar) | grad_rhs (batch x cap) | grad_fixed (batch x nVar)
+    //   adjm  lexls_lse_solve_adjoint_multi   G (batch x ncot x nVar) | grad_rhs (batch x ncot x cap) | grad_fixed (batch x ncot x nVar)
+    //   adjA  lexls_lse_solve_adjoint_matrix  g (batch x nVar) | the gradient (batch x (nVar + 1) x cap) | the flags (batch)
+    //   tan   lexls_lse_solve_tangent         the directions (ntan x batch x (nVar + 1) x cap | ntan x batch x nVar) | dx (ntan x batch x nVar); tan_flag: its flags (batch)
+    //   srhs  lexls_lse_solve_rhs             the right-hand sides (nrhs x batch x cap) | fixed values | solutions (nrhs x batch x nVar)
+    // made for the largest count so far (adj, adjA: one).  The work buffers both forms of a call run on, each made when a call first needs it:
+    //   adj_work    the matrices of the regularized adjoint where they do not fit in LDS (adjoint_reg_work_bytes)
+    //   adjm_work   the buffers of the per-cotangent form (adjoint_multi_work_bytes); the tangents' M^T w runs on them too
+    //   adjrm_work  the matrices of the regularized multi kernel where they do not fit in LDS (adjoint_reg_multi_work_bytes): grows with the tiles of 64 cotangents
+    //   adjA_work   the chain of launch_solve_adjoint_matrix (adjoint_matrix_work_bytes)
+    //   tan_work, srhs_work  the chains of launch_solve_tangent and launch_solve_rhs: grow with the count, and with the placement
+    HostResults adj, adjm, adjA, tan, srhs;
+    DeviceBuffer adj_work, adjm_work, adjrm_work, adjA_work, tan_flag, tan_work, srhs_work;
+    bool adj_regularized       = false; // lexls_lse_set_adjoint_regularized: the single-cotangent calls serve damped factorizations (off: UNSUPPORTED, as before)
     bool adj_regularized_multi = false; // lexls_lse_set_adjoint_regularized_multi: the multi-cotangent calls serve damped factorizations (off: UNSUPPORTED, as before)
-    uint32_t adjm_room = 0, adjm_ncot = 0; // cotangents the three buffers have room for; cotangents of the last lexls_lse_solve_adjoint_multi
-    bool adjm_valid     = false;
-    uint64_t adjm_epoch = 0;
-    // lexls_lse_solve_adjoint_matrix: g (batch x nVar), the gradient (batch x (nVar + 1) x cap) and the flags (batch) of a host caller, the work
-    // buffers of the chain (launch_solve_adjoint_matrix), all made at the first call that needs them
-    double *d_adjA_g = nullptr, *d_adjA_grad = nullptr;
-    uint8_t *d_adjA_flag = nullptr;
-    void *d_adjA_work    = nullptr;
-    bool adjA_valid      = false;
-    uint64_t adjA_epoch  = 0;
-    // lexls_lse_solve_tangent: the directions (ntan x batch x (nVar + 1) x cap, ntan x batch x nVar), dx (ntan x batch x nVar) and the flags (batch)
-    // of a host caller, made for the largest ntan so far; d_tan_work: the work buffers of the chain (launch_solve_tangent), likewise
-    double *d_tan_dlod = nullptr, *d_tan_dfixed = nullptr, *d_tan_dx = nullptr;
-    uint8_t *d_tan_flag = nullptr;
-    void *d_tan_work    = nullptr;
-    uint32_t tan_room = 0, tan_ntan = 0; // tangents the host buffers have room for; tangents of the last host call
-    size_t tan_work_bytes = 0;           // bytes of d_tan_work
-    bool tan_valid     = false;
-    uint64_t tan_epoch = 0;
-    // lexls_lse_solve_rhs: the right-hand sides (nrhs x batch x cap), fixed values and solutions (nrhs x batch x nVar) of a host caller, made for the
-    // largest nrhs so far; d_srhs_work: the work buffer of the chain (launch_solve_rhs), likewise
-    double *d_srhs_rhs = nullptr, *d_srhs_fixed = nullptr, *d_srhs_x = nullptr;
-    void *d_srhs_work   = nullptr;
-    uint32_t srhs_room = 0, srhs_nrhs = 0; // right-hand sides the host buffers have room for; right-hand sides of the last host call
-    size_t srhs_work_bytes = 0;            // bytes of d_srhs_work
-    bool srhs_valid     = false;
-    uint64_t srhs_epoch = 0;
     // accuracy guard (lexls_lse_set_accuracy_guard): mode 0 off, 1 report, 2 report + re-solve; arrays allocated when first switched on
     int guard_mode           = 0;
     double guard_threshold   = 0.0;
@@ -324,11 +355,11 @@ extern "C"
         (void)hipSetDevice(h->device);
         void *ptrs[] = {h->d_in_owned, h->d_fac, h->d_hh, h->d_v, h->d_lambda, h->d_scratch, h->d_perm, h->d_rank, h->d_fcol, h->d_round_in, h->d_round_out,
                         h->d_large_state, h->d_large_ws, h->d_norms, h->d_cdata, h->d_reg_factor, h->d_reg_scratch, h->d_reg_mu, h->d_resume_level, h->d_resume_state,
-                        h->d_guard_est, h->d_guard_status, h->d_guard_ind, h->d_mult, h->d_mult_scratch, h->d_wrong_sign, h->d_adj_g, h->d_adj_rhs, h->d_adj_fixed,
-                        h->d_adj_work, h->d_adjm_G, h->d_adjm_rhs, h->d_adjm_fixed, h->d_adjm_work, h->d_adjrm_work, h->d_adjA_g, h->d_adjA_grad, h->d_adjA_flag, h->d_adjA_work,
-                        h->d_tan_dlod, h->d_tan_dfixed, h->d_tan_dx, h->d_tan_flag, h->d_tan_work, h->d_srhs_rhs, h->d_srhs_fixed, h->d_srhs_x, h->d_srhs_work};
+                        h->d_guard_est, h->d_guard_status, h->d_guard_ind, h->d_mult, h->d_mult_scratch, h->d_wrong_sign};
         for (void *p : ptrs)
             if (p) (void)hipFree(p);
+        h->adj.release(), h->adj_work.release(), h->adjm.release(), h->adjm_work.release(), h->adjrm_work.release(), h->adjA.release(), h->adjA_work.release();
+        h->tan.release(), h->tan_flag.release(), h->tan_work.release(), h->srhs.release(), h->srhs_work.release();
         if (h->h_dims_pinned) (void)hipHostFree(h->h_dims_pinned);
         if (h->dims_event) (void)hipEventDestroy(h->dims_event);
         delete h;
@@ -1056,409 +1087,6 @@ extern "C"
         return LEXLS_OK;
     }
 
-    /// what every form of the adjoint checks before any device work: a kept factor — unregularized, or (AdjointCall::single: lexls_lse_solve_adjoint
-    /// and its device form, once lexls_lse_set_adjoint_regularized switched it on; AdjointCall::multi: the multi-cotangent calls, once
-    /// lexls_lse_set_adjoint_regularized_multi did) regularized with one of the types whose damped solve is an affine map of the kept factor, the
-    /// factors constant
-    enum class AdjointCall { other, single, multi };
-    static int need_adjoint_factor(lexls_lse_t h, const char *who, const void *g, AdjointCall call = AdjointCall::other)
-    {
-        CHECK_HANDLE(h);
-        if (!g) return fail(LEXLS_ERR_INVALID, std::string(who) + ": null g");
-        if (int rc = need_factor(h, who)) return rc;
-        if (h->reg_type == 0) return LEXLS_OK;
-        if (call == AdjointCall::other)
-            return fail(LEXLS_ERR_UNSUPPORTED, std::string(who) + ": the factorization ran with regularization_type != 0 (lexls_lse_solve_adjoint, the single-cotangent call, serves "
-                                                                  "regularization types 1, 3, 4, 5, 8 and 9; this call serves none)");
-        if (call == AdjointCall::multi && !h->adj_regularized_multi)
-            return fail(LEXLS_ERR_UNSUPPORTED, std::string(who) + ": the factorization ran with regularization_type != 0 and the many-cotangent adjoint of damped solves is not "
-                                                                  "switched on for this handle (lexls_lse_set_adjoint_regularized_multi; it serves regularization types 1, 3, 4, 5, 8 "
-                                                                  "and 9, as lexls_lse_solve_adjoint, the single-cotangent call, does under lexls_lse_set_adjoint_regularized)");
-        if (call == AdjointCall::single && !h->adj_regularized)
-            return fail(LEXLS_ERR_UNSUPPORTED, std::string(who) + ": the factorization ran with regularization_type != 0 and the adjoint of damped solves is not switched on "
-                                                                  "for this handle (lexls_lse_set_adjoint_regularized; it serves regularization types 1, 3, 4, 5, 8 and 9)");
-        if (!adjoint_reg_serves(h->reg_type))
-            return fail(LEXLS_ERR_UNSUPPORTED, std::string(who) + ": regularization_type " + std::to_string(h->reg_type) +
-                                                   " is not an affine map of the right-hand side (the CG types 2 and 6 iterate from x = 0, type 7 is experimental); served: 1, 3, 4, 5, 8, 9");
-        if (h->reg_variable != 0.0)
-            return fail(LEXLS_ERR_UNSUPPORTED, std::string(who) + ": variable_regularization_factor != 0 under regularization_type " + std::to_string(h->reg_type) +
-                                                   " (the factor depends on the right-hand side: x is not an affine map of it)");
-        return LEXLS_OK;
-    }
-    /// the work buffer of the regularized adjoint where its matrices do not fit in LDS (adjoint_reg_work_bytes), made at the first call that needs it
-    static int adjoint_reg_work(lexls_lse_t h)
-    {
-        const size_t bytes = adjoint_reg_work_bytes(h->args());
-        if (bytes && !h->d_adj_work) HIP_TRY(hipMalloc((void **)&h->d_adj_work, bytes));
-        return LEXLS_OK;
-    }
-
-    int lexls_lse_set_adjoint_regularized(lexls_lse_t h, int on)
-    {
-        CHECK_HANDLE(h);
-        h->adj_regularized = on != 0;
-        return LEXLS_OK;
-    }
-
-    int lexls_lse_set_adjoint_regularized_multi(lexls_lse_t h, int on)
-    {
-        CHECK_HANDLE(h);
-        h->adj_regularized_multi = on != 0;
-        return LEXLS_OK;
-    }
-
-    /// the host form of an adjoint call, ahead of the function its device form runs too (whose checks it has run before it touches h or h_g): h_g into the handle's buffer
-    static int upload_adjoint_g(lexls_lse_t h, double *d_g, const double *h_g, size_t bytes)
-    {
-        HIP_TRY(hipMemcpyAsync(d_g, h_g, bytes, hipMemcpyHostToDevice, h->stream));
-        if (!h->deferred_sync) HIP_TRY(hipStreamSynchronize(h->stream)); // h_g may be reused by the caller
-        return LEXLS_OK;
-    }
-    /// lexls_lse_get_adjoint, _multi and _matrix (family: "", "_multi", "_matrix"): the results of the host form's last call, while they belong to the factor
-    struct AdjointCopy { void *dst; const void *src; size_t bytes; };
-    static int get_adjoint_results(lexls_lse_t h, const char *family, bool valid, uint64_t epoch, std::initializer_list<AdjointCopy> copies)
-    {
-        const std::string who = std::string("lexls_lse_get_adjoint") + family, call = std::string("lexls_lse_solve_adjoint") + family;
-        if (!valid) return fail(LEXLS_ERR_INVALID, who + ": call " + call + " first");
-        if (!h->factor_valid || epoch != h->factor_epoch) return fail(LEXLS_ERR_INVALID, who + ": the problem or its factorization changed since " + call + " (call it again)");
-        HIP_TRY(hipSetDevice(h->device));
-        for (const AdjointCopy &c : copies)
-            if (c.dst) HIP_TRY(hipMemcpyAsync(c.dst, c.src, c.bytes, hipMemcpyDeviceToHost, h->stream));
-        if (!h->deferred_sync) HIP_TRY(hipStreamSynchronize(h->stream));
-        return LEXLS_OK;
-    }
-
-    /// every form of lexls_lse_solve_adjoint on device memory: the checks, the work buffer, the launch
-    static int run_solve_adjoint(lexls_lse_t h, const char *who, const double *d_g, double *d_grad_rhs, double *d_grad_fixed)
-    {
-        if (int rc = need_adjoint_factor(h, who, d_g, AdjointCall::single)) return rc;
-        if (!d_grad_rhs) return fail(LEXLS_ERR_INVALID, std::string(who) + ": null d_grad_rhs");
-        HIP_TRY(hipSetDevice(h->device));
-        if (int rc = adjoint_reg_work(h)) return rc;
-        HIP_TRY(launch_solve_adjoint(h->args(), d_g, d_grad_rhs, d_grad_fixed, h->stream, &h->last_consumer, h->d_adj_work));
-        return LEXLS_OK;
-    }
-
-    int lexls_lse_solve_adjoint(lexls_lse_t h, const double *h_g)
-    {
-        const char *who = "lexls_lse_solve_adjoint";
-        if (int rc = need_adjoint_factor(h, who, h_g, AdjointCall::single)) return rc;
-        HIP_TRY(hipSetDevice(h->device));
-        const size_t B = h->batch, n = h->nVar, cap = h->cap;
-        if (!h->d_adj_g) HIP_TRY(hipMalloc((void **)&h->d_adj_g, 8 * B * n));
-        if (!h->d_adj_rhs) HIP_TRY(hipMalloc((void **)&h->d_adj_rhs, 8 * B * cap));
-        if (!h->d_adj_fixed) HIP_TRY(hipMalloc((void **)&h->d_adj_fixed, 8 * B * n));
-        if (int rc = upload_adjoint_g(h, h->d_adj_g, h_g, 8 * B * n)) return rc;
-        if (int rc = run_solve_adjoint(h, who, h->d_adj_g, h->d_adj_rhs, h->d_adj_fixed)) return rc;
-        h->adj_valid = true;
-        h->adj_epoch = h->factor_epoch;
-        return LEXLS_OK;
-    }
-
-    int lexls_lse_solve_adjoint_device(lexls_lse_t h, const double *d_g, double *d_grad_rhs, double *d_grad_fixed)
-    {
-        return run_solve_adjoint(h, "lexls_lse_solve_adjoint_device", d_g, d_grad_rhs, d_grad_fixed);
-    }
-
-    int lexls_lse_get_adjoint(lexls_lse_t h, double *h_grad_rhs, double *h_grad_fixed)
-    {
-        CHECK_HANDLE(h);
-        return get_adjoint_results(h, "", h->adj_valid, h->adj_epoch,
-                                   {{h_grad_rhs, h->d_adj_rhs, 8 * (size_t)h->batch * h->cap}, {h_grad_fixed, h->d_adj_fixed, 8 * (size_t)h->batch * h->nVar}});
-    }
-
-    /// what both multi-cotangent forms check before any device work
-    static int need_adjoint_multi(lexls_lse_t h, const char *who, const void *G, uint32_t ncot)
-    {
-        CHECK_HANDLE(h);
-        if (!G) return fail(LEXLS_ERR_INVALID, std::string(who) + ": null G");
-        if (ncot == 0) return fail(LEXLS_ERR_INVALID, std::string(who) + ": ncot == 0");
-        return need_adjoint_factor(h, who, G, AdjointCall::multi);
-    }
-    /// every form of lexls_lse_solve_adjoint_multi on device memory: the checks, the work buffer, the launch
-    static int run_solve_adjoint_multi(lexls_lse_t h, const char *who, const double *d_G, uint32_t ncot, double *d_grad_rhs, double *d_grad_fixed)
-    {
-        if (int rc = need_adjoint_multi(h, who, d_G, ncot)) return rc;
-        if (!d_grad_rhs) return fail(LEXLS_ERR_INVALID, std::string(who) + ": null d_grad_rhs");
-        HIP_TRY(hipSetDevice(h->device));
-        const size_t bytes = adjoint_multi_work_bytes(h->args());
-        if (bytes && !h->d_adjm_work) HIP_TRY(hipMalloc((void **)&h->d_adjm_work, bytes));
-        if (bytes) // (the per-cotangent form runs lexls_lse_solve_adjoint's launch: a regularized factor may want its work buffer)
-            if (int rc = adjoint_reg_work(h)) return rc;
-        const uint32_t tiles = (ncot + 63u) / 64u;
-        if (adjoint_reg_multi_work_bytes(h->args(), ncot) && tiles > h->adjrm_tiles) // the matrices of the hbm form, for the most tiles so far
-        {
-            if (h->d_adjrm_work) (void)hipFree(h->d_adjrm_work); // (waits for whatever still reads it)
-            h->d_adjrm_work = nullptr, h->adjrm_tiles = 0;
-            HIP_TRY(hipMalloc((void **)&h->d_adjrm_work, adjoint_reg_multi_work_bytes(h->args(), ncot)));
-            h->adjrm_tiles = tiles;
-        }
-        HIP_TRY(launch_solve_adjoint_multi(h->args(), d_G, ncot, d_grad_rhs, d_grad_fixed, h->d_adjm_work, h->stream, &h->last_consumer, h->d_adj_work, h->d_adjrm_work));
-        return LEXLS_OK;
-    }
-
-    int lexls_lse_solve_adjoint_multi(lexls_lse_t h, const double *h_G, uint32_t ncot)
-    {
-        const char *who = "lexls_lse_solve_adjoint_multi";
-        if (int rc = need_adjoint_multi(h, who, h_G, ncot)) return rc;
-        HIP_TRY(hipSetDevice(h->device));
-        const size_t B = h->batch, n = h->nVar, cap = h->cap;
-        if (ncot > h->adjm_room) // the buffers hold the largest ncot so far
-        {
-            h->adjm_valid = false;
-            h->adjm_room  = 0;
-            for (double **p : {&h->d_adjm_G, &h->d_adjm_rhs, &h->d_adjm_fixed})
-            {
-                if (*p) (void)hipFree(*p); // (waits for whatever still reads it)
-                *p = nullptr;
-            }
-            HIP_TRY(hipMalloc((void **)&h->d_adjm_G, 8 * B * ncot * n));
-            HIP_TRY(hipMalloc((void **)&h->d_adjm_rhs, 8 * B * ncot * cap));
-            HIP_TRY(hipMalloc((void **)&h->d_adjm_fixed, 8 * B * ncot * n));
-            h->adjm_room = ncot;
-        }
-        if (int rc = upload_adjoint_g(h, h->d_adjm_G, h_G, 8 * B * ncot * n)) return rc;
-        if (int rc = run_solve_adjoint_multi(h, who, h->d_adjm_G, ncot, h->d_adjm_rhs, h->d_adjm_fixed)) return rc;
-        h->adjm_valid = true;
-        h->adjm_ncot  = ncot;
-        h->adjm_epoch = h->factor_epoch;
-        return LEXLS_OK;
-    }
-
-    int lexls_lse_solve_adjoint_multi_device(lexls_lse_t h, const double *d_G, uint32_t ncot, double *d_grad_rhs, double *d_grad_fixed)
-    {
-        return run_solve_adjoint_multi(h, "lexls_lse_solve_adjoint_multi_device", d_G, ncot, d_grad_rhs, d_grad_fixed);
-    }
-
-    int lexls_lse_get_adjoint_multi(lexls_lse_t h, double *h_grad_rhs, double *h_grad_fixed)
-    {
-        CHECK_HANDLE(h);
-        const size_t rows = (size_t)h->batch * h->adjm_ncot;
-        return get_adjoint_results(h, "_multi", h->adjm_valid, h->adjm_epoch, {{h_grad_rhs, h->d_adjm_rhs, 8 * rows * h->cap}, {h_grad_fixed, h->d_adjm_fixed, 8 * rows * h->nVar}});
-    }
-
-    /// what every form of the matrix gradient checks before any device work: a kept, unregularized factor and the x that belongs to it
-    static int need_adjoint_matrix(lexls_lse_t h, const char *who, const void *g)
-    {
-        if (int rc = need_adjoint_factor(h, who, g)) return rc;
-        if (h->x_epoch != h->factor_epoch)
-            return fail(LEXLS_ERR_INVALID, std::string(who) + ": no x belongs to the current factor (lexls_lse_factorize_solve(keep_factor = 1), or lexls_lse_factorize + lexls_lse_solve)");
-        return LEXLS_OK;
-    }
-    /// every form of lexls_lse_solve_adjoint_matrix on device memory: the checks, the work buffer, the launch (d_grad_fixed: lexls_internal_solve_adjoint_matrix's)
-    static int run_solve_adjoint_matrix(lexls_lse_t h, const char *who, const double *d_g, double *d_grad_lod, uint8_t *d_differentiable, double *d_grad_fixed)
-    {
-        if (int rc = need_adjoint_matrix(h, who, d_g)) return rc;
-        if (!d_grad_lod) return fail(LEXLS_ERR_INVALID, std::string(who) + ": null d_grad_lod");
-        HIP_TRY(hipSetDevice(h->device));
-        if (!h->d_adjA_work) HIP_TRY(hipMalloc(&h->d_adjA_work, adjoint_matrix_work_bytes(h->args())));
-        HIP_TRY(launch_solve_adjoint_matrix(h->args(), d_g, d_grad_lod, d_differentiable, h->d_adjA_work, h->max_level_dim, h->stream, &h->last_consumer, d_grad_fixed));
-        return LEXLS_OK;
-    }
-
-    int lexls_lse_solve_adjoint_matrix(lexls_lse_t h, const double *h_g)
-    {
-        const char *who = "lexls_lse_solve_adjoint_matrix";
-        if (int rc = need_adjoint_matrix(h, who, h_g)) return rc;
-        HIP_TRY(hipSetDevice(h->device));
-        const size_t B = h->batch, n = h->nVar, cap = h->cap;
-        if (!h->d_adjA_g) HIP_TRY(hipMalloc((void **)&h->d_adjA_g, 8 * B * n));
-        if (!h->d_adjA_grad) HIP_TRY(hipMalloc((void **)&h->d_adjA_grad, 8 * B * (n + 1) * cap));
-        if (!h->d_adjA_flag) HIP_TRY(hipMalloc((void **)&h->d_adjA_flag, B));
-        if (int rc = upload_adjoint_g(h, h->d_adjA_g, h_g, 8 * B * n)) return rc;
-        if (int rc = run_solve_adjoint_matrix(h, who, h->d_adjA_g, h->d_adjA_grad, h->d_adjA_flag, nullptr)) return rc;
-        h->adjA_valid = true;
-        h->adjA_epoch = h->factor_epoch;
-        return LEXLS_OK;
-    }
-
-    int lexls_lse_solve_adjoint_matrix_device(lexls_lse_t h, const double *d_g, double *d_grad_lod, uint8_t *d_differentiable)
-    {
-        return run_solve_adjoint_matrix(h, "lexls_lse_solve_adjoint_matrix_device", d_g, d_grad_lod, d_differentiable, nullptr);
-    }
-
-    int lexls_internal_solve_adjoint_matrix(lexls_lse_t h, const double *d_g, double *d_grad_lod, double *d_grad_fixed, uint8_t *d_differentiable)
-    {
-        return run_solve_adjoint_matrix(h, "lexls_internal_solve_adjoint_matrix", d_g, d_grad_lod, d_differentiable, d_grad_fixed);
-    }
-
-    int lexls_lse_get_adjoint_matrix(lexls_lse_t h, double *h_grad_lod, uint8_t *h_differentiable)
-    {
-        CHECK_HANDLE(h);
-        return get_adjoint_results(h, "_matrix", h->adjA_valid, h->adjA_epoch,
-                                   {{h_grad_lod, h->d_adjA_grad, 8 * (size_t)h->batch * h->problem_elems()}, {h_differentiable, h->d_adjA_flag, (size_t)h->batch}});
-    }
-
-    /// what every form of lexls_lse_solve_tangent checks before any device work: lexls_lse_solve_adjoint_matrix's preconditions, ntan
-    static int need_tangent(lexls_lse_t h, const char *who, const void *dlod, uint32_t ntan)
-    {
-        CHECK_HANDLE(h);
-        if (!dlod) return fail(LEXLS_ERR_INVALID, std::string(who) + ": null dlod");
-        if (ntan == 0) return fail(LEXLS_ERR_INVALID, std::string(who) + ": ntan == 0");
-        if (ntan > 65535u) return fail(LEXLS_ERR_INVALID, std::string(who) + ": ntan > 65535 (split the directions over several calls)");
-        return need_adjoint_matrix(h, who, dlod);
-    }
-    /// every form of lexls_lse_solve_tangent on device memory: the checks, the work buffers, the launch
-    static int run_solve_tangent(lexls_lse_t h, const char *who, const double *d_dlod, const double *d_dfixed, uint32_t ntan, double *d_dx, uint8_t *d_differentiable)
-    {
-        if (int rc = need_tangent(h, who, d_dlod, ntan)) return rc;
-        if (!d_dx) return fail(LEXLS_ERR_INVALID, std::string(who) + ": null d_dx");
-        HIP_TRY(hipSetDevice(h->device));
-        const size_t need = tangent_work_bytes(h->args(), ntan);
-        if (need > h->tan_work_bytes) // the work buffer holds the largest request so far (it grows with ntan, and with the placement)
-        {
-            if (h->d_tan_work) (void)hipFree(h->d_tan_work); // (waits for whatever still reads it)
-            h->d_tan_work = nullptr, h->tan_work_bytes = 0;
-            HIP_TRY(hipMalloc(&h->d_tan_work, need));
-            h->tan_work_bytes = need;
-        }
-        const size_t bytes = ntan > 1 ? adjoint_multi_work_bytes(h->args()) : 0; // (M^T w of several tangents: the per-cotangent form's buffers)
-        if (bytes && !h->d_adjm_work) HIP_TRY(hipMalloc((void **)&h->d_adjm_work, bytes));
-        HIP_TRY(launch_solve_tangent(h->args(), d_dlod, d_dfixed, ntan, d_dx, d_differentiable, h->d_tan_work, h->d_adjm_work, h->max_level_dim, h->stream, &h->last_consumer));
-        return LEXLS_OK;
-    }
-
-    int lexls_lse_solve_tangent(lexls_lse_t h, const double *h_dlod, const double *h_dfixed, uint32_t ntan)
-    {
-        const char *who = "lexls_lse_solve_tangent";
-        if (int rc = need_tangent(h, who, h_dlod, ntan)) return rc;
-        HIP_TRY(hipSetDevice(h->device));
-        const size_t B = h->batch, n = h->nVar;
-        if (ntan > h->tan_room) // the buffers hold the largest ntan so far
-        {
-            h->tan_valid = false;
-            h->tan_room  = 0;
-            for (double **p : {&h->d_tan_dlod, &h->d_tan_dfixed, &h->d_tan_dx})
-            {
-                if (*p) (void)hipFree(*p); // (waits for whatever still reads it)
-                *p = nullptr;
-            }
-            HIP_TRY(hipMalloc((void **)&h->d_tan_dlod, 8 * B * ntan * h->problem_elems()));
-            HIP_TRY(hipMalloc((void **)&h->d_tan_dfixed, 8 * B * ntan * n));
-            HIP_TRY(hipMalloc((void **)&h->d_tan_dx, 8 * B * ntan * n));
-            h->tan_room = ntan;
-        }
-        if (!h->d_tan_flag) HIP_TRY(hipMalloc((void **)&h->d_tan_flag, B));
-        if (h_dfixed) HIP_TRY(hipMemcpyAsync(h->d_tan_dfixed, h_dfixed, 8 * B * ntan * n, hipMemcpyHostToDevice, h->stream));
-        if (int rc = upload_adjoint_g(h, h->d_tan_dlod, h_dlod, 8 * B * ntan * h->problem_elems())) return rc;
-        if (int rc = run_solve_tangent(h, who, h->d_tan_dlod, h_dfixed ? h->d_tan_dfixed : nullptr, ntan, h->d_tan_dx, h->d_tan_flag)) return rc;
-        h->tan_valid = true;
-        h->tan_ntan  = ntan;
-        h->tan_epoch = h->factor_epoch;
-        return LEXLS_OK;
-    }
-
-    int lexls_lse_solve_tangent_device(lexls_lse_t h, const double *d_dlod, const double *d_dfixed, uint32_t ntan, double *d_dx, uint8_t *d_differentiable)
-    {
-        return run_solve_tangent(h, "lexls_lse_solve_tangent_device", d_dlod, d_dfixed, ntan, d_dx, d_differentiable);
-    }
-
-    int lexls_lse_get_tangent(lexls_lse_t h, double *h_dx, uint8_t *h_differentiable)
-    {
-        CHECK_HANDLE(h);
-        const std::string who = "lexls_lse_get_tangent";
-        if (!h->tan_valid) return fail(LEXLS_ERR_INVALID, who + ": call lexls_lse_solve_tangent first");
-        if (!h->factor_valid || h->tan_epoch != h->factor_epoch)
-            return fail(LEXLS_ERR_INVALID, who + ": the problem or its factorization changed since lexls_lse_solve_tangent (call it again)");
-        HIP_TRY(hipSetDevice(h->device));
-        if (h_dx) HIP_TRY(hipMemcpyAsync(h_dx, h->d_tan_dx, 8 * (size_t)h->batch * h->tan_ntan * h->nVar, hipMemcpyDeviceToHost, h->stream));
-        if (h_differentiable) HIP_TRY(hipMemcpyAsync(h_differentiable, h->d_tan_flag, (size_t)h->batch, hipMemcpyDeviceToHost, h->stream));
-        if (!h->deferred_sync) HIP_TRY(hipStreamSynchronize(h->stream));
-        return LEXLS_OK;
-    }
-
-    /// what every form of lexls_lse_solve_rhs checks before any device work: the arguments, a kept factor — unregularized, or regularized with one
-    /// of the types whose damped solve is an affine map of the kept factor, the factors constant (behind no switch: a new entry)
-    static int need_solve_rhs(lexls_lse_t h, const char *who, const void *rhs, uint32_t nrhs)
-    {
-        CHECK_HANDLE(h);
-        if (!rhs) return fail(LEXLS_ERR_INVALID, std::string(who) + ": null rhs");
-        if (nrhs == 0) return fail(LEXLS_ERR_INVALID, std::string(who) + ": nrhs == 0");
-        if (nrhs > 65535u) return fail(LEXLS_ERR_INVALID, std::string(who) + ": nrhs > 65535 (split the right-hand sides over several calls)");
-        if (int rc = need_factor(h, who)) return rc;
-        if (h->reg_type == 0) return LEXLS_OK;
-        if (!adjoint_reg_serves(h->reg_type))
-            return fail(LEXLS_ERR_UNSUPPORTED, std::string(who) + ": regularization_type " + std::to_string(h->reg_type) +
-                                                   " is not an affine map of the right-hand side (the CG types 2 and 6 iterate from x = 0, type 7 is experimental); served: 1, 3, 4, 5, 8, 9");
-        if (h->reg_variable != 0.0)
-            return fail(LEXLS_ERR_UNSUPPORTED, std::string(who) + ": variable_regularization_factor != 0 under regularization_type " + std::to_string(h->reg_type) +
-                                                   " (the factor depends on the right-hand side: x is not an affine map of it)");
-        return LEXLS_OK;
-    }
-    /// every form of lexls_lse_solve_rhs on device memory: the checks, the work buffer, the launch
-    static int run_solve_rhs(lexls_lse_t h, const char *who, const double *d_rhs, const double *d_fixed, uint32_t nrhs, double *d_x)
-    {
-        if (int rc = need_solve_rhs(h, who, d_rhs, nrhs)) return rc;
-        if (!d_x) return fail(LEXLS_ERR_INVALID, std::string(who) + ": null d_x");
-        HIP_TRY(hipSetDevice(h->device));
-        const size_t need = solve_rhs_work_bytes(h->args(), nrhs);
-        if (need > h->srhs_work_bytes) // the work buffer holds the largest request so far (it grows with nrhs, and with the placement)
-        {
-            if (h->d_srhs_work) (void)hipFree(h->d_srhs_work); // (waits for whatever still reads it)
-            h->d_srhs_work = nullptr, h->srhs_work_bytes = 0;
-            HIP_TRY(hipMalloc(&h->d_srhs_work, need));
-            h->srhs_work_bytes = need;
-        }
-        HIP_TRY(launch_solve_rhs(h->args(), d_rhs, d_fixed, nrhs, d_x, h->d_srhs_work, h->stream, &h->last_consumer));
-        return LEXLS_OK;
-    }
-
-    int lexls_lse_solve_rhs(lexls_lse_t h, const double *h_rhs, const double *h_fixed, uint32_t nrhs)
-    {
-        const char *who = "lexls_lse_solve_rhs";
-        if (int rc = need_solve_rhs(h, who, h_rhs, nrhs)) return rc;
-        HIP_TRY(hipSetDevice(h->device));
-        const size_t B = h->batch, n = h->nVar, cap = h->cap;
-        if (nrhs > h->srhs_room) // the buffers hold the largest nrhs so far
-        {
-            h->srhs_valid = false;
-            h->srhs_room  = 0;
-            for (double **p : {&h->d_srhs_rhs, &h->d_srhs_fixed, &h->d_srhs_x})
-            {
-                if (*p) (void)hipFree(*p); // (waits for whatever still reads it)
-                *p = nullptr;
-            }
-            HIP_TRY(hipMalloc((void **)&h->d_srhs_rhs, 8 * B * nrhs * cap));
-            HIP_TRY(hipMalloc((void **)&h->d_srhs_fixed, 8 * B * nrhs * n));
-            HIP_TRY(hipMalloc((void **)&h->d_srhs_x, 8 * B * nrhs * n));
-            h->srhs_room = nrhs;
-        }
-        if (h_fixed) HIP_TRY(hipMemcpyAsync(h->d_srhs_fixed, h_fixed, 8 * B * nrhs * n, hipMemcpyHostToDevice, h->stream));
-        if (int rc = upload_adjoint_g(h, h->d_srhs_rhs, h_rhs, 8 * B * nrhs * cap)) return rc;
-        if (int rc = run_solve_rhs(h, who, h->d_srhs_rhs, h_fixed ? h->d_srhs_fixed : nullptr, nrhs, h->d_srhs_x)) return rc;
-        h->srhs_valid = true;
-        h->srhs_nrhs  = nrhs;
-        h->srhs_epoch = h->factor_epoch;
-        return LEXLS_OK;
-    }
-
-    int lexls_lse_solve_rhs_device(lexls_lse_t h, const double *d_rhs, const double *d_fixed, uint32_t nrhs, double *d_x)
-    {
-        return run_solve_rhs(h, "lexls_lse_solve_rhs_device", d_rhs, d_fixed, nrhs, d_x);
-    }
-
-    int lexls_lse_get_solve_rhs(lexls_lse_t h, double *h_x)
-    {
-        CHECK_HANDLE(h);
-        const std::string who = "lexls_lse_get_solve_rhs";
-        if (!h->srhs_valid) return fail(LEXLS_ERR_INVALID, who + ": call lexls_lse_solve_rhs first");
-        if (!h->factor_valid || h->srhs_epoch != h->factor_epoch)
-            return fail(LEXLS_ERR_INVALID, who + ": the problem or its factorization changed since lexls_lse_solve_rhs (call it again)");
-        HIP_TRY(hipSetDevice(h->device));
-        if (h_x) HIP_TRY(hipMemcpyAsync(h_x, h->d_srhs_x, 8 * (size_t)h->batch * h->srhs_nrhs * h->nVar, hipMemcpyDeviceToHost, h->stream));
-        if (!h->deferred_sync) HIP_TRY(hipStreamSynchronize(h->stream));
-        return LEXLS_OK;
-    }
-
-    int lexls_internal_apply_solve_map(lexls_lse_t h, const double *d_rhs, double *d_out)
-    {
-        if (int rc = need_adjoint_factor(h, "lexls_internal_apply_solve_map", d_rhs)) return rc;
-        if (!d_out) return fail(LEXLS_ERR_INVALID, "lexls_internal_apply_solve_map: null d_out");
-        HIP_TRY(hipSetDevice(h->device));
-        HIP_TRY(launch_apply_solve_map(h->args(), d_rhs, nullptr, d_out, h->stream));
-        return LEXLS_OK;
-    }
-
     static int need_wrong_sign(lexls_lse_t h)
     {
         if (h->d_wrong_sign) return LEXLS_OK;
@@ -1764,3 +1392,5 @@ extern "C"
         return LEXLS_OK;
     }
 }
+
+#include "lse_kept_capi.h" // the calls that work on a kept factor beyond the solves above: the adjoints, the tangents, new right-hand sides

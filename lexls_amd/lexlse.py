@@ -13,6 +13,7 @@ library; nothing here computes on the CPU.
 from __future__ import annotations
 
 import ctypes as C
+from functools import partial
 
 import numpy as np
 
@@ -21,6 +22,28 @@ from . import capi
 
 def _ptr(a, t):
     return None if a is None else a.ctypes.data_as(C.POINTER(t))
+
+
+def _device_address(who, name, t, shape, dtype="torch.float64", raw_ok=False):
+    """The address of an optional device argument `name` of the method `who`: None stays None, a raw address (anything without data_ptr(), where
+    raw_ok) is taken as it is, everything else has to be a contiguous torch tensor of that dtype and shape."""
+    if t is None:
+        return None
+    if raw_ok and not hasattr(t, "data_ptr"):
+        return C.c_void_p(int(t))
+    if not hasattr(t, "data_ptr") or str(t.dtype) != dtype or not t.is_contiguous() or tuple(t.shape) != shape:
+        raise ValueError(f"{who}: {name} must be a contiguous {dtype.split('.')[1]} tensor of shape {shape}")
+    return C.c_void_p(t.data_ptr())
+
+
+def _leading_axis(shape, item_rank):
+    """(lead, K) of an argument that holds K items of item_rank axes each, or one item without the leading axis: lead, (K,) or (), is what stands
+    in front of an item's shape in every argument of the call.  K == 0 where `shape` has neither rank or no item: the caller refuses it."""
+    if len(shape) == item_rank:
+        return (), 1
+    if len(shape) == item_rank + 1:
+        return (int(shape[0]),), int(shape[0])
+    return (), 0
 
 
 class BatchedLexLSE:
@@ -322,14 +345,7 @@ class BatchedLexLSE:
         """lexls_lse_solve_adjoint_device: g (batch, nVar), grad_rhs (batch, cap) and grad_fixed (batch, nVar; None: not wanted) in device memory —
         contiguous float64 torch tensors (anything with data_ptr()) or raw addresses.  Only enqueued in the handle's stream (set_stream): g has
         to be complete in stream order, nothing is waited for.  Serves the same factors as solve_adjoint (regularization types 1, 3, 4, 5, 8, 9)."""
-        def address(name, t, shape):
-            if t is None:
-                return None
-            if not hasattr(t, "data_ptr"):
-                return C.c_void_p(int(t))
-            if str(t.dtype) != "torch.float64" or not t.is_contiguous() or tuple(t.shape) != shape:
-                raise ValueError(f"solve_adjoint_device: {name} must be a contiguous float64 tensor of shape {shape}")
-            return C.c_void_p(t.data_ptr())
+        address = partial(_device_address, "solve_adjoint_device", raw_ok=True)
         capi.check(capi.lib().lexls_lse_solve_adjoint_device(self._h, address("g", g, (self.batch, self.nVar)),
                                                               address("grad_rhs", grad_rhs, (self.batch, self.cap)),
                                                               address("grad_fixed", grad_fixed, (self.batch, self.nVar))))
@@ -360,13 +376,7 @@ class BatchedLexLSE:
         if not hasattr(G, "data_ptr") or G.dim() != 3 or G.shape[1] == 0:
             raise ValueError("solve_adjoint_multi_device: G must be a tensor of shape (batch, K >= 1, nVar)")
         K = int(G.shape[1])
-
-        def address(name, t, shape):
-            if t is None:
-                return None
-            if not hasattr(t, "data_ptr") or str(t.dtype) != "torch.float64" or not t.is_contiguous() or tuple(t.shape) != shape:
-                raise ValueError(f"solve_adjoint_multi_device: {name} must be a contiguous float64 tensor of shape {shape}")
-            return C.c_void_p(t.data_ptr())
+        address = partial(_device_address, "solve_adjoint_multi_device")
         args = (address("G", G, (self.batch, K, self.nVar)), address("grad_rhs", grad_rhs, (self.batch, K, self.cap)),
                 address("grad_fixed", grad_fixed, (self.batch, K, self.nVar)))
         if K == 1 and not self._one_cotangent_on_the_multi_entry():
@@ -395,14 +405,7 @@ class BatchedLexLSE:
         """lexls_lse_solve_adjoint_matrix_device: g (batch, nVar) float64, grad_lod (batch, nVar + 1, cap) float64 and differentiable (batch,)
         uint8 (None: not wanted) in device memory — contiguous torch tensors or raw addresses.  Only enqueued in the handle's stream (set_stream):
         g has to be complete in stream order, nothing is waited for."""
-        def address(name, t, shape, dtype="torch.float64"):
-            if t is None:
-                return None
-            if not hasattr(t, "data_ptr"):
-                return C.c_void_p(int(t))
-            if str(t.dtype) != dtype or not t.is_contiguous() or tuple(t.shape) != shape:
-                raise ValueError(f"solve_adjoint_matrix_device: {name} must be a contiguous {dtype.split('.')[1]} tensor of shape {shape}")
-            return C.c_void_p(t.data_ptr())
+        address = partial(_device_address, "solve_adjoint_matrix_device", raw_ok=True)
         capi.check(capi.lib().lexls_lse_solve_adjoint_matrix_device(self._h, address("g", g, (self.batch, self.nVar)),
                                                                      address("grad_lod", grad_lod, (self.batch, self.nVar + 1, self.cap)),
                                                                      address("differentiable", differentiable, (self.batch,), "torch.uint8")))
@@ -415,12 +418,12 @@ class BatchedLexLSE:
         single direction given without the leading axis — in the order of get_x(), and differentiable (batch,) uint8, the flags of
         solve_adjoint_matrix; where the flag is 0 the problem's rows of dx are exact zeros.  Needs what solve_adjoint_matrix needs."""
         dlod = np.ascontiguousarray(dlod, np.float64)
-        single = dlod.ndim == 3
+        lead, K = _leading_axis(dlod.shape, 3)
+        single = K == 1 and not lead
         if single:
             dlod = dlod[None]
-        if dlod.ndim != 4 or dlod.shape[0] == 0 or dlod.shape[1:] != (self.batch, self.nVar + 1, self.cap):
+        if K == 0 or dlod.shape[1:] != (self.batch, self.nVar + 1, self.cap):
             raise ValueError(f"dlod must have shape (K >= 1, {self.batch}, {self.nVar + 1}, {self.cap}) or lack the leading axis, got {dlod.shape}")
-        K = dlod.shape[0]
         if dfixed is not None:
             dfixed = np.ascontiguousarray(dfixed, np.float64).reshape((K, self.batch, self.nVar))
         capi.check(capi.lib().lexls_lse_solve_tangent(self._h, _ptr(dlod, C.c_double), None if dfixed is None else _ptr(dfixed, C.c_double), K))
@@ -435,17 +438,10 @@ class BatchedLexLSE:
         axis in all three.  Only enqueued in the handle's stream (set_stream): the directions have to be complete in stream order."""
         if not hasattr(dlod, "data_ptr") or dlod.dim() not in (3, 4):
             raise ValueError("solve_tangent_device: dlod must be a tensor of shape (K >= 1, batch, nVar + 1, cap) or (batch, nVar + 1, cap)")
-        lead = () if dlod.dim() == 3 else (int(dlod.shape[0]),)
-        K = lead[0] if lead else 1
+        lead, K = _leading_axis(dlod.shape, 3)
         if K == 0:
             raise ValueError("solve_tangent_device: K == 0")
-
-        def address(name, t, shape, dtype="torch.float64"):
-            if t is None:
-                return None
-            if not hasattr(t, "data_ptr") or str(t.dtype) != dtype or not t.is_contiguous() or tuple(t.shape) != shape:
-                raise ValueError(f"solve_tangent_device: {name} must be a contiguous {dtype.split('.')[1]} tensor of shape {shape}")
-            return C.c_void_p(t.data_ptr())
+        address = partial(_device_address, "solve_tangent_device")
         capi.check(capi.lib().lexls_lse_solve_tangent_device(self._h, address("dlod", dlod, lead + (self.batch, self.nVar + 1, self.cap)),
                                                               address("dfixed", dfixed, lead + (self.batch, self.nVar)), K,
                                                               address("dx", dx, lead + (self.batch, self.nVar)),
@@ -459,12 +455,12 @@ class BatchedLexLSE:
         factorize_solve() gives for the same matrices under that right-hand side and those fixed values, within the tolerance contract.
         Needs a kept factor only (factorize() is enough); after setRegularization: types 1, 3, 4, 5, 8, 9 with constant factors."""
         rhs = np.ascontiguousarray(rhs, np.float64)
-        single = rhs.ndim == 2
+        lead, K = _leading_axis(rhs.shape, 2)
+        single = K == 1 and not lead
         if single:
             rhs = rhs[None]
-        if rhs.ndim != 3 or rhs.shape[0] == 0 or rhs.shape[1:] != (self.batch, self.cap):
+        if K == 0 or rhs.shape[1:] != (self.batch, self.cap):
             raise ValueError(f"rhs must have shape (K >= 1, {self.batch}, {self.cap}) or lack the leading axis, got {rhs.shape}")
-        K = rhs.shape[0]
         if fixed is not None:
             fixed = np.ascontiguousarray(fixed, np.float64).reshape((K, self.batch, self.nVar))
         capi.check(capi.lib().lexls_lse_solve_rhs(self._h, _ptr(rhs, C.c_double), None if fixed is None else _ptr(fixed, C.c_double), K))
@@ -478,17 +474,10 @@ class BatchedLexLSE:
         handle's stream (set_stream): the inputs have to be complete in stream order."""
         if not hasattr(rhs, "data_ptr") or rhs.dim() not in (2, 3):
             raise ValueError("solve_rhs_device: rhs must be a tensor of shape (K >= 1, batch, cap) or (batch, cap)")
-        lead = () if rhs.dim() == 2 else (int(rhs.shape[0]),)
-        K = lead[0] if lead else 1
+        lead, K = _leading_axis(rhs.shape, 2)
         if K == 0:
             raise ValueError("solve_rhs_device: K == 0")
-
-        def address(name, t, shape):
-            if t is None:
-                return None
-            if not hasattr(t, "data_ptr") or str(t.dtype) != "torch.float64" or not t.is_contiguous() or tuple(t.shape) != shape:
-                raise ValueError(f"solve_rhs_device: {name} must be a contiguous float64 tensor of shape {shape}")
-            return C.c_void_p(t.data_ptr())
+        address = partial(_device_address, "solve_rhs_device")
         capi.check(capi.lib().lexls_lse_solve_rhs_device(self._h, address("rhs", rhs, lead + (self.batch, self.cap)),
                                                           address("fixed", fixed, lead + (self.batch, self.nVar)), K,
                                                           address("x", x, lead + (self.batch, self.nVar))))
