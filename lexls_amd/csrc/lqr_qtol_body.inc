@@ -213,6 +213,10 @@
             // never start at such a column (qt_retire_reachable).
             constexpr int kRetireSlot = NS - 2;
             constexpr bool RETIRE     = !EST && !RAG && PEEL && NV > 0 && qt_retire_reachable(NS, MD, SIG, NV) && 8 * (NV + 1) * RP >= 17 * kHandoffStride;
+            // RING_D / RING_W: how many steps ahead the elimination requests a finished pivot's image row, for the steps with one or two live
+            // slots / with more (qt_elim_ring_dpp, qt_elim_ring_wide in lqr_qtol_impl.h; 0: the one-ahead fetch, the instantiation's earlier code)
+            constexpr int RING_D = qt_elim_ring_dpp(NS, MD, EST, RAG), RING_W = qt_elim_ring_wide(NS, MD, EST, RAG);
+            static_assert((RING_D > 0) == (RING_W > 0), "a ring serves every step form of its instantiation");
             struct qt_level // what the phases of one level hand to each other (per row, uniform inside a row; prefetch: wave-uniform)
             {
                 bool work;     // x only: once the columns are exhausted nothing below matters
@@ -337,8 +341,10 @@
             auto eliminate = [&](const int k, const qt_level &L, double (&blk)[NS][MD]) __attribute__((always_inline)) {
                 (void)k;
                 const int Fcmax = rows_max(L.work ? L.Fc : 0);
+                ESTAMP_DECL
                 {
-                    // U'[c'][P] of this lane's columns is fetched one pivot ahead of its use (the read depends on a row-broadcast address)
+                    // U'[c'][P] of this lane's columns: one LDS read per live slot behind a row-broadcast address.  Everything it reads — rp, rq,
+                    // the index words, the image rows of the finished levels — is final when the level starts
                     auto fetch_u = [&](auto cc, double (&u)[NS]) __attribute__((always_inline)) {
                         constexpr int C  = decltype(cc)::value;
                         constexpr int sc = (C + SIG) / 16, lc = (C + SIG) % 16;
@@ -351,17 +357,81 @@
                             u[s]             = D(rowp + (int)(e << 3));
                         }
                     };
+                    constexpr int NP = 16 * NS - SIG; // pivot positions
+                    if constexpr (RING_D > 0)
+                    {
+                    // The rows are kept in flight several steps ahead, in a ring of registers: the row of pivot P is requested qt_elim_ahead(P)
+                    // steps in front of step P (at the level head when that is before step 0), into entry P % RD.  A step takes its entry and
+                    // re-issues the entries of the pivots whose turn it is, in ascending order, behind the first use of its own: the LDS round
+                    // trip of a row is covered by the fma issue of the steps in front instead of being waited for in every step.  Indices are
+                    // compile-time constants, so every entry is a named register and the compiler counts the reads in flight itself
+                    // (s_waitcnt lgkmcnt(N), N = the reads issued behind the step's own).  The requests are unconditional: a position beyond
+                    // the problem's (or the wavefront's) finished pivots reads a zero of the x block, as such a position does in a step that
+                    // runs for another row's sake, and what was asked for a step that does not run is not used.
+                    constexpr int RD = RING_D > RING_W ? RING_D : RING_W;
+                    double ring[RD][NS];
+                    for_each_index<0, (RD < NP ? RD : NP)>([&](auto pp) __attribute__((always_inline)) {
+                        constexpr int P = decltype(pp)::value;
+                        if constexpr (P < qt_elim_ahead(RING_D, RING_W, NS, SIG, P)) fetch_u(pp, ring[P % RD]);
+                    });
+                    ESTAMP(0)
+                    qt_for_each_while<0, NP>(
+                        [&](auto cc) __attribute__((always_inline)) { return decltype(cc)::value < Fcmax; }, // wave-uniform
+                        [&](auto cc) __attribute__((always_inline)) {
+                            constexpr int C  = decltype(cc)::value;
+                            constexpr int sc = (C + SIG) / 16, lc = (C + SIG) % 16;
+                            if constexpr (C > 0 && lc == 0) { ESTAMP(NS - sc + 1) } // (the form in front ends here)
+                            QT_MARK1("elim", C)
+                            double ucur[NS];
+#pragma unroll
+                            for (int s = sc; s < NS; s++) ucur[s] = ring[C % RD][s];
+                            auto refill = [&]() __attribute__((always_inline)) {
+                                for_each_index<C + 1, (C + RD + 1 < NP ? C + RD + 1 : NP)>([&](auto pp) __attribute__((always_inline)) {
+                                    constexpr int P = decltype(pp)::value;
+                                    if constexpr (P - qt_elim_ahead(RING_D, RING_W, NS, SIG, P) == C) fetch_u(pp, ring[P % RD]);
+                                });
+                            };
+                            if constexpr (NS - sc <= 2)
+                            {
+                                if constexpr (sc + 1 < NS) qt_gauss_dpp<lc>(blk[sc + 1], blk[sc], ucur[sc + 1]);
+                                refill();
+                                qt_gauss_dpp_self<lc>(blk[sc], ucur[sc]);
+                            }
+                            else
+                            {
+                                double lr[MD];
+                                for_each_index<0, MD>([&](auto rr) {
+                                    constexpr int r = decltype(rr)::value;
+                                    lr[r]           = gbc<lc>(blk[sc][r]);
+                                });
+#pragma unroll
+                                for (int r = 0; r < MD; r++) blk[sc][r] = dfma(-lr[r], ucur[sc], blk[sc][r]);
+                                refill();
+#pragma unroll
+                                for (int s = sc + 1; s < NS; s++)
+                                {
+#pragma unroll
+                                    for (int r = 0; r < MD; r++) blk[s][r] = dfma(-lr[r], ucur[s], blk[s][r]);
+                                }
+                            }
+                        });
+                    }
+                    else
+                    {
+                    // (no ring in this instantiation: the row is fetched one pivot ahead of its use)
                     double ua[NS], ub[NS]; // even / odd steps (no copies between the steps)
 #pragma unroll
                     for (int s = 0; s < NS; s++) ua[s] = ub[s] = 0.0;
                     if (Fcmax > 0) fetch_u(std::integral_constant<int, 0>{}, ua);
-                    qt_for_each_while<0, 16 * NS - SIG>(
+                    ESTAMP(0)
+                    qt_for_each_while<0, NP>(
                         [&](auto cc) __attribute__((always_inline)) { return decltype(cc)::value < Fcmax; }, // wave-uniform
                         [&](auto cc) __attribute__((always_inline)) {
                             constexpr int C  = decltype(cc)::value;
                             constexpr int sc = (C + SIG) / 16, lc = (C + SIG) % 16;
                             double(&ucur)[NS]  = (C & 1) ? ub : ua;
                             double(&unext)[NS] = (C & 1) ? ua : ub;
+                            if constexpr (C > 0 && lc == 0) { ESTAMP(NS - sc + 1) } // (the form in front ends here)
                             QT_MARK1("elim", C)
                             // a row of the wavefront whose own pivots end before Fcmax meets the zeros of the x block as "U'": every fma adds a zero product
                             if constexpr (NS - sc <= 2)
@@ -397,6 +467,8 @@
                                 }
                             }
                         });
+                    }
+                    ESTAMP_END(Fcmax)
                     // (what follows may read the block through DPP: the wait states behind the last block's writes, which the compiler does not count.
                     //  Here, once per level, and not at the end of qt_gauss_dpp_self, where it would be paid in every step: between the steps the
                     //  next block's own leading s_nop serves.  A level without a folded step pays two idle cycles)

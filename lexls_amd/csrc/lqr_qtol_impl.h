@@ -107,8 +107,31 @@ namespace lexls
         if (gl == 0 && live) a.lambda[(size_t)b * (n + cap) + 11 + 4 * k + (ph)] = (double)(t_ - lst_t0); \
         lst_t0 = t_;                                                                                 \
     }
+// ... and the elimination of a level split by step form: lambda[40 + 4 k + f], f = 0: the level head's requests for the first image rows, until
+// they have arrived; f = 1, 2, 3: the steps with that many live slots.  One stamp where the form changes and one behind the last step, none
+// between the steps of a form: a stamp waits for lgkmcnt(0), which would drain the rows in flight in every step.  The stamp that ends a form
+// does drain them once, at that form's cost.
+#define ESTAMP_DECL                                                \
+    static_assert(NS <= 3, "four stamp places per level");         \
+    unsigned long long est_acc[4] = {0, 0, 0, 0}, est_t0 = clock64();
+#define ESTAMP(f)                                  \
+    {                                              \
+        const unsigned long long t_ = clock64();   \
+        est_acc[f] += t_ - est_t0;                 \
+        est_t0 = t_;                               \
+    }
+#define ESTAMP_END(fcmax)                                                                                               \
+    {                                                                                                                   \
+        const unsigned long long t_ = clock64();                                                                        \
+        const int f_               = (fcmax) > 0 ? NS - ((fcmax) - 1 + SIG) / 16 : 0;                                   \
+        _Pragma("unroll") for (int i_ = 0; i_ < 4; i_++)                                                                \
+            if (gl == 0 && live) a.lambda[(size_t)b * (n + cap) + 40 + 4 * k + i_] = (double)(est_acc[i_] + (i_ == f_ ? t_ - est_t0 : 0ull)); \
+    }
 #else
 #define LSTAMP(ph)
+#define ESTAMP_DECL
+#define ESTAMP(f)
+#define ESTAMP_END(fcmax)
 #endif
 // Region marks (-DLEXLS_QTOL_MARKS, assembly only): a comment line "; qtol-region <name> [i [j]]" at the head of every phase and of every unrolled
 // step, by which scripts/qtol_insn_table.py splits the kernel's assembly and weighs each part with its trip count.  The product build has none.
@@ -231,6 +254,20 @@ namespace lexls
             }
             return false;
         }
+
+        /// The elimination's ring of image rows (lqr_qtol_body.inc, RING_D / RING_W): how many steps in front of its use the U' row of a
+        /// finished pivot is requested.  A step with one or two live slots (v_fmac_f64_dpp, 12 to 24 instructions) issues in less time than an
+        /// LDS round trip takes, so one step of look-ahead leaves most of the trip to be waited for: three steps cover it.  A step with more
+        /// live slots issues for about as long as the trip takes: two steps.  An entry costs two registers per live slot, eighteen at the
+        /// most, held inside the elimination only.  (In the product kernel as compiled now the wide steps do not get their two steps: the
+        /// compiler sinks their reads, with v_perm and address, to the head of the step that uses them — only the two broadcasts stay two
+        /// steps in front; profiles/r09_qtol_elim_ring.md.  The steps with one or two live slots keep their reads where they are written.)
+        /// Registers: the ring is live inside the elimination only (the register peak of every instantiation is in the pivot steps).  The estimating
+        /// instantiations keep the one-ahead fetch: <3,12,7,40> and <3,12,0,0> of them have no register to spare.
+        constexpr int qt_elim_ring_dpp(int NS, int MD, bool EST, bool RAG) { return EST ? 0 : 3; }
+        constexpr int qt_elim_ring_wide(int NS, int MD, bool EST, bool RAG) { return EST ? 0 : 2; }
+        /// ... of pivot position P: by the live slots of its step
+        constexpr int qt_elim_ahead(int ring_dpp, int ring_wide, int NS, int SIG, int P) { return NS - (P + SIG) / 16 <= 2 ? ring_dpp : ring_wide; }
 
         /// NV: the number of variables when the instantiation serves ONE n (0: taken from the arguments) — the piece counts of the level loads and
         /// the layout tests then fold at compile time.
