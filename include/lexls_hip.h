@@ -410,6 +410,38 @@ int lexls_lse_solve_rhs(lexls_lse_t h, const double *h_rhs, const double *h_fixe
 int lexls_lse_get_solve_rhs(lexls_lse_t h, double *h_x);
 int lexls_lse_solve_rhs_device(lexls_lse_t h, const double *d_rhs, const double *d_fixed, uint32_t nrhs, double *d_x);
 
+/* RESIDUALS OF NEW RIGHT-HAND SIDES on the kept factor: what ranks the nrhs candidates of lexls_lse_solve_rhs — the residual v of every priority
+ * level and its squared norm — without factorizing again and without a second copy of A (the factor overwrote it).
+ * Inputs: rhs and fixed exactly as for lexls_lse_solve_rhs (nrhs x batch x cap; nrhs x batch x nVar, NULL = the handle's fixed values; rows and
+ * slots behind a problem's own dimensions are never read).
+ * v is nrhs x batch x cap in LOD row order: v[c, b, :] is what lexls_lse_residual followed by lexls_lse_get_v returns for problem b with its
+ * right-hand-side column replaced by rhs[c, b] and its fixed values by fixed[c, b] — get_v() of the reference (lexlse.h:1560-1582), A x - b
+ * recovered through Q — within the tolerance contract; rows behind the problem's dimensions are written as 0.  With the handle's own b and
+ * fixed = NULL it equals lexls_lse_get_v within that tolerance.
+ * cost is nrhs x batch x nObj: cost[c, b, k] = the sum of squares of level k's rows of v[c, b], one ordered fma chain in row order by the lane
+ * that owns right-hand side c.  A level with rank == dim has its rows of v and its cost equal to 0.0 exactly (a zero head, nothing to push
+ * through Q: the reference's behaviour).
+ * d_x (device form), when non-NULL, receives the x of lexls_lse_solve_rhs_device for the same inputs, bit for bit: one call serves a caller who
+ * wants both, and the forward pass runs once (nrhs == 1: x comes from the single-vector kernel, as there).
+ * Served: every problem of every kept, UNDAMPED factor from every producer, rank-deficient problems and problems with every variable fixed
+ * included.  After a factorization with regularization_type != 0: LEXLS_ERR_UNSUPPORTED (get_v's formula is the residual of the undamped basic
+ * solution).  No x of the current factor is needed.
+ * lexls_lse_residual_rhs copies the inputs in, launches and keeps v and cost in buffers of the handle (made for the largest nrhs so far);
+ * lexls_lse_get_residual_rhs copies them out (either pointer may be NULL, not both) and answers only while they belong to the current factor;
+ * both follow lexls_lse_set_deferred_sync.  lexls_lse_residual_rhs_device reads and writes device memory (any of d_x, d_v, d_cost may be NULL,
+ * not all three), only enqueues in the handle's stream and makes no host-synchronising call (the work buffer, shared with
+ * lexls_lse_solve_rhs_device, is allocated at the first call and whenever nrhs exceeds every earlier one).  What lexls_lse_get_x, _get_v,
+ * _get_lambda, _get_multipliers, _get_solve_rhs and _get_adjoint* answer is not changed by these calls.
+ * Independence contract: v and cost of a right-hand side do not depend on nrhs, on its position or on its company, bit for bit (one lane per
+ * right-hand side, no cross-lane sums, no atomics); the same bits come back from run to run and from the host and the device form.
+ * Errors, each returned before any device work and with every output left alone: LEXLS_ERR_INVALID for a null handle, a null rhs, every output
+ * null, nrhs == 0 or nrhs > 65535, or no kept factor; LEXLS_ERR_UNSUPPORTED after a damped factorization (the message names the condition).
+ * Kernel variant (lexls_lse_last_consumer_kernel): "residual_rhs<64,staged>", "residual_rhs<64,lds>" or "residual_rhs<64,work>" — the placement
+ * rule of lexls_lse_solve_rhs, from nVar, cap and nObj alone.  Cost: DESIGN.md 5.15. */
+int lexls_lse_residual_rhs(lexls_lse_t h, const double *h_rhs, const double *h_fixed, uint32_t nrhs);
+int lexls_lse_get_residual_rhs(lexls_lse_t h, double *h_v, double *h_cost);
+int lexls_lse_residual_rhs_device(lexls_lse_t h, const double *d_rhs, const double *d_fixed, uint32_t nrhs, double *d_x, double *d_v, double *d_cost);
+
 /* ---- results (synchronise the stream, then D2H) ------------------------------------------------- */
 int lexls_lse_get_x(lexls_lse_t h, double *h_x);                    /* get_x()      lexlse.h:1587 */
 int lexls_lse_get_factor(lexls_lse_t h, double *h_lod);             /* get_lexqr()  lexlse.h:1626 */
@@ -1002,8 +1034,24 @@ int lexls_lsi_batch_solve_tangent_device(lexls_lsi_batch_t b, const double *d_dd
  * Cost: a call costs about the same for 1 as for 64 bound sets. */
 int lexls_lsi_batch_solve_bounds(lexls_lsi_batch_t b, const double *h_lb, const double *h_ub, uint32_t nrhs, double *h_x, double *h_violation, uint8_t *h_valid);
 int lexls_lsi_batch_solve_bounds_device(lexls_lsi_batch_t b, const double *d_lb, const double *d_ub, uint32_t nrhs, double *d_x, double *d_violation, uint8_t *d_valid);
-/* The kernel variant that served the LAST lexls_lsi_batch_solve_bounds(_device) call on this batch (a string the library owns); "" before the
- * first such call or for a null handle. */
+/* PER-OBJECTIVE COST of new bounds: lexls_lsi_batch_solve_bounds(_device) with one more output, the figure that ranks the nrhs candidates.
+ * Everything is as there, except: cost must be non-NULL and x may be NULL (not wanted).  cost is nrhs x batch x nObj:
+ *     cost[c, i, k] = sum over the rows r of objective k, in the user's row order, of d_r^2,   d_r = max(lb - a.x, a.x - ub, 0)
+ * with lb, ub of bound set c and a.x the very fma chain violation uses (a simple bound: x[var]); the sum is one ordered fma chain by the lane that
+ * owns bound set c.  This is the squared norm of LexLSI's v for objective k at x[c, i], measured against bound set c for ALL rows, in or out of
+ * the working set: it depends on x and the bounds alone.  (violation also counts max(lb - ub, 0) of a row; cost does not: violation^2 >= every
+ * d_r^2.)  Rows absent under lexls_lsi_batch_set_instance_obj_dims are never read and contribute nothing; instances with valid == 0 get exact
+ * zeros; a masked instance keeps its bits of cost as of the other outputs (the host form copies the caller's arrays in first).  The independence
+ * contract, the errors (a null cost in the place of a null x) and the LEXLS_ERR_UNSUPPORTED runs are those of lexls_lsi_batch_solve_bounds; the
+ * final factor is shared as before.  A call of lexls_lsi_batch_solve_bounds(_device) launches exactly what it launched before these existed.
+ * Kernel variant (lexls_lsi_batch_last_consumer_kernel): "lsi_bounds_cost<lds>" or "lsi_bounds_cost<hbm>", the same rule of nVar.
+ * Cost: DESIGN.md 5.15. */
+int lexls_lsi_batch_solve_bounds_cost(lexls_lsi_batch_t b, const double *h_lb, const double *h_ub, uint32_t nrhs, double *h_x, double *h_violation, double *h_cost,
+                                      uint8_t *h_valid);
+int lexls_lsi_batch_solve_bounds_cost_device(lexls_lsi_batch_t b, const double *d_lb, const double *d_ub, uint32_t nrhs, double *d_x, double *d_violation, double *d_cost,
+                                             uint8_t *d_valid);
+/* The kernel variant that served the LAST lexls_lsi_batch_solve_bounds(_device) or _solve_bounds_cost(_device) call on this batch (a string the
+ * library owns); "" before the first such call or for a null handle. */
 const char *lexls_lsi_batch_last_consumer_kernel(lexls_lsi_batch_t b);
 /* How often, since the batch was created, the final equality problems of a group were formed and factorized: the stage lexls_lsi_batch_get_lambda,
  * lexls_lsi_batch_solve_adjoint(_multi), lexls_lsi_batch_solve_adjoint_matrix, lexls_lsi_batch_solve_tangent and lexls_lsi_batch_solve_bounds share.  It grows by the number of groups at the first of these

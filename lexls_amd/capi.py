@@ -33,6 +33,7 @@ SYMBOLS = [
     "lexls_lse_solve_adjoint_matrix", "lexls_lse_get_adjoint_matrix", "lexls_lse_solve_adjoint_matrix_device",
     "lexls_lse_solve_tangent", "lexls_lse_get_tangent", "lexls_lse_solve_tangent_device",
     "lexls_lse_solve_rhs", "lexls_lse_get_solve_rhs", "lexls_lse_solve_rhs_device",
+    "lexls_lse_residual_rhs", "lexls_lse_get_residual_rhs", "lexls_lse_residual_rhs_device",
     "lexls_lsi_batch_get_lambda", "lexls_lsi_batch_solve_ex2",
     "lexls_lse_sensitivity_collect", "lexls_lse_sensitivity_collect_resident", "lexls_lse_get_wrong_sign",
     "lexls_lsi_batch_get_cycling_counters", "lexls_lsi_batch_run_device", "lexls_lsi_batch_run_device_ex",
@@ -45,6 +46,7 @@ SYMBOLS = [
     "lexls_lsi_batch_solve_adjoint_matrix", "lexls_lsi_batch_solve_adjoint_matrix_device", "lexls_lsi_batch_final_factorizations",
     "lexls_lsi_batch_solve_tangent", "lexls_lsi_batch_solve_tangent_device",
     "lexls_lsi_batch_solve_bounds", "lexls_lsi_batch_solve_bounds_device", "lexls_lsi_batch_last_consumer_kernel",
+    "lexls_lsi_batch_solve_bounds_cost", "lexls_lsi_batch_solve_bounds_cost_device",
     "lexls_lsi_batch_last_kernel",
 ]
 
@@ -161,6 +163,12 @@ def lib() -> C.CDLL:
         _lib.lexls_lse_get_solve_rhs.argtypes = [C.c_void_p, C.POINTER(C.c_double)]
         _lib.lexls_lse_solve_rhs_device.restype = C.c_int
         _lib.lexls_lse_solve_rhs_device.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p]  # d_rhs, d_fixed, nrhs, d_x
+        _lib.lexls_lse_residual_rhs.restype = C.c_int
+        _lib.lexls_lse_residual_rhs.argtypes = [C.c_void_p, C.POINTER(C.c_double), C.POINTER(C.c_double), C.c_uint32]  # h_rhs, h_fixed, nrhs
+        _lib.lexls_lse_get_residual_rhs.restype = C.c_int
+        _lib.lexls_lse_get_residual_rhs.argtypes = [C.c_void_p, C.POINTER(C.c_double), C.POINTER(C.c_double)]  # h_v, h_cost
+        _lib.lexls_lse_residual_rhs_device.restype = C.c_int
+        _lib.lexls_lse_residual_rhs_device.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p]  # d_rhs, d_fixed, nrhs, d_x, d_v, d_cost
         _lib.lexls_internal_apply_solve_map.restype = C.c_int
         _lib.lexls_internal_apply_solve_map.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]  # d_rhs, d_out: device addresses
         _lib.lexls_lsi_batch_solve_adjoint_multi.restype = C.c_int
@@ -178,6 +186,12 @@ def lib() -> C.CDLL:
                                                       C.POINTER(C.c_uint8)]  # h_lb, h_ub, nrhs, h_x, h_violation, h_valid
         _lib.lexls_lsi_batch_solve_bounds_device.restype = C.c_int
         _lib.lexls_lsi_batch_solve_bounds_device.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p]  # d_lb, d_ub, nrhs, d_x, d_violation, d_valid
+        _lib.lexls_lsi_batch_solve_bounds_cost.restype = C.c_int
+        _lib.lexls_lsi_batch_solve_bounds_cost.argtypes = [C.c_void_p, C.POINTER(C.c_double), C.POINTER(C.c_double), C.c_uint32, C.POINTER(C.c_double), C.POINTER(C.c_double),
+                                                           C.POINTER(C.c_double), C.POINTER(C.c_uint8)]  # h_lb, h_ub, nrhs, h_x, h_violation, h_cost, h_valid
+        _lib.lexls_lsi_batch_solve_bounds_cost_device.restype = C.c_int
+        _lib.lexls_lsi_batch_solve_bounds_cost_device.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p,
+                                                                  C.c_void_p]  # d_lb, d_ub, nrhs, d_x, d_violation, d_cost, d_valid
         _lib.lexls_lsi_batch_last_consumer_kernel.restype = C.c_char_p
         _lib.lexls_lsi_batch_last_consumer_kernel.argtypes = [C.c_void_p]
         _lib.lexls_lsi_batch_final_factorizations.restype = C.c_int

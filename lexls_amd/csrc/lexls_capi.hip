@@ -151,13 +151,14 @@ struct lexls_lse_s
     //   adjA  lexls_lse_solve_adjoint_matrix  g (batch x nVar) | the gradient (batch x (nVar + 1) x cap) | the flags (batch)
     //   tan   lexls_lse_solve_tangent         the directions (ntan x batch x (nVar + 1) x cap | ntan x batch x nVar) | dx (ntan x batch x nVar); tan_flag: its flags (batch)
     //   srhs  lexls_lse_solve_rhs             the right-hand sides (nrhs x batch x cap) | fixed values | solutions (nrhs x batch x nVar)
+    //   rres  lexls_lse_residual_rhs          the right-hand sides (nrhs x batch x cap) | fixed values | v (nrhs x batch x cap), then the costs (nrhs x batch x nObj)
     // made for the largest count so far (adj, adjA: one).  The work buffers both forms of a call run on, each made when a call first needs it:
     //   adj_work    the matrices of the regularized adjoint where they do not fit in LDS (adjoint_reg_work_bytes)
     //   adjm_work   the buffers of the per-cotangent form (adjoint_multi_work_bytes); the tangents' M^T w runs on them too
     //   adjrm_work  the matrices of the regularized multi kernel where they do not fit in LDS (adjoint_reg_multi_work_bytes): grows with the tiles of 64 cotangents
     //   adjA_work   the chain of launch_solve_adjoint_matrix (adjoint_matrix_work_bytes)
-    //   tan_work, srhs_work  the chains of launch_solve_tangent and launch_solve_rhs: grow with the count, and with the placement
-    HostResults adj, adjm, adjA, tan, srhs;
+    //   tan_work, srhs_work  the chains of launch_solve_tangent and launch_solve_rhs: grow with the count, and with the placement (srhs_work: launch_residual_rhs too)
+    HostResults adj, adjm, adjA, tan, srhs, rres;
     DeviceBuffer adj_work, adjm_work, adjrm_work, adjA_work, tan_flag, tan_work, srhs_work;
     bool adj_regularized       = false; // lexls_lse_set_adjoint_regularized: the single-cotangent calls serve damped factorizations (off: UNSUPPORTED, as before)
     bool adj_regularized_multi = false; // lexls_lse_set_adjoint_regularized_multi: the multi-cotangent calls serve damped factorizations (off: UNSUPPORTED, as before)
@@ -359,7 +360,7 @@ extern "C"
         for (void *p : ptrs)
             if (p) (void)hipFree(p);
         h->adj.release(), h->adj_work.release(), h->adjm.release(), h->adjm_work.release(), h->adjrm_work.release(), h->adjA.release(), h->adjA_work.release();
-        h->tan.release(), h->tan_flag.release(), h->tan_work.release(), h->srhs.release(), h->srhs_work.release();
+        h->tan.release(), h->tan_flag.release(), h->tan_work.release(), h->srhs.release(), h->srhs_work.release(), h->rres.release();
         if (h->h_dims_pinned) (void)hipHostFree(h->h_dims_pinned);
         if (h->dims_event) (void)hipEventDestroy(h->dims_event);
         delete h;

@@ -57,6 +57,15 @@ namespace lexls
     size_t solve_rhs_work_bytes(const LseArgs &a, uint32_t nrhs);
     hipError_t launch_solve_rhs(const LseArgs &a, const double *d_rhs, const double *d_fixed, uint32_t nrhs, double *d_x, void *d_work, hipStream_t s,
                                 const char **variant = nullptr);
+    /// lexls_lse_residual_rhs: for the right-hand sides and fixed values of launch_solve_rhs on an UNDAMPED kept factor (a.reg_type != 0:
+    /// hipErrorInvalidValue), d_v (nrhs x batch x cap, LOD row order, zeros behind a problem's own rows) = get_v() of each, d_cost (nrhs x batch x
+    /// nObj) = the sum of squares of each level's rows of it, d_x = launch_solve_rhs's x, bit for bit; each may be NULL, not all.  Chains, in the
+    /// stream: solve_rhs_front_kernel, then residual_rhs_kernel under tangent_map_placement — launch_solve_rhs's pass with the residuals formed
+    /// behind it on the same state (nrhs == 1 with d_x: apply_solve_map_kernel for x in front of it, as launch_solve_rhs takes it).  Everything
+    /// else they write goes to d_work (residual_rhs_work_bytes for this nrhs).  Enqueued only; no atomics
+    size_t residual_rhs_work_bytes(const LseArgs &a, uint32_t nrhs);
+    hipError_t launch_residual_rhs(const LseArgs &a, const double *d_rhs, const double *d_fixed, uint32_t nrhs, double *d_x, double *d_v, double *d_cost, void *d_work,
+                                   hipStream_t s, const char **variant = nullptr);
     /// lexls_lse_solve_adjoint_matrix: d_grad_lod (batch x (nVar + 1) x cap, the layout of the problem data) = the gradient with respect to A and
     /// b for the cotangent d_g (batch x nVar), d_differentiable (batch bytes, may be NULL) = the rank-stability flags; a.x holds the solution of the
     /// kept factor.  Chains, in the stream: launch_solve_adjoint (y), the level search (k*), launch_sensitivity for level k* (lambda; its own rows

@@ -323,6 +323,11 @@ namespace lexls
     {
         return p == TangentPlacement::staged ? "solve_rhs<64,staged>" : p == TangentPlacement::lds ? "solve_rhs<64,lds>" : "solve_rhs<64,work>";
     }
+    /// lexls_lse_residual_rhs (residual_rhs_kernel): the same state under the same rule — the residuals are formed in place on it
+    inline const char *residual_rhs_placement_name(TangentPlacement p)
+    {
+        return p == TangentPlacement::staged ? "residual_rhs<64,staged>" : p == TangentPlacement::lds ? "residual_rhs<64,lds>" : "residual_rhs<64,work>";
+    }
     /// damped factors (apply_solve_map_reg_multi_kernel): the per-lane state t (cap), z, r, the right-hand side of D (nVar each), [index][lane];
     /// the problem's matrices, shared by the lanes: the null-space basis and D (nVar x nVar each — the forward pass reads the basis as it
     /// stands at a level's entry, so it keeps no snapshots)
@@ -376,6 +381,8 @@ namespace lexls
         return bounds_check_lds_bytes(nVar, BoundsCheckPlacement::lds) <= kBoundsCheckLdsBudget ? BoundsCheckPlacement::lds : BoundsCheckPlacement::hbm;
     }
     inline const char *bounds_check_placement_name(BoundsCheckPlacement p) { return p == BoundsCheckPlacement::lds ? "lsi_bounds_check<lds>" : "lsi_bounds_check<hbm>"; }
+    /// lexls_lsi_batch_solve_bounds_cost: lsi_bounds_check_kernel<placement, true>, the variant with the per-objective costs, under the same rule
+    inline const char *bounds_cost_placement_name(BoundsCheckPlacement p) { return p == BoundsCheckPlacement::lds ? "lsi_bounds_cost<lds>" : "lsi_bounds_cost<hbm>"; }
 
     // ---- lqr_large (lqr_large.hip): lqr_large_plan.h ----
 } // namespace lexls

@@ -340,17 +340,20 @@ extern "C"
     }
 
     /// both forms of the re-solve on new bounds: the refusals of lsi_batch_solve_tangent, plus nrhs > 65535 and null bounds
-    static int lsi_batch_solve_bounds(lexls_lsi_batch_t b, const double *lb, const double *ub, uint32_t nrhs, double *x, double *violation, uint8_t *valid, bool on_device)
+    /// (with_cost: lexls_lsi_batch_solve_bounds_cost(_device) — cost is the output that must be there, x may be NULL)
+    static int lsi_batch_solve_bounds(lexls_lsi_batch_t b, const double *lb, const double *ub, uint32_t nrhs, double *x, double *violation, uint8_t *valid, bool on_device,
+                                      bool with_cost = false, double *cost = NULL)
     {
         return guarded([&]() {
-            const std::string who = on_device ? "lexls_lsi_batch_solve_bounds_device" : "lexls_lsi_batch_solve_bounds";
+            const std::string who = std::string("lexls_lsi_batch_solve_bounds") + (with_cost ? "_cost" : "") + (on_device ? "_device" : "");
             if (!b) throw Exception(who + ": null handle");
             if (!lb || !ub) throw Exception(who + ": null lb / ub");
-            if (!x) throw Exception(who + ": null x");
+            if (!with_cost && !x) throw Exception(who + ": null x");
+            if (with_cost && !cost) throw Exception(who + ": null cost");
             if (nrhs == 0) throw Exception(who + ": nrhs == 0");
             if (nrhs > 65535u) throw Exception(who + ": more than 65535 bound sets per instance");
             b->refuse_pending(who.c_str());
-            return b->fin.solve_bounds(lb, ub, nrhs, x, violation, valid, on_device);
+            return b->fin.solve_bounds(lb, ub, nrhs, x, violation, valid, on_device, with_cost, cost);
         });
     }
 
@@ -362,6 +365,18 @@ extern "C"
     int lexls_lsi_batch_solve_bounds_device(lexls_lsi_batch_t b, const double *d_lb, const double *d_ub, uint32_t nrhs, double *d_x, double *d_violation, uint8_t *d_valid)
     {
         return lsi_batch_solve_bounds(b, d_lb, d_ub, nrhs, d_x, d_violation, d_valid, true);
+    }
+
+    int lexls_lsi_batch_solve_bounds_cost(lexls_lsi_batch_t b, const double *h_lb, const double *h_ub, uint32_t nrhs, double *h_x, double *h_violation, double *h_cost,
+                                          uint8_t *h_valid)
+    {
+        return lsi_batch_solve_bounds(b, h_lb, h_ub, nrhs, h_x, h_violation, h_valid, false, true, h_cost);
+    }
+
+    int lexls_lsi_batch_solve_bounds_cost_device(lexls_lsi_batch_t b, const double *d_lb, const double *d_ub, uint32_t nrhs, double *d_x, double *d_violation, double *d_cost,
+                                                 uint8_t *d_valid)
+    {
+        return lsi_batch_solve_bounds(b, d_lb, d_ub, nrhs, d_x, d_violation, d_valid, true, true, d_cost);
     }
 
     const char *lexls_lsi_batch_last_consumer_kernel(lexls_lsi_batch_t b) { return b ? b->fin.bounds_kernel : ""; }

@@ -781,6 +781,99 @@ namespace lexls
             }
         }
 
+        /// lexls_lse_residual_rhs: get_v() and the cost per level for up to 64 right-hand sides of one problem at once on the kept, UNDAMPED factor,
+        /// LANE = RIGHT-HAND SIDE — apply_solve_map_multi_kernel<NT, PLACE, false>'s pass (the same steps on the same state in the same order: dx,
+        /// where asked for, has that kernel's bits), and behind it the residual of every level out of what the pass left in t:
+        ///     v_k = Q_k [0 ; -tail_k],   tail_k = rows rank_k .. dim_k - 1 of the level's transformed right-hand side   (lane_level_residual)
+        /// a level of rank 0 (also: every variable fixed, or no pivot column left) has no Q: v_k = -t_k.  cost[c, b, k] = the lane's own fma chain over
+        /// the level's rows of v, in row order.  No cross-lane sum, no barrier between the steps: a right-hand side's bits do not depend on its lane,
+        /// its tile or its neighbours.  One wavefront per (problem, tile of 64 right-hand sides); lanes beyond nrhs compute on zeros and store nothing.
+        /// R: batch x nrhs x cap and fixed: nrhs x batch x nVar (solve_rhs_front_kernel's); dx (nrhs x batch x nVar), v (nrhs x batch x cap, zeros
+        /// behind the problem's own rows), cost (nrhs x batch x nObj): each may be NULL.  PLACE: TangentPlacement, the state where that kernel keeps
+        /// it (the same LDS, the same work doubles per (problem, tile)).  No atomics.
+        template <int NT, int PLACE>
+        __global__ __launch_bounds__(NT) void residual_rhs_kernel(LseArgs a, const double *__restrict__ R, const double *__restrict__ fixed, uint32_t nrhs, double *__restrict__ dx,
+                                                                  double *__restrict__ v, double *__restrict__ cost, double *work)
+        {
+            static_assert(NT == 64, "one wavefront per (problem, tile): lane = right-hand side");
+            constexpr bool STAGED = PLACE == 0, IN_WORK = PLACE == 2;
+            constexpr uint32_t LD = IN_WORK ? kTangentWorkLd : kAdjointMultiLd;
+            extern __shared__ double smem[];
+            const uint32_t b = blockIdx.x, tile = blockIdx.y, lane = threadIdx.x;
+            if (b >= a.batch || tile * 64u >= nrhs) return; // (block-uniform)
+            const uint32_t kt = nrhs - tile * 64u < 64u ? nrhs - tile * 64u : 64u; // live right-hand sides of this tile
+            const KeptFactor kf = kept_factor_of(a, b);
+            const uint32_t n = kf.n, cap = kf.cap, nObj = kf.nObj, nf = kf.nf, T = kf.T, M = kf.M;
+            const double *__restrict__ W = kf.W;
+            double *state    = IN_WORK ? work + ((size_t)b * gridDim.y + tile) * tangent_map_work_doubles(n, cap) : smem;
+            double *z        = state;
+            double *t        = z + (size_t)n * LD;
+            uint32_t *perm_l = reinterpret_cast<uint32_t *>(IN_WORK ? smem : t + (size_t)cap * LD);
+            uint32_t *pos_l  = perm_l + n;
+            double *L        = reinterpret_cast<double *>(pos_l + n); // (2 n words: still 8-byte aligned)
+            const uint32_t ldl = cap | 1u;                            // odd_ld(cap)
+            double *hh_l       = L + (size_t)ldl * n;
+            auto Wat = [&](uint32_t r, uint32_t c) __attribute__((always_inline)) -> double { return STAGED ? L[r + c * ldl] : W[r + (size_t)c * cap]; };
+            auto tau_at = [&](uint32_t r) __attribute__((always_inline)) -> double { return STAGED ? hh_l[r] : kf.hh[r]; };
+            const size_t B = a.batch;
+
+            // ---- staging; t = R for every right-hand side of the tile, z = 0 ----
+            for (uint32_t i = lane; i < n; i += NT) perm_l[i] = a.perm[(size_t)b * n + i];
+            for (uint32_t i = lane; i < (n + cap) * LD; i += NT) state[i] = 0.0; // (dead lanes, absent rows, unreached columns: zeros)
+            if (STAGED)
+            {
+                for (uint32_t i = lane; i < cap; i += NT) hh_l[i] = kf.hh[i];
+                stage_factor<NT>(W, L, cap, n, ldl, lane); // (ends in a barrier)
+            }
+            else
+                __syncthreads();
+            for (uint32_t i = lane; i < n; i += NT) pos_l[i] = position_after_transpositions(perm_l, T, i);
+            lane_load_rhs<NT, LD>(R, nullptr, ((size_t)b * nrhs + (size_t)tile * 64u) * cap, 0, 0, t, kt, cap, M, lane);
+            __syncthreads();
+            double *zl = z + lane, *tl = t + lane; // this lane's column of the state
+
+            // ---- factorize()'s right-hand-side updates, levels ascending, then solve(), levels descending: apply_solve_map_multi_kernel's ----
+            const uint32_t rows = kf.for_levels_ascending([&](uint32_t k, uint32_t dim, uint32_t F, uint32_t rank, uint32_t Fc) __attribute__((always_inline)) {
+                lane_reflectors_forward<LD>(Wat, tau_at, tl, F, Fc, dim, rank);
+                const uint32_t Fn = F + dim;
+                if (k + 1 < nObj && Fn < M) lane_gauss<LD>(Wat, tl, F, Fn, M, Fc, rank);
+            });
+            if (dx) // (uniform) the solution is asked for too
+            {
+                kf.for_levels_descending(rows, [&](uint32_t, uint32_t, uint32_t F, uint32_t rank, uint32_t Fc) __attribute__((always_inline)) {
+                    lane_back_substitute_level<LD>(Wat, tl, zl, F, Fc, rank, T);
+                });
+                __syncthreads();
+                for (uint32_t e = lane; e < kt * n; e += NT)
+                {
+                    const uint32_t c = e / n, i = e - c * n, p = pos_l[i];
+                    const size_t row = ((size_t)tile * 64u + c) * B + b;
+                    dx[row * n + i]  = p < nf ? fixed[row * n + p] : (p < T ? z[p * LD + c] : 0.0);
+                }
+            }
+
+            // ---- get_v(), every level of the problem's own rows (a level of rank 0 too): in place on the lane's column of t ----
+            uint32_t F = 0, k = 0;
+            for (; k < nObj; k++)
+            {
+                const uint32_t dim = kf.dims[k];
+                if (F + dim > M) break; // (rows the problem does not hold: zeros from here on)
+                const auto [rank, Fc] = kf.level(k, dim);
+                const double ck       = lane_level_residual<LD>(Wat, tau_at, tl, F, Fc, dim, rank);
+                if (cost && lane < kt) cost[(((size_t)tile * 64u + lane) * B + b) * nObj + k] = ck;
+                F += dim;
+            }
+            for (; k < nObj; k++)
+                if (cost && lane < kt) cost[(((size_t)tile * 64u + lane) * B + b) * nObj + k] = 0.0;
+            if (!v) return;
+            __syncthreads();
+            for (uint32_t e = lane; e < kt * cap; e += NT)
+            {
+                const uint32_t c = e / cap, r = e - c * cap;
+                v[(((size_t)tile * 64u + c) * B + b) * cap + r] = r < F ? t[r * LD + c] : 0.0;
+            }
+        }
+
         // new right-hand sides on the kept factor (lexls_lse_solve_rhs): the kernel in front of the map, the map of a damped factor
         /// Right-hand side c = blockIdx.y of problem b = blockIdx.x (rhs: nrhs x batch x cap, LOD row order; fixed: nrhs x batch x nVar, slot
         /// j < nfixed, NULL: the values the handle holds, a.fixed_val): per row i of the problem's own
@@ -1296,6 +1389,62 @@ namespace lexls
             break;
         }
         if (variant) *variant = solve_rhs_placement_name(place);
+        return hipGetLastError();
+    }
+
+    /// R (batch x nrhs x cap) | the fixed slots (nrhs x batch x nVar) | under the work placement the per-lane vectors of every (problem, tile)
+    size_t residual_rhs_work_bytes(const LseArgs &a, uint32_t nrhs)
+    {
+        const size_t B = a.batch, tiles = (nrhs + 63u) / 64u;
+        size_t bytes = 8 * B * nrhs * ((size_t)a.cap + a.nVar);
+        if (tangent_placement_for(a.nVar, a.cap, a.nObj) == TangentPlacement::work) bytes += 8 * B * tiles * tangent_map_work_doubles(a.nVar, a.cap);
+        return bytes;
+    }
+
+    hipError_t launch_residual_rhs(const LseArgs &a, const double *d_rhs, const double *d_fixed, uint32_t nrhs, double *d_x, double *d_v, double *d_cost, void *d_work,
+                                   hipStream_t s, const char **variant)
+    {
+        const uint32_t tiles = (nrhs + 63u) / 64u;
+        if (!d_work || !d_rhs || (!d_x && !d_v && !d_cost) || nrhs == 0 || nrhs > 65535u || a.reg_type != 0) return hipErrorInvalidValue;
+        const size_t B = a.batch, n = a.nVar, cap = a.cap;
+        const TangentPlacement place = tangent_placement_for(a.nVar, a.cap, a.nObj); // solve_rhs's rule: the state is that kernel's
+        const size_t lds_front = 8 * n, lds = tangent_map_lds_bytes(a.nVar, a.cap, a.nObj, place);
+        // one right-hand side: x is the single-vector kernel's, as lexls_lse_solve_rhs's is (its sums are wavefront sums); v and cost are the lane kernel's
+        const bool single_x = nrhs == 1 && d_x;
+        if (lds > kMaxLdsBytes || lds_front > kMaxLdsBytes || (single_x && adjoint_lds_bytes(a.nVar, a.cap) > kMaxLdsBytes)) return hipErrorInvalidValue; // (before anything is enqueued)
+        double *w_r = static_cast<double *>(d_work), *w_f = w_r + B * nrhs * cap, *w_state = w_f + B * nrhs * n;
+        hipError_t e = set_lds(solve_rhs_front_kernel<64>, lds_front);
+        if (e != hipSuccess) return e;
+        hipLaunchKernelGGL((solve_rhs_front_kernel<64>), dim3(a.batch, nrhs), dim3(64), lds_front, s, a, d_rhs, d_fixed, nrhs, w_r, w_f);
+        if ((e = hipGetLastError()) != hipSuccess) return e;
+        if (single_x)
+        {
+            if ((e = set_lds(apply_solve_map_kernel<64, true>, adjoint_lds_bytes(a.nVar, a.cap))) != hipSuccess) return e;
+            hipLaunchKernelGGL((apply_solve_map_kernel<64, true>), dim3(a.batch), dim3(64), adjoint_lds_bytes(a.nVar, a.cap), s, a, w_r, nullptr, d_x, w_f);
+            if ((e = hipGetLastError()) != hipSuccess) return e;
+            d_x = nullptr;
+            if (!d_v && !d_cost)
+            {
+                if (variant) *variant = "solve_rhs<64,single>";
+                return hipSuccess;
+            }
+        }
+        switch (place)
+        {
+        case TangentPlacement::staged:
+            if ((e = set_lds(residual_rhs_kernel<64, 0>, lds)) != hipSuccess) return e;
+            hipLaunchKernelGGL((residual_rhs_kernel<64, 0>), dim3(a.batch, tiles), dim3(64), lds, s, a, w_r, w_f, nrhs, d_x, d_v, d_cost, nullptr);
+            break;
+        case TangentPlacement::lds:
+            if ((e = set_lds(residual_rhs_kernel<64, 1>, lds)) != hipSuccess) return e;
+            hipLaunchKernelGGL((residual_rhs_kernel<64, 1>), dim3(a.batch, tiles), dim3(64), lds, s, a, w_r, w_f, nrhs, d_x, d_v, d_cost, nullptr);
+            break;
+        case TangentPlacement::work:
+            if ((e = set_lds(residual_rhs_kernel<64, 2>, lds)) != hipSuccess) return e;
+            hipLaunchKernelGGL((residual_rhs_kernel<64, 2>), dim3(a.batch, tiles), dim3(64), lds, s, a, w_r, w_f, nrhs, d_x, d_v, d_cost, w_state);
+            break;
+        }
+        if (variant) *variant = residual_rhs_placement_name(place);
         return hipGetLastError();
     }
 } // namespace lexls

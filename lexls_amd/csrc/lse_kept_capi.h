@@ -1,5 +1,5 @@
 // The calls of the C ABI (include/lexls_hip.h) that work on a kept LexLSE factor beyond the solves of lexls_capi.hip, which includes this file once:
-// lexls_lse_solve_adjoint, _adjoint_multi, _adjoint_matrix, _tangent and _rhs.  Every family has a device form (checks, work buffers, launch: enqueue
+// lexls_lse_solve_adjoint, _adjoint_multi, _adjoint_matrix, _tangent, _rhs and lexls_lse_residual_rhs.  Every family has a device form (checks, work buffers, launch: enqueue
 // only), a host form (the handle's HostResults of the family: make room, upload, the device form's function, stamp) and a getter (HostResults::fetch).
 #pragma once
 
@@ -156,6 +156,27 @@ namespace
         HIP_TRY(hipSetDevice(h->device));
         HIP_TRY(h->srhs_work.reserve(solve_rhs_work_bytes(h->args(), nrhs)));
         HIP_TRY(launch_solve_rhs(h->args(), d_rhs, d_fixed, nrhs, d_x, h->srhs_work.ptr, h->stream, &h->last_consumer));
+        return LEXLS_OK;
+    }
+
+    /// what every form of lexls_lse_residual_rhs checks before any device work: lexls_lse_solve_rhs's, and an UNDAMPED factor
+    int need_residual_rhs(lexls_lse_t h, const char *who, const void *rhs, bool any_output, uint32_t nrhs)
+    {
+        CHECK_HANDLE(h);
+        if (!rhs) return fail(LEXLS_ERR_INVALID, std::string(who) + ": null rhs");
+        if (!any_output) return fail(LEXLS_ERR_INVALID, std::string(who) + ": every output is null");
+        if (nrhs == 0) return fail(LEXLS_ERR_INVALID, std::string(who) + ": nrhs == 0");
+        if (nrhs > 65535u) return fail(LEXLS_ERR_INVALID, std::string(who) + ": nrhs > 65535 (split the right-hand sides over several calls)");
+        return need_affine_factor(h, who, ": the factorization ran with regularization_type != 0 (v is the residual of the undamped basic solution; "
+                                          "lexls_lse_solve_rhs serves damped factors, this call serves none)");
+    }
+    /// every form of lexls_lse_residual_rhs on device memory: the checks, the work buffer (lexls_lse_solve_rhs's: scratch of either call), the launch
+    int run_residual_rhs(lexls_lse_t h, const char *who, const double *d_rhs, const double *d_fixed, uint32_t nrhs, double *d_x, double *d_v, double *d_cost)
+    {
+        if (int rc = need_residual_rhs(h, who, d_rhs, d_x || d_v || d_cost, nrhs)) return rc;
+        HIP_TRY(hipSetDevice(h->device));
+        HIP_TRY(h->srhs_work.reserve(residual_rhs_work_bytes(h->args(), nrhs)));
+        HIP_TRY(launch_residual_rhs(h->args(), d_rhs, d_fixed, nrhs, d_x, d_v, d_cost, h->srhs_work.ptr, h->stream, &h->last_consumer));
         return LEXLS_OK;
     }
 } // namespace
@@ -317,6 +338,36 @@ extern "C"
         CHECK_HANDLE(h);
         const HostResults &r = h->srhs;
         return r.fetch(h, "lexls_lse_get_solve_rhs", "lexls_lse_solve_rhs", {{h_x, r.buf[2].ptr, 8 * (size_t)h->batch * r.count * h->nVar}});
+    }
+
+    int lexls_lse_residual_rhs(lexls_lse_t h, const double *h_rhs, const double *h_fixed, uint32_t nrhs)
+    {
+        const char *who = "lexls_lse_residual_rhs";
+        if (int rc = need_residual_rhs(h, who, h_rhs, true, nrhs)) return rc;
+        HIP_TRY(hipSetDevice(h->device));
+        const size_t B = h->batch, n = h->nVar, cap = h->cap, nObj = h->nObj;
+        HostResults &r = h->rres;
+        HIP_TRY(r.make_room(nrhs, {8 * B * nrhs * cap, 8 * B * nrhs * n, 8 * B * nrhs * (cap + nObj)}));
+        if (h_fixed) HIP_TRY(hipMemcpyAsync(r.buf[1].ptr, h_fixed, 8 * B * nrhs * n, hipMemcpyHostToDevice, h->stream));
+        if (int rc = upload_input(h, r.buf[0], h_rhs, 8 * B * nrhs * cap)) return rc;
+        if (int rc = run_residual_rhs(h, who, r.at<double>(0), h_fixed ? r.at<double>(1) : nullptr, nrhs, nullptr, r.at<double>(2), r.at<double>(2) + B * nrhs * cap)) return rc;
+        r.stamp(nrhs, h->factor_epoch);
+        return LEXLS_OK;
+    }
+
+    int lexls_lse_residual_rhs_device(lexls_lse_t h, const double *d_rhs, const double *d_fixed, uint32_t nrhs, double *d_x, double *d_v, double *d_cost)
+    {
+        return run_residual_rhs(h, "lexls_lse_residual_rhs_device", d_rhs, d_fixed, nrhs, d_x, d_v, d_cost);
+    }
+
+    int lexls_lse_get_residual_rhs(lexls_lse_t h, double *h_v, double *h_cost)
+    {
+        CHECK_HANDLE(h);
+        if (!h_v && !h_cost) return fail(LEXLS_ERR_INVALID, "lexls_lse_get_residual_rhs: null h_v and h_cost");
+        const HostResults &r = h->rres;
+        const size_t rows    = (size_t)h->batch * r.count;
+        return r.fetch(h, "lexls_lse_get_residual_rhs", "lexls_lse_residual_rhs",
+                       {{h_v, r.buf[2].ptr, 8 * rows * h->cap}, {h_cost, r.at<double>(2) + rows * h->cap, 8 * rows * h->nObj}});
     }
 
     int lexls_internal_apply_solve_map(lexls_lse_t h, const double *d_rhs, double *d_out)

@@ -3,7 +3,7 @@
 //   lane_*    LANE = VECTOR: the lane's own column of a state laid out [index][lane] with leading dimension LD (65 in LDS, 64 in a work
 //             buffer); every sum is the lane's serial dfma chain, no cross-lane traffic, no barrier — a vector's bits do not depend on its
 //             lane, its tile or its neighbours.  The factor comes through an accessor Wat(r, c) (staged in LDS or read where it is kept).
-//             Consumers: solve_adjoint_multi_kernel, solve_adjoint_reg_multi_kernel, apply_solve_map_multi_kernel, apply_solve_map_reg_multi_kernel
+//             Consumers: solve_adjoint_multi_kernel, solve_adjoint_reg_multi_kernel, apply_solve_map_multi_kernel, apply_solve_map_reg_multi_kernel, residual_rhs_kernel
 //   shared_*  work of the PROBLEM, the lanes of one wavefront spread over entries, barriers inside: the null-space basis and the damped
 //             normal matrix of a regularized factor.  Consumers: solve_adjoint_reg_kernel, solve_adjoint_reg_multi_kernel,
 //             apply_solve_map_reg_multi_kernel
@@ -173,6 +173,22 @@ namespace lexls
             zl[(Fc + j) * LD] = zc;
             for (uint32_t i = 0; i < j; i++) tl[(F + i) * LD] = dfma(-Wat(F + i, Fc + j), zc, tl[(F + i) * LD]);
         }
+    }
+    /// get_v() at one level on the lane's column, in place: v = Q_k [0 ; -tail], where tl rows F .. F + dim hold the level's right-hand side as
+    /// the forward pass left it (reflectors, then the Gauss steps of the levels above): the tail, rows rank .. dim - 1, is written by no later
+    /// step — a Gauss step writes the rows of the levels BEHIND its own, the back-substitution the first `rank` rows of its own.  Returns the
+    /// level's cost, the sum of squares of its rows of v as one fma chain in row order.  rank == dim (uniform): nothing goes through Q, exact zeros
+    template <uint32_t LD, class WAT, class TAU>
+    __device__ __forceinline__ double lane_level_residual(const WAT &Wat, const TAU &tau_at, double *tl, uint32_t F, uint32_t Fc, uint32_t dim, uint32_t rank)
+    {
+        double *v = tl + F * LD;
+        for (uint32_t i = 0; i < rank; i++) v[i * LD] = 0.0;
+        if (rank >= dim) return 0.0;
+        for (uint32_t i = rank; i < dim; i++) v[i * LD] = -v[i * LD];
+        lane_reflectors_reversed<LD>(Wat, tau_at, tl, F, Fc, dim, rank);
+        double cost = 0.0;
+        for (uint32_t i = 0; i < dim; i++) cost = dfma(v[i * LD], v[i * LD], cost);
+        return cost;
     }
     /// entry c of W^T y for the level's W (column c has min(c + 1, rank) rows), y = yb[0, rank)
     template <uint32_t LD, class WAT>

@@ -288,13 +288,17 @@ namespace
     /// j = 0 .. n - 1 (no cross-lane sums: a bound set's bits do not depend on nrhs, its position or its company).  lb / ub of kBoundsCheckRows rows
     /// at a time are loaded along the rows (consecutive lanes at consecutive addresses) and turned to [row][lane] in LDS.  Rows at and behind an
     /// instance's count are never read.  valid[b] = status PROBLEM_SOLVED, written by tile 0.  A masked instance keeps the bits of all three outputs.
-    template <bool XLDS>
+    /// COST (lexls_lsi_batch_solve_bounds_cost: "lsi_bounds_cost<lds|hbm>"; false: every line of it is compiled out, and `cost` is not read):
+    /// besides, cost[c, b, o] (nrhs x batch x nObj) = the sum over objective o's present rows, in the user's row order, of d^2, d = max(lb - a.x,
+    /// a.x - ub, 0) with the very a.x of the violation — the lane's own ordered fma chain —, exact zeros where the instance did not end
+    /// PROBLEM_SOLVED; x may be NULL there (not wanted).
+    template <bool XLDS, bool COST = false>
     __global__ __launch_bounds__(64) void lsi_bounds_check_kernel(const double *__restrict__ x_lse, const double *__restrict__ lbq, const double *__restrict__ ubq,
                                                                   const double *__restrict__ cdata, const uint32_t *__restrict__ var, const uint32_t *__restrict__ counts,
                                                                   uint32_t counts_ld, const uint32_t *__restrict__ map, const int32_t *__restrict__ meta,
                                                                   const uint32_t *__restrict__ shape, uint32_t B, uint32_t batch, uint32_t lo, uint32_t nrhs, uint32_t nObj,
                                                                   uint32_t total, uint32_t n, uint32_t cap, size_t per_data, double *__restrict__ x, double *__restrict__ violation,
-                                                                  uint8_t *__restrict__ valid, const uint8_t *mask)
+                                                                  uint8_t *__restrict__ valid, const uint8_t *mask, double *__restrict__ cost)
     {
         extern __shared__ double s_bounds[];
         constexpr uint32_t LD = lexls::kAdjointMultiLd, ROWS = lexls::kBoundsCheckRows;
@@ -312,15 +316,17 @@ namespace
         {
             const uint32_t cc = e / n, j = e - cc * n;
             const double val  = live ? x_lse[((size_t)(c0 + cc) * B + b) * n + j] : 0.0;
-            x[((size_t)(c0 + cc) * batch + lo + b) * n + j] = val;
+            if (!COST || x) x[((size_t)(c0 + cc) * batch + lo + b) * n + j] = val;
             if (XLDS) s_x[j * LD + cc] = val;
         }
         if (!solved) // (block-uniform: exact zeros)
         {
             if (violation && lane < nc) violation[(size_t)c * batch + lo + b] = 0.0;
+            if constexpr (COST)
+                for (uint32_t e = lane; e < nc * nObj; e += 64) cost[((size_t)(c0 + e / nObj) * batch + lo + b) * nObj + e % nObj] = 0.0;
             return;
         }
-        if (!violation) return;
+        if (!COST && !violation) return;
         __syncthreads();
         const double *xg    = live ? x_lse + ((size_t)min(c, nrhs - 1) * B + b) * n : NULL; // (!XLDS: the lane's own vector)
         const double *d_b   = cdata + (size_t)b * per_data;
@@ -332,6 +338,7 @@ namespace
             const uint32_t dim = shape[4 * o], general = shape[4 * o + 1], first = shape[4 * o + 3];
             const uint32_t cnt = counts && o < counts_ld ? min(counts[(size_t)b * counts_ld + o], dim) : dim;
             const double *blk  = d_b + shape[4 * o + 2];
+            [[maybe_unused]] double co = 0.0; // (COST: the objective's cost of this lane's bound set)
             for (uint32_t i0 = 0; i0 < cnt; i0 += ROWS)
             {
                 const uint32_t len = min(ROWS, cnt - i0);
@@ -365,12 +372,19 @@ namespace
                     {
                         const double l = s_lb[rr * LD + lane], u = s_ub[rr * LD + lane];
                         viol = fmax(viol, fmax(fmax(l - ax, ax - u), l - u));
+                        if constexpr (COST)
+                        {
+                            const double d = fmax(fmax(l - ax, ax - u), 0.0);
+                            co             = fma(d, d, co);
+                        }
                     }
                 }
                 __syncthreads();
             }
+            if constexpr (COST)
+                if (lane < nc) cost[((size_t)c * batch + lo + b) * nObj + o] = co;
         }
-        if (lane < nc) violation[(size_t)c * batch + lo + b] = viol;
+        if ((!COST || violation) && lane < nc) violation[(size_t)c * batch + lo + b] = viol;
     }
 } // namespace
 
@@ -1142,14 +1156,14 @@ struct LsiFinal
     /// a host caller's bounds, solutions, violations and flags on the device (made for the largest request so far)
     struct BoundsStage
     {
-        double *d_lb = NULL, *d_ub = NULL, *d_x = NULL, *d_viol = NULL;
+        double *d_lb = NULL, *d_ub = NULL, *d_x = NULL, *d_viol = NULL, *d_cost = NULL; // (d_cost: made by the first lexls_lsi_batch_solve_bounds_cost)
         uint8_t *d_valid = NULL;
-        uint32_t room = 0;
+        uint32_t room = 0, cost_room = 0;
         void release()
         {
-            for (void *q : {(void *)d_lb, (void *)d_ub, (void *)d_x, (void *)d_viol})
+            for (void *q : {(void *)d_lb, (void *)d_ub, (void *)d_x, (void *)d_viol, (void *)d_cost})
                 if (q) (void)hipFree(q);
-            d_lb = d_ub = d_x = d_viol = NULL, room = 0;
+            d_lb = d_ub = d_x = d_viol = d_cost = NULL, room = cost_room = 0;
         }
         ~BoundsStage()
         {
@@ -1165,9 +1179,12 @@ struct LsiFinal
     /// lexls_lse_solve_rhs_device, lsi_bounds_check_kernel on the constraint data resident in the group's handle.  The rule of the last run is
     /// solve_tangent's (lam_rc).  The host form stages in buffers of the batch (under a mask the caller's outputs travel there first).  Waits for the
     /// groups' streams before it returns.
-    int solve_bounds(const double *lbq, const double *ubq, uint32_t nrhs, double *x, double *violation, uint8_t *valid, bool on_device)
+    /// with_cost (lexls_lsi_batch_solve_bounds_cost(_device)): besides, cost (nrhs x batch x nObj) = every objective's squared distance from bound set
+    /// c at x[c, i], from lsi_bounds_check_kernel<placement, true>; x may be NULL then.  Without it: exactly the launches of before.
+    int solve_bounds(const double *lbq, const double *ubq, uint32_t nrhs, double *x, double *violation, uint8_t *valid, bool on_device, bool with_cost = false,
+                     double *cost = NULL)
     {
-        const std::string who = on_device ? "lexls_lsi_batch_solve_bounds_device" : "lexls_lsi_batch_solve_bounds";
+        const std::string who = std::string("lexls_lsi_batch_solve_bounds") + (with_cost ? "_cost" : "") + (on_device ? "_device" : "");
         if (lam_rc < 0) throw Exception(who + ": no completed lexls_lsi_batch_run on this batch");
         if (lam_rc != LEXLS_OK)
         {
@@ -1177,8 +1194,9 @@ struct LsiFinal
         if (hipSetDevice(s.device) != hipSuccess) throw Exception(who + ": hipSetDevice failed");
         ensure_bounds_bufs(nrhs);
         const size_t total = s.total, in_bytes = 8 * (size_t)nrhs * s.batch * total, x_bytes = 8 * (size_t)nrhs * s.batch * s.nVar, v_bytes = 8 * (size_t)nrhs * s.batch;
+        const size_t c_bytes = 8 * (size_t)nrhs * s.batch * s.nObj;
         const double *d_lbq = lbq, *d_ubq = ubq;
-        double *d_x = x, *d_viol = violation;
+        double *d_x = x, *d_viol = violation, *d_cost = cost;
         uint8_t *d_valid = valid;
         if (!on_device)
         {
@@ -1192,12 +1210,21 @@ struct LsiFinal
                 st.room = nrhs;
             }
             if (!st.d_valid && hipMalloc((void **)&st.d_valid, s.batch) != hipSuccess) throw Exception(who + ": hipMalloc failed");
+            if (with_cost && nrhs > st.cost_room)
+            {
+                if (st.d_cost) (void)hipFree(st.d_cost);
+                st.d_cost = NULL, st.cost_room = 0;
+                if (hipMalloc((void **)&st.d_cost, c_bytes) != hipSuccess) throw Exception(who + ": hipMalloc failed");
+                st.cost_room = nrhs;
+            }
             bool ok = hipMemcpy(st.d_lb, lbq, in_bytes, hipMemcpyHostToDevice) == hipSuccess && hipMemcpy(st.d_ub, ubq, in_bytes, hipMemcpyHostToDevice) == hipSuccess;
-            if (ok && s.d_mask) ok = hipMemcpy(st.d_x, x, x_bytes, hipMemcpyHostToDevice) == hipSuccess; // a skipped instance keeps the caller's bits
+            if (ok && s.d_mask && x) ok = hipMemcpy(st.d_x, x, x_bytes, hipMemcpyHostToDevice) == hipSuccess; // a skipped instance keeps the caller's bits
+            if (ok && s.d_mask && with_cost) ok = hipMemcpy(st.d_cost, cost, c_bytes, hipMemcpyHostToDevice) == hipSuccess;
             if (ok && s.d_mask && violation) ok = hipMemcpy(st.d_viol, violation, v_bytes, hipMemcpyHostToDevice) == hipSuccess;
             if (ok && s.d_mask && valid) ok = hipMemcpy(st.d_valid, valid, s.batch, hipMemcpyHostToDevice) == hipSuccess;
             if (!ok) throw Exception(who + ": hipMemcpy failed (bounds)");
-            d_lbq = st.d_lb, d_ubq = st.d_ub, d_x = st.d_x, d_viol = violation ? st.d_viol : NULL, d_valid = valid ? st.d_valid : NULL;
+            d_lbq = st.d_lb, d_ubq = st.d_ub, d_x = x ? st.d_x : NULL, d_viol = violation ? st.d_viol : NULL, d_valid = valid ? st.d_valid : NULL;
+            d_cost = with_cost ? st.d_cost : NULL;
         }
         const lexls::BoundsCheckPlacement place = lexls::bounds_check_placement(s.nVar);
         const size_t lds                        = lexls::bounds_check_lds_bytes(s.nVar, place);
@@ -1230,22 +1257,31 @@ struct LsiFinal
             const double *x_lse    = any_active ? lb.d_bnd_x : (const double *)NULL;
             const uint32_t *counts = run_counts ? ctx.d_inst_dims : (const uint32_t *)NULL;
             uint8_t *flag          = d_valid ? d_valid + s.lo[g] : (uint8_t *)NULL;
-            if (place == lexls::BoundsCheckPlacement::lds)
+            if (with_cost && place == lexls::BoundsCheckPlacement::lds)
+                hipLaunchKernelGGL((lsi_bounds_check_kernel<true, true>), dim3(ctx.B, tiles), dim3(64), lds, ctx.stream, x_lse, d_lbq, d_ubq, lexls_internal_cdata(ctx.h), d_var, counts,
+                                   (uint32_t)RESIDENT_DIMS_STRIDE, lb.d_map, lb.d_meta, lb.d_shape, ctx.B, s.batch, s.lo[g], nrhs, s.nObj, (uint32_t)total, s.nVar, ctx.cap, s.per_data, d_x,
+                                   d_viol, flag, s.group_mask(g), d_cost);
+            else if (with_cost)
+                hipLaunchKernelGGL((lsi_bounds_check_kernel<false, true>), dim3(ctx.B, tiles), dim3(64), lds, ctx.stream, x_lse, d_lbq, d_ubq, lexls_internal_cdata(ctx.h), d_var, counts,
+                                   (uint32_t)RESIDENT_DIMS_STRIDE, lb.d_map, lb.d_meta, lb.d_shape, ctx.B, s.batch, s.lo[g], nrhs, s.nObj, (uint32_t)total, s.nVar, ctx.cap, s.per_data, d_x,
+                                   d_viol, flag, s.group_mask(g), d_cost);
+            else if (place == lexls::BoundsCheckPlacement::lds)
                 hipLaunchKernelGGL(lsi_bounds_check_kernel<true>, dim3(ctx.B, tiles), dim3(64), lds, ctx.stream, x_lse, d_lbq, d_ubq, lexls_internal_cdata(ctx.h), d_var, counts,
                                    (uint32_t)RESIDENT_DIMS_STRIDE, lb.d_map, lb.d_meta, lb.d_shape, ctx.B, s.batch, s.lo[g], nrhs, s.nObj, (uint32_t)total, s.nVar, ctx.cap, s.per_data, d_x,
-                                   d_viol, flag, s.group_mask(g));
+                                   d_viol, flag, s.group_mask(g), (double *)NULL);
             else
                 hipLaunchKernelGGL(lsi_bounds_check_kernel<false>, dim3(ctx.B, tiles), dim3(64), lds, ctx.stream, x_lse, d_lbq, d_ubq, lexls_internal_cdata(ctx.h), d_var, counts,
                                    (uint32_t)RESIDENT_DIMS_STRIDE, lb.d_map, lb.d_meta, lb.d_shape, ctx.B, s.batch, s.lo[g], nrhs, s.nObj, (uint32_t)total, s.nVar, ctx.cap, s.per_data, d_x,
-                                   d_viol, flag, s.group_mask(g));
+                                   d_viol, flag, s.group_mask(g), (double *)NULL);
             if (hipGetLastError() != hipSuccess) throw Exception("lsi_bounds_check_kernel launch failed");
         }
-        bounds_kernel = lexls::bounds_check_placement_name(place);
+        bounds_kernel = with_cost ? lexls::bounds_cost_placement_name(place) : lexls::bounds_check_placement_name(place);
         for (uint32_t g = 0; g < s.nGroups; g++)
             if (hipStreamSynchronize(s.grp[g]->stream) != hipSuccess) throw Exception(who + ": stream synchronisation failed");
         if (!on_device)
         {
-            bool ok = hipMemcpy(x, d_x, x_bytes, hipMemcpyDeviceToHost) == hipSuccess;
+            bool ok = !x || hipMemcpy(x, d_x, x_bytes, hipMemcpyDeviceToHost) == hipSuccess;
+            if (ok && with_cost) ok = hipMemcpy(cost, d_cost, c_bytes, hipMemcpyDeviceToHost) == hipSuccess;
             if (ok && violation) ok = hipMemcpy(violation, d_viol, v_bytes, hipMemcpyDeviceToHost) == hipSuccess;
             if (ok && valid) ok = hipMemcpy(valid, d_valid, s.batch, hipMemcpyDeviceToHost) == hipSuccess;
             if (!ok) throw Exception(who + ": hipMemcpy failed (results)");

@@ -482,6 +482,42 @@ class BatchedLexLSE:
                                                           address("fixed", fixed, lead + (self.batch, self.nVar)), K,
                                                           address("x", x, lead + (self.batch, self.nVar))))
 
+    # ---- residuals of new right-hand sides on the kept factor (every problem; undamped factors) ----------
+    def residual_rhs(self, rhs, fixed=None):
+        """lexls_lse_residual_rhs + lexls_lse_get_residual_rhs: rhs and fixed as for solve_rhs().  Returns (v, cost): v (K, batch, cap), per
+        right-hand side what residual() + get_v() give for the same matrices under that right-hand side and those fixed values (LOD row order,
+        zeros behind a problem's own rows), within the tolerance contract; cost (K, batch, nObj), the sum of squares of each level's rows of v
+        (exactly 0.0 for a level of full row rank).  Both lack the leading axis for a 2-D rhs.  Needs a kept, undamped factor only."""
+        rhs = np.ascontiguousarray(rhs, np.float64)
+        lead, K = _leading_axis(rhs.shape, 2)
+        single = K == 1 and not lead
+        if single:
+            rhs = rhs[None]
+        if K == 0 or rhs.shape[1:] != (self.batch, self.cap):
+            raise ValueError(f"rhs must have shape (K >= 1, {self.batch}, {self.cap}) or lack the leading axis, got {rhs.shape}")
+        if fixed is not None:
+            fixed = np.ascontiguousarray(fixed, np.float64).reshape((K, self.batch, self.nVar))
+        capi.check(capi.lib().lexls_lse_residual_rhs(self._h, _ptr(rhs, C.c_double), None if fixed is None else _ptr(fixed, C.c_double), K))
+        v, cost = np.zeros((K, self.batch, self.cap)), np.zeros((K, self.batch, self.nObj))
+        capi.check(capi.lib().lexls_lse_get_residual_rhs(self._h, _ptr(v, C.c_double), _ptr(cost, C.c_double)))
+        return (v[0], cost[0]) if single else (v, cost)
+
+    def residual_rhs_device(self, rhs, v=None, cost=None, x=None, fixed=None):
+        """lexls_lse_residual_rhs_device: rhs (K, batch, cap), fixed (K, batch, nVar; None: the handle's values), and the outputs v (K, batch, cap),
+        cost (K, batch, nObj), x (K, batch, nVar: solve_rhs_device()'s, bit for bit) — any of the three may be None, not all — float64 in device
+        memory, contiguous torch tensors; a single right-hand side may lack the leading axis in all of them.  Only enqueued in the handle's
+        stream (set_stream): the inputs have to be complete in stream order."""
+        if not hasattr(rhs, "data_ptr") or rhs.dim() not in (2, 3):
+            raise ValueError("residual_rhs_device: rhs must be a tensor of shape (K >= 1, batch, cap) or (batch, cap)")
+        lead, K = _leading_axis(rhs.shape, 2)
+        if K == 0:
+            raise ValueError("residual_rhs_device: K == 0")
+        address = partial(_device_address, "residual_rhs_device")
+        capi.check(capi.lib().lexls_lse_residual_rhs_device(self._h, address("rhs", rhs, lead + (self.batch, self.cap)),
+                                                             address("fixed", fixed, lead + (self.batch, self.nVar)), K,
+                                                             address("x", x, lead + (self.batch, self.nVar)), address("v", v, lead + (self.batch, self.cap)),
+                                                             address("cost", cost, lead + (self.batch, self.nObj))))
+
     def jacobian_device(self):
         """(dx_db (batch, nVar, cap), dx_dfixed (batch, nVar, nVar)) of the kept factor as torch tensors on the handle's device: the identity
         cotangents are built there and go through solve_adjoint_multi_device, so dx_db[b, i, r] = d x_i / d b_r (LOD row order) and

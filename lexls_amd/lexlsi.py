@@ -767,14 +767,16 @@ class LsiBatch:
         capi.check(capi.lib().lexls_lsi_batch_solve_tangent_device(self._h, d_in, K, d_out, d_flag))
         return dx, differentiable
 
-    def solve_bounds(self, lb, ub):
+    def solve_bounds(self, lb, ub, with_cost=False):
         """lexls_lsi_batch_solve_bounds: `lb`, `ub` (K, batch, total), K other bound sets per instance in the constraint order of `active` / `v`, or
         (batch, total) for one.  Returns (x, violation, valid): x (K, batch, nvar) — (batch, nvar) for a single set given without the leading
         axis —, the solution of every instance's final working set of the last run with its bounds replaced; violation (K, batch) / (batch,), the
         largest amount by which that x breaks a bound of the set, over all rows of all objectives; valid (batch,) uint8, 1 where the instance
         ended PROBLEM_SOLVED, else 0 with exact zeros in its rows of x and violation.  A small violation is necessary for the working set to
         remain the answer under the new bounds, not sufficient: the multipliers' signs are not re-examined.  Nothing is factorized again.
-        Raises after the runs solve_tangent() raises after."""
+        Raises after the runs solve_tangent() raises after.
+        with_cost=True (lexls_lsi_batch_solve_bounds_cost): returns (x, violation, valid, cost), cost (K, batch, nObj) / (batch, nObj) = per
+        objective the sum over its rows of max(lb - a.x, a.x - ub, 0)^2 at that x against that bound set: what lex_argmin() ranks."""
         lb, ub = np.ascontiguousarray(lb, np.float64), np.ascontiguousarray(ub, np.float64)
         single = lb.ndim == 2
         if single:
@@ -783,16 +785,23 @@ class LsiBatch:
             raise ValueError(f"solve_bounds: lb / ub have shapes {lb.shape} / {ub.shape}, (K >= 1, {self.batch}, {self.total}) expected for both")
         K = lb.shape[0]
         x, violation, valid = np.zeros((K, self.batch, self.nvar)), np.zeros((K, self.batch)), np.zeros(self.batch, np.uint8)
+        if with_cost:
+            cost = np.zeros((K, self.batch, len(self.dims)))
+            capi.check(capi.lib().lexls_lsi_batch_solve_bounds_cost(self._h, _p(lb, C.c_double), _p(ub, C.c_double), K, _p(x, C.c_double), _p(violation, C.c_double),
+                                                                    _p(cost, C.c_double), _p(valid, C.c_uint8)))
+            return (x[0], violation[0], valid, cost[0]) if single else (x, violation, valid, cost)
         capi.check(capi.lib().lexls_lsi_batch_solve_bounds(self._h, _p(lb, C.c_double), _p(ub, C.c_double), K, _p(x, C.c_double), _p(violation, C.c_double),
                                                            _p(valid, C.c_uint8)))
         return (x[0], violation[0], valid) if single else (x, violation, valid)
 
-    def solve_bounds_device(self, lb, ub, x=None, violation=None, valid=None):
+    def solve_bounds_device(self, lb, ub, x=None, violation=None, valid=None, cost=None):
         """lexls_lsi_batch_solve_bounds_device: solve_bounds() on torch tensors of the batch's device — `lb`, `ub` float64 (K, batch, total) or
         (batch, total), `x` float64 with the same leading axis and (batch, nvar), `violation` float64 of the leading axis and (batch,), `valid`
         uint8 (batch,), contiguous; an output that is not given is allocated (zeroed).  Returns (x, violation, valid).  Nothing of them passes
         through host memory.  Under an instance mask the rows and the flag of a skipped instance keep their bits: pass the tensors that hold
-        them.  The call waits for the device."""
+        them.  The call waits for the device.
+        cost= a float64 tensor of the leading axis and (batch, nObj), or True to have one allocated (lexls_lsi_batch_solve_bounds_cost_device):
+        returns (x, violation, valid, cost), cost as solve_bounds(with_cost=True) describes it."""
         import torch
         if not hasattr(lb, "dim") or lb.dim() not in (2, 3) or not hasattr(ub, "dim") or ub.dim() != lb.dim():
             raise ValueError("solve_bounds_device: lb and ub must be tensors of shape (K >= 1, batch, total) or (batch, total)")
@@ -812,13 +821,20 @@ class LsiBatch:
         d_x = self._device_array("x", x, torch.float64, lead + (self.batch, self.nvar), optional=False)
         d_viol = self._device_array("violation", violation, torch.float64, lead + (self.batch,), optional=False)
         d_valid = self._device_array("valid", valid, torch.uint8, (self.batch,), optional=False)
+        if cost is not None and cost is not False:
+            if cost is True:
+                cost = torch.zeros(lead + (self.batch, len(self.dims)), dtype=torch.float64, device=dev)
+            d_cost = self._device_array("cost", cost, torch.float64, lead + (self.batch, len(self.dims)), optional=False)
+            torch.cuda.synchronize(dev)
+            capi.check(capi.lib().lexls_lsi_batch_solve_bounds_cost_device(self._h, d_lb, d_ub, K, d_x, d_viol, d_cost, d_valid))
+            return x, violation, valid, cost
         torch.cuda.synchronize(dev)  # the bounds (and the zeroed outputs) are complete before the library's own streams read and write them
         capi.check(capi.lib().lexls_lsi_batch_solve_bounds_device(self._h, d_lb, d_ub, K, d_x, d_viol, d_valid))
         return x, violation, valid
 
     def last_consumer_kernel(self) -> str:
         """the kernel variant of the last solve_bounds() / solve_bounds_device() call (lexls_lsi_batch_last_consumer_kernel):
-        "lsi_bounds_check<lds>" or "lsi_bounds_check<hbm>"; "" before the first such call"""
+        "lsi_bounds_check<lds>" or "lsi_bounds_check<hbm>" ("lsi_bounds_cost<lds>" / "<hbm>" when the cost was asked for); "" before the first such call"""
         return capi.lib().lexls_lsi_batch_last_consumer_kernel(self._h).decode()
 
     def split_grad_data(self, row):
@@ -843,6 +859,31 @@ class LsiBatch:
         lam = self.lambda_array()
         cuts = np.cumsum(self.dims)[:-1]
         return [np.split(np.ascontiguousarray(m.T), cuts) for m in lam]
+
+
+def lex_argmin(cost, tol=0.0):
+    """Per instance the index of the lexicographically smallest of K candidates: `cost` (K, batch, nObj) as LsiBatch.solve_bounds(with_cost=True)
+    or BatchedLexLSE.residual_rhs() return it (numpy array or torch tensor), level 0 the most important.  Level by level, the candidates still in
+    the running are those within `tol` (absolute, the caller's choice) of the smallest cost among them at that level; the first of those left
+    after the last level wins.  Returns (batch,) int64 indices (numpy for numpy, torch for torch).  Plain array operations, no kernel."""
+    if hasattr(cost, "detach"):
+        import torch
+        if cost.dim() != 3 or cost.shape[0] == 0:
+            raise ValueError(f"lex_argmin: cost must have shape (K >= 1, batch, nObj), got {tuple(cost.shape)}")
+        alive = torch.ones(cost.shape[:2], dtype=torch.bool, device=cost.device)
+        inf = torch.full((), float("inf"), dtype=cost.dtype, device=cost.device)
+        for k in range(cost.shape[2]):
+            level = torch.where(alive, cost[:, :, k], inf)
+            alive = alive & (level <= level.min(dim=0).values + tol)
+        return alive.to(torch.uint8).argmax(dim=0)
+    cost = np.asarray(cost, float)
+    if cost.ndim != 3 or cost.shape[0] == 0:
+        raise ValueError(f"lex_argmin: cost must have shape (K >= 1, batch, nObj), got {cost.shape}")
+    alive = np.ones(cost.shape[:2], bool)
+    for k in range(cost.shape[2]):
+        level = np.where(alive, cost[:, :, k], np.inf)
+        alive &= level <= level.min(axis=0) + tol
+    return alive.argmax(axis=0).astype(np.int64)
 
 
 def lsi_batch_solve(nvar: int, problems, active_guess=None, x0=None, device: int = 0, regularization_factors=None, with_lambda: bool = False, **params):
